@@ -21,13 +21,18 @@ ITSELF, as a child `python -m torch.distributed.run ... bench.py <same arguments
 or touched a GPU, relays the one JSON line and exits with the child's status (launch_ranks below); with fewer HIP devices
 than ranks the ranks share device 0 over gloo (a rehearsal, said in the line).
 
-Exactly K steps are timed (W untimed warm-up launches first); `steady` repeats the measurement over a region of at
-least --min-ms (default 50 ms) and is reported beside the headline, never as `value`.  With --gpus N > 1 the same
-line also carries config 4 (`sharded_noto_all`: ONE font's glyphs split over the ranks, strong scaling), config 5
-(`synthetic_ranges`: rank r renders outlines [8192 r, 8192 (r + 1)) of the 65 536) and `in_library` (rank 0 alone
-drives all N devices through the C ABI's one-process form, vg_renderer_new_multi).  Rank 0 prints ONE JSON line.  The CPU
-baseline leg (rank 0, N=1 only) times the oracle — the C restatement of the reference algorithm,
-oracle/ — on the same tessellated batch on the host cores; the oracle is never on the measured path.
+Exactly K steps are timed (W untimed warm-up launches first, after an untimed region of at least --min-ms, default
+50 ms, that brings the GPU to its sustained clocks).  Rank 0 prints ONE JSON line.  `--dump-outputs DIR` writes what
+the last timed step computed (dump_outputs below).
+
+A plain run measures the headline and nothing else.  `--full` adds the side measurements, reported beside the headline
+and never as `value`: `steady` (the timed form of the --min-ms region), `roofline.prep_ms`, `two_in_flight`, the CPU
+baseline, `e2e` and the other workloads (`configs`).  With --gpus N > 1 it adds config 4 (`sharded_noto_all`: ONE
+font's glyphs split over the ranks, strong scaling), config 5 (`synthetic_ranges`: rank r renders outlines
+[8192 r, 8192 (r + 1)) of the 65 536) and `in_library` (rank 0 alone drives all N devices through the C ABI's
+one-process form, vg_renderer_new_multi).  The CPU baseline leg (rank 0, N=1 only) times the oracle — the C
+restatement of the reference algorithm, oracle/ — on the same tessellated batch on the host cores; the oracle is
+never on the measured path.
 """
 import argparse
 import hashlib
@@ -38,6 +43,8 @@ import platform
 import sys
 import time
 from pathlib import Path
+
+import numpy as np
 
 ROOT = Path(__file__).resolve().parent
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
@@ -129,6 +136,26 @@ def steps_for(ctx, db, warmup, min_ms):
     ctx.sync()
     est = db.time(10) / 10  # ms per launch (untimed probe)
     return int(1.15 * min_ms / max(est, 1e-6)) + 1
+
+
+DUMP_LIMIT = 64_000_000   # bytes of .npy files written by --dump-outputs
+
+
+def dump_outputs(out_dir, batch, got):
+    """What a step hands its caller: the SDF bytes of every glyph of the batch, in batch order (glyph g at
+    batch.out_off[g]), as DIR/sdf.npy in float32.  Beyond DUMP_LIMIT a fixed seeded sample of whole glyphs is written
+    instead, with their batch indices in DIR/sdf_glyph_index.npy (float64)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    if got.size * 4 + 4096 <= DUMP_LIMIT:
+        np.save(d / "sdf.npy", got.astype(np.float32))
+        return
+    off = batch.out_off.astype(np.int64)
+    order = np.random.default_rng(0x5DF61F95).permutation(batch.n_glyphs)
+    cost = np.cumsum(np.diff(off)[order] * 4 + 8)   # float32 pixels + one float64 index per glyph
+    pick = np.sort(order[cost + 4096 <= DUMP_LIMIT])
+    np.save(d / "sdf.npy", np.concatenate([got[off[g]:off[g + 1]] for g in pick]).astype(np.float32))
+    np.save(d / "sdf_glyph_index.npy", pick.astype(np.float64))
 
 
 def in_library(n):
@@ -253,6 +280,10 @@ def launch_ranks(n, argv):
             a[i + 1] = "1"
         else:
             a = [x if not x.startswith("--gpus=") else "--gpus=1" for x in a]
+        if r > 0 and "--dump-outputs" in a:     # every process is a rank 0 here: the first one writes the outputs
+            i = a.index("--dump-outputs")
+            del a[i:i + 2]
+        a = [x for x in a if r == 0 or not x.startswith("--dump-outputs=")]
         procs.append(subprocess.Popen([sys.executable, me] + a + ["--no-cpu-baseline", "--no-e2e", "--no-configs", "--no-two-in-flight"],
                                       env=e, stdout=subprocess.PIPE, text=True))
     lines = []
@@ -283,7 +314,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--min-ms", type=float, default=50.0, help="minimum length of the timed region")
+    ap.add_argument("--min-ms", type=float, default=50.0, help="minimum length of the warm-up region (and of `steady` with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (steady, prep, two in flight, CPU baseline, e2e, other workloads, "
+                         "the multi-GPU configs); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the SDF bytes of the last timed step to DIR/*.npy (float32, at most 64 MB)")
     ap.add_argument("--workload", default="noto_regular", choices=sorted(WORKLOADS))
     ap.add_argument("--sharded", action="store_true", help="split the font's glyphs over the ranks (strong scaling)")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 = default)")
@@ -379,7 +415,7 @@ def main():
     # what a step leaves out: making the batch resident (one H2D copy from page-locked staging + sdf_chunk_boxes, once
     # per batch) and fetching the bitmaps (one D2H copy) — wall clock around the synchronous C-ABI calls, best of 5
     prep = None
-    if world == 1:
+    if world == 1 and args.full:
         up, down = [], []
         for _ in range(5):
             t1 = time.perf_counter()
@@ -429,7 +465,7 @@ def main():
     # The long side measurement runs FIRST: a region of >= --min-ms (every rank times the same number of steps).  It also
     # brings the GPU to its sustained clocks — the first launches after an idle period run ~8 % slower (measured: 85.9 us
     # per launch in a cold 20-step region against 79.0 us sustained) — so the headline's W + K launches below measure
-    # the kernel the way a renderer that is busy rendering meets it.
+    # the kernel the way a renderer that is busy rendering meets it.  A plain run runs the same region and ignores its time.
     k_long = steps_for(ctx, db, args.warmup, args.min_ms)
     if dist is not None:
         kk = torch.tensor([k_long], dtype=torch.int64, device=coll_dev)
@@ -442,10 +478,12 @@ def main():
     counters = all_sum([256, st["n_glyphs"], st["n_pixels"]])   # blocks, glyphs, pixels per step; the only RCCL payload: 24 bytes
     if dist is not None and args.sharded:
         counters[0] = 256                               # one font's blocks, whoever assembles them
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hb.batch, db.download())   # the output arena as the last timed launch left it
 
     # ---- N > 1: configs 4 and 5 of BASELINE.json, measured by every rank, reported by rank 0 in the same line ----
     multi = {}
-    if world > 1 and not args.sharded and not synthetic and not args.no_configs:
+    if world > 1 and not args.sharded and not synthetic and not args.no_configs and args.full:
         # config 4: Noto Sans all languages, ONE font's glyphs sharded over the ranks (strong scaling)
         d4, p4 = workload_files("noto_all")
         m4 = vg.FontManager(True)
@@ -490,7 +528,7 @@ def main():
             "hbm_roofline_frac_all_gpus": c5[2] * k5 / el5 * 1e-9 / (HBM_PEAK_GBS * world)}
         db5.free()
         del b5
-    if world > 1 and not args.sharded and not synthetic and not args.no_configs:
+    if world > 1 and not args.sharded and not synthetic and not args.no_configs and args.full:
         # in-library form: ONE process drives all N devices through vg_renderer_new_multi.  It runs as a CHILD of rank 0
         # (this script with --in-library N: its own HIP / RCCL state, and a time limit — a collective that hangs there must
         # not take the headline with it) while the other ranks wait on the CPU (a gloo group, so that no collective kernel
@@ -595,17 +633,19 @@ def main():
                     "rate a brute-force evaluation would need",
         },
         "host_stage_s": host_s,
-        "steady": {"steps": k_long, "ms_per_step": steady_elapsed / k_long * 1e3, "glyphs_per_s": counters[1] * k_long / steady_elapsed,
-                   "kernel_ms_avg": steady_ms / k_long,
-                   "note": f"the same measurement over a region of >= {args.min_ms:g} ms, run BEFORE the headline's warm-up + K steps (it brings "
-                           "the GPU to its sustained clocks; reported beside the headline, never as `value`)"},
     }
+    if args.full:
+        out["steady"] = {
+            "steps": k_long, "ms_per_step": steady_elapsed / k_long * 1e3, "glyphs_per_s": counters[1] * k_long / steady_elapsed,
+            "kernel_ms_avg": steady_ms / k_long,
+            "note": f"the same measurement over a region of >= {args.min_ms:g} ms, run BEFORE the headline's warm-up + K steps (it brings "
+                    "the GPU to its sustained clocks; reported beside the headline, never as `value`)"}
     out.update(multi)
     if world > 1 and not args.sharded:
         out["scaling_note"] = ("weak, replicas: every rank renders its own copy of the config-2 batch, no data-path collective; `value` = "
                                "N x glyphs of one batch x steps / max-over-ranks time.  The strong-scaling figure of BASELINE.json "
                                "configs[3] (ONE font over N devices) is `strong_scaling_config4` (one rank per GPU, resident raster of each "
-                               "rank's glyph shard) and `in_library` (ONE process, N device lanes, fonts -> PBF bytes)")
+                               "rank's glyph shard) and `in_library` (ONE process, N device lanes, fonts -> PBF bytes), both with --full")
         if "sharded_noto_all" in multi:
             m4 = multi["sharded_noto_all"]
             out["strong_scaling_config4"] = {k: m4[k] for k in ("glyphs_per_s", "mpixel_sdf_per_s", "ms_per_step", "steps",
@@ -622,7 +662,7 @@ def main():
     # ---- two batches in flight (reported beside the headline, never as `value`): the same launches alternating
     # between two contexts = two streams, so the tail of one launch overlaps the ramp of the next — what a caller
     # with more than one batch to render gets (FontManager does this with its two lanes)
-    if world == 1 and not args.sharded and not args.no_two_in_flight:
+    if world == 1 and not args.sharded and not args.no_two_in_flight and args.full:
         c2 = vg.SdfContext(local_rank)
         c2.set_variant(args.variant)
         d2 = c2.upload(hb.batch)
@@ -642,7 +682,7 @@ def main():
         d2.free(); c2.close()
 
     # ---- CPU baseline: oracle raster on the same tessellated batch, host cores ---------
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and not args.no_cpu_baseline and args.full:
         from oracle import oracle as O
         # thread counts tried: the CPU affinity of the process (what the box shows: 256 on the one-GPU boxes) and the CPUs the
         # container's cgroup lets it use at once (16 there) — the faster one is reported, with the count it used
@@ -749,7 +789,7 @@ def main():
                 "candidate_rule": best[2]}
 
     r = None
-    if world == 1 and not args.no_e2e:
+    if world == 1 and not args.no_e2e and args.full:
         r = vg.Renderer.new_precise(local_rank)
         out["e2e"] = {"note": "parse -> outline -> (flatten) -> H2D -> kernels -> D2H -> PBF encode, PCIe inclusive, "
                               "best of 15 warm runs; device_front_end = flattening/closing/scale/bbox on the GPU; sustained = the same run "
@@ -785,7 +825,7 @@ def main():
             out["e2e"]["gpu_over_cpu"] = out["e2e"]["gpu_path_glyphs_per_s"] / c["glyphs_per_s"]
 
     # ---- the other font workloads, same measurements, in the same line ---------------------
-    if world == 1 and not args.no_configs and not args.sharded:
+    if world == 1 and not args.no_configs and not args.sharded and args.full:
         out["configs"] = []
         for wl in ("fira", "noto_regular", "noto_all"):
             if wl == args.workload:

@@ -6,13 +6,13 @@ REPO=${GRAFT_REPO_ROOT:-$PWD}
 cd "$REPO"
 OUT=gpurun_out/${TAG}_report
 mkdir -p $OUT
-timeout -k 10 300 python3 bench.py > $OUT/bench_noto_regular.json 2> $OUT/bench.err
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_noto_regular_k20.json 2>> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full > $OUT/bench_noto_regular.json 2> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_noto_regular_k20.json 2>> $OUT/bench.err
 for w in fira noto_all synthetic; do
-  timeout -k 10 300 python3 bench.py --workload $w --no-configs > $OUT/bench_$w.json 2>> $OUT/bench.err
+  timeout -k 10 300 python3 bench.py --full --workload $w --no-configs > $OUT/bench_$w.json 2>> $OUT/bench.err
 done
 # the driver's own command for N > 1 (no launcher: bench.py starts its ranks itself); on a one-GPU box the ranks share device 0
-VG_SHARE_GPU=1 timeout -k 10 400 python3 bench.py --gpus 2 --steps 20 --warmup 5 2>> $OUT/bench.err | tail -n 1 > $OUT/bench_gpus2_self_launched_one_gpu_rehearsal.json
+VG_SHARE_GPU=1 timeout -k 10 400 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 2>> $OUT/bench.err | tail -n 1 > $OUT/bench_gpus2_self_launched_one_gpu_rehearsal.json
 tools/ubench/clock_probe > $OUT/clock_probe.txt 2>&1
 for w in noto_regular noto_all many; do timeout -k 10 120 python3 tools/e2e_sweep.py $w 16 32; done > $OUT/e2e_sweep.txt 2>&1
 VGSDF_LIB=versatiles-glyphs-rs_amd/build/dev/libvgsdf.so timeout -k 10 100 python3 tools/kexp.py noto_regular 58 --rep 1 > $OUT/stamps.txt 2>&1
