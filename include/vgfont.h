@@ -48,6 +48,8 @@ typedef struct {
 	uint64_t blocks, glyphs, rasters, pixels, segments, pbf_bytes;
 	uint64_t glyf_groups;    /* submissions whose glyphs the device decoded from their `glyf` arrays */
 	uint64_t glyf_fallbacks; /* of which the device refused (a malformed entry) and the host's reader recorded again */
+	uint64_t fe_groups;           /* groups of the dispatcher that held glyphs (one device submission each) */
+	uint64_t fe_max_group_glyphs; /* glyphs of the largest of those groups */
 } vg_timings;
 
 /* Writer sink (src/writer/mod.rs:10-19): is_dir=1 for write_directory. Return 0, or

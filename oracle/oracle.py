@@ -165,14 +165,14 @@ class Font:
         return info, bm
 
 
-def build_rings(cmds):
-    """RingBuilder over [(kind,x1,y1,x2,y2,x,y)] -> list of (n,2) point arrays (font units)."""
+def build_rings(cmds, cap: int = 1 << 16, max_rings: int = 4096):
+    """RingBuilder over [(kind,x1,y1,x2,y2,x,y)] -> list of (n,2) point arrays (font units).
+    cap / max_rings: room for the points / rings of the whole stream (a stream beyond them fails)."""
     arr = (Cmd * max(len(cmds), 1))()
     for i, c in enumerate(cmds):
         arr[i] = Cmd(*c)
-    cap = 1 << 16
     pts = np.zeros((cap, 2), dtype=np.float64)
-    offs = np.zeros(4096, dtype=np.int32)
+    offs = np.zeros(max_rings, dtype=np.int32)
     npts = C.c_int32(0)
     n = lib().vgo_build_rings(arr, len(cmds), _f64p(pts), cap, offs.ctypes.data_as(C.POINTER(C.c_int32)),
                               len(offs), C.byref(npts))

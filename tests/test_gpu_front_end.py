@@ -359,6 +359,29 @@ def _varint_len(v):
     return n
 
 
+def restate_pbf_layout(rects, pre, fix):
+    """vgsdf_outlines_packed::pbf_pre / pbf_fix restated in Python: the glyphs laid out as the `glyphs` entries of a fontstack
+    message (glyph.rs:10-41, fontstack.rs:9-25), pbf_pre[g] bytes before entry g -> (position of every glyph's bitmap, size
+    of the arena)"""
+    want_at, pos = [], 0
+    for g in range(len(rects)):
+        r = rects[g]
+        has = bool(r["has_raster"])
+        px = int(r["w"]) * int(r["h"]) if has else 0
+        idlen, advlen = int(fix[g]) & 15, int(fix[g]) >> 4
+        msg = idlen + advlen
+        if has:
+            left, top = int(r["x0"]) + 3, int(r["y0"]) + int(r["h"]) - 27
+            zz = lambda v: (v << 1) ^ (v >> 31)  # noqa: E731
+            msg += 1 + _varint_len(px) + px + 4 + _varint_len(int(r["w"]) - 6) + _varint_len(int(r["h"]) - 6) + \
+                _varint_len(zz(left) & 0xFFFFFFFF) + _varint_len(zz(top) & 0xFFFFFFFF)
+        else:
+            msg += 8
+        want_at.append(pos + int(pre[g]) + 1 + _varint_len(msg) + idlen + ((1 + _varint_len(px)) if has else 0))
+        pos += int(pre[g]) + 1 + _varint_len(msg) + msg
+    return want_at, pos
+
+
 def test_in_place_pbf_layout_at_the_c_abi(vg, fira_oracle):
     """vgsdf_outlines_packed::pbf_pre / pbf_fix: the device lays the glyphs out as the `glyphs` entries of a fontstack
     message (glyph.rs:10-41, fontstack.rs:9-25) and the raster stores every bitmap where the finished file has it.  Checked
@@ -382,26 +405,15 @@ def test_in_place_pbf_layout_at_the_c_abi(vg, fira_oracle):
         if arena is None:
             arena = c.outlines_render()
         at = c.outlines_pbf_positions()
-        pos, poff = 0, 0
+        want_at, pos = restate_pbf_layout(rects, pre, fix)
+        poff = 0
         for g in range(n):
             r = rects[g]
-            has = bool(r["has_raster"])
-            px = int(r["w"]) * int(r["h"]) if has else 0
-            idlen, advlen = int(fix[g]) & 15, int(fix[g]) >> 4
-            msg = idlen + advlen
-            if has:
-                left, top = int(r["x0"]) + 3, int(r["y0"]) + int(r["h"]) - 27
-                zz = lambda v: (v << 1) ^ (v >> 31)  # noqa: E731
-                msg += 1 + _varint_len(px) + px + 4 + _varint_len(int(r["w"]) - 6) + _varint_len(int(r["h"]) - 6) + \
-                    _varint_len(zz(left) & 0xFFFFFFFF) + _varint_len(zz(top) & 0xFFFFFFFF)
-            else:
-                msg += 8
-            want_at = pos + int(pre[g]) + 1 + _varint_len(msg) + idlen + ((1 + _varint_len(px)) if has else 0)
-            assert int(at[g]) == want_at, g
-            if has:
-                assert arena[want_at:want_at + px].tobytes() == packed[poff:poff + px].tobytes(), g
+            px = int(r["w"]) * int(r["h"]) if r["has_raster"] else 0
+            assert int(at[g]) == want_at[g], g
+            if r["has_raster"]:
+                assert arena[want_at[g]:want_at[g] + px].tobytes() == packed[poff:poff + px].tobytes(), g
                 poff += px
-            pos += int(pre[g]) + 1 + _varint_len(msg) + msg
         assert ob2 == pos and poff == ob
     # between submit and wait the front-end's results are available while the raster is still running (vgsdf_outlines_peek)
     c.outlines_submit_packed(cmd_off, dat_off, kinds, coords, scale, shift, 1 << 20, pbf_pre=pre, pbf_fix=fix)

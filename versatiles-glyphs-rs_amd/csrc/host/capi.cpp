@@ -441,7 +441,8 @@ int vg_manager_timings(const vg_manager *m, vg_timings *out)
 {
 	const vg::RenderTimings &t = m->m.last_timings();
 	*out = vg_timings{t.tessellate_s, t.pack_s, t.device_s, t.encode_s, t.write_s, t.total_s, t.blocks,
-	                  t.glyphs,       t.rasters,  t.pixels,   t.segments, t.pbf_bytes,  t.glyf_groups, t.glyf_fallbacks};
+	                  t.glyphs,       t.rasters,  t.pixels,   t.segments, t.pbf_bytes,  t.glyf_groups, t.glyf_fallbacks,
+	                  t.fe_groups,    t.fe_max_group_glyphs};
 	return 0;
 }
 long vg_manager_render_block(vg_manager *m, vg_renderer *r, const char *font_id, uint32_t start, uint8_t *out,

@@ -1229,6 +1229,8 @@ void FontManager::render_tasks_multi(Writer &writer, const Renderer &renderer, i
 		timings_.segments += ct.segments;
 		timings_.glyf_groups += ct.glyf_groups;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
+		timings_.fe_groups += ct.fe_groups;
+		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
 	}
 	renderer.reduce_counters(reduced_);
 	if (std::memcmp(reduced_, want, sizeof want) != 0)
@@ -1330,6 +1332,8 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		timings_.segments += ct.segments;
 		timings_.glyf_groups += ct.glyf_groups;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
+		timings_.fe_groups += ct.fe_groups;
+		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
 	}
 	renderer.reduce_counters(reduced_);
 	if (std::memcmp(reduced_, want, sizeof want) != 0)
@@ -1836,6 +1840,8 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 		mark("submit >", k);
 		const double t = now_s();
 		if (G.n_jobs) {
+			timings_.fe_groups++;
+			timings_.fe_max_group_glyphs = std::max<uint64_t>(timings_.fe_max_group_glyphs, G.n_jobs);
 			if (G.m.glyf) {
 				renderer.submit_outlines((int)(k & 1), G.m.view_glyf(), G.out);
 				timings_.glyf_groups++;
@@ -2056,8 +2062,14 @@ void FontManager::run_tasks(std::vector<Todo> &tasks, Writer &writer, const Rend
 		timings_.write_s += now_s() - t3;
 
 		timings_.blocks += nb;
+		uint64_t group_glyphs = 0;
 		for (const Slice &s : slices)
-			timings_.glyphs += s.job1 - s.job0;
+			group_glyphs += s.job1 - s.job0;
+		timings_.glyphs += group_glyphs;
+		if (group_glyphs) {
+			timings_.fe_groups++;
+			timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, group_glyphs);
+		}
 		timings_.rasters += packed_.n_raster;
 		timings_.pixels += n_pixels;
 		timings_.segments += packed_.n_seg;

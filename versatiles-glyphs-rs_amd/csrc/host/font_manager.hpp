@@ -145,6 +145,7 @@ struct RenderTimings {
 	double tessellate_s = 0, pack_s = 0, device_s = 0, encode_s = 0, write_s = 0, total_s = 0;
 	uint64_t blocks = 0, glyphs = 0, rasters = 0, pixels = 0, segments = 0, pbf_bytes = 0;
 	uint64_t glyf_groups = 0, glyf_fallbacks = 0; // device front-end: groups decoded from `glyf` arrays / re-recorded on the host
+	uint64_t fe_groups = 0, fe_max_group_glyphs = 0; // the dispatcher's groups that held glyphs (one submission each), the largest's glyphs
 };
 
 class FontManager {

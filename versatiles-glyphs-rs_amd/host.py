@@ -27,7 +27,8 @@ class PbfGlyph(C.Structure):
 
 class Timings(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("tessellate_s", "pack_s", "device_s", "encode_s", "write_s", "total_s")] + \
-               [(k, C.c_uint64) for k in ("blocks", "glyphs", "rasters", "pixels", "segments", "pbf_bytes", "glyf_groups", "glyf_fallbacks")]
+               [(k, C.c_uint64) for k in ("blocks", "glyphs", "rasters", "pixels", "segments", "pbf_bytes", "glyf_groups", "glyf_fallbacks",
+                                                 "fe_groups", "fe_max_group_glyphs")]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
