@@ -1,6 +1,7 @@
 """GPU: the raster kernel (sdf_tiles_span, csrc/sdf_span_kernel.inc) and the two planners that feed it (build_descs_and_tiles
-in vgsdf_device.cpp on the host, classify in outline_plan in outline_kernels.hip on the device) at the regimes set by a glyph's
-width and segment count, against the oracle (BRUTE and PRECISE) under both product variants (0: spans, 1: brute force).
+in work_list.cpp on the host, outline_plan in outline_kernels.hip on the device, both on the policy of csrc/work_plan.h) at the
+regimes set by a glyph's width and segment count, against the oracle (BRUTE and PRECISE) under both product variants (0: spans,
+1: brute force).
 
 The routing is restated below (fits, the choice of the span length T from span_max and span_budget, the brute-force class, the
 span count per glyph).  Every host-plan case carries a witness: vgsdf_batch_stats' n_tiles under variant 0 equals the restated

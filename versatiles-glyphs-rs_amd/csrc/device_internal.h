@@ -1,0 +1,123 @@
+// device_internal.h — what the translation units of the C-ABI layer (include/vgsdf.h) share: the context, the resident
+// batch, grow-only buffers and the error macro.
+//   vgsdf_device.cpp        contexts, resident batches, transfers and launches
+//   work_list.cpp           the host's planner of a resident batch's work list
+//   outline_front_end.cpp   outline commands in, rects and bitmaps out
+//   run_counters.cpp        run counters and their RCCL reduction
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <string>
+
+#include "../../include/vgsdf.h"
+#include "sdf_kernels.h"
+
+// grow-only device / pinned-host buffer.  ensure() frees the old block at once: the caller sees to it that nothing in
+// flight still uses it
+struct DevBuf {
+	void *p = nullptr;
+	size_t cap = 0;
+	bool host = false;
+	hipError_t ensure(size_t bytes)
+	{
+		if (bytes <= cap)
+			return hipSuccess;
+		release();
+		const size_t want = bytes + bytes / 4 + 256;
+		hipError_t e = host ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
+		if (e != hipSuccess) {
+			p = nullptr;
+			return e;
+		}
+		cap = want;
+		return hipSuccess;
+	}
+	void release()
+	{
+		if (p)
+			(void)(host ? hipHostFree(p) : hipFree(p));
+		p = nullptr;
+		cap = 0;
+	}
+};
+
+struct vgsdf_ctx {
+	int device = 0;
+	hipStream_t stream = nullptr;
+	hipStream_t copy_stream = nullptr;                 // the front-end's read-back, beside the kernels that follow the plan
+	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	hipEvent_t ev_plan = nullptr, ev_rects = nullptr;   // plan done (kernel stream) / rects on the host (copy stream)
+	int variant = 0;
+	std::string err;
+	// arena and pinned staging of vgsdf_render_batch: no hipMalloc / hipHostMalloc in steady state
+	DevBuf d_scratch, h_scratch{nullptr, 0, true};
+	struct FrontEnd *fe = nullptr; // device outline front-end state (lazy; outline_front_end.cpp)
+	// run counters {blocks, glyphs, pixels} of the work this context did (vgsdf_add_counters), summed over the
+	// contexts of a run by vgsdf_reduce_counters; d_counters: 24 bytes on the device for the collective
+	uint64_t counters[3] = {0, 0, 0};
+	uint64_t *d_counters = nullptr;
+	void *comm = nullptr; // ncclComm_t of the communicator this context last reduced in (owned by run_counters.cpp's cache)
+	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
+};
+
+struct vgsdf_dbatch {
+	vgsdf_stats stats{};
+	// one device arena: [descs | tiles | sx | sy | ex | ey | out]
+	void *d_arena = nullptr;
+	size_t arena_bytes = 0, input_bytes = 0;
+	void *h_stage = nullptr; // pinned staging of the input part
+	vgsdf::GlyphDesc *d_glyphs = nullptr;
+	uint2 *d_tiles = nullptr;
+	void *d_boxes = nullptr; // chunk boxes (span kernel); NULL: none
+	double *d_sx = nullptr, *d_sy = nullptr, *d_ex = nullptr, *d_ey = nullptr;
+	uint32_t seg_stride = 1; // 1: four SoA arrays (C ABI batches); 4: 32-byte records (device front-end)
+	uint8_t *d_out = nullptr;
+	size_t out_bytes = 0;
+	// work list = [main kernel | brute force]
+	uint32_t n_main = 0; // entries [0, n_main): main kernel; the rest: brute-force tiles
+	int tile_order = 1;
+	bool span_list = false; // main-class entries are (glyph, first pixel | tile count): sdf_tiles_span only
+	bool borrowed = false; // arena + staging belong to the context (vgsdf_render_batch)
+};
+
+// kernel id understood by vgsdf_launch_tiles.  Variant 0 (default) = kernel 50: bounded groups over spans of tiles;
+// misfits: brute force.  1: everything brute.  Other ids exist only in development builds (vgsdf_set_variant rejects
+// them otherwise): earlier generations and timing-only ablations, see vgsdf_launch_tiles.
+inline int kernel_id(int variant) { return variant == 0 ? 50 : (variant == 13 ? 10 : variant); }
+// the variant's main-class entries are spans: (glyph, first pixel | tile count)
+inline bool uses_span_list(int variant) { return variant == 0 || (variant >= 50 && variant <= 69); }
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+inline double fe_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// (functions shared between the translation units stay out of the library's exported symbols)
+#define VGSDF_INTERNAL __attribute__((visibility("hidden")))
+
+// true when p is page-locked host memory known to HIP (hipHostMalloc / vgsdf_host_alloc):
+// such arrays are DMA'd straight from/to the caller without a staging copy
+VGSDF_INTERNAL bool is_pinned(const void *p, size_t bytes);
+// The address a KERNEL may use for page-locked host memory: the mapping the runtime reports for it (equal to the host
+// address for hipHostMalloc memory on this platform, but not guaranteed for memory the caller registered itself with
+// hipHostRegister).  NULL when p is not page-locked host memory known to HIP, or has no device mapping.
+VGSDF_INTERNAL void *pinned_device_ptr(void *p, size_t bytes);
+
+// Fills the glyph descriptors and the tile list (routing + order) of a batch, and b->n_main, b->stats.n_tiles,
+// b->span_list, b->tile_order.  `ht` must hold one entry per 256-pixel tile of the batch.  (work_list.cpp)
+VGSDF_INTERNAL void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, uint2 *ht, vgsdf_dbatch *b, bool span);
+
+// frees the front-end state of a context that is being destroyed (outline_front_end.cpp)
+VGSDF_INTERNAL void fe_destroy(struct FrontEnd *fe);
+
+// a failed HIP call ends the entry point: `what` (the text of the call, behind the caller's prefix if it has one) goes
+// into the context's error string
+#define HIP_TRY_AS(ctx, what, expr)                                                            \
+	do {                                                                                       \
+		hipError_t e__ = (expr);                                                               \
+		if (e__ != hipSuccess) {                                                               \
+			(ctx)->err = std::string(what ": ") + hipGetErrorString(e__);                      \
+			return e__ == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;                     \
+		}                                                                                      \
+	} while (0)
+#define HIP_TRY(ctx, expr) HIP_TRY_AS(ctx, #expr, expr)

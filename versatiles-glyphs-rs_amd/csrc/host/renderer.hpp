@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../../include/vgsdf.h"
+#include "../upload_layout.h"
 #include "geometry.hpp"
 #include "pbf.hpp"
 #include "ring_builder.hpp"
@@ -228,7 +229,8 @@ struct GlyfPartsBatch {
 
 // The merged batch handed to the device, in the compact upload form (vgsdf_outlines_packed: one kind byte per
 // command plus the coordinates its kind carries).  All arrays live back to back in ONE page-locked block, in the
-// order vgsdf.h names for a single-copy upload: scale | shift_x | cmd_off | dat_off | (pad to 8) | coords | kinds.
+// order vgsdf.h names for a single-copy upload: scale | shift_x | cmd_off | dat_off | (pad to 8) | coords | kinds
+// (the offsets: ../upload_layout.h, which the device layer recognises the block by).
 struct MergedOutlines {
 	std::vector<GlyphJob> jobs;
 	HostBuffer<uint8_t> blob{true};
@@ -250,22 +252,19 @@ struct MergedOutlines {
 		n_parts = parts_n;
 		n_glyf_bytes = bytes_n; // (a multiple of 4: every part's bytes are padded)
 		glyf = true;
-		const size_t n = jobs_n;
-		const size_t o_shift = 8 * n, o_cmd = 16 * n;
-		const size_t o_parts = (o_cmd + 4 * (n + 1) + 7) & ~(size_t)7, o_bytes = o_parts + sizeof(vgsdf_glyf_part) * (size_t)parts_n;
-		const size_t o_pre = o_bytes + bytes_n, o_fix = o_pre + 4 * n;
-		blob.ensure((with_pbf ? o_fix + n : o_pre) + 16);
+		const vgsdf::GlyfBlockLayout at(jobs_n, parts_n, bytes_n, with_pbf);
+		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
-		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + o_pre) : nullptr;
-		pbf_fix = with_pbf ? b + o_fix : nullptr;
-		scale = reinterpret_cast<double *>(b);
-		shift_x = reinterpret_cast<double *>(b + o_shift);
-		cmd_off = reinterpret_cast<uint32_t *>(b + o_cmd);
+		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
+		pbf_fix = with_pbf ? b + at.pbf_fix : nullptr;
+		scale = reinterpret_cast<double *>(b + at.scale);
+		shift_x = reinterpret_cast<double *>(b + at.shift_x);
+		cmd_off = reinterpret_cast<uint32_t *>(b + at.cmd_off);
 		dat_off = nullptr;
 		coords = nullptr;
 		kinds = nullptr;
-		parts = reinterpret_cast<vgsdf_glyf_part *>(b + o_parts);
-		glyf_bytes = b + o_bytes;
+		parts = reinterpret_cast<vgsdf_glyf_part *>(b + at.parts);
+		glyf_bytes = b + at.glyf_bytes;
 	}
 	vgsdf_outlines_glyf view_glyf() const
 	{
@@ -286,20 +285,17 @@ struct MergedOutlines {
 	{
 		n_jobs = jobs_n;
 		glyf = false;
-		const size_t n = jobs_n;
-		const size_t o_shift = 8 * n, o_cmd = 16 * n, o_dat = o_cmd + 4 * (n + 1);
-		const size_t o_coords = (o_dat + 4 * (n + 1) + 7) & ~(size_t)7, o_kinds = o_coords + 4 * (size_t)n_floats;
-		const size_t o_pre = (o_kinds + n_cmds + 3) & ~(size_t)3, o_fix = o_pre + 4 * n;
-		blob.ensure((with_pbf ? o_fix + n : o_kinds + n_cmds) + 16);
+		const vgsdf::PackedBlockLayout at(jobs_n, n_cmds, n_floats, with_pbf);
+		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
-		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + o_pre) : nullptr;
-		pbf_fix = with_pbf ? b + o_fix : nullptr;
-		scale = reinterpret_cast<double *>(b);
-		shift_x = reinterpret_cast<double *>(b + o_shift);
-		cmd_off = reinterpret_cast<uint32_t *>(b + o_cmd);
-		dat_off = reinterpret_cast<uint32_t *>(b + o_dat);
-		coords = reinterpret_cast<float *>(b + o_coords);
-		kinds = b + o_kinds;
+		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
+		pbf_fix = with_pbf ? b + at.pbf_fix : nullptr;
+		scale = reinterpret_cast<double *>(b + at.scale);
+		shift_x = reinterpret_cast<double *>(b + at.shift_x);
+		cmd_off = reinterpret_cast<uint32_t *>(b + at.cmd_off);
+		dat_off = reinterpret_cast<uint32_t *>(b + at.dat_off);
+		coords = reinterpret_cast<float *>(b + at.coords);
+		kinds = b + at.kinds;
 	}
 	vgsdf_outlines_packed view() const
 	{

@@ -1,0 +1,926 @@
+// outline_front_end.cpp — the device outline front-end behind the vgsdf_outlines_* entry points: outline commands (or
+// packed commands, or `glyf` bytes) in, rects out (prepare); bitmaps out (render).
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "device_internal.h"
+#include "outline_kernels.h"
+#include "upload_layout.h"
+#include "work_plan.h"
+
+// a submission between vgsdf_outlines_submit and vgsdf_outlines_wait
+struct FePending {
+	bool active = false;
+	uint32_t n = 0, n_cmds = 0;
+	size_t hdr_off = 0, rh_bytes = 0, at_off = 0; // rects | PlanHeader | (in-place PBF assembly) bitmap positions u64[n]
+	bool span = false, spec = false;
+	bool spec_direct = false; // the raster stores through the device mapping of the caller's page-locked buffer
+	const uint32_t *d_pbf_pre = nullptr; // device copies of the in-place PBF inputs (NULL: bitmaps packed back to back)
+	const uint8_t *d_pbf_fix = nullptr;
+	uint8_t *spec_out = nullptr, *d_spec = nullptr; // destination of the raster enqueued behind the front-end
+	size_t spec_cap = 0;
+	uint32_t launch_spans = 0, span_max = 4, span_budget = 16;
+	double t0 = 0, t1 = 0;
+};
+
+struct FrontEnd {
+	// device: inputs, per-command / per-ring intermediates, results of measure + plan, the resident batch
+	DevBuf cmds, kinds, coords, meta, cmd_open, counts, pt_local, cmd_box, cmd_mask, rings, cmd_ring, rects_hdr, descs, tiles, flag;
+	DevBuf seg, out, boxes, pbf_in; // seg: records {sx, sy, ex, ey}
+	DevBuf h_rects, h_stage; // pinned
+	size_t seg_cap = 0, tile_cap = 0; // elements the segment arrays / the work list hold
+	uint32_t last_spans = 0;          // work-list length of the previous batch (grid guess of the one-submission form)
+	// error words of the submissions: two 16-byte slots used alternately; the plan kernel of a submission zeroes the other
+	// slot for its successor (no memset launch per submission).  flags_clean: both slots are known to be in that state
+	uint32_t flag_slot = 0;
+	bool flags_clean = false;
+	uint32_t *flag_word() const { return (uint32_t *)((uint8_t *)flag.p + 16 * (size_t)flag_slot); }
+	uint32_t *next_flag_word() const { return (uint32_t *)((uint8_t *)flag.p + 16 * (size_t)(flag_slot ^ 1u)); }
+	FePending pend;
+	uint32_t n_glyphs = 0, n_cmds = 0, n_segs = 0;
+	uint64_t out_bytes = 0;
+	vgsdf_dbatch batch; // borrowed view over the buffers above
+	bool prepared = false;
+	bool peeked = false; // vgsdf_outlines_peek has waited for the read-back of the pending submission
+	FrontEnd()
+	{
+		h_rects.host = true;
+		h_stage.host = true;
+		batch.borrowed = true;
+	}
+	void release_all()
+	{
+		for (DevBuf *b : {&cmds, &kinds, &coords, &meta, &cmd_open, &counts, &pt_local, &cmd_box, &cmd_mask, &rings, &cmd_ring, &rects_hdr, &descs, &tiles, &flag, &seg, &out, &boxes, &pbf_in,
+		                  &h_rects, &h_stage})
+			b->release();
+	}
+};
+
+void fe_destroy(FrontEnd *fe)
+{
+	if (!fe)
+		return;
+	fe->release_all();
+	delete fe;
+}
+
+extern "C" {
+
+#define FE_TRY(expr) HIP_TRY_AS(ctx, "vgsdf_outlines: " #expr, expr)
+// (a launch: its failure is never reported as VGSDF_E_OOM)
+#define FE_KERNEL(expr)                                                                         \
+	do {                                                                                        \
+		int e__ = (expr);                                                                       \
+		if (e__ != 0) {                                                                         \
+			ctx->err = std::string("vgsdf_outlines: " #expr ": ") + hipGetErrorString((hipError_t)e__); \
+			return VGSDF_E_HIP;                                                                 \
+		}                                                                                       \
+	} while (0)
+
+// ---- the front-end as two halves: submit (everything enqueued, nothing waited for) and wait (the one
+// synchronisation, the read-back, second launches if a guess was too small).  With a destination (`spec_out`,
+// `spec_cap` bytes) the raster is enqueued right behind the front-end kernels, before the host has seen the plan: its
+// grid and every capacity are guesses the plan kernel checks on the device (PlanHeader::ok).  When they hold, the
+// bitmaps are in `spec_out` after the wait (written there by the kernel itself if the buffer is page-locked).
+namespace {
+struct FeDev { // device views of a submitted batch
+	const vgsdf::OutlineCmd *cmds;
+	const double *scale, *shift;
+	const uint32_t *cmd_off;
+	vgsdf::OutlineRect *rects;
+	vgsdf::PlanHeader *hdr;
+	vgsdf::GlyphDesc *descs;
+};
+FeDev fe_dev(FrontEnd &fe)
+{
+	const FePending &p = fe.pend;
+	const vgsdf::GlyphArraysLayout at(p.n); // (the head of fe.meta in every input form)
+	FeDev d;
+	d.cmds = (const vgsdf::OutlineCmd *)fe.cmds.p;
+	d.scale = (const double *)((const uint8_t *)fe.meta.p + at.scale);
+	d.shift = (const double *)((const uint8_t *)fe.meta.p + at.shift_x);
+	d.cmd_off = (const uint32_t *)((const uint8_t *)fe.meta.p + at.cmd_off);
+	d.rects = (vgsdf::OutlineRect *)fe.rects_hdr.p;
+	d.hdr = (vgsdf::PlanHeader *)((uint8_t *)fe.rects_hdr.p + p.hdr_off);
+	d.descs = (vgsdf::GlyphDesc *)fe.descs.p;
+	return d;
+}
+int fe_launch_plan(vgsdf_ctx *ctx, FrontEnd &fe, uint32_t spans_launched)
+{
+	const FePending &p = fe.pend;
+	const FeDev d = fe_dev(fe);
+	return vgsdf_outline_plan(d.rects, p.n, p.span ? 1 : 0, (uint32_t)vgsdf_filtered_delta_cap(), p.span_max, p.span_budget,
+	                          (uint32_t)std::min<size_t>(fe.tile_cap, 0x7FFFFFFFu), d.descs, (uint2 *)fe.tiles.p, d.hdr,
+	                          fe.flag_word(), (unsigned long long)fe.seg_cap, (unsigned long long)p.spec_cap,
+	                          spans_launched, p.d_pbf_pre, p.d_pbf_fix,
+	                          p.d_pbf_fix ? (unsigned long long *)((uint8_t *)fe.rects_hdr.p + p.at_off) : nullptr, fe.next_flag_word(), ctx->stream);
+}
+// The second flattening pass and the raster's chunk boxes.  Boxes: by default the first workgroups of the pass's own grid take
+// them from the commands' boxes (outline_kernels.hip, chunk_boxes_of_glyph: supersets of the exact boxes, no launch of their
+// own); VGSDF_CMD_BOXES=0 (measurement switch): from the segments, by sdf_chunk_boxes behind the pass
+int fe_launch_emit(vgsdf_ctx *ctx, FrontEnd &fe)
+{
+	const FePending &p = fe.pend;
+	const FeDev d = fe_dev(fe);
+	static const char *cb_env = std::getenv("VGSDF_CMD_BOXES");
+	const bool cmd_boxes = p.span && !(cb_env && cb_env[0] == '0');
+	int e = vgsdf_outline_emit_segments(d.cmds, p.n_cmds, (const uint8_t *)fe.cmd_open.p, d.scale, d.shift, (const uint32_t *)fe.pt_local.p,
+	                                    (const vgsdf::RingRec *)fe.rings.p, (const uint32_t *)fe.cmd_ring.p, d.descs, d.hdr,
+	                                    (unsigned long long)fe.seg_cap, (double *)fe.seg.p, (const unsigned long long *)fe.cmd_mask.p,
+	                                    cmd_boxes ? p.n : 0u, d.cmd_off, fe.cmd_box.p, fe.boxes.p, ctx->stream);
+	if (e == 0 && p.span && !cmd_boxes)
+		e = vgsdf_launch_chunk_boxes(d.descs, p.n, (const double *)fe.seg.p, (const double *)fe.seg.p + 1, (const double *)fe.seg.p + 2,
+		                             (const double *)fe.seg.p + 3, 4, fe.boxes.p, d.hdr, (unsigned long long)fe.seg_cap, ctx->stream);
+	return e;
+}
+hipError_t fe_ensure_tiles(FrontEnd &fe, size_t want)
+{
+	if (want <= fe.tile_cap)
+		return hipSuccess;
+	hipError_t e = fe.tiles.ensure(sizeof(uint2) * want);
+	if (e == hipSuccess)
+		fe.tile_cap = fe.tiles.cap / sizeof(uint2);
+	return e;
+}
+hipError_t fe_ensure_segs(FrontEnd &fe, size_t want, uint32_t n_glyphs)
+{
+	if (want > fe.seg_cap) {
+		if (hipError_t e = fe.seg.ensure(32 * want + 32); e != hipSuccess)
+			return e;
+		fe.seg_cap = fe.seg.cap / 32 - 1;
+	}
+	return fe.boxes.ensure(vgsdf_chunk_box_bytes(fe.seg_cap, n_glyphs) + 16);
+}
+} // namespace
+
+// the two input forms of a submission: 28-byte command records, or kinds + coordinates (vgsdf_outlines_packed)
+struct FeInput {
+	uint32_t n_glyphs = 0;
+	const uint32_t *cmd_off = nullptr;
+	const double *scale = nullptr, *shift_x = nullptr;
+	const vgsdf_outline_cmd *cmds = nullptr;
+	const uint32_t *dat_off = nullptr;
+	const uint8_t *kinds = nullptr;
+	const float *coords = nullptr;
+	const uint32_t *pbf_pre = nullptr; // in-place PBF assembly (vgsdf_outlines_packed): both or neither
+	const uint8_t *pbf_fix = nullptr;
+	bool packed = false;
+	// vgsdf_outlines_glyf: the glyphs' `glyf` arrays instead of commands (cmd_off counts command SLOTS)
+	bool glyf = false;
+	const vgsdf_glyf_part *parts = nullptr;
+	uint32_t n_parts = 0;
+	const uint8_t *bytes = nullptr;
+	uint32_t n_bytes = 0;
+};
+
+// ---- submit, step by step (fe_submit below keeps their order: it is part of the contract with the device) ----
+
+// 1. argument checks: nothing is touched on a bad call.  Sets the command and coordinate counts of the batch
+static int fe_check_args(vgsdf_ctx *ctx, const FeInput *in, uint32_t &n_cmds, uint32_t &n_floats)
+{
+	if (!in || (in->n_glyphs && (!in->cmd_off || !in->scale || !in->shift_x || (in->packed && !in->dat_off)))) {
+		ctx->err = "vgsdf_outlines: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if ((in->pbf_pre == nullptr) != (in->pbf_fix == nullptr) || (in->pbf_fix && !in->packed && !in->glyf)) {
+		ctx->err = "vgsdf_outlines: pbf_pre and pbf_fix come together (packed and glyf forms only)";
+		return VGSDF_E_ARG;
+	}
+	static_assert(sizeof(vgsdf_glyf_part) == 48, "ABI struct mirrors the kernel struct");
+	static_assert(sizeof(vgsdf_outline_cmd) == sizeof(vgsdf::OutlineCmd), "ABI struct mirrors the kernel struct");
+	static_assert(sizeof(vgsdf_rect) == sizeof(vgsdf::OutlineRect), "ABI struct mirrors the kernel struct");
+	const uint32_t n = in->n_glyphs;
+	if (n && in->cmd_off[0] != 0) {
+		ctx->err = "vgsdf_outlines: cmd_off[0] must be 0";
+		return VGSDF_E_ARG;
+	}
+	n_cmds = n ? in->cmd_off[n] : 0;
+	if (n_cmds && !in->glyf && (in->packed ? !in->kinds : !in->cmds)) {
+		ctx->err = "vgsdf_outlines: NULL command array";
+		return VGSDF_E_ARG;
+	}
+	if (in->glyf && ((in->n_parts && (!in->parts || !in->bytes)) || (in->n_bytes & 3u))) {
+		ctx->err = "vgsdf_outlines_glyf: NULL parts / bytes, or n_bytes not a multiple of 4";
+		return VGSDF_E_ARG;
+	}
+	if (in->packed && n && (in->dat_off[0] != 0 || (in->dat_off[n] && !in->coords))) {
+		ctx->err = in->dat_off[0] != 0 ? "vgsdf_outlines: dat_off[0] must be 0" : "vgsdf_outlines: NULL coordinate array";
+		return VGSDF_E_ARG;
+	}
+	n_floats = in->packed && n ? in->dat_off[n] : 0u;
+	return VGSDF_OK;
+}
+
+// 2. The walks over the input — offsets monotone, parts tiling the command slots inside their glyphs and inside `bytes`, scales —
+// are what every kernel's indexing rests on, so they come before the first kernel that reads the input; but not before the
+// UPLOAD, which reads nothing of it: a single-block submission starts its copy first and validates under it (25 k entries
+// of a 21-font group: ~45 us of this thread that the device used to wait for).
+// (the command kinds are checked on the device: the kernels treat an unknown kind as a no-op and the context
+// pass raises the batch's error flag, so nothing unsafe runs and the host need not walk the commands)
+struct FeFacts { // what the walks note on their way, for the launches
+	uint32_t glyf_max_cap = 0, glyf_max_len = 0; // the largest cmd_cap / byte_len among the parts
+	bool parts_inside_glyphs = true;             // every part's slots lie inside ONE glyph's range (what a sound caller sends)
+	bool scales_plain = true;                    // every scale positive and finite
+};
+static int fe_validate(vgsdf_ctx *ctx, const FeInput *in, uint32_t n_cmds, FeFacts &facts)
+{
+	const uint32_t n = in->n_glyphs;
+	FeFacts &f = facts;
+	uint32_t bad = 0;
+	for (uint32_t g = 0; g < n; g++) {
+		bad |= in->cmd_off[g + 1] < in->cmd_off[g];
+		f.scales_plain = f.scales_plain && in->scale[g] > 0.0 && in->scale[g] < HUGE_VAL;
+	}
+	if (bad) {
+		ctx->err = "vgsdf_outlines: cmd_off not monotone";
+		return VGSDF_E_ARG;
+	}
+	if (in->glyf) {
+		// the parts tile the command slots in order, and their bytes lie inside `bytes` (what the bytes SAY is checked on
+		// the device, entry by entry)
+		uint64_t slots = 0;
+		uint32_t gi = 0;
+		for (uint32_t i = 0; i < in->n_parts; i++) {
+			const vgsdf_glyf_part &pt = in->parts[i];
+			while (gi < n && in->cmd_off[gi + 1] <= pt.cmd_at)
+				gi++;
+			f.parts_inside_glyphs = f.parts_inside_glyphs && gi < n && pt.cmd_at >= in->cmd_off[gi] && (uint64_t)pt.cmd_at + pt.cmd_cap <= in->cmd_off[gi + 1];
+			f.glyf_max_cap = std::max(f.glyf_max_cap, pt.cmd_cap);
+			f.glyf_max_len = std::max(f.glyf_max_len, pt.byte_len);
+			if (pt.cmd_at != slots || (pt.byte_off & 3u) || pt.byte_off > in->n_bytes || pt.byte_len > in->n_bytes - pt.byte_off ||
+			    pt.n_contours == 0) {
+				ctx->err = "vgsdf_outlines_glyf: parts must tile the command slots in order, with 4-aligned byte ranges inside `bytes`";
+				return VGSDF_E_ARG;
+			}
+			slots += pt.cmd_cap;
+		}
+		if (slots != n_cmds) {
+			ctx->err = "vgsdf_outlines_glyf: cmd_off[n_glyphs] differs from the parts' command slots";
+			return VGSDF_E_ARG;
+		}
+	}
+	if (in->packed) {
+		for (uint32_t g = 0; g < n; g++)
+			bad |= in->dat_off[g + 1] < in->dat_off[g];
+		if (bad) {
+			ctx->err = "vgsdf_outlines: dat_off not monotone";
+			return VGSDF_E_ARG;
+		}
+	}
+	return VGSDF_OK;
+}
+
+// How the input of a submission travels.  The device keeps the glyf form, and a packed single block, in fe.meta in the
+// single-block layout (upload_layout.h) whether the arrays arrive as one block or one by one; otherwise fe.meta holds
+// the per-glyph arrays only (staged as one block) and kinds / coords / cmds have buffers of their own.
+struct FeUpload {
+	vgsdf::PackedBlockLayout pk; // (its head also serves the plain command form)
+	vgsdf::GlyfBlockLayout gl;
+	size_t arrays_bytes;          // scale | shift_x | cmd_off [| dat_off]
+	const uint8_t *block = nullptr; // the caller's arrays are ONE page-locked block in their form's layout: one copy
+	size_t block_bytes = 0;
+	const void *mapped = nullptr; // ... that the device can address: uploaded by a kernel (outline_kernels.hip, copy_in)
+	// set by fe_upload: device views of what the form brings besides the per-glyph arrays (those: fe_dev)
+	const uint8_t *d_kinds = nullptr, *d_parts = nullptr, *d_bytes = nullptr;
+	const float *d_coords = nullptr;
+	const uint32_t *d_dat_off = nullptr;
+};
+static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_floats)
+{
+	const uint32_t n = in->n_glyphs;
+	const bool pbf = in->pbf_fix != nullptr;
+	FeUpload up{vgsdf::PackedBlockLayout(n, n_cmds, n_floats, pbf), vgsdf::GlyfBlockLayout(n, in->n_parts, in->n_bytes, pbf), 0};
+	up.arrays_bytes = in->packed ? up.pk.arrays_end : up.pk.end;
+	// the block is recognised by the caller's pointers: every array where the layout has it, counted from `scale`
+	const uint8_t *hb = (const uint8_t *)in->scale;
+	auto at = [hb](const void *array, size_t off) { return (const uint8_t *)array == hb + off; };
+	const vgsdf::PackedBlockLayout &pk = up.pk;
+	const vgsdf::GlyfBlockLayout &gl = up.gl;
+	bool single = false;
+	if (in->glyf) {
+		up.block_bytes = gl.bytes;
+		single = at(in->shift_x, gl.shift_x) && at(in->cmd_off, gl.cmd_off) && at(in->parts, gl.parts) && at(in->bytes, gl.glyf_bytes) &&
+		         (!pbf || (at(in->pbf_pre, gl.pbf_pre) && at(in->pbf_fix, gl.pbf_fix)));
+	} else if (in->packed) {
+		up.block_bytes = pk.bytes;
+		single = at(in->shift_x, pk.shift_x) && at(in->cmd_off, pk.cmd_off) && at(in->dat_off, pk.dat_off) && at(in->coords, pk.coords) &&
+		         at(in->kinds, pk.kinds) && (!pbf || (at(in->pbf_pre, pk.pbf_pre) && at(in->pbf_fix, pk.pbf_fix)));
+	}
+	if (single && is_pinned(hb, up.block_bytes))
+		up.block = hb;
+	static const char *ck_env = std::getenv("VGSDF_COPY_KERNEL"); // (0: measurement switch, the copy engine takes the block)
+	if (up.block && !(ck_env && ck_env[0] == '0') && ((uintptr_t)hb & 15u) == 0)
+		up.mapped = pinned_device_ptr(const_cast<uint8_t *>(hb), up.block_bytes);
+	return up;
+}
+
+// 3. buffer reservation: everything a submission of this size writes.  Sets the layout of the read-back block in fe.pend
+static int fe_reserve(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n_cmds, const FeUpload &up)
+{
+	FePending &p = fe.pend;
+	const uint32_t n = in->n_glyphs;
+	FE_TRY(fe.cmds.ensure(sizeof(vgsdf::OutlineCmd) * (size_t)(n_cmds + 1)));
+	FE_TRY(fe.meta.ensure((in->glyf ? up.gl.bytes : (up.block ? up.pk.bytes : up.arrays_bytes)) + 16));
+	FE_TRY(fe.h_stage.ensure(up.arrays_bytes + 16));
+	FE_TRY(fe.cmd_open.ensure((size_t)n_cmds + 1));
+	FE_TRY(fe.counts.ensure(4 * (size_t)(n_cmds + 1)));
+	FE_TRY(fe.pt_local.ensure(4 * ((size_t)n_cmds + n + 2)));
+	FE_TRY(fe.cmd_box.ensure(32 * (size_t)(n_cmds + 1)));
+	FE_TRY(fe.cmd_mask.ensure(8 * (size_t)(n_cmds + 1)));
+	FE_TRY(fe.rings.ensure(sizeof(vgsdf::RingRec) * (size_t)(n_cmds + 1)));
+	FE_TRY(fe.cmd_ring.ensure(4 * (size_t)(n_cmds + 1)));
+	p.hdr_off = align_up(sizeof(vgsdf::OutlineRect) * (size_t)n, 16); // rects and totals: one block, one read-back
+	p.at_off = align_up(p.hdr_off + sizeof(vgsdf::PlanHeader), 16);
+	p.rh_bytes = in->pbf_fix ? p.at_off + 8 * (size_t)n : p.hdr_off + sizeof(vgsdf::PlanHeader);
+	FE_TRY(fe.rects_hdr.ensure(p.rh_bytes));
+	FE_TRY(fe.h_rects.ensure(p.rh_bytes));
+	FE_TRY(fe.descs.ensure(sizeof(vgsdf::GlyphDesc) * (size_t)n + 16));
+	FE_TRY(fe.flag.ensure(32));
+	// capacities of what only the device knows the size of: the work list and the segment arrays.  Guessed from
+	// the input (and kept from earlier batches); the plan / emit kernels write nothing past them and the totals
+	// that come back with the rects say whether a second launch is needed.
+	FE_TRY(fe_ensure_tiles(fe, 2 * (size_t)n + 1024));
+	FE_TRY(fe_ensure_segs(fe, 12 * (size_t)n_cmds + 4096, n));
+	return VGSDF_OK;
+}
+
+// 4. upload, per input form
+static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n_cmds, uint32_t n_floats, FeUpload &up)
+{
+	FePending &p = fe.pend;
+	hipStream_t st = ctx->stream;
+	const size_t n = in->n_glyphs;
+	const bool pbf = in->pbf_fix != nullptr;
+	const vgsdf::PackedBlockLayout &pk = up.pk;
+	const vgsdf::GlyfBlockLayout &gl = up.gl;
+	uint8_t *dm = (uint8_t *)fe.meta.p;
+	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+	if (up.mapped)
+		FE_KERNEL(vgsdf_copy_in(up.mapped, dm, up.block_bytes, st));
+	else if (up.block)
+		FE_TRY(copy(dm, up.block, up.block_bytes));
+	if (in->glyf) {
+		if (!up.block) {
+			FE_TRY(copy(dm + gl.scale, in->scale, 8 * n));
+			FE_TRY(copy(dm + gl.shift_x, in->shift_x, 8 * n));
+			FE_TRY(copy(dm + gl.cmd_off, in->cmd_off, 4 * (n + 1)));
+			FE_TRY(copy(dm + gl.parts, in->parts, sizeof(vgsdf_glyf_part) * (size_t)in->n_parts));
+			FE_TRY(copy(dm + gl.glyf_bytes, in->bytes, in->n_bytes));
+			FE_TRY(copy(dm + gl.pbf_pre, in->pbf_pre, pbf ? 4 * n : 0));
+			FE_TRY(copy(dm + gl.pbf_fix, in->pbf_fix, pbf ? n : 0));
+		}
+		up.d_parts = dm + gl.parts;
+		up.d_bytes = dm + gl.glyf_bytes;
+		if (pbf) {
+			p.d_pbf_pre = (const uint32_t *)(dm + gl.pbf_pre);
+			p.d_pbf_fix = dm + gl.pbf_fix;
+		}
+		return VGSDF_OK;
+	}
+	if (up.block) { // (packed)
+		up.d_coords = (const float *)(dm + pk.coords);
+		up.d_kinds = dm + pk.kinds;
+		up.d_dat_off = (const uint32_t *)(dm + pk.dat_off);
+		if (pbf) {
+			p.d_pbf_pre = (const uint32_t *)(dm + pk.pbf_pre);
+			p.d_pbf_fix = dm + pk.pbf_fix;
+		}
+		return VGSDF_OK;
+	}
+	if (in->packed) {
+		FE_TRY(fe.kinds.ensure((size_t)n_cmds + 16));
+		FE_TRY(fe.coords.ensure(4 * (size_t)n_floats + 16));
+		FE_TRY(copy(fe.kinds.p, in->kinds, (size_t)n_cmds));
+		FE_TRY(copy(fe.coords.p, in->coords, 4 * (size_t)n_floats));
+		up.d_kinds = (const uint8_t *)fe.kinds.p;
+		up.d_coords = (const float *)fe.coords.p;
+		up.d_dat_off = (const uint32_t *)(dm + pk.dat_off);
+	} else {
+		FE_TRY(copy(fe.cmds.p, in->cmds, sizeof(vgsdf::OutlineCmd) * (size_t)n_cmds));
+	}
+	// per-glyph inputs (scale, shift, command offsets) travel as ONE block through pinned staging
+	uint8_t *hm = (uint8_t *)fe.h_stage.p;
+	std::memcpy(hm + pk.scale, in->scale, 8 * n);
+	std::memcpy(hm + pk.shift_x, in->shift_x, 8 * n);
+	std::memcpy(hm + pk.cmd_off, in->cmd_off, 4 * (n + 1));
+	if (in->packed)
+		std::memcpy(hm + pk.dat_off, in->dat_off, 4 * (n + 1));
+	FE_TRY(copy(dm, hm, up.arrays_bytes));
+	if (pbf) { // arrays that do not sit in the single-copy block: their own copies
+		FE_TRY(fe.pbf_in.ensure(5 * n + 16));
+		FE_TRY(copy(fe.pbf_in.p, in->pbf_pre, 4 * n));
+		FE_TRY(copy((uint8_t *)fe.pbf_in.p + 4 * n, in->pbf_fix, n));
+		p.d_pbf_pre = (const uint32_t *)fe.pbf_in.p;
+		p.d_pbf_fix = (const uint8_t *)fe.pbf_in.p + 4 * n;
+	}
+	return VGSDF_OK;
+}
+
+// the raster launch enqueued behind the front-end: default kernel only, destination the caller's page-locked
+// buffer itself or, for pageable memory, the context's device buffer
+static int fe_place_raster(vgsdf_ctx *ctx, FrontEnd &fe)
+{
+	FePending &p = fe.pend;
+	p.spec = p.spec_out != nullptr && p.spec_cap != 0 && ctx->variant == 0;
+	if (!p.spec)
+		return VGSDF_OK;
+	if (void *mapped = pinned_device_ptr(p.spec_out, p.spec_cap)) {
+		p.d_spec = (uint8_t *)mapped;
+		p.spec_direct = true;
+	} else {
+		FE_TRY(fe.out.ensure(p.spec_cap + 16));
+		p.d_spec = (uint8_t *)fe.out.p;
+	}
+	const size_t guess = fe.last_spans ? (size_t)fe.last_spans + fe.last_spans / 2 + 256 : fe.tile_cap;
+	p.launch_spans = (uint32_t)std::min<size_t>(std::min(guess, fe.tile_cap), 0x7FFFFFFFu);
+	return VGSDF_OK;
+}
+
+// 5. the kernels and the read-back of their results
+static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeUpload &up, const FeFacts &facts)
+{
+	const FePending &p = fe.pend;
+	hipStream_t st = ctx->stream;
+	const uint32_t n = p.n, n_cmds = p.n_cmds;
+	const FeDev d = fe_dev(fe);
+	uint32_t *const flagw = fe.flag_word();
+	// glyf form: the decoder writes the context bytes itself (the ring state follows from the contour rules) when no glyph
+	// of the batch has an odd scale (not positive and finite: bit 1 of the context byte, which only the context pass forms)
+	// and no part straddles two glyphs (the decoder's rule is per part; the ring pass trusts the context bytes to be those of
+	// the glyph's own command sequence — a byte that says "open" in front of a glyph's first command would index a ring
+	// that does not exist)
+	bool decode_makes_context = in->glyf && facts.parts_inside_glyphs && facts.scales_plain;
+	static const char *fuse_env = std::getenv("VGSDF_FUSE_CONTEXT"); // (measurement switch)
+	if (fuse_env && fuse_env[0] == '0')
+		decode_makes_context = false;
+	if (in->glyf)
+		FE_KERNEL(vgsdf_glyf_decode(up.d_parts, in->n_parts, up.d_bytes, (vgsdf::OutlineCmd *)fe.cmds.p, flagw, facts.glyf_max_cap, facts.glyf_max_len,
+		                            decode_makes_context ? (uint8_t *)fe.cmd_open.p : nullptr, st));
+	if (in->packed)
+		FE_KERNEL(vgsdf_outline_context_packed(up.d_kinds, up.d_coords, up.d_dat_off, d.cmd_off, d.scale, n, (vgsdf::OutlineCmd *)fe.cmds.p,
+		                                       (uint8_t *)fe.cmd_open.p, flagw, st));
+	else if (!decode_makes_context)
+		FE_KERNEL(vgsdf_outline_context(d.cmds, d.cmd_off, d.scale, n, (uint8_t *)fe.cmd_open.p, flagw, st));
+	FE_KERNEL(vgsdf_outline_count(d.cmds, (const uint8_t *)fe.cmd_open.p, n_cmds, d.cmd_off, n, d.scale, d.shift,
+	                              (uint32_t *)fe.counts.p, fe.cmd_box.p, (unsigned long long *)fe.cmd_mask.p, flagw, st));
+	FE_KERNEL(vgsdf_outline_rings(d.cmds, d.cmd_off, (const uint8_t *)fe.cmd_open.p, d.scale, d.shift, n,
+	                              (const uint32_t *)fe.counts.p, (uint32_t *)fe.pt_local.p,
+	                              fe.cmd_box.p, (vgsdf::RingRec *)fe.rings.p, (uint32_t *)fe.cmd_ring.p, d.rects,
+	                              flagw, st));
+	FE_KERNEL(fe_launch_plan(ctx, fe, p.launch_spans));
+	// The front-end's results (rects, totals, positions of the bitmaps) are final once the plan has run: they travel back
+	// on a stream of their own, beside the flattening and the raster instead of behind them — the host can have them a
+	// good 100 us before the bitmaps (vgsdf_outlines_peek), and the end of the submission loses a copy and its hand-over.
+	static const char *early_env = std::getenv("VGSDF_EARLY_COPY"); // (measurement switch: 0 = read-back behind the raster, as in round 2)
+	const bool early_copy = !(early_env && early_env[0] == '0');
+	if (early_copy) {
+		FE_TRY(hipEventRecord(ctx->ev_plan, st));
+		FE_TRY(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_plan, 0));
+		FE_TRY(hipMemcpyAsync(fe.h_rects.p, fe.rects_hdr.p, p.rh_bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
+		FE_TRY(hipEventRecord(ctx->ev_rects, ctx->copy_stream));
+	}
+	FE_KERNEL(fe_launch_emit(ctx, fe));
+	if (p.spec)
+		FE_KERNEL(vgsdf_launch_span_planned(d.descs, (const uint2 *)fe.tiles.p, p.launch_spans, (const double *)fe.seg.p,
+		                                    (const double *)fe.seg.p + 1, (const double *)fe.seg.p + 2, (const double *)fe.seg.p + 3, 4,
+		                                    p.d_spec, fe.boxes.p, d.hdr, st));
+	if (!early_copy) {
+		FE_TRY(hipMemcpyAsync(fe.h_rects.p, fe.rects_hdr.p, p.rh_bytes, hipMemcpyDeviceToHost, st));
+		FE_TRY(hipEventRecord(ctx->ev_rects, st));
+	}
+	static const bool trace_span = std::getenv("VGSDF_TRACE") != nullptr;
+	if (trace_span)
+		FE_TRY(hipEventRecord(ctx->ev1, st));
+	return VGSDF_OK;
+}
+
+static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_t spec_cap)
+{
+	const double tr0 = fe_now();
+	if (!ctx)
+		return VGSDF_E_ARG;
+	uint32_t n_cmds = 0, n_floats = 0;
+	if (int rc = fe_check_args(ctx, in, n_cmds, n_floats); rc != VGSDF_OK)
+		return rc;
+	const uint32_t n = in->n_glyphs;
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->fe)
+		ctx->fe = new (std::nothrow) FrontEnd();
+	if (!ctx->fe) {
+		ctx->err = "vgsdf_outlines: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	FrontEnd &fe = *ctx->fe;
+	if (fe.pend.active) {
+		ctx->err = "vgsdf_outlines_submit: the previous submission of this context has not been waited for";
+		return VGSDF_E_ARG;
+	}
+	fe.prepared = false;
+	fe.peeked = false;
+	fe.n_glyphs = n;
+	fe.n_cmds = n_cmds;
+	fe.n_segs = 0;
+	fe.out_bytes = 0;
+	FePending &p = fe.pend;
+	p = FePending{};
+	p.n = n;
+	p.n_cmds = n_cmds;
+	p.spec_out = spec_out;
+	p.spec_cap = spec_out ? spec_cap : 0;
+	p.t0 = tr0;
+	if (n == 0) {
+		fe.batch.stats = vgsdf_stats{};
+		p.active = true;
+		p.t1 = fe_now();
+		return VGSDF_OK;
+	}
+	p.t1 = fe_now();
+	p.span = uses_span_list(ctx->variant);
+	vgsdf::span_policy_from_env(n, p.span_max, p.span_budget);
+	FeUpload up = fe_upload_form(in, n_cmds, n_floats);
+	if (int rc = fe_reserve(ctx, fe, in, n_cmds, up); rc != VGSDF_OK)
+		return rc;
+	if (std::getenv("VGSDF_TRACE") != nullptr)
+		FE_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+	FeFacts facts;
+	const bool validate_under_upload = up.mapped != nullptr; // (not one block uploaded by a kernel: validate first, as ever)
+	if (!validate_under_upload)
+		if (int rc = fe_validate(ctx, in, n_cmds, facts); rc != VGSDF_OK)
+			return rc;
+	// error word of this submission (FrontEnd::flag_slot)
+	if (!fe.flags_clean)
+		FE_TRY(hipMemsetAsync(fe.flag.p, 0, 32, ctx->stream));
+	fe.flags_clean = false; // (until everything below is enqueued: its plan kernel zeroes the other slot)
+	fe.flag_slot ^= 1u;
+	if (int rc = fe_upload(ctx, fe, in, n_cmds, n_floats, up); rc != VGSDF_OK)
+		return rc;
+	if (int rc = fe_place_raster(ctx, fe); rc != VGSDF_OK)
+		return rc;
+	if (validate_under_upload) // the upload is under way: now the walks over the input, before the first kernel that reads it
+		if (int rc = fe_validate(ctx, in, n_cmds, facts); rc != VGSDF_OK)
+			return rc;
+	if (int rc = fe_enqueue(ctx, fe, in, up, facts); rc != VGSDF_OK)
+		return rc;
+	fe.flags_clean = true; // the plan kernel enqueued above leaves the other slot zeroed for the next submission
+	p.active = true;
+	return VGSDF_OK;
+}
+
+static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, uint64_t *n_segments, int *rendered)
+{
+	static const bool trace = std::getenv("VGSDF_TRACE") != nullptr;
+	if (rendered)
+		*rendered = 0;
+	if (out_bytes)
+		*out_bytes = 0;
+	if (n_segments)
+		*n_segments = 0;
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!ctx->fe || !ctx->fe->pend.active) {
+		ctx->err = "vgsdf_outlines_wait: nothing was submitted";
+		return VGSDF_E_ARG;
+	}
+	FrontEnd &fe = *ctx->fe;
+	FePending &p = fe.pend;
+	const uint32_t n = p.n;
+	if (n && !rects_out) {
+		ctx->err = "vgsdf_outlines: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	p.active = false;
+	if (n == 0) {
+		fe.prepared = true;
+		if (rendered && p.spec_out)
+			*rendered = 1;
+		return VGSDF_OK;
+	}
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	FE_TRY(hipStreamSynchronize(st)); // the one synchronisation of the submission
+	FE_TRY(hipEventSynchronize(ctx->ev_rects)); // (the read-back finished long ago: it left right behind the plan)
+	const double tr2 = fe_now();
+	std::memcpy(rects_out, fe.h_rects.p, sizeof(vgsdf_rect) * (size_t)n);
+	vgsdf::PlanHeader hdr;
+	std::memcpy(&hdr, (const uint8_t *)fe.h_rects.p + p.hdr_off, sizeof hdr);
+	if (hdr.error & 16u) {
+		ctx->err = "vgsdf_outlines_glyf: a `glyf` entry whose arrays do not fit its bytes (ttf-parser drops such a glyph): record this batch "
+		           "with the host's reader";
+		return VGSDF_E_GLYF;
+	}
+	if (hdr.error & 2u) {
+		ctx->err = "vgsdf_outlines_prepare: unknown command kind";
+		return VGSDF_E_ARG;
+	}
+	if (hdr.error & 8u) {
+		ctx->err = "vgsdf_outlines: dat_off does not match the command kinds";
+		return VGSDF_E_ARG;
+	}
+	if (hdr.error & 4u) {
+		ctx->err = "vgsdf_outlines_prepare: internal error (a cubic exceeded its subdivision depth bound)";
+		return VGSDF_E_HIP;
+	}
+	if (hdr.error) {
+		ctx->err = "vgsdf_outlines_prepare: a glyph flattens to more than 2^28 points, the batch to more than 2^32 - 1 segments, or a "
+		           "bitmap exceeds 2^32 pixels (non-finite or absurd control points?)";
+		return VGSDF_E_ARG;
+	}
+	if (hdr.n_spans > 0x7FFFFFFFu) {
+		ctx->err = "vgsdf_outlines_prepare: batch too large (tile count exceeds 2^31-1); split it";
+		return VGSDF_E_ARG;
+	}
+	// second launches when a capacity guess was too small (first batches of a context, unusual fonts)
+	const bool replan = hdr.n_spans > fe.tile_cap, reemit = hdr.n_segments > fe.seg_cap;
+	if (replan) {
+		FE_TRY(fe_ensure_tiles(fe, (size_t)hdr.n_spans + hdr.n_spans / 4 + 1024));
+		FE_KERNEL(fe_launch_plan(ctx, fe, 0));
+	}
+	if (reemit) {
+		FE_TRY(fe_ensure_segs(fe, (size_t)hdr.n_segments + hdr.n_segments / 4 + 4096, n));
+		FE_KERNEL(fe_launch_emit(ctx, fe));
+	}
+	const double tr3 = fe_now();
+
+	uint64_t n_pairs = 0, n_pixels = 0;
+	for (uint32_t g = 0; g < n; g++) {
+		const vgsdf_rect &r = rects_out[g];
+		if (r.has_raster) {
+			n_pairs += (uint64_t)r.w * r.h * r.n_segments;
+			n_pixels += (uint64_t)r.w * r.h;
+		}
+	}
+	const FeDev d = fe_dev(fe);
+	fe.n_segs = (uint32_t)hdr.n_segments;
+	fe.out_bytes = hdr.out_bytes;
+	vgsdf_dbatch &b = fe.batch;
+	b.stats.n_glyphs = n;
+	b.stats.n_segments = fe.n_segs;
+	b.stats.n_pixels = n_pixels; // (out_bytes is larger with in-place PBF assembly: headers and gaps)
+	b.stats.n_pairs = n_pairs;
+	b.stats.n_tiles = hdr.n_spans;
+	b.stats.alg_bytes = 32 * (uint64_t)fe.n_segs + 32 * (uint64_t)n + n_pixels;
+	b.out_bytes = (size_t)fe.out_bytes;
+	b.n_main = hdr.n_main;
+	b.span_list = p.span;
+	b.tile_order = 1; // the device-built list is dispatched in list order
+	fe.last_spans = hdr.n_spans;
+	const bool done = p.spec && hdr.ok != 0; // the raster behind the plan ran over the whole list
+	if (!(done && p.spec_direct))
+		FE_TRY(fe.out.ensure(std::max((size_t)fe.out_bytes, done ? p.spec_cap : (size_t)0) + 16));
+	b.d_glyphs = d.descs;
+	b.d_tiles = (uint2 *)fe.tiles.p;
+	b.d_sx = (double *)fe.seg.p;
+	b.d_sy = (double *)fe.seg.p + 1;
+	b.d_ex = (double *)fe.seg.p + 2;
+	b.d_ey = (double *)fe.seg.p + 3;
+	b.seg_stride = 4;
+	b.d_out = (uint8_t *)fe.out.p;
+	b.d_boxes = p.span ? fe.boxes.p : nullptr;
+	fe.prepared = true;
+	if (out_bytes)
+		*out_bytes = fe.out_bytes;
+	if (n_segments)
+		*n_segments = fe.n_segs;
+	if (p.spec_out && fe.out_bytes <= p.spec_cap) {
+		int rc = VGSDF_OK;
+		if (done) {
+			if (!p.spec_direct && fe.out_bytes) { // pageable destination: the raster wrote the device buffer
+				FE_TRY(hipMemcpyAsync(p.spec_out, p.d_spec, (size_t)fe.out_bytes, hipMemcpyDeviceToHost, st));
+				FE_TRY(hipStreamSynchronize(st));
+			}
+		} else if (fe.out_bytes) { // a guess was too small (first batch of a context, a batch unlike the last one)
+			rc = vgsdf_batch_launch(ctx, &fe.batch);
+			if (rc == VGSDF_OK)
+				rc = vgsdf_batch_download(ctx, &fe.batch, p.spec_out);
+		}
+		if (rc != VGSDF_OK)
+			return rc;
+		if (rendered)
+			*rendered = 1;
+	}
+	if (trace) {
+		float span_ms = 0;
+		if (hipEventElapsedTime(&span_ms, ctx->ev0, ctx->ev1) == hipSuccess)
+			std::fprintf(stderr, "[vgsdf] device span of the submission (upload ... last kernel, events on the kernel stream): %.1f us\n", span_ms * 1e3);
+		else
+			(void)hipGetLastError();
+	}
+	if (trace && p.spec_out)
+		std::fprintf(stderr, "[vgsdf] one submission%s, %s destination\n", done ? "" : " (guess too small: second launches)",
+		             p.spec_direct ? "page-locked" : "pageable");
+	if (trace)
+		std::fprintf(stderr, "[vgsdf] prepare: validate %.3f ms, submit ... read-back %.3f ms, second launches%s%s %.3f ms, host %.3f ms\n",
+		             (p.t1 - p.t0) * 1e3, (tr2 - p.t1) * 1e3, replan ? " (plan)" : "", reemit ? " (emit)" : "", (tr3 - tr2) * 1e3,
+		             (fe_now() - tr3) * 1e3);
+	return VGSDF_OK;
+}
+
+static FeInput fe_input(const vgsdf_outlines *in)
+{
+	FeInput f;
+	f.n_glyphs = in->n_glyphs;
+	f.cmd_off = in->cmd_off;
+	f.scale = in->scale;
+	f.shift_x = in->shift_x;
+	f.cmds = in->cmds;
+	return f;
+}
+
+int vgsdf_outlines_prepare(vgsdf_ctx *ctx, const vgsdf_outlines *in, vgsdf_rect *rects_out, uint64_t *out_bytes,
+                           uint64_t *n_segments)
+{
+	if (ctx && in && in->n_glyphs && !rects_out) {
+		ctx->err = "vgsdf_outlines_prepare: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if (ctx && !in) {
+		ctx->err = "vgsdf_outlines: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	FeInput f;
+	if (in)
+		f = fe_input(in);
+	const int rc = fe_submit(ctx, in ? &f : nullptr, nullptr, 0);
+	return rc != VGSDF_OK ? rc : fe_wait(ctx, rects_out, out_bytes, n_segments, nullptr);
+}
+
+int vgsdf_outlines_submit(vgsdf_ctx *ctx, const vgsdf_outlines *in, uint8_t *out_bitmaps, size_t out_capacity)
+{
+	FeInput f;
+	if (in)
+		f = fe_input(in);
+	return fe_submit(ctx, in ? &f : nullptr, out_bitmaps, out_bitmaps ? out_capacity : 0);
+}
+
+int vgsdf_outlines_submit_packed(vgsdf_ctx *ctx, const vgsdf_outlines_packed *in, uint8_t *out_bitmaps, size_t out_capacity)
+{
+	FeInput f;
+	if (in) {
+		f.n_glyphs = in->n_glyphs;
+		f.cmd_off = in->cmd_off;
+		f.scale = in->scale;
+		f.shift_x = in->shift_x;
+		f.dat_off = in->dat_off;
+		f.kinds = in->kinds;
+		f.coords = in->coords;
+		f.pbf_pre = in->pbf_pre;
+		f.pbf_fix = in->pbf_fix;
+		f.packed = true;
+	}
+	return fe_submit(ctx, in ? &f : nullptr, out_bitmaps, out_bitmaps ? out_capacity : 0);
+}
+
+int vgsdf_outlines_submit_glyf(vgsdf_ctx *ctx, const vgsdf_outlines_glyf *in, uint8_t *out_bitmaps, size_t out_capacity)
+{
+	FeInput f;
+	if (in) {
+		f.n_glyphs = in->n_glyphs;
+		f.cmd_off = in->cmd_off;
+		f.scale = in->scale;
+		f.shift_x = in->shift_x;
+		f.pbf_pre = in->pbf_pre;
+		f.pbf_fix = in->pbf_fix;
+		f.glyf = true;
+		f.parts = in->parts;
+		f.n_parts = in->n_parts;
+		f.bytes = in->bytes;
+		f.n_bytes = in->n_bytes;
+	}
+	return fe_submit(ctx, in ? &f : nullptr, out_bitmaps, out_bitmaps ? out_capacity : 0);
+}
+
+int vgsdf_outlines_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, uint64_t *n_segments, int *rendered)
+{
+	return fe_wait(ctx, rects_out, out_bytes, n_segments, rendered);
+}
+
+int vgsdf_outlines_peek(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, int *in_place)
+{
+	if (out_bytes)
+		*out_bytes = 0;
+	if (in_place)
+		*in_place = 0;
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!ctx->fe || !ctx->fe->pend.active) {
+		ctx->err = "vgsdf_outlines_peek: nothing was submitted";
+		return VGSDF_E_ARG;
+	}
+	FrontEnd &fe = *ctx->fe;
+	const FePending &p = fe.pend;
+	if (p.n == 0)
+		return VGSDF_OK;
+	if (!rects_out) {
+		ctx->err = "vgsdf_outlines: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	(void)hipSetDevice(ctx->device);
+	FE_TRY(hipEventSynchronize(ctx->ev_rects));
+	std::memcpy(rects_out, fe.h_rects.p, sizeof(vgsdf_rect) * (size_t)p.n);
+	vgsdf::PlanHeader hdr;
+	std::memcpy(&hdr, (const uint8_t *)fe.h_rects.p + p.hdr_off, sizeof hdr);
+	if (out_bytes)
+		*out_bytes = hdr.out_bytes;
+	// the raster behind the plan runs over the whole list and stores through the caller's own (page-locked) buffer
+	if (in_place)
+		*in_place = p.spec && p.spec_direct && hdr.ok != 0 && hdr.error == 0;
+	fe.peeked = true;
+	return VGSDF_OK;
+}
+
+int vgsdf_outlines_pbf_positions(vgsdf_ctx *ctx, uint64_t *bitmap_at)
+{
+	if (!ctx || !bitmap_at)
+		return VGSDF_E_ARG;
+	if (!ctx->fe || !(ctx->fe->prepared || (ctx->fe->pend.active && ctx->fe->peeked)) || ctx->fe->pend.d_pbf_fix == nullptr) {
+		ctx->err = "vgsdf_outlines_pbf_positions: the last batch was not submitted with pbf_pre / pbf_fix";
+		return VGSDF_E_ARG;
+	}
+	const FePending &p = ctx->fe->pend;
+	std::memcpy(bitmap_at, (const uint8_t *)ctx->fe->h_rects.p + p.at_off, 8 * (size_t)p.n);
+	return VGSDF_OK;
+}
+
+int vgsdf_outlines_render_into(vgsdf_ctx *ctx, const vgsdf_outlines *in, vgsdf_rect *rects_out, uint8_t *out_bitmaps,
+                               size_t out_capacity, uint64_t *out_bytes, uint64_t *n_segments, int *rendered)
+{
+	if (ctx && (!rendered || (in && in->n_glyphs && !rects_out))) {
+		ctx->err = "vgsdf_outlines_render_into: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	FeInput f;
+	if (in)
+		f = fe_input(in);
+	const int rc = fe_submit(ctx, in ? &f : nullptr, out_bitmaps, out_bitmaps ? out_capacity : 0);
+	return rc != VGSDF_OK ? rc : fe_wait(ctx, rects_out, out_bytes, n_segments, rendered);
+}
+
+int vgsdf_outlines_render(vgsdf_ctx *ctx, uint8_t *out_bitmaps)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!ctx->fe || !ctx->fe->prepared) {
+		ctx->err = "vgsdf_outlines_render: call vgsdf_outlines_prepare first";
+		return VGSDF_E_ARG;
+	}
+	FrontEnd &fe = *ctx->fe;
+	if (fe.n_glyphs == 0 || fe.out_bytes == 0)
+		return VGSDF_OK;
+	if (!out_bitmaps) {
+		ctx->err = "vgsdf_outlines_render: NULL output";
+		return VGSDF_E_ARG;
+	}
+	static const bool trace = std::getenv("VGSDF_TRACE") != nullptr;
+	const double t0 = fe_now();
+	(void)hipSetDevice(ctx->device);
+	FE_TRY(fe.out.ensure((size_t)fe.out_bytes + 16)); // (the one-submission form may have rendered elsewhere)
+	fe.batch.d_out = (uint8_t *)fe.out.p;
+	int rc = vgsdf_batch_launch(ctx, &fe.batch);
+	if (rc != VGSDF_OK)
+		return rc;
+	rc = vgsdf_batch_download(ctx, &fe.batch, out_bitmaps);
+	if (trace)
+		std::fprintf(stderr, "[vgsdf] render: launch+D2H+sync %.3f ms\n", (fe_now() - t0) * 1e3);
+	return rc;
+}
+
+int vgsdf_outlines_segments(vgsdf_ctx *ctx, uint32_t *seg_off, double *sx, double *sy, double *ex, double *ey)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!ctx->fe || !ctx->fe->prepared) {
+		ctx->err = "vgsdf_outlines_segments: call vgsdf_outlines_prepare first";
+		return VGSDF_E_ARG;
+	}
+	FrontEnd &fe = *ctx->fe;
+	(void)hipSetDevice(ctx->device);
+	std::vector<vgsdf::GlyphDesc> hd;
+	if (fe.n_glyphs && seg_off) {
+		hd.resize(fe.n_glyphs);
+		FE_TRY(hipMemcpyAsync(hd.data(), fe.descs.p, sizeof(vgsdf::GlyphDesc) * (size_t)fe.n_glyphs, hipMemcpyDeviceToHost, ctx->stream));
+	}
+	std::vector<double> rec;
+	if (fe.n_segs && sx && sy && ex && ey) {
+		rec.resize(4 * (size_t)fe.n_segs);
+		FE_TRY(hipMemcpyAsync(rec.data(), fe.seg.p, 32 * (size_t)fe.n_segs, hipMemcpyDeviceToHost, ctx->stream));
+	}
+	FE_TRY(hipStreamSynchronize(ctx->stream));
+	for (uint32_t g = 0; g < (uint32_t)hd.size(); g++) {
+		seg_off[g] = hd[g].seg_off;
+		seg_off[g + 1] = hd[g].seg_off + hd[g].n_seg;
+	}
+	for (size_t i = 0; i * 4 < rec.size(); i++) { // records -> the four arrays of the C ABI
+		sx[i] = rec[4 * i];
+		sy[i] = rec[4 * i + 1];
+		ex[i] = rec[4 * i + 2];
+		ey[i] = rec[4 * i + 3];
+	}
+	return VGSDF_OK;
+}
+
+} // extern "C"

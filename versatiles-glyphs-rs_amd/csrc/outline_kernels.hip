@@ -33,6 +33,7 @@
 
 #include "outline_kernels.h"
 #include "sdf_kernels.h"
+#include "work_plan.h"
 
 namespace vgsdf {
 
@@ -875,20 +876,12 @@ __global__ __launch_bounds__(64) void outline_rings(const OutlineCmd *__restrict
 // ---------------------------------------------------------------------------------------
 // plan: ONE workgroup.  From the rects: the glyph descriptors (segment and output offsets: exclusive sums),
 // the raster's work list and the totals the host reads back together with the rects.  The list follows the
-// host's policy for resident batches (vgsdf_device.cpp, build_descs_and_tiles): class (main kernel / brute
+// policy the host's planner of resident batches follows too (work_plan.h): class (main kernel / brute
 // force), span length T per glyph, heaviest workgroup first (counting sort over 512 logarithmic weight
 // buckets; the order inside a bucket is whatever the atomics give: it only shapes the schedule).
 // ---------------------------------------------------------------------------------------
 constexpr int kPlanThreads = 1024;
 constexpr int kPlanBuckets = 512;
-
-__device__ __forceinline__ uint32_t plan_bucket(uint32_t wgt) // bucket 0 = heaviest
-{
-	if (wgt < 16u)
-		return 511u - wgt;
-	const uint32_t e = 31u - (uint32_t)__builtin_clz(wgt);      // 4..31
-	return 511u - ((e - 3u) * 16u + ((wgt >> (e - 4u)) & 15u)); // 16..463 -> descending
-}
 
 // block-wide exclusive sum of one value per thread (1024 threads = 16 waves); returns the exclusive prefix, sets total
 __device__ __forceinline__ unsigned long long block_exclusive_sum(unsigned long long v, unsigned long long *s_wave /*[17]*/,
@@ -985,28 +978,14 @@ __global__ __launch_bounds__(kPlanThreads) void outline_plan(const OutlineRect *
 	if (tid == 0)
 		s_carry[0] = s_carry[1] = 0;
 	__syncthreads();
-	// rows touched by T consecutive tiles, times the (odd-padded) row stride, must fit the winding histogram
-	auto fits = [&](uint32_t w, uint32_t T) { return (unsigned long long)((256u * T - 2u) / w + 2u) * ((unsigned long long)w + 2u) <= delta_cap; };
-	// class (0 main / 1 brute), span length and span count of a glyph
+	// class (0 main / 1 brute), span length, span count and weight of a glyph (work_plan.h: the policy shared with the host)
 	auto classify = [&](const OutlineRect &r, uint32_t &cls, uint32_t &T, uint32_t &nspans, uint32_t &weight) {
 		const unsigned long long px = r.has_raster ? (unsigned long long)r.w * r.h : 0ull;
 		cls = 0, T = 1, nspans = 0, weight = 0;
 		if (px == 0 || px > 0xFFFFFFFFull - 256ull) // (a bitmap beyond 2^32 pixels is an error of the batch: no entries)
 			return;
-		const uint32_t nseg = r.n_segments;
-		if (!fits(r.w, 1) || nseg >= (1u << 24)) {
-			cls = 1;
-		} else if (span_list) {
-			const uint32_t chunks = (nseg + 255u) / 256u;
-			const uint32_t t_hi = min(span_max, max(1u, span_budget / max(chunks, 1u)));
-			for (T = t_hi; T > 1; T--)
-				if (fits(r.w, T))
-					break;
-		}
-		const unsigned long long t256 = (px + 255ull) >> 8;
-		nspans = (uint32_t)((t256 + T - 1) / T);
-		const unsigned long long wgt = (unsigned long long)nseg * (t256 < T ? t256 : T);
-		weight = wgt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)wgt;
+		const GlyphPlan gp = plan_glyph(px, r.w, r.n_segments, span_list != 0, delta_cap, span_max, span_budget);
+		cls = gp.cls, T = gp.T, nspans = gp.n_spans, weight = gp.weight;
 	};
 	// pass A: descriptors (exclusive sums of segments and output bytes), span histogram.  Every thread takes a
 	// contiguous run of glyphs: one block-wide scan of the runs' sums, then a running sum inside the run.
@@ -1092,7 +1071,7 @@ __global__ __launch_bounds__(kPlanThreads) void outline_plan(const OutlineRect *
 			descs[g] = d;
 			so += segs;
 			if (nspans)
-				atomicAdd(&s_hist[cls][plan_bucket(weight)], nspans);
+				atomicAdd(&s_hist[cls][weight_bucket(weight)], nspans);
 		};
 		if (kept) {
 #pragma unroll
@@ -1149,7 +1128,7 @@ __global__ __launch_bounds__(kPlanThreads) void outline_plan(const OutlineRect *
 	auto entries = [&](uint32_t g, const OutlineRect &r, uint32_t cls, uint32_t T, uint32_t nspans, uint32_t weight) {
 		if (!nspans)
 			return;
-		uint32_t at = atomicAdd(&s_hist[cls][plan_bucket(weight)], nspans);
+		uint32_t at = atomicAdd(&s_hist[cls][weight_bucket(weight)], nspans);
 		const unsigned long long px = (unsigned long long)r.w * r.h;
 		for (unsigned long long p = 0; p < px; p += 256ull * T) {
 			const uint32_t left = (uint32_t)((px - p + 255ull) >> 8);

@@ -1,0 +1,48 @@
+// upload_layout.h — byte offsets of the single-block upload forms.  include/vgsdf.h states the two layouts for callers
+// (vgsdf_outlines_packed, vgsdf_outlines_glyf); this header is their one computation, used by the host façade that
+// builds such a block (csrc/host/renderer.hpp, MergedOutlines) and by the front-end that recognises one, sizes its
+// device copy and derives the device views from it (outline_front_end.cpp).  Plain C++: no HIP here.
+#pragma once
+#include <stddef.h>
+
+#include "../../include/vgsdf.h"
+
+namespace vgsdf {
+
+// scale f64[n] | shift_x f64[n] | cmd_off u32[n + 1]: the head of both forms, and all of the per-glyph arrays of the
+// plain command form
+struct GlyphArraysLayout {
+	size_t scale = 0, shift_x, cmd_off, end;
+	explicit GlyphArraysLayout(size_t n) : shift_x(8 * n), cmd_off(16 * n), end(16 * n + 4 * (n + 1)) {}
+};
+
+// ... | dat_off u32[n + 1] | pad to 8 | coords f32[n_floats] | kinds u8[n_cmds] [| pad to 4 | pbf_pre u32[n] | pbf_fix u8[n]]
+struct PackedBlockLayout : GlyphArraysLayout {
+	size_t dat_off, arrays_end; // arrays_end: behind the per-glyph arrays
+	size_t coords, kinds, pbf_pre, pbf_fix, bytes;
+	PackedBlockLayout(size_t n, size_t n_cmds, size_t n_floats, bool with_pbf) : GlyphArraysLayout(n)
+	{
+		dat_off = end;
+		arrays_end = dat_off + 4 * (n + 1);
+		coords = (arrays_end + 7) / 8 * 8;
+		kinds = coords + 4 * n_floats;
+		pbf_pre = (kinds + n_cmds + 3) / 4 * 4;
+		pbf_fix = pbf_pre + 4 * n;
+		bytes = with_pbf ? pbf_fix + n : kinds + n_cmds;
+	}
+};
+
+// ... | pad to 8 | parts vgsdf_glyf_part[n_parts] | bytes u8[n_bytes] (a multiple of 4) [| pbf_pre u32[n] | pbf_fix u8[n]]
+struct GlyfBlockLayout : GlyphArraysLayout {
+	size_t parts, glyf_bytes, pbf_pre, pbf_fix, bytes;
+	GlyfBlockLayout(size_t n, size_t n_parts, size_t n_bytes, bool with_pbf) : GlyphArraysLayout(n)
+	{
+		parts = (end + 7) / 8 * 8;
+		glyf_bytes = parts + sizeof(vgsdf_glyf_part) * n_parts;
+		pbf_pre = glyf_bytes + n_bytes;
+		pbf_fix = pbf_pre + 4 * n;
+		bytes = with_pbf ? pbf_fix + n : pbf_pre;
+	}
+};
+
+} // namespace vgsdf
