@@ -96,6 +96,28 @@ void vg_manager_set_in_place_pbf(vg_manager *m, int on);
  * 0 = the host's reader records the callbacks (CFF / CFF2 fonts always take that way; so does a batch in which the device
  * finds a malformed entry).  Same bytes either way. */
 void vg_manager_set_glyf_on_device(vg_manager *m, int on);
+/* Resident fonts, 0 (default) / 1.  With 1 a group of the dispatcher whose faces all have `glyf` outlines (and were not
+ * refused by the device's decoder before) is submitted by (font, glyph id) — vgsdf_outlines_submit_resident, 33 bytes per
+ * glyph — against device copies of the faces that the RENDERER owns: one per (device, face), uploaded on first use,
+ * shared by the two contexts of a lane and by the lanes of vg_renderer_new_multi that share a device, freed with the
+ * renderer.  Every entry point that runs the dispatcher takes it (vg_manager_render_glyphs, _render_glyphs_to,
+ * _render_blocks, every lane form); vg_manager_render_block and vg_render_glyph stay as they are.  A face without a resident
+ * form, or one that does not fit the renderer's budget, sends its groups through the glyf form; a malformed entry falls
+ * back to the host's reader exactly as there (vg_timings.glyf_fallbacks).  Same bytes either way.
+ * vg_renderer_set_resident_budget: HBM the device copies may take per device (default 1 GiB, a setting; no eviction).
+ * vg_renderer_preload_fonts: uploads every face of the manager now, for callers that want the first request warm; returns
+ * the bytes put on the devices, -1 on error.
+ * vg_manager_resident_stats: of the last render. */
+void vg_manager_set_resident_fonts(vg_manager *m, int on);
+void vg_renderer_set_resident_budget(vg_renderer *r, uint64_t bytes_per_device);
+long long vg_renderer_preload_fonts(vg_renderer *r, const vg_manager *m);
+typedef struct {
+	uint64_t groups;         /* groups submitted in the resident form */
+	uint64_t fonts_uploaded; /* faces uploaded during the render */
+	uint64_t font_bytes;     /* ... and what they occupy on the device */
+	uint64_t block_bytes;    /* bytes of the submissions' upload blocks */
+} vg_resident_stats;
+int vg_manager_resident_stats(const vg_manager *m, vg_resident_stats *out);
 /* How a renderer of several device lanes (vg_renderer_new_multi) splits a run: -1 / 2 (default) the hybrid plan — whole
  * (font, block) tasks per lane, manager.rs:86-97's unit, and the heaviest blocks' glyphs split between lanes until the lanes'
  * estimated raster cost is within 4 % of the mean; 1 whole tasks only; 0 glyph-level shards of every font (every block
@@ -204,6 +226,30 @@ typedef struct vg_glyf_batch vg_glyf_batch;
 vg_glyf_batch *vg_manager_record_glyf_parts(const vg_manager *m, const char *font_id);
 int vg_glyf_batch_view(const vg_glyf_batch *b, vgsdf_outlines_glyf *view, const uint32_t **ids, const uint32_t **advances);
 void vg_glyf_batch_free(vg_glyf_batch *b);
+
+/* Host halves of the resident-font form (vgsdf_font_create / vgsdf_outlines_submit_resident), no device needed.
+ * vg_manager_resident_font_desc: the description of file `file_index` of a font id (wrapper.files order) — the leaves of
+ * EVERY glyph id of the face, listed by the walk and the checks that record the parts above, every simple glyph's arrays
+ * stored once.  Built on first use, kept with the face: the pointers in *desc stay valid as long as the manager holds the
+ * font.  -1: unknown font / file, a face without `glyf` outlines, or a face past the bounds of the form (more than 2^22
+ * leaves, a glyph of more than 2^26 command slots, a store past what 32-bit offsets address).
+ * vg_manager_record_resident: what a submission of every glyph of the font id names — per glyph the file (font_of, an index
+ * into the font id's files) and the glyph id, scale / shift_x, and ids[i] / advances[i] as above.  NULL when a file of the
+ * font has no resident form.  Valid until vg_resident_batch_free. */
+typedef struct vg_resident_batch vg_resident_batch;
+typedef struct {
+	uint32_t n_glyphs, n_files;
+	const uint16_t *font_of;  /* [n_glyphs] */
+	const uint16_t *glyph_id; /* [n_glyphs] */
+	const double *scale;      /* [n_glyphs] */
+	const double *shift_x;    /* [n_glyphs] */
+	const uint32_t *ids;      /* [n_glyphs] code points */
+	const uint32_t *advances; /* [n_glyphs] */
+} vg_resident_view;
+int vg_manager_resident_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_desc *desc);
+vg_resident_batch *vg_manager_record_resident(const vg_manager *m, const char *font_id);
+int vg_resident_batch_view(const vg_resident_batch *b, vg_resident_view *view);
+void vg_resident_batch_free(vg_resident_batch *b);
 
 /* Hand-encoder of the glyphs PBF (src/protobuf/glyphs.rs:66-70) for already rendered
  * glyphs; bitmaps[i] may be NULL when !has_bitmap. Returns needed size. */

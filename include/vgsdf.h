@@ -241,6 +241,56 @@ typedef struct {
 	const uint8_t *pbf_fix;       /* [n_glyphs] or NULL */
 } vgsdf_outlines_glyf;
 int vgsdf_outlines_submit_glyf(vgsdf_ctx *ctx, const vgsdf_outlines_glyf *in, uint8_t *out_bitmaps, size_t out_capacity);
+/*
+ * Resident fonts: a font's outlines are uploaded ONCE and live in HBM; a submission then names glyphs by (font, glyph id)
+ * and carries 33 bytes per glyph instead of the parts and a copy of the `glyf` arrays.  Output is the glyf form's, byte for byte.
+ *
+ * vgsdf_font_desc describes a face: for every glyph id its LEAVES — the simple glyphs it is drawn from, records as the parts of
+ * vgsdf_outlines_glyf, except that cmd_at counts from the glyph's FIRST slot (the leaves of one glyph tile [0, its slot count)
+ * in order) and byte_off points into `bytes`, where every simple glyph's endPtsOfContours + flag / x / y arrays are stored
+ * once, 4-aligned, however many composites name it.
+ * vgsdf_font_create validates the description on the host (leaf_off ascending from 0 to n_leaves, every leaf's byte range
+ * 4-aligned inside `bytes`, the leaves tiling their glyph's slots, n_contours > 0, plain 0 or 1; VGSDF_E_ARG otherwise), copies
+ * the three arrays to the device and returns when they are there: the description may be freed at once.  The font belongs to the
+ * context's DEVICE, not to the context: every context of that device may name it from then on (a font of another device is
+ * VGSDF_E_ARG in a submission).  vgsdf_font_free is the caller's to time: no submission that names the font may be in
+ * flight (submitted and not yet waited for) on any context.  vgsdf_font_device_bytes: what the font occupies on the device.
+ */
+typedef struct vgsdf_font vgsdf_font;
+typedef struct {
+	uint32_t n_glyph_ids;          /* numGlyphs of the face */
+	uint32_t n_leaves, n_bytes;    /* n_bytes a multiple of 4 */
+	const uint32_t *leaf_off;      /* [n_glyph_ids + 1] glyph id -> its leaves; ascending, leaf_off[0] = 0 */
+	const vgsdf_glyf_part *leaves; /* [n_leaves] */
+	const uint8_t *bytes;          /* [n_bytes] */
+} vgsdf_font_desc;
+int vgsdf_font_create(vgsdf_ctx *ctx, const vgsdf_font_desc *in, vgsdf_font **out);
+int vgsdf_font_free(vgsdf_ctx *ctx, vgsdf_font *font);
+uint64_t vgsdf_font_device_bytes(const vgsdf_font *font);
+/* A submission that names its glyphs: glyph g is glyph id glyph_id[g] of fonts[font_of[g]].  A glyph id past the face or a
+ * font_of past n_fonts is VGSDF_E_ARG before anything runs; a glyph id without leaves is a glyph without outline (no slots,
+ * has_raster = 0); glyph ids may repeat and come in any order.  The host's share is two table reads and two additions per
+ * glyph (the running sums of leaves and command slots); it gathers the arrays below into one page-locked block of its own
+ *   scale f64[n] | shift_x f64[n] | cmd_off u32[n + 1] | part_off u32[n + 1] | glyph_id u16[n] | font_of u16[n] | pbf_pre u32[n] | pbf_fix u8[n]
+ * followed by 32 bytes of device addresses per font, which ONE kernel reads: it copies the per-glyph arrays and expands the
+ * leaves into this submission's parts on the device (leaf k of glyph g becomes part part_off[g] + k with
+ * cmd_at = cmd_off[g] + leaf.cmd_at).  The decoder then reads every part's bytes from the resident store of its font and the
+ * front-end runs on as in the glyf form — the same number of launches.  The caller's arrays need not outlive the call.
+ * A malformed entry fails the batch with VGSDF_E_GLYF in vgsdf_outlines_wait, as in the glyf form.  Collected with
+ * vgsdf_outlines_wait; _peek, _pbf_positions and _segments work behind it as behind any other form.
+ * vgsdf_outlines_resident_upload_bytes: the size of the block the last resident submission of the context uploaded. */
+typedef struct {
+	uint32_t n_glyphs, n_fonts;
+	const vgsdf_font *const *fonts; /* [n_fonts] */
+	const uint16_t *font_of;        /* [n_glyphs] index into fonts */
+	const uint16_t *glyph_id;       /* [n_glyphs] */
+	const double *scale;            /* [n_glyphs] as in vgsdf_outlines_glyf */
+	const double *shift_x;          /* [n_glyphs] */
+	const uint32_t *pbf_pre;        /* [n_glyphs] or NULL, as in vgsdf_outlines_packed */
+	const uint8_t *pbf_fix;         /* [n_glyphs] or NULL */
+} vgsdf_outlines_resident;
+int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity);
+uint64_t vgsdf_outlines_resident_upload_bytes(const vgsdf_ctx *ctx);
 int vgsdf_outlines_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, uint64_t *n_segments, int *rendered);
 /* Between submit and wait: blocks until the front-end's results are on the host — they leave the device right behind the
  * plan kernel, on a stream of their own, while flattening and raster are still running — and reports the rects and

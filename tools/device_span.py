@@ -1,6 +1,7 @@
 """Device span of one submission (HIP events around upload ... last kernel, VGSDF_TRACE) and end-to-end time of the same run,
 config 2 (Noto Sans Regular) or another workload, over N warm runs: median / min of both.  Development aid.
-    python tools/device_span.py [noto_regular|noto_all|fira|many] [runs]"""
+    python tools/device_span.py [noto_regular|noto_all|fira|many] [runs] [resident]
+`resident`: with resident fonts on (the first run, which builds the tables and uploads the fonts, is printed separately)."""
 import os
 import re
 import subprocess
@@ -25,7 +26,9 @@ from conftest import FIRA, NOTO, load_product, noto_files  # noqa: E402
 vg = load_product()
 which = sys.argv[1] if len(sys.argv) > 1 else "noto_regular"
 runs = int(sys.argv[2]) if len(sys.argv) > 2 else 60
+resident = "resident" in sys.argv[3:]
 m = vg.FontManager(True)
+m.set_resident_fonts(resident)
 if which == "many":
     for i, p in enumerate([FIRA] + list(noto_files())):
         m.add_font_with_name(f"Font {i:02d}", [p])
@@ -39,5 +42,7 @@ for i in range(runs):
     ts.append(time.perf_counter() - t0)
 tm = m.timings()
 w = sorted(ts[runs // 3:])
+if resident:
+    print(f"resident fonts: first run {ts[0] * 1e6:.0f} us (tables + font upload), last run's stats {m.resident_stats()}")
 print(f"{which}: {tm['glyphs']} glyphs, end to end min {w[0] * 1e6:.0f} us ({tm['glyphs'] / w[0] / 1e6:.2f} M glyphs/s), median {w[len(w) // 2] * 1e6:.0f} us; "
       f"phases of the last run: " + " ".join(f"{k[:-2]}={v * 1e6:.0f}" for k, v in tm.items() if k.endswith("_s")))

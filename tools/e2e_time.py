@@ -1,4 +1,5 @@
-"""end-to-end (fonts -> PBF bytes) timing of the host pipeline + GPU (development aid)"""
+"""end-to-end (fonts -> PBF bytes) timing of the host pipeline + GPU (development aid)
+    python tools/e2e_time.py [noto_regular|noto_all|many] [fe|host] [blocks per batch] [resident]"""
 import sys, time
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -12,6 +13,7 @@ r = vg.Renderer.new_precise(0) if vg.device_count() else vg.Renderer.new_dummy()
 fe = len(sys.argv) > 2 and sys.argv[2] == "fe"
 for th in (4, 16):
     m = vg.FontManager(True); m.set_threads(th, int(sys.argv[3]) if len(sys.argv) > 3 else 0); m.set_device_front_end(fe)
+    m.set_resident_fonts("resident" in sys.argv[2:])
     if many:
         from conftest import FIRA
         for i, p in enumerate([FIRA] + list(noto_files())):

@@ -36,6 +36,11 @@ struct vg_glyf_batch {
 	vg::GlyfPartsBatch b;
 	std::vector<uint32_t> ids, advances;
 };
+struct vg_resident_batch {
+	vg::ResidentBatch b;
+	std::vector<uint32_t> ids, advances;
+	uint32_t n_files = 0;
+};
 struct vg_glyph_batch {
 	vg::PackedBatch b;
 	std::vector<uint32_t> ids;
@@ -128,6 +133,23 @@ void vg_manager_free(vg_manager *m) { delete m; }
 void vg_manager_set_device_front_end(vg_manager *m, int on) { m->m.set_device_front_end(on != 0); }
 void vg_manager_set_in_place_pbf(vg_manager *m, int on) { m->m.set_in_place_pbf(on != 0); }
 void vg_manager_set_glyf_on_device(vg_manager *m, int on) { m->m.set_glyf_on_device(on != 0); }
+void vg_manager_set_resident_fonts(vg_manager *m, int on) { m->m.set_resident_fonts(on != 0); }
+void vg_renderer_set_resident_budget(vg_renderer *r, uint64_t bytes_per_device) { r->r->set_resident_budget(bytes_per_device); }
+long long vg_renderer_preload_fonts(vg_renderer *r, const vg_manager *m)
+{
+	try {
+		return (long long)m->m.preload_resident_fonts(*r->r);
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_resident_stats(const vg_manager *m, vg_resident_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_resident_stats{t.resident_groups, t.resident_fonts_uploaded, t.resident_font_bytes, t.resident_block_bytes};
+	return 0;
+}
 void vg_manager_set_lane_form(vg_manager *m, int form) { m->m.set_lane_form(form < 0 || form > 2 ? -1 : form); }
 void vg_manager_set_threads(vg_manager *m, unsigned threads, unsigned blocks_per_batch)
 {
@@ -595,6 +617,63 @@ int vg_glyf_batch_view(const vg_glyf_batch *b, vgsdf_outlines_glyf *view, const 
 	return 0;
 }
 void vg_glyf_batch_free(vg_glyf_batch *b) { delete b; }
+
+int vg_manager_resident_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_desc *desc)
+{
+	try {
+		std::string err;
+		const vg::ResidentTable *t = file_index < 0 ? nullptr : m->m.resident_table(font_id, (size_t)file_index, &err);
+		if (!t || !desc) {
+			g_err = err.empty() ? "vg_manager_resident_font_desc: bad argument" : err;
+			return -1;
+		}
+		desc->n_glyph_ids = (uint32_t)t->leaf_off.size() - 1;
+		desc->n_leaves = (uint32_t)t->leaves.size();
+		desc->n_bytes = (uint32_t)t->bytes.size();
+		desc->leaf_off = t->leaf_off.data();
+		desc->leaves = reinterpret_cast<const vgsdf_glyf_part *>(t->leaves.data());
+		desc->bytes = t->bytes.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+vg_resident_batch *vg_manager_record_resident(const vg_manager *m, const char *font_id)
+{
+	try {
+		auto b = std::make_unique<vg_resident_batch>();
+		std::string err;
+		if (!m->m.record_resident(font_id, b->b, &err)) {
+			g_err = err;
+			return nullptr;
+		}
+		for (const vg::GlyphJob &j : b->b.jobs) {
+			b->ids.push_back(j.id);
+			b->advances.push_back(j.advance);
+		}
+		b->n_files = (uint32_t)m->m.fonts().at(font_id).files().size();
+		return b.release();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return nullptr;
+	}
+}
+int vg_resident_batch_view(const vg_resident_batch *b, vg_resident_view *view)
+{
+	if (!b || !view)
+		return -1;
+	view->n_glyphs = (uint32_t)b->b.jobs.size();
+	view->n_files = b->n_files;
+	view->font_of = b->b.font_of.data();
+	view->glyph_id = b->b.glyph_id.data();
+	view->scale = b->b.scale.data();
+	view->shift_x = b->b.shift_x.data();
+	view->ids = b->ids.data();
+	view->advances = b->advances.data();
+	return 0;
+}
+void vg_resident_batch_free(vg_resident_batch *b) { delete b; }
 
 long vg_pbf_encode(const char *name, const char *range, const vg_pbf_glyph *glyphs, const uint8_t *const *bitmaps,
                    int n, uint8_t *out, size_t cap)

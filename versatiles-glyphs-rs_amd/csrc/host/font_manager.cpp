@@ -503,6 +503,49 @@ bool FontManager::record_glyf_parts(const std::string &font_id, GlyfPartsBatch &
 	return true;
 }
 
+bool FontManager::record_resident(const std::string &font_id, ResidentBatch &out, std::string *err) const
+{
+	auto it = fonts().find(font_id);
+	if (it == fonts().end()) {
+		if (err)
+			*err = "unknown font id " + font_id;
+		return false;
+	}
+	out.clear();
+	const auto &files = it->second.files();
+	std::map<const FontFileEntry *, uint16_t> file_of;
+	for (size_t k = 0; k < files.size(); k++) {
+		if (k > 0xFFFF || !files[k]->face().resident_table().ok) {
+			if (err)
+				*err = "font " + font_id + ": a file without `glyf` outlines, or past the bounds of the resident form (composite fan-out)";
+			return false;
+		}
+		file_of.emplace(files[k].get(), (uint16_t)k);
+	}
+	for (const GlyphBlock &b : task_blocks(it->first, it->second))
+		for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE; ci++)
+			if (const FontFileEntry *f = b.glyphs[ci])
+				Renderer::record_resident(f->face(), file_of.at(f), b.start_index + ci, out);
+	return true;
+}
+
+const ResidentTable *FontManager::resident_table(const std::string &font_id, size_t file_index, std::string *err) const
+{
+	auto it = fonts().find(font_id);
+	if (it == fonts().end() || file_index >= it->second.files().size()) {
+		if (err)
+			*err = "unknown font id " + font_id + ", or a file index past its files";
+		return nullptr;
+	}
+	const ResidentTable &t = it->second.files()[file_index]->face().resident_table();
+	if (!t.ok) {
+		if (err)
+			*err = "font " + font_id + ": the file has no `glyf` outlines, or is past the bounds of the resident form (composite fan-out)";
+		return nullptr;
+	}
+	return &t;
+}
+
 // ---- glyph-level sharding ---------------------------------------------------------------
 namespace {
 
@@ -1228,6 +1271,10 @@ void FontManager::render_tasks_multi(Writer &writer, const Renderer &renderer, i
 		timings_.pixels += ct.pixels;
 		timings_.segments += ct.segments;
 		timings_.glyf_groups += ct.glyf_groups;
+		timings_.resident_groups += ct.resident_groups;
+		timings_.resident_fonts_uploaded += ct.resident_fonts_uploaded;
+		timings_.resident_font_bytes += ct.resident_font_bytes;
+		timings_.resident_block_bytes += ct.resident_block_bytes;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1258,6 +1305,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->device_front_end_ = device_front_end_;
 		c->in_place_pbf_ = in_place_pbf_;
 		c->glyf_on_device_ = glyf_on_device_;
+		c->resident_fonts_ = resident_fonts_;
 		c->batch_blocks_ = batch_blocks_;
 		c->batch_blocks_set_ = batch_blocks_set_;
 		c->set_threads(per_lane);
@@ -1331,6 +1379,10 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		timings_.pixels += ct.pixels;
 		timings_.segments += ct.segments;
 		timings_.glyf_groups += ct.glyf_groups;
+		timings_.resident_groups += ct.resident_groups;
+		timings_.resident_fonts_uploaded += ct.resident_fonts_uploaded;
+		timings_.resident_font_bytes += ct.resident_font_bytes;
+		timings_.resident_block_bytes += ct.resident_block_bytes;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1511,12 +1563,117 @@ void FontManager::fe_layout_common(const std::vector<Todo> &tasks, FeGroup &G)
 		}
 }
 
-void FontManager::fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf)
+// The group's glyphs by name (vgsdf_outlines_resident): the faces' outlines are on the device, so a worker's share per
+// glyph is the cmap and hmtx lookups — no composite is walked, no font byte copied.  Same slices, same merge in task order.
+bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane)
+{
+	constexpr uint32_t kSlice = 64;
+	ThreadPool &tp = pool();
+	const double t0 = now_s();
+	MergedOutlines &m = G.m;
+	// the faces of the group's fonts (tasks of one font follow each other) and their device copies
+	m.fonts.clear();
+	std::vector<std::pair<const FontFileEntry *, uint16_t>> index; // sorted by address (this call only): face -> font_of
+	const std::string *last = nullptr;
+	for (size_t t = G.g0; t < G.g1; t++) {
+		if (tasks[t].name == last)
+			continue;
+		last = tasks[t].name;
+		auto it = fonts().find(*last);
+		if (it == fonts().end())
+			return false;
+		for (const auto &file : it->second.files()) {
+			if (m.fonts.size() >= 0xFFFF)
+				return false;
+			uint64_t uploaded = 0;
+			const vgsdf_font *f = renderer.resident_font(lane, file->face().resident_table(), &uploaded);
+			if (!f)
+				return false;
+			if (uploaded) {
+				timings_.resident_fonts_uploaded++;
+				timings_.resident_font_bytes += uploaded;
+			}
+			index.emplace_back(file.get(), (uint16_t)m.fonts.size());
+			m.fonts.push_back(f);
+		}
+	}
+	std::sort(index.begin(), index.end());
+	auto font_of = [&](const FontFileEntry *f) {
+		return std::lower_bound(index.begin(), index.end(), std::make_pair(f, (uint16_t)0))->second;
+	};
+	std::vector<OSlice> &slices = G.slices;
+	fe_make_slices(tasks, G, kSlice);
+	for (Worker &w : workers_)
+		w.rlocal.clear();
+	tp.run(slices.size(), [&](size_t i, unsigned wid) {
+		OSlice &s = slices[i];
+		Worker &w = workers_[wid];
+		s.worker = wid;
+		s.job0 = (uint32_t)w.rlocal.jobs.size();
+		const GlyphBlock &blk = tasks[s.task].block;
+		const FontFileEntry *prev = nullptr;
+		uint16_t prev_at = 0;
+		for (uint32_t ci = G.slice_ci[i]; ci < G.slice_ci[i] + kSlice; ci++)
+			if (const FontFileEntry *f = blk.glyphs[ci]) {
+				if (f != prev) {
+					prev = f;
+					prev_at = font_of(f);
+				}
+				Renderer::record_resident(f->face(), prev_at, blk.start_index + ci, w.rlocal);
+			}
+		s.job1 = (uint32_t)w.rlocal.jobs.size();
+	}, true);
+	const double t1 = now_s();
+	timings_.tessellate_s += t1 - t0;
+	uint32_t n_jobs = 0;
+	for (OSlice &s : slices) {
+		s.g_job = n_jobs;
+		n_jobs += s.job1 - s.job0;
+	}
+	G.n_jobs = n_jobs;
+	m.jobs.resize(n_jobs);
+	G.in_place = in_place_pbf_;
+	m.layout_resident(n_jobs, G.in_place);
+	tp.run(slices.size(), [&](size_t i, unsigned) {
+		const OSlice &s = slices[i];
+		const ResidentBatch &l = workers_[s.worker].rlocal;
+		for (uint32_t j = s.job0; j < s.job1; j++) {
+			const uint32_t g = s.g_job + (j - s.job0);
+			m.jobs[g] = l.jobs[j];
+			m.scale[g] = l.scale[j];
+			m.shift_x[g] = l.shift_x[j];
+			m.glyph_id[g] = l.glyph_id[j];
+			m.font_of[g] = l.font_of[j];
+			if (m.pbf_fix) {
+				m.pbf_pre[g] = 0;
+				m.pbf_fix[g] = pbf_fix_of(l.jobs[j].id, l.jobs[j].advance);
+			}
+		}
+	}, true);
+	fe_layout_common(tasks, G);
+	timings_.pack_s += now_s() - t1;
+	return true;
+}
+
+uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
+{
+	uint64_t uploaded = 0;
+	for (size_t r = 0; r < renderer.n_devices(); r++)
+		for (const auto &kv : fonts())
+			for (const auto &file : kv.second.files())
+				if (file->face().has_glyf_outlines())
+					(void)renderer.device_lane(r).resident_font(0, file->face().resident_table(), &uploaded);
+	return uploaded;
+}
+
+void FontManager::fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf, const Renderer *renderer, int lane)
 {
 	if (allow_glyf && glyf_on_device_) {
 		bool all_glyf = true;
 		for (size_t t = G.g0; t < G.g1 && all_glyf; t++)
 			all_glyf = tasks[t].block.all_glyf && !glyf_refused_.count(tasks[t].name);
+		if (all_glyf && resident_fonts_ && renderer && fe_record_resident(tasks, G, *renderer, lane))
+			return;
 		if (all_glyf) {
 			if (fe_record_glyf(tasks, G))
 				return;
@@ -1836,13 +1993,18 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 		G.g0 = groups[k].first;
 		G.g1 = groups[k].second;
 		mark("record+pack >", k);
-		fe_record(tasks, G);
+		fe_record(tasks, G, true, &renderer, (int)(k & 1));
 		mark("submit >", k);
 		const double t = now_s();
 		if (G.n_jobs) {
 			timings_.fe_groups++;
 			timings_.fe_max_group_glyphs = std::max<uint64_t>(timings_.fe_max_group_glyphs, G.n_jobs);
-			if (G.m.glyf) {
+			if (G.m.resident) {
+				uint64_t block = 0;
+				renderer.submit_outlines((int)(k & 1), G.m.view_resident(), G.out, &block);
+				timings_.resident_groups++;
+				timings_.resident_block_bytes += block;
+			} else if (G.m.glyf) {
 				renderer.submit_outlines((int)(k & 1), G.m.view_glyf(), G.out);
 				timings_.glyf_groups++;
 			} else

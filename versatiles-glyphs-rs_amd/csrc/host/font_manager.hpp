@@ -146,6 +146,9 @@ struct RenderTimings {
 	uint64_t blocks = 0, glyphs = 0, rasters = 0, pixels = 0, segments = 0, pbf_bytes = 0;
 	uint64_t glyf_groups = 0, glyf_fallbacks = 0; // device front-end: groups decoded from `glyf` arrays / re-recorded on the host
 	uint64_t fe_groups = 0, fe_max_group_glyphs = 0; // the dispatcher's groups that held glyphs (one submission each), the largest's glyphs
+	// resident fonts: groups submitted by (font, glyph id), faces uploaded during the run and their bytes on the device, bytes of
+	// the submissions' upload blocks
+	uint64_t resident_groups = 0, resident_fonts_uploaded = 0, resident_font_bytes = 0, resident_block_bytes = 0;
 };
 
 class FontManager {
@@ -219,11 +222,21 @@ public:
 	// glyf fonts through the device front-end: true (default; VG_GLYF_ON_DEVICE=0 in the environment changes it) = the
 	// device decodes the glyphs' `glyf` arrays, false = the host's reader records the callbacks.  Same bytes either way.
 	void set_glyf_on_device(bool on) { glyf_on_device_ = on; }
+	// Resident fonts (default off): a group whose faces all have `glyf` outlines and a resident form is submitted by
+	// (font, glyph id) against the renderer's device copies of the faces (uploaded on first use); everything else as ever
+	void set_resident_fonts(bool on) { resident_fonts_ = on; }
+	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
+	// returns the bytes put on the devices
+	uint64_t preload_resident_fonts(const Renderer &renderer) const;
 	// a renderer with several device lanes: -1 (default) = whole (font, block) tasks per lane unless there are fewer than four
 	// non-empty blocks per lane, 0 = always glyph-level shards of every font (+ merge), 1 = always whole tasks.  Same bytes.
 	void set_lane_form(int form) { lane_form_ = form; }
 	// every glyph of a font id in the form the device's glyf decoder takes (glyf fonts only; tests, inspection)
 	bool record_glyf_parts(const std::string &font_id, GlyfPartsBatch &out, std::string *err) const;
+	// resident-font form: what a submission of every glyph of the font names, and the description of one of its files
+	// (nullptr: unknown font / file, or a face without a resident form)
+	bool record_resident(const std::string &font_id, ResidentBatch &out, std::string *err) const;
+	const ResidentTable *resident_table(const std::string &font_id, size_t file_index, std::string *err) const;
 
 private:
 	struct Todo {
@@ -254,6 +267,7 @@ private:
 		GlyphBatch local;
 		PackedOutlineBatch olocal;
 		GlyfPartsBatch plocal;
+		ResidentBatch rlocal;
 		char pad[128];
 	};
 	// One process, N devices (renderer.n_devices() > 1): the glyphs of every font are dealt to the device lanes by
@@ -351,7 +365,10 @@ private:
 		uint32_t n_jobs = 0;
 	};
 	FeGroup fe_group_[2]; // two groups in flight: one on the GPU, one being recorded / encoded
-	void fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf = true);
+	// renderer / lane: whose device copies of the fonts a resident group names (nullptr: no resident form for this call)
+	void fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf = true, const Renderer *renderer = nullptr, int lane = 0);
+	// false: a face of the group has no resident form or does not fit the renderer's budget — the glyf form takes the group
+	bool fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane);
 	bool fe_record_glyf(const std::vector<Todo> &tasks, FeGroup &G); // false: not a batch for the device's decoder (fan-out past 32-bit offsets)
 	// fonts (by id) one of whose groups the device's glyf decoder refused (VGSDF_E_GLYF) or whose parts passed the batch bounds:
 	// later groups and runs record them with the host's reader at once instead of paying the double path again; cleared
@@ -371,6 +388,7 @@ private:
 	bool in_place_pbf_ = true;
 	int lane_form_ = -1;
 	bool glyf_on_device_ = glyf_on_device_default(); // glyf fonts: the device decodes the glyphs' arrays (VG_GLYF_ON_DEVICE=0 / set_glyf_on_device(false): the host does)
+	bool resident_fonts_ = false;
 	bool device_front_end_ = true; // HIP renderer: flatten on the GPU unless switched off
 	std::map<std::string, FontWrapper> fonts_; // reference: HashMap (arbitrary order); sorted here
 	bool parallel_;

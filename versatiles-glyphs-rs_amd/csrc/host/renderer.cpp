@@ -159,6 +159,8 @@ std::shared_ptr<Renderer> Renderer::new_multi(const std::vector<int> &devices, s
 		std::shared_ptr<Renderer> p = new_precise(devices[i], err);
 		if (!p)
 			return nullptr;
+		p->resident_ = r->resident_; // lanes that share a device share the device copies of the fonts
+		p->owns_resident_ = false;
 		r->peers_.push_back(std::move(p));
 	}
 	return r;
@@ -203,6 +205,16 @@ std::string Renderer::reduce_path() const
 
 Renderer::~Renderer()
 {
+	if (owns_resident_ && ctx_) { // (the peers and their contexts are still there: members go after this body)
+		for (auto &kv : resident_->fonts)
+			for (size_t i = 0; i < n_devices(); i++)
+				if (device_lane(i).device_ == kv.first.first) {
+					vgsdf_font_free(device_lane(i).ctx_, kv.second);
+					break;
+				}
+		resident_->fonts.clear();
+		resident_->bytes.clear();
+	}
 	if (ctx2_)
 		vgsdf_destroy(ctx2_);
 	if (ctx_)
@@ -347,6 +359,27 @@ bool Renderer::record_parts(const Face &face, uint32_t index, GlyfPartsBatch &ba
 	return true;
 }
 
+bool Renderer::record_resident(const Face &face, uint16_t file, uint32_t index, ResidentBatch &batch)
+{
+	if (index > 0x10FFFF || (index >= 0xD800 && index <= 0xDFFF)) // renderer.rs:104
+		return false;
+	const auto glyph_id = face.glyph_index(index); // :106
+	if (!glyph_id)
+		return false;
+	const double scale = (double)GLYPH_SIZE / (double)face.units_per_em(); // :107
+	const double advance_float = (double)face.glyph_hor_advance(*glyph_id).value_or(0) * scale * 0.95; // :115
+	const uint32_t advance = to_u32(std::round(advance_float));                                          // :116
+	GlyphJob job;
+	job.id = index;
+	job.advance = advance;
+	batch.jobs.push_back(job);
+	batch.font_of.push_back(file);
+	batch.glyph_id.push_back(*glyph_id); // (:109-111: the outline is on the device already)
+	batch.scale.push_back(scale);
+	batch.shift_x.push_back(((double)advance - advance_float) / 2.0); // :130
+	return true;
+}
+
 vgsdf_ctx *Renderer::lane_ctx(int lane) const
 {
 	if (lane == 0)
@@ -397,6 +430,75 @@ void Renderer::submit_outlines(int lane, const vgsdf_outlines_glyf &v, HostBuffe
 		lane_mu_[lane].unlock();
 		throw;
 	}
+}
+
+void Renderer::submit_outlines(int lane, const vgsdf_outlines_resident &v, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const
+{
+	if (mode_ != Mode::Hip)
+		throw std::runtime_error("render_outlines needs the HIP renderer (the device front-end has no CPU form)");
+	lane &= 1;
+	vgsdf_ctx *c = lane_ctx(lane);
+	lane_mu_[lane].lock();
+	try {
+		if (out.capacity() == 0)
+			out.ensure((size_t)v.n_glyphs * 480 + 16384);
+		std::lock_guard<std::mutex> lock(mu_);
+		if (vgsdf_outlines_submit_resident(c, &v, out.data(), out.capacity()) != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_outlines_submit_resident: ") + vgsdf_last_error(c));
+		if (block_bytes)
+			*block_bytes = vgsdf_outlines_resident_upload_bytes(c);
+	} catch (...) {
+		lane_mu_[lane].unlock();
+		throw;
+	}
+}
+
+const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint64_t *uploaded_bytes) const
+{
+	if (mode_ != Mode::Hip || !t.ok)
+		return nullptr;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	const auto key = std::make_pair(device_, t.serial);
+	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
+		return it->second;
+	// (what vgsdf_font_create will allocate, to within its rounding: leaves | bytes | leaf_off)
+	const uint64_t want = sizeof(vgsdf_glyf_part) * (uint64_t)t.leaves.size() + t.bytes.size() + 4 * (uint64_t)t.leaf_off.size();
+	if (rf.bytes[device_] + want > rf.budget)
+		return nullptr;
+	vgsdf_font_desc d;
+	d.n_glyph_ids = (uint32_t)t.leaf_off.size() - 1;
+	d.n_leaves = (uint32_t)t.leaves.size();
+	d.n_bytes = (uint32_t)t.bytes.size();
+	d.leaf_off = t.leaf_off.data();
+	d.leaves = reinterpret_cast<const vgsdf_glyf_part *>(t.leaves.data());
+	d.bytes = t.bytes.data();
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	vgsdf_font *f = nullptr;
+	{
+		std::lock_guard<std::mutex> lock(mu_);
+		if (vgsdf_font_create(c, &d, &f) != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_font_create: ") + vgsdf_last_error(c));
+	}
+	const uint64_t got = vgsdf_font_device_bytes(f);
+	rf.fonts.emplace(key, f);
+	rf.bytes[device_] += got;
+	if (uploaded_bytes)
+		*uploaded_bytes += got;
+	return f;
+}
+
+void Renderer::set_resident_budget(uint64_t bytes_per_device)
+{
+	std::lock_guard<std::mutex> lock(resident_->mu);
+	resident_->budget = bytes_per_device;
+}
+
+uint64_t Renderer::resident_bytes(int device) const
+{
+	std::lock_guard<std::mutex> lock(resident_->mu);
+	auto it = resident_->bytes.find(device);
+	return it == resident_->bytes.end() ? 0 : it->second;
 }
 
 bool Renderer::peek_outlines(int lane, std::vector<vgsdf_rect> &rects, uint64_t &out_bytes, uint32_t n_glyphs,

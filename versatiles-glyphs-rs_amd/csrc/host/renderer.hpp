@@ -14,6 +14,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdlib>
+#include <map>
 #include <memory>
 #include <new>
 #include <mutex>
@@ -227,6 +228,22 @@ struct GlyfPartsBatch {
 	}
 };
 
+// What is recorded for a submission that names its glyphs (vgsdf_outlines_resident): per glyph its metrics, the file of the
+// font id that draws it and its glyph id there — no outline is walked, no font byte copied.
+struct ResidentBatch {
+	std::vector<GlyphJob> jobs;
+	std::vector<uint16_t> font_of, glyph_id;
+	std::vector<double> scale, shift_x;
+	void clear()
+	{
+		jobs.clear();
+		font_of.clear();
+		glyph_id.clear();
+		scale.clear();
+		shift_x.clear();
+	}
+};
+
 // The merged batch handed to the device, in the compact upload form (vgsdf_outlines_packed: one kind byte per
 // command plus the coordinates its kind carries).  All arrays live back to back in ONE page-locked block, in the
 // order vgsdf.h names for a single-copy upload: scale | shift_x | cmd_off | dat_off | (pad to 8) | coords | kinds
@@ -246,12 +263,49 @@ struct MergedOutlines {
 	vgsdf_glyf_part *parts = nullptr;
 	uint8_t *glyf_bytes = nullptr;
 	uint32_t n_parts = 0, n_glyf_bytes = 0;
+	// the form that names its glyphs (vgsdf_outlines_resident): the per-glyph arrays where ResidentBlockLayout has them
+	bool resident = false;
+	uint16_t *glyph_id = nullptr, *font_of = nullptr;
+	std::vector<const vgsdf_font *> fonts; // the device copies of the group's faces
+	void layout_resident(uint32_t jobs_n, bool with_pbf)
+	{
+		n_jobs = jobs_n;
+		glyf = false;
+		resident = true;
+		const vgsdf::ResidentBlockLayout at(jobs_n, fonts.size(), with_pbf);
+		blob.ensure(at.bytes + 16);
+		uint8_t *b = blob.data();
+		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
+		pbf_fix = with_pbf ? b + at.pbf_fix : nullptr;
+		scale = reinterpret_cast<double *>(b + at.scale);
+		shift_x = reinterpret_cast<double *>(b + at.shift_x);
+		glyph_id = reinterpret_cast<uint16_t *>(b + at.glyph_id);
+		font_of = reinterpret_cast<uint16_t *>(b + at.font_of);
+		cmd_off = dat_off = nullptr;
+		coords = nullptr;
+		kinds = nullptr;
+	}
+	vgsdf_outlines_resident view_resident() const
+	{
+		vgsdf_outlines_resident o;
+		o.n_glyphs = n_jobs;
+		o.n_fonts = (uint32_t)fonts.size();
+		o.fonts = fonts.data();
+		o.font_of = font_of;
+		o.glyph_id = glyph_id;
+		o.scale = scale;
+		o.shift_x = shift_x;
+		o.pbf_pre = pbf_pre;
+		o.pbf_fix = pbf_fix;
+		return o;
+	}
 	void layout_glyf(uint32_t jobs_n, uint32_t parts_n, uint32_t bytes_n, bool with_pbf)
 	{
 		n_jobs = jobs_n;
 		n_parts = parts_n;
 		n_glyf_bytes = bytes_n; // (a multiple of 4: every part's bytes are padded)
 		glyf = true;
+		resident = false;
 		const vgsdf::GlyfBlockLayout at(jobs_n, parts_n, bytes_n, with_pbf);
 		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
@@ -285,6 +339,7 @@ struct MergedOutlines {
 	{
 		n_jobs = jobs_n;
 		glyf = false;
+		resident = false;
 		const vgsdf::PackedBlockLayout at(jobs_n, n_cmds, n_floats, with_pbf);
 		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
@@ -385,6 +440,8 @@ public:
 	// ... and for the device's glyf decoder: nothing is decoded, the glyph's simple glyphs are appended as parts
 	// (glyf fonts only: face.has_glyf_outlines())
 	static bool record_parts(const Face &face, uint32_t index, GlyfPartsBatch &batch);
+	// the same for a resident face: the glyph is named, not walked (file = the face's index among the font id's files)
+	static bool record_resident(const Face &face, uint16_t file, uint32_t index, ResidentBatch &batch);
 	// Device front-end + raster for a recorded batch: fills rects (one per job) and `out` with
 	// the bitmaps of the glyphs that have a raster, packed in job order.  Hip mode only.
 	void render_outlines(const vgsdf_outlines &batch, std::vector<vgsdf_rect> &rects, HostBuffer<uint8_t> &out,
@@ -395,6 +452,16 @@ public:
 	// must stay untouched between the two calls; a lane is held from submit to wait.
 	void submit_outlines(int lane, const vgsdf_outlines_packed &batch, HostBuffer<uint8_t> &out) const;
 	void submit_outlines(int lane, const vgsdf_outlines_glyf &batch, HostBuffer<uint8_t> &out) const;
+	// ... and for glyphs named by (font, glyph id) of resident fonts; *block_bytes: what the submission uploaded
+	void submit_outlines(int lane, const vgsdf_outlines_resident &batch, HostBuffer<uint8_t> &out, uint64_t *block_bytes = nullptr) const;
+	// Resident fonts: the device copy of a face (vgsdf_font), one per (device, face), created on first use through the
+	// lane's context, shared by the two contexts of a lane and by the lanes of a multi-device renderer that share a device,
+	// freed with the renderer.  nullptr: the face has no resident form, or its copy would pass the budget of the device
+	// (set_resident_budget, default 1 GiB; no eviction) — the caller takes the glyf form.  *uploaded_bytes (may be NULL) is
+	// raised by what this call put on the device (0: the copy was there).
+	const vgsdf_font *resident_font(int lane, const ResidentTable &table, uint64_t *uploaded_bytes = nullptr) const;
+	void set_resident_budget(uint64_t bytes_per_device);
+	uint64_t resident_bytes(int device) const; // what the renderer's resident fonts occupy on a device
 	void wait_outlines(int lane, std::vector<vgsdf_rect> &rects, HostBuffer<uint8_t> &out, uint64_t &out_bytes,
 	                   uint64_t &n_segments, uint32_t n_glyphs, std::vector<uint64_t> *pbf_at = nullptr) const;
 	// Between the two: the front-end's results as soon as they are on the host, while the raster is still running
@@ -425,6 +492,14 @@ private:
 	mutable std::mutex lane_mu_[2];     // held from submit_outlines to wait_outlines
 	vgsdf_ctx *lane_ctx(int lane) const;
 	std::vector<std::shared_ptr<Renderer>> peers_; // device lanes 1 .. N-1 of a multi-device renderer
+	struct ResidentFonts { // of a renderer and its peers
+		std::mutex mu;
+		std::map<std::pair<int, uint64_t>, vgsdf_font *> fonts; // (device, the face's serial number) -> its copy there
+		std::map<int, uint64_t> bytes;                          // per device
+		uint64_t budget = 1ull << 30;
+	};
+	std::shared_ptr<ResidentFonts> resident_ = std::make_shared<ResidentFonts>();
+	bool owns_resident_ = true; // (a peer shares its primary's table and leaves the freeing to it)
 };
 
 } // namespace vg

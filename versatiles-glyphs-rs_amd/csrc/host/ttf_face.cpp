@@ -8,6 +8,8 @@
 #include "cff.hpp"
 
 #include <algorithm>
+#include <atomic>
+#include <map>
 #include <cstdlib>
 #include <cstring>
 
@@ -845,6 +847,37 @@ namespace {
 // Sink of the parts walk: what walk_simple checks BEFORE it touches the flag / coordinate arrays is checked here, with
 // the same outcome (false: ttf-parser returns None, the walk of a composite stops); the arrays themselves are copied
 // as they stand and checked where they are decoded (a mismatch there fails the batch: vgsdf.h, VGSDF_E_GLYF).
+// what a simple glyph's entry says about itself before its arrays are looked at: shared by the sinks of the parts walk
+struct PartShape {
+	enum Kind { Fail, Nothing, Part }; // Fail: ttf-parser returns None here; Nothing: a lone point, no part, the walk goes on
+	size_t cur = 0, ends = 0, arrays = 0; // cur: first byte behind the instructions; ends / arrays: bytes to copy (0 when !fits)
+	uint32_t n_points = 0;
+	bool fits = false;
+	Kind measure(Bytes body, uint16_t n_contours)
+	{
+		if (!body.has(0, (size_t)n_contours * 2))
+			return Fail;
+		const uint16_t last_end = body.u16((size_t)(n_contours - 1) * 2);
+		if (last_end == 0xFFFF)
+			return Fail;
+		n_points = (uint32_t)last_end + 1;
+		if (n_points == 1)
+			return Nothing; // a lone point yields nothing
+		cur = (size_t)n_contours * 2;
+		if (!body.has(cur, 2))
+			return Fail;
+		cur += 2 + body.u16(cur); // instructions: not needed on the device
+		if (cur > body.size())
+			return Fail;
+		// (an entry longer than the device's decoder takes is not copied — one damaged `loca` entry could otherwise make every
+		// glyph that names it carry megabytes: without its arrays the part fails there and the batch goes to the host's reader)
+		constexpr size_t kMaxEntry = 32 * 1024;
+		fits = (size_t)n_contours * 2 + (body.size() - cur) <= kMaxEntry;
+		ends = fits ? (size_t)n_contours * 2 : 0;
+		arrays = fits ? body.size() - cur : 0;
+		return Part;
+	}
+};
 struct PartsSink {
 	std::vector<GlyfPart> &parts;
 	std::vector<uint8_t> &bytes;
@@ -864,25 +897,12 @@ struct PartsSink {
 	}
 	bool part(Bytes body, uint16_t n_contours, float a, float b, float c, float d, float e, float f, bool plain)
 	{
-		if (!body.has(0, (size_t)n_contours * 2))
-			return false;
-		const uint16_t last_end = body.u16((size_t)(n_contours - 1) * 2);
-		if (last_end == 0xFFFF)
-			return false;
-		const uint32_t n_points = (uint32_t)last_end + 1;
-		if (n_points == 1)
-			return true; // a lone point yields nothing
-		size_t cur = (size_t)n_contours * 2;
-		if (!body.has(cur, 2))
-			return false;
-		cur += 2 + body.u16(cur); // instructions: not needed on the device
-		if (cur > body.size())
-			return false;
-		// (an entry longer than the device's decoder takes is not copied — one damaged `loca` entry could otherwise make every
-		// glyph that names it carry megabytes: without its arrays the part fails there and the batch goes to the host's reader)
-		constexpr size_t kMaxEntry = 32 * 1024;
-		const bool fits = (size_t)n_contours * 2 + (body.size() - cur) <= kMaxEntry;
-		const size_t ends = fits ? (size_t)n_contours * 2 : 0, arrays = fits ? body.size() - cur : 0;
+		PartShape sh;
+		if (const PartShape::Kind k = sh.measure(body, n_contours); k != PartShape::Part)
+			return k == PartShape::Nothing;
+		const size_t cur = sh.cur, ends = sh.ends, arrays = sh.arrays;
+		const uint32_t n_points = sh.n_points;
+		const bool fits = sh.fits;
 		if ((uint64_t)bytes.size() + ends + arrays + 4 > max_batch_bytes() || (uint64_t)slots + n_points + 2ull * n_contours > kMaxBatchSlots ||
 		    parts.size() >= kMaxBatchParts) {
 			if (overflow)
@@ -920,6 +940,87 @@ bool Face::glyph_parts(uint16_t gid, std::vector<GlyfPart> &parts, std::vector<u
 	PartsSink sink{parts, bytes, slots, overflow};
 	GlyfWalker<PartsSink, true> w{*this, sink};
 	return w.walk(*g, 0, Affine{});
+}
+
+namespace {
+// Sink of the resident table's walk: PartsSink's checks (PartShape), but the arrays of a simple glyph are stored once —
+// entries are told apart by where they lie in the font (a damaged `loca` may make many glyph ids name one entry)
+struct ResidentSink {
+	ResidentTable &t;
+	std::map<std::pair<const uint8_t *, size_t>, uint32_t> &stored; // (entry body, its length) -> byte_off
+	uint32_t slots = 0; // of the glyph being walked
+	bool overflow = false;
+	bool part(Bytes body, uint16_t n_contours, float a, float b, float c, float d, float e, float f, bool plain)
+	{
+		PartShape sh;
+		if (const PartShape::Kind k = sh.measure(body, n_contours); k != PartShape::Part)
+			return k == PartShape::Nothing;
+		GlyfPart p;
+		p.byte_len = (uint32_t)(sh.ends + sh.arrays);
+		p.cmd_at = slots;
+		p.cmd_cap = sh.n_points + 2u * n_contours; // (PartsSink::part)
+		p.n_contours = n_contours;
+		p.plain = plain ? 1u : 0u;
+		p.a = a, p.b = b, p.c = c, p.d = d, p.e = e, p.f = f;
+		if ((uint64_t)slots + p.cmd_cap > ResidentTable::kMaxGlyphSlots || t.leaves.size() >= ResidentTable::kMaxLeaves) {
+			overflow = true;
+			return false;
+		}
+		const auto key = std::make_pair(body.data(), body.size());
+		if (auto it = stored.find(key); it != stored.end()) {
+			p.byte_off = it->second;
+		} else {
+			const size_t at = t.bytes.size(), padded = ((size_t)p.byte_len + 3) & ~(size_t)3;
+			if ((uint64_t)at + padded > ResidentTable::kMaxBytes) {
+				overflow = true;
+				return false;
+			}
+			p.byte_off = (uint32_t)at;
+			t.bytes.resize(at + padded); // (zero padding)
+			if (sh.fits) {
+				std::memcpy(t.bytes.data() + at, body.data(), sh.ends);
+				std::memcpy(t.bytes.data() + at + sh.ends, body.data() + sh.cur, sh.arrays);
+			}
+			stored.emplace(key, p.byte_off);
+		}
+		slots += p.cmd_cap;
+		t.leaves.push_back(p);
+		return true;
+	}
+};
+} // namespace
+
+const ResidentTable &Face::resident_table() const
+{
+	ResidentCell &cell = *resident_;
+	std::call_once(cell.once, [&] {
+		ResidentTable &t = cell.table;
+		if (!has_glyf_outlines())
+			return;
+		std::map<std::pair<const uint8_t *, size_t>, uint32_t> stored;
+		const uint32_t n = num_glyphs_;
+		t.leaf_off.assign(1, 0);
+		t.slot_off.assign(1, 0);
+		uint64_t slot_sum = 0;
+		for (uint32_t gid = 0; gid < n; gid++) {
+			ResidentSink sink{t, stored};
+			if (const auto g = glyph_data((uint16_t)gid)) {
+				GlyfWalker<ResidentSink, true> w{*this, sink};
+				(void)w.walk(*g, 0, Affine{});
+			}
+			slot_sum += sink.slots;
+			if (sink.overflow || slot_sum > 0xFFFFFFFFull) {
+				t = ResidentTable{};
+				return;
+			}
+			t.leaf_off.push_back((uint32_t)t.leaves.size());
+			t.slot_off.push_back((uint32_t)slot_sum);
+		}
+		static std::atomic<uint64_t> next_serial{1};
+		t.serial = next_serial.fetch_add(1);
+		t.ok = true;
+	});
+	return cell.table;
 }
 
 bool Face::outline_glyph_packed(uint16_t gid, std::vector<uint8_t> &kinds, std::vector<float> &coords) const

@@ -12,6 +12,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <memory>
+#include <mutex>
 #include <optional>
 #include <string>
 #include <utility>
@@ -40,6 +41,20 @@ struct GlyfPart {
 	uint32_t cmd_at, cmd_cap;
 	uint32_t n_contours, plain;
 	float a, b, c, d, e, f;
+};
+
+// A face's outlines in the form that stays on the device (vgsdf_font_desc of include/vgsdf.h): the leaves — simple glyphs
+// with their accumulated transforms — of EVERY glyph id, and every simple glyph's arrays stored once however many
+// composites name it.  A leaf's cmd_at counts from its glyph's first slot.
+struct ResidentTable {
+	bool ok = false;                // false: the face has no resident form (not glyf, or past the bounds below)
+	uint64_t serial = 0;            // of the face, handed out when the table is built: what a renderer keys its device copy by
+	std::vector<uint32_t> leaf_off; // [numGlyphs + 1]
+	std::vector<uint32_t> slot_off; // [numGlyphs + 1] running sum of the glyphs' command slots (a host convenience: 64-bit safe below 2^32 by the bounds)
+	std::vector<GlyfPart> leaves;
+	std::vector<uint8_t> bytes;     // 4-aligned entries
+	// bounds: more leaves than 2^22, a glyph of more than 2^26 slots, or a store past what 32-bit offsets address
+	static constexpr uint64_t kMaxLeaves = 1ull << 22, kMaxGlyphSlots = 1ull << 26, kMaxBytes = (1ull << 32) - 4;
 };
 
 // Non-owning big-endian byte view with checked reads.
@@ -89,6 +104,9 @@ public:
 	// walk stops) when the batch would pass what its 32-bit offsets address (2^26 bytes / slots, 2^22 parts per recorder): a composite
 	// copies its simple glyphs once per leaf, so a small font can fan out to gigabytes — the caller then drops the glyf form.
 	bool glyph_parts(uint16_t glyph_id, std::vector<GlyfPart> &parts, std::vector<uint8_t> &bytes, uint32_t &slots, bool *overflow = nullptr) const;
+	// The resident form of the face: built once, on first use (thread-safe); the same walk and the same checks as
+	// glyph_parts, glyph id by glyph id, so a failing component leaves a glyph with the leaves recorded so far.
+	const ResidentTable &resident_table() const;
 	// ttf-parser's `tables().cmap.is_some()`; the reference refuses fonts without one (metadata.rs:104-107)
 	bool has_cmap() const { return has_cmap_; }
 	// glyph outlines this reader can emit: `glyf` + `loca`, or `CFF ` charstrings (ttf-parser's order: glyf first).
@@ -121,6 +139,11 @@ private:
 	bool loca_long_ = false, has_cmap_ = false, cff_unreadable_ = false;
 	std::shared_ptr<const CffTable> cff_;
 	size_t loca_entries_ = 0;
+	struct ResidentCell {
+		std::once_flag once;
+		ResidentTable table;
+	};
+	std::shared_ptr<ResidentCell> resident_ = std::make_shared<ResidentCell>(); // (shared by copies of the Face: same bytes)
 
 	template <class B, bool PARTS> friend struct GlyfWalker;
 };

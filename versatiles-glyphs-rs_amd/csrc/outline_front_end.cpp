@@ -42,6 +42,7 @@ struct FrontEnd {
 	uint32_t *flag_word() const { return (uint32_t *)((uint8_t *)flag.p + 16 * (size_t)flag_slot); }
 	uint32_t *next_flag_word() const { return (uint32_t *)((uint8_t *)flag.p + 16 * (size_t)(flag_slot ^ 1u)); }
 	FePending pend;
+	uint64_t resident_upload_bytes = 0; // block of the last vgsdf_outlines_resident submission
 	uint32_t n_glyphs = 0, n_cmds = 0, n_segs = 0;
 	uint64_t out_bytes = 0;
 	vgsdf_dbatch batch; // borrowed view over the buffers above
@@ -59,6 +60,18 @@ struct FrontEnd {
 		                  &h_rects, &h_stage})
 			b->release();
 	}
+};
+
+// A font resident on a device (vgsdf_font_create): one allocation leaves | bytes | leaf_off, and what the host needs per
+// glyph id to lay a submission out without looking at a leaf
+struct vgsdf_font {
+	int device = 0;
+	uint32_t n_glyph_ids = 0, n_leaves = 0, n_bytes = 0;
+	DevBuf store;
+	vgsdf::ResidentFontRef ref{};       // device addresses of the three arrays
+	std::vector<uint32_t> leaf_off;     // [n_glyph_ids + 1]
+	std::vector<uint32_t> slots;        // [n_glyph_ids] command slots of the glyph's leaves
+	uint32_t max_cap = 0, max_len = 0;  // the largest cmd_cap / byte_len among the leaves (the decoder's LDS is sized from them)
 };
 
 void fe_destroy(FrontEnd *fe)
@@ -176,6 +189,12 @@ struct FeInput {
 	uint32_t n_parts = 0;
 	const uint8_t *bytes = nullptr;
 	uint32_t n_bytes = 0;
+	// vgsdf_outlines_resident (glyf is set too: the decoder runs on parts — which the upload kernel expands on the device).
+	// The arrays above point into the block the library gathered in the context's page-locked staging buffer
+	bool resident = false;
+	uint32_t n_fonts = 0;
+	uint32_t res_max_cap = 0, res_max_len = 0; // over the fonts the submission names
+	bool res_scales_plain = true;
 };
 
 // ---- submit, step by step (fe_submit below keeps their order: it is part of the contract with the device) ----
@@ -204,7 +223,7 @@ static int fe_check_args(vgsdf_ctx *ctx, const FeInput *in, uint32_t &n_cmds, ui
 		ctx->err = "vgsdf_outlines: NULL command array";
 		return VGSDF_E_ARG;
 	}
-	if (in->glyf && ((in->n_parts && (!in->parts || !in->bytes)) || (in->n_bytes & 3u))) {
+	if (in->glyf && !in->resident && ((in->n_parts && (!in->parts || !in->bytes)) || (in->n_bytes & 3u))) {
 		ctx->err = "vgsdf_outlines_glyf: NULL parts / bytes, or n_bytes not a multiple of 4";
 		return VGSDF_E_ARG;
 	}
@@ -281,6 +300,7 @@ static int fe_validate(vgsdf_ctx *ctx, const FeInput *in, uint32_t n_cmds, FeFac
 struct FeUpload {
 	vgsdf::PackedBlockLayout pk; // (its head also serves the plain command form)
 	vgsdf::GlyfBlockLayout gl;
+	vgsdf::ResidentBlockLayout rs;
 	size_t arrays_bytes;          // scale | shift_x | cmd_off [| dat_off]
 	const uint8_t *block = nullptr; // the caller's arrays are ONE page-locked block in their form's layout: one copy
 	size_t block_bytes = 0;
@@ -294,7 +314,8 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 {
 	const uint32_t n = in->n_glyphs;
 	const bool pbf = in->pbf_fix != nullptr;
-	FeUpload up{vgsdf::PackedBlockLayout(n, n_cmds, n_floats, pbf), vgsdf::GlyfBlockLayout(n, in->n_parts, in->n_bytes, pbf), 0};
+	FeUpload up{vgsdf::PackedBlockLayout(n, n_cmds, n_floats, pbf), vgsdf::GlyfBlockLayout(n, in->n_parts, in->n_bytes, pbf),
+	            vgsdf::ResidentBlockLayout(n, in->n_fonts, pbf), 0};
 	up.arrays_bytes = in->packed ? up.pk.arrays_end : up.pk.end;
 	// the block is recognised by the caller's pointers: every array where the layout has it, counted from `scale`
 	const uint8_t *hb = (const uint8_t *)in->scale;
@@ -302,7 +323,10 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 	const vgsdf::PackedBlockLayout &pk = up.pk;
 	const vgsdf::GlyfBlockLayout &gl = up.gl;
 	bool single = false;
-	if (in->glyf) {
+	if (in->resident) { // (gathered by the library itself, in the context's page-locked staging buffer)
+		up.block_bytes = up.rs.bytes;
+		single = true;
+	} else if (in->glyf) {
 		up.block_bytes = gl.bytes;
 		single = at(in->shift_x, gl.shift_x) && at(in->cmd_off, gl.cmd_off) && at(in->parts, gl.parts) && at(in->bytes, gl.glyf_bytes) &&
 		         (!pbf || (at(in->pbf_pre, gl.pbf_pre) && at(in->pbf_fix, gl.pbf_fix)));
@@ -325,8 +349,10 @@ static int fe_reserve(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t 
 	FePending &p = fe.pend;
 	const uint32_t n = in->n_glyphs;
 	FE_TRY(fe.cmds.ensure(sizeof(vgsdf::OutlineCmd) * (size_t)(n_cmds + 1)));
-	FE_TRY(fe.meta.ensure((in->glyf ? up.gl.bytes : (up.block ? up.pk.bytes : up.arrays_bytes)) + 16));
-	FE_TRY(fe.h_stage.ensure(up.arrays_bytes + 16));
+	FE_TRY(fe.meta.ensure((in->resident ? up.rs.bytes + sizeof(vgsdf_glyf_part) * (size_t)in->n_parts
+	                                    : (in->glyf ? up.gl.bytes : (up.block ? up.pk.bytes : up.arrays_bytes))) + 16));
+	if (!in->resident) // (a resident submission's block lies there already)
+		FE_TRY(fe.h_stage.ensure(up.arrays_bytes + 16));
 	FE_TRY(fe.cmd_open.ensure((size_t)n_cmds + 1));
 	FE_TRY(fe.counts.ensure(4 * (size_t)(n_cmds + 1)));
 	FE_TRY(fe.pt_local.ensure(4 * ((size_t)n_cmds + n + 2)));
@@ -360,6 +386,27 @@ static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n
 	const vgsdf::GlyfBlockLayout &gl = up.gl;
 	uint8_t *dm = (uint8_t *)fe.meta.p;
 	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+	if (in->resident) {
+		// ONE kernel: the copy of the block and the expansion of the glyphs' leaves into parts behind it.  It reads the
+		// page-locked block itself; without a device mapping (or with VGSDF_COPY_KERNEL=0) the copy engine brings the block
+		// over first and the kernel reads that copy
+		const vgsdf::ResidentBlockLayout &rs = up.rs;
+		const void *src = up.mapped;
+		if (!src) {
+			FE_TRY(fe.coords.ensure(rs.bytes + 16));
+			FE_TRY(copy(fe.coords.p, up.block, rs.bytes));
+			src = fe.coords.p;
+		}
+		FE_KERNEL(vgsdf_resident_expand(src, dm, rs.bytes, (uint32_t)n, in->n_parts, in->n_fonts, pbf, dm + rs.bytes, st));
+		up.d_parts = dm + rs.bytes;
+		up.d_bytes = dm + rs.fonts; // (the fonts' stores: vgsdf_glyf_decode_resident)
+		if (pbf) {
+			p.d_pbf_pre = (const uint32_t *)(dm + rs.pbf_pre);
+			p.d_pbf_fix = dm + rs.pbf_fix;
+		}
+		fe.resident_upload_bytes = rs.bytes;
+		return VGSDF_OK;
+	}
 	if (up.mapped)
 		FE_KERNEL(vgsdf_copy_in(up.mapped, dm, up.block_bytes, st));
 	else if (up.block)
@@ -458,7 +505,10 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	static const char *fuse_env = std::getenv("VGSDF_FUSE_CONTEXT"); // (measurement switch)
 	if (fuse_env && fuse_env[0] == '0')
 		decode_makes_context = false;
-	if (in->glyf)
+	if (in->resident)
+		FE_KERNEL(vgsdf_glyf_decode_resident(up.d_parts, in->n_parts, up.d_bytes, (vgsdf::OutlineCmd *)fe.cmds.p, flagw, facts.glyf_max_cap,
+		                                     facts.glyf_max_len, decode_makes_context ? (uint8_t *)fe.cmd_open.p : nullptr, st));
+	else if (in->glyf)
 		FE_KERNEL(vgsdf_glyf_decode(up.d_parts, in->n_parts, up.d_bytes, (vgsdf::OutlineCmd *)fe.cmds.p, flagw, facts.glyf_max_cap, facts.glyf_max_len,
 		                            decode_makes_context ? (uint8_t *)fe.cmd_open.p : nullptr, st));
 	if (in->packed)
@@ -548,8 +598,14 @@ static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_
 	if (std::getenv("VGSDF_TRACE") != nullptr)
 		FE_TRY(hipEventRecord(ctx->ev0, ctx->stream));
 	FeFacts facts;
-	const bool validate_under_upload = up.mapped != nullptr; // (not one block uploaded by a kernel: validate first, as ever)
-	if (!validate_under_upload)
+	// (a resident submission was validated before its block was gathered, and its offsets are the library's own sums)
+	if (in->resident) {
+		facts.glyf_max_cap = in->res_max_cap;
+		facts.glyf_max_len = in->res_max_len;
+		facts.scales_plain = in->res_scales_plain;
+	}
+	const bool validate_under_upload = up.mapped != nullptr && !in->resident; // (not one block uploaded by a kernel: validate first, as ever)
+	if (!validate_under_upload && !in->resident)
 		if (int rc = fe_validate(ctx, in, n_cmds, facts); rc != VGSDF_OK)
 			return rc;
 	// error word of this submission (FrontEnd::flag_slot)
@@ -792,6 +848,202 @@ int vgsdf_outlines_submit_glyf(vgsdf_ctx *ctx, const vgsdf_outlines_glyf *in, ui
 		f.n_bytes = in->n_bytes;
 	}
 	return fe_submit(ctx, in ? &f : nullptr, out_bitmaps, out_bitmaps ? out_capacity : 0);
+}
+
+// ---- resident fonts ----
+
+int vgsdf_font_create(vgsdf_ctx *ctx, const vgsdf_font_desc *in, vgsdf_font **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->leaf_off || (in->n_leaves && !in->leaves) || (in->n_bytes && !in->bytes)) {
+		ctx->err = "vgsdf_font_create: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	const uint32_t n = in->n_glyph_ids;
+	if (n > 0x10000u || (in->n_bytes & 3u) || in->leaf_off[0] != 0 || in->leaf_off[n] != in->n_leaves) {
+		ctx->err = "vgsdf_font_create: more than 65536 glyph ids, n_bytes not a multiple of 4, or leaf_off does not run from 0 to n_leaves";
+		return VGSDF_E_ARG;
+	}
+	vgsdf_font *f = new (std::nothrow) vgsdf_font();
+	if (!f) {
+		ctx->err = "vgsdf_font_create: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	f->slots.assign(n, 0);
+	for (uint32_t g = 0; g < n; g++) {
+		const uint32_t l0 = in->leaf_off[g], l1 = in->leaf_off[g + 1];
+		if (l1 < l0 || l1 > in->n_leaves) {
+			ctx->err = "vgsdf_font_create: leaf_off not ascending";
+			delete f;
+			return VGSDF_E_ARG;
+		}
+		uint64_t slots = 0;
+		for (uint32_t i = l0; i < l1; i++) {
+			const vgsdf_glyf_part &lf = in->leaves[i];
+			if (lf.cmd_at != slots || (lf.byte_off & 3u) || lf.byte_off > in->n_bytes || lf.byte_len > in->n_bytes - lf.byte_off ||
+			    lf.n_contours == 0 || lf.plain > 1u) {
+				ctx->err = "vgsdf_font_create: the leaves of a glyph must tile its command slots from 0 in order, with 4-aligned byte ranges "
+				           "inside `bytes`, n_contours > 0 and plain 0 or 1";
+				delete f;
+				return VGSDF_E_ARG;
+			}
+			slots += lf.cmd_cap;
+			if (slots > 0x7FFFFFFFull) {
+				ctx->err = "vgsdf_font_create: a glyph of more than 2^31 - 1 command slots";
+				delete f;
+				return VGSDF_E_ARG;
+			}
+			f->max_cap = std::max(f->max_cap, lf.cmd_cap);
+			f->max_len = std::max(f->max_len, lf.byte_len);
+		}
+		f->slots[g] = (uint32_t)slots;
+	}
+	f->device = ctx->device;
+	f->n_glyph_ids = n;
+	f->n_leaves = in->n_leaves;
+	f->n_bytes = in->n_bytes;
+	f->leaf_off.assign(in->leaf_off, in->leaf_off + n + 1);
+	(void)hipSetDevice(ctx->device);
+	const size_t leaves_bytes = sizeof(vgsdf_glyf_part) * (size_t)in->n_leaves; // (a multiple of 16)
+	const size_t bytes_at = leaves_bytes, off_at = align_up(bytes_at + in->n_bytes, 16), total = off_at + 4 * ((size_t)n + 1);
+	auto fail = [&](hipError_t e, const char *what) {
+		ctx->err = std::string("vgsdf_font_create: ") + what + ": " + hipGetErrorString(e);
+		f->store.release();
+		delete f;
+		return e == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;
+	};
+	if (hipError_t e = f->store.ensure(total + 16); e != hipSuccess)
+		return fail(e, "hipMalloc");
+	uint8_t *d = (uint8_t *)f->store.p;
+	hipError_t e = leaves_bytes ? hipMemcpyAsync(d, in->leaves, leaves_bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+	if (e == hipSuccess && in->n_bytes)
+		e = hipMemcpyAsync(d + bytes_at, in->bytes, in->n_bytes, hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(d + off_at, in->leaf_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(ctx->stream); // the arrays are on the device when the call returns: every context may name the font
+	if (e != hipSuccess)
+		return fail(e, "upload");
+	f->ref.leaves = (uint64_t)(uintptr_t)d;
+	f->ref.bytes = (uint64_t)(uintptr_t)(d + bytes_at);
+	f->ref.leaf_off = (uint64_t)(uintptr_t)(d + off_at);
+	*out = f;
+	return VGSDF_OK;
+}
+
+int vgsdf_font_free(vgsdf_ctx *ctx, vgsdf_font *font)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!font)
+		return VGSDF_OK;
+	if (font->device != ctx->device) {
+		ctx->err = "vgsdf_font_free: the font lives on another device than the context";
+		return VGSDF_E_ARG;
+	}
+	(void)hipSetDevice(ctx->device);
+	font->store.release();
+	delete font;
+	return VGSDF_OK;
+}
+
+uint64_t vgsdf_font_device_bytes(const vgsdf_font *font) { return font ? (uint64_t)font->store.cap : 0; }
+
+uint64_t vgsdf_outlines_resident_upload_bytes(const vgsdf_ctx *ctx) { return ctx && ctx->fe ? ctx->fe->resident_upload_bytes : 0; }
+
+int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || (in->n_glyphs && (!in->fonts || !in->font_of || !in->glyph_id || !in->scale || !in->shift_x))) {
+		ctx->err = "vgsdf_outlines_resident: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if ((in->pbf_pre == nullptr) != (in->pbf_fix == nullptr)) {
+		ctx->err = "vgsdf_outlines: pbf_pre and pbf_fix come together (packed and glyf forms only)";
+		return VGSDF_E_ARG;
+	}
+	const uint32_t n = in->n_glyphs;
+	FeInput f;
+	f.n_glyphs = n;
+	f.glyf = true;
+	f.resident = true;
+	if (n == 0)
+		return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
+	if (in->n_fonts == 0 || in->n_fonts > 0x10000u) {
+		ctx->err = "vgsdf_outlines_resident: n_fonts must be 1 .. 65536";
+		return VGSDF_E_ARG;
+	}
+	for (uint32_t k = 0; k < in->n_fonts; k++)
+		if (!in->fonts[k] || in->fonts[k]->device != ctx->device) {
+			ctx->err = "vgsdf_outlines_resident: a NULL font, or a font of another device than the context's";
+			return VGSDF_E_ARG;
+		}
+	// every name before anything is touched
+	for (uint32_t g = 0; g < n; g++)
+		if (in->font_of[g] >= in->n_fonts || in->glyph_id[g] >= in->fonts[in->font_of[g]]->n_glyph_ids) {
+			ctx->err = "vgsdf_outlines_resident: font_of past n_fonts, or a glyph id past its face";
+			return VGSDF_E_ARG;
+		}
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->fe)
+		ctx->fe = new (std::nothrow) FrontEnd();
+	if (!ctx->fe) {
+		ctx->err = "vgsdf_outlines: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	FrontEnd &fe = *ctx->fe;
+	if (fe.pend.active) { // (its upload kernel may still be reading the staging block)
+		ctx->err = "vgsdf_outlines_submit: the previous submission of this context has not been waited for";
+		return VGSDF_E_ARG;
+	}
+	// the block: the caller's arrays gathered, the two running sums, the fonts' device addresses
+	const bool pbf = in->pbf_fix != nullptr;
+	const vgsdf::ResidentBlockLayout rs(n, in->n_fonts, pbf);
+	FE_TRY(fe.h_stage.ensure(rs.bytes + 16));
+	uint8_t *hb = (uint8_t *)fe.h_stage.p;
+	std::memcpy(hb + rs.scale, in->scale, 8 * (size_t)n);
+	std::memcpy(hb + rs.shift_x, in->shift_x, 8 * (size_t)n);
+	std::memcpy(hb + rs.glyph_id, in->glyph_id, 2 * (size_t)n);
+	std::memcpy(hb + rs.font_of, in->font_of, 2 * (size_t)n);
+	if (pbf) {
+		std::memcpy(hb + rs.pbf_pre, in->pbf_pre, 4 * (size_t)n);
+		std::memcpy(hb + rs.pbf_fix, in->pbf_fix, n);
+	}
+	std::memset(hb + rs.arrays_end, 0, rs.fonts - rs.arrays_end);
+	uint32_t *cmd_off = (uint32_t *)(hb + rs.cmd_off), *part_off = (uint32_t *)(hb + rs.part_off);
+	uint64_t slots = 0, parts = 0;
+	for (uint32_t g = 0; g < n; g++) { // two table reads and two additions per glyph
+		const vgsdf_font &ft = *in->fonts[in->font_of[g]];
+		const uint32_t id = in->glyph_id[g];
+		cmd_off[g] = (uint32_t)slots;
+		part_off[g] = (uint32_t)parts;
+		slots += ft.slots[id];
+		parts += ft.leaf_off[id + 1] - ft.leaf_off[id];
+		if (slots > 0x7FFFFFFFull) {
+			ctx->err = "vgsdf_outlines_resident: more than 2^31 - 1 command slots in one submission; split it";
+			return VGSDF_E_ARG;
+		}
+		f.res_scales_plain = f.res_scales_plain && in->scale[g] > 0.0 && in->scale[g] < HUGE_VAL;
+	}
+	cmd_off[n] = (uint32_t)slots;
+	part_off[n] = (uint32_t)parts;
+	vgsdf::ResidentFontRef *refs = (vgsdf::ResidentFontRef *)(hb + rs.fonts);
+	for (uint32_t k = 0; k < in->n_fonts; k++) {
+		refs[k] = in->fonts[k]->ref;
+		f.res_max_cap = std::max(f.res_max_cap, in->fonts[k]->max_cap);
+		f.res_max_len = std::max(f.res_max_len, in->fonts[k]->max_len);
+	}
+	f.cmd_off = cmd_off;
+	f.scale = (const double *)(hb + rs.scale);
+	f.shift_x = (const double *)(hb + rs.shift_x);
+	f.pbf_pre = pbf ? (const uint32_t *)(hb + rs.pbf_pre) : nullptr;
+	f.pbf_fix = pbf ? hb + rs.pbf_fix : nullptr;
+	f.n_parts = (uint32_t)parts;
+	f.n_fonts = in->n_fonts;
+	return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
 }
 
 int vgsdf_outlines_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, uint64_t *n_segments, int *rendered)

@@ -60,6 +60,14 @@ extern "C" {
 // are all positive and finite (bit 1 of that byte is never set here)
 int vgsdf_glyf_decode(const void *parts, uint32_t n_parts, const uint8_t *bytes, vgsdf::OutlineCmd *cmds, uint32_t *error_flag,
                       uint32_t max_cmd_cap, uint32_t max_byte_len, uint8_t *cmd_open, hipStream_t stream);
+// the same for parts expanded from resident fonts: fonts = vgsdf::ResidentFontRef records (upload_layout.h), a part's font
+// index in the upper half of its `plain`
+int vgsdf_glyf_decode_resident(const void *parts, uint32_t n_parts, const void *fonts, vgsdf::OutlineCmd *cmds, uint32_t *error_flag,
+                               uint32_t max_cmd_cap, uint32_t max_byte_len, uint8_t *cmd_open, hipStream_t stream);
+// upload of a vgsdf_outlines_resident submission: copies the block (ResidentBlockLayout, padded to 16 bytes; src: the device
+// address of the page-locked block, or a device copy of it) to dst and expands the glyphs' leaves into parts_out[n_parts]
+int vgsdf_resident_expand(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_parts, uint32_t n_fonts,
+                          bool with_pbf, void *parts_out, hipStream_t stream);
 // upload by a kernel: src_mapped = device address of a page-locked, device-mapped host block (16-byte aligned), dst 16-byte aligned
 int vgsdf_copy_in(const void *src_mapped, void *dst, size_t bytes, hipStream_t stream);
 // cmd_open: one byte per command (bit 0: ring open in front of it, bit 1: the glyph's scale is not positive finite)

@@ -1,9 +1,11 @@
 // upload_layout.h — byte offsets of the single-block upload forms.  include/vgsdf.h states the two layouts for callers
-// (vgsdf_outlines_packed, vgsdf_outlines_glyf); this header is their one computation, used by the host façade that
+// (vgsdf_outlines_packed, vgsdf_outlines_glyf); this header is their one computation (and that of the
+// block the library itself gathers for vgsdf_outlines_resident), used by the host façade that
 // builds such a block (csrc/host/renderer.hpp, MergedOutlines) and by the front-end that recognises one, sizes its
 // device copy and derives the device views from it (outline_front_end.cpp).  Plain C++: no HIP here.
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
 
 #include "../../include/vgsdf.h"
 
@@ -42,6 +44,28 @@ struct GlyfBlockLayout : GlyphArraysLayout {
 		pbf_pre = glyf_bytes + n_bytes;
 		pbf_fix = pbf_pre + 4 * n;
 		bytes = with_pbf ? pbf_fix + n : pbf_pre;
+	}
+};
+
+// The form that names its glyphs (vgsdf_outlines_resident):
+// ... | part_off u32[n + 1] | glyph_id u16[n] | font_of u16[n] [| pbf_pre u32[n] | pbf_fix u8[n]] = 33 n + 8 bytes with the
+// PBF arrays, then (16-aligned) 32 bytes of device addresses per font the submission names, and the whole padded to 16.
+// The device keeps a copy of the block as it stands and, behind it, the parts the upload kernel expands the leaves into.
+struct ResidentFontRef { // a resident font's three arrays (device addresses)
+	uint64_t leaf_off, leaves, bytes, reserved;
+};
+struct ResidentBlockLayout : GlyphArraysLayout {
+	size_t part_off, glyph_id, font_of, pbf_pre, pbf_fix, arrays_end, fonts, bytes; // bytes: the block; the parts follow on the device
+	ResidentBlockLayout(size_t n, size_t n_fonts, bool with_pbf) : GlyphArraysLayout(n)
+	{
+		part_off = end;
+		glyph_id = part_off + 4 * (n + 1);
+		font_of = glyph_id + 2 * n;
+		pbf_pre = font_of + 2 * n;
+		pbf_fix = pbf_pre + 4 * n;
+		arrays_end = with_pbf ? pbf_fix + n : pbf_pre;
+		fonts = (arrays_end + 15) / 16 * 16;
+		bytes = fonts + sizeof(ResidentFontRef) * n_fonts; // (a multiple of 16)
 	}
 };
 

@@ -52,7 +52,19 @@ class _COutlinesGlyf(C.Structure):
 # vgsdf_glyf_part: one simple glyph of a (possibly composite) glyph for the device's glyf decoder
 GLYF_PART_DTYPE = np.dtype([("byte_off", "<u4"), ("byte_len", "<u4"), ("cmd_at", "<u4"), ("cmd_cap", "<u4"), ("n_contours", "<u4"),
                             ("plain", "<u4"), ("a", "<f4"), ("b", "<f4"), ("c", "<f4"), ("d", "<f4"), ("e", "<f4"), ("f", "<f4")])
+VGSDF_E_ARG = -1
 VGSDF_E_GLYF = -4
+
+
+class _CFontDesc(C.Structure):  # vgsdf_font_desc
+    _fields_ = [("n_glyph_ids", C.c_uint32), ("n_leaves", C.c_uint32), ("n_bytes", C.c_uint32), ("leaf_off", C.c_void_p),
+                ("leaves", C.c_void_p), ("bytes", C.c_void_p)]
+
+
+class _COutlinesResident(C.Structure):  # vgsdf_outlines_resident
+    _fields_ = [("n_glyphs", C.c_uint32), ("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("font_of", C.c_void_p),
+                ("glyph_id", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("pbf_pre", C.c_void_p),
+                ("pbf_fix", C.c_void_p)]
 
 VGSDF_SYMBOLS = [
     "vgsdf_device_count", "vgsdf_create", "vgsdf_destroy", "vgsdf_last_error", "vgsdf_render_batch",
@@ -60,6 +72,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_batch_stats", "vgsdf_batch_time", "vgsdf_set_variant", "vgsdf_batch_device_output",
     "vgsdf_host_alloc", "vgsdf_host_free", "vgsdf_outlines_prepare", "vgsdf_outlines_render", "vgsdf_outlines_render_into", "vgsdf_outlines_submit", "vgsdf_outlines_submit_packed", "vgsdf_outlines_submit_glyf", "vgsdf_outlines_wait", "vgsdf_outlines_segments",
     "vgsdf_add_counters", "vgsdf_reset_counters", "vgsdf_reduce_counters", "vgsdf_reduce_counters_rccl", "vgsdf_reduce_path", "vgsdf_outlines_pbf_positions", "vgsdf_outlines_peek",
+    "vgsdf_font_create", "vgsdf_font_free", "vgsdf_font_device_bytes", "vgsdf_outlines_submit_resident", "vgsdf_outlines_resident_upload_bytes",
 ]
 
 _lib = None
@@ -106,6 +119,13 @@ def load_library():
         L.vgsdf_outlines_segments.argtypes = [vp, vp, vp, vp, vp, vp]
         L.vgsdf_outlines_pbf_positions.argtypes = [vp, vp]
         L.vgsdf_outlines_peek.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.vgsdf_font_create.argtypes = [vp, C.POINTER(_CFontDesc), C.POINTER(vp)]
+        L.vgsdf_font_free.argtypes = [vp, vp]
+        L.vgsdf_font_device_bytes.argtypes = [vp]
+        L.vgsdf_font_device_bytes.restype = C.c_uint64
+        L.vgsdf_outlines_submit_resident.argtypes = [vp, vp, vp, C.c_size_t]
+        L.vgsdf_outlines_resident_upload_bytes.argtypes = [vp]
+        L.vgsdf_outlines_resident_upload_bytes.restype = C.c_uint64
         L.vgsdf_add_counters.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
         L.vgsdf_add_counters.restype = None
         L.vgsdf_reset_counters.argtypes = [vp]
@@ -231,6 +251,29 @@ class DeviceBatch:
         try:
             if self.ctx._h:
                 self.free()
+        except Exception:
+            pass
+
+
+class ResidentFont:
+    """vgsdf_font: a face's outlines resident on a context's device (any context of that device may name it)."""
+
+    def __init__(self, ctx: "SdfContext", handle):
+        self.ctx, self._h = ctx, handle
+
+    @property
+    def device_bytes(self) -> int:
+        return int(load_library().vgsdf_font_device_bytes(self._h)) if self._h else 0
+
+    def free(self):
+        """the caller's to time: no submission that names the font may be in flight"""
+        if self._h and self.ctx._h:
+            load_library().vgsdf_font_free(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 
@@ -396,6 +439,47 @@ class SdfContext:
             L.vgsdf_host_free(host)
             self._check(rc)
         self._inflight = (keep, host, capacity, n)
+
+    def font_create(self, leaf_off, leaves, store) -> ResidentFont:
+        """vgsdf_font_create: a face's description (vgsdf_font_desc: leaf_off[numGlyphs + 1], leaves, bytes) -> ResidentFont"""
+        leaf_off = np.ascontiguousarray(leaf_off, dtype=np.uint32)
+        leaves = np.ascontiguousarray(leaves, dtype=GLYF_PART_DTYPE)
+        store = np.ascontiguousarray(store, dtype=np.uint8)
+        d = _CFontDesc(max(len(leaf_off), 1) - 1, len(leaves), len(store), leaf_off.ctypes.data, leaves.ctypes.data, store.ctypes.data)
+        h = C.c_void_p()
+        self._check(load_library().vgsdf_font_create(self._h, C.byref(d), C.byref(h)))
+        return ResidentFont(self, h)
+
+    def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None):
+        """outlines_submit for glyphs named by (font, glyph id) of resident fonts (vgsdf_outlines_resident)"""
+        L = load_library()
+        keep = {
+            "font_of": np.ascontiguousarray(font_of, dtype=np.uint16), "glyph_id": np.ascontiguousarray(glyph_id, dtype=np.uint16),
+            "scale": np.ascontiguousarray(scale, dtype=np.float64), "shift": np.ascontiguousarray(shift_x, dtype=np.float64),
+            "fonts": (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts]), "font_objects": list(fonts),
+        }
+        n = len(keep["scale"])
+        assert len(keep["font_of"]) == n and len(keep["glyph_id"]) == n
+        host = L.vgsdf_host_alloc(max(capacity, 1))
+        if not host:
+            raise MemoryError("vgsdf_host_alloc")
+        co = _COutlinesResident(n, len(fonts), C.cast(keep["fonts"], C.c_void_p), keep["font_of"].ctypes.data, keep["glyph_id"].ctypes.data,
+                                keep["scale"].ctypes.data, keep["shift"].ctypes.data)
+        if pbf_pre is not None:
+            keep["pbf_pre"] = np.ascontiguousarray(pbf_pre, dtype=np.uint32)
+            co.pbf_pre = keep["pbf_pre"].ctypes.data
+        if pbf_fix is not None:
+            keep["pbf_fix"] = np.ascontiguousarray(pbf_fix, dtype=np.uint8)
+            co.pbf_fix = keep["pbf_fix"].ctypes.data
+        rc = L.vgsdf_outlines_submit_resident(self._h, C.byref(co), host, capacity)
+        if rc != 0:
+            L.vgsdf_host_free(host)
+            self._check(rc)
+        self._inflight = (keep, host, capacity, n)
+
+    def resident_upload_bytes(self) -> int:
+        """size of the block the last resident submission of this context uploaded"""
+        return int(load_library().vgsdf_outlines_resident_upload_bytes(self._h))
 
     def outlines_peek(self):
         """between submit and wait: the front-end's results while the raster is still running -> (rects, out_bytes, in_place)"""

@@ -34,6 +34,15 @@ class Timings(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class _CResidentView(C.Structure):  # vg_resident_view
+    _fields_ = [("n_glyphs", C.c_uint32), ("n_files", C.c_uint32), ("font_of", C.c_void_p), ("glyph_id", C.c_void_p),
+                ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("ids", C.c_void_p), ("advances", C.c_void_p)]
+
+
+class ResidentStats(C.Structure):  # vg_resident_stats
+    _fields_ = [(k, C.c_uint64) for k in ("groups", "fonts_uploaded", "font_bytes", "block_bytes")]
+
+
 WRITE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int)
 
 VGFONT_SYMBOLS = [
@@ -43,6 +52,8 @@ VGFONT_SYMBOLS = [
     "vg_manager_render_block", "vg_manager_render_blocks", "vg_render_glyph", "vg_manager_build_batch", "vg_glyph_batch_view",
     "vg_glyph_batch_free", "vg_manager_record_outlines", "vg_outline_batch_view", "vg_outline_batch_free", "vg_pbf_encode",
     "vg_manager_record_glyf_parts", "vg_glyf_batch_view", "vg_glyf_batch_free",
+    "vg_manager_resident_font_desc", "vg_manager_record_resident", "vg_resident_batch_view", "vg_resident_batch_free",
+    "vg_manager_set_resident_fonts", "vg_renderer_set_resident_budget", "vg_renderer_preload_fonts", "vg_manager_resident_stats",
     "vg_manager_scan", "vg_manager_font_ids", "vg_manager_font_file_names", "vg_parse_font_name", "vg_manager_generate_name",
     "vg_encode_codeblocks", "vg_manager_index_json", "vg_manager_families_json", "vg_writer_new_tar_path",
     "vg_writer_new_tar_fd", "vg_writer_new_dir", "vg_writer_write_file", "vg_writer_write_directory", "vg_writer_finish",
@@ -74,6 +85,13 @@ def _L():
         L.vg_manager_set_in_place_pbf.restype = None
         L.vg_manager_set_glyf_on_device.argtypes = [vp, C.c_int]
         L.vg_manager_set_glyf_on_device.restype = None
+        L.vg_manager_set_resident_fonts.argtypes = [vp, C.c_int]
+        L.vg_manager_set_resident_fonts.restype = None
+        L.vg_renderer_set_resident_budget.argtypes = [vp, C.c_uint64]
+        L.vg_renderer_set_resident_budget.restype = None
+        L.vg_renderer_preload_fonts.argtypes = [vp, vp]
+        L.vg_renderer_preload_fonts.restype = C.c_longlong
+        L.vg_manager_resident_stats.argtypes = [vp, C.POINTER(ResidentStats)]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -200,6 +218,18 @@ class Renderer:
     def reset_counters(self):
         _L().vg_renderer_reset_counters(self._h)
 
+    def set_resident_budget(self, bytes_per_device: int):
+        """HBM the device copies of resident fonts may take per device (default 1 GiB; a face that does not fit is rendered
+        through the glyf form)"""
+        _L().vg_renderer_set_resident_budget(self._h, bytes_per_device)
+
+    def preload_fonts(self, manager) -> int:
+        """uploads every face of the manager now -> bytes put on the devices"""
+        n = int(_L().vg_renderer_preload_fonts(self._h, manager._h))
+        if n < 0:
+            raise RuntimeError(_err())
+        return n
+
     def reduce_counters(self):
         """(blocks, glyphs, pixels) summed over the lanes: vgsdf_reduce_counters (RCCL when the devices are distinct)"""
         out = (C.c_uint64 * 3)()
@@ -292,6 +322,18 @@ class FontManager:
     def set_glyf_on_device(self, on: bool):
         """True (default): glyf fonts are decoded on the device; False: the host reader records the outline callbacks"""
         _L().vg_manager_set_glyf_on_device(self._h, 1 if on else 0)
+
+    def set_resident_fonts(self, on: bool):
+        """False (default).  True: groups of glyf fonts are submitted by (font, glyph id) against the renderer's device copies of
+        the faces (uploaded on first use); same bytes either way"""
+        _L().vg_manager_set_resident_fonts(self._h, 1 if on else 0)
+
+    def resident_stats(self) -> dict:
+        """of the last render: groups submitted in the resident form, faces uploaded during it, their bytes on the device, bytes
+        of the submissions' upload blocks"""
+        s = ResidentStats()
+        _L().vg_manager_resident_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in ResidentStats._fields_}
 
     def set_lane_form(self, form: int):
         """several device lanes: -1 / 2 hybrid (whole (font, block) tasks, the heaviest blocks split between lanes), 1 whole tasks
@@ -502,6 +544,53 @@ class FontManager:
                     "advances": arr(C.cast(adv, C.c_void_p).value, n, np.uint32)}
         finally:
             L.vg_glyf_batch_free(h)
+
+    def resident_font_desc(self, font_id: str, file_index: int = 0) -> dict:
+        """description of one file of a font id for vgsdf_font_create: {leaf_off, leaves, bytes} (numpy copies); every glyph
+        id's leaves (cmd_at from the glyph's first slot), every simple glyph's arrays stored once"""
+        from .device import GLYF_PART_DTYPE, _CFontDesc
+        L = _L()
+        L.vg_manager_resident_font_desc.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        d = _CFontDesc()
+        if L.vg_manager_resident_font_desc(self._h, font_id.encode(), file_index, C.byref(d)) != 0:
+            raise RuntimeError(_err())
+
+        def arr(ptr, count, dt):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dt)
+            buf = (C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dt, count=count).copy()
+
+        return {"leaf_off": arr(d.leaf_off, d.n_glyph_ids + 1, np.uint32), "leaves": arr(d.leaves, d.n_leaves, GLYF_PART_DTYPE),
+                "bytes": arr(d.bytes, d.n_bytes, np.uint8)}
+
+    def record_resident(self, font_id: str) -> dict:
+        """what a resident submission of the font names: {font_of, glyph_id, scale, shift_x, ids, advances, n_files}"""
+        L = _L()
+        L.vg_manager_record_resident.restype = C.c_void_p
+        L.vg_manager_record_resident.argtypes = [C.c_void_p, C.c_char_p]
+        L.vg_resident_batch_view.argtypes = [C.c_void_p, C.c_void_p]
+        L.vg_resident_batch_free.argtypes = [C.c_void_p]
+        L.vg_resident_batch_free.restype = None
+        h = L.vg_manager_record_resident(self._h, font_id.encode())
+        if not h:
+            raise RuntimeError(_err())
+        try:
+            v = _CResidentView()
+            L.vg_resident_batch_view(h, C.byref(v))
+            n = v.n_glyphs
+
+            def arr(ptr, dt):
+                if n == 0 or not ptr:
+                    return np.zeros(0, dtype=dt)
+                buf = (C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr)
+                return np.frombuffer(buf, dtype=dt, count=n).copy()
+
+            return {"font_of": arr(v.font_of, np.uint16), "glyph_id": arr(v.glyph_id, np.uint16), "scale": arr(v.scale, np.float64),
+                    "shift_x": arr(v.shift_x, np.float64), "ids": arr(v.ids, np.uint32), "advances": arr(v.advances, np.uint32),
+                    "n_files": int(v.n_files)}
+        finally:
+            L.vg_resident_batch_free(h)
 
     def build_batch(self, font_id: str) -> GlyphBatchHost:
         h = _L().vg_manager_build_batch(self._h, font_id.encode())
