@@ -218,6 +218,8 @@ int vgsdf_outlines_submit_packed(vgsdf_ctx *ctx, const vgsdf_outlines_packed *in
  * do nothing on the empty ring behind a contour's own close().  An entry whose arrays do not fit its bytes or its slots
  * (ttf-parser returns None for such a glyph and, in a composite, skips the components behind it) fails the whole batch with
  * VGSDF_E_GLYF in vgsdf_outlines_wait: the caller records that batch with its host reader and submits commands instead.
+ * The decoder has two limits of its own per part, and a well-formed entry beyond either fails the batch the same way: an entry
+ * of more than 6144 points, or a byte_len above 30720 (30 KB: end points + arrays, whatever lies behind them included).
  * In ONE block from vgsdf_host_alloc() in the order scale | shift_x | cmd_off | (pad to a multiple of 8 bytes) | parts | bytes
  * [| pbf_pre | pbf_fix] the batch is uploaded with a single copy — by a kernel reading the block itself (it is device-mapped), so no
  * copy-engine hand-over sits in front of the decoder — and its offsets are validated under that copy.  When every scale is positive

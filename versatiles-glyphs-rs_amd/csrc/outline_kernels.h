@@ -53,6 +53,10 @@ struct GlyphDesc;
 } // namespace vgsdf
 
 extern "C" {
+// the decoder's limits per part (kGlyfMaxPoints, kGlyfMaxBytes: beyond them a part fails with error_flag bit 4) and the number of
+// font references a workgroup of the resident upload keeps in LDS (kExpandFontCache); any pointer may be NULL.  For tests that
+// restate the constants (as vgsdf_filtered_delta_cap): not part of the public ABI of include/
+void vgsdf_glyf_limits(uint32_t *max_points, uint32_t *max_bytes, uint32_t *expand_font_cache);
 // parts: vgsdf_glyf_part records (include/vgsdf.h); writes the commands of every part into its slots of `cmds`;
 // error_flag bit 4: a malformed entry
 // max_cmd_cap / max_byte_len: the largest cmd_cap / byte_len among the parts (they size the launch's LDS)

@@ -1536,6 +1536,16 @@ __global__ __launch_bounds__(kExpandThreads) void resident_expand(const uint4 *_
 
 using namespace vgsdf;
 
+extern "C" void vgsdf_glyf_limits(uint32_t *max_points, uint32_t *max_bytes, uint32_t *expand_font_cache)
+{
+	if (max_points)
+		*max_points = kGlyfMaxPoints;
+	if (max_bytes)
+		*max_bytes = kGlyfMaxBytes;
+	if (expand_font_cache)
+		*expand_font_cache = kExpandFontCache;
+}
+
 extern "C" int vgsdf_resident_expand(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_parts, uint32_t n_fonts,
                                      bool with_pbf, void *parts_out, hipStream_t stream)
 {
