@@ -118,6 +118,28 @@ typedef struct {
 	uint64_t block_bytes;    /* bytes of the submissions' upload blocks */
 } vg_resident_stats;
 int vg_manager_resident_stats(const vg_manager *m, vg_resident_stats *out);
+/* Command stores, 0 (default) / 1 / 2, independent of vg_manager_set_resident_fonts.  A command store is a face's outline
+ * callbacks by glyph id, expanded once on the device (vgsdf_font_create_commands): every face the reader can read has one.
+ * The renderer owns them as it owns the resident fonts — same registry, one per (device, face), same budget, no eviction.
+ *   0: nothing changes.
+ *   1: a group of the dispatcher that cannot take a glyf form — a face without `glyf` outlines (CFF, CFF2), a font the
+ *      device's decoder or the batch bounds have refused — is submitted by (font, glyph id) against command stores of all
+ *      its faces instead of being read by the host on every render.  Groups that can take a glyf form are untouched; a group
+ *      the device refuses still falls back to the host's reader exactly as before (vg_timings.glyf_fallbacks), and later
+ *      groups of that font go by name.
+ *   2: every group goes by name against command stores, `glyf` faces included (an A/B lever: no decoder launch, more HBM).
+ * A store that does not fit the budget sends its groups the way they go with 0.  Same bytes in every mode.  Every entry point
+ * that runs the dispatcher takes it; vg_manager_render_block and vg_render_glyph stay as they are.
+ * vg_renderer_preload_fonts also uploads the command stores the manager's mode would use.
+ * vg_manager_command_stats: of the last render (vg_resident_stats keeps counting the glyf-resident groups only). */
+void vg_manager_set_resident_commands(vg_manager *m, int mode);
+typedef struct {
+	uint64_t groups;         /* groups submitted by name against command stores */
+	uint64_t fonts_uploaded; /* command stores uploaded during the render */
+	uint64_t font_bytes;     /* ... and what they occupy on the device */
+	uint64_t block_bytes;    /* bytes of those submissions' upload blocks */
+} vg_command_stats;
+int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out);
 /* How a renderer of several device lanes (vg_renderer_new_multi) splits a run: -1 / 2 (default) the hybrid plan — whole
  * (font, block) tasks per lane, manager.rs:86-97's unit, and the heaviest blocks' glyphs split between lanes until the lanes'
  * estimated raster cost is within 4 % of the mean; 1 whole tasks only; 0 glyph-level shards of every font (every block
@@ -250,6 +272,17 @@ int vg_manager_resident_font_desc(const vg_manager *m, const char *font_id, int 
 vg_resident_batch *vg_manager_record_resident(const vg_manager *m, const char *font_id);
 int vg_resident_batch_view(const vg_resident_batch *b, vg_resident_view *view);
 void vg_resident_batch_free(vg_resident_batch *b);
+/* The same against command fonts (vgsdf_font_create_commands), for EVERY face the reader can read — CFF and CFF2 charstrings,
+ * `glyf` faces the forms above refuse — no device needed.
+ * vg_manager_command_font_desc: for every glyph id of file `file_index` the callbacks the reader delivers for it, in the arrays
+ * of the packed form: exactly what a render of the glyph records today (a glyph whose charstring or entry fails midway holds
+ * the callbacks delivered up to there).  Built on first use, kept with the face; the pointers stay valid as long as the manager
+ * holds the font.  -1: unknown font / file, or a face whose store on the device (29 bytes per command, 4 per glyph id) or whose coordinates
+ * would pass what 32-bit offsets address (refused by counting the callbacks, before the table is allocated).
+ * vg_manager_record_resident_commands: what a submission of every glyph of the font id names, as vg_manager_record_resident
+ * (the same view, freed the same way); NULL for an unknown font id or a file without a command table. */
+int vg_manager_command_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_cmds_desc *desc);
+vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, const char *font_id);
 
 /* Hand-encoder of the glyphs PBF (src/protobuf/glyphs.rs:66-70) for already rendered
  * glyphs; bitmaps[i] may be NULL when !has_bitmap. Returns needed size. */

@@ -293,6 +293,36 @@ typedef struct {
 } vgsdf_outlines_resident;
 int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity);
 uint64_t vgsdf_outlines_resident_upload_bytes(const vgsdf_ctx *ctx);
+/*
+ * Command fonts: the resident form for every face whose outlines the caller can read, whatever table they come from (CFF,
+ * CFF2, a `glyf` face the decoder refuses).  vgsdf_font_cmds_desc gives, for every glyph id, the callbacks of its outline in
+ * the arrays of vgsdf_outlines_packed: glyph id g owns kinds[cmd_off[g] .. cmd_off[g + 1]) and
+ * coords[dat_off[g] .. dat_off[g + 1]).  vgsdf_font_create_commands validates on the host everything a packed submission
+ * is checked for per render — at most 65536 glyph ids, a store and coordinates that 32-bit offsets address (29 bytes per command + 4 per glyph id, and
+ * 4 n_floats, below 2^32), both offset arrays ascending from 0 to n_cmds /
+ * n_floats, every kind <= 4, every glyph's dat_off range exactly what its kinds carry (2 floats for a move or a line, 4 for a
+ * quad, 6 for a curve, none for a close) — and refuses with VGSDF_E_ARG, nothing left allocated, the context sound.  It then
+ * expands the commands ONCE on the device (the context pass of the packed form over the whole face) and keeps the 28-byte
+ * records and the byte per command that says whether a ring is open in front of it: 29 bytes per command and 4 per glyph id.
+ * The result is a vgsdf_font like any other: vgsdf_font_free and vgsdf_font_device_bytes work on it, it belongs to the
+ * context's device, and vgsdf_outlines_submit_resident names it — but ONE submission names fonts of one kind (fonts from
+ * vgsdf_font_create and from vgsdf_font_create_commands in one list: VGSDF_E_ARG before anything runs).
+ * Against command fonts the host's share per glyph is one table read and one addition (the running sum of command counts;
+ * more than 2^31 - 1 commands in one submission: VGSDF_E_ARG); the block is
+ *   scale f64[n] | shift_x f64[n] | cmd_off u32[n + 1] | glyph_id u16[n] | font_of u16[n] | pbf_pre u32[n] | pbf_fix u8[n]
+ * followed by 32 bytes of device addresses per font, and ONE kernel copies it and gathers every named glyph's records and
+ * context bytes from the stores.  No decoder runs and, when every scale is positive and finite, no context pass either: one
+ * launch fewer than the packed and the glyf-resident forms.  Output is the packed form's of the same commands, byte for byte.
+ * A glyph id without commands is a glyph without outline (no slots, has_raster = 0).
+ */
+typedef struct {
+	uint32_t n_glyph_ids, n_cmds, n_floats;
+	const uint32_t *cmd_off; /* [n_glyph_ids + 1] into kinds, ascending, cmd_off[0] = 0, last = n_cmds */
+	const uint32_t *dat_off; /* [n_glyph_ids + 1] into coords, likewise, last = n_floats */
+	const uint8_t *kinds;    /* [n_cmds] as in vgsdf_outlines_packed */
+	const float *coords;     /* [n_floats] */
+} vgsdf_font_cmds_desc;
+int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, vgsdf_font **out);
 int vgsdf_outlines_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, uint64_t *n_segments, int *rendered);
 /* Between submit and wait: blocks until the front-end's results are on the host — they leave the device right behind the
  * plan kernel, on a stream of their own, while flattening and raster are still running — and reports the rects and

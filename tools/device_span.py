@@ -1,7 +1,9 @@
 """Device span of one submission (HIP events around upload ... last kernel, VGSDF_TRACE) and end-to-end time of the same run,
 config 2 (Noto Sans Regular) or another workload, over N warm runs: median / min of both.  Development aid.
-    python tools/device_span.py [noto_regular|noto_all|fira|many] [runs] [resident]
-`resident`: with resident fonts on (the first run, which builds the tables and uploads the fonts, is printed separately)."""
+    python tools/device_span.py [noto_regular|noto_all|fira|many|noto_cff] [runs] [resident] [commands|commands1]
+`resident`: with resident fonts on (the first run, which builds the tables and uploads the fonts, is printed separately).
+`commands`: every group by name against command stores (vg_manager_set_resident_commands 2); `commands1`: mode 1, the groups
+without a glyf form only.  noto_cff: Noto Sans Regular re-encoded as CFF with fontTools (as tools/cff_time.py does)."""
 import os
 import re
 import subprocess
@@ -29,7 +31,17 @@ runs = int(sys.argv[2]) if len(sys.argv) > 2 else 60
 resident = "resident" in sys.argv[3:]
 m = vg.FontManager(True)
 m.set_resident_fonts(resident)
-if which == "many":
+commands = 2 if "commands" in sys.argv[3:] else 1 if "commands1" in sys.argv[3:] else 0
+m.set_resident_commands(commands)
+if which == "noto_cff":
+    from fontTools.pens.t2CharStringPen import T2CharStringPen
+    from fontTools.ttLib import TTFont
+    import test_cff_outlines as T
+    src = TTFont(NOTO); gs = src.getGlyphSet(); order = src.getGlyphOrder(); cs = {}
+    for g in order:
+        pen = T2CharStringPen(gs[g].width, gs); gs[g].draw(pen); cs[g] = pen.getCharString()
+    m.add_font_data("Some Font", T._build(order, dict(src.getBestCmap()), cs, {g: gs[g].width for g in order}, src["head"].unitsPerEm))
+elif which == "many":
     for i, p in enumerate([FIRA] + list(noto_files())):
         m.add_font_with_name(f"Font {i:02d}", [p])
 else:
@@ -42,6 +54,8 @@ for i in range(runs):
     ts.append(time.perf_counter() - t0)
 tm = m.timings()
 w = sorted(ts[runs // 3:])
+if commands:
+    print(f"command stores (mode {commands}): first run {ts[0] * 1e6:.0f} us (tables + store upload), last run's stats {m.command_stats()}")
 if resident:
     print(f"resident fonts: first run {ts[0] * 1e6:.0f} us (tables + font upload), last run's stats {m.resident_stats()}")
 print(f"{which}: {tm['glyphs']} glyphs, end to end min {w[0] * 1e6:.0f} us ({tm['glyphs'] / w[0] / 1e6:.2f} M glyphs/s), median {w[len(w) // 2] * 1e6:.0f} us; "

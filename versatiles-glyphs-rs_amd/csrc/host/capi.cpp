@@ -150,6 +150,13 @@ int vg_manager_resident_stats(const vg_manager *m, vg_resident_stats *out)
 	*out = vg_resident_stats{t.resident_groups, t.resident_fonts_uploaded, t.resident_font_bytes, t.resident_block_bytes};
 	return 0;
 }
+void vg_manager_set_resident_commands(vg_manager *m, int mode) { m->m.set_resident_commands(mode); }
+int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_command_stats{t.command_groups, t.command_fonts_uploaded, t.command_font_bytes, t.command_block_bytes};
+	return 0;
+}
 void vg_manager_set_lane_form(vg_manager *m, int form) { m->m.set_lane_form(form < 0 || form > 2 ? -1 : form); }
 void vg_manager_set_threads(vg_manager *m, unsigned threads, unsigned blocks_per_batch)
 {
@@ -646,6 +653,48 @@ vg_resident_batch *vg_manager_record_resident(const vg_manager *m, const char *f
 		std::string err;
 		if (!m->m.record_resident(font_id, b->b, &err)) {
 			g_err = err;
+			return nullptr;
+		}
+		for (const vg::GlyphJob &j : b->b.jobs) {
+			b->ids.push_back(j.id);
+			b->advances.push_back(j.advance);
+		}
+		b->n_files = (uint32_t)m->m.fonts().at(font_id).files().size();
+		return b.release();
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return nullptr;
+	}
+}
+int vg_manager_command_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_cmds_desc *desc)
+{
+	try {
+		std::string err;
+		const vg::CommandTable *t = file_index < 0 || !m || !font_id ? nullptr : m->m.command_table(font_id, (size_t)file_index, &err);
+		if (!t || !desc) {
+			g_err = err.empty() ? "vg_manager_command_font_desc: bad argument" : err;
+			return -1;
+		}
+		desc->n_glyph_ids = (uint32_t)t->cmd_off.size() - 1;
+		desc->n_cmds = (uint32_t)t->kinds.size();
+		desc->n_floats = (uint32_t)t->coords.size();
+		desc->cmd_off = t->cmd_off.data();
+		desc->dat_off = t->dat_off.data();
+		desc->kinds = t->kinds.data();
+		desc->coords = t->coords.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, const char *font_id)
+{
+	try {
+		auto b = std::make_unique<vg_resident_batch>();
+		std::string err;
+		if (!m || !font_id || !m->m.record_resident_commands(font_id, b->b, &err)) {
+			g_err = err.empty() ? "vg_manager_record_resident_commands: bad argument" : err;
 			return nullptr;
 		}
 		for (const vg::GlyphJob &j : b->b.jobs) {

@@ -546,6 +546,49 @@ const ResidentTable *FontManager::resident_table(const std::string &font_id, siz
 	return &t;
 }
 
+bool FontManager::record_resident_commands(const std::string &font_id, ResidentBatch &out, std::string *err) const
+{
+	auto it = fonts().find(font_id);
+	if (it == fonts().end()) {
+		if (err)
+			*err = "unknown font id " + font_id;
+		return false;
+	}
+	out.clear();
+	const auto &files = it->second.files();
+	std::map<const FontFileEntry *, uint16_t> file_of;
+	for (size_t k = 0; k < files.size(); k++) {
+		if (k > 0xFFFF || !files[k]->face().command_table().ok) {
+			if (err)
+				*err = "font " + font_id + ": a file whose outline commands pass what 32-bit offsets address";
+			return false;
+		}
+		file_of.emplace(files[k].get(), (uint16_t)k);
+	}
+	for (const GlyphBlock &b : task_blocks(it->first, it->second))
+		for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE; ci++)
+			if (const FontFileEntry *f = b.glyphs[ci])
+				Renderer::record_resident(f->face(), file_of.at(f), b.start_index + ci, out);
+	return true;
+}
+
+const CommandTable *FontManager::command_table(const std::string &font_id, size_t file_index, std::string *err) const
+{
+	auto it = fonts().find(font_id);
+	if (it == fonts().end() || file_index >= it->second.files().size()) {
+		if (err)
+			*err = "unknown font id " + font_id + ", or a file index past its files";
+		return nullptr;
+	}
+	const CommandTable &t = it->second.files()[file_index]->face().command_table();
+	if (!t.ok) {
+		if (err)
+			*err = "font " + font_id + ": the file's outline commands pass what 32-bit offsets address";
+		return nullptr;
+	}
+	return &t;
+}
+
 // ---- glyph-level sharding ---------------------------------------------------------------
 namespace {
 
@@ -1275,6 +1318,10 @@ void FontManager::render_tasks_multi(Writer &writer, const Renderer &renderer, i
 		timings_.resident_fonts_uploaded += ct.resident_fonts_uploaded;
 		timings_.resident_font_bytes += ct.resident_font_bytes;
 		timings_.resident_block_bytes += ct.resident_block_bytes;
+		timings_.command_groups += ct.command_groups;
+		timings_.command_fonts_uploaded += ct.command_fonts_uploaded;
+		timings_.command_font_bytes += ct.command_font_bytes;
+		timings_.command_block_bytes += ct.command_block_bytes;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1306,6 +1353,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->in_place_pbf_ = in_place_pbf_;
 		c->glyf_on_device_ = glyf_on_device_;
 		c->resident_fonts_ = resident_fonts_;
+		c->resident_commands_ = resident_commands_;
 		c->batch_blocks_ = batch_blocks_;
 		c->batch_blocks_set_ = batch_blocks_set_;
 		c->set_threads(per_lane);
@@ -1383,6 +1431,10 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		timings_.resident_fonts_uploaded += ct.resident_fonts_uploaded;
 		timings_.resident_font_bytes += ct.resident_font_bytes;
 		timings_.resident_block_bytes += ct.resident_block_bytes;
+		timings_.command_groups += ct.command_groups;
+		timings_.command_fonts_uploaded += ct.command_fonts_uploaded;
+		timings_.command_font_bytes += ct.command_font_bytes;
+		timings_.command_block_bytes += ct.command_block_bytes;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1565,7 +1617,7 @@ void FontManager::fe_layout_common(const std::vector<Todo> &tasks, FeGroup &G)
 
 // The group's glyphs by name (vgsdf_outlines_resident): the faces' outlines are on the device, so a worker's share per
 // glyph is the cmap and hmtx lookups — no composite is walked, no font byte copied.  Same slices, same merge in task order.
-bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane)
+bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands)
 {
 	constexpr uint32_t kSlice = 64;
 	ThreadPool &tp = pool();
@@ -1586,12 +1638,13 @@ bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G,
 			if (m.fonts.size() >= 0xFFFF)
 				return false;
 			uint64_t uploaded = 0;
-			const vgsdf_font *f = renderer.resident_font(lane, file->face().resident_table(), &uploaded);
+			const vgsdf_font *f = commands ? renderer.command_font(lane, file->face().command_table(), &uploaded)
+			                               : renderer.resident_font(lane, file->face().resident_table(), &uploaded);
 			if (!f)
 				return false;
 			if (uploaded) {
-				timings_.resident_fonts_uploaded++;
-				timings_.resident_font_bytes += uploaded;
+				(commands ? timings_.command_fonts_uploaded : timings_.resident_fonts_uploaded)++;
+				(commands ? timings_.command_font_bytes : timings_.resident_font_bytes) += uploaded;
 			}
 			index.emplace_back(file.get(), (uint16_t)m.fonts.size());
 			m.fonts.push_back(f);
@@ -1633,7 +1686,7 @@ bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G,
 	G.n_jobs = n_jobs;
 	m.jobs.resize(n_jobs);
 	G.in_place = in_place_pbf_;
-	m.layout_resident(n_jobs, G.in_place);
+	m.layout_resident(n_jobs, G.in_place, commands);
 	tp.run(slices.size(), [&](size_t i, unsigned) {
 		const OSlice &s = slices[i];
 		const ResidentBatch &l = workers_[s.worker].rlocal;
@@ -1663,11 +1716,26 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 			for (const auto &file : kv.second.files())
 				if (file->face().has_glyf_outlines())
 					(void)renderer.device_lane(r).resident_font(0, file->face().resident_table(), &uploaded);
+	// ... and the command stores the manager's mode would use: with 2 every face's, with 1 those of the fonts whose groups cannot
+	// take a glyf form (a file without `glyf` outlines, a font refused before)
+	if (resident_commands_)
+		for (size_t r = 0; r < renderer.n_devices(); r++)
+			for (const auto &kv : fonts()) {
+				bool wanted = resident_commands_ == 2 || glyf_refused_.count(&kv.first) != 0;
+				for (const auto &file : kv.second.files())
+					wanted = wanted || !file->face().has_glyf_outlines();
+				if (wanted)
+					for (const auto &file : kv.second.files())
+						(void)renderer.device_lane(r).command_font(0, file->face().command_table(), &uploaded);
+			}
 	return uploaded;
 }
 
 void FontManager::fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf, const Renderer *renderer, int lane)
 {
+	// (allow_glyf is false where a group the device has refused is recorded again: that fallback is the reader's, as ever)
+	if (allow_glyf && resident_commands_ == 2 && renderer && fe_record_resident(tasks, G, *renderer, lane, true))
+		return;
 	if (allow_glyf && glyf_on_device_) {
 		bool all_glyf = true;
 		for (size_t t = G.g0; t < G.g1 && all_glyf; t++)
@@ -1682,6 +1750,9 @@ void FontManager::fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool all
 			timings_.glyf_fallbacks++;
 		}
 	}
+	// no glyf form for this group: by name against command stores where the mode says so, else the host's reader
+	if (allow_glyf && resident_commands_ == 1 && renderer && fe_record_resident(tasks, G, *renderer, lane, true))
+		return;
 	constexpr uint32_t kSlice = 64;
 	ThreadPool &tp = pool();
 	const double t0 = now_s();
@@ -2002,8 +2073,8 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 			if (G.m.resident) {
 				uint64_t block = 0;
 				renderer.submit_outlines((int)(k & 1), G.m.view_resident(), G.out, &block);
-				timings_.resident_groups++;
-				timings_.resident_block_bytes += block;
+				(G.m.commands ? timings_.command_groups : timings_.resident_groups)++;
+				(G.m.commands ? timings_.command_block_bytes : timings_.resident_block_bytes) += block;
 			} else if (G.m.glyf) {
 				renderer.submit_outlines((int)(k & 1), G.m.view_glyf(), G.out);
 				timings_.glyf_groups++;

@@ -149,6 +149,8 @@ struct RenderTimings {
 	// resident fonts: groups submitted by (font, glyph id), faces uploaded during the run and their bytes on the device, bytes of
 	// the submissions' upload blocks
 	uint64_t resident_groups = 0, resident_fonts_uploaded = 0, resident_font_bytes = 0, resident_block_bytes = 0;
+	// the same for groups submitted by name against command stores (set_resident_commands)
+	uint64_t command_groups = 0, command_fonts_uploaded = 0, command_font_bytes = 0, command_block_bytes = 0;
 };
 
 class FontManager {
@@ -225,6 +227,12 @@ public:
 	// Resident fonts (default off): a group whose faces all have `glyf` outlines and a resident form is submitted by
 	// (font, glyph id) against the renderer's device copies of the faces (uploaded on first use); everything else as ever
 	void set_resident_fonts(bool on) { resident_fonts_ = on; }
+	// Command stores (default 0, independent of the switch above).  1: a group that cannot take a glyf form — a face without
+	// `glyf` outlines, a font the device's decoder or the batch bounds have refused — goes by (font, glyph id) against
+	// command stores of all its faces instead of through the host's reader; groups that can take a glyf form are untouched.
+	// 2: every group goes that way, `glyf` faces included (the A/B lever).  A store that does not fit the renderer's
+	// budget sends its groups the way they go with 0.
+	void set_resident_commands(int mode) { resident_commands_ = mode < 0 || mode > 2 ? 0 : mode; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
 	// returns the bytes put on the devices
 	uint64_t preload_resident_fonts(const Renderer &renderer) const;
@@ -237,6 +245,10 @@ public:
 	// (nullptr: unknown font / file, or a face without a resident form)
 	bool record_resident(const std::string &font_id, ResidentBatch &out, std::string *err) const;
 	const ResidentTable *resident_table(const std::string &font_id, size_t file_index, std::string *err) const;
+	// the same against command fonts (vgsdf_font_create_commands), for every face the reader can read, `glyf` or not
+	// (nullptr / false: unknown font / file, or a face whose commands pass what 32-bit offsets address)
+	bool record_resident_commands(const std::string &font_id, ResidentBatch &out, std::string *err) const;
+	const CommandTable *command_table(const std::string &font_id, size_t file_index, std::string *err) const;
 
 private:
 	struct Todo {
@@ -368,7 +380,8 @@ private:
 	// renderer / lane: whose device copies of the fonts a resident group names (nullptr: no resident form for this call)
 	void fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf = true, const Renderer *renderer = nullptr, int lane = 0);
 	// false: a face of the group has no resident form or does not fit the renderer's budget — the glyf form takes the group
-	bool fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane);
+	// commands: against the faces' command stores (every readable face has one) instead of their glyf stores
+	bool fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands = false);
 	bool fe_record_glyf(const std::vector<Todo> &tasks, FeGroup &G); // false: not a batch for the device's decoder (fan-out past 32-bit offsets)
 	// fonts (by id) one of whose groups the device's glyf decoder refused (VGSDF_E_GLYF) or whose parts passed the batch bounds:
 	// later groups and runs record them with the host's reader at once instead of paying the double path again; cleared
@@ -389,6 +402,7 @@ private:
 	int lane_form_ = -1;
 	bool glyf_on_device_ = glyf_on_device_default(); // glyf fonts: the device decodes the glyphs' arrays (VG_GLYF_ON_DEVICE=0 / set_glyf_on_device(false): the host does)
 	bool resident_fonts_ = false;
+	int resident_commands_ = 0;
 	bool device_front_end_ = true; // HIP renderer: flatten on the GPU unless switched off
 	std::map<std::string, FontWrapper> fonts_; // reference: HashMap (arbitrary order); sorted here
 	bool parallel_;

@@ -488,6 +488,42 @@ const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint
 	return f;
 }
 
+const vgsdf_font *Renderer::command_font(int lane, const CommandTable &t, uint64_t *uploaded_bytes) const
+{
+	if (mode_ != Mode::Hip || !t.ok)
+		return nullptr;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	const auto key = std::make_pair(device_, t.serial);
+	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
+		return it->second;
+	// (what vgsdf_font_create_commands will keep, to within its rounding: records | cmd_off | context bytes)
+	const uint64_t want = CommandTable::kStoreBytesPerCmd * (uint64_t)t.kinds.size() + 4 * (uint64_t)t.cmd_off.size();
+	if (rf.bytes[device_] + want > rf.budget)
+		return nullptr;
+	vgsdf_font_cmds_desc d;
+	d.n_glyph_ids = (uint32_t)t.cmd_off.size() - 1;
+	d.n_cmds = (uint32_t)t.kinds.size();
+	d.n_floats = (uint32_t)t.coords.size();
+	d.cmd_off = t.cmd_off.data();
+	d.dat_off = t.dat_off.data();
+	d.kinds = t.kinds.data();
+	d.coords = t.coords.data();
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	vgsdf_font *f = nullptr;
+	{
+		std::lock_guard<std::mutex> lock(mu_);
+		if (vgsdf_font_create_commands(c, &d, &f) != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_font_create_commands: ") + vgsdf_last_error(c));
+	}
+	const uint64_t got = vgsdf_font_device_bytes(f);
+	rf.fonts.emplace(key, f);
+	rf.bytes[device_] += got;
+	if (uploaded_bytes)
+		*uploaded_bytes += got;
+	return f;
+}
+
 void Renderer::set_resident_budget(uint64_t bytes_per_device)
 {
 	std::lock_guard<std::mutex> lock(resident_->mu);

@@ -264,15 +264,12 @@ struct MergedOutlines {
 	uint8_t *glyf_bytes = nullptr;
 	uint32_t n_parts = 0, n_glyf_bytes = 0;
 	// the form that names its glyphs (vgsdf_outlines_resident): the per-glyph arrays where ResidentBlockLayout has them
-	bool resident = false;
+	// (`commands`: the fonts are command fonts — CommandBlockLayout, no part_off between cmd_off and the names)
+	bool resident = false, commands = false;
 	uint16_t *glyph_id = nullptr, *font_of = nullptr;
 	std::vector<const vgsdf_font *> fonts; // the device copies of the group's faces
-	void layout_resident(uint32_t jobs_n, bool with_pbf)
+	template <class Layout> void place_named(const Layout &at, bool with_pbf)
 	{
-		n_jobs = jobs_n;
-		glyf = false;
-		resident = true;
-		const vgsdf::ResidentBlockLayout at(jobs_n, fonts.size(), with_pbf);
 		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
 		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
@@ -284,6 +281,17 @@ struct MergedOutlines {
 		cmd_off = dat_off = nullptr;
 		coords = nullptr;
 		kinds = nullptr;
+	}
+	void layout_resident(uint32_t jobs_n, bool with_pbf, bool command_fonts = false)
+	{
+		n_jobs = jobs_n;
+		glyf = false;
+		resident = true;
+		commands = command_fonts;
+		if (command_fonts)
+			place_named(vgsdf::CommandBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
+		else
+			place_named(vgsdf::ResidentBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
 	}
 	vgsdf_outlines_resident view_resident() const
 	{
@@ -305,7 +313,7 @@ struct MergedOutlines {
 		n_parts = parts_n;
 		n_glyf_bytes = bytes_n; // (a multiple of 4: every part's bytes are padded)
 		glyf = true;
-		resident = false;
+		resident = commands = false;
 		const vgsdf::GlyfBlockLayout at(jobs_n, parts_n, bytes_n, with_pbf);
 		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
@@ -339,7 +347,7 @@ struct MergedOutlines {
 	{
 		n_jobs = jobs_n;
 		glyf = false;
-		resident = false;
+		resident = commands = false;
 		const vgsdf::PackedBlockLayout at(jobs_n, n_cmds, n_floats, with_pbf);
 		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
@@ -460,6 +468,9 @@ public:
 	// (set_resident_budget, default 1 GiB; no eviction) — the caller takes the glyf form.  *uploaded_bytes (may be NULL) is
 	// raised by what this call put on the device (0: the copy was there).
 	const vgsdf_font *resident_font(int lane, const ResidentTable &table, uint64_t *uploaded_bytes = nullptr) const;
+	// the same for the command store of a face (vgsdf_font_create_commands): same registry (the tables' serials come from one
+	// sequence), same budget, no eviction.  nullptr: no command table, or over the budget — the caller goes on as without
+	const vgsdf_font *command_font(int lane, const CommandTable &table, uint64_t *uploaded_bytes = nullptr) const;
 	void set_resident_budget(uint64_t bytes_per_device);
 	uint64_t resident_bytes(int device) const; // what the renderer's resident fonts occupy on a device
 	void wait_outlines(int lane, std::vector<vgsdf_rect> &rects, HostBuffer<uint8_t> &out, uint64_t &out_bytes,

@@ -990,6 +990,13 @@ struct ResidentSink {
 };
 } // namespace
 
+// serials of the tables a renderer keeps device copies of: one sequence for both kinds, so a key names one table
+static uint64_t next_table_serial()
+{
+	static std::atomic<uint64_t> next_serial{1};
+	return next_serial.fetch_add(1);
+}
+
 const ResidentTable &Face::resident_table() const
 {
 	ResidentCell &cell = *resident_;
@@ -1016,8 +1023,56 @@ const ResidentTable &Face::resident_table() const
 			t.leaf_off.push_back((uint32_t)t.leaves.size());
 			t.slot_off.push_back((uint32_t)slot_sum);
 		}
-		static std::atomic<uint64_t> next_serial{1};
-		t.serial = next_serial.fetch_add(1);
+		t.serial = next_table_serial();
+		t.ok = true;
+	});
+	return cell.table;
+}
+
+namespace {
+// counts what a glyph's callbacks would add to a CommandTable; past the bounds it ends the walk (a composite can fan a few
+// kilobytes out to billions of callbacks)
+struct PastCommandBounds {};
+struct CountingBuilder final : OutlineBuilder {
+	uint64_t cmds = 0, floats = 0, max_cmds = 0;
+	void add(uint64_t n_floats)
+	{
+		cmds++, floats += n_floats;
+		if (cmds > max_cmds || floats > CommandTable::kMaxFloats)
+			throw PastCommandBounds{};
+	}
+	void move_to(float, float) override { add(2); }
+	void line_to(float, float) override { add(2); }
+	void quad_to(float, float, float, float) override { add(4); }
+	void curve_to(float, float, float, float, float, float) override { add(6); }
+	void close() override { add(0); }
+};
+} // namespace
+
+const CommandTable &Face::command_table() const
+{
+	CommandCell &cell = *commands_;
+	std::call_once(cell.once, [&] {
+		CommandTable &t = cell.table;
+		const uint32_t n = num_glyphs_;
+		CountingBuilder count;
+		count.max_cmds = (CommandTable::kMaxStoreBytes - 4 * ((uint64_t)n + 1)) / CommandTable::kStoreBytesPerCmd;
+		try {
+			for (uint32_t gid = 0; gid < n; gid++)
+				(void)outline_glyph((uint16_t)gid, count);
+		} catch (const PastCommandBounds &) {
+			return;
+		}
+		t.kinds.reserve((size_t)count.cmds);
+		t.coords.reserve((size_t)count.floats);
+		t.cmd_off.assign(1, 0);
+		t.dat_off.assign(1, 0);
+		for (uint32_t gid = 0; gid < n; gid++) {
+			(void)outline_glyph_packed((uint16_t)gid, t.kinds, t.coords);
+			t.cmd_off.push_back((uint32_t)t.kinds.size());
+			t.dat_off.push_back((uint32_t)t.coords.size());
+		}
+		t.serial = next_table_serial();
 		t.ok = true;
 	});
 	return cell.table;

@@ -57,6 +57,20 @@ struct ResidentTable {
 	static constexpr uint64_t kMaxLeaves = 1ull << 22, kMaxGlyphSlots = 1ull << 26, kMaxBytes = (1ull << 32) - 4;
 };
 
+// A face's outlines as the callbacks its reader delivers, glyph id by glyph id, in the arrays of the packed upload form
+// (vgsdf_font_cmds_desc of include/vgsdf.h): the resident form of every face this reader can read, whatever table its
+// outlines come from.  A glyph whose charstring or entry fails midway holds the callbacks delivered up to there.
+struct CommandTable {
+	bool ok = false;                // false: the store these commands make on the device (29 bytes each + 4 per glyph id), or their
+	                                // coordinates, pass what 32-bit offsets address
+	uint64_t serial = 0;            // of the table (never that of a ResidentTable): what a renderer keys its device copy by
+	std::vector<uint32_t> cmd_off;  // [numGlyphs + 1] into kinds
+	std::vector<uint32_t> dat_off;  // [numGlyphs + 1] into coords
+	std::vector<uint8_t> kinds;
+	std::vector<float> coords;
+	static constexpr uint64_t kMaxStoreBytes = (1ull << 32) - 4, kStoreBytesPerCmd = 29, kMaxFloats = kMaxStoreBytes / 4;
+};
+
 // Non-owning big-endian byte view with checked reads.
 class Bytes {
 public:
@@ -107,6 +121,10 @@ public:
 	// The resident form of the face: built once, on first use (thread-safe); the same walk and the same checks as
 	// glyph_parts, glyph id by glyph id, so a failing component leaves a glyph with the leaves recorded so far.
 	const ResidentTable &resident_table() const;
+	// The command form of the face: built once, on first use (thread-safe), by the very call Renderer::record makes for a
+	// glyph (outline_glyph_packed, return value ignored) for every glyph id.  The callbacks are counted first and the count stops at the
+	// bounds, so a face past them is refused without its table ever being allocated.
+	const CommandTable &command_table() const;
 	// ttf-parser's `tables().cmap.is_some()`; the reference refuses fonts without one (metadata.rs:104-107)
 	bool has_cmap() const { return has_cmap_; }
 	// glyph outlines this reader can emit: `glyf` + `loca`, or `CFF ` charstrings (ttf-parser's order: glyf first).
@@ -144,6 +162,11 @@ private:
 		ResidentTable table;
 	};
 	std::shared_ptr<ResidentCell> resident_ = std::make_shared<ResidentCell>(); // (shared by copies of the Face: same bytes)
+	struct CommandCell {
+		std::once_flag once;
+		CommandTable table;
+	};
+	std::shared_ptr<CommandCell> commands_ = std::make_shared<CommandCell>();
 
 	template <class B, bool PARTS> friend struct GlyfWalker;
 };

@@ -72,6 +72,10 @@ struct vgsdf_font {
 	std::vector<uint32_t> leaf_off;     // [n_glyph_ids + 1]
 	std::vector<uint32_t> slots;        // [n_glyph_ids] command slots of the glyph's leaves
 	uint32_t max_cap = 0, max_len = 0;  // the largest cmd_cap / byte_len among the leaves (the decoder's LDS is sized from them)
+	// a command font (vgsdf_font_create_commands): one allocation records | cmd_off | context bytes; `slots` holds the glyph
+	// ids' command counts and nothing of the leaves above is used
+	bool commands = false;
+	vgsdf::CommandFontRef cref{};
 };
 
 void fe_destroy(FrontEnd *fe)
@@ -195,6 +199,9 @@ struct FeInput {
 	uint32_t n_fonts = 0;
 	uint32_t res_max_cap = 0, res_max_len = 0; // over the fonts the submission names
 	bool res_scales_plain = true;
+	// ... against command fonts (neither packed nor glyf: the upload kernel gathers the expanded records and their context
+	// bytes from the fonts' stores; resident is NOT set)
+	bool commands = false;
 };
 
 // ---- submit, step by step (fe_submit below keeps their order: it is part of the contract with the device) ----
@@ -206,7 +213,7 @@ static int fe_check_args(vgsdf_ctx *ctx, const FeInput *in, uint32_t &n_cmds, ui
 		ctx->err = "vgsdf_outlines: NULL argument";
 		return VGSDF_E_ARG;
 	}
-	if ((in->pbf_pre == nullptr) != (in->pbf_fix == nullptr) || (in->pbf_fix && !in->packed && !in->glyf)) {
+	if ((in->pbf_pre == nullptr) != (in->pbf_fix == nullptr) || (in->pbf_fix && !in->packed && !in->glyf && !in->commands)) {
 		ctx->err = "vgsdf_outlines: pbf_pre and pbf_fix come together (packed and glyf forms only)";
 		return VGSDF_E_ARG;
 	}
@@ -219,7 +226,7 @@ static int fe_check_args(vgsdf_ctx *ctx, const FeInput *in, uint32_t &n_cmds, ui
 		return VGSDF_E_ARG;
 	}
 	n_cmds = n ? in->cmd_off[n] : 0;
-	if (n_cmds && !in->glyf && (in->packed ? !in->kinds : !in->cmds)) {
+	if (n_cmds && !in->glyf && !in->commands && (in->packed ? !in->kinds : !in->cmds)) {
 		ctx->err = "vgsdf_outlines: NULL command array";
 		return VGSDF_E_ARG;
 	}
@@ -301,6 +308,7 @@ struct FeUpload {
 	vgsdf::PackedBlockLayout pk; // (its head also serves the plain command form)
 	vgsdf::GlyfBlockLayout gl;
 	vgsdf::ResidentBlockLayout rs;
+	vgsdf::CommandBlockLayout cm;
 	size_t arrays_bytes;          // scale | shift_x | cmd_off [| dat_off]
 	const uint8_t *block = nullptr; // the caller's arrays are ONE page-locked block in their form's layout: one copy
 	size_t block_bytes = 0;
@@ -315,7 +323,7 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 	const uint32_t n = in->n_glyphs;
 	const bool pbf = in->pbf_fix != nullptr;
 	FeUpload up{vgsdf::PackedBlockLayout(n, n_cmds, n_floats, pbf), vgsdf::GlyfBlockLayout(n, in->n_parts, in->n_bytes, pbf),
-	            vgsdf::ResidentBlockLayout(n, in->n_fonts, pbf), 0};
+	            vgsdf::ResidentBlockLayout(n, in->n_fonts, pbf), vgsdf::CommandBlockLayout(n, in->n_fonts, pbf), 0};
 	up.arrays_bytes = in->packed ? up.pk.arrays_end : up.pk.end;
 	// the block is recognised by the caller's pointers: every array where the layout has it, counted from `scale`
 	const uint8_t *hb = (const uint8_t *)in->scale;
@@ -325,6 +333,9 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 	bool single = false;
 	if (in->resident) { // (gathered by the library itself, in the context's page-locked staging buffer)
 		up.block_bytes = up.rs.bytes;
+		single = true;
+	} else if (in->commands) { // (likewise)
+		up.block_bytes = up.cm.bytes;
 		single = true;
 	} else if (in->glyf) {
 		up.block_bytes = gl.bytes;
@@ -350,8 +361,9 @@ static int fe_reserve(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t 
 	const uint32_t n = in->n_glyphs;
 	FE_TRY(fe.cmds.ensure(sizeof(vgsdf::OutlineCmd) * (size_t)(n_cmds + 1)));
 	FE_TRY(fe.meta.ensure((in->resident ? up.rs.bytes + sizeof(vgsdf_glyf_part) * (size_t)in->n_parts
-	                                    : (in->glyf ? up.gl.bytes : (up.block ? up.pk.bytes : up.arrays_bytes))) + 16));
-	if (!in->resident) // (a resident submission's block lies there already)
+	                       : in->commands ? up.cm.bytes
+	                                      : (in->glyf ? up.gl.bytes : (up.block ? up.pk.bytes : up.arrays_bytes))) + 16));
+	if (!in->resident && !in->commands) // (a submission that names its glyphs: its block lies there already)
 		FE_TRY(fe.h_stage.ensure(up.arrays_bytes + 16));
 	FE_TRY(fe.cmd_open.ensure((size_t)n_cmds + 1));
 	FE_TRY(fe.counts.ensure(4 * (size_t)(n_cmds + 1)));
@@ -405,6 +417,25 @@ static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n
 			p.d_pbf_fix = dm + rs.pbf_fix;
 		}
 		fe.resident_upload_bytes = rs.bytes;
+		return VGSDF_OK;
+	}
+	if (in->commands) {
+		// ONE kernel again: the copy of the block and the gather of the named glyphs' records and context bytes from the
+		// fonts' stores (the block travels as above)
+		const vgsdf::CommandBlockLayout &cm = up.cm;
+		const void *src = up.mapped;
+		if (!src) {
+			FE_TRY(fe.coords.ensure(cm.bytes + 16));
+			FE_TRY(copy(fe.coords.p, up.block, cm.bytes));
+			src = fe.coords.p;
+		}
+		FE_KERNEL(vgsdf_resident_gather(src, dm, cm.bytes, (uint32_t)n, n_cmds, in->n_fonts, pbf, (vgsdf::OutlineCmd *)fe.cmds.p,
+		                                (uint8_t *)fe.cmd_open.p, st));
+		if (pbf) {
+			p.d_pbf_pre = (const uint32_t *)(dm + cm.pbf_pre);
+			p.d_pbf_fix = dm + cm.pbf_fix;
+		}
+		fe.resident_upload_bytes = cm.bytes;
 		return VGSDF_OK;
 	}
 	if (up.mapped)
@@ -505,6 +536,9 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	static const char *fuse_env = std::getenv("VGSDF_FUSE_CONTEXT"); // (measurement switch)
 	if (fuse_env && fuse_env[0] == '0')
 		decode_makes_context = false;
+	// command fonts: the gathered context bytes are the context pass's own for positive finite scales; a batch with an odd scale
+	// takes the pass over the gathered records, as the glyf form does
+	const bool gather_makes_context = in->commands && facts.scales_plain;
 	if (in->resident)
 		FE_KERNEL(vgsdf_glyf_decode_resident(up.d_parts, in->n_parts, up.d_bytes, (vgsdf::OutlineCmd *)fe.cmds.p, flagw, facts.glyf_max_cap,
 		                                     facts.glyf_max_len, decode_makes_context ? (uint8_t *)fe.cmd_open.p : nullptr, st));
@@ -514,7 +548,7 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	if (in->packed)
 		FE_KERNEL(vgsdf_outline_context_packed(up.d_kinds, up.d_coords, up.d_dat_off, d.cmd_off, d.scale, n, (vgsdf::OutlineCmd *)fe.cmds.p,
 		                                       (uint8_t *)fe.cmd_open.p, flagw, st));
-	else if (!decode_makes_context)
+	else if (!decode_makes_context && !gather_makes_context)
 		FE_KERNEL(vgsdf_outline_context(d.cmds, d.cmd_off, d.scale, n, (uint8_t *)fe.cmd_open.p, flagw, st));
 	FE_KERNEL(vgsdf_outline_count(d.cmds, (const uint8_t *)fe.cmd_open.p, n_cmds, d.cmd_off, n, d.scale, d.shift,
 	                              (uint32_t *)fe.counts.p, fe.cmd_box.p, (unsigned long long *)fe.cmd_mask.p, flagw, st));
@@ -599,13 +633,14 @@ static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_
 		FE_TRY(hipEventRecord(ctx->ev0, ctx->stream));
 	FeFacts facts;
 	// (a resident submission was validated before its block was gathered, and its offsets are the library's own sums)
-	if (in->resident) {
+	const bool named = in->resident || in->commands;
+	if (named) {
 		facts.glyf_max_cap = in->res_max_cap;
 		facts.glyf_max_len = in->res_max_len;
 		facts.scales_plain = in->res_scales_plain;
 	}
-	const bool validate_under_upload = up.mapped != nullptr && !in->resident; // (not one block uploaded by a kernel: validate first, as ever)
-	if (!validate_under_upload && !in->resident)
+	const bool validate_under_upload = up.mapped != nullptr && !named; // (not one block uploaded by a kernel: validate first, as ever)
+	if (!validate_under_upload && !named)
 		if (int rc = fe_validate(ctx, in, n_cmds, facts); rc != VGSDF_OK)
 			return rc;
 	// error word of this submission (FrontEnd::flag_slot)
@@ -933,6 +968,117 @@ int vgsdf_font_create(vgsdf_ctx *ctx, const vgsdf_font_desc *in, vgsdf_font **ou
 	return VGSDF_OK;
 }
 
+int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, vgsdf_font **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->cmd_off || !in->dat_off || (in->n_cmds && !in->kinds) || (in->n_floats && !in->coords)) {
+		ctx->err = "vgsdf_font_create_commands: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	const uint32_t n = in->n_glyph_ids, n_cmds = in->n_cmds;
+	// (the store: 28-byte records | cmd_off | a context byte per record)
+	if (n > 0x10000u || 29ull * n_cmds + 4ull * (n + 1) > 0xFFFFFFFCull || 4ull * in->n_floats > 0xFFFFFFFCull) {
+		ctx->err = "vgsdf_font_create_commands: more than 65536 glyph ids, or a store (29 bytes per command, 4 per glyph id) or "
+		           "coordinates past what 32-bit offsets address";
+		return VGSDF_E_ARG;
+	}
+	if (in->cmd_off[0] != 0 || in->cmd_off[n] != n_cmds || in->dat_off[0] != 0 || in->dat_off[n] != in->n_floats) {
+		ctx->err = "vgsdf_font_create_commands: cmd_off / dat_off do not run from 0 to n_cmds / n_floats";
+		return VGSDF_E_ARG;
+	}
+	vgsdf_font *f = new (std::nothrow) vgsdf_font();
+	if (!f) {
+		ctx->err = "vgsdf_font_create_commands: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	// everything a submission of these commands would be checked for per render, once: the offsets (they bound every read of
+	// the loop below), the kinds, and the coordinates every glyph's kinds carry against its dat_off range
+	f->slots.assign(n, 0);
+	for (uint32_t g = 0; g < n; g++) {
+		const uint32_t c0 = in->cmd_off[g], c1 = in->cmd_off[g + 1], d0 = in->dat_off[g], d1 = in->dat_off[g + 1];
+		if (c1 < c0 || c1 > n_cmds || d1 < d0 || d1 > in->n_floats) {
+			ctx->err = "vgsdf_font_create_commands: cmd_off / dat_off not ascending";
+			delete f;
+			return VGSDF_E_ARG;
+		}
+		uint64_t floats = 0;
+		uint32_t bad_kind = 0;
+		for (uint32_t c = c0; c < c1; c++) {
+			const uint32_t k = in->kinds[c];
+			bad_kind |= k > vgsdf::CMD_CLOSE;
+			floats += k <= vgsdf::CMD_LINE ? 2u : (k == vgsdf::CMD_QUAD ? 4u : (k == vgsdf::CMD_CURVE ? 6u : 0u));
+		}
+		if (bad_kind || floats != (uint64_t)(d1 - d0)) {
+			ctx->err = bad_kind ? "vgsdf_font_create_commands: unknown command kind"
+			                    : "vgsdf_font_create_commands: a glyph's dat_off range does not match its command kinds";
+			delete f;
+			return VGSDF_E_ARG;
+		}
+		f->slots[g] = c1 - c0;
+	}
+	f->device = ctx->device;
+	f->n_glyph_ids = n;
+	f->commands = true;
+	(void)hipSetDevice(ctx->device);
+	// the store: records | cmd_off | context bytes.  Beside it, for the duration of this call, what the packed form's context
+	// pass reads: scale (1: the bytes then say "ring open" and nothing else) | dat_off | coords | kinds | its error word
+	const size_t off_at = sizeof(vgsdf::OutlineCmd) * (size_t)n_cmds, open_at = off_at + 4 * ((size_t)n + 1), total = open_at + n_cmds;
+	const size_t t_dat = 8 * (size_t)n, t_coords = t_dat + 4 * ((size_t)n + 1), t_kinds = t_coords + 4 * (size_t)in->n_floats,
+	             t_flag = align_up(t_kinds + n_cmds, 16), t_total = t_flag + 16;
+	DevBuf tmp;
+	auto fail = [&](hipError_t e, const char *what) {
+		ctx->err = std::string("vgsdf_font_create_commands: ") + what + ": " + hipGetErrorString(e);
+		tmp.release();
+		f->store.release();
+		delete f;
+		return e == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;
+	};
+	if (hipError_t e = f->store.ensure(total + 16); e != hipSuccess)
+		return fail(e, "hipMalloc");
+	if (hipError_t e = tmp.ensure(t_total); e != hipSuccess)
+		return fail(e, "hipMalloc");
+	uint8_t *d = (uint8_t *)f->store.p, *t = (uint8_t *)tmp.p;
+	hipStream_t st = ctx->stream;
+	const std::vector<double> ones(n, 1.0);
+	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+	hipError_t e = copy(d + off_at, in->cmd_off, 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = copy(t, ones.data(), 8 * (size_t)n);
+	if (e == hipSuccess)
+		e = copy(t + t_dat, in->dat_off, 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = copy(t + t_coords, in->coords, 4 * (size_t)in->n_floats);
+	if (e == hipSuccess)
+		e = copy(t + t_kinds, in->kinds, n_cmds);
+	if (e == hipSuccess)
+		e = hipMemsetAsync(t + t_flag, 0, 16, st);
+	if (e == hipSuccess && n_cmds)
+		e = (hipError_t)vgsdf_outline_context_packed(t + t_kinds, (const float *)(t + t_coords), (const uint32_t *)(t + t_dat),
+		                                             (const uint32_t *)(d + off_at), (const double *)t, n, (vgsdf::OutlineCmd *)d, d + open_at,
+		                                             (uint32_t *)(t + t_flag), st);
+	uint32_t flag = 0;
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(&flag, t + t_flag, 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st); // the store is complete when the call returns: every context may name the font
+	if (e != hipSuccess)
+		return fail(e, "upload");
+	tmp.release();
+	if (flag) { // (what the walk above has ruled out, said by the pass itself)
+		ctx->err = "vgsdf_font_create_commands: the device's context pass refused the commands";
+		f->store.release();
+		delete f;
+		return VGSDF_E_ARG;
+	}
+	f->cref.cmds = (uint64_t)(uintptr_t)d;
+	f->cref.cmd_off = (uint64_t)(uintptr_t)(d + off_at);
+	f->cref.open = (uint64_t)(uintptr_t)(d + open_at);
+	*out = f;
+	return VGSDF_OK;
+}
+
 int vgsdf_font_free(vgsdf_ctx *ctx, vgsdf_font *font)
 {
 	if (!ctx)
@@ -981,6 +1127,12 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 			ctx->err = "vgsdf_outlines_resident: a NULL font, or a font of another device than the context's";
 			return VGSDF_E_ARG;
 		}
+	const bool commands = in->fonts[0]->commands;
+	for (uint32_t k = 1; k < in->n_fonts; k++)
+		if (in->fonts[k]->commands != commands) {
+			ctx->err = "vgsdf_outlines_resident: fonts of both kinds (vgsdf_font_create and vgsdf_font_create_commands) in one submission";
+			return VGSDF_E_ARG;
+		}
 	// every name before anything is touched
 	for (uint32_t g = 0; g < n; g++)
 		if (in->font_of[g] >= in->n_fonts || in->glyph_id[g] >= in->fonts[in->font_of[g]]->n_glyph_ids) {
@@ -999,8 +1151,48 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 		ctx->err = "vgsdf_outlines_submit: the previous submission of this context has not been waited for";
 		return VGSDF_E_ARG;
 	}
-	// the block: the caller's arrays gathered, the two running sums, the fonts' device addresses
 	const bool pbf = in->pbf_fix != nullptr;
+	if (commands) {
+		// the block: the caller's arrays gathered, the running sum of command counts, the fonts' device addresses
+		const vgsdf::CommandBlockLayout cm(n, in->n_fonts, pbf);
+		FE_TRY(fe.h_stage.ensure(cm.bytes + 16));
+		uint8_t *hb = (uint8_t *)fe.h_stage.p;
+		std::memcpy(hb + cm.scale, in->scale, 8 * (size_t)n);
+		std::memcpy(hb + cm.shift_x, in->shift_x, 8 * (size_t)n);
+		std::memcpy(hb + cm.glyph_id, in->glyph_id, 2 * (size_t)n);
+		std::memcpy(hb + cm.font_of, in->font_of, 2 * (size_t)n);
+		if (pbf) {
+			std::memcpy(hb + cm.pbf_pre, in->pbf_pre, 4 * (size_t)n);
+			std::memcpy(hb + cm.pbf_fix, in->pbf_fix, n);
+		}
+		std::memset(hb + cm.arrays_end, 0, cm.fonts - cm.arrays_end);
+		uint32_t *cmd_off = (uint32_t *)(hb + cm.cmd_off);
+		uint64_t cmds = 0;
+		for (uint32_t g = 0; g < n; g++) { // one table read and one addition per glyph
+			cmd_off[g] = (uint32_t)cmds;
+			cmds += in->fonts[in->font_of[g]]->slots[in->glyph_id[g]];
+			if (cmds > 0x7FFFFFFFull) {
+				ctx->err = "vgsdf_outlines_resident: more than 2^31 - 1 commands in one submission; split it";
+				return VGSDF_E_ARG;
+			}
+			f.res_scales_plain = f.res_scales_plain && in->scale[g] > 0.0 && in->scale[g] < HUGE_VAL;
+		}
+		cmd_off[n] = (uint32_t)cmds;
+		vgsdf::CommandFontRef *refs = (vgsdf::CommandFontRef *)(hb + cm.fonts);
+		for (uint32_t k = 0; k < in->n_fonts; k++)
+			refs[k] = in->fonts[k]->cref;
+		f.glyf = false;
+		f.resident = false;
+		f.commands = true;
+		f.cmd_off = cmd_off;
+		f.scale = (const double *)(hb + cm.scale);
+		f.shift_x = (const double *)(hb + cm.shift_x);
+		f.pbf_pre = pbf ? (const uint32_t *)(hb + cm.pbf_pre) : nullptr;
+		f.pbf_fix = pbf ? hb + cm.pbf_fix : nullptr;
+		f.n_fonts = in->n_fonts;
+		return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
+	}
+	// the block: the caller's arrays gathered, the two running sums, the fonts' device addresses
 	const vgsdf::ResidentBlockLayout rs(n, in->n_fonts, pbf);
 	FE_TRY(fe.h_stage.ensure(rs.bytes + 16));
 	uint8_t *hb = (uint8_t *)fe.h_stage.p;

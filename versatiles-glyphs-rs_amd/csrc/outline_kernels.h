@@ -72,6 +72,11 @@ int vgsdf_glyf_decode_resident(const void *parts, uint32_t n_parts, const void *
 // address of the page-locked block, or a device copy of it) to dst and expands the glyphs' leaves into parts_out[n_parts]
 int vgsdf_resident_expand(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_parts, uint32_t n_fonts,
                           bool with_pbf, void *parts_out, hipStream_t stream);
+// upload of a vgsdf_outlines_resident submission against command fonts: copies the block (CommandBlockLayout, padded to 16
+// bytes; src as above) to dst and gathers the named glyphs' records and context bytes from the fonts' stores
+// (vgsdf::CommandFontRef records in the block) into cmds_out[n_cmds] / cmd_open[n_cmds] at the block's cmd_off
+int vgsdf_resident_gather(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_fonts,
+                          bool with_pbf, vgsdf::OutlineCmd *cmds_out, uint8_t *cmd_open, hipStream_t stream);
 // upload by a kernel: src_mapped = device address of a page-locked, device-mapped host block (16-byte aligned), dst 16-byte aligned
 int vgsdf_copy_in(const void *src_mapped, void *dst, size_t bytes, hipStream_t stream);
 // cmd_open: one byte per command (bit 0: ring open in front of it, bit 1: the glyph's scale is not positive finite)

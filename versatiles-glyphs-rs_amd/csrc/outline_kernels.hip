@@ -1532,9 +1532,117 @@ __global__ __launch_bounds__(kExpandThreads) void resident_expand(const uint4 *_
 	}
 }
 
+// The upload of a submission that names its glyphs against COMMAND fonts (vgsdf_font_create_commands): copy_in's copy of the
+// ONE page-locked block (upload_layout.h, CommandBlockLayout) and the gather of every named glyph's expanded records and
+// context bytes from its font's store into the batch's command arrays at cmd_off[g] — a pure segmented copy: no decoder and,
+// when every scale is positive and finite, no context pass runs behind it.  A workgroup takes 256 glyphs as resident_expand
+// does: lane t reads glyph g0 + t's offset, id and font index with the same round trip as the copy's loads (and the font
+// references go to LDS), looks its glyph's first record up in the font's offset table and leaves the two source addresses in
+// LDS; then the COMMANDS of those glyphs — [cmd_off[g0], cmd_off[g0 + 256)) — are dealt to the lanes, kGatherUnroll per lane
+// and round with every load of a round in flight before its first store (a 5000-command glyph holds no lane back), and a
+// lane finds its command's glyph by bisection in LDS.  Records are 4-byte aligned only (28 bytes: seven dword copies); the
+// context bytes start at any byte offset on either side and travel a byte per lane.
+constexpr uint32_t kGatherUnroll = 4;
+__global__ __launch_bounds__(kExpandThreads) void resident_gather(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint32_t n16,
+                                                                  uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_fonts, uint32_t cmd_off_at,
+                                                                  uint32_t glyph_id_at, uint32_t font_of_at, uint32_t fonts_at,
+                                                                  uint32_t *__restrict__ cmds_out, uint8_t *__restrict__ open_out)
+{
+	__shared__ uint32_t s_cmd_off[kExpandThreads + 1];
+	__shared__ const uint32_t *s_recs[kExpandThreads];
+	__shared__ const uint8_t *s_open[kExpandThreads];
+	__shared__ CommandFontRef s_fonts[kExpandFontCache];
+	const uint32_t t = threadIdx.x, i = blockIdx.x * kExpandThreads + t, g0 = blockIdx.x * kExpandThreads;
+	const uint8_t *const sb = reinterpret_cast<const uint8_t *>(src);
+	const CommandFontRef *const fonts = reinterpret_cast<const CommandFontRef *>(sb + fonts_at);
+	uint4 v = make_uint4(0, 0, 0, 0);
+	if (i < n16)
+		v = src[i];
+	const uint32_t ng = g0 < n_glyphs ? min(kExpandThreads, n_glyphs - g0) : 0u;
+	uint32_t gid = 0, f = 0;
+	if (ng) {
+		const uint32_t *cmd_off = reinterpret_cast<const uint32_t *>(sb + cmd_off_at) + g0;
+		for (uint32_t k = t; k <= ng; k += kExpandThreads)
+			s_cmd_off[k] = cmd_off[k];
+		if (t < ng) {
+			gid = reinterpret_cast<const uint16_t *>(sb + glyph_id_at)[g0 + t];
+			f = reinterpret_cast<const uint16_t *>(sb + font_of_at)[g0 + t];
+		}
+		for (uint32_t k = t; k < min(n_fonts, kExpandFontCache); k += kExpandThreads)
+			s_fonts[k] = fonts[k];
+	}
+	if (i < n16)
+		dst[i] = v;
+	if (ng == 0) // (uniform in the workgroup)
+		return;
+	__syncthreads();
+	if (t < ng) {
+		const CommandFontRef ref = f < kExpandFontCache ? s_fonts[f] : fonts[f];
+		const uint32_t first = reinterpret_cast<const uint32_t *>(ref.cmd_off)[gid];
+		s_recs[t] = reinterpret_cast<const uint32_t *>(ref.cmds) + 7ull * first;
+		s_open[t] = reinterpret_cast<const uint8_t *>(ref.open) + first;
+	}
+	__syncthreads();
+	const uint32_t c1 = min(s_cmd_off[ng], n_cmds);
+	for (uint32_t base = s_cmd_off[0] + t; base < c1; base += kExpandThreads * kGatherUnroll) {
+		const uint32_t *rp[kGatherUnroll];
+		const uint8_t *op[kGatherUnroll];
+#pragma unroll
+		for (uint32_t u = 0; u < kGatherUnroll; u++) {
+			const uint32_t j = base + u * kExpandThreads;
+			// the glyph of command j: the last one whose commands begin at or in front of j (glyphs without commands share an offset)
+			uint32_t lo = 0, hi = ng;
+			while (hi - lo > 1u) {
+				const uint32_t mid = (lo + hi) >> 1;
+				if (s_cmd_off[mid] <= j)
+					lo = mid;
+				else
+					hi = mid;
+			}
+			const uint32_t k = j - s_cmd_off[lo];
+			rp[u] = j < c1 ? s_recs[lo] + 7u * k : nullptr;
+			op[u] = s_open[lo] + k;
+		}
+		uint32_t r[kGatherUnroll][7];
+		uint8_t o[kGatherUnroll];
+#pragma unroll
+		for (uint32_t u = 0; u < kGatherUnroll; u++)
+			if (rp[u]) {
+#pragma unroll
+				for (uint32_t w = 0; w < 7; w++)
+					r[u][w] = rp[u][w];
+				o[u] = *op[u];
+			}
+#pragma unroll
+		for (uint32_t u = 0; u < kGatherUnroll; u++)
+			if (rp[u]) {
+				const uint32_t j = base + u * kExpandThreads;
+				uint32_t *out = cmds_out + 7ull * j;
+#pragma unroll
+				for (uint32_t w = 0; w < 7; w++)
+					out[w] = r[u][w];
+				open_out[j] = o[u];
+			}
+	}
+}
+
 } // namespace vgsdf
 
 using namespace vgsdf;
+
+extern "C" int vgsdf_resident_gather(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_fonts,
+                                     bool with_pbf, OutlineCmd *cmds_out, uint8_t *cmd_open, hipStream_t stream)
+{
+	if (n_glyphs == 0)
+		return 0;
+	const CommandBlockLayout cl(n_glyphs, n_fonts, with_pbf);
+	const uint32_t n16 = (uint32_t)((block_bytes + 15) / 16); // (the block and its device copy are padded to 16 bytes)
+	const uint32_t grid = (std::max(n16, n_glyphs) + kExpandThreads - 1u) / kExpandThreads;
+	hipLaunchKernelGGL(resident_gather, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint4 *)src, (uint4 *)dst, n16, n_glyphs, n_cmds,
+	                   n_fonts, (uint32_t)cl.cmd_off, (uint32_t)cl.glyph_id, (uint32_t)cl.font_of, (uint32_t)cl.fonts, (uint32_t *)cmds_out,
+	                   cmd_open);
+	return (int)hipGetLastError();
+}
 
 extern "C" void vgsdf_glyf_limits(uint32_t *max_points, uint32_t *max_bytes, uint32_t *expand_font_cache)
 {

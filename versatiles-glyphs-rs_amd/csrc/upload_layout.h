@@ -69,4 +69,27 @@ struct ResidentBlockLayout : GlyphArraysLayout {
 	}
 };
 
+// The same form against command fonts (vgsdf_font_create_commands): a glyph's commands lie expanded in its font's store, so
+// the block needs no second running sum:
+// ... | glyph_id u16[n] | font_of u16[n] [| pbf_pre u32[n] | pbf_fix u8[n]] = 29 n + 4 bytes with the PBF arrays, then
+// (16-aligned) 32 bytes of device addresses per font, the whole a multiple of 16.  The upload kernel copies the block and
+// gathers every named glyph's records and context bytes behind cmd_off[g] of the batch's command arrays.
+struct CommandFontRef { // a command font's three arrays (device addresses)
+	uint64_t cmd_off, cmds, open, reserved; // u32[n_glyph_ids + 1] | 28-byte records | the context pass's byte per record
+};
+static_assert(sizeof(CommandFontRef) == sizeof(ResidentFontRef), "one size of font reference in every block that names fonts");
+struct CommandBlockLayout : GlyphArraysLayout {
+	size_t glyph_id, font_of, pbf_pre, pbf_fix, arrays_end, fonts, bytes;
+	CommandBlockLayout(size_t n, size_t n_fonts, bool with_pbf) : GlyphArraysLayout(n)
+	{
+		glyph_id = end;
+		font_of = glyph_id + 2 * n;
+		pbf_pre = font_of + 2 * n;
+		pbf_fix = pbf_pre + 4 * n;
+		arrays_end = with_pbf ? pbf_fix + n : pbf_pre;
+		fonts = (arrays_end + 15) / 16 * 16;
+		bytes = fonts + sizeof(CommandFontRef) * n_fonts; // (a multiple of 16)
+	}
+};
+
 } // namespace vgsdf

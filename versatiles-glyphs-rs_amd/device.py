@@ -61,6 +61,11 @@ class _CFontDesc(C.Structure):  # vgsdf_font_desc
                 ("leaves", C.c_void_p), ("bytes", C.c_void_p)]
 
 
+class _CFontCmdsDesc(C.Structure):  # vgsdf_font_cmds_desc
+    _fields_ = [("n_glyph_ids", C.c_uint32), ("n_cmds", C.c_uint32), ("n_floats", C.c_uint32), ("cmd_off", C.c_void_p),
+                ("dat_off", C.c_void_p), ("kinds", C.c_void_p), ("coords", C.c_void_p)]
+
+
 class _COutlinesResident(C.Structure):  # vgsdf_outlines_resident
     _fields_ = [("n_glyphs", C.c_uint32), ("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("font_of", C.c_void_p),
                 ("glyph_id", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("pbf_pre", C.c_void_p),
@@ -73,6 +78,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_host_alloc", "vgsdf_host_free", "vgsdf_outlines_prepare", "vgsdf_outlines_render", "vgsdf_outlines_render_into", "vgsdf_outlines_submit", "vgsdf_outlines_submit_packed", "vgsdf_outlines_submit_glyf", "vgsdf_outlines_wait", "vgsdf_outlines_segments",
     "vgsdf_add_counters", "vgsdf_reset_counters", "vgsdf_reduce_counters", "vgsdf_reduce_counters_rccl", "vgsdf_reduce_path", "vgsdf_outlines_pbf_positions", "vgsdf_outlines_peek",
     "vgsdf_font_create", "vgsdf_font_free", "vgsdf_font_device_bytes", "vgsdf_outlines_submit_resident", "vgsdf_outlines_resident_upload_bytes",
+    "vgsdf_font_create_commands",
 ]
 
 _lib = None
@@ -120,6 +126,7 @@ def load_library():
         L.vgsdf_outlines_pbf_positions.argtypes = [vp, vp]
         L.vgsdf_outlines_peek.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.vgsdf_font_create.argtypes = [vp, C.POINTER(_CFontDesc), C.POINTER(vp)]
+        L.vgsdf_font_create_commands.argtypes = [vp, C.POINTER(_CFontCmdsDesc), C.POINTER(vp)]
         L.vgsdf_font_free.argtypes = [vp, vp]
         L.vgsdf_font_device_bytes.argtypes = [vp]
         L.vgsdf_font_device_bytes.restype = C.c_uint64
@@ -448,6 +455,20 @@ class SdfContext:
         d = _CFontDesc(max(len(leaf_off), 1) - 1, len(leaves), len(store), leaf_off.ctypes.data, leaves.ctypes.data, store.ctypes.data)
         h = C.c_void_p()
         self._check(load_library().vgsdf_font_create(self._h, C.byref(d), C.byref(h)))
+        return ResidentFont(self, h)
+
+    def font_create_commands(self, cmd_off, dat_off, kinds, coords) -> ResidentFont:
+        """vgsdf_font_create_commands: a face's outline commands by glyph id (vgsdf_font_cmds_desc: cmd_off / dat_off[numGlyphs + 1]
+        into kinds / coords, the arrays of the packed form) -> ResidentFont, named by outlines_submit_resident like any other"""
+        cmd_off = np.ascontiguousarray(cmd_off, dtype=np.uint32)
+        dat_off = np.ascontiguousarray(dat_off, dtype=np.uint32)
+        kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+        coords = np.ascontiguousarray(coords, dtype=np.float32)
+        assert len(cmd_off) == len(dat_off) >= 1
+        d = _CFontCmdsDesc(len(cmd_off) - 1, len(kinds), len(coords), cmd_off.ctypes.data, dat_off.ctypes.data, kinds.ctypes.data,
+                           coords.ctypes.data)
+        h = C.c_void_p()
+        self._check(load_library().vgsdf_font_create_commands(self._h, C.byref(d), C.byref(h)))
         return ResidentFont(self, h)
 
     def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None):

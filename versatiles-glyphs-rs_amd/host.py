@@ -53,6 +53,8 @@ VGFONT_SYMBOLS = [
     "vg_glyph_batch_free", "vg_manager_record_outlines", "vg_outline_batch_view", "vg_outline_batch_free", "vg_pbf_encode",
     "vg_manager_record_glyf_parts", "vg_glyf_batch_view", "vg_glyf_batch_free",
     "vg_manager_resident_font_desc", "vg_manager_record_resident", "vg_resident_batch_view", "vg_resident_batch_free",
+    "vg_manager_command_font_desc", "vg_manager_record_resident_commands", "vg_manager_set_resident_commands",
+    "vg_manager_command_stats",
     "vg_manager_set_resident_fonts", "vg_renderer_set_resident_budget", "vg_renderer_preload_fonts", "vg_manager_resident_stats",
     "vg_manager_scan", "vg_manager_font_ids", "vg_manager_font_file_names", "vg_parse_font_name", "vg_manager_generate_name",
     "vg_encode_codeblocks", "vg_manager_index_json", "vg_manager_families_json", "vg_writer_new_tar_path",
@@ -92,6 +94,9 @@ def _L():
         L.vg_renderer_preload_fonts.argtypes = [vp, vp]
         L.vg_renderer_preload_fonts.restype = C.c_longlong
         L.vg_manager_resident_stats.argtypes = [vp, C.POINTER(ResidentStats)]
+        L.vg_manager_set_resident_commands.argtypes = [vp, C.c_int]
+        L.vg_manager_set_resident_commands.restype = None
+        L.vg_manager_command_stats.argtypes = [vp, C.POINTER(ResidentStats)]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -335,6 +340,19 @@ class FontManager:
         _L().vg_manager_resident_stats(self._h, C.byref(s))
         return {k: int(getattr(s, k)) for k, _ in ResidentStats._fields_}
 
+    def set_resident_commands(self, mode: int):
+        """0 (default).  1: groups that cannot take a glyf form (CFF / CFF2 faces, fonts the device refused) are submitted by
+        (font, glyph id) against command stores instead of being read by the host on every render; 2: every group is; same
+        bytes in every mode"""
+        _L().vg_manager_set_resident_commands(self._h, int(mode))
+
+    def command_stats(self) -> dict:
+        """of the last render: groups submitted by name against command stores, stores uploaded during it, their bytes on the
+        device, bytes of those submissions' upload blocks (vg_command_stats: the fields of resident_stats)"""
+        s = ResidentStats()
+        _L().vg_manager_command_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in ResidentStats._fields_}
+
     def set_lane_form(self, form: int):
         """several device lanes: -1 / 2 hybrid (whole (font, block) tasks, the heaviest blocks split between lanes), 1 whole tasks
         only, 0 glyph-level shards of every font + merge"""
@@ -564,15 +582,40 @@ class FontManager:
         return {"leaf_off": arr(d.leaf_off, d.n_glyph_ids + 1, np.uint32), "leaves": arr(d.leaves, d.n_leaves, GLYF_PART_DTYPE),
                 "bytes": arr(d.bytes, d.n_bytes, np.uint8)}
 
-    def record_resident(self, font_id: str) -> dict:
+    def command_font_desc(self, font_id: str, file_index: int = 0) -> dict:
+        """description of one file of a font id for vgsdf_font_create_commands: {cmd_off, dat_off, kinds, coords} (numpy
+        copies); for every glyph id the callbacks the reader delivers, in the arrays of the packed form"""
+        from .device import _CFontCmdsDesc
+        L = _L()
+        L.vg_manager_command_font_desc.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        d = _CFontCmdsDesc()
+        if L.vg_manager_command_font_desc(self._h, font_id.encode(), file_index, C.byref(d)) != 0:
+            raise RuntimeError(_err())
+
+        def arr(ptr, count, dt):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dt)
+            buf = (C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dt, count=count).copy()
+
+        return {"cmd_off": arr(d.cmd_off, d.n_glyph_ids + 1, np.uint32), "dat_off": arr(d.dat_off, d.n_glyph_ids + 1, np.uint32),
+                "kinds": arr(d.kinds, d.n_cmds, np.uint8), "coords": arr(d.coords, d.n_floats, np.float32)}
+
+    def record_resident_commands(self, font_id: str) -> dict:
+        """record_resident against command fonts: for any face the reader can read (CFF, CFF2, glyf)"""
+        return self.record_resident(font_id, _commands=True)
+
+    def record_resident(self, font_id: str, _commands: bool = False) -> dict:
         """what a resident submission of the font names: {font_of, glyph_id, scale, shift_x, ids, advances, n_files}"""
         L = _L()
         L.vg_manager_record_resident.restype = C.c_void_p
         L.vg_manager_record_resident.argtypes = [C.c_void_p, C.c_char_p]
+        L.vg_manager_record_resident_commands.restype = C.c_void_p
+        L.vg_manager_record_resident_commands.argtypes = [C.c_void_p, C.c_char_p]
         L.vg_resident_batch_view.argtypes = [C.c_void_p, C.c_void_p]
         L.vg_resident_batch_free.argtypes = [C.c_void_p]
         L.vg_resident_batch_free.restype = None
-        h = L.vg_manager_record_resident(self._h, font_id.encode())
+        h = (L.vg_manager_record_resident_commands if _commands else L.vg_manager_record_resident)(self._h, font_id.encode())
         if not h:
             raise RuntimeError(_err())
         try:
