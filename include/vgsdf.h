@@ -168,7 +168,11 @@ int vgsdf_outlines_render_into(vgsdf_ctx *ctx, const vgsdf_outlines *in, vgsdf_r
  * use two contexts to keep the GPU busy while the host prepares the next batch and encodes the previous one):
  * submit enqueues the upload, the front-end and the raster and returns at once; wait synchronises and reports as
  * vgsdf_outlines_render_into does.  in->cmds and out_bitmaps must stay valid and untouched in between
- * (out_bitmaps may be NULL: no raster is enqueued, wait then equals vgsdf_outlines_prepare). */
+ * (out_bitmaps may be NULL: no raster is enqueued, wait then equals vgsdf_outlines_prepare).
+ * A submit that fails — this one or any of the vgsdf_outlines_submit_* forms below — leaves nothing to wait for, and nothing
+ * of the caller's memory in use: whatever it had enqueued before the failing step (the upload of a page-locked block, which a
+ * kernel reads in place and under which the block's offsets are validated; a raster storing through out_bitmaps) has
+ * finished when the call returns.  Input and output buffers may be freed or reused at once. */
 int vgsdf_outlines_submit(vgsdf_ctx *ctx, const vgsdf_outlines *in, uint8_t *out_bitmaps, size_t out_capacity);
 /* The same commands in their compact form for the upload: one kind byte per command and only the coordinates the kind
  * carries, in callback order (move_to / line_to: x y; quad_to: x1 y1 x y; curve_to: x1 y1 x2 y2 x y; close: none) —

@@ -3,6 +3,7 @@
 //   vgsdf_device.cpp        contexts, resident batches, transfers and launches
 //   work_list.cpp           the host's planner of a resident batch's work list
 //   outline_front_end.cpp   outline commands in, rects and bitmaps out
+//   resident_fonts.cpp      fonts uploaded once and named by glyph id (resident_fonts.h: what the front-end reads of them)
 //   run_counters.cpp        run counters and their RCCL reduction
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2070,16 +2070,26 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 		if (G.n_jobs) {
 			timings_.fe_groups++;
 			timings_.fe_max_group_glyphs = std::max<uint64_t>(timings_.fe_max_group_glyphs, G.n_jobs);
-			if (G.m.resident) {
-				uint64_t block = 0;
+			uint64_t block = 0;
+			switch (G.m.form) {
+			case MergedOutlines::Form::ResidentGlyf:
 				renderer.submit_outlines((int)(k & 1), G.m.view_resident(), G.out, &block);
-				(G.m.commands ? timings_.command_groups : timings_.resident_groups)++;
-				(G.m.commands ? timings_.command_block_bytes : timings_.resident_block_bytes) += block;
-			} else if (G.m.glyf) {
+				timings_.resident_groups++;
+				timings_.resident_block_bytes += block;
+				break;
+			case MergedOutlines::Form::ResidentCommands:
+				renderer.submit_outlines((int)(k & 1), G.m.view_resident(), G.out, &block);
+				timings_.command_groups++;
+				timings_.command_block_bytes += block;
+				break;
+			case MergedOutlines::Form::Glyf:
 				renderer.submit_outlines((int)(k & 1), G.m.view_glyf(), G.out);
 				timings_.glyf_groups++;
-			} else
+				break;
+			case MergedOutlines::Form::Packed:
 				renderer.submit_outlines((int)(k & 1), G.m.view(), G.out);
+				break;
+			}
 			in_flight[k & 1] = true;
 		}
 		timings_.device_s += now_s() - t;

@@ -390,7 +390,9 @@ vgsdf_ctx *Renderer::lane_ctx(int lane) const
 	return ctx2_;
 }
 
-void Renderer::submit_outlines(int lane, const vgsdf_outlines_packed &v, HostBuffer<uint8_t> &out) const
+template <class Batch>
+void Renderer::submit_on_lane(int lane, const Batch &v, HostBuffer<uint8_t> &out, int (*submit)(vgsdf_ctx *, const Batch *, uint8_t *, size_t),
+                              const char *name, uint64_t *block_bytes) const
 {
 	if (mode_ != Mode::Hip)
 		throw std::runtime_error("render_outlines needs the HIP renderer (the device front-end has no CPU form)");
@@ -403,54 +405,29 @@ void Renderer::submit_outlines(int lane, const vgsdf_outlines_packed &v, HostBuf
 		if (out.capacity() == 0)
 			out.ensure((size_t)v.n_glyphs * 480 + 16384);
 		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_outlines_submit_packed(c, &v, out.data(), out.capacity()) != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_outlines_submit_packed: ") + vgsdf_last_error(c));
-	} catch (...) {
-		lane_mu_[lane].unlock();
-		throw;
-	}
-}
-
-void Renderer::submit_outlines(int lane, const vgsdf_outlines_glyf &v, HostBuffer<uint8_t> &out) const
-{
-	if (mode_ != Mode::Hip)
-		throw std::runtime_error("render_outlines needs the HIP renderer (the device front-end has no CPU form)");
-	lane &= 1;
-	vgsdf_ctx *c = lane_ctx(lane);
-	lane_mu_[lane].lock();
-	// one submission: the raster writes into `out` as it stands (capacity kept from earlier groups; first guess
-	// 448 bytes per glyph, the average of the fixture fonts) — a second step in wait only when that was too small
-	try {
-		if (out.capacity() == 0)
-			out.ensure((size_t)v.n_glyphs * 480 + 16384);
-		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_outlines_submit_glyf(c, &v, out.data(), out.capacity()) != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_outlines_submit_glyf: ") + vgsdf_last_error(c));
-	} catch (...) {
-		lane_mu_[lane].unlock();
-		throw;
-	}
-}
-
-void Renderer::submit_outlines(int lane, const vgsdf_outlines_resident &v, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const
-{
-	if (mode_ != Mode::Hip)
-		throw std::runtime_error("render_outlines needs the HIP renderer (the device front-end has no CPU form)");
-	lane &= 1;
-	vgsdf_ctx *c = lane_ctx(lane);
-	lane_mu_[lane].lock();
-	try {
-		if (out.capacity() == 0)
-			out.ensure((size_t)v.n_glyphs * 480 + 16384);
-		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_outlines_submit_resident(c, &v, out.data(), out.capacity()) != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_outlines_submit_resident: ") + vgsdf_last_error(c));
+		if (submit(c, &v, out.data(), out.capacity()) != VGSDF_OK)
+			throw std::runtime_error(std::string(name) + ": " + vgsdf_last_error(c));
 		if (block_bytes)
 			*block_bytes = vgsdf_outlines_resident_upload_bytes(c);
 	} catch (...) {
 		lane_mu_[lane].unlock();
 		throw;
 	}
+}
+
+void Renderer::submit_outlines(int lane, const vgsdf_outlines_packed &v, HostBuffer<uint8_t> &out) const
+{
+	submit_on_lane(lane, v, out, vgsdf_outlines_submit_packed, "vgsdf_outlines_submit_packed");
+}
+
+void Renderer::submit_outlines(int lane, const vgsdf_outlines_glyf &v, HostBuffer<uint8_t> &out) const
+{
+	submit_on_lane(lane, v, out, vgsdf_outlines_submit_glyf, "vgsdf_outlines_submit_glyf");
+}
+
+void Renderer::submit_outlines(int lane, const vgsdf_outlines_resident &v, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const
+{
+	submit_on_lane(lane, v, out, vgsdf_outlines_submit_resident, "vgsdf_outlines_submit_resident", block_bytes);
 }
 
 const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint64_t *uploaded_bytes) const

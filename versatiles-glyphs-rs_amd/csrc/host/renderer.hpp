@@ -249,6 +249,9 @@ struct ResidentBatch {
 // order vgsdf.h names for a single-copy upload: scale | shift_x | cmd_off | dat_off | (pad to 8) | coords | kinds
 // (the offsets: ../upload_layout.h, which the device layer recognises the block by).
 struct MergedOutlines {
+	// which block layout the blob has, and so which view hands it to the device: view() / view_glyf() / view_resident()
+	enum class Form { Packed, Glyf, ResidentGlyf, ResidentCommands };
+	Form form = Form::Packed;
 	std::vector<GlyphJob> jobs;
 	HostBuffer<uint8_t> blob{true};
 	uint32_t n_jobs = 0;
@@ -259,39 +262,20 @@ struct MergedOutlines {
 	uint32_t *pbf_pre = nullptr; // in-place PBF assembly (vgsdf.h): bytes reserved in front of a glyph's entry
 	uint8_t *pbf_fix = nullptr;  // ... and the lengths of its id / advance fields; NULL when `with_pbf` was false
 	// the glyf form (vgsdf_outlines_glyf) in the same block: scale | shift_x | cmd_off | (pad to 8) | parts | bytes [| pbf_pre | pbf_fix]
-	bool glyf = false;
 	vgsdf_glyf_part *parts = nullptr;
 	uint8_t *glyf_bytes = nullptr;
 	uint32_t n_parts = 0, n_glyf_bytes = 0;
-	// the form that names its glyphs (vgsdf_outlines_resident): the per-glyph arrays where ResidentBlockLayout has them
-	// (`commands`: the fonts are command fonts — CommandBlockLayout, no part_off between cmd_off and the names)
-	bool resident = false, commands = false;
+	// the forms that name their glyphs (vgsdf_outlines_resident): the per-glyph arrays where ResidentBlockLayout has them
+	// (command fonts: CommandBlockLayout, no part_off between cmd_off and the names)
 	uint16_t *glyph_id = nullptr, *font_of = nullptr;
 	std::vector<const vgsdf_font *> fonts; // the device copies of the group's faces
-	template <class Layout> void place_named(const Layout &at, bool with_pbf)
-	{
-		blob.ensure(at.bytes + 16);
-		uint8_t *b = blob.data();
-		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
-		pbf_fix = with_pbf ? b + at.pbf_fix : nullptr;
-		scale = reinterpret_cast<double *>(b + at.scale);
-		shift_x = reinterpret_cast<double *>(b + at.shift_x);
-		glyph_id = reinterpret_cast<uint16_t *>(b + at.glyph_id);
-		font_of = reinterpret_cast<uint16_t *>(b + at.font_of);
-		cmd_off = dat_off = nullptr;
-		coords = nullptr;
-		kinds = nullptr;
-	}
+
 	void layout_resident(uint32_t jobs_n, bool with_pbf, bool command_fonts = false)
 	{
-		n_jobs = jobs_n;
-		glyf = false;
-		resident = true;
-		commands = command_fonts;
 		if (command_fonts)
-			place_named(vgsdf::CommandBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
+			place_named(Form::ResidentCommands, jobs_n, vgsdf::CommandBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
 		else
-			place_named(vgsdf::ResidentBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
+			place_named(Form::ResidentGlyf, jobs_n, vgsdf::ResidentBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
 	}
 	vgsdf_outlines_resident view_resident() const
 	{
@@ -309,22 +293,10 @@ struct MergedOutlines {
 	}
 	void layout_glyf(uint32_t jobs_n, uint32_t parts_n, uint32_t bytes_n, bool with_pbf)
 	{
-		n_jobs = jobs_n;
 		n_parts = parts_n;
 		n_glyf_bytes = bytes_n; // (a multiple of 4: every part's bytes are padded)
-		glyf = true;
-		resident = commands = false;
 		const vgsdf::GlyfBlockLayout at(jobs_n, parts_n, bytes_n, with_pbf);
-		blob.ensure(at.bytes + 16);
-		uint8_t *b = blob.data();
-		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
-		pbf_fix = with_pbf ? b + at.pbf_fix : nullptr;
-		scale = reinterpret_cast<double *>(b + at.scale);
-		shift_x = reinterpret_cast<double *>(b + at.shift_x);
-		cmd_off = reinterpret_cast<uint32_t *>(b + at.cmd_off);
-		dat_off = nullptr;
-		coords = nullptr;
-		kinds = nullptr;
+		uint8_t *b = place_shared(Form::Glyf, jobs_n, at, with_pbf);
 		parts = reinterpret_cast<vgsdf_glyf_part *>(b + at.parts);
 		glyf_bytes = b + at.glyf_bytes;
 	}
@@ -345,17 +317,8 @@ struct MergedOutlines {
 	}
 	void layout(uint32_t jobs_n, uint32_t n_cmds, uint32_t n_floats, bool with_pbf = false)
 	{
-		n_jobs = jobs_n;
-		glyf = false;
-		resident = commands = false;
 		const vgsdf::PackedBlockLayout at(jobs_n, n_cmds, n_floats, with_pbf);
-		blob.ensure(at.bytes + 16);
-		uint8_t *b = blob.data();
-		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
-		pbf_fix = with_pbf ? b + at.pbf_fix : nullptr;
-		scale = reinterpret_cast<double *>(b + at.scale);
-		shift_x = reinterpret_cast<double *>(b + at.shift_x);
-		cmd_off = reinterpret_cast<uint32_t *>(b + at.cmd_off);
+		uint8_t *b = place_shared(Form::Packed, jobs_n, at, with_pbf);
 		dat_off = reinterpret_cast<uint32_t *>(b + at.dat_off);
 		coords = reinterpret_cast<float *>(b + at.coords);
 		kinds = b + at.kinds;
@@ -373,6 +336,33 @@ struct MergedOutlines {
 		o.pbf_pre = pbf_pre;
 		o.pbf_fix = pbf_fix;
 		return o;
+	}
+
+private:
+	// The arrays every layout has — pbf_pre, pbf_fix, scale, shift_x, cmd_off — placed in a blob of the layout's size; the
+	// packed form's own arrays are cleared, and the caller adds those of its form.  Returns the blob
+	template <class Layout> uint8_t *place_shared(Form f, uint32_t jobs_n, const Layout &at, bool with_pbf)
+	{
+		form = f;
+		n_jobs = jobs_n;
+		blob.ensure(at.bytes + 16);
+		uint8_t *b = blob.data();
+		pbf_pre = with_pbf ? reinterpret_cast<uint32_t *>(b + at.pbf_pre) : nullptr;
+		pbf_fix = with_pbf ? b + at.pbf_fix : nullptr;
+		scale = reinterpret_cast<double *>(b + at.scale);
+		shift_x = reinterpret_cast<double *>(b + at.shift_x);
+		cmd_off = reinterpret_cast<uint32_t *>(b + at.cmd_off);
+		dat_off = nullptr;
+		coords = nullptr;
+		kinds = nullptr;
+		return b;
+	}
+	template <class Layout> void place_named(Form f, uint32_t jobs_n, const Layout &at, bool with_pbf)
+	{
+		uint8_t *b = place_shared(f, jobs_n, at, with_pbf);
+		cmd_off = nullptr; // (the library sums the offsets itself)
+		glyph_id = reinterpret_cast<uint16_t *>(b + at.glyph_id);
+		font_of = reinterpret_cast<uint16_t *>(b + at.font_of);
 	}
 };
 
@@ -502,6 +492,11 @@ private:
 	mutable vgsdf_ctx *ctx2_ = nullptr; // lane 1 of the two-deep pipeline (created on first use)
 	mutable std::mutex lane_mu_[2];     // held from submit_outlines to wait_outlines
 	vgsdf_ctx *lane_ctx(int lane) const;
+	// what the submit_outlines overloads share: the lane held from here to wait_outlines (released when this throws), the first
+	// capacity guess for `out`, the context's lock around the C call `submit` (`name`: for the error)
+	template <class Batch>
+	void submit_on_lane(int lane, const Batch &v, HostBuffer<uint8_t> &out, int (*submit)(vgsdf_ctx *, const Batch *, uint8_t *, size_t),
+	                    const char *name, uint64_t *block_bytes = nullptr) const;
 	std::vector<std::shared_ptr<Renderer>> peers_; // device lanes 1 .. N-1 of a multi-device renderer
 	struct ResidentFonts { // of a renderer and its peers
 		std::mutex mu;

@@ -6,10 +6,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
+#include <variant>
 #include <vector>
 
 #include "device_internal.h"
 #include "outline_kernels.h"
+#include "resident_fonts.h"
 #include "upload_layout.h"
 #include "work_plan.h"
 
@@ -19,6 +22,7 @@ struct FePending {
 	uint32_t n = 0, n_cmds = 0;
 	size_t hdr_off = 0, rh_bytes = 0, at_off = 0; // rects | PlanHeader | (in-place PBF assembly) bitmap positions u64[n]
 	bool span = false, spec = false;
+	bool copy_stream_waits = false; // the read-back's wait for the plan has been enqueued on the copy stream
 	bool spec_direct = false; // the raster stores through the device mapping of the caller's page-locked buffer
 	const uint32_t *d_pbf_pre = nullptr; // device copies of the in-place PBF inputs (NULL: bitmaps packed back to back)
 	const uint8_t *d_pbf_fix = nullptr;
@@ -62,22 +66,6 @@ struct FrontEnd {
 	}
 };
 
-// A font resident on a device (vgsdf_font_create): one allocation leaves | bytes | leaf_off, and what the host needs per
-// glyph id to lay a submission out without looking at a leaf
-struct vgsdf_font {
-	int device = 0;
-	uint32_t n_glyph_ids = 0, n_leaves = 0, n_bytes = 0;
-	DevBuf store;
-	vgsdf::ResidentFontRef ref{};       // device addresses of the three arrays
-	std::vector<uint32_t> leaf_off;     // [n_glyph_ids + 1]
-	std::vector<uint32_t> slots;        // [n_glyph_ids] command slots of the glyph's leaves
-	uint32_t max_cap = 0, max_len = 0;  // the largest cmd_cap / byte_len among the leaves (the decoder's LDS is sized from them)
-	// a command font (vgsdf_font_create_commands): one allocation records | cmd_off | context bytes; `slots` holds the glyph
-	// ids' command counts and nothing of the leaves above is used
-	bool commands = false;
-	vgsdf::CommandFontRef cref{};
-};
-
 void fe_destroy(FrontEnd *fe)
 {
 	if (!fe)
@@ -85,8 +73,6 @@ void fe_destroy(FrontEnd *fe)
 	fe->release_all();
 	delete fe;
 }
-
-extern "C" {
 
 #define FE_TRY(expr) HIP_TRY_AS(ctx, "vgsdf_outlines: " #expr, expr)
 // (a launch: its failure is never reported as VGSDF_E_OOM)
@@ -175,33 +161,40 @@ hipError_t fe_ensure_segs(FrontEnd &fe, size_t want, uint32_t n_glyphs)
 }
 } // namespace
 
-// the two input forms of a submission: 28-byte command records, or kinds + coordinates (vgsdf_outlines_packed)
+// The input forms of a submission.  A FeInput has exactly one; the legal states are the enumerators
+enum class FeForm {
+	Records,          // 28-byte command records (vgsdf_outlines)
+	Packed,           // kinds + the coordinates they carry (vgsdf_outlines_packed)
+	Glyf,             // the glyphs' `glyf` arrays as parts; cmd_off counts command SLOTS (vgsdf_outlines_glyf)
+	ResidentGlyf,     // glyphs named by (font, glyph id) of fonts from vgsdf_font_create: the upload kernel expands their leaves into parts
+	ResidentCommands, // ... of fonts from vgsdf_font_create_commands: the upload kernel gathers their records and context bytes
+};
 struct FeInput {
+	FeForm form = FeForm::Records;
 	uint32_t n_glyphs = 0;
 	const uint32_t *cmd_off = nullptr;
 	const double *scale = nullptr, *shift_x = nullptr;
-	const vgsdf_outline_cmd *cmds = nullptr;
-	const uint32_t *dat_off = nullptr;
+	const vgsdf_outline_cmd *cmds = nullptr; // Records
+	const uint32_t *dat_off = nullptr;       // Packed
 	const uint8_t *kinds = nullptr;
 	const float *coords = nullptr;
-	const uint32_t *pbf_pre = nullptr; // in-place PBF assembly (vgsdf_outlines_packed): both or neither
+	const uint32_t *pbf_pre = nullptr; // in-place PBF assembly (every form but Records): both or neither
 	const uint8_t *pbf_fix = nullptr;
-	bool packed = false;
-	// vgsdf_outlines_glyf: the glyphs' `glyf` arrays instead of commands (cmd_off counts command SLOTS)
-	bool glyf = false;
-	const vgsdf_glyf_part *parts = nullptr;
+	const vgsdf_glyf_part *parts = nullptr; // Glyf (ResidentGlyf: n_parts only — the parts come to be on the device)
 	uint32_t n_parts = 0;
 	const uint8_t *bytes = nullptr;
 	uint32_t n_bytes = 0;
-	// vgsdf_outlines_resident (glyf is set too: the decoder runs on parts — which the upload kernel expands on the device).
-	// The arrays above point into the block the library gathered in the context's page-locked staging buffer
-	bool resident = false;
+	// the named forms: the arrays above point into the block the library gathered in the context's page-locked staging buffer
 	uint32_t n_fonts = 0;
 	uint32_t res_max_cap = 0, res_max_len = 0; // over the fonts the submission names
 	bool res_scales_plain = true;
-	// ... against command fonts (neither packed nor glyf: the upload kernel gathers the expanded records and their context
-	// bytes from the fonts' stores; resident is NOT set)
-	bool commands = false;
+
+	// the glyphs are named, not sent: the library validated the names, summed the offsets itself and gathered the block
+	bool names_glyphs() const { return form == FeForm::ResidentGlyf || form == FeForm::ResidentCommands; }
+	// the command records come out of the device's glyf decoder, which runs on parts
+	bool decodes_glyf() const { return form == FeForm::Glyf || form == FeForm::ResidentGlyf; }
+	// the form may bring pbf_pre / pbf_fix
+	bool takes_pbf() const { return form != FeForm::Records; }
 };
 
 // ---- submit, step by step (fe_submit below keeps their order: it is part of the contract with the device) ----
@@ -209,11 +202,11 @@ struct FeInput {
 // 1. argument checks: nothing is touched on a bad call.  Sets the command and coordinate counts of the batch
 static int fe_check_args(vgsdf_ctx *ctx, const FeInput *in, uint32_t &n_cmds, uint32_t &n_floats)
 {
-	if (!in || (in->n_glyphs && (!in->cmd_off || !in->scale || !in->shift_x || (in->packed && !in->dat_off)))) {
+	if (!in || (in->n_glyphs && (!in->cmd_off || !in->scale || !in->shift_x || (in->form == FeForm::Packed && !in->dat_off)))) {
 		ctx->err = "vgsdf_outlines: NULL argument";
 		return VGSDF_E_ARG;
 	}
-	if ((in->pbf_pre == nullptr) != (in->pbf_fix == nullptr) || (in->pbf_fix && !in->packed && !in->glyf && !in->commands)) {
+	if ((in->pbf_pre == nullptr) != (in->pbf_fix == nullptr) || (in->pbf_fix && !in->takes_pbf())) {
 		ctx->err = "vgsdf_outlines: pbf_pre and pbf_fix come together (packed and glyf forms only)";
 		return VGSDF_E_ARG;
 	}
@@ -226,19 +219,19 @@ static int fe_check_args(vgsdf_ctx *ctx, const FeInput *in, uint32_t &n_cmds, ui
 		return VGSDF_E_ARG;
 	}
 	n_cmds = n ? in->cmd_off[n] : 0;
-	if (n_cmds && !in->glyf && !in->commands && (in->packed ? !in->kinds : !in->cmds)) {
+	if (n_cmds && ((in->form == FeForm::Packed && !in->kinds) || (in->form == FeForm::Records && !in->cmds))) {
 		ctx->err = "vgsdf_outlines: NULL command array";
 		return VGSDF_E_ARG;
 	}
-	if (in->glyf && !in->resident && ((in->n_parts && (!in->parts || !in->bytes)) || (in->n_bytes & 3u))) {
+	if (in->form == FeForm::Glyf && ((in->n_parts && (!in->parts || !in->bytes)) || (in->n_bytes & 3u))) {
 		ctx->err = "vgsdf_outlines_glyf: NULL parts / bytes, or n_bytes not a multiple of 4";
 		return VGSDF_E_ARG;
 	}
-	if (in->packed && n && (in->dat_off[0] != 0 || (in->dat_off[n] && !in->coords))) {
+	if (in->form == FeForm::Packed && n && (in->dat_off[0] != 0 || (in->dat_off[n] && !in->coords))) {
 		ctx->err = in->dat_off[0] != 0 ? "vgsdf_outlines: dat_off[0] must be 0" : "vgsdf_outlines: NULL coordinate array";
 		return VGSDF_E_ARG;
 	}
-	n_floats = in->packed && n ? in->dat_off[n] : 0u;
+	n_floats = in->form == FeForm::Packed && n ? in->dat_off[n] : 0u;
 	return VGSDF_OK;
 }
 
@@ -266,7 +259,7 @@ static int fe_validate(vgsdf_ctx *ctx, const FeInput *in, uint32_t n_cmds, FeFac
 		ctx->err = "vgsdf_outlines: cmd_off not monotone";
 		return VGSDF_E_ARG;
 	}
-	if (in->glyf) {
+	if (in->form == FeForm::Glyf) {
 		// the parts tile the command slots in order, and their bytes lie inside `bytes` (what the bytes SAY is checked on
 		// the device, entry by entry)
 		uint64_t slots = 0;
@@ -290,7 +283,7 @@ static int fe_validate(vgsdf_ctx *ctx, const FeInput *in, uint32_t n_cmds, FeFac
 			return VGSDF_E_ARG;
 		}
 	}
-	if (in->packed) {
+	if (in->form == FeForm::Packed) {
 		for (uint32_t g = 0; g < n; g++)
 			bad |= in->dat_off[g + 1] < in->dat_off[g];
 		if (bad) {
@@ -304,53 +297,79 @@ static int fe_validate(vgsdf_ctx *ctx, const FeInput *in, uint32_t n_cmds, FeFac
 // How the input of a submission travels.  The device keeps the glyf form, and a packed single block, in fe.meta in the
 // single-block layout (upload_layout.h) whether the arrays arrive as one block or one by one; otherwise fe.meta holds
 // the per-glyph arrays only (staged as one block) and kinds / coords / cmds have buffers of their own.
+using FeLayout = std::variant<vgsdf::PackedBlockLayout, vgsdf::GlyfBlockLayout, vgsdf::ResidentBlockLayout, vgsdf::CommandBlockLayout>;
 struct FeUpload {
-	vgsdf::PackedBlockLayout pk; // (its head also serves the plain command form)
-	vgsdf::GlyfBlockLayout gl;
-	vgsdf::ResidentBlockLayout rs;
-	vgsdf::CommandBlockLayout cm;
-	size_t arrays_bytes;          // scale | shift_x | cmd_off [| dat_off]
+	FeLayout layout; // that of the submission's own form (Records: the head of the packed one)
+	// what every form's layout shares
+	size_t block_bytes = 0;          // the arrays as ONE block
+	size_t pbf_pre = 0, pbf_fix = 0; // where the PBF arrays lie in it
+	size_t arrays_bytes = 0;         // scale | shift_x | cmd_off [| dat_off]
+	size_t meta_bytes = 0;           // what the device keeps in fe.meta
 	const uint8_t *block = nullptr; // the caller's arrays are ONE page-locked block in their form's layout: one copy
-	size_t block_bytes = 0;
 	const void *mapped = nullptr; // ... that the device can address: uploaded by a kernel (outline_kernels.hip, copy_in)
 	// set by fe_upload: device views of what the form brings besides the per-glyph arrays (those: fe_dev)
 	const uint8_t *d_kinds = nullptr, *d_parts = nullptr, *d_bytes = nullptr;
 	const float *d_coords = nullptr;
 	const uint32_t *d_dat_off = nullptr;
 };
-static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_floats)
+static FeLayout fe_layout(const FeInput *in, uint32_t n_cmds, uint32_t n_floats)
 {
 	const uint32_t n = in->n_glyphs;
 	const bool pbf = in->pbf_fix != nullptr;
-	FeUpload up{vgsdf::PackedBlockLayout(n, n_cmds, n_floats, pbf), vgsdf::GlyfBlockLayout(n, in->n_parts, in->n_bytes, pbf),
-	            vgsdf::ResidentBlockLayout(n, in->n_fonts, pbf), vgsdf::CommandBlockLayout(n, in->n_fonts, pbf), 0};
-	up.arrays_bytes = in->packed ? up.pk.arrays_end : up.pk.end;
+	switch (in->form) {
+	case FeForm::Glyf:
+		return vgsdf::GlyfBlockLayout(n, in->n_parts, in->n_bytes, pbf);
+	case FeForm::ResidentGlyf:
+		return vgsdf::ResidentBlockLayout(n, in->n_fonts, pbf);
+	case FeForm::ResidentCommands:
+		return vgsdf::CommandBlockLayout(n, in->n_fonts, pbf);
+	case FeForm::Records:
+	case FeForm::Packed:
+		break;
+	}
+	return vgsdf::PackedBlockLayout(n, n_cmds, n_floats, pbf);
+}
+static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_floats)
+{
+	const bool pbf = in->pbf_fix != nullptr;
+	FeUpload up{fe_layout(in, n_cmds, n_floats)};
+	std::visit([&up](const auto &l) { up.block_bytes = l.bytes, up.pbf_pre = l.pbf_pre, up.pbf_fix = l.pbf_fix, up.arrays_bytes = l.end; }, up.layout);
 	// the block is recognised by the caller's pointers: every array where the layout has it, counted from `scale`
 	const uint8_t *hb = (const uint8_t *)in->scale;
 	auto at = [hb](const void *array, size_t off) { return (const uint8_t *)array == hb + off; };
-	const vgsdf::PackedBlockLayout &pk = up.pk;
-	const vgsdf::GlyfBlockLayout &gl = up.gl;
 	bool single = false;
-	if (in->resident) { // (gathered by the library itself, in the context's page-locked staging buffer)
-		up.block_bytes = up.rs.bytes;
+	switch (in->form) {
+	case FeForm::ResidentGlyf:
+	case FeForm::ResidentCommands: // (gathered by the library itself, in the context's page-locked staging buffer)
 		single = true;
-	} else if (in->commands) { // (likewise)
-		up.block_bytes = up.cm.bytes;
-		single = true;
-	} else if (in->glyf) {
-		up.block_bytes = gl.bytes;
+		break;
+	case FeForm::Glyf: {
+		const auto &gl = std::get<vgsdf::GlyfBlockLayout>(up.layout);
 		single = at(in->shift_x, gl.shift_x) && at(in->cmd_off, gl.cmd_off) && at(in->parts, gl.parts) && at(in->bytes, gl.glyf_bytes) &&
 		         (!pbf || (at(in->pbf_pre, gl.pbf_pre) && at(in->pbf_fix, gl.pbf_fix)));
-	} else if (in->packed) {
-		up.block_bytes = pk.bytes;
+		break;
+	}
+	case FeForm::Packed: {
+		const auto &pk = std::get<vgsdf::PackedBlockLayout>(up.layout);
+		up.arrays_bytes = pk.arrays_end;
 		single = at(in->shift_x, pk.shift_x) && at(in->cmd_off, pk.cmd_off) && at(in->dat_off, pk.dat_off) && at(in->coords, pk.coords) &&
 		         at(in->kinds, pk.kinds) && (!pbf || (at(in->pbf_pre, pk.pbf_pre) && at(in->pbf_fix, pk.pbf_fix)));
+		break;
+	}
+	case FeForm::Records: // (its command records never travel with the per-glyph arrays)
+		break;
 	}
 	if (single && is_pinned(hb, up.block_bytes))
 		up.block = hb;
 	static const char *ck_env = std::getenv("VGSDF_COPY_KERNEL"); // (0: measurement switch, the copy engine takes the block)
 	if (up.block && !(ck_env && ck_env[0] == '0') && ((uintptr_t)hb & 15u) == 0)
 		up.mapped = pinned_device_ptr(const_cast<uint8_t *>(hb), up.block_bytes);
+	// the device's copy: the block as it stands (ResidentGlyf: and the parts its leaves expand into behind it); the
+	// per-glyph arrays alone where commands or kinds / coords arrive one by one and have buffers of their own
+	const bool arrays_only = in->form == FeForm::Records || (in->form == FeForm::Packed && !up.block);
+	up.meta_bytes = arrays_only ? up.arrays_bytes : up.block_bytes;
+	if (in->form == FeForm::ResidentGlyf)
+		up.meta_bytes += sizeof(vgsdf_glyf_part) * (size_t)in->n_parts;
 	return up;
 }
 
@@ -360,10 +379,8 @@ static int fe_reserve(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t 
 	FePending &p = fe.pend;
 	const uint32_t n = in->n_glyphs;
 	FE_TRY(fe.cmds.ensure(sizeof(vgsdf::OutlineCmd) * (size_t)(n_cmds + 1)));
-	FE_TRY(fe.meta.ensure((in->resident ? up.rs.bytes + sizeof(vgsdf_glyf_part) * (size_t)in->n_parts
-	                       : in->commands ? up.cm.bytes
-	                                      : (in->glyf ? up.gl.bytes : (up.block ? up.pk.bytes : up.arrays_bytes))) + 16));
-	if (!in->resident && !in->commands) // (a submission that names its glyphs: its block lies there already)
+	FE_TRY(fe.meta.ensure(up.meta_bytes + 16));
+	if (!in->names_glyphs()) // (a submission that names its glyphs: its block lies there already)
 		FE_TRY(fe.h_stage.ensure(up.arrays_bytes + 16));
 	FE_TRY(fe.cmd_open.ensure((size_t)n_cmds + 1));
 	FE_TRY(fe.counts.ensure(4 * (size_t)(n_cmds + 1)));
@@ -388,62 +405,80 @@ static int fe_reserve(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t 
 }
 
 // 4. upload, per input form
+static hipError_t fe_copy_in(hipStream_t st, void *dst, const void *src, size_t bytes)
+{
+	return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+}
+// The block of a named form as its ONE upload kernel can read it: the page-locked block itself; without a device mapping
+// (or with VGSDF_COPY_KERNEL=0) the copy engine brings the block into fe.coords first and the kernel reads that copy
+static int fe_kernel_readable_block(vgsdf_ctx *ctx, FrontEnd &fe, const FeUpload &up, const void *&src)
+{
+	src = up.mapped;
+	if (src)
+		return VGSDF_OK;
+	FE_TRY(fe.coords.ensure(up.block_bytes + 16));
+	FE_TRY(fe_copy_in(ctx->stream, fe.coords.p, up.block, up.block_bytes));
+	src = fe.coords.p;
+	return VGSDF_OK;
+}
+// per-glyph inputs (scale, shift, command offsets [, coordinate offsets]) of a form whose arrays arrive one by one: they
+// travel as ONE block through pinned staging
+static int fe_stage_arrays(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeUpload &up)
+{
+	const auto &pk = std::get<vgsdf::PackedBlockLayout>(up.layout);
+	const size_t n = in->n_glyphs;
+	uint8_t *hm = (uint8_t *)fe.h_stage.p;
+	std::memcpy(hm + pk.scale, in->scale, 8 * n);
+	std::memcpy(hm + pk.shift_x, in->shift_x, 8 * n);
+	std::memcpy(hm + pk.cmd_off, in->cmd_off, 4 * (n + 1));
+	if (in->form == FeForm::Packed)
+		std::memcpy(hm + pk.dat_off, in->dat_off, 4 * (n + 1));
+	FE_TRY(fe_copy_in(ctx->stream, fe.meta.p, hm, up.arrays_bytes));
+	return VGSDF_OK;
+}
 static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n_cmds, uint32_t n_floats, FeUpload &up)
 {
 	FePending &p = fe.pend;
 	hipStream_t st = ctx->stream;
 	const size_t n = in->n_glyphs;
 	const bool pbf = in->pbf_fix != nullptr;
-	const vgsdf::PackedBlockLayout &pk = up.pk;
-	const vgsdf::GlyfBlockLayout &gl = up.gl;
 	uint8_t *dm = (uint8_t *)fe.meta.p;
-	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
-	if (in->resident) {
-		// ONE kernel: the copy of the block and the expansion of the glyphs' leaves into parts behind it.  It reads the
-		// page-locked block itself; without a device mapping (or with VGSDF_COPY_KERNEL=0) the copy engine brings the block
-		// over first and the kernel reads that copy
-		const vgsdf::ResidentBlockLayout &rs = up.rs;
-		const void *src = up.mapped;
-		if (!src) {
-			FE_TRY(fe.coords.ensure(rs.bytes + 16));
-			FE_TRY(copy(fe.coords.p, up.block, rs.bytes));
-			src = fe.coords.p;
-		}
+	auto copy = [st](void *dst, const void *src, size_t bytes) { return fe_copy_in(st, dst, src, bytes); };
+	// a block the caller built (Glyf, Packed): one kernel or one copy brings it over as it stands
+	auto copy_block = [&]() -> int {
+		if (up.mapped)
+			FE_KERNEL(vgsdf_copy_in(up.mapped, dm, up.block_bytes, st));
+		else if (up.block)
+			FE_TRY(copy(dm, up.block, up.block_bytes));
+		return VGSDF_OK;
+	};
+	switch (in->form) {
+	case FeForm::ResidentGlyf: { // ONE kernel: the copy of the block and the expansion of the glyphs' leaves into parts behind it
+		const auto &rs = std::get<vgsdf::ResidentBlockLayout>(up.layout);
+		const void *src = nullptr;
+		if (int rc = fe_kernel_readable_block(ctx, fe, up, src); rc != VGSDF_OK)
+			return rc;
 		FE_KERNEL(vgsdf_resident_expand(src, dm, rs.bytes, (uint32_t)n, in->n_parts, in->n_fonts, pbf, dm + rs.bytes, st));
 		up.d_parts = dm + rs.bytes;
 		up.d_bytes = dm + rs.fonts; // (the fonts' stores: vgsdf_glyf_decode_resident)
-		if (pbf) {
-			p.d_pbf_pre = (const uint32_t *)(dm + rs.pbf_pre);
-			p.d_pbf_fix = dm + rs.pbf_fix;
-		}
 		fe.resident_upload_bytes = rs.bytes;
-		return VGSDF_OK;
+		break;
 	}
-	if (in->commands) {
-		// ONE kernel again: the copy of the block and the gather of the named glyphs' records and context bytes from the
-		// fonts' stores (the block travels as above)
-		const vgsdf::CommandBlockLayout &cm = up.cm;
-		const void *src = up.mapped;
-		if (!src) {
-			FE_TRY(fe.coords.ensure(cm.bytes + 16));
-			FE_TRY(copy(fe.coords.p, up.block, cm.bytes));
-			src = fe.coords.p;
-		}
-		FE_KERNEL(vgsdf_resident_gather(src, dm, cm.bytes, (uint32_t)n, n_cmds, in->n_fonts, pbf, (vgsdf::OutlineCmd *)fe.cmds.p,
+	case FeForm::ResidentCommands: { // ONE kernel again: the copy of the block and the gather of the named glyphs' records and
+		                             // context bytes from the fonts' stores
+		const void *src = nullptr;
+		if (int rc = fe_kernel_readable_block(ctx, fe, up, src); rc != VGSDF_OK)
+			return rc;
+		FE_KERNEL(vgsdf_resident_gather(src, dm, up.block_bytes, (uint32_t)n, n_cmds, in->n_fonts, pbf, (vgsdf::OutlineCmd *)fe.cmds.p,
 		                                (uint8_t *)fe.cmd_open.p, st));
-		if (pbf) {
-			p.d_pbf_pre = (const uint32_t *)(dm + cm.pbf_pre);
-			p.d_pbf_fix = dm + cm.pbf_fix;
-		}
-		fe.resident_upload_bytes = cm.bytes;
-		return VGSDF_OK;
+		fe.resident_upload_bytes = up.block_bytes;
+		break;
 	}
-	if (up.mapped)
-		FE_KERNEL(vgsdf_copy_in(up.mapped, dm, up.block_bytes, st));
-	else if (up.block)
-		FE_TRY(copy(dm, up.block, up.block_bytes));
-	if (in->glyf) {
-		if (!up.block) {
+	case FeForm::Glyf: {
+		const auto &gl = std::get<vgsdf::GlyfBlockLayout>(up.layout);
+		if (int rc = copy_block(); rc != VGSDF_OK)
+			return rc;
+		if (!up.block) { // (array by array, to where the block would have put them)
 			FE_TRY(copy(dm + gl.scale, in->scale, 8 * n));
 			FE_TRY(copy(dm + gl.shift_x, in->shift_x, 8 * n));
 			FE_TRY(copy(dm + gl.cmd_off, in->cmd_off, 4 * (n + 1)));
@@ -454,47 +489,45 @@ static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n
 		}
 		up.d_parts = dm + gl.parts;
 		up.d_bytes = dm + gl.glyf_bytes;
-		if (pbf) {
-			p.d_pbf_pre = (const uint32_t *)(dm + gl.pbf_pre);
-			p.d_pbf_fix = dm + gl.pbf_fix;
-		}
-		return VGSDF_OK;
+		break;
 	}
-	if (up.block) { // (packed)
-		up.d_coords = (const float *)(dm + pk.coords);
-		up.d_kinds = dm + pk.kinds;
+	case FeForm::Packed: {
+		const auto &pk = std::get<vgsdf::PackedBlockLayout>(up.layout);
 		up.d_dat_off = (const uint32_t *)(dm + pk.dat_off);
-		if (pbf) {
-			p.d_pbf_pre = (const uint32_t *)(dm + pk.pbf_pre);
-			p.d_pbf_fix = dm + pk.pbf_fix;
+		if (up.block) {
+			if (int rc = copy_block(); rc != VGSDF_OK)
+				return rc;
+			up.d_coords = (const float *)(dm + pk.coords);
+			up.d_kinds = dm + pk.kinds;
+			break;
 		}
-		return VGSDF_OK;
-	}
-	if (in->packed) {
 		FE_TRY(fe.kinds.ensure((size_t)n_cmds + 16));
 		FE_TRY(fe.coords.ensure(4 * (size_t)n_floats + 16));
 		FE_TRY(copy(fe.kinds.p, in->kinds, (size_t)n_cmds));
 		FE_TRY(copy(fe.coords.p, in->coords, 4 * (size_t)n_floats));
 		up.d_kinds = (const uint8_t *)fe.kinds.p;
 		up.d_coords = (const float *)fe.coords.p;
-		up.d_dat_off = (const uint32_t *)(dm + pk.dat_off);
-	} else {
-		FE_TRY(copy(fe.cmds.p, in->cmds, sizeof(vgsdf::OutlineCmd) * (size_t)n_cmds));
+		if (int rc = fe_stage_arrays(ctx, fe, in, up); rc != VGSDF_OK)
+			return rc;
+		if (pbf) { // the one exception to the rule below: arrays that did not travel in a block get copies of their own
+			FE_TRY(fe.pbf_in.ensure(5 * n + 16));
+			FE_TRY(copy(fe.pbf_in.p, in->pbf_pre, 4 * n));
+			FE_TRY(copy((uint8_t *)fe.pbf_in.p + 4 * n, in->pbf_fix, n));
+			p.d_pbf_pre = (const uint32_t *)fe.pbf_in.p;
+			p.d_pbf_fix = (const uint8_t *)fe.pbf_in.p + 4 * n;
+		}
+		break;
 	}
-	// per-glyph inputs (scale, shift, command offsets) travel as ONE block through pinned staging
-	uint8_t *hm = (uint8_t *)fe.h_stage.p;
-	std::memcpy(hm + pk.scale, in->scale, 8 * n);
-	std::memcpy(hm + pk.shift_x, in->shift_x, 8 * n);
-	std::memcpy(hm + pk.cmd_off, in->cmd_off, 4 * (n + 1));
-	if (in->packed)
-		std::memcpy(hm + pk.dat_off, in->dat_off, 4 * (n + 1));
-	FE_TRY(copy(dm, hm, up.arrays_bytes));
-	if (pbf) { // arrays that do not sit in the single-copy block: their own copies
-		FE_TRY(fe.pbf_in.ensure(5 * n + 16));
-		FE_TRY(copy(fe.pbf_in.p, in->pbf_pre, 4 * n));
-		FE_TRY(copy((uint8_t *)fe.pbf_in.p + 4 * n, in->pbf_fix, n));
-		p.d_pbf_pre = (const uint32_t *)fe.pbf_in.p;
-		p.d_pbf_fix = (const uint8_t *)fe.pbf_in.p + 4 * n;
+	case FeForm::Records:
+		FE_TRY(copy(fe.cmds.p, in->cmds, sizeof(vgsdf::OutlineCmd) * (size_t)n_cmds));
+		if (int rc = fe_stage_arrays(ctx, fe, in, up); rc != VGSDF_OK)
+			return rc;
+		break;
+	}
+	// the PBF arrays: the block travelled as one (or was laid out as one on the device), so they sit at the layout's offsets in fe.meta
+	if (pbf && !p.d_pbf_fix) {
+		p.d_pbf_pre = (const uint32_t *)(dm + up.pbf_pre);
+		p.d_pbf_fix = dm + up.pbf_fix;
 	}
 	return VGSDF_OK;
 }
@@ -532,20 +565,20 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	// and no part straddles two glyphs (the decoder's rule is per part; the ring pass trusts the context bytes to be those of
 	// the glyph's own command sequence — a byte that says "open" in front of a glyph's first command would index a ring
 	// that does not exist)
-	bool decode_makes_context = in->glyf && facts.parts_inside_glyphs && facts.scales_plain;
+	bool decode_makes_context = in->decodes_glyf() && facts.parts_inside_glyphs && facts.scales_plain;
 	static const char *fuse_env = std::getenv("VGSDF_FUSE_CONTEXT"); // (measurement switch)
 	if (fuse_env && fuse_env[0] == '0')
 		decode_makes_context = false;
 	// command fonts: the gathered context bytes are the context pass's own for positive finite scales; a batch with an odd scale
 	// takes the pass over the gathered records, as the glyf form does
-	const bool gather_makes_context = in->commands && facts.scales_plain;
-	if (in->resident)
+	const bool gather_makes_context = in->form == FeForm::ResidentCommands && facts.scales_plain;
+	if (in->form == FeForm::ResidentGlyf)
 		FE_KERNEL(vgsdf_glyf_decode_resident(up.d_parts, in->n_parts, up.d_bytes, (vgsdf::OutlineCmd *)fe.cmds.p, flagw, facts.glyf_max_cap,
 		                                     facts.glyf_max_len, decode_makes_context ? (uint8_t *)fe.cmd_open.p : nullptr, st));
-	else if (in->glyf)
+	else if (in->form == FeForm::Glyf)
 		FE_KERNEL(vgsdf_glyf_decode(up.d_parts, in->n_parts, up.d_bytes, (vgsdf::OutlineCmd *)fe.cmds.p, flagw, facts.glyf_max_cap, facts.glyf_max_len,
 		                            decode_makes_context ? (uint8_t *)fe.cmd_open.p : nullptr, st));
-	if (in->packed)
+	if (in->form == FeForm::Packed)
 		FE_KERNEL(vgsdf_outline_context_packed(up.d_kinds, up.d_coords, up.d_dat_off, d.cmd_off, d.scale, n, (vgsdf::OutlineCmd *)fe.cmds.p,
 		                                       (uint8_t *)fe.cmd_open.p, flagw, st));
 	else if (!decode_makes_context && !gather_makes_context)
@@ -565,6 +598,7 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	if (early_copy) {
 		FE_TRY(hipEventRecord(ctx->ev_plan, st));
 		FE_TRY(hipStreamWaitEvent(ctx->copy_stream, ctx->ev_plan, 0));
+		fe.pend.copy_stream_waits = true;
 		FE_TRY(hipMemcpyAsync(fe.h_rects.p, fe.rects_hdr.p, p.rh_bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
 		FE_TRY(hipEventRecord(ctx->ev_rects, ctx->copy_stream));
 	}
@@ -583,6 +617,48 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	return VGSDF_OK;
 }
 
+// The context's front-end state for a new submission: its device made current, the state created on first use, and refused
+// while a submission is pending (its kernels may still be reading their input, the staging buffer included)
+static int fe_acquire(vgsdf_ctx *ctx, FrontEnd *&fe)
+{
+	(void)hipSetDevice(ctx->device);
+	if (!ctx->fe)
+		ctx->fe = new (std::nothrow) FrontEnd();
+	if (!ctx->fe) {
+		ctx->err = "vgsdf_outlines: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	if (ctx->fe->pend.active) {
+		ctx->err = "vgsdf_outlines_submit: the previous submission of this context has not been waited for";
+		return VGSDF_E_ARG;
+	}
+	fe = ctx->fe;
+	return VGSDF_OK;
+}
+
+// Steps 4 and 5 with the error word's handling around them: everything of a submission that enqueues work.  When a step in
+// here fails, what the steps before it enqueued is still running: fe_submit, the one caller, drains it
+static int fe_upload_and_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n_cmds, uint32_t n_floats, FeUpload &up, FeFacts &facts,
+                                 bool validate_under_upload)
+{
+	// error word of this submission (FrontEnd::flag_slot)
+	if (!fe.flags_clean)
+		FE_TRY(hipMemsetAsync(fe.flag.p, 0, 32, ctx->stream));
+	fe.flags_clean = false; // (until everything below is enqueued: its plan kernel zeroes the other slot)
+	fe.flag_slot ^= 1u;
+	if (int rc = fe_upload(ctx, fe, in, n_cmds, n_floats, up); rc != VGSDF_OK)
+		return rc;
+	if (int rc = fe_place_raster(ctx, fe); rc != VGSDF_OK)
+		return rc;
+	if (validate_under_upload) // the upload is under way: now the walks over the input, before the first kernel that reads it
+		if (int rc = fe_validate(ctx, in, n_cmds, facts); rc != VGSDF_OK)
+			return rc;
+	if (int rc = fe_enqueue(ctx, fe, in, up, facts); rc != VGSDF_OK)
+		return rc;
+	fe.flags_clean = true; // the plan kernel enqueued above leaves the other slot zeroed for the next submission
+	return VGSDF_OK;
+}
+
 static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_t spec_cap)
 {
 	const double tr0 = fe_now();
@@ -592,18 +668,10 @@ static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_
 	if (int rc = fe_check_args(ctx, in, n_cmds, n_floats); rc != VGSDF_OK)
 		return rc;
 	const uint32_t n = in->n_glyphs;
-	(void)hipSetDevice(ctx->device);
-	if (!ctx->fe)
-		ctx->fe = new (std::nothrow) FrontEnd();
-	if (!ctx->fe) {
-		ctx->err = "vgsdf_outlines: out of host memory";
-		return VGSDF_E_OOM;
-	}
-	FrontEnd &fe = *ctx->fe;
-	if (fe.pend.active) {
-		ctx->err = "vgsdf_outlines_submit: the previous submission of this context has not been waited for";
-		return VGSDF_E_ARG;
-	}
+	FrontEnd *fe_p = nullptr;
+	if (int rc = fe_acquire(ctx, fe_p); rc != VGSDF_OK)
+		return rc;
+	FrontEnd &fe = *fe_p;
 	fe.prepared = false;
 	fe.peeked = false;
 	fe.n_glyphs = n;
@@ -632,8 +700,8 @@ static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_
 	if (std::getenv("VGSDF_TRACE") != nullptr)
 		FE_TRY(hipEventRecord(ctx->ev0, ctx->stream));
 	FeFacts facts;
-	// (a resident submission was validated before its block was gathered, and its offsets are the library's own sums)
-	const bool named = in->resident || in->commands;
+	// (a submission that names its glyphs was validated before its block was gathered, and its offsets are the library's own sums)
+	const bool named = in->names_glyphs();
 	if (named) {
 		facts.glyf_max_cap = in->res_max_cap;
 		facts.glyf_max_len = in->res_max_len;
@@ -643,21 +711,15 @@ static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_
 	if (!validate_under_upload && !named)
 		if (int rc = fe_validate(ctx, in, n_cmds, facts); rc != VGSDF_OK)
 			return rc;
-	// error word of this submission (FrontEnd::flag_slot)
-	if (!fe.flags_clean)
-		FE_TRY(hipMemsetAsync(fe.flag.p, 0, 32, ctx->stream));
-	fe.flags_clean = false; // (until everything below is enqueued: its plan kernel zeroes the other slot)
-	fe.flag_slot ^= 1u;
-	if (int rc = fe_upload(ctx, fe, in, n_cmds, n_floats, up); rc != VGSDF_OK)
+	if (int rc = fe_upload_and_enqueue(ctx, fe, in, n_cmds, n_floats, up, facts, validate_under_upload); rc != VGSDF_OK) {
+		// A failed submit leaves the caller nothing to wait on (pend stays inactive), so nothing of the caller's memory may
+		// be in use when it returns: what was enqueued — the upload kernel reading a page-locked block, a raster storing through
+		// the output buffer — is drained here.  The code and the message are those of the step that failed
+		(void)hipStreamSynchronize(ctx->stream);
+		if (p.copy_stream_waits)
+			(void)hipStreamSynchronize(ctx->copy_stream);
 		return rc;
-	if (int rc = fe_place_raster(ctx, fe); rc != VGSDF_OK)
-		return rc;
-	if (validate_under_upload) // the upload is under way: now the walks over the input, before the first kernel that reads it
-		if (int rc = fe_validate(ctx, in, n_cmds, facts); rc != VGSDF_OK)
-			return rc;
-	if (int rc = fe_enqueue(ctx, fe, in, up, facts); rc != VGSDF_OK)
-		return rc;
-	fe.flags_clean = true; // the plan kernel enqueued above leaves the other slot zeroed for the next submission
+	}
 	p.active = true;
 	return VGSDF_OK;
 }
@@ -811,6 +873,72 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 	return VGSDF_OK;
 }
 
+// The block of a submission that names its glyphs, gathered in the context's page-locked staging buffer in the layout of
+// its kind of font: the caller's arrays, the running sum(s), the fonts' device addresses.  Points `f` into it
+template <class Layout> static int fe_gather_named(vgsdf_ctx *ctx, FrontEnd &fe, const vgsdf_outlines_resident *in, FeInput &f)
+{
+	constexpr bool glyf = std::is_same_v<Layout, vgsdf::ResidentBlockLayout>; // (else: command fonts, CommandBlockLayout)
+	const uint32_t n = in->n_glyphs;
+	const bool pbf = in->pbf_fix != nullptr;
+	const Layout at(n, in->n_fonts, pbf);
+	FE_TRY(fe.h_stage.ensure(at.bytes + 16));
+	uint8_t *hb = (uint8_t *)fe.h_stage.p;
+	std::memcpy(hb + at.scale, in->scale, 8 * (size_t)n);
+	std::memcpy(hb + at.shift_x, in->shift_x, 8 * (size_t)n);
+	std::memcpy(hb + at.glyph_id, in->glyph_id, 2 * (size_t)n);
+	std::memcpy(hb + at.font_of, in->font_of, 2 * (size_t)n);
+	if (pbf) {
+		std::memcpy(hb + at.pbf_pre, in->pbf_pre, 4 * (size_t)n);
+		std::memcpy(hb + at.pbf_fix, in->pbf_fix, n);
+	}
+	std::memset(hb + at.arrays_end, 0, at.fonts - at.arrays_end);
+	// per glyph one table read and one addition: the running sum of command slots (command fonts: of commands) — and, for
+	// glyf fonts, the same again for the leaves that become the submission's parts
+	uint32_t *cmd_off = (uint32_t *)(hb + at.cmd_off), *part_off = nullptr;
+	if constexpr (glyf)
+		part_off = (uint32_t *)(hb + at.part_off);
+	uint64_t cmds = 0, parts = 0;
+	for (uint32_t g = 0; g < n; g++) {
+		const vgsdf_font &ft = *in->fonts[in->font_of[g]];
+		const uint32_t id = in->glyph_id[g];
+		cmd_off[g] = (uint32_t)cmds;
+		cmds += ft.slots[id];
+		if constexpr (glyf) {
+			part_off[g] = (uint32_t)parts;
+			parts += ft.leaf_off[id + 1] - ft.leaf_off[id];
+		}
+		if (cmds > 0x7FFFFFFFull) {
+			ctx->err = glyf ? "vgsdf_outlines_resident: more than 2^31 - 1 command slots in one submission; split it"
+			                : "vgsdf_outlines_resident: more than 2^31 - 1 commands in one submission; split it";
+			return VGSDF_E_ARG;
+		}
+		f.res_scales_plain = f.res_scales_plain && in->scale[g] > 0.0 && in->scale[g] < HUGE_VAL;
+	}
+	cmd_off[n] = (uint32_t)cmds;
+	if constexpr (glyf) {
+		part_off[n] = (uint32_t)parts;
+		vgsdf::ResidentFontRef *refs = (vgsdf::ResidentFontRef *)(hb + at.fonts);
+		for (uint32_t k = 0; k < in->n_fonts; k++) {
+			refs[k] = in->fonts[k]->ref;
+			f.res_max_cap = std::max(f.res_max_cap, in->fonts[k]->max_cap);
+			f.res_max_len = std::max(f.res_max_len, in->fonts[k]->max_len);
+		}
+	} else {
+		vgsdf::CommandFontRef *refs = (vgsdf::CommandFontRef *)(hb + at.fonts);
+		for (uint32_t k = 0; k < in->n_fonts; k++)
+			refs[k] = in->fonts[k]->cref;
+	}
+	f.form = glyf ? FeForm::ResidentGlyf : FeForm::ResidentCommands;
+	f.cmd_off = cmd_off;
+	f.scale = (const double *)(hb + at.scale);
+	f.shift_x = (const double *)(hb + at.shift_x);
+	f.pbf_pre = pbf ? (const uint32_t *)(hb + at.pbf_pre) : nullptr;
+	f.pbf_fix = pbf ? hb + at.pbf_fix : nullptr;
+	f.n_parts = (uint32_t)parts;
+	f.n_fonts = in->n_fonts;
+	return VGSDF_OK;
+}
+
 static FeInput fe_input(const vgsdf_outlines *in)
 {
 	FeInput f;
@@ -821,6 +949,8 @@ static FeInput fe_input(const vgsdf_outlines *in)
 	f.cmds = in->cmds;
 	return f;
 }
+
+extern "C" {
 
 int vgsdf_outlines_prepare(vgsdf_ctx *ctx, const vgsdf_outlines *in, vgsdf_rect *rects_out, uint64_t *out_bytes,
                            uint64_t *n_segments)
@@ -861,7 +991,7 @@ int vgsdf_outlines_submit_packed(vgsdf_ctx *ctx, const vgsdf_outlines_packed *in
 		f.coords = in->coords;
 		f.pbf_pre = in->pbf_pre;
 		f.pbf_fix = in->pbf_fix;
-		f.packed = true;
+		f.form = FeForm::Packed;
 	}
 	return fe_submit(ctx, in ? &f : nullptr, out_bitmaps, out_bitmaps ? out_capacity : 0);
 }
@@ -876,7 +1006,7 @@ int vgsdf_outlines_submit_glyf(vgsdf_ctx *ctx, const vgsdf_outlines_glyf *in, ui
 		f.shift_x = in->shift_x;
 		f.pbf_pre = in->pbf_pre;
 		f.pbf_fix = in->pbf_fix;
-		f.glyf = true;
+		f.form = FeForm::Glyf;
 		f.parts = in->parts;
 		f.n_parts = in->n_parts;
 		f.bytes = in->bytes;
@@ -885,217 +1015,7 @@ int vgsdf_outlines_submit_glyf(vgsdf_ctx *ctx, const vgsdf_outlines_glyf *in, ui
 	return fe_submit(ctx, in ? &f : nullptr, out_bitmaps, out_bitmaps ? out_capacity : 0);
 }
 
-// ---- resident fonts ----
-
-int vgsdf_font_create(vgsdf_ctx *ctx, const vgsdf_font_desc *in, vgsdf_font **out)
-{
-	if (!ctx)
-		return VGSDF_E_ARG;
-	if (!in || !out || !in->leaf_off || (in->n_leaves && !in->leaves) || (in->n_bytes && !in->bytes)) {
-		ctx->err = "vgsdf_font_create: NULL argument";
-		return VGSDF_E_ARG;
-	}
-	*out = nullptr;
-	const uint32_t n = in->n_glyph_ids;
-	if (n > 0x10000u || (in->n_bytes & 3u) || in->leaf_off[0] != 0 || in->leaf_off[n] != in->n_leaves) {
-		ctx->err = "vgsdf_font_create: more than 65536 glyph ids, n_bytes not a multiple of 4, or leaf_off does not run from 0 to n_leaves";
-		return VGSDF_E_ARG;
-	}
-	vgsdf_font *f = new (std::nothrow) vgsdf_font();
-	if (!f) {
-		ctx->err = "vgsdf_font_create: out of host memory";
-		return VGSDF_E_OOM;
-	}
-	f->slots.assign(n, 0);
-	for (uint32_t g = 0; g < n; g++) {
-		const uint32_t l0 = in->leaf_off[g], l1 = in->leaf_off[g + 1];
-		if (l1 < l0 || l1 > in->n_leaves) {
-			ctx->err = "vgsdf_font_create: leaf_off not ascending";
-			delete f;
-			return VGSDF_E_ARG;
-		}
-		uint64_t slots = 0;
-		for (uint32_t i = l0; i < l1; i++) {
-			const vgsdf_glyf_part &lf = in->leaves[i];
-			if (lf.cmd_at != slots || (lf.byte_off & 3u) || lf.byte_off > in->n_bytes || lf.byte_len > in->n_bytes - lf.byte_off ||
-			    lf.n_contours == 0 || lf.plain > 1u) {
-				ctx->err = "vgsdf_font_create: the leaves of a glyph must tile its command slots from 0 in order, with 4-aligned byte ranges "
-				           "inside `bytes`, n_contours > 0 and plain 0 or 1";
-				delete f;
-				return VGSDF_E_ARG;
-			}
-			slots += lf.cmd_cap;
-			if (slots > 0x7FFFFFFFull) {
-				ctx->err = "vgsdf_font_create: a glyph of more than 2^31 - 1 command slots";
-				delete f;
-				return VGSDF_E_ARG;
-			}
-			f->max_cap = std::max(f->max_cap, lf.cmd_cap);
-			f->max_len = std::max(f->max_len, lf.byte_len);
-		}
-		f->slots[g] = (uint32_t)slots;
-	}
-	f->device = ctx->device;
-	f->n_glyph_ids = n;
-	f->n_leaves = in->n_leaves;
-	f->n_bytes = in->n_bytes;
-	f->leaf_off.assign(in->leaf_off, in->leaf_off + n + 1);
-	(void)hipSetDevice(ctx->device);
-	const size_t leaves_bytes = sizeof(vgsdf_glyf_part) * (size_t)in->n_leaves; // (a multiple of 16)
-	const size_t bytes_at = leaves_bytes, off_at = align_up(bytes_at + in->n_bytes, 16), total = off_at + 4 * ((size_t)n + 1);
-	auto fail = [&](hipError_t e, const char *what) {
-		ctx->err = std::string("vgsdf_font_create: ") + what + ": " + hipGetErrorString(e);
-		f->store.release();
-		delete f;
-		return e == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;
-	};
-	if (hipError_t e = f->store.ensure(total + 16); e != hipSuccess)
-		return fail(e, "hipMalloc");
-	uint8_t *d = (uint8_t *)f->store.p;
-	hipError_t e = leaves_bytes ? hipMemcpyAsync(d, in->leaves, leaves_bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
-	if (e == hipSuccess && in->n_bytes)
-		e = hipMemcpyAsync(d + bytes_at, in->bytes, in->n_bytes, hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(d + off_at, in->leaf_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(ctx->stream); // the arrays are on the device when the call returns: every context may name the font
-	if (e != hipSuccess)
-		return fail(e, "upload");
-	f->ref.leaves = (uint64_t)(uintptr_t)d;
-	f->ref.bytes = (uint64_t)(uintptr_t)(d + bytes_at);
-	f->ref.leaf_off = (uint64_t)(uintptr_t)(d + off_at);
-	*out = f;
-	return VGSDF_OK;
-}
-
-int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, vgsdf_font **out)
-{
-	if (!ctx)
-		return VGSDF_E_ARG;
-	if (!in || !out || !in->cmd_off || !in->dat_off || (in->n_cmds && !in->kinds) || (in->n_floats && !in->coords)) {
-		ctx->err = "vgsdf_font_create_commands: NULL argument";
-		return VGSDF_E_ARG;
-	}
-	*out = nullptr;
-	const uint32_t n = in->n_glyph_ids, n_cmds = in->n_cmds;
-	// (the store: 28-byte records | cmd_off | a context byte per record)
-	if (n > 0x10000u || 29ull * n_cmds + 4ull * (n + 1) > 0xFFFFFFFCull || 4ull * in->n_floats > 0xFFFFFFFCull) {
-		ctx->err = "vgsdf_font_create_commands: more than 65536 glyph ids, or a store (29 bytes per command, 4 per glyph id) or "
-		           "coordinates past what 32-bit offsets address";
-		return VGSDF_E_ARG;
-	}
-	if (in->cmd_off[0] != 0 || in->cmd_off[n] != n_cmds || in->dat_off[0] != 0 || in->dat_off[n] != in->n_floats) {
-		ctx->err = "vgsdf_font_create_commands: cmd_off / dat_off do not run from 0 to n_cmds / n_floats";
-		return VGSDF_E_ARG;
-	}
-	vgsdf_font *f = new (std::nothrow) vgsdf_font();
-	if (!f) {
-		ctx->err = "vgsdf_font_create_commands: out of host memory";
-		return VGSDF_E_OOM;
-	}
-	// everything a submission of these commands would be checked for per render, once: the offsets (they bound every read of
-	// the loop below), the kinds, and the coordinates every glyph's kinds carry against its dat_off range
-	f->slots.assign(n, 0);
-	for (uint32_t g = 0; g < n; g++) {
-		const uint32_t c0 = in->cmd_off[g], c1 = in->cmd_off[g + 1], d0 = in->dat_off[g], d1 = in->dat_off[g + 1];
-		if (c1 < c0 || c1 > n_cmds || d1 < d0 || d1 > in->n_floats) {
-			ctx->err = "vgsdf_font_create_commands: cmd_off / dat_off not ascending";
-			delete f;
-			return VGSDF_E_ARG;
-		}
-		uint64_t floats = 0;
-		uint32_t bad_kind = 0;
-		for (uint32_t c = c0; c < c1; c++) {
-			const uint32_t k = in->kinds[c];
-			bad_kind |= k > vgsdf::CMD_CLOSE;
-			floats += k <= vgsdf::CMD_LINE ? 2u : (k == vgsdf::CMD_QUAD ? 4u : (k == vgsdf::CMD_CURVE ? 6u : 0u));
-		}
-		if (bad_kind || floats != (uint64_t)(d1 - d0)) {
-			ctx->err = bad_kind ? "vgsdf_font_create_commands: unknown command kind"
-			                    : "vgsdf_font_create_commands: a glyph's dat_off range does not match its command kinds";
-			delete f;
-			return VGSDF_E_ARG;
-		}
-		f->slots[g] = c1 - c0;
-	}
-	f->device = ctx->device;
-	f->n_glyph_ids = n;
-	f->commands = true;
-	(void)hipSetDevice(ctx->device);
-	// the store: records | cmd_off | context bytes.  Beside it, for the duration of this call, what the packed form's context
-	// pass reads: scale (1: the bytes then say "ring open" and nothing else) | dat_off | coords | kinds | its error word
-	const size_t off_at = sizeof(vgsdf::OutlineCmd) * (size_t)n_cmds, open_at = off_at + 4 * ((size_t)n + 1), total = open_at + n_cmds;
-	const size_t t_dat = 8 * (size_t)n, t_coords = t_dat + 4 * ((size_t)n + 1), t_kinds = t_coords + 4 * (size_t)in->n_floats,
-	             t_flag = align_up(t_kinds + n_cmds, 16), t_total = t_flag + 16;
-	DevBuf tmp;
-	auto fail = [&](hipError_t e, const char *what) {
-		ctx->err = std::string("vgsdf_font_create_commands: ") + what + ": " + hipGetErrorString(e);
-		tmp.release();
-		f->store.release();
-		delete f;
-		return e == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;
-	};
-	if (hipError_t e = f->store.ensure(total + 16); e != hipSuccess)
-		return fail(e, "hipMalloc");
-	if (hipError_t e = tmp.ensure(t_total); e != hipSuccess)
-		return fail(e, "hipMalloc");
-	uint8_t *d = (uint8_t *)f->store.p, *t = (uint8_t *)tmp.p;
-	hipStream_t st = ctx->stream;
-	const std::vector<double> ones(n, 1.0);
-	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
-	hipError_t e = copy(d + off_at, in->cmd_off, 4 * ((size_t)n + 1));
-	if (e == hipSuccess)
-		e = copy(t, ones.data(), 8 * (size_t)n);
-	if (e == hipSuccess)
-		e = copy(t + t_dat, in->dat_off, 4 * ((size_t)n + 1));
-	if (e == hipSuccess)
-		e = copy(t + t_coords, in->coords, 4 * (size_t)in->n_floats);
-	if (e == hipSuccess)
-		e = copy(t + t_kinds, in->kinds, n_cmds);
-	if (e == hipSuccess)
-		e = hipMemsetAsync(t + t_flag, 0, 16, st);
-	if (e == hipSuccess && n_cmds)
-		e = (hipError_t)vgsdf_outline_context_packed(t + t_kinds, (const float *)(t + t_coords), (const uint32_t *)(t + t_dat),
-		                                             (const uint32_t *)(d + off_at), (const double *)t, n, (vgsdf::OutlineCmd *)d, d + open_at,
-		                                             (uint32_t *)(t + t_flag), st);
-	uint32_t flag = 0;
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(&flag, t + t_flag, 4, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(st); // the store is complete when the call returns: every context may name the font
-	if (e != hipSuccess)
-		return fail(e, "upload");
-	tmp.release();
-	if (flag) { // (what the walk above has ruled out, said by the pass itself)
-		ctx->err = "vgsdf_font_create_commands: the device's context pass refused the commands";
-		f->store.release();
-		delete f;
-		return VGSDF_E_ARG;
-	}
-	f->cref.cmds = (uint64_t)(uintptr_t)d;
-	f->cref.cmd_off = (uint64_t)(uintptr_t)(d + off_at);
-	f->cref.open = (uint64_t)(uintptr_t)(d + open_at);
-	*out = f;
-	return VGSDF_OK;
-}
-
-int vgsdf_font_free(vgsdf_ctx *ctx, vgsdf_font *font)
-{
-	if (!ctx)
-		return VGSDF_E_ARG;
-	if (!font)
-		return VGSDF_OK;
-	if (font->device != ctx->device) {
-		ctx->err = "vgsdf_font_free: the font lives on another device than the context";
-		return VGSDF_E_ARG;
-	}
-	(void)hipSetDevice(ctx->device);
-	font->store.release();
-	delete font;
-	return VGSDF_OK;
-}
-
-uint64_t vgsdf_font_device_bytes(const vgsdf_font *font) { return font ? (uint64_t)font->store.cap : 0; }
+// ---- glyphs named by (font, glyph id) of resident fonts (resident_fonts.cpp) ----
 
 uint64_t vgsdf_outlines_resident_upload_bytes(const vgsdf_ctx *ctx) { return ctx && ctx->fe ? ctx->fe->resident_upload_bytes : 0; }
 
@@ -1113,9 +1033,8 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 	}
 	const uint32_t n = in->n_glyphs;
 	FeInput f;
+	f.form = FeForm::ResidentGlyf;
 	f.n_glyphs = n;
-	f.glyf = true;
-	f.resident = true;
 	if (n == 0)
 		return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
 	if (in->n_fonts == 0 || in->n_fonts > 0x10000u) {
@@ -1139,102 +1058,12 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 			ctx->err = "vgsdf_outlines_resident: font_of past n_fonts, or a glyph id past its face";
 			return VGSDF_E_ARG;
 		}
-	(void)hipSetDevice(ctx->device);
-	if (!ctx->fe)
-		ctx->fe = new (std::nothrow) FrontEnd();
-	if (!ctx->fe) {
-		ctx->err = "vgsdf_outlines: out of host memory";
-		return VGSDF_E_OOM;
-	}
-	FrontEnd &fe = *ctx->fe;
-	if (fe.pend.active) { // (its upload kernel may still be reading the staging block)
-		ctx->err = "vgsdf_outlines_submit: the previous submission of this context has not been waited for";
-		return VGSDF_E_ARG;
-	}
-	const bool pbf = in->pbf_fix != nullptr;
-	if (commands) {
-		// the block: the caller's arrays gathered, the running sum of command counts, the fonts' device addresses
-		const vgsdf::CommandBlockLayout cm(n, in->n_fonts, pbf);
-		FE_TRY(fe.h_stage.ensure(cm.bytes + 16));
-		uint8_t *hb = (uint8_t *)fe.h_stage.p;
-		std::memcpy(hb + cm.scale, in->scale, 8 * (size_t)n);
-		std::memcpy(hb + cm.shift_x, in->shift_x, 8 * (size_t)n);
-		std::memcpy(hb + cm.glyph_id, in->glyph_id, 2 * (size_t)n);
-		std::memcpy(hb + cm.font_of, in->font_of, 2 * (size_t)n);
-		if (pbf) {
-			std::memcpy(hb + cm.pbf_pre, in->pbf_pre, 4 * (size_t)n);
-			std::memcpy(hb + cm.pbf_fix, in->pbf_fix, n);
-		}
-		std::memset(hb + cm.arrays_end, 0, cm.fonts - cm.arrays_end);
-		uint32_t *cmd_off = (uint32_t *)(hb + cm.cmd_off);
-		uint64_t cmds = 0;
-		for (uint32_t g = 0; g < n; g++) { // one table read and one addition per glyph
-			cmd_off[g] = (uint32_t)cmds;
-			cmds += in->fonts[in->font_of[g]]->slots[in->glyph_id[g]];
-			if (cmds > 0x7FFFFFFFull) {
-				ctx->err = "vgsdf_outlines_resident: more than 2^31 - 1 commands in one submission; split it";
-				return VGSDF_E_ARG;
-			}
-			f.res_scales_plain = f.res_scales_plain && in->scale[g] > 0.0 && in->scale[g] < HUGE_VAL;
-		}
-		cmd_off[n] = (uint32_t)cmds;
-		vgsdf::CommandFontRef *refs = (vgsdf::CommandFontRef *)(hb + cm.fonts);
-		for (uint32_t k = 0; k < in->n_fonts; k++)
-			refs[k] = in->fonts[k]->cref;
-		f.glyf = false;
-		f.resident = false;
-		f.commands = true;
-		f.cmd_off = cmd_off;
-		f.scale = (const double *)(hb + cm.scale);
-		f.shift_x = (const double *)(hb + cm.shift_x);
-		f.pbf_pre = pbf ? (const uint32_t *)(hb + cm.pbf_pre) : nullptr;
-		f.pbf_fix = pbf ? hb + cm.pbf_fix : nullptr;
-		f.n_fonts = in->n_fonts;
-		return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
-	}
-	// the block: the caller's arrays gathered, the two running sums, the fonts' device addresses
-	const vgsdf::ResidentBlockLayout rs(n, in->n_fonts, pbf);
-	FE_TRY(fe.h_stage.ensure(rs.bytes + 16));
-	uint8_t *hb = (uint8_t *)fe.h_stage.p;
-	std::memcpy(hb + rs.scale, in->scale, 8 * (size_t)n);
-	std::memcpy(hb + rs.shift_x, in->shift_x, 8 * (size_t)n);
-	std::memcpy(hb + rs.glyph_id, in->glyph_id, 2 * (size_t)n);
-	std::memcpy(hb + rs.font_of, in->font_of, 2 * (size_t)n);
-	if (pbf) {
-		std::memcpy(hb + rs.pbf_pre, in->pbf_pre, 4 * (size_t)n);
-		std::memcpy(hb + rs.pbf_fix, in->pbf_fix, n);
-	}
-	std::memset(hb + rs.arrays_end, 0, rs.fonts - rs.arrays_end);
-	uint32_t *cmd_off = (uint32_t *)(hb + rs.cmd_off), *part_off = (uint32_t *)(hb + rs.part_off);
-	uint64_t slots = 0, parts = 0;
-	for (uint32_t g = 0; g < n; g++) { // two table reads and two additions per glyph
-		const vgsdf_font &ft = *in->fonts[in->font_of[g]];
-		const uint32_t id = in->glyph_id[g];
-		cmd_off[g] = (uint32_t)slots;
-		part_off[g] = (uint32_t)parts;
-		slots += ft.slots[id];
-		parts += ft.leaf_off[id + 1] - ft.leaf_off[id];
-		if (slots > 0x7FFFFFFFull) {
-			ctx->err = "vgsdf_outlines_resident: more than 2^31 - 1 command slots in one submission; split it";
-			return VGSDF_E_ARG;
-		}
-		f.res_scales_plain = f.res_scales_plain && in->scale[g] > 0.0 && in->scale[g] < HUGE_VAL;
-	}
-	cmd_off[n] = (uint32_t)slots;
-	part_off[n] = (uint32_t)parts;
-	vgsdf::ResidentFontRef *refs = (vgsdf::ResidentFontRef *)(hb + rs.fonts);
-	for (uint32_t k = 0; k < in->n_fonts; k++) {
-		refs[k] = in->fonts[k]->ref;
-		f.res_max_cap = std::max(f.res_max_cap, in->fonts[k]->max_cap);
-		f.res_max_len = std::max(f.res_max_len, in->fonts[k]->max_len);
-	}
-	f.cmd_off = cmd_off;
-	f.scale = (const double *)(hb + rs.scale);
-	f.shift_x = (const double *)(hb + rs.shift_x);
-	f.pbf_pre = pbf ? (const uint32_t *)(hb + rs.pbf_pre) : nullptr;
-	f.pbf_fix = pbf ? hb + rs.pbf_fix : nullptr;
-	f.n_parts = (uint32_t)parts;
-	f.n_fonts = in->n_fonts;
+	FrontEnd *fe = nullptr; // (pending: its upload kernel may still be reading the staging block)
+	if (int rc = fe_acquire(ctx, fe); rc != VGSDF_OK)
+		return rc;
+	if (int rc = commands ? fe_gather_named<vgsdf::CommandBlockLayout>(ctx, *fe, in, f) : fe_gather_named<vgsdf::ResidentBlockLayout>(ctx, *fe, in, f);
+	    rc != VGSDF_OK)
+		return rc;
 	return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
 }
 

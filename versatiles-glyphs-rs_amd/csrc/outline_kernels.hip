@@ -1678,16 +1678,23 @@ extern "C" int vgsdf_copy_in(const void *src_mapped, void *dst, size_t bytes, hi
 	return (int)hipGetLastError();
 }
 
+// LDS of a workgroup of the glyf decoder (either stamping): the largest part's bytes + 5 bytes and a bit per point (a part has
+// fewer points than command slots); parts beyond the limits fail on the device (error_flag bit 4: the host's reader takes the
+// batch).  Sets the two bounds the kernel is launched with
+static size_t glyf_decode_lds(uint32_t max_cmd_cap, uint32_t max_byte_len, uint32_t &max_points, uint32_t &max_bytes)
+{
+	max_points = std::min(std::max(max_cmd_cap, 64u), kGlyfMaxPoints);
+	max_bytes = std::min((std::max(max_byte_len, 64u) + 15u) & ~15u, kGlyfMaxBytes);
+	return (size_t)max_bytes + 4 * (size_t)max_points + 4 * (size_t)((max_points + 31u) / 32u) + max_points;
+}
+
 extern "C" int vgsdf_glyf_decode(const void *parts, uint32_t n_parts, const uint8_t *bytes, OutlineCmd *cmds, uint32_t *error_flag,
                                  uint32_t max_cmd_cap, uint32_t max_byte_len, uint8_t *cmd_open, hipStream_t stream)
 {
 	if (n_parts == 0)
 		return 0;
-	// LDS of a workgroup: the largest part's bytes + 5 bytes and a bit per point (a part has fewer points than command slots);
-	// parts beyond the limits fail on the device (error_flag bit 4: the host's reader takes the batch)
-	const uint32_t max_points = std::min(std::max(max_cmd_cap, 64u), kGlyfMaxPoints);
-	const uint32_t max_bytes = std::min((std::max(max_byte_len, 64u) + 15u) & ~15u, kGlyfMaxBytes);
-	const size_t lds = (size_t)max_bytes + 4 * (size_t)max_points + 4 * (size_t)((max_points + 31u) / 32u) + max_points;
+	uint32_t max_points, max_bytes;
+	const size_t lds = glyf_decode_lds(max_cmd_cap, max_byte_len, max_points, max_bytes);
 	hipLaunchKernelGGL(glyf_decode, dim3(n_parts), dim3(64), lds, stream, (const GlyfPart *)parts, n_parts, bytes, cmds, error_flag, max_points,
 	                   max_bytes, cmd_open);
 	return (int)hipGetLastError();
@@ -1698,10 +1705,8 @@ extern "C" int vgsdf_glyf_decode_resident(const void *parts, uint32_t n_parts, c
 {
 	if (n_parts == 0)
 		return 0;
-	// (LDS as in vgsdf_glyf_decode)
-	const uint32_t max_points = std::min(std::max(max_cmd_cap, 64u), kGlyfMaxPoints);
-	const uint32_t max_bytes = std::min((std::max(max_byte_len, 64u) + 15u) & ~15u, kGlyfMaxBytes);
-	const size_t lds = (size_t)max_bytes + 4 * (size_t)max_points + 4 * (size_t)((max_points + 31u) / 32u) + max_points;
+	uint32_t max_points, max_bytes;
+	const size_t lds = glyf_decode_lds(max_cmd_cap, max_byte_len, max_points, max_bytes);
 	hipLaunchKernelGGL(glyf_decode_resident, dim3(n_parts), dim3(64), lds, stream, (const GlyfPart *)parts, n_parts,
 	                   (const ResidentFontRef *)fonts, cmds, error_flag, max_points, max_bytes, cmd_open);
 	return (int)hipGetLastError();

@@ -1,0 +1,214 @@
+// resident_fonts.cpp — the stores behind vgsdf_font: a face's outlines uploaded once, as `glyf` leaves (vgsdf_font_create)
+// or as expanded commands (vgsdf_font_create_commands).  Submissions that name their glyphs read them
+// (outline_front_end.cpp, vgsdf_outlines_submit_resident).
+#include <algorithm>
+#include <memory>
+#include <new>
+
+#include "outline_kernels.h"
+#include "resident_fonts.h"
+#include "work_plan.h"
+
+namespace {
+// a failed HIP call of a constructor: the entry point's name, what it was doing and the runtime's words
+int font_hip_error(vgsdf_ctx *ctx, const char *entry, const char *what, hipError_t e)
+{
+	ctx->err = std::string(entry) + ": " + what + ": " + hipGetErrorString(e);
+	return e == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;
+}
+struct ScratchBuf : DevBuf { // device memory for the duration of one call
+	~ScratchBuf() { release(); }
+};
+} // namespace
+
+extern "C" {
+
+int vgsdf_font_create(vgsdf_ctx *ctx, const vgsdf_font_desc *in, vgsdf_font **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->leaf_off || (in->n_leaves && !in->leaves) || (in->n_bytes && !in->bytes)) {
+		ctx->err = "vgsdf_font_create: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	const uint32_t n = in->n_glyph_ids;
+	if (n > 0x10000u || (in->n_bytes & 3u) || in->leaf_off[0] != 0 || in->leaf_off[n] != in->n_leaves) {
+		ctx->err = "vgsdf_font_create: more than 65536 glyph ids, n_bytes not a multiple of 4, or leaf_off does not run from 0 to n_leaves";
+		return VGSDF_E_ARG;
+	}
+	std::unique_ptr<vgsdf_font> f(new (std::nothrow) vgsdf_font());
+	if (!f) {
+		ctx->err = "vgsdf_font_create: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	f->slots.assign(n, 0);
+	for (uint32_t g = 0; g < n; g++) {
+		const uint32_t l0 = in->leaf_off[g], l1 = in->leaf_off[g + 1];
+		if (l1 < l0 || l1 > in->n_leaves) {
+			ctx->err = "vgsdf_font_create: leaf_off not ascending";
+			return VGSDF_E_ARG;
+		}
+		uint64_t slots = 0;
+		for (uint32_t i = l0; i < l1; i++) {
+			const vgsdf_glyf_part &lf = in->leaves[i];
+			if (lf.cmd_at != slots || (lf.byte_off & 3u) || lf.byte_off > in->n_bytes || lf.byte_len > in->n_bytes - lf.byte_off ||
+			    lf.n_contours == 0 || lf.plain > 1u) {
+				ctx->err = "vgsdf_font_create: the leaves of a glyph must tile its command slots from 0 in order, with 4-aligned byte ranges "
+				           "inside `bytes`, n_contours > 0 and plain 0 or 1";
+				return VGSDF_E_ARG;
+			}
+			slots += lf.cmd_cap;
+			if (slots > 0x7FFFFFFFull) {
+				ctx->err = "vgsdf_font_create: a glyph of more than 2^31 - 1 command slots";
+				return VGSDF_E_ARG;
+			}
+			f->max_cap = std::max(f->max_cap, lf.cmd_cap);
+			f->max_len = std::max(f->max_len, lf.byte_len);
+		}
+		f->slots[g] = (uint32_t)slots;
+	}
+	f->device = ctx->device;
+	f->n_glyph_ids = n;
+	f->n_leaves = in->n_leaves;
+	f->n_bytes = in->n_bytes;
+	f->leaf_off.assign(in->leaf_off, in->leaf_off + n + 1);
+	(void)hipSetDevice(ctx->device);
+	const size_t leaves_bytes = sizeof(vgsdf_glyf_part) * (size_t)in->n_leaves; // (a multiple of 16)
+	const size_t bytes_at = leaves_bytes, off_at = align_up(bytes_at + in->n_bytes, 16), total = off_at + 4 * ((size_t)n + 1);
+	if (hipError_t e = f->store.ensure(total + 16); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create", "hipMalloc", e);
+	uint8_t *d = (uint8_t *)f->store.p;
+	hipError_t e = leaves_bytes ? hipMemcpyAsync(d, in->leaves, leaves_bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+	if (e == hipSuccess && in->n_bytes)
+		e = hipMemcpyAsync(d + bytes_at, in->bytes, in->n_bytes, hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(d + off_at, in->leaf_off, 4 * ((size_t)n + 1), hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(ctx->stream); // the arrays are on the device when the call returns: every context may name the font
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create", "upload", e);
+	f->ref.leaves = (uint64_t)(uintptr_t)d;
+	f->ref.bytes = (uint64_t)(uintptr_t)(d + bytes_at);
+	f->ref.leaf_off = (uint64_t)(uintptr_t)(d + off_at);
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, vgsdf_font **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->cmd_off || !in->dat_off || (in->n_cmds && !in->kinds) || (in->n_floats && !in->coords)) {
+		ctx->err = "vgsdf_font_create_commands: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	const uint32_t n = in->n_glyph_ids, n_cmds = in->n_cmds;
+	// (the store: 28-byte records | cmd_off | a context byte per record)
+	if (n > 0x10000u || 29ull * n_cmds + 4ull * (n + 1) > 0xFFFFFFFCull || 4ull * in->n_floats > 0xFFFFFFFCull) {
+		ctx->err = "vgsdf_font_create_commands: more than 65536 glyph ids, or a store (29 bytes per command, 4 per glyph id) or "
+		           "coordinates past what 32-bit offsets address";
+		return VGSDF_E_ARG;
+	}
+	if (in->cmd_off[0] != 0 || in->cmd_off[n] != n_cmds || in->dat_off[0] != 0 || in->dat_off[n] != in->n_floats) {
+		ctx->err = "vgsdf_font_create_commands: cmd_off / dat_off do not run from 0 to n_cmds / n_floats";
+		return VGSDF_E_ARG;
+	}
+	std::unique_ptr<vgsdf_font> f(new (std::nothrow) vgsdf_font());
+	if (!f) {
+		ctx->err = "vgsdf_font_create_commands: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	// everything a submission of these commands would be checked for per render, once: the offsets (they bound every read of
+	// the loop below), the kinds, and the coordinates every glyph's kinds carry against its dat_off range
+	f->slots.assign(n, 0);
+	for (uint32_t g = 0; g < n; g++) {
+		const uint32_t c0 = in->cmd_off[g], c1 = in->cmd_off[g + 1], d0 = in->dat_off[g], d1 = in->dat_off[g + 1];
+		if (c1 < c0 || c1 > n_cmds || d1 < d0 || d1 > in->n_floats) {
+			ctx->err = "vgsdf_font_create_commands: cmd_off / dat_off not ascending";
+			return VGSDF_E_ARG;
+		}
+		uint64_t floats = 0;
+		uint32_t bad_kind = 0;
+		for (uint32_t c = c0; c < c1; c++) {
+			const uint32_t k = in->kinds[c];
+			bad_kind |= k > vgsdf::CMD_CLOSE;
+			floats += k <= vgsdf::CMD_LINE ? 2u : (k == vgsdf::CMD_QUAD ? 4u : (k == vgsdf::CMD_CURVE ? 6u : 0u));
+		}
+		if (bad_kind || floats != (uint64_t)(d1 - d0)) {
+			ctx->err = bad_kind ? "vgsdf_font_create_commands: unknown command kind"
+			                    : "vgsdf_font_create_commands: a glyph's dat_off range does not match its command kinds";
+			return VGSDF_E_ARG;
+		}
+		f->slots[g] = c1 - c0;
+	}
+	f->device = ctx->device;
+	f->n_glyph_ids = n;
+	f->commands = true;
+	(void)hipSetDevice(ctx->device);
+	// the store: records | cmd_off | context bytes.  Beside it, for the duration of this call, what the packed form's context
+	// pass reads: scale (1: the bytes then say "ring open" and nothing else) | dat_off | coords | kinds | its error word
+	const size_t off_at = sizeof(vgsdf::OutlineCmd) * (size_t)n_cmds, open_at = off_at + 4 * ((size_t)n + 1), total = open_at + n_cmds;
+	const size_t t_dat = 8 * (size_t)n, t_coords = t_dat + 4 * ((size_t)n + 1), t_kinds = t_coords + 4 * (size_t)in->n_floats,
+	             t_flag = align_up(t_kinds + n_cmds, 16), t_total = t_flag + 16;
+	ScratchBuf tmp;
+	if (hipError_t e = f->store.ensure(total + 16); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_commands", "hipMalloc", e);
+	if (hipError_t e = tmp.ensure(t_total); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_commands", "hipMalloc", e);
+	uint8_t *d = (uint8_t *)f->store.p, *t = (uint8_t *)tmp.p;
+	hipStream_t st = ctx->stream;
+	const std::vector<double> ones(n, 1.0);
+	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+	hipError_t e = copy(d + off_at, in->cmd_off, 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = copy(t, ones.data(), 8 * (size_t)n);
+	if (e == hipSuccess)
+		e = copy(t + t_dat, in->dat_off, 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = copy(t + t_coords, in->coords, 4 * (size_t)in->n_floats);
+	if (e == hipSuccess)
+		e = copy(t + t_kinds, in->kinds, n_cmds);
+	if (e == hipSuccess)
+		e = hipMemsetAsync(t + t_flag, 0, 16, st);
+	if (e == hipSuccess && n_cmds)
+		e = (hipError_t)vgsdf_outline_context_packed(t + t_kinds, (const float *)(t + t_coords), (const uint32_t *)(t + t_dat),
+		                                             (const uint32_t *)(d + off_at), (const double *)t, n, (vgsdf::OutlineCmd *)d, d + open_at,
+		                                             (uint32_t *)(t + t_flag), st);
+	uint32_t flag = 0;
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(&flag, t + t_flag, 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st); // the store is complete when the call returns: every context may name the font
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_commands", "upload", e);
+	if (flag) { // (what the walk above has ruled out, said by the pass itself)
+		ctx->err = "vgsdf_font_create_commands: the device's context pass refused the commands";
+		return VGSDF_E_ARG;
+	}
+	f->cref.cmds = (uint64_t)(uintptr_t)d;
+	f->cref.cmd_off = (uint64_t)(uintptr_t)(d + off_at);
+	f->cref.open = (uint64_t)(uintptr_t)(d + open_at);
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+int vgsdf_font_free(vgsdf_ctx *ctx, vgsdf_font *font)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!font)
+		return VGSDF_OK;
+	if (font->device != ctx->device) {
+		ctx->err = "vgsdf_font_free: the font lives on another device than the context";
+		return VGSDF_E_ARG;
+	}
+	(void)hipSetDevice(ctx->device);
+	delete font;
+	return VGSDF_OK;
+}
+
+uint64_t vgsdf_font_device_bytes(const vgsdf_font *font) { return font ? (uint64_t)font->store.cap : 0; }
+
+} // extern "C"

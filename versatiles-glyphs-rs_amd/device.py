@@ -362,23 +362,34 @@ class SdfContext:
                 L.vgsdf_host_free(host)
         return rects, out, int(ob.value), int(ns.value)
 
+    def _submit(self, entry: str, co, keep: dict, capacity: int, pbf_pre=None, pbf_fix=None):
+        """what the outlines_submit* wrappers share: the PBF arrays attached to the C struct `co`, a page-locked output buffer
+        (freed when the submit fails), and the arrays, the buffer and the glyph count kept until outlines_wait"""
+        L = load_library()
+        if pbf_pre is not None:
+            keep["pbf_pre"] = np.ascontiguousarray(pbf_pre, dtype=np.uint32)
+            co.pbf_pre = keep["pbf_pre"].ctypes.data
+        if pbf_fix is not None:
+            keep["pbf_fix"] = np.ascontiguousarray(pbf_fix, dtype=np.uint8)
+            co.pbf_fix = keep["pbf_fix"].ctypes.data
+        host = L.vgsdf_host_alloc(max(capacity, 1))
+        if not host:
+            raise MemoryError("vgsdf_host_alloc")
+        rc = getattr(L, entry)(self._h, C.byref(co), host, capacity)
+        if rc != 0:
+            L.vgsdf_host_free(host)
+            self._check(rc)
+        self._inflight = (keep, host, capacity, co.n_glyphs)
+
     def outlines_submit(self, cmd_off, cmds, scale, shift_x, capacity: int):
         """first half of the one-submission form: everything is enqueued, nothing waited for (one per context)"""
-        L = load_library()
         keep = {
             "cmd_off": np.ascontiguousarray(cmd_off, dtype=np.uint32), "cmds": np.ascontiguousarray(cmds, dtype=OUTLINE_CMD_DTYPE),
             "scale": np.ascontiguousarray(scale, dtype=np.float64), "shift": np.ascontiguousarray(shift_x, dtype=np.float64),
         }
-        n = len(keep["scale"])
-        host = L.vgsdf_host_alloc(max(capacity, 1))
-        if not host:
-            raise MemoryError("vgsdf_host_alloc")
-        co = _COutlines(n, keep["cmd_off"].ctypes.data, keep["cmds"].ctypes.data, keep["scale"].ctypes.data, keep["shift"].ctypes.data)
-        rc = L.vgsdf_outlines_submit(self._h, C.byref(co), host, capacity)
-        if rc != 0:
-            L.vgsdf_host_free(host)
-            self._check(rc)
-        self._inflight = (keep, host, capacity, n)
+        co = _COutlines(len(keep["scale"]), keep["cmd_off"].ctypes.data, keep["cmds"].ctypes.data, keep["scale"].ctypes.data,
+                        keep["shift"].ctypes.data)
+        self._submit("vgsdf_outlines_submit", co, keep, capacity)
 
     @staticmethod
     def pack_outlines(cmd_off, cmds):
@@ -397,55 +408,25 @@ class SdfContext:
 
     def outlines_submit_packed(self, cmd_off, dat_off, kinds, coords, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None):
         """outlines_submit for the compact upload form (vgsdf_outlines_packed); pbf_pre / pbf_fix: in-place PBF assembly"""
-        L = load_library()
         keep = {
             "cmd_off": np.ascontiguousarray(cmd_off, dtype=np.uint32), "dat_off": np.ascontiguousarray(dat_off, dtype=np.uint32),
             "kinds": np.ascontiguousarray(kinds, dtype=np.uint8), "coords": np.ascontiguousarray(coords, dtype=np.float32),
             "scale": np.ascontiguousarray(scale, dtype=np.float64), "shift": np.ascontiguousarray(shift_x, dtype=np.float64),
         }
-        n = len(keep["scale"])
-        host = L.vgsdf_host_alloc(max(capacity, 1))
-        if not host:
-            raise MemoryError("vgsdf_host_alloc")
-        co = _COutlinesPacked(n, keep["cmd_off"].ctypes.data, keep["dat_off"].ctypes.data, keep["kinds"].ctypes.data,
+        co = _COutlinesPacked(len(keep["scale"]), keep["cmd_off"].ctypes.data, keep["dat_off"].ctypes.data, keep["kinds"].ctypes.data,
                               keep["coords"].ctypes.data, keep["scale"].ctypes.data, keep["shift"].ctypes.data)
-        if pbf_pre is not None:
-            keep["pbf_pre"] = np.ascontiguousarray(pbf_pre, dtype=np.uint32)
-            co.pbf_pre = keep["pbf_pre"].ctypes.data
-        if pbf_fix is not None:
-            keep["pbf_fix"] = np.ascontiguousarray(pbf_fix, dtype=np.uint8)
-            co.pbf_fix = keep["pbf_fix"].ctypes.data
-        rc = L.vgsdf_outlines_submit_packed(self._h, C.byref(co), host, capacity)
-        if rc != 0:
-            L.vgsdf_host_free(host)
-            self._check(rc)
-        self._inflight = (keep, host, capacity, n)
+        self._submit("vgsdf_outlines_submit_packed", co, keep, capacity, pbf_pre, pbf_fix)
 
     def outlines_submit_glyf(self, cmd_off, parts, glyf_bytes, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None):
         """outlines_submit for glyphs that arrive as their `glyf` arrays (vgsdf_outlines_glyf): the device decodes them"""
-        L = load_library()
         keep = {
             "cmd_off": np.ascontiguousarray(cmd_off, dtype=np.uint32), "parts": np.ascontiguousarray(parts, dtype=GLYF_PART_DTYPE),
             "bytes": np.ascontiguousarray(glyf_bytes, dtype=np.uint8),
             "scale": np.ascontiguousarray(scale, dtype=np.float64), "shift": np.ascontiguousarray(shift_x, dtype=np.float64),
         }
-        n = len(keep["scale"])
-        host = L.vgsdf_host_alloc(max(capacity, 1))
-        if not host:
-            raise MemoryError("vgsdf_host_alloc")
-        co = _COutlinesGlyf(n, len(keep["parts"]), len(keep["bytes"]), keep["cmd_off"].ctypes.data, keep["parts"].ctypes.data,
+        co = _COutlinesGlyf(len(keep["scale"]), len(keep["parts"]), len(keep["bytes"]), keep["cmd_off"].ctypes.data, keep["parts"].ctypes.data,
                             keep["bytes"].ctypes.data, keep["scale"].ctypes.data, keep["shift"].ctypes.data)
-        if pbf_pre is not None:
-            keep["pbf_pre"] = np.ascontiguousarray(pbf_pre, dtype=np.uint32)
-            co.pbf_pre = keep["pbf_pre"].ctypes.data
-        if pbf_fix is not None:
-            keep["pbf_fix"] = np.ascontiguousarray(pbf_fix, dtype=np.uint8)
-            co.pbf_fix = keep["pbf_fix"].ctypes.data
-        rc = L.vgsdf_outlines_submit_glyf(self._h, C.byref(co), host, capacity)
-        if rc != 0:
-            L.vgsdf_host_free(host)
-            self._check(rc)
-        self._inflight = (keep, host, capacity, n)
+        self._submit("vgsdf_outlines_submit_glyf", co, keep, capacity, pbf_pre, pbf_fix)
 
     def font_create(self, leaf_off, leaves, store) -> ResidentFont:
         """vgsdf_font_create: a face's description (vgsdf_font_desc: leaf_off[numGlyphs + 1], leaves, bytes) -> ResidentFont"""
@@ -473,7 +454,6 @@ class SdfContext:
 
     def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None):
         """outlines_submit for glyphs named by (font, glyph id) of resident fonts (vgsdf_outlines_resident)"""
-        L = load_library()
         keep = {
             "font_of": np.ascontiguousarray(font_of, dtype=np.uint16), "glyph_id": np.ascontiguousarray(glyph_id, dtype=np.uint16),
             "scale": np.ascontiguousarray(scale, dtype=np.float64), "shift": np.ascontiguousarray(shift_x, dtype=np.float64),
@@ -481,22 +461,9 @@ class SdfContext:
         }
         n = len(keep["scale"])
         assert len(keep["font_of"]) == n and len(keep["glyph_id"]) == n
-        host = L.vgsdf_host_alloc(max(capacity, 1))
-        if not host:
-            raise MemoryError("vgsdf_host_alloc")
         co = _COutlinesResident(n, len(fonts), C.cast(keep["fonts"], C.c_void_p), keep["font_of"].ctypes.data, keep["glyph_id"].ctypes.data,
                                 keep["scale"].ctypes.data, keep["shift"].ctypes.data)
-        if pbf_pre is not None:
-            keep["pbf_pre"] = np.ascontiguousarray(pbf_pre, dtype=np.uint32)
-            co.pbf_pre = keep["pbf_pre"].ctypes.data
-        if pbf_fix is not None:
-            keep["pbf_fix"] = np.ascontiguousarray(pbf_fix, dtype=np.uint8)
-            co.pbf_fix = keep["pbf_fix"].ctypes.data
-        rc = L.vgsdf_outlines_submit_resident(self._h, C.byref(co), host, capacity)
-        if rc != 0:
-            L.vgsdf_host_free(host)
-            self._check(rc)
-        self._inflight = (keep, host, capacity, n)
+        self._submit("vgsdf_outlines_submit_resident", co, keep, capacity, pbf_pre, pbf_fix)
 
     def resident_upload_bytes(self) -> int:
         """size of the block the last resident submission of this context uploaded"""
