@@ -140,6 +140,23 @@ typedef struct {
 	uint64_t block_bytes;    /* bytes of those submissions' upload blocks */
 } vg_command_stats;
 int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out);
+/* Resident families, 0 (default) / 1: a group that the two switches above would submit by (font, glyph id) — against resident
+ * fonts or command stores — is submitted as code-point ranges of its font ids' families instead (vgsdf_outlines_submit_ranges):
+ * one task per (font, block), one per run of code points for a block the hybrid lane plan has split.  The renderer owns the
+ * families beside the fonts (same registry, budget and lifetime; rebuilt when a file is added to the font id); recording a
+ * group is O(tasks), the device writes the PBF entries and the host only the block headers (in-place PBF off: the bitmaps come
+ * packed and the host encodes, id and advance from the family's host table).  A group the device refuses falls back to the
+ * host's reader as ever; with glyph sharding on (vg_manager_set_glyph_shard, lane form 0) groups go by glyph names as without
+ * the switch.  Same bytes.  vg_renderer_preload_fonts also builds the families when the mode is on.
+ * vg_manager_family_stats: of the last render (such groups are counted here, not in the two stats above). */
+void vg_manager_set_resident_families(vg_manager *m, int on);
+typedef struct {
+	uint64_t groups;            /* groups submitted as ranges of families */
+	uint64_t families_uploaded; /* families put on a device during the render */
+	uint64_t family_bytes;      /* ... and what they occupy there */
+	uint64_t block_bytes;       /* bytes of those submissions' upload blocks */
+} vg_family_stats;
+int vg_manager_family_stats(const vg_manager *m, vg_family_stats *out);
 /* How a renderer of several device lanes (vg_renderer_new_multi) splits a run: -1 / 2 (default) the hybrid plan — whole
  * (font, block) tasks per lane, manager.rs:86-97's unit, and the heaviest blocks' glyphs split between lanes until the lanes'
  * estimated raster cost is within 4 % of the mean; 1 whole tasks only; 0 glyph-level shards of every font (every block
@@ -283,6 +300,23 @@ void vg_resident_batch_free(vg_resident_batch *b);
  * (the same view, freed the same way); NULL for an unknown font id or a file without a command table. */
 int vg_manager_command_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_cmds_desc *desc);
 vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, const char *font_id);
+
+/* The host half of a resident family (vgsdf_family_create / vgsdf_outlines_submit_ranges), no device needed: for every code
+ * point the font id maps (up to 0xFFFF, strictly ascending) the file that draws it (font_of: an index into the font id's files,
+ * first provider wins), its glyph id there, PbfGlyph.advance, scale and shift_x — element for element the arrays of
+ * vg_manager_record_resident / _record_resident_commands, whichever kind of store the files get: with fonts[k] the device font
+ * of file k, the view is a vgsdf_family_desc.  Built on first use, kept with the manager and rebuilt when a file is added to the
+ * font id: the pointers stay valid until then.  -1: unknown font id. */
+typedef struct {
+	uint32_t n_entries, n_files;
+	const uint16_t *code_point; /* [n_entries] */
+	const uint16_t *font_of;    /* [n_entries] */
+	const uint16_t *glyph_id;   /* [n_entries] */
+	const uint32_t *advance;    /* [n_entries] */
+	const double *scale;        /* [n_entries] */
+	const double *shift_x;      /* [n_entries] */
+} vg_family_view;
+int vg_manager_family_desc(const vg_manager *m, const char *font_id, vg_family_view *view);
 
 /* Hand-encoder of the glyphs PBF (src/protobuf/glyphs.rs:66-70) for already rendered
  * glyphs; bitmaps[i] may be NULL when !has_bitmap. Returns needed size. */

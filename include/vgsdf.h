@@ -327,6 +327,60 @@ typedef struct {
 	const float *coords;     /* [n_floats] */
 } vgsdf_font_cmds_desc;
 int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, vgsdf_font **out);
+/*
+ * Resident families: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id lives on the device
+ * beside its fonts, and a submission names CODE-POINT RANGES of families instead of glyphs.  The host's share per submission
+ * is O(tasks): the block it uploads holds 32 bytes per task that maps a glyph, per family and per font, and no per-glyph byte.
+ *
+ * vgsdf_family_create validates the description on the host (code points strictly ascending, font_of < n_fonts, every glyph id
+ * inside its face, every font on the context's device and of ONE kind; VGSDF_E_ARG otherwise, nothing left allocated, the
+ * context sound), keeps per entry its fields, pbf_fix (from code point and advance, as vgsdf_outlines_packed states it) and the
+ * prefix sums over the entries of the glyphs' command slots (glyf fonts: and of their leaves), copies the table to the device and
+ * returns when it is there.  A family owns no font: the fonts must outlive it.  vgsdf_family_free follows the timing rule of
+ * vgsdf_font_free.  vgsdf_family_count: the mapped code points in [first, last].
+ */
+typedef struct vgsdf_family vgsdf_family;
+typedef struct {
+	uint32_t n_fonts;               /* 1 .. 65536 */
+	const vgsdf_font *const *fonts; /* one device, ONE kind (all from vgsdf_font_create or all from _create_commands) */
+	uint32_t n_entries;             /* mapped code points, <= 65536 */
+	const uint16_t *code_point;     /* [n_entries] strictly ascending */
+	const uint16_t *font_of;        /* [n_entries] index into fonts */
+	const uint16_t *glyph_id;       /* [n_entries] */
+	const uint32_t *advance;        /* [n_entries] PbfGlyph.advance */
+	const double *scale, *shift_x;  /* [n_entries] as in vgsdf_outlines_resident */
+} vgsdf_family_desc;
+int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out);
+int vgsdf_family_free(vgsdf_ctx *ctx, vgsdf_family *family);
+uint64_t vgsdf_family_device_bytes(const vgsdf_family *family);
+uint32_t vgsdf_family_count(const vgsdf_family *family, uint32_t first, uint32_t last);
+/*
+ * The glyph sequence of a ranges submission: the tasks in order, and inside a task the mapped code points of
+ * [first, last] of its family, ascending.  The output is, byte for byte, that of vgsdf_outlines_submit_resident given that
+ * sequence with the families' fonts, the entries' scale and shift_x, pbf_pre[g] = the task's value on its first glyph and 0
+ * elsewhere, and pbf_fix[g] from the entries' code points (the ids) and advances: rects, segments, bitmaps and
+ * vgsdf_outlines_pbf_positions alike.  With pbf_pre NULL the bitmaps are packed back to back.  With pbf_pre given the device
+ * also WRITES every glyph's entry bytes around its bitmap (0x1A varint(len) 0x08 varint(id) [0x12 varint(w h)] in front,
+ * 0x18 width 0x20 height 0x28 left 0x30 top 0x38 advance behind), wherever the raster stores the bitmaps, so the arena comes
+ * back as finished entries; only the bytes a task reserved with pbf_pre are left for the caller.
+ * Tasks may come in any order, repeat and overlap; a task that maps nothing occupies nothing.  Refused with VGSDF_E_ARG before
+ * anything runs: a family of another device, families of both kinds, more than 65536 fonts over the families, first > last,
+ * family_of past n_families, more than 2^31 - 1 command slots (or glyphs).  n_tasks == 0, or tasks that map nothing, make an
+ * empty submission that waits cleanly.  Collected with vgsdf_outlines_wait; _peek, _pbf_positions and _segments work behind it
+ * as behind any other form, and rects_out of _wait / _peek may be NULL.  The fonts of the block are the families' lists in the
+ * order of `families`, whether or not a task names the family: all of them count towards the 65536 fonts and the upload.  vgsdf_outlines_resident_upload_bytes reports the block.
+ * vgsdf_outlines_task_extents (after _peek or _wait of a ranges submission with pbf_pre): begin[t] = where task t's reserved room
+ * starts in the arena, begin[n_tasks] = the arena's size; a task without glyphs has begin[t] == begin[t + 1].
+ */
+typedef struct {
+	uint32_t n_tasks, n_families;
+	const vgsdf_family *const *families;
+	const uint16_t *family_of;    /* [n_tasks] */
+	const uint16_t *first, *last; /* [n_tasks] inclusive code-point range, first <= last */
+	const uint32_t *pbf_pre;      /* [n_tasks] or NULL: bytes reserved in front of the task's FIRST glyph entry */
+} vgsdf_outlines_ranges;
+int vgsdf_outlines_submit_ranges(vgsdf_ctx *ctx, const vgsdf_outlines_ranges *in, uint8_t *out_bitmaps, size_t out_capacity);
+int vgsdf_outlines_task_extents(vgsdf_ctx *ctx, uint64_t *begin /* [n_tasks + 1] */);
 int vgsdf_outlines_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, uint64_t *n_segments, int *rendered);
 /* Between submit and wait: blocks until the front-end's results are on the host — they leave the device right behind the
  * plan kernel, on a stream of their own, while flattening and raster are still running — and reports the rects and

@@ -157,6 +157,13 @@ int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out)
 	*out = vg_command_stats{t.command_groups, t.command_fonts_uploaded, t.command_font_bytes, t.command_block_bytes};
 	return 0;
 }
+void vg_manager_set_resident_families(vg_manager *m, int on) { m->m.set_resident_families(on != 0); }
+int vg_manager_family_stats(const vg_manager *m, vg_family_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_family_stats{t.family_groups, t.families_uploaded, t.family_bytes, t.family_block_bytes};
+	return 0;
+}
 void vg_manager_set_lane_form(vg_manager *m, int form) { m->m.set_lane_form(form < 0 || form > 2 ? -1 : form); }
 void vg_manager_set_threads(vg_manager *m, unsigned threads, unsigned blocks_per_batch)
 {
@@ -706,6 +713,29 @@ vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, cons
 	} catch (const std::exception &e) {
 		g_err = e.what();
 		return nullptr;
+	}
+}
+int vg_manager_family_desc(const vg_manager *m, const char *font_id, vg_family_view *view)
+{
+	try {
+		std::string err;
+		const vg::FontManager::FamilyTable *t = m && font_id && view ? m->m.family_table(font_id, &err) : nullptr;
+		if (!t) {
+			g_err = err.empty() ? "vg_manager_family_desc: bad argument" : err;
+			return -1;
+		}
+		view->n_entries = (uint32_t)t->code_point.size();
+		view->n_files = (uint32_t)t->n_files;
+		view->code_point = t->code_point.data();
+		view->font_of = t->font_of.data();
+		view->glyph_id = t->glyph_id.data();
+		view->advance = t->advance.data();
+		view->scale = t->scale.data();
+		view->shift_x = t->shift_x.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
 	}
 }
 int vg_resident_batch_view(const vg_resident_batch *b, vg_resident_view *view)

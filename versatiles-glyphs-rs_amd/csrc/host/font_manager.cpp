@@ -572,6 +572,45 @@ bool FontManager::record_resident_commands(const std::string &font_id, ResidentB
 	return true;
 }
 
+const FontManager::FamilyTable *FontManager::family_table(const std::string &font_id, std::string *err) const
+{
+	auto it = fonts().find(font_id);
+	if (it == fonts().end() || it->second.files().size() > 0x10000) {
+		if (err)
+			*err = it == fonts().end() ? "unknown font id " + font_id : "font " + font_id + ": more than 65536 files";
+		return nullptr;
+	}
+	if (parent_) // (a lane of a multi-device run: the table is the font id's, whatever share of its blocks the lane renders)
+		return parent_->family_table(font_id, err);
+	const auto &files = it->second.files();
+	std::lock_guard<std::mutex> lock(family_mu_);
+	std::unique_ptr<FamilyTable> &slot = family_tables_[font_id];
+	if (slot && slot->n_files == files.size())
+		return slot.get();
+	std::map<const FontFileEntry *, uint16_t> file_of;
+	for (size_t k = 0; k < files.size(); k++)
+		file_of.emplace(files[k].get(), (uint16_t)k);
+	ResidentBatch all;
+	for (const GlyphBlock &b : it->second.blocks()) // (the font id's own blocks, not a rank's share of them)
+		for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE && b.start_index + ci <= 0xFFFFu; ci++)
+			if (const FontFileEntry *f = b.glyphs[ci])
+				Renderer::record_resident(f->face(), file_of.at(f), b.start_index + ci, all);
+	auto t = std::make_unique<FamilyTable>();
+	static std::atomic<uint64_t> next_serial{1};
+	t->serial = next_serial++;
+	t->n_files = files.size();
+	for (const GlyphJob &j : all.jobs) {
+		t->code_point.push_back((uint16_t)j.id);
+		t->advance.push_back(j.advance);
+	}
+	t->font_of = std::move(all.font_of);
+	t->glyph_id = std::move(all.glyph_id);
+	t->scale = std::move(all.scale);
+	t->shift_x = std::move(all.shift_x);
+	slot = std::move(t); // (a table built for fewer files is dropped here: its pointers end with it)
+	return slot.get();
+}
+
 const CommandTable *FontManager::command_table(const std::string &font_id, size_t file_index, std::string *err) const
 {
 	auto it = fonts().find(font_id);
@@ -1322,6 +1361,10 @@ void FontManager::render_tasks_multi(Writer &writer, const Renderer &renderer, i
 		timings_.command_fonts_uploaded += ct.command_fonts_uploaded;
 		timings_.command_font_bytes += ct.command_font_bytes;
 		timings_.command_block_bytes += ct.command_block_bytes;
+		timings_.family_groups += ct.family_groups;
+		timings_.families_uploaded += ct.families_uploaded;
+		timings_.family_bytes += ct.family_bytes;
+		timings_.family_block_bytes += ct.family_block_bytes;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1354,6 +1397,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->glyf_on_device_ = glyf_on_device_;
 		c->resident_fonts_ = resident_fonts_;
 		c->resident_commands_ = resident_commands_;
+		c->resident_families_ = resident_families_;
 		c->batch_blocks_ = batch_blocks_;
 		c->batch_blocks_set_ = batch_blocks_set_;
 		c->set_threads(per_lane);
@@ -1369,6 +1413,8 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 			return;
 		}
 	}
+	for (auto &c : children_) // (glyph-level shards: the lanes' groups go by glyph names)
+		c->resident_families_ = false;
 	// shard tables of every font, built on this manager's pool before the lanes start (they only read them)
 	for (const auto &[name, font] : fonts_)
 		(void)cached_shard(name, font, world);
@@ -1435,6 +1481,10 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		timings_.command_fonts_uploaded += ct.command_fonts_uploaded;
 		timings_.command_font_bytes += ct.command_font_bytes;
 		timings_.command_block_bytes += ct.command_block_bytes;
+		timings_.family_groups += ct.family_groups;
+		timings_.families_uploaded += ct.families_uploaded;
+		timings_.family_bytes += ct.family_bytes;
+		timings_.family_block_bytes += ct.family_block_bytes;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1708,6 +1758,112 @@ bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G,
 	return true;
 }
 
+const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font,
+                                               bool commands, const FamilyTable **table, RenderTimings &counts) const
+{
+	const FamilyTable *ft = family_table(font_id, nullptr);
+	if (!ft)
+		return nullptr;
+	std::vector<const vgsdf_font *> stores;
+	for (const auto &file : font.files()) {
+		uint64_t uploaded = 0;
+		const vgsdf_font *f = commands ? renderer.command_font(lane, file->face().command_table(), &uploaded)
+		                               : (file->face().has_glyf_outlines() ? renderer.resident_font(lane, file->face().resident_table(), &uploaded) : nullptr);
+		if (!f)
+			return nullptr;
+		if (uploaded) {
+			(commands ? counts.command_fonts_uploaded : counts.resident_fonts_uploaded)++;
+			(commands ? counts.command_font_bytes : counts.resident_font_bytes) += uploaded;
+		}
+		stores.push_back(f);
+	}
+	uint64_t uploaded = 0;
+	const Renderer::FamilyArrays fa{ft->serial, &ft->code_point, &ft->font_of, &ft->glyph_id, &ft->advance, &ft->scale, &ft->shift_x};
+	const vgsdf_family *fam = renderer.family(lane, fa, stores, commands, &uploaded);
+	if (fam && uploaded) {
+		counts.families_uploaded++;
+		counts.family_bytes += uploaded;
+	}
+	if (table)
+		*table = ft;
+	return fam;
+}
+
+// The group as code-point ranges of its font ids' resident families (vgsdf_outlines_submit_ranges): no glyph is touched — per
+// task two bisections of the family's code points; the device names the glyphs and, in place, writes their PBF entries.
+bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands)
+{
+	const double t0 = now_s();
+	FeGroup::Ranges &R = G.ranges;
+	R.clear();
+	const size_t nb = G.g1 - G.g0;
+	std::vector<uint32_t> task_g0(nb + 1, 0);
+	const std::string *last = nullptr;
+	const FamilyTable *ft = nullptr;
+	uint32_t n_jobs = 0;
+	for (size_t t = G.g0; t < G.g1; t++) {
+		if (tasks[t].name != last) {
+			auto it = fonts().find(*tasks[t].name);
+			if (it == fonts().end() || R.families.size() >= 0xFFFF)
+				return false;
+			const vgsdf_family *fam = device_family(renderer, lane, it->first, it->second, commands, &ft, timings_);
+			if (!fam)
+				return false;
+			last = tasks[t].name;
+			R.families.push_back(fam);
+			R.tables.push_back(ft);
+		}
+		const GlyphBlock &blk = tasks[t].block;
+		task_g0[t - G.g0] = n_jobs;
+		R.task_r0.push_back((uint32_t)R.first.size());
+		if (blk.len() == 0)
+			continue;
+		if (blk.start_index + GLYPH_BLOCK_SIZE - 1 > 0xFFFFu)
+			return false;
+		const auto &cp = ft->code_point;
+		auto add = [&](uint32_t a, uint32_t b, uint32_t room) { // code points [a, b] of the block
+			const auto lo = std::lower_bound(cp.begin(), cp.end(), (uint16_t)a), hi = std::upper_bound(cp.begin(), cp.end(), (uint16_t)b);
+			R.family_of.push_back((uint16_t)(R.families.size() - 1));
+			R.first.push_back((uint16_t)a);
+			R.last.push_back((uint16_t)b);
+			R.pre.push_back(room);
+			R.entry_first.push_back((uint32_t)(lo - cp.begin()));
+			n_jobs += (uint32_t)(hi - lo);
+			return (uint32_t)(hi - lo);
+		};
+		const uint32_t room = (uint32_t)(kPbfHeadRoom + pbf_block_fields(tasks[t].name->size(), blk.range().size()));
+		const uint32_t s = blk.start_index;
+		const auto lo = std::lower_bound(cp.begin(), cp.end(), (uint16_t)s), hi = std::upper_bound(cp.begin(), cp.end(), (uint16_t)(s + GLYPH_BLOCK_SIZE - 1));
+		if ((size_t)(hi - lo) == blk.len()) {
+			add(s, s + GLYPH_BLOCK_SIZE - 1, room);
+		} else { // a block that keeps some of its glyphs (the hybrid lane plan's split): one task per run of code points it keeps
+			bool first = true;
+			for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE;) {
+				if (!blk.glyphs[ci]) {
+					ci++;
+					continue;
+				}
+				uint32_t cj = ci;
+				while (cj < GLYPH_BLOCK_SIZE && blk.glyphs[cj])
+					cj++;
+				if (add(s + ci, s + cj - 1, first ? room : 0u))
+					first = false;
+				else // (a run the family maps nothing of: no task)
+					R.family_of.pop_back(), R.first.pop_back(), R.last.pop_back(), R.pre.pop_back(), R.entry_first.pop_back();
+				ci = cj;
+			}
+		}
+	}
+	task_g0[nb] = n_jobs;
+	R.task_r0.push_back((uint32_t)R.first.size());
+	G.task_g0 = std::move(task_g0);
+	G.n_jobs = n_jobs;
+	G.in_place = in_place_pbf_;
+	G.by_ranges = true;
+	timings_.pack_s += now_s() - t0;
+	return true;
+}
+
 uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 {
 	uint64_t uploaded = 0;
@@ -1728,18 +1884,36 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 					for (const auto &file : kv.second.files())
 						(void)renderer.device_lane(r).command_font(0, file->face().command_table(), &uploaded);
 			}
+	// ... and the families over them, of the kinds of store the modes would name
+	if (resident_families_)
+		for (size_t r = 0; r < renderer.n_devices(); r++)
+			for (const auto &kv : fonts())
+				for (int commands = 0; commands < 2; commands++)
+					if (commands ? resident_commands_ != 0 : resident_fonts_) {
+						RenderTimings counts;
+						(void)device_family(renderer.device_lane(r), 0, kv.first, kv.second, commands != 0, nullptr, counts);
+						uploaded += counts.family_bytes + counts.resident_font_bytes + counts.command_font_bytes;
+					}
 	return uploaded;
 }
 
 void FontManager::fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf, const Renderer *renderer, int lane)
 {
 	// (allow_glyf is false where a group the device has refused is recorded again: that fallback is the reader's, as ever)
+	G.by_ranges = false;
+	// families: wherever a group would go by glyph names below, its ranges go instead (not under glyph sharding, whose blocks
+	// hold a rank's share of every block)
+	const bool families = resident_families_ && (parent_ != nullptr || shard_world_ == 1) && renderer != nullptr;
+	if (allow_glyf && resident_commands_ == 2 && families && fe_record_ranges(tasks, G, *renderer, lane, true))
+		return;
 	if (allow_glyf && resident_commands_ == 2 && renderer && fe_record_resident(tasks, G, *renderer, lane, true))
 		return;
 	if (allow_glyf && glyf_on_device_) {
 		bool all_glyf = true;
 		for (size_t t = G.g0; t < G.g1 && all_glyf; t++)
 			all_glyf = tasks[t].block.all_glyf && !glyf_refused_.count(tasks[t].name);
+		if (all_glyf && resident_fonts_ && families && fe_record_ranges(tasks, G, *renderer, lane, false))
+			return;
 		if (all_glyf && resident_fonts_ && renderer && fe_record_resident(tasks, G, *renderer, lane))
 			return;
 		if (all_glyf) {
@@ -1751,6 +1925,8 @@ void FontManager::fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool all
 		}
 	}
 	// no glyf form for this group: by name against command stores where the mode says so, else the host's reader
+	if (allow_glyf && resident_commands_ == 1 && families && fe_record_ranges(tasks, G, *renderer, lane, true))
+		return;
 	if (allow_glyf && resident_commands_ == 1 && renderer && fe_record_resident(tasks, G, *renderer, lane, true))
 		return;
 	constexpr uint32_t kSlice = 64;
@@ -1873,8 +2049,37 @@ void FontManager::fe_prepare_pieces(const std::vector<Todo> &tasks, FeGroup &G)
 	timings_.encode_s += now_s() - t3;
 }
 
+// A group submitted as ranges: the device has written every glyph's entry; what is left is the block header of every task, in
+// the room in front of its first entry, from the tasks' extents.  The counters come from the rects
+void FontManager::fe_assemble_ranges(const std::vector<Todo> &tasks, FeGroup &G)
+{
+	const double t3 = now_s();
+	const FeGroup::Ranges &R = G.ranges;
+	uint8_t *arena = G.out.data();
+	for (const uint32_t i : G.busy) {
+		const Todo &td = tasks[G.g0 + i];
+		const uint32_t r0 = R.task_r0[i], r1 = R.task_r0[i + 1];
+		if (r0 >= r1 || r1 >= R.extents.size() || R.extents[r1] > G.out_bytes || R.extents[r0] + R.pre[r0] > R.extents[r1])
+			throw std::runtime_error("in-place PBF assembly: the device's extents of a task do not lie inside the arena");
+		uint8_t *first = arena + R.extents[r0] + R.pre[r0], *end = arena + R.extents[r1];
+		uint8_t *file = write_pbf_block_header(first, *td.name, td.block.range(), (size_t)(end - first));
+		G.piece[i] = FeGroup::Piece{file, (size_t)(end - file)};
+	}
+	uint64_t n_raster = 0, n_pixels = 0;
+	for (const vgsdf_rect &r : G.rects)
+		if (r.has_raster) {
+			n_raster++;
+			n_pixels += (uint64_t)r.w * r.h;
+		}
+	G.n_raster = n_raster;
+	G.n_pixels = n_pixels;
+	timings_.encode_s += now_s() - t3;
+}
+
 void FontManager::fe_assemble(const std::vector<Todo> &tasks, FeGroup &G)
 {
+	if (G.by_ranges)
+		return fe_assemble_ranges(tasks, G);
 	ThreadPool &tp = pool();
 	const double t3 = now_s();
 	MergedOutlines &m = G.m;
@@ -1954,6 +2159,18 @@ void FontManager::fe_encode_write(const std::vector<Todo> &tasks, FeGroup &G, Wr
 	const size_t nb = G.g1 - G.g0;
 	const uint32_t n_jobs = G.n_jobs;
 	MergedOutlines &m = G.m;
+	if (G.by_ranges) { // no glyph was recorded: id and advance come from the families' host tables, range by range
+		m.jobs.assign(n_jobs, GlyphJob{});
+		const FeGroup::Ranges &R = G.ranges;
+		uint32_t g = 0;
+		for (size_t r = 0; r < R.first.size(); r++) {
+			const FamilyTable &ft = *R.tables[R.family_of[r]];
+			for (uint32_t e = R.entry_first[r]; e < ft.code_point.size() && ft.code_point[e] <= R.last[r] && g < n_jobs; e++, g++) {
+				m.jobs[g].id = ft.code_point[e];
+				m.jobs[g].advance = ft.advance[e];
+			}
+		}
+	}
 	// bitmap offsets: rasterised glyphs are packed in job order
 	std::vector<uint64_t> boff((size_t)n_jobs + 1, 0);
 	uint64_t n_raster = 0;
@@ -1972,7 +2189,7 @@ void FontManager::fe_encode_write(const std::vector<Todo> &tasks, FeGroup &G, Wr
 		n_raster += job.has_raster;
 	}
 	std::vector<std::pair<size_t, size_t>> span(nb, {0, 0});
-	for (size_t i = 0; i < G.slices.size(); i++) {
+	for (size_t i = 0; !G.by_ranges && i < G.slices.size(); i++) {
 		auto &sp = span[G.slices[i].task - G.g0];
 		if (sp.second == 0)
 			sp.first = i;
@@ -1981,6 +2198,8 @@ void FontManager::fe_encode_write(const std::vector<Todo> &tasks, FeGroup &G, Wr
 	std::vector<std::vector<uint8_t>> encoded(nb);
 	tp.run(nb, [&](size_t i, unsigned) {
 		std::vector<PbfGlyphRef> refs;
+		for (uint32_t g = G.by_ranges ? G.task_g0[i] : 0; G.by_ranges && g < G.task_g0[i + 1]; g++)
+			refs.push_back(m.jobs[g].to_pbf(m.jobs[g].has_raster ? G.out.data() + boff[g] : nullptr));
 		for (size_t k = span[i].first; k < span[i].second; k++) {
 			const OSlice &s = G.slices[k];
 			for (uint32_t j = 0; j < s.job1 - s.job0; j++) {
@@ -2071,6 +2290,11 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 			timings_.fe_groups++;
 			timings_.fe_max_group_glyphs = std::max<uint64_t>(timings_.fe_max_group_glyphs, G.n_jobs);
 			uint64_t block = 0;
+			if (G.by_ranges) {
+				renderer.submit_ranges((int)(k & 1), G.ranges.view(G.in_place), G.n_jobs, G.out, &block);
+				timings_.family_groups++;
+				timings_.family_block_bytes += block;
+			} else
 			switch (G.m.form) {
 			case MergedOutlines::Form::ResidentGlyf:
 				renderer.submit_outlines((int)(k & 1), G.m.view_resident(), G.out, &block);
@@ -2112,6 +2336,8 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 			early = renderer.peek_outlines((int)(k & 1), G.rects, G.out_bytes, G.n_jobs, &G.pbf_at);
 			timings_.device_s += now_s() - t;
 			mark("assemble >", k);
+			if (early && G.by_ranges)
+				renderer.task_extents((int)(k & 1), G.ranges.extents, (uint32_t)G.ranges.first.size());
 			if (early)
 				fe_assemble(tasks, G);
 			t = now_s();
@@ -2142,6 +2368,8 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 		timings_.device_s += now_s() - t;
 		mark("write >", k);
 		if (G.in_place && G.n_jobs) {
+			if (!early && G.by_ranges)
+				renderer.task_extents((int)(k & 1), G.ranges.extents, (uint32_t)G.ranges.first.size());
 			if (!early)
 				fe_assemble(tasks, G);
 			fe_write_pieces(tasks, G, writer);

@@ -151,6 +151,9 @@ struct RenderTimings {
 	uint64_t resident_groups = 0, resident_fonts_uploaded = 0, resident_font_bytes = 0, resident_block_bytes = 0;
 	// the same for groups submitted by name against command stores (set_resident_commands)
 	uint64_t command_groups = 0, command_fonts_uploaded = 0, command_font_bytes = 0, command_block_bytes = 0;
+	// groups submitted as code-point ranges of resident families (counted here and not above), families put on a device, their
+	// bytes there, bytes of those submissions' upload blocks
+	uint64_t family_groups = 0, families_uploaded = 0, family_bytes = 0, family_block_bytes = 0;
 };
 
 class FontManager {
@@ -233,6 +236,11 @@ public:
 	// 2: every group goes that way, `glyf` faces included (the A/B lever).  A store that does not fit the renderer's
 	// budget sends its groups the way they go with 0.
 	void set_resident_commands(int mode) { resident_commands_ = mode < 0 || mode > 2 ? 0 : mode; }
+	// Resident families (default off): a group that would be recorded glyph by glyph against resident fonts or command stores
+	// (the two switches above) is submitted as code-point ranges of its font ids' families instead — one task per (font, block),
+	// one per run of code points for a block the hybrid lane plan has split — and the device writes the PBF entries; recording
+	// is O(tasks).  With glyph sharding on (set_glyph_shard, lane form 0) groups go by glyph names as without the switch
+	void set_resident_families(bool on) { resident_families_ = on; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
 	// returns the bytes put on the devices
 	uint64_t preload_resident_fonts(const Renderer &renderer) const;
@@ -249,8 +257,23 @@ public:
 	// (nullptr / false: unknown font / file, or a face whose commands pass what 32-bit offsets address)
 	bool record_resident_commands(const std::string &font_id, ResidentBatch &out, std::string *err) const;
 	const CommandTable *command_table(const std::string &font_id, size_t file_index, std::string *err) const;
+	// The host half of a resident family (vgsdf_family_create): for every code point the font id maps, up to 0xFFFF and
+	// ascending, the file that draws it (first provider wins), its glyph id there, advance, scale and shift_x — the arithmetic
+	// of Renderer::record_resident, so the arrays equal those of record_resident / record_resident_commands element for
+	// element.  Needs no outline table of either kind.  Built on first use and kept until a file is added to the font id;
+	// the pointer stays valid until then (nullptr: unknown font id, or more than 65536 files)
+	struct FamilyTable {
+		uint64_t serial = 0; // of this build of the table (a rebuilt table is another family on the device)
+		size_t n_files = 0;
+		std::vector<uint16_t> code_point, font_of, glyph_id;
+		std::vector<uint32_t> advance;
+		std::vector<double> scale, shift_x;
+	};
+	const FamilyTable *family_table(const std::string &font_id, std::string *err) const;
 
 private:
+	mutable std::map<std::string, std::unique_ptr<FamilyTable>> family_tables_; // per font id
+	mutable std::mutex family_mu_;
 	struct Todo {
 		const std::string *name;
 		const GlyphBlock &block; // lives in its FontWrapper's table
@@ -375,6 +398,26 @@ private:
 		HostBuffer<uint8_t> out{true};
 		uint64_t out_bytes = 0, n_segs = 0;
 		uint32_t n_jobs = 0;
+		// a group submitted as code-point ranges of resident families (fe_record_ranges): range r is a task of the submission
+		bool by_ranges = false;
+		struct Ranges {
+			std::vector<const vgsdf_family *> families; // of the group's font ids, in task order
+			std::vector<const FamilyTable *> tables;    // ... and their host halves
+			std::vector<uint16_t> family_of, first, last;
+			std::vector<uint32_t> pre;         // bytes in front of the range's first entry: the block header's room, 0 for a block's later runs
+			std::vector<uint32_t> entry_first; // the range's first entry in its family's table
+			std::vector<uint32_t> task_r0;     // first range of every task of the group (+ one past the last)
+			std::vector<uint64_t> extents;     // vgsdf_outlines_task_extents: [ranges + 1]
+			void clear()
+			{
+				families.clear(), tables.clear(), family_of.clear(), first.clear(), last.clear(), pre.clear(), entry_first.clear(), task_r0.clear();
+			}
+			vgsdf_outlines_ranges view(bool with_pre) const
+			{
+				return vgsdf_outlines_ranges{(uint32_t)first.size(), (uint32_t)families.size(), families.data(), family_of.data(), first.data(),
+				                             last.data(), with_pre ? pre.data() : nullptr};
+			}
+		} ranges;
 	};
 	FeGroup fe_group_[2]; // two groups in flight: one on the GPU, one being recorded / encoded
 	// renderer / lane: whose device copies of the fonts a resident group names (nullptr: no resident form for this call)
@@ -382,6 +425,12 @@ private:
 	// false: a face of the group has no resident form or does not fit the renderer's budget — the glyf form takes the group
 	// commands: against the faces' command stores (every readable face has one) instead of their glyf stores
 	bool fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands = false);
+	// false: as above, or a family over the budget, or a block past code point 0xFFFF — the form that names glyphs takes the group
+	bool fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands);
+	// the device family of a font id over its files' stores of one kind (nullptr: a file without such a store, or the budget)
+	const vgsdf_family *device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font, bool commands,
+	                                  const FamilyTable **table, RenderTimings &counts) const;
+	void fe_assemble_ranges(const std::vector<Todo> &tasks, FeGroup &G);
 	bool fe_record_glyf(const std::vector<Todo> &tasks, FeGroup &G); // false: not a batch for the device's decoder (fan-out past 32-bit offsets)
 	// fonts (by id) one of whose groups the device's glyf decoder refused (VGSDF_E_GLYF) or whose parts passed the batch bounds:
 	// later groups and runs record them with the host's reader at once instead of paying the double path again; cleared
@@ -403,6 +452,7 @@ private:
 	bool glyf_on_device_ = glyf_on_device_default(); // glyf fonts: the device decodes the glyphs' arrays (VG_GLYF_ON_DEVICE=0 / set_glyf_on_device(false): the host does)
 	bool resident_fonts_ = false;
 	int resident_commands_ = 0;
+	bool resident_families_ = false;
 	bool device_front_end_ = true; // HIP renderer: flatten on the GPU unless switched off
 	std::map<std::string, FontWrapper> fonts_; // reference: HashMap (arbitrary order); sorted here
 	bool parallel_;

@@ -206,6 +206,13 @@ std::string Renderer::reduce_path() const
 Renderer::~Renderer()
 {
 	if (owns_resident_ && ctx_) { // (the peers and their contexts are still there: members go after this body)
+		for (auto &kv : resident_->families) // (they name the fonts below)
+			for (size_t i = 0; i < n_devices(); i++)
+				if (device_lane(i).device_ == std::get<0>(kv.first)) {
+					vgsdf_family_free(device_lane(i).ctx_, kv.second);
+					break;
+				}
+		resident_->families.clear();
 		for (auto &kv : resident_->fonts)
 			for (size_t i = 0; i < n_devices(); i++)
 				if (device_lane(i).device_ == kv.first.first) {
@@ -499,6 +506,77 @@ const vgsdf_font *Renderer::command_font(int lane, const CommandTable &t, uint64
 	if (uploaded_bytes)
 		*uploaded_bytes += got;
 	return f;
+}
+
+const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std::vector<const vgsdf_font *> &fonts, bool commands,
+                                     uint64_t *uploaded_bytes) const
+{
+	if (mode_ != Mode::Hip)
+		return nullptr;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	const auto key = std::make_tuple(device_, t.serial, commands);
+	if (auto it = rf.families.find(key); it != rf.families.end())
+		return it->second;
+	const uint64_t want = vgsdf::FamilyTableLayout(t.code_point->size()).bytes;
+	if (rf.bytes[device_] + want > rf.budget)
+		return nullptr;
+	vgsdf_family_desc d;
+	d.n_fonts = (uint32_t)fonts.size();
+	d.fonts = fonts.data();
+	d.n_entries = (uint32_t)t.code_point->size();
+	d.code_point = t.code_point->data();
+	d.font_of = t.font_of->data();
+	d.glyph_id = t.glyph_id->data();
+	d.advance = t.advance->data();
+	d.scale = t.scale->data();
+	d.shift_x = t.shift_x->data();
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	vgsdf_family *f = nullptr;
+	{
+		std::lock_guard<std::mutex> lock(mu_);
+		if (vgsdf_family_create(c, &d, &f) != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_family_create: ") + vgsdf_last_error(c));
+	}
+	const uint64_t got = vgsdf_family_device_bytes(f);
+	rf.families.emplace(key, f);
+	rf.bytes[device_] += got;
+	if (uploaded_bytes)
+		*uploaded_bytes += got;
+	return f;
+}
+
+void Renderer::submit_ranges(int lane, const vgsdf_outlines_ranges &v, uint32_t n_glyphs, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const
+{
+	if (mode_ != Mode::Hip)
+		throw std::runtime_error("render_outlines needs the HIP renderer (the device front-end has no CPU form)");
+	lane &= 1;
+	vgsdf_ctx *c = lane_ctx(lane);
+	lane_mu_[lane].lock();
+	try { // (as submit_on_lane)
+		if (out.capacity() == 0)
+			out.ensure((size_t)n_glyphs * 480 + 16384);
+		std::lock_guard<std::mutex> lock(mu_);
+		if (vgsdf_outlines_submit_ranges(c, &v, out.data(), out.capacity()) != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_outlines_submit_ranges: ") + vgsdf_last_error(c));
+		if (block_bytes)
+			*block_bytes = vgsdf_outlines_resident_upload_bytes(c);
+	} catch (...) {
+		lane_mu_[lane].unlock();
+		throw;
+	}
+}
+
+void Renderer::task_extents(int lane, std::vector<uint64_t> &begin, uint32_t n_tasks) const
+{
+	lane &= 1;
+	vgsdf_ctx *c = lane == 0 ? ctx_ : ctx2_;
+	begin.assign((size_t)n_tasks + 1, 0);
+	std::unique_lock<std::mutex> lock(mu_, std::defer_lock);
+	if (lane == 0)
+		lock.lock();
+	if (vgsdf_outlines_task_extents(c, begin.data()) != VGSDF_OK)
+		throw std::runtime_error(std::string("vgsdf_outlines_task_extents: ") + vgsdf_last_error(c));
 }
 
 void Renderer::set_resident_budget(uint64_t bytes_per_device)

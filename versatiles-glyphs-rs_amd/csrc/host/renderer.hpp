@@ -21,6 +21,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../../include/vgsdf.h"
@@ -461,6 +462,22 @@ public:
 	// the same for the command store of a face (vgsdf_font_create_commands): same registry (the tables' serials come from one
 	// sequence), same budget, no eviction.  nullptr: no command table, or over the budget — the caller goes on as without
 	const vgsdf_font *command_font(int lane, const CommandTable &table, uint64_t *uploaded_bytes = nullptr) const;
+	// Resident families (vgsdf_family_create): the device copy of a font id's table code point -> (file, glyph id, advance,
+	// scale, shift_x) over the device fonts of its files, one per (device, table serial, kind of store) in the registry of the
+	// fonts — same budget, freed with the renderer, in front of the fonts.  A table rebuilt after a file was added has a new
+	// serial and so a new family.  nullptr: over the budget
+	struct FamilyArrays {
+		uint64_t serial = 0;
+		const std::vector<uint16_t> *code_point, *font_of, *glyph_id;
+		const std::vector<uint32_t> *advance;
+		const std::vector<double> *scale, *shift_x;
+	};
+	const vgsdf_family *family(int lane, const FamilyArrays &table, const std::vector<const vgsdf_font *> &fonts, bool commands,
+	                           uint64_t *uploaded_bytes = nullptr) const;
+	// a submission of code-point ranges of such families (n_glyphs: for the first capacity guess), and where its tasks'
+	// rooms begin in the arena once it has been peeked at or waited for
+	void submit_ranges(int lane, const vgsdf_outlines_ranges &batch, uint32_t n_glyphs, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const;
+	void task_extents(int lane, std::vector<uint64_t> &begin, uint32_t n_tasks) const;
 	void set_resident_budget(uint64_t bytes_per_device);
 	uint64_t resident_bytes(int device) const; // what the renderer's resident fonts occupy on a device
 	void wait_outlines(int lane, std::vector<vgsdf_rect> &rects, HostBuffer<uint8_t> &out, uint64_t &out_bytes,
@@ -501,6 +518,7 @@ private:
 	struct ResidentFonts { // of a renderer and its peers
 		std::mutex mu;
 		std::map<std::pair<int, uint64_t>, vgsdf_font *> fonts; // (device, the face's serial number) -> its copy there
+		std::map<std::tuple<int, uint64_t, bool>, vgsdf_family *> families; // (device, table serial, command stores) -> the family
 		std::map<int, uint64_t> bytes;                          // per device
 		uint64_t budget = 1ull << 30;
 	};

@@ -30,6 +30,12 @@ struct FePending {
 	size_t spec_cap = 0;
 	uint32_t launch_spans = 0, span_max = 4, span_budget = 16;
 	double t0 = 0, t1 = 0;
+	// a submission of code-point ranges (vgsdf_outlines_submit_ranges)
+	bool by_ranges = false;
+	uint32_t n_tasks = 0, n_live = 0;    // the caller's tasks; of which map a glyph (the block's)
+	std::vector<uint32_t> task_live;     // [n_tasks] the first task of the block at or behind the caller's task t
+	size_t begin_off = 0;                // in the read-back block, with pbf_pre: u64[n_live + 1] where the tasks' reserved rooms begin
+	const void *d_names = nullptr;       // with pbf_pre: vgsdf::EntryName[n] of the device (pbf_entries)
 };
 
 struct FrontEnd {
@@ -141,6 +147,16 @@ int fe_launch_emit(vgsdf_ctx *ctx, FrontEnd &fe)
 		                             (const double *)fe.seg.p + 3, 4, fe.boxes.p, d.hdr, (unsigned long long)fe.seg_cap, ctx->stream);
 	return e;
 }
+// pbf_entries of a ranges submission with pbf_pre: into `out` (NULL: the tasks' extents only); need_ok: under PlanHeader::ok, as
+// the raster enqueued behind the plan — the launches the host repeats after a guess that did not hold pass false
+int fe_launch_entries(vgsdf_ctx *ctx, FrontEnd &fe, uint8_t *out, size_t out_cap, bool need_ok)
+{
+	const FePending &p = fe.pend;
+	const FeDev d = fe_dev(fe);
+	uint8_t *const rh = (uint8_t *)fe.rects_hdr.p;
+	return vgsdf_pbf_entries(d.rects, (const unsigned long long *)(rh + p.at_off), p.d_pbf_pre, p.d_names, p.n, p.n_live, d.hdr, need_ok,
+	                         (unsigned long long)out_cap, out, (unsigned long long *)(rh + p.begin_off), ctx->stream);
+}
 hipError_t fe_ensure_tiles(FrontEnd &fe, size_t want)
 {
 	if (want <= fe.tile_cap)
@@ -188,6 +204,9 @@ struct FeInput {
 	uint32_t n_fonts = 0;
 	uint32_t res_max_cap = 0, res_max_len = 0; // over the fonts the submission names
 	bool res_scales_plain = true;
+	// code-point ranges of families: no per-glyph array exists on the host (the ones above stay NULL but for pbf_pre / pbf_fix,
+	// which only SAY that the submission assembles PBF in place); the block lies in the context's staging buffer
+	const struct FeRanges *ranges = nullptr;
 
 	// the glyphs are named, not sent: the library validated the names, summed the offsets itself and gathered the block
 	bool names_glyphs() const { return form == FeForm::ResidentGlyf || form == FeForm::ResidentCommands; }
@@ -197,11 +216,24 @@ struct FeInput {
 	bool takes_pbf() const { return form != FeForm::Records; }
 };
 
+struct FeRanges {
+	uint32_t n_cmds = 0, n_families = 0;
+	uint32_t n_tasks = 0, n_live = 0;
+	std::vector<uint32_t> task_live;
+	const uint8_t *block = nullptr; // RangesBlockLayout(n_live, n_families, n_fonts)
+	size_t block_bytes = 0;
+};
+
 // ---- submit, step by step (fe_submit below keeps their order: it is part of the contract with the device) ----
 
 // 1. argument checks: nothing is touched on a bad call.  Sets the command and coordinate counts of the batch
 static int fe_check_args(vgsdf_ctx *ctx, const FeInput *in, uint32_t &n_cmds, uint32_t &n_floats)
 {
+	if (in && in->ranges) { // (laid out by the library itself from validated families)
+		n_cmds = in->ranges->n_cmds;
+		n_floats = 0;
+		return VGSDF_OK;
+	}
 	if (!in || (in->n_glyphs && (!in->cmd_off || !in->scale || !in->shift_x || (in->form == FeForm::Packed && !in->dat_off)))) {
 		ctx->err = "vgsdf_outlines: NULL argument";
 		return VGSDF_E_ARG;
@@ -335,7 +367,10 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 	FeUpload up{fe_layout(in, n_cmds, n_floats)};
 	std::visit([&up](const auto &l) { up.block_bytes = l.bytes, up.pbf_pre = l.pbf_pre, up.pbf_fix = l.pbf_fix, up.arrays_bytes = l.end; }, up.layout);
 	// the block is recognised by the caller's pointers: every array where the layout has it, counted from `scale`
-	const uint8_t *hb = (const uint8_t *)in->scale;
+	const uint8_t *hb = in->ranges ? in->ranges->block : (const uint8_t *)in->scale;
+	const size_t layout_bytes = up.block_bytes; // (what the device keeps of a named form, whatever was uploaded)
+	if (in->ranges)
+		up.block_bytes = in->ranges->block_bytes;
 	auto at = [hb](const void *array, size_t off) { return (const uint8_t *)array == hb + off; };
 	bool single = false;
 	switch (in->form) {
@@ -367,7 +402,7 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 	// the device's copy: the block as it stands (ResidentGlyf: and the parts its leaves expand into behind it); the
 	// per-glyph arrays alone where commands or kinds / coords arrive one by one and have buffers of their own
 	const bool arrays_only = in->form == FeForm::Records || (in->form == FeForm::Packed && !up.block);
-	up.meta_bytes = arrays_only ? up.arrays_bytes : up.block_bytes;
+	up.meta_bytes = arrays_only ? up.arrays_bytes : layout_bytes;
 	if (in->form == FeForm::ResidentGlyf)
 		up.meta_bytes += sizeof(vgsdf_glyf_part) * (size_t)in->n_parts;
 	return up;
@@ -392,6 +427,12 @@ static int fe_reserve(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t 
 	p.hdr_off = align_up(sizeof(vgsdf::OutlineRect) * (size_t)n, 16); // rects and totals: one block, one read-back
 	p.at_off = align_up(p.hdr_off + sizeof(vgsdf::PlanHeader), 16);
 	p.rh_bytes = in->pbf_fix ? p.at_off + 8 * (size_t)n : p.hdr_off + sizeof(vgsdf::PlanHeader);
+	if (in->ranges && in->pbf_fix) { // the tasks' extents travel back with the positions; the entries' names stay on the device
+		p.begin_off = p.rh_bytes;
+		p.rh_bytes += 8 * ((size_t)p.n_live + 1);
+		FE_TRY(fe.pbf_in.ensure(sizeof(vgsdf::EntryName) * (size_t)n + 16));
+		p.d_names = fe.pbf_in.p;
+	}
 	FE_TRY(fe.rects_hdr.ensure(p.rh_bytes));
 	FE_TRY(fe.h_rects.ensure(p.rh_bytes));
 	FE_TRY(fe.descs.ensure(sizeof(vgsdf::GlyphDesc) * (size_t)n + 16));
@@ -452,6 +493,23 @@ static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n
 			FE_TRY(copy(dm, up.block, up.block_bytes));
 		return VGSDF_OK;
 	};
+	if (in->ranges) { // ONE kernel: it names the glyphs from the families' tables, then expands / gathers as the cases below
+		const bool commands = in->form == FeForm::ResidentCommands;
+		const void *src = nullptr;
+		if (int rc = fe_kernel_readable_block(ctx, fe, up, src); rc != VGSDF_OK)
+			return rc;
+		// (the device's copy is laid out as that of the form that names its glyphs one by one)
+		const size_t fonts_at = commands ? std::get<vgsdf::CommandBlockLayout>(up.layout).fonts : std::get<vgsdf::ResidentBlockLayout>(up.layout).fonts;
+		const size_t parts_at = commands ? 0 : std::get<vgsdf::ResidentBlockLayout>(up.layout).bytes;
+		FE_KERNEL(vgsdf_family_upload(commands, src, dm, (uint32_t)n, n_cmds, in->n_parts, in->n_fonts, in->ranges->n_live, in->ranges->n_families,
+		                              pbf, dm + parts_at, (vgsdf::OutlineCmd *)fe.cmds.p, (uint8_t *)fe.cmd_open.p, const_cast<void *>(p.d_names),
+		                              fe.flag_word(), st));
+		if (!commands) {
+			up.d_parts = dm + parts_at;
+			up.d_bytes = dm + fonts_at;
+		}
+		fe.resident_upload_bytes = up.block_bytes;
+	} else
 	switch (in->form) {
 	case FeForm::ResidentGlyf: { // ONE kernel: the copy of the block and the expansion of the glyphs' leaves into parts behind it
 		const auto &rs = std::get<vgsdf::ResidentBlockLayout>(up.layout);
@@ -590,6 +648,8 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	                              fe.cmd_box.p, (vgsdf::RingRec *)fe.rings.p, (uint32_t *)fe.cmd_ring.p, d.rects,
 	                              flagw, st));
 	FE_KERNEL(fe_launch_plan(ctx, fe, p.launch_spans));
+	if (p.d_names) // ranges with pbf_pre: the entry bytes, where the raster below stores the bitmaps, and the tasks' extents
+		FE_KERNEL(fe_launch_entries(ctx, fe, p.spec ? p.d_spec : nullptr, p.spec_cap, true));
 	// The front-end's results (rects, totals, positions of the bitmaps) are final once the plan has run: they travel back
 	// on a stream of their own, beside the flattening and the raster instead of behind them — the host can have them a
 	// good 100 us before the bitmaps (vgsdf_outlines_peek), and the end of the submission loses a copy and its hand-over.
@@ -685,6 +745,12 @@ static int fe_submit(vgsdf_ctx *ctx, const FeInput *in, uint8_t *spec_out, size_
 	p.spec_out = spec_out;
 	p.spec_cap = spec_out ? spec_cap : 0;
 	p.t0 = tr0;
+	if (in->ranges) {
+		p.by_ranges = true;
+		p.n_tasks = in->ranges->n_tasks;
+		p.n_live = in->ranges->n_live;
+		p.task_live = in->ranges->task_live;
+	}
 	if (n == 0) {
 		fe.batch.stats = vgsdf_stats{};
 		p.active = true;
@@ -742,7 +808,7 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 	FrontEnd &fe = *ctx->fe;
 	FePending &p = fe.pend;
 	const uint32_t n = p.n;
-	if (n && !rects_out) {
+	if (n && !rects_out && !p.by_ranges) { // (a ranges submission's entries come back finished: its caller may not want the rects)
 		ctx->err = "vgsdf_outlines: NULL argument";
 		return VGSDF_E_ARG;
 	}
@@ -758,9 +824,15 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 	FE_TRY(hipStreamSynchronize(st)); // the one synchronisation of the submission
 	FE_TRY(hipEventSynchronize(ctx->ev_rects)); // (the read-back finished long ago: it left right behind the plan)
 	const double tr2 = fe_now();
-	std::memcpy(rects_out, fe.h_rects.p, sizeof(vgsdf_rect) * (size_t)n);
+	if (rects_out)
+		std::memcpy(rects_out, fe.h_rects.p, sizeof(vgsdf_rect) * (size_t)n);
+	const vgsdf_rect *const rects = (const vgsdf_rect *)fe.h_rects.p;
 	vgsdf::PlanHeader hdr;
 	std::memcpy(&hdr, (const uint8_t *)fe.h_rects.p + p.hdr_off, sizeof hdr);
+	if (hdr.error & 32u) {
+		ctx->err = "vgsdf_outlines_ranges: internal error (an index of the block outside what its upload kernel was launched with)";
+		return VGSDF_E_HIP;
+	}
 	if (hdr.error & 16u) {
 		ctx->err = "vgsdf_outlines_glyf: a `glyf` entry whose arrays do not fit its bytes (ttf-parser drops such a glyph): record this batch "
 		           "with the host's reader";
@@ -801,7 +873,7 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 
 	uint64_t n_pairs = 0, n_pixels = 0;
 	for (uint32_t g = 0; g < n; g++) {
-		const vgsdf_rect &r = rects_out[g];
+		const vgsdf_rect &r = rects[g];
 		if (r.has_raster) {
 			n_pairs += (uint64_t)r.w * r.h * r.n_segments;
 			n_pixels += (uint64_t)r.w * r.h;
@@ -847,6 +919,8 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 				FE_TRY(hipStreamSynchronize(st));
 			}
 		} else if (fe.out_bytes) { // a guess was too small (first batch of a context, a batch unlike the last one)
+			if (p.d_names) // (the entries with the raster, into the device buffer the download takes them from)
+				FE_KERNEL(fe_launch_entries(ctx, fe, b.d_out, (size_t)fe.out_bytes, false));
 			rc = vgsdf_batch_launch(ctx, &fe.batch);
 			if (rc == VGSDF_OK)
 				rc = vgsdf_batch_download(ctx, &fe.batch, p.spec_out);
@@ -1067,6 +1141,149 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 	return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
 }
 
+// ---- code-point ranges of resident families (resident_fonts.cpp, vgsdf_family_create) ----
+
+// The host's share is O(tasks): per task two bisections of its family's code points and two reads of each prefix sum; per
+// submission the totals that size buffers and grids.  The block it uploads (upload_layout.h, RangesBlockLayout) holds a record
+// per task that maps a glyph, per family and per font; the upload kernel names the glyphs (family_upload_kernel.inc)
+int vgsdf_outlines_submit_ranges(vgsdf_ctx *ctx, const vgsdf_outlines_ranges *in, uint8_t *out_bitmaps, size_t out_capacity)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || (in->n_families && !in->families) || (in->n_tasks && (!in->family_of || !in->first || !in->last))) {
+		ctx->err = "vgsdf_outlines_ranges: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	// the families: one device, one kind; their fonts, list after list, are the block's fonts
+	uint64_t n_fonts = 0;
+	uint32_t max_cap = 0, max_len = 0;
+	bool scales_plain = true;
+	for (uint32_t k = 0; k < in->n_families; k++) {
+		const vgsdf_family *fm = in->families[k];
+		if (!fm || fm->device != ctx->device || fm->commands != in->families[0]->commands) {
+			ctx->err = "vgsdf_outlines_ranges: a NULL family, a family of another device than the context's, or families of both kinds "
+			           "(vgsdf_font_create and vgsdf_font_create_commands) in one submission";
+			return VGSDF_E_ARG;
+		}
+		n_fonts += fm->fonts.size();
+		max_cap = std::max(max_cap, fm->max_cap);
+		max_len = std::max(max_len, fm->max_len);
+		scales_plain = scales_plain && fm->scales_plain;
+	}
+	if (n_fonts > 0x10000u) {
+		ctx->err = "vgsdf_outlines_ranges: more than 65536 fonts over the families";
+		return VGSDF_E_ARG;
+	}
+	for (uint32_t t = 0; t < in->n_tasks; t++)
+		if (in->family_of[t] >= in->n_families || in->first[t] > in->last[t]) {
+			ctx->err = "vgsdf_outlines_ranges: family_of past n_families, or first > last";
+			return VGSDF_E_ARG;
+		}
+	const bool commands = in->n_families ? in->families[0]->commands : false;
+	const bool pbf = in->pbf_pre != nullptr;
+	FrontEnd *fe = nullptr; // (pending: its upload kernel may still be reading the staging block)
+	if (int rc = fe_acquire(ctx, fe); rc != VGSDF_OK)
+		return rc;
+	// the tasks: entry range, glyph base, command base, part base
+	FeRanges rg;
+	rg.n_tasks = in->n_tasks;
+	rg.n_families = in->n_families;
+	rg.task_live.resize(in->n_tasks);
+	std::vector<vgsdf::RangeTask> tasks;
+	tasks.reserve(in->n_tasks);
+	uint64_t glyphs = 0, cmds = 0, parts = 0;
+	for (uint32_t t = 0; t < in->n_tasks; t++) {
+		const vgsdf_family &fm = *in->families[in->family_of[t]];
+		const auto e0 = std::lower_bound(fm.code_point.begin(), fm.code_point.end(), in->first[t]) - fm.code_point.begin();
+		const auto e1 = std::upper_bound(fm.code_point.begin(), fm.code_point.end(), in->last[t]) - fm.code_point.begin();
+		rg.task_live[t] = (uint32_t)tasks.size();
+		if (e1 <= e0)
+			continue; // (maps nothing: not in the block; its extent is empty, at the next task's begin)
+		vgsdf::RangeTask rt{};
+		rt.glyph_base = (uint32_t)glyphs;
+		rt.n_glyphs = (uint32_t)(e1 - e0);
+		rt.entry_first = (uint32_t)e0;
+		rt.family = in->family_of[t];
+		rt.cmd_rel = (uint32_t)cmds - (uint32_t)fm.cmd_pre[e0];
+		rt.part_rel = (uint32_t)parts - (uint32_t)fm.leaf_pre[e0];
+		rt.pbf_pre = pbf ? in->pbf_pre[t] : 0u;
+		tasks.push_back(rt);
+		glyphs += rt.n_glyphs;
+		cmds += fm.cmd_pre[e1] - fm.cmd_pre[e0];
+		parts += fm.leaf_pre[e1] - fm.leaf_pre[e0];
+		if (cmds > 0x7FFFFFFFull || glyphs > 0x7FFFFFFFull) {
+			ctx->err = "vgsdf_outlines_ranges: more than 2^31 - 1 command slots (or glyphs) in one submission; split it";
+			return VGSDF_E_ARG;
+		}
+	}
+	rg.n_live = (uint32_t)tasks.size();
+	rg.n_cmds = (uint32_t)cmds;
+	// the block, in the context's page-locked staging buffer
+	const vgsdf::RangesBlockLayout at(rg.n_live, in->n_families, (size_t)n_fonts);
+	FE_TRY(fe->h_stage.ensure(at.bytes + 16));
+	uint8_t *hb = (uint8_t *)fe->h_stage.p;
+	if (!tasks.empty())
+		std::memcpy(hb + at.tasks, tasks.data(), sizeof(vgsdf::RangeTask) * tasks.size());
+	vgsdf::FamilyRef *frefs = (vgsdf::FamilyRef *)(hb + at.families);
+	uint32_t font_base = 0;
+	for (uint32_t k = 0; k < in->n_families; k++) {
+		const vgsdf_family &fm = *in->families[k];
+		vgsdf::FamilyRef r{};
+		r.table = (uint64_t)(uintptr_t)fm.table.p;
+		r.n_entries = (uint32_t)fm.code_point.size();
+		r.font_base = font_base;
+		r.n_fonts = (uint32_t)fm.fonts.size();
+		frefs[k] = r;
+		for (const vgsdf_font *ft : fm.fonts) { // (both references are 32 bytes)
+			if (commands)
+				((vgsdf::CommandFontRef *)(hb + at.fonts))[font_base++] = ft->cref;
+			else
+				((vgsdf::ResidentFontRef *)(hb + at.fonts))[font_base++] = ft->ref;
+		}
+	}
+	rg.block = hb;
+	rg.block_bytes = at.bytes;
+	FeInput f;
+	f.form = commands ? FeForm::ResidentCommands : FeForm::ResidentGlyf;
+	f.n_glyphs = (uint32_t)glyphs;
+	f.n_parts = (uint32_t)parts;
+	f.n_fonts = (uint32_t)n_fonts;
+	f.res_max_cap = max_cap;
+	f.res_max_len = max_len;
+	f.res_scales_plain = scales_plain;
+	f.ranges = &rg;
+	if (pbf) { // (never read on the host in a named form: they say that the submission assembles PBF in place)
+		f.pbf_pre = (const uint32_t *)hb;
+		f.pbf_fix = hb;
+	}
+	fe->resident_upload_bytes = at.bytes;
+	return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
+}
+
+int vgsdf_outlines_task_extents(vgsdf_ctx *ctx, uint64_t *begin)
+{
+	if (!ctx || !begin)
+		return VGSDF_E_ARG;
+	FrontEnd *fe = ctx->fe;
+	if (!fe || !(fe->prepared || (fe->pend.active && fe->peeked)) || !fe->pend.by_ranges || (fe->pend.n && !fe->pend.d_names)) {
+		ctx->err = "vgsdf_outlines_task_extents: the last batch was not a ranges submission with pbf_pre that has been peeked at or waited for";
+		return VGSDF_E_ARG;
+	}
+	const FePending &p = fe->pend;
+	if (p.n) { // (peeked at, not yet waited for: a batch in error has no extents, and says so in wait)
+		vgsdf::PlanHeader hdr;
+		std::memcpy(&hdr, (const uint8_t *)fe->h_rects.p + p.hdr_off, sizeof hdr);
+		if (hdr.error) {
+			ctx->err = "vgsdf_outlines_task_extents: the batch is in error (vgsdf_outlines_wait reports it)";
+			return VGSDF_E_ARG;
+		}
+	}
+	const uint64_t *live = p.n ? (const uint64_t *)((const uint8_t *)fe->h_rects.p + p.begin_off) : nullptr;
+	for (uint32_t t = 0; t <= p.n_tasks; t++)
+		begin[t] = live ? live[t < p.n_tasks ? p.task_live[t] : p.n_live] : 0;
+	return VGSDF_OK;
+}
+
 int vgsdf_outlines_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, uint64_t *n_segments, int *rendered)
 {
 	return fe_wait(ctx, rects_out, out_bytes, n_segments, rendered);
@@ -1088,13 +1305,14 @@ int vgsdf_outlines_peek(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_byt
 	const FePending &p = fe.pend;
 	if (p.n == 0)
 		return VGSDF_OK;
-	if (!rects_out) {
+	if (!rects_out && !p.by_ranges) {
 		ctx->err = "vgsdf_outlines: NULL argument";
 		return VGSDF_E_ARG;
 	}
 	(void)hipSetDevice(ctx->device);
 	FE_TRY(hipEventSynchronize(ctx->ev_rects));
-	std::memcpy(rects_out, fe.h_rects.p, sizeof(vgsdf_rect) * (size_t)p.n);
+	if (rects_out)
+		std::memcpy(rects_out, fe.h_rects.p, sizeof(vgsdf_rect) * (size_t)p.n);
 	vgsdf::PlanHeader hdr;
 	std::memcpy(&hdr, (const uint8_t *)fe.h_rects.p + p.hdr_off, sizeof hdr);
 	if (out_bytes)
@@ -1153,6 +1371,8 @@ int vgsdf_outlines_render(vgsdf_ctx *ctx, uint8_t *out_bitmaps)
 	(void)hipSetDevice(ctx->device);
 	FE_TRY(fe.out.ensure((size_t)fe.out_bytes + 16)); // (the one-submission form may have rendered elsewhere)
 	fe.batch.d_out = (uint8_t *)fe.out.p;
+	if (fe.pend.d_names) // (a ranges submission with pbf_pre: its entries with its bitmaps)
+		FE_KERNEL(fe_launch_entries(ctx, fe, fe.batch.d_out, (size_t)fe.out_bytes, false));
 	int rc = vgsdf_batch_launch(ctx, &fe.batch);
 	if (rc != VGSDF_OK)
 		return rc;

@@ -43,7 +43,8 @@ struct PlanHeader {
 	uint32_t n_main;               // of which for the main kernel (they come first)
 	uint32_t error;                // bit 0: absurd input (a glyph beyond 2^28 points / 2^32 pixels, more than 2^32 - 1 segments);
 	                               // bit 1: a command kind that is none of the five callbacks; bit 2: a cubic broke its depth bound;
-	                               // bit 3: dat_off does not match the kinds; bit 4: a malformed `glyf` entry (vgsdf_outlines_glyf)
+	                               // bit 3: dat_off does not match the kinds; bit 4: a malformed `glyf` entry (vgsdf_outlines_glyf);
+	                               // bit 5: an index of a ranges block outside what its upload kernel was launched with
 	uint32_t ok;                   // the raster launch enqueued behind the plan may run: no error, everything within the
 	                               // capacities and the grid it was planned against (outline_plan's last arguments)
 };
@@ -77,6 +78,21 @@ int vgsdf_resident_expand(const void *src, void *dst, size_t block_bytes, uint32
 // (vgsdf::CommandFontRef records in the block) into cmds_out[n_cmds] / cmd_open[n_cmds] at the block's cmd_off
 int vgsdf_resident_gather(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_fonts,
                           bool with_pbf, vgsdf::OutlineCmd *cmds_out, uint8_t *cmd_open, hipStream_t stream);
+// upload of a vgsdf_outlines_ranges submission, against fonts of either kind: src = the block (upload_layout.h,
+// RangesBlockLayout: n_tasks task records, n_families family records, n_fonts font references; device-readable as above),
+// dst = the device's copy in ResidentBlockLayout / CommandBlockLayout, whose per-glyph arrays and font references the kernel
+// WRITES; then the expansion into parts_out[n_parts] (glyf fonts) or the gather into cmds_out / cmd_open[n_cmds] (command
+// fonts).  names: vgsdf::EntryName[n_glyphs], written when with_pbf (for vgsdf_pbf_entries).  error_flag bit 5: an index of the
+// block that does not hold against these counts
+int vgsdf_family_upload(bool commands, const void *src, void *dst, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts, uint32_t n_fonts,
+                        uint32_t n_tasks, uint32_t n_families, bool with_pbf, void *parts_out, vgsdf::OutlineCmd *cmds_out,
+                        uint8_t *cmd_open, void *names, uint32_t *error_flag, hipStream_t stream);
+// behind the plan of a ranges submission with pbf_pre: the entry bytes around every bitmap into `out` (out_cap bytes; NULL: none;
+// need_ok: only under PlanHeader::ok, as the raster enqueued behind the plan), and begin[n_tasks + 1]: where every task's
+// reserved room starts, and the arena's size
+int vgsdf_pbf_entries(const vgsdf::OutlineRect *rects, const unsigned long long *pbf_at, const uint32_t *pbf_pre, const void *names,
+                      uint32_t n_glyphs, uint32_t n_tasks, const vgsdf::PlanHeader *hdr, bool need_ok, unsigned long long out_cap,
+                      uint8_t *out, unsigned long long *begin, hipStream_t stream);
 // upload by a kernel: src_mapped = device address of a page-locked, device-mapped host block (16-byte aligned), dst 16-byte aligned
 int vgsdf_copy_in(const void *src_mapped, void *dst, size_t bytes, hipStream_t stream);
 // cmd_open: one byte per command (bit 0: ring open in front of it, bit 1: the glyph's scale is not positive finite)

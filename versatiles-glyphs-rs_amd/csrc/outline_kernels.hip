@@ -1506,30 +1506,7 @@ __global__ __launch_bounds__(kExpandThreads) void resident_expand(const uint4 *_
 	if (ng == 0) // (uniform in the workgroup)
 		return;
 	__syncthreads();
-	const uint32_t p1 = min(s_part_off[ng], n_parts);
-	for (uint32_t j = s_part_off[0] + t; j < p1; j += kExpandThreads) {
-		// the glyph of part j: the last one whose parts begin at or in front of j (glyphs without leaves share an offset)
-		uint32_t lo = 0, hi = ng;
-		while (hi - lo > 1u) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (s_part_off[mid] <= j)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		const uint32_t f = s_font[lo];
-		const ResidentFontRef ref = f < kExpandFontCache ? s_fonts[f] : fonts[f];
-		const uint32_t leaf = reinterpret_cast<const uint32_t *>(ref.leaf_off)[s_gid[lo]] + (j - s_part_off[lo]);
-		const uint4 *lp = reinterpret_cast<const uint4 *>(reinterpret_cast<const GlyfPart *>(ref.leaves) + leaf);
-		uint4 r0 = lp[0], r1 = lp[1];
-		const uint4 r2 = lp[2];
-		r0.z += s_cmd_off[lo]; // cmd_at: from the glyph's first slot -> in the batch
-		r1.y |= f << 16;       // plain | font index (glyf_decode_resident)
-		uint4 *op = reinterpret_cast<uint4 *>(parts_out + j);
-		op[0] = r0;
-		op[1] = r1;
-		op[2] = r2;
-	}
+#include "resident_expand_leaves.inc"
 }
 
 // The upload of a submission that names its glyphs against COMMAND fonts (vgsdf_font_create_commands): copy_in's copy of the
@@ -1576,54 +1553,91 @@ __global__ __launch_bounds__(kExpandThreads) void resident_gather(const uint4 *_
 	if (ng == 0) // (uniform in the workgroup)
 		return;
 	__syncthreads();
-	if (t < ng) {
-		const CommandFontRef ref = f < kExpandFontCache ? s_fonts[f] : fonts[f];
-		const uint32_t first = reinterpret_cast<const uint32_t *>(ref.cmd_off)[gid];
-		s_recs[t] = reinterpret_cast<const uint32_t *>(ref.cmds) + 7ull * first;
-		s_open[t] = reinterpret_cast<const uint8_t *>(ref.open) + first;
+#include "resident_gather_records.inc"
+}
+
+// The uploads of a submission that names code-point ranges of resident families: what the launch is given (the counts every
+// index of the block is bounded against, where the block's records lie, where the device's copy has its per-glyph arrays)
+constexpr uint32_t kFamilyCache = 64; // family records a workgroup keeps in LDS
+struct FamilyLaunch {
+	uint32_t n_glyphs, n_cmds, n_parts, n_fonts, n_tasks, n_families, with_pbf;
+	uint32_t families_at, fonts_at; // in the block (its task records begin it)
+	uint32_t d_scale, d_shift_x, d_cmd_off, d_part_off, d_glyph_id, d_font_of, d_pbf_pre, d_pbf_fix, d_fonts; // in the device's copy
+};
+#define FAMILY_GLYF 1
+#include "family_upload_kernel.inc"
+#undef FAMILY_GLYF
+#define FAMILY_GLYF 0
+#include "family_upload_kernel.inc"
+#undef FAMILY_GLYF
+
+// In-place PBF assembly of a ranges submission: the bytes of every glyph's entry AROUND its bitmap, written on the device —
+// what the host's write_pbf_entry_headers (csrc/host/pbf.cpp) writes for the other forms once the rects are back.  A lane per
+// glyph, behind the plan: from the rect, the bitmap's position pbf_at[g] and the entry's id and advance (left by the upload
+// kernel) it stores
+//   0x1A varint(msg) 0x08 varint(id) [0x12 varint(w h)]                      ending at pbf_at[g]
+//   0x18 width 0x20 height 0x28 zigzag(left) 0x30 zigzag(top) 0x38 advance   behind the bitmap (PbfGlyph::empty without a raster)
+// with pbf_place's arithmetic, into `out`: wherever the submission's raster stores its bitmaps, under the same PlanHeader::ok
+// guard (need_ok = 0: the launch the host repeats after a guess that did not hold).  No byte of a bitmap or of a task's
+// reserved room is touched; plain byte stores.  It also notes where every task's reserved room begins (begin[task], and the
+// arena's size behind the last): positions, valid whether or not the entries could be stored.
+__device__ __forceinline__ uint8_t *put_varint(uint8_t *p, unsigned long long v)
+{
+	for (; v >= 0x80ull; v >>= 7)
+		*p++ = (uint8_t)(v | 0x80ull);
+	*p++ = (uint8_t)v;
+	return p;
+}
+__global__ __launch_bounds__(256) void pbf_entries(const OutlineRect *__restrict__ rects, const unsigned long long *__restrict__ pbf_at,
+                                                   const uint32_t *__restrict__ pbf_pre, const EntryName *__restrict__ names,
+                                                   uint32_t n_glyphs, uint32_t n_tasks, const PlanHeader *__restrict__ hdr, uint32_t need_ok,
+                                                   unsigned long long out_cap, uint8_t *__restrict__ out,
+                                                   unsigned long long *__restrict__ begin)
+{
+	const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+	if (g >= n_glyphs || hdr->error != 0) // (the positions of a batch in error say nothing)
+		return;
+	const OutlineRect r = rects[g];
+	const EntryName nm = names[g];
+	const unsigned long long at = pbf_at[g];
+	const uint32_t idlen = 1u + varint_len(nm.id), advlen = 1u + varint_len(nm.advance);
+	const unsigned long long px = r.has_raster ? (unsigned long long)r.w * r.h : 0ull;
+	uint32_t width = 0, height = 0, zl = 0, zt = 0, bm_hdr = 0;
+	if (r.has_raster) {
+		const uint32_t left = (uint32_t)r.x0 + 3u, top = (uint32_t)r.y0 + r.h - 27u; // two's complement, as i32 arithmetic wraps
+		width = r.w - 6u, height = r.h - 6u;
+		zl = (left << 1) ^ (uint32_t)((int32_t)left >> 31), zt = (top << 1) ^ (uint32_t)((int32_t)top >> 31);
+		bm_hdr = 1u + varint_len(px);
 	}
-	__syncthreads();
-	const uint32_t c1 = min(s_cmd_off[ng], n_cmds);
-	for (uint32_t base = s_cmd_off[0] + t; base < c1; base += kExpandThreads * kGatherUnroll) {
-		const uint32_t *rp[kGatherUnroll];
-		const uint8_t *op[kGatherUnroll];
-#pragma unroll
-		for (uint32_t u = 0; u < kGatherUnroll; u++) {
-			const uint32_t j = base + u * kExpandThreads;
-			// the glyph of command j: the last one whose commands begin at or in front of j (glyphs without commands share an offset)
-			uint32_t lo = 0, hi = ng;
-			while (hi - lo > 1u) {
-				const uint32_t mid = (lo + hi) >> 1;
-				if (s_cmd_off[mid] <= j)
-					lo = mid;
-				else
-					hi = mid;
-			}
-			const uint32_t k = j - s_cmd_off[lo];
-			rp[u] = j < c1 ? s_recs[lo] + 7u * k : nullptr;
-			op[u] = s_open[lo] + k;
-		}
-		uint32_t r[kGatherUnroll][7];
-		uint8_t o[kGatherUnroll];
-#pragma unroll
-		for (uint32_t u = 0; u < kGatherUnroll; u++)
-			if (rp[u]) {
-#pragma unroll
-				for (uint32_t w = 0; w < 7; w++)
-					r[u][w] = rp[u][w];
-				o[u] = *op[u];
-			}
-#pragma unroll
-		for (uint32_t u = 0; u < kGatherUnroll; u++)
-			if (rp[u]) {
-				const uint32_t j = base + u * kExpandThreads;
-				uint32_t *out = cmds_out + 7ull * j;
-#pragma unroll
-				for (uint32_t w = 0; w < 7; w++)
-					out[w] = r[u][w];
-				open_out[j] = o[u];
-			}
+	const uint32_t back = 4u + varint_len(width) + varint_len(height) + varint_len(zl) + varint_len(zt) + advlen;
+	const unsigned long long msg = (unsigned long long)idlen + bm_hdr + px + back;
+	const uint32_t front = 1u + varint_len(msg) + idlen + bm_hdr;
+	if (nm.task_first != 0 && nm.task_first <= n_tasks)
+		begin[nm.task_first - 1u] = at - front - pbf_pre[g];
+	if (g == n_glyphs - 1u)
+		begin[n_tasks] = hdr->out_bytes;
+	if (out == nullptr || (need_ok && hdr->ok == 0) || at < front || at + px + back > out_cap)
+		return;
+	uint8_t *p = out + (at - front);
+	*p++ = 0x1A;
+	p = put_varint(p, msg);
+	*p++ = 0x08;
+	p = put_varint(p, nm.id);
+	if (r.has_raster) {
+		*p++ = 0x12;
+		p = put_varint(p, px);
 	}
+	p = out + at + px; // (behind the bitmap, which the raster stores)
+	*p++ = 0x18;
+	p = put_varint(p, width);
+	*p++ = 0x20;
+	p = put_varint(p, height);
+	*p++ = 0x28;
+	p = put_varint(p, zl);
+	*p++ = 0x30;
+	p = put_varint(p, zt);
+	*p++ = 0x38;
+	p = put_varint(p, nm.advance);
 }
 
 } // namespace vgsdf
@@ -1665,6 +1679,47 @@ extern "C" int vgsdf_resident_expand(const void *src, void *dst, size_t block_by
 	hipLaunchKernelGGL(resident_expand, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint4 *)src, (uint4 *)dst, n16, n_glyphs, n_parts,
 	                   n_fonts, (uint32_t)rl.cmd_off, (uint32_t)rl.part_off, (uint32_t)rl.glyph_id, (uint32_t)rl.font_of, (uint32_t)rl.fonts,
 	                   (GlyfPart *)parts_out);
+	return (int)hipGetLastError();
+}
+
+extern "C" int vgsdf_family_upload(bool commands, const void *src, void *dst, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts,
+                                   uint32_t n_fonts, uint32_t n_tasks, uint32_t n_families, bool with_pbf, void *parts_out,
+                                   OutlineCmd *cmds_out, uint8_t *cmd_open, void *names, uint32_t *error_flag, hipStream_t stream)
+{
+	if (n_glyphs == 0)
+		return 0;
+	const RangesBlockLayout bl(n_tasks, n_families, n_fonts);
+	FamilyLaunch L{};
+	L.n_glyphs = n_glyphs, L.n_cmds = n_cmds, L.n_parts = n_parts, L.n_fonts = n_fonts, L.n_tasks = n_tasks, L.n_families = n_families;
+	L.with_pbf = with_pbf ? 1u : 0u;
+	L.families_at = (uint32_t)bl.families, L.fonts_at = (uint32_t)bl.fonts;
+	const uint32_t grid = (std::max(n_glyphs, 2u * n_fonts) + kExpandThreads - 1u) / kExpandThreads;
+	if (commands) {
+		const CommandBlockLayout cl(n_glyphs, n_fonts, with_pbf);
+		L.d_scale = (uint32_t)cl.scale, L.d_shift_x = (uint32_t)cl.shift_x, L.d_cmd_off = (uint32_t)cl.cmd_off;
+		L.d_glyph_id = (uint32_t)cl.glyph_id, L.d_font_of = (uint32_t)cl.font_of, L.d_pbf_pre = (uint32_t)cl.pbf_pre;
+		L.d_pbf_fix = (uint32_t)cl.pbf_fix, L.d_fonts = (uint32_t)cl.fonts;
+		hipLaunchKernelGGL(family_gather, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint8_t *)src, (uint8_t *)dst, L,
+		                   (uint32_t *)cmds_out, cmd_open, (EntryName *)names, error_flag);
+	} else {
+		const ResidentBlockLayout rl(n_glyphs, n_fonts, with_pbf);
+		L.d_scale = (uint32_t)rl.scale, L.d_shift_x = (uint32_t)rl.shift_x, L.d_cmd_off = (uint32_t)rl.cmd_off, L.d_part_off = (uint32_t)rl.part_off;
+		L.d_glyph_id = (uint32_t)rl.glyph_id, L.d_font_of = (uint32_t)rl.font_of, L.d_pbf_pre = (uint32_t)rl.pbf_pre;
+		L.d_pbf_fix = (uint32_t)rl.pbf_fix, L.d_fonts = (uint32_t)rl.fonts;
+		hipLaunchKernelGGL(family_expand, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint8_t *)src, (uint8_t *)dst, L,
+		                   (GlyfPart *)parts_out, (EntryName *)names, error_flag);
+	}
+	return (int)hipGetLastError();
+}
+
+extern "C" int vgsdf_pbf_entries(const OutlineRect *rects, const unsigned long long *pbf_at, const uint32_t *pbf_pre, const void *names,
+                                 uint32_t n_glyphs, uint32_t n_tasks, const PlanHeader *hdr, bool need_ok, unsigned long long out_cap,
+                                 uint8_t *out, unsigned long long *begin, hipStream_t stream)
+{
+	if (n_glyphs == 0)
+		return 0;
+	hipLaunchKernelGGL(pbf_entries, dim3((n_glyphs + 255u) / 256u), dim3(256), 0, stream, rects, pbf_at, pbf_pre, (const EntryName *)names,
+	                   n_glyphs, n_tasks, hdr, need_ok ? 1u : 0u, out_cap, out, begin);
 	return (int)hipGetLastError();
 }
 

@@ -1,7 +1,11 @@
 // resident_fonts.cpp — the stores behind vgsdf_font: a face's outlines uploaded once, as `glyf` leaves (vgsdf_font_create)
 // or as expanded commands (vgsdf_font_create_commands).  Submissions that name their glyphs read them
-// (outline_front_end.cpp, vgsdf_outlines_submit_resident).
+// (outline_front_end.cpp, vgsdf_outlines_submit_resident).  And the families over them (vgsdf_family_create): a font id's table
+// code point -> (font, glyph id, advance, scale, shift_x) on host and device, for submissions that name code-point ranges
+// (vgsdf_outlines_submit_ranges).
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <memory>
 #include <new>
 
@@ -210,5 +214,116 @@ int vgsdf_font_free(vgsdf_ctx *ctx, vgsdf_font *font)
 }
 
 uint64_t vgsdf_font_device_bytes(const vgsdf_font *font) { return font ? (uint64_t)font->store.cap : 0; }
+
+int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->fonts ||
+	    (in->n_entries && (!in->code_point || !in->font_of || !in->glyph_id || !in->advance || !in->scale || !in->shift_x))) {
+		ctx->err = "vgsdf_family_create: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	const uint32_t n = in->n_entries;
+	if (in->n_fonts == 0 || in->n_fonts > 0x10000u || n > 0x10000u) {
+		ctx->err = "vgsdf_family_create: n_fonts must be 1 .. 65536 and n_entries at most 65536";
+		return VGSDF_E_ARG;
+	}
+	for (uint32_t k = 0; k < in->n_fonts; k++)
+		if (!in->fonts[k] || in->fonts[k]->device != ctx->device || in->fonts[k]->commands != in->fonts[0]->commands) {
+			ctx->err = "vgsdf_family_create: a NULL font, a font of another device than the context's, or fonts of both kinds";
+			return VGSDF_E_ARG;
+		}
+	for (uint32_t i = 0; i < n; i++)
+		if ((i && in->code_point[i] <= in->code_point[i - 1]) || in->font_of[i] >= in->n_fonts ||
+		    in->glyph_id[i] >= in->fonts[in->font_of[i]]->n_glyph_ids) {
+			ctx->err = "vgsdf_family_create: code points not strictly ascending, font_of past n_fonts, or a glyph id past its face";
+			return VGSDF_E_ARG;
+		}
+	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
+	if (!f) {
+		ctx->err = "vgsdf_family_create: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	f->device = ctx->device;
+	f->commands = in->fonts[0]->commands;
+	f->fonts.assign(in->fonts, in->fonts + in->n_fonts);
+	for (const vgsdf_font *ft : f->fonts) {
+		f->max_cap = std::max(f->max_cap, ft->max_cap);
+		f->max_len = std::max(f->max_len, ft->max_len);
+	}
+	f->code_point.assign(in->code_point, in->code_point + n);
+	f->font_of.assign(in->font_of, in->font_of + n);
+	f->glyph_id.assign(in->glyph_id, in->glyph_id + n);
+	f->advance.assign(in->advance, in->advance + n);
+	f->scale.assign(in->scale, in->scale + n);
+	f->shift_x.assign(in->shift_x, in->shift_x + n);
+	f->pbf_fix.resize(n);
+	f->cmd_pre.assign((size_t)n + 1, 0);
+	f->leaf_pre.assign((size_t)n + 1, 0);
+	auto varint_len = [](uint32_t v) { return v < 0x80u ? 1u : v < 0x4000u ? 2u : v < 0x200000u ? 3u : v < 0x10000000u ? 4u : 5u; };
+	for (uint32_t i = 0; i < n; i++) {
+		const vgsdf_font &ft = *f->fonts[f->font_of[i]];
+		const uint32_t id = f->glyph_id[i];
+		f->cmd_pre[i + 1] = f->cmd_pre[i] + ft.slots[id];
+		f->leaf_pre[i + 1] = f->leaf_pre[i] + (ft.commands ? 0u : ft.leaf_off[id + 1] - ft.leaf_off[id]);
+		f->pbf_fix[i] = (uint8_t)((1u + varint_len(f->code_point[i])) | ((1u + varint_len(f->advance[i])) << 4));
+		f->scales_plain = f->scales_plain && f->scale[i] > 0.0 && f->scale[i] < HUGE_VAL;
+	}
+	// the device's copy: one block in FamilyTableLayout, staged on the host and copied once
+	const vgsdf::FamilyTableLayout at(n);
+	std::vector<uint8_t> h(at.bytes + 16, 0);
+	std::memcpy(h.data() + at.scale, f->scale.data(), 8 * (size_t)n);
+	std::memcpy(h.data() + at.shift_x, f->shift_x.data(), 8 * (size_t)n);
+	for (uint32_t i = 0; i <= n; i++) {
+		((uint32_t *)(h.data() + at.cmd_pre))[i] = (uint32_t)f->cmd_pre[i];
+		((uint32_t *)(h.data() + at.leaf_pre))[i] = (uint32_t)f->leaf_pre[i];
+	}
+	std::memcpy(h.data() + at.advance, f->advance.data(), 4 * (size_t)n);
+	std::memcpy(h.data() + at.code_point, f->code_point.data(), 2 * (size_t)n);
+	std::memcpy(h.data() + at.font_of, f->font_of.data(), 2 * (size_t)n);
+	std::memcpy(h.data() + at.glyph_id, f->glyph_id.data(), 2 * (size_t)n);
+	std::memcpy(h.data() + at.pbf_fix, f->pbf_fix.data(), n);
+	(void)hipSetDevice(ctx->device);
+	if (hipError_t e = f->table.ensure(h.size()); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create", "hipMalloc", e);
+	hipError_t e = hipMemcpyAsync(f->table.p, h.data(), h.size(), hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(ctx->stream); // the table is on the device when the call returns: every context may name the family
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create", "upload", e);
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+int vgsdf_family_free(vgsdf_ctx *ctx, vgsdf_family *family)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!family)
+		return VGSDF_OK;
+	if (family->device != ctx->device) {
+		ctx->err = "vgsdf_family_free: the family lives on another device than the context";
+		return VGSDF_E_ARG;
+	}
+	(void)hipSetDevice(ctx->device);
+	delete family;
+	return VGSDF_OK;
+}
+
+uint64_t vgsdf_family_device_bytes(const vgsdf_family *family) { return family ? (uint64_t)family->table.cap : 0; }
+
+uint32_t vgsdf_family_count(const vgsdf_family *family, uint32_t first, uint32_t last)
+{
+	if (!family || first > last)
+		return 0;
+	const auto &cp = family->code_point;
+	const auto lo = std::lower_bound(cp.begin(), cp.end(), (uint16_t)std::min(first, 0xFFFFu));
+	if (first > 0xFFFFu)
+		return 0;
+	const auto hi = std::upper_bound(cp.begin(), cp.end(), (uint16_t)std::min(last, 0xFFFFu));
+	return (uint32_t)(hi - lo);
+}
 
 } // extern "C"

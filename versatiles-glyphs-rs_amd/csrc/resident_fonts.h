@@ -25,3 +25,24 @@ struct vgsdf_font {
 	vgsdf_font &operator=(const vgsdf_font &) = delete;
 	~vgsdf_font() { store.release(); } // (the owner has made the font's device current)
 };
+
+// vgsdf_family_create: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id, on the host (what a
+// ranges submission is laid out from in O(tasks)) and on the device (upload_layout.h, FamilyTableLayout: what its upload
+// kernel names the glyphs from).  Owns no font
+struct vgsdf_family {
+	int device = 0;
+	bool commands = false;    // the kind of its fonts
+	bool scales_plain = true; // every scale positive and finite
+	uint32_t max_cap = 0, max_len = 0; // over its fonts (vgsdf_font)
+	std::vector<const vgsdf_font *> fonts;
+	std::vector<uint16_t> code_point, font_of, glyph_id;
+	std::vector<uint32_t> advance;
+	std::vector<double> scale, shift_x;
+	std::vector<uint8_t> pbf_fix;
+	std::vector<uint64_t> cmd_pre, leaf_pre; // [n_entries + 1] prefix sums of command slots / leaves (leaves: glyf fonts only)
+	DevBuf table;
+	vgsdf_family() = default;
+	vgsdf_family(const vgsdf_family &) = delete;
+	vgsdf_family &operator=(const vgsdf_family &) = delete;
+	~vgsdf_family() { table.release(); }
+};

@@ -92,4 +92,54 @@ struct CommandBlockLayout : GlyphArraysLayout {
 	}
 };
 
+// The form that names code-point RANGES of resident families (vgsdf_outlines_ranges).  A family's table lives on the device
+// (resident_fonts.cpp, vgsdf_family_create), one allocation of arrays over its n entries:
+//   scale f64[n] | shift_x f64[n] | cmd_pre u32[n + 1] | leaf_pre u32[n + 1] | advance u32[n] | code_point u16[n] |
+//   font_of u16[n] | glyph_id u16[n] | pbf_fix u8[n]
+// cmd_pre / leaf_pre: prefix sums over the entries of their glyphs' command slots / leaves, mod 2^32 (a submission holds fewer
+// than 2^31 of either, so differences are exact).  Used by the host and, with the entry count of the block's family record,
+// by the upload kernels (constexpr: callable on the device).
+struct FamilyTableLayout {
+	size_t scale = 0, shift_x, cmd_pre, leaf_pre, advance, code_point, font_of, glyph_id, pbf_fix, bytes;
+	constexpr explicit FamilyTableLayout(size_t n)
+	    : shift_x(8 * n), cmd_pre(16 * n), leaf_pre(16 * n + 4 * (n + 1)), advance(16 * n + 8 * (n + 1)), code_point(20 * n + 8 * (n + 1)),
+	      font_of(22 * n + 8 * (n + 1)), glyph_id(24 * n + 8 * (n + 1)), pbf_fix(26 * n + 8 * (n + 1)), bytes(27 * n + 8 * (n + 1))
+	{
+	}
+};
+// The block of such a submission: 32 bytes per task that maps a glyph, per family and per font, nothing per glyph —
+//   RangeTask[n_live] | FamilyRef[n_families] | font references[n_fonts] (ResidentFontRef or CommandFontRef)
+// The upload kernel of the form WRITES the per-glyph arrays of ResidentBlockLayout / CommandBlockLayout into the device's copy
+// (where every later kernel reads them) and copies the font references to that layout's `fonts`.
+struct RangeTask {
+	uint32_t glyph_base;  // the task's first glyph in the submission (ascending over the block's tasks: they are bisected)
+	uint32_t n_glyphs;    // > 0: tasks that map nothing are not in the block
+	uint32_t entry_first; // its first entry in the family's table
+	uint32_t family;      // index into the block's family records
+	uint32_t cmd_rel;     // the task's first command slot in the batch - cmd_pre[entry_first] (mod 2^32)
+	uint32_t part_rel;    // glyf fonts: the task's first part - leaf_pre[entry_first] (mod 2^32)
+	uint32_t pbf_pre;     // bytes reserved in front of the task's first glyph entry
+	uint32_t reserved;
+};
+struct FamilyRef {
+	uint64_t table;     // device address of the family's table
+	uint32_t n_entries; // (what FamilyTableLayout is made from)
+	uint32_t font_base; // where the family's fonts begin in the block's font list
+	uint32_t n_fonts;
+	uint32_t reserved[3];
+};
+static_assert(sizeof(RangeTask) == 32 && sizeof(FamilyRef) == 32, "one record size throughout the block");
+struct RangesBlockLayout {
+	size_t tasks = 0, families, fonts, bytes;
+	RangesBlockLayout(size_t n_live, size_t n_families, size_t n_fonts)
+	    : families(32 * n_live), fonts(32 * (n_live + n_families)), bytes(32 * (n_live + n_families + n_fonts))
+	{
+	}
+};
+// what the upload kernel leaves per glyph for pbf_entries (device only): the entry's id (its code point) and advance, and
+// 1 + the index of the block's task whose first glyph this is (0: not a first glyph)
+struct EntryName {
+	uint32_t id, advance, task_first, reserved;
+};
+
 } // namespace vgsdf

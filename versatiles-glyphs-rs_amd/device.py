@@ -71,6 +71,16 @@ class _COutlinesResident(C.Structure):  # vgsdf_outlines_resident
                 ("glyph_id", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("pbf_pre", C.c_void_p),
                 ("pbf_fix", C.c_void_p)]
 
+class _CFamilyDesc(C.Structure):  # vgsdf_family_desc
+    _fields_ = [("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("n_entries", C.c_uint32), ("code_point", C.c_void_p),
+                ("font_of", C.c_void_p), ("glyph_id", C.c_void_p), ("advance", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p)]
+
+
+class _COutlinesRanges(C.Structure):  # vgsdf_outlines_ranges
+    _fields_ = [("n_tasks", C.c_uint32), ("n_families", C.c_uint32), ("families", C.c_void_p), ("family_of", C.c_void_p),
+                ("first", C.c_void_p), ("last", C.c_void_p), ("pbf_pre", C.c_void_p)]
+
+
 VGSDF_SYMBOLS = [
     "vgsdf_device_count", "vgsdf_create", "vgsdf_destroy", "vgsdf_last_error", "vgsdf_render_batch",
     "vgsdf_batch_upload", "vgsdf_batch_launch", "vgsdf_batch_download", "vgsdf_batch_free", "vgsdf_sync",
@@ -79,6 +89,8 @@ VGSDF_SYMBOLS = [
     "vgsdf_add_counters", "vgsdf_reset_counters", "vgsdf_reduce_counters", "vgsdf_reduce_counters_rccl", "vgsdf_reduce_path", "vgsdf_outlines_pbf_positions", "vgsdf_outlines_peek",
     "vgsdf_font_create", "vgsdf_font_free", "vgsdf_font_device_bytes", "vgsdf_outlines_submit_resident", "vgsdf_outlines_resident_upload_bytes",
     "vgsdf_font_create_commands",
+    "vgsdf_family_create", "vgsdf_family_free", "vgsdf_family_device_bytes", "vgsdf_family_count", "vgsdf_outlines_submit_ranges",
+    "vgsdf_outlines_task_extents",
 ]
 
 _lib = None
@@ -133,6 +145,14 @@ def load_library():
         L.vgsdf_outlines_submit_resident.argtypes = [vp, vp, vp, C.c_size_t]
         L.vgsdf_outlines_resident_upload_bytes.argtypes = [vp]
         L.vgsdf_outlines_resident_upload_bytes.restype = C.c_uint64
+        L.vgsdf_family_create.argtypes = [vp, C.POINTER(_CFamilyDesc), C.POINTER(vp)]
+        L.vgsdf_family_free.argtypes = [vp, vp]
+        L.vgsdf_family_device_bytes.argtypes = [vp]
+        L.vgsdf_family_device_bytes.restype = C.c_uint64
+        L.vgsdf_family_count.argtypes = [vp, C.c_uint32, C.c_uint32]
+        L.vgsdf_family_count.restype = C.c_uint32
+        L.vgsdf_outlines_submit_ranges.argtypes = [vp, vp, vp, C.c_size_t]
+        L.vgsdf_outlines_task_extents.argtypes = [vp, vp]
         L.vgsdf_add_counters.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
         L.vgsdf_add_counters.restype = None
         L.vgsdf_reset_counters.argtypes = [vp]
@@ -285,6 +305,34 @@ class ResidentFont:
             pass
 
 
+class ResidentFamily:
+    """vgsdf_family: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id, resident beside its fonts
+    (which it does not own: they must outlive it)."""
+
+    def __init__(self, ctx: "SdfContext", handle, fonts):
+        self.ctx, self._h, self.fonts = ctx, handle, list(fonts)
+
+    @property
+    def device_bytes(self) -> int:
+        return int(load_library().vgsdf_family_device_bytes(self._h)) if self._h else 0
+
+    def count(self, first: int, last: int) -> int:
+        """mapped code points in [first, last]"""
+        return int(load_library().vgsdf_family_count(self._h, first, last))
+
+    def free(self):
+        """the caller's to time: no submission that names the family may be in flight"""
+        if self._h and self.ctx._h:
+            load_library().vgsdf_family_free(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class SdfContext:
     """vgsdf_ctx: one per (thread, GPU)."""
 
@@ -362,9 +410,10 @@ class SdfContext:
                 L.vgsdf_host_free(host)
         return rects, out, int(ob.value), int(ns.value)
 
-    def _submit(self, entry: str, co, keep: dict, capacity: int, pbf_pre=None, pbf_fix=None):
+    def _submit(self, entry: str, co, keep: dict, capacity: int, pbf_pre=None, pbf_fix=None, fill=None, pinned=True, n=None):
         """what the outlines_submit* wrappers share: the PBF arrays attached to the C struct `co`, a page-locked output buffer
-        (freed when the submit fails), and the arrays, the buffer and the glyph count kept until outlines_wait"""
+        (freed when the submit fails), and the arrays, the buffer and the glyph count kept until outlines_wait.  fill: a byte
+        the buffer is filled with first; pinned=False: a pageable buffer (numpy's) instead"""
         L = load_library()
         if pbf_pre is not None:
             keep["pbf_pre"] = np.ascontiguousarray(pbf_pre, dtype=np.uint32)
@@ -372,14 +421,21 @@ class SdfContext:
         if pbf_fix is not None:
             keep["pbf_fix"] = np.ascontiguousarray(pbf_fix, dtype=np.uint8)
             co.pbf_fix = keep["pbf_fix"].ctypes.data
+        if not pinned:      # numpy owns the buffer: the fifth entry of _inflight keeps it, and tells outlines_wait not to free it
+            pageable = np.full(max(capacity, 1), 0 if fill is None else fill, dtype=np.uint8)
+            self._check(getattr(L, entry)(self._h, C.byref(co), pageable.ctypes.data, capacity))
+            self._inflight = (keep, pageable.ctypes.data, capacity, co.n_glyphs if n is None else n, pageable)
+            return
         host = L.vgsdf_host_alloc(max(capacity, 1))
         if not host:
             raise MemoryError("vgsdf_host_alloc")
+        if fill is not None:
+            C.memset(host, fill, max(capacity, 1))
         rc = getattr(L, entry)(self._h, C.byref(co), host, capacity)
         if rc != 0:
             L.vgsdf_host_free(host)
             self._check(rc)
-        self._inflight = (keep, host, capacity, co.n_glyphs)
+        self._inflight = (keep, host, capacity, co.n_glyphs if n is None else n)
 
     def outlines_submit(self, cmd_off, cmds, scale, shift_x, capacity: int):
         """first half of the one-submission form: everything is enqueued, nothing waited for (one per context)"""
@@ -452,7 +508,7 @@ class SdfContext:
         self._check(load_library().vgsdf_font_create_commands(self._h, C.byref(d), C.byref(h)))
         return ResidentFont(self, h)
 
-    def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None):
+    def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None):
         """outlines_submit for glyphs named by (font, glyph id) of resident fonts (vgsdf_outlines_resident)"""
         keep = {
             "font_of": np.ascontiguousarray(font_of, dtype=np.uint16), "glyph_id": np.ascontiguousarray(glyph_id, dtype=np.uint16),
@@ -463,7 +519,46 @@ class SdfContext:
         assert len(keep["font_of"]) == n and len(keep["glyph_id"]) == n
         co = _COutlinesResident(n, len(fonts), C.cast(keep["fonts"], C.c_void_p), keep["font_of"].ctypes.data, keep["glyph_id"].ctypes.data,
                                 keep["scale"].ctypes.data, keep["shift"].ctypes.data)
-        self._submit("vgsdf_outlines_submit_resident", co, keep, capacity, pbf_pre, pbf_fix)
+        self._submit("vgsdf_outlines_submit_resident", co, keep, capacity, pbf_pre, pbf_fix, fill=fill)
+
+    def family_create(self, fonts, code_point, font_of, glyph_id, advance, scale, shift_x) -> ResidentFamily:
+        """vgsdf_family_create: the entries of a font id over `fonts` (ResidentFont, one kind), code points strictly ascending"""
+        a = [np.ascontiguousarray(code_point, dtype=np.uint16), np.ascontiguousarray(font_of, dtype=np.uint16),
+             np.ascontiguousarray(glyph_id, dtype=np.uint16), np.ascontiguousarray(advance, dtype=np.uint32),
+             np.ascontiguousarray(scale, dtype=np.float64), np.ascontiguousarray(shift_x, dtype=np.float64)]
+        assert all(len(x) == len(a[0]) for x in a)
+        handles = (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts])
+        d = _CFamilyDesc(len(fonts), C.cast(handles, C.c_void_p), len(a[0]), *[x.ctypes.data for x in a])
+        h = C.c_void_p()
+        self._check(load_library().vgsdf_family_create(self._h, C.byref(d), C.byref(h)))
+        return ResidentFamily(self, h, fonts)
+
+    def outlines_submit_ranges(self, families, family_of, first, last, capacity: int, pbf_pre=None, fill=None, pinned=True):
+        """outlines_submit for code-point ranges of resident families (vgsdf_outlines_ranges): task t is the mapped code points of
+        [first[t], last[t]] of families[family_of[t]]; pbf_pre (per TASK): in-place PBF assembly, the device writes the entries"""
+        keep = {
+            "family_of": np.ascontiguousarray(family_of, dtype=np.uint16), "first": np.ascontiguousarray(first, dtype=np.uint16),
+            "last": np.ascontiguousarray(last, dtype=np.uint16),
+            "families": (C.c_void_p * max(len(families), 1))(*[f._h for f in families]), "family_objects": list(families),
+        }
+        n_tasks = len(keep["family_of"])
+        assert len(keep["first"]) == n_tasks and len(keep["last"]) == n_tasks
+        co = _COutlinesRanges(n_tasks, len(families), C.cast(keep["families"], C.c_void_p), keep["family_of"].ctypes.data,
+                              keep["first"].ctypes.data, keep["last"].ctypes.data)
+        if pbf_pre is not None:
+            keep["task_pre"] = np.ascontiguousarray(pbf_pre, dtype=np.uint32)
+            assert len(keep["task_pre"]) == n_tasks
+            co.pbf_pre = keep["task_pre"].ctypes.data
+        n = sum(families[k].count(int(a), int(b)) for k, a, b in zip(keep["family_of"], keep["first"], keep["last"])
+                if k < len(families) and a <= b)
+        self._n_tasks = n_tasks
+        self._submit("vgsdf_outlines_submit_ranges", co, keep, capacity, fill=fill, pinned=pinned, n=n)
+
+    def outlines_task_extents(self) -> np.ndarray:
+        """after outlines_peek / outlines_wait of a ranges submission with pbf_pre: begin[n_tasks + 1] in the arena"""
+        begin = np.zeros(self._n_tasks + 1, dtype=np.uint64)
+        self._check(load_library().vgsdf_outlines_task_extents(self._h, begin.ctypes.data))
+        return begin
 
     def resident_upload_bytes(self) -> int:
         """size of the block the last resident submission of this context uploaded"""
@@ -474,7 +569,7 @@ class SdfContext:
         ob, ip = C.c_uint64(0), C.c_int(0)
         if getattr(self, "_inflight", None) is None:  # (the library says so)
             self._check(load_library().vgsdf_outlines_peek(self._h, None, C.byref(ob), C.byref(ip)))
-        keep, host, capacity, n = self._inflight
+        keep, host, capacity, n = self._inflight[:4]
         rects = np.zeros(n, dtype=RECT_DTYPE)
         self._check(load_library().vgsdf_outlines_peek(self._h, rects.ctypes.data, C.byref(ob), C.byref(ip)))
         return rects, int(ob.value), bool(ip.value)
@@ -482,7 +577,8 @@ class SdfContext:
     def outlines_wait(self):
         """second half -> (rects, bitmaps | None, out_bytes, n_segments)"""
         L = load_library()
-        keep, host, capacity, n = self._inflight
+        keep, host, capacity, n = self._inflight[:4]
+        pageable = self._inflight[4:]           # (the buffer is numpy's: kept alive to the end of this call, not freed here)
         self._inflight = None
         try:
             rects = np.zeros(n, dtype=RECT_DTYPE)
@@ -492,7 +588,8 @@ class SdfContext:
             buf = (C.c_uint8 * max(capacity, 1)).from_address(host)
             out = np.frombuffer(buf, dtype=np.uint8, count=int(ob.value)).copy() if done.value else None
         finally:
-            L.vgsdf_host_free(host)
+            if not pageable:
+                L.vgsdf_host_free(host)
         return rects, out, int(ob.value), int(ns.value)
 
     def outlines_pbf_positions(self) -> np.ndarray:

@@ -34,6 +34,11 @@ class Timings(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class _CFamilyView(C.Structure):  # vg_family_view
+    _fields_ = [("n_entries", C.c_uint32), ("n_files", C.c_uint32), ("code_point", C.c_void_p), ("font_of", C.c_void_p),
+                ("glyph_id", C.c_void_p), ("advance", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p)]
+
+
 class _CResidentView(C.Structure):  # vg_resident_view
     _fields_ = [("n_glyphs", C.c_uint32), ("n_files", C.c_uint32), ("font_of", C.c_void_p), ("glyph_id", C.c_void_p),
                 ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("ids", C.c_void_p), ("advances", C.c_void_p)]
@@ -50,11 +55,11 @@ VGFONT_SYMBOLS = [
     "vg_manager_set_threads", "vg_manager_set_device_front_end", "vg_manager_add_font_with_name", "vg_manager_add_font_data", "vg_manager_add_path",
     "vg_name_to_id", "vg_manager_block_counts", "vg_manager_render_glyphs", "vg_manager_timings",
     "vg_manager_render_block", "vg_manager_render_blocks", "vg_render_glyph", "vg_manager_build_batch", "vg_glyph_batch_view",
-    "vg_glyph_batch_free", "vg_manager_record_outlines", "vg_outline_batch_view", "vg_outline_batch_free", "vg_pbf_encode",
+    "vg_glyph_batch_free", "vg_manager_record_outlines", "vg_outline_batch_view", "vg_outline_batch_free", "vg_pbf_encode", "vg_manager_family_desc",
     "vg_manager_record_glyf_parts", "vg_glyf_batch_view", "vg_glyf_batch_free",
     "vg_manager_resident_font_desc", "vg_manager_record_resident", "vg_resident_batch_view", "vg_resident_batch_free",
     "vg_manager_command_font_desc", "vg_manager_record_resident_commands", "vg_manager_set_resident_commands",
-    "vg_manager_command_stats",
+    "vg_manager_command_stats", "vg_manager_set_resident_families", "vg_manager_family_stats",
     "vg_manager_set_resident_fonts", "vg_renderer_set_resident_budget", "vg_renderer_preload_fonts", "vg_manager_resident_stats",
     "vg_manager_scan", "vg_manager_font_ids", "vg_manager_font_file_names", "vg_parse_font_name", "vg_manager_generate_name",
     "vg_encode_codeblocks", "vg_manager_index_json", "vg_manager_families_json", "vg_writer_new_tar_path",
@@ -97,6 +102,10 @@ def _L():
         L.vg_manager_set_resident_commands.argtypes = [vp, C.c_int]
         L.vg_manager_set_resident_commands.restype = None
         L.vg_manager_command_stats.argtypes = [vp, C.POINTER(ResidentStats)]
+        L.vg_manager_set_resident_families.argtypes = [vp, C.c_int]
+        L.vg_manager_set_resident_families.restype = None
+        L.vg_manager_family_stats.argtypes = [vp, C.POINTER(ResidentStats)]
+        L.vg_manager_family_desc.argtypes = [vp, C.c_char_p, vp]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -345,6 +354,17 @@ class FontManager:
         (font, glyph id) against command stores instead of being read by the host on every render; 2: every group is; same
         bytes in every mode"""
         _L().vg_manager_set_resident_commands(self._h, int(mode))
+
+    def set_resident_families(self, on: bool):
+        """groups that would go by (font, glyph id) go as code-point ranges of resident families instead (default off)"""
+        _L().vg_manager_set_resident_families(self._h, int(bool(on)))
+
+    def family_stats(self) -> dict:
+        """of the last render: groups submitted as ranges, families uploaded, their bytes, block bytes (vg_family_stats)"""
+        s = ResidentStats()
+        _L().vg_manager_family_stats(self._h, C.byref(s))
+        return {"groups": int(s.groups), "families_uploaded": int(s.fonts_uploaded), "family_bytes": int(s.font_bytes),
+                "block_bytes": int(s.block_bytes)}
 
     def command_stats(self) -> dict:
         """of the last render: groups submitted by name against command stores, stores uploaded during it, their bytes on the
@@ -600,6 +620,25 @@ class FontManager:
 
         return {"cmd_off": arr(d.cmd_off, d.n_glyph_ids + 1, np.uint32), "dat_off": arr(d.dat_off, d.n_glyph_ids + 1, np.uint32),
                 "kinds": arr(d.kinds, d.n_cmds, np.uint8), "coords": arr(d.coords, d.n_floats, np.float32)}
+
+    def family_desc(self, font_id: str) -> dict:
+        """the host half of a resident family (vg_manager_family_desc): {code_point, font_of, glyph_id, advance, scale, shift_x,
+        n_files}, copies of the manager's table"""
+        L = _L()
+        v = _CFamilyView()
+        if L.vg_manager_family_desc(self._h, font_id.encode(), C.byref(v)) != 0:
+            raise RuntimeError(_err())
+        n = v.n_entries
+
+        def arr(ptr, dt):
+            if n == 0 or not ptr:
+                return np.zeros(0, dtype=dt)
+            buf = (C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dt, count=n).copy()
+
+        return {"code_point": arr(v.code_point, np.uint16), "font_of": arr(v.font_of, np.uint16), "glyph_id": arr(v.glyph_id, np.uint16),
+                "advance": arr(v.advance, np.uint32), "scale": arr(v.scale, np.float64), "shift_x": arr(v.shift_x, np.float64),
+                "n_files": int(v.n_files)}
 
     def record_resident_commands(self, font_id: str) -> dict:
         """record_resident against command fonts: for any face the reader can read (CFF, CFF2, glyf)"""
