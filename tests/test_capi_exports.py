@@ -43,11 +43,14 @@ def test_product_does_not_reference_oracle():
 def test_product_library_holds_only_product_kernels(vg):
     """The shipped libvgsdf.so carries the default raster, the brute-force raster and the batch
     preparation kernels; the earlier generations and the timing-only ablation instances (wrong
-    pixels) exist only in `make dev` builds."""
+    pixels) exist only in `make dev` builds, the margin instances only in `make margins` builds."""
     blob = vg.lib_path().read_bytes()
     assert b"sdf_tiles_span" in blob and b"sdf_tiles_brute" in blob
     for retired in (b"sdf_tiles_filtered", b"sdf_tiles_pk", b"sdf_tiles_hier"):
         assert retired not in blob, retired
+    # the margin instances of the span kernel (weakened margins: wrong pixels on purpose) exist only in `make margins` builds
+    for margins_only in (b"sdf_margin_span", b"vgsdf_margin_"):
+        assert margins_only not in blob, margins_only
     import ctypes
     lib = ctypes.CDLL(str(vg.lib_path()))
     lib.vgsdf_kernel_known.argtypes = [ctypes.c_int]

@@ -53,48 +53,70 @@ def random_polys(rng, n_glyphs, n_rings, n_pts, size, jitter=0.35):
     return out
 
 
-def test_random_polygons_small(oracle, vg, ctx):
+# The input sets below are functions (glyphs_*) so that tests/raster_margin_sets.py can run the same inputs through the
+# instances of the margins build (old_sets); every test renders exactly what its function returns.
+def glyphs_random_small():
     rng = np.random.default_rng(1)
-    run_both(oracle, vg, ctx, random_polys(rng, 40, 3, 40, 30))
+    return random_polys(rng, 40, 3, 40, 30)
+
+
+def test_random_polygons_small(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_random_small())
+
+
+def glyphs_random_multichunk():
+    # N = 2600 and 5200 segments: 3 and 6 LDS chunks of the filtered kernel
+    rng = np.random.default_rng(2)
+    return random_polys(rng, 3, 2, 1300, 50) + random_polys(rng, 2, 4, 1300, 60)
 
 
 def test_random_polygons_multichunk(oracle, vg, ctx):
-    # N = 2600 and 5200 segments: 3 and 6 LDS chunks of the filtered kernel
-    rng = np.random.default_rng(2)
-    run_both(oracle, vg, ctx, random_polys(rng, 3, 2, 1300, 50) + random_polys(rng, 2, 4, 1300, 60))
+    run_both(oracle, vg, ctx, glyphs_random_multichunk())
 
 
-def test_overlapping_rings_winding(oracle, vg, ctx):
+def glyphs_overlapping_rings():
     sq = lambda a, b: [(a, a), (b, a), (b, b), (a, b)]  # noqa: E731
     ccw = ring(sq(2, 12))
     ccw2 = ring(sq(6, 16))
     cw = ring(sq(6, 16)[::-1])
-    glyphs = [
+    return [
         (np.concatenate([ccw, ccw2]), -1, -1, 20, 20),   # winding 2 in the overlap
         (np.concatenate([ccw, cw]), -1, -1, 20, 20),     # winding 0 in the overlap (XOR-like)
         (np.concatenate([ccw, ccw, ccw]), -1, -1, 16, 16),  # identical rings: ties everywhere
     ]
-    run_both(oracle, vg, ctx, glyphs)
 
 
-def test_samples_on_vertices_and_rows(oracle, vg, ctx):
+def test_overlapping_rings_winding(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_overlapping_rings())
+
+
+def glyphs_on_vertices_and_rows():
     # vertices exactly on pixel centres (x.5), horizontal edges exactly on sample rows,
     # zero-length segments, a vertex repeated
     pts = [(2.5, 2.5), (9.5, 2.5), (9.5, 2.5), (9.5, 7.5), (6.5, 7.5), (6.5, 4.5), (2.5, 4.5)]
     segs = ring(pts)
     segs = np.concatenate([segs, [[4.5, 3.5, 4.5, 3.5]]])  # isolated degenerate segment
-    run_both(oracle, vg, ctx, [(segs, 0, 0, 13, 11), (segs, -3, -2, 19, 15)])
-    run_both(oracle, vg, ctx, [(segs, 0, 0, 13, 11)], mode=oracle.PRECISE)
+    return [(segs, 0, 0, 13, 11), (segs, -3, -2, 19, 15)]
 
 
-def test_many_ties_queue_overflow(oracle, vg, ctx):
+def test_samples_on_vertices_and_rows(oracle, vg, ctx):
+    glyphs = glyphs_on_vertices_and_rows()
+    run_both(oracle, vg, ctx, glyphs)
+    run_both(oracle, vg, ctx, glyphs[:1], mode=oracle.PRECISE)
+
+
+def glyphs_many_ties():
     # 3000 copies of one small triangle: every segment copy ties -> >2048 survivors per tile
     tri = ring([(3, 3), (9, 4), (5, 9)])
     segs = np.tile(tri, (3000, 1))
-    run_both(oracle, vg, ctx, [(segs, 0, 0, 12, 12)])
+    return [(segs, 0, 0, 12, 12)]
 
 
-def test_distances_on_rounding_boundaries(oracle, vg, ctx):
+def test_many_ties_queue_overflow(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_many_ties())
+
+
+def glyphs_on_rounding_boundaries():
     """axis-aligned edges at multiples of 1/64 px: 32 d is a multiple of 1/2 for most pixels, i.e.
     exactly ON the byte rounding boundary for half of them (the bounded-group kernel may only skip
     the f64 evaluation when the whole error interval is strictly inside one bin)"""
@@ -104,10 +126,14 @@ def test_distances_on_rounding_boundaries(oracle, vg, ctx):
         box = ring([(2 + o, 2 + o), (17 + o, 2 + o), (17 + o, 12 + o), (2 + o, 12 + o)])
         hole = ring([(5 + o, 5.5), (5 + o, 9.5), (14.5, 9.5 + o), (14.5, 5.5)])
         glyphs.append((np.concatenate([box, hole]), -1, -1, 22, 17))
-    run_both(oracle, vg, ctx, glyphs)
+    return glyphs
 
 
-def test_finely_flattened_outlines(oracle, vg, ctx):
+def test_distances_on_rounding_boundaries(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_on_rounding_boundaries())
+
+
+def glyphs_finely_flattened():
     """what real fonts look like after flattening at 0.1 font units: hundreds of sub-pixel segments
     per ring, several 256-segment chunks, groups straddling ring boundaries and sharp corners"""
     rng = np.random.default_rng(11)
@@ -132,10 +158,14 @@ def test_finely_flattened_outlines(oracle, vg, ctx):
             lo = np.floor(segs[:, [0, 1]].min(0)).astype(int) - 3
             hi = np.ceil(segs[:, [0, 1]].max(0)).astype(int) + 3
             glyphs.append((segs, int(lo[0]), int(lo[1]), int(hi[0] - lo[0]), int(hi[1] - lo[1])))
-    run_both(oracle, vg, ctx, glyphs)
+    return glyphs
 
 
-def test_tall_glyphs_with_localised_chunks(oracle, vg, ctx):
+def test_finely_flattened_outlines(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_finely_flattened())
+
+
+def glyphs_tall_localised_chunks():
     """tall bitmaps made of small finely flattened rings stacked vertically (and horizontally): each
     chunk of 256 segments is compact, so the default kernel skips most chunks per span by their boxes;
     rings straddling chunk and row-band boundaries, winding through skipped chunks' neighbours"""
@@ -155,25 +185,31 @@ def test_tall_glyphs_with_localised_chunks(oracle, vg, ctx):
         lo = np.floor(segs[:, [0, 1]].min(0)).astype(int) - 3
         hi = np.ceil(segs[:, [0, 1]].max(0)).astype(int) + 3
         glyphs.append((segs, int(lo[0]), int(lo[1]), int(hi[0] - lo[0]), int(hi[1] - lo[1])))
-    run_both(oracle, vg, ctx, glyphs)
+    return glyphs
 
 
-def test_wide_and_thin_rects(oracle, vg, ctx):
-    rng = np.random.default_rng(3)
+def test_tall_glyphs_with_localised_chunks(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_tall_localised_chunks())
+
+
+def glyphs_wide_and_thin():
     wide = ring(np.stack([np.linspace(5, 1500, 60), 6 + 3 * np.sin(np.linspace(0, 20, 60))], 1).tolist()
                 + [(1500, 14), (5, 14)])
     thin = ring(np.stack([3 + 0.8 * np.sin(np.linspace(0, 9, 50)), np.linspace(4, 400, 50)], 1).tolist()
                 + [(5.5, 400), (5.5, 4)])
-    glyphs = [
+    return [
         (wide, 0, 0, 1510, 20),    # w > 1023: histogram does not fit -> brute-force route
         (wide, 0, 0, 900, 20),     # clipped rect, filtered route, 2 rows per tile
         (thin, 0, 0, 7, 410),      # 7 px wide: 38 rows per tile
         (thin, -40, -40, 60, 30),  # rect mostly away from the outline
     ]
-    run_both(oracle, vg, ctx, glyphs)
 
 
-def test_big_and_far_coordinates(oracle, vg, ctx):
+def test_wide_and_thin_rects(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_wide_and_thin())
+
+
+def glyphs_big_and_far():
     rng = np.random.default_rng(4)
     base = random_polys(rng, 2, 2, 60, 24)
     glyphs = []
@@ -184,7 +220,11 @@ def test_big_and_far_coordinates(oracle, vg, ctx):
             glyphs.append((s, x0 + int(np.floor(off)), y0, w, h))
         # segments far outside the rect (relative coordinates ~1e7: no usable f32 bound)
         glyphs.append((np.concatenate([segs, segs + 1.0e7]), x0, y0, w, h))
-    run_both(oracle, vg, ctx, glyphs)
+    return glyphs
+
+
+def test_big_and_far_coordinates(oracle, vg, ctx):
+    run_both(oracle, vg, ctx, glyphs_big_and_far())
 
 
 def test_synthetic_first_outlines(oracle, vg, ctx):
@@ -197,10 +237,14 @@ def test_synthetic_first_outlines(oracle, vg, ctx):
     ctx.set_variant(0)
 
 
+def glyphs_tiny():
+    tri = ring([(1, 1), (3, 1), (2, 3)])
+    return [(tri, 0, 0, 1, 1), (tri, 0, 0, 4, 4), (tri[:0], 0, 0, 3, 3)]
+
+
 def test_empty_and_tiny_batches(oracle, vg, ctx):
     assert ctx.render_batch(vg.make_batch([])).size == 0
-    tri = ring([(1, 1), (3, 1), (2, 3)])
-    run_both(oracle, vg, ctx, [(tri, 0, 0, 1, 1), (tri, 0, 0, 4, 4), (tri[:0], 0, 0, 3, 3)])
+    run_both(oracle, vg, ctx, glyphs_tiny())
 
 
 def test_argument_validation(vg, ctx):

@@ -22,61 +22,11 @@
 #include <stdint.h>
 #include <cstdio>
 
-#include "outline_kernels.h" // PlanHeader (guard of the chunk-box pass behind the device front-end)
-#include "sdf_kernels.h"
+#include "sdf_span_support.h" // TPB, FCHUNK, quantise, exact_dist_sq, first_ge, filter_err, sc_filter: shared with the margin instances
 
 namespace vgsdf {
 
-constexpr int TPB = VGSDF_TILE_PIXELS; // 256 threads, one pixel each
-constexpr int SEG_CHUNK = 512;         // segments per LDS stage: 7 * 512 * 8 B = 28 KiB
-
-// Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Remap so that
-// each XCD walks a contiguous range of tiles: tiles of one glyph (which re-read the same
-// segment list) then hit the same L2.  Pure performance hint; any placement is correct.
-__device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t n_and_flag)
-{
-	constexpr uint32_t X = 8;
-	if (n_and_flag & 0x80000000u) // host asked for dispatch order == list order
-		return b;
-	const uint32_t n = n_and_flag;
-	uint32_t per = n / X, rem = n % X;
-	uint32_t xcd = b % X, idx = b / X;
-	// XCDs [0, rem) own per+1 tiles, the rest own per tiles
-	uint32_t start = xcd * per + (xcd < rem ? xcd : rem);
-	return start + idx;
-}
-
-// Rust `n.round() as u8` on a value already clamped to [0,255]
-__device__ __forceinline__ uint8_t quantise(double best_sq, bool inside)
-{
-	double d = sqrt(best_sq);            // rtree_segments.rs:67 (correctly rounded)
-	if (inside)
-		d = -d;                          // renderer_precise.rs:71-73
-	d = d * (256.0 / 8.0) + 64.0;        // :75  (two roundings, no FMA)
-	double n = 255.0 - d;                // :76
-	n = n < 0.0 ? 0.0 : n;
-	n = n > 255.0 ? 255.0 : n;
-	return (uint8_t)(int)round(n);       // :79  half away from zero
-}
-
-// Exact squared distance from p to segment (v,w): Segment::squared_distance_to_point,
-// segment.rs:54-72,96-99 with Point::squared_distance_to, point.rs:38-42.  dx,dy,l2 are the
-// reference's (w.x - v.x), (w.y - v.y) and v.squared_distance_to(w), bit for bit.
-__device__ __forceinline__ double exact_dist_sq(double px, double py, double vx, double vy, double wx,
-                                                double wy, double dx, double dy, double l2)
-{
-	const double pvx = px - vx, pvy = py - vy;
-	const double t = (pvx * dx + pvy * dy) / l2; // NaN when l2 == 0 (0/0): masked by at_v below
-	double qx = vx + t * dx, qy = vy + t * dy;
-	const bool at_v = (l2 == 0.0) | (t < 0.0); // segment.rs:59-61, :65-66
-	const bool at_w = t > 1.0;                 // :67-68
-	qx = at_w ? wx : qx;
-	qy = at_w ? wy : qy;
-	qx = at_v ? vx : qx;
-	qy = at_v ? vy : qy;
-	const double ex = qx - px, ey = qy - py; // point.rs:39-40 (other - self)
-	return ex * ex + ey * ey;
-}
+constexpr int SEG_CHUNK = 512; // segments per LDS stage: 7 * 512 * 8 B = 28 KiB
 
 // ---------------------------------------------------------------------------------------
 // Variant 1: brute force.  Every pixel evaluates every segment.
@@ -149,43 +99,6 @@ __global__ __launch_bounds__(TPB) void sdf_tiles_brute(const GlyphDesc *__restri
 		out[g.out_off + o] = quantise(best, wn != 0);
 }
 
-// ---------------------------------------------------------------------------------------
-// Shared pieces of the filtered kernels (the default kernel at the end of this file, and the earlier
-// generations kept in tools/experiments/sdf_retired.inc for development builds).
-// ---------------------------------------------------------------------------------------
-constexpr int FCHUNK = 256;      // segments per LDS stage: 20 B filter record + 32 B exact end points each
-constexpr int DELTA_CAP = 2048;  // winding histogram cells per span: rows * (w + 1)
-
-// smallest integer n in [A, B] with (double)n + c >= v   (B if none): exact f64 compares
-__device__ __forceinline__ int first_ge(double v, double c, int A, int B)
-{
-	double a = ceil(v - c);
-	a = a < (double)A ? (double)A : a;
-	a = a > (double)B ? (double)B : a; // NaN ends up inside [A, B] too; the compares below are then false
-	int n = (int)a;
-	if (n > A && (double)(n - 1) + c >= v)
-		n--;
-	else if (n < B && (double)n + c < v)
-		n++;
-	return n;
-}
-
-// h(F): bound on |Ft - D| for a filter value F, coordinates bounded by M:
-// 64 u M sqrt(F) + 32 u F + 2^-34 M^2 with u = 2^-24, evaluated with upward slack.
-__device__ __forceinline__ float filter_err(float F, float M)
-{
-	return 1.001f * (3.814697265625e-06f * M * __builtin_sqrtf(F) + 1.9073486328125e-06f * F +
-	                 5.820766091346741e-11f * M * M);
-}
-
-__device__ __forceinline__ float sc_filter(float rpx, float rpy, float vx, float vy, float dx, float dy, float inv)
-{
-	const float pvx = rpx - vx, pvy = rpy - vy;
-	const float t = __builtin_amdgcn_fmed3f(__builtin_fmaf(pvy, dy, pvx * dx) * inv, 0.0f, 1.0f);
-	const float ex = __builtin_fmaf(-t, dx, pvx), ey = __builtin_fmaf(-t, dy, pvy);
-	return __builtin_fmaf(ey, ey, ex * ex);
-}
-
 #ifdef VGSDF_DEV_VARIANTS
 } // namespace vgsdf
 #include "sdf_retired.inc" // tools/experiments/: earlier kernel generations (A/B measurements, `make dev` only: -I../tools/experiments)
@@ -254,8 +167,6 @@ __global__ __launch_bounds__(256) void sdf_chunk_boxes(const GlyphDesc *__restri
 	}
 }
 
-constexpr uint32_t SPAN_TILES = 4; // tiles a workgroup of the default kernel sweeps per staged chunk
-
 #include "sdf_span_kernel.inc" // the default kernel: bounded groups over spans (sdf_tiles_span)
 
 #ifdef VGSDF_DEV_VARIANTS
@@ -318,8 +229,20 @@ extern "C" int vgsdf_launch_span_planned(const vgsdf::GlyphDesc *glyphs, const u
 // kernel ids: 50 = the bounded-group span kernel (public variant 0), 1 = brute force, also the fallback
 // for the tiles the host routes there: glyphs too wide for the winding histogram, or with >= 2^24
 // segments.  Everything else exists only in development builds (-DVGSDF_DEV_VARIANTS).
+#ifdef VGSDF_MARGIN_VARIANTS
+// `make margins` only: the margin instances of the span kernel (sdf_margin_kernels.hip), ids 60..83
+extern "C" int vgsdf_margin_known(int kernel);
+extern "C" int vgsdf_margin_launch(int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::GlyphDesc *glyphs, const uint2 *tiles,
+                                   const double *sx, const double *sy, const double *ex, const double *ey, uint32_t seg_stride,
+                                   uint8_t *out, const void *boxes, hipStream_t stream);
+#endif
+
 extern "C" int vgsdf_kernel_known(int kernel)
 {
+#ifdef VGSDF_MARGIN_VARIANTS
+	if (vgsdf_margin_known(kernel))
+		return 1;
+#endif
 #ifdef VGSDF_DEV_VARIANTS
 	switch (kernel) {
 	case 10: case 12: case 22: case 23: case 30: case 45: case 58:
@@ -345,6 +268,10 @@ extern "C" int vgsdf_launch_tiles(int variant, int list_order, const vgsdf::Glyp
 	else if (variant == 50) // bounded groups over spans of up to 4 tiles (tile list: first pixel | T)
 		hipLaunchKernelGGL(vgsdf::sdf_tiles_span, grid, dim3(vgsdf::TPB), 0, stream, glyphs, tiles, n_tiles, sx, sy, ex, ey,
 		                   seg_stride, out, (const float4 *)boxes, (const vgsdf::PlanHeader *)nullptr);
+#ifdef VGSDF_MARGIN_VARIANTS
+	else if (vgsdf_margin_known(variant))
+		return vgsdf_margin_launch(variant, n_tiles_in, n_tiles, glyphs, tiles, sx, sy, ex, ey, seg_stride, out, boxes, stream);
+#endif
 #ifdef VGSDF_DEV_VARIANTS
 	// development builds only (`make dev`): the stamped instance of the span kernel and the earlier generations
 	else if (seg_stride != 1 && variant != 58) // the earlier generations read SoA arrays only

@@ -20,8 +20,83 @@
 #endif
 #ifndef VG_SPAN_KERNEL
 #define VG_SPAN_KERNEL sdf_tiles_span
+#endif
+#ifndef VG_STAMP
 #define VG_STAMP(region)
+#endif
+#ifndef VG_COUNT
 #define VG_COUNT(stmt)
+#endif
+// ---- The numerical margins the exactness argument rests on (DESIGN.md §4.1), by name.  The defaults ARE the product:
+// the product instance compiles to the same instructions as with the literals in place (profiles/raster_margins_isa_ab.txt).
+// Only the margin instances of `make margins` (sdf_margin_kernels.hip) override one, each an arithmetic change only (a
+// constant, or the outcome of a float comparison), to measure whether the suite notices a margin that is wrong.
+// (h(F)'s own constants: VG_HERR_* / VG_E64_C in sdf_span_support.h.) ----
+#ifndef VG_M_BOX_PADK
+#define VG_M_BOX_PADK(mag) (0.02f + 2.0e-6f * (mag)) // chunk-box skip: f32 roundings of box and pixel centres
+#endif
+#ifndef VG_M_BOX_SAT
+#define VG_M_BOX_SAT 6.2f // chunk-box skip: SAT
+#endif
+#ifndef VG_M_BOX_R
+#define VG_M_BOX_R(r) (r) // chunk-box skip: the reach R = SAT + padk
+#endif
+#ifndef VG_M_BOX_BAND
+#define VG_M_BOX_BAND(dy) ((dy) > 0.0f) // chunk-box skip: the box lies strictly outside the span's band of sample rows
+#endif
+#ifndef VG_M_INFL
+#define VG_M_INFL (1.0f + 1.0f / 512.0f) // phase 1: inflation of U and r_g
+#endif
+#ifndef VG_M_GRP_SLACK
+#define VG_M_GRP_SLACK 1.004f // phase 1: (U + r_g) against the bf16-packed D_g^2
+#endif
+#ifndef VG_M_PAD
+#define VG_M_PAD(Mc) (0.01f + 1.0e-5f * (Mc)) // phase 1: absolute pad of U and r_g
+#endif
+#ifndef VG_M_RG
+#define VG_M_RG(r) (r) // phase 1: the group radius in the candidate rule D_g <= U + r_g
+#endif
+#ifndef VG_M_SAT
+#define VG_M_SAT 6.2f // phase 1: beyond it the byte is saturated (5.97 px outside / 2.02 px inside)
+#endif
+#ifndef VG_M_SANE
+#define VG_M_SANE(Mc) ((Mc) < 1.0e6f) // the f32 filter is used at all
+#endif
+#ifndef VG_M_BOUNDED
+#define VG_M_BOUNDED(Mc) ((Mc) < 4096.0f) // the group bounds are used
+#endif
+#ifndef VG_M_MABS0
+#define VG_M_MABS0(m) (m) // largest absolute coordinate of the bitmap (e64)
+#endif
+#ifndef VG_M_E64
+#define VG_M_E64(e) (e) // the reference's own f64 error against the real distance
+#endif
+#ifndef VG_M_E
+#define VG_M_E(e) (e) // h(F) + e64 as used in decide, in the carried bound and in Tk
+#endif
+#ifndef VG_M_CARRY
+#define VG_M_CARRY (1.0f + 1.0f / 1048576.0f) // carried bound ub2 = (f1 + e) (1 + 2^-20)
+#endif
+#ifndef VG_M_DL
+#define VG_M_DL(dl) (dl) // decide: distance of s from the next integer that the interval needs
+#endif
+#ifndef VG_M_DL_C
+#define VG_M_DL_C 17.0f // decide: dl = 17 e / sqrt(f1) + 3e-4
+#endif
+#ifndef VG_M_DL_ABS
+#define VG_M_DL_ABS 3.0e-4f
+#endif
+#ifndef VG_M_E8
+#define VG_M_E8(e, f1) (8.0f * (e) <= (f1)) // decide: the sqrt bound behind dl holds
+#endif
+#ifndef VG_M_FAR
+#define VG_M_FAR 35.9f // decide: both bytes saturated beyond it
+#endif
+#ifndef VG_M_TK_PUSH
+#define VG_M_TK_PUSH(tk) ((tk) * 1.001f + 1e-30f) // fallback threshold: pushed up behind the iteration
+#endif
+#ifndef VG_M_TK
+#define VG_M_TK(tk, f1) (tk) // fallback threshold as used by the exact evaluation
 #endif
 
 __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__restrict__ glyphs,
@@ -39,7 +114,10 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 		return;
 #ifdef VG_SPAN_STAMPED
 	unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
+#endif
+#if defined(VG_SPAN_STAMPED) || defined(VG_SPAN_COUNTED)
 	unsigned long long cn_pairs = 0, cn_rounds = 0, cn_tc = 0, cn_fb = 0, cn_fbl = 0;
+	unsigned long long cn_over = 0, cn_fb_pool = 0, cn_fb_lane = 0; // phase-2 pool overflows; waves by exact-evaluation branch
 #endif
 	VG_STAMP(-1);
 	constexpr uint32_t GRP = 8, NGRP = FCHUNK / GRP; // 32 groups per chunk: one mask bit each
@@ -92,8 +170,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	uint32_t par = 0;
 	if (tid == 0)
 		s_mbits[0] = __float_as_uint(mpix);
-	const float mabs0 = fmaxf(fmaxf(fabsf((float)g.x0), fabsf((float)g.y0)),
-	                          fmaxf(fabsf((float)g.x0 + (float)g.w), fabsf((float)g.y0 + (float)g.h)));
+	const float mabs0 = VG_M_MABS0(fmaxf(fmaxf(fabsf((float)g.x0), fabsf((float)g.y0)),
+	                                     fmaxf(fabsf((float)g.x0 + (float)g.w), fabsf((float)g.y0 + (float)g.h))));
 
 	// the box test pays for glyphs with several chunks; with one or two there is nothing to gain
 	const bool use_boxes = boxes != nullptr && g.n_seg > 2 * FCHUNK;
@@ -111,20 +189,20 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// measured: the bookkeeping costs more than the extra skips on real fonts.) ----
 			const float4 bb = boxes[chunk_box_index(g.seg_off, t.x, c0 / FCHUNK)];
 			const float mag = fmaxf(fmaxf(fabsf(bb.x), fabsf(bb.y)), fmaxf(fmaxf(fabsf(bb.z), fabsf(bb.w)), wh));
-			const float padk = 0.02f + 2.0e-6f * mag;
+			const float padk = VG_M_BOX_PADK(mag);
 			const float ry0 = (float)y_lo + 0.5f, ry1 = (float)y_hi + 0.5f; // sample rows of the span, relative to y0
 			const float dy = fmaxf(bb.y - ry1, ry0 - bb.w) - padk;
 			float dx = fmaxf(bb.x - ((float)g.w - 0.5f), 0.5f - bb.z) - padk;
 			dx = dx > 0.0f ? dx : 0.0f;
-			const float R = 6.2f + padk; // SAT
-			if (dy > 0.0f && __builtin_fmaf(dy, dy, dx * dx) > R * R)
+			const float R = VG_M_BOX_R(VG_M_BOX_SAT + padk); // SAT
+			if (VG_M_BOX_BAND(dy) && __builtin_fmaf(dy, dy, dx * dx) > R * R)
 				continue; // NaN anywhere -> comparison false -> the chunk is processed
 		}
 		// ---- stage (thread i <-> record i): exact endpoints, f32 record, coordinate bound, group bounds,
 		// row crossings.  Everything a thread needs from other threads here comes from lanes of its own wave
 		// (a group of 8 records, the crossings of the wave's 64 segments), so there is one workgroup barrier
 		// behind the stage and none inside it. ----
-		constexpr float INFL = 1.0f + 1.0f / 512.0f;
+		constexpr float INFL = VG_M_INFL;
 		{
 			// Workgroup-uniform f64 values of the stage (there is no scalar f64 unit: each would occupy a VGPR pair for the
 			// whole kernel, and the kernel sits at the 128-VGPR limit of 4 waves per SIMD): formed here, behind a barrier
@@ -203,7 +281,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					const bool empty = gb >= cnt;
 					s_g[0][tid / GRP] = empty ? 1.0e18f : ax;
 					s_g[1][tid / GRP] = empty ? 1.0e18f : ay;
-					s_g[2][tid / GRP] = empty ? 0.0f : __builtin_sqrtf(r2) * (INFL * INFL * 1.004f); // 1.004: see phase 1
+					s_g[2][tid / GRP] = empty ? 0.0f : __builtin_sqrtf(r2) * (INFL * INFL * VG_M_GRP_SLACK); // 1.004: see phase 1
 				}
 			}
 
@@ -262,18 +340,18 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 		par ^= 1u;
 		if (tid == 0)
 			s_mbits[par] = __float_as_uint(mpix); // the next processed chunk's accumulator (nobody touches it before the next chunk-top barrier)
-		const bool sane = Mc < 1.0e6f;   // else: no usable f32 bound -> every segment is evaluated exactly
-		const bool bounded = Mc < 4096.0f; // group bounds have a useful margin
-		const float pad = 0.01f + 1.0e-5f * Mc;
+		const bool sane = VG_M_SANE(Mc);   // else: no usable f32 bound -> every segment is evaluated exactly
+		const bool bounded = VG_M_BOUNDED(Mc); // group bounds have a useful margin
+		const float pad = VG_M_PAD(Mc);
 		const uint32_t n_groups = (cnt + GRP - 1) / GRP;
 
 		const float4 *q_vx = reinterpret_cast<const float4 *>(s_vx), *q_vy = reinterpret_cast<const float4 *>(s_vy);
 		const float4 *q_dx = reinterpret_cast<const float4 *>(s_dx), *q_dy = reinterpret_cast<const float4 *>(s_dy);
 		const float4 *q_inv = reinterpret_cast<const float4 *>(s_inv);
 		const float M = Mc;
-		const float e64 = 5.6843418860808015e-14f * M * (M + mabs0 + M); // 2^-44 M (M + Mabs)
+		const float e64 = VG_M_E64(VG_E64_C * M * (M + mabs0 + M)); // 2^-44 M (M + Mabs)
 		// h(F) + e64 as one fused expression in the decide step: h(F) = 1.001 (64 u M sqrt(F) + 32 u F + 2^-34 M^2)
-		const float herr_c1 = 1.001f * 3.814697265625e-06f * M, herr_c3 = 1.001f * 5.820766091346741e-11f * M * M + e64;
+		const float herr_c1 = VG_HERR_SLACK * VG_HERR_C1 * M, herr_c3 = VG_HERR_SLACK * VG_HERR_C3 * M * M + e64;
 
 		// ---- sweep: every tile of the span against the staged chunk ----
 #pragma unroll 1
@@ -327,8 +405,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				}
 				ub2 = __uint_as_float(dmin);
 				float U = (__builtin_sqrtf(ub2) * INFL + pad) * INFL;
-				U = U < 6.2f ? U : 6.2f; // SAT: beyond it the byte is saturated whatever the minimum is
-				const float Ui = (U + pad * INFL) * 1.004f; // s_gr is stored with the same factor; it lacks the pad of r_g
+				U = U < VG_M_SAT ? U : VG_M_SAT; // SAT: beyond it the byte is saturated whatever the minimum is
+				const float Ui = (U + pad * INFL) * VG_M_GRP_SLACK; // s_gr is stored with the same factor; it lacks the pad of r_g
 				// One bit per group, 3-4 VALU ops each: tt = (U + r_g) 1.004, diff = tt^2 - D_g^2 (sign bit set
 				// <=> not a candidate; -3.4e38 for the groups past n_groups), shifted in with v_alignbit.  The
 				// bits arrive inverted and in reverse order: fixed once with v_not / v_bfrev.
@@ -343,7 +421,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					for (int j = 0; j < 4; j++) {
 						const uint32_t pk = D2p[b * 2 + j / 2];
 						const float d2 = __uint_as_float((j & 1) ? pk : (pk << 16));
-						const float tt = Ui + rs[j];
+						const float tt = Ui + VG_M_RG(rs[j]);
 						const float diff = __builtin_fmaf(tt, tt, -d2);
 						rej = __builtin_amdgcn_alignbit(rej, __float_as_uint(diff), 31); // (rej << 1) | sign(diff)
 					}
@@ -415,6 +493,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					__builtin_amdgcn_wave_barrier();
 					k1 = q_min[wv][lane];
 				} else {
+					VG_COUNT(cn_over += 1);
 					uint32_t m = cand;
 					while (m) {
 						const uint32_t gq = (uint32_t)__builtin_ctz(m);
@@ -461,16 +540,16 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				// whatever the bin is.  NaN anywhere -> every comparison false -> not decided -> exact evaluation.
 				const float f1 = __uint_as_float(k1);
 				const float sq = __builtin_sqrtf(f1);
-				const float e = __builtin_fmaf(herr_c1, sq, __builtin_fmaf(1.9092559814453125e-06f, f1, herr_c3));
+				const float e = VG_M_E(__builtin_fmaf(herr_c1, sq, __builtin_fmaf(VG_HERR_C2S, f1, herr_c3)));
 				float U = f1 + e;
-				const float uf = U * (1.0f + 1.0f / 1048576.0f);
+				const float uf = U * VG_M_CARRY;
 				ub2 = uf < ub2 ? uf : ub2; // bounds the later chunks' candidates too
 				const float s = __builtin_fmaf(32.0f, sq, 0.5f);
-				const float dl = __builtin_fmaf(17.0f * e, __builtin_amdgcn_rcpf(sq), 3.0e-4f);
+				const float dl = VG_M_DL(__builtin_fmaf(VG_M_DL_C * e, __builtin_amdgcn_rcpf(sq), VG_M_DL_ABS));
 				const float fr = __builtin_amdgcn_fractf(s);
 				const float mn = fr < 1.0f - fr ? fr : 1.0f - fr;
-				const bool far = f1 - e > 35.9f;
-				const bool decided = far || (8.0f * e <= f1 && mn > dl);
+				const bool far = f1 - e > VG_M_FAR;
+				const bool decided = far || (VG_M_E8(e, f1) && mn > dl);
 				if (decided) {
 					const int q = far ? 200 : (int)s;
 					b_in = (uint32_t)min(191 + q, 255);
@@ -483,10 +562,11 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 						U = __builtin_inff();
 					Tk = U + e64;
 					for (int it = 0; it < 3; it++)
-						Tk = U + e64 + filter_err(Tk, M);
-					Tk = Tk * 1.001f + 1e-30f;
-					if (!(Tk - filter_err(Tk, M) - e64 > U))
+						Tk = U + e64 + VG_M_E(filter_err(Tk, M));
+					Tk = VG_M_TK_PUSH(Tk);
+					if (!(Tk - VG_M_E(filter_err(Tk, M)) - e64 > U))
 						Tk = __builtin_inff();
+					Tk = VG_M_TK(Tk, f1);
 					undecided = true;
 				}
 			}
@@ -500,7 +580,9 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// above Tk) and the f64 operations on each are what the single lane did; min is exact, so is the result. ----
 			{
 				unsigned long long amb = __ballot(undecided);
-				VG_COUNT(cn_fb += amb != 0; cn_fbl += (unsigned long long)__builtin_popcountll(amb));
+				VG_COUNT(cn_fb += amb != 0; cn_fbl += (unsigned long long)__builtin_popcountll(amb);
+				         cn_fb_pool += amb != 0 && VG_POOL_MAX != 0 && (uint32_t)__builtin_popcountll(amb) <= (uint32_t)VG_POOL_MAX;
+				         cn_fb_lane += amb != 0 && !(VG_POOL_MAX != 0 && (uint32_t)__builtin_popcountll(amb) <= (uint32_t)VG_POOL_MAX));
 				if (VG_POOL_MAX != 0 && (uint32_t)__builtin_popcountll(amb) <= (uint32_t)VG_POOL_MAX) {
 					while (amb) {
 						const int src = (int)__builtin_ctzll(amb);
@@ -612,16 +694,21 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 		}
 	}
 	VG_STAMP(11); // epilogue: winding prefix sums, stores
-#ifdef VG_SPAN_STAMPED
+#if defined(VG_SPAN_STAMPED) || defined(VG_SPAN_COUNTED)
 	if (lane == 0) {
+#ifdef VG_SPAN_STAMPED
 		for (int r = 0; r < 12; r++)
 			atomicAdd(&g_span_dbg[r], st_acc[r]);
+#endif
 		atomicAdd(&g_span_dbg[12], 1ull);
 		atomicAdd(&g_span_dbg[13], cn_pairs);
 		atomicAdd(&g_span_dbg[14], cn_rounds);
 		atomicAdd(&g_span_dbg[15], cn_tc);
 		atomicAdd(&g_span_dbg[16], cn_fb);
 		atomicAdd(&g_span_dbg[17], cn_fbl);
+		atomicAdd(&g_span_dbg[20], cn_over);
+		atomicAdd(&g_span_dbg[21], cn_fb_pool);
+		atomicAdd(&g_span_dbg[22], cn_fb_lane);
 	}
 #endif
 }
@@ -629,3 +716,28 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 #undef VG_SPAN_KERNEL
 #undef VG_STAMP
 #undef VG_COUNT
+// one #undef per VG_M_* macro defined at the top of this file (keep the two lists in step: a macro left defined would
+// carry one stamping's override into the next; the VG_HERR_* / VG_E64_C constants of sdf_span_support.h are per file, not
+// per stamping).  Not every name has an instance that overrides it: the names are the inventory of DESIGN.md §4.1.
+#undef VG_M_BOX_PADK
+#undef VG_M_BOX_SAT
+#undef VG_M_BOX_R
+#undef VG_M_BOX_BAND
+#undef VG_M_INFL
+#undef VG_M_GRP_SLACK
+#undef VG_M_PAD
+#undef VG_M_RG
+#undef VG_M_SAT
+#undef VG_M_SANE
+#undef VG_M_BOUNDED
+#undef VG_M_MABS0
+#undef VG_M_E64
+#undef VG_M_E
+#undef VG_M_CARRY
+#undef VG_M_DL
+#undef VG_M_DL_C
+#undef VG_M_DL_ABS
+#undef VG_M_E8
+#undef VG_M_FAR
+#undef VG_M_TK_PUSH
+#undef VG_M_TK

@@ -1,0 +1,125 @@
+// sdf_span_support.h — device helpers shared by the raster kernels of sdf_kernels.hip and by every stamping of
+// sdf_span_kernel.inc (the product instance there; the margin instances of sdf_margin_kernels.hip, `make margins`).
+// NOTE for profiles/traffic.json: bench.py keys the recorded PMC numbers of the raster kernel to the text of sdf_kernels.hip,
+// sdf_span_kernel.inc and sdf_kernels.h only.  This header holds code of that kernel too (filter_err, sc_filter, quantise,
+// exact_dist_sq) and is NOT part of that key: after an edit here that changes the kernel's instructions, collect the profile
+// again (tools/profile.sh) or remove the entries, or bench.py keeps reporting numbers of the old instructions.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "outline_kernels.h" // PlanHeader (guard of the chunk-box pass behind the device front-end)
+#include "sdf_kernels.h"
+
+namespace vgsdf {
+
+constexpr int TPB = VGSDF_TILE_PIXELS; // 256 threads, one pixel each
+
+// Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Remap so that
+// each XCD walks a contiguous range of tiles: tiles of one glyph (which re-read the same
+// segment list) then hit the same L2.  Pure performance hint; any placement is correct.
+__device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t n_and_flag)
+{
+	constexpr uint32_t X = 8;
+	if (n_and_flag & 0x80000000u) // host asked for dispatch order == list order
+		return b;
+	const uint32_t n = n_and_flag;
+	uint32_t per = n / X, rem = n % X;
+	uint32_t xcd = b % X, idx = b / X;
+	// XCDs [0, rem) own per+1 tiles, the rest own per tiles
+	uint32_t start = xcd * per + (xcd < rem ? xcd : rem);
+	return start + idx;
+}
+
+// Rust `n.round() as u8` on a value already clamped to [0,255]
+__device__ __forceinline__ uint8_t quantise(double best_sq, bool inside)
+{
+	double d = sqrt(best_sq);            // rtree_segments.rs:67 (correctly rounded)
+	if (inside)
+		d = -d;                          // renderer_precise.rs:71-73
+	d = d * (256.0 / 8.0) + 64.0;        // :75  (two roundings, no FMA)
+	double n = 255.0 - d;                // :76
+	n = n < 0.0 ? 0.0 : n;
+	n = n > 255.0 ? 255.0 : n;
+	return (uint8_t)(int)round(n);       // :79  half away from zero
+}
+
+// Exact squared distance from p to segment (v,w): Segment::squared_distance_to_point,
+// segment.rs:54-72,96-99 with Point::squared_distance_to, point.rs:38-42.  dx,dy,l2 are the
+// reference's (w.x - v.x), (w.y - v.y) and v.squared_distance_to(w), bit for bit.
+__device__ __forceinline__ double exact_dist_sq(double px, double py, double vx, double vy, double wx,
+                                                double wy, double dx, double dy, double l2)
+{
+	const double pvx = px - vx, pvy = py - vy;
+	const double t = (pvx * dx + pvy * dy) / l2; // NaN when l2 == 0 (0/0): masked by at_v below
+	double qx = vx + t * dx, qy = vy + t * dy;
+	const bool at_v = (l2 == 0.0) | (t < 0.0); // segment.rs:59-61, :65-66
+	const bool at_w = t > 1.0;                 // :67-68
+	qx = at_w ? wx : qx;
+	qy = at_w ? wy : qy;
+	qx = at_v ? vx : qx;
+	qy = at_v ? vy : qy;
+	const double ex = qx - px, ey = qy - py; // point.rs:39-40 (other - self)
+	return ex * ex + ey * ey;
+}
+
+// ---------------------------------------------------------------------------------------
+// Shared pieces of the filtered kernels (the default kernel at the end of sdf_kernels.hip, and the earlier
+// generations kept in tools/experiments/sdf_retired.inc for development builds).
+// ---------------------------------------------------------------------------------------
+constexpr int FCHUNK = 256;      // segments per LDS stage: 20 B filter record + 32 B exact end points each
+constexpr int DELTA_CAP = 2048;  // winding histogram cells per span: rows * (w + 1)
+
+// smallest integer n in [A, B] with (double)n + c >= v   (B if none): exact f64 compares
+__device__ __forceinline__ int first_ge(double v, double c, int A, int B)
+{
+	double a = ceil(v - c);
+	a = a < (double)A ? (double)A : a;
+	a = a > (double)B ? (double)B : a; // NaN ends up inside [A, B] too; the compares below are then false
+	int n = (int)a;
+	if (n > A && (double)(n - 1) + c >= v)
+		n--;
+	else if (n < B && (double)n + c < v)
+		n++;
+	return n;
+}
+
+// h(F): bound on |Ft - D| for a filter value F, coordinates bounded by M:
+// 64 u M sqrt(F) + 32 u F + 2^-34 M^2 with u = 2^-24, evaluated with upward slack.
+// The constants by name (defaults = the analysed values; only a `make margins` instance overrides one, see
+// sdf_margin_kernels.hip): the span kernel's decide step uses the same ones in its fused form of h(F) + e64.
+#ifndef VG_HERR_SLACK
+#define VG_HERR_SLACK 1.001f               // covers the roundings of evaluating h itself
+#endif
+#ifndef VG_HERR_C1
+#define VG_HERR_C1 3.814697265625e-06f     // 64 u
+#endif
+#ifndef VG_HERR_C2
+#define VG_HERR_C2 1.9073486328125e-06f    // 32 u
+#endif
+#ifndef VG_HERR_C2S
+#define VG_HERR_C2S 1.9092559814453125e-06f // VG_HERR_SLACK * VG_HERR_C2, one literal (the decide step's fused form)
+#endif
+#ifndef VG_HERR_C3
+#define VG_HERR_C3 5.820766091346741e-11f  // 2^-34
+#endif
+#ifndef VG_E64_C
+#define VG_E64_C 5.6843418860808015e-14f   // 2^-44: e64 = 2^-44 M (M + Mabs)
+#endif
+__device__ __forceinline__ float filter_err(float F, float M)
+{
+	return VG_HERR_SLACK * (VG_HERR_C1 * M * __builtin_sqrtf(F) + VG_HERR_C2 * F +
+	                        VG_HERR_C3 * M * M);
+}
+
+__device__ __forceinline__ float sc_filter(float rpx, float rpy, float vx, float vy, float dx, float dy, float inv)
+{
+	const float pvx = rpx - vx, pvy = rpy - vy;
+	const float t = __builtin_amdgcn_fmed3f(__builtin_fmaf(pvy, dy, pvx * dx) * inv, 0.0f, 1.0f);
+	const float ex = __builtin_fmaf(-t, dx, pvx), ey = __builtin_fmaf(-t, dy, pvy);
+	return __builtin_fmaf(ey, ey, ex * ex);
+}
+
+constexpr uint32_t SPAN_TILES = 4; // tiles a workgroup of the default kernel sweeps per staged chunk
+
+} // namespace vgsdf
