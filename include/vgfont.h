@@ -140,6 +140,21 @@ typedef struct {
 	uint64_t block_bytes;    /* bytes of those submissions' upload blocks */
 } vg_command_stats;
 int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out);
+/* Charstrings on the device, 0 (default) / 1.  With 1, wherever the renderer would build the command store of a `CFF ` version 1
+ * face — modes 1 and 2 above, vg_renderer_preload_fonts, families — the DEVICE interprets the face's charstrings
+ * (vgsdf_font_create_charstrings) instead of the host's reader; the host only resolves the INDEX offsets.  A face the device
+ * refuses (a seac glyph, a glyph past VGSDF_CHARSTRING_MAX_TOKENS, a store past the bounds) gets its store from the host reader as with 0.  Same
+ * registry, same budget, same store bytes and same output either way.  CFF2 and `glyf` faces are not affected.
+ * vg_manager_charstring_stats: of the last render; the decoded stores count among vg_command_stats.fonts_uploaded too. */
+void vg_manager_set_charstrings_on_device(vg_manager *m, int on);
+typedef struct {
+	uint64_t fonts_decoded; /* command stores the device decoded from charstrings during the render */
+	uint64_t font_bytes;    /* their bytes on the device */
+	uint64_t fallbacks;     /* faces the device refused: their stores came from the host reader */
+} vg_charstring_stats;
+int vg_manager_charstring_stats(const vg_manager *m, vg_charstring_stats *out);
+/* the same of the manager's last vg_renderer_preload_fonts (its stores are built outside any render) */
+int vg_manager_charstring_preload_stats(const vg_manager *m, vg_charstring_stats *out);
 /* Resident families, 0 (default) / 1: a group that the two switches above would submit by (font, glyph id) — against resident
  * fonts or command stores — is submitted as code-point ranges of its font ids' families instead (vgsdf_outlines_submit_ranges):
  * one task per (font, block), one per run of code points for a block the hybrid lane plan has split.  The renderer owns the
@@ -299,6 +314,11 @@ void vg_resident_batch_free(vg_resident_batch *b);
  * vg_manager_record_resident_commands: what a submission of every glyph of the font id names, as vg_manager_record_resident
  * (the same view, freed the same way); NULL for an unknown font id or a file without a command table. */
 int vg_manager_command_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_cmds_desc *desc);
+/* The description of file `file_index` for vgsdf_font_create_charstrings, without a device: the face's charstrings and
+ * subroutine bodies and their resolved INDEX offsets, built once per face; no charstring is interpreted.  The pointers stay valid
+ * as long as the manager holds the font.  -1: unknown font / file, a face with `glyf` outlines, a CFF2 face, or a `CFF ` table whose
+ * INDEX entries do not ascend inside their data. */
+int vg_manager_charstring_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings_desc *desc);
 vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, const char *font_id);
 
 /* The host half of a resident family (vgsdf_family_create / vgsdf_outlines_submit_ranges), no device needed: for every code

@@ -328,6 +328,58 @@ typedef struct {
 } vgsdf_font_cmds_desc;
 int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, vgsdf_font **out);
 /*
+ * The same command font made from a `CFF ` (version 1) face's own bytes: the DEVICE interprets the Type 2 charstrings of every
+ * glyph id (csrc/charstring_kernels.hip: the operator set and the rules of the host reader, csrc/host/cff.cpp, whose callbacks it
+ * equals bit for bit), so the host's share is to locate the INDEX tables and resolve their offsets.  The description:
+ *   bytes        every charstring and subroutine body of the face, back to back in any order, padded to a multiple of 4
+ *   cs_off       glyph id g's charstring is bytes[cs_off[g] .. cs_off[g + 1]) (an empty range: a glyph without outline)
+ *   gsubr_off    global subroutine k is bytes[gsubr_off[k] .. gsubr_off[k + 1])
+ *   lsubr_first  Font DICT d owns the local subroutines [lsubr_first[d], lsubr_first[d + 1]) of lsubr_off (lsubr_first[0] = 0;
+ *                name-keyed fonts have one Font DICT), subroutine j of it being bytes[lsubr_off[lsubr_first[d] + j] .. the next entry)
+ *   fd_of        FDSelect expanded to one byte per glyph id; NULL when n_fds == 1
+ * vgsdf_font_create_charstrings validates on the host, before anything runs, every range the device will read: 1 .. 65536 glyph
+ * ids, n_bytes a multiple of 4, 1 .. 256 Font DICTs, at most 65535 subroutines per set, every offset array ascending and ending inside
+ * `bytes`, every fd_of below n_fds — VGSDF_E_ARG otherwise, nothing left allocated, the context sound.  The device never reads
+ * outside a validated range.  It then runs a count pass (commands and coordinates per glyph id), reads the counts back, lays
+ * the store out, runs an emit pass that writes kinds | coords on the device, and the context pass of vgsdf_font_create_commands
+ * over them: the result is the font vgsdf_font_create_commands makes from the host reader's callbacks of the same face — the same
+ * records, cmd_off and context bytes, the same vgsdf_font_device_bytes — and is used and freed like it.  Synchronous like it.
+ * Refused with VGSDF_E_GLYF, nothing left allocated, the context sound (the caller then describes the face with its host reader
+ * and calls vgsdf_font_create_commands):
+ *   - a glyph whose `endchar` takes the seac form (it needs the charset and two further charstrings);
+ *   - a glyph that executes more than VGSDF_CHARSTRING_MAX_TOKENS tokens, operands and operators alike (ten nested calls of
+ *     fan-out k are k^10 tokens: the bound keeps a crafted font from holding the device; real glyphs stay below a few thousand);
+ *   - a store or coordinates past the bounds vgsdf_font_create_commands states.
+ * CFF2 is not offered to this entry point.
+ */
+#define VGSDF_CHARSTRING_MAX_TOKENS (1u << 20)
+typedef struct {
+	uint32_t n_glyph_ids;        /* 1 .. 65536 */
+	uint32_t n_bytes;            /* multiple of 4 */
+	const uint8_t *bytes;        /* [n_bytes] */
+	const uint32_t *cs_off;      /* [n_glyph_ids + 1] */
+	uint32_t n_gsubrs;           /* <= 65535 */
+	const uint32_t *gsubr_off;   /* [n_gsubrs + 1] */
+	uint32_t n_fds;              /* 1 .. 256 */
+	const uint32_t *lsubr_first; /* [n_fds + 1] */
+	const uint32_t *lsubr_off;   /* [lsubr_first[n_fds] + 1] */
+	const uint8_t *fd_of;        /* [n_glyph_ids] or NULL (n_fds == 1) */
+} vgsdf_font_charstrings_desc;
+int vgsdf_font_create_charstrings(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, vgsdf_font **out);
+/* The same under a limit on the store, for callers that keep a budget of device memory: behind the count pass, and before
+ * the store is allocated, *store_bytes (may be NULL) is what the store will hold (29 bytes per command + 4 per glyph id + 4); when
+ * that exceeds max_store_bytes the call returns VGSDF_OK with *out = NULL and nothing allocated.  Refusals as above. */
+int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, uint64_t max_store_bytes,
+                                         vgsdf_font **out, uint64_t *store_bytes);
+/* test / inspection (tools/charstrings_ab.py): milliseconds the count and the emit kernel of the context's last vgsdf_font_create_charstrings took (HIP events; 0 0 before
+ * the first, and for a pass that did not run) */
+void vgsdf_font_charstrings_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
+/* test / inspection: download a command font's store.  *n_glyph_ids / *n_cmds: its counts (either may be NULL); cmd_off
+ * [n_glyph_ids + 1], records [28 * n_cmds bytes: x1 y1 x2 y2 x y as f32, kind as u32], context [n_cmds]: each NULL or filled.
+ * A font from vgsdf_font_create: VGSDF_E_ARG. */
+int vgsdf_font_commands_read(vgsdf_ctx *ctx, const vgsdf_font *font, uint32_t *n_glyph_ids, uint32_t *n_cmds, uint32_t *cmd_off,
+                             void *records, uint8_t *context);
+/*
  * Resident families: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id lives on the device
  * beside its fonts, and a submission names CODE-POINT RANGES of families instead of glyphs.  The host's share per submission
  * is O(tasks): the block it uploads holds 32 bytes per task that maps a glyph, per family and per font, and no per-glyph byte.

@@ -59,6 +59,7 @@ struct vgsdf_ctx {
 	uint64_t counters[3] = {0, 0, 0};
 	uint64_t *d_counters = nullptr;
 	void *comm = nullptr; // ncclComm_t of the communicator this context last reduced in (owned by run_counters.cpp's cache)
+	float charstring_ms[2] = {0.0f, 0.0f}; // count / emit kernel of the last vgsdf_font_create_charstrings (resident_fonts.cpp)
 	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
 };
 

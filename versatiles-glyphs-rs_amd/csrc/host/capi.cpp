@@ -157,6 +157,19 @@ int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out)
 	*out = vg_command_stats{t.command_groups, t.command_fonts_uploaded, t.command_font_bytes, t.command_block_bytes};
 	return 0;
 }
+void vg_manager_set_charstrings_on_device(vg_manager *m, int on) { m->m.set_charstrings_on_device(on != 0); }
+int vg_manager_charstring_stats(const vg_manager *m, vg_charstring_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_charstring_stats{t.charstring_fonts_decoded, t.charstring_font_bytes, t.charstring_fallbacks};
+	return 0;
+}
+int vg_manager_charstring_preload_stats(const vg_manager *m, vg_charstring_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_preload_counts();
+	*out = vg_charstring_stats{t.charstring_fonts_decoded, t.charstring_font_bytes, t.charstring_fallbacks};
+	return 0;
+}
 void vg_manager_set_resident_families(vg_manager *m, int on) { m->m.set_resident_families(on != 0); }
 int vg_manager_family_stats(const vg_manager *m, vg_family_stats *out)
 {
@@ -689,6 +702,31 @@ int vg_manager_command_font_desc(const vg_manager *m, const char *font_id, int f
 		desc->dat_off = t->dat_off.data();
 		desc->kinds = t->kinds.data();
 		desc->coords = t->coords.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_charstring_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings_desc *desc)
+{
+	try {
+		std::string err;
+		const vg::CharstringTable *t = file_index < 0 || !m || !font_id ? nullptr : m->m.charstring_table(font_id, (size_t)file_index, &err);
+		if (!t || !desc) {
+			g_err = err.empty() ? "vg_manager_charstring_font_desc: bad argument" : err;
+			return -1;
+		}
+		desc->n_glyph_ids = (uint32_t)t->cs_off.size() - 1;
+		desc->n_bytes = (uint32_t)t->bytes.size();
+		desc->bytes = t->bytes.data();
+		desc->cs_off = t->cs_off.data();
+		desc->n_gsubrs = (uint32_t)t->gsubr_off.size() - 1;
+		desc->gsubr_off = t->gsubr_off.data();
+		desc->n_fds = t->n_fds;
+		desc->lsubr_first = t->lsubr_first.data();
+		desc->lsubr_off = t->lsubr_off.data();
+		desc->fd_of = t->fd_of.empty() ? nullptr : t->fd_of.data();
 		return 0;
 	} catch (const std::exception &e) {
 		g_err = e.what();

@@ -2,16 +2,19 @@
 #include "cff.hpp"
 
 #include <cmath>
+#include <cstring>
 #include <limits>
+
+#include "../charstring_limits.h"
 
 namespace vg {
 
 namespace {
 
-constexpr int kMaxOperands = 48;   // ttf-parser: MAX_ARGUMENTS_STACK_LEN of cff1
+constexpr int kMaxOperands = kCharstringMaxOperands; // (shared with the device's decoder: charstring_limits.h)
 constexpr int kMaxOperands2 = 513; // ... of cff2
 constexpr size_t kMaxRegions = 64; // ttf-parser: scalars of one ItemVariationData (cff2)
-constexpr int kMaxDepth = 10;    // ttf-parser: STACK_LIMIT (nested subroutine calls)
+constexpr int kMaxDepth = kCharstringMaxDepth;
 
 // DICT data (Technical Note #5176, section 4): operands followed by an operator
 struct DictReader {
@@ -375,10 +378,8 @@ std::optional<CffTable> CffTable::parse2(Bytes table, uint32_t n_coords)
 	return t;
 }
 
-const CffTable::Index *CffTable::local_subrs_for(uint16_t gid) const
+uint32_t CffTable::fd_index_for(uint16_t gid) const
 {
-	if (!cid_)
-		return &private_.local_subrs;
 	// FDSelect (Technical Note #5176, section 19): format 0 = one byte per glyph, format 3 = ranges
 	uint32_t fd = 0xFFFFFFFFu;
 	const Bytes &s = fd_select_;
@@ -398,7 +399,80 @@ const CffTable::Index *CffTable::local_subrs_for(uint16_t gid) const
 			}
 		}
 	}
-	return fd < fd_priv_.size() ? &fd_priv_[fd].local_subrs : nullptr;
+	return fd < fd_priv_.size() ? fd : 0xFFFFFFFFu;
+}
+
+const CffTable::Index *CffTable::local_subrs_for(uint16_t gid) const
+{
+	if (!cid_)
+		return &private_.local_subrs;
+	const uint32_t fd = fd_index_for(gid);
+	return fd != 0xFFFFFFFFu ? &fd_priv_[fd].local_subrs : nullptr;
+}
+
+bool CffTable::charstring_table(uint32_t n_glyph_ids, CharstringTable &out) const
+{
+	if (cff2_ || n_glyph_ids == 0 || n_glyph_ids > 0x10000u)
+		return false;
+	constexpr size_t kMaxBytes = 0xFFFFFFF0u;
+	// entries [0, count) of an INDEX behind `off` (which ends with the store's size so far), as Index::get checks them
+	auto append = [&](const Index &ix, std::vector<uint32_t> &off) {
+		auto at = [&](uint32_t k) {
+			uint32_t v = 0;
+			for (uint8_t b = 0; b < ix.off_size; b++)
+				v = (v << 8) | ix.data.u8(ix.offsets_at + (size_t)k * ix.off_size + b);
+			return v;
+		};
+		for (uint32_t i = 0; i < ix.count; i++) {
+			const uint32_t a = at(i), b = at(i + 1);
+			if (a < 1 || b < a || !ix.data.has(ix.data_at + a - 1, b - a) || out.bytes.size() + (b - a) > kMaxBytes)
+				return false;
+			out.bytes.insert(out.bytes.end(), ix.data.data() + ix.data_at + a - 1, ix.data.data() + ix.data_at + b - 1);
+			off.push_back((uint32_t)out.bytes.size());
+		}
+		return true;
+	};
+	out.cs_off.assign(1, 0);
+	if (!append(charstrings_, out.cs_off))
+		return false;
+	out.cs_off.resize((size_t)n_glyph_ids + 1, out.cs_off.back()); // (past the INDEX: empty)
+	out.gsubr_off.assign(1, (uint32_t)out.bytes.size());
+	if (!append(global_subrs_, out.gsubr_off))
+		return false;
+	out.lsubr_first.assign(1, 0);
+	out.lsubr_off.assign(1, (uint32_t)out.bytes.size());
+	out.fd_of.clear();
+	if (!cid_) {
+		if (!append(private_.local_subrs, out.lsubr_off))
+			return false;
+		out.lsubr_first.push_back((uint32_t)out.lsubr_off.size() - 1);
+	} else {
+		// a glyph without a Font DICT has no local subroutines: an empty set behind the font's own stands for "none"
+		const size_t n_own = fd_priv_.size() < 256 ? fd_priv_.size() : 256;
+		for (size_t k = 0; k < n_own; k++) {
+			if (!append(fd_priv_[k].local_subrs, out.lsubr_off))
+				return false;
+			out.lsubr_first.push_back((uint32_t)out.lsubr_off.size() - 1);
+		}
+		bool need_none = n_own == 0;
+		out.fd_of.assign(n_glyph_ids, 0);
+		for (uint32_t g = 0; g < n_glyph_ids; g++) {
+			const uint32_t fd = g < 0x10000u ? fd_index_for((uint16_t)g) : 0xFFFFFFFFu;
+			if (fd == 0xFFFFFFFFu)
+				need_none = true;
+			out.fd_of[g] = (uint8_t)(fd == 0xFFFFFFFFu ? n_own : fd);
+		}
+		if (need_none) {
+			if (n_own == 256)
+				return false;
+			out.lsubr_first.push_back(out.lsubr_first.back());
+		}
+	}
+	out.n_fds = (uint32_t)out.lsubr_first.size() - 1;
+	if (out.n_fds == 1)
+		out.fd_of.clear();
+	out.bytes.resize((out.bytes.size() + 3) & ~(size_t)3, 0);
+	return true;
 }
 
 // StandardEncoding code -> string id (Technical Note #5176, appendices A and B), then string id -> glyph through
@@ -531,7 +605,7 @@ struct CharStringRun {
 		stack[sp++] = v;
 		return true;
 	}
-	static uint32_t bias(uint32_t n) { return n < 1240 ? 107 : (n < 33900 ? 1131 : 32768); }
+	static uint32_t bias(uint32_t n) { return charstring_subr_bias(n); }
 
 	bool do_move(int skip, bool hx, bool hy)
 	{

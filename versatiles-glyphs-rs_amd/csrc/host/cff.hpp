@@ -43,6 +43,12 @@ public:
 	uint32_t number_of_glyphs() const { return charstrings_.count; }
 	// false = ttf-parser returns None (callbacks already delivered stay delivered)
 	bool outline(uint16_t glyph_id, OutlineBuilder &builder) const;
+	// The charstrings and subroutines of the face as the device's decoder takes them (CharstringTable of ttf_face.hpp), from the
+	// tables parse() has located: every body copied once, every INDEX offset resolved and checked.  false (nothing of `out` is
+	// to be used): CFF2, an INDEX entry that does not ascend or leaves its data, or 256 Font DICTs in use AND a glyph without one
+	// (Font DICTs past the 256 an FDSelect byte can name are left out; a glyph without Font DICT gets an empty set behind the font's own).
+	// n_glyph_ids = the face's numGlyphs: glyph ids past the CharStrings INDEX get an empty charstring (no outline, as outline())
+	bool charstring_table(uint32_t n_glyph_ids, CharstringTable &out) const;
 
 private:
 	struct Index {
@@ -57,6 +63,7 @@ private:
 		Index local_subrs;
 	};
 	static bool parse_private(Bytes table, size_t offset, size_t size, PrivateDict &out);
+	uint32_t fd_index_for(uint16_t glyph_id) const; // CID-keyed fonts: the glyph's Font DICT by FDSelect, 0xFFFFFFFF: none
 	const Index *local_subrs_for(uint16_t glyph_id) const;
 	// glyph of a code of Adobe's StandardEncoding (seac operands), through the charset; nullopt: none
 	std::optional<uint16_t> standard_code_to_glyph(uint32_t code) const;

@@ -628,6 +628,23 @@ const CommandTable *FontManager::command_table(const std::string &font_id, size_
 	return &t;
 }
 
+const CharstringTable *FontManager::charstring_table(const std::string &font_id, size_t file_index, std::string *err) const
+{
+	auto it = fonts().find(font_id);
+	if (it == fonts().end() || file_index >= it->second.files().size()) {
+		if (err)
+			*err = "unknown font id " + font_id + ", or a file index past its files";
+		return nullptr;
+	}
+	const CharstringTable &t = it->second.files()[file_index]->face().charstring_table();
+	if (!t.ok) {
+		if (err)
+			*err = "font " + font_id + ": the file has no `CFF ` version 1 charstrings the device's decoder could be given";
+		return nullptr;
+	}
+	return &t;
+}
+
 // ---- glyph-level sharding ---------------------------------------------------------------
 namespace {
 
@@ -1365,6 +1382,9 @@ void FontManager::render_tasks_multi(Writer &writer, const Renderer &renderer, i
 		timings_.families_uploaded += ct.families_uploaded;
 		timings_.family_bytes += ct.family_bytes;
 		timings_.family_block_bytes += ct.family_block_bytes;
+		timings_.charstring_fonts_decoded += ct.charstring_fonts_decoded;
+		timings_.charstring_font_bytes += ct.charstring_font_bytes;
+		timings_.charstring_fallbacks += ct.charstring_fallbacks;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1397,6 +1417,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->glyf_on_device_ = glyf_on_device_;
 		c->resident_fonts_ = resident_fonts_;
 		c->resident_commands_ = resident_commands_;
+		c->charstrings_on_device_ = charstrings_on_device_;
 		c->resident_families_ = resident_families_;
 		c->batch_blocks_ = batch_blocks_;
 		c->batch_blocks_set_ = batch_blocks_set_;
@@ -1485,6 +1506,9 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		timings_.families_uploaded += ct.families_uploaded;
 		timings_.family_bytes += ct.family_bytes;
 		timings_.family_block_bytes += ct.family_block_bytes;
+		timings_.charstring_fonts_decoded += ct.charstring_fonts_decoded;
+		timings_.charstring_font_bytes += ct.charstring_font_bytes;
+		timings_.charstring_fallbacks += ct.charstring_fallbacks;
 		timings_.glyf_fallbacks += ct.glyf_fallbacks;
 		timings_.fe_groups += ct.fe_groups;
 		timings_.fe_max_group_glyphs = std::max(timings_.fe_max_group_glyphs, ct.fe_max_group_glyphs);
@@ -1688,13 +1712,13 @@ bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G,
 			if (m.fonts.size() >= 0xFFFF)
 				return false;
 			uint64_t uploaded = 0;
-			const vgsdf_font *f = commands ? renderer.command_font(lane, file->face().command_table(), &uploaded)
+			const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), timings_)
 			                               : renderer.resident_font(lane, file->face().resident_table(), &uploaded);
 			if (!f)
 				return false;
 			if (uploaded) {
-				(commands ? timings_.command_fonts_uploaded : timings_.resident_fonts_uploaded)++;
-				(commands ? timings_.command_font_bytes : timings_.resident_font_bytes) += uploaded;
+				timings_.resident_fonts_uploaded++;
+				timings_.resident_font_bytes += uploaded;
 			}
 			index.emplace_back(file.get(), (uint16_t)m.fonts.size());
 			m.fonts.push_back(f);
@@ -1758,6 +1782,31 @@ bool FontManager::fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G,
 	return true;
 }
 
+const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const
+{
+	uint64_t uploaded = 0;
+	const vgsdf_font *f = nullptr;
+	if (charstrings_on_device_ && face.charstring_table().ok) {
+		bool refused = false, over_budget = false;
+		f = renderer.charstring_font(lane, face.charstring_table(), &uploaded, &refused, &over_budget);
+		if (refused)
+			counts.charstring_fallbacks++;
+		if (over_budget)
+			return nullptr; // (the host's table would make the same store, over the same budget: it is not built for that)
+		if (f && uploaded) {
+			counts.charstring_fonts_decoded++;
+			counts.charstring_font_bytes += uploaded;
+		}
+	}
+	if (!f)
+		f = renderer.command_font(lane, face.command_table(), &uploaded);
+	if (f && uploaded) {
+		counts.command_fonts_uploaded++;
+		counts.command_font_bytes += uploaded;
+	}
+	return f;
+}
+
 const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font,
                                                bool commands, const FamilyTable **table, RenderTimings &counts) const
 {
@@ -1767,13 +1816,13 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 	std::vector<const vgsdf_font *> stores;
 	for (const auto &file : font.files()) {
 		uint64_t uploaded = 0;
-		const vgsdf_font *f = commands ? renderer.command_font(lane, file->face().command_table(), &uploaded)
+		const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), counts)
 		                               : (file->face().has_glyf_outlines() ? renderer.resident_font(lane, file->face().resident_table(), &uploaded) : nullptr);
 		if (!f)
 			return nullptr;
 		if (uploaded) {
-			(commands ? counts.command_fonts_uploaded : counts.resident_fonts_uploaded)++;
-			(commands ? counts.command_font_bytes : counts.resident_font_bytes) += uploaded;
+			counts.resident_fonts_uploaded++;
+			counts.resident_font_bytes += uploaded;
 		}
 		stores.push_back(f);
 	}
@@ -1867,6 +1916,7 @@ bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, c
 uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 {
 	uint64_t uploaded = 0;
+	preload_counts_ = RenderTimings{};
 	for (size_t r = 0; r < renderer.n_devices(); r++)
 		for (const auto &kv : fonts())
 			for (const auto &file : kv.second.files())
@@ -1881,8 +1931,14 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 				for (const auto &file : kv.second.files())
 					wanted = wanted || !file->face().has_glyf_outlines();
 				if (wanted)
-					for (const auto &file : kv.second.files())
-						(void)renderer.device_lane(r).command_font(0, file->face().command_table(), &uploaded);
+					for (const auto &file : kv.second.files()) {
+						RenderTimings counts;
+						(void)command_store(renderer.device_lane(r), 0, file->face(), counts);
+						uploaded += counts.command_font_bytes;
+						preload_counts_.charstring_fonts_decoded += counts.charstring_fonts_decoded;
+						preload_counts_.charstring_font_bytes += counts.charstring_font_bytes;
+						preload_counts_.charstring_fallbacks += counts.charstring_fallbacks;
+					}
 			}
 	// ... and the families over them, of the kinds of store the modes would name
 	if (resident_families_)
@@ -1893,6 +1949,9 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 						RenderTimings counts;
 						(void)device_family(renderer.device_lane(r), 0, kv.first, kv.second, commands != 0, nullptr, counts);
 						uploaded += counts.family_bytes + counts.resident_font_bytes + counts.command_font_bytes;
+						preload_counts_.charstring_fonts_decoded += counts.charstring_fonts_decoded;
+						preload_counts_.charstring_font_bytes += counts.charstring_font_bytes;
+						preload_counts_.charstring_fallbacks += counts.charstring_fallbacks;
 					}
 	return uploaded;
 }

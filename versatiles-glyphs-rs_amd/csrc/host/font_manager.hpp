@@ -154,6 +154,9 @@ struct RenderTimings {
 	// groups submitted as code-point ranges of resident families (counted here and not above), families put on a device, their
 	// bytes there, bytes of those submissions' upload blocks
 	uint64_t family_groups = 0, families_uploaded = 0, family_bytes = 0, family_block_bytes = 0;
+	// command stores the device decoded from charstrings (set_charstrings_on_device; counted among command_fonts_uploaded too),
+	// their bytes, and faces it refused, whose stores were built from the host reader's table instead
+	uint64_t charstring_fonts_decoded = 0, charstring_font_bytes = 0, charstring_fallbacks = 0;
 };
 
 class FontManager {
@@ -236,6 +239,12 @@ public:
 	// 2: every group goes that way, `glyf` faces included (the A/B lever).  A store that does not fit the renderer's
 	// budget sends its groups the way they go with 0.
 	void set_resident_commands(int mode) { resident_commands_ = mode < 0 || mode > 2 ? 0 : mode; }
+	// Command stores of `CFF ` version 1 faces decoded on the device from the charstrings (vgsdf_font_create_charstrings) instead
+	// of uploaded from command_table(); a face the device refuses falls back.  Default off.  The stores' bytes are the same.
+	void set_charstrings_on_device(bool on) { charstrings_on_device_ = on; }
+	const CharstringTable *charstring_table(const std::string &font_id, size_t file_index, std::string *err) const;
+	// what the last preload_resident_fonts built: its uploads are counted here, not in the timings of a render
+	const RenderTimings &last_preload_counts() const { return preload_counts_; }
 	// Resident families (default off): a group that would be recorded glyph by glyph against resident fonts or command stores
 	// (the two switches above) is submitted as code-point ranges of its font ids' families instead — one task per (font, block),
 	// one per run of code points for a block the hybrid lane plan has split — and the device writes the PBF entries; recording
@@ -452,6 +461,10 @@ private:
 	bool glyf_on_device_ = glyf_on_device_default(); // glyf fonts: the device decodes the glyphs' arrays (VG_GLYF_ON_DEVICE=0 / set_glyf_on_device(false): the host does)
 	bool resident_fonts_ = false;
 	int resident_commands_ = 0;
+	bool charstrings_on_device_ = false;
+	mutable RenderTimings preload_counts_;
+	// a face's command store on the renderer's device, by either path; counts into `counts`
+	const vgsdf_font *command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
 	bool resident_families_ = false;
 	bool device_front_end_ = true; // HIP renderer: flatten on the GPU unless switched off
 	std::map<std::string, FontWrapper> fonts_; // reference: HashMap (arbitrary order); sorted here

@@ -220,6 +220,8 @@ Renderer::~Renderer()
 					break;
 				}
 		resident_->fonts.clear();
+		resident_->refused_charstrings.clear();
+		resident_->unfit_charstrings.clear();
 		resident_->bytes.clear();
 	}
 	if (ctx2_)
@@ -500,6 +502,66 @@ const vgsdf_font *Renderer::command_font(int lane, const CommandTable &t, uint64
 		if (vgsdf_font_create_commands(c, &d, &f) != VGSDF_OK)
 			throw std::runtime_error(std::string("vgsdf_font_create_commands: ") + vgsdf_last_error(c));
 	}
+	const uint64_t got = vgsdf_font_device_bytes(f);
+	rf.fonts.emplace(key, f);
+	rf.bytes[device_] += got;
+	if (uploaded_bytes)
+		*uploaded_bytes += got;
+	return f;
+}
+
+const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, uint64_t *uploaded_bytes, bool *refused, bool *over_budget) const
+{
+	if (mode_ != Mode::Hip || !t.ok)
+		return nullptr;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	const auto key = std::make_pair(device_, t.serial);
+	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
+		return it->second;
+	if (rf.refused_charstrings.count(key))
+		return nullptr;
+	const uint64_t used = rf.bytes[device_], room = rf.budget > used ? rf.budget - used : 0;
+	if (auto it = rf.unfit_charstrings.find(key); it != rf.unfit_charstrings.end() && it->second > room) {
+		if (over_budget)
+			*over_budget = true;
+		return nullptr;
+	}
+	vgsdf_font_charstrings_desc d;
+	d.n_glyph_ids = (uint32_t)t.cs_off.size() - 1;
+	d.n_bytes = (uint32_t)t.bytes.size();
+	d.bytes = t.bytes.data();
+	d.cs_off = t.cs_off.data();
+	d.n_gsubrs = (uint32_t)t.gsubr_off.size() - 1;
+	d.gsubr_off = t.gsubr_off.data();
+	d.n_fds = t.n_fds;
+	d.lsubr_first = t.lsubr_first.data();
+	d.lsubr_off = t.lsubr_off.data();
+	d.fd_of = t.fd_of.empty() ? nullptr : t.fd_of.data();
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	vgsdf_font *f = nullptr;
+	{
+		// the budget as command_font holds it: the store's size is known behind the count pass, and checked there, before
+		// anything of the store is allocated
+		uint64_t want = 0;
+		std::lock_guard<std::mutex> lock(mu_);
+		const int rc = vgsdf_font_create_charstrings_within(c, &d, room, &f, &want);
+		if (rc == VGSDF_E_GLYF) {
+			rf.refused_charstrings.insert(key);
+			if (refused)
+				*refused = true;
+			return nullptr;
+		}
+		if (rc != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_font_create_charstrings: ") + vgsdf_last_error(c));
+		if (!f) { // over the budget as it stands
+			rf.unfit_charstrings[key] = want;
+			if (over_budget)
+				*over_budget = true;
+			return nullptr;
+		}
+	}
+	rf.unfit_charstrings.erase(key);
 	const uint64_t got = vgsdf_font_device_bytes(f);
 	rf.fonts.emplace(key, f);
 	rf.bytes[device_] += got;

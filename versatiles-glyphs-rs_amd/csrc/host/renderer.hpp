@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <map>
+#include <set>
 #include <memory>
 #include <new>
 #include <mutex>
@@ -462,6 +463,15 @@ public:
 	// the same for the command store of a face (vgsdf_font_create_commands): same registry (the tables' serials come from one
 	// sequence), same budget, no eviction.  nullptr: no command table, or over the budget — the caller goes on as without
 	const vgsdf_font *command_font(int lane, const CommandTable &table, uint64_t *uploaded_bytes = nullptr) const;
+	// the same store made on the device from a `CFF ` face's charstrings (vgsdf_font_create_charstrings): the key is the face's
+	// command serial, so whichever of the two calls comes first makes the store and the other finds it.  nullptr: no charstring
+	// table; the device refused the face (*refused is set then, once per face and device: a seac glyph, a glyph past the token
+	// budget, a store past the bounds) and the caller takes command_font(), which needs the host's table; or the store would
+	// pass the budget (*over_budget is set: command_font() would find the same store over the same budget, so the caller need
+	// not build the host's table).  The size of a store that did not fit is kept, so the count pass is not run again while
+	// it does not fit, and is once the budget has room for it
+	const vgsdf_font *charstring_font(int lane, const CharstringTable &table, uint64_t *uploaded_bytes = nullptr, bool *refused = nullptr,
+	                                  bool *over_budget = nullptr) const;
 	// Resident families (vgsdf_family_create): the device copy of a font id's table code point -> (file, glyph id, advance,
 	// scale, shift_x) over the device fonts of its files, one per (device, table serial, kind of store) in the registry of the
 	// fonts — same budget, freed with the renderer, in front of the fonts.  A table rebuilt after a file was added has a new
@@ -520,6 +530,8 @@ private:
 		std::map<std::pair<int, uint64_t>, vgsdf_font *> fonts; // (device, the face's serial number) -> its copy there
 		std::map<std::tuple<int, uint64_t, bool>, vgsdf_family *> families; // (device, table serial, command stores) -> the family
 		std::map<int, uint64_t> bytes;                          // per device
+		std::set<std::pair<int, uint64_t>> refused_charstrings; // (device, serial): the device's decoder has refused the face
+		std::map<std::pair<int, uint64_t>, uint64_t> unfit_charstrings; // (device, serial) -> bytes of a store that passed the budget
 		uint64_t budget = 1ull << 30;
 	};
 	std::shared_ptr<ResidentFonts> resident_ = std::make_shared<ResidentFonts>();

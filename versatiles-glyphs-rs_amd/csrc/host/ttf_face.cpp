@@ -1072,10 +1072,34 @@ const CommandTable &Face::command_table() const
 			t.cmd_off.push_back((uint32_t)t.kinds.size());
 			t.dat_off.push_back((uint32_t)t.coords.size());
 		}
-		t.serial = next_table_serial();
+		t.serial = command_serial();
 		t.ok = true;
 	});
 	return cell.table;
+}
+
+uint64_t Face::command_serial() const
+{
+	CommandCell &cell = *commands_;
+	std::call_once(cell.serial_once, [&] { cell.serial = next_table_serial(); });
+	return cell.serial;
+}
+
+const CharstringTable &Face::charstring_table() const
+{
+	CommandCell &cell = *commands_;
+	std::call_once(cell.charstrings_once, [&] {
+		CharstringTable &t = cell.charstrings;
+		if (has_glyf_outlines() || !cff_ || cff_->is_cff2())
+			return;
+		if (!cff_->charstring_table(num_glyphs_, t)) {
+			t = CharstringTable{};
+			return;
+		}
+		t.serial = command_serial();
+		t.ok = true;
+	});
+	return cell.charstrings;
 }
 
 bool Face::outline_glyph_packed(uint16_t gid, std::vector<uint8_t> &kinds, std::vector<float> &coords) const

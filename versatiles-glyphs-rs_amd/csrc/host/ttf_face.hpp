@@ -71,6 +71,21 @@ struct CommandTable {
 	static constexpr uint64_t kMaxStoreBytes = (1ull << 32) - 4, kStoreBytesPerCmd = 29, kMaxFloats = kMaxStoreBytes / 4;
 };
 
+// A `CFF ` (version 1) face's charstrings for the device's decoder (vgsdf_font_charstrings_desc of include/vgsdf.h, array for
+// array): every charstring and subroutine body copied once into `bytes`, the INDEX offsets resolved to ranges of it.  The
+// store the device makes of it is the one CommandTable describes, so the two share the face's command serial.
+struct CharstringTable {
+	bool ok = false;                   // false: no `CFF ` outlines (glyf, CFF2), or an INDEX the description cannot state
+	uint64_t serial = 0;               // Face::command_serial()
+	std::vector<uint8_t> bytes;        // padded to a multiple of 4
+	std::vector<uint32_t> cs_off;      // [numGlyphs + 1]
+	std::vector<uint32_t> gsubr_off;   // [global subroutines + 1]
+	uint32_t n_fds = 1;
+	std::vector<uint32_t> lsubr_first; // [n_fds + 1]
+	std::vector<uint32_t> lsubr_off;   // [lsubr_first[n_fds] + 1]
+	std::vector<uint8_t> fd_of;        // [numGlyphs], empty when n_fds == 1
+};
+
 // Non-owning big-endian byte view with checked reads.
 class Bytes {
 public:
@@ -125,6 +140,12 @@ public:
 	// glyph (outline_glyph_packed, return value ignored) for every glyph id.  The callbacks are counted first and the count stops at the
 	// bounds, so a face past them is refused without its table ever being allocated.
 	const CommandTable &command_table() const;
+	// What a renderer keys the face's command store by, whichever way the store is made (command_table().serial is this number);
+	// handed out on first use, without building a table.
+	uint64_t command_serial() const;
+	// The charstring form of a `CFF ` version 1 face: built once, on first use (thread-safe), from the tables CffTable::parse has
+	// located — no charstring is interpreted.
+	const CharstringTable &charstring_table() const;
 	// ttf-parser's `tables().cmap.is_some()`; the reference refuses fonts without one (metadata.rs:104-107)
 	bool has_cmap() const { return has_cmap_; }
 	// glyph outlines this reader can emit: `glyf` + `loca`, or `CFF ` charstrings (ttf-parser's order: glyf first).
@@ -163,8 +184,10 @@ private:
 	};
 	std::shared_ptr<ResidentCell> resident_ = std::make_shared<ResidentCell>(); // (shared by copies of the Face: same bytes)
 	struct CommandCell {
-		std::once_flag once;
+		std::once_flag once, serial_once, charstrings_once;
+		uint64_t serial = 0;
 		CommandTable table;
+		CharstringTable charstrings;
 	};
 	std::shared_ptr<CommandCell> commands_ = std::make_shared<CommandCell>();
 

@@ -1,5 +1,5 @@
 // resident_fonts.cpp — the stores behind vgsdf_font: a face's outlines uploaded once, as `glyf` leaves (vgsdf_font_create)
-// or as expanded commands (vgsdf_font_create_commands).  Submissions that name their glyphs read them
+// or as expanded commands (vgsdf_font_create_commands; vgsdf_font_create_charstrings: decoded on the device from a CFF face's charstrings).  Submissions that name their glyphs read them
 // (outline_front_end.cpp, vgsdf_outlines_submit_resident).  And the families over them (vgsdf_family_create): a font id's table
 // code point -> (font, glyph id, advance, scale, shift_x) on host and device, for submissions that name code-point ranges
 // (vgsdf_outlines_submit_ranges).
@@ -9,6 +9,7 @@
 #include <memory>
 #include <new>
 
+#include "charstring_kernels.h"
 #include "outline_kernels.h"
 #include "resident_fonts.h"
 #include "work_plan.h"
@@ -191,10 +192,241 @@ int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, v
 		ctx->err = "vgsdf_font_create_commands: the device's context pass refused the commands";
 		return VGSDF_E_ARG;
 	}
+	f->n_cmds = n_cmds;
 	f->cref.cmds = (uint64_t)(uintptr_t)d;
 	f->cref.cmd_off = (uint64_t)(uintptr_t)(d + off_at);
 	f->cref.open = (uint64_t)(uintptr_t)(d + open_at);
 	*out = f.release();
+	return VGSDF_OK;
+}
+
+int vgsdf_font_create_charstrings(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, vgsdf_font **out)
+{
+	return vgsdf_font_create_charstrings_within(ctx, in, ~0ull, out, nullptr);
+}
+
+int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
+                                         uint64_t *store_bytes)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->cs_off || !in->gsubr_off || !in->lsubr_first || !in->lsubr_off || (in->n_bytes && !in->bytes) ||
+	    (in->n_fds > 1 && !in->fd_of)) {
+		ctx->err = "vgsdf_font_create_charstrings: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	if (store_bytes)
+		*store_bytes = 0;
+	const uint32_t n = in->n_glyph_ids, n_bytes = in->n_bytes;
+	if (n == 0 || n > 0x10000u || (n_bytes & 3u) || n_bytes > 0xFFFFFFF0u || in->n_gsubrs > 0xFFFFu || in->n_fds == 0 || in->n_fds > 256u) {
+		ctx->err = "vgsdf_font_create_charstrings: glyph ids not 1 .. 65536, n_bytes not a multiple of 4 (or past 2^32 - 16), more than "
+		           "65535 global subroutines, or Font DICTs not 1 .. 256";
+		return VGSDF_E_ARG;
+	}
+	// every range the device will read, before anything runs
+	auto ascends_inside = [&](const uint32_t *off, size_t count) {
+		for (size_t i = 0; i < count; i++)
+			if (off[i + 1] < off[i])
+				return false;
+		return off[count] <= n_bytes;
+	};
+	if (in->lsubr_first[0] != 0) {
+		ctx->err = "vgsdf_font_create_charstrings: lsubr_first does not start at 0";
+		return VGSDF_E_ARG;
+	}
+	for (uint32_t k = 0; k < in->n_fds; k++)
+		if (in->lsubr_first[k + 1] < in->lsubr_first[k] || in->lsubr_first[k + 1] - in->lsubr_first[k] > 0xFFFFu) {
+			ctx->err = "vgsdf_font_create_charstrings: lsubr_first not ascending, or a Font DICT of more than 65535 local subroutines";
+			return VGSDF_E_ARG;
+		}
+	const uint32_t n_lsubrs = in->lsubr_first[in->n_fds];
+	if (!ascends_inside(in->cs_off, n) || !ascends_inside(in->gsubr_off, in->n_gsubrs) || !ascends_inside(in->lsubr_off, n_lsubrs)) {
+		ctx->err = "vgsdf_font_create_charstrings: cs_off, gsubr_off or lsubr_off not ascending, or ending past n_bytes";
+		return VGSDF_E_ARG;
+	}
+	if (in->fd_of)
+		for (uint32_t g = 0; g < n; g++)
+			if (in->fd_of[g] >= in->n_fds) {
+				ctx->err = "vgsdf_font_create_charstrings: an fd_of past n_fds";
+				return VGSDF_E_ARG;
+			}
+	std::unique_ptr<vgsdf_font> f(new (std::nothrow) vgsdf_font());
+	if (!f) {
+		ctx->err = "vgsdf_font_create_charstrings: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	ctx->charstring_ms[0] = ctx->charstring_ms[1] = 0.0f;
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	// the description on the device, for the duration of this call:
+	// bytes | cs_off | gsubr_off | lsubr_first | lsubr_off | counts (commands, coordinates per glyph id) | flags | fd_of
+	const size_t a_cs = align_up(n_bytes, 16), a_gs = a_cs + 4 * ((size_t)n + 1), a_lf = a_gs + 4 * ((size_t)in->n_gsubrs + 1),
+	             a_lo = a_lf + 4 * ((size_t)in->n_fds + 1), a_counts = a_lo + 4 * ((size_t)n_lsubrs + 1), a_flags = a_counts + 8 * (size_t)n,
+	             a_fd = a_flags + 16, a_total = a_fd + (in->fd_of ? n : 0);
+	ScratchBuf face_buf, tmp;
+	struct Events {
+		hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+		~Events()
+		{
+			for (hipEvent_t ev : e)
+				if (ev)
+					(void)hipEventDestroy(ev);
+		}
+	} ev;
+	for (hipEvent_t &e : ev.e)
+		if (hipError_t err = hipEventCreate(&e); err != hipSuccess)
+			return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipEventCreate", err);
+	if (hipError_t e = face_buf.ensure(a_total + 16); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipMalloc", e);
+	uint8_t *a = (uint8_t *)face_buf.p;
+	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+	hipError_t e = copy(a, in->bytes, n_bytes);
+	if (e == hipSuccess)
+		e = copy(a + a_cs, in->cs_off, 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = copy(a + a_gs, in->gsubr_off, 4 * ((size_t)in->n_gsubrs + 1));
+	if (e == hipSuccess)
+		e = copy(a + a_lf, in->lsubr_first, 4 * ((size_t)in->n_fds + 1));
+	if (e == hipSuccess)
+		e = copy(a + a_lo, in->lsubr_off, 4 * ((size_t)n_lsubrs + 1));
+	if (e == hipSuccess && in->fd_of)
+		e = copy(a + a_fd, in->fd_of, n);
+	if (e == hipSuccess)
+		e = hipMemsetAsync(a + a_flags, 0, 16, st);
+	vgsdf::CharstringsRef face{};
+	face.words = (const uint32_t *)a;
+	face.cs_off = (const uint32_t *)(a + a_cs);
+	face.gsubr_off = (const uint32_t *)(a + a_gs);
+	face.lsubr_first = (const uint32_t *)(a + a_lf);
+	face.lsubr_off = (const uint32_t *)(a + a_lo);
+	face.fd_of = in->fd_of ? a + a_fd : nullptr;
+	face.n_glyph_ids = n;
+	face.n_gsubrs = in->n_gsubrs;
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[0], st);
+	if (e == hipSuccess)
+		e = (hipError_t)vgsdf_charstring_count(&face, (uint32_t *)(a + a_counts), (uint32_t *)(a + a_flags), st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[1], st);
+	std::vector<uint32_t> counts(2 * (size_t)n);
+	uint32_t flags = 0;
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(counts.data(), a + a_counts, 8 * (size_t)n, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(&flags, a + a_flags, 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st);
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "count pass", e);
+	(void)hipEventElapsedTime(&ctx->charstring_ms[0], ev.e[0], ev.e[1]);
+	if (flags) {
+		ctx->err = flags & vgsdf::CS_FLAG_SEAC ? "vgsdf_font_create_charstrings: a glyph whose endchar takes the seac form"
+		                                       : "vgsdf_font_create_charstrings: a glyph past VGSDF_CHARSTRING_MAX_TOKENS";
+		return VGSDF_E_GLYF;
+	}
+	// the store's layout from the counts: what vgsdf_font_create_commands is given by its caller
+	std::vector<uint32_t> cmd_off((size_t)n + 1), dat_off((size_t)n + 1);
+	uint64_t cmds = 0, floats = 0;
+	f->slots.assign(n, 0);
+	for (uint32_t g = 0; g < n; g++) {
+		cmd_off[g] = (uint32_t)cmds, dat_off[g] = (uint32_t)floats;
+		f->slots[g] = counts[2 * (size_t)g];
+		cmds += counts[2 * (size_t)g], floats += counts[2 * (size_t)g + 1];
+		if (29ull * cmds + 4ull * (n + 1) > 0xFFFFFFFCull || 4ull * floats > 0xFFFFFFFCull) {
+			ctx->err = "vgsdf_font_create_charstrings: a store (29 bytes per command, 4 per glyph id) or coordinates past what 32-bit "
+			           "offsets address";
+			return VGSDF_E_GLYF;
+		}
+	}
+	const uint32_t n_cmds = (uint32_t)cmds, n_floats = (uint32_t)floats;
+	cmd_off[n] = n_cmds, dat_off[n] = n_floats;
+	if (store_bytes)
+		*store_bytes = 29ull * n_cmds + 4ull * (n + 1);
+	if (29ull * n_cmds + 4ull * (n + 1) > max_store_bytes)
+		return VGSDF_OK; // (*out stays NULL: the caller's limit, nothing allocated)
+	f->device = ctx->device;
+	f->n_glyph_ids = n;
+	f->commands = true;
+	f->n_cmds = n_cmds;
+	// store and temporaries as vgsdf_font_create_commands lays them out (the same sizes: the same vgsdf_font_device_bytes)
+	const size_t off_at = sizeof(vgsdf::OutlineCmd) * (size_t)n_cmds, open_at = off_at + 4 * ((size_t)n + 1), total = open_at + n_cmds;
+	const size_t t_dat = 8 * (size_t)n, t_coords = t_dat + 4 * ((size_t)n + 1), t_kinds = t_coords + 4 * (size_t)n_floats,
+	             t_flag = align_up(t_kinds + n_cmds, 16), t_total = t_flag + 16;
+	if (hipError_t err = f->store.ensure(total + 16); err != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipMalloc", err);
+	if (hipError_t err = tmp.ensure(t_total); err != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipMalloc", err);
+	uint8_t *d = (uint8_t *)f->store.p, *t = (uint8_t *)tmp.p;
+	const std::vector<double> ones(n, 1.0);
+	e = copy(d + off_at, cmd_off.data(), 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = copy(t, ones.data(), 8 * (size_t)n);
+	if (e == hipSuccess)
+		e = copy(t + t_dat, dat_off.data(), 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = hipMemsetAsync(t + t_flag, 0, 16, st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[1], st);
+	// (cmd_off is read from the store, where it stays; dat_off from the temporaries, as the context pass below reads them)
+	if (e == hipSuccess && n_cmds)
+		e = (hipError_t)vgsdf_charstring_emit(&face, (const uint32_t *)(d + off_at), (const uint32_t *)(t + t_dat), t + t_kinds,
+		                                      (float *)(t + t_coords), (uint32_t *)(a + a_flags), st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[2], st);
+	if (e == hipSuccess && n_cmds)
+		e = (hipError_t)vgsdf_outline_context_packed(t + t_kinds, (const float *)(t + t_coords), (const uint32_t *)(t + t_dat),
+		                                             (const uint32_t *)(d + off_at), (const double *)t, n, (vgsdf::OutlineCmd *)d, d + open_at,
+		                                             (uint32_t *)(t + t_flag), st);
+	uint32_t flag = 0;
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(&flag, t + t_flag, 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(&flags, a + a_flags, 4, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st); // the store is complete when the call returns: every context may name the font
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "emit pass", e);
+	if (n_cmds)
+		(void)hipEventElapsedTime(&ctx->charstring_ms[1], ev.e[1], ev.e[2]);
+	if (flag || flags) { // (the two passes walk one text over the same bytes: said by the passes themselves)
+		ctx->err = "vgsdf_font_create_charstrings: the emit pass did not match the count pass, or the context pass refused the commands";
+		return VGSDF_E_HIP;
+	}
+	f->cref.cmds = (uint64_t)(uintptr_t)d;
+	f->cref.cmd_off = (uint64_t)(uintptr_t)(d + off_at);
+	f->cref.open = (uint64_t)(uintptr_t)(d + open_at);
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+void vgsdf_font_charstrings_kernel_ms(const vgsdf_ctx *ctx, float ms[2])
+{
+	if (ms)
+		ms[0] = ctx ? ctx->charstring_ms[0] : 0.0f, ms[1] = ctx ? ctx->charstring_ms[1] : 0.0f;
+}
+
+int vgsdf_font_commands_read(vgsdf_ctx *ctx, const vgsdf_font *font, uint32_t *n_glyph_ids, uint32_t *n_cmds, uint32_t *cmd_off,
+                             void *records, uint8_t *context)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!font || !font->commands || font->device != ctx->device) {
+		ctx->err = "vgsdf_font_commands_read: no font, a font from vgsdf_font_create, or a font of another device than the context's";
+		return VGSDF_E_ARG;
+	}
+	if (n_glyph_ids)
+		*n_glyph_ids = font->n_glyph_ids;
+	if (n_cmds)
+		*n_cmds = font->n_cmds;
+	(void)hipSetDevice(ctx->device);
+	const size_t n = font->n_cmds;
+	if (cmd_off)
+		HIP_TRY(ctx, hipMemcpy(cmd_off, (const void *)(uintptr_t)font->cref.cmd_off, 4 * ((size_t)font->n_glyph_ids + 1), hipMemcpyDeviceToHost));
+	if (records && n)
+		HIP_TRY(ctx, hipMemcpy(records, (const void *)(uintptr_t)font->cref.cmds, sizeof(vgsdf::OutlineCmd) * n, hipMemcpyDeviceToHost));
+	if (context && n)
+		HIP_TRY(ctx, hipMemcpy(context, (const void *)(uintptr_t)font->cref.open, n, hipMemcpyDeviceToHost));
 	return VGSDF_OK;
 }
 

@@ -19,6 +19,7 @@ struct vgsdf_font {
 	// a command font (vgsdf_font_create_commands): one allocation records | cmd_off | context bytes; `slots` holds the glyph
 	// ids' command counts and nothing of the leaves above is used
 	bool commands = false;
+	uint32_t n_cmds = 0; // of the store
 	vgsdf::CommandFontRef cref{};
 	vgsdf_font() = default;
 	vgsdf_font(const vgsdf_font &) = delete;

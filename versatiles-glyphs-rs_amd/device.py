@@ -66,6 +66,12 @@ class _CFontCmdsDesc(C.Structure):  # vgsdf_font_cmds_desc
                 ("dat_off", C.c_void_p), ("kinds", C.c_void_p), ("coords", C.c_void_p)]
 
 
+class _CFontCharstringsDesc(C.Structure):  # vgsdf_font_charstrings_desc
+    _fields_ = [("n_glyph_ids", C.c_uint32), ("n_bytes", C.c_uint32), ("bytes", C.c_void_p), ("cs_off", C.c_void_p),
+                ("n_gsubrs", C.c_uint32), ("gsubr_off", C.c_void_p), ("n_fds", C.c_uint32), ("lsubr_first", C.c_void_p),
+                ("lsubr_off", C.c_void_p), ("fd_of", C.c_void_p)]
+
+
 class _COutlinesResident(C.Structure):  # vgsdf_outlines_resident
     _fields_ = [("n_glyphs", C.c_uint32), ("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("font_of", C.c_void_p),
                 ("glyph_id", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("pbf_pre", C.c_void_p),
@@ -88,7 +94,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_host_alloc", "vgsdf_host_free", "vgsdf_outlines_prepare", "vgsdf_outlines_render", "vgsdf_outlines_render_into", "vgsdf_outlines_submit", "vgsdf_outlines_submit_packed", "vgsdf_outlines_submit_glyf", "vgsdf_outlines_wait", "vgsdf_outlines_segments",
     "vgsdf_add_counters", "vgsdf_reset_counters", "vgsdf_reduce_counters", "vgsdf_reduce_counters_rccl", "vgsdf_reduce_path", "vgsdf_outlines_pbf_positions", "vgsdf_outlines_peek",
     "vgsdf_font_create", "vgsdf_font_free", "vgsdf_font_device_bytes", "vgsdf_outlines_submit_resident", "vgsdf_outlines_resident_upload_bytes",
-    "vgsdf_font_create_commands",
+    "vgsdf_font_create_commands", "vgsdf_font_create_charstrings", "vgsdf_font_create_charstrings_within", "vgsdf_font_charstrings_kernel_ms", "vgsdf_font_commands_read",
     "vgsdf_family_create", "vgsdf_family_free", "vgsdf_family_device_bytes", "vgsdf_family_count", "vgsdf_outlines_submit_ranges",
     "vgsdf_outlines_task_extents",
 ]
@@ -139,6 +145,11 @@ def load_library():
         L.vgsdf_outlines_peek.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.vgsdf_font_create.argtypes = [vp, C.POINTER(_CFontDesc), C.POINTER(vp)]
         L.vgsdf_font_create_commands.argtypes = [vp, C.POINTER(_CFontCmdsDesc), C.POINTER(vp)]
+        L.vgsdf_font_create_charstrings.argtypes = [vp, C.POINTER(_CFontCharstringsDesc), C.POINTER(vp)]
+        L.vgsdf_font_create_charstrings_within.argtypes = [vp, C.POINTER(_CFontCharstringsDesc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.vgsdf_font_charstrings_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_font_charstrings_kernel_ms.restype = None
+        L.vgsdf_font_commands_read.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp]
         L.vgsdf_font_free.argtypes = [vp, vp]
         L.vgsdf_font_device_bytes.argtypes = [vp]
         L.vgsdf_font_device_bytes.restype = C.c_uint64
@@ -507,6 +518,52 @@ class SdfContext:
         h = C.c_void_p()
         self._check(load_library().vgsdf_font_create_commands(self._h, C.byref(d), C.byref(h)))
         return ResidentFont(self, h)
+
+    def font_create_charstrings(self, desc: dict, max_store_bytes=None, **override):
+        """vgsdf_font_create_charstrings: a `CFF ` face's charstrings (vgsdf_font_charstrings_desc as a dict: bytes, cs_off,
+        gsubr_off, lsubr_first, lsubr_off, fd_of or None — what FontManager.charstring_font_desc returns) -> the command font the
+        DEVICE decodes from them.  override: raw struct fields (n_glyph_ids, n_bytes, n_gsubrs, n_fds) for descriptions that lie.
+        VgsdfError with code VGSDF_E_GLYF: the device refuses the face (seac, token budget, store bounds).
+        max_store_bytes (vgsdf_font_create_charstrings_within): -> (ResidentFont or None when the store would pass it, store bytes)"""
+        keep = {k: np.ascontiguousarray(desc[k], dtype=np.uint32) for k in ("cs_off", "gsubr_off", "lsubr_first", "lsubr_off")}
+        keep["bytes"] = np.ascontiguousarray(desc["bytes"], dtype=np.uint8)
+        fd_of = desc.get("fd_of")
+        keep["fd_of"] = None if fd_of is None or len(fd_of) == 0 else np.ascontiguousarray(fd_of, dtype=np.uint8)
+        d = _CFontCharstringsDesc()
+        d.n_glyph_ids = override.get("n_glyph_ids", len(keep["cs_off"]) - 1)
+        d.n_bytes = override.get("n_bytes", len(keep["bytes"]))
+        d.bytes = keep["bytes"].ctypes.data
+        d.cs_off = keep["cs_off"].ctypes.data
+        d.n_gsubrs = override.get("n_gsubrs", len(keep["gsubr_off"]) - 1)
+        d.gsubr_off = keep["gsubr_off"].ctypes.data
+        d.n_fds = override.get("n_fds", len(keep["lsubr_first"]) - 1)
+        d.lsubr_first = keep["lsubr_first"].ctypes.data
+        d.lsubr_off = keep["lsubr_off"].ctypes.data
+        d.fd_of = None if keep["fd_of"] is None else keep["fd_of"].ctypes.data
+        h = C.c_void_p()
+        if max_store_bytes is not None:
+            want = C.c_uint64()
+            self._check(load_library().vgsdf_font_create_charstrings_within(self._h, C.byref(d), int(max_store_bytes), C.byref(h), C.byref(want)))
+            return (ResidentFont(self, h) if h.value else None), int(want.value)
+        self._check(load_library().vgsdf_font_create_charstrings(self._h, C.byref(d), C.byref(h)))
+        return ResidentFont(self, h)
+
+    def font_charstrings_kernel_ms(self):
+        """(count, emit) kernel milliseconds of this context's last font_create_charstrings"""
+        ms = (C.c_float * 2)()
+        load_library().vgsdf_font_charstrings_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
+
+    def font_commands_read(self, font: ResidentFont) -> dict:
+        """vgsdf_font_commands_read (test / inspection): a command font's store as {cmd_off, records (OUTLINE_CMD_DTYPE), context}"""
+        L = load_library()
+        n, n_cmds = C.c_uint32(), C.c_uint32()
+        self._check(L.vgsdf_font_commands_read(self._h, font._h, C.byref(n), C.byref(n_cmds), None, None, None))
+        cmd_off = np.zeros(n.value + 1, dtype=np.uint32)
+        records = np.zeros(n_cmds.value, dtype=OUTLINE_CMD_DTYPE)
+        context = np.zeros(n_cmds.value, dtype=np.uint8)
+        self._check(L.vgsdf_font_commands_read(self._h, font._h, None, None, cmd_off.ctypes.data, records.ctypes.data, context.ctypes.data))
+        return {"cmd_off": cmd_off, "records": records, "context": context}
 
     def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None):
         """outlines_submit for glyphs named by (font, glyph id) of resident fonts (vgsdf_outlines_resident)"""

@@ -48,6 +48,10 @@ class ResidentStats(C.Structure):  # vg_resident_stats
     _fields_ = [(k, C.c_uint64) for k in ("groups", "fonts_uploaded", "font_bytes", "block_bytes")]
 
 
+class CharstringStats(C.Structure):  # vg_charstring_stats
+    _fields_ = [(k, C.c_uint64) for k in ("fonts_decoded", "font_bytes", "fallbacks")]
+
+
 WRITE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int)
 
 VGFONT_SYMBOLS = [
@@ -59,7 +63,8 @@ VGFONT_SYMBOLS = [
     "vg_manager_record_glyf_parts", "vg_glyf_batch_view", "vg_glyf_batch_free",
     "vg_manager_resident_font_desc", "vg_manager_record_resident", "vg_resident_batch_view", "vg_resident_batch_free",
     "vg_manager_command_font_desc", "vg_manager_record_resident_commands", "vg_manager_set_resident_commands",
-    "vg_manager_command_stats", "vg_manager_set_resident_families", "vg_manager_family_stats",
+    "vg_manager_command_stats", "vg_manager_charstring_font_desc", "vg_manager_set_charstrings_on_device",
+    "vg_manager_charstring_stats", "vg_manager_charstring_preload_stats", "vg_manager_set_resident_families", "vg_manager_family_stats",
     "vg_manager_set_resident_fonts", "vg_renderer_set_resident_budget", "vg_renderer_preload_fonts", "vg_manager_resident_stats",
     "vg_manager_scan", "vg_manager_font_ids", "vg_manager_font_file_names", "vg_parse_font_name", "vg_manager_generate_name",
     "vg_encode_codeblocks", "vg_manager_index_json", "vg_manager_families_json", "vg_writer_new_tar_path",
@@ -102,6 +107,10 @@ def _L():
         L.vg_manager_set_resident_commands.argtypes = [vp, C.c_int]
         L.vg_manager_set_resident_commands.restype = None
         L.vg_manager_command_stats.argtypes = [vp, C.POINTER(ResidentStats)]
+        L.vg_manager_set_charstrings_on_device.argtypes = [vp, C.c_int]
+        L.vg_manager_set_charstrings_on_device.restype = None
+        L.vg_manager_charstring_stats.argtypes = [vp, C.POINTER(CharstringStats)]
+        L.vg_manager_charstring_preload_stats.argtypes = [vp, C.POINTER(CharstringStats)]
         L.vg_manager_set_resident_families.argtypes = [vp, C.c_int]
         L.vg_manager_set_resident_families.restype = None
         L.vg_manager_family_stats.argtypes = [vp, C.POINTER(ResidentStats)]
@@ -354,6 +363,23 @@ class FontManager:
         (font, glyph id) against command stores instead of being read by the host on every render; 2: every group is; same
         bytes in every mode"""
         _L().vg_manager_set_resident_commands(self._h, int(mode))
+
+    def set_charstrings_on_device(self, on: bool):
+        """False (default).  True: the command stores of `CFF ` version 1 faces are decoded on the device from the charstrings
+        (vgsdf_font_create_charstrings) instead of built by the host's reader; a face the device refuses falls back; same bytes"""
+        _L().vg_manager_set_charstrings_on_device(self._h, 1 if on else 0)
+
+    def charstring_stats(self) -> dict:
+        """of the last render: {fonts_decoded, font_bytes, fallbacks} (vg_charstring_stats)"""
+        s = CharstringStats()
+        _L().vg_manager_charstring_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in CharstringStats._fields_}
+
+    def charstring_preload_stats(self) -> dict:
+        """the same of the manager's last Renderer.preload_fonts (vg_manager_charstring_preload_stats)"""
+        s = CharstringStats()
+        _L().vg_manager_charstring_preload_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in CharstringStats._fields_}
 
     def set_resident_families(self, on: bool):
         """groups that would go by (font, glyph id) go as code-point ranges of resident families instead (default off)"""
@@ -620,6 +646,29 @@ class FontManager:
 
         return {"cmd_off": arr(d.cmd_off, d.n_glyph_ids + 1, np.uint32), "dat_off": arr(d.dat_off, d.n_glyph_ids + 1, np.uint32),
                 "kinds": arr(d.kinds, d.n_cmds, np.uint8), "coords": arr(d.coords, d.n_floats, np.float32)}
+
+    def charstring_font_desc(self, font_id: str, file_index: int = 0) -> dict:
+        """description of one file of a font id for vgsdf_font_create_charstrings (vg_manager_charstring_font_desc; no device):
+        {bytes, cs_off, gsubr_off, lsubr_first, lsubr_off, fd_of (None when there is one Font DICT)} as numpy copies.
+        RuntimeError: a glyf face, a CFF2 face, a `CFF ` table the description cannot state"""
+        from .device import _CFontCharstringsDesc
+        L = _L()
+        L.vg_manager_charstring_font_desc.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        d = _CFontCharstringsDesc()
+        if L.vg_manager_charstring_font_desc(self._h, font_id.encode(), file_index, C.byref(d)) != 0:
+            raise RuntimeError(_err())
+
+        def arr(ptr, count, dt):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dt)
+            buf = (C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dt, count=count).copy()
+
+        lsubr_first = arr(d.lsubr_first, d.n_fds + 1, np.uint32)
+        return {"bytes": arr(d.bytes, d.n_bytes, np.uint8), "cs_off": arr(d.cs_off, d.n_glyph_ids + 1, np.uint32),
+                "gsubr_off": arr(d.gsubr_off, d.n_gsubrs + 1, np.uint32), "lsubr_first": lsubr_first,
+                "lsubr_off": arr(d.lsubr_off, int(lsubr_first[-1]) + 1, np.uint32),
+                "fd_of": arr(d.fd_of, d.n_glyph_ids, np.uint8) if d.fd_of else None}
 
     def family_desc(self, font_id: str) -> dict:
         """the host half of a resident family (vg_manager_family_desc): {code_point, font_of, glyph_id, advance, scale, shift_x,
