@@ -94,8 +94,8 @@ def test_bias_steps_and_font_dicts(vg, ctx, face):
 
 
 def test_the_fonttools_built_faces(vg, ctx):
-    from test_gpu_resident_commands import _fira_as_cff
-    assert assert_device_equals_host(ctx, *_host(vg, _fira_as_cff(400))) > 5000
+    from fira_cff_kit import fira_as_cff
+    assert assert_device_equals_host(ctx, *_host(vg, fira_as_cff(400))) > 5000
 
 
 def _refused(vg, ctx, code, desc, why="", **override):

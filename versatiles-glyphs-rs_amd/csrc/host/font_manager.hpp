@@ -11,6 +11,7 @@
 //   FontManager::{add_path,add_paths}  manager.rs:39-61;  scan  src/commands/recurse.rs:104-133
 //   write_index_json / write_families_json   manager.rs:128-138 (index_files.hpp)
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <functional>
@@ -157,7 +158,36 @@ struct RenderTimings {
 	// command stores the device decoded from charstrings (set_charstrings_on_device; counted among command_fonts_uploaded too),
 	// their bytes, and faces it refused, whose stores were built from the host reader's table instead
 	uint64_t charstring_fonts_decoded = 0, charstring_font_bytes = 0, charstring_fallbacks = 0;
+
+	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
+	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
+	void absorb_lane(const RenderTimings &lane)
+	{
+		tessellate_s = std::max(tessellate_s, lane.tessellate_s);
+		pack_s = std::max(pack_s, lane.pack_s);
+		device_s = std::max(device_s, lane.device_s);
+		encode_s = std::max(encode_s, lane.encode_s);
+		glyphs += lane.glyphs, rasters += lane.rasters, pixels += lane.pixels, segments += lane.segments;
+		glyf_groups += lane.glyf_groups, glyf_fallbacks += lane.glyf_fallbacks;
+		fe_groups += lane.fe_groups;
+		fe_max_group_glyphs = std::max(fe_max_group_glyphs, lane.fe_max_group_glyphs);
+		resident_groups += lane.resident_groups, resident_block_bytes += lane.resident_block_bytes;
+		command_groups += lane.command_groups, command_block_bytes += lane.command_block_bytes;
+		family_groups += lane.family_groups, family_block_bytes += lane.family_block_bytes;
+		add_uploads(lane);
+	}
+	// what `counts` says was put on a device — stores, families, decoded charstrings — added to these
+	void add_uploads(const RenderTimings &counts)
+	{
+		resident_fonts_uploaded += counts.resident_fonts_uploaded, resident_font_bytes += counts.resident_font_bytes;
+		command_fonts_uploaded += counts.command_fonts_uploaded, command_font_bytes += counts.command_font_bytes;
+		families_uploaded += counts.families_uploaded, family_bytes += counts.family_bytes;
+		charstring_fonts_decoded += counts.charstring_fonts_decoded, charstring_font_bytes += counts.charstring_font_bytes;
+		charstring_fallbacks += counts.charstring_fallbacks;
+	}
 };
+// (a field added above belongs in one of the two folds, or in the comment of the first)
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 25 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -260,11 +290,11 @@ public:
 	bool record_glyf_parts(const std::string &font_id, GlyfPartsBatch &out, std::string *err) const;
 	// resident-font form: what a submission of every glyph of the font names, and the description of one of its files
 	// (nullptr: unknown font / file, or a face without a resident form)
-	bool record_resident(const std::string &font_id, ResidentBatch &out, std::string *err) const;
+	bool record_resident(const std::string &font_id, ResidentBatch &out, std::string *err) const { return record_named(font_id, out, false, err); }
 	const ResidentTable *resident_table(const std::string &font_id, size_t file_index, std::string *err) const;
 	// the same against command fonts (vgsdf_font_create_commands), for every face the reader can read, `glyf` or not
 	// (nullptr / false: unknown font / file, or a face whose commands pass what 32-bit offsets address)
-	bool record_resident_commands(const std::string &font_id, ResidentBatch &out, std::string *err) const;
+	bool record_resident_commands(const std::string &font_id, ResidentBatch &out, std::string *err) const { return record_named(font_id, out, true, err); }
 	const CommandTable *command_table(const std::string &font_id, size_t file_index, std::string *err) const;
 	// The host half of a resident family (vgsdf_family_create): for every code point the font id maps, up to 0xFFFF and
 	// ascending, the file that draws it (first provider wins), its glyph id there, advance, scale and shift_x — the arithmetic
@@ -281,6 +311,12 @@ public:
 	const FamilyTable *family_table(const std::string &font_id, std::string *err) const;
 
 private:
+	using FontEntry = std::map<std::string, FontWrapper>::value_type;
+	// the font of an id (nullptr, and "unknown font id ..." in *err: there is none)
+	const FontEntry *find_font(const std::string &font_id, std::string *err) const;
+	bool record_named(const std::string &font_id, ResidentBatch &out, bool commands, std::string *err) const;
+	template <class Table>
+	const Table *file_table(const std::string &font_id, size_t file_index, const Table &(Face::*table)() const, const char *why, std::string *err) const;
 	mutable std::map<std::string, std::unique_ptr<FamilyTable>> family_tables_; // per font id
 	mutable std::mutex family_mu_;
 	struct Todo {
@@ -302,9 +338,10 @@ private:
 		unsigned worker = 0;
 		uint32_t job0 = 0, job1 = 0;
 		uint32_t g_job = 0; // first glyph index in the merged batch
-		// what the slice added to its worker's batch, noted by the worker while that batch is hot in its cache (the merge's
-		// serial pass then reads this array only): commands / command slots, coordinates / parts, bytes
-		uint32_t n_cmd = 0, n_dat = 0, n_byte = 0;
+		// commands / command slots, coordinates / parts and bytes: first what the slice added to its worker's batch, noted by the
+		// worker while that batch is hot in its cache; the merge's serial pass (which touches no other array) turns the counts
+		// into where the first of each lies in the merged batch
+		uint32_t g_cmd = 0, g_dat = 0, g_byte = 0;
 	};
 	struct alignas(128) Worker { // own cache lines: the vector headers inside are written per glyph
 		TessScratch scratch;
@@ -385,12 +422,15 @@ private:
 	std::unique_ptr<ThreadPool> pool_;
 	std::vector<Worker> workers_;
 	PackedBatch packed_;
+	// The form a group of the device front-end is submitted in: the host reader's commands in the packed upload form; the glyphs'
+	// `glyf` parts; the glyphs named by (font, glyph id) against the renderer's resident glyf stores / command stores; code-point
+	// ranges of the font ids' families over either kind of store
+	enum class GroupForm : uint8_t { Packed, GlyfParts, NamedGlyf, NamedCommands, RangesGlyf, RangesCommands };
 	// device front-end: the buffers of one group of tasks (<= batch_blocks_ blocks, normally one font)
 	struct FeGroup {
 		size_t g0 = 0, g1 = 0;
 		std::vector<OSlice> slices;
-		std::vector<uint32_t> slice_ci, slice_cmd, slice_dat;
-		std::vector<uint32_t> slice_part, slice_byte; // glyf form: first part / first byte of every slice in the merged batch
+		std::vector<uint32_t> slice_ci;
 		MergedOutlines m;
 		std::vector<vgsdf_rect> rects;
 		std::vector<uint64_t> pbf_at;       // in-place assembly: position of every job's bitmap in `out`
@@ -407,8 +447,9 @@ private:
 		HostBuffer<uint8_t> out{true};
 		uint64_t out_bytes = 0, n_segs = 0;
 		uint32_t n_jobs = 0;
+		GroupForm form = GroupForm::Packed; // what fe_record made of the group
 		// a group submitted as code-point ranges of resident families (fe_record_ranges): range r is a task of the submission
-		bool by_ranges = false;
+		bool by_ranges() const { return form == GroupForm::RangesGlyf || form == GroupForm::RangesCommands; }
 		struct Ranges {
 			std::vector<const vgsdf_family *> families; // of the group's font ids, in task order
 			std::vector<const FamilyTable *> tables;    // ... and their host halves
@@ -429,18 +470,32 @@ private:
 		} ranges;
 	};
 	FeGroup fe_group_[2]; // two groups in flight: one on the GPU, one being recorded / encoded
-	// renderer / lane: whose device copies of the fonts a resident group names (nullptr: no resident form for this call)
+	// Records the group in the first form, of those the switches and the group's faces allow, that takes it (G.form).  renderer /
+	// lane: whose device copies of the fonts a group names (nullptr: no such form for this call); allow_glyf is false where a
+	// group the device has refused is recorded again: that fallback is the reader's, as ever
 	void fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf = true, const Renderer *renderer = nullptr, int lane = 0);
-	// false: a face of the group has no resident form or does not fit the renderer's budget — the glyf form takes the group
+	struct FormList { // the forms to try, in order
+		GroupForm form[6];
+		unsigned n = 0;
+	};
+	FormList fe_candidates(bool device_forms, bool glyf_forms, bool by_name, bool by_ranges) const;
+	// the one recorder of the forms that merge what the workers record slice by slice, and what differs between them
+	// (front_end_dispatch.cpp)
+	struct PackedForm;
+	struct GlyfForm;
+	struct NamedForm;
+	template <class Form> bool fe_record_slices(const std::vector<Todo> &tasks, FeGroup &G, Form form, double t0);
+	void fe_record_packed(const std::vector<Todo> &tasks, FeGroup &G);
+	bool fe_record_glyf(const std::vector<Todo> &tasks, FeGroup &G); // false: not a batch for the device's decoder (fan-out past 32-bit offsets)
+	// false: a face of the group has no store of the kind or does not fit the renderer's budget
 	// commands: against the faces' command stores (every readable face has one) instead of their glyf stores
-	bool fe_record_resident(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands = false);
-	// false: as above, or a family over the budget, or a block past code point 0xFFFF — the form that names glyphs takes the group
+	bool fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands);
+	// false: as above, or a family over the budget, or a block past code point 0xFFFF
 	bool fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands);
 	// the device family of a font id over its files' stores of one kind (nullptr: a file without such a store, or the budget)
 	const vgsdf_family *device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font, bool commands,
 	                                  const FamilyTable **table, RenderTimings &counts) const;
 	void fe_assemble_ranges(const std::vector<Todo> &tasks, FeGroup &G);
-	bool fe_record_glyf(const std::vector<Todo> &tasks, FeGroup &G); // false: not a batch for the device's decoder (fan-out past 32-bit offsets)
 	// fonts (by id) one of whose groups the device's glyf decoder refused (VGSDF_E_GLYF) or whose parts passed the batch bounds:
 	// later groups and runs record them with the host's reader at once instead of paying the double path again; cleared
 	// with the shard tables when a font is added

@@ -251,9 +251,8 @@ struct ResidentBatch {
 // order vgsdf.h names for a single-copy upload: scale | shift_x | cmd_off | dat_off | (pad to 8) | coords | kinds
 // (the offsets: ../upload_layout.h, which the device layer recognises the block by).
 struct MergedOutlines {
-	// which block layout the blob has, and so which view hands it to the device: view() / view_glyf() / view_resident()
-	enum class Form { Packed, Glyf, ResidentGlyf, ResidentCommands };
-	Form form = Form::Packed;
+	// (which layout the blob has, and so which of view() / view_glyf() / view_resident() hands it to the device, is the caller's
+	// to remember)
 	std::vector<GlyphJob> jobs;
 	HostBuffer<uint8_t> blob{true};
 	uint32_t n_jobs = 0;
@@ -275,9 +274,9 @@ struct MergedOutlines {
 	void layout_resident(uint32_t jobs_n, bool with_pbf, bool command_fonts = false)
 	{
 		if (command_fonts)
-			place_named(Form::ResidentCommands, jobs_n, vgsdf::CommandBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
+			place_named(jobs_n, vgsdf::CommandBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
 		else
-			place_named(Form::ResidentGlyf, jobs_n, vgsdf::ResidentBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
+			place_named(jobs_n, vgsdf::ResidentBlockLayout(jobs_n, fonts.size(), with_pbf), with_pbf);
 	}
 	vgsdf_outlines_resident view_resident() const
 	{
@@ -298,7 +297,7 @@ struct MergedOutlines {
 		n_parts = parts_n;
 		n_glyf_bytes = bytes_n; // (a multiple of 4: every part's bytes are padded)
 		const vgsdf::GlyfBlockLayout at(jobs_n, parts_n, bytes_n, with_pbf);
-		uint8_t *b = place_shared(Form::Glyf, jobs_n, at, with_pbf);
+		uint8_t *b = place_shared(jobs_n, at, with_pbf);
 		parts = reinterpret_cast<vgsdf_glyf_part *>(b + at.parts);
 		glyf_bytes = b + at.glyf_bytes;
 	}
@@ -320,7 +319,7 @@ struct MergedOutlines {
 	void layout(uint32_t jobs_n, uint32_t n_cmds, uint32_t n_floats, bool with_pbf = false)
 	{
 		const vgsdf::PackedBlockLayout at(jobs_n, n_cmds, n_floats, with_pbf);
-		uint8_t *b = place_shared(Form::Packed, jobs_n, at, with_pbf);
+		uint8_t *b = place_shared(jobs_n, at, with_pbf);
 		dat_off = reinterpret_cast<uint32_t *>(b + at.dat_off);
 		coords = reinterpret_cast<float *>(b + at.coords);
 		kinds = b + at.kinds;
@@ -343,9 +342,8 @@ struct MergedOutlines {
 private:
 	// The arrays every layout has — pbf_pre, pbf_fix, scale, shift_x, cmd_off — placed in a blob of the layout's size; the
 	// packed form's own arrays are cleared, and the caller adds those of its form.  Returns the blob
-	template <class Layout> uint8_t *place_shared(Form f, uint32_t jobs_n, const Layout &at, bool with_pbf)
+	template <class Layout> uint8_t *place_shared(uint32_t jobs_n, const Layout &at, bool with_pbf)
 	{
-		form = f;
 		n_jobs = jobs_n;
 		blob.ensure(at.bytes + 16);
 		uint8_t *b = blob.data();
@@ -359,9 +357,9 @@ private:
 		kinds = nullptr;
 		return b;
 	}
-	template <class Layout> void place_named(Form f, uint32_t jobs_n, const Layout &at, bool with_pbf)
+	template <class Layout> void place_named(uint32_t jobs_n, const Layout &at, bool with_pbf)
 	{
-		uint8_t *b = place_shared(f, jobs_n, at, with_pbf);
+		uint8_t *b = place_shared(jobs_n, at, with_pbf);
 		cmd_off = nullptr; // (the library sums the offsets itself)
 		glyph_id = reinterpret_cast<uint16_t *>(b + at.glyph_id);
 		font_of = reinterpret_cast<uint16_t *>(b + at.font_of);

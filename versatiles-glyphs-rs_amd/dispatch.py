@@ -1,6 +1,6 @@
 """One process per GPU (torchrun): sharding of the (font, block) task list, or of a font's glyphs, over the ranks.
 
-The library itself drives N devices from ONE process (Renderer.new_multi; csrc/host/font_manager.cpp,
+The library itself drives N devices from ONE process (Renderer.new_multi; csrc/host/lane_plan.cpp,
 render_glyphs_multi) — that is the form a host application links.  This module is the launcher-side plumbing for the
 one-process-per-GPU form the benchmark driver uses: the reference's unit of parallel work is the 256-code-point
 GlyphBlock (/root/reference/src/font/manager.rs:86-97,117-121); whole blocks need no exchange at all
