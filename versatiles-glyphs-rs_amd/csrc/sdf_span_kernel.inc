@@ -140,6 +140,12 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 
 	const uint32_t tid = threadIdx.x, lane = threadIdx.x & 63;
 	const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // wave-uniform: addresses of the per-wave LDS rows stay scalar
+	// The 64-pixel quarters of a tile go to the waves rotated by `rot` (0..3, a hash of the workgroup's index): wave wv takes
+	// the pixels from pw of every tile, in the sweep and in the final stores.  Only a glyph's last tile is partial and its
+	// empty quarters are the last ones, so unrotated the waves with the high numbers sweep less than wave 0 in every
+	// workgroup (tools/model_wave_shares.py).  Whatever is indexed by tid (the stage's records, st_ub2, st_byte) stays put.
+	const uint32_t rot = wave_rot(blockIdx.x);
+	const uint32_t pw = ((wv + rot) & 3u) * 64u;
 	const uint32_t tile = xcd_remap(blockIdx.x, n_tiles);
 	const uint2 t = tiles[tile];
 	const GlyphDesc g = glyphs[t.x];
@@ -359,9 +365,9 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// compiler barrier: keeps the (loop-invariant, wave-uniform) group-bound loads inside the loop
 			// instead of parking 96 VGPRs of them across it
 			asm volatile("" ::: "memory");
-			const uint32_t o = p0 + k * TPB + tid;
+			const uint32_t o = p0 + k * TPB + pw + lane;
 			// a wave whose 64 pixels all lie past the end of the bitmap (last tile of the glyph) has nothing to do
-			if (p0 + k * TPB + (tid & ~63u) >= npix)
+			if (p0 + k * TPB + pw >= npix)
 				continue;
 			const uint32_t oc = o < npix ? o : npix - 1;
 			const uint32_t row = oc / g.w;
@@ -684,7 +690,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	}
 	__syncthreads();
 	for (uint32_t k = 0; k < T; k++) {
-		const uint32_t o = p0 + k * TPB + tid;
+		const uint32_t o = p0 + k * TPB + pw + lane;
 		if (o < npix) {
 			const uint32_t row = o / g.w;
 			const uint32_t x = o - row * g.w;

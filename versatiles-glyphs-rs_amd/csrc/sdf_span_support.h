@@ -122,4 +122,14 @@ __device__ __forceinline__ float sc_filter(float rpx, float rpy, float vx, float
 
 constexpr uint32_t SPAN_TILES = 4; // tiles a workgroup of the default kernel sweeps per staged chunk
 
+// The rotation of workgroup b (sdf_span_kernel.inc: wave wv takes the 64-pixel quarter (wv + rot) & 3 of every tile): 0..3,
+// wave-uniform, scalar arithmetic only.  The top two bits of a multiplicative hash: workgroups are dealt round-robin
+// over the 8 XCDs and then over an XCD's CUs, so the workgroups that share a CU have equal low bits of b.
+// tools/model_wave_shares.py restates this function and checks what it does to the three font batches.
+constexpr uint32_t WAVE_ROT_MUL = 0x13C6EF37u;
+__device__ __forceinline__ uint32_t wave_rot(uint32_t b)
+{
+	return (b * WAVE_ROT_MUL) >> 30;
+}
+
 } // namespace vgsdf
