@@ -140,11 +140,13 @@ typedef struct {
 	uint64_t block_bytes;    /* bytes of those submissions' upload blocks */
 } vg_command_stats;
 int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out);
-/* Charstrings on the device, 0 (default) / 1.  With 1, wherever the renderer would build the command store of a `CFF ` version 1
+/* Charstrings on the device, 0 (default) / 1 / 2.  With 1, wherever the renderer would build the command store of a `CFF ` version 1
  * face — modes 1 and 2 above, vg_renderer_preload_fonts, families — the DEVICE interprets the face's charstrings
  * (vgsdf_font_create_charstrings) instead of the host's reader; the host only resolves the INDEX offsets.  A face the device
  * refuses (a seac glyph, a glyph past VGSDF_CHARSTRING_MAX_TOKENS, a store past the bounds) gets its store from the host reader as with 0.  Same
- * registry, same budget, same store bytes and same output either way.  CFF2 and `glyf` faces are not affected.
+ * registry, same budget, same store bytes and same output either way.  With 1, CFF2 and `glyf` faces are not affected.  With 2,
+ * everything 1 does, and CFF2 faces likewise through vgsdf_font_create_charstrings2, with the blend factors of the host reader
+ * (the default position of the design space); same fallback, same stats.  `glyf` faces are not affected.  Any other non-zero value: 1.
  * vg_manager_charstring_stats: of the last render; the decoded stores count among vg_command_stats.fonts_uploaded too. */
 void vg_manager_set_charstrings_on_device(vg_manager *m, int on);
 typedef struct {
@@ -319,6 +321,11 @@ int vg_manager_command_font_desc(const vg_manager *m, const char *font_id, int f
  * as long as the manager holds the font.  -1: unknown font / file, a face with `glyf` outlines, a CFF2 face, or a `CFF ` table whose
  * INDEX entries do not ascend inside their data. */
 int vg_manager_charstring_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings_desc *desc);
+/* The same of a CFF2 face for vgsdf_font_create_charstrings2: INDEX counts read as 32 bits, the one set of local subroutines the
+ * reader uses for every glyph, and the blend sets — one per ItemVariationData of the variation store, with its usable flag and the
+ * factors the reader multiplies `blend` deltas by (the default position).  -1: unknown font / file, anything that is not CFF2, an
+ * INDEX whose entries do not ascend inside their data, or a set of more than 65535 subroutines. */
+int vg_manager_charstring2_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings2_desc *desc);
 vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, const char *font_id);
 
 /* The host half of a resident family (vgsdf_family_create / vgsdf_outlines_submit_ranges), no device needed: for every code

@@ -350,7 +350,7 @@ int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, v
  *   - a glyph that executes more than VGSDF_CHARSTRING_MAX_TOKENS tokens, operands and operators alike (ten nested calls of
  *     fan-out k are k^10 tokens: the bound keeps a crafted font from holding the device; real glyphs stay below a few thousand);
  *   - a store or coordinates past the bounds vgsdf_font_create_commands states.
- * CFF2 is not offered to this entry point.
+ * A `CFF2` face goes to vgsdf_font_create_charstrings2 below.
  */
 #define VGSDF_CHARSTRING_MAX_TOKENS (1u << 20)
 typedef struct {
@@ -371,7 +371,38 @@ int vgsdf_font_create_charstrings(vgsdf_ctx *ctx, const vgsdf_font_charstrings_d
  * that exceeds max_store_bytes the call returns VGSDF_OK with *out = NULL and nothing allocated.  Refusals as above. */
 int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, uint64_t max_store_bytes,
                                          vgsdf_font **out, uint64_t *store_bytes);
-/* test / inspection (tools/charstrings_ab.py): milliseconds the count and the emit kernel of the context's last vgsdf_font_create_charstrings took (HIP events; 0 0 before
+/*
+ * The same for a `CFF2` face: the device interprets its charstrings by the rules of the host reader's CFF2 mode (no width operand,
+ * an operand stack of 513, `return` and `endchar` fail the glyph, a glyph ends with its data and its last contour is not closed,
+ * `vsindex` and `blend`), and equals its callbacks bit for bit.  The description is the one above with n_fds == 1 and fd_of == NULL
+ * (one set of local subroutines serves every glyph) plus the BLEND SETS, one per ItemVariationData of the face's variation store:
+ *   n_sets     their count; 0 is legal: no glyph has an outline (set 0 is selected before a glyph's first operator, and a glyph
+ *              whose selected set does not exist or is not usable delivers nothing from there on)
+ *   set_ok     one byte per set, 0 = not usable
+ *   set_off    set s owns factors[set_off[s] .. set_off[s + 1]), one factor per region (set_off[0] = 0)
+ *   factors    f32; `blend` adds to each of its values delta x factor for every region, last region first, one product and one
+ *              sum per delta in f32
+ * The factors are plain data: the entry point neither knows nor checks which position of the design space they stand for (the
+ * host reader's are those of the default position).  Validated on the host before anything runs, VGSDF_E_ARG otherwise: all the
+ * above validates, n_fds == 1, fd_of == NULL, at most 65536 sets, set_off ascending from 0 and ending at or below n_factors, at
+ * most 64 factors per set, every factor finite.  Count pass, store, emit pass, refusals (no seac form exists in CFF2), budget
+ * form, result and vgsdf_font_device_bytes are those of vgsdf_font_create_charstrings.  The passes run in launches of at most
+ * 16384 glyph ids; operand slots past the first 48 live in a workspace the CONTEXT owns (at most 465 x 4 x 16384 bytes, grown on
+ * demand, freed with the context, not counted by vgsdf_font_device_bytes).
+ */
+typedef struct {
+	vgsdf_font_charstrings_desc charstrings; /* n_fds == 1, fd_of == NULL */
+	uint32_t n_sets;                         /* <= 65536 */
+	uint32_t n_factors;
+	const uint8_t *set_ok;                   /* [n_sets] (may be NULL when n_sets == 0) */
+	const uint32_t *set_off;                 /* [n_sets + 1] (may be NULL when n_sets == 0) */
+	const float *factors;                    /* [n_factors] (may be NULL when n_factors == 0) */
+} vgsdf_font_charstrings2_desc;
+int vgsdf_font_create_charstrings2(vgsdf_ctx *ctx, const vgsdf_font_charstrings2_desc *in, vgsdf_font **out);
+int vgsdf_font_create_charstrings2_within(vgsdf_ctx *ctx, const vgsdf_font_charstrings2_desc *in, uint64_t max_store_bytes,
+                                          vgsdf_font **out, uint64_t *store_bytes);
+/* test / inspection (tools/charstrings_ab.py): milliseconds the count and the emit pass of the context's last
+ * vgsdf_font_create_charstrings or vgsdf_font_create_charstrings2 took (HIP events around the pass, all its launches; 0 0 before
  * the first, and for a pass that did not run) */
 void vgsdf_font_charstrings_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
 /* test / inspection: download a command font's store.  *n_glyph_ids / *n_cmds: its counts (either may be NULL); cmd_off

@@ -1,6 +1,7 @@
-// charstring_kernels.hip — Type 2 charstrings (`CFF ` version 1) decoded on the device: the operator set and the rules of
-// host/cff.cpp's CharStringRun, restated for one lane per glyph id.  The host reader is the statement of behaviour; what this
-// kernel delivers equals its callbacks bit for bit (f32, one addition per coordinate in operand order, -ffp-contract=off).
+// charstring_kernels.hip — Type 2 charstrings (`CFF ` version 1, and `CFF2` with its `vsindex` / `blend`) decoded on the device:
+// the operator set and the rules of host/cff.cpp's CharStringRun, restated for one lane per glyph id.  The host reader is the
+// statement of behaviour; what this kernel delivers equals its callbacks bit for bit (f32, one addition per coordinate in
+// operand order, -ffp-contract=off).
 //
 // A charstring is sequential (variable-length tokens, a hintmask whose length depends on the stems counted so far,
 // subroutine calls), so a lane walks one glyph id's program from its first byte to its end.  The walk runs twice from one
@@ -13,6 +14,15 @@
 // subroutine index is checked against its set's count after the bias; every stack index against its limit.  Termination
 // does not depend on the font: a glyph executes at most VGSDF_CHARSTRING_MAX_TOKENS tokens (ten call levels of fan-out k are
 // k^10 of them), then sets CS_FLAG_BUDGET and stops.
+//
+// The CFF2 stamping (second template parameter) is the same text with CharStringRun's cff2 rules: no width operand, `return` and
+// `endchar` fail the glyph, a mask past the end ends the stream, the glyph ends with its data, `vsindex` selects a set of blend
+// factors and `blend` folds each value's deltas into it (f32, one product and one sum per delta, in the host's order).  The
+// factors are data in device memory: a position in the design space is another array, not another kernel.  Its operand stack
+// holds 513 values: the first kCharstringWindow slots are the LDS array of the version 1 stamping (the same LDS per workgroup,
+// the same waves per SIMD), slots past it live in a global workspace laid out like the LDS array, [slot - window][lane of the
+// launch], so the lanes of a wave at one depth touch consecutive words.  Every workspace index is below
+// (513 - window) x spill_stride, which the launch allocates.
 #include "charstring_kernels.h"
 
 #include "../../include/vgsdf.h"
@@ -21,10 +31,14 @@
 
 namespace {
 
+using vgsdf::Charstrings2Ref;
 using vgsdf::CharstringsRef;
 
 constexpr int kLanes = 64;
 constexpr int kMaxOperands = vg::kCharstringMaxOperands;
+constexpr int kMaxOperands2 = vg::kCharstringMaxOperands2;
+constexpr int kWindow = vg::kCharstringWindow; // slots of the operand stack in LDS (every slot of the version 1 stamping)
+static_assert(kWindow == kMaxOperands, "the version 1 stamping keeps its whole stack in the LDS window");
 constexpr int kMaxDepth = vg::kCharstringMaxDepth;
 constexpr uint32_t kMaxTokens = VGSDF_CHARSTRING_MAX_TOKENS;
 
@@ -84,17 +98,48 @@ template <bool EMIT> struct Sink {
 	__device__ void close() { (void)take(vgsdf::CMD_CLOSE, 0); }
 };
 
-template <bool EMIT>
-__global__ __launch_bounds__(kLanes) void charstring_decode(const CharstringsRef face, uint32_t *__restrict__ counts,
+template <bool CFF2> struct FaceOf {
+	using type = CharstringsRef;
+};
+template <> struct FaceOf<true> {
+	using type = Charstrings2Ref;
+};
+
+template <bool EMIT, bool CFF2>
+__global__ __launch_bounds__(kLanes) void charstring_decode(const typename FaceOf<CFF2>::type face, uint32_t *__restrict__ counts,
                                                              const uint32_t *__restrict__ cmd_off, const uint32_t *__restrict__ dat_off,
                                                              uint8_t *__restrict__ kinds, float *__restrict__ coords, uint32_t *flags)
 {
-	__shared__ float stack_lds[kMaxOperands][kLanes];
+	__shared__ float stack_lds[kWindow][kLanes];
 	__shared__ uint32_t ret_pos[kMaxDepth][kLanes], ret_end[kMaxDepth][kLanes];
 	const uint32_t lane = threadIdx.x, gid = blockIdx.x * kLanes + lane;
 	if (gid >= face.n_glyph_ids)
 		return; // (no barrier below: a lane's slots of the stacks are its own)
-#define STK(i) stack_lds[i][lane]
+	// the operand stack: slot i of this lane (CFF2: past the window, the launch's workspace)
+	float *spill = nullptr;
+	uint32_t spill_stride = 0;
+	if constexpr (CFF2) {
+		spill = face.spill + (blockIdx.x * kLanes + lane);
+		spill_stride = face.spill_stride;
+	}
+	auto stk = [&](int i) -> float {
+		if constexpr (CFF2) {
+			if (i >= kWindow)
+				return spill[(size_t)(i - kWindow) * spill_stride];
+		}
+		return stack_lds[i][lane];
+	};
+	auto stk_put = [&](int i, float v) {
+		if constexpr (CFF2) {
+			if (i >= kWindow) {
+				spill[(size_t)(i - kWindow) * spill_stride] = v;
+				return;
+			}
+		}
+		stack_lds[i][lane] = v;
+	};
+#define STK(i) stk(i)
+	constexpr int kCap = CFF2 ? kMaxOperands2 : kMaxOperands;
 
 	Sink<EMIT> out;
 	if (EMIT) {
@@ -106,12 +151,31 @@ __global__ __launch_bounds__(kLanes) void charstring_decode(const CharstringsRef
 	}
 	ByteReader cs{face.words};
 	uint32_t pos = face.cs_off[gid], end = face.cs_off[gid + 1];
-	const uint32_t fd = face.fd_of ? face.fd_of[gid] : 0u;
+	uint32_t fd = 0u; // (CFF2: one set of local subroutines serves every glyph)
+	if constexpr (!CFF2)
+		fd = face.fd_of ? face.fd_of[gid] : 0u;
 	const uint32_t local_first = face.lsubr_first[fd], n_local = face.lsubr_first[fd + 1] - local_first;
 	int sp = 0, depth = 0;
 	float x = 0.0f, y = 0.0f;
-	bool has_move_to = false, first_move_to = true, have_width = false, has_endchar = false;
+	bool has_move_to = false, first_move_to = true, have_width = CFF2, has_endchar = false;
 	uint32_t stems = 0, tokens = 0, raised = 0;
+	// CFF2: the factors of the selected set ([n_regions] at `factors`), `vsindex` / `blend` bookkeeping
+	const float *factors = nullptr;
+	uint32_t n_regions = 0;
+	auto select_set = [&](uint32_t set) {
+		if constexpr (CFF2) {
+			factors = face.factors + face.set_off[set];
+			n_regions = face.set_off[set + 1] - face.set_off[set];
+		}
+	};
+	bool had_vsindex = false, had_blend = false;
+	if constexpr (CFF2) {
+		// set 0 is selected before the first operator: without it the glyph delivers nothing
+		if (face.n_sets == 0 || !face.set_ok[0])
+			pos = end;
+		else
+			select_set(0);
+	}
 
 	for (;;) {
 		if (pos >= end) { // the stream ends: the subroutine (or the charstring) returns
@@ -155,13 +219,52 @@ __global__ __launch_bounds__(kLanes) void charstring_decode(const CharstringsRef
 				v = (float)(int32_t)((b0 << 24) | (b1 << 16) | (b2 << 8) | b3) / 65536.0f;
 				pos += 4;
 			}
-			if (sp >= kMaxOperands)
+			if (sp >= kCap)
 				break;
-			STK(sp) = v;
+			stk_put(sp, v);
 			sp++;
 			continue;
 		}
 		bool ok = true; // false: the charstring fails here (the callbacks delivered so far stay)
+		if constexpr (CFF2) {
+			if (op == 15) { // vsindex: |- ivs vsindex |- , once and before the first blend
+				if (had_blend || had_vsindex || sp != 1)
+					break;
+				const float v = STK(0);
+				if (!(v >= 0.0f && v <= 65535.0f))
+					break;
+				const uint32_t set = (uint32_t)v;
+				if (set >= face.n_sets || !face.set_ok[set])
+					break;
+				select_set(set);
+				had_vsindex = true;
+				sp = 0;
+				continue;
+			}
+			if (op == 16) { // blend: n values, then their k deltas each, then n; the values stay, each moved by its deltas
+				if (sp == 0)
+					break;
+				had_blend = true;
+				const float fn = STK(--sp);
+				if (!(fn >= 0.0f && fn <= 65535.0f))
+					break;
+				const uint32_t n = (uint32_t)fn, k = n_regions; // (n (k + 1) <= 65535 x 65: no overflow)
+				const uint32_t len = n * (k + 1);
+				if ((uint32_t)sp < len)
+					break;
+				const int start = sp - (int)len;
+				// popped from the top: value n - 1 first, each with its last region's delta first (one product and one sum each)
+				for (uint32_t i = n; i-- > 0;) {
+					float v = STK(start + (int)i);
+					for (uint32_t j = 0; j < k; j++) {
+						const float delta = STK(--sp);
+						v += delta * factors[k - j - 1];
+					}
+					stk_put(start + (int)i, v);
+				}
+				continue;
+			}
+		}
 		switch (op) {
 		case 1:  // hstem
 		case 3:  // vstem
@@ -188,9 +291,12 @@ __global__ __launch_bounds__(kLanes) void charstring_decode(const CharstringsRef
 			}
 			stems += (uint32_t)len >> 1; // an implied vstem
 			const uint32_t mask = (stems + 7) >> 3;
-			if (mask > end - pos)
-				ok = false;
-			else
+			if (mask > end - pos) {
+				if constexpr (CFF2)
+					pos = end; // (the stream simply ends; there is no endchar to miss)
+				else
+					ok = false;
+			} else
 				pos += mask;
 			break;
 		}
@@ -398,9 +504,16 @@ __global__ __launch_bounds__(kLanes) void charstring_decode(const CharstringsRef
 			break;
 		}
 		case 11: // return
-			pos = end;
+			if constexpr (CFF2)
+				ok = false; // (not an operator of CFF2: a subroutine ends with its data)
+			else
+				pos = end;
 			break;
 		case 14: // endchar
+			if constexpr (CFF2) {
+				ok = false;
+				break;
+			}
 			if (sp == 4 || (!have_width && sp == 5)) { // the seac form: the charset and two further charstrings — the host's
 				raised |= vgsdf::CS_FLAG_SEAC;
 				ok = false;
@@ -493,7 +606,7 @@ __global__ __launch_bounds__(kLanes) void charstring_decode(const CharstringsRef
 			break;
 		}
 		default:
-			ok = false; // 0, 2, 9, 13, 15, 16, 17: reserved
+			ok = false; // 0, 2, 9, 13, 17 (and 15, 16 outside CFF2): reserved
 			break;
 		}
 		if (!ok)
@@ -514,12 +627,16 @@ __global__ __launch_bounds__(kLanes) void charstring_decode(const CharstringsRef
 
 } // namespace
 
+namespace {
+uint32_t groups_of(const CharstringsRef &face) { return (face.n_glyph_ids + kLanes - 1) / kLanes; }
+} // namespace
+
 extern "C" {
 
 int vgsdf_charstring_count(const CharstringsRef *face, uint32_t *counts, uint32_t *flags, hipStream_t stream)
 {
 	const uint32_t groups = (face->n_glyph_ids + kLanes - 1) / kLanes;
-	hipLaunchKernelGGL(charstring_decode<false>, dim3(groups), dim3(kLanes), 0, stream, *face, counts, nullptr, nullptr, nullptr, nullptr, flags);
+	hipLaunchKernelGGL((charstring_decode<false, false>), dim3(groups), dim3(kLanes), 0, stream, *face, counts, nullptr, nullptr, nullptr, nullptr, flags);
 	return (int)hipGetLastError();
 }
 
@@ -527,7 +644,26 @@ int vgsdf_charstring_emit(const CharstringsRef *face, const uint32_t *cmd_off, c
                           uint32_t *flags, hipStream_t stream)
 {
 	const uint32_t groups = (face->n_glyph_ids + kLanes - 1) / kLanes;
-	hipLaunchKernelGGL(charstring_decode<true>, dim3(groups), dim3(kLanes), 0, stream, *face, nullptr, cmd_off, dat_off, kinds, coords, flags);
+	hipLaunchKernelGGL((charstring_decode<true, false>), dim3(groups), dim3(kLanes), 0, stream, *face, nullptr, cmd_off, dat_off, kinds, coords, flags);
+	return (int)hipGetLastError();
+}
+
+int vgsdf_charstring2_count(const Charstrings2Ref *face, uint32_t *counts, uint32_t *flags, hipStream_t stream)
+{
+	if (face->spill_stride < groups_of(*face) * kLanes)
+		return (int)hipErrorInvalidValue;
+	hipLaunchKernelGGL((charstring_decode<false, true>), dim3(groups_of(*face)), dim3(kLanes), 0, stream, *face, counts, nullptr, nullptr,
+	                   nullptr, nullptr, flags);
+	return (int)hipGetLastError();
+}
+
+int vgsdf_charstring2_emit(const Charstrings2Ref *face, const uint32_t *cmd_off, const uint32_t *dat_off, uint8_t *kinds, float *coords,
+                           uint32_t *flags, hipStream_t stream)
+{
+	if (face->spill_stride < groups_of(*face) * kLanes)
+		return (int)hipErrorInvalidValue;
+	hipLaunchKernelGGL((charstring_decode<true, true>), dim3(groups_of(*face)), dim3(kLanes), 0, stream, *face, nullptr, cmd_off, dat_off,
+	                   kinds, coords, flags);
 	return (int)hipGetLastError();
 }
 }

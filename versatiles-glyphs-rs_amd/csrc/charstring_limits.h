@@ -7,6 +7,9 @@
 namespace vg {
 
 constexpr int kCharstringMaxOperands = 48; // ttf-parser: MAX_ARGUMENTS_STACK_LEN of cff1
+constexpr int kCharstringMaxOperands2 = 513; // ttf-parser: MAX_ARGUMENTS_STACK_LEN of cff2
+constexpr int kCharstringWindow = 48; // device: slots of the operand stack kept in LDS; CFF2's further slots live in global memory
+constexpr int kCharstringMaxRegions = 64; // ttf-parser: scalars of one ItemVariationData (cff2), the factors of one blend set
 constexpr int kCharstringMaxDepth = 10;    // ttf-parser: STACK_LIMIT (nested subroutine calls)
 // Technical Note #5176, section 16: the bias added to a subroutine operand, by the number of subroutines of the set
 constexpr uint32_t charstring_subr_bias(uint32_t n) { return n < 1240 ? 107 : (n < 33900 ? 1131 : 32768); }

@@ -59,7 +59,11 @@ struct vgsdf_ctx {
 	uint64_t counters[3] = {0, 0, 0};
 	uint64_t *d_counters = nullptr;
 	void *comm = nullptr; // ncclComm_t of the communicator this context last reduced in (owned by run_counters.cpp's cache)
-	float charstring_ms[2] = {0.0f, 0.0f}; // count / emit kernel of the last vgsdf_font_create_charstrings (resident_fonts.cpp)
+	float charstring_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_font_create_charstrings / _charstrings2 (resident_fonts.cpp)
+	// vgsdf_font_create_charstrings2: operand slots past the decoder's LDS window, for one launch (at most 16384 glyph ids); grows
+	// to exactly what the largest launch so far needed and belongs to no font
+	void *charstring_spill = nullptr;
+	size_t charstring_spill_bytes = 0;
 	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
 };
 

@@ -157,7 +157,7 @@ int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out)
 	*out = vg_command_stats{t.command_groups, t.command_fonts_uploaded, t.command_font_bytes, t.command_block_bytes};
 	return 0;
 }
-void vg_manager_set_charstrings_on_device(vg_manager *m, int on) { m->m.set_charstrings_on_device(on != 0); }
+void vg_manager_set_charstrings_on_device(vg_manager *m, int on) { m->m.set_charstrings_on_device(on == 2 ? 2 : (on != 0 ? 1 : 0)); }
 int vg_manager_charstring_stats(const vg_manager *m, vg_charstring_stats *out)
 {
 	const vg::RenderTimings &t = m->m.last_timings();
@@ -727,6 +727,37 @@ int vg_manager_charstring_font_desc(const vg_manager *m, const char *font_id, in
 		desc->lsubr_first = t->lsubr_first.data();
 		desc->lsubr_off = t->lsubr_off.data();
 		desc->fd_of = t->fd_of.empty() ? nullptr : t->fd_of.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_charstring2_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings2_desc *desc)
+{
+	try {
+		std::string err;
+		const vg::CharstringTable *t = file_index < 0 || !m || !font_id ? nullptr : m->m.charstring2_table(font_id, (size_t)file_index, &err);
+		if (!t || !desc) {
+			g_err = err.empty() ? "vg_manager_charstring2_font_desc: bad argument" : err;
+			return -1;
+		}
+		vgsdf_font_charstrings_desc &cs = desc->charstrings;
+		cs.n_glyph_ids = (uint32_t)t->cs_off.size() - 1;
+		cs.n_bytes = (uint32_t)t->bytes.size();
+		cs.bytes = t->bytes.data();
+		cs.cs_off = t->cs_off.data();
+		cs.n_gsubrs = (uint32_t)t->gsubr_off.size() - 1;
+		cs.gsubr_off = t->gsubr_off.data();
+		cs.n_fds = t->n_fds;
+		cs.lsubr_first = t->lsubr_first.data();
+		cs.lsubr_off = t->lsubr_off.data();
+		cs.fd_of = nullptr;
+		desc->n_sets = (uint32_t)t->set_ok.size();
+		desc->n_factors = (uint32_t)t->factors.size();
+		desc->set_ok = t->set_ok.data();
+		desc->set_off = t->set_off.data();
+		desc->factors = t->factors.data();
 		return 0;
 	} catch (const std::exception &e) {
 		g_err = e.what();

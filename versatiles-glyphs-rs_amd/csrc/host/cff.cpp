@@ -12,8 +12,8 @@ namespace vg {
 namespace {
 
 constexpr int kMaxOperands = kCharstringMaxOperands; // (shared with the device's decoder: charstring_limits.h)
-constexpr int kMaxOperands2 = 513; // ... of cff2
-constexpr size_t kMaxRegions = 64; // ttf-parser: scalars of one ItemVariationData (cff2)
+constexpr int kMaxOperands2 = kCharstringMaxOperands2; // ... of cff2
+constexpr size_t kMaxRegions = kCharstringMaxRegions;
 constexpr int kMaxDepth = kCharstringMaxDepth;
 
 // DICT data (Technical Note #5176, section 4): operands followed by an operator
@@ -412,8 +412,10 @@ const CffTable::Index *CffTable::local_subrs_for(uint16_t gid) const
 
 bool CffTable::charstring_table(uint32_t n_glyph_ids, CharstringTable &out) const
 {
-	if (cff2_ || n_glyph_ids == 0 || n_glyph_ids > 0x10000u)
+	if (n_glyph_ids == 0 || n_glyph_ids > 0x10000u)
 		return false;
+	if (cff2_ && (private_.local_subrs.count > 0xFFFFu || global_subrs_.count > 0xFFFFu))
+		return false; // (card32 counts: such a face goes the host's way)
 	constexpr size_t kMaxBytes = 0xFFFFFFF0u;
 	// entries [0, count) of an INDEX behind `off` (which ends with the store's size so far), as Index::get checks them
 	auto append = [&](const Index &ix, std::vector<uint32_t> &off) {
@@ -472,6 +474,15 @@ bool CffTable::charstring_table(uint32_t n_glyph_ids, CharstringTable &out) cons
 	if (out.n_fds == 1)
 		out.fd_of.clear();
 	out.bytes.resize((out.bytes.size() + 3) & ~(size_t)3, 0);
+	out.cff2 = cff2_;
+	out.set_ok.clear();
+	out.factors.clear();
+	out.set_off.assign(1, 0);
+	for (const BlendSet &set : blend_sets_) {
+		out.set_ok.push_back(set.ok ? 1 : 0);
+		out.factors.insert(out.factors.end(), set.scalars.begin(), set.scalars.end());
+		out.set_off.push_back((uint32_t)out.factors.size());
+	}
 	return true;
 }
 

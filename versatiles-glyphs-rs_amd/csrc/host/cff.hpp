@@ -45,9 +45,11 @@ public:
 	bool outline(uint16_t glyph_id, OutlineBuilder &builder) const;
 	// The charstrings and subroutines of the face as the device's decoder takes them (CharstringTable of ttf_face.hpp), from the
 	// tables parse() has located: every body copied once, every INDEX offset resolved and checked.  false (nothing of `out` is
-	// to be used): CFF2, an INDEX entry that does not ascend or leaves its data, or 256 Font DICTs in use AND a glyph without one
+	// to be used): an INDEX entry that does not ascend or leaves its data, or 256 Font DICTs in use AND a glyph without one
 	// (Font DICTs past the 256 an FDSelect byte can name are left out; a glyph without Font DICT gets an empty set behind the font's own).
 	// n_glyph_ids = the face's numGlyphs: glyph ids past the CharStrings INDEX get an empty charstring (no outline, as outline())
+	// A CFF2 table: the one set of local subroutines parse2() picked (false past 65535 of them or of the global ones: the device's
+	// description cannot state such a set), and every blend set with its ok flag and its factors as the reader uses them.
 	bool charstring_table(uint32_t n_glyph_ids, CharstringTable &out) const;
 
 private:

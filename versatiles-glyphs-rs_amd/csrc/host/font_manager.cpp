@@ -560,6 +560,11 @@ const CharstringTable *FontManager::charstring_table(const std::string &font_id,
 	                  "the file has no `CFF ` version 1 charstrings the device's decoder could be given", err);
 }
 
+const CharstringTable *FontManager::charstring2_table(const std::string &font_id, size_t file_index, std::string *err) const
+{
+	return file_table(font_id, file_index, &Face::charstring2_table, "the file has no `CFF2` charstrings the device's decoder could be given", err);
+}
+
 const FontManager::FamilyTable *FontManager::family_table(const std::string &font_id, std::string *err) const
 {
 	const FontEntry *it = find_font(font_id, err);

@@ -271,8 +271,10 @@ public:
 	void set_resident_commands(int mode) { resident_commands_ = mode < 0 || mode > 2 ? 0 : mode; }
 	// Command stores of `CFF ` version 1 faces decoded on the device from the charstrings (vgsdf_font_create_charstrings) instead
 	// of uploaded from command_table(); a face the device refuses falls back.  Default off.  The stores' bytes are the same.
-	void set_charstrings_on_device(bool on) { charstrings_on_device_ = on; }
+	// 2: CFF2 faces too (vgsdf_font_create_charstrings2, with the reader's blend factors: the default position).
+	void set_charstrings_on_device(int mode) { charstrings_on_device_ = mode < 0 || mode > 2 ? 0 : mode; }
 	const CharstringTable *charstring_table(const std::string &font_id, size_t file_index, std::string *err) const;
+	const CharstringTable *charstring2_table(const std::string &font_id, size_t file_index, std::string *err) const;
 	// what the last preload_resident_fonts built: its uploads are counted here, not in the timings of a render
 	const RenderTimings &last_preload_counts() const { return preload_counts_; }
 	// Resident families (default off): a group that would be recorded glyph by glyph against resident fonts or command stores
@@ -516,7 +518,7 @@ private:
 	bool glyf_on_device_ = glyf_on_device_default(); // glyf fonts: the device decodes the glyphs' arrays (VG_GLYF_ON_DEVICE=0 / set_glyf_on_device(false): the host does)
 	bool resident_fonts_ = false;
 	int resident_commands_ = 0;
-	bool charstrings_on_device_ = false;
+	int charstrings_on_device_ = 0;
 	mutable RenderTimings preload_counts_;
 	// a face's command store on the renderer's device, by either path; counts into `counts`
 	const vgsdf_font *command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;

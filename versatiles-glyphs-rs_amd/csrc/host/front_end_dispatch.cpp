@@ -296,9 +296,13 @@ const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane,
 {
 	uint64_t uploaded = 0;
 	const vgsdf_font *f = nullptr;
-	if (charstrings_on_device_ && face.charstring_table().ok) {
+	// (1: `CFF ` version 1 faces; 2: CFF2 faces as well)
+	const CharstringTable *cs = charstrings_on_device_ >= 1 && face.charstring_table().ok ? &face.charstring_table() : nullptr;
+	if (!cs && charstrings_on_device_ >= 2 && face.charstring2_table().ok)
+		cs = &face.charstring2_table();
+	if (cs) {
 		bool refused = false, over_budget = false;
-		f = renderer.charstring_font(lane, face.charstring_table(), &uploaded, &refused, &over_budget);
+		f = renderer.charstring_font(lane, *cs, &uploaded, &refused, &over_budget);
 		if (refused)
 			counts.charstring_fallbacks++;
 		if (over_budget)

@@ -527,7 +527,13 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 			*over_budget = true;
 		return nullptr;
 	}
-	vgsdf_font_charstrings_desc d;
+	vgsdf_font_charstrings2_desc d2{};
+	vgsdf_font_charstrings_desc &d = d2.charstrings;
+	d2.n_sets = (uint32_t)t.set_ok.size();
+	d2.n_factors = (uint32_t)t.factors.size();
+	d2.set_ok = t.set_ok.data();
+	d2.set_off = t.set_off.data();
+	d2.factors = t.factors.data();
 	d.n_glyph_ids = (uint32_t)t.cs_off.size() - 1;
 	d.n_bytes = (uint32_t)t.bytes.size();
 	d.bytes = t.bytes.data();
@@ -545,7 +551,7 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 		// anything of the store is allocated
 		uint64_t want = 0;
 		std::lock_guard<std::mutex> lock(mu_);
-		const int rc = vgsdf_font_create_charstrings_within(c, &d, room, &f, &want);
+		const int rc = t.cff2 ? vgsdf_font_create_charstrings2_within(c, &d2, room, &f, &want) : vgsdf_font_create_charstrings_within(c, &d, room, &f, &want);
 		if (rc == VGSDF_E_GLYF) {
 			rf.refused_charstrings.insert(key);
 			if (refused)

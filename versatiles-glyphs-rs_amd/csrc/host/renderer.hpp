@@ -461,7 +461,8 @@ public:
 	// the same for the command store of a face (vgsdf_font_create_commands): same registry (the tables' serials come from one
 	// sequence), same budget, no eviction.  nullptr: no command table, or over the budget — the caller goes on as without
 	const vgsdf_font *command_font(int lane, const CommandTable &table, uint64_t *uploaded_bytes = nullptr) const;
-	// the same store made on the device from a `CFF ` face's charstrings (vgsdf_font_create_charstrings): the key is the face's
+	// the same store made on the device from a `CFF ` face's charstrings (vgsdf_font_create_charstrings) or, for a table with
+	// cff2 set, from a `CFF2` face's and its blend sets (vgsdf_font_create_charstrings2): the key is the face's
 	// command serial, so whichever of the two calls comes first makes the store and the other finds it.  nullptr: no charstring
 	// table; the device refused the face (*refused is set then, once per face and device: a seac glyph, a glyph past the token
 	// budget, a store past the bounds) and the caller takes command_font(), which needs the host's table; or the store would

@@ -1102,6 +1102,23 @@ const CharstringTable &Face::charstring_table() const
 	return cell.charstrings;
 }
 
+const CharstringTable &Face::charstring2_table() const
+{
+	CommandCell &cell = *commands_;
+	std::call_once(cell.charstrings2_once, [&] {
+		CharstringTable &t = cell.charstrings2;
+		if (has_glyf_outlines() || !cff_ || !cff_->is_cff2())
+			return;
+		if (!cff_->charstring_table(num_glyphs_, t)) {
+			t = CharstringTable{};
+			return;
+		}
+		t.serial = command_serial();
+		t.ok = true;
+	});
+	return cell.charstrings2;
+}
+
 bool Face::outline_glyph_packed(uint16_t gid, std::vector<uint8_t> &kinds, std::vector<float> &coords) const
 {
 	PackedSink sink{kinds, coords};

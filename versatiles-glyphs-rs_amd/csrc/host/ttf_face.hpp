@@ -71,11 +71,12 @@ struct CommandTable {
 	static constexpr uint64_t kMaxStoreBytes = (1ull << 32) - 4, kStoreBytesPerCmd = 29, kMaxFloats = kMaxStoreBytes / 4;
 };
 
-// A `CFF ` (version 1) face's charstrings for the device's decoder (vgsdf_font_charstrings_desc of include/vgsdf.h, array for
-// array): every charstring and subroutine body copied once into `bytes`, the INDEX offsets resolved to ranges of it.  The
-// store the device makes of it is the one CommandTable describes, so the two share the face's command serial.
+// A `CFF ` (version 1) or `CFF2` face's charstrings for the device's decoder (vgsdf_font_charstrings_desc / _charstrings2_desc of
+// include/vgsdf.h, array for array): every charstring and subroutine body copied once into `bytes`, the INDEX offsets resolved to
+// ranges of it.  The store the device makes of it is the one CommandTable describes, so the two share the face's command serial.
 struct CharstringTable {
-	bool ok = false;                   // false: no `CFF ` outlines (glyf, CFF2), or an INDEX the description cannot state
+	bool ok = false;                   // false: no outlines of the table's kind (Face::charstring_table: `CFF `, Face::charstring2_table:
+	                                   // `CFF2`), or an INDEX the description cannot state
 	uint64_t serial = 0;               // Face::command_serial()
 	std::vector<uint8_t> bytes;        // padded to a multiple of 4
 	std::vector<uint32_t> cs_off;      // [numGlyphs + 1]
@@ -84,6 +85,11 @@ struct CharstringTable {
 	std::vector<uint32_t> lsubr_first; // [n_fds + 1]
 	std::vector<uint32_t> lsubr_off;   // [lsubr_first[n_fds] + 1]
 	std::vector<uint8_t> fd_of;        // [numGlyphs], empty when n_fds == 1
+	// CFF2 only: the blend sets, one per ItemVariationData of the variation store, with the reader's factors (default position)
+	bool cff2 = false;
+	std::vector<uint8_t> set_ok;       // [sets] 0: a charstring that selects the set ends there
+	std::vector<uint32_t> set_off;     // [sets + 1] into factors
+	std::vector<float> factors;
 };
 
 // Non-owning big-endian byte view with checked reads.
@@ -146,6 +152,9 @@ public:
 	// The charstring form of a `CFF ` version 1 face: built once, on first use (thread-safe), from the tables CffTable::parse has
 	// located — no charstring is interpreted.
 	const CharstringTable &charstring_table() const;
+	// The same of a `CFF2` face, with its blend sets (not ok for every other face, and for one whose local subroutines are more
+	// than the description's 65535).
+	const CharstringTable &charstring2_table() const;
 	// ttf-parser's `tables().cmap.is_some()`; the reference refuses fonts without one (metadata.rs:104-107)
 	bool has_cmap() const { return has_cmap_; }
 	// glyph outlines this reader can emit: `glyf` + `loca`, or `CFF ` charstrings (ttf-parser's order: glyf first).
@@ -184,10 +193,10 @@ private:
 	};
 	std::shared_ptr<ResidentCell> resident_ = std::make_shared<ResidentCell>(); // (shared by copies of the Face: same bytes)
 	struct CommandCell {
-		std::once_flag once, serial_once, charstrings_once;
+		std::once_flag once, serial_once, charstrings_once, charstrings2_once;
 		uint64_t serial = 0;
 		CommandTable table;
-		CharstringTable charstrings;
+		CharstringTable charstrings, charstrings2;
 	};
 	std::shared_ptr<CommandCell> commands_ = std::make_shared<CommandCell>();
 

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "charstring_kernels.h"
+#include "charstring_limits.h"
 #include "outline_kernels.h"
 #include "resident_fonts.h"
 #include "work_plan.h"
@@ -200,27 +201,60 @@ int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, v
 	return VGSDF_OK;
 }
 
-int vgsdf_font_create_charstrings(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, vgsdf_font **out)
-{
-	return vgsdf_font_create_charstrings_within(ctx, in, ~0ull, out, nullptr);
-}
+} // extern "C"
 
-int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
-                                         uint64_t *store_bytes)
+namespace {
+// the blend sets of a CFF2 description (vgsdf_font_charstrings2_desc)
+struct BlendSets {
+	uint32_t n_sets, n_factors;
+	const uint8_t *set_ok;
+	const uint32_t *set_off;
+	const float *factors;
+};
+constexpr uint32_t kChunkGlyphIds = 16384; // CFF2: glyph ids per launch, which bounds the workspace of the operand stack
+
+// vgsdf_font_create_charstrings_within (blend == nullptr) and vgsdf_font_create_charstrings2_within: one sequence
+int create_charstrings(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, const BlendSets *blend, uint64_t max_store_bytes,
+                       vgsdf_font **out, uint64_t *store_bytes)
 {
-	if (!ctx)
-		return VGSDF_E_ARG;
+	const char *name = blend ? "vgsdf_font_create_charstrings2" : "vgsdf_font_create_charstrings";
+	const std::string entry = std::string(name) + ": ";
 	if (!in || !out || !in->cs_off || !in->gsubr_off || !in->lsubr_first || !in->lsubr_off || (in->n_bytes && !in->bytes) ||
 	    (in->n_fds > 1 && !in->fd_of)) {
-		ctx->err = "vgsdf_font_create_charstrings: NULL argument";
+		ctx->err = entry + "NULL argument";
 		return VGSDF_E_ARG;
 	}
 	*out = nullptr;
 	if (store_bytes)
 		*store_bytes = 0;
 	const uint32_t n = in->n_glyph_ids, n_bytes = in->n_bytes;
+	if (blend) {
+		if (in->n_fds != 1 || in->fd_of) {
+			ctx->err = entry + "n_fds must be 1 and fd_of NULL";
+			return VGSDF_E_ARG;
+		}
+		if (blend->n_sets > 0x10000u || (blend->n_sets && (!blend->set_ok || !blend->set_off)) || (blend->n_factors && !blend->factors)) {
+			ctx->err = entry + "more than 65536 blend sets, or a NULL array of them";
+			return VGSDF_E_ARG;
+		}
+		if (blend->n_sets && blend->set_off[0] != 0) {
+			ctx->err = entry + "set_off does not start at 0";
+			return VGSDF_E_ARG;
+		}
+		for (uint32_t s = 0; s < blend->n_sets; s++)
+			if (blend->set_off[s + 1] < blend->set_off[s] || blend->set_off[s + 1] - blend->set_off[s] > (uint32_t)vg::kCharstringMaxRegions ||
+			    blend->set_off[s + 1] > blend->n_factors) {
+				ctx->err = entry + "set_off not ascending, a set of more than 64 factors, or one ending past n_factors";
+				return VGSDF_E_ARG;
+			}
+		for (uint32_t i = 0; i < blend->n_factors; i++)
+			if (!std::isfinite(blend->factors[i])) {
+				ctx->err = entry + "a factor that is not finite";
+				return VGSDF_E_ARG;
+			}
+	}
 	if (n == 0 || n > 0x10000u || (n_bytes & 3u) || n_bytes > 0xFFFFFFF0u || in->n_gsubrs > 0xFFFFu || in->n_fds == 0 || in->n_fds > 256u) {
-		ctx->err = "vgsdf_font_create_charstrings: glyph ids not 1 .. 65536, n_bytes not a multiple of 4 (or past 2^32 - 16), more than "
+		ctx->err = entry + "glyph ids not 1 .. 65536, n_bytes not a multiple of 4 (or past 2^32 - 16), more than "
 		           "65535 global subroutines, or Font DICTs not 1 .. 256";
 		return VGSDF_E_ARG;
 	}
@@ -232,28 +266,28 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 		return off[count] <= n_bytes;
 	};
 	if (in->lsubr_first[0] != 0) {
-		ctx->err = "vgsdf_font_create_charstrings: lsubr_first does not start at 0";
+		ctx->err = entry + "lsubr_first does not start at 0";
 		return VGSDF_E_ARG;
 	}
 	for (uint32_t k = 0; k < in->n_fds; k++)
 		if (in->lsubr_first[k + 1] < in->lsubr_first[k] || in->lsubr_first[k + 1] - in->lsubr_first[k] > 0xFFFFu) {
-			ctx->err = "vgsdf_font_create_charstrings: lsubr_first not ascending, or a Font DICT of more than 65535 local subroutines";
+			ctx->err = entry + "lsubr_first not ascending, or a Font DICT of more than 65535 local subroutines";
 			return VGSDF_E_ARG;
 		}
 	const uint32_t n_lsubrs = in->lsubr_first[in->n_fds];
 	if (!ascends_inside(in->cs_off, n) || !ascends_inside(in->gsubr_off, in->n_gsubrs) || !ascends_inside(in->lsubr_off, n_lsubrs)) {
-		ctx->err = "vgsdf_font_create_charstrings: cs_off, gsubr_off or lsubr_off not ascending, or ending past n_bytes";
+		ctx->err = entry + "cs_off, gsubr_off or lsubr_off not ascending, or ending past n_bytes";
 		return VGSDF_E_ARG;
 	}
 	if (in->fd_of)
 		for (uint32_t g = 0; g < n; g++)
 			if (in->fd_of[g] >= in->n_fds) {
-				ctx->err = "vgsdf_font_create_charstrings: an fd_of past n_fds";
+				ctx->err = entry + "an fd_of past n_fds";
 				return VGSDF_E_ARG;
 			}
 	std::unique_ptr<vgsdf_font> f(new (std::nothrow) vgsdf_font());
 	if (!f) {
-		ctx->err = "vgsdf_font_create_charstrings: out of host memory";
+		ctx->err = entry + "out of host memory";
 		return VGSDF_E_OOM;
 	}
 	ctx->charstring_ms[0] = ctx->charstring_ms[1] = 0.0f;
@@ -261,9 +295,13 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 	hipStream_t st = ctx->stream;
 	// the description on the device, for the duration of this call:
 	// bytes | cs_off | gsubr_off | lsubr_first | lsubr_off | counts (commands, coordinates per glyph id) | flags | fd_of
+	// CFF2, behind them: set_off | factors | set_ok
 	const size_t a_cs = align_up(n_bytes, 16), a_gs = a_cs + 4 * ((size_t)n + 1), a_lf = a_gs + 4 * ((size_t)in->n_gsubrs + 1),
 	             a_lo = a_lf + 4 * ((size_t)in->n_fds + 1), a_counts = a_lo + 4 * ((size_t)n_lsubrs + 1), a_flags = a_counts + 8 * (size_t)n,
-	             a_fd = a_flags + 16, a_total = a_fd + (in->fd_of ? n : 0);
+	             a_fd = a_flags + 16, a_fd_end = a_fd + (in->fd_of ? n : 0);
+	const uint32_t n_sets = blend ? blend->n_sets : 0, n_factors = blend ? blend->n_factors : 0;
+	const size_t a_so = align_up(a_fd_end, 16), a_fac = a_so + 4 * ((size_t)n_sets + 1), a_ok = a_fac + 4 * (size_t)n_factors,
+	             a_total = blend ? a_ok + n_sets : a_fd_end;
 	ScratchBuf face_buf, tmp;
 	struct Events {
 		hipEvent_t e[3] = {nullptr, nullptr, nullptr};
@@ -276,9 +314,9 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 	} ev;
 	for (hipEvent_t &e : ev.e)
 		if (hipError_t err = hipEventCreate(&e); err != hipSuccess)
-			return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipEventCreate", err);
+			return font_hip_error(ctx, name, "hipEventCreate", err);
 	if (hipError_t e = face_buf.ensure(a_total + 16); e != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipMalloc", e);
+		return font_hip_error(ctx, name, "hipMalloc", e);
 	uint8_t *a = (uint8_t *)face_buf.p;
 	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
 	hipError_t e = copy(a, in->bytes, n_bytes);
@@ -292,9 +330,15 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 		e = copy(a + a_lo, in->lsubr_off, 4 * ((size_t)n_lsubrs + 1));
 	if (e == hipSuccess && in->fd_of)
 		e = copy(a + a_fd, in->fd_of, n);
+	if (e == hipSuccess && n_sets)
+		e = copy(a + a_so, blend->set_off, 4 * ((size_t)n_sets + 1));
+	if (e == hipSuccess && n_factors)
+		e = copy(a + a_fac, blend->factors, 4 * (size_t)n_factors);
+	if (e == hipSuccess && n_sets)
+		e = copy(a + a_ok, blend->set_ok, n_sets);
 	if (e == hipSuccess)
 		e = hipMemsetAsync(a + a_flags, 0, 16, st);
-	vgsdf::CharstringsRef face{};
+	vgsdf::Charstrings2Ref face{}; // (a version 1 face: its CharstringsRef part)
 	face.words = (const uint32_t *)a;
 	face.cs_off = (const uint32_t *)(a + a_cs);
 	face.gsubr_off = (const uint32_t *)(a + a_gs);
@@ -303,10 +347,48 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 	face.fd_of = in->fd_of ? a + a_fd : nullptr;
 	face.n_glyph_ids = n;
 	face.n_gsubrs = in->n_gsubrs;
+	if (blend) {
+		face.set_ok = a + a_ok;
+		face.set_off = (const uint32_t *)(a + a_so);
+		face.factors = (const float *)(a + a_fac);
+		face.n_sets = n_sets;
+		face.spill_stride = (std::min(kChunkGlyphIds, n) + 63u) & ~63u;
+		// the context's workspace: the operand slots past the decoder's LDS window, for one launch (at most 465 x 4 x 16384 B)
+		const size_t want = 4 * (size_t)(vg::kCharstringMaxOperands2 - vg::kCharstringWindow) * face.spill_stride;
+		if (want > ctx->charstring_spill_bytes) {
+			if (ctx->charstring_spill)
+				(void)hipFree(ctx->charstring_spill); // (nothing in flight reads it: every call ends synchronised)
+			ctx->charstring_spill = nullptr;
+			ctx->charstring_spill_bytes = 0;
+			if (hipError_t err = hipMalloc(&ctx->charstring_spill, want); err != hipSuccess) {
+				ctx->charstring_spill = nullptr;
+				return font_hip_error(ctx, name, "hipMalloc", err);
+			}
+			ctx->charstring_spill_bytes = want;
+		}
+		face.spill = (float *)ctx->charstring_spill;
+	}
+	// the two passes; CFF2: in launches of at most kChunkGlyphIds glyph ids, one after the other over the workspace
+	auto run_pass = [&](bool emit, const uint32_t *cmd_off, const uint32_t *dat_off, uint8_t *kinds, float *coords) -> hipError_t {
+		uint32_t *counts = (uint32_t *)(a + a_counts), *flags = (uint32_t *)(a + a_flags);
+		if (!blend)
+			return (hipError_t)(emit ? vgsdf_charstring_emit(&face, cmd_off, dat_off, kinds, coords, flags, st)
+			                         : vgsdf_charstring_count(&face, counts, flags, st));
+		for (uint32_t g0 = 0; g0 < n; g0 += kChunkGlyphIds) {
+			vgsdf::Charstrings2Ref part = face;
+			part.cs_off = face.cs_off + g0;
+			part.n_glyph_ids = std::min(kChunkGlyphIds, n - g0);
+			const hipError_t err = (hipError_t)(emit ? vgsdf_charstring2_emit(&part, cmd_off + g0, dat_off + g0, kinds, coords, flags, st)
+			                                         : vgsdf_charstring2_count(&part, counts + 2 * (size_t)g0, flags, st));
+			if (err != hipSuccess)
+				return err;
+		}
+		return hipSuccess;
+	};
 	if (e == hipSuccess)
 		e = hipEventRecord(ev.e[0], st);
 	if (e == hipSuccess)
-		e = (hipError_t)vgsdf_charstring_count(&face, (uint32_t *)(a + a_counts), (uint32_t *)(a + a_flags), st);
+		e = run_pass(false, nullptr, nullptr, nullptr, nullptr);
 	if (e == hipSuccess)
 		e = hipEventRecord(ev.e[1], st);
 	std::vector<uint32_t> counts(2 * (size_t)n);
@@ -318,11 +400,10 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(st);
 	if (e != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "count pass", e);
+		return font_hip_error(ctx, name, "count pass", e);
 	(void)hipEventElapsedTime(&ctx->charstring_ms[0], ev.e[0], ev.e[1]);
 	if (flags) {
-		ctx->err = flags & vgsdf::CS_FLAG_SEAC ? "vgsdf_font_create_charstrings: a glyph whose endchar takes the seac form"
-		                                       : "vgsdf_font_create_charstrings: a glyph past VGSDF_CHARSTRING_MAX_TOKENS";
+		ctx->err = entry + (flags & vgsdf::CS_FLAG_SEAC ? "a glyph whose endchar takes the seac form" : "a glyph past VGSDF_CHARSTRING_MAX_TOKENS");
 		return VGSDF_E_GLYF;
 	}
 	// the store's layout from the counts: what vgsdf_font_create_commands is given by its caller
@@ -334,7 +415,7 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 		f->slots[g] = counts[2 * (size_t)g];
 		cmds += counts[2 * (size_t)g], floats += counts[2 * (size_t)g + 1];
 		if (29ull * cmds + 4ull * (n + 1) > 0xFFFFFFFCull || 4ull * floats > 0xFFFFFFFCull) {
-			ctx->err = "vgsdf_font_create_charstrings: a store (29 bytes per command, 4 per glyph id) or coordinates past what 32-bit "
+			ctx->err = entry + "a store (29 bytes per command, 4 per glyph id) or coordinates past what 32-bit "
 			           "offsets address";
 			return VGSDF_E_GLYF;
 		}
@@ -354,9 +435,9 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 	const size_t t_dat = 8 * (size_t)n, t_coords = t_dat + 4 * ((size_t)n + 1), t_kinds = t_coords + 4 * (size_t)n_floats,
 	             t_flag = align_up(t_kinds + n_cmds, 16), t_total = t_flag + 16;
 	if (hipError_t err = f->store.ensure(total + 16); err != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipMalloc", err);
+		return font_hip_error(ctx, name, "hipMalloc", err);
 	if (hipError_t err = tmp.ensure(t_total); err != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "hipMalloc", err);
+		return font_hip_error(ctx, name, "hipMalloc", err);
 	uint8_t *d = (uint8_t *)f->store.p, *t = (uint8_t *)tmp.p;
 	const std::vector<double> ones(n, 1.0);
 	e = copy(d + off_at, cmd_off.data(), 4 * ((size_t)n + 1));
@@ -370,8 +451,7 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 		e = hipEventRecord(ev.e[1], st);
 	// (cmd_off is read from the store, where it stays; dat_off from the temporaries, as the context pass below reads them)
 	if (e == hipSuccess && n_cmds)
-		e = (hipError_t)vgsdf_charstring_emit(&face, (const uint32_t *)(d + off_at), (const uint32_t *)(t + t_dat), t + t_kinds,
-		                                      (float *)(t + t_coords), (uint32_t *)(a + a_flags), st);
+		e = run_pass(true, (const uint32_t *)(d + off_at), (const uint32_t *)(t + t_dat), t + t_kinds, (float *)(t + t_coords));
 	if (e == hipSuccess)
 		e = hipEventRecord(ev.e[2], st);
 	if (e == hipSuccess && n_cmds)
@@ -386,11 +466,11 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 	if (e == hipSuccess)
 		e = hipStreamSynchronize(st); // the store is complete when the call returns: every context may name the font
 	if (e != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_font_create_charstrings", "emit pass", e);
+		return font_hip_error(ctx, name, "emit pass", e);
 	if (n_cmds)
 		(void)hipEventElapsedTime(&ctx->charstring_ms[1], ev.e[1], ev.e[2]);
 	if (flag || flags) { // (the two passes walk one text over the same bytes: said by the passes themselves)
-		ctx->err = "vgsdf_font_create_charstrings: the emit pass did not match the count pass, or the context pass refused the commands";
+		ctx->err = entry + "the emit pass did not match the count pass, or the context pass refused the commands";
 		return VGSDF_E_HIP;
 	}
 	f->cref.cmds = (uint64_t)(uintptr_t)d;
@@ -398,6 +478,41 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
 	f->cref.open = (uint64_t)(uintptr_t)(d + open_at);
 	*out = f.release();
 	return VGSDF_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vgsdf_font_create_charstrings(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, vgsdf_font **out)
+{
+	return vgsdf_font_create_charstrings_within(ctx, in, ~0ull, out, nullptr);
+}
+
+int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charstrings_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
+                                         uint64_t *store_bytes)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	return create_charstrings(ctx, in, nullptr, max_store_bytes, out, store_bytes);
+}
+
+int vgsdf_font_create_charstrings2(vgsdf_ctx *ctx, const vgsdf_font_charstrings2_desc *in, vgsdf_font **out)
+{
+	return vgsdf_font_create_charstrings2_within(ctx, in, ~0ull, out, nullptr);
+}
+
+int vgsdf_font_create_charstrings2_within(vgsdf_ctx *ctx, const vgsdf_font_charstrings2_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
+                                          uint64_t *store_bytes)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in) {
+		ctx->err = "vgsdf_font_create_charstrings2: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	const BlendSets blend{in->n_sets, in->n_factors, in->set_ok, in->set_off, in->factors};
+	return create_charstrings(ctx, &in->charstrings, &blend, max_store_bytes, out, store_bytes);
 }
 
 void vgsdf_font_charstrings_kernel_ms(const vgsdf_ctx *ctx, float ms[2])

@@ -130,6 +130,8 @@ void vgsdf_destroy(vgsdf_ctx *ctx)
 		(void)hipFree(ctx->d_counters);
 	ctx->d_scratch.release();
 	ctx->h_scratch.release();
+	if (ctx->charstring_spill)
+		(void)hipFree(ctx->charstring_spill);
 	delete ctx;
 }
 

@@ -72,6 +72,11 @@ class _CFontCharstringsDesc(C.Structure):  # vgsdf_font_charstrings_desc
                 ("lsubr_off", C.c_void_p), ("fd_of", C.c_void_p)]
 
 
+class _CFontCharstrings2Desc(C.Structure):  # vgsdf_font_charstrings2_desc
+    _fields_ = [("charstrings", _CFontCharstringsDesc), ("n_sets", C.c_uint32), ("n_factors", C.c_uint32), ("set_ok", C.c_void_p),
+                ("set_off", C.c_void_p), ("factors", C.c_void_p)]
+
+
 class _COutlinesResident(C.Structure):  # vgsdf_outlines_resident
     _fields_ = [("n_glyphs", C.c_uint32), ("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("font_of", C.c_void_p),
                 ("glyph_id", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("pbf_pre", C.c_void_p),
@@ -94,7 +99,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_host_alloc", "vgsdf_host_free", "vgsdf_outlines_prepare", "vgsdf_outlines_render", "vgsdf_outlines_render_into", "vgsdf_outlines_submit", "vgsdf_outlines_submit_packed", "vgsdf_outlines_submit_glyf", "vgsdf_outlines_wait", "vgsdf_outlines_segments",
     "vgsdf_add_counters", "vgsdf_reset_counters", "vgsdf_reduce_counters", "vgsdf_reduce_counters_rccl", "vgsdf_reduce_path", "vgsdf_outlines_pbf_positions", "vgsdf_outlines_peek",
     "vgsdf_font_create", "vgsdf_font_free", "vgsdf_font_device_bytes", "vgsdf_outlines_submit_resident", "vgsdf_outlines_resident_upload_bytes",
-    "vgsdf_font_create_commands", "vgsdf_font_create_charstrings", "vgsdf_font_create_charstrings_within", "vgsdf_font_charstrings_kernel_ms", "vgsdf_font_commands_read",
+    "vgsdf_font_create_commands", "vgsdf_font_create_charstrings", "vgsdf_font_create_charstrings_within", "vgsdf_font_create_charstrings2", "vgsdf_font_create_charstrings2_within", "vgsdf_font_charstrings_kernel_ms", "vgsdf_font_commands_read",
     "vgsdf_family_create", "vgsdf_family_free", "vgsdf_family_device_bytes", "vgsdf_family_count", "vgsdf_outlines_submit_ranges",
     "vgsdf_outlines_task_extents",
 ]
@@ -147,6 +152,8 @@ def load_library():
         L.vgsdf_font_create_commands.argtypes = [vp, C.POINTER(_CFontCmdsDesc), C.POINTER(vp)]
         L.vgsdf_font_create_charstrings.argtypes = [vp, C.POINTER(_CFontCharstringsDesc), C.POINTER(vp)]
         L.vgsdf_font_create_charstrings_within.argtypes = [vp, C.POINTER(_CFontCharstringsDesc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.vgsdf_font_create_charstrings2.argtypes = [vp, C.POINTER(_CFontCharstrings2Desc), C.POINTER(vp)]
+        L.vgsdf_font_create_charstrings2_within.argtypes = [vp, C.POINTER(_CFontCharstrings2Desc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.vgsdf_font_charstrings_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_font_charstrings_kernel_ms.restype = None
         L.vgsdf_font_commands_read.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp]
@@ -525,11 +532,22 @@ class SdfContext:
         DEVICE decodes from them.  override: raw struct fields (n_glyph_ids, n_bytes, n_gsubrs, n_fds) for descriptions that lie.
         VgsdfError with code VGSDF_E_GLYF: the device refuses the face (seac, token budget, store bounds).
         max_store_bytes (vgsdf_font_create_charstrings_within): -> (ResidentFont or None when the store would pass it, store bytes)"""
-        keep = {k: np.ascontiguousarray(desc[k], dtype=np.uint32) for k in ("cs_off", "gsubr_off", "lsubr_first", "lsubr_off")}
+        d, keep = _CFontCharstringsDesc(), {}
+        self._fill_charstrings_desc(d, keep, desc, override)
+        h = C.c_void_p()
+        if max_store_bytes is not None:
+            want = C.c_uint64()
+            self._check(load_library().vgsdf_font_create_charstrings_within(self._h, C.byref(d), int(max_store_bytes), C.byref(h), C.byref(want)))
+            return (ResidentFont(self, h) if h.value else None), int(want.value)
+        self._check(load_library().vgsdf_font_create_charstrings(self._h, C.byref(d), C.byref(h)))
+        return ResidentFont(self, h)
+
+    @staticmethod
+    def _fill_charstrings_desc(d, keep, desc, override):
+        keep.update({k: np.ascontiguousarray(desc[k], dtype=np.uint32) for k in ("cs_off", "gsubr_off", "lsubr_first", "lsubr_off")})
         keep["bytes"] = np.ascontiguousarray(desc["bytes"], dtype=np.uint8)
         fd_of = desc.get("fd_of")
         keep["fd_of"] = None if fd_of is None or len(fd_of) == 0 else np.ascontiguousarray(fd_of, dtype=np.uint8)
-        d = _CFontCharstringsDesc()
         d.n_glyph_ids = override.get("n_glyph_ids", len(keep["cs_off"]) - 1)
         d.n_bytes = override.get("n_bytes", len(keep["bytes"]))
         d.bytes = keep["bytes"].ctypes.data
@@ -540,16 +558,32 @@ class SdfContext:
         d.lsubr_first = keep["lsubr_first"].ctypes.data
         d.lsubr_off = keep["lsubr_off"].ctypes.data
         d.fd_of = None if keep["fd_of"] is None else keep["fd_of"].ctypes.data
+
+    def font_create_charstrings2(self, desc: dict, max_store_bytes=None, **override):
+        """vgsdf_font_create_charstrings2: a `CFF2` face's charstrings and blend sets (vgsdf_font_charstrings2_desc as a dict: the keys
+        of font_create_charstrings plus set_ok, set_off, factors — what FontManager.charstring2_font_desc returns) -> the command
+        font the DEVICE decodes from them.  override: raw struct fields (those of font_create_charstrings, n_sets, n_factors).
+        Errors and max_store_bytes as font_create_charstrings."""
+        d, keep = _CFontCharstrings2Desc(), {}
+        self._fill_charstrings_desc(d.charstrings, keep, desc, override)
+        keep["set_ok"] = np.ascontiguousarray(desc["set_ok"], dtype=np.uint8)
+        keep["set_off"] = np.ascontiguousarray(desc["set_off"], dtype=np.uint32)
+        keep["factors"] = np.ascontiguousarray(desc["factors"], dtype=np.float32)
+        d.n_sets = override.get("n_sets", len(keep["set_ok"]))
+        d.n_factors = override.get("n_factors", len(keep["factors"]))
+        d.set_ok = keep["set_ok"].ctypes.data
+        d.set_off = keep["set_off"].ctypes.data
+        d.factors = keep["factors"].ctypes.data
         h = C.c_void_p()
         if max_store_bytes is not None:
             want = C.c_uint64()
-            self._check(load_library().vgsdf_font_create_charstrings_within(self._h, C.byref(d), int(max_store_bytes), C.byref(h), C.byref(want)))
+            self._check(load_library().vgsdf_font_create_charstrings2_within(self._h, C.byref(d), int(max_store_bytes), C.byref(h), C.byref(want)))
             return (ResidentFont(self, h) if h.value else None), int(want.value)
-        self._check(load_library().vgsdf_font_create_charstrings(self._h, C.byref(d), C.byref(h)))
+        self._check(load_library().vgsdf_font_create_charstrings2(self._h, C.byref(d), C.byref(h)))
         return ResidentFont(self, h)
 
     def font_charstrings_kernel_ms(self):
-        """(count, emit) kernel milliseconds of this context's last font_create_charstrings"""
+        """(count, emit) pass milliseconds of this context's last font_create_charstrings / font_create_charstrings2"""
         ms = (C.c_float * 2)()
         load_library().vgsdf_font_charstrings_kernel_ms(self._h, ms)
         return float(ms[0]), float(ms[1])

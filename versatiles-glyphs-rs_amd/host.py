@@ -63,7 +63,7 @@ VGFONT_SYMBOLS = [
     "vg_manager_record_glyf_parts", "vg_glyf_batch_view", "vg_glyf_batch_free",
     "vg_manager_resident_font_desc", "vg_manager_record_resident", "vg_resident_batch_view", "vg_resident_batch_free",
     "vg_manager_command_font_desc", "vg_manager_record_resident_commands", "vg_manager_set_resident_commands",
-    "vg_manager_command_stats", "vg_manager_charstring_font_desc", "vg_manager_set_charstrings_on_device",
+    "vg_manager_command_stats", "vg_manager_charstring_font_desc", "vg_manager_charstring2_font_desc", "vg_manager_set_charstrings_on_device",
     "vg_manager_charstring_stats", "vg_manager_charstring_preload_stats", "vg_manager_set_resident_families", "vg_manager_family_stats",
     "vg_manager_set_resident_fonts", "vg_renderer_set_resident_budget", "vg_renderer_preload_fonts", "vg_manager_resident_stats",
     "vg_manager_scan", "vg_manager_font_ids", "vg_manager_font_file_names", "vg_parse_font_name", "vg_manager_generate_name",
@@ -364,10 +364,11 @@ class FontManager:
         bytes in every mode"""
         _L().vg_manager_set_resident_commands(self._h, int(mode))
 
-    def set_charstrings_on_device(self, on: bool):
-        """False (default).  True: the command stores of `CFF ` version 1 faces are decoded on the device from the charstrings
-        (vgsdf_font_create_charstrings) instead of built by the host's reader; a face the device refuses falls back; same bytes"""
-        _L().vg_manager_set_charstrings_on_device(self._h, 1 if on else 0)
+    def set_charstrings_on_device(self, on):
+        """False / 0 (default).  True / 1: the command stores of `CFF ` version 1 faces are decoded on the device from the charstrings
+        (vgsdf_font_create_charstrings) instead of built by the host's reader; a face the device refuses falls back; same bytes.
+        2: CFF2 faces as well (vgsdf_font_create_charstrings2, the reader's blend factors: the default position)"""
+        _L().vg_manager_set_charstrings_on_device(self._h, int(on))
 
     def charstring_stats(self) -> dict:
         """of the last render: {fonts_decoded, font_bytes, fallbacks} (vg_charstring_stats)"""
@@ -669,6 +670,31 @@ class FontManager:
                 "gsubr_off": arr(d.gsubr_off, d.n_gsubrs + 1, np.uint32), "lsubr_first": lsubr_first,
                 "lsubr_off": arr(d.lsubr_off, int(lsubr_first[-1]) + 1, np.uint32),
                 "fd_of": arr(d.fd_of, d.n_glyph_ids, np.uint8) if d.fd_of else None}
+
+    def charstring2_font_desc(self, font_id: str, file_index: int = 0) -> dict:
+        """description of one file of a font id for vgsdf_font_create_charstrings2 (vg_manager_charstring2_font_desc; no device):
+        the keys of charstring_font_desc (fd_of None) plus the blend sets {set_ok, set_off, factors} as numpy copies.
+        RuntimeError: anything that is not CFF2, a table the description cannot state"""
+        from .device import _CFontCharstrings2Desc
+        L = _L()
+        L.vg_manager_charstring2_font_desc.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        d2 = _CFontCharstrings2Desc()
+        if L.vg_manager_charstring2_font_desc(self._h, font_id.encode(), file_index, C.byref(d2)) != 0:
+            raise RuntimeError(_err())
+        d = d2.charstrings
+
+        def arr(ptr, count, dt):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dt)
+            buf = (C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dt, count=count).copy()
+
+        lsubr_first = arr(d.lsubr_first, d.n_fds + 1, np.uint32)
+        return {"bytes": arr(d.bytes, d.n_bytes, np.uint8), "cs_off": arr(d.cs_off, d.n_glyph_ids + 1, np.uint32),
+                "gsubr_off": arr(d.gsubr_off, d.n_gsubrs + 1, np.uint32), "lsubr_first": lsubr_first,
+                "lsubr_off": arr(d.lsubr_off, int(lsubr_first[-1]) + 1, np.uint32), "fd_of": None,
+                "set_ok": arr(d2.set_ok, d2.n_sets, np.uint8), "set_off": arr(d2.set_off, d2.n_sets + 1, np.uint32),
+                "factors": arr(d2.factors, d2.n_factors, np.float32)}
 
     def family_desc(self, font_id: str) -> dict:
         """the host half of a resident family (vg_manager_family_desc): {code_point, font_of, glyph_id, advance, scale, shift_x,
