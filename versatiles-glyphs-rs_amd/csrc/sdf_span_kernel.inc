@@ -260,9 +260,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			s_dy[i] = fdy;
 			s_inv[i] = finv;
 			// coordinate bound: wave maximum first, one LDS atomic per wave (non-negative floats order like uints)
-			uint32_t mb = __float_as_uint(mf);
-			for (int sh = 32; sh > 0; sh >>= 1)
-				mb = max(mb, (uint32_t)__shfl_xor((int)mb, sh));
+			// (the maximum arrives as a scalar: lane 0's atomic then takes a wave-uniform value, nothing for the compiler to reduce)
+			const uint32_t mb = wave_max_u32(__float_as_uint(mf));
 			if (lane == 0)
 				atomicMax(&s_mbits[par], mb);
 
@@ -279,15 +278,15 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					const float dv = __builtin_fmaf(ey, ey, ex * ex), dw = __builtin_fmaf(fy, fy, fx * fx);
 					r2 = dv > dw ? dv : dw;
 				}
-				for (int sh = 1; sh < (int)GRP; sh <<= 1) {
-					const float other = __shfl_xor(r2, sh);
-					r2 = other > r2 ? other : r2;
-				}
+				// maximum over the group's 8 lanes on the bits (r2 >= +0: unsigned order is float order; a NaN, which only
+				// coordinates beyond the f32 range produce, stays a NaN, and Mc = inf then switches the group bounds off)
+				r2 = __uint_as_float(oct_max_u32(__float_as_uint(r2)));
 				if ((tid & (GRP - 1)) == 0) {
 					const bool empty = gb >= cnt;
 					s_g[0][tid / GRP] = empty ? 1.0e18f : ax;
 					s_g[1][tid / GRP] = empty ? 1.0e18f : ay;
-					s_g[2][tid / GRP] = empty ? 0.0f : __builtin_sqrtf(r2) * (INFL * INFL * VG_M_GRP_SLACK); // 1.004: see phase 1
+					// (raw v_sqrt_f32: within 1 ulp of the rounded root, 0 for a denormal r2 < 1.2e-38; INFL and the pad of phase 1 cover both)
+					s_g[2][tid / GRP] = empty ? 0.0f : __builtin_amdgcn_sqrtf(r2) * (INFL * INFL * VG_M_GRP_SLACK); // 1.004: see phase 1
 				}
 			}
 
@@ -296,13 +295,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// at the barrier for the one long segment (2.6 trips per wave on average, up to 24, against 7.5
 			// crossings per wave in total). ----
 			{
-				uint32_t incl = nrow; // inclusive prefix sum over the wave: DPP row shifts + row broadcasts
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false); // row_shr:1
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false); // row_shr:2
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false); // row_shr:4
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false); // row_shr:8
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xA, 0xF, false); // row_bcast:15 -> rows 1, 3
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xC, 0xF, false); // row_bcast:31 -> rows 2, 3
+				const uint32_t incl = wave_scan_add(nrow); // inclusive prefix sum over the wave
 				const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 				auto cross = [&](double vx, double vy, double dx, double dy, bool up, int yy) {
 					const double pyy = (double)yy + y0c;
@@ -369,7 +362,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// a wave whose 64 pixels all lie past the end of the bitmap (last tile of the glyph) has nothing to do
 			if (p0 + k * TPB + pw >= npix)
 				continue;
-			const uint32_t oc = o < npix ? o : npix - 1;
+			const uint32_t oc = min(o, npix - 1);
 			const uint32_t row = oc / g.w;
 			const uint32_t x = oc - row * g.w;
 			const uint32_t y = g.h - 1 - row;
@@ -410,7 +403,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					}
 				}
 				ub2 = __uint_as_float(dmin);
-				float U = (__builtin_sqrtf(ub2) * INFL + pad) * INFL;
+				float U = (__builtin_amdgcn_sqrtf(ub2) * INFL + pad) * INFL; // (raw v_sqrt_f32, as for the group radius: DESIGN.md §4.1)
 				U = U < VG_M_SAT ? U : VG_M_SAT; // SAT: beyond it the byte is saturated whatever the minimum is
 				const float Ui = (U + pad * INFL) * VG_M_GRP_SLACK; // s_gr is stored with the same factor; it lacks the pad of r_g
 				// One bit per group, 3-4 VALU ops each: tt = (U + r_g) 1.004, diff = tt^2 - D_g^2 (sign bit set
@@ -419,9 +412,9 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				uint32_t rej = 0xFFFFFFFFu;
 #pragma unroll
 				for (uint32_t b = 0; b < NGRP / 4; b++) {
-					float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-					if (b * 4 < n_groups)
-						r = gr4[b];
+					// (unconditional: the stage writes all NGRP radii in every processed chunk, 0 for the empty groups, and
+					// the blocks past n_groups carry D2p = 3.4e38 : 3.4e38, rejected whatever the radius is)
+					const float4 r = gr4[b];
 					const float rs[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
 					for (int j = 0; j < 4; j++) {
@@ -466,13 +459,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				// wave pools its (pixel, group) pairs in LDS and deals them out evenly: 64 pairs per round,
 				// results merged with ds_min_u32 on the owning pixel's slot.
 				const uint32_t c = (uint32_t)__builtin_popcount(cand);
-				uint32_t incl = c; // inclusive prefix sum over the wave: DPP row shifts + row broadcasts
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false); // row_shr:1
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false); // row_shr:2
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false); // row_shr:4
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false); // row_shr:8
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xA, 0xF, false); // row_bcast:15 -> rows 1, 3
-				incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xC, 0xF, false); // row_bcast:31 -> rows 2, 3
+				const uint32_t incl = wave_scan_add(c); // inclusive prefix sum over the wave
 				const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 				VG_COUNT(cn_pairs += total; cn_rounds += (total + 63) / 64; cn_tc += 1);
 				if (total <= QCAP) {
@@ -545,7 +532,9 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				// falls into bin floor(s).  Beyond C = 35.9 (32 sqrt(C) + 1/2 >= 192) both bytes are saturated (0 / 255)
 				// whatever the bin is.  NaN anywhere -> every comparison false -> not decided -> exact evaluation.
 				const float f1 = __uint_as_float(k1);
-				const float sq = __builtin_sqrtf(f1);
+				// (raw v_sqrt_f32: within 1 ulp of the rounded root, which moves s by <= 32 ulp(sq) < 1.6e-5 and e by a 1.2e-7th of its
+				// first term, inside the 3e-4 of dl and the 1.001 of h; a denormal f1 gives sq = 0, fails 8 e <= f1 and has dl = inf)
+				const float sq = __builtin_amdgcn_sqrtf(f1);
 				const float e = VG_M_E(__builtin_fmaf(herr_c1, sq, __builtin_fmaf(VG_HERR_C2S, f1, herr_c3)));
 				float U = f1 + e;
 				const float uf = U * VG_M_CARRY;
@@ -618,10 +607,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 							for (uint32_t i = 0; i < 8; i++)
 								scand &= scand - 1; // (wave-uniform: scalar)
 						}
-						for (int sh = 32; sh > 0; sh >>= 1) {
-							const double other = __shfl_xor(wbest, sh);
-							wbest = other < wbest ? other : wbest;
-						}
+						wbest = wave_min_f64(wbest); // (min is exact in any order; wbest is never a NaN)
 						if ((int)lane == src)
 							best = wbest;
 					}

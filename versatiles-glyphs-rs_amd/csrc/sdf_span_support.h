@@ -132,4 +132,82 @@ __device__ __forceinline__ uint32_t wave_rot(uint32_t b)
 	return (b * WAVE_ROT_MUL) >> 30;
 }
 
+// ---------------------------------------------------------------------------------------
+// Wave-level scans and reductions on DPP row shifts and row broadcasts: one VALU instruction per step (the DPP move folds
+// into the add / max that consumes it), no LDS permute.  A lane without a source lane, or in a row the step masks off,
+// reads 0, the identity of the two unsigned operations.
+// ALL 64 LANES MUST BE ACTIVE at every call of wave_scan_add, wave_max_u32 and wave_min_f64 (an inactive lane is a hole in
+// the chain of row shifts, and the two reductions read their result from lane 63), and all 8 of a run at oct_max_u32:
+// call them from wave-uniform control flow only, as the stage and the sweep do.
+// ---------------------------------------------------------------------------------------
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v)
+{
+	return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
+}
+
+// inclusive prefix sum over the 64 lanes.  Written out: the compiler folds the DPP move into v_max_u32 (below) but leaves
+// v_mov_b32_dpp + v_add_u32 for the sum.  A DPP operand must not be read in the two wait states behind the VALU
+// instruction that wrote it, hence the s_nop 1 ahead of every step; the compiler pads nothing inside the statement and
+// does not know that its input is read through DPP, so the first step waits for itself too, and for the five states a
+// DPP instruction needs behind a VALU write of EXEC (v_cmpx).  In the rows a broadcast step masks off the destination
+// keeps its value, which is the operand: "+v".
+__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v)
+{
+	asm("s_nop 4\n\t"
+	    "v_add_u32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+	    "s_nop 1\n\t"
+	    "v_add_u32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+	    "s_nop 1\n\t"
+	    "v_add_u32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+	    "s_nop 1\n\t"
+	    "v_add_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+	    "s_nop 1\n\t"
+	    "v_add_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" // -> rows 1, 3
+	    "s_nop 1\n\t"
+	    "v_add_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" // -> rows 2, 3
+	    : "+v"(v));
+	return v;
+}
+
+// maximum over the 64 lanes, wave-uniform (lane 63 of the same six steps holds it)
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+	v = max(v, dpp_or_zero<0x111, 0xF>(v));
+	v = max(v, dpp_or_zero<0x112, 0xF>(v));
+	v = max(v, dpp_or_zero<0x114, 0xF>(v));
+	v = max(v, dpp_or_zero<0x118, 0xF>(v));
+	v = max(v, dpp_or_zero<0x142, 0xA>(v));
+	v = max(v, dpp_or_zero<0x143, 0xC>(v));
+	return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// maximum over each aligned run of 8 lanes, in all 8 of them
+__device__ __forceinline__ uint32_t oct_max_u32(uint32_t v)
+{
+	v = max(v, dpp_or_zero<0xB1, 0xF>(v));  // quad_perm:[1,0,3,2]
+	v = max(v, dpp_or_zero<0x4E, 0xF>(v));  // quad_perm:[2,3,0,1]
+	v = max(v, dpp_or_zero<0x141, 0xF>(v)); // row_half_mirror: lane i of the 8 <-> lane 7 - i
+	return v;
+}
+
+// minimum over the 64 lanes of values that are never NaN, wave-uniform.  (v_min_f64 has no DPP form: two moves per step;
+// a lane without a source lane, or in a masked row, reads its own value.)
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_min_f64(double v)
+{
+	const int lo = __double2loint(v), hi = __double2hiint(v);
+	const double other = __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xF, false),
+	                                      __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xF, false));
+	return other < v ? other : v;
+}
+__device__ __forceinline__ double wave_min_f64(double v)
+{
+	v = dpp_min_f64<0x111, 0xF>(v);
+	v = dpp_min_f64<0x112, 0xF>(v);
+	v = dpp_min_f64<0x114, 0xF>(v);
+	v = dpp_min_f64<0x118, 0xF>(v);
+	v = dpp_min_f64<0x142, 0xA>(v);
+	v = dpp_min_f64<0x143, 0xC>(v);
+	return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+
 } // namespace vgsdf
