@@ -174,6 +174,19 @@ typedef struct {
 	uint64_t block_bytes;       /* bytes of those submissions' upload blocks */
 } vg_family_stats;
 int vg_manager_family_stats(const vg_manager *m, vg_family_stats *out);
+/* Family tables on the device, 0 (default) / 1: wherever the renderer makes a resident family — groups of the switch above,
+ * vg_renderer_preload_fonts — the DEVICE builds its table from the faces' `cmap` and `hmtx` tables (vgsdf_family_create_tables);
+ * the host only says where the unicode subtables are (vg_manager_family_tables_desc) and looks no code point up.  A font id
+ * whose description refuses (a cmap subtable that is not regular), or whose build the device refuses, gets its family from the
+ * host's table as with 0, remembered per font id and device.  Same registry key, budget and lifetime, same table bytes and
+ * same output either way.  vg_manager_family_table_stats: of the last render; the families built count among
+ * vg_family_stats.families_uploaded too. */
+void vg_manager_set_family_tables_on_device(vg_manager *m, int on);
+typedef struct {
+	uint64_t built_on_device; /* families whose tables the device built during the render */
+	uint64_t fallbacks;       /* font ids whose families came from the host's table although the switch is on */
+} vg_family_table_stats;
+int vg_manager_family_table_stats(const vg_manager *m, vg_family_table_stats *out);
 /* How a renderer of several device lanes (vg_renderer_new_multi) splits a run: -1 / 2 (default) the hybrid plan — whole
  * (font, block) tasks per lane, manager.rs:86-97's unit, and the heaviest blocks' glyphs split between lanes until the lanes'
  * estimated raster cost is within 4 % of the mean; 1 whole tasks only; 0 glyph-level shards of every font (every block
@@ -344,6 +357,14 @@ typedef struct {
 	const double *shift_x;      /* [n_entries] */
 } vg_family_view;
 int vg_manager_family_desc(const vg_manager *m, const char *font_id, vg_family_view *view);
+/* The same family stated by its faces' TABLES, for vgsdf_family_create_tables (no device needed, and no code point looked up):
+ * file `file_index`'s whole `cmap` and `hmtx` tables as views into the face, units_per_em, num_glyphs (maxp), num_hmetrics (hhea),
+ * and the encoding records, in the table's order, that are unicode and of format 0, 4, 6, 10, 12 or 13.  With fonts[k] the device
+ * font of file k and tables[k] this description, the device builds the table vg_manager_family_desc states.  The pointers stay
+ * valid as long as the manager holds the font.  -1: unknown font / file, or a description that REFUSES: a format 4 subtable whose
+ * segments are not regular (segCountX2 >= 2, the arrays inside the table, start <= end, start above the previous end), or a
+ * format 12 / 13 subtable whose groups are not ascending and disjoint inside the table; vg_last_error then begins "refused". */
+int vg_manager_family_tables_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_face_tables *desc);
 
 /* Hand-encoder of the glyphs PBF (src/protobuf/glyphs.rs:66-70) for already rendered
  * glyphs; bitmaps[i] may be NULL when !has_bitmap. Returns needed size. */

@@ -438,6 +438,43 @@ int vgsdf_family_free(vgsdf_ctx *ctx, vgsdf_family *family);
 uint64_t vgsdf_family_device_bytes(const vgsdf_family *family);
 uint32_t vgsdf_family_count(const vgsdf_family *family, uint32_t first, uint32_t last);
 /*
+ * The same family from its faces' `cmap` and `hmtx` TABLES: no code point is looked up on the host.  The host says where the
+ * unicode subtables are (vg_manager_family_tables_desc of vgfont.h builds such a description), the device looks every code point
+ * of [0, 0xFFFF] outside the surrogates up in the faces in order and writes the table in place: a count pass sizes it, an
+ * emit pass places every entry at its rank.  A face MAPS a code point when one of its subtables enumerates it and that
+ * subtable's lookup has a value; the entry belongs to the first face that maps it, its glyph id is the first value any of
+ * that face's subtables has, and advance, scale and shift_x are those of the packed form's recorder in f64:
+ * scale = 24 / units_per_em, advance = round(hmtx advance * scale * 0.95), shift_x = (advance - that product) / 2.  The lookups
+ * are bounded by cmap_len / hmtx_len throughout, whatever the tables' own length fields say.
+ * Validated on the host (VGSDF_E_ARG): pointers that are NULL beside a length that is not 0, subtable_off < cmap_len, formats
+ * from the list, units_per_em in 16 .. 16384, fonts on the context's device and of one kind.  A glyph id at or past its font's
+ * glyph ids is found by the count pass: VGSDF_E_ARG, nothing left allocated, the context sound.  The family is
+ * indistinguishable from one vgsdf_family_create makes of the same entries.
+ */
+typedef struct { /* one face, as vg_manager_family_tables_desc states it */
+	const uint8_t *cmap;
+	uint32_t cmap_len;
+	const uint8_t *hmtx;
+	uint32_t hmtx_len;
+	uint16_t units_per_em, num_glyphs, num_hmetrics, n_subtables;
+	const uint32_t *subtable_off;    /* [n_subtables] into cmap */
+	const uint16_t *subtable_format; /* [n_subtables] 0 4 6 10 12 13 */
+} vgsdf_face_tables;
+typedef struct {
+	uint32_t n_fonts;                /* 1 .. 65536, provider order: the first face that maps a code point wins */
+	const vgsdf_font *const *fonts;  /* one device, one kind */
+	const vgsdf_face_tables *tables; /* [n_fonts] */
+} vgsdf_family_tables_desc;
+int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out);
+/* test / inspection: download the DEVICE's copy of a family's table, whichever call made it; *n_entries: its entries; code_point,
+ * font_of, glyph_id, advance, scale, shift_x, pbf_fix [n_entries], cmd_pre, leaf_pre [n_entries + 1] (mod 2^32): each NULL or filled */
+int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_entries, uint16_t *code_point, uint16_t *font_of,
+                      uint16_t *glyph_id, uint32_t *advance, double *scale, double *shift_x, uint32_t *cmd_pre, uint32_t *leaf_pre,
+                      uint8_t *pbf_fix);
+/* test / inspection (tools/family_tables_ab.py): milliseconds the count and the emit pass of the context's last
+ * vgsdf_family_create_tables took (HIP events around the pass; 0 0 before the first, and for a pass that did not run) */
+void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
+/*
  * The glyph sequence of a ranges submission: the tasks in order, and inside a task the mapped code points of
  * [first, last] of its family, ascending.  The output is, byte for byte, that of vgsdf_outlines_submit_resident given that
  * sequence with the families' fonts, the entries' scale and shift_x, pbf_pre[g] = the task's value on its first glyph and 0

@@ -1,0 +1,301 @@
+// family_table_kernels.hip — a font id's table code point -> (font, glyph id, advance, scale, shift_x) from its faces' `cmap` and
+// `hmtx` bytes (family_table_kernels.h).  What a lane computes for its code point is, step for step, what the host computes in
+// FontManager::family_table: the face is the first in order that MAPS the code point (a unicode subtable lists it and its
+// lookup has a value: Face::unicode_codepoints), the glyph id is the first value any of that face's subtables has
+// (Face::glyph_index), and the entry's numbers are Renderer::record_resident's in f64 (this unit is built with
+// -ffp-contract=off).  The lookups are CmapSubtable::glyph_index's bisections; every read is bounded by the table lengths of the
+// face record.  Two passes of one text: the count pass leaves per workgroup its entries, command slots and leaves, the emit pass
+// places every entry at its rank and writes all nine arrays of FamilyTableLayout.
+#include "family_table_kernels.h"
+
+#include "upload_layout.h"
+
+namespace vgsdf {
+namespace {
+
+// a cmap subtable: from its first byte to the END OF THE CMAP TABLE (the bound of data.has on the host)
+struct Sub {
+	const uint8_t *p;
+	uint64_t n;
+};
+__device__ inline bool has(const Sub &d, uint64_t off, uint64_t len) { return off <= d.n && len <= d.n - off; }
+__device__ inline uint32_t be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
+__device__ inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// CmapSubtable::glyph_index: the glyph id, or -1 for "no value"; listed: for_each_codepoint visits c (meaningful with a value)
+__device__ int32_t lookup(const Sub &d, uint32_t format, uint32_t c, bool &listed)
+{
+	listed = true;
+	switch (format) {
+	case 0: {
+		if (c >= 256 || !has(d, 6, 256))
+			return -1;
+		const uint32_t g = d.p[6 + c];
+		return g ? (int32_t)g : -1;
+	}
+	case 4: {
+		if (!has(d, 0, 14))
+			return -1;
+		const uint32_t x2 = be16(d.p + 6);
+		if (x2 < 2)
+			return -1;
+		const uint32_t segs = x2 / 2, ends = 14, starts = ends + segs * 2 + 2, deltas = starts + segs * 2, offsets = deltas + segs * 2;
+		if (!has(d, offsets, segs * 2))
+			return -1;
+		uint32_t lo = 0, hi = segs;
+		while (lo < hi) {
+			const uint32_t mid = (lo + hi) / 2;
+			const uint32_t end = be16(d.p + ends + mid * 2);
+			if (end < c) {
+				lo = mid + 1;
+				continue;
+			}
+			const uint32_t first = be16(d.p + starts + mid * 2);
+			if (first > c) {
+				hi = mid;
+				continue;
+			}
+			listed = !(first == 0xFFFFu && end == 0xFFFFu); // the closing segment is not enumerated
+			const uint32_t range_off = be16(d.p + offsets + mid * 2), delta = be16(d.p + deltas + mid * 2);
+			if (range_off == 0)
+				return (int32_t)((c + delta) & 0xFFFFu);
+			if (range_off == 0xFFFFu)
+				return -1;
+			const uint32_t twice = (c - first) * 2;
+			if (twice > 0xFFFFu)
+				return -1;
+			const uint32_t pos = (offsets + mid * 2 + twice + range_off) & 0xFFFFu; // wraps in u16, from the subtable start
+			if (!has(d, pos, 2))
+				return -1;
+			const uint32_t raw = be16(d.p + pos);
+			if (raw == 0)
+				return -1;
+			const uint32_t id = (raw + delta) & 0xFFFFu;
+			return id & 0x8000u ? -1 : (int32_t)id; // negative as i16
+		}
+		return -1;
+	}
+	case 6: {
+		if (!has(d, 0, 10))
+			return -1;
+		const uint32_t first = be16(d.p + 6), count = be16(d.p + 8);
+		if (c < first || c - first >= count || !has(d, 10 + (uint64_t)(c - first) * 2, 2))
+			return -1;
+		return (int32_t)be16(d.p + 10 + (size_t)(c - first) * 2);
+	}
+	case 10: {
+		if (!has(d, 0, 20))
+			return -1;
+		const uint32_t first = be32(d.p + 12), count = be32(d.p + 16);
+		if (c < first || c - first >= count || !has(d, 20 + (uint64_t)(c - first) * 2, 2))
+			return -1;
+		return (int32_t)be16(d.p + 20 + (size_t)(c - first) * 2);
+	}
+	case 12:
+	case 13: {
+		if (!has(d, 0, 16))
+			return -1;
+		const uint32_t n = be32(d.p + 12);
+		if (!has(d, 16, (uint64_t)n * 12))
+			return -1;
+		uint32_t lo = 0, hi = n;
+		while (lo < hi) {
+			const uint32_t mid = lo + (hi - lo) / 2;
+			const uint8_t *g = d.p + 16 + (size_t)mid * 12;
+			const uint32_t start = be32(g);
+			if (start > c)
+				hi = mid;
+			else if (be32(g + 4) < c)
+				lo = mid + 1;
+			else {
+				uint64_t id = be32(g + 8);
+				if (format == 12)
+					id = id + c - start; // (c <= 0xFFFF: the sum stays below 2^33)
+				return id > 0xFFFFu ? -1 : (int32_t)id;
+			}
+		}
+		return -1;
+	}
+	default:
+		return -1;
+	}
+}
+
+struct Entry {
+	bool found;
+	uint32_t face, gid;
+};
+
+__device__ Entry find_entry(const FamilyFaceRef *faces, uint32_t n_faces, uint32_t c)
+{
+	Entry e{false, 0, 0};
+	if (c >= 0xD800u && c <= 0xDFFFu)
+		return e;
+	for (uint32_t k = 0; k < n_faces; k++) {
+		const FamilyFaceRef &F = faces[k];
+		const FamilySubtable *subs = (const FamilySubtable *)(uintptr_t)F.subtables;
+		int32_t first_value = -1;
+		bool maps = false;
+		for (uint32_t s = 0; s < F.n_subtables; s++) {
+			const FamilySubtable st = subs[s];
+			if (st.off >= F.cmap_len)
+				continue;
+			const Sub d{(const uint8_t *)(uintptr_t)F.cmap + st.off, (uint64_t)F.cmap_len - st.off};
+			bool listed;
+			const int32_t v = lookup(d, st.format, c, listed);
+			if (v >= 0) {
+				if (first_value < 0)
+					first_value = v;
+				maps = maps || listed;
+			}
+		}
+		if (maps) {
+			e.found = true;
+			e.face = k;
+			e.gid = (uint32_t)first_value;
+			break;
+		}
+	}
+	return e;
+}
+
+// the command slots and leaves of a glyph id inside its font (gid < n_glyph_ids): cmd_off's difference of a command font; of a
+// glyf font the leaves of leaf_off, which tile the glyph's slots from 0 in order, so the last one ends them
+__device__ void glyph_extent(const FamilyFaceRef &F, uint32_t gid, uint32_t &slots, uint32_t &leaves)
+{
+	const uint32_t *off = (const uint32_t *)(uintptr_t)F.off;
+	const uint32_t a = off[gid], b = off[gid + 1];
+	if (F.commands) {
+		slots = b - a;
+		leaves = 0;
+		return;
+	}
+	leaves = b - a;
+	slots = 0;
+	if (b > a) {
+		const vgsdf_glyf_part *parts = (const vgsdf_glyf_part *)(uintptr_t)F.leaves;
+		slots = parts[b - 1].cmd_at + parts[b - 1].cmd_cap;
+	}
+}
+
+__device__ inline uint32_t varint_len(uint32_t v) { return v < 0x80u ? 1u : v < 0x4000u ? 2u : v < 0x200000u ? 3u : v < 0x10000000u ? 4u : 5u; }
+
+struct Sum3 {
+	uint32_t e, s, l;
+};
+// the workgroup's sums, in every thread
+__device__ Sum3 block_sum(Sum3 v, uint32_t (*lds)[3])
+{
+	for (int d = 32; d >= 1; d >>= 1) {
+		v.e += __shfl_xor(v.e, d);
+		v.s += __shfl_xor(v.s, d);
+		v.l += __shfl_xor(v.l, d);
+	}
+	const uint32_t w = threadIdx.x >> 6;
+	if ((threadIdx.x & 63u) == 0)
+		lds[w][0] = v.e, lds[w][1] = v.s, lds[w][2] = v.l;
+	__syncthreads();
+	Sum3 r{0, 0, 0};
+	for (uint32_t j = 0; j < kFamilyThreads / 64; j++)
+		r.e += lds[j][0], r.s += lds[j][1], r.l += lds[j][2];
+	return r;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(kFamilyThreads) void family_tables_pass(const FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts,
+                                                                       uint32_t *flags, uint32_t n_entries, uint8_t *table)
+{
+	__shared__ uint32_t lds_base[kFamilyThreads / 64][3], lds_wave[kFamilyThreads / 64][3];
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = blockIdx.x * kFamilyThreads + tid;
+	const Entry e = find_entry(faces, n_faces, c);
+	uint32_t slots = 0, leaves = 0;
+	if (e.found) {
+		const FamilyFaceRef &F = faces[e.face];
+		if (e.gid < F.n_glyph_ids)
+			glyph_extent(F, e.gid, slots, leaves);
+		else if (!EMIT)
+			*flags = FAMILY_FLAG_GLYPH; // (one bit: every writer stores the same word)
+	}
+	// inclusive sums over the wave, then the earlier waves' totals
+	Sum3 inc{e.found ? 1u : 0u, slots, leaves};
+	for (uint32_t d = 1; d < 64; d <<= 1) {
+		const uint32_t te = __shfl_up(inc.e, d), ts = __shfl_up(inc.s, d), tl = __shfl_up(inc.l, d);
+		if (lane >= d)
+			inc.e += te, inc.s += ts, inc.l += tl;
+	}
+	if (lane == 63)
+		lds_wave[wave][0] = inc.e, lds_wave[wave][1] = inc.s, lds_wave[wave][2] = inc.l;
+	__syncthreads();
+	Sum3 before{0, 0, 0}, total{0, 0, 0};
+	for (uint32_t j = 0; j < kFamilyThreads / 64; j++) {
+		if (j < wave)
+			before.e += lds_wave[j][0], before.s += lds_wave[j][1], before.l += lds_wave[j][2];
+		total.e += lds_wave[j][0], total.s += lds_wave[j][1], total.l += lds_wave[j][2];
+	}
+	if (!EMIT) {
+		if (tid == 0) {
+			uint32_t *o = counts + kFamilyCounts * blockIdx.x;
+			o[0] = total.e, o[1] = total.s, o[2] = total.l, o[3] = 0;
+		}
+		return;
+	}
+	// the workgroups in front of this one (tid names a workgroup here: kFamilyGroups == kFamilyThreads)
+	static_assert(kFamilyGroups <= kFamilyThreads, "one thread per workgroup's counts");
+	Sum3 mine{0, 0, 0};
+	if (tid < blockIdx.x)
+		mine = Sum3{counts[kFamilyCounts * tid], counts[kFamilyCounts * tid + 1], counts[kFamilyCounts * tid + 2]};
+	const Sum3 base = block_sum(mine, lds_base);
+	const FamilyTableLayout at(n_entries);
+	uint32_t *cmd_pre = (uint32_t *)(table + at.cmd_pre), *leaf_pre = (uint32_t *)(table + at.leaf_pre);
+	if (blockIdx.x == kFamilyGroups - 1 && tid == kFamilyThreads - 1 && base.e + total.e == n_entries) {
+		cmd_pre[n_entries] = base.s + total.s;
+		leaf_pre[n_entries] = base.l + total.l;
+	}
+	if (!e.found)
+		return;
+	const uint32_t rank = base.e + before.e + inc.e - 1;
+	if (rank >= n_entries) // (never: the host sized the table from the count pass of the same text)
+		return;
+	const FamilyFaceRef &F = faces[e.face];
+	// Face::glyph_hor_advance(gid).value_or(0)
+	uint32_t adv = 0;
+	if (F.hmtx_len != 0 && F.num_hmetrics != 0 && F.num_glyphs != 0 && e.gid < F.num_glyphs && (uint32_t)F.num_hmetrics * 4u <= F.hmtx_len) {
+		const uint32_t i = e.gid < (uint32_t)F.num_hmetrics - 1u ? e.gid : (uint32_t)F.num_hmetrics - 1u;
+		adv = be16((const uint8_t *)(uintptr_t)F.hmtx + (size_t)i * 4);
+	}
+	// Renderer::record_resident
+	const double scale = 24.0 / (double)F.units_per_em;
+	const double advance_float = (double)adv * scale * 0.95;
+	const uint32_t advance = (uint32_t)round(advance_float);
+	((double *)(table + at.scale))[rank] = scale;
+	((double *)(table + at.shift_x))[rank] = ((double)advance - advance_float) / 2.0;
+	cmd_pre[rank] = base.s + before.s + inc.s - slots;
+	leaf_pre[rank] = base.l + before.l + inc.l - leaves;
+	((uint32_t *)(table + at.advance))[rank] = advance;
+	((uint16_t *)(table + at.code_point))[rank] = (uint16_t)c;
+	((uint16_t *)(table + at.font_of))[rank] = (uint16_t)e.face;
+	((uint16_t *)(table + at.glyph_id))[rank] = (uint16_t)e.gid;
+	(table + at.pbf_fix)[rank] = (uint8_t)((1u + varint_len(c)) | ((1u + varint_len(advance)) << 4));
+}
+
+} // namespace
+} // namespace vgsdf
+
+extern "C" {
+
+int vgsdf_family_tables_count(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts, uint32_t *flags, hipStream_t stream)
+{
+	hipLaunchKernelGGL(vgsdf::family_tables_pass<false>, dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces, n_faces,
+	                   counts, flags, 0u, (uint8_t *)nullptr);
+	return (int)hipGetLastError();
+}
+
+int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, const uint32_t *counts, uint32_t n_entries,
+                             uint8_t *table, hipStream_t stream)
+{
+	hipLaunchKernelGGL(vgsdf::family_tables_pass<true>, dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces, n_faces,
+	                   const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table);
+	return (int)hipGetLastError();
+}
+
+} // extern "C"

@@ -177,6 +177,13 @@ int vg_manager_family_stats(const vg_manager *m, vg_family_stats *out)
 	*out = vg_family_stats{t.family_groups, t.families_uploaded, t.family_bytes, t.family_block_bytes};
 	return 0;
 }
+void vg_manager_set_family_tables_on_device(vg_manager *m, int on) { m->m.set_family_tables_on_device(on != 0); }
+int vg_manager_family_table_stats(const vg_manager *m, vg_family_table_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_family_table_stats{t.family_tables_built, t.family_table_fallbacks};
+	return 0;
+}
 void vg_manager_set_lane_form(vg_manager *m, int form) { m->m.set_lane_form(form < 0 || form > 2 ? -1 : form); }
 void vg_manager_set_threads(vg_manager *m, unsigned threads, unsigned blocks_per_batch)
 {
@@ -801,6 +808,35 @@ int vg_manager_family_desc(const vg_manager *m, const char *font_id, vg_family_v
 		view->advance = t->advance.data();
 		view->scale = t->scale.data();
 		view->shift_x = t->shift_x.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_family_tables_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_face_tables *desc)
+{
+	try {
+		if (!m || !font_id || !desc || file_index < 0) {
+			g_err = "vg_manager_family_tables_desc: bad argument";
+			return -1;
+		}
+		auto it = m->m.fonts().find(font_id);
+		if (it == m->m.fonts().end() || (size_t)file_index >= it->second.files().size()) {
+			g_err = std::string("unknown font id ") + font_id + ", or a file index past its files";
+			return -1;
+		}
+		const vg::FamilyTables &t = it->second.files()[(size_t)file_index]->face().family_tables();
+		if (!t.ok) {
+			g_err = std::string("refused: font ") + font_id + ": a cmap subtable whose segments or groups are not regular";
+			return -1;
+		}
+		desc->cmap = t.cmap, desc->cmap_len = t.cmap_len;
+		desc->hmtx = t.hmtx, desc->hmtx_len = t.hmtx_len;
+		desc->units_per_em = t.units_per_em, desc->num_glyphs = t.num_glyphs, desc->num_hmetrics = t.num_hmetrics;
+		desc->n_subtables = (uint16_t)t.subtable_off.size();
+		desc->subtable_off = t.subtable_off.data();
+		desc->subtable_format = t.subtable_format.data();
 		return 0;
 	} catch (const std::exception &e) {
 		g_err = e.what();

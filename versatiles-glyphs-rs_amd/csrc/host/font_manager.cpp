@@ -565,6 +565,28 @@ const CharstringTable *FontManager::charstring2_table(const std::string &font_id
 	return file_table(font_id, file_index, &Face::charstring2_table, "the file has no `CFF2` charstrings the device's decoder could be given", err);
 }
 
+namespace {
+uint64_t next_family_serial()
+{
+	static std::atomic<uint64_t> next_serial{1};
+	return next_serial++;
+}
+} // namespace
+
+FontManager::FamilyTable *FontManager::family_shell(const std::string &font_id, size_t n_files) const
+{
+	if (parent_)
+		return parent_->family_shell(font_id, n_files);
+	std::lock_guard<std::mutex> lock(family_mu_);
+	std::unique_ptr<FamilyTable> &slot = family_shells_[font_id];
+	if (!slot || slot->n_files != n_files) {
+		slot = std::make_unique<FamilyTable>();
+		slot->serial = next_family_serial();
+		slot->n_files = n_files;
+	}
+	return slot.get();
+}
+
 const FontManager::FamilyTable *FontManager::family_table(const std::string &font_id, std::string *err) const
 {
 	const FontEntry *it = find_font(font_id, err);
@@ -591,8 +613,7 @@ const FontManager::FamilyTable *FontManager::family_table(const std::string &fon
 			if (const FontFileEntry *f = b.glyphs[ci])
 				Renderer::record_resident(f->face(), file_of.at(f), b.start_index + ci, all);
 	auto t = std::make_unique<FamilyTable>();
-	static std::atomic<uint64_t> next_serial{1};
-	t->serial = next_serial++;
+	t->serial = next_family_serial();
 	t->n_files = files.size();
 	for (const GlyphJob &j : all.jobs) {
 		t->code_point.push_back((uint16_t)j.id);

@@ -158,6 +158,9 @@ struct RenderTimings {
 	// command stores the device decoded from charstrings (set_charstrings_on_device; counted among command_fonts_uploaded too),
 	// their bytes, and faces it refused, whose stores were built from the host reader's table instead
 	uint64_t charstring_fonts_decoded = 0, charstring_font_bytes = 0, charstring_fallbacks = 0;
+	// families whose tables the device built from cmap and hmtx (set_family_tables_on_device; counted among families_uploaded
+	// too), and font ids whose description refused or whose build the device refused: their families were made the host's way
+	uint64_t family_tables_built = 0, family_table_fallbacks = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -184,10 +187,11 @@ struct RenderTimings {
 		families_uploaded += counts.families_uploaded, family_bytes += counts.family_bytes;
 		charstring_fonts_decoded += counts.charstring_fonts_decoded, charstring_font_bytes += counts.charstring_font_bytes;
 		charstring_fallbacks += counts.charstring_fallbacks;
+		family_tables_built += counts.family_tables_built, family_table_fallbacks += counts.family_table_fallbacks;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 25 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 27 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -282,6 +286,10 @@ public:
 	// one per run of code points for a block the hybrid lane plan has split — and the device writes the PBF entries; recording
 	// is O(tasks).  With glyph sharding on (set_glyph_shard, lane form 0) groups go by glyph names as without the switch
 	void set_resident_families(bool on) { resident_families_ = on; }
+	// Family tables on the device (default off): a resident family's table is built by the device from the faces' cmap and hmtx
+	// tables (Face::family_tables, vgsdf_family_create_tables) and family_table() below is not built for the font id; a font id
+	// whose description refuses, or whose build the device refuses, gets its family the host's way (remembered).  Same table bytes.
+	void set_family_tables_on_device(bool on) { family_tables_on_device_ = on; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
 	// returns the bytes put on the devices
 	uint64_t preload_resident_fonts(const Renderer &renderer) const;
@@ -306,6 +314,9 @@ public:
 	struct FamilyTable {
 		uint64_t serial = 0; // of this build of the table (a rebuilt table is another family on the device)
 		size_t n_files = 0;
+		// a table the DEVICE builds (family_shell): code_point and advance are the family's read-back, filled when the first
+		// device has built it, the other arrays stay empty; refused: the faces' description refuses, the host builds the table
+		bool filled = false, refused = false;
 		std::vector<uint16_t> code_point, font_of, glyph_id;
 		std::vector<uint32_t> advance;
 		std::vector<double> scale, shift_x;
@@ -320,7 +331,12 @@ private:
 	template <class Table>
 	const Table *file_table(const std::string &font_id, size_t file_index, const Table &(Face::*table)() const, const char *why, std::string *err) const;
 	mutable std::map<std::string, std::unique_ptr<FamilyTable>> family_tables_; // per font id
+	mutable std::map<std::string, std::unique_ptr<FamilyTable>> family_shells_; // per font id: set_family_tables_on_device
+	// the font id's table as the device builds it: serial and n_files at once, the names once a device has built it (rebuilt, as
+	// family_table, when a file is added)
+	FamilyTable *family_shell(const std::string &font_id, size_t n_files) const;
 	mutable std::mutex family_mu_;
+	std::mutex &family_mu_of() const { return parent_ ? parent_->family_mu_ : family_mu_; }
 	struct Todo {
 		const std::string *name;
 		const GlyphBlock &block; // lives in its FontWrapper's table
@@ -519,6 +535,7 @@ private:
 	bool resident_fonts_ = false;
 	int resident_commands_ = 0;
 	int charstrings_on_device_ = 0;
+	bool family_tables_on_device_ = false;
 	mutable RenderTimings preload_counts_;
 	// a face's command store on the renderer's device, by either path; counts into `counts`
 	const vgsdf_font *command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;

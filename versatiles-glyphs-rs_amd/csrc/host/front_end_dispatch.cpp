@@ -320,8 +320,9 @@ const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane,
 const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font,
                                                bool commands, const FamilyTable **table, RenderTimings &counts) const
 {
-	const FamilyTable *ft = family_table(font_id, nullptr);
-	if (!ft)
+	const bool on_device = family_tables_on_device_ && font.files().size() <= 0x10000;
+	const FamilyTable *ft = on_device ? nullptr : family_table(font_id, nullptr);
+	if (!ft && !on_device)
 		return nullptr;
 	std::vector<const vgsdf_font *> stores;
 	for (const auto &file : font.files()) {
@@ -334,6 +335,55 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 		stores.push_back(f);
 	}
 	uint64_t uploaded = 0;
+	if (on_device) {
+		// the faces' descriptions (no code point is looked up) and the device's build; a refusal of either sends the font id the
+		// host's way below, for good
+		FamilyTable *shell = family_shell(font_id, font.files().size());
+		std::vector<vgsdf_face_tables> descs;
+		for (const auto &file : font.files()) {
+			const FamilyTables &t = file->face().family_tables();
+			if (!t.ok) {
+				std::lock_guard<std::mutex> lock(family_mu_of());
+				if (!shell->refused)
+					counts.family_table_fallbacks++;
+				shell->refused = true;
+				break;
+			}
+			vgsdf_face_tables d;
+			d.cmap = t.cmap, d.cmap_len = t.cmap_len, d.hmtx = t.hmtx, d.hmtx_len = t.hmtx_len;
+			d.units_per_em = t.units_per_em, d.num_glyphs = t.num_glyphs, d.num_hmetrics = t.num_hmetrics;
+			d.n_subtables = (uint16_t)t.subtable_off.size();
+			d.subtable_off = t.subtable_off.data(), d.subtable_format = t.subtable_format.data();
+			descs.push_back(d);
+		}
+		if (descs.size() == font.files().size()) {
+			int refused = 0;
+			bool built = false;
+			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, commands, &uploaded, &refused, &built);
+			if (refused == 1)
+				counts.family_table_fallbacks++;
+			if (built) {
+				count_upload(uploaded, counts.families_uploaded, counts.family_bytes);
+				counts.family_tables_built++;
+			}
+			if (fam) {
+				std::lock_guard<std::mutex> lock(family_mu_of());
+				if (!shell->filled) {
+					renderer.family_names(lane, fam, shell->code_point, shell->advance);
+					shell->filled = true;
+				}
+			}
+			if (fam || !refused) { // (no family and no refusal: over the budget, as the host's way would be)
+				if (table)
+					*table = shell;
+				return fam;
+			}
+		}
+		uploaded = 0;
+		ft = family_table(font_id, nullptr);
+		if (!ft)
+			return nullptr;
+	}
 	const Renderer::FamilyArrays fa{ft->serial, &ft->code_point, &ft->font_of, &ft->glyph_id, &ft->advance, &ft->scale, &ft->shift_x};
 	const vgsdf_family *fam = renderer.family(lane, fa, stores, commands, &uploaded);
 	if (fam)

@@ -221,6 +221,7 @@ Renderer::~Renderer()
 				}
 		resident_->fonts.clear();
 		resident_->refused_charstrings.clear();
+		resident_->refused_family_tables.clear();
 		resident_->unfit_charstrings.clear();
 		resident_->bytes.clear();
 	}
@@ -612,6 +613,61 @@ const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std:
 	if (uploaded_bytes)
 		*uploaded_bytes += got;
 	return f;
+}
+
+const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
+                                                 const std::vector<const vgsdf_font *> &fonts, bool commands, uint64_t *uploaded_bytes, int *refused,
+                                                 bool *built) const
+{
+	if (mode_ != Mode::Hip)
+		return nullptr;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	const auto key = std::make_tuple(device_, serial, commands);
+	if (auto it = rf.families.find(key); it != rf.families.end())
+		return it->second;
+	if (rf.refused_family_tables.count(key)) {
+		*refused = 2;
+		return nullptr;
+	}
+	vgsdf_family_tables_desc d;
+	d.n_fonts = (uint32_t)fonts.size();
+	d.fonts = fonts.data();
+	d.tables = tables.data();
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	vgsdf_family *f = nullptr;
+	{
+		std::lock_guard<std::mutex> lock(mu_);
+		if (tables.size() != fonts.size() || vgsdf_family_create_tables(c, &d, &f) != VGSDF_OK) {
+			rf.refused_family_tables.insert(key);
+			*refused = 1;
+			return nullptr;
+		}
+		// the budget as family() holds it: the table's size is known behind the count pass
+		const uint64_t want = vgsdf::FamilyTableLayout(vgsdf_family_count(f, 0, 0xFFFF)).bytes;
+		if (rf.bytes[device_] + want > rf.budget) {
+			(void)vgsdf_family_free(c, f);
+			return nullptr;
+		}
+	}
+	const uint64_t got = vgsdf_family_device_bytes(f);
+	rf.families.emplace(key, f);
+	rf.bytes[device_] += got;
+	if (uploaded_bytes)
+		*uploaded_bytes += got;
+	*built = true;
+	return f;
+}
+
+void Renderer::family_names(int lane, const vgsdf_family *family, std::vector<uint16_t> &code_point, std::vector<uint32_t> &advance) const
+{
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	const uint32_t n = vgsdf_family_count(family, 0, 0xFFFF);
+	code_point.assign(n, 0);
+	advance.assign(n, 0);
+	std::lock_guard<std::mutex> lock(mu_);
+	if (vgsdf_family_read(c, family, nullptr, code_point.data(), nullptr, nullptr, advance.data(), nullptr, nullptr, nullptr, nullptr, nullptr) != VGSDF_OK)
+		throw std::runtime_error(std::string("vgsdf_family_read: ") + vgsdf_last_error(c));
 }
 
 void Renderer::submit_ranges(int lane, const vgsdf_outlines_ranges &v, uint32_t n_glyphs, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const

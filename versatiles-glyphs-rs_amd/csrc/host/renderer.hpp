@@ -483,6 +483,15 @@ public:
 	};
 	const vgsdf_family *family(int lane, const FamilyArrays &table, const std::vector<const vgsdf_font *> &fonts, bool commands,
 	                           uint64_t *uploaded_bytes = nullptr) const;
+	// the same family built by the DEVICE from the faces' cmap and hmtx tables (vgsdf_family_create_tables): same key (`serial`
+	// stands for the table's), same budget, same lifetime.  *refused: the device has returned an error for this (device, serial),
+	// 1 now or 2 earlier — the caller makes the family with family() instead; *built: this call put it on the device.  nullptr
+	// without *refused: over the budget
+	const vgsdf_family *family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
+	                                       const std::vector<const vgsdf_font *> &fonts, bool commands, uint64_t *uploaded_bytes, int *refused,
+	                                       bool *built) const;
+	// a family's code points and advances, read back (what a host that built no table names the glyphs of a ranges group by)
+	void family_names(int lane, const vgsdf_family *family, std::vector<uint16_t> &code_point, std::vector<uint32_t> &advance) const;
 	// a submission of code-point ranges of such families (n_glyphs: for the first capacity guess), and where its tasks'
 	// rooms begin in the arena once it has been peeked at or waited for
 	void submit_ranges(int lane, const vgsdf_outlines_ranges &batch, uint32_t n_glyphs, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const;
@@ -530,6 +539,7 @@ private:
 		std::map<std::tuple<int, uint64_t, bool>, vgsdf_family *> families; // (device, table serial, command stores) -> the family
 		std::map<int, uint64_t> bytes;                          // per device
 		std::set<std::pair<int, uint64_t>> refused_charstrings; // (device, serial): the device's decoder has refused the face
+		std::set<std::tuple<int, uint64_t, bool>> refused_family_tables; // the key of `families`: the device has refused to build the table
 		std::map<std::pair<int, uint64_t>, uint64_t> unfit_charstrings; // (device, serial) -> bytes of a store that passed the budget
 		uint64_t budget = 1ull << 30;
 	};

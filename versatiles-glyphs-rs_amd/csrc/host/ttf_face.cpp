@@ -107,6 +107,7 @@ std::optional<Face> Face::parse(const uint8_t *data, size_t len)
 	}
 	const Bytes cmap = find_table(file, "cmap");
 	f.has_cmap_ = cmap.has(0, 4);
+	f.cmap_table_ = cmap;
 	if (cmap.has(0, 4)) {
 		const uint16_t n = cmap.u16(2);
 		for (uint16_t i = 0; i < n; i++) {
@@ -117,6 +118,7 @@ std::optional<Face> Face::parse(const uint8_t *data, size_t len)
 			st.platform = cmap.u16(rec);
 			st.encoding = cmap.u16(rec + 2);
 			st.data = cmap.from(cmap.u32(rec + 4));
+			st.offset = cmap.u32(rec + 4);
 			if (st.data.has(0, 2))
 				st.format = st.data.u16(0);
 			f.cmap_.push_back(st);
@@ -416,6 +418,64 @@ std::vector<uint32_t> Face::unicode_codepoints() const
 	std::sort(cps.begin(), cps.end());
 	cps.erase(std::unique(cps.begin(), cps.end()), cps.end());
 	return cps;
+}
+
+// The description of cmap and hmtx for the device.  On REGULAR tables the bisection of glyph_index and the enumeration of
+// for_each_codepoint agree about the segment or group that holds a code point, which is what the device's statement rests on;
+// a table that is not regular is refused here and its family is built by the reader above.
+const FamilyTables &Face::family_tables() const
+{
+	FamilyCell &cell = *family_;
+	std::call_once(cell.once, [&] {
+		FamilyTables &t = cell.tables;
+		t.cmap = cmap_table_.data(), t.cmap_len = (uint32_t)std::min<size_t>(cmap_table_.size(), 0xFFFFFFFFu);
+		t.hmtx = hmtx_.data(), t.hmtx_len = (uint32_t)std::min<size_t>(hmtx_.size(), 0xFFFFFFFFu);
+		t.units_per_em = units_per_em_, t.num_glyphs = num_glyphs_, t.num_hmetrics = num_hmetrics_;
+		if (cmap_table_.size() > 0xFFFFFFFFu || hmtx_.size() > 0xFFFFFFFFu)
+			return;
+		for (const CmapSubtable &st : cmap_) {
+			if (st.format == 0xFFFF || !st.is_unicode())
+				continue;
+			const Bytes &d = st.data;
+			switch (st.format) {
+			case 0:
+			case 6:
+			case 10:
+				break;
+			case 4: {
+				const Format4 f4(d);
+				if (!f4.ok)
+					return;
+				for (size_t k = 0; k < f4.segs; k++) {
+					const uint16_t a = d.u16(f4.starts + k * 2), b = d.u16(f4.ends + k * 2);
+					if (a > b || (k && a <= d.u16(f4.ends + (k - 1) * 2)))
+						return;
+				}
+				break;
+			}
+			case 12:
+			case 13: {
+				if (!d.has(0, 16))
+					return;
+				const uint32_t n = d.u32(12);
+				if (!d.has(16, (size_t)n * 12))
+					return;
+				for (uint32_t k = 0; k < n; k++) {
+					const size_t g = 16 + (size_t)k * 12;
+					if (d.u32(g) > d.u32(g + 4) || (k && d.u32(g) <= d.u32(g - 12 + 4)))
+						return;
+				}
+				break;
+			}
+			default: // 2, 8, 14: glyph_index has no value for them
+				continue;
+			}
+			t.subtable_off.push_back(st.offset);
+			t.subtable_format.push_back(st.format);
+		}
+		t.ok = t.subtable_off.size() <= 0xFFFFu;
+	});
+	return cell.tables;
 }
 
 // ---- glyf ------------------------------------------------------------------------------

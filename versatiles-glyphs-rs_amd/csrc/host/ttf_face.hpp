@@ -92,6 +92,18 @@ struct CharstringTable {
 	std::vector<float> factors;
 };
 
+// A face's `cmap` and `hmtx` for the device's family-table kernels (vgsdf_face_tables of include/vgsdf.h, field for field): views of
+// the two tables and where the unicode subtables are.  No code point is looked up.
+struct FamilyTables {
+	bool ok = false;                       // false: a format 4 subtable whose segments, or a format 12 / 13 subtable whose groups, are
+	                                       // not regular (the device's bisection and the reader's enumeration could then disagree)
+	const uint8_t *cmap = nullptr, *hmtx = nullptr; // views into the face's bytes
+	uint32_t cmap_len = 0, hmtx_len = 0;
+	uint16_t units_per_em = 0, num_glyphs = 0, num_hmetrics = 0;
+	std::vector<uint32_t> subtable_off;    // into cmap: the encoding records, in the table's order, that are unicode and of format
+	std::vector<uint16_t> subtable_format; // 0, 4, 6, 10, 12 or 13 (2, 8, 14 and unreadable ones map nothing and are left out)
+};
+
 // Non-owning big-endian byte view with checked reads.
 class Bytes {
 public:
@@ -155,6 +167,8 @@ public:
 	// The same of a `CFF2` face, with its blend sets (not ok for every other face, and for one whose local subroutines are more
 	// than the description's 65535).
 	const CharstringTable &charstring2_table() const;
+	// The face's tables for the device's family-table kernels: built once, on first use (thread-safe).
+	const FamilyTables &family_tables() const;
 	// ttf-parser's `tables().cmap.is_some()`; the reference refuses fonts without one (metadata.rs:104-107)
 	bool has_cmap() const { return has_cmap_; }
 	// glyph outlines this reader can emit: `glyf` + `loca`, or `CFF ` charstrings (ttf-parser's order: glyf first).
@@ -174,6 +188,7 @@ private:
 	struct CmapSubtable {
 		uint16_t platform = 0, encoding = 0, format = 0xFFFF;
 		Bytes data; // from the subtable start to the end of the cmap table
+		uint32_t offset = 0; // of the subtable in the cmap table
 		bool is_unicode() const;
 		std::optional<uint16_t> glyph_index(uint32_t cp) const;
 		template <class F> void for_each_codepoint(F &&f) const;
@@ -181,7 +196,7 @@ private:
 
 	std::optional<Bytes> glyph_data(uint16_t glyph_id) const;
 
-	Bytes hmtx_, loca_, glyf_, name_;
+	Bytes hmtx_, loca_, glyf_, name_, cmap_table_;
 	std::vector<CmapSubtable> cmap_;
 	uint16_t units_per_em_ = 0, num_glyphs_ = 0, num_hmetrics_ = 0;
 	bool loca_long_ = false, has_cmap_ = false, cff_unreadable_ = false;
@@ -199,6 +214,11 @@ private:
 		CharstringTable charstrings, charstrings2;
 	};
 	std::shared_ptr<CommandCell> commands_ = std::make_shared<CommandCell>();
+	struct FamilyCell {
+		std::once_flag once;
+		FamilyTables tables;
+	};
+	std::shared_ptr<FamilyCell> family_ = std::make_shared<FamilyCell>();
 
 	template <class B, bool PARTS> friend struct GlyfWalker;
 };

@@ -11,6 +11,7 @@
 
 #include "charstring_kernels.h"
 #include "charstring_limits.h"
+#include "family_table_kernels.h"
 #include "outline_kernels.h"
 #include "resident_fonts.h"
 #include "work_plan.h"
@@ -641,6 +642,209 @@ int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_famil
 	if (e != hipSuccess)
 		return font_hip_error(ctx, "vgsdf_family_create", "upload", e);
 	*out = f.release();
+	return VGSDF_OK;
+}
+
+int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->fonts || !in->tables) {
+		ctx->err = "vgsdf_family_create_tables: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	ctx->family_tables_ms[0] = ctx->family_tables_ms[1] = 0.0f;
+	const uint32_t n_fonts = in->n_fonts;
+	if (n_fonts == 0 || n_fonts > 0x10000u) {
+		ctx->err = "vgsdf_family_create_tables: n_fonts must be 1 .. 65536";
+		return VGSDF_E_ARG;
+	}
+	// what can be said without a lookup; the staging block's layout on the way:
+	// FamilyFaceRef[n_fonts] | FamilySubtable[all] | per face cmap, hmtx (4-aligned) | counts | flags
+	size_t n_subtables = 0, table_bytes = 0;
+	for (uint32_t k = 0; k < n_fonts; k++) {
+		const vgsdf_font *ft = in->fonts[k];
+		const vgsdf_face_tables &t = in->tables[k];
+		if (!ft || ft->device != ctx->device || ft->commands != in->fonts[0]->commands) {
+			ctx->err = "vgsdf_family_create_tables: a NULL font, a font of another device than the context's, or fonts of both kinds";
+			return VGSDF_E_ARG;
+		}
+		if ((t.cmap_len && !t.cmap) || (t.hmtx_len && !t.hmtx) || (t.n_subtables && (!t.subtable_off || !t.subtable_format))) {
+			ctx->err = "vgsdf_family_create_tables: a NULL table or subtable array of a length that is not 0";
+			return VGSDF_E_ARG;
+		}
+		if (t.units_per_em < 16 || t.units_per_em > 16384) {
+			ctx->err = "vgsdf_family_create_tables: units_per_em not 16 .. 16384";
+			return VGSDF_E_ARG;
+		}
+		for (uint32_t s = 0; s < t.n_subtables; s++) {
+			const uint16_t fm = t.subtable_format[s];
+			if (t.subtable_off[s] >= t.cmap_len || !(fm == 0 || fm == 4 || fm == 6 || fm == 10 || fm == 12 || fm == 13)) {
+				ctx->err = "vgsdf_family_create_tables: a subtable offset at or past cmap_len, or a format that is not 0, 4, 6, 10, 12 or 13";
+				return VGSDF_E_ARG;
+			}
+		}
+		n_subtables += t.n_subtables;
+		table_bytes += align_up(t.cmap_len, 4) + align_up(t.hmtx_len, 4);
+	}
+	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
+	if (!f) {
+		ctx->err = "vgsdf_family_create_tables: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	f->device = ctx->device;
+	f->commands = in->fonts[0]->commands;
+	f->fonts.assign(in->fonts, in->fonts + n_fonts);
+	for (const vgsdf_font *ft : f->fonts) {
+		f->max_cap = std::max(f->max_cap, ft->max_cap);
+		f->max_len = std::max(f->max_len, ft->max_len);
+	}
+	const size_t a_subs = sizeof(vgsdf::FamilyFaceRef) * (size_t)n_fonts, a_bytes = a_subs + sizeof(vgsdf::FamilySubtable) * n_subtables,
+	             a_counts = align_up(a_bytes + table_bytes, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
+	             a_total = a_flags + 16;
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	ScratchBuf dev;
+	if (hipError_t e = dev.ensure(a_total); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipMalloc", e);
+	uint8_t *d = (uint8_t *)dev.p;
+	std::vector<uint8_t> h(a_counts, 0);
+	{
+		vgsdf::FamilyFaceRef *faces = (vgsdf::FamilyFaceRef *)h.data();
+		vgsdf::FamilySubtable *subs = (vgsdf::FamilySubtable *)(h.data() + a_subs);
+		size_t at_sub = 0, at_byte = a_bytes;
+		for (uint32_t k = 0; k < n_fonts; k++) {
+			const vgsdf_font &ft = *in->fonts[k];
+			const vgsdf_face_tables &t = in->tables[k];
+			vgsdf::FamilyFaceRef &r = faces[k];
+			r.subtables = (uint64_t)(uintptr_t)(d + a_subs + sizeof(vgsdf::FamilySubtable) * at_sub);
+			for (uint32_t s = 0; s < t.n_subtables; s++)
+				subs[at_sub++] = vgsdf::FamilySubtable{t.subtable_off[s], t.subtable_format[s]};
+			r.cmap = (uint64_t)(uintptr_t)(d + at_byte);
+			if (t.cmap_len)
+				std::memcpy(h.data() + at_byte, t.cmap, t.cmap_len);
+			at_byte += align_up(t.cmap_len, 4);
+			r.hmtx = t.hmtx_len ? (uint64_t)(uintptr_t)(d + at_byte) : 0;
+			if (t.hmtx_len)
+				std::memcpy(h.data() + at_byte, t.hmtx, t.hmtx_len);
+			at_byte += align_up(t.hmtx_len, 4);
+			r.off = ft.commands ? ft.cref.cmd_off : ft.ref.leaf_off;
+			r.leaves = ft.commands ? 0 : ft.ref.leaves;
+			r.cmap_len = t.cmap_len, r.hmtx_len = t.hmtx_len;
+			r.n_glyph_ids = ft.n_glyph_ids;
+			r.units_per_em = t.units_per_em, r.num_glyphs = t.num_glyphs, r.num_hmetrics = t.num_hmetrics, r.n_subtables = t.n_subtables;
+			r.commands = ft.commands ? 1u : 0u;
+		}
+	}
+	struct Events {
+		hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+		~Events()
+		{
+			for (hipEvent_t ev : e)
+				if (ev)
+					(void)hipEventDestroy(ev);
+		}
+	} ev;
+	for (hipEvent_t &e : ev.e)
+		if (hipError_t err = hipEventCreate(&e); err != hipSuccess)
+			return font_hip_error(ctx, "vgsdf_family_create_tables", "hipEventCreate", err);
+	const vgsdf::FamilyFaceRef *faces = (const vgsdf::FamilyFaceRef *)d;
+	uint32_t *counts = (uint32_t *)(d + a_counts), *flags = (uint32_t *)(d + a_flags);
+	hipError_t e = hipMemcpyAsync(d, h.data(), h.size(), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess)
+		e = hipMemsetAsync(d + a_flags, 0, 16, st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[0], st);
+	if (e == hipSuccess)
+		e = (hipError_t)vgsdf_family_tables_count(faces, n_fonts, counts, flags, st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[1], st);
+	uint32_t got[vgsdf::kFamilyCounts * vgsdf::kFamilyGroups + 1]; // the counts and, behind them, the flag word
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(got, counts, sizeof got, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st);
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "count pass", e);
+	(void)hipEventElapsedTime(&ctx->family_tables_ms[0], ev.e[0], ev.e[1]);
+	if (got[vgsdf::kFamilyCounts * vgsdf::kFamilyGroups]) {
+		ctx->err = "vgsdf_family_create_tables: a glyph id past its face";
+		return VGSDF_E_ARG;
+	}
+	uint32_t n = 0;
+	for (uint32_t w = 0; w < vgsdf::kFamilyGroups; w++)
+		n += got[vgsdf::kFamilyCounts * w];
+	// the table as vgsdf_family_create allocates it (the same size: the same vgsdf_family_device_bytes)
+	const vgsdf::FamilyTableLayout at(n);
+	if (hipError_t err = f->table.ensure(at.bytes + 16); err != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipMalloc", err);
+	std::vector<uint8_t> back(at.bytes);
+	e = hipEventRecord(ev.e[1], st);
+	if (e == hipSuccess)
+		e = (hipError_t)vgsdf_family_tables_emit(faces, n_fonts, counts, n, (uint8_t *)f->table.p, st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[2], st);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(back.data(), f->table.p, at.bytes, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st); // the table is complete when the call returns: every context may name the family
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "emit pass", e);
+	(void)hipEventElapsedTime(&ctx->family_tables_ms[1], ev.e[1], ev.e[2]);
+	// the host's copy from the one read-back; the 64-bit running sums from the table's differences (exact: a glyph holds fewer
+	// than 2^31 slots and fewer than 2^32 leaves)
+	auto slice = [&](auto &v, size_t off, size_t count) {
+		v.resize(count);
+		if (count)
+			std::memcpy(v.data(), back.data() + off, sizeof(v[0]) * count);
+	};
+	slice(f->scale, at.scale, n), slice(f->shift_x, at.shift_x, n), slice(f->advance, at.advance, n), slice(f->code_point, at.code_point, n);
+	slice(f->font_of, at.font_of, n), slice(f->glyph_id, at.glyph_id, n), slice(f->pbf_fix, at.pbf_fix, n);
+	f->cmd_pre.assign((size_t)n + 1, 0);
+	f->leaf_pre.assign((size_t)n + 1, 0);
+	const uint32_t *cp32 = (const uint32_t *)(back.data() + at.cmd_pre), *lp32 = (const uint32_t *)(back.data() + at.leaf_pre);
+	for (uint32_t i = 0; i < n; i++) {
+		f->cmd_pre[i + 1] = f->cmd_pre[i] + (uint32_t)(cp32[i + 1] - cp32[i]);
+		f->leaf_pre[i + 1] = f->leaf_pre[i] + (uint32_t)(lp32[i + 1] - lp32[i]);
+	}
+	// (scales_plain stays true: every scale is 24 / units_per_em of a checked units_per_em)
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2])
+{
+	if (ms)
+		ms[0] = ctx ? ctx->family_tables_ms[0] : 0.0f, ms[1] = ctx ? ctx->family_tables_ms[1] : 0.0f;
+}
+
+int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_entries, uint16_t *code_point, uint16_t *font_of,
+                      uint16_t *glyph_id, uint32_t *advance, double *scale, double *shift_x, uint32_t *cmd_pre, uint32_t *leaf_pre,
+                      uint8_t *pbf_fix)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!family || family->device != ctx->device) {
+		ctx->err = "vgsdf_family_read: no family, or a family of another device than the context's";
+		return VGSDF_E_ARG;
+	}
+	const size_t n = family->code_point.size();
+	if (n_entries)
+		*n_entries = (uint32_t)n;
+	(void)hipSetDevice(ctx->device);
+	const vgsdf::FamilyTableLayout at(n);
+	const uint8_t *t = (const uint8_t *)family->table.p;
+	auto read = [&](void *dst, size_t off, size_t bytes) { return dst && bytes ? hipMemcpy(dst, t + off, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+	HIP_TRY(ctx, read(code_point, at.code_point, 2 * n));
+	HIP_TRY(ctx, read(font_of, at.font_of, 2 * n));
+	HIP_TRY(ctx, read(glyph_id, at.glyph_id, 2 * n));
+	HIP_TRY(ctx, read(advance, at.advance, 4 * n));
+	HIP_TRY(ctx, read(scale, at.scale, 8 * n));
+	HIP_TRY(ctx, read(shift_x, at.shift_x, 8 * n));
+	HIP_TRY(ctx, read(cmd_pre, at.cmd_pre, 4 * (n + 1)));
+	HIP_TRY(ctx, read(leaf_pre, at.leaf_pre, 4 * (n + 1)));
+	HIP_TRY(ctx, read(pbf_fix, at.pbf_fix, n));
 	return VGSDF_OK;
 }
 

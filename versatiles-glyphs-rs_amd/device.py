@@ -87,6 +87,16 @@ class _CFamilyDesc(C.Structure):  # vgsdf_family_desc
                 ("font_of", C.c_void_p), ("glyph_id", C.c_void_p), ("advance", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p)]
 
 
+class _CFaceTables(C.Structure):  # vgsdf_face_tables
+    _fields_ = [("cmap", C.c_void_p), ("cmap_len", C.c_uint32), ("hmtx", C.c_void_p), ("hmtx_len", C.c_uint32),
+                ("units_per_em", C.c_uint16), ("num_glyphs", C.c_uint16), ("num_hmetrics", C.c_uint16), ("n_subtables", C.c_uint16),
+                ("subtable_off", C.c_void_p), ("subtable_format", C.c_void_p)]
+
+
+class _CFamilyTablesDesc(C.Structure):  # vgsdf_family_tables_desc
+    _fields_ = [("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("tables", C.c_void_p)]
+
+
 class _COutlinesRanges(C.Structure):  # vgsdf_outlines_ranges
     _fields_ = [("n_tasks", C.c_uint32), ("n_families", C.c_uint32), ("families", C.c_void_p), ("family_of", C.c_void_p),
                 ("first", C.c_void_p), ("last", C.c_void_p), ("pbf_pre", C.c_void_p)]
@@ -101,7 +111,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_font_create", "vgsdf_font_free", "vgsdf_font_device_bytes", "vgsdf_outlines_submit_resident", "vgsdf_outlines_resident_upload_bytes",
     "vgsdf_font_create_commands", "vgsdf_font_create_charstrings", "vgsdf_font_create_charstrings_within", "vgsdf_font_create_charstrings2", "vgsdf_font_create_charstrings2_within", "vgsdf_font_charstrings_kernel_ms", "vgsdf_font_commands_read",
     "vgsdf_family_create", "vgsdf_family_free", "vgsdf_family_device_bytes", "vgsdf_family_count", "vgsdf_outlines_submit_ranges",
-    "vgsdf_outlines_task_extents",
+    "vgsdf_outlines_task_extents", "vgsdf_family_create_tables", "vgsdf_family_read", "vgsdf_family_tables_kernel_ms",
 ]
 
 _lib = None
@@ -169,6 +179,10 @@ def load_library():
         L.vgsdf_family_device_bytes.restype = C.c_uint64
         L.vgsdf_family_count.argtypes = [vp, C.c_uint32, C.c_uint32]
         L.vgsdf_family_count.restype = C.c_uint32
+        L.vgsdf_family_create_tables.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), C.POINTER(vp)]
+        L.vgsdf_family_read.argtypes = [vp, vp, C.POINTER(C.c_uint32)] + [vp] * 9
+        L.vgsdf_family_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_family_tables_kernel_ms.restype = None
         L.vgsdf_outlines_submit_ranges.argtypes = [vp, vp, vp, C.c_size_t]
         L.vgsdf_outlines_task_extents.argtypes = [vp, vp]
         L.vgsdf_add_counters.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64]
@@ -623,6 +637,46 @@ class SdfContext:
         h = C.c_void_p()
         self._check(load_library().vgsdf_family_create(self._h, C.byref(d), C.byref(h)))
         return ResidentFamily(self, h, fonts)
+
+    def family_create_tables(self, fonts, faces) -> ResidentFamily:
+        """vgsdf_family_create_tables: the family of `fonts` (ResidentFont, one kind, provider order) built on the device from
+        `faces`, one dict per font as FontManager.family_tables_desc returns it: {cmap, hmtx (bytes or uint8 arrays),
+        units_per_em, num_glyphs, num_hmetrics, subtable_off, subtable_format}"""
+        assert len(fonts) == len(faces)
+        keep, recs = [], (_CFaceTables * max(len(faces), 1))()
+        for r, t in zip(recs, faces):
+            cmap, hmtx = np.frombuffer(bytes(t["cmap"]), dtype=np.uint8), np.frombuffer(bytes(t["hmtx"]), dtype=np.uint8)
+            off = np.ascontiguousarray(t["subtable_off"], dtype=np.uint32)
+            fmt = np.ascontiguousarray(t["subtable_format"], dtype=np.uint16)
+            assert len(off) == len(fmt)
+            keep += [cmap, hmtx, off, fmt]
+            r.cmap, r.cmap_len = (cmap.ctypes.data if len(cmap) else None), len(cmap)
+            r.hmtx, r.hmtx_len = (hmtx.ctypes.data if len(hmtx) else None), len(hmtx)
+            r.units_per_em, r.num_glyphs, r.num_hmetrics = int(t["units_per_em"]), int(t["num_glyphs"]), int(t["num_hmetrics"])
+            r.n_subtables = len(off)
+            r.subtable_off, r.subtable_format = (off.ctypes.data if len(off) else None), (fmt.ctypes.data if len(fmt) else None)
+        handles = (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts])
+        d = _CFamilyTablesDesc(len(fonts), C.cast(handles, C.c_void_p), C.cast(recs, C.c_void_p))
+        h = C.c_void_p()
+        self._check(load_library().vgsdf_family_create_tables(self._h, C.byref(d), C.byref(h)))
+        return ResidentFamily(self, h, fonts)
+
+    def family_read(self, family: ResidentFamily) -> dict:
+        """vgsdf_family_read: the DEVICE's copy of a family's table, whichever call made it"""
+        L, n = load_library(), C.c_uint32()
+        self._check(L.vgsdf_family_read(self._h, family._h, C.byref(n), *[None] * 9))
+        n = n.value
+        a = {"code_point": np.zeros(n, np.uint16), "font_of": np.zeros(n, np.uint16), "glyph_id": np.zeros(n, np.uint16),
+             "advance": np.zeros(n, np.uint32), "scale": np.zeros(n, np.float64), "shift_x": np.zeros(n, np.float64),
+             "cmd_pre": np.zeros(n + 1, np.uint32), "leaf_pre": np.zeros(n + 1, np.uint32), "pbf_fix": np.zeros(n, np.uint8)}
+        self._check(L.vgsdf_family_read(self._h, family._h, None, *[v.ctypes.data for v in a.values()]))
+        return a
+
+    def family_tables_kernel_ms(self):
+        """(count, emit) milliseconds of the kernels of this context's last family_create_tables"""
+        ms = (C.c_float * 2)()
+        load_library().vgsdf_family_tables_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
 
     def outlines_submit_ranges(self, families, family_of, first, last, capacity: int, pbf_pre=None, fill=None, pinned=True):
         """outlines_submit for code-point ranges of resident families (vgsdf_outlines_ranges): task t is the mapped code points of

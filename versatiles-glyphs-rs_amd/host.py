@@ -48,6 +48,16 @@ class ResidentStats(C.Structure):  # vg_resident_stats
     _fields_ = [(k, C.c_uint64) for k in ("groups", "fonts_uploaded", "font_bytes", "block_bytes")]
 
 
+class _CFaceTables(C.Structure):  # vgsdf_face_tables
+    _fields_ = [("cmap", C.c_void_p), ("cmap_len", C.c_uint32), ("hmtx", C.c_void_p), ("hmtx_len", C.c_uint32),
+                ("units_per_em", C.c_uint16), ("num_glyphs", C.c_uint16), ("num_hmetrics", C.c_uint16), ("n_subtables", C.c_uint16),
+                ("subtable_off", C.c_void_p), ("subtable_format", C.c_void_p)]
+
+
+class FamilyTableStats(C.Structure):  # vg_family_table_stats
+    _fields_ = [(k, C.c_uint64) for k in ("built_on_device", "fallbacks")]
+
+
 class CharstringStats(C.Structure):  # vg_charstring_stats
     _fields_ = [(k, C.c_uint64) for k in ("fonts_decoded", "font_bytes", "fallbacks")]
 
@@ -73,6 +83,7 @@ VGFONT_SYMBOLS = [
     "vg_manager_shard_glyphs", "vg_manager_set_glyph_shard", "vg_pbf_merge", "vg_pbf_concat",
     "vg_renderer_new_multi", "vg_renderer_device_count", "vg_renderer_reduce_counters", "vg_renderer_reduce_path", "vg_renderer_add_counters",
     "vg_renderer_reset_counters", "vg_manager_reduced_counters", "vg_manager_set_in_place_pbf", "vg_manager_set_glyf_on_device", "vg_manager_set_lane_form", "vg_manager_plan_lanes",
+    "vg_manager_family_tables_desc", "vg_manager_set_family_tables_on_device", "vg_manager_family_table_stats",
 ]
 
 _bound = False
@@ -115,6 +126,10 @@ def _L():
         L.vg_manager_set_resident_families.restype = None
         L.vg_manager_family_stats.argtypes = [vp, C.POINTER(ResidentStats)]
         L.vg_manager_family_desc.argtypes = [vp, C.c_char_p, vp]
+        L.vg_manager_family_tables_desc.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(_CFaceTables)]
+        L.vg_manager_set_family_tables_on_device.argtypes = [vp, C.c_int]
+        L.vg_manager_set_family_tables_on_device.restype = None
+        L.vg_manager_family_table_stats.argtypes = [vp, C.POINTER(FamilyTableStats)]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -385,6 +400,17 @@ class FontManager:
     def set_resident_families(self, on: bool):
         """groups that would go by (font, glyph id) go as code-point ranges of resident families instead (default off)"""
         _L().vg_manager_set_resident_families(self._h, int(bool(on)))
+
+    def set_family_tables_on_device(self, on: bool):
+        """resident families' tables are built by the device from the faces' cmap and hmtx tables (vgsdf_family_create_tables)
+        instead of by the host's reader; a font id whose description or build is refused falls back; same bytes (default off)"""
+        _L().vg_manager_set_family_tables_on_device(self._h, int(bool(on)))
+
+    def family_table_stats(self) -> dict:
+        """of the last render: {built_on_device, fallbacks} (vg_family_table_stats)"""
+        s = FamilyTableStats()
+        _L().vg_manager_family_table_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in FamilyTableStats._fields_}
 
     def family_stats(self) -> dict:
         """of the last render: groups submitted as ranges, families uploaded, their bytes, block bytes (vg_family_stats)"""
@@ -714,6 +740,27 @@ class FontManager:
         return {"code_point": arr(v.code_point, np.uint16), "font_of": arr(v.font_of, np.uint16), "glyph_id": arr(v.glyph_id, np.uint16),
                 "advance": arr(v.advance, np.uint32), "scale": arr(v.scale, np.float64), "shift_x": arr(v.shift_x, np.float64),
                 "n_files": int(v.n_files)}
+
+    def family_tables_desc(self, font_id: str, file_index: int):
+        """the description of one file's cmap and hmtx for SdfContext.family_create_tables (vg_manager_family_tables_desc), no
+        device needed and no code point looked up: {cmap, hmtx (bytes), units_per_em, num_glyphs, num_hmetrics, subtable_off,
+        subtable_format}, copies.  None: the description refuses (a cmap subtable that is not regular)"""
+        L = _L()
+        d = _CFaceTables()
+        if L.vg_manager_family_tables_desc(self._h, font_id.encode(), int(file_index), C.byref(d)) != 0:
+            if _err().startswith("refused"):
+                return None
+            raise RuntimeError(_err())
+        n = d.n_subtables
+
+        def arr(ptr, dt):
+            if n == 0 or not ptr:
+                return np.zeros(0, dtype=dt)
+            return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt, count=n).copy()
+
+        return {"cmap": C.string_at(d.cmap, d.cmap_len) if d.cmap_len else b"", "hmtx": C.string_at(d.hmtx, d.hmtx_len) if d.hmtx_len else b"",
+                "units_per_em": int(d.units_per_em), "num_glyphs": int(d.num_glyphs), "num_hmetrics": int(d.num_hmetrics),
+                "subtable_off": arr(d.subtable_off, np.uint32), "subtable_format": arr(d.subtable_format, np.uint16)}
 
     def record_resident_commands(self, font_id: str) -> dict:
         """record_resident against command fonts: for any face the reader can read (CFF, CFF2, glyf)"""
