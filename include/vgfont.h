@@ -187,6 +187,19 @@ typedef struct {
 	uint64_t fallbacks;       /* font ids whose families came from the host's table although the switch is on */
 } vg_family_table_stats;
 int vg_manager_family_table_stats(const vg_manager *m, vg_family_table_stats *out);
+/* Glyf tables on the device, 0 (default) / 1: wherever the renderer makes a glyf-kind resident font — glyph-named groups, the
+ * families, vg_renderer_preload_fonts — the DEVICE walks the face's `loca` and `glyf` tables (vgsdf_font_create_tables); the host
+ * only says where the tables are (vg_manager_font_tables_desc) and interprets no glyph.  A face whose build the device refuses
+ * (a glyph that reads more than 2^20 component records, the bounds of the resident form, a device error) gets its font from the host's table
+ * as with 0, remembered per face and device.  Same registry key, budget and lifetime, same leaves and same output either way.
+ * vg_manager_glyf_table_stats: of the last render; the fonts built count among vg_resident_stats.fonts_uploaded too. */
+void vg_manager_set_glyf_tables_on_device(vg_manager *m, int on);
+typedef struct {
+	uint64_t built_on_device; /* fonts the device walked from loca and glyf during the render */
+	uint64_t bytes;           /* ... and what they occupy there */
+	uint64_t fallbacks;       /* faces whose fonts came from the host's table although the switch is on */
+} vg_glyf_table_stats;
+int vg_manager_glyf_table_stats(const vg_manager *m, vg_glyf_table_stats *out);
 /* How a renderer of several device lanes (vg_renderer_new_multi) splits a run: -1 / 2 (default) the hybrid plan — whole
  * (font, block) tasks per lane, manager.rs:86-97's unit, and the heaviest blocks' glyphs split between lanes until the lanes'
  * estimated raster cost is within 4 % of the mean; 1 whole tasks only; 0 glyph-level shards of every font (every block
@@ -365,6 +378,12 @@ int vg_manager_family_desc(const vg_manager *m, const char *font_id, vg_family_v
  * segments are not regular (segCountX2 >= 2, the arrays inside the table, start <= end, start above the previous end), or a
  * format 12 / 13 subtable whose groups are not ascending and disjoint inside the table; vg_last_error then begins "refused". */
 int vg_manager_family_tables_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_face_tables *desc);
+/* A `glyf` face stated by its TABLES, for vgsdf_font_create_tables (no device needed, and no glyph looked at): file `file_index`'s
+ * whole `loca` and `glyf` tables as views into the face, num_glyphs (maxp), the loca format (head) and the loca entries the reader
+ * goes by.  The device builds from it the leaves vg_manager_resident_font_desc states, with the simple entries' bytes in glyph-id
+ * order.  The pointers stay valid as long as the manager holds the font.  -1: unknown font / file, or a face without `glyf`
+ * outlines (vg_last_error then begins "refused"). */
+int vg_manager_font_tables_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_tables_desc *desc);
 
 /* Hand-encoder of the glyphs PBF (src/protobuf/glyphs.rs:66-70) for already rendered
  * glyphs; bitmaps[i] may be NULL when !has_bitmap. Returns needed size. */

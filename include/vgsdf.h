@@ -411,6 +411,43 @@ void vgsdf_font_charstrings_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
 int vgsdf_font_commands_read(vgsdf_ctx *ctx, const vgsdf_font *font, uint32_t *n_glyph_ids, uint32_t *n_cmds, uint32_t *cmd_off,
                              void *records, uint8_t *context);
 /*
+ * A `glyf` face's resident font built on the DEVICE from its `loca` and `glyf` tables: the host says where the tables are and
+ * looks at no glyph.  One lane per glyph id walks the glyph's component tree by the rules of the host reader (ttf-parser 0.25:
+ * the loca rules of both formats, a child that does not resolve is skipped, anchor-point arguments are not consumed, a
+ * truncated record ends its composite, a depth of 32 fails the glyph and keeps the leaves delivered so far, transforms composed
+ * in f32); a count pass sizes the arrays, the host lays them out, an emit pass writes them.  The result is the font
+ * vgsdf_font_create makes of
+ *   leaves    the host reader's, in its order; byte_off = byte_at[the simple glyph's id]
+ *   bytes     in GLYPH-ID order: for every glyph id whose own entry is a simple glyph of more than one point, its
+ *             endPtsOfContours followed by the bytes from behind its instructions to the end of the entry (nothing for an entry
+ *             whose two ranges pass 32 KB: byte_len 0), zero-padded to a multiple of 4; byte_at is the running sum
+ * and is used and freed like it.  Validated on the host, VGSDF_E_ARG, nothing allocated: a NULL argument (a table of length 0
+ * may be NULL), num_glyphs > 65535, loca_long > 1, loca_entries past what the loca bytes hold or past num_glyphs + 1 (a component could
+ * otherwise resolve to a glyph id the font has no place for).  Refused with VGSDF_E_GLYF,
+ * nothing left allocated, the context sound (the caller then describes the face with its host reader and calls
+ * vgsdf_font_create): a glyph id that reads more than 2^20 component records (a record counts when its four leading bytes have
+ * been read; the library's VGSDF_GLYF_MAX_COMPONENTS), more than 2^22 leaves, a glyph id of more than 2^26 command slots, a store past 2^32 - 4 bytes, command slots that sum past 2^32 - 1.
+ * _within: the budget form of vgsdf_font_create_charstrings_within; *needed is leaves + bytes + 4 per glyph id.
+ */
+typedef struct {
+	uint32_t num_glyphs;                 /* maxp */
+	uint32_t loca_entries;               /* min(num_glyphs + 1 (0xFFFF when num_glyphs == 0xFFFF), loca bytes / entry size) */
+	uint32_t loca_long;                  /* 0 or 1 */
+	uint32_t n_loca_bytes, n_glyf_bytes;
+	const uint8_t *loca, *glyf;          /* the whole tables as they stand in the file */
+} vgsdf_font_tables_desc;
+int vgsdf_font_create_tables(vgsdf_ctx *ctx, const vgsdf_font_tables_desc *in, vgsdf_font **out);
+int vgsdf_font_create_tables_within(vgsdf_ctx *ctx, const vgsdf_font_tables_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
+                                    uint64_t *needed);
+/* test / inspection: download a glyf-kind font's store, whichever call made it.  *n_glyph_ids / *n_leaves / *n_bytes: its counts
+ * (each may be NULL); leaf_off [n_glyph_ids + 1], leaves [n_leaves], bytes [n_bytes]: each NULL or filled.  A command font:
+ * VGSDF_E_ARG. */
+int vgsdf_font_read(vgsdf_ctx *ctx, const vgsdf_font *font, uint32_t *n_glyph_ids, uint32_t *n_leaves, uint32_t *n_bytes,
+                    uint32_t *leaf_off, vgsdf_glyf_part *leaves, uint8_t *bytes);
+/* test / inspection (tools/glyf_tables_ab.py): milliseconds the count pass and the emit pass (with its copy of the bytes) of the
+ * context's last vgsdf_font_create_tables took (HIP events around the pass; 0 0 before the first, and for a pass that did not run) */
+void vgsdf_font_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
+/*
  * Resident families: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id lives on the device
  * beside its fonts, and a submission names CODE-POINT RANGES of families instead of glyphs.  The host's share per submission
  * is O(tasks): the block it uploads holds 32 bytes per task that maps a glyph, per family and per font, and no per-glyph byte.

@@ -65,6 +65,7 @@ struct vgsdf_ctx {
 	void *charstring_spill = nullptr;
 	size_t charstring_spill_bytes = 0;
 	float family_tables_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_family_create_tables (resident_fonts.cpp)
+	float glyf_tables_ms[2] = {0.0f, 0.0f};   // count / emit kernels of the last vgsdf_font_create_tables (resident_fonts.cpp)
 	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
 };
 

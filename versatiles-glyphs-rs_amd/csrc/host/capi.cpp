@@ -178,6 +178,13 @@ int vg_manager_family_stats(const vg_manager *m, vg_family_stats *out)
 	return 0;
 }
 void vg_manager_set_family_tables_on_device(vg_manager *m, int on) { m->m.set_family_tables_on_device(on != 0); }
+void vg_manager_set_glyf_tables_on_device(vg_manager *m, int on) { m->m.set_glyf_tables_on_device(on != 0); }
+int vg_manager_glyf_table_stats(const vg_manager *m, vg_glyf_table_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_glyf_table_stats{t.glyf_tables_built, t.glyf_table_bytes, t.glyf_table_fallbacks};
+	return 0;
+}
 int vg_manager_family_table_stats(const vg_manager *m, vg_family_table_stats *out)
 {
 	const vg::RenderTimings &t = m->m.last_timings();
@@ -837,6 +844,32 @@ int vg_manager_family_tables_desc(const vg_manager *m, const char *font_id, int 
 		desc->n_subtables = (uint16_t)t.subtable_off.size();
 		desc->subtable_off = t.subtable_off.data();
 		desc->subtable_format = t.subtable_format.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_font_tables_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_tables_desc *desc)
+{
+	try {
+		if (!m || !font_id || !desc || file_index < 0) {
+			g_err = "vg_manager_font_tables_desc: bad argument";
+			return -1;
+		}
+		auto it = m->m.fonts().find(font_id);
+		if (it == m->m.fonts().end() || (size_t)file_index >= it->second.files().size()) {
+			g_err = std::string("unknown font id ") + font_id + ", or a file index past its files";
+			return -1;
+		}
+		const vg::FontTables t = it->second.files()[(size_t)file_index]->face().font_tables();
+		if (!t.ok) {
+			g_err = std::string("refused: font ") + font_id + ": no glyf outlines";
+			return -1;
+		}
+		desc->num_glyphs = t.num_glyphs, desc->loca_entries = t.loca_entries, desc->loca_long = t.loca_long;
+		desc->n_loca_bytes = t.n_loca_bytes, desc->n_glyf_bytes = t.n_glyf_bytes;
+		desc->loca = t.loca, desc->glyf = t.glyf;
 		return 0;
 	} catch (const std::exception &e) {
 		g_err = e.what();

@@ -161,6 +161,9 @@ struct RenderTimings {
 	// families whose tables the device built from cmap and hmtx (set_family_tables_on_device; counted among families_uploaded
 	// too), and font ids whose description refused or whose build the device refused: their families were made the host's way
 	uint64_t family_tables_built = 0, family_table_fallbacks = 0;
+	// glyf-kind fonts the device walked from loca and glyf (set_glyf_tables_on_device; counted among resident_fonts_uploaded too),
+	// their bytes, and faces whose build the device refused: their fonts were made from the host's table instead
+	uint64_t glyf_tables_built = 0, glyf_table_bytes = 0, glyf_table_fallbacks = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -188,10 +191,11 @@ struct RenderTimings {
 		charstring_fonts_decoded += counts.charstring_fonts_decoded, charstring_font_bytes += counts.charstring_font_bytes;
 		charstring_fallbacks += counts.charstring_fallbacks;
 		family_tables_built += counts.family_tables_built, family_table_fallbacks += counts.family_table_fallbacks;
+		glyf_tables_built += counts.glyf_tables_built, glyf_table_bytes += counts.glyf_table_bytes, glyf_table_fallbacks += counts.glyf_table_fallbacks;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 27 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 30 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -290,6 +294,11 @@ public:
 	// tables (Face::family_tables, vgsdf_family_create_tables) and family_table() below is not built for the font id; a font id
 	// whose description refuses, or whose build the device refuses, gets its family the host's way (remembered).  Same table bytes.
 	void set_family_tables_on_device(bool on) { family_tables_on_device_ = on; }
+	// Glyf tables on the device (default off): wherever the renderer makes a glyf-kind resident font — glyph-named groups, the
+	// families, preload_resident_fonts — the DEVICE walks the face's loca and glyf (Face::font_tables, vgsdf_font_create_tables)
+	// and Face::resident_table() is not built for the face; a face whose build the device refuses gets its font from the host's
+	// table (remembered per face and device).  Same leaves, same output.
+	void set_glyf_tables_on_device(bool on) { glyf_tables_on_device_ = on; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
 	// returns the bytes put on the devices
 	uint64_t preload_resident_fonts(const Renderer &renderer) const;
@@ -536,6 +545,9 @@ private:
 	int resident_commands_ = 0;
 	int charstrings_on_device_ = 0;
 	bool family_tables_on_device_ = false;
+	bool glyf_tables_on_device_ = false;
+	// a face's glyf-kind font on the renderer's device, by either path; counts into `counts`
+	const vgsdf_font *glyf_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
 	mutable RenderTimings preload_counts_;
 	// a face's command store on the renderer's device, by either path; counts into `counts`
 	const vgsdf_font *command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;

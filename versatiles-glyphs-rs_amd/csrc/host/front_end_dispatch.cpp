@@ -278,18 +278,36 @@ bool FontManager::fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, co
 		for (const auto &file : it->second.files()) {
 			if (m.fonts.size() >= 0xFFFF)
 				return false;
-			uint64_t uploaded = 0;
-			const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), timings_)
-			                               : renderer.resident_font(lane, file->face().resident_table(), &uploaded);
+			const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), timings_) : glyf_store(renderer, lane, file->face(), timings_);
 			if (!f)
 				return false;
-			count_upload(uploaded, timings_.resident_fonts_uploaded, timings_.resident_font_bytes);
 			index.emplace_back(file.get(), (uint16_t)m.fonts.size());
 			m.fonts.push_back(f);
 		}
 	}
 	std::sort(index.begin(), index.end());
 	return fe_record_slices(tasks, G, NamedForm{index, commands}, t0);
+}
+
+const vgsdf_font *FontManager::glyf_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const
+{
+	uint64_t uploaded = 0;
+	const vgsdf_font *f = nullptr;
+	if (glyf_tables_on_device_) {
+		bool refused = false, over_budget = false, built = false;
+		f = renderer.font_from_tables(lane, face.resident_serial(), face.font_tables(), &uploaded, &refused, &over_budget, &built);
+		if (refused)
+			counts.glyf_table_fallbacks++;
+		if (over_budget)
+			return nullptr; // (the host's table would make a font of the same leaves over the same budget: it is not built for that)
+		if (built)
+			counts.glyf_tables_built++, counts.glyf_table_bytes += uploaded;
+	}
+	if (!f)
+		f = renderer.resident_font(lane, face.resident_table(), &uploaded);
+	if (f)
+		count_upload(uploaded, counts.resident_fonts_uploaded, counts.resident_font_bytes);
+	return f;
 }
 
 const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const
@@ -326,12 +344,10 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 		return nullptr;
 	std::vector<const vgsdf_font *> stores;
 	for (const auto &file : font.files()) {
-		uint64_t uploaded = 0;
 		const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), counts)
-		                               : (file->face().has_glyf_outlines() ? renderer.resident_font(lane, file->face().resident_table(), &uploaded) : nullptr);
+		                               : (file->face().has_glyf_outlines() ? glyf_store(renderer, lane, file->face(), counts) : nullptr);
 		if (!f)
 			return nullptr;
-		count_upload(uploaded, counts.resident_fonts_uploaded, counts.resident_font_bytes);
 		stores.push_back(f);
 	}
 	uint64_t uploaded = 0;
@@ -474,8 +490,13 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 	for (size_t r = 0; r < renderer.n_devices(); r++)
 		for (const auto &kv : fonts())
 			for (const auto &file : kv.second.files())
-				if (file->face().has_glyf_outlines())
-					(void)renderer.device_lane(r).resident_font(0, file->face().resident_table(), &uploaded);
+				if (file->face().has_glyf_outlines()) {
+					RenderTimings counts;
+					(void)glyf_store(renderer.device_lane(r), 0, file->face(), counts);
+					uploaded += counts.resident_font_bytes;
+					if (glyf_tables_on_device_) // (with the switch off these uploads go into the returned total only, as they always have)
+						preload_counts_.add_uploads(counts);
+				}
 	// ... and the command stores the manager's mode would use: with 2 every face's, with 1 those of the fonts whose groups cannot
 	// take a glyf form (a file without `glyf` outlines, a font refused before)
 	if (resident_commands_)

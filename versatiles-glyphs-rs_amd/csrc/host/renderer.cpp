@@ -223,6 +223,8 @@ Renderer::~Renderer()
 		resident_->refused_charstrings.clear();
 		resident_->refused_family_tables.clear();
 		resident_->unfit_charstrings.clear();
+		resident_->refused_glyf_tables.clear();
+		resident_->unfit_glyf_tables.clear();
 		resident_->bytes.clear();
 	}
 	if (ctx2_)
@@ -472,6 +474,55 @@ const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint
 	rf.bytes[device_] += got;
 	if (uploaded_bytes)
 		*uploaded_bytes += got;
+	return f;
+}
+
+const vgsdf_font *Renderer::font_from_tables(int lane, uint64_t serial, const FontTables &t, uint64_t *uploaded_bytes, bool *refused,
+                                             bool *over_budget, bool *built) const
+{
+	if (mode_ != Mode::Hip || !t.ok)
+		return nullptr;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	const auto key = std::make_pair(device_, serial);
+	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
+		return it->second;
+	if (rf.refused_glyf_tables.count(key))
+		return nullptr;
+	const uint64_t used = rf.bytes[device_], room = rf.budget > used ? rf.budget - used : 0;
+	if (auto it = rf.unfit_glyf_tables.find(key); it != rf.unfit_glyf_tables.end() && it->second > room) {
+		*over_budget = true;
+		return nullptr;
+	}
+	vgsdf_font_tables_desc d;
+	d.num_glyphs = t.num_glyphs, d.loca_entries = t.loca_entries, d.loca_long = t.loca_long;
+	d.n_loca_bytes = t.n_loca_bytes, d.n_glyf_bytes = t.n_glyf_bytes;
+	d.loca = t.loca, d.glyf = t.glyf;
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	vgsdf_font *f = nullptr;
+	{
+		// the budget as resident_font holds it: the font's size is known behind the count pass, and checked there, before
+		// anything of it is allocated
+		uint64_t want = 0;
+		std::lock_guard<std::mutex> lock(mu_);
+		if (vgsdf_font_create_tables_within(c, &d, room, &f, &want) != VGSDF_OK) { // (a refusal or a device error: the host's way)
+			rf.refused_glyf_tables.insert(key);
+			*refused = true;
+			return nullptr;
+		}
+		if (!f) { // over the budget as it stands
+			rf.unfit_glyf_tables[key] = want;
+			*over_budget = true;
+			return nullptr;
+		}
+	}
+	rf.unfit_glyf_tables.erase(key);
+	const uint64_t got = vgsdf_font_device_bytes(f);
+	rf.fonts.emplace(key, f);
+	rf.bytes[device_] += got;
+	if (uploaded_bytes)
+		*uploaded_bytes += got;
+	*built = true;
 	return f;
 }
 

@@ -458,6 +458,14 @@ public:
 	// (set_resident_budget, default 1 GiB; no eviction) — the caller takes the glyf form.  *uploaded_bytes (may be NULL) is
 	// raised by what this call put on the device (0: the copy was there).
 	const vgsdf_font *resident_font(int lane, const ResidentTable &table, uint64_t *uploaded_bytes = nullptr) const;
+	// the same font walked by the DEVICE from the face's loca and glyf tables (vgsdf_font_create_tables): same key (`serial` is
+	// Face::resident_serial(), the table's), same budget through the call's own limit, same lifetime — whichever of the two calls
+	// comes first makes the font and the other finds it.  nullptr: the device refused the face (*refused is set then, once per face
+	// and device: the component budget, the bounds of the resident form, a device error) and the caller takes resident_font(),
+	// which needs the host's table; or the font would pass the budget (*over_budget is set: the caller takes the glyf form).
+	// *built: this call put the font on the device
+	const vgsdf_font *font_from_tables(int lane, uint64_t serial, const FontTables &tables, uint64_t *uploaded_bytes, bool *refused,
+	                                   bool *over_budget, bool *built) const;
 	// the same for the command store of a face (vgsdf_font_create_commands): same registry (the tables' serials come from one
 	// sequence), same budget, no eviction.  nullptr: no command table, or over the budget — the caller goes on as without
 	const vgsdf_font *command_font(int lane, const CommandTable &table, uint64_t *uploaded_bytes = nullptr) const;
@@ -541,6 +549,8 @@ private:
 		std::set<std::pair<int, uint64_t>> refused_charstrings; // (device, serial): the device's decoder has refused the face
 		std::set<std::tuple<int, uint64_t, bool>> refused_family_tables; // the key of `families`: the device has refused to build the table
 		std::map<std::pair<int, uint64_t>, uint64_t> unfit_charstrings; // (device, serial) -> bytes of a store that passed the budget
+		std::set<std::pair<int, uint64_t>> refused_glyf_tables;         // (device, serial): the device's table builder has refused the face
+		std::map<std::pair<int, uint64_t>, uint64_t> unfit_glyf_tables; // (device, serial) -> bytes of a font that passed the budget
 		uint64_t budget = 1ull << 30;
 	};
 	std::shared_ptr<ResidentFonts> resident_ = std::make_shared<ResidentFonts>();

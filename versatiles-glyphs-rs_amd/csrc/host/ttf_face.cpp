@@ -650,7 +650,7 @@ private:
 	float *cp_ = nullptr;
 };
 
-constexpr int kMaxComponentDepth = 32;
+constexpr int kMaxComponentDepth = kGlyfMaxComponentDepth; // (glyf_table_limits.h)
 
 enum : uint8_t { ON_CURVE = 0x01, X_SHORT = 0x02, Y_SHORT = 0x04, REPEAT = 0x08, X_SAME_POS = 0x10, Y_SAME_POS = 0x20 };
 
@@ -931,7 +931,7 @@ struct PartShape {
 			return Fail;
 		// (an entry longer than the device's decoder takes is not copied — one damaged `loca` entry could otherwise make every
 		// glyph that names it carry megabytes: without its arrays the part fails there and the batch goes to the host's reader)
-		constexpr size_t kMaxEntry = 32 * 1024;
+		constexpr size_t kMaxEntry = kGlyfMaxEntry; // (glyf_table_limits.h)
 		fits = (size_t)n_contours * 2 + (body.size() - cur) <= kMaxEntry;
 		ends = fits ? (size_t)n_contours * 2 : 0;
 		arrays = fits ? body.size() - cur : 0;
@@ -1076,17 +1076,36 @@ const ResidentTable &Face::resident_table() const
 				(void)w.walk(*g, 0, Affine{});
 			}
 			slot_sum += sink.slots;
-			if (sink.overflow || slot_sum > 0xFFFFFFFFull) {
+			if (sink.overflow || slot_sum > kResidentMaxSlotSum) {
 				t = ResidentTable{};
 				return;
 			}
 			t.leaf_off.push_back((uint32_t)t.leaves.size());
 			t.slot_off.push_back((uint32_t)slot_sum);
 		}
-		t.serial = next_table_serial();
+		t.serial = resident_serial();
 		t.ok = true;
 	});
 	return cell.table;
+}
+
+uint64_t Face::resident_serial() const
+{
+	ResidentCell &cell = *resident_;
+	std::call_once(cell.serial_once, [&] { cell.serial = next_table_serial(); });
+	return cell.serial;
+}
+
+FontTables Face::font_tables() const
+{
+	FontTables t;
+	if (!has_glyf_outlines() || loca_.size() > 0xFFFFFFFFu || glyf_.size() > 0xFFFFFFFFu)
+		return t;
+	t.loca = loca_.data(), t.n_loca_bytes = (uint32_t)loca_.size();
+	t.glyf = glyf_.data(), t.n_glyf_bytes = (uint32_t)glyf_.size();
+	t.num_glyphs = num_glyphs_, t.loca_entries = (uint32_t)loca_entries_, t.loca_long = loca_long_ ? 1u : 0u;
+	t.ok = true;
+	return t;
 }
 
 namespace {

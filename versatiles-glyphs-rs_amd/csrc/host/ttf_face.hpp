@@ -18,6 +18,8 @@
 #include <utility>
 #include <vector>
 
+#include "../glyf_table_limits.h"
+
 namespace vg {
 
 class CffTable;
@@ -54,7 +56,8 @@ struct ResidentTable {
 	std::vector<GlyfPart> leaves;
 	std::vector<uint8_t> bytes;     // 4-aligned entries
 	// bounds: more leaves than 2^22, a glyph of more than 2^26 slots, or a store past what 32-bit offsets address
-	static constexpr uint64_t kMaxLeaves = 1ull << 22, kMaxGlyphSlots = 1ull << 26, kMaxBytes = (1ull << 32) - 4;
+	// (glyf_table_limits.h: the device's table builder refuses at the same bounds)
+	static constexpr uint64_t kMaxLeaves = kResidentMaxLeaves, kMaxGlyphSlots = kResidentMaxGlyphSlots, kMaxBytes = kResidentMaxBytes;
 };
 
 // A face's outlines as the callbacks its reader delivers, glyph id by glyph id, in the arrays of the packed upload form
@@ -102,6 +105,15 @@ struct FamilyTables {
 	uint16_t units_per_em = 0, num_glyphs = 0, num_hmetrics = 0;
 	std::vector<uint32_t> subtable_off;    // into cmap: the encoding records, in the table's order, that are unicode and of format
 	std::vector<uint16_t> subtable_format; // 0, 4, 6, 10, 12 or 13 (2, 8, 14 and unreadable ones map nothing and are left out)
+};
+
+// A `glyf` face's `loca` and `glyf` for the device's table builder (vgsdf_font_tables_desc of include/vgsdf.h, field for field):
+// views of the two tables and the three numbers Face::glyph_data goes by.  No glyph is looked at.
+struct FontTables {
+	bool ok = false;                                // false: no `glyf` outlines, or a table of 4 GiB or more
+	const uint8_t *loca = nullptr, *glyf = nullptr; // views into the face's bytes
+	uint32_t n_loca_bytes = 0, n_glyf_bytes = 0;
+	uint32_t num_glyphs = 0, loca_entries = 0, loca_long = 0;
 };
 
 // Non-owning big-endian byte view with checked reads.
@@ -154,6 +166,9 @@ public:
 	// The resident form of the face: built once, on first use (thread-safe); the same walk and the same checks as
 	// glyph_parts, glyph id by glyph id, so a failing component leaves a glyph with the leaves recorded so far.
 	const ResidentTable &resident_table() const;
+	// What a renderer keys the face's glyf-kind device font by, whichever way the font is made (resident_table().serial is this
+	// number when the table is ok); handed out on first use, without building the table.
+	uint64_t resident_serial() const;
 	// The command form of the face: built once, on first use (thread-safe), by the very call Renderer::record makes for a
 	// glyph (outline_glyph_packed, return value ignored) for every glyph id.  The callbacks are counted first and the count stops at the
 	// bounds, so a face past them is refused without its table ever being allocated.
@@ -167,6 +182,8 @@ public:
 	// The same of a `CFF2` face, with its blend sets (not ok for every other face, and for one whose local subroutines are more
 	// than the description's 65535).
 	const CharstringTable &charstring2_table() const;
+	// The face's loca and glyf for the device's table builder (the resident form without the host walking a glyph).
+	FontTables font_tables() const;
 	// The face's tables for the device's family-table kernels: built once, on first use (thread-safe).
 	const FamilyTables &family_tables() const;
 	// ttf-parser's `tables().cmap.is_some()`; the reference refuses fonts without one (metadata.rs:104-107)
@@ -203,7 +220,8 @@ private:
 	std::shared_ptr<const CffTable> cff_;
 	size_t loca_entries_ = 0;
 	struct ResidentCell {
-		std::once_flag once;
+		std::once_flag once, serial_once;
+		uint64_t serial = 0;
 		ResidentTable table;
 	};
 	std::shared_ptr<ResidentCell> resident_ = std::make_shared<ResidentCell>(); // (shared by copies of the Face: same bytes)

@@ -1,5 +1,5 @@
 // resident_fonts.cpp — the stores behind vgsdf_font: a face's outlines uploaded once, as `glyf` leaves (vgsdf_font_create)
-// or as expanded commands (vgsdf_font_create_commands; vgsdf_font_create_charstrings: decoded on the device from a CFF face's charstrings).  Submissions that name their glyphs read them
+// (vgsdf_font_create_tables: walked on the device from a face's loca and glyf) or as expanded commands (vgsdf_font_create_commands; vgsdf_font_create_charstrings: decoded on the device from a CFF face's charstrings).  Submissions that name their glyphs read them
 // (outline_front_end.cpp, vgsdf_outlines_submit_resident).  And the families over them (vgsdf_family_create): a font id's table
 // code point -> (font, glyph id, advance, scale, shift_x) on host and device, for submissions that name code-point ranges
 // (vgsdf_outlines_submit_ranges).
@@ -12,6 +12,8 @@
 #include "charstring_kernels.h"
 #include "charstring_limits.h"
 #include "family_table_kernels.h"
+#include "glyf_table_kernels.h"
+#include "glyf_table_limits.h"
 #include "outline_kernels.h"
 #include "resident_fonts.h"
 #include "work_plan.h"
@@ -543,6 +545,180 @@ int vgsdf_font_commands_read(vgsdf_ctx *ctx, const vgsdf_font *font, uint32_t *n
 		HIP_TRY(ctx, hipMemcpy(records, (const void *)(uintptr_t)font->cref.cmds, sizeof(vgsdf::OutlineCmd) * n, hipMemcpyDeviceToHost));
 	if (context && n)
 		HIP_TRY(ctx, hipMemcpy(context, (const void *)(uintptr_t)font->cref.open, n, hipMemcpyDeviceToHost));
+	return VGSDF_OK;
+}
+
+int vgsdf_font_create_tables(vgsdf_ctx *ctx, const vgsdf_font_tables_desc *in, vgsdf_font **out)
+{
+	return vgsdf_font_create_tables_within(ctx, in, ~0ull, out, nullptr);
+}
+
+int vgsdf_font_create_tables_within(vgsdf_ctx *ctx, const vgsdf_font_tables_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
+                                    uint64_t *needed)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || (in->n_loca_bytes && !in->loca) || (in->n_glyf_bytes && !in->glyf)) {
+		ctx->err = "vgsdf_font_create_tables: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	if (needed)
+		*needed = 0;
+	ctx->glyf_tables_ms[0] = ctx->glyf_tables_ms[1] = 0.0f;
+	const uint32_t n = in->num_glyphs;
+	// (tables of 4 GiB or more cannot be stated: the lengths are 32-bit)
+	// (loca_entries <= num_glyphs + 1: every glyph id a component can resolve to is then one of the face's, with a place in the store)
+	if (n > 0xFFFFu || in->loca_long > 1u || (uint64_t)in->loca_entries * (in->loca_long ? 4u : 2u) > in->n_loca_bytes || in->loca_entries > n + 1) {
+		ctx->err = "vgsdf_font_create_tables: more than 65535 glyphs, loca_long not 0 or 1, or more loca entries than the loca bytes hold or than num_glyphs + 1";
+		return VGSDF_E_ARG;
+	}
+	std::unique_ptr<vgsdf_font> f(new (std::nothrow) vgsdf_font());
+	if (!f) {
+		ctx->err = "vgsdf_font_create_tables: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	struct Events {
+		hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+		~Events()
+		{
+			for (hipEvent_t ev : e)
+				if (ev)
+					(void)hipEventDestroy(ev);
+		}
+	} ev;
+	for (hipEvent_t &e : ev.e)
+		if (hipError_t err = hipEventCreate(&e); err != hipSuccess)
+			return font_hip_error(ctx, "vgsdf_font_create_tables", "hipEventCreate", err);
+	// the description on the device, for the duration of this call: loca | glyf | counts (4 per glyph id) | flags | byte_at
+	const size_t a_glyf = align_up(in->n_loca_bytes, 16), a_counts = align_up(a_glyf + in->n_glyf_bytes, 16),
+	             a_flags = a_counts + 4 * (size_t)vgsdf::kGlyfTableCounts * n, a_at = a_flags + 4 * (size_t)vgsdf::GLYF_FLAG_WORDS,
+	             a_total = a_at + 4 * ((size_t)n + 1);
+	ScratchBuf dev;
+	if (hipError_t e = dev.ensure(a_total + 16); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_tables", "hipMalloc", e);
+	uint8_t *a = (uint8_t *)dev.p;
+	auto copy = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+	hipError_t e = copy(a, in->loca, in->n_loca_bytes);
+	if (e == hipSuccess)
+		e = copy(a + a_glyf, in->glyf, in->n_glyf_bytes);
+	if (e == hipSuccess)
+		e = hipMemsetAsync(a + a_flags, 0, 4 * (size_t)vgsdf::GLYF_FLAG_WORDS, st);
+	vgsdf::GlyfTablesRef face{};
+	face.loca = a, face.glyf = a + a_glyf;
+	face.glyf_len = in->n_glyf_bytes, face.loca_entries = in->loca_entries, face.loca_long = in->loca_long, face.n_glyph_ids = n;
+	uint32_t *d_counts = (uint32_t *)(a + a_counts), *d_flags = (uint32_t *)(a + a_flags), *d_at = (uint32_t *)(a + a_at);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[0], st);
+	if (e == hipSuccess && n)
+		e = (hipError_t)vgsdf_glyf_tables_count(&face, d_counts, d_flags, st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[1], st);
+	// the counts and, behind them, the flag words: one read-back
+	std::vector<uint32_t> got((size_t)vgsdf::kGlyfTableCounts * n + vgsdf::GLYF_FLAG_WORDS);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(got.data(), d_counts, 4 * got.size(), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st);
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_tables", "count pass", e);
+	(void)hipEventElapsedTime(&ctx->glyf_tables_ms[0], ev.e[0], ev.e[1]);
+	const uint32_t *fl = got.data() + (size_t)vgsdf::kGlyfTableCounts * n;
+	if (fl[vgsdf::GLYF_FLAG_BUDGET] || fl[vgsdf::GLYF_FLAG_SLOTS]) {
+		ctx->err = fl[vgsdf::GLYF_FLAG_BUDGET] ? "vgsdf_font_create_tables: a glyph past VGSDF_GLYF_MAX_COMPONENTS"
+		                                       : "vgsdf_font_create_tables: a glyph of more than 2^26 command slots";
+		return VGSDF_E_GLYF;
+	}
+	// the running sums, and the bounds of the host's table (glyf_table_limits.h)
+	std::vector<uint32_t> byte_at((size_t)n + 1);
+	f->leaf_off.assign((size_t)n + 1, 0);
+	f->slots.assign(n, 0);
+	uint64_t n_bytes = 0, n_leaves = 0, slot_sum = 0;
+	for (uint32_t g = 0; g < n; g++) {
+		const uint32_t *c = got.data() + (size_t)vgsdf::kGlyfTableCounts * g;
+		byte_at[g] = (uint32_t)n_bytes, f->leaf_off[g] = (uint32_t)n_leaves;
+		f->slots[g] = c[2];
+		n_bytes += align_up(c[0], 4), n_leaves += c[1], slot_sum += c[2];
+		if (n_bytes > vg::kResidentMaxBytes || n_leaves > vg::kResidentMaxLeaves || slot_sum > vg::kResidentMaxSlotSum) {
+			ctx->err = "vgsdf_font_create_tables: more than 2^22 leaves, a store past 2^32 - 4 bytes, or command slots that sum past 2^32 - 1";
+			return VGSDF_E_GLYF;
+		}
+		f->max_cap = std::max(f->max_cap, c[3]); // (every simple entry a leaf names is some glyph id's own)
+		f->max_len = std::max(f->max_len, c[0]);
+	}
+	byte_at[n] = (uint32_t)n_bytes, f->leaf_off[n] = (uint32_t)n_leaves;
+	// the store as vgsdf_font_create lays it out (the same size: the same vgsdf_font_device_bytes)
+	const size_t leaves_bytes = sizeof(vgsdf_glyf_part) * (size_t)n_leaves;
+	const size_t bytes_at = leaves_bytes, off_at = align_up(bytes_at + n_bytes, 16), total = off_at + 4 * ((size_t)n + 1);
+	if (needed)
+		*needed = total;
+	if (total > max_store_bytes)
+		return VGSDF_OK; // (*out stays NULL: the caller's limit, nothing allocated)
+	f->device = ctx->device;
+	f->n_glyph_ids = n;
+	f->n_leaves = (uint32_t)n_leaves;
+	f->n_bytes = (uint32_t)n_bytes;
+	if (hipError_t err = f->store.ensure(total + 16); err != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_tables", "hipMalloc", err);
+	uint8_t *d = (uint8_t *)f->store.p;
+	e = copy(d + off_at, f->leaf_off.data(), 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = copy(d_at, byte_at.data(), 4 * ((size_t)n + 1));
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[1], st);
+	if (e == hipSuccess && n)
+		e = (hipError_t)vgsdf_glyf_tables_emit(&face, (const uint32_t *)(d + off_at), d_at, d, d + bytes_at, d_flags, st);
+	if (e == hipSuccess)
+		e = hipEventRecord(ev.e[2], st);
+	uint32_t flags[vgsdf::GLYF_FLAG_WORDS] = {};
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st); // the store is complete when the call returns: every context may name the font
+	if (e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_font_create_tables", "emit pass", e);
+	(void)hipEventElapsedTime(&ctx->glyf_tables_ms[1], ev.e[1], ev.e[2]);
+	if (flags[vgsdf::GLYF_FLAG_EMIT]) { // (the two passes walk one text over the same bytes: said by the pass itself)
+		ctx->err = "vgsdf_font_create_tables: the emit pass did not match the count pass";
+		return VGSDF_E_HIP;
+	}
+	f->ref.leaves = (uint64_t)(uintptr_t)d;
+	f->ref.bytes = (uint64_t)(uintptr_t)(d + bytes_at);
+	f->ref.leaf_off = (uint64_t)(uintptr_t)(d + off_at);
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+void vgsdf_font_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2])
+{
+	if (ms)
+		ms[0] = ctx ? ctx->glyf_tables_ms[0] : 0.0f, ms[1] = ctx ? ctx->glyf_tables_ms[1] : 0.0f;
+}
+
+int vgsdf_font_read(vgsdf_ctx *ctx, const vgsdf_font *font, uint32_t *n_glyph_ids, uint32_t *n_leaves, uint32_t *n_bytes,
+                    uint32_t *leaf_off, vgsdf_glyf_part *leaves, uint8_t *bytes)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!font || font->commands || font->device != ctx->device) {
+		ctx->err = "vgsdf_font_read: no font, a command font, or a font of another device than the context's";
+		return VGSDF_E_ARG;
+	}
+	if (n_glyph_ids)
+		*n_glyph_ids = font->n_glyph_ids;
+	if (n_leaves)
+		*n_leaves = font->n_leaves;
+	if (n_bytes)
+		*n_bytes = font->n_bytes;
+	(void)hipSetDevice(ctx->device);
+	if (leaf_off)
+		HIP_TRY(ctx, hipMemcpy(leaf_off, (const void *)(uintptr_t)font->ref.leaf_off, 4 * ((size_t)font->n_glyph_ids + 1), hipMemcpyDeviceToHost));
+	if (leaves && font->n_leaves)
+		HIP_TRY(ctx, hipMemcpy(leaves, (const void *)(uintptr_t)font->ref.leaves, sizeof(vgsdf_glyf_part) * (size_t)font->n_leaves, hipMemcpyDeviceToHost));
+	if (bytes && font->n_bytes)
+		HIP_TRY(ctx, hipMemcpy(bytes, (const void *)(uintptr_t)font->ref.bytes, font->n_bytes, hipMemcpyDeviceToHost));
 	return VGSDF_OK;
 }
 

@@ -97,6 +97,11 @@ class _CFamilyTablesDesc(C.Structure):  # vgsdf_family_tables_desc
     _fields_ = [("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("tables", C.c_void_p)]
 
 
+class _CFontTablesDesc(C.Structure):  # vgsdf_font_tables_desc
+    _fields_ = [("num_glyphs", C.c_uint32), ("loca_entries", C.c_uint32), ("loca_long", C.c_uint32), ("n_loca_bytes", C.c_uint32),
+                ("n_glyf_bytes", C.c_uint32), ("loca", C.c_void_p), ("glyf", C.c_void_p)]
+
+
 class _COutlinesRanges(C.Structure):  # vgsdf_outlines_ranges
     _fields_ = [("n_tasks", C.c_uint32), ("n_families", C.c_uint32), ("families", C.c_void_p), ("family_of", C.c_void_p),
                 ("first", C.c_void_p), ("last", C.c_void_p), ("pbf_pre", C.c_void_p)]
@@ -112,6 +117,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_font_create_commands", "vgsdf_font_create_charstrings", "vgsdf_font_create_charstrings_within", "vgsdf_font_create_charstrings2", "vgsdf_font_create_charstrings2_within", "vgsdf_font_charstrings_kernel_ms", "vgsdf_font_commands_read",
     "vgsdf_family_create", "vgsdf_family_free", "vgsdf_family_device_bytes", "vgsdf_family_count", "vgsdf_outlines_submit_ranges",
     "vgsdf_outlines_task_extents", "vgsdf_family_create_tables", "vgsdf_family_read", "vgsdf_family_tables_kernel_ms",
+    "vgsdf_font_create_tables", "vgsdf_font_create_tables_within", "vgsdf_font_read", "vgsdf_font_tables_kernel_ms",
 ]
 
 _lib = None
@@ -167,6 +173,11 @@ def load_library():
         L.vgsdf_font_charstrings_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_font_charstrings_kernel_ms.restype = None
         L.vgsdf_font_commands_read.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp]
+        L.vgsdf_font_create_tables.argtypes = [vp, C.POINTER(_CFontTablesDesc), C.POINTER(vp)]
+        L.vgsdf_font_create_tables_within.argtypes = [vp, C.POINTER(_CFontTablesDesc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.vgsdf_font_read.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp]
+        L.vgsdf_font_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_font_tables_kernel_ms.restype = None
         L.vgsdf_font_free.argtypes = [vp, vp]
         L.vgsdf_font_device_bytes.argtypes = [vp]
         L.vgsdf_font_device_bytes.restype = C.c_uint64
@@ -612,6 +623,42 @@ class SdfContext:
         context = np.zeros(n_cmds.value, dtype=np.uint8)
         self._check(L.vgsdf_font_commands_read(self._h, font._h, None, None, cmd_off.ctypes.data, records.ctypes.data, context.ctypes.data))
         return {"cmd_off": cmd_off, "records": records, "context": context}
+
+    def font_create_tables(self, desc: dict, max_store_bytes=None, **override):
+        """vgsdf_font_create_tables: a `glyf` face's tables (vgsdf_font_tables_desc as a dict: loca, glyf (bytes or uint8 arrays),
+        num_glyphs, loca_entries, loca_long — what FontManager.font_tables_desc returns) -> the glyf-kind font the DEVICE walks
+        from them.  override: raw struct fields (n_loca_bytes, n_glyf_bytes) for descriptions that lie.
+        VgsdfError with code VGSDF_E_GLYF: the device refuses the face (component budget, the bounds of the resident form).
+        max_store_bytes (vgsdf_font_create_tables_within): -> (ResidentFont or None when the store would pass it, store bytes)"""
+        loca, glyf = np.frombuffer(bytes(desc["loca"]), dtype=np.uint8), np.frombuffer(bytes(desc["glyf"]), dtype=np.uint8)
+        d = _CFontTablesDesc(int(desc["num_glyphs"]), int(desc["loca_entries"]), int(desc["loca_long"]),
+                             override.get("n_loca_bytes", len(loca)), override.get("n_glyf_bytes", len(glyf)),
+                             loca.ctypes.data if len(loca) else None, glyf.ctypes.data if len(glyf) else None)
+        h = C.c_void_p()
+        if max_store_bytes is not None:
+            want = C.c_uint64()
+            self._check(load_library().vgsdf_font_create_tables_within(self._h, C.byref(d), int(max_store_bytes), C.byref(h), C.byref(want)))
+            return (ResidentFont(self, h) if h.value else None), int(want.value)
+        self._check(load_library().vgsdf_font_create_tables(self._h, C.byref(d), C.byref(h)))
+        return ResidentFont(self, h)
+
+    def font_read(self, font: ResidentFont) -> dict:
+        """vgsdf_font_read (test / inspection): the DEVICE's copy of a glyf-kind font as {leaf_off, leaves (GLYF_PART_DTYPE), bytes},
+        whichever call made it"""
+        L = load_library()
+        n, n_leaves, n_bytes = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(L.vgsdf_font_read(self._h, font._h, C.byref(n), C.byref(n_leaves), C.byref(n_bytes), None, None, None))
+        leaf_off = np.zeros(n.value + 1, dtype=np.uint32)
+        leaves = np.zeros(n_leaves.value, dtype=GLYF_PART_DTYPE)
+        store = np.zeros(n_bytes.value, dtype=np.uint8)
+        self._check(L.vgsdf_font_read(self._h, font._h, None, None, None, leaf_off.ctypes.data, leaves.ctypes.data, store.ctypes.data))
+        return {"leaf_off": leaf_off, "leaves": leaves, "bytes": store}
+
+    def font_tables_kernel_ms(self):
+        """(count, emit + copy) milliseconds of the kernels of this context's last font_create_tables"""
+        ms = (C.c_float * 2)()
+        load_library().vgsdf_font_tables_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
 
     def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None):
         """outlines_submit for glyphs named by (font, glyph id) of resident fonts (vgsdf_outlines_resident)"""

@@ -58,6 +58,10 @@ class FamilyTableStats(C.Structure):  # vg_family_table_stats
     _fields_ = [(k, C.c_uint64) for k in ("built_on_device", "fallbacks")]
 
 
+class GlyfTableStats(C.Structure):  # vg_glyf_table_stats
+    _fields_ = [(k, C.c_uint64) for k in ("built_on_device", "bytes", "fallbacks")]
+
+
 class CharstringStats(C.Structure):  # vg_charstring_stats
     _fields_ = [(k, C.c_uint64) for k in ("fonts_decoded", "font_bytes", "fallbacks")]
 
@@ -83,7 +87,8 @@ VGFONT_SYMBOLS = [
     "vg_manager_shard_glyphs", "vg_manager_set_glyph_shard", "vg_pbf_merge", "vg_pbf_concat",
     "vg_renderer_new_multi", "vg_renderer_device_count", "vg_renderer_reduce_counters", "vg_renderer_reduce_path", "vg_renderer_add_counters",
     "vg_renderer_reset_counters", "vg_manager_reduced_counters", "vg_manager_set_in_place_pbf", "vg_manager_set_glyf_on_device", "vg_manager_set_lane_form", "vg_manager_plan_lanes",
-    "vg_manager_family_tables_desc", "vg_manager_set_family_tables_on_device", "vg_manager_family_table_stats",
+    "vg_manager_family_tables_desc", "vg_manager_font_tables_desc", "vg_manager_set_family_tables_on_device", "vg_manager_family_table_stats",
+    "vg_manager_set_glyf_tables_on_device", "vg_manager_glyf_table_stats",
 ]
 
 _bound = False
@@ -130,6 +135,9 @@ def _L():
         L.vg_manager_set_family_tables_on_device.argtypes = [vp, C.c_int]
         L.vg_manager_set_family_tables_on_device.restype = None
         L.vg_manager_family_table_stats.argtypes = [vp, C.POINTER(FamilyTableStats)]
+        L.vg_manager_set_glyf_tables_on_device.argtypes = [vp, C.c_int]
+        L.vg_manager_set_glyf_tables_on_device.restype = None
+        L.vg_manager_glyf_table_stats.argtypes = [vp, C.POINTER(GlyfTableStats)]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -405,6 +413,17 @@ class FontManager:
         """resident families' tables are built by the device from the faces' cmap and hmtx tables (vgsdf_family_create_tables)
         instead of by the host's reader; a font id whose description or build is refused falls back; same bytes (default off)"""
         _L().vg_manager_set_family_tables_on_device(self._h, int(bool(on)))
+
+    def set_glyf_tables_on_device(self, on: bool):
+        """glyf-kind resident fonts are walked by the DEVICE from the faces' loca and glyf tables (vgsdf_font_create_tables): the host
+        interprets no glyph.  A face the device refuses falls back to the host's table.  Default off.  Same output"""
+        _L().vg_manager_set_glyf_tables_on_device(self._h, int(bool(on)))
+
+    def glyf_table_stats(self) -> dict:
+        """of the last render: {built_on_device, bytes, fallbacks} (vg_glyf_table_stats)"""
+        s = GlyfTableStats()
+        _L().vg_manager_glyf_table_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in GlyfTableStats._fields_}
 
     def family_table_stats(self) -> dict:
         """of the last render: {built_on_device, fallbacks} (vg_family_table_stats)"""
@@ -761,6 +780,21 @@ class FontManager:
         return {"cmap": C.string_at(d.cmap, d.cmap_len) if d.cmap_len else b"", "hmtx": C.string_at(d.hmtx, d.hmtx_len) if d.hmtx_len else b"",
                 "units_per_em": int(d.units_per_em), "num_glyphs": int(d.num_glyphs), "num_hmetrics": int(d.num_hmetrics),
                 "subtable_off": arr(d.subtable_off, np.uint32), "subtable_format": arr(d.subtable_format, np.uint16)}
+
+    def font_tables_desc(self, font_id: str, file_index: int = 0):
+        """the description of one file's loca and glyf for SdfContext.font_create_tables (vg_manager_font_tables_desc), no device
+        needed and no glyph looked at: {loca, glyf (bytes), num_glyphs, loca_entries, loca_long}, copies.  None: the description
+        refuses (a face without glyf outlines)"""
+        from .device import _CFontTablesDesc
+        L = _L()
+        L.vg_manager_font_tables_desc.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        d = _CFontTablesDesc()
+        if L.vg_manager_font_tables_desc(self._h, font_id.encode(), int(file_index), C.byref(d)) != 0:
+            if _err().startswith("refused"):
+                return None
+            raise RuntimeError(_err())
+        return {"loca": C.string_at(d.loca, d.n_loca_bytes) if d.n_loca_bytes else b"", "glyf": C.string_at(d.glyf, d.n_glyf_bytes) if d.n_glyf_bytes else b"",
+                "num_glyphs": int(d.num_glyphs), "loca_entries": int(d.loca_entries), "loca_long": int(d.loca_long)}
 
     def record_resident_commands(self, font_id: str) -> dict:
         """record_resident against command fonts: for any face the reader can read (CFF, CFF2, glyf)"""
