@@ -134,8 +134,11 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	// per wave: the groups that survive the wave-level cull, compacted (4 pad entries behind the last one)
 	__shared__ float st_ub2[SPAN_TILES * TPB];    // per pixel: upper bound of the squared distance so far
 	__shared__ uint16_t st_byte[SPAN_TILES * TPB]; // per pixel: byte if inside (low), byte if outside (high)
+	__shared__ uint32_t st_pix[SPAN_TILES * TPB];  // per pixel: its coordinates (pix_pack, sdf_span_support.h), divided out once
 	constexpr uint32_t QCAP = 256;                 // pooled (pixel, group) pairs per wave and sweep; beyond: per-lane walk
-	__shared__ uint16_t q_pair[TPB / 64][QCAP];    // (lane << 5) | group
+	// a pooled pair is its two LDS byte offsets: (4 lane) << 16 (the lane's ds_bpermute address and its q_min slot) | 32 group
+	// (the group's first record in a row of s_rec).  The stage's row crossings pool (lane << 10) | row in the same entries.
+	__shared__ uint32_t q_pair[TPB / 64][QCAP];
 	__shared__ uint32_t q_min[TPB / 64][64];       // per pixel of the wave: smallest filter value (bits)
 
 	const uint32_t tid = threadIdx.x, lane = threadIdx.x & 63;
@@ -161,17 +164,26 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	const uint32_t n_delta = (r_last - r_first + 1) * stride; // <= DELTA_CAP (host-checked)
 	for (uint32_t i = tid; i < n_delta; i += TPB)
 		s_delta[i] = 0;
-	for (uint32_t k = 0; k < T; k++) {
-		st_ub2[k * TPB + tid] = __builtin_inff();
-		st_byte[k * TPB + tid] = 0x00FFu; // neutral: 255 for the min (inside), 0 for the max (outside)
-	}
-
 	const float wh = (float)max(g.w, g.h);
 	// Origin of every f32 quantity of the filter (records, anchors, pixel centres): the middle of the bitmap,
 	// an integer point.  The filter's error bound h(F) scales with M = the largest |coordinate| relative to
 	// that origin, so the middle halves it against the corner (x0, y0) (and with it the share of pixels whose
 	// byte needs the exact f64 evaluation).  Pixel centres stay exact in f32 (half-integers).
 	const int hw = (int)(g.w >> 1), hh = (int)(g.h >> 1);
+	// The pixel of thread tid in tile k is p0 + k TPB + pw + lane for the whole kernel: its column and row are divided
+	// out here, once, and every sweep (one per chunk) and the final stores read them from st_pix.  A padding lane of
+	// the last tile gets the bitmap's last pixel (it takes part in the wave's shuffles; its candidate mask is cleared
+	// in the sweep and it stores nothing).  Each thread reads only what it wrote itself: no barrier.
+	for (uint32_t k = 0; k < T; k++) {
+		st_ub2[k * TPB + tid] = __builtin_inff();
+		st_byte[k * TPB + tid] = 0x00FFu; // neutral: 255 for the min (inside), 0 for the max (outside)
+		const uint32_t oc = min(p0 + k * TPB + pw + lane, npix - 1);
+		const uint32_t row = oc / g.w; // r_first <= row <= r_last
+		st_pix[k * TPB + tid] = pix_pack((float)((int)(oc - row * g.w) - hw) + 0.5f, row - r_first);
+	}
+	// the span's first row against the origin, as one opaque scalar (or the compiler re-derives it from h, r_first and hh per lane)
+	int y_mid = y_hi - hh;
+	asm volatile("" : "+s"(y_mid));
 	const float mpix = 0.5f * wh + 1.0f; // >= |pixel centre - origin| in both axes
 	uint32_t par = 0;
 	if (tid == 0)
@@ -309,7 +321,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					// (lane, row) pairs of the wave, pooled in LDS (rows of a span: < 1024, host-checked through DELTA_CAP)
 					uint32_t off = incl - nrow;
 					for (uint32_t r = 0; r < nrow; r++)
-						q_pair[wv][off++] = (uint16_t)((lane << 10) | (uint32_t)(y_hi - (ya + (int)r)));
+						q_pair[wv][off++] = (lane << 10) | (uint32_t)(y_hi - (ya + (int)r));
 					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 					__builtin_amdgcn_wave_barrier();
 					for (uint32_t base = 0; base < total; base += 64) {
@@ -362,11 +374,11 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// a wave whose 64 pixels all lie past the end of the bitmap (last tile of the glyph) has nothing to do
 			if (p0 + k * TPB + pw >= npix)
 				continue;
-			const uint32_t oc = min(o, npix - 1);
-			const uint32_t row = oc / g.w;
-			const uint32_t x = oc - row * g.w;
-			const uint32_t y = g.h - 1 - row;
-			const float rpx = (float)((int)x - hw) + 0.5f, rpy = (float)((int)y - hh) + 0.5f; // pixel centre relative to the origin
+			// pixel centre relative to the origin, from the table: column x = pix_col(rpx, hw), row y = y_hi - roff above y0
+			const uint32_t pe = st_pix[k * TPB + tid];
+			const float rpx = pix_rpx(pe);
+			const int roff = (int)pix_roff(pe);
+			const float rpy = (float)(y_mid - roff) + 0.5f; // (the integer first: the same rounding as (float)(y - hh) at any h)
 			float ub2 = st_ub2[k * TPB + tid];
 			VG_STAMP(0);
 
@@ -398,47 +410,72 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 						asm("v_min3_u32 %0, %1, %2, %3" : "=v"(dmin) : "v"(dmin), "v"(d2[2]), "v"(d2[3]));
 						D2p[b * 2] = __builtin_amdgcn_perm(d2[1], d2[0], 0x07060302u);     // hi16(d2[1]) : hi16(d2[0])
 						D2p[b * 2 + 1] = __builtin_amdgcn_perm(d2[3], d2[2], 0x07060302u);
-					} else {
-						D2p[b * 2] = D2p[b * 2 + 1] = 0x7F7F7F7Fu; // 3.4e38 : 3.4e38 (finite: the test below stays NaN-free)
-					}
+					} // (a block past n_groups leaves its D2p unset: the second pass skips the same blocks)
 				}
 				ub2 = __uint_as_float(dmin);
 				float U = (__builtin_amdgcn_sqrtf(ub2) * INFL + pad) * INFL; // (raw v_sqrt_f32, as for the group radius: DESIGN.md §4.1)
 				U = U < VG_M_SAT ? U : VG_M_SAT; // SAT: beyond it the byte is saturated whatever the minimum is
 				const float Ui = (U + pad * INFL) * VG_M_GRP_SLACK; // s_gr is stored with the same factor; it lacks the pad of r_g
 				// One bit per group, 3-4 VALU ops each: tt = (U + r_g) 1.004, diff = tt^2 - D_g^2 (sign bit set
-				// <=> not a candidate; -3.4e38 for the groups past n_groups), shifted in with v_alignbit.  The
-				// bits arrive inverted and in reverse order: fixed once with v_not / v_bfrev.
-				uint32_t rej = 0xFFFFFFFFu;
-#pragma unroll
-				for (uint32_t b = 0; b < NGRP / 4; b++) {
-					// (unconditional: the stage writes all NGRP radii in every processed chunk, 0 for the empty groups, and
-					// the blocks past n_groups carry D2p = 3.4e38 : 3.4e38, rejected whatever the radius is)
+				// <=> not a candidate), shifted in with v_alignbit from the chunk's highest block of four down to
+				// group 0, so group i lands on bit i however many blocks the chunk holds.
+				// A full chunk (every chunk of a glyph but its last) runs all eight blocks in a straight line: the
+				// eight loads of the radii are issued ahead of the arithmetic and their latency is paid once.
+				// A partial chunk skips the blocks past n_groups by the first pass's workgroup-uniform condition
+				// (scalar branches: the switch enters at the chunk's block count and falls through; each block
+				// waits for its own load, which costs more than the skipped blocks save once all eight are real:
+				// profiles/sweep_diet2_ab.txt).  There the bits above the real blocks' are whatever rej held
+				// before: cand, which starts as the mask of the chunk's real groups, ignores them, so rej needs no
+				// initial value (a constant costs up to two v_mov at every entry of the switch; the empty statement
+				// below hands the compiler "some register" instead, one copy per entry passed).  The empty groups
+				// inside the last real block have their anchors at 1e18 (D_g^2 = 2e36, finite: the pass stays
+				// NaN-free) and radius 0, and lie outside cand too.
+				uint32_t rej;
+				asm volatile("" : "=v"(rej));
+				auto reject4 = [&](uint32_t b) {
 					const float4 r = gr4[b];
 					const float rs[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
-					for (int j = 0; j < 4; j++) {
+					for (int j = 3; j >= 0; j--) {
 						const uint32_t pk = D2p[b * 2 + j / 2];
 						const float d2 = __uint_as_float((j & 1) ? pk : (pk << 16));
 						const float tt = Ui + VG_M_RG(rs[j]);
 						const float diff = __builtin_fmaf(tt, tt, -d2);
 						rej = __builtin_amdgcn_alignbit(rej, __float_as_uint(diff), 31); // (rej << 1) | sign(diff)
 					}
+				};
+				static_assert(NGRP / 4 == 8, "one case per block of four groups");
+				if (n_groups == NGRP) {
+#pragma unroll
+					for (int b = NGRP / 4 - 1; b >= 0; b--)
+						reject4((uint32_t)b);
+				} else switch ((n_groups + 3) / 4) { // 1..8 (a processed chunk holds a record)
+				default: reject4(7); [[fallthrough]];
+				case 7: reject4(6); [[fallthrough]];
+				case 6: reject4(5); [[fallthrough]];
+				case 5: reject4(4); [[fallthrough]];
+				case 4: reject4(3); [[fallthrough]];
+				case 3: reject4(2); [[fallthrough]];
+				case 2: reject4(1); [[fallthrough]];
+				case 1: reject4(0);
 				}
-				cand &= __builtin_bitreverse32(~rej); // (cand starts as the mask of the chunk's real groups)
+				cand &= ~rej;
 			}
 
 			VG_STAMP(6); // phase 1
 			// ---- phase 2: smallest f32 filter value over the lane's candidate groups (F >= +0: unsigned
 			// order of the bits is float order) ----
 			uint32_t k1 = 0xFFFFFFFFu;
-			auto group_min = [&](uint32_t acc, uint32_t gq, float qx, float qy) { // min(acc, F of the 8 members of group gq)
+			auto rec4 = [](const float4 *row, uint32_t goff, uint32_t hq) { // records 4 hq .. 4 hq + 3 of the group at byte goff of `row`
+				return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(row) + goff + 16u * hq);
+			};
+			auto group_min = [&](uint32_t acc, uint32_t goff, float qx, float qy) { // min(acc, F of the 8 members of the group at byte goff = 32 g of a row)
 				// two halves of 4 records: 20 + 4 live values instead of 40 + 8 (the kernel sits at the 128-VGPR
 				// limit of 4 waves per SIMD; spills would go to scratch, i.e. to memory)
 #pragma unroll
 				for (uint32_t hq = 0; hq < 2; hq++) {
-					const float4 vx4 = q_vx[2 * gq + hq], vy4 = q_vy[2 * gq + hq], dx4 = q_dx[2 * gq + hq], dy4 = q_dy[2 * gq + hq],
-					             iv4 = q_inv[2 * gq + hq];
+					const float4 vx4 = rec4(q_vx, goff, hq), vy4 = rec4(q_vy, goff, hq), dx4 = rec4(q_dx, goff, hq), dy4 = rec4(q_dy, goff, hq),
+					             iv4 = rec4(q_inv, goff, hq);
 					const uint32_t f0 = __float_as_uint(sc_filter(qx, qy, vx4.x, vy4.x, dx4.x, dy4.x, iv4.x));
 					const uint32_t f1 = __float_as_uint(sc_filter(qx, qy, vx4.y, vy4.y, dx4.y, dy4.y, iv4.y));
 					const uint32_t f2 = __float_as_uint(sc_filter(qx, qy, vx4.z, vy4.z, dx4.z, dy4.z, iv4.z));
@@ -463,24 +500,26 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 				VG_COUNT(cn_pairs += total; cn_rounds += (total + 63) / 64; cn_tc += 1);
 				if (total <= QCAP) {
-					uint32_t off = incl - c;
+					uint32_t *qp = &q_pair[wv][incl - c];
 					q_min[wv][lane] = 0xFFFFFFFFu;
 					uint32_t m = cand;
 					while (m) {
-						q_pair[wv][off++] = (uint16_t)((lane << 5) | (uint32_t)__builtin_ctz(m));
+						*qp = (lane << 18) | ((uint32_t)__builtin_ctz(m) << 5);
+						__builtin_amdgcn_sched_barrier(0); // (the store first: the pointer is then bumped in place, no copy)
+						qp++;
 						m &= m - 1;
 					}
 					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 					__builtin_amdgcn_wave_barrier();
 					for (uint32_t base = 0; base < total; base += 64) {
 						const uint32_t idx = base + lane;
-						const bool valid = idx < total;
-						const uint32_t e = q_pair[wv][valid ? idx : base];
-						const uint32_t src = e >> 5;
-						const float qx = __shfl(rpx, (int)src), qy = __shfl(rpy, (int)src);
-						const uint32_t mn = group_min(0xFFFFFFFFu, e & 31u, qx, qy);
-						if (valid)
-							atomicMin(&q_min[wv][src], mn);
+						const uint32_t e = q_pair[wv][min(idx, total - 1)]; // (a lane past the end takes the last pair and drops its result)
+						const uint32_t src4 = e >> 16;
+						const float qx = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpx)));
+						const float qy = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpy)));
+						const uint32_t mn = group_min(0xFFFFFFFFu, e & 0xFFFFu, qx, qy);
+						if (idx < total)
+							atomicMin(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(q_min[wv]) + src4), mn);
 					}
 					__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 					__builtin_amdgcn_wave_barrier();
@@ -491,7 +530,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					while (m) {
 						const uint32_t gq = (uint32_t)__builtin_ctz(m);
 						m &= m - 1;
-						k1 = group_min(k1, gq, rpx, rpy);
+						k1 = group_min(k1, gq * 32u, rpx, rpy);
 					}
 				}
 			}
@@ -516,7 +555,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			if (!sane) {
 				int gx0 = g.x0, gy0 = g.y0;
 				asm volatile("" : "+s"(gx0), "+s"(gy0)); // (see the stage: keeps the f64 values out of the kernel-long live ranges)
-				const double px = (double)x + ((double)gx0 + 0.5), py = (double)y + ((double)gy0 + 0.5); // renderer_precise.rs:27-28,34,62
+				const double px = (double)pix_col(rpx, hw) + ((double)gx0 + 0.5), py = (double)(y_hi - roff) + ((double)gy0 + 0.5); // renderer_precise.rs:27-28,34,62
 				for (uint32_t j = 0; j < cnt; j++) {
 					const double d2 = exact_at(px, py, j);
 					best = d2 < best ? d2 : best; // rtree_segments.rs:60-62
@@ -587,8 +626,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 						const float sTk = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(Tk), src));
 						int gx0 = g.x0, gy0 = g.y0;
 						asm volatile("" : "+s"(gx0), "+s"(gy0));
-						const double dpx = (double)__builtin_amdgcn_readlane((int)x, src) + ((double)gx0 + 0.5); // renderer_precise.rs:27-28,34,62
-						const double dpy = (double)__builtin_amdgcn_readlane((int)y, src) + ((double)gy0 + 0.5);
+						const double dpx = (double)pix_col(spx, hw) + ((double)gx0 + 0.5); // renderer_precise.rs:27-28,34,62
+						const double dpy = (double)(y_hi - __builtin_amdgcn_readlane(roff, src)) + ((double)gy0 + 0.5);
 						uint32_t scand = (uint32_t)__builtin_amdgcn_readlane((int)cand, src);
 						double wbest = __builtin_huge_val();
 						while (scand) {
@@ -615,7 +654,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					// many undecided lanes (pixels along an edge that sits on a byte boundary): every lane for itself, in parallel
 					int gx0 = g.x0, gy0 = g.y0;
 					asm volatile("" : "+s"(gx0), "+s"(gy0));
-					const double px = (double)x + ((double)gx0 + 0.5), py = (double)y + ((double)gy0 + 0.5); // renderer_precise.rs:27-28,34,62
+					const double px = (double)pix_col(rpx, hw) + ((double)gx0 + 0.5), py = (double)(y_hi - roff) + ((double)gy0 + 0.5); // renderer_precise.rs:27-28,34,62
 					uint32_t m = cand;
 					while (m) {
 						const uint32_t gq = (uint32_t)__builtin_ctz(m);
@@ -678,9 +717,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	for (uint32_t k = 0; k < T; k++) {
 		const uint32_t o = p0 + k * TPB + pw + lane;
 		if (o < npix) {
-			const uint32_t row = o / g.w;
-			const uint32_t x = o - row * g.w;
-			const int wn = s_delta[(row - r_first) * stride + x];
+			const uint32_t pe = st_pix[k * TPB + tid]; // (o < npix: the entry is this pixel's own)
+			const int wn = s_delta[pix_roff(pe) * stride + (uint32_t)pix_col(pix_rpx(pe), hw)];
 			const uint32_t sb = st_byte[k * TPB + tid];
 			out[g.out_off + o] = (uint8_t)(wn != 0 ? (sb & 255u) : (sb >> 8));
 		}

@@ -2,7 +2,7 @@
 // sdf_span_kernel.inc (the product instance there; the margin instances of sdf_margin_kernels.hip, `make margins`).
 // NOTE for profiles/traffic.json: bench.py keys the recorded PMC numbers of the raster kernel to the text of sdf_kernels.hip,
 // sdf_span_kernel.inc and sdf_kernels.h only.  This header holds code of that kernel too (filter_err, sc_filter, quantise,
-// exact_dist_sq) and is NOT part of that key: after an edit here that changes the kernel's instructions, collect the profile
+// exact_dist_sq, pix_pack and its readers) and is NOT part of that key: after an edit here that changes the kernel's instructions, collect the profile
 // again (tools/profile.sh) or remove the entries, or bench.py keeps reporting numbers of the old instructions.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -121,6 +121,20 @@ __device__ __forceinline__ float sc_filter(float rpx, float rpy, float vx, float
 }
 
 constexpr uint32_t SPAN_TILES = 4; // tiles a workgroup of the default kernel sweeps per staged chunk
+
+// A pixel of a span in 4 bytes (the span kernel's st_pix): rpx = column - (w >> 1) + 0.5 as an f16 in the low half, the row's
+// offset from the span's first row in the high half.  Exact for every bitmap the span kernel is given: the planner admits
+// a width only if two histogram rows fit DELTA_CAP (work_plan.h, span_fits: 2 (w + 2) <= 2048), so w <= 1022, 2 rpx is an odd
+// integer of magnitude <= 1023 (column 0 .. w - 1 against w >> 1 <= 511) and fits the 11-bit significand of an f16 at an
+// exponent far inside its range; a span touches at most DELTA_CAP / (w + 1) < 1024 rows.  The height is not bounded that way,
+// which is why the row is kept as an offset and not as a coordinate.
+__device__ __forceinline__ uint32_t pix_pack(float rpx, uint32_t row_off)
+{
+	return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)rpx) | (row_off << 16);
+}
+__device__ __forceinline__ float pix_rpx(uint32_t e) { return (float)__builtin_bit_cast(_Float16, (uint16_t)e); }
+__device__ __forceinline__ uint32_t pix_roff(uint32_t e) { return e >> 16; }
+__device__ __forceinline__ int pix_col(float rpx, int hw) { return (int)(rpx - 0.5f) + hw; } // (rpx - 0.5 is an integer: exact)
 
 // The rotation of workgroup b (sdf_span_kernel.inc: wave wv takes the 64-pixel quarter (wv + rot) & 3 of every tile): 0..3,
 // wave-uniform, scalar arithmetic only.  The top two bits of a multiplicative hash: workgroups are dealt round-robin
