@@ -4,6 +4,7 @@
 //   work_list.cpp           the host's planner of a resident batch's work list
 //   outline_front_end.cpp   outline commands in, rects and bitmaps out
 //   resident_fonts.cpp      fonts uploaded once and named by glyph id (resident_fonts.h: what the front-end reads of them)
+//   resident_families.cpp   the families over them, named by code-point range (resident_build.h: what the two share)
 //   run_counters.cpp        run counters and their RCCL reduction
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,7 +65,7 @@ struct vgsdf_ctx {
 	// to exactly what the largest launch so far needed and belongs to no font
 	void *charstring_spill = nullptr;
 	size_t charstring_spill_bytes = 0;
-	float family_tables_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_family_create_tables (resident_fonts.cpp)
+	float family_tables_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_family_create_tables (resident_families.cpp)
 	float glyf_tables_ms[2] = {0.0f, 0.0f};   // count / emit kernels of the last vgsdf_font_create_tables (resident_fonts.cpp)
 	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
 };

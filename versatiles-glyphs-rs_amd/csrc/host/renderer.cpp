@@ -442,6 +442,17 @@ void Renderer::submit_outlines(int lane, const vgsdf_outlines_resident &v, HostB
 	submit_on_lane(lane, v, out, vgsdf_outlines_submit_resident, "vgsdf_outlines_submit_resident", block_bytes);
 }
 
+template <class Desc, class Made>
+Made *Renderer::create_resident(int lane, int (*create)(vgsdf_ctx *, const Desc *, Made **), const Desc &d, const char *name) const
+{
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	Made *made = nullptr;
+	std::lock_guard<std::mutex> lock(mu_);
+	if (create(c, &d, &made) != VGSDF_OK)
+		throw std::runtime_error(std::string(name) + ": " + vgsdf_last_error(c));
+	return made;
+}
+
 const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint64_t *uploaded_bytes) const
 {
 	if (mode_ != Mode::Hip || !t.ok)
@@ -449,9 +460,9 @@ const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
 	const auto key = std::make_pair(device_, t.serial);
-	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
-		return it->second;
-	// (what vgsdf_font_create will allocate, to within its rounding: leaves | bytes | leaf_off)
+	if (auto *found = rf.find(rf.fonts, key))
+		return found;
+	// (what vgsdf_font_create will allocate, to within its rounding: vgsdf::GlyfStoreLayout's arrays without the padding between them)
 	const uint64_t want = sizeof(vgsdf_glyf_part) * (uint64_t)t.leaves.size() + t.bytes.size() + 4 * (uint64_t)t.leaf_off.size();
 	if (rf.bytes[device_] + want > rf.budget)
 		return nullptr;
@@ -462,19 +473,8 @@ const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint
 	d.leaf_off = t.leaf_off.data();
 	d.leaves = reinterpret_cast<const vgsdf_glyf_part *>(t.leaves.data());
 	d.bytes = t.bytes.data();
-	vgsdf_ctx *c = lane_ctx(lane & 1);
-	vgsdf_font *f = nullptr;
-	{
-		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_font_create(c, &d, &f) != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_font_create: ") + vgsdf_last_error(c));
-	}
-	const uint64_t got = vgsdf_font_device_bytes(f);
-	rf.fonts.emplace(key, f);
-	rf.bytes[device_] += got;
-	if (uploaded_bytes)
-		*uploaded_bytes += got;
-	return f;
+	vgsdf_font *f = create_resident(lane, vgsdf_font_create, d, "vgsdf_font_create");
+	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
 const vgsdf_font *Renderer::font_from_tables(int lane, uint64_t serial, const FontTables &t, uint64_t *uploaded_bytes, bool *refused,
@@ -485,11 +485,11 @@ const vgsdf_font *Renderer::font_from_tables(int lane, uint64_t serial, const Fo
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
 	const auto key = std::make_pair(device_, serial);
-	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
-		return it->second;
+	if (auto *found = rf.find(rf.fonts, key))
+		return found;
 	if (rf.refused_glyf_tables.count(key))
 		return nullptr;
-	const uint64_t used = rf.bytes[device_], room = rf.budget > used ? rf.budget - used : 0;
+	const uint64_t room = rf.room(device_);
 	if (auto it = rf.unfit_glyf_tables.find(key); it != rf.unfit_glyf_tables.end() && it->second > room) {
 		*over_budget = true;
 		return nullptr;
@@ -517,13 +517,8 @@ const vgsdf_font *Renderer::font_from_tables(int lane, uint64_t serial, const Fo
 		}
 	}
 	rf.unfit_glyf_tables.erase(key);
-	const uint64_t got = vgsdf_font_device_bytes(f);
-	rf.fonts.emplace(key, f);
-	rf.bytes[device_] += got;
-	if (uploaded_bytes)
-		*uploaded_bytes += got;
 	*built = true;
-	return f;
+	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
 const vgsdf_font *Renderer::command_font(int lane, const CommandTable &t, uint64_t *uploaded_bytes) const
@@ -533,10 +528,11 @@ const vgsdf_font *Renderer::command_font(int lane, const CommandTable &t, uint64
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
 	const auto key = std::make_pair(device_, t.serial);
-	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
-		return it->second;
+	if (auto *found = rf.find(rf.fonts, key))
+		return found;
 	// (what vgsdf_font_create_commands will keep, to within its rounding: records | cmd_off | context bytes)
-	const uint64_t want = CommandTable::kStoreBytesPerCmd * (uint64_t)t.kinds.size() + 4 * (uint64_t)t.cmd_off.size();
+	static_assert(vgsdf::CommandStoreLayout(0, 1).total - vgsdf::CommandStoreLayout(0, 0).total == CommandTable::kStoreBytesPerCmd, "the reader's command budget (ttf_face.cpp) counts the store's bytes per command");
+	const uint64_t want = vgsdf::CommandStoreLayout(t.cmd_off.size() - 1, t.kinds.size()).total;
 	if (rf.bytes[device_] + want > rf.budget)
 		return nullptr;
 	vgsdf_font_cmds_desc d;
@@ -547,19 +543,8 @@ const vgsdf_font *Renderer::command_font(int lane, const CommandTable &t, uint64
 	d.dat_off = t.dat_off.data();
 	d.kinds = t.kinds.data();
 	d.coords = t.coords.data();
-	vgsdf_ctx *c = lane_ctx(lane & 1);
-	vgsdf_font *f = nullptr;
-	{
-		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_font_create_commands(c, &d, &f) != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_font_create_commands: ") + vgsdf_last_error(c));
-	}
-	const uint64_t got = vgsdf_font_device_bytes(f);
-	rf.fonts.emplace(key, f);
-	rf.bytes[device_] += got;
-	if (uploaded_bytes)
-		*uploaded_bytes += got;
-	return f;
+	vgsdf_font *f = create_resident(lane, vgsdf_font_create_commands, d, "vgsdf_font_create_commands");
+	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
 const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, uint64_t *uploaded_bytes, bool *refused, bool *over_budget) const
@@ -569,11 +554,11 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
 	const auto key = std::make_pair(device_, t.serial);
-	if (auto it = rf.fonts.find(key); it != rf.fonts.end())
-		return it->second;
+	if (auto *found = rf.find(rf.fonts, key))
+		return found;
 	if (rf.refused_charstrings.count(key))
 		return nullptr;
-	const uint64_t used = rf.bytes[device_], room = rf.budget > used ? rf.budget - used : 0;
+	const uint64_t room = rf.room(device_);
 	if (auto it = rf.unfit_charstrings.find(key); it != rf.unfit_charstrings.end() && it->second > room) {
 		if (over_budget)
 			*over_budget = true;
@@ -620,12 +605,7 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 		}
 	}
 	rf.unfit_charstrings.erase(key);
-	const uint64_t got = vgsdf_font_device_bytes(f);
-	rf.fonts.emplace(key, f);
-	rf.bytes[device_] += got;
-	if (uploaded_bytes)
-		*uploaded_bytes += got;
-	return f;
+	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
 const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std::vector<const vgsdf_font *> &fonts, bool commands,
@@ -636,8 +616,8 @@ const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std:
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
 	const auto key = std::make_tuple(device_, t.serial, commands);
-	if (auto it = rf.families.find(key); it != rf.families.end())
-		return it->second;
+	if (auto *found = rf.find(rf.families, key))
+		return found;
 	const uint64_t want = vgsdf::FamilyTableLayout(t.code_point->size()).bytes;
 	if (rf.bytes[device_] + want > rf.budget)
 		return nullptr;
@@ -651,19 +631,8 @@ const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std:
 	d.advance = t.advance->data();
 	d.scale = t.scale->data();
 	d.shift_x = t.shift_x->data();
-	vgsdf_ctx *c = lane_ctx(lane & 1);
-	vgsdf_family *f = nullptr;
-	{
-		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_family_create(c, &d, &f) != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_family_create: ") + vgsdf_last_error(c));
-	}
-	const uint64_t got = vgsdf_family_device_bytes(f);
-	rf.families.emplace(key, f);
-	rf.bytes[device_] += got;
-	if (uploaded_bytes)
-		*uploaded_bytes += got;
-	return f;
+	vgsdf_family *f = create_resident(lane, vgsdf_family_create, d, "vgsdf_family_create");
+	return rf.keep(rf.families, key, f, vgsdf_family_device_bytes(f), uploaded_bytes);
 }
 
 const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
@@ -675,8 +644,8 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
 	const auto key = std::make_tuple(device_, serial, commands);
-	if (auto it = rf.families.find(key); it != rf.families.end())
-		return it->second;
+	if (auto *found = rf.find(rf.families, key))
+		return found;
 	if (rf.refused_family_tables.count(key)) {
 		*refused = 2;
 		return nullptr;
@@ -701,13 +670,8 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 			return nullptr;
 		}
 	}
-	const uint64_t got = vgsdf_family_device_bytes(f);
-	rf.families.emplace(key, f);
-	rf.bytes[device_] += got;
-	if (uploaded_bytes)
-		*uploaded_bytes += got;
 	*built = true;
-	return f;
+	return rf.keep(rf.families, key, f, vgsdf_family_device_bytes(f), uploaded_bytes);
 }
 
 void Renderer::family_names(int lane, const vgsdf_family *family, std::vector<uint16_t> &code_point, std::vector<uint32_t> &advance) const

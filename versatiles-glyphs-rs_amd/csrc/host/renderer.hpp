@@ -540,6 +540,8 @@ private:
 	template <class Batch>
 	void submit_on_lane(int lane, const Batch &v, HostBuffer<uint8_t> &out, int (*submit)(vgsdf_ctx *, const Batch *, uint8_t *, size_t),
 	                    const char *name, uint64_t *block_bytes = nullptr) const;
+	// a resident font or family made by the C call `create` through the lane's context, under its lock; throws what the call says (`name`: for the error)
+	template <class Desc, class Made> Made *create_resident(int lane, int (*create)(vgsdf_ctx *, const Desc *, Made **), const Desc &d, const char *name) const;
 	std::vector<std::shared_ptr<Renderer>> peers_; // device lanes 1 .. N-1 of a multi-device renderer
 	struct ResidentFonts { // of a renderer and its peers
 		std::mutex mu;
@@ -552,6 +554,18 @@ private:
 		std::set<std::pair<int, uint64_t>> refused_glyf_tables;         // (device, serial): the device's table builder has refused the face
 		std::map<std::pair<int, uint64_t>, uint64_t> unfit_glyf_tables; // (device, serial) -> bytes of a font that passed the budget
 		uint64_t budget = 1ull << 30;
+		// the frame of resident_font() .. family_from_tables() (under `mu`): what the registry holds under a key, the budget a device has left, and a new
+		// font or family of `got` device bytes taken in and accounted (the key's first member is the device)
+		template <class Map, class Key> static typename Map::mapped_type find(const Map &map, const Key &key) { const auto it = map.find(key); return it != map.end() ? it->second : nullptr; }
+		uint64_t room(int device) { return budget > bytes[device] ? budget - bytes[device] : 0; }
+		template <class Map, class Key> typename Map::mapped_type keep(Map &map, const Key &key, typename Map::mapped_type made, uint64_t got, uint64_t *uploaded_bytes)
+		{
+			map.emplace(key, made);
+			bytes[std::get<0>(key)] += got;
+			if (uploaded_bytes)
+				*uploaded_bytes += got;
+			return made;
+		}
 	};
 	std::shared_ptr<ResidentFonts> resident_ = std::make_shared<ResidentFonts>();
 	bool owns_resident_ = true; // (a peer shares its primary's table and leaves the freeing to it)

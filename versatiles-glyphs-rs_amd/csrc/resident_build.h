@@ -1,0 +1,62 @@
+// resident_build.h — what the constructors of resident fonts (resident_fonts.cpp) and families (resident_families.cpp) share:
+// their error text, device memory for one call, the sequence of HIP calls of a phase and the events around a count and an emit pass.
+// Every allocation here and there asks for 16 bytes more than its layout states, as the front-end's buffers do: a kernel that
+// moves a buffer in 16-byte units may touch the whole unit its last byte lies in.  The layouts (upload_layout.h) do not count them.
+#pragma once
+#include "resident_fonts.h"
+
+// a failed HIP call of a constructor: the entry point's name, what it was doing and the runtime's words
+VGSDF_INTERNAL inline int font_hip_error(vgsdf_ctx *ctx, const char *entry, const char *what, hipError_t e)
+{
+	ctx->err = std::string(entry) + ": " + what + ": " + hipGetErrorString(e);
+	return e == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;
+}
+
+struct VGSDF_INTERNAL ScratchBuf : DevBuf { // device memory for the duration of one call
+	~ScratchBuf() { release(); }
+};
+
+// The calls of a constructor on its stream, in order, up to the first that fails: after it nothing more is issued, and the
+// caller hands `e` to font_hip_error under the name of the phase it is in.  A constructor ends with sync(): its store is complete
+// on the device when the call returns, so every context may name the font or family.
+struct VGSDF_INTERNAL Calls {
+	hipStream_t st;
+	hipError_t e = hipSuccess;
+	explicit Calls(hipStream_t stream) : st(stream) {}
+	bool failed() const { return e != hipSuccess; }
+	// host to device; nothing for no bytes
+	void copy(void *dst, const void *src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); }
+	void zero(void *dst, size_t bytes) { if (e == hipSuccess) e = hipMemsetAsync(dst, 0, bytes, st); }
+	// f() returns hipError_t or a kernel launcher's int; it is not called once a call has failed
+	template <class F> void launch(F &&f) { if (e == hipSuccess) e = (hipError_t)f(); }
+	void record(hipEvent_t ev) { if (e == hipSuccess) e = hipEventRecord(ev, st); }
+	void read_back(void *dst, const void *src, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st); }
+	void sync() { if (e == hipSuccess) e = hipStreamSynchronize(st); }
+};
+
+// what an exported `…_kernel_ms` getter answers: the context's pair of the last call, zeros without a context
+inline void pass_ms_out(const float *pair, float ms[2])
+{
+	if (ms)
+		ms[0] = pair ? pair[0] : 0.0f, ms[1] = pair ? pair[1] : 0.0f;
+}
+
+// the events around a count pass (0 .. 1) and an emit pass (1 .. 2; the emit pass records 1 again), and their times for the
+// context's `…_ms` pair
+struct VGSDF_INTERNAL PassEvents {
+	hipEvent_t at[3] = {nullptr, nullptr, nullptr};
+	hipError_t create()
+	{
+		for (hipEvent_t &ev : at)
+			if (hipError_t err = hipEventCreate(&ev); err != hipSuccess)
+				return err;
+		return hipSuccess;
+	}
+	void elapsed(float ms[2], int pass) const { (void)hipEventElapsedTime(&ms[pass], at[pass], at[pass + 1]); } // behind a sync()
+	~PassEvents()
+	{
+		for (hipEvent_t ev : at)
+			if (ev)
+				(void)hipEventDestroy(ev);
+	}
+};

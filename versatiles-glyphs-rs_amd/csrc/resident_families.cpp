@@ -1,0 +1,314 @@
+// resident_families.cpp — the families over resident fonts (resident_fonts.cpp): a font id's table
+// code point -> (font, glyph id, advance, scale, shift_x) on host and device (upload_layout.h, FamilyTableLayout), stated by the
+// host (vgsdf_family_create) or built by the device from the faces' cmap and hmtx (vgsdf_family_create_tables), for submissions
+// that name code-point ranges (vgsdf_outlines_submit_ranges).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <new>
+
+#include "family_table_kernels.h"
+#include "resident_build.h"
+
+namespace {
+// font k of a family: there, on the context's device and of the kind of font 0
+bool family_font_fits(const vgsdf_ctx *ctx, const vgsdf_font *const *fonts, uint32_t k)
+{
+	return fonts[k] && fonts[k]->device == ctx->device && fonts[k]->commands == fonts[0]->commands;
+}
+// what a family keeps of its (checked) fonts
+void adopt_fonts(vgsdf_family &f, const vgsdf_ctx *ctx, const vgsdf_font *const *fonts, uint32_t n_fonts)
+{
+	f.device = ctx->device;
+	f.commands = fonts[0]->commands;
+	f.fonts.assign(fonts, fonts + n_fonts);
+	for (const vgsdf_font *ft : f.fonts) {
+		f.max_cap = std::max(f.max_cap, ft->max_cap);
+		f.max_len = std::max(f.max_len, ft->max_len);
+	}
+}
+} // namespace
+
+extern "C" {
+
+int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->fonts ||
+	    (in->n_entries && (!in->code_point || !in->font_of || !in->glyph_id || !in->advance || !in->scale || !in->shift_x))) {
+		ctx->err = "vgsdf_family_create: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	const uint32_t n = in->n_entries;
+	if (in->n_fonts == 0 || in->n_fonts > 0x10000u || n > 0x10000u) {
+		ctx->err = "vgsdf_family_create: n_fonts must be 1 .. 65536 and n_entries at most 65536";
+		return VGSDF_E_ARG;
+	}
+	for (uint32_t k = 0; k < in->n_fonts; k++)
+		if (!family_font_fits(ctx, in->fonts, k)) {
+			ctx->err = "vgsdf_family_create: a NULL font, a font of another device than the context's, or fonts of both kinds";
+			return VGSDF_E_ARG;
+		}
+	for (uint32_t i = 0; i < n; i++)
+		if ((i && in->code_point[i] <= in->code_point[i - 1]) || in->font_of[i] >= in->n_fonts ||
+		    in->glyph_id[i] >= in->fonts[in->font_of[i]]->n_glyph_ids) {
+			ctx->err = "vgsdf_family_create: code points not strictly ascending, font_of past n_fonts, or a glyph id past its face";
+			return VGSDF_E_ARG;
+		}
+	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
+	if (!f) {
+		ctx->err = "vgsdf_family_create: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	adopt_fonts(*f, ctx, in->fonts, in->n_fonts);
+	f->code_point.assign(in->code_point, in->code_point + n);
+	f->font_of.assign(in->font_of, in->font_of + n);
+	f->glyph_id.assign(in->glyph_id, in->glyph_id + n);
+	f->advance.assign(in->advance, in->advance + n);
+	f->scale.assign(in->scale, in->scale + n);
+	f->shift_x.assign(in->shift_x, in->shift_x + n);
+	f->pbf_fix.resize(n);
+	f->cmd_pre.assign((size_t)n + 1, 0);
+	f->leaf_pre.assign((size_t)n + 1, 0);
+	auto varint_len = [](uint32_t v) { return v < 0x80u ? 1u : v < 0x4000u ? 2u : v < 0x200000u ? 3u : v < 0x10000000u ? 4u : 5u; };
+	for (uint32_t i = 0; i < n; i++) {
+		const vgsdf_font &ft = *f->fonts[f->font_of[i]];
+		const uint32_t id = f->glyph_id[i];
+		f->cmd_pre[i + 1] = f->cmd_pre[i] + ft.slots[id];
+		f->leaf_pre[i + 1] = f->leaf_pre[i] + (ft.commands ? 0u : ft.leaf_off[id + 1] - ft.leaf_off[id]);
+		f->pbf_fix[i] = (uint8_t)((1u + varint_len(f->code_point[i])) | ((1u + varint_len(f->advance[i])) << 4));
+		f->scales_plain = f->scales_plain && f->scale[i] > 0.0 && f->scale[i] < HUGE_VAL;
+	}
+	// the device's copy: one block in FamilyTableLayout, staged on the host and copied once
+	const vgsdf::FamilyTableLayout at(n);
+	std::vector<uint8_t> h(at.bytes + 16, 0);
+	std::memcpy(h.data() + at.scale, f->scale.data(), 8 * (size_t)n);
+	std::memcpy(h.data() + at.shift_x, f->shift_x.data(), 8 * (size_t)n);
+	for (uint32_t i = 0; i <= n; i++) {
+		((uint32_t *)(h.data() + at.cmd_pre))[i] = (uint32_t)f->cmd_pre[i];
+		((uint32_t *)(h.data() + at.leaf_pre))[i] = (uint32_t)f->leaf_pre[i];
+	}
+	std::memcpy(h.data() + at.advance, f->advance.data(), 4 * (size_t)n);
+	std::memcpy(h.data() + at.code_point, f->code_point.data(), 2 * (size_t)n);
+	std::memcpy(h.data() + at.font_of, f->font_of.data(), 2 * (size_t)n);
+	std::memcpy(h.data() + at.glyph_id, f->glyph_id.data(), 2 * (size_t)n);
+	std::memcpy(h.data() + at.pbf_fix, f->pbf_fix.data(), n);
+	(void)hipSetDevice(ctx->device);
+	if (hipError_t e = f->table.ensure(h.size()); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create", "hipMalloc", e);
+	Calls q(ctx->stream);
+	q.copy(f->table.p, h.data(), h.size());
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, "vgsdf_family_create", "upload", q.e);
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !out || !in->fonts || !in->tables) {
+		ctx->err = "vgsdf_family_create_tables: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	ctx->family_tables_ms[0] = ctx->family_tables_ms[1] = 0.0f;
+	const uint32_t n_fonts = in->n_fonts;
+	if (n_fonts == 0 || n_fonts > 0x10000u) {
+		ctx->err = "vgsdf_family_create_tables: n_fonts must be 1 .. 65536";
+		return VGSDF_E_ARG;
+	}
+	// what can be said without a lookup; the staging block's layout on the way:
+	// FamilyFaceRef[n_fonts] | FamilySubtable[all] | per face cmap, hmtx (4-aligned) | counts | flags
+	size_t n_subtables = 0, table_bytes = 0;
+	for (uint32_t k = 0; k < n_fonts; k++) {
+		const vgsdf_face_tables &t = in->tables[k];
+		if (!family_font_fits(ctx, in->fonts, k)) {
+			ctx->err = "vgsdf_family_create_tables: a NULL font, a font of another device than the context's, or fonts of both kinds";
+			return VGSDF_E_ARG;
+		}
+		if ((t.cmap_len && !t.cmap) || (t.hmtx_len && !t.hmtx) || (t.n_subtables && (!t.subtable_off || !t.subtable_format))) {
+			ctx->err = "vgsdf_family_create_tables: a NULL table or subtable array of a length that is not 0";
+			return VGSDF_E_ARG;
+		}
+		if (t.units_per_em < 16 || t.units_per_em > 16384) {
+			ctx->err = "vgsdf_family_create_tables: units_per_em not 16 .. 16384";
+			return VGSDF_E_ARG;
+		}
+		for (uint32_t s = 0; s < t.n_subtables; s++) {
+			const uint16_t fm = t.subtable_format[s];
+			if (t.subtable_off[s] >= t.cmap_len || !(fm == 0 || fm == 4 || fm == 6 || fm == 10 || fm == 12 || fm == 13)) {
+				ctx->err = "vgsdf_family_create_tables: a subtable offset at or past cmap_len, or a format that is not 0, 4, 6, 10, 12 or 13";
+				return VGSDF_E_ARG;
+			}
+		}
+		n_subtables += t.n_subtables;
+		table_bytes += align_up(t.cmap_len, 4) + align_up(t.hmtx_len, 4);
+	}
+	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
+	if (!f) {
+		ctx->err = "vgsdf_family_create_tables: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	adopt_fonts(*f, ctx, in->fonts, n_fonts);
+	const size_t a_subs = sizeof(vgsdf::FamilyFaceRef) * (size_t)n_fonts, a_bytes = a_subs + sizeof(vgsdf::FamilySubtable) * n_subtables,
+	             a_counts = align_up(a_bytes + table_bytes, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
+	             a_total = a_flags + 16;
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	ScratchBuf dev;
+	if (hipError_t e = dev.ensure(a_total); e != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipMalloc", e);
+	uint8_t *d = (uint8_t *)dev.p;
+	std::vector<uint8_t> h(a_counts, 0);
+	{
+		vgsdf::FamilyFaceRef *faces = (vgsdf::FamilyFaceRef *)h.data();
+		vgsdf::FamilySubtable *subs = (vgsdf::FamilySubtable *)(h.data() + a_subs);
+		size_t at_sub = 0, at_byte = a_bytes;
+		for (uint32_t k = 0; k < n_fonts; k++) {
+			const vgsdf_font &ft = *in->fonts[k];
+			const vgsdf_face_tables &t = in->tables[k];
+			vgsdf::FamilyFaceRef &r = faces[k];
+			r.subtables = (uint64_t)(uintptr_t)(d + a_subs + sizeof(vgsdf::FamilySubtable) * at_sub);
+			for (uint32_t s = 0; s < t.n_subtables; s++)
+				subs[at_sub++] = vgsdf::FamilySubtable{t.subtable_off[s], t.subtable_format[s]};
+			r.cmap = (uint64_t)(uintptr_t)(d + at_byte);
+			if (t.cmap_len)
+				std::memcpy(h.data() + at_byte, t.cmap, t.cmap_len);
+			at_byte += align_up(t.cmap_len, 4);
+			r.hmtx = t.hmtx_len ? (uint64_t)(uintptr_t)(d + at_byte) : 0;
+			if (t.hmtx_len)
+				std::memcpy(h.data() + at_byte, t.hmtx, t.hmtx_len);
+			at_byte += align_up(t.hmtx_len, 4);
+			r.off = ft.commands ? ft.cref.cmd_off : ft.ref.leaf_off;
+			r.leaves = ft.commands ? 0 : ft.ref.leaves;
+			r.cmap_len = t.cmap_len, r.hmtx_len = t.hmtx_len;
+			r.n_glyph_ids = ft.n_glyph_ids;
+			r.units_per_em = t.units_per_em, r.num_glyphs = t.num_glyphs, r.num_hmetrics = t.num_hmetrics, r.n_subtables = t.n_subtables;
+			r.commands = ft.commands ? 1u : 0u;
+		}
+	}
+	PassEvents ev;
+	if (hipError_t err = ev.create(); err != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipEventCreate", err);
+	const vgsdf::FamilyFaceRef *faces = (const vgsdf::FamilyFaceRef *)d;
+	uint32_t *counts = (uint32_t *)(d + a_counts), *flags = (uint32_t *)(d + a_flags);
+	Calls q(st);
+	q.copy(d, h.data(), h.size());
+	q.zero(d + a_flags, 16);
+	q.record(ev.at[0]);
+	q.launch([&] { return vgsdf_family_tables_count(faces, n_fonts, counts, flags, st); });
+	q.record(ev.at[1]);
+	uint32_t got[vgsdf::kFamilyCounts * vgsdf::kFamilyGroups + 1]; // the counts and, behind them, the flag word
+	q.read_back(got, counts, sizeof got);
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "count pass", q.e);
+	ev.elapsed(ctx->family_tables_ms, 0);
+	if (got[vgsdf::kFamilyCounts * vgsdf::kFamilyGroups]) {
+		ctx->err = "vgsdf_family_create_tables: a glyph id past its face";
+		return VGSDF_E_ARG;
+	}
+	uint32_t n = 0;
+	for (uint32_t w = 0; w < vgsdf::kFamilyGroups; w++)
+		n += got[vgsdf::kFamilyCounts * w];
+	// the table as vgsdf_family_create allocates it (the same size: the same vgsdf_family_device_bytes)
+	const vgsdf::FamilyTableLayout at(n);
+	if (hipError_t err = f->table.ensure(at.bytes + 16); err != hipSuccess)
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipMalloc", err);
+	std::vector<uint8_t> back(at.bytes);
+	q.record(ev.at[1]);
+	q.launch([&] { return vgsdf_family_tables_emit(faces, n_fonts, counts, n, (uint8_t *)f->table.p, st); });
+	q.record(ev.at[2]);
+	q.read_back(back.data(), f->table.p, at.bytes);
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, "vgsdf_family_create_tables", "emit pass", q.e);
+	ev.elapsed(ctx->family_tables_ms, 1);
+	// the host's copy from the one read-back; the 64-bit running sums from the table's differences (exact: a glyph holds fewer
+	// than 2^31 slots and fewer than 2^32 leaves)
+	auto slice = [&](auto &v, size_t off, size_t count) {
+		v.resize(count);
+		if (count)
+			std::memcpy(v.data(), back.data() + off, sizeof(v[0]) * count);
+	};
+	slice(f->scale, at.scale, n), slice(f->shift_x, at.shift_x, n), slice(f->advance, at.advance, n), slice(f->code_point, at.code_point, n);
+	slice(f->font_of, at.font_of, n), slice(f->glyph_id, at.glyph_id, n), slice(f->pbf_fix, at.pbf_fix, n);
+	f->cmd_pre.assign((size_t)n + 1, 0);
+	f->leaf_pre.assign((size_t)n + 1, 0);
+	const uint32_t *cp32 = (const uint32_t *)(back.data() + at.cmd_pre), *lp32 = (const uint32_t *)(back.data() + at.leaf_pre);
+	for (uint32_t i = 0; i < n; i++) {
+		f->cmd_pre[i + 1] = f->cmd_pre[i] + (uint32_t)(cp32[i + 1] - cp32[i]);
+		f->leaf_pre[i + 1] = f->leaf_pre[i] + (uint32_t)(lp32[i + 1] - lp32[i]);
+	}
+	// (scales_plain stays true: every scale is 24 / units_per_em of a checked units_per_em)
+	*out = f.release();
+	return VGSDF_OK;
+}
+
+void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]) { pass_ms_out(ctx ? ctx->family_tables_ms : nullptr, ms); }
+
+int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_entries, uint16_t *code_point, uint16_t *font_of,
+                      uint16_t *glyph_id, uint32_t *advance, double *scale, double *shift_x, uint32_t *cmd_pre, uint32_t *leaf_pre,
+                      uint8_t *pbf_fix)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!family || family->device != ctx->device) {
+		ctx->err = "vgsdf_family_read: no family, or a family of another device than the context's";
+		return VGSDF_E_ARG;
+	}
+	const size_t n = family->code_point.size();
+	if (n_entries)
+		*n_entries = (uint32_t)n;
+	(void)hipSetDevice(ctx->device);
+	const vgsdf::FamilyTableLayout at(n);
+	const uint8_t *t = (const uint8_t *)family->table.p;
+	auto read = [&](void *dst, size_t off, size_t bytes) { return dst && bytes ? hipMemcpy(dst, t + off, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+	HIP_TRY(ctx, read(code_point, at.code_point, 2 * n));
+	HIP_TRY(ctx, read(font_of, at.font_of, 2 * n));
+	HIP_TRY(ctx, read(glyph_id, at.glyph_id, 2 * n));
+	HIP_TRY(ctx, read(advance, at.advance, 4 * n));
+	HIP_TRY(ctx, read(scale, at.scale, 8 * n));
+	HIP_TRY(ctx, read(shift_x, at.shift_x, 8 * n));
+	HIP_TRY(ctx, read(cmd_pre, at.cmd_pre, 4 * (n + 1)));
+	HIP_TRY(ctx, read(leaf_pre, at.leaf_pre, 4 * (n + 1)));
+	HIP_TRY(ctx, read(pbf_fix, at.pbf_fix, n));
+	return VGSDF_OK;
+}
+
+int vgsdf_family_free(vgsdf_ctx *ctx, vgsdf_family *family)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!family)
+		return VGSDF_OK;
+	if (family->device != ctx->device) {
+		ctx->err = "vgsdf_family_free: the family lives on another device than the context";
+		return VGSDF_E_ARG;
+	}
+	(void)hipSetDevice(ctx->device);
+	delete family;
+	return VGSDF_OK;
+}
+
+uint64_t vgsdf_family_device_bytes(const vgsdf_family *family) { return family ? (uint64_t)family->table.cap : 0; }
+
+uint32_t vgsdf_family_count(const vgsdf_family *family, uint32_t first, uint32_t last)
+{
+	if (!family || first > last)
+		return 0;
+	const auto &cp = family->code_point;
+	const auto lo = std::lower_bound(cp.begin(), cp.end(), (uint16_t)std::min(first, 0xFFFFu));
+	if (first > 0xFFFFu)
+		return 0;
+	const auto hi = std::upper_bound(cp.begin(), cp.end(), (uint16_t)std::min(last, 0xFFFFu));
+	return (uint32_t)(hi - lo);
+}
+
+} // extern "C"

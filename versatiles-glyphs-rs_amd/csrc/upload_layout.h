@@ -92,8 +92,38 @@ struct CommandBlockLayout : GlyphArraysLayout {
 	}
 };
 
+// The stores those references point into: one device allocation per font, laid out the same by every constructor of a kind
+// (resident_fonts.cpp), so the same face takes the same vgsdf_font_device_bytes whichever way it was built.  A glyf font:
+//   leaves vgsdf_glyf_part[n_leaves] | bytes u8[n_bytes] (a multiple of 4) | pad to 16 | leaf_off u32[n_glyph_ids + 1]
+struct GlyfStoreLayout {
+	size_t leaves = 0, bytes, leaf_off, total;
+	constexpr GlyfStoreLayout(size_t n_glyph_ids, size_t n_leaves, size_t n_bytes)
+	    : bytes(sizeof(vgsdf_glyf_part) * n_leaves), leaf_off((bytes + n_bytes + 15) / 16 * 16), total(leaf_off + 4 * (n_glyph_ids + 1))
+	{
+	}
+};
+// A command font: records (28 bytes each) [n_cmds] | cmd_off u32[n_glyph_ids + 1] | open u8[n_cmds] (the context pass's byte per
+// record) = 29 n_cmds + 4 (n_glyph_ids + 1) bytes; `total` is also what the 32-bit offsets of a store are checked against
+struct CommandStoreLayout {
+	size_t cmds = 0, cmd_off, open, total;
+	constexpr CommandStoreLayout(size_t n_glyph_ids, size_t n_cmds)
+	    : cmd_off(28 * n_cmds), open(cmd_off + 4 * (n_glyph_ids + 1)), total(open + n_cmds)
+	{
+	}
+};
+static_assert(sizeof(vgsdf_glyf_part) == 48, "a leaf of a glyf store");
+static_assert(GlyfStoreLayout(5, 3, 16).bytes == 144 && GlyfStoreLayout(5, 3, 16).leaf_off == 160 && GlyfStoreLayout(5, 3, 16).total == 184 &&
+                  GlyfStoreLayout(5, 3, 20).leaf_off == 176 && GlyfStoreLayout(5, 3, 24).leaf_off == 176 && GlyfStoreLayout(5, 3, 28).leaf_off == 176 &&
+                  GlyfStoreLayout(5, 3, 28).total == 200 && GlyfStoreLayout(7, 0, 0).leaf_off == 0 && GlyfStoreLayout(7, 0, 0).total == 32 &&
+                  GlyfStoreLayout(0, 0, 0).total == 4 && GlyfStoreLayout(0, 1, 4).leaf_off == 64 && GlyfStoreLayout(0, 1, 4).total == 68,
+              "leaves | bytes | pad to 16 | leaf_off, at n_bytes = 0, 4, 8, 12 (mod 16), without leaves and without glyph ids");
+static_assert(CommandStoreLayout(3, 10).cmd_off == 280 && CommandStoreLayout(3, 10).open == 296 && CommandStoreLayout(3, 10).total == 29 * 10 + 4 * 4 &&
+                  CommandStoreLayout(65, 0).cmd_off == 0 && CommandStoreLayout(65, 0).open == 264 && CommandStoreLayout(65, 0).total == 264 &&
+                  CommandStoreLayout(0, 0).total == 4 && CommandStoreLayout(0x10000, 0x8000000).total == 29ull * 0x8000000 + 4ull * 0x10001,
+              "records | cmd_off | open: 29 bytes per command and 4 per glyph id + 4, without commands and without glyph ids");
+
 // The form that names code-point RANGES of resident families (vgsdf_outlines_ranges).  A family's table lives on the device
-// (resident_fonts.cpp, vgsdf_family_create), one allocation of arrays over its n entries:
+// (resident_families.cpp, vgsdf_family_create), one allocation of arrays over its n entries:
 //   scale f64[n] | shift_x f64[n] | cmd_pre u32[n + 1] | leaf_pre u32[n + 1] | advance u32[n] | code_point u16[n] |
 //   font_of u16[n] | glyph_id u16[n] | pbf_fix u8[n]
 // cmd_pre / leaf_pre: prefix sums over the entries of their glyphs' command slots / leaves, mod 2^32 (a submission holds fewer
