@@ -200,6 +200,16 @@ typedef struct {
 	uint64_t fallbacks;       /* faces whose fonts came from the host's table although the switch is on */
 } vg_glyf_table_stats;
 int vg_manager_glyf_table_stats(const vg_manager *m, vg_glyf_table_stats *out);
+/* ... batched, 0 (default) / 1; has an effect only with vg_manager_set_glyf_tables_on_device: the glyf fonts of ALL files of a
+ * font id that the device has yet to build are built in one call (vgsdf_fonts_create_tables: one count launch, one read-back, one
+ * emit launch) instead of one call per file, so what a call costs beside its two passes is paid once per font id.  Same fonts,
+ * same registry, budget, fallbacks and vg_glyf_table_stats, same output.  vg_manager_glyf_table_batch_stats: of the last render. */
+void vg_manager_set_glyf_tables_batched(vg_manager *m, int on);
+typedef struct {
+	uint64_t calls; /* batched calls made during the render (a font id whose fonts were all there makes none) */
+	uint64_t faces; /* the faces they were given */
+} vg_glyf_table_batch_stats;
+int vg_manager_glyf_table_batch_stats(const vg_manager *m, vg_glyf_table_batch_stats *out);
 /* How a renderer of several device lanes (vg_renderer_new_multi) splits a run: -1 / 2 (default) the hybrid plan — whole
  * (font, block) tasks per lane, manager.rs:86-97's unit, and the heaviest blocks' glyphs split between lanes until the lanes'
  * estimated raster cost is within 4 % of the mean; 1 whole tasks only; 0 glyph-level shards of every font (every block

@@ -448,6 +448,28 @@ int vgsdf_font_read(vgsdf_ctx *ctx, const vgsdf_font *font, uint32_t *n_glyph_id
  * context's last vgsdf_font_create_tables took (HIP events around the pass; 0 0 before the first, and for a pass that did not run) */
 void vgsdf_font_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
 /*
+ * The same for ALL FACES OF A FONT ID in one call: one count launch, one read-back, one emit launch, so that what a call costs
+ * beside its two passes (its synchronisations, events, scratch allocation) is paid once and not once per face.  Each face that
+ * is built is a vgsdf_font of its own, with its own store: it cannot be told from what vgsdf_font_create_tables makes of that
+ * face alone, and is read, named by submissions and families, and freed like it, each alone.  Per face f:
+ *   built                                      status[f] VGSDF_OK      out[f] the font
+ *   over the limit (_within)                   status[f] VGSDF_OK      out[f] NULL, needed[f] its store's bytes
+ *   badly described (the single call's VGSDF_E_ARG conditions)   status[f] VGSDF_E_ARG   out[f] NULL
+ *   refused (its VGSDF_E_GLYF conditions)      status[f] VGSDF_E_GLYF  out[f] NULL
+ * and a bad or refused face leaves the others untouched.  _within takes the faces in order: a face is built when its store fits
+ * into what the faces built before it have left of max_store_bytes; one that does not fit is passed over and does not stop the
+ * faces behind it.  needed (may be NULL): [n_faces], 0 for a face that was badly described or refused.
+ * The whole call fails with VGSDF_E_ARG, before anything runs, for a NULL argument, more than 65536 faces or well-described
+ * faces of more than 2^22 glyph ids together; a HIP error or an exhausted host fails it too: nothing is left allocated, every
+ * out[f] is NULL and the context stays sound.  n_faces == 0: VGSDF_OK, nothing is touched.
+ */
+int vgsdf_fonts_create_tables(vgsdf_ctx *ctx, const vgsdf_font_tables_desc *faces, uint32_t n_faces, vgsdf_font **out /* [n_faces] */,
+                              int *status /* [n_faces] */);
+int vgsdf_fonts_create_tables_within(vgsdf_ctx *ctx, const vgsdf_font_tables_desc *faces, uint32_t n_faces, uint64_t max_store_bytes,
+                                     vgsdf_font **out, int *status, uint64_t *needed /* [n_faces], may be NULL */);
+/* test / inspection (tools/glyf_tables_ab.py): the count and the emit pass of the context's last vgsdf_fonts_create_tables */
+void vgsdf_fonts_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
+/*
  * Resident families: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id lives on the device
  * beside its fonts, and a submission names CODE-POINT RANGES of families instead of glyphs.  The host's share per submission
  * is O(tasks): the block it uploads holds 32 bytes per task that maps a glyph, per family and per font, and no per-glyph byte.

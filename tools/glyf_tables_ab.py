@@ -1,9 +1,10 @@
-"""A/B of the two ways to a glyf-kind resident font, the forms alternating in one process, every run on a fresh FontManager (so
-the host's table is built in the timed span: the first use of a face is what is measured):
+"""A/B of the three ways to the glyf-kind resident fonts of a font id, the forms alternating in one process, every run on a fresh
+FontManager (so the host's table is built in the timed span: the first use of a face is what is measured):
   (a) Face::resident_table (every glyph id's composite tree walked, every simple entry copied) + vgsdf_font_create  [the baseline]
-  (b) Face::font_tables (where loca and glyf are; no glyph looked at) + vgsdf_font_create_tables
+  (b) Face::font_tables (where loca and glyf are; no glyph looked at) + vgsdf_font_create_tables, one call per face
+  (c) Face::font_tables of every face + ONE vgsdf_fonts_create_tables over all of them
 at the C ABI, with the count and emit passes' own times from HIP events, and through the façade: the first render_glyphs of a
-fresh manager with vg_manager_set_glyf_tables_on_device off and on (resident glyf fonts).
+fresh manager with vg_manager_set_glyf_tables_on_device off, on, and on with vg_manager_set_glyf_tables_batched (resident glyf fonts).
 Inputs: Fira Sans, Noto Sans Regular, the 20 Noto files, and Noto Sans Regular's glyphs repeated to 60 000 glyph ids (C ABI only).
   python tools/glyf_tables_ab.py [--runs 20]"""
 import argparse
@@ -21,7 +22,7 @@ from conftest import FIRA, NOTO, load_product, noto_files  # noqa: E402
 
 
 def stats(v):
-    return f"best {min(v) * 1e3:8.3f} ms  median {statistics.median(v) * 1e3:8.3f} ms"
+    return f"best {min(v) * 1e3:8.3f} ms  median {statistics.median(v) * 1e3:8.3f} ms  worst {max(v) * 1e3:8.3f} ms"
 
 
 def repeated(path, n_glyphs):
@@ -70,71 +71,97 @@ def main():
             return mgr, mgr.add_font_data("Font", files[0])
         return mgr, mgr.add_font_with_name("Font", files)
 
-    def abi_once(files, device):
-        """-> (description seconds, create seconds, (count, emit) ms, leaves, font bytes) summed over the files"""
+    def abi_once(files, form):
+        """form 0 (a), 1 (b), 2 (c) -> (description seconds, create seconds, (count, emit) ms, leaves, font bytes) summed over the files"""
         mgr, fid = manager(files)
         t_desc = t_create = 0.0
         ms, leaves, size = [0.0, 0.0], 0, 0
-        for k in range(len(files)):
-            h, n_leaves = C.c_void_p(), C.c_uint32()
+        made = []
+        if form == 2:
+            n = len(files)
+            descs, out, status = (D._CFontTablesDesc * n)(), (C.c_void_p * n)(), (C.c_int * n)()
             t0 = time.perf_counter()
-            if device:
-                d = D._CFontTablesDesc()
-                assert HL.vg_manager_font_tables_desc(mgr._h, fid.encode(), k, C.byref(d)) == 0
-                t1 = time.perf_counter()
-                rc = L.vgsdf_font_create_tables(ctx._h, C.byref(d), C.byref(h))
-            else:
-                d = D._CFontDesc()
-                assert HL.vg_manager_resident_font_desc(mgr._h, fid.encode(), k, C.byref(d)) == 0
-                t1 = time.perf_counter()
-                rc = L.vgsdf_font_create(ctx._h, C.byref(d), C.byref(h))
+            for k in range(n):
+                assert HL.vg_manager_font_tables_desc(mgr._h, fid.encode(), k, C.byref(descs[k])) == 0
+            t1 = time.perf_counter()
+            rc = L.vgsdf_fonts_create_tables(ctx._h, descs, n, out, status)
             t2 = time.perf_counter()
-            assert rc == 0, rc
-            t_desc, t_create = t_desc + t1 - t0, t_create + t2 - t1
-            if device:
-                km = ctx.font_tables_kernel_ms()
-                ms[0], ms[1] = ms[0] + km[0], ms[1] + km[1]
+            assert rc == 0 and not any(status) and all(out), (rc, list(status))
+            t_desc, t_create, ms = t1 - t0, t2 - t1, list(ctx.fonts_tables_kernel_ms())
+            made = [C.c_void_p(h) for h in out]
+        else:
+            for k in range(len(files)):
+                h = C.c_void_p()
+                t0 = time.perf_counter()
+                if form == 1:
+                    d = D._CFontTablesDesc()
+                    assert HL.vg_manager_font_tables_desc(mgr._h, fid.encode(), k, C.byref(d)) == 0
+                    t1 = time.perf_counter()
+                    rc = L.vgsdf_font_create_tables(ctx._h, C.byref(d), C.byref(h))
+                else:
+                    d = D._CFontDesc()
+                    assert HL.vg_manager_resident_font_desc(mgr._h, fid.encode(), k, C.byref(d)) == 0
+                    t1 = time.perf_counter()
+                    rc = L.vgsdf_font_create(ctx._h, C.byref(d), C.byref(h))
+                t2 = time.perf_counter()
+                assert rc == 0, rc
+                t_desc, t_create = t_desc + t1 - t0, t_create + t2 - t1
+                if form == 1:
+                    km = ctx.font_tables_kernel_ms()
+                    ms[0], ms[1] = ms[0] + km[0], ms[1] + km[1]
+                made.append(h)
+        for h in made:                                                                 # (outside the timed spans)
+            n_leaves = C.c_uint32()
             assert L.vgsdf_font_read(ctx._h, h, None, C.byref(n_leaves), None, None, None, None) == 0
             leaves += n_leaves.value
             size += L.vgsdf_font_device_bytes(h)
             L.vgsdf_font_free(ctx._h, h)
         return t_desc, t_create, ms, leaves, size
 
-    def facade_once(files, device):
+    def facade_once(files, form):
         mgr, _ = manager(files)
         mgr.set_resident_fonts(True)
-        mgr.set_glyf_tables_on_device(device)
+        mgr.set_glyf_tables_on_device(form >= 1)
+        mgr.set_glyf_tables_batched(form == 2)
         r = vg.Renderer.new_precise(0)
         w = vg.DummyWriter()
         t0 = time.perf_counter()
         mgr.render_glyphs(w, r)
         t = time.perf_counter() - t0
-        s = mgr.glyf_table_stats()
-        assert (s["built_on_device"], s["fallbacks"]) == (len(files) if device else 0, 0), s
+        s, b = mgr.glyf_table_stats(), mgr.glyf_table_batch_stats()
+        assert (s["built_on_device"], s["fallbacks"]) == (len(files) if form else 0, 0), s
+        assert b == ({"calls": 1, "faces": len(files)} if form == 2 else {"calls": 0, "faces": 0}), b
         r.close()
         return t
 
+    forms = (0, 1, 2)
+    labels = {0: "(a) resident_table + vgsdf_font_create           ", 1: "(b) font_tables + vgsdf_font_create_tables, each  ",
+              2: "(c) font_tables + ONE vgsdf_fonts_create_tables   "}
     for name, files, render in inputs:
-        abi_once(files, False), abi_once(files, True)                                  # warm: code, allocator, clocks
-        rows, renders = {False: [], True: []}, {False: [], True: []}
+        for form in forms:
+            abi_once(files, form)                                                      # warm: code, allocator, clocks
+        rows, renders = {f: [] for f in forms}, {f: [] for f in forms}
         for _ in range(args.runs):
-            for device in (False, True):
-                rows[device].append(abi_once(files, device))
-        assert rows[True][0][3] == rows[False][0][3]
-        print(f"\n{name}: {rows[True][0][3]} leaves, fonts of {rows[False][0][4]} (a) / {rows[True][0][4]} (b) bytes on the device, {args.runs} runs each, alternating")
-        for device, label in ((False, "(a) resident_table + vgsdf_font_create    "), (True, "(b) font_tables + vgsdf_font_create_tables")):
-            r = rows[device]
-            print(f"  {label} description {stats([x[0] for x in r])} | create {stats([x[1] for x in r])} | both {stats([x[0] + x[1] for x in r])}")
-        k = [x[2] for x in rows[True]]
-        print(f"  passes of (b): count best {min(x[0] for x in k):.3f} ms median {statistics.median(x[0] for x in k):.3f} ms | "
-              f"emit + copy best {min(x[1] for x in k):.3f} ms median {statistics.median(x[1] for x in k):.3f} ms")
+            for form in forms:
+                rows[form].append(abi_once(files, form))
+        assert rows[0][0][3] == rows[1][0][3] == rows[2][0][3]
+        print(f"\n{name}: {len(files)} file(s), {rows[1][0][3]} leaves, fonts of {rows[0][0][4]} (a) / {rows[1][0][4]} (b) / {rows[2][0][4]} (c) bytes on the device, "
+              f"{args.runs} runs each, alternating")
+        for form in forms:
+            r = rows[form]
+            print(f"  {labels[form]} description {stats([x[0] for x in r])} | create {stats([x[1] for x in r])} | both {stats([x[0] + x[1] for x in r])}")
+        for form in (1, 2):
+            k = [x[2] for x in rows[form]]
+            print(f"  passes of ({'abc'[form]}), summed over its calls: count best {min(x[0] for x in k):.3f} ms median {statistics.median(x[0] for x in k):.3f} ms | "
+                  f"emit + copy best {min(x[1] for x in k):.3f} ms median {statistics.median(x[1] for x in k):.3f} ms")
         if render:
-            facade_once(files, False), facade_once(files, True)
+            for form in forms:
+                facade_once(files, form)
             for _ in range(args.runs):
-                for device in (False, True):
-                    renders[device].append(facade_once(files, device))
-            for device, label in ((False, "switch off"), (True, "switch on ")):
-                print(f"  façade, first render of a fresh manager, {label}: {stats(renders[device])}")
+                for form in forms:
+                    renders[form].append(facade_once(files, form))
+            for form, label in ((0, "switch off          "), (1, "tables on device    "), (2, "... and batched     ")):
+                print(f"  façade, first render of a fresh manager, {label}: {stats(renders[form])}")
     ctx.close()
 
 

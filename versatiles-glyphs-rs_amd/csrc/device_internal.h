@@ -67,6 +67,7 @@ struct vgsdf_ctx {
 	size_t charstring_spill_bytes = 0;
 	float family_tables_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_family_create_tables (resident_families.cpp)
 	float glyf_tables_ms[2] = {0.0f, 0.0f};   // count / emit kernels of the last vgsdf_font_create_tables (resident_fonts.cpp)
+	float glyf_batch_ms[2] = {0.0f, 0.0f};    // the same of the last vgsdf_fonts_create_tables: one launch each over all its faces
 	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
 };
 

@@ -30,9 +30,35 @@ enum : uint32_t {
 	GLYF_FLAG_WORDS = 4,
 };
 
+// One face of a batch (vgsdf_fonts_create_tables), all addresses on the device: GlyfTablesRef's fields, where the face's
+// workgroups and glyph ids begin in the launch, and, for the emit pass, its store (GlyfStoreLayout: the leaves at its start).
+// The batch's counts lie at counts[4 * (glyph_base + g)], its byte_at at byte_at[glyph_base + f + g] (n_glyph_ids + 1 entries per
+// face f), its flags at flags[GLYF_FLAG_WORDS * f].  Read through the scalar cache, as the family tables' face records are.
+struct GlyfFaceRecord {
+	uint64_t loca, glyf;
+	uint32_t glyf_len, loca_entries, loca_long, n_glyph_ids;
+	uint32_t first_block; // the workgroups of the faces before it that take part in this pass
+	uint32_t glyph_base;  // the glyph ids of ALL faces before it
+	uint64_t store;       // emit pass: the face's store; count pass: 0
+	uint32_t bytes_at, leaf_off_at16; // emit pass: GlyfStoreLayout's bytes and leaf_off / 16 (a store may pass 4 GiB) inside the store
+	uint32_t takes_part;  // 0: the face owns no workgroup of this pass (badly described; emit pass: refused or over the limit)
+	uint32_t reserved;
+};
+static_assert(sizeof(GlyfFaceRecord) == 64, "one 64-byte record per face");
+
+// what one batched call takes: the bisection's table and 64 MB of counts
+constexpr uint32_t kGlyfBatchMaxFaces = 65536;
+constexpr uint32_t kGlyfBatchMaxGlyphIds = 1u << 22;
+
 } // namespace vgsdf
 
 extern "C" {
+// the two passes over all faces of a batch in one launch each; n_blocks > 0: the sum of ceil(n_glyph_ids / 64) over the faces that
+// take part, which is what their first_block fields run over.  flags: GLYF_FLAG_WORDS zeroed words per face
+int vgsdf_glyf_tables_batch_count(const vgsdf::GlyfFaceRecord *faces, uint32_t n_faces, uint32_t n_blocks, uint32_t *counts, uint32_t *flags,
+                                  hipStream_t stream);
+int vgsdf_glyf_tables_batch_emit(const vgsdf::GlyfFaceRecord *faces, uint32_t n_faces, uint32_t n_blocks, const uint32_t *byte_at,
+                                 uint32_t *flags, hipStream_t stream);
 // count pass: counts[4 g ..] = {byte_len of g's own simple entry (0: none), leaves, command slots, cmd_cap of the own entry}
 int vgsdf_glyf_tables_count(const vgsdf::GlyfTablesRef *face, uint32_t *counts, uint32_t *flags, hipStream_t stream);
 // emit pass: glyph id g's leaves to leaves[leaf_off[g] .. leaf_off[g + 1]) (48-byte vgsdf_glyf_part records), its own simple

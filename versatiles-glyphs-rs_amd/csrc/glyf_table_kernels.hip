@@ -5,6 +5,9 @@
 // loop over an explicit stack in LDS ([level][word][lane]: indexed at run time, so not a private array); the composite being
 // read lives in registers.  Every read is bounded by loca_entries / glyf_len, every store of the emit pass by the ranges the
 // count pass of the same text has sized.  A glyph id reads at most VGSDF_GLYF_MAX_COMPONENTS component records.
+// The walk itself is glyf_table_walk.inc, the body of two pairs of kernels: glyf_tables_pass over one face that comes in the
+// kernel's arguments (vgsdf_font_create_tables), glyf_tables_batch_pass over the faces of a batch, each workgroup finding its
+// face's record in device memory (vgsdf_fonts_create_tables).
 #include "glyf_table_kernels.h"
 
 #include "glyf_table_limits.h"
@@ -89,167 +92,42 @@ __global__ __launch_bounds__(kGlyfTableLanes) void glyf_tables_pass(GlyfTablesRe
 {
 	__shared__ uint32_t stack[kGlyfTableLevels][kGlyfTableFrameWords][kGlyfTableLanes];
 	const uint32_t lane = threadIdx.x, gid = blockIdx.x * kGlyfTableLanes + lane;
-	const bool live = gid < F.n_glyph_ids;
-	uint32_t n_leaves = 0, slots = 0, records = 0;
-	uint32_t own_len = 0, own_cap = 0, own_body = 0, own_ends = 0, own_cur = 0; // the glyph id's own simple entry
-	uint32_t leaf_at = 0, leaf_end = 0;
-	if (EMIT && live)
-		leaf_at = leaf_off[gid], leaf_end = leaf_off[gid + 1];
+#include "glyf_table_walk.inc"
+}
 
-	// the composite being read: its depth (-1: none), where its next record is, where its entry ends, its transform
-	int depth = -1;
-	uint32_t p = 0, end = 0;
-	Affine T = identity();
-	// a glyph that has been named and resolved, to be entered at depth + 1
-	bool pending = false;
-	uint32_t pa = 0, pb = 0, pgid = gid;
-	Affine PT = identity();
-	if (live)
-		pending = glyph_range(F, gid, pa, pb);
-	bool run = pending;
-	while (run) {
-		if (pending) { // GlyfWalker::walk(glyph, depth + 1, PT) up to its loop
-			pending = false;
-			const int d = depth + 1;
-			const uint32_t len = pb - pa;
-			if (d >= vg::kGlyfMaxComponentDepth || len < 2)
-				break; // fails: the whole glyph stops, the leaves so far stay
-			const int n_contours = (int16_t)be16(F.glyf + pa);
-			if (n_contours > 0) {
-				if (len < 10)
-					break;
-				const Shape sh = measure(F.glyf + pa + 10, len - 10, (uint32_t)n_contours);
-				if (sh.kind == SHAPE_FAIL)
-					break;
-				if (sh.kind == SHAPE_PART) { // ResidentSink::part
-					const uint32_t cap = sh.n_points + 2u * (uint32_t)n_contours, byte_len = sh.ends + sh.arrays;
-					if ((uint64_t)slots + cap > vg::kResidentMaxGlyphSlots) {
-						if (!EMIT)
-							flags[GLYF_FLAG_SLOTS] = 1;
-						break;
-					}
-					if (EMIT) {
-						const uint32_t at = leaf_at + n_leaves;
-						if (at < leaf_end) {
-							uint4 *o = (uint4 *)(leaves + (size_t)at * 12);
-							o[0] = make_uint4(byte_at[pgid], byte_len, slots, cap);
-							o[1] = make_uint4((uint32_t)n_contours, is_identity(PT) ? 1u : 0u, __float_as_uint(PT.a), __float_as_uint(PT.b));
-							o[2] = make_uint4(__float_as_uint(PT.c), __float_as_uint(PT.d), __float_as_uint(PT.e), __float_as_uint(PT.f));
-						} else {
-							flags[GLYF_FLAG_EMIT] = 1;
-						}
-					}
-					if (d == 0)
-						own_len = byte_len, own_cap = cap, own_body = pa + 10, own_ends = sh.ends, own_cur = sh.cur;
-					slots += cap;
-					n_leaves++;
-				}
-			} else if (n_contours < 0) {
-				if (len < 10)
-					break;
-				if (depth >= 0) { // the composite being read waits on the stack
-					uint32_t(*fr)[kGlyfTableLanes] = stack[depth];
-					fr[0][lane] = p, fr[1][lane] = end;
-					fr[2][lane] = __float_as_uint(T.a), fr[3][lane] = __float_as_uint(T.b), fr[4][lane] = __float_as_uint(T.c);
-					fr[5][lane] = __float_as_uint(T.d), fr[6][lane] = __float_as_uint(T.e), fr[7][lane] = __float_as_uint(T.f);
-				}
-				depth = d, p = pa + 10, end = pb, T = PT;
-			}
-			if (depth < 0)
-				break; // the glyph id itself was simple or empty
-			continue;
-		}
-		// the loop of GlyfWalker::walk over the component records of [p, end); p <= end throughout
-		bool more = end - p >= 4;
-		if (more) {
-			const uint32_t fl = be16(F.glyf + p), child = be16(F.glyf + p + 2);
-			p += 4;
-			if (++records > VGSDF_GLYF_MAX_COMPONENTS) {
-				if (!EMIT)
-					flags[GLYF_FLAG_BUDGET] = 1;
-				break;
-			}
-			Affine k = identity();
-			if (fl & 0x0002u) { // ARGS_ARE_XY_VALUES (anchor-point arguments are not consumed)
-				if (fl & 0x0001u) {
-					if ((more = end - p >= 4)) {
-						k.e = (float)(int16_t)be16(F.glyf + p);
-						k.f = (float)(int16_t)be16(F.glyf + p + 2);
-						p += 4;
-					}
-				} else if ((more = end - p >= 2)) {
-					k.e = (float)(int8_t)F.glyf[p];
-					k.f = (float)(int8_t)F.glyf[p + 1];
-					p += 2;
-				}
-			}
-			if (more) {
-				if (fl & 0x0080u) {
-					if ((more = end - p >= 8)) {
-						k.a = f2dot14(F.glyf + p), k.b = f2dot14(F.glyf + p + 2), k.c = f2dot14(F.glyf + p + 4), k.d = f2dot14(F.glyf + p + 6);
-						p += 8;
-					}
-				} else if (fl & 0x0040u) {
-					if ((more = end - p >= 4)) {
-						k.a = f2dot14(F.glyf + p), k.d = f2dot14(F.glyf + p + 2);
-						p += 4;
-					}
-				} else if (fl & 0x0008u) {
-					if ((more = end - p >= 2)) {
-						k.a = k.d = f2dot14(F.glyf + p);
-						p += 2;
-					}
-				}
-			}
-			if (more) {
-				if (!(fl & 0x0020u)) // no MORE_COMPONENTS: the loop ends behind this child
-					p = end;
-				if (glyph_range(F, child, pa, pb)) {
-					pending = true;
-					pgid = child;
-					PT = then(T, k);
-				}
-				continue;
-			}
-		}
-		// the records are through (or one was truncated): walk returns true, its caller goes on
-		depth--;
-		if (depth < 0)
-			break;
-		const uint32_t(*fr)[kGlyfTableLanes] = stack[depth];
-		p = fr[0][lane], end = fr[1][lane];
-		T.a = __uint_as_float(fr[2][lane]), T.b = __uint_as_float(fr[3][lane]), T.c = __uint_as_float(fr[4][lane]);
-		T.d = __uint_as_float(fr[5][lane]), T.e = __uint_as_float(fr[6][lane]), T.f = __uint_as_float(fr[7][lane]);
+// The same walk over all faces of a batch in one launch (vgsdf_fonts_create_tables).  A workgroup belongs to one face: the LAST
+// record f with first_block[f] <= blockIdx.x, found by a bisection every lane runs alike (the records are read through the
+// scalar cache).  A face that owns no workgroup — no glyph ids, or not taking part in this pass — has the first_block of the
+// face behind it and is passed over by that rule wherever it stands.  Every read stays inside the face's own loca_entries and
+// glyf_len; counts and byte_at are the batch's arrays at the face's glyph_base (byte_at: + f, one entry more per face), flags the
+// face's own GLYF_FLAG_WORDS words; leaves, bytes and leaf_off lie in the face's own store.
+template <bool EMIT>
+__global__ __launch_bounds__(kGlyfTableLanes) void glyf_tables_batch_pass(const GlyfFaceRecord *__restrict__ faces, uint32_t n_faces,
+                                                                           uint32_t *counts, const uint32_t *byte_at, uint32_t *flags)
+{
+	__shared__ uint32_t stack[kGlyfTableLevels][kGlyfTableFrameWords][kGlyfTableLanes];
+	uint32_t lo = 0, hi = n_faces; // faces[lo].first_block <= blockIdx.x < faces[hi].first_block (faces[0].first_block == 0)
+	while (hi - lo > 1) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (faces[mid].first_block <= blockIdx.x)
+			lo = mid;
+		else
+			hi = mid;
 	}
-
-	if (!EMIT) {
-		if (live)
-			((uint4 *)counts)[gid] = make_uint4(own_len, n_leaves, slots, own_cap);
+	const GlyfFaceRecord &R = faces[lo];
+	const uint32_t gid = (blockIdx.x - R.first_block) * kGlyfTableLanes + threadIdx.x;
+	if (!R.takes_part) // (never: the host lays the grid over the faces that take part)
 		return;
-	}
-	// the simple entries' bytes, the whole wave over one entry after the other: endPtsOfContours, then what lies behind the
-	// instructions, zero-padded to the next multiple of 4.  The source has any alignment: bytes in, words out
-	uint32_t dst = 0, dst_end = 0;
-	if (own_len)
-		dst = byte_at[gid], dst_end = byte_at[gid + 1];
-	for (unsigned long long m = __ballot(own_len != 0); m; m &= m - 1) {
-		const int j = __ffsll(m) - 1;
-		const uint32_t body = __shfl(own_body, j), ends = __shfl(own_ends, j), cur = __shfl(own_cur, j), len = __shfl(own_len, j);
-		const uint32_t to = __shfl(dst, j), to_end = __shfl(dst_end, j);
-		const uint8_t *src = F.glyf + body;
-		for (uint32_t w = lane; w < (len + 3) / 4; w += kGlyfTableLanes) {
-			uint32_t word = 0;
-			for (uint32_t i = 0; i < 4; i++) {
-				const uint32_t at = 4 * w + i;
-				if (at < len)
-					word |= (uint32_t)(at < ends ? src[at] : src[cur + (at - ends)]) << (8 * i);
-			}
-			if (4 * w + 4 <= to_end - to)
-				*(uint32_t *)(bytes + to + 4 * (size_t)w) = word;
-			else
-				flags[GLYF_FLAG_EMIT] = 1;
-		}
-	}
+	GlyfTablesRef F;
+	F.loca = (const uint8_t *)(uintptr_t)R.loca, F.glyf = (const uint8_t *)(uintptr_t)R.glyf;
+	F.glyf_len = R.glyf_len, F.loca_entries = R.loca_entries, F.loca_long = R.loca_long, F.n_glyph_ids = R.n_glyph_ids;
+	uint8_t *store = (uint8_t *)(uintptr_t)R.store;
+	uint32_t *const leaves = (uint32_t *)store;
+	uint8_t *const bytes = store + R.bytes_at;
+	const uint32_t *const leaf_off = (const uint32_t *)(store + 16 * (size_t)R.leaf_off_at16);
+	const uint32_t lane = threadIdx.x;
+	counts += (size_t)kGlyfTableCounts * R.glyph_base, byte_at += R.glyph_base + lo, flags += (size_t)GLYF_FLAG_WORDS * lo;
+#include "glyf_table_walk.inc"
 }
 
 } // namespace
@@ -271,6 +149,22 @@ int vgsdf_glyf_tables_emit(const vgsdf::GlyfTablesRef *face, const uint32_t *lea
 	const uint32_t groups = (face->n_glyph_ids + vgsdf::kGlyfTableLanes - 1) / vgsdf::kGlyfTableLanes;
 	hipLaunchKernelGGL(vgsdf::glyf_tables_pass<true>, dim3(groups), dim3(vgsdf::kGlyfTableLanes), 0, stream, *face, (uint32_t *)nullptr,
 	                   leaf_off, byte_at, (uint32_t *)leaves, bytes, flags);
+	return (int)hipGetLastError();
+}
+
+int vgsdf_glyf_tables_batch_count(const vgsdf::GlyfFaceRecord *faces, uint32_t n_faces, uint32_t n_blocks, uint32_t *counts, uint32_t *flags,
+                                  hipStream_t stream)
+{
+	hipLaunchKernelGGL(vgsdf::glyf_tables_batch_pass<false>, dim3(n_blocks), dim3(vgsdf::kGlyfTableLanes), 0, stream, faces, n_faces, counts,
+	                   (const uint32_t *)nullptr, flags);
+	return (int)hipGetLastError();
+}
+
+int vgsdf_glyf_tables_batch_emit(const vgsdf::GlyfFaceRecord *faces, uint32_t n_faces, uint32_t n_blocks, const uint32_t *byte_at,
+                                 uint32_t *flags, hipStream_t stream)
+{
+	hipLaunchKernelGGL(vgsdf::glyf_tables_batch_pass<true>, dim3(n_blocks), dim3(vgsdf::kGlyfTableLanes), 0, stream, faces, n_faces,
+	                   (uint32_t *)nullptr, byte_at, flags);
 	return (int)hipGetLastError();
 }
 

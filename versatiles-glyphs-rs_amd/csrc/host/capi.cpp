@@ -185,6 +185,13 @@ int vg_manager_glyf_table_stats(const vg_manager *m, vg_glyf_table_stats *out)
 	*out = vg_glyf_table_stats{t.glyf_tables_built, t.glyf_table_bytes, t.glyf_table_fallbacks};
 	return 0;
 }
+void vg_manager_set_glyf_tables_batched(vg_manager *m, int on) { m->m.set_glyf_tables_batched(on != 0); }
+int vg_manager_glyf_table_batch_stats(const vg_manager *m, vg_glyf_table_batch_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_glyf_table_batch_stats{t.glyf_table_batch_calls, t.glyf_table_batch_faces};
+	return 0;
+}
 int vg_manager_family_table_stats(const vg_manager *m, vg_family_table_stats *out)
 {
 	const vg::RenderTimings &t = m->m.last_timings();

@@ -164,6 +164,8 @@ struct RenderTimings {
 	// glyf-kind fonts the device walked from loca and glyf (set_glyf_tables_on_device; counted among resident_fonts_uploaded too),
 	// their bytes, and faces whose build the device refused: their fonts were made from the host's table instead
 	uint64_t glyf_tables_built = 0, glyf_table_bytes = 0, glyf_table_fallbacks = 0;
+	// ... and, with set_glyf_tables_batched, the calls that built them (one per font id whose faces needed building) and the faces sent
+	uint64_t glyf_table_batch_calls = 0, glyf_table_batch_faces = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -192,10 +194,11 @@ struct RenderTimings {
 		charstring_fallbacks += counts.charstring_fallbacks;
 		family_tables_built += counts.family_tables_built, family_table_fallbacks += counts.family_table_fallbacks;
 		glyf_tables_built += counts.glyf_tables_built, glyf_table_bytes += counts.glyf_table_bytes, glyf_table_fallbacks += counts.glyf_table_fallbacks;
+		glyf_table_batch_calls += counts.glyf_table_batch_calls, glyf_table_batch_faces += counts.glyf_table_batch_faces;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 30 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 32 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -299,6 +302,8 @@ public:
 	// and Face::resident_table() is not built for the face; a face whose build the device refuses gets its font from the host's
 	// table (remembered per face and device).  Same leaves, same output.
 	void set_glyf_tables_on_device(bool on) { glyf_tables_on_device_ = on; }
+	// with set_glyf_tables_on_device: the glyf fonts of a font id's files built in one call (Renderer::fonts_from_tables)
+	void set_glyf_tables_batched(bool on) { glyf_tables_batched_ = on; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
 	// returns the bytes put on the devices
 	uint64_t preload_resident_fonts(const Renderer &renderer) const;
@@ -546,6 +551,10 @@ private:
 	int charstrings_on_device_ = 0;
 	bool family_tables_on_device_ = false;
 	bool glyf_tables_on_device_ = false;
+	bool glyf_tables_batched_ = false;
+	// glyf_tables_batched_: the glyf fonts of `font`'s files that the device has yet to build, in one call; the glyf_store of each
+	// file behind it finds its font (or goes the way of a face that was refused or did not fit); counts into `counts`
+	void glyf_stores_batched(const Renderer &renderer, int lane, const FontWrapper &font, RenderTimings &counts) const;
 	// a face's glyf-kind font on the renderer's device, by either path; counts into `counts`
 	const vgsdf_font *glyf_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
 	mutable RenderTimings preload_counts_;

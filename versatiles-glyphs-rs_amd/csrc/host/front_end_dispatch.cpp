@@ -275,6 +275,8 @@ bool FontManager::fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, co
 		auto it = fonts().find(*last);
 		if (it == fonts().end())
 			return false;
+		if (!commands)
+			glyf_stores_batched(renderer, lane, it->second, timings_);
 		for (const auto &file : it->second.files()) {
 			if (m.fonts.size() >= 0xFFFF)
 				return false;
@@ -310,6 +312,26 @@ const vgsdf_font *FontManager::glyf_store(const Renderer &renderer, int lane, co
 	return f;
 }
 
+void FontManager::glyf_stores_batched(const Renderer &renderer, int lane, const FontWrapper &font, RenderTimings &counts) const
+{
+	if (!glyf_tables_on_device_ || !glyf_tables_batched_)
+		return;
+	std::vector<Renderer::TablesJob> faces;
+	for (const auto &file : font.files())
+		if (file->face().has_glyf_outlines())
+			faces.push_back(Renderer::TablesJob{file->face().resident_serial(), file->face().font_tables()});
+	std::vector<Renderer::TablesOutcome> outcomes;
+	renderer.fonts_from_tables(lane, faces, outcomes, &counts.glyf_table_batch_calls, &counts.glyf_table_batch_faces);
+	for (const Renderer::TablesOutcome &o : outcomes) { // (as glyf_store counts what font_from_tables says)
+		if (o.refused)
+			counts.glyf_table_fallbacks++;
+		if (o.built) {
+			counts.glyf_tables_built++, counts.glyf_table_bytes += o.uploaded;
+			count_upload(o.uploaded, counts.resident_fonts_uploaded, counts.resident_font_bytes);
+		}
+	}
+}
+
 const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const
 {
 	uint64_t uploaded = 0;
@@ -343,6 +365,8 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 	if (!ft && !on_device)
 		return nullptr;
 	std::vector<const vgsdf_font *> stores;
+	if (!commands)
+		glyf_stores_batched(renderer, lane, font, counts);
 	for (const auto &file : font.files()) {
 		const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), counts)
 		                               : (file->face().has_glyf_outlines() ? glyf_store(renderer, lane, file->face(), counts) : nullptr);
@@ -488,7 +512,11 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 	uint64_t uploaded = 0;
 	preload_counts_ = RenderTimings{};
 	for (size_t r = 0; r < renderer.n_devices(); r++)
-		for (const auto &kv : fonts())
+		for (const auto &kv : fonts()) {
+			RenderTimings batch;
+			glyf_stores_batched(renderer.device_lane(r), 0, kv.second, batch);
+			uploaded += batch.resident_font_bytes;
+			preload_counts_.add_uploads(batch);
 			for (const auto &file : kv.second.files())
 				if (file->face().has_glyf_outlines()) {
 					RenderTimings counts;
@@ -497,6 +525,7 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 					if (glyf_tables_on_device_) // (with the switch off these uploads go into the returned total only, as they always have)
 						preload_counts_.add_uploads(counts);
 				}
+		}
 	// ... and the command stores the manager's mode would use: with 2 every face's, with 1 those of the fonts whose groups cannot
 	// take a glyf form (a file without `glyf` outlines, a font refused before)
 	if (resident_commands_)

@@ -406,6 +406,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->charstrings_on_device_ = charstrings_on_device_;
 		c->family_tables_on_device_ = family_tables_on_device_;
 		c->glyf_tables_on_device_ = glyf_tables_on_device_;
+		c->glyf_tables_batched_ = glyf_tables_batched_;
 		c->resident_families_ = resident_families_;
 		c->batch_blocks_ = batch_blocks_;
 		c->batch_blocks_set_ = batch_blocks_set_;

@@ -521,6 +521,80 @@ const vgsdf_font *Renderer::font_from_tables(int lane, uint64_t serial, const Fo
 	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
+void Renderer::fonts_from_tables(int lane, const std::vector<TablesJob> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls,
+                                 uint64_t *n_sent) const
+{
+	outcomes.assign(faces.size(), TablesOutcome{});
+	if (mode_ != Mode::Hip)
+		return;
+	// what one call takes (vgsdf.h): 65536 faces, 2^22 glyph ids
+	constexpr size_t kMaxFaces = 65536;
+	constexpr uint64_t kMaxGlyphIds = 1ull << 22;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	std::vector<size_t> sent;
+	std::vector<vgsdf_font_tables_desc> descs;
+	std::vector<vgsdf_font *> made;
+	std::vector<int> status;
+	std::vector<uint64_t> needed;
+	auto flush = [&] {
+		if (sent.empty())
+			return;
+		made.assign(sent.size(), nullptr), status.assign(sent.size(), 0), needed.assign(sent.size(), 0);
+		vgsdf_ctx *c = lane_ctx(lane & 1);
+		int rc;
+		{
+			std::lock_guard<std::mutex> lock(mu_);
+			rc = vgsdf_fonts_create_tables_within(c, descs.data(), (uint32_t)descs.size(), rf.room(device_), made.data(), status.data(), needed.data());
+		}
+		*calls += 1, *n_sent += sent.size();
+		for (size_t i = 0; i < sent.size(); i++) {
+			TablesOutcome &o = outcomes[sent[i]];
+			const auto key = std::make_pair(device_, faces[sent[i]].serial);
+			if (rc != VGSDF_OK || status[i] != VGSDF_OK) { // (a refusal or a device error: the host's way)
+				rf.refused_glyf_tables.insert(key);
+				o.refused = true;
+				continue;
+			}
+			if (made[i] && needed[i] > rf.room(device_)) {
+				std::lock_guard<std::mutex> lock(mu_);
+				(void)vgsdf_font_free(c, made[i]);
+				made[i] = nullptr;
+			}
+			if (!made[i]) { // over the budget as it stands
+				rf.unfit_glyf_tables[key] = needed[i];
+				o.over_budget = true;
+				continue;
+			}
+			rf.unfit_glyf_tables.erase(key);
+			o.built = true;
+			(void)rf.keep(rf.fonts, key, made[i], vgsdf_font_device_bytes(made[i]), &o.uploaded);
+		}
+		sent.clear(), descs.clear();
+	};
+	uint64_t glyph_ids = 0;
+	std::set<uint64_t> seen;
+	for (size_t i = 0; i < faces.size(); i++) {
+		const FontTables &t = faces[i].tables;
+		const auto key = std::make_pair(device_, faces[i].serial);
+		if (!t.ok || rf.find(rf.fonts, key) || rf.refused_glyf_tables.count(key))
+			continue;
+		if (auto it = rf.unfit_glyf_tables.find(key); it != rf.unfit_glyf_tables.end() && it->second > rf.room(device_))
+			continue; // (font_from_tables says over_budget when it is asked)
+		if (!seen.insert(faces[i].serial).second)
+			continue; // (a face named twice: one font)
+		if (sent.size() == kMaxFaces || glyph_ids + t.num_glyphs > kMaxGlyphIds)
+			flush(), glyph_ids = 0;
+		vgsdf_font_tables_desc d;
+		d.num_glyphs = t.num_glyphs, d.loca_entries = t.loca_entries, d.loca_long = t.loca_long;
+		d.n_loca_bytes = t.n_loca_bytes, d.n_glyf_bytes = t.n_glyf_bytes;
+		d.loca = t.loca, d.glyf = t.glyf;
+		sent.push_back(i), descs.push_back(d);
+		glyph_ids += t.num_glyphs;
+	}
+	flush();
+}
+
 const vgsdf_font *Renderer::command_font(int lane, const CommandTable &t, uint64_t *uploaded_bytes) const
 {
 	if (mode_ != Mode::Hip || !t.ok)

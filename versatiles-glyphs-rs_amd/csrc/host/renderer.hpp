@@ -466,6 +466,23 @@ public:
 	// *built: this call put the font on the device
 	const vgsdf_font *font_from_tables(int lane, uint64_t serial, const FontTables &tables, uint64_t *uploaded_bytes, bool *refused,
 	                                   bool *over_budget, bool *built) const;
+	// font_from_tables for ALL faces of a font id in as few calls as their number and glyph ids allow (vgsdf_fonts_create_tables_within:
+	// one count launch, one read-back, one emit launch per call).  Under the registry's lock for the whole of it, so two lanes of a
+	// device never build a face twice.  A face is sent when its tables are ok, the registry has no font under (device, serial) and
+	// it is not remembered as refused or as past the budget's room; what becomes of it is in outcomes[i] as font_from_tables says it
+	// (uploaded: the font's device bytes), and the registry, the refused set and the sizes that did not fit are left as that
+	// function would leave them, so that a font_from_tables of any of the faces behind this call finds its font, or goes the way it
+	// went.  The call's own limit counts the stores' bytes and the registry their allocations (a quarter more): a font that the
+	// registry's room does not take after all is freed again and remembered as one that did not fit.  *calls / *faces: the calls made, the faces sent
+	struct TablesJob {
+		uint64_t serial = 0;
+		FontTables tables;
+	};
+	struct TablesOutcome {
+		bool refused = false, over_budget = false, built = false;
+		uint64_t uploaded = 0;
+	};
+	void fonts_from_tables(int lane, const std::vector<TablesJob> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls, uint64_t *n_sent) const;
 	// the same for the command store of a face (vgsdf_font_create_commands): same registry (the tables' serials come from one
 	// sequence), same budget, no eviction.  nullptr: no command table, or over the budget — the caller goes on as without
 	const vgsdf_font *command_font(int lane, const CommandTable &table, uint64_t *uploaded_bytes = nullptr) const;

@@ -118,6 +118,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_family_create", "vgsdf_family_free", "vgsdf_family_device_bytes", "vgsdf_family_count", "vgsdf_outlines_submit_ranges",
     "vgsdf_outlines_task_extents", "vgsdf_family_create_tables", "vgsdf_family_read", "vgsdf_family_tables_kernel_ms",
     "vgsdf_font_create_tables", "vgsdf_font_create_tables_within", "vgsdf_font_read", "vgsdf_font_tables_kernel_ms",
+    "vgsdf_fonts_create_tables", "vgsdf_fonts_create_tables_within", "vgsdf_fonts_tables_kernel_ms",
 ]
 
 _lib = None
@@ -178,6 +179,10 @@ def load_library():
         L.vgsdf_font_read.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp]
         L.vgsdf_font_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_font_tables_kernel_ms.restype = None
+        L.vgsdf_fonts_create_tables.argtypes = [vp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.vgsdf_fonts_create_tables_within.argtypes = [vp, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vgsdf_fonts_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_fonts_tables_kernel_ms.restype = None
         L.vgsdf_font_free.argtypes = [vp, vp]
         L.vgsdf_font_device_bytes.argtypes = [vp]
         L.vgsdf_font_device_bytes.restype = C.c_uint64
@@ -658,6 +663,45 @@ class SdfContext:
         """(count, emit + copy) milliseconds of the kernels of this context's last font_create_tables"""
         ms = (C.c_float * 2)()
         load_library().vgsdf_font_tables_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
+
+    def fonts_create_tables(self, descs, max_store_bytes=None, **override):
+        """vgsdf_fonts_create_tables: the glyf-kind fonts of ALL `descs` (each as font_create_tables takes it; the keys n_loca_bytes /
+        n_glyf_bytes, when present, overrule the tables' lengths) built by one count and one emit launch -> a list, per face, of
+        (ResidentFont or None, status, needed): status VGSDF_OK with a font, VGSDF_OK without one when the store would pass what
+        the faces before it have left of max_store_bytes (vgsdf_fonts_create_tables_within; needed: its bytes, 0 without a limit),
+        VGSDF_E_ARG for a bad description, VGSDF_E_GLYF for a face the device refuses.  VgsdfError: the whole call failed.
+        override (for calls that lie): n_faces; null: the names among "faces", "out", "status" to pass as NULL"""
+        keep = []
+        arr = (_CFontTablesDesc * max(len(descs), 1))()
+        for i, desc in enumerate(descs):
+            loca, glyf = np.frombuffer(bytes(desc["loca"]), dtype=np.uint8), np.frombuffer(bytes(desc["glyf"]), dtype=np.uint8)
+            keep.append((loca, glyf))
+            arr[i] = _CFontTablesDesc(int(desc["num_glyphs"]), int(desc["loca_entries"]), int(desc["loca_long"]),
+                                      int(desc.get("n_loca_bytes", len(loca))), int(desc.get("n_glyf_bytes", len(glyf))),
+                                      loca.ctypes.data if len(loca) else None, glyf.ctypes.data if len(glyf) else None)
+        n = int(override.get("n_faces", len(descs)))
+        null = set(override.get("null", ()))
+        out = (C.c_void_p * max(len(descs), 1))()
+        status = (C.c_int * max(len(descs), 1))()
+        needed = (C.c_uint64 * max(len(descs), 1))()
+        args = [None if "faces" in null else arr, n]
+        tail = [None if "out" in null else out, None if "status" in null else status]
+        L = load_library()
+        try:
+            if max_store_bytes is not None:
+                self._check(L.vgsdf_fonts_create_tables_within(self._h, *args, int(max_store_bytes), *tail, needed))
+            else:
+                self._check(L.vgsdf_fonts_create_tables(self._h, *args, *tail))
+        except VgsdfError:
+            assert not any(out[i] for i in range(len(descs))), "a failed call left a font behind"
+            raise
+        return [(ResidentFont(self, C.c_void_p(out[i])) if out[i] else None, int(status[i]), int(needed[i])) for i in range(min(n, len(descs)))]
+
+    def fonts_tables_kernel_ms(self):
+        """(count, emit + copy) milliseconds of the two launches of this context's last fonts_create_tables"""
+        ms = (C.c_float * 2)()
+        load_library().vgsdf_fonts_tables_kernel_ms(self._h, ms)
         return float(ms[0]), float(ms[1])
 
     def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None):

@@ -62,6 +62,10 @@ class GlyfTableStats(C.Structure):  # vg_glyf_table_stats
     _fields_ = [(k, C.c_uint64) for k in ("built_on_device", "bytes", "fallbacks")]
 
 
+class GlyfTableBatchStats(C.Structure):  # vg_glyf_table_batch_stats
+    _fields_ = [("calls", C.c_uint64), ("faces", C.c_uint64)]
+
+
 class CharstringStats(C.Structure):  # vg_charstring_stats
     _fields_ = [(k, C.c_uint64) for k in ("fonts_decoded", "font_bytes", "fallbacks")]
 
@@ -89,6 +93,7 @@ VGFONT_SYMBOLS = [
     "vg_renderer_reset_counters", "vg_manager_reduced_counters", "vg_manager_set_in_place_pbf", "vg_manager_set_glyf_on_device", "vg_manager_set_lane_form", "vg_manager_plan_lanes",
     "vg_manager_family_tables_desc", "vg_manager_font_tables_desc", "vg_manager_set_family_tables_on_device", "vg_manager_family_table_stats",
     "vg_manager_set_glyf_tables_on_device", "vg_manager_glyf_table_stats",
+    "vg_manager_set_glyf_tables_batched", "vg_manager_glyf_table_batch_stats",
 ]
 
 _bound = False
@@ -138,6 +143,9 @@ def _L():
         L.vg_manager_set_glyf_tables_on_device.argtypes = [vp, C.c_int]
         L.vg_manager_set_glyf_tables_on_device.restype = None
         L.vg_manager_glyf_table_stats.argtypes = [vp, C.POINTER(GlyfTableStats)]
+        L.vg_manager_set_glyf_tables_batched.argtypes = [vp, C.c_int]
+        L.vg_manager_set_glyf_tables_batched.restype = None
+        L.vg_manager_glyf_table_batch_stats.argtypes = [vp, C.POINTER(GlyfTableBatchStats)]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -424,6 +432,17 @@ class FontManager:
         s = GlyfTableStats()
         _L().vg_manager_glyf_table_stats(self._h, C.byref(s))
         return {k: int(getattr(s, k)) for k, _ in GlyfTableStats._fields_}
+
+    def set_glyf_tables_batched(self, on: bool):
+        """with set_glyf_tables_on_device: the glyf fonts of all files of a font id are built in ONE call
+        (vgsdf_fonts_create_tables) instead of one per file; same fonts, same output (default off)"""
+        _L().vg_manager_set_glyf_tables_batched(self._h, int(bool(on)))
+
+    def glyf_table_batch_stats(self) -> dict:
+        """of the last render: {calls, faces} of the batched builds (vg_glyf_table_batch_stats)"""
+        s = GlyfTableBatchStats()
+        _L().vg_manager_glyf_table_batch_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in GlyfTableBatchStats._fields_}
 
     def family_table_stats(self) -> dict:
         """of the last render: {built_on_device, fallbacks} (vg_family_table_stats)"""
