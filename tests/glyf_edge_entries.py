@@ -13,7 +13,7 @@ import numpy as np
 
 from test_glyf_parts_host import _decode_part
 
-# what the decoder's constants are (csrc/outline_kernels.hip); tests compare them with the library's own (vgsdf_glyf_limits)
+# what the decoder's constants are (csrc/input_form_kernels.hip); tests compare them with the library's own (vgsdf_glyf_limits)
 MAX_POINTS, MAX_BYTES, EXPAND_FONT_CACHE = 6144, 30 * 1024, 128
 
 ACCEPTED, MALFORMED, DEVICE_LIMIT = "accepted", "malformed", "device_limit"

@@ -1,5 +1,5 @@
 """GPU: the device front-end (outline commands -> flattened rings -> scaled segments + rects,
-csrc/outline_kernels.hip) against the oracle, and the whole pipeline through it against the
+csrc/outline_kernels.hip, csrc/outline_plan_kernels.hip) against the oracle, and the whole pipeline through it against the
 golden PBF hashes.  Commands are what ttf-parser's OutlineBuilder receives (taken from the
 oracle's TTF reader here; the product's own reader is pinned to it in test_host_vs_oracle)."""
 import hashlib

@@ -1,4 +1,4 @@
-"""GPU: the device front-end (csrc/outline_kernels.hip) across its size-dependent branches, at the C ABI.
+"""GPU: the device front-end (csrc/outline_kernels.hip, csrc/outline_plan_kernels.hip) across its size-dependent branches, at the C ABI.
 
 A. Plan regimes.  Noto Sans Regular, recorded with the oracle's reader and tiled cyclically to n glyphs, through every
    submission form.  n crosses the plan's instances (outline_plan<4, true> up to 4096 glyphs with in-place PBF,

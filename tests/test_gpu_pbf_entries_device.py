@@ -1,4 +1,4 @@
-"""pbf_entries (csrc/outline_kernels.hip): the bytes of every glyph's PBF entry around its bitmap, written on the device behind
+"""pbf_entries (csrc/outline_plan_kernels.hip): the bytes of every glyph's PBF entry around its bitmap, written on the device behind
 the plan of a ranges submission with pbf_pre.  Command fonts of axis-aligned rectangles at scale 1 make every field of an entry
 the test's to choose — a rectangle (X, Y, W, H) has width W, height H, left X, top Y + H - 24 and a bitmap of (W + 6)(H + 6)
 bytes — and the family gives every glyph its id (the code point) and advance.  Per task the arena's bytes behind the reserved

@@ -1,4 +1,4 @@
-"""The upload kernel of resident submissions (resident_expand, csrc/outline_kernels.hip) at its edges: 256 glyphs per workgroup,
+"""The upload kernel of resident submissions (resident_expand, csrc/input_form_kernels.hip) at its edges: 256 glyphs per workgroup,
 the bisection over offsets that glyphs without leaves share, glyphs of more leaves than a workgroup has lanes, the 128 font
 references a workgroup keeps in LDS and the load from the block behind them, both block layouts (with and without the in-place
 PBF arrays) and their 16-byte tails.

@@ -1,4 +1,4 @@
-"""The upload kernel of submissions against command fonts (resident_gather, csrc/outline_kernels.hip) at its edges: 256 glyphs
+"""The upload kernel of submissions against command fonts (resident_gather, csrc/input_form_kernels.hip) at its edges: 256 glyphs
 per workgroup, the bisection over offsets that glyphs without commands share, a glyph of more commands than a workgroup deals
 in a round, records that are 4-byte aligned only, context bytes at every pair of byte offsets in store and batch, the 128 font
 references a workgroup keeps in LDS, both block layouts, and the context-pass route of batches with an odd scale.

@@ -1,5 +1,5 @@
 """GPU: the raster kernel (sdf_tiles_span, csrc/sdf_span_kernel.inc) and the two planners that feed it (build_descs_and_tiles
-in work_list.cpp on the host, outline_plan in outline_kernels.hip on the device, both on the policy of csrc/work_plan.h) at the
+in work_list.cpp on the host, outline_plan in outline_plan_kernels.hip on the device, both on the policy of csrc/work_plan.h) at the
 regimes set by a glyph's width and segment count, against the oracle (BRUTE and PRECISE) under both product variants (0: spans,
 1: brute force).
 

@@ -4,8 +4,10 @@ in B?  Comments and the function number inside basic-block labels are ignored (t
 everything else — instructions, operands, directives, the kernel descriptors' values — must be equal.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -S --cuda-device-only \\
-          -Rpass-analysis=kernel-resource-usage csrc/outline_kernels.hip -o new.s 2> new_usage.txt      (and the parent's)
+          -Rpass-analysis=kernel-resource-usage csrc/input_form_kernels.hip -o new.s 2> new_usage.txt      (and the parent's)
     python tools/isa_ab.py parent.s new.s
+
+For kernels that moved between files, concatenate the .s files of either side (as for profiles/kernel_files_split_isa_ab.txt).
 """
 import hashlib
 import re

@@ -6,6 +6,9 @@
 //   resident_fonts.cpp      fonts uploaded once and named by glyph id (resident_fonts.h: what the front-end reads of them)
 //   resident_families.cpp   the families over them, named by code-point range (resident_build.h: what the two share)
 //   run_counters.cpp        run counters and their RCCL reduction
+// The kernels they launch are translation units of their own, each with a header of its name: sdf_kernels (raster),
+// input_form_kernels, outline_kernels, outline_plan_kernels (the device front-end: input forms, flattening, plan),
+// charstring_kernels, family_table_kernels, glyf_table_kernels (the constructors of resident stores).
 #pragma once
 #include <hip/hip_runtime.h>
 

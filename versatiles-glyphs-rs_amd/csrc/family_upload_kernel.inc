@@ -1,5 +1,5 @@
 // family_upload_kernel.inc — the upload kernel of a submission that names code-point RANGES of resident families
-// (vgsdf_outlines_ranges), stamped once per kind of font by outline_kernels.hip:
+// (vgsdf_outlines_ranges), stamped once per kind of font by input_form_kernels.hip:
 //   FAMILY_GLYF 1  family_expand   fonts from vgsdf_font_create: takes resident_expand's place
 //   FAMILY_GLYF 0  family_gather   fonts from vgsdf_font_create_commands: takes resident_gather's place
 // The block (upload_layout.h, RangesBlockLayout) holds a record per task, per family and per font and NOTHING per glyph: the

@@ -1,4 +1,4 @@
-// glyf_decode_kernel.inc — the decoder of outline_kernels.hip, stamped twice (as sdf_span_kernel.inc is): once as it ever
+// glyf_decode_kernel.inc — the decoder of input_form_kernels.hip, stamped twice (as sdf_span_kernel.inc is): once as it ever
 // was (GLYF_DECODE_RESIDENT 0: the parts' bytes lie in the batch's own store) and once for parts that the upload kernel of
 // vgsdf_outlines_resident expanded from resident fonts (1: `fonts` lists the fonts' stores, and the font's index lies in the
 // upper half of the part's `plain`).  Everything else is the same text, so the first instance compiles to what it did.

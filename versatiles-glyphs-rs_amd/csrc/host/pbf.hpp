@@ -43,7 +43,7 @@ struct PbfGlyphRef {
 // ---- in-place assembly (include/vgsdf.h, vgsdf_outlines_packed::pbf_pre / pbf_fix) ------------------------------
 // The raster stores every bitmap where the finished block file has it, inside an arena that holds the blocks of a
 // submission one after the other; the ~20 bytes around each bitmap and the block headers are written here once the
-// glyphs' rects are known.  The arithmetic below is the device's (csrc/outline_kernels.hip, pbf_place), which has
+// glyphs' rects are known.  The arithmetic below is the device's (csrc/outline_plan_kernels.hip, pbf_place), which has
 // already placed the bitmaps.
 inline uint32_t pbf_varint_len(uint64_t v)
 {

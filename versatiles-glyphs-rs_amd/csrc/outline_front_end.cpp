@@ -11,7 +11,9 @@
 #include <vector>
 
 #include "device_internal.h"
+#include "input_form_kernels.h"
 #include "outline_kernels.h"
+#include "outline_plan_kernels.h"
 #include "resident_fonts.h"
 #include "upload_layout.h"
 #include "work_plan.h"
@@ -338,7 +340,7 @@ struct FeUpload {
 	size_t arrays_bytes = 0;         // scale | shift_x | cmd_off [| dat_off]
 	size_t meta_bytes = 0;           // what the device keeps in fe.meta
 	const uint8_t *block = nullptr; // the caller's arrays are ONE page-locked block in their form's layout: one copy
-	const void *mapped = nullptr; // ... that the device can address: uploaded by a kernel (outline_kernels.hip, copy_in)
+	const void *mapped = nullptr; // ... that the device can address: uploaded by a kernel (input_form_kernels.hip, copy_in)
 	// set by fe_upload: device views of what the form brings besides the per-glyph arrays (those: fe_dev)
 	const uint8_t *d_kinds = nullptr, *d_parts = nullptr, *d_bytes = nullptr;
 	const float *d_coords = nullptr;

@@ -1,4 +1,4 @@
-// outline_kernels.hip — device front-end: outline commands ->
+// outline_kernels.hip — the flattening pipeline of the device front-end: outline commands ->
 // flattened, closed rings -> scaled + shifted segments and the raster rect of every glyph,
 // all on the GPU, bit-exact with the host/reference path:
 //   RingBuilder          /root/reference/src/render/ring_builder.rs:26-117
@@ -11,7 +11,7 @@
 // units); everything after that is f64 arithmetic replayed here operation by operation
 // (-ffp-contract=off, IEEE divide).
 //
-// Pipeline: five launches, no intermediate point arrays, one read-back (the rects) for the host:
+// Pipeline: five launches, no intermediate point arrays, one read-back (the rects) for the host; four of them are here:
 //   context  wave per glyph: is the ring non-empty in front of every command; commands that arrive in the compact
 //            upload form (kind byte + the coordinates the kind carries) are expanded into 28-byte records here
 //   count    wave per 64 commands: first flattening pass — how many points every command appends, their
@@ -19,22 +19,21 @@
 //   rings    wave per glyph: point offsets inside the glyph, ring acceptance / closing rules, segment count,
 //            bbox -> rect
 //   plan     one workgroup: segment / output offsets of all glyphs (descriptors), the raster's work list
-//            (spans, heaviest first), totals
+//            (spans, heaviest first), totals — outline_plan_kernels.hip
 //   emit     wave per 64 commands: second flattening pass; every point goes straight into the scaled + shifted
 //            segment records as the start of one segment and the end of its predecessor
 // The two flattening passes deal the points of 64 consecutive commands out to the 64 lanes of a wave in items
 // of up to 8 points ("Leaf-parallel flattening" below); one command per thread left 63 lanes waiting for the
 // lane with a 32-point curve (36 + 45 us per Noto Sans Regular font; now 7 + 21), and a wave-per-glyph form
 // measured 2.5x slower still.
+// How the commands come to be on the device in the first place (the glyf decoder, the uploads of resident and ranges
+// submissions) is input_form_kernels.hip's.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <type_traits>
 #include <stdint.h>
 
 #include "outline_kernels.h"
 #include "sdf_kernels.h"
-#include "upload_layout.h"
-#include "work_plan.h"
+#include "wave_ops.h"
 
 namespace vgsdf {
 
@@ -204,20 +203,6 @@ __device__ __forceinline__ bool ring_open_before(uint32_t kind, uint32_t lane, b
 		carry = (opens >> top) & 1ull;
 	}
 	return open;
-}
-
-// exclusive prefix sum over the wave (DPP row shifts + row broadcasts); total = sum over all lanes
-__device__ __forceinline__ uint32_t wave_exclusive_sum(uint32_t v, uint32_t &total)
-{
-	uint32_t incl = v;
-	incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false); // row_shr:1
-	incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false); // row_shr:2
-	incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false); // row_shr:4
-	incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false); // row_shr:8
-	incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xA, 0xF, false); // row_bcast:15 -> rows 1, 3
-	incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xC, 0xF, false); // row_bcast:31 -> rows 2, 3
-	total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-	return incl - v;
 }
 
 // Rust `as i32` on f64: truncate, saturate, NaN -> 0
@@ -875,283 +860,6 @@ __global__ __launch_bounds__(64) void outline_rings(const OutlineCmd *__restrict
 }
 
 // ---------------------------------------------------------------------------------------
-// plan: ONE workgroup.  From the rects: the glyph descriptors (segment and output offsets: exclusive sums),
-// the raster's work list and the totals the host reads back together with the rects.  The list follows the
-// policy the host's planner of resident batches follows too (work_plan.h): class (main kernel / brute
-// force), span length T per glyph, heaviest workgroup first (counting sort over 512 logarithmic weight
-// buckets; the order inside a bucket is whatever the atomics give: it only shapes the schedule).
-// ---------------------------------------------------------------------------------------
-constexpr int kPlanThreads = 1024;
-constexpr int kPlanBuckets = 512;
-
-// block-wide exclusive sum of one value per thread (1024 threads = 16 waves); returns the exclusive prefix, sets total
-__device__ __forceinline__ unsigned long long block_exclusive_sum(unsigned long long v, unsigned long long *s_wave /*[17]*/,
-                                                                  unsigned long long &total)
-{
-	const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	unsigned long long incl = v;
-	for (int d = 1; d < 64; d <<= 1) {
-		const unsigned long long o = __shfl_up(incl, d);
-		if ((int)lane >= d)
-			incl += o;
-	}
-	__syncthreads(); // s_wave free again
-	if (lane == 63)
-		s_wave[wv] = incl;
-	__syncthreads();
-	if (wv == 0) { // the 16 wave totals: one shuffle scan in the first wave
-		constexpr int kWaves = kPlanThreads / 64;
-		const unsigned long long t = lane < (uint32_t)kWaves ? s_wave[lane] : 0ull;
-		unsigned long long in = t;
-		for (int d = 1; d < kWaves; d <<= 1) {
-			const unsigned long long o = __shfl_up(in, d);
-			if ((int)lane >= d)
-				in += o;
-		}
-		if (lane < (uint32_t)kWaves)
-			s_wave[lane] = in - t;
-		if (lane == (uint32_t)kWaves - 1)
-			s_wave[kWaves] = in;
-	}
-	__syncthreads();
-	total = s_wave[kPlanThreads / 64];
-	return s_wave[wv] + incl - v;
-}
-
-// bytes of a protobuf varint
-__device__ __forceinline__ uint32_t varint_len(unsigned long long v)
-{
-	const uint32_t bits = 64u - (uint32_t)__builtin_clzll(v | 1ull); // 1 .. 64 significant bits, 7 per byte
-	return (bits + 6u) / 7u;
-}
-
-// In-place PBF assembly (vgsdf.h, vgsdf_outlines_packed::pbf_pre / pbf_fix): what glyph `r` occupies in the arena of
-// finished PBF blocks — `pre` reserved bytes in front of it (the block's file and fontstack header when it is the first
-// glyph of its block), then its `glyphs` entry of the fontstack message (src/protobuf/glyph.rs:10-41, fontstack.rs:9-25):
-//   0x1A varint(msg) | 0x08 varint(id) | [0x12 varint(w h) bitmap] | 0x18 width 0x20 height 0x28 left 0x30 top 0x38 advance
-// with width = w - 6, height = h - 6, left = x0 + 3, top = y0 + h - 27 (src/render/result.rs:66-76 after renderer.rs:146).
-// fix = (1 + varint_len(id)) | (1 + varint_len(advance)) << 4, from the host (it knows id and advance).
-// Returns the bytes taken, sets `bitmap_at` to the bitmap's offset in them.  The host writes the headers with the same
-// arithmetic (csrc/host/pbf.hpp, pbf_entry_layout) once the rects are back.
-__device__ __forceinline__ unsigned long long pbf_place(const OutlineRect &r, uint32_t pre, uint32_t fix, unsigned long long &bitmap_at)
-{
-	const uint32_t idlen = fix & 15u, advlen = fix >> 4;
-	unsigned long long msg = idlen + advlen;
-	const unsigned long long px = r.has_raster ? (unsigned long long)r.w * r.h : 0ull;
-	uint32_t bm_hdr = 0;
-	if (r.has_raster) {
-		bm_hdr = 1u + varint_len(px);
-		msg += bm_hdr + px;
-		const uint32_t left = (uint32_t)r.x0 + 3u, top = (uint32_t)r.y0 + r.h - 27u; // two's complement, as i32 arithmetic wraps
-		const uint32_t zl = (left << 1) ^ (uint32_t)((int32_t)left >> 31), zt = (top << 1) ^ (uint32_t)((int32_t)top >> 31);
-		msg += 4u + varint_len(r.w - 6u) + varint_len(r.h - 6u) + varint_len(zl) + varint_len(zt);
-	} else {
-		msg += 8u; // PbfGlyph::empty: width, height, left, top = 0 (glyph.rs:60-70), one byte each behind its tag
-	}
-	const uint32_t ent_hdr = 1u + varint_len(msg);
-	bitmap_at = (unsigned long long)pre + ent_hdr + idlen + bm_hdr;
-	return (unsigned long long)pre + ent_hdr + msg;
-}
-
-// KEEP: glyphs per thread whose rects (and classification) stay in registers for all three passes; PBF: in-place placement
-// is part of the unrolled passes (instances: <8, false> for packed bitmaps, <4, true> for in-place batches of <= 4096 glyphs;
-// eight inlined placements spill the 1024-thread workgroup to scratch: 21 -> 26 us)
-template <uint32_t KEEP, bool PBF>
-__global__ __launch_bounds__(kPlanThreads) void outline_plan(const OutlineRect *__restrict__ rects, uint32_t n_glyphs, int span_list,
-                                                             uint32_t delta_cap, uint32_t span_max, uint32_t span_budget,
-                                                             uint32_t tile_cap, GlyphDesc *__restrict__ descs,
-                                                             uint2 *__restrict__ tiles, PlanHeader *__restrict__ hdr,
-                                                             const uint32_t *__restrict__ error_flag, unsigned long long seg_cap,
-                                                             unsigned long long out_cap, uint32_t launch_spans,
-                                                             const uint32_t *__restrict__ pbf_pre, const uint8_t *__restrict__ pbf_fix,
-                                                             unsigned long long *__restrict__ pbf_at, uint32_t *__restrict__ next_flag)
-{
-	__shared__ unsigned long long s_wave[kPlanThreads / 64 + 1];
-	// the error word of the NEXT submission of this context (the two alternate): zeroed here, behind everything that could
-	// still raise the previous use of that word, instead of a memset launch in front of every submission
-	if (threadIdx.x == 0 && next_flag != nullptr)
-		next_flag[0] = 0;
-	__shared__ uint32_t s_hist[2][kPlanBuckets]; // spans per (class, bucket); then the bucket's write cursor
-	__shared__ unsigned long long s_carry[2];
-	const uint32_t tid = threadIdx.x;
-	for (uint32_t i = tid; i < 2 * kPlanBuckets; i += kPlanThreads)
-		(&s_hist[0][0])[i] = 0;
-	if (tid == 0)
-		s_carry[0] = s_carry[1] = 0;
-	__syncthreads();
-	// class (0 main / 1 brute), span length, span count and weight of a glyph (work_plan.h: the policy shared with the host)
-	auto classify = [&](const OutlineRect &r, uint32_t &cls, uint32_t &T, uint32_t &nspans, uint32_t &weight) {
-		const unsigned long long px = r.has_raster ? (unsigned long long)r.w * r.h : 0ull;
-		cls = 0, T = 1, nspans = 0, weight = 0;
-		if (px == 0 || px > 0xFFFFFFFFull - 256ull) // (a bitmap beyond 2^32 pixels is an error of the batch: no entries)
-			return;
-		const GlyphPlan gp = plan_glyph(px, r.w, r.n_segments, span_list != 0, delta_cap, span_max, span_budget);
-		cls = gp.cls, T = gp.T, nspans = gp.n_spans, weight = gp.weight;
-	};
-	// pass A: descriptors (exclusive sums of segments and output bytes), span histogram.  Every thread takes a
-	// contiguous run of glyphs: one block-wide scan of the runs' sums, then a running sum inside the run.
-	bool bad = false;
-	const uint32_t per = (n_glyphs + kPlanThreads - 1) / kPlanThreads;
-	const uint32_t g_lo = min(tid * per, n_glyphs), g_hi = min(g_lo + per, n_glyphs);
-	// a run of up to eight glyphs (batches of <= 8192 glyphs: every group the dispatcher forms) stays in registers with its classification, so
-	// the rects are read once and classified once for both passes
-	constexpr uint32_t kKeep = KEEP;
-	const bool kept = per <= kKeep && (PBF || pbf_fix == nullptr);
-	OutlineRect kr[kKeep];
-	uint32_t kcls[kKeep], kT[kKeep], kn[kKeep], kw[kKeep];
-#pragma unroll
-	for (uint32_t j = 0; j < kKeep; j++) {
-		kr[j].x0 = kr[j].y0 = 0;
-		kr[j].w = kr[j].h = kr[j].n_segments = kr[j].has_raster = 0;
-		kcls[j] = kT[j] = kn[j] = kw[j] = 0;
-		if (kept && g_lo + j < g_hi) {
-			kr[j] = rects[g_lo + j];
-			classify(kr[j], kcls[j], kT[j], kn[j], kw[j]);
-		}
-	}
-	{
-		unsigned long long my_s = 0, my_p = 0;
-		// output bytes of a glyph: its bitmap, or — in-place PBF assembly — everything it occupies in the arena
-		auto sum_one = [&](uint32_t g, const OutlineRect &r) {
-			if (r.has_raster) {
-				my_s += r.n_segments;
-				bad |= (unsigned long long)r.w * r.h > 0xFFFFFFFFull - 256ull;
-			}
-			if (pbf_fix != nullptr) {
-				unsigned long long at;
-				my_p += pbf_place(r, pbf_pre[g], pbf_fix[g], at);
-			} else if (r.has_raster) {
-				my_p += (unsigned long long)r.w * r.h;
-			}
-		};
-		if (kept) {
-#pragma unroll
-			for (uint32_t j = 0; j < kKeep; j++) {
-				if (kr[j].has_raster) { // (absent glyphs: zero rects)
-					my_s += kr[j].n_segments;
-					if (!(PBF && pbf_fix != nullptr))
-						my_p += (unsigned long long)kr[j].w * kr[j].h;
-					bad |= (unsigned long long)kr[j].w * kr[j].h > 0xFFFFFFFFull - 256ull;
-				}
-				if (PBF && pbf_fix != nullptr && g_lo + j < g_hi) {
-					unsigned long long at;
-					my_p += pbf_place(kr[j], pbf_pre[g_lo + j], pbf_fix[g_lo + j], at);
-				}
-			}
-		} else {
-			for (uint32_t g = g_lo; g < g_hi; g++)
-				sum_one(g, rects[g]);
-		}
-		unsigned long long tot_s, tot_p;
-		unsigned long long so = block_exclusive_sum(my_s, s_wave, tot_s);
-		unsigned long long po = block_exclusive_sum(my_p, s_wave, tot_p);
-		if (tid == 0) {
-			s_carry[0] = tot_s;
-			s_carry[1] = tot_p;
-		}
-		auto desc_one = [&](uint32_t g, const OutlineRect &r, uint32_t cls, uint32_t nspans, uint32_t weight, auto in_place) {
-			const unsigned long long px = r.has_raster ? (unsigned long long)r.w * r.h : 0ull;
-			const unsigned long long segs = r.has_raster ? r.n_segments : 0u;
-			GlyphDesc d;
-			d.seg_off = (uint32_t)so; // (the host rejects batches with more than 2^32 - 1 segments: header)
-			d.n_seg = (uint32_t)segs;
-			d.x0 = r.x0;
-			d.y0 = r.y0;
-			d.w = r.has_raster ? r.w : 0;
-			d.h = r.has_raster ? r.h : 0;
-			if (decltype(in_place)::value && pbf_fix != nullptr) {
-				unsigned long long at;
-				const unsigned long long took = pbf_place(r, pbf_pre[g], pbf_fix[g], at);
-				d.out_off = po + at; // the raster stores the bitmap where the finished file has it
-				pbf_at[g] = po + at; // (read back with the rects: the host writes the bytes around it)
-				po += took;
-			} else {
-				d.out_off = po;
-				po += px;
-			}
-			descs[g] = d;
-			so += segs;
-			if (nspans)
-				atomicAdd(&s_hist[cls][weight_bucket(weight)], nspans);
-		};
-		if (kept) {
-#pragma unroll
-			for (uint32_t j = 0; j < kKeep; j++)
-				if (g_lo + j < g_hi)
-					desc_one(g_lo + j, kr[j], kcls[j], kn[j], kw[j], std::integral_constant<bool, PBF>{});
-		} else {
-			for (uint32_t g = g_lo; g < g_hi; g++) {
-				const OutlineRect r = rects[g];
-				uint32_t cls, T, nspans, weight;
-				classify(r, cls, T, nspans, weight);
-				desc_one(g, r, cls, nspans, weight, std::true_type{});
-			}
-		}
-	}
-	__syncthreads();
-	// bucket bases: main class first (heaviest bucket first), then the brute-force class — one (class, bucket)
-	// cell per thread
-	__shared__ uint32_t s_nmain, s_nall;
-	static_assert(2 * kPlanBuckets == kPlanThreads, "one histogram cell per thread");
-	{
-		const unsigned long long mine = (&s_hist[0][0])[tid];
-		unsigned long long acc;
-		const unsigned long long base_at = block_exclusive_sum(mine, s_wave, acc);
-		(&s_hist[0][0])[tid] = (uint32_t)(base_at > 0xFFFFFFFFull ? 0xFFFFFFFFull : base_at);
-		if (tid == kPlanBuckets) // first cell of the brute-force class: everything before it is main class
-			s_nmain = (uint32_t)(base_at > 0x7FFFFFFFull ? 0x7FFFFFFFull : base_at);
-		if (tid == 0)
-			s_nall = (uint32_t)(acc > 0x7FFFFFFFull ? 0x80000000ull : acc);
-	}
-	__syncthreads();
-	if (tid == 0) {
-		const unsigned long long acc = s_nall;
-		hdr->n_segments = s_carry[0];
-		hdr->out_bytes = s_carry[1];
-		hdr->n_spans = s_nall;
-		hdr->n_main = s_nmain;
-		hdr->error = error_flag[0] | (((s_carry[0] > 0xFFFFFFFFull) || (acc > 0x7FFFFFFFull)) ? 1u : 0u); // bit 0: sizes, bit 1: unknown command kind
-		hdr->ok = 0;
-	}
-	__syncthreads();
-	const bool any_bad = __syncthreads_or(bad);
-	if (tid == 0 && any_bad)
-		hdr->error |= 1u;
-	// no work list for a batch in error (its sizes may be absurd), nor when the list does not fit: the host
-	// grows it and runs the plan again
-	if (any_bad || error_flag[0] != 0 || s_carry[0] > 0xFFFFFFFFull || s_nall > tile_cap || s_nall > 0x7FFFFFFFu)
-		return;
-	// (every glyph's entries are in place when the kernel ends: a launch enqueued behind it may read the list)
-	if (tid == 0)
-		hdr->ok = s_carry[0] <= seg_cap && s_carry[1] <= out_cap && s_nall == s_nmain && s_nmain <= launch_spans;
-	// pass B: entries.  One per span of T tiles: (glyph, first pixel | T) in the span list's main class, else
-	// (glyph, first pixel).
-	auto entries = [&](uint32_t g, const OutlineRect &r, uint32_t cls, uint32_t T, uint32_t nspans, uint32_t weight) {
-		if (!nspans)
-			return;
-		uint32_t at = atomicAdd(&s_hist[cls][weight_bucket(weight)], nspans);
-		const unsigned long long px = (unsigned long long)r.w * r.h;
-		for (unsigned long long p = 0; p < px; p += 256ull * T) {
-			const uint32_t left = (uint32_t)((px - p + 255ull) >> 8);
-			tiles[at++] = make_uint2(g, span_list && cls == 0 ? ((uint32_t)p | min(T, left)) : (uint32_t)p);
-		}
-	};
-	if (kept) {
-#pragma unroll
-		for (uint32_t j = 0; j < kKeep; j++)
-			if (g_lo + j < g_hi)
-				entries(g_lo + j, kr[j], kcls[j], kT[j], kn[j], kw[j]);
-	} else {
-		for (uint32_t g = tid; g < n_glyphs; g += kPlanThreads) {
-			const OutlineRect r = rects[g];
-			uint32_t cls, T, nspans, weight;
-			classify(r, cls, T, nspans, weight);
-			entries(g, r, cls, T, nspans, weight);
-		}
-	}
-}
-
-// ---------------------------------------------------------------------------------------
 // chunk boxes from the commands' boxes (one wave per glyph of more than two chunks).  The raster skips a chunk of 256
 // segments whose box is far from a span (sdf_span_kernel.inc); sdf_chunk_boxes takes those boxes from the segments, i.e.
 // behind the second flattening pass, on the path every bitmap waits for.  Everything needed for a box that CONTAINS the
@@ -1383,389 +1091,9 @@ __global__ __launch_bounds__(kFlattenThreads) void outline_emit_segments(const O
 	}
 }
 
-
-// ---------------------------------------------------------------------------------------
-// glyf decode: thread per PART (one simple glyph of a — possibly composite — glyph, with the transform ttf-parser has
-// accumulated for it).  The host only looks glyphs up and copies each simple glyph's `glyf` arrays (end points of the
-// contours, then flags / x / y as they stand in the font, instructions left out); this pass replays ttf-parser's walk
-// (glyf.rs: parse_simple_outline — flag runs, short / same-or-positive coordinates, wrapping i16 sums — and Builder:
-// implied on-curve midpoints, the closing curve of a contour, close()) and writes the OutlineBuilder callbacks as the
-// OutlineCmd records every later pass reads: what csrc/host/ttf_face.cpp records on the host, callback for callback
-// (f32, one multiply-add pair per transformed coordinate, never fused).
-// A part owns `cmd_cap` >= points + 2 * contours command slots (a contour of L points brings at most L + 2 callbacks: one per
-// point, the closing line or curve, close(); the second closing curve of a contour that begins and ends off the curve comes
-// instead of its first point's callback; end points that do not ascend cannot add contours — the lengths EndpointsIter
-// hands out sum to at least the point count); the slots it does not need are filled with close():
-// on the empty ring that follows a contour's own close() the RingBuilder does nothing (ring_builder.rs:33-38).
-// error_flag bit 4: an entry whose arrays do not fit its bytes or its slots — ttf-parser would drop that glyph and, in a
-// composite, the components after it; the host records such a batch itself.
-// ---------------------------------------------------------------------------------------
-struct GlyfPart {          // mirrors vgsdf_glyf_part (include/vgsdf.h)
-	uint32_t byte_off;     // into `bytes`: endPtsOfContours[n_contours], then the flag / x / y arrays of the entry
-	uint32_t byte_len;
-	uint32_t cmd_at, cmd_cap;
-	uint32_t n_contours;
-	uint32_t plain;        // 1: identity transform
-	float a, b, c, d, e, f;
-};
-static_assert(sizeof(GlyfPart) == 48, "GlyfPart layout");
-
-// One wave per part, the points dealt out to the lanes (a lane that walks a 300-point glyph alone needs ~0.2 ms: ~700 dependent
-// instructions per point on a machine that issues one every few cycles per wave):
-//   A  flags: run-length decoding without a walk.  A byte of the flag stream is a repeat COUNT iff the byte in front of it
-//      is a flag with REPEAT set — inside a run of bytes that all carry bit 3 flags and counts alternate, so a byte's role
-//      follows from the length of the run of such bytes in front of it (one ballot per 64 bytes); runs are laid out by a
-//      prefix sum, every flag lands on the points it covers (LDS), the sizes of the x / y arrays come out as sums.
-//   B  coordinates: offset of a point's delta = prefix sum of the sizes its flags give, value = prefix sum of the deltas
-//      (mod 2^16, as the i16 additions of the walk wrap).
-//   C  contours and callbacks: the end points give every contour's first and last point (ttf-parser's EndpointsIter, also for
-//      end points that do not ascend); what Builder::push_point emits for a point depends on its own flag, the flag of
-//      the point in front of it and the first two points of its contour — no state is carried; the last point of a
-//      contour also emits what Builder::finish adds; positions by prefix sum.
-// A wave's time is a handful of dependent memory round trips (~1.5 us each), not arithmetic: the part's bytes are fetched
-// ONCE (coalesced dwords into LDS; flags, coordinates and end points are then read there), and the LDS a workgroup takes is
-// sized per launch from the batch's largest part, so that as a rule every part of a font is resident at once (3993 parts of
-// Noto Sans Regular: 25.8 us with 21 KB of LDS per wave and the arrays read from global memory).
-constexpr uint32_t kGlyfMaxPoints = 6144; // per part (LDS: 1 + 2 + 2 bytes per point + its bytes); beyond: the host's reader (error_flag bit 4)
-constexpr uint32_t kGlyfMaxBytes = 30 * 1024;   // (together below the 64 KB a workgroup gets without asking for more)
-
-__device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t v)
-{
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = (uint32_t)__shfl_up((int)v, d);
-		if ((int)(threadIdx.x & 63u) >= d)
-			v = max(v, o);
-	}
-	return v;
-}
-
-// max_points / max_bytes: what the launch's LDS was sized for (the batch's largest cmd_cap bounds its largest point count)
-// cmd_open (may be NULL): the context pass's result for these commands, written here as well — whether the ring is non-empty in
-// front of a command follows from the contour rules alone: every contour of a part begins on an empty ring (the contour
-// in front of it, or the filler behind the previous part, ended with close()), its move_to opens the ring and everything
-// behind it up to its close() finds it open.  (Bit 1 of the context byte — a glyph whose scale is not positive and finite —
-// is the caller's to rule out: the host passes cmd_open only when every scale of the batch is.)
-#define GLYF_DECODE_RESIDENT 0
-#include "glyf_decode_kernel.inc"
-#undef GLYF_DECODE_RESIDENT
-#define GLYF_DECODE_RESIDENT 1
-#include "glyf_decode_kernel.inc"
-#undef GLYF_DECODE_RESIDENT
-
-
-// The upload of a submission whose input sits in ONE page-locked, device-mapped block: 16 bytes per thread, every load of
-// the block in flight at once — one PCIe round trip plus the bytes, without the copy engine's hand-over in front of the
-// first kernel (hipMemcpyAsync: 16.5 us for the 200 KB of a font + 8.7 us until the next kernel starts).
-__global__ __launch_bounds__(256) void copy_in(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint32_t n16, const uint8_t *__restrict__ src_tail,
-                                               uint8_t *__restrict__ dst_tail, uint32_t n_tail)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n16)
-		dst[i] = src[i];
-	if (i < n_tail)
-		dst_tail[i] = src_tail[i];
-}
-
-// The upload of a submission that names its glyphs (vgsdf_outlines_resident): copy_in's copy of the ONE page-locked block
-// (upload_layout.h, ResidentBlockLayout: per-glyph arrays + the fonts' device addresses), and the expansion of the glyphs'
-// leaves into this submission's parts.  A workgroup takes 256 glyphs: their offsets, glyph ids and font indices go to LDS
-// with the same round trip as the copy's loads, then the LEAVES of those glyphs — [part_off[g0], part_off[g0 + 256)) — are
-// dealt to the lanes one each (1.3 - 1.5 per glyph with a long tail: a composite of composites does not hold a lane back);
-// a lane finds its leaf's glyph by bisection in LDS, reads the leaf from the resident table of the glyph's font (HBM) and
-// stores it as part part_off[g] + k with cmd_at moved to the glyph's slots and the font's index beside `plain`.
-constexpr uint32_t kExpandThreads = 256, kExpandFontCache = 128;
-__global__ __launch_bounds__(kExpandThreads) void resident_expand(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint32_t n16,
-                                                                  uint32_t n_glyphs, uint32_t n_parts, uint32_t n_fonts, uint32_t cmd_off_at,
-                                                                  uint32_t part_off_at, uint32_t glyph_id_at, uint32_t font_of_at,
-                                                                  uint32_t fonts_at, GlyfPart *__restrict__ parts_out)
-{
-	__shared__ uint32_t s_part_off[kExpandThreads + 1], s_cmd_off[kExpandThreads];
-	__shared__ uint16_t s_gid[kExpandThreads], s_font[kExpandThreads];
-	__shared__ ResidentFontRef s_fonts[kExpandFontCache];
-	const uint32_t t = threadIdx.x, i = blockIdx.x * kExpandThreads + t, g0 = blockIdx.x * kExpandThreads;
-	const uint8_t *const sb = reinterpret_cast<const uint8_t *>(src);
-	const ResidentFontRef *const fonts = reinterpret_cast<const ResidentFontRef *>(sb + fonts_at);
-	uint4 v = make_uint4(0, 0, 0, 0);
-	if (i < n16)
-		v = src[i];
-	const uint32_t ng = g0 < n_glyphs ? min(kExpandThreads, n_glyphs - g0) : 0u;
-	if (ng) {
-		const uint32_t *part_off = reinterpret_cast<const uint32_t *>(sb + part_off_at) + g0;
-		for (uint32_t k = t; k <= ng; k += kExpandThreads)
-			s_part_off[k] = part_off[k];
-		if (t < ng) {
-			s_cmd_off[t] = reinterpret_cast<const uint32_t *>(sb + cmd_off_at)[g0 + t];
-			s_gid[t] = reinterpret_cast<const uint16_t *>(sb + glyph_id_at)[g0 + t];
-			s_font[t] = reinterpret_cast<const uint16_t *>(sb + font_of_at)[g0 + t];
-		}
-		for (uint32_t k = t; k < min(n_fonts, kExpandFontCache); k += kExpandThreads)
-			s_fonts[k] = fonts[k];
-	}
-	if (i < n16)
-		dst[i] = v;
-	if (ng == 0) // (uniform in the workgroup)
-		return;
-	__syncthreads();
-#include "resident_expand_leaves.inc"
-}
-
-// The upload of a submission that names its glyphs against COMMAND fonts (vgsdf_font_create_commands): copy_in's copy of the
-// ONE page-locked block (upload_layout.h, CommandBlockLayout) and the gather of every named glyph's expanded records and
-// context bytes from its font's store into the batch's command arrays at cmd_off[g] — a pure segmented copy: no decoder and,
-// when every scale is positive and finite, no context pass runs behind it.  A workgroup takes 256 glyphs as resident_expand
-// does: lane t reads glyph g0 + t's offset, id and font index with the same round trip as the copy's loads (and the font
-// references go to LDS), looks its glyph's first record up in the font's offset table and leaves the two source addresses in
-// LDS; then the COMMANDS of those glyphs — [cmd_off[g0], cmd_off[g0 + 256)) — are dealt to the lanes, kGatherUnroll per lane
-// and round with every load of a round in flight before its first store (a 5000-command glyph holds no lane back), and a
-// lane finds its command's glyph by bisection in LDS.  Records are 4-byte aligned only (28 bytes: seven dword copies); the
-// context bytes start at any byte offset on either side and travel a byte per lane.
-constexpr uint32_t kGatherUnroll = 4;
-__global__ __launch_bounds__(kExpandThreads) void resident_gather(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint32_t n16,
-                                                                  uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_fonts, uint32_t cmd_off_at,
-                                                                  uint32_t glyph_id_at, uint32_t font_of_at, uint32_t fonts_at,
-                                                                  uint32_t *__restrict__ cmds_out, uint8_t *__restrict__ open_out)
-{
-	__shared__ uint32_t s_cmd_off[kExpandThreads + 1];
-	__shared__ const uint32_t *s_recs[kExpandThreads];
-	__shared__ const uint8_t *s_open[kExpandThreads];
-	__shared__ CommandFontRef s_fonts[kExpandFontCache];
-	const uint32_t t = threadIdx.x, i = blockIdx.x * kExpandThreads + t, g0 = blockIdx.x * kExpandThreads;
-	const uint8_t *const sb = reinterpret_cast<const uint8_t *>(src);
-	const CommandFontRef *const fonts = reinterpret_cast<const CommandFontRef *>(sb + fonts_at);
-	uint4 v = make_uint4(0, 0, 0, 0);
-	if (i < n16)
-		v = src[i];
-	const uint32_t ng = g0 < n_glyphs ? min(kExpandThreads, n_glyphs - g0) : 0u;
-	uint32_t gid = 0, f = 0;
-	if (ng) {
-		const uint32_t *cmd_off = reinterpret_cast<const uint32_t *>(sb + cmd_off_at) + g0;
-		for (uint32_t k = t; k <= ng; k += kExpandThreads)
-			s_cmd_off[k] = cmd_off[k];
-		if (t < ng) {
-			gid = reinterpret_cast<const uint16_t *>(sb + glyph_id_at)[g0 + t];
-			f = reinterpret_cast<const uint16_t *>(sb + font_of_at)[g0 + t];
-		}
-		for (uint32_t k = t; k < min(n_fonts, kExpandFontCache); k += kExpandThreads)
-			s_fonts[k] = fonts[k];
-	}
-	if (i < n16)
-		dst[i] = v;
-	if (ng == 0) // (uniform in the workgroup)
-		return;
-	__syncthreads();
-#include "resident_gather_records.inc"
-}
-
-// The uploads of a submission that names code-point ranges of resident families: what the launch is given (the counts every
-// index of the block is bounded against, where the block's records lie, where the device's copy has its per-glyph arrays)
-constexpr uint32_t kFamilyCache = 64; // family records a workgroup keeps in LDS
-struct FamilyLaunch {
-	uint32_t n_glyphs, n_cmds, n_parts, n_fonts, n_tasks, n_families, with_pbf;
-	uint32_t families_at, fonts_at; // in the block (its task records begin it)
-	uint32_t d_scale, d_shift_x, d_cmd_off, d_part_off, d_glyph_id, d_font_of, d_pbf_pre, d_pbf_fix, d_fonts; // in the device's copy
-};
-#define FAMILY_GLYF 1
-#include "family_upload_kernel.inc"
-#undef FAMILY_GLYF
-#define FAMILY_GLYF 0
-#include "family_upload_kernel.inc"
-#undef FAMILY_GLYF
-
-// In-place PBF assembly of a ranges submission: the bytes of every glyph's entry AROUND its bitmap, written on the device —
-// what the host's write_pbf_entry_headers (csrc/host/pbf.cpp) writes for the other forms once the rects are back.  A lane per
-// glyph, behind the plan: from the rect, the bitmap's position pbf_at[g] and the entry's id and advance (left by the upload
-// kernel) it stores
-//   0x1A varint(msg) 0x08 varint(id) [0x12 varint(w h)]                      ending at pbf_at[g]
-//   0x18 width 0x20 height 0x28 zigzag(left) 0x30 zigzag(top) 0x38 advance   behind the bitmap (PbfGlyph::empty without a raster)
-// with pbf_place's arithmetic, into `out`: wherever the submission's raster stores its bitmaps, under the same PlanHeader::ok
-// guard (need_ok = 0: the launch the host repeats after a guess that did not hold).  No byte of a bitmap or of a task's
-// reserved room is touched; plain byte stores.  It also notes where every task's reserved room begins (begin[task], and the
-// arena's size behind the last): positions, valid whether or not the entries could be stored.
-__device__ __forceinline__ uint8_t *put_varint(uint8_t *p, unsigned long long v)
-{
-	for (; v >= 0x80ull; v >>= 7)
-		*p++ = (uint8_t)(v | 0x80ull);
-	*p++ = (uint8_t)v;
-	return p;
-}
-__global__ __launch_bounds__(256) void pbf_entries(const OutlineRect *__restrict__ rects, const unsigned long long *__restrict__ pbf_at,
-                                                   const uint32_t *__restrict__ pbf_pre, const EntryName *__restrict__ names,
-                                                   uint32_t n_glyphs, uint32_t n_tasks, const PlanHeader *__restrict__ hdr, uint32_t need_ok,
-                                                   unsigned long long out_cap, uint8_t *__restrict__ out,
-                                                   unsigned long long *__restrict__ begin)
-{
-	const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-	if (g >= n_glyphs || hdr->error != 0) // (the positions of a batch in error say nothing)
-		return;
-	const OutlineRect r = rects[g];
-	const EntryName nm = names[g];
-	const unsigned long long at = pbf_at[g];
-	const uint32_t idlen = 1u + varint_len(nm.id), advlen = 1u + varint_len(nm.advance);
-	const unsigned long long px = r.has_raster ? (unsigned long long)r.w * r.h : 0ull;
-	uint32_t width = 0, height = 0, zl = 0, zt = 0, bm_hdr = 0;
-	if (r.has_raster) {
-		const uint32_t left = (uint32_t)r.x0 + 3u, top = (uint32_t)r.y0 + r.h - 27u; // two's complement, as i32 arithmetic wraps
-		width = r.w - 6u, height = r.h - 6u;
-		zl = (left << 1) ^ (uint32_t)((int32_t)left >> 31), zt = (top << 1) ^ (uint32_t)((int32_t)top >> 31);
-		bm_hdr = 1u + varint_len(px);
-	}
-	const uint32_t back = 4u + varint_len(width) + varint_len(height) + varint_len(zl) + varint_len(zt) + advlen;
-	const unsigned long long msg = (unsigned long long)idlen + bm_hdr + px + back;
-	const uint32_t front = 1u + varint_len(msg) + idlen + bm_hdr;
-	if (nm.task_first != 0 && nm.task_first <= n_tasks)
-		begin[nm.task_first - 1u] = at - front - pbf_pre[g];
-	if (g == n_glyphs - 1u)
-		begin[n_tasks] = hdr->out_bytes;
-	if (out == nullptr || (need_ok && hdr->ok == 0) || at < front || at + px + back > out_cap)
-		return;
-	uint8_t *p = out + (at - front);
-	*p++ = 0x1A;
-	p = put_varint(p, msg);
-	*p++ = 0x08;
-	p = put_varint(p, nm.id);
-	if (r.has_raster) {
-		*p++ = 0x12;
-		p = put_varint(p, px);
-	}
-	p = out + at + px; // (behind the bitmap, which the raster stores)
-	*p++ = 0x18;
-	p = put_varint(p, width);
-	*p++ = 0x20;
-	p = put_varint(p, height);
-	*p++ = 0x28;
-	p = put_varint(p, zl);
-	*p++ = 0x30;
-	p = put_varint(p, zt);
-	*p++ = 0x38;
-	p = put_varint(p, nm.advance);
-}
-
 } // namespace vgsdf
 
 using namespace vgsdf;
-
-extern "C" int vgsdf_resident_gather(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_fonts,
-                                     bool with_pbf, OutlineCmd *cmds_out, uint8_t *cmd_open, hipStream_t stream)
-{
-	if (n_glyphs == 0)
-		return 0;
-	const CommandBlockLayout cl(n_glyphs, n_fonts, with_pbf);
-	const uint32_t n16 = (uint32_t)((block_bytes + 15) / 16); // (the block and its device copy are padded to 16 bytes)
-	const uint32_t grid = (std::max(n16, n_glyphs) + kExpandThreads - 1u) / kExpandThreads;
-	hipLaunchKernelGGL(resident_gather, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint4 *)src, (uint4 *)dst, n16, n_glyphs, n_cmds,
-	                   n_fonts, (uint32_t)cl.cmd_off, (uint32_t)cl.glyph_id, (uint32_t)cl.font_of, (uint32_t)cl.fonts, (uint32_t *)cmds_out,
-	                   cmd_open);
-	return (int)hipGetLastError();
-}
-
-extern "C" void vgsdf_glyf_limits(uint32_t *max_points, uint32_t *max_bytes, uint32_t *expand_font_cache)
-{
-	if (max_points)
-		*max_points = kGlyfMaxPoints;
-	if (max_bytes)
-		*max_bytes = kGlyfMaxBytes;
-	if (expand_font_cache)
-		*expand_font_cache = kExpandFontCache;
-}
-
-extern "C" int vgsdf_resident_expand(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_parts, uint32_t n_fonts,
-                                     bool with_pbf, void *parts_out, hipStream_t stream)
-{
-	if (n_glyphs == 0)
-		return 0;
-	const ResidentBlockLayout rl(n_glyphs, n_fonts, with_pbf);
-	const uint32_t n16 = (uint32_t)((block_bytes + 15) / 16); // (the block and its device copy are padded to 16 bytes)
-	const uint32_t grid = (std::max(n16, n_glyphs) + kExpandThreads - 1u) / kExpandThreads;
-	hipLaunchKernelGGL(resident_expand, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint4 *)src, (uint4 *)dst, n16, n_glyphs, n_parts,
-	                   n_fonts, (uint32_t)rl.cmd_off, (uint32_t)rl.part_off, (uint32_t)rl.glyph_id, (uint32_t)rl.font_of, (uint32_t)rl.fonts,
-	                   (GlyfPart *)parts_out);
-	return (int)hipGetLastError();
-}
-
-extern "C" int vgsdf_family_upload(bool commands, const void *src, void *dst, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts,
-                                   uint32_t n_fonts, uint32_t n_tasks, uint32_t n_families, bool with_pbf, void *parts_out,
-                                   OutlineCmd *cmds_out, uint8_t *cmd_open, void *names, uint32_t *error_flag, hipStream_t stream)
-{
-	if (n_glyphs == 0)
-		return 0;
-	const RangesBlockLayout bl(n_tasks, n_families, n_fonts);
-	FamilyLaunch L{};
-	L.n_glyphs = n_glyphs, L.n_cmds = n_cmds, L.n_parts = n_parts, L.n_fonts = n_fonts, L.n_tasks = n_tasks, L.n_families = n_families;
-	L.with_pbf = with_pbf ? 1u : 0u;
-	L.families_at = (uint32_t)bl.families, L.fonts_at = (uint32_t)bl.fonts;
-	const uint32_t grid = (std::max(n_glyphs, 2u * n_fonts) + kExpandThreads - 1u) / kExpandThreads;
-	if (commands) {
-		const CommandBlockLayout cl(n_glyphs, n_fonts, with_pbf);
-		L.d_scale = (uint32_t)cl.scale, L.d_shift_x = (uint32_t)cl.shift_x, L.d_cmd_off = (uint32_t)cl.cmd_off;
-		L.d_glyph_id = (uint32_t)cl.glyph_id, L.d_font_of = (uint32_t)cl.font_of, L.d_pbf_pre = (uint32_t)cl.pbf_pre;
-		L.d_pbf_fix = (uint32_t)cl.pbf_fix, L.d_fonts = (uint32_t)cl.fonts;
-		hipLaunchKernelGGL(family_gather, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint8_t *)src, (uint8_t *)dst, L,
-		                   (uint32_t *)cmds_out, cmd_open, (EntryName *)names, error_flag);
-	} else {
-		const ResidentBlockLayout rl(n_glyphs, n_fonts, with_pbf);
-		L.d_scale = (uint32_t)rl.scale, L.d_shift_x = (uint32_t)rl.shift_x, L.d_cmd_off = (uint32_t)rl.cmd_off, L.d_part_off = (uint32_t)rl.part_off;
-		L.d_glyph_id = (uint32_t)rl.glyph_id, L.d_font_of = (uint32_t)rl.font_of, L.d_pbf_pre = (uint32_t)rl.pbf_pre;
-		L.d_pbf_fix = (uint32_t)rl.pbf_fix, L.d_fonts = (uint32_t)rl.fonts;
-		hipLaunchKernelGGL(family_expand, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint8_t *)src, (uint8_t *)dst, L,
-		                   (GlyfPart *)parts_out, (EntryName *)names, error_flag);
-	}
-	return (int)hipGetLastError();
-}
-
-extern "C" int vgsdf_pbf_entries(const OutlineRect *rects, const unsigned long long *pbf_at, const uint32_t *pbf_pre, const void *names,
-                                 uint32_t n_glyphs, uint32_t n_tasks, const PlanHeader *hdr, bool need_ok, unsigned long long out_cap,
-                                 uint8_t *out, unsigned long long *begin, hipStream_t stream)
-{
-	if (n_glyphs == 0)
-		return 0;
-	hipLaunchKernelGGL(pbf_entries, dim3((n_glyphs + 255u) / 256u), dim3(256), 0, stream, rects, pbf_at, pbf_pre, (const EntryName *)names,
-	                   n_glyphs, n_tasks, hdr, need_ok ? 1u : 0u, out_cap, out, begin);
-	return (int)hipGetLastError();
-}
-
-extern "C" int vgsdf_copy_in(const void *src_mapped, void *dst, size_t bytes, hipStream_t stream)
-{
-	if (bytes == 0)
-		return 0;
-	const uint32_t n16 = (uint32_t)(bytes / 16), n_tail = (uint32_t)(bytes % 16);
-	hipLaunchKernelGGL(copy_in, dim3((std::max(n16, 1u) + 255u) / 256u), dim3(256), 0, stream, (const uint4 *)src_mapped, (uint4 *)dst, n16,
-	                   (const uint8_t *)src_mapped + 16 * (size_t)n16, (uint8_t *)dst + 16 * (size_t)n16, n_tail);
-	return (int)hipGetLastError();
-}
-
-// LDS of a workgroup of the glyf decoder (either stamping): the largest part's bytes + 5 bytes and a bit per point (a part has
-// fewer points than command slots); parts beyond the limits fail on the device (error_flag bit 4: the host's reader takes the
-// batch).  Sets the two bounds the kernel is launched with
-static size_t glyf_decode_lds(uint32_t max_cmd_cap, uint32_t max_byte_len, uint32_t &max_points, uint32_t &max_bytes)
-{
-	max_points = std::min(std::max(max_cmd_cap, 64u), kGlyfMaxPoints);
-	max_bytes = std::min((std::max(max_byte_len, 64u) + 15u) & ~15u, kGlyfMaxBytes);
-	return (size_t)max_bytes + 4 * (size_t)max_points + 4 * (size_t)((max_points + 31u) / 32u) + max_points;
-}
-
-extern "C" int vgsdf_glyf_decode(const void *parts, uint32_t n_parts, const uint8_t *bytes, OutlineCmd *cmds, uint32_t *error_flag,
-                                 uint32_t max_cmd_cap, uint32_t max_byte_len, uint8_t *cmd_open, hipStream_t stream)
-{
-	if (n_parts == 0)
-		return 0;
-	uint32_t max_points, max_bytes;
-	const size_t lds = glyf_decode_lds(max_cmd_cap, max_byte_len, max_points, max_bytes);
-	hipLaunchKernelGGL(glyf_decode, dim3(n_parts), dim3(64), lds, stream, (const GlyfPart *)parts, n_parts, bytes, cmds, error_flag, max_points,
-	                   max_bytes, cmd_open);
-	return (int)hipGetLastError();
-}
-
-extern "C" int vgsdf_glyf_decode_resident(const void *parts, uint32_t n_parts, const void *fonts, OutlineCmd *cmds, uint32_t *error_flag,
-                                          uint32_t max_cmd_cap, uint32_t max_byte_len, uint8_t *cmd_open, hipStream_t stream)
-{
-	if (n_parts == 0)
-		return 0;
-	uint32_t max_points, max_bytes;
-	const size_t lds = glyf_decode_lds(max_cmd_cap, max_byte_len, max_points, max_bytes);
-	hipLaunchKernelGGL(glyf_decode_resident, dim3(n_parts), dim3(64), lds, stream, (const GlyfPart *)parts, n_parts,
-	                   (const ResidentFontRef *)fonts, cmds, error_flag, max_points, max_bytes, cmd_open);
-	return (int)hipGetLastError();
-}
 
 extern "C" int vgsdf_outline_context(const OutlineCmd *cmds, const uint32_t *cmd_off, const double *scale, uint32_t n_glyphs,
                                      uint8_t *cmd_open, uint32_t *error_flag, hipStream_t stream)
@@ -1808,27 +1136,6 @@ extern "C" int vgsdf_outline_rings(const OutlineCmd *cmds, const uint32_t *cmd_o
 		return 0;
 	hipLaunchKernelGGL(outline_rings, dim3(n_glyphs), dim3(64), 0, stream, cmds, cmd_off, cmd_open, scale, shift_x, n_glyphs, counts, pt_local,
 	                   (const double4 *)cmd_box, rings, cmd_ring, rects, error_flag);
-	return (int)hipGetLastError();
-}
-
-extern "C" int vgsdf_outline_plan(const OutlineRect *rects, uint32_t n_glyphs, int span_list, uint32_t delta_cap, uint32_t span_max,
-                                  uint32_t span_budget, uint32_t tile_cap, GlyphDesc *descs, uint2 *tiles, PlanHeader *hdr,
-                                  const uint32_t *error_flag, unsigned long long seg_cap, unsigned long long out_cap,
-                                  uint32_t launch_spans, const uint32_t *pbf_pre, const uint8_t *pbf_fix,
-                                  unsigned long long *pbf_at, uint32_t *next_flag, hipStream_t stream)
-{
-	if (pbf_fix != nullptr && n_glyphs <= 4u * kPlanThreads)
-		hipLaunchKernelGGL((outline_plan<4, true>), dim3(1), dim3(kPlanThreads), 0, stream, rects, n_glyphs, span_list, delta_cap, span_max,
-		                   span_budget, tile_cap, descs, tiles, hdr, error_flag, seg_cap, out_cap, launch_spans, pbf_pre, pbf_fix, pbf_at, next_flag);
-	else if (pbf_fix != nullptr && n_glyphs <= 8u * kPlanThreads)
-		// groups of 4097 .. 8192 glyphs (the dispatcher's groups of several fonts: ~7000): eight placements per thread spill
-		// to scratch, and still beat the unkept path below, which reads and classifies every rect twice (21 fonts in two
-		// groups: 48 / 90 us per plan)
-		hipLaunchKernelGGL((outline_plan<8, true>), dim3(1), dim3(kPlanThreads), 0, stream, rects, n_glyphs, span_list, delta_cap, span_max,
-		                   span_budget, tile_cap, descs, tiles, hdr, error_flag, seg_cap, out_cap, launch_spans, pbf_pre, pbf_fix, pbf_at, next_flag);
-	else
-	hipLaunchKernelGGL((outline_plan<8, false>), dim3(1), dim3(kPlanThreads), 0, stream, rects, n_glyphs, span_list, delta_cap, span_max,
-	                   span_budget, tile_cap, descs, tiles, hdr, error_flag, seg_cap, out_cap, launch_spans, pbf_pre, pbf_fix, pbf_at, next_flag);
 	return (int)hipGetLastError();
 }
 

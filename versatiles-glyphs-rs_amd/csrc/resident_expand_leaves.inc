@@ -1,6 +1,6 @@
 // resident_expand_leaves.inc — the second phase of the upload kernels that expand resident `glyf` fonts' leaves into a
 // submission's parts, stamped into resident_expand (glyphs named one by one) and family_expand (code-point ranges of families):
-// outline_kernels.hip.  Expects, in the including kernel: t (threadIdx.x), ng (glyphs of this workgroup), n_parts, parts_out,
+// input_form_kernels.hip.  Expects, in the including kernel: t (threadIdx.x), ng (glyphs of this workgroup), n_parts, parts_out,
 // `fonts` (the block's font references) and, in LDS and complete behind a barrier, s_part_off[0 .. ng], s_cmd_off, s_gid, s_font
 // [0 .. ng) and s_fonts (the first kExpandFontCache references).
 	const uint32_t p1 = min(s_part_off[ng], n_parts);

@@ -1,6 +1,6 @@
 // resident_gather_records.inc — the second phase of the upload kernels that gather command fonts' records and context bytes into
 // a submission's command arrays, stamped into resident_gather (glyphs named one by one) and family_gather (code-point ranges of
-// families): outline_kernels.hip.  Expects, in the including kernel: t, ng, n_cmds, cmds_out, open_out, `fonts`, lane t's glyph id
+// families): input_form_kernels.hip.  Expects, in the including kernel: t, ng, n_cmds, cmds_out, open_out, `fonts`, lane t's glyph id
 // and font index in gid / f, the LDS arrays s_recs / s_open, and — complete behind a barrier — s_cmd_off[0 .. ng] and s_fonts.
 	if (t < ng) {
 		const CommandFontRef ref = f < kExpandFontCache ? s_fonts[f] : fonts[f];

@@ -1,5 +1,5 @@
 // work_list.cpp — the host's planner of a resident batch's work list (the segment entry points of the C ABI; the outline
-// front-end plans on the device: outline_kernels.hip, outline_plan).  The policy itself is work_plan.h's.
+// front-end plans on the device: outline_plan_kernels.hip, outline_plan).  The policy itself is work_plan.h's.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>

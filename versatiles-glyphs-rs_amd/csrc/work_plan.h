@@ -1,5 +1,5 @@
 // work_plan.h — the policy of the raster's work list, for both of its planners: the host's (work_list.cpp, resident
-// batches of the C ABI) and the device's (outline_kernels.hip, outline_plan).  Which glyphs go to brute force, the span
+// batches of the C ABI) and the device's (outline_plan_kernels.hip, outline_plan).  Which glyphs go to brute force, the span
 // length T, the spans per glyph, a workgroup's weight and the weight's bucket are decided here and nowhere else
 // (tests/test_gpu_span_regimes.py restates the policy on purpose, as the independent check).
 #pragma once
