@@ -140,6 +140,28 @@ typedef struct {
 	uint64_t block_bytes;    /* bytes of those submissions' upload blocks */
 } vg_command_stats;
 int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out);
+/* Mixed stores, 0 (default) / 1; has an effect only with vg_manager_set_glyf_on_device, vg_manager_set_resident_fonts and
+ * vg_manager_set_resident_commands(1).  Without it, ONE glyph from a file without `glyf` outlines sends every file of its group's
+ * font ids to the command stores — a Noto Sans directory with the CFF CJK files under the same font id has every TrueType file
+ * interpreted on the host for that.  With it, stores go per FILE: a face with `glyf` outlines whose glyf store can be made (host
+ * table or device builder, batched or not) gets a glyf store, every other face a command store (charstrings on the device where
+ * that switch is on), and a group that is not all `glyf` and has at least one glyf store among its files is submitted against
+ * both kinds at once: vgsdf_outlines_submit_resident_mixed, or with vg_manager_set_resident_families as ranges of MIXED families
+ * (vgsdf_family_create_mixed; _create_tables_mixed with vg_manager_set_family_tables_on_device), which the renderer keeps beside
+ * the others under their own key — same budget, lifetime and fallbacks.  A group without a glyf store goes to the command forms
+ * exactly as with 0, a group that is all `glyf` to the glyf forms, mode 2 of the command stores is untouched; a group the
+ * device refuses falls back to the host's reader as ever (and its font ids get command stores from then on).  Same bytes.
+ * vg_renderer_preload_fonts also builds the mixed families when the mode is on.
+ * vg_manager_mixed_stats: of the last render; such groups are counted here and in none of vg_family_stats, vg_resident_stats and
+ * vg_command_stats, while the stores uploaded for them count in the upload counters of their kind. */
+void vg_manager_set_mixed_stores(vg_manager *m, int on);
+typedef struct {
+	uint64_t groups;        /* groups submitted against stores of both kinds (by name or as ranges of mixed families) */
+	uint64_t glyf_fonts;    /* glyf stores those groups named */
+	uint64_t command_fonts; /* command stores those groups named */
+	uint64_t block_bytes;   /* bytes of those submissions' upload blocks */
+} vg_mixed_stats;
+int vg_manager_mixed_stats(const vg_manager *m, vg_mixed_stats *out);
 /* Charstrings on the device, 0 (default) / 1 / 2.  With 1, wherever the renderer would build the command store of a `CFF ` version 1
  * face — modes 1 and 2 above, vg_renderer_preload_fonts, families — the DEVICE interprets the face's charstrings
  * (vgsdf_font_create_charstrings) instead of the host's reader; the host only resolves the INDEX offsets.  A face the device

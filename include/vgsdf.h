@@ -328,6 +328,19 @@ typedef struct {
 } vgsdf_font_cmds_desc;
 int vgsdf_font_create_commands(vgsdf_ctx *ctx, const vgsdf_font_cmds_desc *in, vgsdf_font **out);
 /*
+ * Fonts of BOTH kinds in one submission: the same description and the same validation as vgsdf_outlines_submit_resident, except
+ * that `fonts` may hold fonts from vgsdf_font_create (and _create_tables) and command fonts in any order; a list of one kind is
+ * accepted too.  Every glyph gives, byte for byte, what it gives in a submission of its own kind: rects, segments, bitmaps.
+ * The block is the one vgsdf_outlines_submit_resident gathers for glyf fonts,
+ *   scale f64[n] | shift_x f64[n] | cmd_off u32[n + 1] | part_off u32[n + 1] | glyph_id u16[n] | font_of u16[n] | pbf_pre u32[n] | pbf_fix u8[n]
+ * with cmd_off the running sum of command slots (glyf fonts) and commands (command fonts) over all glyphs, part_off standing
+ * still over a glyph of a command font, and 32 bytes of device addresses per font that also say the font's kind.  ONE kernel
+ * copies it, expands the leaves of the glyf fonts' glyphs into parts and gathers the records and context bytes of the command
+ * fonts' glyphs; the decoder then runs over the parts.  With pbf_pre / pbf_fix the arena is laid out as vgsdf_outlines_packed
+ * states it, whatever the kinds.  More than 2^31 - 1 slots and commands together: VGSDF_E_ARG.
+ */
+int vgsdf_outlines_submit_resident_mixed(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity);
+/*
  * The same command font made from a `CFF ` (version 1) face's own bytes: the DEVICE interprets the Type 2 charstrings of every
  * glyph id (csrc/charstring_kernels.hip: the operator set and the rules of the host reader, csrc/host/cff.cpp, whose callbacks it
  * equals bit for bit), so the host's share is to locate the INDEX tables and resolve their offsets.  The description:
@@ -496,6 +509,11 @@ int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_famil
 int vgsdf_family_free(vgsdf_ctx *ctx, vgsdf_family *family);
 uint64_t vgsdf_family_device_bytes(const vgsdf_family *family);
 uint32_t vgsdf_family_count(const vgsdf_family *family, uint32_t first, uint32_t last);
+/* The same description with fonts of EITHER kind in `fonts`.  The family is of a third kind, MIXED, even when its fonts happen to
+ * be of one kind: the prefix sum of command slots runs over every font's glyphs (slots of a glyf font, commands of a command
+ * font), the prefix sum of leaves over the glyf fonts' and stands still over an entry of a command font.  vgsdf_family_free,
+ * _device_bytes, _count and _read work on it as on any family. */
+int vgsdf_family_create_mixed(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out);
 /*
  * The same family from its faces' `cmap` and `hmtx` TABLES: no code point is looked up on the host.  The host says where the
  * unicode subtables are (vg_manager_family_tables_desc of vgfont.h builds such a description), the device looks every code point
@@ -525,6 +543,9 @@ typedef struct {
 	const vgsdf_face_tables *tables; /* [n_fonts] */
 } vgsdf_family_tables_desc;
 int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out);
+/* The same with fonts of either kind: a mixed family, indistinguishable from one vgsdf_family_create_mixed makes of the same
+ * entries.  (vgsdf_family_tables_kernel_ms reports its passes as well.) */
+int vgsdf_family_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out);
 /* test / inspection: download the DEVICE's copy of a family's table, whichever call made it; *n_entries: its entries; code_point,
  * font_of, glyph_id, advance, scale, shift_x, pbf_fix [n_entries], cmd_pre, leaf_pre [n_entries + 1] (mod 2^32): each NULL or filled */
 int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_entries, uint16_t *code_point, uint16_t *font_of,
@@ -543,7 +564,9 @@ void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
  * 0x18 width 0x20 height 0x28 left 0x30 top 0x38 advance behind), wherever the raster stores the bitmaps, so the arena comes
  * back as finished entries; only the bytes a task reserved with pbf_pre are left for the caller.
  * Tasks may come in any order, repeat and overlap; a task that maps nothing occupies nothing.  Refused with VGSDF_E_ARG before
- * anything runs: a family of another device, families of both kinds, more than 65536 fonts over the families, first > last,
+ * anything runs: a family of another device, families of more than one kind (there are three: glyf, commands, mixed — a
+ * submission of mixed families is, byte for byte, vgsdf_outlines_submit_resident_mixed of its sequence; a mixed family beside a
+ * family of glyf or of command fonts is refused like glyf beside commands), more than 65536 fonts over the families, first > last,
  * family_of past n_families, more than 2^31 - 1 command slots (or glyphs).  n_tasks == 0, or tasks that map nothing, make an
  * empty submission that waits cleanly.  Collected with vgsdf_outlines_wait; _peek, _pbf_positions and _segments work behind it
  * as behind any other form, and rects_out of _wait / _peek may be NULL.  The fonts of the block are the families' lists in the

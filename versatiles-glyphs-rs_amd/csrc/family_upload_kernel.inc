@@ -2,6 +2,9 @@
 // (vgsdf_outlines_ranges), stamped once per kind of font by input_form_kernels.hip:
 //   FAMILY_GLYF 1  family_expand   fonts from vgsdf_font_create: takes resident_expand's place
 //   FAMILY_GLYF 0  family_gather   fonts from vgsdf_font_create_commands: takes resident_gather's place
+//   FAMILY_MIXED   family_mixed    mixed families, fonts of both kinds in one list (upload_layout.h, MixedFontRef): takes
+//                                  resident_mixed's place — the per-glyph arrays of ResidentBlockLayout with no parts for an
+//                                  entry of a command font, then BOTH second phases
 // The block (upload_layout.h, RangesBlockLayout) holds a record per task, per family and per font and NOTHING per glyph: the
 // naming — task -> family entry -> (font, glyph id, scale, shift, offsets) — happens here, in front of the expansion / gather
 // the kernel would run anyway, so the form adds no launch.  A workgroup takes 256 glyphs of the submission, as those kernels
@@ -17,17 +20,27 @@
 // entry count, the font count, n_cmds, n_parts) before it is followed; a bad one raises bit 5 of the batch's error word, its
 // glyph is named as a glyph without outline and the workgroup, instead of expanding / gathering, makes every part / record of
 // the submission a benign one (below).
-#if FAMILY_GLYF
+#if defined(FAMILY_MIXED)
+#define FAMILY_KERNEL family_mixed
+#define FAMILY_FONT_REF MixedFontRef
+#define FAMILY_PARTS 1
+#define FAMILY_RECORDS 1
+#elif FAMILY_GLYF
 #define FAMILY_KERNEL family_expand
 #define FAMILY_FONT_REF ResidentFontRef
+#define FAMILY_PARTS 1
+#define FAMILY_RECORDS 0
 #else
 #define FAMILY_KERNEL family_gather
 #define FAMILY_FONT_REF CommandFontRef
+#define FAMILY_PARTS 0
+#define FAMILY_RECORDS 1
 #endif
 __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const FamilyLaunch L,
-#if FAMILY_GLYF
+#if FAMILY_PARTS
                                                                 GlyfPart *__restrict__ parts_out,
-#else
+#endif
+#if FAMILY_RECORDS
                                                                 uint32_t *__restrict__ cmds_out, uint8_t *__restrict__ open_out,
 #endif
                                                                 EntryName *__restrict__ names, uint32_t *__restrict__ error_flag)
@@ -35,12 +48,14 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 	__shared__ RangeTask s_task[kExpandThreads];
 	__shared__ FamilyRef s_fam[kFamilyCache];
 	__shared__ FAMILY_FONT_REF s_fonts[kExpandFontCache];
-#if FAMILY_GLYF
-	__shared__ uint32_t s_part_off[kExpandThreads + 1], s_cmd_off[kExpandThreads];
+#if FAMILY_PARTS
+	__shared__ uint32_t s_part_off[kExpandThreads + 1], s_cmd_off[kExpandThreads + FAMILY_RECORDS];
 	__shared__ uint16_t s_gid[kExpandThreads], s_font[kExpandThreads];
 	const uint32_t n_parts = L.n_parts;
 #else
 	__shared__ uint32_t s_cmd_off[kExpandThreads + 1];
+#endif
+#if FAMILY_RECORDS
 	__shared__ const uint32_t *s_recs[kExpandThreads];
 	__shared__ const uint8_t *s_open[kExpandThreads];
 #endif
@@ -92,7 +107,7 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 		const uint32_t k = g - T.glyph_base;
 		// a glyph without outline at the end of everything: what a lane names whose indices do not hold
 		uint32_t cmd_at = n_cmds, cmd_n = 0, pre = 0, fix = 0x22u;
-#if FAMILY_GLYF
+#if FAMILY_PARTS
 		uint32_t part_at = n_parts, part_n = 0;
 #endif
 		double scale = 1.0, shift = 0.0;
@@ -111,7 +126,7 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 				cmd_at = T.cmd_rel + c0;
 				cmd_n = c1 - c0;
 				bad = fo >= F.n_fonts || (unsigned long long)cmd_at + cmd_n > n_cmds;
-#if FAMILY_GLYF
+#if FAMILY_PARTS
 				const uint32_t *const lp = reinterpret_cast<const uint32_t *>(tb + at.leaf_pre) + e;
 				const uint32_t l0 = lp[0], l1 = lp[1];
 				part_at = T.part_rel + l0;
@@ -136,7 +151,7 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 		if (bad) {
 			atomicOr(error_flag, 32u);
 			cmd_at = n_cmds, cmd_n = 0;
-#if FAMILY_GLYF
+#if FAMILY_PARTS
 			part_at = n_parts, part_n = 0;
 #endif
 		}
@@ -154,7 +169,7 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 			names[g] = nm;
 		}
 		s_cmd_off[t] = cmd_at;
-#if FAMILY_GLYF
+#if FAMILY_PARTS
 		uint32_t *const d_part_off = reinterpret_cast<uint32_t *>(dst + L.d_part_off);
 		d_part_off[g] = part_at;
 		if (g == L.n_glyphs - 1u)
@@ -164,7 +179,8 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 			s_part_off[ng] = part_at + part_n;
 		s_gid[t] = (uint16_t)gid;
 		s_font[t] = (uint16_t)f;
-#else
+#endif
+#if FAMILY_RECORDS
 		if (t == ng - 1u)
 			s_cmd_off[ng] = cmd_at + cmd_n;
 #endif
@@ -175,12 +191,13 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 		// decoder reads nothing for it and writes nothing), a close() with no ring open in front of it — racing with the
 		// other workgroups' good ones; whichever 16 bytes win, every part names font 0 or its own font and slots inside the
 		// batch.  The batch fails in wait either way
-#if FAMILY_GLYF
+#if FAMILY_PARTS
 		for (uint32_t j = t; j < n_parts; j += kExpandThreads) {
 			uint4 *op = reinterpret_cast<uint4 *>(parts_out + j);
 			op[0] = op[1] = op[2] = make_uint4(0, 0, 0, 0);
 		}
-#else
+#endif
+#if FAMILY_RECORDS
 		for (uint32_t j = t; j < n_cmds; j += kExpandThreads) {
 			uint32_t *out = cmds_out + 7ull * j;
 			for (uint32_t w = 0; w < 6; w++)
@@ -191,7 +208,13 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 #endif
 		return;
 	}
-#if FAMILY_GLYF
+#if FAMILY_PARTS && FAMILY_RECORDS
+	// both second phases: the leaves of the workgroup's glyf glyphs into parts, then the records of its command glyphs
+	{
+#include "resident_expand_leaves.inc"
+	}
+#include "resident_gather_records.inc"
+#elif FAMILY_PARTS
 #include "resident_expand_leaves.inc"
 #else
 #include "resident_gather_records.inc"
@@ -199,3 +222,5 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 }
 #undef FAMILY_KERNEL
 #undef FAMILY_FONT_REF
+#undef FAMILY_PARTS
+#undef FAMILY_RECORDS

@@ -157,6 +157,13 @@ int vg_manager_command_stats(const vg_manager *m, vg_command_stats *out)
 	*out = vg_command_stats{t.command_groups, t.command_fonts_uploaded, t.command_font_bytes, t.command_block_bytes};
 	return 0;
 }
+void vg_manager_set_mixed_stores(vg_manager *m, int on) { m->m.set_mixed_stores(on != 0); }
+int vg_manager_mixed_stats(const vg_manager *m, vg_mixed_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_mixed_stats{t.mixed_groups, t.mixed_glyf_fonts, t.mixed_command_fonts, t.mixed_block_bytes};
+	return 0;
+}
 void vg_manager_set_charstrings_on_device(vg_manager *m, int on) { m->m.set_charstrings_on_device(on == 2 ? 2 : (on != 0 ? 1 : 0)); }
 int vg_manager_charstring_stats(const vg_manager *m, vg_charstring_stats *out)
 {

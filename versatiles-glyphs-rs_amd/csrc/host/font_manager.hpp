@@ -166,6 +166,9 @@ struct RenderTimings {
 	uint64_t glyf_tables_built = 0, glyf_table_bytes = 0, glyf_table_fallbacks = 0;
 	// ... and, with set_glyf_tables_batched, the calls that built them (one per font id whose faces needed building) and the faces sent
 	uint64_t glyf_table_batch_calls = 0, glyf_table_batch_faces = 0;
+	// groups submitted against stores of BOTH kinds (set_mixed_stores; counted here and in none of the group counters above), the
+	// glyf stores and the command stores those groups named, bytes of their upload blocks
+	uint64_t mixed_groups = 0, mixed_glyf_fonts = 0, mixed_command_fonts = 0, mixed_block_bytes = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -182,6 +185,8 @@ struct RenderTimings {
 		resident_groups += lane.resident_groups, resident_block_bytes += lane.resident_block_bytes;
 		command_groups += lane.command_groups, command_block_bytes += lane.command_block_bytes;
 		family_groups += lane.family_groups, family_block_bytes += lane.family_block_bytes;
+		mixed_groups += lane.mixed_groups, mixed_glyf_fonts += lane.mixed_glyf_fonts, mixed_command_fonts += lane.mixed_command_fonts;
+		mixed_block_bytes += lane.mixed_block_bytes;
 		add_uploads(lane);
 	}
 	// what `counts` says was put on a device — stores, families, decoded charstrings — added to these
@@ -198,7 +203,7 @@ struct RenderTimings {
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 32 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 36 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -280,6 +285,14 @@ public:
 	// 2: every group goes that way, `glyf` faces included (the A/B lever).  A store that does not fit the renderer's
 	// budget sends its groups the way they go with 0.
 	void set_resident_commands(int mode) { resident_commands_ = mode < 0 || mode > 2 ? 0 : mode; }
+	// Mixed stores (default off; has an effect only with the device's glyf decoder, resident fonts and set_resident_commands(1)): a
+	// group that cannot take a glyf form because SOME glyph comes from a file without `glyf` outlines no longer sends every file of
+	// its font ids to the command stores.  Stores go per FILE — a `glyf` file whose glyf store can be made gets that one, every
+	// other file a command store — and the group is submitted against both kinds at once (by name, or as ranges of mixed
+	// families).  A group none of whose files gets a glyf store goes to the command forms as without the switch.
+	void set_mixed_stores(bool on) { mixed_stores_ = on; }
+	// ... and whether the switches are such that it has an effect
+	bool mixes() const { return mixed_stores_ && glyf_on_device_ && resident_fonts_ && resident_commands_ == 1; }
 	// Command stores of `CFF ` version 1 faces decoded on the device from the charstrings (vgsdf_font_create_charstrings) instead
 	// of uploaded from command_table(); a face the device refuses falls back.  Default off.  The stores' bytes are the same.
 	// 2: CFF2 faces too (vgsdf_font_create_charstrings2, with the reader's blend factors: the default position).
@@ -457,7 +470,10 @@ private:
 	// The form a group of the device front-end is submitted in: the host reader's commands in the packed upload form; the glyphs'
 	// `glyf` parts; the glyphs named by (font, glyph id) against the renderer's resident glyf stores / command stores; code-point
 	// ranges of the font ids' families over either kind of store
-	enum class GroupForm : uint8_t { Packed, GlyfParts, NamedGlyf, NamedCommands, RangesGlyf, RangesCommands };
+	// ... or over both kinds, store by store (set_mixed_stores)
+	enum class GroupForm : uint8_t { Packed, GlyfParts, NamedGlyf, NamedCommands, RangesGlyf, RangesCommands, NamedMixed, RangesMixed };
+	// the kind of store a form names its glyphs against: one kind for every file, or per file whichever the file gets
+	enum class StoreKind : uint8_t { Glyf, Commands, Mixed };
 	// device front-end: the buffers of one group of tasks (<= batch_blocks_ blocks, normally one font)
 	struct FeGroup {
 		size_t g0 = 0, g1 = 0;
@@ -480,8 +496,9 @@ private:
 		uint64_t out_bytes = 0, n_segs = 0;
 		uint32_t n_jobs = 0;
 		GroupForm form = GroupForm::Packed; // what fe_record made of the group
+		uint32_t mixed_glyf_stores = 0, mixed_command_stores = 0; // a mixed form: the stores of either kind the group names
 		// a group submitted as code-point ranges of resident families (fe_record_ranges): range r is a task of the submission
-		bool by_ranges() const { return form == GroupForm::RangesGlyf || form == GroupForm::RangesCommands; }
+		bool by_ranges() const { return form == GroupForm::RangesGlyf || form == GroupForm::RangesCommands || form == GroupForm::RangesMixed; }
 		struct Ranges {
 			std::vector<const vgsdf_family *> families; // of the group's font ids, in task order
 			std::vector<const FamilyTable *> tables;    // ... and their host halves
@@ -507,7 +524,7 @@ private:
 	// group the device has refused is recorded again: that fallback is the reader's, as ever
 	void fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool allow_glyf = true, const Renderer *renderer = nullptr, int lane = 0);
 	struct FormList { // the forms to try, in order
-		GroupForm form[6];
+		GroupForm form[8];
 		unsigned n = 0;
 	};
 	FormList fe_candidates(bool device_forms, bool glyf_forms, bool by_name, bool by_ranges) const;
@@ -521,12 +538,22 @@ private:
 	bool fe_record_glyf(const std::vector<Todo> &tasks, FeGroup &G); // false: not a batch for the device's decoder (fan-out past 32-bit offsets)
 	// false: a face of the group has no store of the kind or does not fit the renderer's budget
 	// commands: against the faces' command stores (every readable face has one) instead of their glyf stores
-	bool fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands);
+	// Mixed: per file the store it gets (file_store); false also when no file of the group gets a glyf store
+	bool fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, StoreKind kind);
 	// false: as above, or a family over the budget, or a block past code point 0xFFFF
-	bool fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands);
-	// the device family of a font id over its files' stores of one kind (nullptr: a file without such a store, or the budget)
-	const vgsdf_family *device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font, bool commands,
-	                                  const FamilyTable **table, RenderTimings &counts) const;
+	bool fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, StoreKind kind);
+	// the device family of a font id over its files' stores of one kind (nullptr: a file without such a store, or the budget), or
+	// (Mixed) over the store each file gets, a family of the mixed kind; *glyf_stores / *command_stores (may be NULL): += the stores of
+	// either kind among them
+	const vgsdf_family *device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font, StoreKind kind,
+	                                  const FamilyTable **table, RenderTimings &counts, uint32_t *glyf_stores = nullptr,
+	                                  uint32_t *command_stores = nullptr) const;
+	// Mixed stores: the store a FILE gets — its glyf store where the face has `glyf` outlines, its font id has not been refused by
+	// the decoder and the store can be made (host table or device builder); a command store otherwise.  *glyf says which
+	const vgsdf_font *file_store(const Renderer &renderer, int lane, const std::string &font_id, const Face &face, RenderTimings &counts,
+	                             bool *glyf) const;
+	// whether a mixed form can be worth trying for the fonts of tasks [g0, g1): a `glyf` file of a font id not refused among them
+	bool may_mix(const std::vector<Todo> &tasks, size_t g0, size_t g1) const;
 	void fe_assemble_ranges(const std::vector<Todo> &tasks, FeGroup &G);
 	// fonts (by id) one of whose groups the device's glyf decoder refused (VGSDF_E_GLYF) or whose parts passed the batch bounds:
 	// later groups and runs record them with the host's reader at once instead of paying the double path again; cleared
@@ -548,6 +575,7 @@ private:
 	bool glyf_on_device_ = glyf_on_device_default(); // glyf fonts: the device decodes the glyphs' arrays (VG_GLYF_ON_DEVICE=0 / set_glyf_on_device(false): the host does)
 	bool resident_fonts_ = false;
 	int resident_commands_ = 0;
+	bool mixed_stores_ = false;
 	int charstrings_on_device_ = 0;
 	bool family_tables_on_device_ = false;
 	bool glyf_tables_on_device_ = false;

@@ -236,7 +236,7 @@ struct FontManager::NamedForm {
 	using Local = ResidentBatch;
 	static constexpr bool kLight = true, kTracePack = false;
 	const std::vector<std::pair<const FontFileEntry *, uint16_t>> &index; // sorted by address: a face -> its place in m.fonts
-	bool commands;
+	bool commands; // the block of command fonts (else: the glyf form's, which fonts of both kinds take as well)
 	static Local &local(Worker &w) { return w.rlocal; }
 	auto recorder(Local &l) const
 	{
@@ -260,9 +260,11 @@ void FontManager::fe_record_packed(const std::vector<Todo> &tasks, FeGroup &G) {
 
 bool FontManager::fe_record_glyf(const std::vector<Todo> &tasks, FeGroup &G) { return fe_record_slices(tasks, G, GlyfForm{}, now_s()); }
 
-bool FontManager::fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands)
+bool FontManager::fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, StoreKind kind)
 {
 	const double t0 = now_s();
+	const bool commands = kind == StoreKind::Commands;
+	G.mixed_glyf_stores = G.mixed_command_stores = 0;
 	MergedOutlines &m = G.m;
 	// the faces of the group's fonts (tasks of one font follow each other) and their device copies
 	m.fonts.clear();
@@ -275,18 +277,24 @@ bool FontManager::fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, co
 		auto it = fonts().find(*last);
 		if (it == fonts().end())
 			return false;
-		if (!commands)
+		if (kind == StoreKind::Glyf || (kind == StoreKind::Mixed && !glyf_refused_.count(&it->first)))
 			glyf_stores_batched(renderer, lane, it->second, timings_);
 		for (const auto &file : it->second.files()) {
 			if (m.fonts.size() >= 0xFFFF)
 				return false;
-			const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), timings_) : glyf_store(renderer, lane, file->face(), timings_);
+			bool glyf = kind == StoreKind::Glyf;
+			const vgsdf_font *f = kind == StoreKind::Mixed ? file_store(renderer, lane, it->first, file->face(), timings_, &glyf)
+			                      : commands               ? command_store(renderer, lane, file->face(), timings_)
+			                                               : glyf_store(renderer, lane, file->face(), timings_);
 			if (!f)
 				return false;
+			(glyf ? G.mixed_glyf_stores : G.mixed_command_stores)++;
 			index.emplace_back(file.get(), (uint16_t)m.fonts.size());
 			m.fonts.push_back(f);
 		}
 	}
+	if (kind == StoreKind::Mixed && G.mixed_glyf_stores == 0) // (nothing to mix: the command forms take the group, as without the switch)
+		return false;
 	std::sort(index.begin(), index.end());
 	return fe_record_slices(tasks, G, NamedForm{index, commands}, t0);
 }
@@ -357,22 +365,58 @@ const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane,
 	return f;
 }
 
-const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font,
-                                               bool commands, const FamilyTable **table, RenderTimings &counts) const
+const vgsdf_font *FontManager::file_store(const Renderer &renderer, int lane, const std::string &font_id, const Face &face,
+                                          RenderTimings &counts, bool *glyf) const
 {
+	*glyf = false;
+	if (face.has_glyf_outlines() && !glyf_refused_.count(&font_id))
+		if (const vgsdf_font *f = glyf_store(renderer, lane, face, counts)) {
+			*glyf = true;
+			return f;
+		}
+	return command_store(renderer, lane, face, counts);
+}
+
+bool FontManager::may_mix(const std::vector<Todo> &tasks, size_t g0, size_t g1) const
+{
+	const std::string *last = nullptr;
+	for (size_t t = g0; t < g1; t++) {
+		if (tasks[t].name == last)
+			continue;
+		last = tasks[t].name;
+		auto it = fonts().find(*last);
+		if (it == fonts().end() || glyf_refused_.count(&it->first))
+			continue;
+		for (const auto &file : it->second.files())
+			if (file->face().has_glyf_outlines())
+				return true;
+	}
+	return false;
+}
+
+const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font,
+                                               StoreKind kind, const FamilyTable **table, RenderTimings &counts, uint32_t *glyf_stores,
+                                               uint32_t *command_stores) const
+{
+	const bool commands = kind == StoreKind::Commands;
+	const int family_kind = kind == StoreKind::Mixed ? Renderer::kFamilyMixed : commands ? Renderer::kFamilyCommands : Renderer::kFamilyGlyf;
 	const bool on_device = family_tables_on_device_ && font.files().size() <= 0x10000;
 	const FamilyTable *ft = on_device ? nullptr : family_table(font_id, nullptr);
 	if (!ft && !on_device)
 		return nullptr;
 	std::vector<const vgsdf_font *> stores;
-	if (!commands)
+	if (kind == StoreKind::Glyf || (kind == StoreKind::Mixed && !glyf_refused_.count(&font_id)))
 		glyf_stores_batched(renderer, lane, font, counts);
 	for (const auto &file : font.files()) {
-		const vgsdf_font *f = commands ? command_store(renderer, lane, file->face(), counts)
-		                               : (file->face().has_glyf_outlines() ? glyf_store(renderer, lane, file->face(), counts) : nullptr);
+		bool glyf = kind == StoreKind::Glyf;
+		const vgsdf_font *f = kind == StoreKind::Mixed ? file_store(renderer, lane, font_id, file->face(), counts, &glyf)
+		                      : commands               ? command_store(renderer, lane, file->face(), counts)
+		                                               : (file->face().has_glyf_outlines() ? glyf_store(renderer, lane, file->face(), counts) : nullptr);
 		if (!f)
 			return nullptr;
 		stores.push_back(f);
+		if (uint32_t *n = glyf ? glyf_stores : command_stores)
+			++*n;
 	}
 	uint64_t uploaded = 0;
 	if (on_device) {
@@ -399,7 +443,7 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 		if (descs.size() == font.files().size()) {
 			int refused = 0;
 			bool built = false;
-			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, commands, &uploaded, &refused, &built);
+			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, family_kind, &uploaded, &refused, &built);
 			if (refused == 1)
 				counts.family_table_fallbacks++;
 			if (built) {
@@ -425,7 +469,7 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 			return nullptr;
 	}
 	const Renderer::FamilyArrays fa{ft->serial, &ft->code_point, &ft->font_of, &ft->glyph_id, &ft->advance, &ft->scale, &ft->shift_x};
-	const vgsdf_family *fam = renderer.family(lane, fa, stores, commands, &uploaded);
+	const vgsdf_family *fam = renderer.family(lane, fa, stores, family_kind, &uploaded);
 	if (fam)
 		count_upload(uploaded, counts.families_uploaded, counts.family_bytes);
 	if (table)
@@ -435,9 +479,10 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 
 // The group as code-point ranges of its font ids' resident families (vgsdf_outlines_submit_ranges): no glyph is touched — per
 // task two bisections of the family's code points; the device names the glyphs and, in place, writes their PBF entries.
-bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, bool commands)
+bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, StoreKind kind)
 {
 	const double t0 = now_s();
+	G.mixed_glyf_stores = G.mixed_command_stores = 0;
 	FeGroup::Ranges &R = G.ranges;
 	R.clear();
 	const size_t nb = G.g1 - G.g0;
@@ -450,7 +495,7 @@ bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, c
 			auto it = fonts().find(*tasks[t].name);
 			if (it == fonts().end() || R.families.size() >= 0xFFFF)
 				return false;
-			const vgsdf_family *fam = device_family(renderer, lane, it->first, it->second, commands, &ft, timings_);
+			const vgsdf_family *fam = device_family(renderer, lane, it->first, it->second, kind, &ft, timings_, &G.mixed_glyf_stores, &G.mixed_command_stores);
 			if (!fam)
 				return false;
 			last = tasks[t].name;
@@ -498,6 +543,8 @@ bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, c
 			}
 		}
 	}
+	if (kind == StoreKind::Mixed && G.mixed_glyf_stores == 0) // (nothing to mix: the command forms take the group)
+		return false;
 	task_g0[nb] = n_jobs;
 	R.task_r0.push_back((uint32_t)R.first.size());
 	G.task_g0 = std::move(task_g0);
@@ -527,7 +574,9 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 				}
 		}
 	// ... and the command stores the manager's mode would use: with 2 every face's, with 1 those of the fonts whose groups cannot
-	// take a glyf form (a file without `glyf` outlines, a font refused before)
+	// take a glyf form (a file without `glyf` outlines, a font refused before) — with mixed stores, of such a font the files alone
+	// that get no glyf store (file_store)
+	auto glyf_files_keep_glyf_stores = [this](const std::string &font_id) { return mixes() && !glyf_refused_.count(&font_id); };
 	if (resident_commands_)
 		for (size_t r = 0; r < renderer.n_devices(); r++)
 			for (const auto &kv : fonts()) {
@@ -536,23 +585,32 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 					wanted = wanted || !file->face().has_glyf_outlines();
 				if (wanted)
 					for (const auto &file : kv.second.files()) {
+						if (file->face().has_glyf_outlines() && glyf_files_keep_glyf_stores(kv.first))
+							continue;
 						RenderTimings counts;
 						(void)command_store(renderer.device_lane(r), 0, file->face(), counts);
 						uploaded += counts.command_font_bytes;
 						preload_counts_.add_uploads(counts);
 					}
 			}
-	// ... and the families over them, of the kinds of store the modes would name
+	// ... and the families over them, of the kinds of store the modes would name (with mixed stores a font id with a `glyf` file
+	// goes by its glyf or its mixed family, and gets no family over command stores of all its files)
 	if (resident_families_)
 		for (size_t r = 0; r < renderer.n_devices(); r++)
-			for (const auto &kv : fonts())
-				for (int commands = 0; commands < 2; commands++)
-					if (commands ? resident_commands_ != 0 : resident_fonts_) {
+			for (const auto &kv : fonts()) {
+				bool a_glyf_file = false;
+				for (const auto &file : kv.second.files())
+					a_glyf_file = a_glyf_file || file->face().has_glyf_outlines();
+				for (const StoreKind kind : {StoreKind::Glyf, StoreKind::Commands, StoreKind::Mixed})
+					if (kind == StoreKind::Mixed      ? mixes()
+					    : kind == StoreKind::Commands ? resident_commands_ != 0 && !(a_glyf_file && glyf_files_keep_glyf_stores(kv.first))
+					                                  : resident_fonts_) {
 						RenderTimings counts;
-						(void)device_family(renderer.device_lane(r), 0, kv.first, kv.second, commands != 0, nullptr, counts);
+						(void)device_family(renderer.device_lane(r), 0, kv.first, kv.second, kind, nullptr, counts);
 						uploaded += counts.family_bytes + counts.resident_font_bytes + counts.command_font_bytes;
 						preload_counts_.add_uploads(counts);
 					}
+			}
 	return uploaded;
 }
 
@@ -579,8 +637,13 @@ FontManager::FormList FontManager::fe_candidates(bool device_forms, bool glyf_fo
 				against_stores(false);
 			add(true, GroupForm::GlyfParts);
 		}
-		if (resident_commands_ == 1) // a group that took no glyf form
+		if (resident_commands_ == 1) { // a group that took no glyf form
+			if (glyf_forms && mixes()) { // ... against the store each of its files gets (fe_record: not for a group that is all `glyf`)
+				add(by_ranges, GroupForm::RangesMixed);
+				add(by_name, GroupForm::NamedMixed);
+			}
 			against_stores(true);
+		}
 	}
 	add(true, GroupForm::Packed); // the host's reader records whatever is left
 	return c;
@@ -592,26 +655,47 @@ void FontManager::fe_record(const std::vector<Todo> &tasks, FeGroup &G, bool all
 	const bool families = resident_families_ && (parent_ != nullptr || shard_world_ == 1) && renderer != nullptr;
 	const FormList forms = fe_candidates(allow_glyf, glyf_on_device_, renderer != nullptr, families);
 	int all_glyf = -1; // every glyph of the group comes from a `glyf` file of a font not refused; looked at when a glyf form's turn comes
+	int can_mix = -1;  // ... and, when a mixed form's turn comes, whether the group is one for them
+	auto group_all_glyf = [&] {
+		if (all_glyf < 0) {
+			all_glyf = 1;
+			for (size_t t = G.g0; t < G.g1 && all_glyf; t++)
+				all_glyf = tasks[t].block.all_glyf && !glyf_refused_.count(tasks[t].name);
+		}
+		return all_glyf != 0;
+	};
 	for (unsigned k = 0; k < forms.n; k++) {
 		G.form = forms.form[k];
 		if (G.form == GroupForm::RangesGlyf || G.form == GroupForm::NamedGlyf || G.form == GroupForm::GlyfParts) {
-			if (all_glyf < 0) {
-				all_glyf = 1;
-				for (size_t t = G.g0; t < G.g1 && all_glyf; t++)
-					all_glyf = tasks[t].block.all_glyf && !glyf_refused_.count(tasks[t].name);
-			}
+			(void)group_all_glyf();
 			if (!all_glyf)
+				continue;
+		}
+		if (G.form == GroupForm::RangesMixed || G.form == GroupForm::NamedMixed) {
+			// a group whose glyphs all come from `glyf` files has had its turn with the glyf forms; a group without a `glyf` file
+			// that could get a glyf store has nothing to mix
+			if (can_mix < 0)
+				can_mix = !group_all_glyf() && may_mix(tasks, G.g0, G.g1);
+			if (!can_mix)
 				continue;
 		}
 		switch (G.form) {
 		case GroupForm::RangesGlyf:
 		case GroupForm::RangesCommands:
-			if (fe_record_ranges(tasks, G, *renderer, lane, G.form == GroupForm::RangesCommands))
+		case GroupForm::RangesMixed:
+			if (fe_record_ranges(tasks, G, *renderer, lane,
+			                     G.form == GroupForm::RangesMixed      ? StoreKind::Mixed
+			                     : G.form == GroupForm::RangesCommands ? StoreKind::Commands
+			                                                           : StoreKind::Glyf))
 				return;
 			break;
 		case GroupForm::NamedGlyf:
 		case GroupForm::NamedCommands:
-			if (fe_record_named(tasks, G, *renderer, lane, G.form == GroupForm::NamedCommands))
+		case GroupForm::NamedMixed:
+			if (fe_record_named(tasks, G, *renderer, lane,
+			                    G.form == GroupForm::NamedMixed      ? StoreKind::Mixed
+			                    : G.form == GroupForm::NamedCommands ? StoreKind::Commands
+			                                                         : StoreKind::Glyf))
 				return;
 			break;
 		case GroupForm::GlyfParts:
@@ -936,6 +1020,17 @@ void FontManager::run_tasks_device_front_end(std::vector<Todo> &tasks, Writer &w
 				renderer.submit_outlines((int)(k & 1), G.m.view_resident(), G.out, &block);
 				timings_.command_groups++;
 				timings_.command_block_bytes += block;
+				break;
+			case GroupForm::RangesMixed: // (counted as mixed groups, and among no others)
+			case GroupForm::NamedMixed:
+				if (G.form == GroupForm::RangesMixed)
+					renderer.submit_ranges((int)(k & 1), G.ranges.view(G.in_place), G.n_jobs, G.out, &block);
+				else
+					renderer.submit_outlines((int)(k & 1), G.m.view_resident(), G.out, &block, true);
+				timings_.mixed_groups++;
+				timings_.mixed_glyf_fonts += G.mixed_glyf_stores;
+				timings_.mixed_command_fonts += G.mixed_command_stores;
+				timings_.mixed_block_bytes += block;
 				break;
 			case GroupForm::GlyfParts:
 				renderer.submit_outlines((int)(k & 1), G.m.view_glyf(), G.out);

@@ -403,6 +403,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->glyf_on_device_ = glyf_on_device_;
 		c->resident_fonts_ = resident_fonts_;
 		c->resident_commands_ = resident_commands_;
+		c->mixed_stores_ = mixed_stores_;
 		c->charstrings_on_device_ = charstrings_on_device_;
 		c->family_tables_on_device_ = family_tables_on_device_;
 		c->glyf_tables_on_device_ = glyf_tables_on_device_;

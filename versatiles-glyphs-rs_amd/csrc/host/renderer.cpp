@@ -437,9 +437,12 @@ void Renderer::submit_outlines(int lane, const vgsdf_outlines_glyf &v, HostBuffe
 	submit_on_lane(lane, v, out, vgsdf_outlines_submit_glyf, "vgsdf_outlines_submit_glyf");
 }
 
-void Renderer::submit_outlines(int lane, const vgsdf_outlines_resident &v, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const
+void Renderer::submit_outlines(int lane, const vgsdf_outlines_resident &v, HostBuffer<uint8_t> &out, uint64_t *block_bytes, bool mixed) const
 {
-	submit_on_lane(lane, v, out, vgsdf_outlines_submit_resident, "vgsdf_outlines_submit_resident", block_bytes);
+	if (mixed)
+		submit_on_lane(lane, v, out, vgsdf_outlines_submit_resident_mixed, "vgsdf_outlines_submit_resident_mixed", block_bytes);
+	else
+		submit_on_lane(lane, v, out, vgsdf_outlines_submit_resident, "vgsdf_outlines_submit_resident", block_bytes);
 }
 
 template <class Desc, class Made>
@@ -682,14 +685,14 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
-const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std::vector<const vgsdf_font *> &fonts, bool commands,
+const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std::vector<const vgsdf_font *> &fonts, int kind,
                                      uint64_t *uploaded_bytes) const
 {
 	if (mode_ != Mode::Hip)
 		return nullptr;
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
-	const auto key = std::make_tuple(device_, t.serial, commands);
+	const auto key = std::make_tuple(device_, t.serial, kind);
 	if (auto *found = rf.find(rf.families, key))
 		return found;
 	const uint64_t want = vgsdf::FamilyTableLayout(t.code_point->size()).bytes;
@@ -705,19 +708,20 @@ const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std:
 	d.advance = t.advance->data();
 	d.scale = t.scale->data();
 	d.shift_x = t.shift_x->data();
-	vgsdf_family *f = create_resident(lane, vgsdf_family_create, d, "vgsdf_family_create");
+	vgsdf_family *f = kind == kFamilyMixed ? create_resident(lane, vgsdf_family_create_mixed, d, "vgsdf_family_create_mixed")
+	                                       : create_resident(lane, vgsdf_family_create, d, "vgsdf_family_create");
 	return rf.keep(rf.families, key, f, vgsdf_family_device_bytes(f), uploaded_bytes);
 }
 
 const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
-                                                 const std::vector<const vgsdf_font *> &fonts, bool commands, uint64_t *uploaded_bytes, int *refused,
+                                                 const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
                                                  bool *built) const
 {
 	if (mode_ != Mode::Hip)
 		return nullptr;
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
-	const auto key = std::make_tuple(device_, serial, commands);
+	const auto key = std::make_tuple(device_, serial, kind);
 	if (auto *found = rf.find(rf.families, key))
 		return found;
 	if (rf.refused_family_tables.count(key)) {
@@ -732,7 +736,8 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 	vgsdf_family *f = nullptr;
 	{
 		std::lock_guard<std::mutex> lock(mu_);
-		if (tables.size() != fonts.size() || vgsdf_family_create_tables(c, &d, &f) != VGSDF_OK) {
+		if (tables.size() != fonts.size() ||
+		    (kind == kFamilyMixed ? vgsdf_family_create_tables_mixed(c, &d, &f) : vgsdf_family_create_tables(c, &d, &f)) != VGSDF_OK) {
 			rf.refused_family_tables.insert(key);
 			*refused = 1;
 			return nullptr;

@@ -451,7 +451,9 @@ public:
 	void submit_outlines(int lane, const vgsdf_outlines_packed &batch, HostBuffer<uint8_t> &out) const;
 	void submit_outlines(int lane, const vgsdf_outlines_glyf &batch, HostBuffer<uint8_t> &out) const;
 	// ... and for glyphs named by (font, glyph id) of resident fonts; *block_bytes: what the submission uploaded
-	void submit_outlines(int lane, const vgsdf_outlines_resident &batch, HostBuffer<uint8_t> &out, uint64_t *block_bytes = nullptr) const;
+	// (mixed: `batch.fonts` holds stores of both kinds — vgsdf_outlines_submit_resident_mixed)
+	void submit_outlines(int lane, const vgsdf_outlines_resident &batch, HostBuffer<uint8_t> &out, uint64_t *block_bytes = nullptr,
+	                     bool mixed = false) const;
 	// Resident fonts: the device copy of a face (vgsdf_font), one per (device, face), created on first use through the
 	// lane's context, shared by the two contexts of a lane and by the lanes of a multi-device renderer that share a device,
 	// freed with the renderer.  nullptr: the face has no resident form, or its copy would pass the budget of the device
@@ -506,14 +508,17 @@ public:
 		const std::vector<uint32_t> *advance;
 		const std::vector<double> *scale, *shift_x;
 	};
-	const vgsdf_family *family(int lane, const FamilyArrays &table, const std::vector<const vgsdf_font *> &fonts, bool commands,
+	// kind: kFamilyGlyf / kFamilyCommands — every font of `fonts` of that kind — or kFamilyMixed: fonts of either kind, the family
+	// made with the _mixed constructors (a third kind to the device, and a third key here)
+	static constexpr int kFamilyGlyf = 0, kFamilyCommands = 1, kFamilyMixed = 2;
+	const vgsdf_family *family(int lane, const FamilyArrays &table, const std::vector<const vgsdf_font *> &fonts, int kind,
 	                           uint64_t *uploaded_bytes = nullptr) const;
 	// the same family built by the DEVICE from the faces' cmap and hmtx tables (vgsdf_family_create_tables): same key (`serial`
 	// stands for the table's), same budget, same lifetime.  *refused: the device has returned an error for this (device, serial),
 	// 1 now or 2 earlier — the caller makes the family with family() instead; *built: this call put it on the device.  nullptr
 	// without *refused: over the budget
 	const vgsdf_family *family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
-	                                       const std::vector<const vgsdf_font *> &fonts, bool commands, uint64_t *uploaded_bytes, int *refused,
+	                                       const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
 	                                       bool *built) const;
 	// a family's code points and advances, read back (what a host that built no table names the glyphs of a ranges group by)
 	void family_names(int lane, const vgsdf_family *family, std::vector<uint16_t> &code_point, std::vector<uint32_t> &advance) const;
@@ -563,10 +568,10 @@ private:
 	struct ResidentFonts { // of a renderer and its peers
 		std::mutex mu;
 		std::map<std::pair<int, uint64_t>, vgsdf_font *> fonts; // (device, the face's serial number) -> its copy there
-		std::map<std::tuple<int, uint64_t, bool>, vgsdf_family *> families; // (device, table serial, command stores) -> the family
+		std::map<std::tuple<int, uint64_t, int>, vgsdf_family *> families; // (device, table serial, kind of stores) -> the family
 		std::map<int, uint64_t> bytes;                          // per device
 		std::set<std::pair<int, uint64_t>> refused_charstrings; // (device, serial): the device's decoder has refused the face
-		std::set<std::tuple<int, uint64_t, bool>> refused_family_tables; // the key of `families`: the device has refused to build the table
+		std::set<std::tuple<int, uint64_t, int>> refused_family_tables; // the key of `families`: the device has refused to build the table
 		std::map<std::pair<int, uint64_t>, uint64_t> unfit_charstrings; // (device, serial) -> bytes of a store that passed the budget
 		std::set<std::pair<int, uint64_t>> refused_glyf_tables;         // (device, serial): the device's table builder has refused the face
 		std::map<std::pair<int, uint64_t>, uint64_t> unfit_glyf_tables; // (device, serial) -> bytes of a font that passed the budget

@@ -27,13 +27,21 @@ int vgsdf_resident_expand(const void *src, void *dst, size_t block_bytes, uint32
 // (vgsdf::CommandFontRef records in the block) into cmds_out[n_cmds] / cmd_open[n_cmds] at the block's cmd_off
 int vgsdf_resident_gather(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_fonts,
                           bool with_pbf, vgsdf::OutlineCmd *cmds_out, uint8_t *cmd_open, hipStream_t stream);
-// upload of a vgsdf_outlines_ranges submission, against fonts of either kind: src = the block (upload_layout.h,
+// upload of a vgsdf_outlines_submit_resident_mixed submission, fonts of both kinds in one list: copies the block
+// (ResidentBlockLayout, its font references vgsdf::MixedFontRef records that say their kind) to dst, expands the leaves of the
+// glyphs of glyf fonts into parts_out[n_parts] and gathers the records and context bytes of the glyphs of command fonts into
+// cmds_out / cmd_open at the block's cmd_off; the slots of the glyf glyphs are left to the decoder
+int vgsdf_resident_mixed(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts, uint32_t n_fonts,
+                         bool with_pbf, void *parts_out, vgsdf::OutlineCmd *cmds_out, uint8_t *cmd_open, hipStream_t stream);
+// the kinds of font list an upload kernel of a named form is stamped for
+enum { VGSDF_FONTS_GLYF = 0, VGSDF_FONTS_COMMANDS = 1, VGSDF_FONTS_MIXED = 2 };
+// upload of a vgsdf_outlines_ranges submission, against fonts of either kind or (VGSDF_FONTS_MIXED: both arrays written) of both: src = the block (upload_layout.h,
 // RangesBlockLayout: n_tasks task records, n_families family records, n_fonts font references; device-readable as above),
 // dst = the device's copy in ResidentBlockLayout / CommandBlockLayout, whose per-glyph arrays and font references the kernel
 // WRITES; then the expansion into parts_out[n_parts] (glyf fonts) or the gather into cmds_out / cmd_open[n_cmds] (command
 // fonts).  names: vgsdf::EntryName[n_glyphs], written when with_pbf (for vgsdf_pbf_entries).  error_flag bit 5: an index of the
 // block that does not hold against these counts
-int vgsdf_family_upload(bool commands, const void *src, void *dst, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts, uint32_t n_fonts,
+int vgsdf_family_upload(int kind, const void *src, void *dst, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts, uint32_t n_fonts,
                         uint32_t n_tasks, uint32_t n_families, bool with_pbf, void *parts_out, vgsdf::OutlineCmd *cmds_out,
                         uint8_t *cmd_open, void *names, uint32_t *error_flag, hipStream_t stream);
 // upload by a kernel: src_mapped = device address of a page-locked, device-mapped host block (16-byte aligned), dst 16-byte aligned

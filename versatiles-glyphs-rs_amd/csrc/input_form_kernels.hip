@@ -174,6 +174,61 @@ __global__ __launch_bounds__(kExpandThreads) void resident_gather(const uint4 *_
 #include "resident_gather_records.inc"
 }
 
+// The upload of a submission that names its glyphs against fonts of BOTH kinds in one list (vgsdf_outlines_submit_resident_mixed):
+// the block is ResidentBlockLayout's, part_off standing still over a glyph of a command font and cmd_off running over the glyphs of
+// both kinds, and every font reference says its kind (upload_layout.h, MixedFontRef).  One launch of 256 glyphs per workgroup as
+// the two kernels above, one LDS cache of kExpandFontCache references, and BOTH second phases: the leaves of the workgroup's
+// glyf glyphs become parts, the records and context bytes of its command glyphs are gathered.  The gather's range
+// [cmd_off[g0], cmd_off[g0 + 256)) spans the slots of the workgroup's glyf glyphs as well: those it passes over — the decoder,
+// which runs behind this kernel over the parts, fills them.
+__global__ __launch_bounds__(kExpandThreads) void resident_mixed(const uint4 *__restrict__ src, uint4 *__restrict__ dst, uint32_t n16,
+                                                                 uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts, uint32_t n_fonts,
+                                                                 uint32_t cmd_off_at, uint32_t part_off_at, uint32_t glyph_id_at,
+                                                                 uint32_t font_of_at, uint32_t fonts_at, GlyfPart *__restrict__ parts_out,
+                                                                 uint32_t *__restrict__ cmds_out, uint8_t *__restrict__ open_out)
+{
+	__shared__ uint32_t s_part_off[kExpandThreads + 1], s_cmd_off[kExpandThreads + 1];
+	__shared__ uint16_t s_gid[kExpandThreads], s_font[kExpandThreads];
+	__shared__ const uint32_t *s_recs[kExpandThreads];
+	__shared__ const uint8_t *s_open[kExpandThreads];
+	__shared__ MixedFontRef s_fonts[kExpandFontCache];
+	const uint32_t t = threadIdx.x, i = blockIdx.x * kExpandThreads + t, g0 = blockIdx.x * kExpandThreads;
+	const uint8_t *const sb = reinterpret_cast<const uint8_t *>(src);
+	const MixedFontRef *const fonts = reinterpret_cast<const MixedFontRef *>(sb + fonts_at);
+	uint4 v = make_uint4(0, 0, 0, 0);
+	if (i < n16)
+		v = src[i];
+	const uint32_t ng = g0 < n_glyphs ? min(kExpandThreads, n_glyphs - g0) : 0u;
+	uint32_t gid = 0, f = 0;
+	if (ng) {
+		const uint32_t *part_off = reinterpret_cast<const uint32_t *>(sb + part_off_at) + g0;
+		const uint32_t *cmd_off = reinterpret_cast<const uint32_t *>(sb + cmd_off_at) + g0;
+		for (uint32_t k = t; k <= ng; k += kExpandThreads) {
+			s_part_off[k] = part_off[k];
+			s_cmd_off[k] = cmd_off[k];
+		}
+		if (t < ng) {
+			gid = reinterpret_cast<const uint16_t *>(sb + glyph_id_at)[g0 + t];
+			f = reinterpret_cast<const uint16_t *>(sb + font_of_at)[g0 + t];
+			s_gid[t] = (uint16_t)gid;
+			s_font[t] = (uint16_t)f;
+		}
+		for (uint32_t k = t; k < min(n_fonts, kExpandFontCache); k += kExpandThreads)
+			s_fonts[k] = fonts[k];
+	}
+	if (i < n16)
+		dst[i] = v;
+	if (ng == 0) // (uniform in the workgroup)
+		return;
+	__syncthreads();
+	{
+#include "resident_expand_leaves.inc"
+	}
+#define RESIDENT_GATHER_MIXED
+#include "resident_gather_records.inc"
+#undef RESIDENT_GATHER_MIXED
+}
+
 // The uploads of a submission that names code-point ranges of resident families: what the launch is given (the counts every
 // index of the block is bounded against, where the block's records lie, where the device's copy has its per-glyph arrays)
 constexpr uint32_t kFamilyCache = 64; // family records a workgroup keeps in LDS
@@ -188,6 +243,11 @@ struct FamilyLaunch {
 #define FAMILY_GLYF 0
 #include "family_upload_kernel.inc"
 #undef FAMILY_GLYF
+#define FAMILY_MIXED
+#define RESIDENT_GATHER_MIXED
+#include "family_upload_kernel.inc"
+#undef RESIDENT_GATHER_MIXED
+#undef FAMILY_MIXED
 
 } // namespace vgsdf
 
@@ -231,7 +291,21 @@ extern "C" int vgsdf_resident_expand(const void *src, void *dst, size_t block_by
 	return (int)hipGetLastError();
 }
 
-extern "C" int vgsdf_family_upload(bool commands, const void *src, void *dst, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts,
+extern "C" int vgsdf_resident_mixed(const void *src, void *dst, size_t block_bytes, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts,
+                                    uint32_t n_fonts, bool with_pbf, void *parts_out, OutlineCmd *cmds_out, uint8_t *cmd_open, hipStream_t stream)
+{
+	if (n_glyphs == 0)
+		return 0;
+	const ResidentBlockLayout rl(n_glyphs, n_fonts, with_pbf);
+	const uint32_t n16 = (uint32_t)((block_bytes + 15) / 16); // (the block and its device copy are padded to 16 bytes)
+	const uint32_t grid = (std::max(n16, n_glyphs) + kExpandThreads - 1u) / kExpandThreads;
+	hipLaunchKernelGGL(resident_mixed, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint4 *)src, (uint4 *)dst, n16, n_glyphs, n_cmds,
+	                   n_parts, n_fonts, (uint32_t)rl.cmd_off, (uint32_t)rl.part_off, (uint32_t)rl.glyph_id, (uint32_t)rl.font_of,
+	                   (uint32_t)rl.fonts, (GlyfPart *)parts_out, (uint32_t *)cmds_out, cmd_open);
+	return (int)hipGetLastError();
+}
+
+extern "C" int vgsdf_family_upload(int kind, const void *src, void *dst, uint32_t n_glyphs, uint32_t n_cmds, uint32_t n_parts,
                                    uint32_t n_fonts, uint32_t n_tasks, uint32_t n_families, bool with_pbf, void *parts_out,
                                    OutlineCmd *cmds_out, uint8_t *cmd_open, void *names, uint32_t *error_flag, hipStream_t stream)
 {
@@ -243,7 +317,7 @@ extern "C" int vgsdf_family_upload(bool commands, const void *src, void *dst, ui
 	L.with_pbf = with_pbf ? 1u : 0u;
 	L.families_at = (uint32_t)bl.families, L.fonts_at = (uint32_t)bl.fonts;
 	const uint32_t grid = (std::max(n_glyphs, 2u * n_fonts) + kExpandThreads - 1u) / kExpandThreads;
-	if (commands) {
+	if (kind == VGSDF_FONTS_COMMANDS) {
 		const CommandBlockLayout cl(n_glyphs, n_fonts, with_pbf);
 		L.d_scale = (uint32_t)cl.scale, L.d_shift_x = (uint32_t)cl.shift_x, L.d_cmd_off = (uint32_t)cl.cmd_off;
 		L.d_glyph_id = (uint32_t)cl.glyph_id, L.d_font_of = (uint32_t)cl.font_of, L.d_pbf_pre = (uint32_t)cl.pbf_pre;
@@ -255,8 +329,12 @@ extern "C" int vgsdf_family_upload(bool commands, const void *src, void *dst, ui
 		L.d_scale = (uint32_t)rl.scale, L.d_shift_x = (uint32_t)rl.shift_x, L.d_cmd_off = (uint32_t)rl.cmd_off, L.d_part_off = (uint32_t)rl.part_off;
 		L.d_glyph_id = (uint32_t)rl.glyph_id, L.d_font_of = (uint32_t)rl.font_of, L.d_pbf_pre = (uint32_t)rl.pbf_pre;
 		L.d_pbf_fix = (uint32_t)rl.pbf_fix, L.d_fonts = (uint32_t)rl.fonts;
-		hipLaunchKernelGGL(family_expand, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint8_t *)src, (uint8_t *)dst, L,
-		                   (GlyfPart *)parts_out, (EntryName *)names, error_flag);
+		if (kind == VGSDF_FONTS_MIXED)
+			hipLaunchKernelGGL(family_mixed, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint8_t *)src, (uint8_t *)dst, L,
+			                   (GlyfPart *)parts_out, (uint32_t *)cmds_out, cmd_open, (EntryName *)names, error_flag);
+		else
+			hipLaunchKernelGGL(family_expand, dim3(grid), dim3(kExpandThreads), 0, stream, (const uint8_t *)src, (uint8_t *)dst, L,
+			                   (GlyfPart *)parts_out, (EntryName *)names, error_flag);
 	}
 	return (int)hipGetLastError();
 }

@@ -186,6 +186,7 @@ enum class FeForm {
 	Glyf,             // the glyphs' `glyf` arrays as parts; cmd_off counts command SLOTS (vgsdf_outlines_glyf)
 	ResidentGlyf,     // glyphs named by (font, glyph id) of fonts from vgsdf_font_create: the upload kernel expands their leaves into parts
 	ResidentCommands, // ... of fonts from vgsdf_font_create_commands: the upload kernel gathers their records and context bytes
+	ResidentMixed,    // ... of fonts of both kinds in one list: the upload kernel does both, glyph by glyph, and the decoder runs over the parts
 };
 struct FeInput {
 	FeForm form = FeForm::Records;
@@ -211,9 +212,13 @@ struct FeInput {
 	const struct FeRanges *ranges = nullptr;
 
 	// the glyphs are named, not sent: the library validated the names, summed the offsets itself and gathered the block
-	bool names_glyphs() const { return form == FeForm::ResidentGlyf || form == FeForm::ResidentCommands; }
+	bool names_glyphs() const { return form == FeForm::ResidentGlyf || form == FeForm::ResidentCommands || form == FeForm::ResidentMixed; }
+	// ... and some of them have leaves that the upload kernel expands into parts behind the device's copy of the block
+	bool expands_leaves() const { return form == FeForm::ResidentGlyf || form == FeForm::ResidentMixed; }
+	// ... and some of them have records that the upload kernel gathers from their fonts' stores
+	bool gathers_records() const { return form == FeForm::ResidentCommands || form == FeForm::ResidentMixed; }
 	// the command records come out of the device's glyf decoder, which runs on parts
-	bool decodes_glyf() const { return form == FeForm::Glyf || form == FeForm::ResidentGlyf; }
+	bool decodes_glyf() const { return form == FeForm::Glyf || expands_leaves(); }
 	// the form may bring pbf_pre / pbf_fix
 	bool takes_pbf() const { return form != FeForm::Records; }
 };
@@ -354,6 +359,7 @@ static FeLayout fe_layout(const FeInput *in, uint32_t n_cmds, uint32_t n_floats)
 	case FeForm::Glyf:
 		return vgsdf::GlyfBlockLayout(n, in->n_parts, in->n_bytes, pbf);
 	case FeForm::ResidentGlyf:
+	case FeForm::ResidentMixed: // (the glyf form's block: a glyph of a command font has no parts)
 		return vgsdf::ResidentBlockLayout(n, in->n_fonts, pbf);
 	case FeForm::ResidentCommands:
 		return vgsdf::CommandBlockLayout(n, in->n_fonts, pbf);
@@ -377,6 +383,7 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 	bool single = false;
 	switch (in->form) {
 	case FeForm::ResidentGlyf:
+	case FeForm::ResidentMixed:
 	case FeForm::ResidentCommands: // (gathered by the library itself, in the context's page-locked staging buffer)
 		single = true;
 		break;
@@ -405,7 +412,7 @@ static FeUpload fe_upload_form(const FeInput *in, uint32_t n_cmds, uint32_t n_fl
 	// per-glyph arrays alone where commands or kinds / coords arrive one by one and have buffers of their own
 	const bool arrays_only = in->form == FeForm::Records || (in->form == FeForm::Packed && !up.block);
 	up.meta_bytes = arrays_only ? up.arrays_bytes : layout_bytes;
-	if (in->form == FeForm::ResidentGlyf)
+	if (in->expands_leaves())
 		up.meta_bytes += sizeof(vgsdf_glyf_part) * (size_t)in->n_parts;
 	return up;
 }
@@ -497,13 +504,14 @@ static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n
 	};
 	if (in->ranges) { // ONE kernel: it names the glyphs from the families' tables, then expands / gathers as the cases below
 		const bool commands = in->form == FeForm::ResidentCommands;
+		const int kind = commands ? VGSDF_FONTS_COMMANDS : in->form == FeForm::ResidentMixed ? VGSDF_FONTS_MIXED : VGSDF_FONTS_GLYF;
 		const void *src = nullptr;
 		if (int rc = fe_kernel_readable_block(ctx, fe, up, src); rc != VGSDF_OK)
 			return rc;
 		// (the device's copy is laid out as that of the form that names its glyphs one by one)
 		const size_t fonts_at = commands ? std::get<vgsdf::CommandBlockLayout>(up.layout).fonts : std::get<vgsdf::ResidentBlockLayout>(up.layout).fonts;
 		const size_t parts_at = commands ? 0 : std::get<vgsdf::ResidentBlockLayout>(up.layout).bytes;
-		FE_KERNEL(vgsdf_family_upload(commands, src, dm, (uint32_t)n, n_cmds, in->n_parts, in->n_fonts, in->ranges->n_live, in->ranges->n_families,
+		FE_KERNEL(vgsdf_family_upload(kind, src, dm, (uint32_t)n, n_cmds, in->n_parts, in->n_fonts, in->ranges->n_live, in->ranges->n_families,
 		                              pbf, dm + parts_at, (vgsdf::OutlineCmd *)fe.cmds.p, (uint8_t *)fe.cmd_open.p, const_cast<void *>(p.d_names),
 		                              fe.flag_word(), st));
 		if (!commands) {
@@ -521,6 +529,19 @@ static int fe_upload(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, uint32_t n
 		FE_KERNEL(vgsdf_resident_expand(src, dm, rs.bytes, (uint32_t)n, in->n_parts, in->n_fonts, pbf, dm + rs.bytes, st));
 		up.d_parts = dm + rs.bytes;
 		up.d_bytes = dm + rs.fonts; // (the fonts' stores: vgsdf_glyf_decode_resident)
+		fe.resident_upload_bytes = rs.bytes;
+		break;
+	}
+	case FeForm::ResidentMixed: { // ONE kernel here too: the copy of the block, the expansion for the glyphs of glyf fonts and the
+		                          // gather for those of command fonts
+		const auto &rs = std::get<vgsdf::ResidentBlockLayout>(up.layout);
+		const void *src = nullptr;
+		if (int rc = fe_kernel_readable_block(ctx, fe, up, src); rc != VGSDF_OK)
+			return rc;
+		FE_KERNEL(vgsdf_resident_mixed(src, dm, rs.bytes, (uint32_t)n, n_cmds, in->n_parts, in->n_fonts, pbf, dm + rs.bytes,
+		                               (vgsdf::OutlineCmd *)fe.cmds.p, (uint8_t *)fe.cmd_open.p, st));
+		up.d_parts = dm + rs.bytes;
+		up.d_bytes = dm + rs.fonts; // (the decoder follows a part's font index: parts name glyf fonts only)
 		fe.resident_upload_bytes = rs.bytes;
 		break;
 	}
@@ -631,8 +652,12 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 		decode_makes_context = false;
 	// command fonts: the gathered context bytes are the context pass's own for positive finite scales; a batch with an odd scale
 	// takes the pass over the gathered records, as the glyf form does
-	const bool gather_makes_context = in->form == FeForm::ResidentCommands && facts.scales_plain;
-	if (in->form == FeForm::ResidentGlyf)
+	const bool gather_makes_context = in->gathers_records() && facts.scales_plain;
+	// fonts of both kinds: the decoder writes the bytes of its parts' slots and the gather has copied those of its records, so no
+	// pass runs when BOTH hold; otherwise the pass runs over the whole batch
+	const bool context_made = in->form == FeForm::ResidentMixed ? decode_makes_context && gather_makes_context
+	                                                           : decode_makes_context || gather_makes_context;
+	if (in->expands_leaves())
 		FE_KERNEL(vgsdf_glyf_decode_resident(up.d_parts, in->n_parts, up.d_bytes, (vgsdf::OutlineCmd *)fe.cmds.p, flagw, facts.glyf_max_cap,
 		                                     facts.glyf_max_len, decode_makes_context ? (uint8_t *)fe.cmd_open.p : nullptr, st));
 	else if (in->form == FeForm::Glyf)
@@ -641,7 +666,7 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	if (in->form == FeForm::Packed)
 		FE_KERNEL(vgsdf_outline_context_packed(up.d_kinds, up.d_coords, up.d_dat_off, d.cmd_off, d.scale, n, (vgsdf::OutlineCmd *)fe.cmds.p,
 		                                       (uint8_t *)fe.cmd_open.p, flagw, st));
-	else if (!decode_makes_context && !gather_makes_context)
+	else if (!context_made)
 		FE_KERNEL(vgsdf_outline_context(d.cmds, d.cmd_off, d.scale, n, (uint8_t *)fe.cmd_open.p, flagw, st));
 	FE_KERNEL(vgsdf_outline_count(d.cmds, (const uint8_t *)fe.cmd_open.p, n_cmds, d.cmd_off, n, d.scale, d.shift,
 	                              (uint32_t *)fe.counts.p, fe.cmd_box.p, (unsigned long long *)fe.cmd_mask.p, flagw, st));
@@ -951,9 +976,12 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 
 // The block of a submission that names its glyphs, gathered in the context's page-locked staging buffer in the layout of
 // its kind of font: the caller's arrays, the running sum(s), the fonts' device addresses.  Points `f` into it
-template <class Layout> static int fe_gather_named(vgsdf_ctx *ctx, FrontEnd &fe, const vgsdf_outlines_resident *in, FeInput &f)
+// Mixed: fonts of both kinds in the list (ResidentBlockLayout): per glyph the slots of either kind, leaves of the glyf kind alone
+template <class Layout, bool Mixed = false>
+static int fe_gather_named(vgsdf_ctx *ctx, FrontEnd &fe, const vgsdf_outlines_resident *in, FeInput &f)
 {
 	constexpr bool glyf = std::is_same_v<Layout, vgsdf::ResidentBlockLayout>; // (else: command fonts, CommandBlockLayout)
+	static_assert(glyf || !Mixed, "a list of both kinds takes the glyf form's block");
 	const uint32_t n = in->n_glyphs;
 	const bool pbf = in->pbf_fix != nullptr;
 	const Layout at(n, in->n_fonts, pbf);
@@ -981,17 +1009,30 @@ template <class Layout> static int fe_gather_named(vgsdf_ctx *ctx, FrontEnd &fe,
 		cmds += ft.slots[id];
 		if constexpr (glyf) {
 			part_off[g] = (uint32_t)parts;
-			parts += ft.leaf_off[id + 1] - ft.leaf_off[id];
+			if (!Mixed || !ft.commands)
+				parts += ft.leaf_off[id + 1] - ft.leaf_off[id];
 		}
 		if (cmds > 0x7FFFFFFFull) {
-			ctx->err = glyf ? "vgsdf_outlines_resident: more than 2^31 - 1 command slots in one submission; split it"
+			ctx->err = Mixed  ? "vgsdf_outlines_resident_mixed: more than 2^31 - 1 command slots and commands in one submission; split it"
+			           : glyf ? "vgsdf_outlines_resident: more than 2^31 - 1 command slots in one submission; split it"
 			                : "vgsdf_outlines_resident: more than 2^31 - 1 commands in one submission; split it";
 			return VGSDF_E_ARG;
 		}
 		f.res_scales_plain = f.res_scales_plain && in->scale[g] > 0.0 && in->scale[g] < HUGE_VAL;
 	}
 	cmd_off[n] = (uint32_t)cmds;
-	if constexpr (glyf) {
+	if constexpr (Mixed) {
+		part_off[n] = (uint32_t)parts;
+		vgsdf::MixedFontRef *refs = (vgsdf::MixedFontRef *)(hb + at.fonts);
+		for (uint32_t k = 0; k < in->n_fonts; k++) {
+			const vgsdf_font &ft = *in->fonts[k];
+			refs[k] = mixed_font_ref(ft);
+			if (!ft.commands) { // (the decoder's LDS: from the fonts it reads)
+				f.res_max_cap = std::max(f.res_max_cap, ft.max_cap);
+				f.res_max_len = std::max(f.res_max_len, ft.max_len);
+			}
+		}
+	} else if constexpr (glyf) {
 		part_off[n] = (uint32_t)parts;
 		vgsdf::ResidentFontRef *refs = (vgsdf::ResidentFontRef *)(hb + at.fonts);
 		for (uint32_t k = 0; k < in->n_fonts; k++) {
@@ -1004,7 +1045,7 @@ template <class Layout> static int fe_gather_named(vgsdf_ctx *ctx, FrontEnd &fe,
 		for (uint32_t k = 0; k < in->n_fonts; k++)
 			refs[k] = in->fonts[k]->cref;
 	}
-	f.form = glyf ? FeForm::ResidentGlyf : FeForm::ResidentCommands;
+	f.form = Mixed ? FeForm::ResidentMixed : glyf ? FeForm::ResidentGlyf : FeForm::ResidentCommands;
 	f.cmd_off = cmd_off;
 	f.scale = (const double *)(hb + at.scale);
 	f.shift_x = (const double *)(hb + at.shift_x);
@@ -1095,7 +1136,8 @@ int vgsdf_outlines_submit_glyf(vgsdf_ctx *ctx, const vgsdf_outlines_glyf *in, ui
 
 uint64_t vgsdf_outlines_resident_upload_bytes(const vgsdf_ctx *ctx) { return ctx && ctx->fe ? ctx->fe->resident_upload_bytes : 0; }
 
-int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity)
+// both entry points of the form; mixed: fonts of both kinds may stand in the list (vgsdf_outlines_submit_resident_mixed)
+static int fe_submit_named(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity, bool mixed)
 {
 	if (!ctx)
 		return VGSDF_E_ARG;
@@ -1109,7 +1151,7 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 	}
 	const uint32_t n = in->n_glyphs;
 	FeInput f;
-	f.form = FeForm::ResidentGlyf;
+	f.form = mixed ? FeForm::ResidentMixed : FeForm::ResidentGlyf;
 	f.n_glyphs = n;
 	if (n == 0)
 		return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
@@ -1123,7 +1165,7 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 			return VGSDF_E_ARG;
 		}
 	const bool commands = in->fonts[0]->commands;
-	for (uint32_t k = 1; k < in->n_fonts; k++)
+	for (uint32_t k = 1; k < in->n_fonts && !mixed; k++)
 		if (in->fonts[k]->commands != commands) {
 			ctx->err = "vgsdf_outlines_resident: fonts of both kinds (vgsdf_font_create and vgsdf_font_create_commands) in one submission";
 			return VGSDF_E_ARG;
@@ -1137,10 +1179,22 @@ int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident
 	FrontEnd *fe = nullptr; // (pending: its upload kernel may still be reading the staging block)
 	if (int rc = fe_acquire(ctx, fe); rc != VGSDF_OK)
 		return rc;
-	if (int rc = commands ? fe_gather_named<vgsdf::CommandBlockLayout>(ctx, *fe, in, f) : fe_gather_named<vgsdf::ResidentBlockLayout>(ctx, *fe, in, f);
+	if (int rc = mixed      ? fe_gather_named<vgsdf::ResidentBlockLayout, true>(ctx, *fe, in, f)
+	             : commands ? fe_gather_named<vgsdf::CommandBlockLayout>(ctx, *fe, in, f)
+	                        : fe_gather_named<vgsdf::ResidentBlockLayout>(ctx, *fe, in, f);
 	    rc != VGSDF_OK)
 		return rc;
 	return fe_submit(ctx, &f, out_bitmaps, out_bitmaps ? out_capacity : 0);
+}
+
+int vgsdf_outlines_submit_resident(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity)
+{
+	return fe_submit_named(ctx, in, out_bitmaps, out_capacity, false);
+}
+
+int vgsdf_outlines_submit_resident_mixed(vgsdf_ctx *ctx, const vgsdf_outlines_resident *in, uint8_t *out_bitmaps, size_t out_capacity)
+{
+	return fe_submit_named(ctx, in, out_bitmaps, out_capacity, true);
 }
 
 // ---- code-point ranges of resident families (resident_fonts.cpp, vgsdf_family_create) ----
@@ -1162,9 +1216,9 @@ int vgsdf_outlines_submit_ranges(vgsdf_ctx *ctx, const vgsdf_outlines_ranges *in
 	bool scales_plain = true;
 	for (uint32_t k = 0; k < in->n_families; k++) {
 		const vgsdf_family *fm = in->families[k];
-		if (!fm || fm->device != ctx->device || fm->commands != in->families[0]->commands) {
-			ctx->err = "vgsdf_outlines_ranges: a NULL family, a family of another device than the context's, or families of both kinds "
-			           "(vgsdf_font_create and vgsdf_font_create_commands) in one submission";
+		if (!fm || fm->device != ctx->device || fm->commands != in->families[0]->commands || fm->mixed != in->families[0]->mixed) {
+			ctx->err = "vgsdf_outlines_ranges: a NULL family, a family of another device than the context's, or families of more than one "
+			           "kind (over fonts from vgsdf_font_create, from vgsdf_font_create_commands, mixed) in one submission";
 			return VGSDF_E_ARG;
 		}
 		n_fonts += fm->fonts.size();
@@ -1182,6 +1236,7 @@ int vgsdf_outlines_submit_ranges(vgsdf_ctx *ctx, const vgsdf_outlines_ranges *in
 			return VGSDF_E_ARG;
 		}
 	const bool commands = in->n_families ? in->families[0]->commands : false;
+	const bool mixed = in->n_families ? in->families[0]->mixed : false; // (a third kind: its font lists hold both, reference by reference)
 	const bool pbf = in->pbf_pre != nullptr;
 	FrontEnd *fe = nullptr; // (pending: its upload kernel may still be reading the staging block)
 	if (int rc = fe_acquire(ctx, fe); rc != VGSDF_OK)
@@ -1237,7 +1292,9 @@ int vgsdf_outlines_submit_ranges(vgsdf_ctx *ctx, const vgsdf_outlines_ranges *in
 		r.n_fonts = (uint32_t)fm.fonts.size();
 		frefs[k] = r;
 		for (const vgsdf_font *ft : fm.fonts) { // (both references are 32 bytes)
-			if (commands)
+			if (mixed)
+				((vgsdf::MixedFontRef *)(hb + at.fonts))[font_base++] = mixed_font_ref(*ft);
+			else if (commands)
 				((vgsdf::CommandFontRef *)(hb + at.fonts))[font_base++] = ft->cref;
 			else
 				((vgsdf::ResidentFontRef *)(hb + at.fonts))[font_base++] = ft->ref;
@@ -1246,7 +1303,7 @@ int vgsdf_outlines_submit_ranges(vgsdf_ctx *ctx, const vgsdf_outlines_ranges *in
 	rg.block = hb;
 	rg.block_bytes = at.bytes;
 	FeInput f;
-	f.form = commands ? FeForm::ResidentCommands : FeForm::ResidentGlyf;
+	f.form = mixed ? FeForm::ResidentMixed : commands ? FeForm::ResidentCommands : FeForm::ResidentGlyf;
 	f.n_glyphs = (uint32_t)glyphs;
 	f.n_parts = (uint32_t)parts;
 	f.n_fonts = (uint32_t)n_fonts;

@@ -12,58 +12,60 @@
 #include "resident_build.h"
 
 namespace {
-// font k of a family: there, on the context's device and of the kind of font 0
-bool family_font_fits(const vgsdf_ctx *ctx, const vgsdf_font *const *fonts, uint32_t k)
+// font k of a family: there, on the context's device and of the kind of font 0 (a mixed family: of either kind)
+bool family_font_fits(const vgsdf_ctx *ctx, const vgsdf_font *const *fonts, uint32_t k, bool mixed)
 {
-	return fonts[k] && fonts[k]->device == ctx->device && fonts[k]->commands == fonts[0]->commands;
+	return fonts[k] && fonts[k]->device == ctx->device && (mixed || (fonts[0] && fonts[k]->commands == fonts[0]->commands));
 }
 // what a family keeps of its (checked) fonts
-void adopt_fonts(vgsdf_family &f, const vgsdf_ctx *ctx, const vgsdf_font *const *fonts, uint32_t n_fonts)
+void adopt_fonts(vgsdf_family &f, const vgsdf_ctx *ctx, const vgsdf_font *const *fonts, uint32_t n_fonts, bool mixed)
 {
 	f.device = ctx->device;
-	f.commands = fonts[0]->commands;
+	f.mixed = mixed;
+	f.commands = !mixed && fonts[0]->commands;
 	f.fonts.assign(fonts, fonts + n_fonts);
-	for (const vgsdf_font *ft : f.fonts) {
-		f.max_cap = std::max(f.max_cap, ft->max_cap);
-		f.max_len = std::max(f.max_len, ft->max_len);
-	}
+	for (const vgsdf_font *ft : f.fonts)
+		if (!ft->commands) { // (what the decoder's LDS is sized from: the leaves of glyf fonts)
+			f.max_cap = std::max(f.max_cap, ft->max_cap);
+			f.max_len = std::max(f.max_len, ft->max_len);
+		}
 }
-} // namespace
+const char *const kFontsRefused[2] = {"a NULL font, a font of another device than the context's, or fonts of both kinds",
+                                      "a NULL font, or a font of another device than the context's"};
 
-extern "C" {
-
-int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out)
+// vgsdf_family_create and vgsdf_family_create_mixed: `me` names the call in its messages
+int family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out, bool mixed, const char *me)
 {
 	if (!ctx)
 		return VGSDF_E_ARG;
 	if (!in || !out || !in->fonts ||
 	    (in->n_entries && (!in->code_point || !in->font_of || !in->glyph_id || !in->advance || !in->scale || !in->shift_x))) {
-		ctx->err = "vgsdf_family_create: NULL argument";
+		ctx->err = std::string(me) + ": NULL argument";
 		return VGSDF_E_ARG;
 	}
 	*out = nullptr;
 	const uint32_t n = in->n_entries;
 	if (in->n_fonts == 0 || in->n_fonts > 0x10000u || n > 0x10000u) {
-		ctx->err = "vgsdf_family_create: n_fonts must be 1 .. 65536 and n_entries at most 65536";
+		ctx->err = std::string(me) + ": n_fonts must be 1 .. 65536 and n_entries at most 65536";
 		return VGSDF_E_ARG;
 	}
 	for (uint32_t k = 0; k < in->n_fonts; k++)
-		if (!family_font_fits(ctx, in->fonts, k)) {
-			ctx->err = "vgsdf_family_create: a NULL font, a font of another device than the context's, or fonts of both kinds";
+		if (!family_font_fits(ctx, in->fonts, k, mixed)) {
+			ctx->err = std::string(me) + ": " + kFontsRefused[mixed];
 			return VGSDF_E_ARG;
 		}
 	for (uint32_t i = 0; i < n; i++)
 		if ((i && in->code_point[i] <= in->code_point[i - 1]) || in->font_of[i] >= in->n_fonts ||
 		    in->glyph_id[i] >= in->fonts[in->font_of[i]]->n_glyph_ids) {
-			ctx->err = "vgsdf_family_create: code points not strictly ascending, font_of past n_fonts, or a glyph id past its face";
+			ctx->err = std::string(me) + ": code points not strictly ascending, font_of past n_fonts, or a glyph id past its face";
 			return VGSDF_E_ARG;
 		}
 	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
 	if (!f) {
-		ctx->err = "vgsdf_family_create: out of host memory";
+		ctx->err = std::string(me) + ": out of host memory";
 		return VGSDF_E_OOM;
 	}
-	adopt_fonts(*f, ctx, in->fonts, in->n_fonts);
+	adopt_fonts(*f, ctx, in->fonts, in->n_fonts, mixed);
 	f->code_point.assign(in->code_point, in->code_point + n);
 	f->font_of.assign(in->font_of, in->font_of + n);
 	f->glyph_id.assign(in->glyph_id, in->glyph_id + n);
@@ -98,29 +100,30 @@ int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_famil
 	std::memcpy(h.data() + at.pbf_fix, f->pbf_fix.data(), n);
 	(void)hipSetDevice(ctx->device);
 	if (hipError_t e = f->table.ensure(h.size()); e != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_family_create", "hipMalloc", e);
+		return font_hip_error(ctx, me, "hipMalloc", e);
 	Calls q(ctx->stream);
 	q.copy(f->table.p, h.data(), h.size());
 	q.sync();
 	if (q.failed())
-		return font_hip_error(ctx, "vgsdf_family_create", "upload", q.e);
+		return font_hip_error(ctx, me, "upload", q.e);
 	*out = f.release();
 	return VGSDF_OK;
 }
 
-int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out)
+// vgsdf_family_create_tables and vgsdf_family_create_tables_mixed (the kernels take the kind face by face: FamilyFaceRef::commands)
+int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out, bool mixed, const char *me)
 {
 	if (!ctx)
 		return VGSDF_E_ARG;
 	if (!in || !out || !in->fonts || !in->tables) {
-		ctx->err = "vgsdf_family_create_tables: NULL argument";
+		ctx->err = std::string(me) + ": NULL argument";
 		return VGSDF_E_ARG;
 	}
 	*out = nullptr;
 	ctx->family_tables_ms[0] = ctx->family_tables_ms[1] = 0.0f;
 	const uint32_t n_fonts = in->n_fonts;
 	if (n_fonts == 0 || n_fonts > 0x10000u) {
-		ctx->err = "vgsdf_family_create_tables: n_fonts must be 1 .. 65536";
+		ctx->err = std::string(me) + ": n_fonts must be 1 .. 65536";
 		return VGSDF_E_ARG;
 	}
 	// what can be said without a lookup; the staging block's layout on the way:
@@ -128,22 +131,22 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	size_t n_subtables = 0, table_bytes = 0;
 	for (uint32_t k = 0; k < n_fonts; k++) {
 		const vgsdf_face_tables &t = in->tables[k];
-		if (!family_font_fits(ctx, in->fonts, k)) {
-			ctx->err = "vgsdf_family_create_tables: a NULL font, a font of another device than the context's, or fonts of both kinds";
+		if (!family_font_fits(ctx, in->fonts, k, mixed)) {
+			ctx->err = std::string(me) + ": " + kFontsRefused[mixed];
 			return VGSDF_E_ARG;
 		}
 		if ((t.cmap_len && !t.cmap) || (t.hmtx_len && !t.hmtx) || (t.n_subtables && (!t.subtable_off || !t.subtable_format))) {
-			ctx->err = "vgsdf_family_create_tables: a NULL table or subtable array of a length that is not 0";
+			ctx->err = std::string(me) + ": a NULL table or subtable array of a length that is not 0";
 			return VGSDF_E_ARG;
 		}
 		if (t.units_per_em < 16 || t.units_per_em > 16384) {
-			ctx->err = "vgsdf_family_create_tables: units_per_em not 16 .. 16384";
+			ctx->err = std::string(me) + ": units_per_em not 16 .. 16384";
 			return VGSDF_E_ARG;
 		}
 		for (uint32_t s = 0; s < t.n_subtables; s++) {
 			const uint16_t fm = t.subtable_format[s];
 			if (t.subtable_off[s] >= t.cmap_len || !(fm == 0 || fm == 4 || fm == 6 || fm == 10 || fm == 12 || fm == 13)) {
-				ctx->err = "vgsdf_family_create_tables: a subtable offset at or past cmap_len, or a format that is not 0, 4, 6, 10, 12 or 13";
+				ctx->err = std::string(me) + ": a subtable offset at or past cmap_len, or a format that is not 0, 4, 6, 10, 12 or 13";
 				return VGSDF_E_ARG;
 			}
 		}
@@ -152,10 +155,10 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	}
 	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
 	if (!f) {
-		ctx->err = "vgsdf_family_create_tables: out of host memory";
+		ctx->err = std::string(me) + ": out of host memory";
 		return VGSDF_E_OOM;
 	}
-	adopt_fonts(*f, ctx, in->fonts, n_fonts);
+	adopt_fonts(*f, ctx, in->fonts, n_fonts, mixed);
 	const size_t a_subs = sizeof(vgsdf::FamilyFaceRef) * (size_t)n_fonts, a_bytes = a_subs + sizeof(vgsdf::FamilySubtable) * n_subtables,
 	             a_counts = align_up(a_bytes + table_bytes, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
 	             a_total = a_flags + 16;
@@ -163,7 +166,7 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	hipStream_t st = ctx->stream;
 	ScratchBuf dev;
 	if (hipError_t e = dev.ensure(a_total); e != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipMalloc", e);
+		return font_hip_error(ctx, me, "hipMalloc", e);
 	uint8_t *d = (uint8_t *)dev.p;
 	std::vector<uint8_t> h(a_counts, 0);
 	{
@@ -195,7 +198,7 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	}
 	PassEvents ev;
 	if (hipError_t err = ev.create(); err != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipEventCreate", err);
+		return font_hip_error(ctx, me, "hipEventCreate", err);
 	const vgsdf::FamilyFaceRef *faces = (const vgsdf::FamilyFaceRef *)d;
 	uint32_t *counts = (uint32_t *)(d + a_counts), *flags = (uint32_t *)(d + a_flags);
 	Calls q(st);
@@ -208,10 +211,10 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	q.read_back(got, counts, sizeof got);
 	q.sync();
 	if (q.failed())
-		return font_hip_error(ctx, "vgsdf_family_create_tables", "count pass", q.e);
+		return font_hip_error(ctx, me, "count pass", q.e);
 	ev.elapsed(ctx->family_tables_ms, 0);
 	if (got[vgsdf::kFamilyCounts * vgsdf::kFamilyGroups]) {
-		ctx->err = "vgsdf_family_create_tables: a glyph id past its face";
+		ctx->err = std::string(me) + ": a glyph id past its face";
 		return VGSDF_E_ARG;
 	}
 	uint32_t n = 0;
@@ -220,7 +223,7 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	// the table as vgsdf_family_create allocates it (the same size: the same vgsdf_family_device_bytes)
 	const vgsdf::FamilyTableLayout at(n);
 	if (hipError_t err = f->table.ensure(at.bytes + 16); err != hipSuccess)
-		return font_hip_error(ctx, "vgsdf_family_create_tables", "hipMalloc", err);
+		return font_hip_error(ctx, me, "hipMalloc", err);
 	std::vector<uint8_t> back(at.bytes);
 	q.record(ev.at[1]);
 	q.launch([&] { return vgsdf_family_tables_emit(faces, n_fonts, counts, n, (uint8_t *)f->table.p, st); });
@@ -228,7 +231,7 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	q.read_back(back.data(), f->table.p, at.bytes);
 	q.sync();
 	if (q.failed())
-		return font_hip_error(ctx, "vgsdf_family_create_tables", "emit pass", q.e);
+		return font_hip_error(ctx, me, "emit pass", q.e);
 	ev.elapsed(ctx->family_tables_ms, 1);
 	// the host's copy from the one read-back; the 64-bit running sums from the table's differences (exact: a glyph holds fewer
 	// than 2^31 slots and fewer than 2^32 leaves)
@@ -249,6 +252,27 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 	// (scales_plain stays true: every scale is 24 / units_per_em of a checked units_per_em)
 	*out = f.release();
 	return VGSDF_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int vgsdf_family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out)
+{
+	return family_create(ctx, in, out, false, "vgsdf_family_create");
+}
+int vgsdf_family_create_mixed(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out)
+{
+	return family_create(ctx, in, out, true, "vgsdf_family_create_mixed");
+}
+int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out)
+{
+	return family_create_tables(ctx, in, out, false, "vgsdf_family_create_tables");
+}
+int vgsdf_family_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out)
+{
+	return family_create_tables(ctx, in, out, true, "vgsdf_family_create_tables_mixed");
 }
 
 void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]) { pass_ms_out(ctx ? ctx->family_tables_ms : nullptr, ms); }

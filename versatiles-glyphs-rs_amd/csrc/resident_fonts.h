@@ -27,14 +27,22 @@ struct vgsdf_font {
 	~vgsdf_font() { store.release(); } // (the owner has made the font's device current)
 };
 
+// a font's reference in a list that holds fonts of both kinds (upload_layout.h): its three addresses and its kind
+inline vgsdf::MixedFontRef mixed_font_ref(const vgsdf_font &ft)
+{
+	return ft.commands ? vgsdf::MixedFontRef{ft.cref.cmd_off, ft.cref.cmds, ft.cref.open, vgsdf::kFontRefCommands}
+	                   : vgsdf::MixedFontRef{ft.ref.leaf_off, ft.ref.leaves, ft.ref.bytes, vgsdf::kFontRefGlyf};
+}
+
 // vgsdf_family_create: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id, on the host (what a
 // ranges submission is laid out from in O(tasks)) and on the device (upload_layout.h, FamilyTableLayout: what its upload
 // kernel names the glyphs from).  Owns no font
 struct vgsdf_family {
 	int device = 0;
 	bool commands = false;    // the kind of its fonts
+	bool mixed = false;       // a third kind (vgsdf_family_create_mixed): fonts of either kind, font by font; `commands` stays false
 	bool scales_plain = true; // every scale positive and finite
-	uint32_t max_cap = 0, max_len = 0; // over its fonts (vgsdf_font)
+	uint32_t max_cap = 0, max_len = 0; // over its fonts (vgsdf_font); a mixed family: over its glyf fonts
 	std::vector<const vgsdf_font *> fonts;
 	std::vector<uint16_t> code_point, font_of, glyph_id;
 	std::vector<uint32_t> advance;

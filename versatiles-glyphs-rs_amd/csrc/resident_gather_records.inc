@@ -2,11 +2,22 @@
 // a submission's command arrays, stamped into resident_gather (glyphs named one by one) and family_gather (code-point ranges of
 // families): input_form_kernels.hip.  Expects, in the including kernel: t, ng, n_cmds, cmds_out, open_out, `fonts`, lane t's glyph id
 // and font index in gid / f, the LDS arrays s_recs / s_open, and — complete behind a barrier — s_cmd_off[0 .. ng] and s_fonts.
+// With RESIDENT_GATHER_MIXED defined (resident_mixed, family_mixed) the list holds fonts of both kinds: a glyph of a glyf font
+// leaves no source address, and the slots of such glyphs — they lie inside the workgroup's range, the decoder fills them —
+// are passed over.
 	if (t < ng) {
 		const CommandFontRef ref = f < kExpandFontCache ? s_fonts[f] : fonts[f];
-		const uint32_t first = reinterpret_cast<const uint32_t *>(ref.cmd_off)[gid];
-		s_recs[t] = reinterpret_cast<const uint32_t *>(ref.cmds) + 7ull * first;
-		s_open[t] = reinterpret_cast<const uint8_t *>(ref.open) + first;
+#ifdef RESIDENT_GATHER_MIXED
+		if (ref.reserved != kFontRefCommands) {
+			s_recs[t] = nullptr;
+			s_open[t] = nullptr;
+		} else
+#endif
+		{
+			const uint32_t first = reinterpret_cast<const uint32_t *>(ref.cmd_off)[gid];
+			s_recs[t] = reinterpret_cast<const uint32_t *>(ref.cmds) + 7ull * first;
+			s_open[t] = reinterpret_cast<const uint8_t *>(ref.open) + first;
+		}
 	}
 	__syncthreads();
 	const uint32_t c1 = min(s_cmd_off[ng], n_cmds);
@@ -26,8 +37,14 @@
 					hi = mid;
 			}
 			const uint32_t k = j - s_cmd_off[lo];
+#ifdef RESIDENT_GATHER_MIXED
+			const uint32_t *const recs = s_recs[lo];
+			rp[u] = j < c1 && recs ? recs + 7u * k : nullptr;
+			op[u] = rp[u] ? s_open[lo] + k : nullptr;
+#else
 			rp[u] = j < c1 ? s_recs[lo] + 7u * k : nullptr;
 			op[u] = s_open[lo] + k;
+#endif
 		}
 		uint32_t r[kGatherUnroll][7];
 		uint8_t o[kGatherUnroll];

@@ -78,6 +78,30 @@ struct CommandFontRef { // a command font's three arrays (device addresses)
 	uint64_t cmd_off, cmds, open, reserved; // u32[n_glyph_ids + 1] | 28-byte records | the context pass's byte per record
 };
 static_assert(sizeof(CommandFontRef) == sizeof(ResidentFontRef), "one size of font reference in every block that names fonts");
+// The kind of a font reference, in its `reserved` word.  0: the block's own kind — every block of the forms above, whose lists
+// hold ONE kind.  The mixed forms (vgsdf_outlines_submit_resident_mixed, mixed families) keep fonts of both kinds in one list
+// of ResidentBlockLayout and say which a reference is; a command glyph has no parts there (part_off stands still over it) and
+// cmd_off runs over the glyphs of both kinds.
+constexpr uint64_t kFontRefOfBlock = 0, kFontRefGlyf = 1, kFontRefCommands = 2;
+// a reference of such a list, read as either kind (the three addresses share their places)
+struct MixedFontRef {
+	uint64_t a, b, c, kind;
+#if defined(__HIPCC__)
+	__host__ __device__
+#endif
+	    operator ResidentFontRef() const
+	{
+		return ResidentFontRef{a, b, c, kind};
+	}
+#if defined(__HIPCC__)
+	__host__ __device__
+#endif
+	    operator CommandFontRef() const
+	{
+		return CommandFontRef{a, b, c, kind};
+	}
+};
+static_assert(sizeof(MixedFontRef) == sizeof(ResidentFontRef), "one size of font reference in every block that names fonts");
 struct CommandBlockLayout : GlyphArraysLayout {
 	size_t glyph_id, font_of, pbf_pre, pbf_fix, arrays_end, fonts, bytes;
 	CommandBlockLayout(size_t n, size_t n_fonts, bool with_pbf) : GlyphArraysLayout(n)
@@ -138,7 +162,8 @@ struct FamilyTableLayout {
 	}
 };
 // The block of such a submission: 32 bytes per task that maps a glyph, per family and per font, nothing per glyph —
-//   RangeTask[n_live] | FamilyRef[n_families] | font references[n_fonts] (ResidentFontRef or CommandFontRef)
+//   RangeTask[n_live] | FamilyRef[n_families] | font references[n_fonts] (ResidentFontRef or CommandFontRef; a submission of mixed
+//   families: MixedFontRef, each saying its kind, and the device's copy is ResidentBlockLayout's)
 // The upload kernel of the form WRITES the per-glyph arrays of ResidentBlockLayout / CommandBlockLayout into the device's copy
 // (where every later kernel reads them) and copies the font references to that layout's `fonts`.
 struct RangeTask {

@@ -119,6 +119,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_outlines_task_extents", "vgsdf_family_create_tables", "vgsdf_family_read", "vgsdf_family_tables_kernel_ms",
     "vgsdf_font_create_tables", "vgsdf_font_create_tables_within", "vgsdf_font_read", "vgsdf_font_tables_kernel_ms",
     "vgsdf_fonts_create_tables", "vgsdf_fonts_create_tables_within", "vgsdf_fonts_tables_kernel_ms",
+    "vgsdf_outlines_submit_resident_mixed", "vgsdf_family_create_mixed", "vgsdf_family_create_tables_mixed",
 ]
 
 _lib = None
@@ -187,9 +188,12 @@ def load_library():
         L.vgsdf_font_device_bytes.argtypes = [vp]
         L.vgsdf_font_device_bytes.restype = C.c_uint64
         L.vgsdf_outlines_submit_resident.argtypes = [vp, vp, vp, C.c_size_t]
+        L.vgsdf_outlines_submit_resident_mixed.argtypes = [vp, vp, vp, C.c_size_t]
         L.vgsdf_outlines_resident_upload_bytes.argtypes = [vp]
         L.vgsdf_outlines_resident_upload_bytes.restype = C.c_uint64
         L.vgsdf_family_create.argtypes = [vp, C.POINTER(_CFamilyDesc), C.POINTER(vp)]
+        L.vgsdf_family_create_mixed.argtypes = [vp, C.POINTER(_CFamilyDesc), C.POINTER(vp)]
+        L.vgsdf_family_create_tables_mixed.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), C.POINTER(vp)]
         L.vgsdf_family_free.argtypes = [vp, vp]
         L.vgsdf_family_device_bytes.argtypes = [vp]
         L.vgsdf_family_device_bytes.restype = C.c_uint64
@@ -704,7 +708,13 @@ class SdfContext:
         load_library().vgsdf_fonts_tables_kernel_ms(self._h, ms)
         return float(ms[0]), float(ms[1])
 
-    def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None):
+    def outlines_submit_resident_mixed(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None):
+        """vgsdf_outlines_submit_resident_mixed: outlines_submit_resident with fonts of BOTH kinds (glyf and command fonts) in `fonts`"""
+        self.outlines_submit_resident(fonts, font_of, glyph_id, scale, shift_x, capacity, pbf_pre, pbf_fix, fill,
+                                      entry="vgsdf_outlines_submit_resident_mixed")
+
+    def outlines_submit_resident(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None,
+                                 entry="vgsdf_outlines_submit_resident"):
         """outlines_submit for glyphs named by (font, glyph id) of resident fonts (vgsdf_outlines_resident)"""
         keep = {
             "font_of": np.ascontiguousarray(font_of, dtype=np.uint16), "glyph_id": np.ascontiguousarray(glyph_id, dtype=np.uint16),
@@ -715,9 +725,17 @@ class SdfContext:
         assert len(keep["font_of"]) == n and len(keep["glyph_id"]) == n
         co = _COutlinesResident(n, len(fonts), C.cast(keep["fonts"], C.c_void_p), keep["font_of"].ctypes.data, keep["glyph_id"].ctypes.data,
                                 keep["scale"].ctypes.data, keep["shift"].ctypes.data)
-        self._submit("vgsdf_outlines_submit_resident", co, keep, capacity, pbf_pre, pbf_fix, fill=fill)
+        self._submit(entry, co, keep, capacity, pbf_pre, pbf_fix, fill=fill)
 
-    def family_create(self, fonts, code_point, font_of, glyph_id, advance, scale, shift_x) -> ResidentFamily:
+    def family_create_mixed(self, fonts, code_point, font_of, glyph_id, advance, scale, shift_x) -> ResidentFamily:
+        """vgsdf_family_create_mixed: family_create over `fonts` of either kind -> a family of the third kind, mixed"""
+        return self.family_create(fonts, code_point, font_of, glyph_id, advance, scale, shift_x, entry="vgsdf_family_create_mixed")
+
+    def family_create_tables_mixed(self, fonts, faces) -> ResidentFamily:
+        """vgsdf_family_create_tables_mixed: family_create_tables over `fonts` of either kind -> a mixed family"""
+        return self.family_create_tables(fonts, faces, entry="vgsdf_family_create_tables_mixed")
+
+    def family_create(self, fonts, code_point, font_of, glyph_id, advance, scale, shift_x, entry="vgsdf_family_create") -> ResidentFamily:
         """vgsdf_family_create: the entries of a font id over `fonts` (ResidentFont, one kind), code points strictly ascending"""
         a = [np.ascontiguousarray(code_point, dtype=np.uint16), np.ascontiguousarray(font_of, dtype=np.uint16),
              np.ascontiguousarray(glyph_id, dtype=np.uint16), np.ascontiguousarray(advance, dtype=np.uint32),
@@ -726,10 +744,10 @@ class SdfContext:
         handles = (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts])
         d = _CFamilyDesc(len(fonts), C.cast(handles, C.c_void_p), len(a[0]), *[x.ctypes.data for x in a])
         h = C.c_void_p()
-        self._check(load_library().vgsdf_family_create(self._h, C.byref(d), C.byref(h)))
+        self._check(getattr(load_library(), entry)(self._h, C.byref(d), C.byref(h)))
         return ResidentFamily(self, h, fonts)
 
-    def family_create_tables(self, fonts, faces) -> ResidentFamily:
+    def family_create_tables(self, fonts, faces, entry="vgsdf_family_create_tables") -> ResidentFamily:
         """vgsdf_family_create_tables: the family of `fonts` (ResidentFont, one kind, provider order) built on the device from
         `faces`, one dict per font as FontManager.family_tables_desc returns it: {cmap, hmtx (bytes or uint8 arrays),
         units_per_em, num_glyphs, num_hmetrics, subtable_off, subtable_format}"""
@@ -749,7 +767,7 @@ class SdfContext:
         handles = (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts])
         d = _CFamilyTablesDesc(len(fonts), C.cast(handles, C.c_void_p), C.cast(recs, C.c_void_p))
         h = C.c_void_p()
-        self._check(load_library().vgsdf_family_create_tables(self._h, C.byref(d), C.byref(h)))
+        self._check(getattr(load_library(), entry)(self._h, C.byref(d), C.byref(h)))
         return ResidentFamily(self, h, fonts)
 
     def family_read(self, family: ResidentFamily) -> dict:

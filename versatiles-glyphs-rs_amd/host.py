@@ -48,6 +48,10 @@ class ResidentStats(C.Structure):  # vg_resident_stats
     _fields_ = [(k, C.c_uint64) for k in ("groups", "fonts_uploaded", "font_bytes", "block_bytes")]
 
 
+class MixedStats(C.Structure):  # vg_mixed_stats
+    _fields_ = [(k, C.c_uint64) for k in ("groups", "glyf_fonts", "command_fonts", "block_bytes")]
+
+
 class _CFaceTables(C.Structure):  # vgsdf_face_tables
     _fields_ = [("cmap", C.c_void_p), ("cmap_len", C.c_uint32), ("hmtx", C.c_void_p), ("hmtx_len", C.c_uint32),
                 ("units_per_em", C.c_uint16), ("num_glyphs", C.c_uint16), ("num_hmetrics", C.c_uint16), ("n_subtables", C.c_uint16),
@@ -94,6 +98,7 @@ VGFONT_SYMBOLS = [
     "vg_manager_family_tables_desc", "vg_manager_font_tables_desc", "vg_manager_set_family_tables_on_device", "vg_manager_family_table_stats",
     "vg_manager_set_glyf_tables_on_device", "vg_manager_glyf_table_stats",
     "vg_manager_set_glyf_tables_batched", "vg_manager_glyf_table_batch_stats",
+    "vg_manager_set_mixed_stores", "vg_manager_mixed_stats",
 ]
 
 _bound = False
@@ -128,6 +133,9 @@ def _L():
         L.vg_manager_set_resident_commands.argtypes = [vp, C.c_int]
         L.vg_manager_set_resident_commands.restype = None
         L.vg_manager_command_stats.argtypes = [vp, C.POINTER(ResidentStats)]
+        L.vg_manager_set_mixed_stores.argtypes = [vp, C.c_int]
+        L.vg_manager_set_mixed_stores.restype = None
+        L.vg_manager_mixed_stats.argtypes = [vp, C.POINTER(MixedStats)]
         L.vg_manager_set_charstrings_on_device.argtypes = [vp, C.c_int]
         L.vg_manager_set_charstrings_on_device.restype = None
         L.vg_manager_charstring_stats.argtypes = [vp, C.POINTER(CharstringStats)]
@@ -394,6 +402,19 @@ class FontManager:
         (font, glyph id) against command stores instead of being read by the host on every render; 2: every group is; same
         bytes in every mode"""
         _L().vg_manager_set_resident_commands(self._h, int(mode))
+
+    def set_mixed_stores(self, on: bool):
+        """with the device's glyf decoder, resident fonts and set_resident_commands(1): a group that is not all `glyf` is submitted
+        against stores of BOTH kinds, a glyf store for every `glyf` file and a command store for every other, instead of against
+        command stores of all its files; same bytes (default off)"""
+        _L().vg_manager_set_mixed_stores(self._h, int(bool(on)))
+
+    def mixed_stats(self) -> dict:
+        """of the last render: {groups, glyf_fonts, command_fonts, block_bytes} of the groups submitted against stores of both
+        kinds (vg_mixed_stats)"""
+        s = MixedStats()
+        _L().vg_manager_mixed_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in MixedStats._fields_}
 
     def set_charstrings_on_device(self, on):
         """False / 0 (default).  True / 1: the command stores of `CFF ` version 1 faces are decoded on the device from the charstrings
