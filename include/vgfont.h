@@ -168,7 +168,7 @@ int vg_manager_mixed_stats(const vg_manager *m, vg_mixed_stats *out);
  * refuses (a seac glyph, a glyph past VGSDF_CHARSTRING_MAX_TOKENS, a store past the bounds) gets its store from the host reader as with 0.  Same
  * registry, same budget, same store bytes and same output either way.  With 1, CFF2 and `glyf` faces are not affected.  With 2,
  * everything 1 does, and CFF2 faces likewise through vgsdf_font_create_charstrings2, with the blend factors of the host reader
- * (the default position of the design space); same fallback, same stats.  `glyf` faces are not affected.  Any other non-zero value: 1.
+ * (those of the file's position: the default one of the design space unless vg_manager_add_font_instance put it elsewhere); same fallback, same stats.  `glyf` faces are not affected.  Any other non-zero value: 1.
  * vg_manager_charstring_stats: of the last render; the decoded stores count among vg_command_stats.fonts_uploaded too. */
 void vg_manager_set_charstrings_on_device(vg_manager *m, int on);
 typedef struct {
@@ -239,6 +239,36 @@ int vg_manager_glyf_table_batch_stats(const vg_manager *m, vg_glyf_table_batch_s
 void vg_manager_set_lane_form(vg_manager *m, int form);
 int vg_manager_add_font_with_name(vg_manager *m, const char *name, const char *const *paths, int n_paths);
 int vg_manager_add_font_data(vg_manager *m, const char *name, const uint8_t *data, size_t len);
+/*
+ * A VARIABLE file at a position of its design space, under a name of the caller's ("this file, at this position, under this
+ * name"): axis_tags[i] (4 bytes, e.g. "wght") is set to values[i] in user space; axes not named stay at their default.  The
+ * values are normalised in f32 (clamped to the axis, (v - def) / (def - min) or / (max - def), times 16384, truncated) and sent
+ * through the file's `avar` (version 1.0).  CFF2 outlines are drawn at the position and advances follow `HVAR`; everything that
+ * describes the file afterwards (vg_manager_charstring2_font_desc, _command_font_desc, _family_desc ...) describes it there.
+ * Several instances of one file under different names are several font ids; the same name merges them into one font id like
+ * any other files; no two instances share a store on a device.  Returns what vg_manager_add_font_data returns; -1 with
+ * vg_last_error also for an unknown tag, a tag given twice, a value that is not finite, a file without a readable `fvar`, a
+ * face with `glyf` outlines (no `gvar` reader), an HVAR store of another format than 1 or with 32-bit deltas.  A file added
+ * any other way (vg_manager_add_font_data, _add_path, _scan) is at its default position, as the reference renders it.
+ * _normalized: the final normalised coordinates (F2Dot14), one per `fvar` axis (at most 64 are counted; another number: -1);
+ * nothing is normalised and `avar` is not applied.
+ */
+int vg_manager_add_font_instance(vg_manager *m, const char *name, const uint8_t *data, size_t len, const char *const *axis_tags,
+                                 const float *values, int n);
+int vg_manager_add_font_instance_normalized(vg_manager *m, const char *name, const uint8_t *data, size_t len, const int16_t *coords, int n);
+/* What a file's `fvar` offers (host only), so that a caller can turn "the named instances of this file" into calls of
+ * vg_manager_add_font_instance without a font parser of its own.  _axes: the number of axes, and the first `cap` of them in
+ * tags / min / def / max (user space; each array may be NULL).  _named_instances: the number of instance records, and the first
+ * cap_instances of them in name_id (the subfamily name's id in `name`) and coords [cap_instances * n_axes] (user space); n_axes
+ * must be the file's.  -1: no readable `fvar`, or n_axes is not the number of its axes. */
+/* test / inspection of a file the manager holds.  _font_position: the number of normalised coordinates file `file_index` of the
+ * font id was placed at (0: it was not added at a position), and the first `cap` of them in coords (may be NULL).
+ * _font_hor_advances: the file's numGlyphs, and in advances[0 .. cap) the reader's advance of every glyph id in font units
+ * (hmtx, plus HVAR for a file at a position; 0 for "none" and for ids at and past numGlyphs).  -1: unknown font / file. */
+int vg_manager_font_position(const vg_manager *m, const char *font_id, int file_index, int16_t *coords, int cap);
+int vg_manager_font_hor_advances(const vg_manager *m, const char *font_id, int file_index, uint16_t *advances, int cap);
+int vg_font_variation_axes(const uint8_t *data, size_t len, char (*tags)[4], float *min, float *def, float *max, int cap);
+int vg_font_named_instances(const uint8_t *data, size_t len, uint16_t *name_id, float *coords, int cap_instances, int n_axes);
 /* manager.rs:39-53: the file's name table decides the font id (family/width/weight/style ->
  * generate_name -> name_to_id); files with the same id merge in call order. */
 int vg_manager_add_path(vg_manager *m, const char *path);
@@ -381,7 +411,7 @@ int vg_manager_command_font_desc(const vg_manager *m, const char *font_id, int f
 int vg_manager_charstring_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings_desc *desc);
 /* The same of a CFF2 face for vgsdf_font_create_charstrings2: INDEX counts read as 32 bits, the one set of local subroutines the
  * reader uses for every glyph, and the blend sets — one per ItemVariationData of the variation store, with its usable flag and the
- * factors the reader multiplies `blend` deltas by (the default position).  -1: unknown font / file, anything that is not CFF2, an
+ * factors the reader multiplies `blend` deltas by (at the file's position: the default one unless it is an instance).  -1: unknown font / file, anything that is not CFF2, an
  * INDEX whose entries do not ascend inside their data, or a set of more than 65535 subroutines. */
 int vg_manager_charstring2_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings2_desc *desc);
 vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, const char *font_id);
@@ -408,8 +438,15 @@ int vg_manager_family_desc(const vg_manager *m, const char *font_id, vg_family_v
  * font of file k and tables[k] this description, the device builds the table vg_manager_family_desc states.  The pointers stay
  * valid as long as the manager holds the font.  -1: unknown font / file, or a description that REFUSES: a format 4 subtable whose
  * segments are not regular (segCountX2 >= 2, the arrays inside the table, start <= end, start above the previous end), or a
- * format 12 / 13 subtable whose groups are not ascending and disjoint inside the table; vg_last_error then begins "refused". */
+ * format 12 / 13 subtable whose groups are not ascending and disjoint inside the table, or (a file at a position) an HVAR that
+ * vg_manager_family_variation_desc refuses; vg_last_error then begins "refused" and names which. */
 int vg_manager_family_tables_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_face_tables *desc);
+/* ... and what vgsdf_family_create_tables_var takes beside it for a file at a position (vg_manager_add_font_instance): its whole
+ * `HVAR` table as a view into the face, where its store and advance map are, and the factor of every region of the store at the
+ * file's position.  A file that is not at a position, or has no readable HVAR: 0 with hvar NULL (a static face).  -1: as above,
+ * or an HVAR the description REFUSES — an advance map of a format other than 0 and 1 or outside the table, an ItemVariationData
+ * with more word deltas than regions — whose font id gets its family the host's way. */
+int vg_manager_family_variation_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_face_variation *desc);
 /* A `glyf` face stated by its TABLES, for vgsdf_font_create_tables (no device needed, and no glyph looked at): file `file_index`'s
  * whole `loca` and `glyf` tables as views into the face, num_glyphs (maxp), the loca format (head) and the loca entries the reader
  * goes by.  The device builds from it the leaves vg_manager_resident_font_desc states, with the simple entries' bytes in glyph-id

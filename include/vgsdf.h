@@ -396,7 +396,7 @@ int vgsdf_font_create_charstrings_within(vgsdf_ctx *ctx, const vgsdf_font_charst
  *   factors    f32; `blend` adds to each of its values delta x factor for every region, last region first, one product and one
  *              sum per delta in f32
  * The factors are plain data: the entry point neither knows nor checks which position of the design space they stand for (the
- * host reader's are those of the default position).  Validated on the host before anything runs, VGSDF_E_ARG otherwise: all the
+ * host reader's are those of the face's position: the default one, or where vg_manager_add_font_instance put it).  Validated on the host before anything runs, VGSDF_E_ARG otherwise: all the
  * above validates, n_fds == 1, fd_of == NULL, at most 65536 sets, set_off ascending from 0 and ending at or below n_factors, at
  * most 64 factors per set, every factor finite.  Count pass, store, emit pass, refusals (no seac form exists in CFF2), budget
  * form, result and vgsdf_font_device_bytes are those of vgsdf_font_create_charstrings.  The passes run in launches of at most
@@ -546,6 +546,37 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
 /* The same with fonts of either kind: a mixed family, indistinguishable from one vgsdf_family_create_mixed makes of the same
  * entries.  (vgsdf_family_tables_kernel_ms reports its passes as well.) */
 int vgsdf_family_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out);
+/*
+ * The same with faces AT A POSITION of their design space, whose advances follow `HVAR` (vg_manager_add_font_instance of
+ * vgfont.h): var[k] beside tables[k] says where face k's HVAR is and what factor every region of its ItemVariationStore has at
+ * the face's position (the host evaluates the regions, once; the device takes the factors as data, as the CFF2 decoder takes
+ * its own).  A record with hvar NULL and hvar_len 0 is a static face; var NULL: every face is (the call is then
+ * vgsdf_family_create_tables).  A family may mix both.  Where the emit pass has a glyph's `hmtx` advance it adds, in f32,
+ * what the host's reader adds (Face::glyph_hor_advance of a face at a position):
+ *   (outer, inner) = the advance map's entry of min(glyph id, mapCount - 1) (DeltaSetIndexMap format 0 or 1, entry size
+ *   ((entryFormat >> 4) & 3) + 1 bytes, inner bits (entryFormat & 15) + 1), or (0, glyph id) without a map (map_off 0);
+ *   delta = sum over the columns of row `inner` of ItemVariationData[outer] of delta * factor(regionIndex), one f32 product and
+ *   one f32 sum per column in column order, the first wordDeltaCount columns i16 and the rest i8, a region index at or past
+ *   n_regions with factor 0;  advance = trunc((f32)hmtx advance + delta + 0.5), 0 when that leaves 0 .. 65535.
+ * No delta — the `hmtx` advance stands — for a map without entries or of another format, outer past the store's list, inner at
+ * or past itemCount, more word deltas than columns, and whenever a byte of the walk would lie at or past hvar_len: every read is
+ * bounded by hvar_len, whatever the table's own fields say.  Everything else is as in vgsdf_family_create_tables; the count
+ * pass is the same.  Validated on the host in addition (VGSDF_E_ARG, nothing left allocated, the context sound): hvar NULL
+ * beside a length, region_scalars NULL beside n_regions, store_off + 8 past hvar_len, map_off at or past hvar_len, a store
+ * whose format is not 1, an ItemVariationData (its header inside the table) with the LONG_WORDS bit, a factor that is not finite.
+ * The family is indistinguishable from one vgsdf_family_create makes of the same entries with the reader's advances.
+ */
+typedef struct { /* one face's variation, as vg_manager_family_variation_desc states it */
+	const uint8_t *hvar;         /* the whole table as it stands in the file; NULL: a static face */
+	uint32_t hvar_len;
+	uint32_t store_off, map_off; /* into hvar: the ItemVariationStore, the advance-width map (0: none) */
+	const float *region_scalars; /* [n_regions] */
+	uint32_t n_regions;
+} vgsdf_face_variation;
+int vgsdf_family_create_tables_var(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var /* [n_fonts] or NULL */,
+                                   vgsdf_family **out);
+int vgsdf_family_create_tables_var_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var,
+                                         vgsdf_family **out);
 /* test / inspection: download the DEVICE's copy of a family's table, whichever call made it; *n_entries: its entries; code_point,
  * font_of, glyph_id, advance, scale, shift_x, pbf_fix [n_entries], cmd_pre, leaf_pre [n_entries + 1] (mod 2^32): each NULL or filled */
 int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_entries, uint16_t *code_point, uint16_t *font_of,

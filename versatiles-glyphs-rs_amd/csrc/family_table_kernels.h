@@ -20,6 +20,15 @@ struct FamilyFaceRef {
 	uint32_t commands;    // 1: a command font
 };
 static_assert(sizeof(FamilyFaceRef) == 64, "one 64-byte record per face");
+// what a face at a position adds (vgsdf_face_variation), in an array beside the faces' records (those are full): the `HVAR`
+// bytes on the device and the factors of its store's regions.  Every read of hvar is bounded by hvar_len; the host has checked
+// store_off + 8 <= hvar_len and map_off < hvar_len (vgsdf_family_create_tables_var).
+struct FamilyFaceVar {
+	uint64_t hvar;    // 0: a static face
+	uint64_t scalars; // f32[n_regions]
+	uint32_t hvar_len, store_off, map_off, n_regions; // map_off 0: no advance map
+};
+static_assert(sizeof(FamilyFaceVar) == 32, "one 32-byte record per face");
 struct FamilySubtable {
 	uint32_t off, format; // into cmap; 0 4 6 10 12 13
 };
@@ -42,4 +51,7 @@ int vgsdf_family_tables_count(const vgsdf::FamilyFaceRef *faces, uint32_t n_face
 // emit pass: the n_entries = sum of the counted entries, each at its rank, into `table` (FamilyTableLayout(n_entries))
 int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, const uint32_t *counts, uint32_t n_entries,
                              uint8_t *table, hipStream_t stream);
+// the emit pass over faces some of which are at a position: var[n_faces] beside faces
+int vgsdf_family_tables_emit_var(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, uint32_t n_faces, const uint32_t *counts,
+                                 uint32_t n_entries, uint8_t *table, hipStream_t stream);
 }

@@ -5,7 +5,8 @@
 // (Face::glyph_index), and the entry's numbers are Renderer::record_resident's in f64 (this unit is built with
 // -ffp-contract=off).  The lookups are CmapSubtable::glyph_index's bisections; every read is bounded by the table lengths of the
 // face record.  Two passes of one text: the count pass leaves per workgroup its entries, command slots and leaves, the emit pass
-// places every entry at its rank and writes all nine arrays of FamilyTableLayout.
+// places every entry at its rank and writes all nine arrays of FamilyTableLayout.  A third instantiation of that text, the emit
+// pass with VAR, adds to the `hmtx` advance of a face at a position what Face::hvar_advance_delta finds in the face's `HVAR`.
 #include "family_table_kernels.h"
 
 #include "upload_layout.h"
@@ -201,10 +202,80 @@ __device__ Sum3 block_sum(Sum3 v, uint32_t (*lds)[3])
 	return r;
 }
 
-template <bool EMIT>
-__global__ __launch_bounds__(kFamilyThreads) void family_tables_pass(const FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts,
-                                                                       uint32_t *flags, uint32_t n_entries, uint8_t *table)
+// an `HVAR` table: every read is asked for here first, against the length the face's record gives
+struct Tab {
+	const uint8_t *p;
+	uint64_t n;
+};
+__device__ inline bool has(const Tab &t, uint64_t off, uint64_t len) { return off <= t.n && len <= t.n - off; }
+
+// Face::hvar_advance_delta: the advance map's (outer, inner) of the glyph id, row `inner` of ItemVariationData[outer] times the
+// factors of its regions; false: no delta.  Byte and be16 / be32 loads from one base, each inside hvar_len.
+__device__ bool hvar_delta(const FamilyFaceVar &V, uint32_t gid, float &delta)
 {
+	const Tab t{(const uint8_t *)(uintptr_t)V.hvar, V.hvar_len};
+	uint32_t outer = 0, inner = gid;
+	if (V.map_off != 0) {
+		const uint64_t m = V.map_off;
+		if (!has(t, m, 2))
+			return false;
+		const uint32_t format = t.p[m], ef = t.p[m + 1];
+		if (format > 1 || !has(t, m + 2, format ? 4 : 2))
+			return false;
+		const uint32_t count = format ? be32(t.p + m + 2) : be16(t.p + m + 2);
+		if (count == 0)
+			return false;
+		const uint32_t entry_size = ((ef >> 4) & 3u) + 1u, idx = gid < count - 1u ? gid : count - 1u;
+		const uint64_t at = m + (format ? 6u : 4u) + (uint64_t)entry_size * idx;
+		if (!has(t, at, entry_size))
+			return false;
+		uint32_t n = 0;
+		for (uint32_t k = 0; k < entry_size; k++)
+			n = (n << 8) | t.p[at + k];
+		const uint32_t bits = (ef & 15u) + 1u;
+		outer = n >> bits, inner = n & ((1u << bits) - 1u);
+		if (outer > 0xFFFFu)
+			return false;
+	}
+	const uint64_t s = V.store_off;
+	if (!has(t, s, 8) || outer >= be16(t.p + s + 6) || !has(t, s + 8 + 4ull * outer, 4))
+		return false;
+	const uint64_t at = s + be32(t.p + s + 8 + 4ull * outer);
+	if (!has(t, at, 6))
+		return false;
+	const uint32_t item_count = be16(t.p + at), words = be16(t.p + at + 2), n_cols = be16(t.p + at + 4);
+	// (a LONG_WORDS bit the host had not seen makes `words` larger than n_cols: no delta)
+	if (!has(t, at + 6, 2ull * n_cols) || inner >= item_count || words > n_cols)
+		return false;
+	const uint64_t row = at + 6 + 2ull * n_cols + (uint64_t)inner * (words + n_cols);
+	if (!has(t, row, (uint64_t)words + n_cols))
+		return false;
+	const float *scalars = (const float *)(uintptr_t)V.scalars;
+	float d = 0.0f;
+	uint64_t p = row;
+	for (uint32_t c = 0; c < n_cols; c++) {
+		const uint32_t region = be16(t.p + at + 6 + 2ull * c);
+		float num;
+		if (c < words) {
+			num = (float)(int16_t)be16(t.p + p);
+			p += 2;
+		} else {
+			num = (float)(int8_t)t.p[p];
+			p += 1;
+		}
+		d += num * (region < V.n_regions ? scalars[region] : 0.0f);
+	}
+	delta = d;
+	return true;
+}
+
+// VAR: the emit pass over faces some of which are at a position; its one further argument, `const FamilyFaceVar *`, is a pack so
+// that the instantiations without it keep the arguments (and with them the kernel descriptor) they have always had
+template <bool EMIT, bool VAR = false, class... Var>
+__global__ __launch_bounds__(kFamilyThreads) void family_tables_pass(const FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts,
+                                                                       uint32_t *flags, uint32_t n_entries, uint8_t *table, Var... var)
+{
+	static_assert(sizeof...(Var) == (VAR ? 1 : 0), "the variation records come with VAR and only with it");
 	__shared__ uint32_t lds_base[kFamilyThreads / 64][3], lds_wave[kFamilyThreads / 64][3];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = blockIdx.x * kFamilyThreads + tid;
 	const Entry e = find_entry(faces, n_faces, c);
@@ -262,6 +333,14 @@ __global__ __launch_bounds__(kFamilyThreads) void family_tables_pass(const Famil
 	if (F.hmtx_len != 0 && F.num_hmetrics != 0 && F.num_glyphs != 0 && e.gid < F.num_glyphs && (uint32_t)F.num_hmetrics * 4u <= F.hmtx_len) {
 		const uint32_t i = e.gid < (uint32_t)F.num_hmetrics - 1u ? e.gid : (uint32_t)F.num_hmetrics - 1u;
 		adv = be16((const uint8_t *)(uintptr_t)F.hmtx + (size_t)i * 4);
+		if constexpr (VAR) { // Face::glyph_hor_advance of a face at a position: f32, `+ 0.5`, truncated; outside u16: none
+			const FamilyFaceVar &V = (var, ...)[e.face]; // (the pack's one element)
+			float delta;
+			if (V.hvar != 0 && hvar_delta(V, e.gid, delta)) {
+				const float a = (float)adv + (delta + 0.5f);
+				adv = a > -1.0f && a < 65536.0f ? (uint32_t)(int32_t)a : 0u;
+			}
+		}
 	}
 	// Renderer::record_resident
 	const double scale = 24.0 / (double)F.units_per_em;
@@ -295,6 +374,14 @@ int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces
 {
 	hipLaunchKernelGGL(vgsdf::family_tables_pass<true>, dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces, n_faces,
 	                   const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table);
+	return (int)hipGetLastError();
+}
+
+int vgsdf_family_tables_emit_var(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, uint32_t n_faces, const uint32_t *counts,
+                                 uint32_t n_entries, uint8_t *table, hipStream_t stream)
+{
+	hipLaunchKernelGGL((vgsdf::family_tables_pass<true, true>), dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces,
+	                   n_faces, const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, var);
 	return (int)hipGetLastError();
 }
 

@@ -224,6 +224,124 @@ int vg_manager_add_font_data(vg_manager *m, const char *name, const uint8_t *dat
 	std::string err;
 	return m->m.add_font_data(name, std::vector<uint8_t>(data, data + len), &err) ? 0 : fail(err);
 }
+int vg_manager_add_font_instance(vg_manager *m, const char *name, const uint8_t *data, size_t len, const char *const *axis_tags,
+                                 const float *values, int n)
+{
+	try {
+		if (!m || !name || (!data && len) || n < 0 || (n && (!axis_tags || !values)))
+			return fail("vg_manager_add_font_instance: bad argument");
+		std::vector<std::array<char, 4>> tags;
+		for (int i = 0; i < n; i++) {
+			if (!axis_tags[i] || std::strlen(axis_tags[i]) != 4)
+				return fail("vg_manager_add_font_instance: an axis tag is four characters");
+			std::array<char, 4> t;
+			std::memcpy(t.data(), axis_tags[i], 4);
+			tags.push_back(t);
+		}
+		std::string err;
+		return m->m.add_font_instance(name, std::vector<uint8_t>(data, data + len), tags, std::vector<float>(values, values + n), &err) ? 0 : fail(err);
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+int vg_manager_add_font_instance_normalized(vg_manager *m, const char *name, const uint8_t *data, size_t len, const int16_t *coords, int n)
+{
+	try {
+		if (!m || !name || (!data && len) || n < 0 || (n && !coords))
+			return fail("vg_manager_add_font_instance_normalized: bad argument");
+		std::string err;
+		return m->m.add_font_instance_normalized(name, std::vector<uint8_t>(data, data + len), std::vector<int16_t>(coords, coords + n), &err) ? 0 : fail(err);
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+namespace {
+// file `file_index` of a font id (nullptr and g_err: none)
+const vg::Face *face_of(const vg_manager *m, const char *font_id, int file_index, const char *me)
+{
+	if (!m || !font_id || file_index < 0) {
+		g_err = std::string(me) + ": bad argument";
+		return nullptr;
+	}
+	auto it = m->m.fonts().find(font_id);
+	if (it == m->m.fonts().end() || (size_t)file_index >= it->second.files().size()) {
+		g_err = std::string("unknown font id ") + font_id + ", or a file index past its files";
+		return nullptr;
+	}
+	return &it->second.files()[(size_t)file_index]->face();
+}
+} // namespace
+int vg_manager_font_position(const vg_manager *m, const char *font_id, int file_index, int16_t *coords, int cap)
+{
+	try {
+		const vg::Face *f = face_of(m, font_id, file_index, "vg_manager_font_position");
+		if (!f)
+			return -1;
+		if (!f->at_position())
+			return 0;
+		for (int i = 0; coords && i < cap && (size_t)i < f->coords().size(); i++)
+			coords[i] = f->coords()[(size_t)i];
+		return (int)f->coords().size();
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+int vg_manager_font_hor_advances(const vg_manager *m, const char *font_id, int file_index, uint16_t *advances, int cap)
+{
+	try {
+		const vg::Face *f = face_of(m, font_id, file_index, "vg_manager_font_hor_advances");
+		if (!f)
+			return -1;
+		if (advances && cap > 0) {
+			const std::vector<uint16_t> a = f->hor_advances((uint32_t)cap);
+			std::copy(a.begin(), a.end(), advances);
+		}
+		return (int)f->number_of_glyphs();
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+int vg_font_variation_axes(const uint8_t *data, size_t len, char (*tags)[4], float *min, float *def, float *max, int cap)
+{
+	try {
+		std::vector<vg::VariationAxis> axes;
+		if ((!data && len) || !vg::read_variation_axes(data, len, axes))
+			return fail("no readable fvar table");
+		for (int i = 0; i < cap && (size_t)i < axes.size(); i++) {
+			if (tags)
+				std::memcpy(tags[i], axes[i].tag, 4);
+			if (min)
+				min[i] = axes[i].min;
+			if (def)
+				def[i] = axes[i].def;
+			if (max)
+				max[i] = axes[i].max;
+		}
+		return (int)axes.size();
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+int vg_font_named_instances(const uint8_t *data, size_t len, uint16_t *name_id, float *coords, int cap_instances, int n_axes)
+{
+	try {
+		std::vector<vg::VariationAxis> axes;
+		std::vector<vg::NamedInstance> inst;
+		if ((!data && len) || !vg::read_variation_axes(data, len, axes, &inst))
+			return fail("no readable fvar table");
+		if ((size_t)n_axes != axes.size())
+			return fail("vg_font_named_instances: n_axes is not the number of the file's axes");
+		for (int k = 0; k < cap_instances && (size_t)k < inst.size(); k++) {
+			if (name_id)
+				name_id[k] = inst[k].name_id;
+			if (coords)
+				std::copy(inst[k].coords.begin(), inst[k].coords.end(), coords + (size_t)k * axes.size());
+		}
+		return (int)inst.size();
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
 int vg_manager_add_path(vg_manager *m, const char *path)
 {
 	std::string err;
@@ -849,7 +967,9 @@ int vg_manager_family_tables_desc(const vg_manager *m, const char *font_id, int 
 		}
 		const vg::FamilyTables &t = it->second.files()[(size_t)file_index]->face().family_tables();
 		if (!t.ok) {
-			g_err = std::string("refused: font ") + font_id + ": a cmap subtable whose segments or groups are not regular";
+			g_err = std::string("refused: font ") + font_id +
+			        (t.hvar_refused ? ": an HVAR advance map of a format other than 0 and 1 or outside the table, or more word deltas than regions"
+			                        : ": a cmap subtable whose segments or groups are not regular");
 			return -1;
 		}
 		desc->cmap = t.cmap, desc->cmap_len = t.cmap_len;
@@ -858,6 +978,33 @@ int vg_manager_family_tables_desc(const vg_manager *m, const char *font_id, int 
 		desc->n_subtables = (uint16_t)t.subtable_off.size();
 		desc->subtable_off = t.subtable_off.data();
 		desc->subtable_format = t.subtable_format.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_family_variation_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_face_variation *desc)
+{
+	try {
+		if (!m || !font_id || !desc || file_index < 0) {
+			g_err = "vg_manager_family_variation_desc: bad argument";
+			return -1;
+		}
+		auto it = m->m.fonts().find(font_id);
+		if (it == m->m.fonts().end() || (size_t)file_index >= it->second.files().size()) {
+			g_err = std::string("unknown font id ") + font_id + ", or a file index past its files";
+			return -1;
+		}
+		const vg::FamilyTables &t = it->second.files()[(size_t)file_index]->face().family_tables();
+		if (!t.ok) {
+			g_err = std::string("refused: font ") + font_id +
+			        (t.hvar_refused ? ": an HVAR advance map of a format other than 0 and 1 or outside the table, or more word deltas than regions"
+			                        : ": a cmap subtable whose segments or groups are not regular");
+			return -1;
+		}
+		*desc = vgsdf_face_variation{t.hvar, t.hvar_len, t.hvar_store, t.hvar_map, t.hvar ? t.region_scalars.data() : nullptr,
+		                             t.hvar ? (uint32_t)t.region_scalars.size() : 0u};
 		return 0;
 	} catch (const std::exception &e) {
 		g_err = e.what();

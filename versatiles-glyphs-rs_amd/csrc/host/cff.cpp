@@ -240,27 +240,42 @@ std::optional<CffTable> CffTable::parse(Bytes table)
 	return t;
 }
 
-namespace {
-
-// factor of one axis of a variation region at normalised coordinate 0 (the crate's evaluate_axis with coord = 0; all
-// values F2Dot14 as integers).  Only 0 and 1 can come out: the interpolating branches need start < 0 < end with the
-// peak off 0, which the second rule has already answered with 1.
-float axis_factor_at_default(int start, int peak, int end)
+float axis_factor(int16_t coord, int16_t start, int16_t peak, int16_t end)
 {
 	if (start > peak || peak > end)
 		return 1.0f;
 	if (start < 0 && end > 0 && peak != 0)
 		return 1.0f;
-	if (peak == 0)
+	if (peak == 0 || coord == peak)
 		return 1.0f;
-	return 0.0f; // 0 <= start or end <= 0: outside the region (or on its border)
+	if (coord <= start || coord >= end)
+		return 0.0f; // outside the region (or on its border)
+	if (coord < peak)
+		return (float)(coord - start) / (float)(peak - start);
+	return (float)(end - coord) / (float)(end - peak);
 }
 
-} // namespace
+float variation_region_factor(Bytes list, uint32_t region, const std::vector<int16_t> &coords)
+{
+	const uint32_t axis_count = list.u16(0), region_count = list.u16(2);
+	const uint32_t n_records = axis_count * region_count;
+	float v = 1.0f;
+	for (uint32_t i = 0; i < coords.size(); i++) {
+		const uint32_t rec = region * axis_count + i;
+		if (region * axis_count > 0xFFFFu || rec > 0xFFFFu || rec >= n_records)
+			return 0.0f;
+		const size_t at = 4 + (size_t)rec * 6;
+		const float f = axis_factor(coords[i], list.i16(at), list.i16(at + 2), list.i16(at + 4));
+		if (f == 0.0f)
+			return 0.0f;
+		v *= f;
+	}
+	return v;
+}
 
 // OpenType `CFF2` table, as the crate's cff2::Table::parse reads it: header, Top DICT (CharStrings 17, FDArray 12 36,
 // vstore 24), global subroutines behind the Top DICT, ItemVariationStore, the first local subroutines found.
-std::optional<CffTable> CffTable::parse2(Bytes table, uint32_t n_coords)
+std::optional<CffTable> CffTable::parse2(Bytes table, const std::vector<int16_t> &coords)
 {
 	if (!table.has(0, 5) || table.u8(0) != 2)
 		return std::nullopt;
@@ -310,22 +325,8 @@ std::optional<CffTable> CffTable::parse2(Bytes table, uint32_t n_coords)
 		const uint32_t n_records = axis_count * region_count;
 		if (n_records > 0xFFFFu || !st.has(regions_at + 4, (size_t)n_records * 6))
 			return std::nullopt;
-		auto region_factor = [&](uint32_t region) {
-			float v = 1.0f;
-			for (uint32_t i = 0; i < n_coords; i++) {
-				// (flat record index in 16 bits, as the crate computes it: a face with more coordinates than the
-				// store has axes reads on into the next region's records)
-				const uint32_t rec = region * axis_count + i;
-				if (region * axis_count > 0xFFFFu || rec > 0xFFFFu || rec >= n_records)
-					return 0.0f;
-				const size_t at = regions_at + 4 + (size_t)rec * 6;
-				const float f = axis_factor_at_default(st.i16(at), st.i16(at + 2), st.i16(at + 4));
-				if (f == 0.0f)
-					return 0.0f;
-				v *= f;
-			}
-			return v;
-		};
+		const Bytes list = st.from(regions_at);
+		auto region_factor = [&](uint32_t region) { return variation_region_factor(list, region, coords); };
 		t.blend_sets_.resize(n_data);
 		for (uint32_t d = 0; d < n_data; d++) {
 			const size_t at = st.u32(8 + (size_t)d * 4);

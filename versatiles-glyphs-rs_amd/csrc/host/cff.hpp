@@ -25,6 +25,13 @@
 // loaded before the first operator, so a table without a VariationStore yields no outline at all.
 // PARITY UNPINNED like the rest of CFF, and more so: these rules are restated from the crate's documented behaviour
 // without a fixture; the default-position outlines are checked against fontTools (tests/test_cff2_outlines.py).
+//
+// A face made by Face::parse_at carries coordinates other than 0 (the crate's set_variation): the factor of an axis of a
+// region is then axis_factor below at the face's coordinate — 1 for a malformed or neutral axis, 0 at and outside the region's
+// ends, else ONE f32 divide of the two differences, each converted to f32 first — and a region's factor the f32 product over
+// the face's coordinates in axis order, 0 as soon as one factor is 0.  These rules (and those of `avar` and `HVAR` in
+// ttf_face.hpp) are restated from the crate's set_variation / glyph_hor_advance as read, without the crate at hand: parity
+// UNPINNED as well; outlines at a position are checked against fontTools (tests/test_variable_instances_host.py).
 #pragma once
 #include <cstdint>
 #include <optional>
@@ -34,11 +41,22 @@
 
 namespace vg {
 
+// Factor of one axis of a variation region at normalised coordinate `coord` (the crate's evaluate_axis; all values F2Dot14 as
+// integers).  At coord 0 only 0 and 1 can come out: the interpolating branches need start < 0 < end with the peak off 0, which
+// the second rule has already answered with 1.
+float axis_factor(int16_t coord, int16_t start, int16_t peak, int16_t end);
+// Factor of region `region` of a VariationRegionList (`list` from its axisCount; the caller has checked that its
+// axisCount * regionCount records of 6 bytes lie inside) at `coords`: the product above.  The flat record index is kept in 16
+// bits, as the crate computes it: a face with more coordinates than the list has axes reads on into the next region's records,
+// and an index past 0xFFFF or past the records gives 0.
+float variation_region_factor(Bytes list, uint32_t region, const std::vector<int16_t> &coords);
+
 class CffTable {
 public:
 	static std::optional<CffTable> parse(Bytes table);
-	// `CFF2`; n_coords = the face's variation coordinates (fvar axes, at most 64; all at 0), 0 without `fvar`
-	static std::optional<CffTable> parse2(Bytes table, uint32_t n_coords);
+	// `CFF2`; coords = the face's normalised variation coordinates (F2Dot14; one per fvar axis, at most 64; all 0 for a face
+	// made by Face::parse), none without `fvar`
+	static std::optional<CffTable> parse2(Bytes table, const std::vector<int16_t> &coords);
 	bool is_cff2() const { return cff2_; }
 	uint32_t number_of_glyphs() const { return charstrings_.count; }
 	// false = ttf-parser returns None (callbacks already delivered stay delivered)
@@ -77,7 +95,7 @@ private:
 	std::vector<PrivateDict> fd_priv_; // CID-keyed fonts: one per font dict
 	Bytes fd_select_;                  // CID-keyed fonts: FDSelect, from its format byte
 	size_t charset_at_ = 0;            // Top DICT `charset`: 0 / 1 / 2 = ISOAdobe / Expert / ExpertSubset, else its offset
-	// CFF2: per ItemVariationData subtable the factor of each of its regions at the default position
+	// CFF2: per ItemVariationData subtable the factor of each of its regions at the face's position
 	struct BlendSet {
 		bool ok = false; // false: no such subtable, or more than 64 regions (the crate's limit)
 		std::vector<float> scalars;

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <cmath>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
@@ -61,14 +62,15 @@ std::string name_to_id(const std::string &name)
 	return out;
 }
 
-std::unique_ptr<FontFileEntry> FontFileEntry::create(std::vector<uint8_t> data, std::string *err)
+std::unique_ptr<FontFileEntry> FontFileEntry::create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords)
 {
 	std::unique_ptr<FontFileEntry> e(new FontFileEntry());
 	e->data_ = std::move(data);
-	auto face = Face::parse(e->data_.data(), e->data_.size());
+	std::string why = "font parse failed";
+	auto face = coords ? Face::parse_at(e->data_.data(), e->data_.size(), *coords, &why) : Face::parse(e->data_.data(), e->data_.size());
 	if (!face) {
 		if (err)
-			*err = "font parse failed";
+			*err = why;
 		return nullptr;
 	}
 	e->face_ = *face;
@@ -210,6 +212,52 @@ bool FontManager::add_font_data(const std::string &name, std::vector<uint8_t> da
 	invalidate_shards();
 	fonts_[name_to_id(name)].add_file(std::move(e));
 	return true;
+}
+
+bool FontManager::add_font_instance_normalized(const std::string &name, std::vector<uint8_t> data, const std::vector<int16_t> &coords,
+                                               std::string *err)
+{
+	auto e = FontFileEntry::create(std::move(data), err, &coords);
+	if (!e)
+		return false;
+	invalidate_shards();
+	fonts_[name_to_id(name)].add_file(std::move(e));
+	return true;
+}
+
+bool FontManager::add_font_instance(const std::string &name, std::vector<uint8_t> data, const std::vector<std::array<char, 4>> &tags,
+                                    const std::vector<float> &values, std::string *err)
+{
+	auto refuse = [&](const std::string &why) {
+		if (err)
+			*err = why;
+		return false;
+	};
+	std::vector<VariationAxis> axes;
+	if (!read_variation_axes(data.data(), data.size(), axes))
+		return refuse("a position needs a readable fvar table, and this file has none");
+	if (tags.size() != values.size())
+		return refuse("add_font_instance: as many values as tags");
+	if (axes.size() > 64)
+		axes.resize(64); // (the face counts no more)
+	std::vector<int16_t> coords(axes.size(), 0);
+	std::vector<bool> given(axes.size(), false);
+	for (size_t k = 0; k < tags.size(); k++) {
+		const std::string tag(tags[k].data(), 4);
+		if (!std::isfinite(values[k]))
+			return refuse("axis " + tag + ": a value that is not finite");
+		size_t i = 0;
+		while (i < axes.size() && std::memcmp(axes[i].tag, tags[k].data(), 4) != 0)
+			i++;
+		if (i == axes.size())
+			return refuse("axis " + tag + ": the file's fvar has no such axis");
+		if (given[i])
+			return refuse("axis " + tag + ": given twice");
+		given[i] = true;
+		coords[i] = normalize_axis_value(axes[i], values[k]);
+	}
+	apply_avar(data.data(), data.size(), coords);
+	return add_font_instance_normalized(name, std::move(data), coords, err);
 }
 
 bool FontManager::add_path(const std::string &path, std::string *err)

@@ -56,7 +56,8 @@ struct Writer {
 // file_entry.rs: owns the bytes, the parsed face and the cmap coverage
 class FontFileEntry {
 public:
-	static std::unique_ptr<FontFileEntry> create(std::vector<uint8_t> data, std::string *err);
+	// coords: the face at that position (Face::parse_at) instead of as parsed
+	static std::unique_ptr<FontFileEntry> create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords = nullptr);
 	const Face &face() const { return face_; }
 	const std::vector<uint32_t> &codepoints() const { return codepoints_; } // metadata.rs:105-119
 	const FontMetadata &metadata() const { return metadata_; }                // metadata.rs:89-103
@@ -213,6 +214,15 @@ public:
 	// manager.rs:66-75
 	bool add_font_with_name(const std::string &name, const std::vector<std::string> &sources, std::string *err);
 	bool add_font_data(const std::string &name, std::vector<uint8_t> data, std::string *err);
+	// A variable file at a position of its design space, under a name of the caller's: a file like any other from here on (the
+	// same name merges, another name is another font id; every instance is a Face of its own with its own serials, so no two
+	// share a store on a device).  Normalised: final coordinates, one per fvar axis.  The other form takes user-space values by
+	// axis tag (4 bytes each), axes not named stay at their default; values are normalised (normalize_axis_value) and sent
+	// through the file's avar (apply_avar).  false: an unknown tag, a tag twice, a value that is not finite, or what
+	// Face::parse_at refuses.
+	bool add_font_instance_normalized(const std::string &name, std::vector<uint8_t> data, const std::vector<int16_t> &coords, std::string *err);
+	bool add_font_instance(const std::string &name, std::vector<uint8_t> data, const std::vector<std::array<char, 4>> &tags,
+	                       const std::vector<float> &values, std::string *err);
 	// manager.rs:39-53: the file's own name table decides the font id (family + width + weight + style
 	// through parse_font_name / generate_name / name_to_id); files with the same id merge, in call order
 	bool add_path(const std::string &path, std::string *err);
@@ -295,7 +305,8 @@ public:
 	bool mixes() const { return mixed_stores_ && glyf_on_device_ && resident_fonts_ && resident_commands_ == 1; }
 	// Command stores of `CFF ` version 1 faces decoded on the device from the charstrings (vgsdf_font_create_charstrings) instead
 	// of uploaded from command_table(); a face the device refuses falls back.  Default off.  The stores' bytes are the same.
-	// 2: CFF2 faces too (vgsdf_font_create_charstrings2, with the reader's blend factors: the default position).
+	// 2: CFF2 faces too (vgsdf_font_create_charstrings2, with the reader's blend factors: those of the face's position, the
+	// default one unless the file was added by add_font_instance).
 	void set_charstrings_on_device(int mode) { charstrings_on_device_ = mode < 0 || mode > 2 ? 0 : mode; }
 	const CharstringTable *charstring_table(const std::string &font_id, size_t file_index, std::string *err) const;
 	const CharstringTable *charstring2_table(const std::string &font_id, size_t file_index, std::string *err) const;
@@ -309,6 +320,8 @@ public:
 	// Family tables on the device (default off): a resident family's table is built by the device from the faces' cmap and hmtx
 	// tables (Face::family_tables, vgsdf_family_create_tables) and family_table() below is not built for the font id; a font id
 	// whose description refuses, or whose build the device refuses, gets its family the host's way (remembered).  Same table bytes.
+	// A file at a position (add_font_instance) hands its HVAR and the factors of its regions over as well
+	// (vgsdf_family_create_tables_var): the device adds the advance's offset where the host's reader would.
 	void set_family_tables_on_device(bool on) { family_tables_on_device_ = on; }
 	// Glyf tables on the device (default off): wherever the renderer makes a glyf-kind resident font — glyph-named groups, the
 	// families, preload_resident_fonts — the DEVICE walks the face's loca and glyf (Face::font_tables, vgsdf_font_create_tables)

@@ -424,6 +424,7 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 		// host's way below, for good
 		FamilyTable *shell = family_shell(font_id, font.files().size());
 		std::vector<vgsdf_face_tables> descs;
+		std::vector<vgsdf_face_variation> variation; // filled once a face at a position with an HVAR is met
 		for (const auto &file : font.files()) {
 			const FamilyTables &t = file->face().family_tables();
 			if (!t.ok) {
@@ -439,11 +440,15 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 			d.n_subtables = (uint16_t)t.subtable_off.size();
 			d.subtable_off = t.subtable_off.data(), d.subtable_format = t.subtable_format.data();
 			descs.push_back(d);
+			if (t.hvar || !variation.empty()) {
+				variation.resize(descs.size(), vgsdf_face_variation{nullptr, 0, 0, 0, nullptr, 0});
+				variation.back() = vgsdf_face_variation{t.hvar, t.hvar_len, t.hvar_store, t.hvar_map, t.region_scalars.data(), (uint32_t)t.region_scalars.size()};
+			}
 		}
 		if (descs.size() == font.files().size()) {
 			int refused = 0;
 			bool built = false;
-			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, family_kind, &uploaded, &refused, &built);
+			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, family_kind, &uploaded, &refused, &built, variation);
 			if (refused == 1)
 				counts.family_table_fallbacks++;
 			if (built) {

@@ -715,7 +715,7 @@ const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std:
 
 const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
                                                  const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
-                                                 bool *built) const
+                                                 bool *built, const std::vector<vgsdf_face_variation> &variation) const
 {
 	if (mode_ != Mode::Hip)
 		return nullptr;
@@ -736,8 +736,10 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 	vgsdf_family *f = nullptr;
 	{
 		std::lock_guard<std::mutex> lock(mu_);
-		if (tables.size() != fonts.size() ||
-		    (kind == kFamilyMixed ? vgsdf_family_create_tables_mixed(c, &d, &f) : vgsdf_family_create_tables(c, &d, &f)) != VGSDF_OK) {
+		const vgsdf_face_variation *var = variation.empty() ? nullptr : variation.data();
+		if (tables.size() != fonts.size() || (var && variation.size() != fonts.size()) ||
+		    (var ? (kind == kFamilyMixed ? vgsdf_family_create_tables_var_mixed(c, &d, var, &f) : vgsdf_family_create_tables_var(c, &d, var, &f))
+		         : (kind == kFamilyMixed ? vgsdf_family_create_tables_mixed(c, &d, &f) : vgsdf_family_create_tables(c, &d, &f))) != VGSDF_OK) {
 			rf.refused_family_tables.insert(key);
 			*refused = 1;
 			return nullptr;

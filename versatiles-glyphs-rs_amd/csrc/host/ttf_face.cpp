@@ -59,17 +59,135 @@ Bytes find_table(Bytes file, const char tag[4])
 
 } // namespace
 
-std::optional<Face> Face::parse(const uint8_t *data, size_t len)
+std::optional<Face> Face::parse(const uint8_t *data, size_t len) { return parse_impl(data, len, nullptr, nullptr); }
+
+std::optional<Face> Face::parse_at(const uint8_t *data, size_t len, const std::vector<int16_t> &coords, std::string *err)
 {
+	return parse_impl(data, len, &coords, err);
+}
+
+namespace {
+// the axes of a readable `fvar` (version 1.0, at least one axis, the axis records of 20 bytes each inside the table), 0: none
+uint32_t fvar_axes(Bytes fvar, size_t &axes_at)
+{
+	if (!fvar.has(0, 10) || fvar.u32(0) != 0x00010000u)
+		return 0;
+	axes_at = fvar.u16(4);
+	const uint32_t n_axes = fvar.u16(8);
+	return n_axes != 0 && fvar.has(axes_at, (size_t)n_axes * 20) ? n_axes : 0;
+}
+float fixed_to_float(uint32_t v) { return (float)(int32_t)v / 65536.0f; }
+} // namespace
+
+bool read_variation_axes(const uint8_t *data, size_t len, std::vector<VariationAxis> &axes, std::vector<NamedInstance> *instances)
+{
+	const Bytes fvar = find_table(Bytes(data, len), "fvar");
+	size_t axes_at = 0;
+	const uint32_t n = fvar_axes(fvar, axes_at);
+	if (!n)
+		return false;
+	axes.clear();
+	for (uint32_t i = 0; i < n; i++) {
+		const size_t at = axes_at + (size_t)i * 20;
+		VariationAxis a;
+		std::memcpy(a.tag, fvar.data() + at, 4);
+		a.min = fixed_to_float(fvar.u32(at + 4)), a.def = fixed_to_float(fvar.u32(at + 8)), a.max = fixed_to_float(fvar.u32(at + 12));
+		axes.push_back(a);
+	}
+	if (instances) {
+		instances->clear();
+		if (fvar.has(0, 16)) {
+			const size_t axis_size = fvar.u16(10), n_inst = fvar.u16(12), inst_size = fvar.u16(14);
+			const size_t first = axes_at + (size_t)n * axis_size;
+			for (size_t k = 0; k < n_inst && inst_size >= 4 + (size_t)n * 4; k++) {
+				const size_t at = first + k * inst_size;
+				if (!fvar.has(at, inst_size))
+					break;
+				NamedInstance ni;
+				ni.name_id = fvar.u16(at);
+				for (uint32_t i = 0; i < n; i++)
+					ni.coords.push_back(fixed_to_float(fvar.u32(at + 4 + (size_t)i * 4)));
+				instances->push_back(std::move(ni));
+			}
+		}
+	}
+	return true;
+}
+
+int16_t normalize_axis_value(const VariationAxis &axis, float v)
+{
+	v = v < axis.min ? axis.min : v > axis.max ? axis.max : v;
+	float n;
+	if (v == axis.def)
+		n = 0.0f;
+	else if (v < axis.def)
+		n = (v - axis.def) / (axis.def - axis.min);
+	else
+		n = (v - axis.def) / (axis.max - axis.def);
+	n = n < -1.0f ? -1.0f : n > 1.0f ? 1.0f : n;
+	return (int16_t)(n * 16384.0f); // (|n| <= 1, or NaN from a degenerate axis: sent to 0)
+}
+
+void apply_avar(const uint8_t *data, size_t len, std::vector<int16_t> &coords)
+{
+	const Bytes avar = find_table(Bytes(data, len), "avar");
+	if (!avar.has(0, 8) || avar.u32(0) != 0x00010000u || avar.u16(6) != coords.size())
+		return;
+	size_t at = 8;
+	for (int16_t &coord : coords) {
+		if (!avar.has(at, 2))
+			return;
+		const size_t n = avar.u16(at);
+		if (!avar.has(at + 2, n * 4))
+			return;
+		// (i64: the product of two differences of i16 values does not fit i32; a result outside i16 is discarded below)
+		auto from = [&](size_t i) { return (int64_t)avar.i16(at + 2 + i * 4); };
+		auto to = [&](size_t i) { return (int64_t)avar.i16(at + 4 + i * 4); };
+		const int64_t v = coord;
+		int64_t r = v;
+		if (n == 1) {
+			r = v - from(0) + to(0);
+		} else if (n > 1) {
+			if (v <= from(0)) {
+				r = v - from(0) + to(0);
+			} else {
+				size_t i = 1;
+				while (i < n && v > from(i))
+					i++;
+				if (i == n)
+					i = n - 1;
+				if (v >= from(i)) {
+					r = v - from(i) + to(i);
+				} else if (from(i - 1) == from(i)) {
+					r = to(i - 1);
+				} else {
+					const int64_t d = from(i) - from(i - 1);
+					r = to(i - 1) + ((to(i) - to(i - 1)) * (v - from(i - 1)) + d / 2) / d;
+				}
+			}
+		}
+		if (r >= -32768 && r <= 32767)
+			coord = (int16_t)r;
+		at += 2 + n * 4;
+	}
+}
+
+std::optional<Face> Face::parse_impl(const uint8_t *data, size_t len, const std::vector<int16_t> *at_coords, std::string *err)
+{
+	auto refuse = [&](const char *why) {
+		if (err)
+			*err = why;
+		return std::nullopt;
+	};
 	Bytes file(data, len);
 	const Bytes head = find_table(file, "head"), maxp = find_table(file, "maxp"),
 	            hhea = find_table(file, "hhea");
 	if (!head.has(0, 54) || !maxp.has(0, 6) || !hhea.has(0, 36))
-		return std::nullopt;
+		return refuse("font parse failed");
 	Face f;
 	f.units_per_em_ = head.u16(18);
 	if (f.units_per_em_ < 16 || f.units_per_em_ > 16384)
-		return std::nullopt;
+		return refuse("font parse failed");
 	f.loca_long_ = head.i16(50) != 0;
 	f.num_glyphs_ = maxp.u16(4);
 	f.num_hmetrics_ = hhea.u16(34);
@@ -92,15 +210,12 @@ std::optional<Face> Face::parse(const uint8_t *data, size_t len)
 	if (const Bytes cff2 = find_table(file, "CFF2"); !f.cff_ && !cff2.empty()) {
 		// ttf-parser: glyf, then cff1, then cff2 — drawn at the face's variation coordinates, which the reference
 		// leaves at their defaults: one (zero) coordinate per `fvar` axis, at most 64, none without a readable `fvar`
-		// (version 1.0, at least one axis, the axis records of 20 bytes each inside the table)
-		uint32_t n_coords = 0;
-		if (const Bytes fvar = find_table(file, "fvar"); fvar.has(0, 10) && fvar.u32(0) == 0x00010000u) {
-			const size_t axes_at = fvar.u16(4);
-			const uint32_t n_axes = fvar.u16(8);
-			if (n_axes != 0 && fvar.has(axes_at, (size_t)n_axes * 20))
-				n_coords = std::min<uint32_t>(n_axes, 64);
-		}
-		if (auto t = CffTable::parse2(cff2, n_coords))
+		// (parse_at: the coordinates it was given, checked below to be as many)
+		size_t axes_at = 0;
+		std::vector<int16_t> coords(std::min<uint32_t>(fvar_axes(find_table(file, "fvar"), axes_at), 64), 0);
+		if (at_coords && at_coords->size() == coords.size())
+			coords = *at_coords;
+		if (auto t = CffTable::parse2(cff2, coords))
 			f.cff_ = std::make_shared<const CffTable>(std::move(*t));
 		else
 			f.cff_unreadable_ = true;
@@ -122,6 +237,45 @@ std::optional<Face> Face::parse(const uint8_t *data, size_t len)
 			if (st.data.has(0, 2))
 				st.format = st.data.u16(0);
 			f.cmap_.push_back(st);
+		}
+	}
+	if (at_coords) {
+		size_t axes_at = 0;
+		const uint32_t n_axes = std::min<uint32_t>(fvar_axes(find_table(file, "fvar"), axes_at), 64);
+		if (!n_axes)
+			return refuse("a position needs a readable fvar table, and this file has none");
+		if (f.has_glyf_outlines())
+			return refuse("a position for a face with glyf outlines is not supported (no gvar reader)");
+		if (at_coords->size() != n_axes)
+			return refuse("the number of coordinates is not the number of fvar axes (at most 64 are counted)");
+		f.at_position_ = true;
+		f.coords_ = *at_coords;
+		// HVAR: majorVersion, minorVersion, the store's offset, the advance map's (0: none), two more maps
+		const Bytes hvar = find_table(file, "HVAR");
+		if (hvar.has(0, 20) && hvar.u16(0) == 1 && hvar.size() <= 0xFFFFFFFFu) {
+			const size_t store = hvar.u32(4);
+			const Bytes st = hvar.from(store);
+			if (st.has(0, 8)) {
+				if (st.u16(0) != 1)
+					return refuse("HVAR: an ItemVariationStore of a format other than 1");
+				const size_t regions_at = st.u32(2);
+				const uint32_t n_data = st.u16(6);
+				if (st.has(8, (size_t)n_data * 4) && st.has(regions_at, 4) &&
+				    st.has(regions_at + 4, (size_t)st.u16(regions_at) * st.u16(regions_at + 2) * 6)) {
+					for (uint32_t d = 0; d < n_data; d++) {
+						const size_t at = st.u32(8 + (size_t)d * 4);
+						if (st.has(at, 6) && (st.u16(at + 2) & 0x8000u))
+							return refuse("HVAR: an ItemVariationData with 32-bit deltas (LONG_WORDS)");
+					}
+					const Bytes list = st.from(regions_at);
+					const uint32_t n_regions = list.u16(2);
+					for (uint32_t r = 0; r < n_regions; r++)
+						f.hvar_scalars_.push_back(variation_region_factor(list, r, f.coords_));
+					f.hvar_ = hvar;
+					f.hvar_store_ = (uint32_t)store;
+					f.hvar_map_ = hvar.u32(8);
+				}
+			}
 		}
 	}
 	return f;
@@ -196,7 +350,75 @@ std::optional<uint16_t> Face::glyph_hor_advance(uint16_t gid) const
 		return std::nullopt;
 	// fewer long metrics than glyphs: the last advance applies to the rest
 	const size_t i = std::min<size_t>(gid, (size_t)num_hmetrics_ - 1);
-	return hmtx_.u16(i * 4);
+	if (!at_position_)
+		return hmtx_.u16(i * 4);
+	// the crate's variable path: f32 throughout, `+ 0.5` for rounding, u16::try_from of the truncated value
+	float a = (float)hmtx_.u16(i * 4);
+	if (const auto delta = hvar_advance_delta(gid))
+		a += *delta + 0.5f;
+	if (!(a > -1.0f && a < 65536.0f))
+		return std::nullopt;
+	return (uint16_t)(int32_t)a;
+}
+
+std::vector<uint16_t> Face::hor_advances(uint32_t n) const
+{
+	std::vector<uint16_t> out(n, 0);
+	for (uint32_t g = 0; g < n && g <= 0xFFFFu; g++)
+		out[g] = glyph_hor_advance((uint16_t)g).value_or(0);
+	return out;
+}
+
+std::optional<float> Face::hvar_advance_delta(uint16_t gid) const
+{
+	if (hvar_.empty())
+		return std::nullopt;
+	uint32_t outer = 0, inner = gid;
+	if (hvar_map_ != 0) { // DeltaSetIndexMap: format, entryFormat, mapCount (u16: format 0, u32: format 1), entries
+		const Bytes m = hvar_.from(hvar_map_);
+		if (!m.has(0, 2))
+			return std::nullopt;
+		const uint32_t format = m.u8(0), ef = m.u8(1);
+		if (format > 1 || !m.has(2, format ? 4 : 2))
+			return std::nullopt;
+		const uint32_t count = format ? m.u32(2) : m.u16(2);
+		if (count == 0)
+			return std::nullopt;
+		const size_t entry_size = ((ef >> 4) & 3) + 1, at = (format ? 6 : 4) + entry_size * std::min<uint32_t>(gid, count - 1);
+		if (!m.has(at, entry_size))
+			return std::nullopt;
+		uint32_t n = 0;
+		for (size_t k = 0; k < entry_size; k++)
+			n = (n << 8) | m.u8(at + k);
+		const uint32_t bits = (ef & 15) + 1;
+		outer = n >> bits, inner = n & ((1u << bits) - 1);
+		if (outer > 0xFFFFu)
+			return std::nullopt;
+	}
+	const Bytes st = hvar_.from(hvar_store_);
+	if (outer >= st.u16(6))
+		return std::nullopt;
+	const size_t at = st.u32(8 + (size_t)outer * 4);
+	if (!st.has(at, 6))
+		return std::nullopt;
+	const uint32_t item_count = st.u16(at), words = st.u16(at + 2), n_cols = st.u16(at + 4); // (no LONG_WORDS: parse_at)
+	if (!st.has(at + 6, (size_t)n_cols * 2) || inner >= item_count || words > n_cols)
+		return std::nullopt;
+	const size_t row = at + 6 + (size_t)n_cols * 2 + (size_t)inner * (words + n_cols);
+	if (!st.has(row, (size_t)words + n_cols))
+		return std::nullopt;
+	float delta = 0.0f;
+	size_t p = row;
+	for (uint32_t c = 0; c < n_cols; c++) {
+		const uint32_t region = st.u16(at + 6 + (size_t)c * 2);
+		float num;
+		if (c < words)
+			num = (float)st.i16(p), p += 2;
+		else
+			num = (float)(int8_t)st.u8(p), p += 1;
+		delta += num * (region < hvar_scalars_.size() ? hvar_scalars_[region] : 0.0f);
+	}
+	return delta;
 }
 
 // ---- cmap ------------------------------------------------------------------------------
@@ -474,6 +696,31 @@ const FamilyTables &Face::family_tables() const
 			t.subtable_format.push_back(st.format);
 		}
 		t.ok = t.subtable_off.size() <= 0xFFFFu;
+		if (!hvar_.empty()) {
+			// An advance map outside the table is what vgsdf_family_create_tables_var refuses.  A map of a format above 1 and
+			// more word deltas than regions are refused here as well although the kernel answers both as the reader does, with
+			// "no delta" (tests/test_gpu_family_tables_var_regimes.py holds it to that): no font tool writes such a table, and
+			// a font id that has one goes the road every other refusal goes instead of being a case of its own on the device
+			bool fits = true;
+			if (hvar_map_ != 0) {
+				const Bytes m = hvar_.from(hvar_map_);
+				fits = hvar_map_ < hvar_.size() && !(m.has(0, 1) && m.u8(0) > 1);
+			}
+			const Bytes st = hvar_.from(hvar_store_);
+			for (uint32_t d = 0, n_data = st.u16(6); d < n_data; d++) {
+				const size_t at = st.u32(8 + (size_t)d * 4);
+				if (st.has(at, 6) && st.u16(at + 2) > st.u16(at + 4))
+					fits = false;
+			}
+			if (!fits) {
+				t.hvar_refused = true;
+				t.ok = false;
+				return;
+			}
+			t.hvar = hvar_.data(), t.hvar_len = (uint32_t)hvar_.size();
+			t.hvar_store = hvar_store_, t.hvar_map = hvar_map_;
+			t.region_scalars = hvar_scalars_;
+		}
 	});
 	return cell.tables;
 }

@@ -88,7 +88,8 @@ struct CharstringTable {
 	std::vector<uint32_t> lsubr_first; // [n_fds + 1]
 	std::vector<uint32_t> lsubr_off;   // [lsubr_first[n_fds] + 1]
 	std::vector<uint8_t> fd_of;        // [numGlyphs], empty when n_fds == 1
-	// CFF2 only: the blend sets, one per ItemVariationData of the variation store, with the reader's factors (default position)
+	// CFF2 only: the blend sets, one per ItemVariationData of the variation store, with the reader's factors (at the face's
+	// position: the default one unless the face was made by Face::parse_at)
 	bool cff2 = false;
 	std::vector<uint8_t> set_ok;       // [sets] 0: a charstring that selects the set ends there
 	std::vector<uint32_t> set_off;     // [sets + 1] into factors
@@ -105,7 +106,36 @@ struct FamilyTables {
 	uint16_t units_per_em = 0, num_glyphs = 0, num_hmetrics = 0;
 	std::vector<uint32_t> subtable_off;    // into cmap: the encoding records, in the table's order, that are unicode and of format
 	std::vector<uint16_t> subtable_format; // 0, 4, 6, 10, 12 or 13 (2, 8, 14 and unreadable ones map nothing and are left out)
+	// a face at a position whose advances follow `HVAR` (vgsdf_face_variation of include/vgsdf.h, field for field); hvar is
+	// nullptr for every other face.  Not ok as well (hvar_refused): an advance map of a format other than 0 and 1, or an
+	// ItemVariationData with more word deltas than regions — the reader gives such glyphs their `hmtx` advance, the device is
+	// not asked to
+	bool hvar_refused = false;
+	const uint8_t *hvar = nullptr;
+	uint32_t hvar_len = 0, hvar_store = 0, hvar_map = 0; // offsets into hvar; hvar_map 0: no advance map
+	std::vector<float> region_scalars; // the factor of every region of the store at the face's position
 };
+
+// What `fvar` offers (host only): its axes in user space, and its named instances
+struct VariationAxis {
+	char tag[4];
+	float min, def, max;
+};
+struct NamedInstance {
+	uint16_t name_id;
+	std::vector<float> coords; // one per axis, user space
+};
+// false: no readable `fvar` (version 1.0, at least one axis, the axis records inside the table).  Instance records that
+// leave the table are left out.
+bool read_variation_axes(const uint8_t *data, size_t len, std::vector<VariationAxis> &axes, std::vector<NamedInstance> *instances = nullptr);
+// A user-space value of an axis as a normalised coordinate (F2Dot14), in f32: clamped to [min, max]; 0 at the default, else
+// (v - def) / (def - min) below it and (v - def) / (max - def) above; clamped to [-1, 1], times 16384, truncated toward zero.
+// (The crate's rule as read; whether it truncates or rounds is unpinned.)
+int16_t normalize_axis_value(const VariationAxis &axis, float v);
+// The file's `avar` (version 1.0 with as many segment maps as there are coordinates; anything else changes nothing) applied
+// to normalised coordinates in place: per axis the piecewise-linear map over its records in i32 with rounding, truncating
+// division; an empty map, or a result outside i16, leaves the value as it is.
+void apply_avar(const uint8_t *data, size_t len, std::vector<int16_t> &coords);
 
 // A `glyf` face's `loca` and `glyf` for the device's table builder (vgsdf_font_tables_desc of include/vgsdf.h, field for field):
 // views of the two tables and the three numbers Face::glyph_data goes by.  No glyph is looked at.
@@ -145,10 +175,30 @@ class Face {
 public:
 	// Face::parse(data, 0).  The bytes must outlive the Face.
 	static std::optional<Face> parse(const uint8_t *data, size_t len);
+	// (The rules of a position — normalisation, avar, region factors, HVAR — are the crate's set_variation / glyph_hor_advance as
+	// read, without the crate at hand: PARITY UNPINNED, see cff.hpp.)
+	// The same face AT A POSITION of its design space (the crate's set_variation for every axis): coords are final normalised
+	// coordinates, F2Dot14, one per `fvar` axis (at most 64 are counted).  CFF2 outlines, and everything built from them, are
+	// drawn there, and glyph_hor_advance follows `HVAR`.  Refused (nullopt, *err says why): a file without a readable `fvar`,
+	// a face whose outlines are `glyf` (there is no `gvar` reader), a coordinate count other than the axes', an `HVAR` whose
+	// store is not of format 1 or holds 32-bit deltas (LONG_WORDS).  An `HVAR` that cannot be read at all (major version not
+	// 1, a header, store header or region list outside the table) counts as absent, as the crate drops it.
+	static std::optional<Face> parse_at(const uint8_t *data, size_t len, const std::vector<int16_t> &coords, std::string *err = nullptr);
+	// made by parse_at (even at all-zero coordinates)
+	bool at_position() const { return at_position_; }
+	const std::vector<int16_t> &coords() const { return coords_; }
+	// every glyph id's glyph_hor_advance().value_or(0), for ids 0 .. n - 1 (test / inspection: ids at and past numGlyphs give 0)
+	std::vector<uint16_t> hor_advances(uint32_t n) const;
+	// parse_at with an `HVAR`: the factor of every region of its store at the face's position, evaluated once
+	const std::vector<float> &hvar_region_scalars() const { return hvar_scalars_; }
+	// ... and the offset `HVAR` has for the glyph's advance there (nullopt: none — no map entry, an index outside the store, a
+	// row that leaves the table): the sum over the row's columns of delta * factor, one f32 product and one f32 sum each
+	std::optional<float> hvar_advance_delta(uint16_t glyph_id) const;
 
 	uint16_t units_per_em() const { return units_per_em_; }
 	uint16_t number_of_glyphs() const { return num_glyphs_; }
 	std::optional<uint16_t> glyph_index(uint32_t code_point) const;
+	// (a face made by parse_at: (f32)advance + delta + 0.5, truncated; outside 0 .. 65535: none)
 	std::optional<uint16_t> glyph_hor_advance(uint16_t glyph_id) const;
 	// Emits the glyph's outline; returns false when ttf-parser would return None
 	// (callbacks already delivered stay delivered, as in the crate).
@@ -212,8 +262,14 @@ private:
 	};
 
 	std::optional<Bytes> glyph_data(uint16_t glyph_id) const;
+	static std::optional<Face> parse_impl(const uint8_t *data, size_t len, const std::vector<int16_t> *coords, std::string *err);
 
 	Bytes hmtx_, loca_, glyf_, name_, cmap_table_;
+	bool at_position_ = false;
+	std::vector<int16_t> coords_;
+	Bytes hvar_;                      // parse_at: the table when its store can be read, else empty
+	uint32_t hvar_store_ = 0, hvar_map_ = 0;
+	std::vector<float> hvar_scalars_; // one per region of the store
 	std::vector<CmapSubtable> cmap_;
 	uint16_t units_per_em_ = 0, num_glyphs_ = 0, num_hmetrics_ = 0;
 	bool loca_long_ = false, has_cmap_ = false, cff_unreadable_ = false;

@@ -110,8 +110,36 @@ int family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **ou
 	return VGSDF_OK;
 }
 
+// what can be said of a face's variation record without walking a glyph's row (vgsdf.h); nullptr: nothing against it
+const char *variation_refused(const vgsdf_face_variation &v)
+{
+	if ((v.hvar_len && !v.hvar) || (v.n_regions && !v.region_scalars))
+		return "a NULL HVAR table or factor array of a length that is not 0";
+	if (!v.hvar)
+		return v.hvar_len || v.n_regions ? "factors or a length without an HVAR table" : nullptr;
+	if ((uint64_t)v.store_off + 8 > v.hvar_len || v.map_off >= v.hvar_len)
+		return "an HVAR store or advance-map offset outside the table";
+	const uint8_t *st = v.hvar + v.store_off;
+	const uint64_t room = v.hvar_len - v.store_off;
+	auto be16 = [](const uint8_t *p) { return (uint32_t)((p[0] << 8) | p[1]); };
+	auto be32 = [](const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3]; };
+	if (be16(st) != 1)
+		return "an HVAR store of a format other than 1";
+	for (uint64_t d = 0, n = be16(st + 6); d < n && 8 + 4 * d + 4 <= room; d++) {
+		const uint64_t at = be32(st + 8 + 4 * d);
+		if (at <= room && 6 <= room - at && (be16(st + at + 2) & 0x8000u))
+			return "an HVAR ItemVariationData with 32-bit deltas (LONG_WORDS)";
+	}
+	for (uint32_t r = 0; r < v.n_regions; r++)
+		if (!std::isfinite(v.region_scalars[r]))
+			return "a region factor that is not finite";
+	return nullptr;
+}
+
 // vgsdf_family_create_tables and vgsdf_family_create_tables_mixed (the kernels take the kind face by face: FamilyFaceRef::commands)
-int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out, bool mixed, const char *me)
+// and their _var forms (var: NULL, or a record per face)
+int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out, bool mixed,
+                         const char *me)
 {
 	if (!ctx)
 		return VGSDF_E_ARG;
@@ -127,8 +155,10 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgs
 		return VGSDF_E_ARG;
 	}
 	// what can be said without a lookup; the staging block's layout on the way:
-	// FamilyFaceRef[n_fonts] | FamilySubtable[all] | per face cmap, hmtx (4-aligned) | counts | flags
-	size_t n_subtables = 0, table_bytes = 0;
+	// FamilyFaceRef[n_fonts] | FamilySubtable[all] | per face cmap, hmtx (4-aligned) |
+	// with a variation: FamilyFaceVar[n_fonts] | per face HVAR, factors (4-aligned) | then, 16-aligned: counts | flags
+	size_t n_subtables = 0, table_bytes = 0, var_bytes = 0;
+	bool any_var = false;
 	for (uint32_t k = 0; k < n_fonts; k++) {
 		const vgsdf_face_tables &t = in->tables[k];
 		if (!family_font_fits(ctx, in->fonts, k, mixed)) {
@@ -152,7 +182,19 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgs
 		}
 		n_subtables += t.n_subtables;
 		table_bytes += align_up(t.cmap_len, 4) + align_up(t.hmtx_len, 4);
+		if (var) {
+			if (const char *why = variation_refused(var[k])) {
+				ctx->err = std::string(me) + ": " + why;
+				return VGSDF_E_ARG;
+			}
+			if (var[k].hvar) {
+				any_var = true;
+				var_bytes += align_up(var[k].hvar_len, 4) + 4 * (size_t)var[k].n_regions;
+			}
+		}
 	}
+	if (any_var)
+		var_bytes += sizeof(vgsdf::FamilyFaceVar) * (size_t)n_fonts;
 	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
 	if (!f) {
 		ctx->err = std::string(me) + ": out of host memory";
@@ -160,7 +202,7 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgs
 	}
 	adopt_fonts(*f, ctx, in->fonts, n_fonts, mixed);
 	const size_t a_subs = sizeof(vgsdf::FamilyFaceRef) * (size_t)n_fonts, a_bytes = a_subs + sizeof(vgsdf::FamilySubtable) * n_subtables,
-	             a_counts = align_up(a_bytes + table_bytes, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
+	             a_var = align_up(a_bytes + table_bytes, 8), a_counts = align_up(a_var + var_bytes, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
 	             a_total = a_flags + 16;
 	(void)hipSetDevice(ctx->device);
 	hipStream_t st = ctx->stream;
@@ -195,6 +237,24 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgs
 			r.units_per_em = t.units_per_em, r.num_glyphs = t.num_glyphs, r.num_hmetrics = t.num_hmetrics, r.n_subtables = t.n_subtables;
 			r.commands = ft.commands ? 1u : 0u;
 		}
+		if (any_var) {
+			vgsdf::FamilyFaceVar *vars = (vgsdf::FamilyFaceVar *)(h.data() + a_var);
+			size_t at = a_var + sizeof(vgsdf::FamilyFaceVar) * (size_t)n_fonts;
+			for (uint32_t k = 0; k < n_fonts; k++) {
+				const vgsdf_face_variation &v = var[k];
+				vgsdf::FamilyFaceVar &r = vars[k]; // (zeroed: a static face)
+				if (!v.hvar)
+					continue;
+				r.hvar = (uint64_t)(uintptr_t)(d + at);
+				std::memcpy(h.data() + at, v.hvar, v.hvar_len);
+				at += align_up(v.hvar_len, 4);
+				r.scalars = (uint64_t)(uintptr_t)(d + at);
+				if (v.n_regions)
+					std::memcpy(h.data() + at, v.region_scalars, 4 * (size_t)v.n_regions);
+				at += 4 * (size_t)v.n_regions;
+				r.hvar_len = v.hvar_len, r.store_off = v.store_off, r.map_off = v.map_off, r.n_regions = v.n_regions;
+			}
+		}
 	}
 	PassEvents ev;
 	if (hipError_t err = ev.create(); err != hipSuccess)
@@ -226,7 +286,10 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgs
 		return font_hip_error(ctx, me, "hipMalloc", err);
 	std::vector<uint8_t> back(at.bytes);
 	q.record(ev.at[1]);
-	q.launch([&] { return vgsdf_family_tables_emit(faces, n_fonts, counts, n, (uint8_t *)f->table.p, st); });
+	q.launch([&] {
+		return any_var ? vgsdf_family_tables_emit_var(faces, (const vgsdf::FamilyFaceVar *)(d + a_var), n_fonts, counts, n, (uint8_t *)f->table.p, st)
+		               : vgsdf_family_tables_emit(faces, n_fonts, counts, n, (uint8_t *)f->table.p, st);
+	});
 	q.record(ev.at[2]);
 	q.read_back(back.data(), f->table.p, at.bytes);
 	q.sync();
@@ -268,11 +331,19 @@ int vgsdf_family_create_mixed(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf
 }
 int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out)
 {
-	return family_create_tables(ctx, in, out, false, "vgsdf_family_create_tables");
+	return family_create_tables(ctx, in, nullptr, out, false, "vgsdf_family_create_tables");
 }
 int vgsdf_family_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out)
 {
-	return family_create_tables(ctx, in, out, true, "vgsdf_family_create_tables_mixed");
+	return family_create_tables(ctx, in, nullptr, out, true, "vgsdf_family_create_tables_mixed");
+}
+int vgsdf_family_create_tables_var(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out)
+{
+	return family_create_tables(ctx, in, var, out, false, "vgsdf_family_create_tables_var");
+}
+int vgsdf_family_create_tables_var_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out)
+{
+	return family_create_tables(ctx, in, var, out, true, "vgsdf_family_create_tables_var_mixed");
 }
 
 void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]) { pass_ms_out(ctx ? ctx->family_tables_ms : nullptr, ms); }

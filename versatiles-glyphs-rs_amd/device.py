@@ -93,6 +93,11 @@ class _CFaceTables(C.Structure):  # vgsdf_face_tables
                 ("subtable_off", C.c_void_p), ("subtable_format", C.c_void_p)]
 
 
+class _CFaceVariation(C.Structure):  # vgsdf_face_variation
+    _fields_ = [("hvar", C.c_void_p), ("hvar_len", C.c_uint32), ("store_off", C.c_uint32), ("map_off", C.c_uint32),
+                ("region_scalars", C.c_void_p), ("n_regions", C.c_uint32)]
+
+
 class _CFamilyTablesDesc(C.Structure):  # vgsdf_family_tables_desc
     _fields_ = [("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("tables", C.c_void_p)]
 
@@ -120,6 +125,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_font_create_tables", "vgsdf_font_create_tables_within", "vgsdf_font_read", "vgsdf_font_tables_kernel_ms",
     "vgsdf_fonts_create_tables", "vgsdf_fonts_create_tables_within", "vgsdf_fonts_tables_kernel_ms",
     "vgsdf_outlines_submit_resident_mixed", "vgsdf_family_create_mixed", "vgsdf_family_create_tables_mixed",
+    "vgsdf_family_create_tables_var", "vgsdf_family_create_tables_var_mixed",
 ]
 
 _lib = None
@@ -200,6 +206,8 @@ def load_library():
         L.vgsdf_family_count.argtypes = [vp, C.c_uint32, C.c_uint32]
         L.vgsdf_family_count.restype = C.c_uint32
         L.vgsdf_family_create_tables.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), C.POINTER(vp)]
+        L.vgsdf_family_create_tables_var.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), vp, C.POINTER(vp)]
+        L.vgsdf_family_create_tables_var_mixed.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), vp, C.POINTER(vp)]
         L.vgsdf_family_read.argtypes = [vp, vp, C.POINTER(C.c_uint32)] + [vp] * 9
         L.vgsdf_family_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_family_tables_kernel_ms.restype = None
@@ -747,7 +755,14 @@ class SdfContext:
         self._check(getattr(load_library(), entry)(self._h, C.byref(d), C.byref(h)))
         return ResidentFamily(self, h, fonts)
 
-    def family_create_tables(self, fonts, faces, entry="vgsdf_family_create_tables") -> ResidentFamily:
+    def family_create_tables_var(self, fonts, faces, variation, mixed=False) -> ResidentFamily:
+        """vgsdf_family_create_tables_var (mixed: its _mixed twin): family_create_tables with, per font, what
+        FontManager.family_variation_desc returns: {hvar, store_off, map_off, region_scalars}, or {} / None for a static face;
+        variation None: no record at all"""
+        return self.family_create_tables(fonts, faces, entry="vgsdf_family_create_tables_var" + ("_mixed" if mixed else ""),
+                                         variation=[None] * len(fonts) if variation is None else variation, no_records=variation is None)
+
+    def family_create_tables(self, fonts, faces, entry="vgsdf_family_create_tables", variation=None, no_records=False) -> ResidentFamily:
         """vgsdf_family_create_tables: the family of `fonts` (ResidentFont, one kind, provider order) built on the device from
         `faces`, one dict per font as FontManager.family_tables_desc returns it: {cmap, hmtx (bytes or uint8 arrays),
         units_per_em, num_glyphs, num_hmetrics, subtable_off, subtable_format}"""
@@ -767,7 +782,21 @@ class SdfContext:
         handles = (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts])
         d = _CFamilyTablesDesc(len(fonts), C.cast(handles, C.c_void_p), C.cast(recs, C.c_void_p))
         h = C.c_void_p()
-        self._check(getattr(load_library(), entry)(self._h, C.byref(d), C.byref(h)))
+        if variation is None:
+            self._check(getattr(load_library(), entry)(self._h, C.byref(d), C.byref(h)))
+            return ResidentFamily(self, h, fonts)
+        assert len(variation) == len(fonts)
+        vrecs = (_CFaceVariation * max(len(fonts), 1))()
+        for r, v in zip(vrecs, variation):
+            if not v:
+                continue
+            hv = np.frombuffer(bytes(v["hvar"]), dtype=np.uint8)
+            sc = np.ascontiguousarray(v["region_scalars"], dtype=np.float32)
+            keep += [hv, sc]
+            r.hvar, r.hvar_len = (hv.ctypes.data if len(hv) else None), int(v.get("hvar_len", len(hv)))
+            r.store_off, r.map_off = int(v["store_off"]), int(v["map_off"])
+            r.region_scalars, r.n_regions = (sc.ctypes.data if len(sc) else None), len(sc)
+        self._check(getattr(load_library(), entry)(self._h, C.byref(d), None if no_records else C.cast(vrecs, C.c_void_p), C.byref(h)))
         return ResidentFamily(self, h, fonts)
 
     def family_read(self, family: ResidentFamily) -> dict:

@@ -58,6 +58,11 @@ class _CFaceTables(C.Structure):  # vgsdf_face_tables
                 ("subtable_off", C.c_void_p), ("subtable_format", C.c_void_p)]
 
 
+class _CFaceVariation(C.Structure):  # vgsdf_face_variation
+    _fields_ = [("hvar", C.c_void_p), ("hvar_len", C.c_uint32), ("store_off", C.c_uint32), ("map_off", C.c_uint32),
+                ("region_scalars", C.c_void_p), ("n_regions", C.c_uint32)]
+
+
 class FamilyTableStats(C.Structure):  # vg_family_table_stats
     _fields_ = [(k, C.c_uint64) for k in ("built_on_device", "fallbacks")]
 
@@ -99,6 +104,8 @@ VGFONT_SYMBOLS = [
     "vg_manager_set_glyf_tables_on_device", "vg_manager_glyf_table_stats",
     "vg_manager_set_glyf_tables_batched", "vg_manager_glyf_table_batch_stats",
     "vg_manager_set_mixed_stores", "vg_manager_mixed_stats",
+    "vg_manager_add_font_instance", "vg_manager_add_font_instance_normalized", "vg_font_variation_axes", "vg_font_named_instances",
+    "vg_manager_family_variation_desc", "vg_manager_font_position", "vg_manager_font_hor_advances",
 ]
 
 _bound = False
@@ -160,6 +167,13 @@ def _L():
         L.vg_manager_add_font_with_name.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int]
         L.vg_manager_add_font_data.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t]
         L.vg_manager_add_path.argtypes = [vp, C.c_char_p]
+        L.vg_manager_add_font_instance.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
+        L.vg_manager_add_font_instance_normalized.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int16), C.c_int]
+        L.vg_font_variation_axes.argtypes = [C.c_char_p, C.c_size_t, vp, vp, vp, vp, C.c_int]
+        L.vg_font_named_instances.argtypes = [C.c_char_p, C.c_size_t, vp, vp, C.c_int, C.c_int]
+        L.vg_manager_family_variation_desc.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(_CFaceVariation)]
+        L.vg_manager_font_position.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_int]
+        L.vg_manager_font_hor_advances.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_int]
         L.vg_name_to_id.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.vg_manager_block_counts.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint32)]
         L.vg_manager_render_glyphs.argtypes = [vp, vp, WRITE_CB, vp]
@@ -231,6 +245,32 @@ def _L():
 
 def _err() -> str:
     return (_L().vg_last_error() or b"").decode()
+
+
+def variation_axes(data: bytes):
+    """what a file's fvar offers (vg_font_variation_axes): [(tag, min, default, max)] in user space; [] without a readable fvar"""
+    L = _L()
+    n = L.vg_font_variation_axes(data, len(data), None, None, None, None, 0)
+    if n <= 0:
+        return []
+    tags = (C.c_char * (4 * n))()
+    lo, de, hi = ((C.c_float * n)() for _ in range(3))
+    L.vg_font_variation_axes(data, len(data), tags, lo, de, hi, n)
+    return [(bytes(tags[4 * i:4 * i + 4]).decode("latin-1"), float(lo[i]), float(de[i]), float(hi[i])) for i in range(n)]
+
+
+def named_instances(data: bytes):
+    """the named instances of a file's fvar (vg_font_named_instances): [(subfamily name id, {tag: user-space value})]"""
+    L = _L()
+    axes = variation_axes(data)
+    if not axes:
+        return []
+    n = L.vg_font_named_instances(data, len(data), None, None, 0, len(axes))
+    if n <= 0:
+        return []
+    ids, co = (C.c_uint16 * n)(), (C.c_float * (n * len(axes)))()
+    L.vg_font_named_instances(data, len(data), ids, co, n, len(axes))
+    return [(int(ids[k]), {axes[i][0]: float(co[k * len(axes) + i]) for i in range(len(axes))}) for k in range(n)]
 
 
 def name_to_id(name: str) -> str:
@@ -419,7 +459,8 @@ class FontManager:
     def set_charstrings_on_device(self, on):
         """False / 0 (default).  True / 1: the command stores of `CFF ` version 1 faces are decoded on the device from the charstrings
         (vgsdf_font_create_charstrings) instead of built by the host's reader; a face the device refuses falls back; same bytes.
-        2: CFF2 faces as well (vgsdf_font_create_charstrings2, the reader's blend factors: the default position)"""
+        2: CFF2 faces as well (vgsdf_font_create_charstrings2, the reader's blend factors: those of the file's position, the default
+        one unless add_font_instance put it elsewhere)"""
         _L().vg_manager_set_charstrings_on_device(self._h, int(on))
 
     def charstring_stats(self) -> dict:
@@ -501,8 +542,28 @@ class FontManager:
             raise RuntimeError(_err())
         return name_to_id(name)
 
+    variation_axes = staticmethod(variation_axes)    # what a file's fvar offers, without a manager
+    named_instances = staticmethod(named_instances)
+
     def add_font_data(self, name: str, data: bytes):
         if _L().vg_manager_add_font_data(self._h, name.encode(), data, len(data)) != 0:
+            raise RuntimeError(_err())
+        return name_to_id(name)
+
+    def add_font_instance(self, name: str, data: bytes, location: dict):
+        """a variable file at a position of its design space under `name` (vg_manager_add_font_instance): location maps axis
+        tags to user-space values ({"wght": 650}); axes not named stay at their default"""
+        tags = [t.encode() for t in location]
+        arr = (C.c_char_p * max(len(tags), 1))(*tags)
+        vals = (C.c_float * max(len(tags), 1))(*[float(v) for v in location.values()])
+        if _L().vg_manager_add_font_instance(self._h, name.encode(), data, len(data), arr, vals, len(tags)) != 0:
+            raise RuntimeError(_err())
+        return name_to_id(name)
+
+    def add_font_instance_normalized(self, name: str, data: bytes, coords):
+        """the same with final normalised coordinates (F2Dot14 as int16), one per fvar axis; avar is not applied"""
+        c = (C.c_int16 * max(len(coords), 1))(*[int(v) for v in coords])
+        if _L().vg_manager_add_font_instance_normalized(self._h, name.encode(), data, len(data), c, len(coords)) != 0:
             raise RuntimeError(_err())
         return name_to_id(name)
 
@@ -820,6 +881,44 @@ class FontManager:
         return {"cmap": C.string_at(d.cmap, d.cmap_len) if d.cmap_len else b"", "hmtx": C.string_at(d.hmtx, d.hmtx_len) if d.hmtx_len else b"",
                 "units_per_em": int(d.units_per_em), "num_glyphs": int(d.num_glyphs), "num_hmetrics": int(d.num_hmetrics),
                 "subtable_off": arr(d.subtable_off, np.uint32), "subtable_format": arr(d.subtable_format, np.uint16)}
+
+    def font_position(self, font_id: str, file_index: int = 0):
+        """the normalised coordinates (F2Dot14) a file was placed at (vg_manager_font_position); None: not at a position"""
+        L = _L()
+        n = L.vg_manager_font_position(self._h, font_id.encode(), int(file_index), None, 0)
+        if n < 0:
+            raise RuntimeError(_err())
+        if n == 0:
+            return None
+        c = (C.c_int16 * n)()
+        L.vg_manager_font_position(self._h, font_id.encode(), int(file_index), c, n)
+        return [int(v) for v in c]
+
+    def font_hor_advances(self, font_id: str, file_index: int = 0, extra: int = 0):
+        """the reader's advance of every glyph id of a file, and of `extra` ids past numGlyphs, in font units
+        (vg_manager_font_hor_advances; 0 for none)"""
+        L = _L()
+        n = L.vg_manager_font_hor_advances(self._h, font_id.encode(), int(file_index), None, 0)
+        if n < 0:
+            raise RuntimeError(_err())
+        a = np.zeros(n + extra, np.uint16)
+        L.vg_manager_font_hor_advances(self._h, font_id.encode(), int(file_index), a.ctypes.data, len(a))
+        return a
+
+    def family_variation_desc(self, font_id: str, file_index: int):
+        """what SdfContext.family_create_tables_var takes beside family_tables_desc for a file at a position
+        (vg_manager_family_variation_desc): {hvar (bytes), store_off, map_off, region_scalars (float32)}, copies; {} for a file
+        that is not at a position or has no HVAR (a static face).  None: the description refuses"""
+        d = _CFaceVariation()
+        if _L().vg_manager_family_variation_desc(self._h, font_id.encode(), int(file_index), C.byref(d)) != 0:
+            if _err().startswith("refused"):
+                return None
+            raise RuntimeError(_err())
+        if not d.hvar:
+            return {}
+        sc = np.frombuffer((C.c_char * (4 * d.n_regions)).from_address(d.region_scalars), dtype=np.float32, count=d.n_regions).copy() \
+            if d.n_regions else np.zeros(0, np.float32)
+        return {"hvar": C.string_at(d.hvar, d.hvar_len), "store_off": int(d.store_off), "map_off": int(d.map_off), "region_scalars": sc}
 
     def font_tables_desc(self, font_id: str, file_index: int = 0):
         """the description of one file's loca and glyf for SdfContext.font_create_tables (vg_manager_font_tables_desc), no device
