@@ -222,6 +222,21 @@ typedef struct {
 	uint64_t fallbacks;       /* faces whose fonts came from the host's table although the switch is on */
 } vg_glyf_table_stats;
 int vg_manager_glyf_table_stats(const vg_manager *m, vg_glyf_table_stats *out);
+/* gvar on the device, 0 (default) / 1: the command store of a `glyf` face placed by vg_manager_add_font_instance is built by the
+ * DEVICE from the face's `loca`, `glyf` and `gvar` at the face's coordinates (vgsdf_font_create_gvar: deltas, inferred points and
+ * component offsets there); the host only says where the tables are (vg_manager_gvar_font_desc) and interprets no glyph.  A face
+ * the device refuses (malformed variation data, a glyph past VGSDF_GVAR_MAX_DELTAS, the walk's and the store's bounds) gets its
+ * store from the host reader as with 0, remembered per face and device, so it is tried once.  Same registry key (the face's
+ * command serial), budget and lifetime, same store and same output either way.  Off by default whatever a measurement says
+ * (profiles/gvar_instances_ab.txt).  vg_manager_gvar_stats: of the last render; the stores built count among
+ * vg_command_stats.fonts_uploaded too. */
+void vg_manager_set_gvar_on_device(vg_manager *m, int on);
+typedef struct {
+	uint64_t fonts_built; /* command stores the device built from loca, glyf and gvar during the render */
+	uint64_t font_bytes;  /* their bytes on the device */
+	uint64_t fallbacks;   /* faces the device refused: their stores came from the host reader */
+} vg_gvar_stats;
+int vg_manager_gvar_stats(const vg_manager *m, vg_gvar_stats *out);
 /* ... batched, 0 (default) / 1; has an effect only with vg_manager_set_glyf_tables_on_device: the glyf fonts of ALL files of a
  * font id that the device has yet to build are built in one call (vgsdf_fonts_create_tables: one count launch, one read-back, one
  * emit launch) instead of one call per file, so what a call costs beside its two passes is paid once per font id.  Same fonts,
@@ -243,12 +258,16 @@ int vg_manager_add_font_data(vg_manager *m, const char *name, const uint8_t *dat
  * A VARIABLE file at a position of its design space, under a name of the caller's ("this file, at this position, under this
  * name"): axis_tags[i] (4 bytes, e.g. "wght") is set to values[i] in user space; axes not named stay at their default.  The
  * values are normalised in f32 (clamped to the axis, (v - def) / (def - min) or / (max - def), times 16384, truncated) and sent
- * through the file's `avar` (version 1.0).  CFF2 outlines are drawn at the position and advances follow `HVAR`; everything that
+ * through the file's `avar` (version 1.0).  CFF2 outlines are drawn at the position, `glyf` outlines are moved by `gvar` (tuple
+ * scalars, deltas, inferred points, component offsets: the rules G1 to G6 of csrc/host/ttf_face.hpp) and advances follow `HVAR`
+ * (without `HVAR` the `hmtx` advance stands: advances from gvar's phantom points are not read).  A placed `glyf` face is a command
+ * face for every form: vg_manager_record_glyf_parts, _resident_font_desc and _font_tables_desc refuse it.  Everything that
  * describes the file afterwards (vg_manager_charstring2_font_desc, _command_font_desc, _family_desc ...) describes it there.
  * Several instances of one file under different names are several font ids; the same name merges them into one font id like
  * any other files; no two instances share a store on a device.  Returns what vg_manager_add_font_data returns; -1 with
  * vg_last_error also for an unknown tag, a tag given twice, a value that is not finite, a file without a readable `fvar`, a
- * face with `glyf` outlines (no `gvar` reader), an HVAR store of another format than 1 or with 32-bit deltas.  A file added
+ * face with `glyf` outlines and no readable `gvar` (version 1.0, axisCount equal to fvar's, header, shared tuples and offset array
+ * inside the table), an HVAR store of another format than 1 or with 32-bit deltas.  A file added
  * any other way (vg_manager_add_font_data, _add_path, _scan) is at its default position, as the reference renders it.
  * _normalized: the final normalised coordinates (F2Dot14), one per `fvar` axis (at most 64 are counted; another number: -1);
  * nothing is normalised and `avar` is not applied.
@@ -453,6 +472,9 @@ int vg_manager_family_variation_desc(const vg_manager *m, const char *font_id, i
  * order.  The pointers stay valid as long as the manager holds the font.  -1: unknown font / file, or a face without `glyf`
  * outlines (vg_last_error then begins "refused"). */
 int vg_manager_font_tables_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_tables_desc *desc);
+/* The same of a `glyf` face placed by `gvar` for vgsdf_font_create_gvar: views of its loca, glyf and gvar and of its normalised
+ * coordinates, alive as long as the manager holds the file.  -1 for every other face. */
+int vg_manager_gvar_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_gvar_desc *desc);
 
 /* Hand-encoder of the glyphs PBF (src/protobuf/glyphs.rs:66-70) for already rendered
  * glyphs; bitmaps[i] may be NULL when !has_bitmap. Returns needed size. */

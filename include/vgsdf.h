@@ -483,6 +483,44 @@ int vgsdf_fonts_create_tables_within(vgsdf_ctx *ctx, const vgsdf_font_tables_des
 /* test / inspection (tools/glyf_tables_ab.py): the count and the emit pass of the context's last vgsdf_fonts_create_tables */
 void vgsdf_fonts_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
 /*
+ * The command font of a `glyf` face PLACED BY `gvar` at a position of its design space, built on the DEVICE from the face's
+ * `loca`, `glyf` and `gvar` tables: the host says where the tables are and looks at no glyph.  The description: the tables of
+ * vgsdf_font_tables_desc, the whole `gvar` table, and the position as n_axes normalised coordinates (F2Dot14 as int16, behind
+ * `avar`).  Validated on the host, VGSDF_E_ARG, nothing allocated: what vgsdf_font_create_tables validates; 1 .. 64 axes; a
+ * `gvar` that is not version 1.0, whose axisCount is not n_axes, or whose header, shared tuples or offset array leave gvar_len.
+ * Three passes, one lane per glyph id (csrc/gvar_kernels.hip), every read bounded by the table lengths:
+ *   count   the points of the glyph id's own entry, and over its component tree the commands and coordinates it delivers
+ *   deltas  rules G1 to G6 of the host reader (csrc/host/ttf_face.hpp) over the own entry: per point the f32 sums of its tuples
+ *   emit    the tree again: component offsets take the composite's sums, a leaf's points those of the leaf's glyph id
+ * and the context pass of vgsdf_font_create_commands over the result, which is the font that call makes of the host reader's
+ * command table of the same face at the same position — the same records, cmd_off and context bytes, the same
+ * vgsdf_font_device_bytes — used and freed like it.  Synchronous like it.  The deltas pass works in a scratch the CONTEXT owns
+ * (13 bytes per point of a launch; launches of at most 2^17 points, or one glyph id; grown on demand, freed with the context, not
+ * counted by vgsdf_font_device_bytes).  Refused with VGSDF_E_GLYF, nothing left allocated, the context sound (the caller then
+ * takes the host reader's table to vgsdf_font_create_commands):
+ *   - a glyph id whose variation data is malformed (the host reader delivers nothing for it from there on);
+ *   - a glyph id whose own entry has more than VGSDF_GVAR_MAX_DELTAS tuples x points (phantom points included), whatever the
+ *     tuples' scalars: one lane works through them, and the bound keeps a crafted table from holding the device;
+ *   - a glyph id that reads more than 2^20 component records, or a composite entry of more than 65535; a glyph id of more than 2^26
+ *     commands;
+ *   - a store or coordinates past the bounds vgsdf_font_create_commands states.
+ * _within: the budget form of vgsdf_font_create_charstrings_within.
+ */
+#define VGSDF_GVAR_MAX_DELTAS (1u << 20)
+typedef struct {
+	vgsdf_font_tables_desc tables; /* loca, glyf */
+	const uint8_t *gvar;           /* the whole table as it stands in the file */
+	uint32_t gvar_len;
+	uint32_t n_axes;               /* 1 .. 64, the table's axisCount */
+	const int16_t *coords;         /* [n_axes] */
+} vgsdf_font_gvar_desc;
+int vgsdf_font_create_gvar(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in, vgsdf_font **out);
+int vgsdf_font_create_gvar_within(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
+                                  uint64_t *store_bytes);
+/* test / inspection (tools/gvar_instances_ab.py): milliseconds the count, the deltas and the emit pass of the context's last
+ * vgsdf_font_create_gvar took (HIP events around the pass, all its launches; 0 before the first, and for a pass that did not run) */
+void vgsdf_font_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3]);
+/*
  * Resident families: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id lives on the device
  * beside its fonts, and a submission names CODE-POINT RANGES of families instead of glyphs.  The host's share per submission
  * is O(tasks): the block it uploads holds 32 bytes per task that maps a glyph, per family and per font, and no per-glyph byte.

@@ -186,6 +186,13 @@ int vg_manager_family_stats(const vg_manager *m, vg_family_stats *out)
 }
 void vg_manager_set_family_tables_on_device(vg_manager *m, int on) { m->m.set_family_tables_on_device(on != 0); }
 void vg_manager_set_glyf_tables_on_device(vg_manager *m, int on) { m->m.set_glyf_tables_on_device(on != 0); }
+void vg_manager_set_gvar_on_device(vg_manager *m, int on) { m->m.set_gvar_on_device(on != 0); }
+int vg_manager_gvar_stats(const vg_manager *m, vg_gvar_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_gvar_stats{t.gvar_fonts_built, t.gvar_font_bytes, t.gvar_fallbacks};
+	return 0;
+}
 int vg_manager_glyf_table_stats(const vg_manager *m, vg_glyf_table_stats *out)
 {
 	const vg::RenderTimings &t = m->m.last_timings();
@@ -1031,6 +1038,33 @@ int vg_manager_font_tables_desc(const vg_manager *m, const char *font_id, int fi
 		desc->num_glyphs = t.num_glyphs, desc->loca_entries = t.loca_entries, desc->loca_long = t.loca_long;
 		desc->n_loca_bytes = t.n_loca_bytes, desc->n_glyf_bytes = t.n_glyf_bytes;
 		desc->loca = t.loca, desc->glyf = t.glyf;
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_gvar_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_gvar_desc *desc)
+{
+	try {
+		if (!m || !font_id || !desc || file_index < 0) {
+			g_err = "vg_manager_gvar_font_desc: bad argument";
+			return -1;
+		}
+		auto it = m->m.fonts().find(font_id);
+		if (it == m->m.fonts().end() || (size_t)file_index >= it->second.files().size()) {
+			g_err = std::string("unknown font id ") + font_id + ", or a file index past its files";
+			return -1;
+		}
+		const vg::GvarTables t = it->second.files()[(size_t)file_index]->face().gvar_tables();
+		if (!t.ok) {
+			g_err = std::string("refused: font ") + font_id + ": not a glyf face placed by gvar";
+			return -1;
+		}
+		desc->tables.num_glyphs = t.tables.num_glyphs, desc->tables.loca_entries = t.tables.loca_entries, desc->tables.loca_long = t.tables.loca_long;
+		desc->tables.n_loca_bytes = t.tables.n_loca_bytes, desc->tables.n_glyf_bytes = t.tables.n_glyf_bytes;
+		desc->tables.loca = t.tables.loca, desc->tables.glyf = t.tables.glyf;
+		desc->gvar = t.gvar, desc->gvar_len = t.gvar_len, desc->n_axes = t.n_axes, desc->coords = t.coords;
 		return 0;
 	} catch (const std::exception &e) {
 		g_err = e.what();

@@ -82,7 +82,7 @@ struct GlyphBlock {
 		if (!glyphs[char_index]) {
 			glyphs[char_index] = font;
 			count++;
-			all_glyf = all_glyf && font->face().has_glyf_outlines();
+			all_glyf = all_glyf && font->face().has_glyf_form();
 		}
 	}
 	size_t len() const { return count; }
@@ -170,6 +170,9 @@ struct RenderTimings {
 	// groups submitted against stores of BOTH kinds (set_mixed_stores; counted here and in none of the group counters above), the
 	// glyf stores and the command stores those groups named, bytes of their upload blocks
 	uint64_t mixed_groups = 0, mixed_glyf_fonts = 0, mixed_command_fonts = 0, mixed_block_bytes = 0;
+	// command stores the device built from a placed glyf face's loca, glyf and gvar (set_gvar_on_device; counted among
+	// command_fonts_uploaded too), their bytes, and faces it refused, whose stores were built from the host reader's table instead
+	uint64_t gvar_fonts_built = 0, gvar_font_bytes = 0, gvar_fallbacks = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -201,10 +204,11 @@ struct RenderTimings {
 		family_tables_built += counts.family_tables_built, family_table_fallbacks += counts.family_table_fallbacks;
 		glyf_tables_built += counts.glyf_tables_built, glyf_table_bytes += counts.glyf_table_bytes, glyf_table_fallbacks += counts.glyf_table_fallbacks;
 		glyf_table_batch_calls += counts.glyf_table_batch_calls, glyf_table_batch_faces += counts.glyf_table_batch_faces;
+		gvar_fonts_built += counts.gvar_fonts_built, gvar_font_bytes += counts.gvar_font_bytes, gvar_fallbacks += counts.gvar_fallbacks;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 36 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 39 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -328,6 +332,9 @@ public:
 	// and Face::resident_table() is not built for the face; a face whose build the device refuses gets its font from the host's
 	// table (remembered per face and device).  Same leaves, same output.
 	void set_glyf_tables_on_device(bool on) { glyf_tables_on_device_ = on; }
+	// a placed glyf face's command store is built on the device from loca, glyf and gvar (Renderer::gvar_font); a face the device
+	// refuses gets its store from the host reader's table, as with the switch off
+	void set_gvar_on_device(bool on) { gvar_on_device_ = on; }
 	// with set_glyf_tables_on_device: the glyf fonts of a font id's files built in one call (Renderer::fonts_from_tables)
 	void set_glyf_tables_batched(bool on) { glyf_tables_batched_ = on; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
@@ -592,6 +599,7 @@ private:
 	int charstrings_on_device_ = 0;
 	bool family_tables_on_device_ = false;
 	bool glyf_tables_on_device_ = false;
+	bool gvar_on_device_ = false;
 	bool glyf_tables_batched_ = false;
 	// glyf_tables_batched_: the glyf fonts of `font`'s files that the device has yet to build, in one call; the glyf_store of each
 	// file behind it finds its font (or goes the way of a face that was refused or did not fit); counts into `counts`

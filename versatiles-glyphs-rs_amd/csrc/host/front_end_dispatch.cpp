@@ -326,7 +326,7 @@ void FontManager::glyf_stores_batched(const Renderer &renderer, int lane, const 
 		return;
 	std::vector<Renderer::TablesJob> faces;
 	for (const auto &file : font.files())
-		if (file->face().has_glyf_outlines())
+		if (file->face().has_glyf_form())
 			faces.push_back(Renderer::TablesJob{file->face().resident_serial(), file->face().font_tables()});
 	std::vector<Renderer::TablesOutcome> outcomes;
 	renderer.fonts_from_tables(lane, faces, outcomes, &counts.glyf_table_batch_calls, &counts.glyf_table_batch_faces);
@@ -358,6 +358,16 @@ const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane,
 		if (f)
 			count_upload(uploaded, counts.charstring_fonts_decoded, counts.charstring_font_bytes);
 	}
+	if (!f && gvar_on_device_ && face.placed_by_gvar()) {
+		bool refused = false, over_budget = false;
+		f = renderer.gvar_font(lane, face.command_serial(), face.gvar_tables(), &uploaded, &refused, &over_budget);
+		if (refused)
+			counts.gvar_fallbacks++;
+		if (over_budget)
+			return nullptr; // (the host's table would make the same store, over the same budget: it is not built for that)
+		if (f)
+			count_upload(uploaded, counts.gvar_fonts_built, counts.gvar_font_bytes);
+	}
 	if (!f)
 		f = renderer.command_font(lane, face.command_table(), &uploaded);
 	if (f)
@@ -369,7 +379,7 @@ const vgsdf_font *FontManager::file_store(const Renderer &renderer, int lane, co
                                           RenderTimings &counts, bool *glyf) const
 {
 	*glyf = false;
-	if (face.has_glyf_outlines() && !glyf_refused_.count(&font_id))
+	if (face.has_glyf_form() && !glyf_refused_.count(&font_id))
 		if (const vgsdf_font *f = glyf_store(renderer, lane, face, counts)) {
 			*glyf = true;
 			return f;
@@ -388,7 +398,7 @@ bool FontManager::may_mix(const std::vector<Todo> &tasks, size_t g0, size_t g1) 
 		if (it == fonts().end() || glyf_refused_.count(&it->first))
 			continue;
 		for (const auto &file : it->second.files())
-			if (file->face().has_glyf_outlines())
+			if (file->face().has_glyf_form())
 				return true;
 	}
 	return false;
@@ -411,7 +421,7 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 		bool glyf = kind == StoreKind::Glyf;
 		const vgsdf_font *f = kind == StoreKind::Mixed ? file_store(renderer, lane, font_id, file->face(), counts, &glyf)
 		                      : commands               ? command_store(renderer, lane, file->face(), counts)
-		                                               : (file->face().has_glyf_outlines() ? glyf_store(renderer, lane, file->face(), counts) : nullptr);
+		                                               : (file->face().has_glyf_form() ? glyf_store(renderer, lane, file->face(), counts) : nullptr);
 		if (!f)
 			return nullptr;
 		stores.push_back(f);
@@ -570,7 +580,7 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 			uploaded += batch.resident_font_bytes;
 			preload_counts_.add_uploads(batch);
 			for (const auto &file : kv.second.files())
-				if (file->face().has_glyf_outlines()) {
+				if (file->face().has_glyf_form()) {
 					RenderTimings counts;
 					(void)glyf_store(renderer.device_lane(r), 0, file->face(), counts);
 					uploaded += counts.resident_font_bytes;
@@ -587,10 +597,10 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 			for (const auto &kv : fonts()) {
 				bool wanted = resident_commands_ == 2 || glyf_refused_.count(&kv.first) != 0;
 				for (const auto &file : kv.second.files())
-					wanted = wanted || !file->face().has_glyf_outlines();
+					wanted = wanted || !file->face().has_glyf_form();
 				if (wanted)
 					for (const auto &file : kv.second.files()) {
-						if (file->face().has_glyf_outlines() && glyf_files_keep_glyf_stores(kv.first))
+						if (file->face().has_glyf_form() && glyf_files_keep_glyf_stores(kv.first))
 							continue;
 						RenderTimings counts;
 						(void)command_store(renderer.device_lane(r), 0, file->face(), counts);
@@ -605,7 +615,7 @@ uint64_t FontManager::preload_resident_fonts(const Renderer &renderer) const
 			for (const auto &kv : fonts()) {
 				bool a_glyf_file = false;
 				for (const auto &file : kv.second.files())
-					a_glyf_file = a_glyf_file || file->face().has_glyf_outlines();
+					a_glyf_file = a_glyf_file || file->face().has_glyf_form();
 				for (const StoreKind kind : {StoreKind::Glyf, StoreKind::Commands, StoreKind::Mixed})
 					if (kind == StoreKind::Mixed      ? mixes()
 					    : kind == StoreKind::Commands ? resident_commands_ != 0 && !(a_glyf_file && glyf_files_keep_glyf_stores(kv.first))

@@ -74,7 +74,7 @@ void FontManager::build_lane_plan(uint32_t world, int form)
 		for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE; ci++)
 			if (const FontFileEntry *f = blk.glyphs[ci]) {
 				uint32_t slots = 32;
-				if (f->face().has_glyf_outlines()) {
+				if (f->face().has_glyf_form()) {
 					slots = 0;
 					parts.clear();
 					bytes.clear();
@@ -407,6 +407,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->charstrings_on_device_ = charstrings_on_device_;
 		c->family_tables_on_device_ = family_tables_on_device_;
 		c->glyf_tables_on_device_ = glyf_tables_on_device_;
+		c->gvar_on_device_ = gvar_on_device_;
 		c->glyf_tables_batched_ = glyf_tables_batched_;
 		c->resident_families_ = resident_families_;
 		c->batch_blocks_ = batch_blocks_;

@@ -225,6 +225,8 @@ Renderer::~Renderer()
 		resident_->unfit_charstrings.clear();
 		resident_->refused_glyf_tables.clear();
 		resident_->unfit_glyf_tables.clear();
+		resident_->refused_gvar.clear();
+		resident_->unfit_gvar.clear();
 		resident_->bytes.clear();
 	}
 	if (ctx2_)
@@ -682,6 +684,51 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 		}
 	}
 	rf.unfit_charstrings.erase(key);
+	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
+}
+
+const vgsdf_font *Renderer::gvar_font(int lane, uint64_t serial, const GvarTables &t, uint64_t *uploaded_bytes, bool *refused, bool *over_budget) const
+{
+	if (mode_ != Mode::Hip || !t.ok)
+		return nullptr;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	const auto key = std::make_pair(device_, serial);
+	if (auto *found = rf.find(rf.fonts, key))
+		return found;
+	if (rf.refused_gvar.count(key))
+		return nullptr;
+	const uint64_t room = rf.room(device_);
+	if (auto it = rf.unfit_gvar.find(key); it != rf.unfit_gvar.end() && it->second > room) {
+		*over_budget = true;
+		return nullptr;
+	}
+	vgsdf_font_gvar_desc d{};
+	d.tables.num_glyphs = t.tables.num_glyphs, d.tables.loca_entries = t.tables.loca_entries, d.tables.loca_long = t.tables.loca_long;
+	d.tables.n_loca_bytes = t.tables.n_loca_bytes, d.tables.n_glyf_bytes = t.tables.n_glyf_bytes;
+	d.tables.loca = t.tables.loca, d.tables.glyf = t.tables.glyf;
+	d.gvar = t.gvar, d.gvar_len = t.gvar_len, d.n_axes = t.n_axes, d.coords = t.coords;
+	vgsdf_ctx *c = lane_ctx(lane & 1);
+	vgsdf_font *f = nullptr;
+	{
+		// the budget as charstring_font holds it: the store's size is known behind the count pass, and checked there
+		uint64_t want = 0;
+		std::lock_guard<std::mutex> lock(mu_);
+		const int rc = vgsdf_font_create_gvar_within(c, &d, room, &f, &want);
+		if (rc == VGSDF_E_GLYF) {
+			rf.refused_gvar.insert(key);
+			*refused = true;
+			return nullptr;
+		}
+		if (rc != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_font_create_gvar: ") + vgsdf_last_error(c));
+		if (!f) { // over the budget as it stands
+			rf.unfit_gvar[key] = want;
+			*over_budget = true;
+			return nullptr;
+		}
+	}
+	rf.unfit_gvar.erase(key);
 	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 

@@ -436,7 +436,7 @@ public:
 	static bool record(const Face &face, uint32_t index, OutlineBatch &batch);
 	static bool record(const Face &face, uint32_t index, PackedOutlineBatch &batch); // the same into the compact form
 	// ... and for the device's glyf decoder: nothing is decoded, the glyph's simple glyphs are appended as parts
-	// (glyf fonts only: face.has_glyf_outlines())
+	// (glyf fonts only: face.has_glyf_form())
 	static bool record_parts(const Face &face, uint32_t index, GlyfPartsBatch &batch);
 	// the same for a resident face: the glyph is named, not walked (file = the face's index among the font id's files)
 	static bool record_resident(const Face &face, uint16_t file, uint32_t index, ResidentBatch &batch);
@@ -498,6 +498,10 @@ public:
 	// it does not fit, and is once the budget has room for it
 	const vgsdf_font *charstring_font(int lane, const CharstringTable &table, uint64_t *uploaded_bytes = nullptr, bool *refused = nullptr,
 	                                  bool *over_budget = nullptr) const;
+	// the same store made on the device from a placed glyf face's loca, glyf and gvar (vgsdf_font_create_gvar_within), under the
+	// face's command serial: command_font() of the same face finds it.  refused / over_budget: as charstring_font says them; a
+	// refusal is remembered per (device, serial), so the face goes the host's way once and is not tried again
+	const vgsdf_font *gvar_font(int lane, uint64_t serial, const GvarTables &tables, uint64_t *uploaded_bytes, bool *refused, bool *over_budget) const;
 	// Resident families (vgsdf_family_create): the device copy of a font id's table code point -> (file, glyph id, advance,
 	// scale, shift_x) over the device fonts of its files, one per (device, table serial, kind of store) in the registry of the
 	// fonts — same budget, freed with the renderer, in front of the fonts.  A table rebuilt after a file was added has a new
@@ -576,6 +580,8 @@ private:
 		std::map<std::pair<int, uint64_t>, uint64_t> unfit_charstrings; // (device, serial) -> bytes of a store that passed the budget
 		std::set<std::pair<int, uint64_t>> refused_glyf_tables;         // (device, serial): the device's table builder has refused the face
 		std::map<std::pair<int, uint64_t>, uint64_t> unfit_glyf_tables; // (device, serial) -> bytes of a font that passed the budget
+		std::set<std::pair<int, uint64_t>> refused_gvar;                // (device, serial): the device's gvar builder has refused the face
+		std::map<std::pair<int, uint64_t>, uint64_t> unfit_gvar;        // (device, serial) -> bytes of a store that passed the budget
 		uint64_t budget = 1ull << 30;
 		// the frame of resident_font() .. family_from_tables() (under `mu`): what the registry holds under a key, the budget a device has left, and a new
 		// font or family of `got` device bytes taken in and accounted (the key's first member is the device)

@@ -6,6 +6,7 @@
 #include "ttf_face.hpp"
 
 #include "cff.hpp"
+#include "gvar.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -244,8 +245,13 @@ std::optional<Face> Face::parse_impl(const uint8_t *data, size_t len, const std:
 		const uint32_t n_axes = std::min<uint32_t>(fvar_axes(find_table(file, "fvar"), axes_at), 64);
 		if (!n_axes)
 			return refuse("a position needs a readable fvar table, and this file has none");
-		if (f.has_glyf_outlines())
-			return refuse("a position for a face with glyf outlines is not supported (no gvar reader)");
+		if (f.has_glyf_outlines()) {
+			// (gvar's axisCount is fvar's own, not the 64 the coordinates are counted to: a file of more axes is refused below)
+			if (auto g = GvarTable::parse(find_table(file, "gvar"), n_axes))
+				f.gvar_ = std::make_shared<const GvarTable>(std::move(*g));
+			else
+				return refuse("a position for a face with glyf outlines needs a readable gvar table (version 1.0, as many axes as fvar), and this file has none");
+		}
 		if (at_coords->size() != n_axes)
 			return refuse("the number of coordinates is not the number of fvar axes (at most 64 are counted)");
 		f.at_position_ = true;
@@ -725,6 +731,250 @@ const FamilyTables &Face::family_tables() const
 	return cell.tables;
 }
 
+// ---- gvar (gvar.hpp; here and not in a file of its own: this file and cff.cpp are the reader, whoever compiles it) ---
+std::optional<GvarTable> GvarTable::parse(Bytes table, uint32_t n_axes)
+{
+	// majorVersion, minorVersion, axisCount, sharedTupleCount, sharedTuplesOffset, glyphCount, flags, glyphVariationDataArrayOffset
+	if (!table.has(0, 20) || table.size() > 0xFFFFFFFFu || table.u32(0) != 0x00010000u || table.u16(4) != n_axes || n_axes == 0)
+		return std::nullopt;
+	GvarTable t;
+	t.table_ = table;
+	t.axis_count_ = n_axes;
+	t.shared_count_ = table.u16(6);
+	t.shared_at_ = table.u32(8);
+	t.glyph_count_ = table.u16(12);
+	t.long_offsets_ = (table.u16(14) & 1) != 0;
+	t.data_at_ = table.u32(16);
+	if (!table.has(t.shared_at_, (size_t)t.shared_count_ * n_axes * 2) ||
+	    !table.has(20, ((size_t)t.glyph_count_ + 1) * (t.long_offsets_ ? 4u : 2u)))
+		return std::nullopt;
+	return t;
+}
+
+namespace {
+
+// G2: packed point numbers at b[p...]; false: they leave b, or do not ascend
+bool read_point_numbers(Bytes b, size_t &p, bool &all, std::vector<uint16_t> &numbers)
+{
+	numbers.clear();
+	all = false;
+	if (!b.has(p, 1))
+		return false;
+	uint32_t count = b.u8(p++);
+	if (count == 0) {
+		all = true;
+		return true;
+	}
+	if (count & 0x80) {
+		if (!b.has(p, 1))
+			return false;
+		count = ((count & 0x7F) << 8) | b.u8(p++);
+	}
+	uint16_t number = 0;
+	while (numbers.size() < count) {
+		if (!b.has(p, 1))
+			return false;
+		const uint8_t control = b.u8(p++);
+		const bool words = (control & 0x80) != 0;
+		for (uint32_t left = (control & 0x7Fu) + 1; left && numbers.size() < count; left--) {
+			if (!b.has(p, words ? 2 : 1))
+				return false;
+			const uint16_t step = words ? b.u16(p) : b.u8(p);
+			p += words ? 2 : 1;
+			const uint16_t next = (uint16_t)(number + step);
+			if (!numbers.empty() && next <= number)
+				return false;
+			numbers.push_back(number = next);
+		}
+	}
+	return true;
+}
+
+// G3: the packed deltas of a tuple as one stream of values
+struct DeltaStream {
+	Bytes b;
+	size_t p;
+	uint32_t left = 0; // of the run in hand
+	uint8_t control = 0;
+	bool next(int32_t &v)
+	{
+		if (left == 0) {
+			if (!b.has(p, 1))
+				return false;
+			control = b.u8(p++);
+			left = (control & 0x3Fu) + 1;
+		}
+		left--;
+		if (control & 0x80) {
+			v = 0;
+		} else if (control & 0x40) {
+			if (!b.has(p, 2))
+				return false;
+			v = b.i16(p), p += 2;
+		} else {
+			if (!b.has(p, 1))
+				return false;
+			v = (int8_t)b.u8(p), p += 1;
+		}
+		return true;
+	}
+};
+
+// G5: what a point at p takes from the touched points at pa (before it) and pb (behind it) of its contour
+float inferred(int32_t p, int32_t pa, int32_t pb, float da, float db)
+{
+	if (pa == pb)
+		return da == db ? da : 0.0f;
+	if (p <= std::min(pa, pb))
+		return pa < pb ? da : db;
+	if (p >= std::max(pa, pb))
+		return pa > pb ? da : db;
+	const float d = (float)(p - pa) / (float)(pb - pa);
+	return (1.0f - d) * da + d * db;
+}
+
+} // namespace
+
+bool GvarTable::accumulate(uint16_t gid, const std::vector<int16_t> &coords, const GvarPoints &pts, std::vector<float> &acc) const
+{
+	const uint32_t n_all = pts.n + 4;
+	acc.assign((size_t)2 * n_all, 0.0f);
+	if (gid >= glyph_count_ || coords.size() != axis_count_)
+		return true;
+	// G1
+	size_t from, to;
+	if (long_offsets_)
+		from = table_.u32(20 + (size_t)gid * 4), to = table_.u32(24 + (size_t)gid * 4);
+	else
+		from = (size_t)table_.u16(20 + (size_t)gid * 2) * 2, to = (size_t)table_.u16(22 + (size_t)gid * 2) * 2;
+	if (from == to)
+		return true;
+	if (from > to || !table_.has(data_at_, to))
+		return false;
+	const Bytes d = table_.sub(data_at_ + from, to - from);
+	if (!d.has(0, 4))
+		return false;
+	const uint32_t n_tuples = d.u16(0) & 0x0FFFu;
+	const bool have_shared = (d.u16(0) & 0x8000u) != 0;
+	if (n_tuples == 0)
+		return true;
+	size_t cursor = d.u16(2);
+	if (cursor > d.size())
+		return false;
+	bool shared_all = true, all = true;
+	std::vector<uint16_t> shared, own;
+	if (have_shared && !read_point_numbers(d, cursor, shared_all, shared))
+		return false;
+	std::vector<float> sx, sy;
+	std::vector<uint8_t> mark; // 1: touched, 2: inferred
+	std::vector<uint32_t> before, behind;
+	size_t h = 4;
+	const size_t tuple_bytes = (size_t)axis_count_ * 2;
+	for (uint32_t t = 0; t < n_tuples; t++) {
+		if (!d.has(h, 4))
+			return false;
+		const size_t size = d.u16(h);
+		const uint32_t index = d.u16(h + 2);
+		h += 4;
+		Bytes peak, start, end;
+		if (index & 0x8000u) {
+			if (!d.has(h, tuple_bytes))
+				return false;
+			peak = d.sub(h, tuple_bytes);
+			h += tuple_bytes;
+		} else {
+			if ((index & 0x0FFFu) >= shared_count_)
+				return false;
+			peak = table_.sub(shared_at_ + (size_t)(index & 0x0FFFu) * tuple_bytes, tuple_bytes);
+		}
+		if (index & 0x4000u) {
+			if (!d.has(h, 2 * tuple_bytes))
+				return false;
+			start = d.sub(h, tuple_bytes), end = d.sub(h + tuple_bytes, tuple_bytes);
+			h += 2 * tuple_bytes;
+		}
+		if (!d.has(cursor, size))
+			return false;
+		const Bytes data = d.sub(cursor, size);
+		cursor += size;
+		// G4
+		float scalar = 1.0f;
+		for (uint32_t i = 0; i < axis_count_ && scalar != 0.0f; i++) {
+			const int16_t pk = peak.i16((size_t)i * 2);
+			const int16_t st = start.empty() ? std::min<int16_t>(pk, 0) : start.i16((size_t)i * 2);
+			const int16_t en = end.empty() ? std::max<int16_t>(pk, 0) : end.i16((size_t)i * 2);
+			const float f = axis_factor(coords[i], st, pk, en);
+			scalar = f == 0.0f ? 0.0f : scalar * f;
+		}
+		if (scalar == 0.0f)
+			continue;
+		size_t p = 0;
+		const std::vector<uint16_t> *numbers = &shared;
+		all = shared_all;
+		if (index & 0x2000u) {
+			if (!read_point_numbers(data, p, all, own))
+				return false;
+			numbers = &own;
+		}
+		DeltaStream deltas{data, p};
+		int32_t v;
+		if (all) {
+			for (int axis = 0; axis < 2; axis++)
+				for (uint32_t i = 0; i < n_all; i++) {
+					if (!deltas.next(v))
+						return false;
+					acc[(size_t)2 * i + axis] += (float)v * scalar;
+				}
+			continue;
+		}
+		sx.assign(n_all, 0.0f), sy.assign(n_all, 0.0f), mark.assign(n_all, 0);
+		for (int axis = 0; axis < 2; axis++)
+			for (const uint16_t number : *numbers) {
+				if (!deltas.next(v))
+					return false;
+				if (number < n_all) // (a number at or past the count names no point)
+					(axis ? sy : sx)[number] = (float)v * scalar, mark[number] = 1;
+			}
+		if (pts.last_of_contour) {
+			before.resize(pts.n), behind.resize(pts.n);
+			for (uint32_t first = 0; first < pts.n;) {
+				uint32_t last = first;
+				while (last + 1 < pts.n && !pts.last_of_contour[last])
+					last++;
+				uint32_t lo = 0xFFFFFFFFu, hi = 0;
+				for (uint32_t i = first; i <= last; i++)
+					if (mark[i] == 1)
+						lo = std::min(lo, i), hi = i;
+				if (lo != 0xFFFFFFFFu) {
+					// (cyclic: in front of the first touched point lies the last one, behind the last the first)
+					for (uint32_t i = first, at = hi; i <= last; i++) {
+						if (mark[i] == 1)
+							at = i;
+						before[i] = at;
+					}
+					for (uint32_t i = last + 1, at = lo; i-- > first;) {
+						if (mark[i] == 1)
+							at = i;
+						behind[i] = at;
+					}
+					for (uint32_t i = first; i <= last; i++)
+						if (mark[i] == 0) {
+							const uint32_t a = before[i], b = behind[i];
+							sx[i] = inferred(pts.x[i], pts.x[a], pts.x[b], sx[a], sx[b]);
+							sy[i] = inferred(pts.y[i], pts.y[a], pts.y[b], sy[a], sy[b]);
+							mark[i] = 2;
+						}
+				}
+				first = last + 1;
+			}
+		}
+		for (uint32_t i = 0; i < n_all; i++)
+			if (mark[i])
+				acc[(size_t)2 * i] += sx[i], acc[(size_t)2 * i + 1] += sy[i];
+	}
+	return true;
+}
+
 // ---- glyf ------------------------------------------------------------------------------
 std::optional<Bytes> Face::glyph_data(uint16_t gid) const
 {
@@ -902,7 +1152,8 @@ constexpr int kMaxComponentDepth = kGlyfMaxComponentDepth; // (glyf_table_limits
 enum : uint8_t { ON_CURVE = 0x01, X_SHORT = 0x02, Y_SHORT = 0x04, REPEAT = 0x08, X_SAME_POS = 0x10, Y_SAME_POS = 0x20 };
 
 // simple glyph body (after numberOfContours + bbox); false = malformed (ttf-parser -> None)
-template <class B> bool walk_simple(Bytes body, uint16_t n_contours, ContourEmitter<B> &em)
+// (E: ContourEmitter, or the point collector of the gvar walk)
+template <class E> bool walk_simple(Bytes body, uint16_t n_contours, E &em)
 {
 	if (!body.has(0, (size_t)n_contours * 2))
 		return false;
@@ -991,6 +1242,54 @@ template <class B> bool walk_simple(Bytes body, uint16_t n_contours, ContourEmit
 	return true;
 }
 
+// The gvar walk's (GvarWalker, which reads every composite twice: once to count its records, once to follow them): one component
+// record of a composite's body at p, by the rules of GlyfWalker::walk's loop — its flags, its glyph id and its transform; p moves
+// behind it.  false: the record leaves the entry (ttf-parser's iterator ends there).
+inline bool read_component(Bytes body, size_t &p, uint16_t &flags, uint16_t &child, Affine &k)
+{
+	if (!body.has(p, 4))
+		return false;
+	flags = body.u16(p), child = body.u16(p + 2);
+	p += 4;
+	if (flags & 0x0002) { // ARGS_ARE_XY_VALUES
+		if (flags & 0x0001) {
+			if (!body.has(p, 4))
+				return false;
+			k.e = (float)body.i16(p);
+			k.f = (float)body.i16(p + 2);
+			p += 4;
+		} else {
+			if (!body.has(p, 2))
+				return false;
+			k.e = (float)(int8_t)body.u8(p);
+			k.f = (float)(int8_t)body.u8(p + 1);
+			p += 2;
+		}
+	} // anchor-point arguments are not consumed by ttf-parser 0.25 (parity unpinned)
+	auto f2dot14 = [&](size_t at) { return (float)body.i16(at) / 16384.0f; };
+	if (flags & 0x0080) {
+		if (!body.has(p, 8))
+			return false;
+		k.a = f2dot14(p);
+		k.b = f2dot14(p + 2);
+		k.c = f2dot14(p + 4);
+		k.d = f2dot14(p + 6);
+		p += 8;
+	} else if (flags & 0x0040) {
+		if (!body.has(p, 4))
+			return false;
+		k.a = f2dot14(p);
+		k.d = f2dot14(p + 2);
+		p += 4;
+	} else if (flags & 0x0008) {
+		if (!body.has(p, 2))
+			return false;
+		k.a = k.d = f2dot14(p);
+		p += 2;
+	}
+	return true;
+}
+
 } // namespace
 
 // PARTS: the sink does not take callbacks but every simple glyph as it stands (B::part): the device decodes it
@@ -1070,10 +1369,112 @@ template <class B, bool PARTS> struct GlyfWalker {
 	}
 };
 
+namespace {
+// the gvar walk's sinks: the callbacks of an OutlineBuilder, and the packed recorder
+struct GvarCallbacks {
+	static constexpr bool kRawCursor = false;
+	OutlineBuilder &to;
+	void move_to(float x, float y) { to.move_to(x, y); }
+	void line_to(float x, float y) { to.line_to(x, y); }
+	void quad_to(float x1, float y1, float x, float y) { to.quad_to(x1, y1, x, y); }
+	void close() { to.close(); }
+};
+// walk_simple's sink of the gvar walk: the entry's points as they stand, for G5
+struct PointCollector {
+	std::vector<int16_t> x, y;
+	std::vector<uint8_t> on_curve, last_of_contour;
+	void begin(uint32_t n_points, uint32_t)
+	{
+		x.reserve(n_points), y.reserve(n_points), on_curve.reserve(n_points), last_of_contour.reserve(n_points);
+	}
+	void point(float px, float py, bool on, bool last)
+	{
+		x.push_back((int16_t)px), y.push_back((int16_t)py); // (whole numbers of i16 range: walk_simple made them of such)
+		on_curve.push_back(on), last_of_contour.push_back(last);
+	}
+	void end() {}
+};
+} // namespace
+
+// The walk of a face placed by `gvar` (G5, G6 of ttf_face.hpp): GlyfWalker's, glyph id by glyph id, with every entry's points
+// moved by the sums GvarTable::accumulate has for it before the static walk's emitter and transforms see them.
+// B: a sink type of the gvar walk's own (GvarCallbacks, GvarCursorSink below), so that the static walk's emitter remains the
+// instantiation with one caller that it was.
+template <class B> struct GvarWalker {
+	const Face &face;
+	const GvarTable &gvar;
+	B &out;
+
+	bool walk(uint16_t gid, int depth, const Affine &t)
+	{
+		const auto entry = face.glyph_data(gid);
+		if (!entry)
+			return depth != 0; // (a component without an entry is passed over, as in GlyfWalker)
+		const Bytes glyph = *entry;
+		if (depth >= kMaxComponentDepth || !glyph.has(0, 2))
+			return false;
+		const int16_t n_contours = glyph.i16(0);
+		const Bytes body = glyph.from(10);
+		std::vector<float> acc;
+		if (n_contours > 0) {
+			if (glyph.size() < 10)
+				return false;
+			PointCollector pc;
+			if (!walk_simple(body, (uint16_t)n_contours, pc))
+				return false;
+			if (pc.x.empty())
+				return true; // a lone point yields nothing
+			const uint32_t n = (uint32_t)pc.x.size();
+			if (!gvar.accumulate(gid, face.coords(), GvarPoints{n, pc.x.data(), pc.y.data(), pc.last_of_contour.data()}, acc))
+				return false;
+			ContourEmitter<B> em(out, t);
+			em.begin(n, (uint16_t)n_contours);
+			for (uint32_t i = 0; i < n; i++)
+				em.point((float)pc.x[i] + acc[(size_t)2 * i], (float)pc.y[i] + acc[(size_t)2 * i + 1], pc.on_curve[i] != 0, pc.last_of_contour[i] != 0);
+			em.end();
+			return true;
+		}
+		if (n_contours == 0 || glyph.size() < 10)
+			return n_contours == 0;
+		// composite: one point per record the static walk reads
+		uint32_t n_records = 0;
+		for (size_t p = 0;;) {
+			uint16_t flags, child;
+			Affine k;
+			if (!read_component(body, p, flags, child, k))
+				break;
+			n_records++;
+			if (!(flags & 0x0020))
+				break;
+		}
+		if (!gvar.accumulate(gid, face.coords(), GvarPoints{n_records}, acc))
+			return false;
+		uint32_t record = 0;
+		for (size_t p = 0;; record++) {
+			uint16_t flags, child;
+			Affine k;
+			if (!read_component(body, p, flags, child, k))
+				break;
+			k.e += acc[(size_t)2 * record];
+			k.f += acc[(size_t)2 * record + 1];
+			if (!walk(child, depth + 1, t.then(k)))
+				return false;
+			if (!(flags & 0x0020)) // MORE_COMPONENTS
+				break;
+		}
+		return true;
+	}
+};
+
 bool Face::outline_glyph(uint16_t gid, OutlineBuilder &builder) const
 {
 	if (!has_glyf_outlines() && cff_) // ttf-parser: glyf first, then cff
 		return cff_->outline(gid, builder);
+	if (gvar_) {
+		GvarCallbacks sink{builder};
+		GvarWalker<GvarCallbacks> w{*this, *gvar_, sink};
+		return w.walk(gid, 0, Affine{});
+	}
 	const auto g = glyph_data(gid);
 	if (!g)
 		return false;
@@ -1133,6 +1534,7 @@ struct PackedCursorSink {
 		coords.resize((size_t)(cp - coords.data()));
 	}
 };
+struct GvarCursorSink : PackedCursorSink {}; // (the gvar walk's: GvarWalker)
 // (CFF charstrings go through the OutlineBuilder interface)
 struct PackedSinkVirtual final : OutlineBuilder {
 	PackedSink s;
@@ -1241,7 +1643,7 @@ struct PartsSink {
 
 bool Face::glyph_parts(uint16_t gid, std::vector<GlyfPart> &parts, std::vector<uint8_t> &bytes, uint32_t &slots, bool *overflow) const
 {
-	const auto g = glyph_data(gid);
+	const auto g = has_glyf_form() ? glyph_data(gid) : std::nullopt;
 	if (!g)
 		return false;
 	PartsSink sink{parts, bytes, slots, overflow};
@@ -1309,7 +1711,7 @@ const ResidentTable &Face::resident_table() const
 	ResidentCell &cell = *resident_;
 	std::call_once(cell.once, [&] {
 		ResidentTable &t = cell.table;
-		if (!has_glyf_outlines())
+		if (!has_glyf_form())
 			return;
 		std::map<std::pair<const uint8_t *, size_t>, uint32_t> stored;
 		const uint32_t n = num_glyphs_;
@@ -1346,11 +1748,27 @@ uint64_t Face::resident_serial() const
 FontTables Face::font_tables() const
 {
 	FontTables t;
-	if (!has_glyf_outlines() || loca_.size() > 0xFFFFFFFFu || glyf_.size() > 0xFFFFFFFFu)
+	if (!has_glyf_form() || loca_.size() > 0xFFFFFFFFu || glyf_.size() > 0xFFFFFFFFu)
 		return t;
 	t.loca = loca_.data(), t.n_loca_bytes = (uint32_t)loca_.size();
 	t.glyf = glyf_.data(), t.n_glyf_bytes = (uint32_t)glyf_.size();
 	t.num_glyphs = num_glyphs_, t.loca_entries = (uint32_t)loca_entries_, t.loca_long = loca_long_ ? 1u : 0u;
+	t.ok = true;
+	return t;
+}
+
+GvarTables Face::gvar_tables() const
+{
+	GvarTables t;
+	if (!placed_by_gvar() || loca_.size() > 0xFFFFFFFFu || glyf_.size() > 0xFFFFFFFFu || gvar_->table().size() > 0xFFFFFFFFu)
+		return t;
+	t.tables.loca = loca_.data(), t.tables.n_loca_bytes = (uint32_t)loca_.size();
+	t.tables.glyf = glyf_.data(), t.tables.n_glyf_bytes = (uint32_t)glyf_.size();
+	t.tables.num_glyphs = num_glyphs_, t.tables.loca_entries = (uint32_t)loca_entries_, t.tables.loca_long = loca_long_ ? 1u : 0u;
+	t.tables.ok = true;
+	t.gvar = gvar_->table().data(), t.gvar_len = (uint32_t)gvar_->table().size();
+	t.n_axes = (uint32_t)coords().size(), t.coords = coords().data();
+	t.shared_tuple_count = gvar_->shared_tuple_count(), t.glyph_count = gvar_->glyph_count();
 	t.ok = true;
 	return t;
 }
@@ -1451,6 +1869,11 @@ bool Face::outline_glyph_packed(uint16_t gid, std::vector<uint8_t> &kinds, std::
 	if (!has_glyf_outlines() && cff_) {
 		PackedSinkVirtual v(sink);
 		return cff_->outline(gid, v);
+	}
+	if (gvar_) {
+		GvarCursorSink cursor{{kinds, coords}};
+		GvarWalker<GvarCursorSink> w{*this, *gvar_, cursor};
+		return w.walk(gid, 0, Affine{});
 	}
 	const auto g = glyph_data(gid);
 	if (!g)

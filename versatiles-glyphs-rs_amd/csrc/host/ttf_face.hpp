@@ -23,6 +23,7 @@
 namespace vg {
 
 class CffTable;
+class GvarTable;
 
 // ttf_parser::OutlineBuilder — f32 font units
 struct OutlineBuilder {
@@ -140,10 +141,23 @@ void apply_avar(const uint8_t *data, size_t len, std::vector<int16_t> &coords);
 // A `glyf` face's `loca` and `glyf` for the device's table builder (vgsdf_font_tables_desc of include/vgsdf.h, field for field):
 // views of the two tables and the three numbers Face::glyph_data goes by.  No glyph is looked at.
 struct FontTables {
-	bool ok = false;                                // false: no `glyf` outlines, or a table of 4 GiB or more
+	bool ok = false;                                // false: no glyf form (Face::has_glyf_form), or a table of 4 GiB or more
 	const uint8_t *loca = nullptr, *glyf = nullptr; // views into the face's bytes
 	uint32_t n_loca_bytes = 0, n_glyf_bytes = 0;
 	uint32_t num_glyphs = 0, loca_entries = 0, loca_long = 0;
+};
+
+// A placed `glyf` face's tables for the device's gvar builder (vgsdf_font_gvar_desc of include/vgsdf.h): FontTables' views of
+// loca and glyf (filled although the face has no glyf form: its entries are outlines only together with gvar), a view of the
+// whole gvar, and the face's coordinates.  No glyph is looked at.
+struct GvarTables {
+	bool ok = false; // false: not a face placed by gvar (Face::placed_by_gvar), or a table of 4 GiB or more
+	FontTables tables;
+	const uint8_t *gvar = nullptr;
+	uint32_t gvar_len = 0, n_axes = 0;
+	const int16_t *coords = nullptr; // [n_axes]: the face's own, alive as long as the face
+	// the header numbers, as GvarTable::parse read them
+	uint32_t shared_tuple_count = 0, glyph_count = 0;
 };
 
 // Non-owning big-endian byte view with checked reads.
@@ -179,10 +193,50 @@ public:
 	// read, without the crate at hand: PARITY UNPINNED, see cff.hpp.)
 	// The same face AT A POSITION of its design space (the crate's set_variation for every axis): coords are final normalised
 	// coordinates, F2Dot14, one per `fvar` axis (at most 64 are counted).  CFF2 outlines, and everything built from them, are
-	// drawn there, and glyph_hor_advance follows `HVAR`.  Refused (nullopt, *err says why): a file without a readable `fvar`,
-	// a face whose outlines are `glyf` (there is no `gvar` reader), a coordinate count other than the axes', an `HVAR` whose
-	// store is not of format 1 or holds 32-bit deltas (LONG_WORDS).  An `HVAR` that cannot be read at all (major version not
-	// 1, a header, store header or region list outside the table) counts as absent, as the crate drops it.
+	// drawn there, `glyf` outlines are moved by `gvar` (G1 to G6 below), and glyph_hor_advance follows `HVAR`.  Refused (nullopt,
+	// *err says why): a file without a readable `fvar`, a face whose outlines are `glyf` without a readable `gvar` (version 1.0,
+	// axisCount equal to fvar's, the header, the shared tuples and the offset array inside the table), a coordinate count other
+	// than the axes', an `HVAR` whose store is not of format 1 or holds 32-bit deltas (LONG_WORDS).  An `HVAR` that cannot be
+	// read at all (major version not 1, a header, store header or region list outside the table) counts as absent, as the crate
+	// drops it; without `HVAR` the `hmtx` advance stands (advances from gvar's phantom points are not read).
+	//
+	// A `glyf` face at a position: outline_glyph, outline_glyph_packed and command_table() deliver the outline there.  The rules
+	// are the OpenType specification's; where it leaves the f32 order open, the order below is the definition.
+	// G1, glyph data.  Glyph id g owns the `gvar` bytes [offset[g], offset[g+1]) behind glyphVariationDataArrayOffset, in the
+	//   short (times 2) or the long offset form.  A glyph id at or past glyphCount, or with an empty range, has no deltas; a
+	//   range that descends or leaves the table is malformed.  tupleVariationCount: bit 0x8000 = shared point numbers (they
+	//   stand first in the serialized data, and are read whenever the bit is set), the low 12 bits the count (0: no deltas);
+	//   dataOffset follows.  Each tuple header holds variationDataSize and tupleIndex — 0x8000 an embedded peak, 0x4000
+	//   intermediate start and end, 0x2000 private point numbers, the low 12 bits the shared tuple index — and the tuples' data
+	//   lie one behind the other from dataOffset (behind the shared point numbers) on, variationDataSize bytes each, whether
+	//   the tuple is applied or skipped.
+	// G2, packed point numbers.  A count byte of 0: all points.  Bit 7 set: the two-byte count form (a count of 0 in that form
+	//   lists no point).  Runs of 1 to 128 values (control byte: bit 7 = 16-bit values, low 7 bits + 1 the length; a run is read
+	//   as far as the count goes), increments summed in u16.  Numbers that are not strictly ascending make the glyph's data
+	//   malformed; a number at or past the point count names no point (its deltas are read and dropped).  A tuple with neither
+	//   private nor shared numbers is over all points.
+	// G3, packed deltas.  One stream of 2 * count values, the x deltas first: a control byte — 0x80 a zero run, 0x40 a word
+	//   run, else a byte run, the low 6 bits + 1 the run length — and the run's values.
+	// G4, scalar of a tuple.  The f32 product over the axes, in axis order, of axis_factor(coord, start, peak, end) (cff.hpp);
+	//   without an intermediate region start = min(peak, 0) and end = max(peak, 0).  A tuple whose scalar is 0 is skipped (its
+	//   point numbers and deltas are not looked at).  A shared tuple index at or past sharedTupleCount makes the data malformed.
+	// G5, simple glyph of n points (+ 4 phantom points, numbered n .. n + 3).  An accumulator (ax, ay) per point starts at 0;
+	//   tuples are applied in order; a touched point gets a += f32(delta) * scalar, one product and one sum.  A tuple over all
+	//   points touches every point.  A tuple over a subset leaves the other points of a contour to inference, x and y each on
+	//   its own, from the nearest touched points before and behind it in the contour (cyclic) and the ORIGINAL INTEGER
+	//   coordinates: with pa / da of the touched point before, pb / db of the one behind (da, db already scaled) and p the
+	//   target — pa == pb: da if da == db, else 0; p <= min(pa, pb): the delta of the smaller of the two coordinates;
+	//   p >= max(pa, pb): that of the larger; otherwise d = f32(p - pa) / f32(pb - pa) and (1 - d) * da + d * db in f32 — and the
+	//   result is added as a touched point's would be.  A contour without a touched point gets nothing from that tuple; phantom
+	//   points are never inferred.  The point is then f32(i16 coordinate) + a; everything behind that is the static walk's
+	//   (transform, implied midpoints, closing curve).  Contours are those of the static walk's own end-point iterator.
+	// G6, composite glyph.  One point per component record the static walk reads, in record order, + 4 phantom points; touched
+	//   points only, no inference.  Component k's e and f, as the static walk has them, get += a in f32 before the transform is
+	//   combined with the parent's.  Children vary by their own data.
+	// Malformed data of a glyph id — a header, point numbers or deltas that leave the glyph's range, a tuple that ends before
+	// its deltas do — delivers nothing from where the data is needed: outline_glyph returns false there, leaves delivered
+	// before it stay.  PARITY UNPINNED like the rest of the variation code; checked against fontTools and a strict restatement
+	// (tests/test_gvar_instances_host.py).
 	static std::optional<Face> parse_at(const uint8_t *data, size_t len, const std::vector<int16_t> &coords, std::string *err = nullptr);
 	// made by parse_at (even at all-zero coordinates)
 	bool at_position() const { return at_position_; }
@@ -207,7 +261,7 @@ public:
 	// 0..4 = move / line / quad / curve / close + the coordinates the kind carries); glyf outlines are walked with the sink
 	// inlined (no virtual call per point).
 	bool outline_glyph_packed(uint16_t glyph_id, std::vector<uint8_t> &kinds, std::vector<float> &coords) const;
-	// glyf fonts only (has_glyf_outlines()): the same walk up to the simple glyphs, which are not decoded but appended as
+	// glyf fonts only (has_glyf_form()): the same walk up to the simple glyphs, which are not decoded but appended as
 	// parts — their bytes to `bytes` (4-aligned), their command slots counted from `slots` on.  false: ttf-parser returns
 	// None at this point (parts appended so far stay, as the callbacks delivered so far would).  *overflow is set (and the
 	// walk stops) when the batch would pass what its 32-bit offsets address (2^26 bytes / slots, 2^22 parts per recorder): a composite
@@ -234,6 +288,9 @@ public:
 	const CharstringTable &charstring2_table() const;
 	// The face's loca and glyf for the device's table builder (the resident form without the host walking a glyph).
 	FontTables font_tables() const;
+	// A face placed by gvar: its loca, glyf and gvar and its coordinates for the device's builder of its command store — the host
+	// half of vgsdf_font_create_gvar, as font_tables() is of vgsdf_font_create_tables.
+	GvarTables gvar_tables() const;
 	// The face's tables for the device's family-table kernels: built once, on first use (thread-safe).
 	const FamilyTables &family_tables() const;
 	// ttf-parser's `tables().cmap.is_some()`; the reference refuses fonts without one (metadata.rs:104-107)
@@ -242,6 +299,12 @@ public:
 	// A font whose outlines live in a table this reader cannot walk (`CFF2`, or a `CFF ` table it fails to parse)
 	// is refused at load time instead of yielding empty glyphs.
 	bool has_glyf_outlines() const { return !glyf_.empty() && !loca_.empty(); }
+	// made by parse_at from `glyf` + `gvar`: the entries of `glyf` are NOT the face's outlines as they stand
+	bool placed_by_gvar() const { return gvar_ != nullptr; }
+	// THE predicate of every form that reads `glyf` entries as outlines (glyph_parts, resident_table, font_tables, the glyf
+	// stores and the glyf submission form, a font id's say in mixing): a face placed by gvar has none of them and is a command
+	// face everywhere
+	bool has_glyf_form() const { return has_glyf_outlines() && !placed_by_gvar(); }
 	bool has_cff_outlines() const { return cff_ != nullptr; }
 	bool has_unsupported_outlines() const { return !has_glyf_outlines() && !cff_ && cff_unreadable_; }
 	// Face::names() (src/font/metadata.rs:92-97): every record of the `name` table in table order as
@@ -274,6 +337,7 @@ private:
 	uint16_t units_per_em_ = 0, num_glyphs_ = 0, num_hmetrics_ = 0;
 	bool loca_long_ = false, has_cmap_ = false, cff_unreadable_ = false;
 	std::shared_ptr<const CffTable> cff_;
+	std::shared_ptr<const GvarTable> gvar_; // parse_at of a `glyf` face
 	size_t loca_entries_ = 0;
 	struct ResidentCell {
 		std::once_flag once, serial_once;
@@ -295,6 +359,7 @@ private:
 	std::shared_ptr<FamilyCell> family_ = std::make_shared<FamilyCell>();
 
 	template <class B, bool PARTS> friend struct GlyfWalker;
+	template <class B> friend struct GvarWalker;
 };
 
 } // namespace vg

@@ -12,6 +12,8 @@
 #include "charstring_limits.h"
 #include "glyf_table_kernels.h"
 #include "glyf_table_limits.h"
+#include "gvar_kernels.h"
+#include "gvar_limits.h"
 #include "outline_kernels.h"
 #include "resident_build.h"
 
@@ -633,6 +635,226 @@ int vgsdf_font_create_tables_within(vgsdf_ctx *ctx, const vgsdf_font_tables_desc
 }
 
 void vgsdf_font_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]) { pass_ms_out(ctx ? ctx->glyf_tables_ms : nullptr, ms); }
+
+} // extern "C"
+
+namespace {
+uint32_t be16_at(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
+uint32_t be32_at(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+// vgsdf_font_create_gvar_within: count pass, read-back and layout, deltas pass in slices over the context's scratch, emit pass,
+// context pass (gvar_kernels.h)
+int create_gvar(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *desc, uint64_t max_store_bytes, vgsdf_font **out, uint64_t *store_bytes)
+{
+	const char *name = "vgsdf_font_create_gvar";
+	if (!desc || !out || (desc->tables.n_loca_bytes && !desc->tables.loca) || (desc->tables.n_glyf_bytes && !desc->tables.glyf) || !desc->gvar ||
+	    !desc->coords) {
+		ctx->err = "vgsdf_font_create_gvar: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	*out = nullptr;
+	if (store_bytes)
+		*store_bytes = 0;
+	ctx->gvar_ms[0] = ctx->gvar_ms[1] = ctx->gvar_ms[2] = 0.0f;
+	const vgsdf_font_tables_desc &in = desc->tables;
+	const uint32_t n = in.num_glyphs;
+	if (n > 0xFFFFu || in.loca_long > 1u || (uint64_t)in.loca_entries * (in.loca_long ? 4u : 2u) > in.n_loca_bytes || in.loca_entries > n + 1) {
+		ctx->err = "vgsdf_font_create_gvar: more than 65535 glyphs, loca_long not 0 or 1, or more loca entries than the loca bytes hold or than num_glyphs + 1";
+		return VGSDF_E_ARG;
+	}
+	// GvarTable::parse: majorVersion, minorVersion, axisCount, sharedTupleCount, sharedTuplesOffset, glyphCount, flags,
+	// glyphVariationDataArrayOffset; the shared tuples and the offset array inside the table
+	const uint8_t *g = desc->gvar;
+	const uint64_t gvar_len = desc->gvar_len;
+	vgsdf::GvarRef face{};
+	bool readable = desc->n_axes >= 1 && desc->n_axes <= vg::kGvarMaxAxes && gvar_len >= 20 && be32_at(g) == 0x00010000u && be16_at(g + 4) == desc->n_axes;
+	if (readable) {
+		face.shared_count = be16_at(g + 6), face.shared_at = be32_at(g + 8), face.glyph_count = be16_at(g + 12);
+		face.long_offsets = be16_at(g + 14) & 1u, face.data_at = be32_at(g + 16);
+		const uint64_t tuples = (uint64_t)face.shared_count * desc->n_axes * 2, offsets = ((uint64_t)face.glyph_count + 1) * (face.long_offsets ? 4u : 2u);
+		readable = face.shared_at <= gvar_len && tuples <= gvar_len - face.shared_at && offsets <= gvar_len - 20;
+	}
+	if (!readable) {
+		ctx->err = "vgsdf_font_create_gvar: axes not 1 .. 64, a gvar that is not version 1.0 or has another axisCount, or a header, shared tuples "
+		           "or offset array outside gvar_len";
+		return VGSDF_E_ARG;
+	}
+	std::unique_ptr<vgsdf_font> f(new (std::nothrow) vgsdf_font());
+	if (!f) {
+		ctx->err = "vgsdf_font_create_gvar: out of host memory";
+		return VGSDF_E_OOM;
+	}
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	PassEvents ev;
+	hipEvent_t ev_deltas = nullptr; // (the deltas pass ends here; PassEvents has the other three)
+	struct EventGuard {
+		hipEvent_t &e;
+		~EventGuard()
+		{
+			if (e)
+				(void)hipEventDestroy(e);
+		}
+	} guard{ev_deltas};
+	if (hipError_t err = ev.create(); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipEventCreate", err);
+	if (hipError_t err = hipEventCreate(&ev_deltas); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipEventCreate", err);
+	// the description on the device, for the duration of this call: loca | glyf | gvar | coords | counts (4 per glyph id) | flags | pt_at
+	const size_t a_glyf = align_up(in.n_loca_bytes, 16), a_gvar = align_up(a_glyf + in.n_glyf_bytes, 16), a_coords = align_up(a_gvar + (size_t)gvar_len, 16),
+	             a_counts = align_up(a_coords + 2 * (size_t)desc->n_axes, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kGvarCounts * n,
+	             a_at = a_flags + 4 * (size_t)vgsdf::GVAR_FLAG_WORDS, a_total = a_at + 4 * ((size_t)n + 1);
+	ScratchBuf dev, sums, tmp;
+	if (hipError_t e = dev.ensure(a_total + 16); e != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", e);
+	uint8_t *a = (uint8_t *)dev.p;
+	Calls q(st);
+	q.copy(a, in.loca, in.n_loca_bytes);
+	q.copy(a + a_glyf, in.glyf, in.n_glyf_bytes);
+	q.copy(a + a_gvar, desc->gvar, (size_t)gvar_len);
+	q.copy(a + a_coords, desc->coords, 2 * (size_t)desc->n_axes);
+	q.zero(a + a_flags, 4 * (size_t)vgsdf::GVAR_FLAG_WORDS);
+	face.loca = a, face.glyf = a + a_glyf, face.gvar = a + a_gvar, face.coords = (const int16_t *)(a + a_coords);
+	face.glyf_len = in.n_glyf_bytes, face.loca_entries = in.loca_entries, face.loca_long = in.loca_long, face.n_glyph_ids = n;
+	face.gvar_len = (uint32_t)gvar_len, face.n_axes = desc->n_axes;
+	uint32_t *d_counts = (uint32_t *)(a + a_counts), *d_flags = (uint32_t *)(a + a_flags), *d_at = (uint32_t *)(a + a_at);
+	q.record(ev.at[0]);
+	if (n)
+		q.launch([&] { return vgsdf_gvar_count(&face, d_counts, d_flags, st); });
+	q.record(ev.at[1]);
+	// the counts and, behind them, the flag words: one read-back
+	std::vector<uint32_t> got((size_t)vgsdf::kGvarCounts * n + vgsdf::GVAR_FLAG_WORDS);
+	q.read_back(got.data(), d_counts, 4 * got.size());
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, name, "count pass", q.e);
+	ev.elapsed(ctx->gvar_ms, 0);
+	const uint32_t *fl = got.data() + (size_t)vgsdf::kGvarCounts * n;
+	if (fl[vgsdf::GVAR_FLAG_RECORDS] || fl[vgsdf::GVAR_FLAG_CMDS]) {
+		ctx->err = fl[vgsdf::GVAR_FLAG_RECORDS]
+		               ? "vgsdf_font_create_gvar: a glyph past VGSDF_GLYF_MAX_COMPONENTS, or a composite of more than 65535 component records"
+		               : "vgsdf_font_create_gvar: a glyph of more than 2^26 commands";
+		return VGSDF_E_GLYF;
+	}
+	// the running sums: the points of the deltas pass, the store's layout (what vgsdf_font_create_commands is given by its caller)
+	std::vector<uint32_t> pt_at((size_t)n + 1), cmd_off((size_t)n + 1), dat_off((size_t)n + 1);
+	uint64_t points = 0, cmds = 0, floats = 0;
+	f->slots.assign(n, 0);
+	for (uint32_t gid = 0; gid < n; gid++) {
+		const uint32_t *c = got.data() + (size_t)vgsdf::kGvarCounts * gid;
+		pt_at[gid] = (uint32_t)points, cmd_off[gid] = (uint32_t)cmds, dat_off[gid] = (uint32_t)floats;
+		f->slots[gid] = c[1];
+		points += c[0], cmds += c[1], floats += c[2];
+		if (vgsdf::CommandStoreLayout(n, cmds).total > 0xFFFFFFFCull || 4ull * floats > 0xFFFFFFFCull) {
+			ctx->err = "vgsdf_font_create_gvar: a store (29 bytes per command, 4 per glyph id) or coordinates past what 32-bit offsets address";
+			return VGSDF_E_GLYF;
+		}
+	}
+	// (65535 glyph ids of at most 65539 points: below 2^32)
+	const uint32_t n_cmds = (uint32_t)cmds, n_floats = (uint32_t)floats;
+	pt_at[n] = (uint32_t)points, cmd_off[n] = n_cmds, dat_off[n] = n_floats;
+	const vgsdf::CommandStoreLayout at(n, n_cmds);
+	if (store_bytes)
+		*store_bytes = at.total;
+	if (at.total > max_store_bytes)
+		return VGSDF_OK; // (*out stays NULL: the caller's limit, nothing allocated)
+	// the deltas pass, in slices of glyph ids over the context's scratch
+	if (hipError_t err = sums.ensure(8 * (size_t)points + 16); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", err);
+	float *d_acc = (float *)sums.p;
+	q.copy(d_at, pt_at.data(), 4 * ((size_t)n + 1));
+	q.record(ev.at[1]);
+	for (uint32_t g0 = 0; g0 < n && !q.failed();) {
+		uint32_t g1 = g0 + 1;
+		while (g1 < n && pt_at[g1 + 1] - pt_at[g0] <= vg::kGvarSlicePoints)
+			g1++;
+		const size_t slice = pt_at[g1] - pt_at[g0];
+		if (slice) {
+			// sx | sy | x | y | mark, each 16-aligned
+			const size_t s_sy = align_up(4 * slice, 16), s_x = s_sy + s_sy, s_y = s_x + align_up(2 * slice, 16), s_mark = s_y + align_up(2 * slice, 16),
+			             s_total = s_mark + slice;
+			if (hipError_t err = ctx->gvar_scratch.ensure(s_total + 16); err != hipSuccess) // (nothing in flight reads it: see below)
+				return font_hip_error(ctx, name, "hipMalloc", err);
+			uint8_t *s = (uint8_t *)ctx->gvar_scratch.p;
+			const vgsdf::GvarScratch scratch{(float *)s, (float *)(s + s_sy), (int16_t *)(s + s_x), (int16_t *)(s + s_y), s + s_mark};
+			q.launch([&] { return vgsdf_gvar_deltas(&face, g0, g1, d_counts, d_at, d_acc, &scratch, d_flags, st); });
+			// (the launches follow one another on one stream over one scratch; it grows only between them, so the stream is drained
+			// before the next slice may replace it)
+			if (g1 < n)
+				q.sync();
+		}
+		g0 = g1;
+	}
+	q.record(ev_deltas);
+	uint32_t flags[vgsdf::GVAR_FLAG_WORDS] = {};
+	q.read_back(flags, d_flags, sizeof flags);
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, name, "deltas pass", q.e);
+	(void)hipEventElapsedTime(&ctx->gvar_ms[1], ev.at[1], ev_deltas);
+	if (flags[vgsdf::GVAR_FLAG_MALFORMED] || flags[vgsdf::GVAR_FLAG_DELTAS]) {
+		ctx->err = flags[vgsdf::GVAR_FLAG_MALFORMED] ? "vgsdf_font_create_gvar: a glyph with malformed variation data"
+		                                             : "vgsdf_font_create_gvar: a glyph past VGSDF_GVAR_MAX_DELTAS";
+		return VGSDF_E_GLYF;
+	}
+	f->device = ctx->device;
+	f->n_glyph_ids = n;
+	f->commands = true;
+	const ContextStagingLayout tat(n, n_cmds, n_floats);
+	if (hipError_t err = f->store.ensure(at.total + 16); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", err);
+	if (hipError_t err = tmp.ensure(tat.total); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", err);
+	uint8_t *d = (uint8_t *)f->store.p, *t = (uint8_t *)tmp.p;
+	uint32_t emit_flag = 0;
+	// (the emit pass reads cmd_off from the store, where it stays, and dat_off from the staging, as the context pass behind it does)
+	const uint32_t flag = finish_command_store(q, *f, at, t, tat, n_cmds, cmd_off.data(), dat_off.data(), [&] {
+		q.record(ev.at[1]);
+		if (n)
+			q.launch([&] {
+				return vgsdf_gvar_emit(&face, d_counts, d_at, d_acc, (const uint32_t *)(d + at.cmd_off), (const uint32_t *)(t + tat.dat_off), t + tat.kinds,
+				                       (float *)(t + tat.coords), d_flags, st);
+			});
+		q.record(ev.at[2]);
+	}, &emit_flag, d_flags + vgsdf::GVAR_FLAG_EMIT);
+	if (q.failed())
+		return font_hip_error(ctx, name, "emit pass", q.e);
+	(void)hipEventElapsedTime(&ctx->gvar_ms[2], ev.at[1], ev.at[2]);
+	if (flag || emit_flag) { // (the two passes walk one text over the same bytes: said by the passes themselves)
+		ctx->err = "vgsdf_font_create_gvar: the emit pass did not match the count pass, or the context pass refused the commands";
+		return VGSDF_E_HIP;
+	}
+	*out = f.release();
+	return VGSDF_OK;
+}
+} // namespace
+
+extern "C" {
+
+int vgsdf_font_create_gvar(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in, vgsdf_font **out)
+{
+	return vgsdf_font_create_gvar_within(ctx, in, ~0ull, out, nullptr);
+}
+
+int vgsdf_font_create_gvar_within(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in, uint64_t max_store_bytes, vgsdf_font **out,
+                                  uint64_t *store_bytes)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	try {
+		return create_gvar(ctx, in, max_store_bytes, out, store_bytes);
+	} catch (const std::bad_alloc &) {
+		ctx->err = "vgsdf_font_create_gvar: out of host memory";
+		return VGSDF_E_OOM;
+	}
+}
+
+void vgsdf_font_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3])
+{
+	if (ms)
+		for (int i = 0; i < 3; i++)
+			ms[i] = ctx ? ctx->gvar_ms[i] : 0.0f;
+}
 
 } // extern "C"
 

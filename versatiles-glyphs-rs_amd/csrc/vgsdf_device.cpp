@@ -132,6 +132,7 @@ void vgsdf_destroy(vgsdf_ctx *ctx)
 	ctx->h_scratch.release();
 	if (ctx->charstring_spill)
 		(void)hipFree(ctx->charstring_spill);
+	ctx->gvar_scratch.release();
 	delete ctx;
 }
 

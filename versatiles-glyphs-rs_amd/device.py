@@ -107,6 +107,10 @@ class _CFontTablesDesc(C.Structure):  # vgsdf_font_tables_desc
                 ("n_glyf_bytes", C.c_uint32), ("loca", C.c_void_p), ("glyf", C.c_void_p)]
 
 
+class _CFontGvarDesc(C.Structure):  # vgsdf_font_gvar_desc
+    _fields_ = [("tables", _CFontTablesDesc), ("gvar", C.c_void_p), ("gvar_len", C.c_uint32), ("n_axes", C.c_uint32), ("coords", C.c_void_p)]
+
+
 class _COutlinesRanges(C.Structure):  # vgsdf_outlines_ranges
     _fields_ = [("n_tasks", C.c_uint32), ("n_families", C.c_uint32), ("families", C.c_void_p), ("family_of", C.c_void_p),
                 ("first", C.c_void_p), ("last", C.c_void_p), ("pbf_pre", C.c_void_p)]
@@ -124,6 +128,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_outlines_task_extents", "vgsdf_family_create_tables", "vgsdf_family_read", "vgsdf_family_tables_kernel_ms",
     "vgsdf_font_create_tables", "vgsdf_font_create_tables_within", "vgsdf_font_read", "vgsdf_font_tables_kernel_ms",
     "vgsdf_fonts_create_tables", "vgsdf_fonts_create_tables_within", "vgsdf_fonts_tables_kernel_ms",
+    "vgsdf_font_create_gvar", "vgsdf_font_create_gvar_within", "vgsdf_font_gvar_kernel_ms",
     "vgsdf_outlines_submit_resident_mixed", "vgsdf_family_create_mixed", "vgsdf_family_create_tables_mixed",
     "vgsdf_family_create_tables_var", "vgsdf_family_create_tables_var_mixed",
 ]
@@ -190,6 +195,10 @@ def load_library():
         L.vgsdf_fonts_create_tables_within.argtypes = [vp, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.vgsdf_fonts_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_fonts_tables_kernel_ms.restype = None
+        L.vgsdf_font_create_gvar.argtypes = [vp, C.POINTER(_CFontGvarDesc), C.POINTER(vp)]
+        L.vgsdf_font_create_gvar_within.argtypes = [vp, C.POINTER(_CFontGvarDesc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.vgsdf_font_gvar_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_font_gvar_kernel_ms.restype = None
         L.vgsdf_font_free.argtypes = [vp, vp]
         L.vgsdf_font_device_bytes.argtypes = [vp]
         L.vgsdf_font_device_bytes.restype = C.c_uint64
@@ -658,6 +667,38 @@ class SdfContext:
             return (ResidentFont(self, h) if h.value else None), int(want.value)
         self._check(load_library().vgsdf_font_create_tables(self._h, C.byref(d), C.byref(h)))
         return ResidentFont(self, h)
+
+    def font_create_gvar(self, desc: dict, max_store_bytes=None, **override):
+        """vgsdf_font_create_gvar: a placed `glyf` face's tables and position (vgsdf_font_gvar_desc as a dict: the keys of
+        font_create_tables plus gvar (bytes) and coords (int16, one per axis) — what FontManager.gvar_font_desc returns) -> the
+        command font the DEVICE builds from them.  override: raw struct fields (n_loca_bytes, n_glyf_bytes, gvar_len, n_axes) for
+        descriptions that lie.  VgsdfError with code VGSDF_E_GLYF: the device refuses the face (malformed variation data,
+        VGSDF_GVAR_MAX_DELTAS, the walk's and the store's bounds).
+        max_store_bytes (vgsdf_font_create_gvar_within): -> (ResidentFont or None when the store would pass it, store bytes)"""
+        loca, glyf = np.frombuffer(bytes(desc["loca"]), dtype=np.uint8), np.frombuffer(bytes(desc["glyf"]), dtype=np.uint8)
+        gvar = np.frombuffer(bytes(desc["gvar"]), dtype=np.uint8)
+        coords = np.ascontiguousarray(desc["coords"], dtype=np.int16)
+        d = _CFontGvarDesc()
+        d.tables = _CFontTablesDesc(int(desc["num_glyphs"]), int(desc["loca_entries"]), int(desc["loca_long"]),
+                                    override.get("n_loca_bytes", len(loca)), override.get("n_glyf_bytes", len(glyf)),
+                                    loca.ctypes.data if len(loca) else None, glyf.ctypes.data if len(glyf) else None)
+        d.gvar = gvar.ctypes.data if len(gvar) else None
+        d.gvar_len = override.get("gvar_len", len(gvar))
+        d.n_axes = override.get("n_axes", len(coords))
+        d.coords = coords.ctypes.data if len(coords) else None
+        h = C.c_void_p()
+        if max_store_bytes is not None:
+            want = C.c_uint64()
+            self._check(load_library().vgsdf_font_create_gvar_within(self._h, C.byref(d), int(max_store_bytes), C.byref(h), C.byref(want)))
+            return (ResidentFont(self, h) if h.value else None), int(want.value)
+        self._check(load_library().vgsdf_font_create_gvar(self._h, C.byref(d), C.byref(h)))
+        return ResidentFont(self, h)
+
+    def font_gvar_kernel_ms(self):
+        """(count, deltas, emit) pass milliseconds of this context's last font_create_gvar"""
+        ms = (C.c_float * 3)()
+        load_library().vgsdf_font_gvar_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def font_read(self, font: ResidentFont) -> dict:
         """vgsdf_font_read (test / inspection): the DEVICE's copy of a glyf-kind font as {leaf_off, leaves (GLYF_PART_DTYPE), bytes},

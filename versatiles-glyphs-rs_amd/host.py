@@ -79,6 +79,10 @@ class CharstringStats(C.Structure):  # vg_charstring_stats
     _fields_ = [(k, C.c_uint64) for k in ("fonts_decoded", "font_bytes", "fallbacks")]
 
 
+class GvarStats(C.Structure):  # vg_gvar_stats
+    _fields_ = [(k, C.c_uint64) for k in ("fonts_built", "font_bytes", "fallbacks")]
+
+
 WRITE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int)
 
 VGFONT_SYMBOLS = [
@@ -102,6 +106,7 @@ VGFONT_SYMBOLS = [
     "vg_renderer_reset_counters", "vg_manager_reduced_counters", "vg_manager_set_in_place_pbf", "vg_manager_set_glyf_on_device", "vg_manager_set_lane_form", "vg_manager_plan_lanes",
     "vg_manager_family_tables_desc", "vg_manager_font_tables_desc", "vg_manager_set_family_tables_on_device", "vg_manager_family_table_stats",
     "vg_manager_set_glyf_tables_on_device", "vg_manager_glyf_table_stats",
+    "vg_manager_set_gvar_on_device", "vg_manager_gvar_stats", "vg_manager_gvar_font_desc",
     "vg_manager_set_glyf_tables_batched", "vg_manager_glyf_table_batch_stats",
     "vg_manager_set_mixed_stores", "vg_manager_mixed_stats",
     "vg_manager_add_font_instance", "vg_manager_add_font_instance_normalized", "vg_font_variation_axes", "vg_font_named_instances",
@@ -157,6 +162,9 @@ def _L():
         L.vg_manager_family_table_stats.argtypes = [vp, C.POINTER(FamilyTableStats)]
         L.vg_manager_set_glyf_tables_on_device.argtypes = [vp, C.c_int]
         L.vg_manager_set_glyf_tables_on_device.restype = None
+        L.vg_manager_set_gvar_on_device.argtypes = [vp, C.c_int]
+        L.vg_manager_set_gvar_on_device.restype = None
+        L.vg_manager_gvar_stats.argtypes = [vp, C.POINTER(GvarStats)]
         L.vg_manager_glyf_table_stats.argtypes = [vp, C.POINTER(GlyfTableStats)]
         L.vg_manager_set_glyf_tables_batched.argtypes = [vp, C.c_int]
         L.vg_manager_set_glyf_tables_batched.restype = None
@@ -483,6 +491,17 @@ class FontManager:
         """resident families' tables are built by the device from the faces' cmap and hmtx tables (vgsdf_family_create_tables)
         instead of by the host's reader; a font id whose description or build is refused falls back; same bytes (default off)"""
         _L().vg_manager_set_family_tables_on_device(self._h, int(bool(on)))
+
+    def set_gvar_on_device(self, on: bool):
+        """the command store of a `glyf` face placed by add_font_instance is built by the DEVICE from loca, glyf and gvar
+        (vgsdf_font_create_gvar); a face it refuses goes the host reader's way, once.  Same store and output.  Off by default"""
+        _L().vg_manager_set_gvar_on_device(self._h, int(bool(on)))
+
+    def gvar_stats(self) -> dict:
+        """of the last render: {fonts_built, font_bytes, fallbacks} (vg_gvar_stats)"""
+        s = GvarStats()
+        _L().vg_manager_gvar_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in GvarStats._fields_}
 
     def set_glyf_tables_on_device(self, on: bool):
         """glyf-kind resident fonts are walked by the DEVICE from the faces' loca and glyf tables (vgsdf_font_create_tables): the host
@@ -934,6 +953,23 @@ class FontManager:
             raise RuntimeError(_err())
         return {"loca": C.string_at(d.loca, d.n_loca_bytes) if d.n_loca_bytes else b"", "glyf": C.string_at(d.glyf, d.n_glyf_bytes) if d.n_glyf_bytes else b"",
                 "num_glyphs": int(d.num_glyphs), "loca_entries": int(d.loca_entries), "loca_long": int(d.loca_long)}
+
+    def gvar_font_desc(self, font_id: str, file_index: int = 0):
+        """the description of one placed `glyf` file for SdfContext.font_create_gvar (vg_manager_gvar_font_desc), no device needed
+        and no glyph looked at: the keys of font_tables_desc plus gvar (bytes) and coords (int16 per axis), copies.  None: the
+        description refuses (not a glyf face placed by gvar)"""
+        from .device import _CFontGvarDesc
+        L = _L()
+        L.vg_manager_gvar_font_desc.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        d = _CFontGvarDesc()
+        if L.vg_manager_gvar_font_desc(self._h, font_id.encode(), int(file_index), C.byref(d)) != 0:
+            if _err().startswith("refused"):
+                return None
+            raise RuntimeError(_err())
+        t = d.tables
+        return {"loca": C.string_at(t.loca, t.n_loca_bytes) if t.n_loca_bytes else b"", "glyf": C.string_at(t.glyf, t.n_glyf_bytes) if t.n_glyf_bytes else b"",
+                "num_glyphs": int(t.num_glyphs), "loca_entries": int(t.loca_entries), "loca_long": int(t.loca_long),
+                "gvar": C.string_at(d.gvar, d.gvar_len), "coords": np.frombuffer(C.string_at(d.coords, 2 * d.n_axes), dtype=np.int16).copy()}
 
     def record_resident_commands(self, font_id: str) -> dict:
         """record_resident against command fonts: for any face the reader can read (CFF, CFF2, glyf)"""
