@@ -237,6 +237,20 @@ typedef struct {
 	uint64_t fallbacks;   /* faces the device refused: their stores came from the host reader */
 } vg_gvar_stats;
 int vg_manager_gvar_stats(const vg_manager *m, vg_gvar_stats *out);
+/* ... batched, 0 (default) / 1; has an effect only with vg_manager_set_gvar_on_device: when the store of a placed `glyf` face
+ * that shares its bytes with other placed faces — the instances of vg_manager_add_font_named_instances; files added with
+ * vg_manager_add_font_instance keep their own copies and their own calls — is asked for, the stores of ALL faces of that group
+ * that the lane's device has yet to build are built in one call (vgsdf_fonts_create_gvar: the tables uploaded once, one count
+ * launch, the deltas and the emit pass over all positions), each under its own command serial.  A refused position gets its store
+ * from the host reader, counted in vg_gvar_stats.fallbacks and remembered; one past the budget is left unbuilt, as without the
+ * switch.  vg_renderer_preload_fonts does the same.  Same stores, registry, budget and vg_gvar_stats, same output.  Off by
+ * default whatever a measurement says (profiles/gvar_batch_ab.txt).  vg_manager_gvar_batch_stats: of the last render. */
+void vg_manager_set_gvar_batched(vg_manager *m, int on);
+typedef struct {
+	uint64_t calls; /* batched calls made during the render (a group whose stores were all there makes none) */
+	uint64_t faces; /* the faces they were given */
+} vg_gvar_batch_stats;
+int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out);
 /* ... batched, 0 (default) / 1; has an effect only with vg_manager_set_glyf_tables_on_device: the glyf fonts of ALL files of a
  * font id that the device has yet to build are built in one call (vgsdf_fonts_create_tables: one count launch, one read-back, one
  * emit launch) instead of one call per file, so what a call costs beside its two passes is paid once per font id.  Same fonts,
@@ -275,6 +289,27 @@ int vg_manager_add_font_data(vg_manager *m, const char *name, const uint8_t *dat
 int vg_manager_add_font_instance(vg_manager *m, const char *name, const uint8_t *data, size_t len, const char *const *axis_tags,
                                  const float *values, int n);
 int vg_manager_add_font_instance_normalized(vg_manager *m, const char *name, const uint8_t *data, size_t len, const int16_t *coords, int n);
+/*
+ * EVERY NAMED INSTANCE of a variable file as a font id of its own — "Noto Sans Thin ... Black" from one file with one call.  Each
+ * instance record of the file's `fvar` is added by the rules of vg_manager_add_font_instance at the record's coordinates (same
+ * normalisation, same `avar` handling, same refusals); all instances share ONE copy of the bytes.  CFF2 files are accepted: their
+ * instances are drawn at their positions, one store each.  The font id of an instance is parse_font_name(family, ps_name) sent
+ * through the name generation every file's id comes from (vg_manager_generate_name, vg_name_to_id), where family is the file's name id 1
+ * and ps_name is
+ *   - the string of the record's postScriptNameID, when the record carries one that is not 0xFFFF and `name` has it;
+ *   - otherwise the variations PostScript name prefix (name id 25) — absent or empty: the family name with everything but ASCII
+ *     letters and digits removed —, then "-", then the string of the record's subfamilyNameID with its spaces removed (an id
+ *     that `name` does not have: nothing).
+ * Two instances that arrive at the same id merge like any files of one id (first provider wins).  Returns the number of
+ * instances added and writes the first `cap` font ids (NUL terminated, cut at VG_FONT_ID_MAX - 1 bytes) in the table's order;
+ * -1 with vg_last_error, nothing added: no readable `fvar`, no instance record, a face with `glyf` outlines and no readable
+ * `gvar`, or anything else vg_manager_add_font_instance refuses.
+ * vg_manager_set_scan_named_instances, 0 (default) / 1: vg_manager_scan and vg_manager_add_path treat a variable file that has
+ * instance records this way; with 0, and for every other file, they add the file at its default position as the reference does.
+ */
+#define VG_FONT_ID_MAX 256
+int vg_manager_add_font_named_instances(vg_manager *m, const uint8_t *data, size_t len, char (*ids)[VG_FONT_ID_MAX], int cap);
+void vg_manager_set_scan_named_instances(vg_manager *m, int on);
 /* What a file's `fvar` offers (host only), so that a caller can turn "the named instances of this file" into calls of
  * vg_manager_add_font_instance without a font parser of its own.  _axes: the number of axes, and the first `cap` of them in
  * tags / min / def / max (user space; each array may be NULL).  _named_instances: the number of instance records, and the first

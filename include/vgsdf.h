@@ -521,6 +521,46 @@ int vgsdf_font_create_gvar_within(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in
  * vgsdf_font_create_gvar took (HIP events around the pass, all its launches; 0 before the first, and for a pass that did not run) */
 void vgsdf_font_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3]);
 /*
+ * The same for ONE FACE AT MANY POSITIONS in one call — the named instances of a variable file, say.  The tables are uploaded
+ * once; the count pass (it looks at no coordinate), its read-back and the layout are done once and serve every position, whose
+ * stores all have the same sizes; the deltas pass and the emit pass run over (glyph id, position) pairs, the lanes of one glyph
+ * id at different positions side by side (csrc/gvar_batch_kernels.hip: the single call's device text); the context pass runs
+ * per store; three synchronisations for the whole call.  The deltas pass's launches cover glyph ids x positions of at most 2^17
+ * points x positions (or one glyph id at one position), so the context's scratch grows no further than under the single call.
+ * coords: n_positions x n_axes, position after position.  Each position that is built is a vgsdf_font of its own, with its own
+ * store: it cannot be told from what vgsdf_font_create_gvar makes of the same tables at that position alone, and is read, named
+ * by submissions and families, and freed like it, each alone (the same position given twice: two fonts).  Per position p:
+ *   built                                      status[p] VGSDF_OK      out[p] the font
+ *   over the limit (_within)                   status[p] VGSDF_OK      out[p] NULL, needed[p] its store's bytes
+ *   refused where the position decides: a glyph id whose variation data is malformed AT p (a tuple of scalar 0 is not read)
+ *                                              status[p] VGSDF_E_GLYF  out[p] NULL, the other positions untouched
+ *   refused whatever the position: the single call's other VGSDF_E_GLYF conditions — component records, a composite of more
+ *   than 65535, 2^26 commands, the store's bounds, and VGSDF_GVAR_MAX_DELTAS (tuples x points, whatever the scalars)
+ *                                              status[p] VGSDF_E_GLYF at every p (the call itself returns VGSDF_OK)
+ * _within takes the positions in order: one that is not refused is built when its store fits into what the positions built
+ * before it have left of max_store_bytes; one that does not fit is passed over and does not stop those behind it.  needed (may
+ * be NULL): [n_positions], 0 for a refused position.  When not even one store fits, no position is looked at (needed[p] is set,
+ * status[p] VGSDF_OK), as the single call returns before its deltas pass.
+ * The whole call fails with VGSDF_E_ARG, before anything runs, for a NULL argument, more than VGSDF_GVAR_MAX_POSITIONS
+ * positions or anything vgsdf_font_create_gvar validates; a HIP error or an exhausted host fails it too: nothing is left
+ * allocated, every out[p] is NULL and the context stays sound.  n_positions == 0: VGSDF_OK, nothing is touched.
+ */
+#define VGSDF_GVAR_MAX_POSITIONS 64u
+typedef struct {
+	vgsdf_font_tables_desc tables; /* loca, glyf */
+	const uint8_t *gvar;           /* the whole table as it stands in the file */
+	uint32_t gvar_len;
+	uint32_t n_axes;               /* 1 .. 64, the table's axisCount */
+	const int16_t *coords;         /* [n_positions * n_axes], normalised, behind avar */
+	uint32_t n_positions;          /* 0 .. VGSDF_GVAR_MAX_POSITIONS */
+} vgsdf_fonts_gvar_desc;
+int vgsdf_fonts_create_gvar(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *in, vgsdf_font **out /* [n_positions] */,
+                            int *status /* [n_positions] */);
+int vgsdf_fonts_create_gvar_within(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *in, uint64_t max_store_bytes, vgsdf_font **out, int *status,
+                                   uint64_t *needed /* [n_positions], may be NULL */);
+/* test / inspection (tools/gvar_batch_ab.py): the count, the deltas and the emit pass of the context's last vgsdf_fonts_create_gvar */
+void vgsdf_fonts_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3]);
+/*
  * Resident families: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id lives on the device
  * beside its fonts, and a submission names CODE-POINT RANGES of families instead of glyphs.  The host's share per submission
  * is O(tasks): the block it uploads holds 32 bytes per task that maps a glyph, per family and per font, and no per-glyph byte.

@@ -72,8 +72,10 @@ struct vgsdf_ctx {
 	float glyf_tables_ms[2] = {0.0f, 0.0f};   // count / emit kernels of the last vgsdf_font_create_tables (resident_fonts.cpp)
 	float glyf_batch_ms[2] = {0.0f, 0.0f};    // the same of the last vgsdf_fonts_create_tables: one launch each over all its faces
 	float gvar_ms[3] = {0.0f, 0.0f, 0.0f};    // count / deltas / emit kernels of the last vgsdf_font_create_gvar (resident_fonts.cpp)
-	// vgsdf_font_create_gvar: the deltas pass's scratch for one launch (GvarScratch: 13 bytes per point of at most 2^17 points, or of
-	// one glyph id); grown on demand, belongs to no font
+	float gvar_batch_ms[3] = {0.0f, 0.0f, 0.0f}; // the same of the last vgsdf_fonts_create_gvar: one face at all its positions
+	// vgsdf_font_create_gvar, vgsdf_fonts_create_gvar: the deltas pass's scratch for one launch (GvarScratch: 13 bytes per point of
+	// at most 2^17 points — points x positions in the batched call —, or of one glyph id at one position); grown on demand, belongs
+	// to no font
 	DevBuf gvar_scratch;
 	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
 };

@@ -41,6 +41,16 @@ struct GvarScratch {
 };
 constexpr uint32_t kGvarScratchBytesPerPoint = 4 + 4 + 2 + 2 + 1;
 
+// one position of the batched emit pass (gvar_batch_kernels.hip; vgsdf_fonts_create_gvar), all addresses on the device: the
+// position's sums, its store's cmd_off, and the staging of its context pass (dat_off, kinds, coords); flags: its GVAR_FLAG_WORDS
+struct GvarPositionRef {
+	const float *acc;
+	const uint32_t *cmd_off, *dat_off;
+	uint8_t *kinds;
+	float *coords;
+	uint32_t *flags;
+};
+
 } // namespace vgsdf
 
 extern "C" {
@@ -53,4 +63,14 @@ int vgsdf_gvar_deltas(const vgsdf::GvarRef *face, uint32_t g0, uint32_t g1, cons
 // emit pass: glyph id g's kinds to kinds[cmd_off[g] .. cmd_off[g + 1]), its coordinates to coords[dat_off[g] .. dat_off[g + 1])
 int vgsdf_gvar_emit(const vgsdf::GvarRef *face, const uint32_t *counts, const uint32_t *pt_at, const float *acc, const uint32_t *cmd_off,
                     const uint32_t *dat_off, uint8_t *kinds, float *coords, uint32_t *flags, hipStream_t stream);
+// the same face at many positions (gvar_batch_kernels.hip), one lane per (glyph id, position), position fastest.
+// deltas pass over glyph ids [g0, g1) x positions [p0, p1), p1 > p0: coords_all holds face->n_axes coordinates per position
+// (face->coords is not read), acc + p * acc_stride the sums of position p laid out as above, flags + p * GVAR_FLAG_WORDS its flag
+// words; scratch holds (p1 - p0) stretches of slice = pt_at[g1] - pt_at[g0] points
+int vgsdf_gvar_batch_deltas(const vgsdf::GvarRef *face, uint32_t g0, uint32_t g1, uint32_t p0, uint32_t p1, const int16_t *coords_all,
+                            const uint32_t *counts, const uint32_t *pt_at, float *acc, uint64_t acc_stride, const vgsdf::GvarScratch *scratch,
+                            uint32_t slice, uint32_t *flags, hipStream_t stream);
+// emit pass over every glyph id x positions[0, n_positions), n_positions >= 1 (an array on the device)
+int vgsdf_gvar_batch_emit(const vgsdf::GvarRef *face, const vgsdf::GvarPositionRef *positions, uint32_t n_positions, const uint32_t *counts,
+                          const uint32_t *pt_at, hipStream_t stream);
 }

@@ -16,6 +16,8 @@ constexpr uint32_t kGvarMaxAxes = 64;            // fvar axes of a face (the ins
 constexpr uint32_t kGvarMaxRecords = 0xFFFF;     // component records of ONE composite entry (its points are numbered in 16 bits)
 constexpr uint32_t kGvarMaxGlyphCmds = 1u << 26; // commands of one glyph id (kResidentMaxGlyphSlots of glyf_table_limits.h)
 constexpr uint32_t kGvarSlicePoints = 1u << 17;  // points of one launch of the deltas pass: a slice of glyph ids ends before the
-                                                 // glyph id that would pass it (a slice of one glyph id may: at most 65539)
+                                                 // glyph id that would pass it (a slice of one glyph id may: at most 65539).
+                                                 // vgsdf_fonts_create_gvar: points x positions of one launch, by the same rule
+                                                 // (a glyph id that passes it with all positions goes in runs of positions)
 
 } // namespace vg

@@ -262,6 +262,33 @@ int vg_manager_add_font_instance_normalized(vg_manager *m, const char *name, con
 		return fail(e.what());
 	}
 }
+int vg_manager_add_font_named_instances(vg_manager *m, const uint8_t *data, size_t len, char (*ids)[VG_FONT_ID_MAX], int cap)
+{
+	try {
+		if (!m || (!data && len) || cap < 0 || (cap && !ids))
+			return fail("vg_manager_add_font_named_instances: bad argument");
+		std::string err;
+		std::vector<std::string> made;
+		if (!m->m.add_font_named_instances(std::vector<uint8_t>(data, data + len), made, &err))
+			return fail(err);
+		for (int k = 0; k < cap && (size_t)k < made.size(); k++) {
+			const size_t n = std::min(made[(size_t)k].size(), (size_t)VG_FONT_ID_MAX - 1);
+			std::memcpy(ids[k], made[(size_t)k].data(), n);
+			ids[k][n] = 0;
+		}
+		return (int)made.size();
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+void vg_manager_set_scan_named_instances(vg_manager *m, int on) { m->m.set_scan_named_instances(on != 0); }
+void vg_manager_set_gvar_batched(vg_manager *m, int on) { m->m.set_gvar_batched(on != 0); }
+int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_gvar_batch_stats{t.gvar_batch_calls, t.gvar_batch_faces};
+	return 0;
+}
 namespace {
 // file `file_index` of a font id (nullptr and g_err: none)
 const vg::Face *face_of(const vg_manager *m, const char *font_id, int file_index, const char *me)

@@ -64,10 +64,16 @@ std::string name_to_id(const std::string &name)
 
 std::unique_ptr<FontFileEntry> FontFileEntry::create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords)
 {
+	return create(std::make_shared<const std::vector<uint8_t>>(std::move(data)), err, coords, nullptr);
+}
+
+std::unique_ptr<FontFileEntry> FontFileEntry::create(std::shared_ptr<const std::vector<uint8_t>> data, std::string *err,
+                                                     const std::vector<int16_t> *coords, const std::string *ps_name)
+{
 	std::unique_ptr<FontFileEntry> e(new FontFileEntry());
 	e->data_ = std::move(data);
 	std::string why = "font parse failed";
-	auto face = coords ? Face::parse_at(e->data_.data(), e->data_.size(), *coords, &why) : Face::parse(e->data_.data(), e->data_.size());
+	auto face = coords ? Face::parse_at(e->data_->data(), e->data_->size(), *coords, &why) : Face::parse(e->data_->data(), e->data_->size());
 	if (!face) {
 		if (err)
 			*err = why;
@@ -96,7 +102,7 @@ std::unique_ptr<FontFileEntry> FontFileEntry::create(std::vector<uint8_t> data, 
 		for (auto &kv : e->face_.names())
 			names[kv.first] = std::move(kv.second);
 		e->metadata_.name = names.count(1) ? names[1] : std::string(); // name_id::FAMILY
-		const ParsedFontName pn = parse_font_name(e->metadata_.name, names.count(6) ? names[6] : std::string()); // POST_SCRIPT_NAME
+		const ParsedFontName pn = parse_font_name(e->metadata_.name, ps_name ? *ps_name : names.count(6) ? names[6] : std::string()); // POST_SCRIPT_NAME
 		e->metadata_.family = pn.family;
 		e->metadata_.style = pn.style;
 		e->metadata_.weight = pn.weight;
@@ -260,11 +266,61 @@ bool FontManager::add_font_instance(const std::string &name, std::vector<uint8_t
 	return add_font_instance_normalized(name, std::move(data), coords, err);
 }
 
+bool FontManager::add_font_named_instances(std::vector<uint8_t> data, std::vector<std::string> &ids, std::string *err)
+{
+	auto refuse = [&](const std::string &why) {
+		if (err)
+			*err = why;
+		return false;
+	};
+	std::vector<VariationAxis> axes;
+	std::vector<NamedInstance> instances;
+	if (!read_variation_axes(data.data(), data.size(), axes, &instances))
+		return refuse("named instances need a readable fvar table, and this file has none");
+	if (instances.empty())
+		return refuse("the file's fvar has no instance record");
+	std::string family;
+	std::vector<std::string> ps_names;
+	if (!named_instance_ps_names(data.data(), data.size(), instances, family, ps_names))
+		return refuse("font parse failed");
+	if (axes.size() > 64)
+		axes.resize(64); // (the face counts no more)
+	const auto bytes = std::make_shared<const std::vector<uint8_t>>(std::move(data));
+	std::vector<std::unique_ptr<FontFileEntry>> entries;
+	for (size_t k = 0; k < instances.size(); k++) {
+		std::vector<int16_t> coords(axes.size(), 0);
+		for (size_t i = 0; i < axes.size(); i++)
+			coords[i] = normalize_axis_value(axes[i], instances[k].coords[i]);
+		apply_avar(bytes->data(), bytes->size(), coords);
+		auto e = FontFileEntry::create(bytes, err, &coords, &ps_names[k]);
+		if (!e)
+			return false;
+		entries.push_back(std::move(e));
+	}
+	invalidate_shards();
+	ids.clear();
+	for (auto &e : entries) {
+		if (e->face().placed_by_gvar())
+			gvar_groups_[e->face().gvar_tables().gvar].push_back(&e->face());
+		ids.push_back(name_to_id(e->metadata().generate_name()));
+		fonts_[ids.back()].add_file(std::move(e));
+	}
+	return true;
+}
+
 bool FontManager::add_path(const std::string &path, std::string *err)
 {
 	std::vector<uint8_t> data;
 	if (!read_file(path, data, err))
 		return false;
+	if (scan_named_instances_) {
+		std::vector<VariationAxis> axes;
+		std::vector<NamedInstance> instances;
+		if (read_variation_axes(data.data(), data.size(), axes, &instances) && !instances.empty()) {
+			std::vector<std::string> ids;
+			return add_font_named_instances(std::move(data), ids, err);
+		}
+	}
 	auto e = FontFileEntry::create(std::move(data), err);
 	if (!e)
 		return false;

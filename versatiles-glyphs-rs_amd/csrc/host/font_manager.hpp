@@ -58,12 +58,16 @@ class FontFileEntry {
 public:
 	// coords: the face at that position (Face::parse_at) instead of as parsed
 	static std::unique_ptr<FontFileEntry> create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords = nullptr);
+	// the same over bytes that several entries share (the named instances of one file); ps_name: the PostScript name the metadata
+	// is parsed from instead of the file's name id 6
+	static std::unique_ptr<FontFileEntry> create(std::shared_ptr<const std::vector<uint8_t>> data, std::string *err,
+	                                             const std::vector<int16_t> *coords, const std::string *ps_name);
 	const Face &face() const { return face_; }
 	const std::vector<uint32_t> &codepoints() const { return codepoints_; } // metadata.rs:105-119
 	const FontMetadata &metadata() const { return metadata_; }                // metadata.rs:89-103
 
 private:
-	std::vector<uint8_t> data_;
+	std::shared_ptr<const std::vector<uint8_t>> data_;
 	Face face_;
 	std::vector<uint32_t> codepoints_;
 	FontMetadata metadata_;
@@ -173,6 +177,8 @@ struct RenderTimings {
 	// command stores the device built from a placed glyf face's loca, glyf and gvar (set_gvar_on_device; counted among
 	// command_fonts_uploaded too), their bytes, and faces it refused, whose stores were built from the host reader's table instead
 	uint64_t gvar_fonts_built = 0, gvar_font_bytes = 0, gvar_fallbacks = 0;
+	// ... and, with set_gvar_batched, the calls that built them (one per group of faces over the same bytes) and the faces sent
+	uint64_t gvar_batch_calls = 0, gvar_batch_faces = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -205,10 +211,11 @@ struct RenderTimings {
 		glyf_tables_built += counts.glyf_tables_built, glyf_table_bytes += counts.glyf_table_bytes, glyf_table_fallbacks += counts.glyf_table_fallbacks;
 		glyf_table_batch_calls += counts.glyf_table_batch_calls, glyf_table_batch_faces += counts.glyf_table_batch_faces;
 		gvar_fonts_built += counts.gvar_fonts_built, gvar_font_bytes += counts.gvar_font_bytes, gvar_fallbacks += counts.gvar_fallbacks;
+		gvar_batch_calls += counts.gvar_batch_calls, gvar_batch_faces += counts.gvar_batch_faces;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 39 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 41 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -227,6 +234,14 @@ public:
 	bool add_font_instance_normalized(const std::string &name, std::vector<uint8_t> data, const std::vector<int16_t> &coords, std::string *err);
 	bool add_font_instance(const std::string &name, std::vector<uint8_t> data, const std::vector<std::array<char, 4>> &tags,
 	                       const std::vector<float> &values, std::string *err);
+	// Every named instance of the file's fvar as a font id of its own, by add_font_instance's rules (normalize_axis_value, apply_avar,
+	// what Face::parse_at refuses); all instances share ONE copy of the bytes.  The id of an instance: parse_font_name(family,
+	// ps_name) -> generate_name -> name_to_id, with ps_name by named_instance_ps_names (ttf_face.hpp); two instances that arrive at
+	// one id merge like any files of one id.  ids: the font id of every record, in the table's order.  false, nothing added: no
+	// readable fvar, no instance record, or a refusal of add_font_instance's (a glyf face without a readable gvar ...).
+	bool add_font_named_instances(std::vector<uint8_t> data, std::vector<std::string> &ids, std::string *err);
+	// add_path and scan treat a variable file that has instance records as add_font_named_instances does (default off: as any file)
+	void set_scan_named_instances(bool on) { scan_named_instances_ = on; }
 	// manager.rs:39-53: the file's own name table decides the font id (family + width + weight + style
 	// through parse_font_name / generate_name / name_to_id); files with the same id merge, in call order
 	bool add_path(const std::string &path, std::string *err);
@@ -335,6 +350,9 @@ public:
 	// a placed glyf face's command store is built on the device from loca, glyf and gvar (Renderer::gvar_font); a face the device
 	// refuses gets its store from the host reader's table, as with the switch off
 	void set_gvar_on_device(bool on) { gvar_on_device_ = on; }
+	// with set_gvar_on_device: the stores of ALL placed glyf faces over the same bytes (add_font_named_instances) that the lane's
+	// device has yet to build, in one call when the first of them is asked for (Renderer::gvar_fonts)
+	void set_gvar_batched(bool on) { gvar_batched_ = on; }
 	// with set_glyf_tables_on_device: the glyf fonts of a font id's files built in one call (Renderer::fonts_from_tables)
 	void set_glyf_tables_batched(bool on) { glyf_tables_batched_ = on; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
@@ -601,6 +619,13 @@ private:
 	bool glyf_tables_on_device_ = false;
 	bool gvar_on_device_ = false;
 	bool glyf_tables_batched_ = false;
+	bool gvar_batched_ = false, scan_named_instances_ = false;
+	// the placed glyf faces that share their bytes, by the address of their gvar table (the faces of add_font_named_instances; a
+	// child manager reads its parent's); a group of one makes no batched call
+	std::map<const uint8_t *, std::vector<const Face *>> gvar_groups_;
+	// gvar_batched_: the command stores of `face`'s group that the device has yet to build, in one call; the gvar_font of each face
+	// behind it finds its store (or goes the way of a face that was refused or did not fit); counts into `counts`
+	void gvar_stores_batched(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
 	// glyf_tables_batched_: the glyf fonts of `font`'s files that the device has yet to build, in one call; the glyf_store of each
 	// file behind it finds its font (or goes the way of a face that was refused or did not fit); counts into `counts`
 	void glyf_stores_batched(const Renderer &renderer, int lane, const FontWrapper &font, RenderTimings &counts) const;

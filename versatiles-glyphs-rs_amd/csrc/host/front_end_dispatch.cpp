@@ -340,6 +340,29 @@ void FontManager::glyf_stores_batched(const Renderer &renderer, int lane, const 
 	}
 }
 
+void FontManager::gvar_stores_batched(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const
+{
+	if (!gvar_batched_)
+		return;
+	const auto &groups = parent_ ? parent_->gvar_groups_ : gvar_groups_;
+	const auto group = groups.find(face.gvar_tables().gvar);
+	if (group == groups.end() || group->second.size() < 2)
+		return; // (a face with bytes of its own: its own call)
+	std::vector<Renderer::GvarJob> faces;
+	for (const Face *f : group->second)
+		faces.push_back(Renderer::GvarJob{f->command_serial(), f->gvar_tables()});
+	std::vector<Renderer::TablesOutcome> outcomes;
+	renderer.gvar_fonts(lane, faces, outcomes, &counts.gvar_batch_calls, &counts.gvar_batch_faces);
+	for (const Renderer::TablesOutcome &o : outcomes) { // (as command_store counts what gvar_font says)
+		if (o.refused)
+			counts.gvar_fallbacks++;
+		if (o.built) {
+			count_upload(o.uploaded, counts.gvar_fonts_built, counts.gvar_font_bytes);
+			count_upload(o.uploaded, counts.command_fonts_uploaded, counts.command_font_bytes);
+		}
+	}
+}
+
 const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const
 {
 	uint64_t uploaded = 0;
@@ -359,6 +382,7 @@ const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane,
 			count_upload(uploaded, counts.charstring_fonts_decoded, counts.charstring_font_bytes);
 	}
 	if (!f && gvar_on_device_ && face.placed_by_gvar()) {
+		gvar_stores_batched(renderer, lane, face, counts);
 		bool refused = false, over_budget = false;
 		f = renderer.gvar_font(lane, face.command_serial(), face.gvar_tables(), &uploaded, &refused, &over_budget);
 		if (refused)

@@ -409,6 +409,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->glyf_tables_on_device_ = glyf_tables_on_device_;
 		c->gvar_on_device_ = gvar_on_device_;
 		c->glyf_tables_batched_ = glyf_tables_batched_;
+		c->gvar_batched_ = gvar_batched_;
 		c->resident_families_ = resident_families_;
 		c->batch_blocks_ = batch_blocks_;
 		c->batch_blocks_set_ = batch_blocks_set_;

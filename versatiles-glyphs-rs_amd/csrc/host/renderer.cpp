@@ -732,6 +732,83 @@ const vgsdf_font *Renderer::gvar_font(int lane, uint64_t serial, const GvarTable
 	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
+void Renderer::gvar_fonts(int lane, const std::vector<GvarJob> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls, uint64_t *n_sent) const
+{
+	outcomes.assign(faces.size(), TablesOutcome{});
+	if (mode_ != Mode::Hip)
+		return;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	std::vector<size_t> sent;
+	std::vector<int16_t> coords;
+	const GvarTables *first = nullptr;
+	auto flush = [&] {
+		if (sent.empty())
+			return;
+		const GvarTables &t = *first;
+		vgsdf_fonts_gvar_desc d{};
+		d.tables.num_glyphs = t.tables.num_glyphs, d.tables.loca_entries = t.tables.loca_entries, d.tables.loca_long = t.tables.loca_long;
+		d.tables.n_loca_bytes = t.tables.n_loca_bytes, d.tables.n_glyf_bytes = t.tables.n_glyf_bytes;
+		d.tables.loca = t.tables.loca, d.tables.glyf = t.tables.glyf;
+		d.gvar = t.gvar, d.gvar_len = t.gvar_len, d.n_axes = t.n_axes, d.coords = coords.data(), d.n_positions = (uint32_t)sent.size();
+		std::vector<vgsdf_font *> made(sent.size(), nullptr);
+		std::vector<int> status(sent.size(), 0);
+		std::vector<uint64_t> needed(sent.size(), 0);
+		vgsdf_ctx *c = lane_ctx(lane & 1);
+		int rc;
+		{
+			std::lock_guard<std::mutex> lock(mu_);
+			rc = vgsdf_fonts_create_gvar_within(c, &d, rf.room(device_), made.data(), status.data(), needed.data());
+		}
+		if (rc != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_fonts_create_gvar: ") + vgsdf_last_error(c));
+		*calls += 1, *n_sent += sent.size();
+		for (size_t i = 0; i < sent.size(); i++) {
+			TablesOutcome &o = outcomes[sent[i]];
+			const auto key = std::make_pair(device_, faces[sent[i]].serial);
+			if (status[i] != VGSDF_OK) { // (refused at this position, or whatever the position: the host's way, once)
+				rf.refused_gvar.insert(key);
+				o.refused = true;
+				continue;
+			}
+			if (made[i] && needed[i] > rf.room(device_)) { // (the registry counts allocations, a quarter more than the stores)
+				std::lock_guard<std::mutex> lock(mu_);
+				(void)vgsdf_font_free(c, made[i]);
+				made[i] = nullptr;
+			}
+			if (!made[i]) { // over the budget as it stands
+				rf.unfit_gvar[key] = needed[i];
+				o.over_budget = true;
+				continue;
+			}
+			rf.unfit_gvar.erase(key);
+			o.built = true;
+			(void)rf.keep(rf.fonts, key, made[i], vgsdf_font_device_bytes(made[i]), &o.uploaded);
+		}
+		sent.clear(), coords.clear();
+	};
+	std::set<uint64_t> seen;
+	for (size_t i = 0; i < faces.size(); i++) {
+		const GvarTables &t = faces[i].tables;
+		const auto key = std::make_pair(device_, faces[i].serial);
+		if (!t.ok || rf.find(rf.fonts, key) || rf.refused_gvar.count(key))
+			continue;
+		if (auto it = rf.unfit_gvar.find(key); it != rf.unfit_gvar.end() && it->second > rf.room(device_))
+			continue; // (gvar_font says over_budget when it is asked)
+		if (!seen.insert(faces[i].serial).second)
+			continue; // (a face named twice: one store)
+		if (!first)
+			first = &t;
+		if (t.gvar != first->gvar || t.n_axes != first->n_axes || t.tables.glyf != first->tables.glyf || t.tables.loca != first->tables.loca)
+			continue; // (not over the first face's tables: its own gvar_font builds it)
+		if (sent.size() == VGSDF_GVAR_MAX_POSITIONS)
+			flush();
+		sent.push_back(i);
+		coords.insert(coords.end(), t.coords, t.coords + t.n_axes);
+	}
+	flush();
+}
+
 const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std::vector<const vgsdf_font *> &fonts, int kind,
                                      uint64_t *uploaded_bytes) const
 {

@@ -502,6 +502,18 @@ public:
 	// face's command serial: command_font() of the same face finds it.  refused / over_budget: as charstring_font says them; a
 	// refusal is remembered per (device, serial), so the face goes the host's way once and is not tried again
 	const vgsdf_font *gvar_font(int lane, uint64_t serial, const GvarTables &tables, uint64_t *uploaded_bytes, bool *refused, bool *over_budget) const;
+	// gvar_font for ALL placed faces over ONE file's tables (the same loca, glyf and gvar; each its own coordinates and command
+	// serial) in as few calls as their number allows (vgsdf_fonts_create_gvar_within: the tables uploaded once, one count launch,
+	// the deltas and emit passes over all positions).  Shaped like fonts_from_tables: under the registry's lock for the whole of it;
+	// a face is sent when its tables are ok, the registry has no font under (device, serial) and it is not remembered as refused or
+	// as past the budget's room; outcomes[i], the registry, the refused set and the sizes that did not fit are left as gvar_font
+	// would leave them, so that a gvar_font of any of the faces behind this call finds its store, or goes the way it went.
+	// *calls / *n_sent: the calls made, the faces sent
+	struct GvarJob {
+		uint64_t serial = 0;
+		GvarTables tables;
+	};
+	void gvar_fonts(int lane, const std::vector<GvarJob> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls, uint64_t *n_sent) const;
 	// Resident families (vgsdf_family_create): the device copy of a font id's table code point -> (file, glyph id, advance,
 	// scale, shift_x) over the device fonts of its files, one per (device, table serial, kind of store) in the registry of the
 	// fonts — same budget, freed with the renderer, in front of the fonts.  A table rebuilt after a file was added has a new

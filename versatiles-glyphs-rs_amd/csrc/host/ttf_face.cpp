@@ -108,9 +108,42 @@ bool read_variation_axes(const uint8_t *data, size_t len, std::vector<VariationA
 				ni.name_id = fvar.u16(at);
 				for (uint32_t i = 0; i < n; i++)
 					ni.coords.push_back(fixed_to_float(fvar.u32(at + 4 + (size_t)i * 4)));
+				if (inst_size >= 6 + (size_t)n * 4)
+					ni.ps_name_id = fvar.u16(at + 4 + (size_t)n * 4);
 				instances->push_back(std::move(ni));
 			}
 		}
+	}
+	return true;
+}
+
+bool named_instance_ps_names(const uint8_t *data, size_t len, const std::vector<NamedInstance> &instances, std::string &family,
+                             std::vector<std::string> &ps_names)
+{
+	const auto face = Face::parse(data, len);
+	if (!face)
+		return false;
+	std::map<uint16_t, std::string> names;
+	for (auto &kv : face->names())
+		names[kv.first] = std::move(kv.second);
+	family = names.count(1) ? names[1] : std::string();
+	std::string prefix = names.count(25) ? names[25] : std::string();
+	if (prefix.empty())
+		for (const char c : family)
+			if ((c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9'))
+				prefix.push_back(c);
+	ps_names.clear();
+	for (const NamedInstance &ni : instances) {
+		if (ni.ps_name_id != 0xFFFF && names.count(ni.ps_name_id)) {
+			ps_names.push_back(names[ni.ps_name_id]);
+			continue;
+		}
+		std::string ps = prefix + "-";
+		if (names.count(ni.name_id))
+			for (const char c : names[ni.name_id])
+				if (c != ' ')
+					ps.push_back(c);
+		ps_names.push_back(std::move(ps));
 	}
 	return true;
 }

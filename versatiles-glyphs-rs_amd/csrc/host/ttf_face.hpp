@@ -125,10 +125,18 @@ struct VariationAxis {
 struct NamedInstance {
 	uint16_t name_id;
 	std::vector<float> coords; // one per axis, user space
+	uint16_t ps_name_id = 0xFFFF; // postScriptNameID of a record that has room for one (instanceSize >= 4 + 4 axes + 2); 0xFFFF: none
 };
 // false: no readable `fvar` (version 1.0, at least one axis, the axis records inside the table).  Instance records that
 // leave the table are left out.
 bool read_variation_axes(const uint8_t *data, size_t len, std::vector<VariationAxis> &axes, std::vector<NamedInstance> *instances = nullptr);
+// The PostScript name a named instance is known by, from the file's `name` table (its records as Face::names() reads them, a
+// later record of an id replacing an earlier one): the string of the record's postScriptNameID when that is not 0xFFFF and `name`
+// has it; otherwise the variations PostScript name prefix (name id 25; absent or empty: the family name, id 1, without everything
+// but ASCII letters and digits), "-", and the string of the record's subfamilyNameID (absent: empty) without its spaces.
+// family: the file's name id 1 (absent: empty).  false: the file does not parse as a face.
+bool named_instance_ps_names(const uint8_t *data, size_t len, const std::vector<NamedInstance> &instances, std::string &family,
+                             std::vector<std::string> &ps_names);
 // A user-space value of an axis as a normalised coordinate (F2Dot14), in f32: clamped to [min, max]; 0 at the default, else
 // (v - def) / (def - min) below it and (v - def) / (max - def) above; clamped to [-1, 1], times 16384, truncated toward zero.
 // (The crate's rule as read; whether it truncates or rounds is unpinned.)

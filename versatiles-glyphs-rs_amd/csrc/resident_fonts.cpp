@@ -27,6 +27,14 @@ void name_glyf_store(vgsdf_font &f, const vgsdf::GlyfStoreLayout &at)
 	f.ref.leaves = d + at.leaves, f.ref.bytes = d + at.bytes, f.ref.leaf_off = d + at.leaf_off;
 }
 
+// a command font's three arrays, once its store is allocated
+void name_command_store(vgsdf_font &f, const vgsdf::CommandStoreLayout &at, uint32_t n_cmds)
+{
+	uint8_t *d = (uint8_t *)f.store.p;
+	f.n_cmds = n_cmds;
+	f.cref.cmds = (uintptr_t)d, f.cref.cmd_off = (uintptr_t)(d + at.cmd_off), f.cref.open = (uintptr_t)(d + at.open);
+}
+
 // what the packed form's context pass reads beside a command store, for the duration of the call that builds it:
 // scale f64[n] (1: the bytes then say "ring open" and nothing else) | dat_off u32[n + 1] | coords | kinds | pad to 16 | its error word
 struct ContextStagingLayout {
@@ -68,8 +76,7 @@ uint32_t finish_command_store(Calls &q, vgsdf_font &f, const vgsdf::CommandStore
 	if (more_flags)
 		q.read_back(more_flags, d_more_flags, 4);
 	q.sync();
-	f.n_cmds = n_cmds;
-	f.cref.cmds = (uintptr_t)d, f.cref.cmd_off = (uintptr_t)(d + at.cmd_off), f.cref.open = (uintptr_t)(d + at.open);
+	name_command_store(f, at, n_cmds);
 	return flag;
 }
 } // namespace
@@ -642,6 +649,41 @@ namespace {
 uint32_t be16_at(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
 uint32_t be32_at(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
+// what both gvar constructors validate of the tables and the gvar header before anything runs; fills the header's fields of `face`
+bool gvar_face_described(vgsdf_ctx *ctx, const char *entry, const vgsdf_font_tables_desc &in, const uint8_t *g, uint64_t gvar_len, uint32_t n_axes,
+                         vgsdf::GvarRef &face)
+{
+	const uint32_t n = in.num_glyphs;
+	if (n > 0xFFFFu || in.loca_long > 1u || (uint64_t)in.loca_entries * (in.loca_long ? 4u : 2u) > in.n_loca_bytes || in.loca_entries > n + 1) {
+		ctx->err = std::string(entry) + ": more than 65535 glyphs, loca_long not 0 or 1, or more loca entries than the loca bytes hold or than num_glyphs + 1";
+		return false;
+	}
+	// GvarTable::parse: majorVersion, minorVersion, axisCount, sharedTupleCount, sharedTuplesOffset, glyphCount, flags,
+	// glyphVariationDataArrayOffset; the shared tuples and the offset array inside the table
+	bool readable = n_axes >= 1 && n_axes <= vg::kGvarMaxAxes && gvar_len >= 20 && be32_at(g) == 0x00010000u && be16_at(g + 4) == n_axes;
+	if (readable) {
+		face.shared_count = be16_at(g + 6), face.shared_at = be32_at(g + 8), face.glyph_count = be16_at(g + 12);
+		face.long_offsets = be16_at(g + 14) & 1u, face.data_at = be32_at(g + 16);
+		const uint64_t tuples = (uint64_t)face.shared_count * n_axes * 2, offsets = ((uint64_t)face.glyph_count + 1) * (face.long_offsets ? 4u : 2u);
+		readable = face.shared_at <= gvar_len && tuples <= gvar_len - face.shared_at && offsets <= gvar_len - 20;
+	}
+	if (!readable) {
+		ctx->err = std::string(entry) + ": axes not 1 .. 64, a gvar that is not version 1.0 or has another axisCount, or a header, shared tuples "
+		                                "or offset array outside gvar_len";
+		return false;
+	}
+	return true;
+}
+
+struct EventGuard { // an event beside PassEvents' three, destroyed with the call
+	hipEvent_t &e;
+	~EventGuard()
+	{
+		if (e)
+			(void)hipEventDestroy(e);
+	}
+};
+
 // vgsdf_font_create_gvar_within: count pass, read-back and layout, deltas pass in slices over the context's scratch, emit pass,
 // context pass (gvar_kernels.h)
 int create_gvar(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *desc, uint64_t max_store_bytes, vgsdf_font **out, uint64_t *store_bytes)
@@ -658,27 +700,10 @@ int create_gvar(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *desc, uint64_t max_s
 	ctx->gvar_ms[0] = ctx->gvar_ms[1] = ctx->gvar_ms[2] = 0.0f;
 	const vgsdf_font_tables_desc &in = desc->tables;
 	const uint32_t n = in.num_glyphs;
-	if (n > 0xFFFFu || in.loca_long > 1u || (uint64_t)in.loca_entries * (in.loca_long ? 4u : 2u) > in.n_loca_bytes || in.loca_entries > n + 1) {
-		ctx->err = "vgsdf_font_create_gvar: more than 65535 glyphs, loca_long not 0 or 1, or more loca entries than the loca bytes hold or than num_glyphs + 1";
-		return VGSDF_E_ARG;
-	}
-	// GvarTable::parse: majorVersion, minorVersion, axisCount, sharedTupleCount, sharedTuplesOffset, glyphCount, flags,
-	// glyphVariationDataArrayOffset; the shared tuples and the offset array inside the table
-	const uint8_t *g = desc->gvar;
 	const uint64_t gvar_len = desc->gvar_len;
 	vgsdf::GvarRef face{};
-	bool readable = desc->n_axes >= 1 && desc->n_axes <= vg::kGvarMaxAxes && gvar_len >= 20 && be32_at(g) == 0x00010000u && be16_at(g + 4) == desc->n_axes;
-	if (readable) {
-		face.shared_count = be16_at(g + 6), face.shared_at = be32_at(g + 8), face.glyph_count = be16_at(g + 12);
-		face.long_offsets = be16_at(g + 14) & 1u, face.data_at = be32_at(g + 16);
-		const uint64_t tuples = (uint64_t)face.shared_count * desc->n_axes * 2, offsets = ((uint64_t)face.glyph_count + 1) * (face.long_offsets ? 4u : 2u);
-		readable = face.shared_at <= gvar_len && tuples <= gvar_len - face.shared_at && offsets <= gvar_len - 20;
-	}
-	if (!readable) {
-		ctx->err = "vgsdf_font_create_gvar: axes not 1 .. 64, a gvar that is not version 1.0 or has another axisCount, or a header, shared tuples "
-		           "or offset array outside gvar_len";
+	if (!gvar_face_described(ctx, name, in, desc->gvar, desc->gvar_len, desc->n_axes, face))
 		return VGSDF_E_ARG;
-	}
 	std::unique_ptr<vgsdf_font> f(new (std::nothrow) vgsdf_font());
 	if (!f) {
 		ctx->err = "vgsdf_font_create_gvar: out of host memory";
@@ -688,14 +713,7 @@ int create_gvar(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *desc, uint64_t max_s
 	hipStream_t st = ctx->stream;
 	PassEvents ev;
 	hipEvent_t ev_deltas = nullptr; // (the deltas pass ends here; PassEvents has the other three)
-	struct EventGuard {
-		hipEvent_t &e;
-		~EventGuard()
-		{
-			if (e)
-				(void)hipEventDestroy(e);
-		}
-	} guard{ev_deltas};
+	EventGuard guard{ev_deltas};
 	if (hipError_t err = ev.create(); err != hipSuccess)
 		return font_hip_error(ctx, name, "hipEventCreate", err);
 	if (hipError_t err = hipEventCreate(&ev_deltas); err != hipSuccess)
@@ -854,6 +872,281 @@ void vgsdf_font_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3])
 	if (ms)
 		for (int i = 0; i < 3; i++)
 			ms[i] = ctx ? ctx->gvar_ms[i] : 0.0f;
+}
+
+} // extern "C"
+
+namespace {
+// vgsdf_fonts_create_gvar_within: create_gvar for one face at all its positions.  The tables go up once; the count pass, its
+// read-back and the layout are the single call's and serve every position; the deltas pass and the emit pass run over (glyph id,
+// position) pairs (gvar_batch_kernels.hip), the context pass once per store; two more read-backs (the positions' flag words
+// behind the deltas pass and behind the emit pass) and three synchronisations for the whole call
+int create_gvar_batch(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *desc, uint64_t max_store_bytes, vgsdf_font **out, int *status, uint64_t *needed)
+{
+	const char *name = "vgsdf_fonts_create_gvar";
+	if (!desc) {
+		ctx->err = "vgsdf_fonts_create_gvar: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	const uint32_t n_pos = desc->n_positions;
+	if (n_pos == 0)
+		return VGSDF_OK;
+	if (!out || !status || (desc->tables.n_loca_bytes && !desc->tables.loca) || (desc->tables.n_glyf_bytes && !desc->tables.glyf) || !desc->gvar ||
+	    !desc->coords) {
+		ctx->err = "vgsdf_fonts_create_gvar: NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if (n_pos > VGSDF_GVAR_MAX_POSITIONS) {
+		ctx->err = "vgsdf_fonts_create_gvar: more than 64 positions in one call";
+		return VGSDF_E_ARG;
+	}
+	for (uint32_t p = 0; p < n_pos; p++) {
+		out[p] = nullptr, status[p] = VGSDF_OK;
+		if (needed)
+			needed[p] = 0;
+	}
+	ctx->gvar_batch_ms[0] = ctx->gvar_batch_ms[1] = ctx->gvar_batch_ms[2] = 0.0f;
+	const vgsdf_font_tables_desc &in = desc->tables;
+	const uint32_t n = in.num_glyphs, n_axes = desc->n_axes;
+	const uint64_t gvar_len = desc->gvar_len;
+	vgsdf::GvarRef face{};
+	if (!gvar_face_described(ctx, name, in, desc->gvar, gvar_len, n_axes, face))
+		return VGSDF_E_ARG;
+	auto refuse_all = [&](const char *why) { // a refusal that no position can change
+		ctx->err = std::string(name) + ": " + why;
+		for (uint32_t p = 0; p < n_pos; p++)
+			status[p] = VGSDF_E_GLYF;
+		return VGSDF_OK;
+	};
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	PassEvents ev;
+	hipEvent_t ev_deltas = nullptr;
+	EventGuard guard{ev_deltas};
+	if (hipError_t err = ev.create(); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipEventCreate", err);
+	if (hipError_t err = hipEventCreate(&ev_deltas); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipEventCreate", err);
+	// the description on the device, for the duration of this call:
+	// loca | glyf | gvar | coords (n_axes per position) | counts (4 per glyph id) | flags (8 per position) | pt_at | position records
+	const size_t a_glyf = align_up(in.n_loca_bytes, 16), a_gvar = align_up(a_glyf + in.n_glyf_bytes, 16), a_coords = align_up(a_gvar + (size_t)gvar_len, 16),
+	             a_counts = align_up(a_coords + 2 * (size_t)n_axes * n_pos, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kGvarCounts * n,
+	             a_at = a_flags + 4 * (size_t)vgsdf::GVAR_FLAG_WORDS * n_pos, a_rec = align_up(a_at + 4 * ((size_t)n + 1), 16),
+	             a_total = a_rec + sizeof(vgsdf::GvarPositionRef) * (size_t)n_pos;
+	ScratchBuf dev, sums, tmp;
+	if (hipError_t e = dev.ensure(a_total + 16); e != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", e);
+	uint8_t *a = (uint8_t *)dev.p;
+	Calls q(st);
+	q.copy(a, in.loca, in.n_loca_bytes);
+	q.copy(a + a_glyf, in.glyf, in.n_glyf_bytes);
+	q.copy(a + a_gvar, desc->gvar, (size_t)gvar_len);
+	q.copy(a + a_coords, desc->coords, 2 * (size_t)n_axes * n_pos);
+	q.zero(a + a_flags, 4 * (size_t)vgsdf::GVAR_FLAG_WORDS * n_pos);
+	const int16_t *d_coords = (const int16_t *)(a + a_coords);
+	face.loca = a, face.glyf = a + a_glyf, face.gvar = a + a_gvar, face.coords = d_coords; // (the batched kernels take each lane's own)
+	face.glyf_len = in.n_glyf_bytes, face.loca_entries = in.loca_entries, face.loca_long = in.loca_long, face.n_glyph_ids = n;
+	face.gvar_len = (uint32_t)gvar_len, face.n_axes = n_axes;
+	uint32_t *d_counts = (uint32_t *)(a + a_counts), *d_flags = (uint32_t *)(a + a_flags), *d_at = (uint32_t *)(a + a_at);
+	vgsdf::GvarPositionRef *d_rec = (vgsdf::GvarPositionRef *)(a + a_rec);
+	// the count pass looks at no coordinate: one launch for all positions; its two flag words land among those of position 0
+	q.record(ev.at[0]);
+	if (n)
+		q.launch([&] { return vgsdf_gvar_count(&face, d_counts, d_flags, st); });
+	q.record(ev.at[1]);
+	std::vector<uint32_t> got((size_t)vgsdf::kGvarCounts * n + vgsdf::GVAR_FLAG_WORDS);
+	q.read_back(got.data(), d_counts, 4 * got.size());
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, name, "count pass", q.e);
+	ev.elapsed(ctx->gvar_batch_ms, 0);
+	const uint32_t *fl = got.data() + (size_t)vgsdf::kGvarCounts * n;
+	if (fl[vgsdf::GVAR_FLAG_RECORDS])
+		return refuse_all("a glyph past VGSDF_GLYF_MAX_COMPONENTS, or a composite of more than 65535 component records");
+	if (fl[vgsdf::GVAR_FLAG_CMDS])
+		return refuse_all("a glyph of more than 2^26 commands");
+	// the running sums, the same for every position: the points of the deltas pass, the stores' layout
+	std::vector<uint32_t> pt_at((size_t)n + 1), cmd_off((size_t)n + 1), dat_off((size_t)n + 1), slots(n, 0);
+	uint64_t points = 0, cmds = 0, floats = 0;
+	for (uint32_t gid = 0; gid < n; gid++) {
+		const uint32_t *c = got.data() + (size_t)vgsdf::kGvarCounts * gid;
+		pt_at[gid] = (uint32_t)points, cmd_off[gid] = (uint32_t)cmds, dat_off[gid] = (uint32_t)floats;
+		slots[gid] = c[1];
+		points += c[0], cmds += c[1], floats += c[2];
+		if (vgsdf::CommandStoreLayout(n, cmds).total > 0xFFFFFFFCull || 4ull * floats > 0xFFFFFFFCull)
+			return refuse_all("a store (29 bytes per command, 4 per glyph id) or coordinates past what 32-bit offsets address");
+	}
+	const uint32_t n_cmds = (uint32_t)cmds, n_floats = (uint32_t)floats;
+	pt_at[n] = (uint32_t)points, cmd_off[n] = n_cmds, dat_off[n] = n_floats;
+	const vgsdf::CommandStoreLayout at(n, n_cmds);
+	if (needed)
+		for (uint32_t p = 0; p < n_pos; p++)
+			needed[p] = at.total;
+	if (at.total > max_store_bytes)
+		return VGSDF_OK; // (not one store fits: nothing allocated, no position looked at, as the single call)
+	// the deltas pass: launches of glyph ids x positions whose points x positions stay within the single call's slice; a glyph id
+	// that passes it with all positions goes alone, in runs of positions (at least one)
+	struct Launch {
+		uint32_t g0, g1, p0, p1;
+	};
+	std::vector<Launch> launches;
+	size_t most = 0;
+	for (uint32_t g0 = 0; g0 < n;) {
+		uint32_t g1 = g0 + 1;
+		const uint64_t own = pt_at[g1] - pt_at[g0];
+		uint32_t step = n_pos;
+		if (own * n_pos > vg::kGvarSlicePoints)
+			step = (uint32_t)std::max<uint64_t>(1, vg::kGvarSlicePoints / own);
+		else
+			while (g1 < n && (uint64_t)(pt_at[g1 + 1] - pt_at[g0]) * n_pos <= vg::kGvarSlicePoints)
+				g1++;
+		const size_t slice = pt_at[g1] - pt_at[g0];
+		for (uint32_t p0 = 0; slice && p0 < n_pos; p0 += step) {
+			const uint32_t p1 = std::min(n_pos, p0 + step);
+			launches.push_back(Launch{g0, g1, p0, p1});
+			most = std::max(most, slice * (p1 - p0));
+		}
+		g0 = g1;
+	}
+	const size_t acc_stride = 2 * (size_t)points; // floats of one position's sums
+	if (hipError_t err = sums.ensure(4 * acc_stride * n_pos + 16); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", err);
+	float *d_acc = (float *)sums.p;
+	// sx | sy | x | y | mark, each 16-aligned, for the points x positions of a launch (nothing in flight reads the scratch: every
+	// call that uses it ends with a synchronisation)
+	auto scratch_bytes = [](size_t e, size_t *sy, size_t *x, size_t *y, size_t *mark) {
+		*sy = align_up(4 * e, 16), *x = 2 * *sy, *y = *x + align_up(2 * e, 16), *mark = *y + align_up(2 * e, 16);
+		return *mark + e;
+	};
+	size_t s_sy = 0, s_x = 0, s_y = 0, s_mark = 0;
+	if (most)
+		if (hipError_t err = ctx->gvar_scratch.ensure(scratch_bytes(most, &s_sy, &s_x, &s_y, &s_mark) + 16); err != hipSuccess)
+			return font_hip_error(ctx, name, "hipMalloc", err);
+	q.copy(d_at, pt_at.data(), 4 * ((size_t)n + 1));
+	q.record(ev.at[1]);
+	for (const Launch &l : launches) {
+		const uint32_t slice = pt_at[l.g1] - pt_at[l.g0];
+		(void)scratch_bytes((size_t)slice * (l.p1 - l.p0), &s_sy, &s_x, &s_y, &s_mark);
+		uint8_t *s = (uint8_t *)ctx->gvar_scratch.p;
+		const vgsdf::GvarScratch scratch{(float *)s, (float *)(s + s_sy), (int16_t *)(s + s_x), (int16_t *)(s + s_y), s + s_mark};
+		q.launch([&] {
+			return vgsdf_gvar_batch_deltas(&face, l.g0, l.g1, l.p0, l.p1, d_coords, d_counts, d_at, d_acc, acc_stride, &scratch, slice, d_flags, st);
+		});
+	}
+	q.record(ev_deltas);
+	std::vector<uint32_t> flags((size_t)vgsdf::GVAR_FLAG_WORDS * n_pos, 0);
+	q.read_back(flags.data(), d_flags, 4 * flags.size());
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, name, "deltas pass", q.e);
+	(void)hipEventElapsedTime(&ctx->gvar_batch_ms[1], ev.at[1], ev_deltas);
+	// per position: refused, passed over, or a font with its store
+	std::vector<std::unique_ptr<vgsdf_font>> made(n_pos); // freed on every way out but the last
+	std::vector<uint32_t> built;
+	uint64_t room = max_store_bytes;
+	for (uint32_t p = 0; p < n_pos; p++) {
+		const uint32_t *f = flags.data() + (size_t)vgsdf::GVAR_FLAG_WORDS * p;
+		if (f[vgsdf::GVAR_FLAG_MALFORMED] || f[vgsdf::GVAR_FLAG_DELTAS]) {
+			ctx->err = std::string(name) + ": position " + std::to_string(p) +
+			           (f[vgsdf::GVAR_FLAG_MALFORMED] ? ": a glyph with malformed variation data" : ": a glyph past VGSDF_GVAR_MAX_DELTAS");
+			status[p] = VGSDF_E_GLYF;
+			if (needed)
+				needed[p] = 0;
+			continue;
+		}
+		if (at.total > room)
+			continue; // (out[p] stays NULL: passed over, the positions behind it go on with the same room)
+		room -= at.total;
+		std::unique_ptr<vgsdf_font> font(new vgsdf_font());
+		font->slots = slots;
+		font->device = ctx->device;
+		font->n_glyph_ids = n;
+		font->commands = true;
+		if (hipError_t err = font->store.ensure(at.total + 16); err != hipSuccess)
+			return font_hip_error(ctx, name, "hipMalloc", err);
+		made[p] = std::move(font);
+		built.push_back(p);
+	}
+	if (built.empty())
+		return VGSDF_OK;
+	// what the context passes read, for the duration of this call: scale | dat_off (one for all: ContextStagingLayout's) | the
+	// context passes' error words | per built position coords | kinds | pad to 16
+	const uint32_t n_built = (uint32_t)built.size();
+	const size_t t_dat = 8 * (size_t)n, t_flags = align_up(t_dat + 4 * ((size_t)n + 1), 16), t_first = t_flags + align_up(4 * (size_t)n_built, 16),
+	             t_each = align_up(4 * (size_t)n_floats + n_cmds, 16);
+	if (hipError_t err = tmp.ensure(t_first + t_each * n_built + 16); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", err);
+	uint8_t *t = (uint8_t *)tmp.p;
+	const std::vector<double> ones(n, 1.0);
+	q.copy(t, ones.data(), 8 * (size_t)n);
+	q.copy(t + t_dat, dat_off.data(), 4 * ((size_t)n + 1));
+	q.zero(t + t_flags, 4 * (size_t)n_built);
+	std::vector<vgsdf::GvarPositionRef> rec(n_built);
+	for (uint32_t k = 0; k < n_built; k++) {
+		const uint32_t p = built[k];
+		uint8_t *d = (uint8_t *)made[p]->store.p, *tp = t + t_first + t_each * k;
+		q.copy(d + at.cmd_off, cmd_off.data(), 4 * ((size_t)n + 1));
+		rec[k] = vgsdf::GvarPositionRef{d_acc + acc_stride * p, (const uint32_t *)(d + at.cmd_off), (const uint32_t *)(t + t_dat),
+		                                tp + 4 * (size_t)n_floats, (float *)tp, d_flags + (size_t)vgsdf::GVAR_FLAG_WORDS * p};
+	}
+	q.copy(d_rec, rec.data(), sizeof(vgsdf::GvarPositionRef) * (size_t)n_built);
+	q.record(ev.at[1]);
+	if (n)
+		q.launch([&] { return vgsdf_gvar_batch_emit(&face, d_rec, n_built, d_counts, d_at, st); });
+	q.record(ev.at[2]);
+	if (n_cmds)
+		for (uint32_t k = 0; k < n_built; k++) {
+			uint8_t *d = (uint8_t *)made[built[k]]->store.p;
+			q.launch([&] {
+				return vgsdf_outline_context_packed(rec[k].kinds, rec[k].coords, rec[k].dat_off, rec[k].cmd_off, (const double *)t, n, (vgsdf::OutlineCmd *)d,
+				                                    d + at.open, (uint32_t *)(t + t_flags) + k, q.st);
+			});
+		}
+	std::vector<uint32_t> context_flags(n_built, 0);
+	q.read_back(context_flags.data(), t + t_flags, 4 * (size_t)n_built);
+	q.read_back(flags.data(), d_flags, 4 * flags.size());
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, name, "emit pass", q.e);
+	(void)hipEventElapsedTime(&ctx->gvar_batch_ms[2], ev.at[1], ev.at[2]);
+	for (uint32_t k = 0; k < n_built; k++)
+		if (context_flags[k] || flags[(size_t)vgsdf::GVAR_FLAG_WORDS * built[k] + vgsdf::GVAR_FLAG_EMIT]) { // (one text over the same bytes)
+			ctx->err = "vgsdf_fonts_create_gvar: the emit pass did not match the count pass, or the context pass refused the commands";
+			return VGSDF_E_HIP;
+		}
+	for (uint32_t p : built) {
+		name_command_store(*made[p], at, n_cmds);
+		out[p] = made[p].release();
+	}
+	return VGSDF_OK;
+}
+} // namespace
+
+extern "C" {
+
+int vgsdf_fonts_create_gvar_within(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *in, uint64_t max_store_bytes, vgsdf_font **out, int *status,
+                                   uint64_t *needed)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	try {
+		return create_gvar_batch(ctx, in, max_store_bytes, out, status, needed);
+	} catch (const std::bad_alloc &) { // (the fonts made so far are freed on the way here; out[] holds none of them)
+		ctx->err = "vgsdf_fonts_create_gvar: out of host memory";
+		return VGSDF_E_OOM;
+	}
+}
+
+int vgsdf_fonts_create_gvar(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *in, vgsdf_font **out, int *status)
+{
+	return vgsdf_fonts_create_gvar_within(ctx, in, ~0ull, out, status, nullptr);
+}
+
+void vgsdf_fonts_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3])
+{
+	if (ms)
+		for (int i = 0; i < 3; i++)
+			ms[i] = ctx ? ctx->gvar_batch_ms[i] : 0.0f;
 }
 
 } // extern "C"

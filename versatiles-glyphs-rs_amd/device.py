@@ -111,6 +111,10 @@ class _CFontGvarDesc(C.Structure):  # vgsdf_font_gvar_desc
     _fields_ = [("tables", _CFontTablesDesc), ("gvar", C.c_void_p), ("gvar_len", C.c_uint32), ("n_axes", C.c_uint32), ("coords", C.c_void_p)]
 
 
+class _CFontsGvarDesc(C.Structure):  # vgsdf_fonts_gvar_desc
+    _fields_ = _CFontGvarDesc._fields_ + [("n_positions", C.c_uint32)]
+
+
 class _COutlinesRanges(C.Structure):  # vgsdf_outlines_ranges
     _fields_ = [("n_tasks", C.c_uint32), ("n_families", C.c_uint32), ("families", C.c_void_p), ("family_of", C.c_void_p),
                 ("first", C.c_void_p), ("last", C.c_void_p), ("pbf_pre", C.c_void_p)]
@@ -129,6 +133,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_font_create_tables", "vgsdf_font_create_tables_within", "vgsdf_font_read", "vgsdf_font_tables_kernel_ms",
     "vgsdf_fonts_create_tables", "vgsdf_fonts_create_tables_within", "vgsdf_fonts_tables_kernel_ms",
     "vgsdf_font_create_gvar", "vgsdf_font_create_gvar_within", "vgsdf_font_gvar_kernel_ms",
+    "vgsdf_fonts_create_gvar", "vgsdf_fonts_create_gvar_within", "vgsdf_fonts_gvar_kernel_ms",
     "vgsdf_outlines_submit_resident_mixed", "vgsdf_family_create_mixed", "vgsdf_family_create_tables_mixed",
     "vgsdf_family_create_tables_var", "vgsdf_family_create_tables_var_mixed",
 ]
@@ -199,6 +204,10 @@ def load_library():
         L.vgsdf_font_create_gvar_within.argtypes = [vp, C.POINTER(_CFontGvarDesc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.vgsdf_font_gvar_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_font_gvar_kernel_ms.restype = None
+        L.vgsdf_fonts_create_gvar.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vgsdf_fonts_create_gvar_within.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vgsdf_fonts_gvar_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_fonts_gvar_kernel_ms.restype = None
         L.vgsdf_font_free.argtypes = [vp, vp]
         L.vgsdf_font_device_bytes.argtypes = [vp]
         L.vgsdf_font_device_bytes.restype = C.c_uint64
@@ -416,6 +425,11 @@ class SdfContext:
     def _check(self, rc: int):
         if rc != 0:
             raise VgsdfError(rc, (load_library().vgsdf_last_error(self._h) or b"").decode())
+
+    def last_error(self) -> str:
+        """vgsdf_last_error: the words of this context's last failure or per-item refusal (a call that returns VGSDF_OK with a
+        status that is not leaves them here)"""
+        return (load_library().vgsdf_last_error(self._h) or b"").decode()
 
     def set_variant(self, v: int):
         self._check(load_library().vgsdf_set_variant(self._h, v))
@@ -756,6 +770,50 @@ class SdfContext:
         ms = (C.c_float * 2)()
         load_library().vgsdf_fonts_tables_kernel_ms(self._h, ms)
         return float(ms[0]), float(ms[1])
+
+    def fonts_create_gvar(self, desc: dict, positions, max_store_bytes=None, **override):
+        """vgsdf_fonts_create_gvar: ONE placed `glyf` face (desc as font_create_gvar takes it; its own "coords" is not looked at) at
+        every position of `positions` (each n_axes normalised int16 coordinates) in one call -> (fonts, statuses, needed), each a
+        list per position: a ResidentFont or None; VGSDF_OK with a font, VGSDF_OK without one when the store would pass what the
+        positions before it have left of max_store_bytes (vgsdf_fonts_create_gvar_within; needed: the store's bytes, 0 without a
+        limit), VGSDF_E_GLYF for a position the device refuses.  VgsdfError: the whole call failed.
+        override (for calls that lie): n_positions, n_axes, n_loca_bytes, n_glyf_bytes, gvar_len; null: the names among "desc",
+        "gvar", "coords", "out", "status" to pass as NULL"""
+        loca, glyf = np.frombuffer(bytes(desc["loca"]), dtype=np.uint8), np.frombuffer(bytes(desc["glyf"]), dtype=np.uint8)
+        gvar = np.frombuffer(bytes(desc["gvar"]), dtype=np.uint8)
+        coords = np.ascontiguousarray(np.asarray(positions, dtype=np.int16).reshape(len(positions), -1 if len(positions) else 0))
+        null = set(override.get("null", ()))
+        d = _CFontsGvarDesc()
+        d.tables = _CFontTablesDesc(int(desc["num_glyphs"]), int(desc["loca_entries"]), int(desc["loca_long"]),
+                                    override.get("n_loca_bytes", len(loca)), override.get("n_glyf_bytes", len(glyf)),
+                                    loca.ctypes.data if len(loca) else None, glyf.ctypes.data if len(glyf) else None)
+        d.gvar = gvar.ctypes.data if len(gvar) and "gvar" not in null else None
+        d.gvar_len = override.get("gvar_len", len(gvar))
+        d.n_axes = override.get("n_axes", coords.shape[1] if len(positions) else len(desc["coords"]))
+        d.coords = coords.ctypes.data if coords.size and "coords" not in null else None
+        d.n_positions = n = int(override.get("n_positions", len(positions)))
+        room = max(len(positions), n if n <= 4096 else 0, 1)
+        out, status, needed = (C.c_void_p * room)(), (C.c_int * room)(), (C.c_uint64 * room)()
+        args = [None if "desc" in null else C.byref(d)]
+        tail = [None if "out" in null else out, None if "status" in null else status]
+        L = load_library()
+        try:
+            if max_store_bytes is not None:
+                self._check(L.vgsdf_fonts_create_gvar_within(self._h, *args, int(max_store_bytes), *tail, needed))
+            else:
+                self._check(L.vgsdf_fonts_create_gvar(self._h, *args, *tail))
+        except VgsdfError:
+            assert not any(out[i] for i in range(room)), "a failed call left a font behind"
+            raise
+        k = min(n, room)
+        return ([ResidentFont(self, C.c_void_p(out[i])) if out[i] else None for i in range(k)], [int(status[i]) for i in range(k)],
+                [int(needed[i]) for i in range(k)])
+
+    def fonts_gvar_kernel_ms(self):
+        """(count, deltas, emit) pass milliseconds of this context's last fonts_create_gvar"""
+        ms = (C.c_float * 3)()
+        load_library().vgsdf_fonts_gvar_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def outlines_submit_resident_mixed(self, fonts, font_of, glyph_id, scale, shift_x, capacity: int, pbf_pre=None, pbf_fix=None, fill=None):
         """vgsdf_outlines_submit_resident_mixed: outlines_submit_resident with fonts of BOTH kinds (glyf and command fonts) in `fonts`"""

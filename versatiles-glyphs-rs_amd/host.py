@@ -111,7 +111,10 @@ VGFONT_SYMBOLS = [
     "vg_manager_set_mixed_stores", "vg_manager_mixed_stats",
     "vg_manager_add_font_instance", "vg_manager_add_font_instance_normalized", "vg_font_variation_axes", "vg_font_named_instances",
     "vg_manager_family_variation_desc", "vg_manager_font_position", "vg_manager_font_hor_advances",
+    "vg_manager_add_font_named_instances", "vg_manager_set_scan_named_instances", "vg_manager_set_gvar_batched", "vg_manager_gvar_batch_stats",
 ]
+
+VG_FONT_ID_MAX = 256
 
 _bound = False
 
@@ -169,6 +172,12 @@ def _L():
         L.vg_manager_set_glyf_tables_batched.argtypes = [vp, C.c_int]
         L.vg_manager_set_glyf_tables_batched.restype = None
         L.vg_manager_glyf_table_batch_stats.argtypes = [vp, C.POINTER(GlyfTableBatchStats)]
+        L.vg_manager_add_font_named_instances.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_int]
+        L.vg_manager_set_scan_named_instances.argtypes = [vp, C.c_int]
+        L.vg_manager_set_scan_named_instances.restype = None
+        L.vg_manager_set_gvar_batched.argtypes = [vp, C.c_int]
+        L.vg_manager_set_gvar_batched.restype = None
+        L.vg_manager_gvar_batch_stats.argtypes = [vp, C.POINTER(GlyfTableBatchStats)]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -585,6 +594,33 @@ class FontManager:
         if _L().vg_manager_add_font_instance_normalized(self._h, name.encode(), data, len(data), c, len(coords)) != 0:
             raise RuntimeError(_err())
         return name_to_id(name)
+
+    def add_font_named_instances(self, data: bytes):
+        """vg_manager_add_font_named_instances: every named instance of the file's fvar as a font id of its own, by add_font_instance's
+        rules, over ONE copy of the bytes -> the font ids in the table's order (the id rule: include/vgfont.h).  RuntimeError: no
+        readable fvar, no instance record, or what add_font_instance refuses"""
+        L = _L()
+        cap = 4096
+        ids = ((C.c_char * VG_FONT_ID_MAX) * cap)()
+        n = L.vg_manager_add_font_named_instances(self._h, data, len(data), ids, cap)
+        if n < 0:
+            raise RuntimeError(_err())
+        return [ids[k].value.decode() for k in range(min(n, cap))]
+
+    def set_scan_named_instances(self, on: bool):
+        """scan and add_path treat a variable file that has instance records as add_font_named_instances does (default off)"""
+        _L().vg_manager_set_scan_named_instances(self._h, int(bool(on)))
+
+    def set_gvar_batched(self, on: bool):
+        """with set_gvar_on_device: the command stores of all placed glyf faces over the same bytes (add_font_named_instances) are
+        built in ONE call (vgsdf_fonts_create_gvar) instead of one per face; same stores, same output (default off)"""
+        _L().vg_manager_set_gvar_batched(self._h, int(bool(on)))
+
+    def gvar_batch_stats(self) -> dict:
+        """of the last render: {calls, faces} of the batched gvar builds (vg_gvar_batch_stats)"""
+        s = GlyfTableBatchStats()  # (vg_gvar_batch_stats has the same two fields)
+        _L().vg_manager_gvar_batch_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in GlyfTableBatchStats._fields_}
 
     def add_path(self, path):
         """manager.rs:39-53: the file's own name table decides the font id."""
