@@ -4,7 +4,10 @@
 //   work_list.cpp           the host's planner of a resident batch's work list
 //   outline_front_end.cpp   outline commands in, rects and bitmaps out
 //   resident_fonts.cpp      fonts uploaded once and named by glyph id (resident_fonts.h: what the front-end reads of them)
-//   resident_families.cpp   the families over them, named by code-point range (resident_build.h: what the two share)
+//   resident_glyf_tables.cpp, resident_charstrings.cpp, resident_gvar.cpp
+//                           the fonts the device builds: from loca and glyf, from charstrings, from loca, glyf and gvar
+//                           (resident_command_store.h: what the builders of command stores share)
+//   resident_families.cpp   the families over them, named by code-point range (resident_build.h: what all of these share)
 //   run_counters.cpp        run counters and their RCCL reduction
 // The kernels they launch are translation units of their own, each with a header of its name: sdf_kernels (raster),
 // input_form_kernels, outline_kernels, outline_plan_kernels (the device front-end: input forms, flattening, plan),
@@ -63,15 +66,15 @@ struct vgsdf_ctx {
 	uint64_t counters[3] = {0, 0, 0};
 	uint64_t *d_counters = nullptr;
 	void *comm = nullptr; // ncclComm_t of the communicator this context last reduced in (owned by run_counters.cpp's cache)
-	float charstring_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_font_create_charstrings / _charstrings2 (resident_fonts.cpp)
+	float charstring_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_font_create_charstrings / _charstrings2 (resident_charstrings.cpp)
 	// vgsdf_font_create_charstrings2: operand slots past the decoder's LDS window, for one launch (at most 16384 glyph ids); grows
 	// to exactly what the largest launch so far needed and belongs to no font
 	void *charstring_spill = nullptr;
 	size_t charstring_spill_bytes = 0;
 	float family_tables_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_family_create_tables (resident_families.cpp)
-	float glyf_tables_ms[2] = {0.0f, 0.0f};   // count / emit kernels of the last vgsdf_font_create_tables (resident_fonts.cpp)
+	float glyf_tables_ms[2] = {0.0f, 0.0f};   // count / emit kernels of the last vgsdf_font_create_tables (resident_glyf_tables.cpp)
 	float glyf_batch_ms[2] = {0.0f, 0.0f};    // the same of the last vgsdf_fonts_create_tables: one launch each over all its faces
-	float gvar_ms[3] = {0.0f, 0.0f, 0.0f};    // count / deltas / emit kernels of the last vgsdf_font_create_gvar (resident_fonts.cpp)
+	float gvar_ms[3] = {0.0f, 0.0f, 0.0f};    // count / deltas / emit kernels of the last vgsdf_font_create_gvar (resident_gvar.cpp)
 	float gvar_batch_ms[3] = {0.0f, 0.0f, 0.0f}; // the same of the last vgsdf_fonts_create_gvar: one face at all its positions
 	// vgsdf_font_create_gvar, vgsdf_fonts_create_gvar: the deltas pass's scratch for one launch (GvarScratch: 13 bytes per point of
 	// at most 2^17 points — points x positions in the batched call —, or of one glyph id at one position); grown on demand, belongs
@@ -108,7 +111,7 @@ inline int kernel_id(int variant) { return variant == 0 ? 50 : (variant == 13 ? 
 // the variant's main-class entries are spans: (glyph, first pixel | tile count)
 inline bool uses_span_list(int variant) { return variant == 0 || (variant >= 50 && variant <= 99); }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 inline double fe_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 

@@ -28,6 +28,16 @@ inline uint32_t to_u32(double v)
 	return (uint32_t)v;
 }
 
+// a face's loca and glyf as the device's constructors take them
+vgsdf_font_tables_desc tables_desc(const FontTables &t)
+{
+	vgsdf_font_tables_desc d;
+	d.num_glyphs = t.num_glyphs, d.loca_entries = t.loca_entries, d.loca_long = t.loca_long;
+	d.n_loca_bytes = t.n_loca_bytes, d.n_glyf_bytes = t.n_glyf_bytes;
+	d.loca = t.loca, d.glyf = t.glyf;
+	return d;
+}
+
 } // namespace
 
 void GlyphBatch::clear()
@@ -212,22 +222,13 @@ Renderer::~Renderer()
 					vgsdf_family_free(device_lane(i).ctx_, kv.second);
 					break;
 				}
-		resident_->families.clear();
 		for (auto &kv : resident_->fonts)
 			for (size_t i = 0; i < n_devices(); i++)
 				if (device_lane(i).device_ == kv.first.first) {
 					vgsdf_font_free(device_lane(i).ctx_, kv.second);
 					break;
 				}
-		resident_->fonts.clear();
-		resident_->refused_charstrings.clear();
-		resident_->refused_family_tables.clear();
-		resident_->unfit_charstrings.clear();
-		resident_->refused_glyf_tables.clear();
-		resident_->unfit_glyf_tables.clear();
-		resident_->refused_gvar.clear();
-		resident_->unfit_gvar.clear();
-		resident_->bytes.clear();
+		resident_->clear();
 	}
 	if (ctx2_)
 		vgsdf_destroy(ctx2_);
@@ -482,48 +483,88 @@ const vgsdf_font *Renderer::resident_font(int lane, const ResidentTable &t, uint
 	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
 }
 
-const vgsdf_font *Renderer::font_from_tables(int lane, uint64_t serial, const FontTables &t, uint64_t *uploaded_bytes, bool *refused,
-                                             bool *over_budget, bool *built) const
+template <class Build>
+const vgsdf_font *Renderer::device_built_font(int lane, ResidentFonts::DeviceBuilt &kind, uint64_t serial, const char *throws_as, Build build,
+                                              uint64_t *uploaded_bytes, bool *refused, bool *over_budget, bool *built) const
 {
-	if (mode_ != Mode::Hip || !t.ok)
+	const auto say = [](bool *flag) {
+		if (flag)
+			*flag = true;
 		return nullptr;
+	};
 	ResidentFonts &rf = *resident_;
 	std::lock_guard<std::mutex> table_lock(rf.mu);
 	const auto key = std::make_pair(device_, serial);
 	if (auto *found = rf.find(rf.fonts, key))
 		return found;
-	if (rf.refused_glyf_tables.count(key))
-		return nullptr;
 	const uint64_t room = rf.room(device_);
-	if (auto it = rf.unfit_glyf_tables.find(key); it != rf.unfit_glyf_tables.end() && it->second > room) {
-		*over_budget = true;
-		return nullptr;
-	}
-	vgsdf_font_tables_desc d;
-	d.num_glyphs = t.num_glyphs, d.loca_entries = t.loca_entries, d.loca_long = t.loca_long;
-	d.n_loca_bytes = t.n_loca_bytes, d.n_glyf_bytes = t.n_glyf_bytes;
-	d.loca = t.loca, d.glyf = t.glyf;
+	if (const auto known = kind.known(key, room))
+		return known == ResidentFonts::DeviceBuilt::kUnfit ? say(over_budget) : nullptr;
 	vgsdf_ctx *c = lane_ctx(lane & 1);
 	vgsdf_font *f = nullptr;
 	{
-		// the budget as resident_font holds it: the font's size is known behind the count pass, and checked there, before
-		// anything of it is allocated
+		// the budget as resident_font and command_font hold it: the store's size is known behind the count pass, and checked there,
+		// before anything of the store is allocated
 		uint64_t want = 0;
 		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_font_create_tables_within(c, &d, room, &f, &want) != VGSDF_OK) { // (a refusal or a device error: the host's way)
-			rf.refused_glyf_tables.insert(key);
-			*refused = true;
-			return nullptr;
+		const int rc = build(c, room, &f, &want);
+		if (rc == VGSDF_E_GLYF || (rc != VGSDF_OK && !throws_as)) {
+			kind.remember_refused(key);
+			return say(refused);
 		}
+		if (rc != VGSDF_OK)
+			throw std::runtime_error(std::string(throws_as) + ": " + vgsdf_last_error(c));
 		if (!f) { // over the budget as it stands
-			rf.unfit_glyf_tables[key] = want;
-			*over_budget = true;
-			return nullptr;
+			kind.remember_unfit(key, want);
+			return say(over_budget);
 		}
 	}
-	rf.unfit_glyf_tables.erase(key);
-	*built = true;
+	kind.fitted(key);
+	if (built)
+		*built = true;
 	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
+}
+
+template <class Job>
+void Renderer::settle_batch(ResidentFonts::DeviceBuilt &kind, vgsdf_ctx *c, bool failed, const std::vector<Job> &faces, const std::vector<size_t> &sent,
+                            std::vector<vgsdf_font *> &made, const std::vector<int> &status, const std::vector<uint64_t> &needed,
+                            std::vector<TablesOutcome> &outcomes) const
+{
+	ResidentFonts &rf = *resident_;
+	for (size_t i = 0; i < sent.size(); i++) {
+		TablesOutcome &o = outcomes[sent[i]];
+		const auto key = std::make_pair(device_, faces[sent[i]].serial);
+		if (failed || status[i] != VGSDF_OK) { // (refused, whatever the reason: the host's way, once)
+			kind.remember_refused(key);
+			o.refused = true;
+			continue;
+		}
+		if (made[i] && needed[i] > rf.room(device_)) { // (the registry counts allocations, a quarter more than the stores)
+			std::lock_guard<std::mutex> lock(mu_);
+			(void)vgsdf_font_free(c, made[i]);
+			made[i] = nullptr;
+		}
+		if (!made[i]) { // over the budget as it stands
+			kind.remember_unfit(key, needed[i]);
+			o.over_budget = true;
+			continue;
+		}
+		kind.fitted(key);
+		o.built = true;
+		(void)rf.keep(rf.fonts, key, made[i], vgsdf_font_device_bytes(made[i]), &o.uploaded);
+	}
+}
+
+const vgsdf_font *Renderer::font_from_tables(int lane, uint64_t serial, const FontTables &t, uint64_t *uploaded_bytes, bool *refused,
+                                             bool *over_budget, bool *built) const
+{
+	if (mode_ != Mode::Hip || !t.ok)
+		return nullptr;
+	// (throws_as NULL: a refusal or a device error, the host's way)
+	return device_built_font(lane, resident_->glyf_tables, serial, nullptr, [&](vgsdf_ctx *c, uint64_t room, vgsdf_font **f, uint64_t *want) {
+		const vgsdf_font_tables_desc d = tables_desc(t);
+		return vgsdf_font_create_tables_within(c, &d, room, f, want);
+	}, uploaded_bytes, refused, over_budget, built);
 }
 
 void Renderer::fonts_from_tables(int lane, const std::vector<TablesJob> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls,
@@ -553,28 +594,7 @@ void Renderer::fonts_from_tables(int lane, const std::vector<TablesJob> &faces, 
 			rc = vgsdf_fonts_create_tables_within(c, descs.data(), (uint32_t)descs.size(), rf.room(device_), made.data(), status.data(), needed.data());
 		}
 		*calls += 1, *n_sent += sent.size();
-		for (size_t i = 0; i < sent.size(); i++) {
-			TablesOutcome &o = outcomes[sent[i]];
-			const auto key = std::make_pair(device_, faces[sent[i]].serial);
-			if (rc != VGSDF_OK || status[i] != VGSDF_OK) { // (a refusal or a device error: the host's way)
-				rf.refused_glyf_tables.insert(key);
-				o.refused = true;
-				continue;
-			}
-			if (made[i] && needed[i] > rf.room(device_)) {
-				std::lock_guard<std::mutex> lock(mu_);
-				(void)vgsdf_font_free(c, made[i]);
-				made[i] = nullptr;
-			}
-			if (!made[i]) { // over the budget as it stands
-				rf.unfit_glyf_tables[key] = needed[i];
-				o.over_budget = true;
-				continue;
-			}
-			rf.unfit_glyf_tables.erase(key);
-			o.built = true;
-			(void)rf.keep(rf.fonts, key, made[i], vgsdf_font_device_bytes(made[i]), &o.uploaded);
-		}
+		settle_batch(rf.glyf_tables, c, rc != VGSDF_OK, faces, sent, made, status, needed, outcomes); // (a device error: the host's way)
 		sent.clear(), descs.clear();
 	};
 	uint64_t glyph_ids = 0;
@@ -582,19 +602,13 @@ void Renderer::fonts_from_tables(int lane, const std::vector<TablesJob> &faces, 
 	for (size_t i = 0; i < faces.size(); i++) {
 		const FontTables &t = faces[i].tables;
 		const auto key = std::make_pair(device_, faces[i].serial);
-		if (!t.ok || rf.find(rf.fonts, key) || rf.refused_glyf_tables.count(key))
-			continue;
-		if (auto it = rf.unfit_glyf_tables.find(key); it != rf.unfit_glyf_tables.end() && it->second > rf.room(device_))
+		if (!t.ok || rf.find(rf.fonts, key) || rf.glyf_tables.known(key, rf.room(device_)))
 			continue; // (font_from_tables says over_budget when it is asked)
 		if (!seen.insert(faces[i].serial).second)
 			continue; // (a face named twice: one font)
 		if (sent.size() == kMaxFaces || glyph_ids + t.num_glyphs > kMaxGlyphIds)
 			flush(), glyph_ids = 0;
-		vgsdf_font_tables_desc d;
-		d.num_glyphs = t.num_glyphs, d.loca_entries = t.loca_entries, d.loca_long = t.loca_long;
-		d.n_loca_bytes = t.n_loca_bytes, d.n_glyf_bytes = t.n_glyf_bytes;
-		d.loca = t.loca, d.glyf = t.glyf;
-		sent.push_back(i), descs.push_back(d);
+		sent.push_back(i), descs.push_back(tables_desc(t));
 		glyph_ids += t.num_glyphs;
 	}
 	flush();
@@ -630,19 +644,6 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 {
 	if (mode_ != Mode::Hip || !t.ok)
 		return nullptr;
-	ResidentFonts &rf = *resident_;
-	std::lock_guard<std::mutex> table_lock(rf.mu);
-	const auto key = std::make_pair(device_, t.serial);
-	if (auto *found = rf.find(rf.fonts, key))
-		return found;
-	if (rf.refused_charstrings.count(key))
-		return nullptr;
-	const uint64_t room = rf.room(device_);
-	if (auto it = rf.unfit_charstrings.find(key); it != rf.unfit_charstrings.end() && it->second > room) {
-		if (over_budget)
-			*over_budget = true;
-		return nullptr;
-	}
 	vgsdf_font_charstrings2_desc d2{};
 	vgsdf_font_charstrings_desc &d = d2.charstrings;
 	d2.n_sets = (uint32_t)t.set_ok.size();
@@ -660,76 +661,21 @@ const vgsdf_font *Renderer::charstring_font(int lane, const CharstringTable &t, 
 	d.lsubr_first = t.lsubr_first.data();
 	d.lsubr_off = t.lsubr_off.data();
 	d.fd_of = t.fd_of.empty() ? nullptr : t.fd_of.data();
-	vgsdf_ctx *c = lane_ctx(lane & 1);
-	vgsdf_font *f = nullptr;
-	{
-		// the budget as command_font holds it: the store's size is known behind the count pass, and checked there, before
-		// anything of the store is allocated
-		uint64_t want = 0;
-		std::lock_guard<std::mutex> lock(mu_);
-		const int rc = t.cff2 ? vgsdf_font_create_charstrings2_within(c, &d2, room, &f, &want) : vgsdf_font_create_charstrings_within(c, &d, room, &f, &want);
-		if (rc == VGSDF_E_GLYF) {
-			rf.refused_charstrings.insert(key);
-			if (refused)
-				*refused = true;
-			return nullptr;
-		}
-		if (rc != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_font_create_charstrings: ") + vgsdf_last_error(c));
-		if (!f) { // over the budget as it stands
-			rf.unfit_charstrings[key] = want;
-			if (over_budget)
-				*over_budget = true;
-			return nullptr;
-		}
-	}
-	rf.unfit_charstrings.erase(key);
-	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
+	return device_built_font(lane, resident_->charstrings, t.serial, "vgsdf_font_create_charstrings", [&](vgsdf_ctx *c, uint64_t room, vgsdf_font **f, uint64_t *want) {
+		return t.cff2 ? vgsdf_font_create_charstrings2_within(c, &d2, room, f, want) : vgsdf_font_create_charstrings_within(c, &d, room, f, want);
+	}, uploaded_bytes, refused, over_budget, nullptr);
 }
 
 const vgsdf_font *Renderer::gvar_font(int lane, uint64_t serial, const GvarTables &t, uint64_t *uploaded_bytes, bool *refused, bool *over_budget) const
 {
 	if (mode_ != Mode::Hip || !t.ok)
 		return nullptr;
-	ResidentFonts &rf = *resident_;
-	std::lock_guard<std::mutex> table_lock(rf.mu);
-	const auto key = std::make_pair(device_, serial);
-	if (auto *found = rf.find(rf.fonts, key))
-		return found;
-	if (rf.refused_gvar.count(key))
-		return nullptr;
-	const uint64_t room = rf.room(device_);
-	if (auto it = rf.unfit_gvar.find(key); it != rf.unfit_gvar.end() && it->second > room) {
-		*over_budget = true;
-		return nullptr;
-	}
-	vgsdf_font_gvar_desc d{};
-	d.tables.num_glyphs = t.tables.num_glyphs, d.tables.loca_entries = t.tables.loca_entries, d.tables.loca_long = t.tables.loca_long;
-	d.tables.n_loca_bytes = t.tables.n_loca_bytes, d.tables.n_glyf_bytes = t.tables.n_glyf_bytes;
-	d.tables.loca = t.tables.loca, d.tables.glyf = t.tables.glyf;
-	d.gvar = t.gvar, d.gvar_len = t.gvar_len, d.n_axes = t.n_axes, d.coords = t.coords;
-	vgsdf_ctx *c = lane_ctx(lane & 1);
-	vgsdf_font *f = nullptr;
-	{
-		// the budget as charstring_font holds it: the store's size is known behind the count pass, and checked there
-		uint64_t want = 0;
-		std::lock_guard<std::mutex> lock(mu_);
-		const int rc = vgsdf_font_create_gvar_within(c, &d, room, &f, &want);
-		if (rc == VGSDF_E_GLYF) {
-			rf.refused_gvar.insert(key);
-			*refused = true;
-			return nullptr;
-		}
-		if (rc != VGSDF_OK)
-			throw std::runtime_error(std::string("vgsdf_font_create_gvar: ") + vgsdf_last_error(c));
-		if (!f) { // over the budget as it stands
-			rf.unfit_gvar[key] = want;
-			*over_budget = true;
-			return nullptr;
-		}
-	}
-	rf.unfit_gvar.erase(key);
-	return rf.keep(rf.fonts, key, f, vgsdf_font_device_bytes(f), uploaded_bytes);
+	return device_built_font(lane, resident_->gvar, serial, "vgsdf_font_create_gvar", [&](vgsdf_ctx *c, uint64_t room, vgsdf_font **f, uint64_t *want) {
+		vgsdf_font_gvar_desc d{};
+		d.tables = tables_desc(t.tables);
+		d.gvar = t.gvar, d.gvar_len = t.gvar_len, d.n_axes = t.n_axes, d.coords = t.coords;
+		return vgsdf_font_create_gvar_within(c, &d, room, f, want);
+	}, uploaded_bytes, refused, over_budget, nullptr);
 }
 
 void Renderer::gvar_fonts(int lane, const std::vector<GvarJob> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls, uint64_t *n_sent) const
@@ -747,9 +693,7 @@ void Renderer::gvar_fonts(int lane, const std::vector<GvarJob> &faces, std::vect
 			return;
 		const GvarTables &t = *first;
 		vgsdf_fonts_gvar_desc d{};
-		d.tables.num_glyphs = t.tables.num_glyphs, d.tables.loca_entries = t.tables.loca_entries, d.tables.loca_long = t.tables.loca_long;
-		d.tables.n_loca_bytes = t.tables.n_loca_bytes, d.tables.n_glyf_bytes = t.tables.n_glyf_bytes;
-		d.tables.loca = t.tables.loca, d.tables.glyf = t.tables.glyf;
+		d.tables = tables_desc(t.tables);
 		d.gvar = t.gvar, d.gvar_len = t.gvar_len, d.n_axes = t.n_axes, d.coords = coords.data(), d.n_positions = (uint32_t)sent.size();
 		std::vector<vgsdf_font *> made(sent.size(), nullptr);
 		std::vector<int> status(sent.size(), 0);
@@ -763,37 +707,14 @@ void Renderer::gvar_fonts(int lane, const std::vector<GvarJob> &faces, std::vect
 		if (rc != VGSDF_OK)
 			throw std::runtime_error(std::string("vgsdf_fonts_create_gvar: ") + vgsdf_last_error(c));
 		*calls += 1, *n_sent += sent.size();
-		for (size_t i = 0; i < sent.size(); i++) {
-			TablesOutcome &o = outcomes[sent[i]];
-			const auto key = std::make_pair(device_, faces[sent[i]].serial);
-			if (status[i] != VGSDF_OK) { // (refused at this position, or whatever the position: the host's way, once)
-				rf.refused_gvar.insert(key);
-				o.refused = true;
-				continue;
-			}
-			if (made[i] && needed[i] > rf.room(device_)) { // (the registry counts allocations, a quarter more than the stores)
-				std::lock_guard<std::mutex> lock(mu_);
-				(void)vgsdf_font_free(c, made[i]);
-				made[i] = nullptr;
-			}
-			if (!made[i]) { // over the budget as it stands
-				rf.unfit_gvar[key] = needed[i];
-				o.over_budget = true;
-				continue;
-			}
-			rf.unfit_gvar.erase(key);
-			o.built = true;
-			(void)rf.keep(rf.fonts, key, made[i], vgsdf_font_device_bytes(made[i]), &o.uploaded);
-		}
+		settle_batch(rf.gvar, c, false, faces, sent, made, status, needed, outcomes); // (refused at this position, or whatever the position)
 		sent.clear(), coords.clear();
 	};
 	std::set<uint64_t> seen;
 	for (size_t i = 0; i < faces.size(); i++) {
 		const GvarTables &t = faces[i].tables;
 		const auto key = std::make_pair(device_, faces[i].serial);
-		if (!t.ok || rf.find(rf.fonts, key) || rf.refused_gvar.count(key))
-			continue;
-		if (auto it = rf.unfit_gvar.find(key); it != rf.unfit_gvar.end() && it->second > rf.room(device_))
+		if (!t.ok || rf.find(rf.fonts, key) || rf.gvar.known(key, rf.room(device_)))
 			continue; // (gvar_font says over_budget when it is asked)
 		if (!seen.insert(faces[i].serial).second)
 			continue; // (a face named twice: one store)

@@ -587,14 +587,34 @@ private:
 		std::map<std::pair<int, uint64_t>, vgsdf_font *> fonts; // (device, the face's serial number) -> its copy there
 		std::map<std::tuple<int, uint64_t, int>, vgsdf_family *> families; // (device, table serial, kind of stores) -> the family
 		std::map<int, uint64_t> bytes;                          // per device
-		std::set<std::pair<int, uint64_t>> refused_charstrings; // (device, serial): the device's decoder has refused the face
 		std::set<std::tuple<int, uint64_t, int>> refused_family_tables; // the key of `families`: the device has refused to build the table
-		std::map<std::pair<int, uint64_t>, uint64_t> unfit_charstrings; // (device, serial) -> bytes of a store that passed the budget
-		std::set<std::pair<int, uint64_t>> refused_glyf_tables;         // (device, serial): the device's table builder has refused the face
-		std::map<std::pair<int, uint64_t>, uint64_t> unfit_glyf_tables; // (device, serial) -> bytes of a font that passed the budget
-		std::set<std::pair<int, uint64_t>> refused_gvar;                // (device, serial): the device's gvar builder has refused the face
-		std::map<std::pair<int, uint64_t>, uint64_t> unfit_gvar;        // (device, serial) -> bytes of a store that passed the budget
+		// What the registry remembers of the faces one kind of DEVICE-BUILT font was asked for and did not get, by (device, serial):
+		// those the device's builder has refused (they go the host's way, once) and the bytes of those that passed the budget (the
+		// count pass is not run again while they do not fit, and is once the budget has room for them)
+		struct DeviceBuilt {
+			using Key = std::pair<int, uint64_t>;
+			enum Known { kNothing, kRefused, kUnfit };
+			std::set<Key> refused;
+			std::map<Key, uint64_t> unfit;
+			Known known(const Key &key, uint64_t room) const // refused, or known not to fit this room?
+			{
+				if (refused.count(key))
+					return kRefused;
+				const auto it = unfit.find(key);
+				return it != unfit.end() && it->second > room ? kUnfit : kNothing;
+			}
+			void remember_refused(const Key &key) { refused.insert(key); }
+			void remember_unfit(const Key &key, uint64_t bytes) { unfit[key] = bytes; }
+			void fitted(const Key &key) { unfit.erase(key); }
+			void clear() { refused.clear(), unfit.clear(); }
+		};
+		DeviceBuilt glyf_tables, charstrings, gvar; // font_from_tables / fonts_from_tables, charstring_font, gvar_font / gvar_fonts
 		uint64_t budget = 1ull << 30;
+		void clear() // (the owner has freed the fonts and families)
+		{
+			families.clear(), fonts.clear(), bytes.clear(), refused_family_tables.clear();
+			glyf_tables.clear(), charstrings.clear(), gvar.clear();
+		}
 		// the frame of resident_font() .. family_from_tables() (under `mu`): what the registry holds under a key, the budget a device has left, and a new
 		// font or family of `got` device bytes taken in and accounted (the key's first member is the device)
 		template <class Map, class Key> static typename Map::mapped_type find(const Map &map, const Key &key) { const auto it = map.find(key); return it != map.end() ? it->second : nullptr; }
@@ -608,6 +628,19 @@ private:
 			return made;
 		}
 	};
+	// The protocol of font_from_tables(), charstring_font() and gvar_font(), under the registry's lock: found? refused before? known not
+	// to fit the room?  Then build(context, room, &font, &bytes) makes the C call under the context's lock: refused — VGSDF_E_GLYF, or
+	// any failure where `throws_as` is NULL; another failure throws under that name —, over the budget as it stands (no font), or kept.
+	// The three out-parameters may be NULL
+	template <class Build>
+	const vgsdf_font *device_built_font(int lane, ResidentFonts::DeviceBuilt &kind, uint64_t serial, const char *throws_as, Build build,
+	                                    uint64_t *uploaded_bytes, bool *refused, bool *over_budget, bool *built) const;
+	// ... and what fonts_from_tables() and gvar_fonts() make of one batched call's made[], status[] and needed[] for the faces `sent`
+	// (failed: the call itself did, every face counts as refused): outcomes[] and the registry as that protocol leaves them
+	template <class Job>
+	void settle_batch(ResidentFonts::DeviceBuilt &kind, vgsdf_ctx *c, bool failed, const std::vector<Job> &faces, const std::vector<size_t> &sent,
+	                  std::vector<vgsdf_font *> &made, const std::vector<int> &status, const std::vector<uint64_t> &needed,
+	                  std::vector<TablesOutcome> &outcomes) const;
 	std::shared_ptr<ResidentFonts> resident_ = std::make_shared<ResidentFonts>();
 	bool owns_resident_ = true; // (a peer shares its primary's table and leaves the freeing to it)
 };

@@ -1197,7 +1197,7 @@ int vgsdf_outlines_submit_resident_mixed(vgsdf_ctx *ctx, const vgsdf_outlines_re
 	return fe_submit_named(ctx, in, out_bitmaps, out_capacity, true);
 }
 
-// ---- code-point ranges of resident families (resident_fonts.cpp, vgsdf_family_create) ----
+// ---- code-point ranges of resident families (resident_families.cpp, vgsdf_family_create) ----
 
 // The host's share is O(tasks): per task two bisections of its family's code points and two reads of each prefix sum; per
 // submission the totals that size buffers and grids.  The block it uploads (upload_layout.h, RangesBlockLayout) holds a record

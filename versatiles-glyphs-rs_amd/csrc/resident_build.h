@@ -1,5 +1,6 @@
-// resident_build.h — what the constructors of resident fonts (resident_fonts.cpp) and families (resident_families.cpp) share:
-// their error text, device memory for one call, the sequence of HIP calls of a phase and the events around a count and an emit pass.
+// resident_build.h — what the constructors of resident fonts (resident_fonts.cpp, resident_charstrings.cpp, resident_glyf_tables.cpp,
+// resident_gvar.cpp) and families (resident_families.cpp) share: their error text, what a description of loca and glyf must hold,
+// device memory for one call, the sequence of HIP calls of a phase and the events around a count and an emit pass.
 // Every allocation here and there asks for 16 bytes more than its layout states, as the front-end's buffers do: a kernel that
 // moves a buffer in 16-byte units may touch the whole unit its last byte lies in.  The layouts (upload_layout.h) do not count them.
 #pragma once
@@ -10,6 +11,23 @@ VGSDF_INTERNAL inline int font_hip_error(vgsdf_ctx *ctx, const char *entry, cons
 {
 	ctx->err = std::string(entry) + ": " + what + ": " + hipGetErrorString(e);
 	return e == hipErrorOutOfMemory ? VGSDF_E_OOM : VGSDF_E_HIP;
+}
+
+// a glyf font's three arrays, once its store is allocated
+inline void name_glyf_store(vgsdf_font &f, const vgsdf::GlyfStoreLayout &at)
+{
+	const uintptr_t d = (uintptr_t)f.store.p;
+	f.ref.leaves = d + at.leaves, f.ref.bytes = d + at.bytes, f.ref.leaf_off = d + at.leaf_off;
+}
+
+// A face's loca and glyf as a constructor is given them (resident_glyf_tables.cpp, resident_gvar.cpp): both tables there ...
+inline bool tables_given(const vgsdf_font_tables_desc &in) { return !((in.n_loca_bytes && !in.loca) || (in.n_glyf_bytes && !in.glyf)); }
+// ... and a description that can be stated.  (Tables of 4 GiB or more cannot: the lengths are 32-bit.  loca_entries <= num_glyphs + 1:
+// every glyph id a component can resolve to is then one of the face's, with a place in the store)
+inline bool tables_stateable(const vgsdf_font_tables_desc &in)
+{
+	return !(in.num_glyphs > 0xFFFFu || in.loca_long > 1u || (uint64_t)in.loca_entries * (in.loca_long ? 4u : 2u) > in.n_loca_bytes ||
+	         in.loca_entries > in.num_glyphs + 1);
 }
 
 struct VGSDF_INTERNAL ScratchBuf : DevBuf { // device memory for the duration of one call

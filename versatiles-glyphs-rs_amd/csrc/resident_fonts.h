@@ -1,4 +1,4 @@
-// resident_fonts.h — a font resident on a device, as its store (resident_fonts.cpp) fills it and the front-end
+// resident_fonts.h — a font resident on a device, as its constructor (resident_*.cpp) fills it and the front-end
 // (outline_front_end.cpp) reads it when a submission names glyphs by (font, glyph id).
 #pragma once
 #include <vector>

@@ -117,7 +117,7 @@ struct CommandBlockLayout : GlyphArraysLayout {
 };
 
 // The stores those references point into: one device allocation per font, laid out the same by every constructor of a kind
-// (resident_fonts.cpp), so the same face takes the same vgsdf_font_device_bytes whichever way it was built.  A glyf font:
+// (resident_*.cpp), so the same face takes the same vgsdf_font_device_bytes whichever way it was built.  A glyf font:
 //   leaves vgsdf_glyf_part[n_leaves] | bytes u8[n_bytes] (a multiple of 4) | pad to 16 | leaf_off u32[n_glyph_ids + 1]
 struct GlyfStoreLayout {
 	size_t leaves = 0, bytes, leaf_off, total;
