@@ -57,6 +57,20 @@ for k, v in sorted(allc.items()):
 if "SQ_LDS_BANK_CONFLICT" in allc and allc.get("SQ_ACTIVE_INST_LDS"):
     lines += ["", f"LDS bank conflicts: SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS = **{allc['SQ_LDS_BANK_CONFLICT'] / allc['SQ_ACTIVE_INST_LDS']:.2f}** "
               "of the LDS-active cycles"]
+main_ns = max([float(r["AverageNs"]) for r in stats if "sdf_tiles" in r["Name"]], default=0.0)
+if main_ns and all(k in allc for k in ("SQ_INSTS_LDS", "SQ_ACTIVE_INST_LDS", "SQ_LDS_BANK_CONFLICT")):
+    # What the counters count (tools/ubench/lds_probe.hip, profiles/lds_probe.txt): SQ_ACTIVE_INST_LDS reads ~1 per LDS instruction
+    # whatever it costs (no busy time: its ratio to SQ_WAVE_CYCLES is per wave and says nothing about the CU's one LDS, which
+    # 16 waves share); SQ_LDS_BANK_CONFLICT reads the extra cycles of a conflicting access (4 per 2-way ds_read_b128, 12 per
+    # 4-way); a conflict-free ds_read_b128 occupies the CU's LDS for 4.95 cycles.  Costing EVERY LDS instruction as one gives
+    # an upper bound of the array's busy share (narrower reads and the atomics cost less).
+    cu_cycles = 256.0 * main_ns * 2.4
+    busy = 4.95 * allc["SQ_INSTS_LDS"] + allc["SQ_LDS_BANK_CONFLICT"]
+    lines += ["", f"LDS per wave: SQ_ACTIVE_INST_LDS / SQ_WAVE_CYCLES = {allc['SQ_ACTIVE_INST_LDS'] / allc['SQ_WAVE_CYCLES']:.3f}"
+              if allc.get("SQ_WAVE_CYCLES") else "",
+              f"LDS array per CU: (4.95 x SQ_INSTS_LDS + SQ_LDS_BANK_CONFLICT) / (256 CUs x {main_ns:.0f} ns x 2.4 GHz) <= "
+              f"**{busy / cu_cycles:.2f}** busy ({allc['SQ_INSTS_LDS'] / 256.0:.0f} LDS instructions per CU and launch; every one costed "
+              "as a conflict-free ds_read_b128, tools/ubench/lds_probe.hip)"]
 if "GRBM_GUI_ACTIVE" in allc:
     lines += ["", f"GRBM_GUI_ACTIVE / 8 XCDs = {allc['GRBM_GUI_ACTIVE'] / 8:.0f} cycles per launch (MI355X_MICROARCH.md, DVFS give-back: / kernel wall "
               "time = effective clock; reads high on dispatches this short — the clock a VALU-bound kernel holds is measured by "

@@ -394,23 +394,50 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				uint32_t dmin = __float_as_uint(ub2);
 				const float4 *gx4 = reinterpret_cast<const float4 *>(s_g[0]), *gy4 = reinterpret_cast<const float4 *>(s_g[1]);
 				const float4 *gr4 = reinterpret_cast<const float4 *>(s_g[2]);
+				auto near4 = [&](uint32_t b, const float4 ax, const float4 ay) { // D_g^2 of the four groups of block b
+					const float axs[4] = {ax.x, ax.y, ax.z, ax.w}, ays[4] = {ay.x, ay.y, ay.z, ay.w};
+					uint32_t d2[4];
 #pragma unroll
-				for (uint32_t b = 0; b < NGRP / 4; b++) {
-					if (b * 4 < n_groups) {
-						const float4 ax = gx4[b], ay = gy4[b];
-						const float axs[4] = {ax.x, ax.y, ax.z, ax.w}, ays[4] = {ay.x, ay.y, ay.z, ay.w};
-						uint32_t d2[4];
+					for (int j = 0; j < 4; j++) {
+						const float ddx = rpx - axs[j], ddy = rpy - ays[j];
+						d2[j] = __float_as_uint(__builtin_fmaf(ddy, ddy, ddx * ddx));
+					}
+					// d2 >= +0: unsigned order of the bits is float order; one v_min3_u32 per two groups
+					asm("v_min3_u32 %0, %1, %2, %3" : "=v"(dmin) : "v"(dmin), "v"(d2[0]), "v"(d2[1]));
+					asm("v_min3_u32 %0, %1, %2, %3" : "=v"(dmin) : "v"(dmin), "v"(d2[2]), "v"(d2[3]));
+					D2p[b * 2] = __builtin_amdgcn_perm(d2[1], d2[0], 0x07060302u);     // hi16(d2[1]) : hi16(d2[0])
+					D2p[b * 2 + 1] = __builtin_amdgcn_perm(d2[3], d2[2], 0x07060302u);
+				};
+				// Both shapes issue a block's two anchor loads ahead of the arithmetic of the block before it: a wave
+				// waits for an LDS round trip it has nothing to put in front of, whatever the other three waves of
+				// its SIMD do (profiles/sweep_latency_ab.txt).  A full chunk runs the eight blocks in a straight line,
+				// as the second pass does.  A partial chunk leaves at the first block past n_groups (a block past
+				// n_groups leaves its D2p unset: the second pass skips the same blocks); the load issued ahead for
+				// that block reads what the stage wrote for its empty groups (1e18 / 0 in every processed chunk).
+				if (n_groups == NGRP) {
 #pragma unroll
-						for (int j = 0; j < 4; j++) {
-							const float ddx = rpx - axs[j], ddy = rpy - ays[j];
-							d2[j] = __float_as_uint(__builtin_fmaf(ddy, ddy, ddx * ddx));
+					for (uint32_t b = 0; b < NGRP / 4; b++)
+						near4(b, gx4[b], gy4[b]);
+				} else {
+					float4 ax = gx4[0], ay = gy4[0];
+#pragma unroll
+					for (uint32_t b = 0; b < NGRP / 4; b++) {
+						if (b * 4 < n_groups) {
+							if (b + 1 == NGRP / 4) { // (unrolled: no condition is left in the code)
+								near4(b, ax, ay);
+								break;
+							}
+							const float4 nx = gx4[b + 1], ny = gy4[b + 1];
+							near4(b, ax, ay);
+							// (pins the two loads to this block: left alone the compiler sinks them into the next block, their only
+							// user, where they are waited for at once)
+							asm volatile("" ::"v"(nx.x), "v"(nx.y), "v"(nx.z), "v"(nx.w), "v"(ny.x), "v"(ny.y), "v"(ny.z), "v"(ny.w));
+							ax = nx;
+							ay = ny;
+						} else {
+							break;
 						}
-						// d2 >= +0: unsigned order of the bits is float order; one v_min3_u32 per two groups
-						asm("v_min3_u32 %0, %1, %2, %3" : "=v"(dmin) : "v"(dmin), "v"(d2[0]), "v"(d2[1]));
-						asm("v_min3_u32 %0, %1, %2, %3" : "=v"(dmin) : "v"(dmin), "v"(d2[2]), "v"(d2[3]));
-						D2p[b * 2] = __builtin_amdgcn_perm(d2[1], d2[0], 0x07060302u);     // hi16(d2[1]) : hi16(d2[0])
-						D2p[b * 2 + 1] = __builtin_amdgcn_perm(d2[3], d2[2], 0x07060302u);
-					} // (a block past n_groups leaves its D2p unset: the second pass skips the same blocks)
+					}
 				}
 				ub2 = __uint_as_float(dmin);
 				float U = (__builtin_amdgcn_sqrtf(ub2) * INFL + pad) * INFL; // (raw v_sqrt_f32, as for the group radius: DESIGN.md §4.1)
@@ -511,15 +538,22 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					}
 					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 					__builtin_amdgcn_wave_barrier();
-					for (uint32_t base = 0; base < total; base += 64) {
-						const uint32_t idx = base + lane;
-						const uint32_t e = q_pair[wv][min(idx, total - 1)]; // (a lane past the end takes the last pair and drops its result)
+					// The entry of the round after this one is read before this round's filters: a round then waits for the
+					// pixel and the records only, not for its entry first (the first round's is read ahead of the loop; past
+					// the last round the read takes the last pair again: q_pair holds QCAP entries, total = 0 reads its own lane's).
+					// The loop runs on the NEXT round's base, the only index a round forms: its own is that minus 64.
+					uint32_t e = q_pair[wv][min(lane, total - 1)]; // (a lane past the end takes the last pair and drops its result)
+					const uint32_t total64 = total + 64;          // (total <= QCAP)
+					for (uint32_t next = 64; next < total64; next += 64) {
+						const uint32_t idx_next = next + lane;
+						const uint32_t e_next = q_pair[wv][min(idx_next, total - 1)];
 						const uint32_t src4 = e >> 16;
 						const float qx = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpx)));
 						const float qy = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpy)));
 						const uint32_t mn = group_min(0xFFFFFFFFu, e & 0xFFFFu, qx, qy);
-						if (idx < total)
+						if (idx_next < total64) // this round's index < total
 							atomicMin(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(q_min[wv]) + src4), mn);
+						e = e_next;
 					}
 					__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 					__builtin_amdgcn_wave_barrier();
