@@ -251,6 +251,26 @@ typedef struct {
 	uint64_t faces; /* the faces they were given */
 } vg_gvar_batch_stats;
 int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out);
+/* advances from gvar's phantom points, 0 (default) / 1: a `glyf` + `gvar` face placed AFTER the call — by
+ * vg_manager_add_font_instance, _normalized, vg_manager_add_font_named_instances or the named-instance scan — whose file has no
+ * readable `HVAR` takes every glyph id's advance from the deltas of phantom points n and n + 1 of its `gvar` data (rule G7 of
+ * csrc/host/ttf_face.hpp) instead of keeping `hmtx`'s.  The advance is the PBF entry's and the source of the sub-pixel shift
+ * that moves the outline, so entries and bitmaps follow.  A file with a readable `HVAR` is not touched by the switch.  NOT
+ * RETROACTIVE: stores and families are keyed by serials taken at placement, so faces placed before the call keep what they had.
+ * Everything that asks the reader for an advance follows (the host's family table, record_resident, command tables, the CPU
+ * path); nothing else differs from an `HVAR` face: named instances, ranges, mixed families, in-place PBF, lane plans, glyph
+ * sharding, gvar on the device and its batched form see only another advance.  With vg_manager_set_family_tables_on_device the
+ * faces' loca, glyf and gvar go to the device beside the variation records (vg_manager_family_gvar_desc,
+ * vgsdf_family_create_tables_gvar: the phantom pass and the emit pass there); a refusal or device error sends the font id the
+ * host's way, counted as any family-table fallback and in `fallbacks` below.  Off by default whatever a measurement says
+ * (profiles/gvar_advances_ab.txt). */
+void vg_manager_set_gvar_advances(vg_manager *m, int on);
+typedef struct {
+	uint64_t faces;         /* faces placed so far whose advances follow G7 */
+	uint64_t device_builds; /* of the last render: families with such a face that the device built, the phantom pass included */
+	uint64_t fallbacks;     /* ... and those it refused, whose tables came from the host reader instead */
+} vg_gvar_advance_stats;
+int vg_manager_gvar_advance_stats(const vg_manager *m, vg_gvar_advance_stats *out);
 /* ... batched, 0 (default) / 1; has an effect only with vg_manager_set_glyf_tables_on_device: the glyf fonts of ALL files of a
  * font id that the device has yet to build are built in one call (vgsdf_fonts_create_tables: one count launch, one read-back, one
  * emit launch) instead of one call per file, so what a call costs beside its two passes is paid once per font id.  Same fonts,
@@ -274,7 +294,8 @@ int vg_manager_add_font_data(vg_manager *m, const char *name, const uint8_t *dat
  * values are normalised in f32 (clamped to the axis, (v - def) / (def - min) or / (max - def), times 16384, truncated) and sent
  * through the file's `avar` (version 1.0).  CFF2 outlines are drawn at the position, `glyf` outlines are moved by `gvar` (tuple
  * scalars, deltas, inferred points, component offsets: the rules G1 to G6 of csrc/host/ttf_face.hpp) and advances follow `HVAR`
- * (without `HVAR` the `hmtx` advance stands: advances from gvar's phantom points are not read).  A placed `glyf` face is a command
+ * (without `HVAR` the `hmtx` advance stands, or, for a `glyf` face placed after vg_manager_set_gvar_advances(m, 1), the
+ * advance follows gvar's phantom points: rule G7 there).  A placed `glyf` face is a command
  * face for every form: vg_manager_record_glyf_parts, _resident_font_desc and _font_tables_desc refuse it.  Everything that
  * describes the file afterwards (vg_manager_charstring2_font_desc, _command_font_desc, _family_desc ...) describes it there.
  * Several instances of one file under different names are several font ids; the same name merges them into one font id like
@@ -318,9 +339,15 @@ void vg_manager_set_scan_named_instances(vg_manager *m, int on);
 /* test / inspection of a file the manager holds.  _font_position: the number of normalised coordinates file `file_index` of the
  * font id was placed at (0: it was not added at a position), and the first `cap` of them in coords (may be NULL).
  * _font_hor_advances: the file's numGlyphs, and in advances[0 .. cap) the reader's advance of every glyph id in font units
- * (hmtx, plus HVAR for a file at a position; 0 for "none" and for ids at and past numGlyphs).  -1: unknown font / file. */
+ * (hmtx, plus HVAR — or, for a face that follows G7, gvar's phantom points — for a file at a position; 0 for "none" and for ids
+ * at and past numGlyphs).  -1: unknown font / file.
+ * _font_gvar_advance_deltas: rule G7 for every glyph id of a `glyf` face placed by `gvar`, WHETHER OR NOT its advances follow it
+ * (the switch and an HVAR are not looked at): the file's numGlyphs, and for ids 0 .. cap - 1 the f32 d = r - l in delta[] and
+ * in state[] 0 (no variation data, d = 0), 1 (delta) or 2 (malformed: d = 0, hmtx stands) — what vgsdf_gvar_advance_deltas
+ * is held to, bit for bit.  -1 as well: not a face placed by gvar. */
 int vg_manager_font_position(const vg_manager *m, const char *font_id, int file_index, int16_t *coords, int cap);
 int vg_manager_font_hor_advances(const vg_manager *m, const char *font_id, int file_index, uint16_t *advances, int cap);
+int vg_manager_font_gvar_advance_deltas(const vg_manager *m, const char *font_id, int file_index, float *delta, uint8_t *state, int cap);
 int vg_font_variation_axes(const uint8_t *data, size_t len, char (*tags)[4], float *min, float *def, float *max, int cap);
 int vg_font_named_instances(const uint8_t *data, size_t len, uint16_t *name_id, float *coords, int cap_instances, int n_axes);
 /* manager.rs:39-53: the file's name table decides the font id (family/width/weight/style ->
@@ -510,6 +537,11 @@ int vg_manager_font_tables_desc(const vg_manager *m, const char *font_id, int fi
 /* The same of a `glyf` face placed by `gvar` for vgsdf_font_create_gvar: views of its loca, glyf and gvar and of its normalised
  * coordinates, alive as long as the manager holds the file.  -1 for every other face. */
 int vg_manager_gvar_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_gvar_desc *desc);
+/* Beside vg_manager_family_variation_desc: what vgsdf_family_create_tables_gvar takes for file `file_index` of the font id — the
+ * description above when the face's advances follow gvar's phantom points (placed with vg_manager_set_gvar_advances on, glyf +
+ * gvar, no readable HVAR), all zero (gvar NULL: hand the call a NULL for this face) for every other face.  -1: unknown font /
+ * file. */
+int vg_manager_family_gvar_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_gvar_desc *desc);
 
 /* Hand-encoder of the glyphs PBF (src/protobuf/glyphs.rs:66-70) for already rendered
  * glyphs; bitmaps[i] may be NULL when !has_bitmap. Returns needed size. */

@@ -561,6 +561,27 @@ int vgsdf_fonts_create_gvar_within(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *
 /* test / inspection (tools/gvar_batch_ab.py): the count, the deltas and the emit pass of the context's last vgsdf_fonts_create_gvar */
 void vgsdf_fonts_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3]);
 /*
+ * The PHANTOM PASS (csrc/gvar_advance_kernels.hip): what the advances of a placed `glyf` face whose file has no `HVAR` take from
+ * `gvar`, rule G7 of csrc/host/ttf_face.hpp, computed on the device from the description vgsdf_font_create_gvar takes.  One lane
+ * per glyph id, one pass, no scratch: the lane reads the point count n of its glyph id's OWN entry (a simple entry's last end
+ * point + 1, a composite's component records, 0 for a glyph id without an entry or with an entry of no contours) and streams the
+ * glyph id's tuples, taking from every applied one the x deltas of the phantom points n (l) and n + 1 (r) — += f32(delta) *
+ * scalar each, in tuple order — while walking its point numbers and all 2 x count of its deltas to their end.  delta[g] = r - l
+ * in f32, and state[g]: 0, no variation data (a glyph id at or past glyphCount, an empty range, tuple count 0; delta 0);
+ * 1, a delta; 2, malformed — the entry (its count cannot be read) or the data, by the meaning the outline's rules G1 to G5 give
+ * the word at that position (delta 0: the `hmtx` advance stands).  Both arrays hold tables.num_glyphs elements and equal, bit for
+ * bit, what the host reader gives (vg_manager_font_gvar_advance_deltas of vgfont.h).  Every read is bounded by loca_entries,
+ * n_glyf_bytes and gvar_len.  Test / inspection: the pass alone, read back.  Synchronous; nothing stays allocated.
+ * Validated on the host as vgsdf_font_create_gvar validates its description (VGSDF_E_ARG).  Refused with VGSDF_E_GLYF, delta and
+ * state untouched, the context sound: a glyph id of more than VGSDF_GVAR_MAX_DELTAS tuples x (n + 4), whatever the scalars —
+ * refused by the count, its tuples are not walked.
+ */
+int vgsdf_gvar_advance_deltas(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in, float *delta /* [num_glyphs] */, uint8_t *state /* [num_glyphs] */);
+/* test / inspection (tools/gvar_advances_ab.py): milliseconds the phantom pass of the context's last vgsdf_gvar_advance_deltas or
+ * vgsdf_family_create_tables_gvar took (HIP events around the pass, summed over the faces it ran for; 0 before the first, and
+ * when it did not run) */
+float vgsdf_gvar_advance_kernel_ms(const vgsdf_ctx *ctx);
+/*
  * Resident families: the table code point -> (font, glyph id, advance, scale, shift_x) of a font id lives on the device
  * beside its fonts, and a submission names CODE-POINT RANGES of families instead of glyphs.  The host's share per submission
  * is O(tasks): the block it uploads holds 32 bytes per task that maps a glyph, per family and per font, and no per-glyph byte.
@@ -655,6 +676,26 @@ int vgsdf_family_create_tables_var(vgsdf_ctx *ctx, const vgsdf_family_tables_des
                                    vgsdf_family **out);
 int vgsdf_family_create_tables_var_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var,
                                          vgsdf_family **out);
+/*
+ * The same with placed `glyf` faces whose file has NO `HVAR` and whose advances follow gvar's phantom points instead (rule G7 of
+ * csrc/host/ttf_face.hpp; vg_manager_set_gvar_advances of vgfont.h): gvar is [n_fonts] pointers, gvar[k] the description
+ * vgsdf_font_create_gvar takes of face k (vg_manager_family_gvar_desc states it), or NULL for a face that takes nothing from
+ * gvar.  gvar NULL: the call is vgsdf_family_create_tables_var.  For face k with gvar[k] and without var[k].hvar (var may be NULL)
+ * the call uploads the three tables and runs the PHANTOM PASS (vgsdf_gvar_advance_deltas above: the same pass) into an array the
+ * CONTEXT owns (5 bytes per glyph id; grown on demand, freed with the context, counted by no family); where the emit pass has a
+ * glyph's `hmtx` advance of such a face it adds, unless the glyph id's state is "malformed" or the glyph id lies at or past the
+ * description's num_glyphs, the pass's delta where the `HVAR` form adds HVAR's:  advance = trunc((f32)hmtx advance + (delta +
+ * 0.5)), 0 when that leaves 0 .. 65535.  A face with both descriptions uses its HVAR, as the host's reader does; its gvar
+ * description is validated and otherwise not looked at.  Validated on the host in addition (VGSDF_E_ARG): every gvar[k] as
+ * vgsdf_font_create_gvar validates its description.  Refused with VGSDF_E_GLYF, nothing left allocated, the context sound: a
+ * glyph id past VGSDF_GVAR_MAX_DELTAS (tuples x (points + 4)) in a face the pass runs over.  The count pass and everything else
+ * are vgsdf_family_create_tables'; the family is indistinguishable from one vgsdf_family_create makes of the same entries with
+ * the reader's advances.  Existing structs and entry points are as they were.
+ */
+int vgsdf_family_create_tables_gvar(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var /* [n_fonts] or NULL */,
+                                    const vgsdf_font_gvar_desc *const *gvar /* [n_fonts] or NULL */, vgsdf_family **out);
+int vgsdf_family_create_tables_gvar_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var,
+                                          const vgsdf_font_gvar_desc *const *gvar, vgsdf_family **out);
 /* test / inspection: download the DEVICE's copy of a family's table, whichever call made it; *n_entries: its entries; code_point,
  * font_of, glyph_id, advance, scale, shift_x, pbf_fix [n_entries], cmd_pre, leaf_pre [n_entries + 1] (mod 2^32): each NULL or filled */
 int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_entries, uint16_t *code_point, uint16_t *font_of,

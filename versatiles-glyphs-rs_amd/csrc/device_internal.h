@@ -76,6 +76,11 @@ struct vgsdf_ctx {
 	float glyf_batch_ms[2] = {0.0f, 0.0f};    // the same of the last vgsdf_fonts_create_tables: one launch each over all its faces
 	float gvar_ms[3] = {0.0f, 0.0f, 0.0f};    // count / deltas / emit kernels of the last vgsdf_font_create_gvar (resident_gvar.cpp)
 	float gvar_batch_ms[3] = {0.0f, 0.0f, 0.0f}; // the same of the last vgsdf_fonts_create_gvar: one face at all its positions
+	// the phantom pass (all its launches) of the last vgsdf_gvar_advance_deltas or vgsdf_family_create_tables_gvar (resident_gvar.cpp)
+	float gvar_advance_ms = 0.0f;
+	// vgsdf_family_create_tables_gvar: the phantom pass's output for the call's faces, read by its emit pass; grown on demand,
+	// belongs to no family (the call ends with a synchronisation)
+	DevBuf gvar_advance;
 	// vgsdf_font_create_gvar, vgsdf_fonts_create_gvar: the deltas pass's scratch for one launch (GvarScratch: 13 bytes per point of
 	// at most 2^17 points — points x positions in the batched call —, or of one glyph id at one position); grown on demand, belongs
 	// to no font

@@ -29,6 +29,16 @@ struct FamilyFaceVar {
 	uint32_t hvar_len, store_off, map_off, n_regions; // map_off 0: no advance map
 };
 static_assert(sizeof(FamilyFaceVar) == 32, "one 32-byte record per face");
+// what a placed `glyf` face WITHOUT an `HVAR` adds instead (rule G7 of host/ttf_face.hpp), in a second array beside the faces'
+// records: the output of the phantom pass (gvar_advance_kernels.h) over the face, one f32 delta and one state byte per glyph id.
+// Read for a face whose FamilyFaceVar has no hvar, by glyph ids below n_glyph_ids only.
+struct FamilyFaceGvar {
+	uint64_t delta;       // f32[n_glyph_ids]; 0: the face takes no delta from gvar
+	uint64_t state;       // u8[n_glyph_ids]: GVAR_ADVANCE_NONE / _DELTA / _MALFORMED
+	uint32_t n_glyph_ids; // of the description the pass ran over
+	uint32_t pad;
+};
+static_assert(sizeof(FamilyFaceGvar) == 24, "one 24-byte record per face");
 struct FamilySubtable {
 	uint32_t off, format; // into cmap; 0 4 6 10 12 13
 };
@@ -54,4 +64,7 @@ int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces
 // the emit pass over faces some of which are at a position: var[n_faces] beside faces
 int vgsdf_family_tables_emit_var(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, uint32_t n_faces, const uint32_t *counts,
                                  uint32_t n_entries, uint8_t *table, hipStream_t stream);
+// ... and some of which take their advance's delta from gvar's phantom points: gvar[n_faces] beside var[n_faces]
+int vgsdf_family_tables_emit_gvar(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, const vgsdf::FamilyFaceGvar *gvar,
+                                  uint32_t n_faces, const uint32_t *counts, uint32_t n_entries, uint8_t *table, hipStream_t stream);
 }

@@ -6,7 +6,8 @@
 // -ffp-contract=off).  The lookups are CmapSubtable::glyph_index's bisections; every read is bounded by the table lengths of the
 // face record.  Two passes of one text: the count pass leaves per workgroup its entries, command slots and leaves, the emit pass
 // places every entry at its rank and writes all nine arrays of FamilyTableLayout.  A third instantiation of that text, the emit
-// pass with VAR, adds to the `hmtx` advance of a face at a position what Face::hvar_advance_delta finds in the face's `HVAR`.
+// pass with VAR, adds to the `hmtx` advance of a face at a position what Face::hvar_advance_delta finds in the face's `HVAR`; a
+// fourth, VAR with a second record array, adds for a face without `HVAR` what the phantom pass found in its `gvar` (rule G7).
 #include "family_table_kernels.h"
 
 #include "upload_layout.h"
@@ -269,13 +270,18 @@ __device__ bool hvar_delta(const FamilyFaceVar &V, uint32_t gid, float &delta)
 	return true;
 }
 
-// VAR: the emit pass over faces some of which are at a position; its one further argument, `const FamilyFaceVar *`, is a pack so
-// that the instantiations without it keep the arguments (and with them the kernel descriptor) they have always had
+// the first and the second of a pack's elements
+template <class A, class... R> __device__ inline A first_of(A a, R...) { return a; }
+template <class A, class B> __device__ inline B second_of(A, B b) { return b; }
+
+// VAR: the emit pass over faces some of which are at a position; its further arguments, `const FamilyFaceVar *` and, for faces
+// whose advances follow gvar's phantom points, `const FamilyFaceGvar *` behind it, are a pack so that the instantiations without
+// them keep the arguments (and with them the kernel descriptor and the name) they have always had
 template <bool EMIT, bool VAR = false, class... Var>
 __global__ __launch_bounds__(kFamilyThreads) void family_tables_pass(const FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts,
                                                                        uint32_t *flags, uint32_t n_entries, uint8_t *table, Var... var)
 {
-	static_assert(sizeof...(Var) == (VAR ? 1 : 0), "the variation records come with VAR and only with it");
+	static_assert(VAR ? sizeof...(Var) == 1 || sizeof...(Var) == 2 : sizeof...(Var) == 0, "the variation records come with VAR and only with it");
 	__shared__ uint32_t lds_base[kFamilyThreads / 64][3], lds_wave[kFamilyThreads / 64][3];
 	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = blockIdx.x * kFamilyThreads + tid;
 	const Entry e = find_entry(faces, n_faces, c);
@@ -334,9 +340,17 @@ __global__ __launch_bounds__(kFamilyThreads) void family_tables_pass(const Famil
 		const uint32_t i = e.gid < (uint32_t)F.num_hmetrics - 1u ? e.gid : (uint32_t)F.num_hmetrics - 1u;
 		adv = be16((const uint8_t *)(uintptr_t)F.hmtx + (size_t)i * 4);
 		if constexpr (VAR) { // Face::glyph_hor_advance of a face at a position: f32, `+ 0.5`, truncated; outside u16: none
-			const FamilyFaceVar &V = (var, ...)[e.face]; // (the pack's one element)
+			const FamilyFaceVar &V = first_of(var...)[e.face];
 			float delta;
-			if (V.hvar != 0 && hvar_delta(V, e.gid, delta)) {
+			bool moved = V.hvar != 0 && hvar_delta(V, e.gid, delta);
+			if constexpr (sizeof...(Var) == 2) { // G7: a face without HVAR whose record names the phantom pass's output
+				const FamilyFaceGvar &G = second_of(var...)[e.face];
+				if (V.hvar == 0 && G.delta != 0 && e.gid < G.n_glyph_ids && ((const uint8_t *)(uintptr_t)G.state)[e.gid] != 2u) {
+					delta = ((const float *)(uintptr_t)G.delta)[e.gid];
+					moved = true;
+				}
+			}
+			if (moved) {
 				const float a = (float)adv + (delta + 0.5f);
 				adv = a > -1.0f && a < 65536.0f ? (uint32_t)(int32_t)a : 0u;
 			}
@@ -382,6 +396,14 @@ int vgsdf_family_tables_emit_var(const vgsdf::FamilyFaceRef *faces, const vgsdf:
 {
 	hipLaunchKernelGGL((vgsdf::family_tables_pass<true, true>), dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces,
 	                   n_faces, const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, var);
+	return (int)hipGetLastError();
+}
+
+int vgsdf_family_tables_emit_gvar(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, const vgsdf::FamilyFaceGvar *gvar,
+                                  uint32_t n_faces, const uint32_t *counts, uint32_t n_entries, uint8_t *table, hipStream_t stream)
+{
+	hipLaunchKernelGGL((vgsdf::family_tables_pass<true, true>), dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces,
+	                   n_faces, const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, var, gvar);
 	return (int)hipGetLastError();
 }
 

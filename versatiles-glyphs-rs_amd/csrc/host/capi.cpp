@@ -289,6 +289,13 @@ int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out)
 	*out = vg_gvar_batch_stats{t.gvar_batch_calls, t.gvar_batch_faces};
 	return 0;
 }
+void vg_manager_set_gvar_advances(vg_manager *m, int on) { m->m.set_gvar_advances(on != 0); }
+int vg_manager_gvar_advance_stats(const vg_manager *m, vg_gvar_advance_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_gvar_advance_stats{m->m.gvar_advance_faces(), t.gvar_advance_builds, t.gvar_advance_fallbacks};
+	return 0;
+}
 namespace {
 // file `file_index` of a font id (nullptr and g_err: none)
 const vg::Face *face_of(const vg_manager *m, const char *font_id, int file_index, const char *me)
@@ -329,6 +336,27 @@ int vg_manager_font_hor_advances(const vg_manager *m, const char *font_id, int f
 		if (advances && cap > 0) {
 			const std::vector<uint16_t> a = f->hor_advances((uint32_t)cap);
 			std::copy(a.begin(), a.end(), advances);
+		}
+		return (int)f->number_of_glyphs();
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+int vg_manager_font_gvar_advance_deltas(const vg_manager *m, const char *font_id, int file_index, float *delta, uint8_t *state, int cap)
+{
+	try {
+		const vg::Face *f = face_of(m, font_id, file_index, "vg_manager_font_gvar_advance_deltas");
+		if (!f)
+			return -1;
+		if (!f->placed_by_gvar())
+			return fail(std::string("refused: font ") + font_id + ": not a glyf face placed by gvar");
+		for (int g = 0; g < cap && g <= 0xFFFF; g++) {
+			float d = 0.0f;
+			const uint8_t s = f->gvar_advance_delta((uint16_t)g, d);
+			if (delta)
+				delta[g] = d;
+			if (state)
+				state[g] = s;
 		}
 		return (int)f->number_of_glyphs();
 	} catch (const std::exception &e) {
@@ -1093,6 +1121,24 @@ int vg_manager_gvar_font_desc(const vg_manager *m, const char *font_id, int file
 		desc->tables.loca = t.tables.loca, desc->tables.glyf = t.tables.glyf;
 		desc->gvar = t.gvar, desc->gvar_len = t.gvar_len, desc->n_axes = t.n_axes, desc->coords = t.coords;
 		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_family_gvar_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_gvar_desc *desc)
+{
+	try {
+		const vg::Face *f = desc ? face_of(m, font_id, file_index, "vg_manager_family_gvar_desc") : nullptr;
+		if (!f) {
+			if (!desc)
+				g_err = "vg_manager_family_gvar_desc: bad argument";
+			return -1;
+		}
+		*desc = vgsdf_font_gvar_desc{};
+		if (!f->advances_by_gvar())
+			return 0; // (all zero: the face takes nothing from gvar)
+		return vg_manager_gvar_font_desc(m, font_id, file_index, desc);
 	} catch (const std::exception &e) {
 		g_err = e.what();
 		return -1;

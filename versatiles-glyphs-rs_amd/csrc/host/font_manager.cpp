@@ -62,18 +62,18 @@ std::string name_to_id(const std::string &name)
 	return out;
 }
 
-std::unique_ptr<FontFileEntry> FontFileEntry::create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords)
+std::unique_ptr<FontFileEntry> FontFileEntry::create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords, bool gvar_advances)
 {
-	return create(std::make_shared<const std::vector<uint8_t>>(std::move(data)), err, coords, nullptr);
+	return create(std::make_shared<const std::vector<uint8_t>>(std::move(data)), err, coords, nullptr, gvar_advances);
 }
 
 std::unique_ptr<FontFileEntry> FontFileEntry::create(std::shared_ptr<const std::vector<uint8_t>> data, std::string *err,
-                                                     const std::vector<int16_t> *coords, const std::string *ps_name)
+                                                     const std::vector<int16_t> *coords, const std::string *ps_name, bool gvar_advances)
 {
 	std::unique_ptr<FontFileEntry> e(new FontFileEntry());
 	e->data_ = std::move(data);
 	std::string why = "font parse failed";
-	auto face = coords ? Face::parse_at(e->data_->data(), e->data_->size(), *coords, &why) : Face::parse(e->data_->data(), e->data_->size());
+	auto face = coords ? Face::parse_at(e->data_->data(), e->data_->size(), *coords, &why, gvar_advances) : Face::parse(e->data_->data(), e->data_->size());
 	if (!face) {
 		if (err)
 			*err = why;
@@ -223,9 +223,10 @@ bool FontManager::add_font_data(const std::string &name, std::vector<uint8_t> da
 bool FontManager::add_font_instance_normalized(const std::string &name, std::vector<uint8_t> data, const std::vector<int16_t> &coords,
                                                std::string *err)
 {
-	auto e = FontFileEntry::create(std::move(data), err, &coords);
+	auto e = FontFileEntry::create(std::move(data), err, &coords, gvar_advances_);
 	if (!e)
 		return false;
+	gvar_advance_faces_ += e->face().advances_by_gvar();
 	invalidate_shards();
 	fonts_[name_to_id(name)].add_file(std::move(e));
 	return true;
@@ -292,7 +293,7 @@ bool FontManager::add_font_named_instances(std::vector<uint8_t> data, std::vecto
 		for (size_t i = 0; i < axes.size(); i++)
 			coords[i] = normalize_axis_value(axes[i], instances[k].coords[i]);
 		apply_avar(bytes->data(), bytes->size(), coords);
-		auto e = FontFileEntry::create(bytes, err, &coords, &ps_names[k]);
+		auto e = FontFileEntry::create(bytes, err, &coords, &ps_names[k], gvar_advances_);
 		if (!e)
 			return false;
 		entries.push_back(std::move(e));
@@ -300,6 +301,7 @@ bool FontManager::add_font_named_instances(std::vector<uint8_t> data, std::vecto
 	invalidate_shards();
 	ids.clear();
 	for (auto &e : entries) {
+		gvar_advance_faces_ += e->face().advances_by_gvar();
 		if (e->face().placed_by_gvar())
 			gvar_groups_[e->face().gvar_tables().gvar].push_back(&e->face());
 		ids.push_back(name_to_id(e->metadata().generate_name()));

@@ -57,11 +57,13 @@ struct Writer {
 class FontFileEntry {
 public:
 	// coords: the face at that position (Face::parse_at) instead of as parsed
-	static std::unique_ptr<FontFileEntry> create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords = nullptr);
+	// (gvar_advances: Face::parse_at's — a placed glyf face without HVAR takes its advances from gvar's phantom points)
+	static std::unique_ptr<FontFileEntry> create(std::vector<uint8_t> data, std::string *err, const std::vector<int16_t> *coords = nullptr,
+	                                             bool gvar_advances = false);
 	// the same over bytes that several entries share (the named instances of one file); ps_name: the PostScript name the metadata
 	// is parsed from instead of the file's name id 6
 	static std::unique_ptr<FontFileEntry> create(std::shared_ptr<const std::vector<uint8_t>> data, std::string *err,
-	                                             const std::vector<int16_t> *coords, const std::string *ps_name);
+	                                             const std::vector<int16_t> *coords, const std::string *ps_name, bool gvar_advances = false);
 	const Face &face() const { return face_; }
 	const std::vector<uint32_t> &codepoints() const { return codepoints_; } // metadata.rs:105-119
 	const FontMetadata &metadata() const { return metadata_; }                // metadata.rs:89-103
@@ -179,6 +181,10 @@ struct RenderTimings {
 	uint64_t gvar_fonts_built = 0, gvar_font_bytes = 0, gvar_fallbacks = 0;
 	// ... and, with set_gvar_batched, the calls that built them (one per group of faces over the same bytes) and the faces sent
 	uint64_t gvar_batch_calls = 0, gvar_batch_faces = 0;
+	// families with a face whose advances follow gvar's phantom points (set_gvar_advances) that the device built, the phantom pass
+	// included (set_family_tables_on_device; counted among family_tables_built too), and those it refused, whose tables came from
+	// the host reader instead (counted among family_table_fallbacks too)
+	uint64_t gvar_advance_builds = 0, gvar_advance_fallbacks = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -212,10 +218,11 @@ struct RenderTimings {
 		glyf_table_batch_calls += counts.glyf_table_batch_calls, glyf_table_batch_faces += counts.glyf_table_batch_faces;
 		gvar_fonts_built += counts.gvar_fonts_built, gvar_font_bytes += counts.gvar_font_bytes, gvar_fallbacks += counts.gvar_fallbacks;
 		gvar_batch_calls += counts.gvar_batch_calls, gvar_batch_faces += counts.gvar_batch_faces;
+		gvar_advance_builds += counts.gvar_advance_builds, gvar_advance_fallbacks += counts.gvar_advance_fallbacks;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 41 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 43 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -353,6 +360,12 @@ public:
 	// with set_gvar_on_device: the stores of ALL placed glyf faces over the same bytes (add_font_named_instances) that the lane's
 	// device has yet to build, in one call when the first of them is asked for (Renderer::gvar_fonts)
 	void set_gvar_batched(bool on) { gvar_batched_ = on; }
+	// faces placed from now on (add_font_instance, _normalized, add_font_named_instances and the named-instance scan) that are
+	// glyf + gvar without a readable HVAR take their advances from gvar's phantom points (rule G7 of ttf_face.hpp; default off:
+	// their hmtx advances stand).  Not retroactive: stores and families are keyed by serials taken at placement.
+	void set_gvar_advances(bool on) { gvar_advances_ = on; }
+	// the faces placed so far whose advances follow G7
+	uint64_t gvar_advance_faces() const { return gvar_advance_faces_; }
 	// with set_glyf_tables_on_device: the glyf fonts of a font id's files built in one call (Renderer::fonts_from_tables)
 	void set_glyf_tables_batched(bool on) { glyf_tables_batched_ = on; }
 	// uploads every face of the manager that has a resident form now (through lane 0 of every device lane of the renderer);
@@ -620,6 +633,8 @@ private:
 	bool gvar_on_device_ = false;
 	bool glyf_tables_batched_ = false;
 	bool gvar_batched_ = false, scan_named_instances_ = false;
+	bool gvar_advances_ = false;
+	uint64_t gvar_advance_faces_ = 0;
 	// the placed glyf faces that share their bytes, by the address of their gvar table (the faces of add_font_named_instances; a
 	// child manager reads its parent's); a group of one makes no batched call
 	std::map<const uint8_t *, std::vector<const Face *>> gvar_groups_;

@@ -459,6 +459,10 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 		FamilyTable *shell = family_shell(font_id, font.files().size());
 		std::vector<vgsdf_face_tables> descs;
 		std::vector<vgsdf_face_variation> variation; // filled once a face at a position with an HVAR is met
+		// the faces whose advances follow gvar's phantom points (Face::advances_by_gvar): their tables beside `variation`
+		std::vector<vgsdf_font_gvar_desc> gvar_descs;
+		std::vector<const vgsdf_font_gvar_desc *> gvar;
+		gvar_descs.reserve(font.files().size());
 		for (const auto &file : font.files()) {
 			const FamilyTables &t = file->face().family_tables();
 			if (!t.ok) {
@@ -478,16 +482,32 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 				variation.resize(descs.size(), vgsdf_face_variation{nullptr, 0, 0, 0, nullptr, 0});
 				variation.back() = vgsdf_face_variation{t.hvar, t.hvar_len, t.hvar_store, t.hvar_map, t.region_scalars.data(), (uint32_t)t.region_scalars.size()};
 			}
+			const GvarTables g = file->face().advances_by_gvar() ? file->face().gvar_tables() : GvarTables{};
+			if (g.ok || !gvar.empty()) {
+				gvar.resize(descs.size(), nullptr);
+				if (g.ok) {
+					vgsdf_font_gvar_desc gd{};
+					gd.tables.num_glyphs = g.tables.num_glyphs, gd.tables.loca_entries = g.tables.loca_entries, gd.tables.loca_long = g.tables.loca_long;
+					gd.tables.n_loca_bytes = g.tables.n_loca_bytes, gd.tables.n_glyf_bytes = g.tables.n_glyf_bytes;
+					gd.tables.loca = g.tables.loca, gd.tables.glyf = g.tables.glyf;
+					gd.gvar = g.gvar, gd.gvar_len = g.gvar_len, gd.n_axes = g.n_axes, gd.coords = g.coords;
+					gvar_descs.push_back(gd);
+					gvar.back() = &gvar_descs.back();
+				}
+			}
 		}
 		if (descs.size() == font.files().size()) {
 			int refused = 0;
 			bool built = false;
-			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, family_kind, &uploaded, &refused, &built, variation);
-			if (refused == 1)
+			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, family_kind, &uploaded, &refused, &built, variation, gvar);
+			if (refused == 1) {
 				counts.family_table_fallbacks++;
+				counts.gvar_advance_fallbacks += !gvar_descs.empty();
+			}
 			if (built) {
 				count_upload(uploaded, counts.families_uploaded, counts.family_bytes);
 				counts.family_tables_built++;
+				counts.gvar_advance_builds += !gvar_descs.empty();
 			}
 			if (fam) {
 				std::lock_guard<std::mutex> lock(family_mu_of());

@@ -28,6 +28,11 @@ public:
 	// G1 to G5 for one entry: acc (2 floats per point, x then y, the phantom points included: 2 * (pts.n + 4)) is set to the
 	// sums of the glyph id's tuples at coords (as many as the table has axes).  false: malformed data — acc is not to be used.
 	bool accumulate(uint16_t glyph_id, const std::vector<int16_t> &coords, const GvarPoints &pts, std::vector<float> &acc) const;
+	// G7 for one entry of n points: l and r, the sums of the x deltas of points n and n + 1 over the glyph id's tuples at coords,
+	// streamed (no per-point storage; every applied tuple's numbers and deltas are walked to their end, so that malformed means
+	// what it means to accumulate).  Face::kGvarAdvanceNone: no variation data (l = r = 0), kGvarAdvanceDelta, or
+	// kGvarAdvanceMalformed (l and r are not to be used).
+	uint8_t phantom_sums(uint16_t glyph_id, const std::vector<int16_t> &coords, uint32_t n, float &l, float &r) const;
 
 	Bytes table() const { return table_; }
 	uint32_t axis_count() const { return axis_count_; }

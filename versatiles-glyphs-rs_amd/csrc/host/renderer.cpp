@@ -760,7 +760,8 @@ const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std:
 
 const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
                                                  const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
-                                                 bool *built, const std::vector<vgsdf_face_variation> &variation) const
+                                                 bool *built, const std::vector<vgsdf_face_variation> &variation,
+                                                 const std::vector<const vgsdf_font_gvar_desc *> &gvar) const
 {
 	if (mode_ != Mode::Hip)
 		return nullptr;
@@ -782,8 +783,10 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 	{
 		std::lock_guard<std::mutex> lock(mu_);
 		const vgsdf_face_variation *var = variation.empty() ? nullptr : variation.data();
-		if (tables.size() != fonts.size() || (var && variation.size() != fonts.size()) ||
-		    (var ? (kind == kFamilyMixed ? vgsdf_family_create_tables_var_mixed(c, &d, var, &f) : vgsdf_family_create_tables_var(c, &d, var, &f))
+		if (tables.size() != fonts.size() || (var && variation.size() != fonts.size()) || (!gvar.empty() && gvar.size() != fonts.size()) ||
+		    (!gvar.empty() ? (kind == kFamilyMixed ? vgsdf_family_create_tables_gvar_mixed(c, &d, var, gvar.data(), &f)
+		                                          : vgsdf_family_create_tables_gvar(c, &d, var, gvar.data(), &f))
+		     : var ? (kind == kFamilyMixed ? vgsdf_family_create_tables_var_mixed(c, &d, var, &f) : vgsdf_family_create_tables_var(c, &d, var, &f))
 		         : (kind == kFamilyMixed ? vgsdf_family_create_tables_mixed(c, &d, &f) : vgsdf_family_create_tables(c, &d, &f))) != VGSDF_OK) {
 			rf.refused_family_tables.insert(key);
 			*refused = 1;

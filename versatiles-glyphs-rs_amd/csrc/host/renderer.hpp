@@ -533,10 +533,12 @@ public:
 	// stands for the table's), same budget, same lifetime.  *refused: the device has returned an error for this (device, serial),
 	// 1 now or 2 earlier — the caller makes the family with family() instead; *built: this call put it on the device.  nullptr
 	// without *refused: over the budget.  variation: empty (static faces only), or a record per face
-	// (vgsdf_family_create_tables_var)
+	// (vgsdf_family_create_tables_var).  gvar: empty, or per face the description of one whose advances follow gvar's phantom
+	// points, nullptr for every other (vgsdf_family_create_tables_gvar)
 	const vgsdf_family *family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
 	                                       const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
-	                                       bool *built, const std::vector<vgsdf_face_variation> &variation = {}) const;
+	                                       bool *built, const std::vector<vgsdf_face_variation> &variation = {},
+	                                       const std::vector<const vgsdf_font_gvar_desc *> &gvar = {}) const;
 	// a family's code points and advances, read back (what a host that built no table names the glyphs of a ranges group by)
 	void family_names(int lane, const vgsdf_family *family, std::vector<uint16_t> &code_point, std::vector<uint32_t> &advance) const;
 	// a submission of code-point ranges of such families (n_glyphs: for the first capacity guess), and where its tasks'

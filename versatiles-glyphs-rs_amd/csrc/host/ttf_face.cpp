@@ -62,9 +62,12 @@ Bytes find_table(Bytes file, const char tag[4])
 
 std::optional<Face> Face::parse(const uint8_t *data, size_t len) { return parse_impl(data, len, nullptr, nullptr); }
 
-std::optional<Face> Face::parse_at(const uint8_t *data, size_t len, const std::vector<int16_t> &coords, std::string *err)
+std::optional<Face> Face::parse_at(const uint8_t *data, size_t len, const std::vector<int16_t> &coords, std::string *err, bool gvar_advances)
 {
-	return parse_impl(data, len, &coords, err);
+	auto f = parse_impl(data, len, &coords, err);
+	if (f)
+		f->gvar_advances_ = gvar_advances; // (before the face is shared: G7 holds for everything built from it)
+	return f;
 }
 
 namespace {
@@ -393,8 +396,13 @@ std::optional<uint16_t> Face::glyph_hor_advance(uint16_t gid) const
 		return hmtx_.u16(i * 4);
 	// the crate's variable path: f32 throughout, `+ 0.5` for rounding, u16::try_from of the truncated value
 	float a = (float)hmtx_.u16(i * 4);
-	if (const auto delta = hvar_advance_delta(gid))
+	if (const auto delta = hvar_advance_delta(gid)) {
 		a += *delta + 0.5f;
+	} else if (advances_by_gvar()) { // G7
+		float d;
+		if (gvar_advance_delta(gid, d) != kGvarAdvanceMalformed)
+			a += d + 0.5f;
+	}
 	if (!(a > -1.0f && a < 65536.0f))
 		return std::nullopt;
 	return (uint16_t)(int32_t)a;
@@ -1008,6 +1016,179 @@ bool GvarTable::accumulate(uint16_t gid, const std::vector<int16_t> &coords, con
 	return true;
 }
 
+namespace {
+
+// G2 as a stream (G7's walk): the packed point numbers of b from p on, one after the other
+struct PointNumberStream {
+	Bytes b;
+	size_t p = 0;
+	uint32_t count = 0, got = 0, run_left = 0;
+	uint16_t number = 0;
+	bool words = false, all = false;
+	bool open(Bytes bytes, size_t at)
+	{
+		b = bytes, p = at;
+		if (!b.has(p, 1))
+			return false;
+		count = b.u8(p++);
+		if (count == 0) {
+			all = true;
+		} else if (count & 0x80u) {
+			if (!b.has(p, 1))
+				return false;
+			count = ((count & 0x7Fu) << 8) | b.u8(p++);
+		}
+		return true;
+	}
+	bool next(uint16_t &out)
+	{
+		if (run_left == 0) {
+			if (!b.has(p, 1))
+				return false;
+			const uint8_t control = b.u8(p++);
+			words = (control & 0x80) != 0;
+			run_left = (control & 0x7Fu) + 1;
+		}
+		if (!b.has(p, words ? 2 : 1))
+			return false;
+		const uint16_t step = words ? b.u16(p) : b.u8(p);
+		p += words ? 2 : 1;
+		const uint16_t following = (uint16_t)(number + step);
+		if (got && following <= number)
+			return false;
+		number = out = following;
+		got++, run_left--;
+		return true;
+	}
+};
+// the numbers at b[p...] are well formed; all: they stand for every point; end: the first byte behind them
+bool check_point_numbers(Bytes b, size_t p, bool &all, size_t &end)
+{
+	PointNumberStream s;
+	if (!s.open(b, p))
+		return false;
+	uint16_t number;
+	while (s.got < s.count)
+		if (!s.next(number))
+			return false;
+	all = s.all, end = s.p;
+	return true;
+}
+
+} // namespace
+
+uint8_t GvarTable::phantom_sums(uint16_t gid, const std::vector<int16_t> &coords, uint32_t n, float &l, float &r) const
+{
+	l = r = 0.0f;
+	if (gid >= glyph_count_ || coords.size() != axis_count_)
+		return Face::kGvarAdvanceNone;
+	// G1
+	size_t from, to;
+	if (long_offsets_)
+		from = table_.u32(20 + (size_t)gid * 4), to = table_.u32(24 + (size_t)gid * 4);
+	else
+		from = (size_t)table_.u16(20 + (size_t)gid * 2) * 2, to = (size_t)table_.u16(22 + (size_t)gid * 2) * 2;
+	if (from == to)
+		return Face::kGvarAdvanceNone;
+	if (from > to || !table_.has(data_at_, to))
+		return Face::kGvarAdvanceMalformed;
+	const Bytes d = table_.sub(data_at_ + from, to - from);
+	if (!d.has(0, 4))
+		return Face::kGvarAdvanceMalformed;
+	const uint32_t n_tuples = d.u16(0) & 0x0FFFu;
+	const bool have_shared = (d.u16(0) & 0x8000u) != 0;
+	if (n_tuples == 0)
+		return Face::kGvarAdvanceNone;
+	size_t cursor = d.u16(2);
+	if (cursor > d.size())
+		return Face::kGvarAdvanceMalformed;
+	bool shared_all = true;
+	size_t shared_at = 0;
+	if (have_shared) {
+		shared_at = cursor;
+		if (!check_point_numbers(d, shared_at, shared_all, cursor))
+			return Face::kGvarAdvanceMalformed;
+	}
+	size_t h = 4;
+	const size_t tuple_bytes = (size_t)axis_count_ * 2;
+	for (uint32_t t = 0; t < n_tuples; t++) {
+		if (!d.has(h, 4))
+			return Face::kGvarAdvanceMalformed;
+		const size_t size = d.u16(h);
+		const uint32_t index = d.u16(h + 2);
+		h += 4;
+		Bytes peak, start, end;
+		if (index & 0x8000u) {
+			if (!d.has(h, tuple_bytes))
+				return Face::kGvarAdvanceMalformed;
+			peak = d.sub(h, tuple_bytes);
+			h += tuple_bytes;
+		} else {
+			if ((index & 0x0FFFu) >= shared_count_)
+				return Face::kGvarAdvanceMalformed;
+			peak = table_.sub(shared_at_ + (size_t)(index & 0x0FFFu) * tuple_bytes, tuple_bytes);
+		}
+		if (index & 0x4000u) {
+			if (!d.has(h, 2 * tuple_bytes))
+				return Face::kGvarAdvanceMalformed;
+			start = d.sub(h, tuple_bytes), end = d.sub(h + tuple_bytes, tuple_bytes);
+			h += 2 * tuple_bytes;
+		}
+		if (!d.has(cursor, size))
+			return Face::kGvarAdvanceMalformed;
+		const Bytes data = d.sub(cursor, size);
+		cursor += size;
+		// G4
+		float scalar = 1.0f;
+		for (uint32_t i = 0; i < axis_count_ && scalar != 0.0f; i++) {
+			const int16_t pk = peak.i16((size_t)i * 2);
+			const int16_t st = start.empty() ? std::min<int16_t>(pk, 0) : start.i16((size_t)i * 2);
+			const int16_t en = end.empty() ? std::max<int16_t>(pk, 0) : end.i16((size_t)i * 2);
+			const float f = axis_factor(coords[i], st, pk, en);
+			scalar = f == 0.0f ? 0.0f : scalar * f;
+		}
+		if (scalar == 0.0f)
+			continue;
+		// the tuple's point numbers: its own (in its data, the deltas behind them) or the shared ones
+		Bytes numbers_in = d;
+		size_t numbers_at = shared_at, deltas_at = 0;
+		bool all = shared_all;
+		if (index & 0x2000u) {
+			numbers_in = data, numbers_at = 0;
+			if (!check_point_numbers(data, 0, all, deltas_at))
+				return Face::kGvarAdvanceMalformed;
+		}
+		DeltaStream deltas{data, deltas_at};
+		int32_t v;
+		if (all) {
+			for (uint32_t i = 0; i < 2 * (n + 4); i++) { // the x deltas first
+				if (!deltas.next(v))
+					return Face::kGvarAdvanceMalformed;
+				if (i == n)
+					l += (float)v * scalar;
+				else if (i == n + 1)
+					r += (float)v * scalar;
+			}
+			continue;
+		}
+		PointNumberStream numbers;
+		(void)numbers.open(numbers_in, numbers_at); // (checked above)
+		while (numbers.got < numbers.count) {
+			uint16_t number = 0;
+			if (!numbers.next(number) || !deltas.next(v))
+				return Face::kGvarAdvanceMalformed;
+			if (number == n)
+				l += (float)v * scalar;
+			else if (number == n + 1)
+				r += (float)v * scalar;
+		}
+		for (uint32_t i = 0; i < numbers.count; i++) // the y deltas
+			if (!deltas.next(v))
+				return Face::kGvarAdvanceMalformed;
+	}
+	return Face::kGvarAdvanceDelta;
+}
+
 // ---- glyf ------------------------------------------------------------------------------
 std::optional<Bytes> Face::glyph_data(uint16_t gid) const
 {
@@ -1498,6 +1679,58 @@ template <class B> struct GvarWalker {
 		return true;
 	}
 };
+
+// G7: the points of the glyph id's own entry
+bool Face::own_point_count(uint16_t gid, uint32_t &n) const
+{
+	n = 0;
+	const auto entry = glyph_data(gid);
+	if (!entry)
+		return true; // no entry: no point, and still the four phantom ones
+	const Bytes glyph = *entry;
+	if (!glyph.has(0, 2))
+		return false;
+	const int16_t n_contours = glyph.i16(0);
+	if (n_contours == 0)
+		return true;
+	if (glyph.size() < 10)
+		return false;
+	const Bytes body = glyph.from(10);
+	if (n_contours > 0) {
+		if (!body.has(0, (size_t)n_contours * 2))
+			return false;
+		const uint16_t last_end = body.u16((size_t)(n_contours - 1) * 2);
+		if (last_end == 0xFFFF)
+			return false;
+		n = (uint32_t)last_end + 1;
+		return true;
+	}
+	for (size_t p = 0;;) { // composite: one point per record the static walk reads
+		uint16_t flags, child;
+		Affine k;
+		if (!read_component(body, p, flags, child, k))
+			break;
+		n++;
+		if (!(flags & 0x0020))
+			break;
+	}
+	return true;
+}
+
+uint8_t Face::gvar_advance_delta(uint16_t gid, float &d) const
+{
+	d = 0.0f;
+	uint32_t n;
+	if (!gvar_)
+		return kGvarAdvanceNone;
+	if (!own_point_count(gid, n))
+		return kGvarAdvanceMalformed;
+	float l, r;
+	const uint8_t state = gvar_->phantom_sums(gid, coords_, n, l, r);
+	if (state == kGvarAdvanceDelta)
+		d = r - l;
+	return state;
+}
 
 bool Face::outline_glyph(uint16_t gid, OutlineBuilder &builder) const
 {

@@ -206,7 +206,8 @@ public:
 	// axisCount equal to fvar's, the header, the shared tuples and the offset array inside the table), a coordinate count other
 	// than the axes', an `HVAR` whose store is not of format 1 or holds 32-bit deltas (LONG_WORDS).  An `HVAR` that cannot be
 	// read at all (major version not 1, a header, store header or region list outside the table) counts as absent, as the crate
-	// drops it; without `HVAR` the `hmtx` advance stands (advances from gvar's phantom points are not read).
+	// drops it; without `HVAR` the `hmtx` advance stands, unless the face is `glyf` + `gvar` and was placed with gvar_advances
+	// on: then its advances follow gvar's phantom points (G7 below).
 	//
 	// A `glyf` face at a position: outline_glyph, outline_glyph_packed and command_table() deliver the outline there.  The rules
 	// are the OpenType specification's; where it leaves the f32 order open, the order below is the definition.
@@ -241,13 +242,39 @@ public:
 	// G6, composite glyph.  One point per component record the static walk reads, in record order, + 4 phantom points; touched
 	//   points only, no inference.  Component k's e and f, as the static walk has them, get += a in f32 before the transform is
 	//   combined with the parent's.  Children vary by their own data.
+	// G7, advance from the phantom points.  Followed by a face placed with gvar_advances on that has no readable `HVAR` (`HVAR`
+	//   wins whenever it is there).  Point count n of glyph id g's OWN entry: a simple entry (numberOfContours > 0) has its last
+	//   end point + 1 (only the end points are read: whether the flags and coordinates behind them are sound is the outline's
+	//   matter); an entry of numberOfContours 0 has 0; a composite has one point per component record the static walk reads;
+	//   a glyph id WITHOUT an entry (Face::glyph_data has none: a `loca` range of length 0, `space` for instance, or one that
+	//   descends or leaves `glyf`) has n = 0 and still its four phantom points.  An entry whose count cannot be read — shorter
+	//   than 2 bytes, a simple or composite one shorter than 10, end points that leave the entry, a last end point of 0xFFFF — is
+	//   malformed.  Two f32 accumulators l (point n, x) and r (point n + 1, x) start at 0.  The glyph's tuples are taken in order
+	//   by G1 to G4, a tuple of scalar 0 skipped unread.  An applied tuple over all points contributes its x deltas number n and
+	//   n + 1; one with point numbers, private or shared, the x delta at the position in its list where n or n + 1 is named, and
+	//   nothing for a number not named; each contribution is += f32(delta) * scalar, one product and one sum, as in G5.  Phantom
+	//   points are never inferred.  d = r - l, one f32 subtraction, stands where `HVAR`'s delta stands in glyph_hor_advance:
+	//   (f32)hmtx advance + (d + 0.5), truncated, none outside 0 .. 65535.  A glyph id at or past glyphCount, with an empty
+	//   range of `gvar` or with tuple count 0 has d = 0.  Malformed data, by G1 to G5's meaning at that position — every applied
+	//   tuple's point numbers and all 2 * count of its deltas are walked, not only those up to n + 1 — or a malformed entry
+	//   gives no delta: the `hmtx` advance stands.  NOT BUILT: USE_MY_METRICS is not consulted (a composite's phantom points take
+	//   the composite's own data, as fontTools does); the outline is not shifted by the left phantom point, as it is not under
+	//   `HVAR`; the vertical phantom points (n + 2, n + 3) are not read.
 	// Malformed data of a glyph id — a header, point numbers or deltas that leave the glyph's range, a tuple that ends before
 	// its deltas do — delivers nothing from where the data is needed: outline_glyph returns false there, leaves delivered
 	// before it stay.  PARITY UNPINNED like the rest of the variation code; checked against fontTools and a strict restatement
 	// (tests/test_gvar_instances_host.py).
-	static std::optional<Face> parse_at(const uint8_t *data, size_t len, const std::vector<int16_t> &coords, std::string *err = nullptr);
+	static std::optional<Face> parse_at(const uint8_t *data, size_t len, const std::vector<int16_t> &coords, std::string *err = nullptr,
+	                                    bool gvar_advances = false);
 	// made by parse_at (even at all-zero coordinates)
 	bool at_position() const { return at_position_; }
+	// THE predicate of G7: placed with gvar_advances on, by gvar, and without a readable `HVAR`
+	bool advances_by_gvar() const { return gvar_advances_ && gvar_ != nullptr && hvar_.empty(); }
+	// G7 for one glyph id of a face placed by gvar, whether or not its advances follow it (test / inspection, and what the
+	// device's phantom pass is held to): the state — kGvarAdvanceNone (no variation data: d = 0), kGvarAdvanceDelta,
+	// kGvarAdvanceMalformed (d = 0: not to be used) — and d.  A streaming walk: no per-point storage, nothing inferred.
+	enum : uint8_t { kGvarAdvanceNone = 0, kGvarAdvanceDelta = 1, kGvarAdvanceMalformed = 2 };
+	uint8_t gvar_advance_delta(uint16_t glyph_id, float &d) const;
 	const std::vector<int16_t> &coords() const { return coords_; }
 	// every glyph id's glyph_hor_advance().value_or(0), for ids 0 .. n - 1 (test / inspection: ids at and past numGlyphs give 0)
 	std::vector<uint16_t> hor_advances(uint32_t n) const;
@@ -334,9 +361,11 @@ private:
 
 	std::optional<Bytes> glyph_data(uint16_t glyph_id) const;
 	static std::optional<Face> parse_impl(const uint8_t *data, size_t len, const std::vector<int16_t> *coords, std::string *err);
+	// G7's point count of the glyph id's own entry; false: the entry is malformed
+	bool own_point_count(uint16_t glyph_id, uint32_t &n) const;
 
 	Bytes hmtx_, loca_, glyf_, name_, cmap_table_;
-	bool at_position_ = false;
+	bool at_position_ = false, gvar_advances_ = false;
 	std::vector<int16_t> coords_;
 	Bytes hvar_;                      // parse_at: the table when its store can be read, else empty
 	uint32_t hvar_store_ = 0, hvar_map_ = 0;

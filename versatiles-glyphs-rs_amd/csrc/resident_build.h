@@ -34,6 +34,15 @@ struct VGSDF_INTERNAL ScratchBuf : DevBuf { // device memory for the duration of
 	~ScratchBuf() { release(); }
 };
 
+// resident_gvar.cpp: the phantom pass over one placed glyf face (gvar_advance_kernels.h).  _described: vgsdf_font_create_gvar's
+// validation of the description (VGSDF_E_ARG and the context's error text otherwise; num_glyphs is then at most 65535);
+// _on_device, over such a description: the pass into `out` — device memory of gvar_advance_bytes(num_glyphs), the f32 delta per
+// glyph id at 0, the state byte per glyph id at gvar_advance_state_at(num_glyphs) — complete when the call returns
+VGSDF_INTERNAL int gvar_advance_described(vgsdf_ctx *ctx, const char *entry, const vgsdf_font_gvar_desc *desc);
+VGSDF_INTERNAL size_t gvar_advance_bytes(uint32_t n_glyph_ids);
+VGSDF_INTERNAL size_t gvar_advance_state_at(uint32_t n_glyph_ids);
+VGSDF_INTERNAL int gvar_advance_on_device(vgsdf_ctx *ctx, const char *entry, const vgsdf_font_gvar_desc *desc, uint8_t *out, float *ms);
+
 // The calls of a constructor on its stream, in order, up to the first that fails: after it nothing more is issued, and the
 // caller hands `e` to font_hip_error under the name of the phase it is in.  A constructor ends with sync(): its store is complete
 // on the device when the call returns, so every context may name the font or family.

@@ -137,9 +137,9 @@ const char *variation_refused(const vgsdf_face_variation &v)
 }
 
 // vgsdf_family_create_tables and vgsdf_family_create_tables_mixed (the kernels take the kind face by face: FamilyFaceRef::commands)
-// and their _var forms (var: NULL, or a record per face)
+// and their _var forms (var: NULL, or a record per face) and _gvar forms (gvar: NULL, or per face a description or NULL)
 int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out, bool mixed,
-                         const char *me)
+                         const char *me, const vgsdf_font_gvar_desc *const *gvar = nullptr)
 {
 	if (!ctx)
 		return VGSDF_E_ARG;
@@ -149,6 +149,8 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 	}
 	*out = nullptr;
 	ctx->family_tables_ms[0] = ctx->family_tables_ms[1] = 0.0f;
+	if (gvar)
+		ctx->gvar_advance_ms = 0.0f;
 	const uint32_t n_fonts = in->n_fonts;
 	if (n_fonts == 0 || n_fonts > 0x10000u) {
 		ctx->err = std::string(me) + ": n_fonts must be 1 .. 65536";
@@ -157,8 +159,10 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 	// what can be said without a lookup; the staging block's layout on the way:
 	// FamilyFaceRef[n_fonts] | FamilySubtable[all] | per face cmap, hmtx (4-aligned) |
 	// with a variation: FamilyFaceVar[n_fonts] | per face HVAR, factors (4-aligned) | then, 16-aligned: counts | flags
-	size_t n_subtables = 0, table_bytes = 0, var_bytes = 0;
-	bool any_var = false;
+	// with faces that take their advances' deltas from gvar (a description and no HVAR): FamilyFaceVar[n_fonts] as well (zeroed
+	// for such a face), FamilyFaceGvar[n_fonts] behind the variation's bytes; the phantom pass's output lies in the context's array
+	size_t n_subtables = 0, table_bytes = 0, var_bytes = 0, advance_bytes = 0;
+	bool any_var = false, any_gvar = false;
 	for (uint32_t k = 0; k < n_fonts; k++) {
 		const vgsdf_face_tables &t = in->tables[k];
 		if (!family_font_fits(ctx, in->fonts, k, mixed)) {
@@ -192,9 +196,19 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 				var_bytes += align_up(var[k].hvar_len, 4) + 4 * (size_t)var[k].n_regions;
 			}
 		}
+		if (gvar && gvar[k]) {
+			if (const int rc = gvar_advance_described(ctx, me, gvar[k]); rc != VGSDF_OK)
+				return rc;
+			if (!(var && var[k].hvar)) { // (a face with both descriptions uses HVAR)
+				any_gvar = true;
+				advance_bytes += gvar_advance_bytes(gvar[k]->tables.num_glyphs);
+			}
+		}
 	}
-	if (any_var)
+	const bool with_var = any_var || any_gvar;
+	if (with_var)
 		var_bytes += sizeof(vgsdf::FamilyFaceVar) * (size_t)n_fonts;
+	const size_t gvar_records = any_gvar ? sizeof(vgsdf::FamilyFaceGvar) * (size_t)n_fonts : 0;
 	std::unique_ptr<vgsdf_family> f(new (std::nothrow) vgsdf_family());
 	if (!f) {
 		ctx->err = std::string(me) + ": out of host memory";
@@ -202,7 +216,7 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 	}
 	adopt_fonts(*f, ctx, in->fonts, n_fonts, mixed);
 	const size_t a_subs = sizeof(vgsdf::FamilyFaceRef) * (size_t)n_fonts, a_bytes = a_subs + sizeof(vgsdf::FamilySubtable) * n_subtables,
-	             a_var = align_up(a_bytes + table_bytes, 8), a_counts = align_up(a_var + var_bytes, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
+	             a_var = align_up(a_bytes + table_bytes, 8), a_gvar = align_up(a_var + var_bytes, 8), a_counts = align_up(a_gvar + gvar_records, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
 	             a_total = a_flags + 16;
 	(void)hipSetDevice(ctx->device);
 	hipStream_t st = ctx->stream;
@@ -210,6 +224,21 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 	if (hipError_t e = dev.ensure(a_total); e != hipSuccess)
 		return font_hip_error(ctx, me, "hipMalloc", e);
 	uint8_t *d = (uint8_t *)dev.p;
+	if (any_gvar) { // the phantom pass, face by face, into the context's array (nothing in flight reads it: every call that does ends synchronised)
+		if (hipError_t e = ctx->gvar_advance.ensure(advance_bytes + 16); e != hipSuccess)
+			return font_hip_error(ctx, me, "hipMalloc", e);
+		size_t at = 0;
+		for (uint32_t k = 0; k < n_fonts; k++) {
+			if (!gvar[k] || (var && var[k].hvar))
+				continue;
+			float ms = 0.0f;
+			const int rc = gvar_advance_on_device(ctx, me, gvar[k], (uint8_t *)ctx->gvar_advance.p + at, &ms);
+			ctx->gvar_advance_ms += ms;
+			if (rc != VGSDF_OK)
+				return rc;
+			at += gvar_advance_bytes(gvar[k]->tables.num_glyphs);
+		}
+	}
 	std::vector<uint8_t> h(a_counts, 0);
 	{
 		vgsdf::FamilyFaceRef *faces = (vgsdf::FamilyFaceRef *)h.data();
@@ -236,6 +265,18 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 			r.n_glyph_ids = ft.n_glyph_ids;
 			r.units_per_em = t.units_per_em, r.num_glyphs = t.num_glyphs, r.num_hmetrics = t.num_hmetrics, r.n_subtables = t.n_subtables;
 			r.commands = ft.commands ? 1u : 0u;
+		}
+		if (any_gvar) {
+			vgsdf::FamilyFaceGvar *recs = (vgsdf::FamilyFaceGvar *)(h.data() + a_gvar);
+			size_t at = 0;
+			for (uint32_t k = 0; k < n_fonts; k++) {
+				if (!gvar[k] || (var && var[k].hvar))
+					continue; // (zeroed: the face takes none)
+				const uint32_t n_ids = gvar[k]->tables.num_glyphs;
+				const uint64_t base = (uint64_t)(uintptr_t)((uint8_t *)ctx->gvar_advance.p + at);
+				recs[k] = vgsdf::FamilyFaceGvar{base, base + gvar_advance_state_at(n_ids), n_ids, 0};
+				at += gvar_advance_bytes(n_ids);
+			}
 		}
 		if (any_var) {
 			vgsdf::FamilyFaceVar *vars = (vgsdf::FamilyFaceVar *)(h.data() + a_var);
@@ -287,6 +328,9 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 	std::vector<uint8_t> back(at.bytes);
 	q.record(ev.at[1]);
 	q.launch([&] {
+		if (any_gvar)
+			return vgsdf_family_tables_emit_gvar(faces, (const vgsdf::FamilyFaceVar *)(d + a_var), (const vgsdf::FamilyFaceGvar *)(d + a_gvar), n_fonts,
+			                                     counts, n, (uint8_t *)f->table.p, st);
 		return any_var ? vgsdf_family_tables_emit_var(faces, (const vgsdf::FamilyFaceVar *)(d + a_var), n_fonts, counts, n, (uint8_t *)f->table.p, st)
 		               : vgsdf_family_tables_emit(faces, n_fonts, counts, n, (uint8_t *)f->table.p, st);
 	});
@@ -344,6 +388,17 @@ int vgsdf_family_create_tables_var(vgsdf_ctx *ctx, const vgsdf_family_tables_des
 int vgsdf_family_create_tables_var_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out)
 {
 	return family_create_tables(ctx, in, var, out, true, "vgsdf_family_create_tables_var_mixed");
+}
+
+int vgsdf_family_create_tables_gvar(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var,
+                                    const vgsdf_font_gvar_desc *const *gvar, vgsdf_family **out)
+{
+	return family_create_tables(ctx, in, var, out, false, "vgsdf_family_create_tables_gvar", gvar);
+}
+int vgsdf_family_create_tables_gvar_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var,
+                                          const vgsdf_font_gvar_desc *const *gvar, vgsdf_family **out)
+{
+	return family_create_tables(ctx, in, var, out, true, "vgsdf_family_create_tables_gvar_mixed", gvar);
 }
 
 void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]) { pass_ms_out(ctx ? ctx->family_tables_ms : nullptr, ms); }

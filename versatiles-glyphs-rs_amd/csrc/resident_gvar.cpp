@@ -7,6 +7,7 @@
 #include <memory>
 #include <new>
 
+#include "gvar_advance_kernels.h"
 #include "gvar_kernels.h"
 #include "gvar_limits.h"
 #include "resident_command_store.h"
@@ -469,6 +470,69 @@ int create_gvar_batch(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *desc, uint64_
 	return VGSDF_OK;
 }
 
+// the phantom pass's output on the device: delta (f32 per glyph id) | state (a byte per glyph id) | flags, each 16-aligned
+struct GvarAdvanceLayout {
+	size_t delta = 0, state, flags, total;
+	constexpr explicit GvarAdvanceLayout(size_t n) : state(align_up(4 * n, 16)), flags(align_up(state + n, 16)), total(flags + 4 * vgsdf::GVAR_ADVANCE_FLAG_WORDS) {}
+};
+static_assert(GvarAdvanceLayout(5).state == 32 && GvarAdvanceLayout(5).flags == 48 && GvarAdvanceLayout(5).total == 64, "delta | state | flags");
+} // namespace
+
+// The phantom pass over one face (gvar_advance_kernels.h).  _described: the description validated as create_gvar validates it
+// (VGSDF_E_ARG).  _bytes / _state_at: what the pass writes for n glyph ids, delta at 0 | state (GvarAdvanceLayout).  _on_device,
+// over a description that passed _described: the tables uploaded into an arena of the call's own, the pass into `out` (device
+// memory of _bytes(num_glyphs)), its flag word read back, synchronisation; *ms: the pass's milliseconds.
+int gvar_advance_described(vgsdf_ctx *ctx, const char *name, const vgsdf_font_gvar_desc *desc)
+{
+	if (!desc || !tables_given(desc->tables) || !desc->gvar || !desc->coords) {
+		ctx->err = std::string(name) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	vgsdf::GvarRef face{};
+	return gvar_face_described(ctx, name, desc->tables, desc->gvar, desc->gvar_len, desc->n_axes, face) ? VGSDF_OK : VGSDF_E_ARG;
+}
+size_t gvar_advance_bytes(uint32_t n) { return GvarAdvanceLayout(n).total; }
+size_t gvar_advance_state_at(uint32_t n) { return GvarAdvanceLayout(n).state; }
+
+int gvar_advance_on_device(vgsdf_ctx *ctx, const char *name, const vgsdf_font_gvar_desc *desc, uint8_t *o, float *ms)
+{
+	*ms = 0.0f;
+	const vgsdf_font_tables_desc &in = desc->tables;
+	const uint32_t n = in.num_glyphs;
+	vgsdf::GvarRef face{};
+	if (!gvar_face_described(ctx, name, in, desc->gvar, desc->gvar_len, desc->n_axes, face))
+		return VGSDF_E_ARG;
+	(void)hipSetDevice(ctx->device);
+	PassEvents ev;
+	if (hipError_t err = ev.create(); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipEventCreate", err);
+	const GvarArenaLayout arena(in.n_loca_bytes, in.n_glyf_bytes, desc->gvar_len, desc->n_axes, 0, 1, false);
+	const GvarAdvanceLayout at(n);
+	ScratchBuf dev;
+	if (hipError_t e = dev.ensure(arena.total + 16); e != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", e);
+	uint8_t *a = (uint8_t *)dev.p;
+	Calls q(ctx->stream);
+	upload_gvar_face(q, a, arena, in, desc->gvar, desc->gvar_len, desc->n_axes, desc->coords, 1, face);
+	q.zero(o + at.flags, 4 * vgsdf::GVAR_ADVANCE_FLAG_WORDS);
+	q.record(ev.at[0]);
+	if (n)
+		q.launch([&] { return vgsdf_gvar_advance_pass(&face, (float *)(o + at.delta), o + at.state, (uint32_t *)(o + at.flags), q.st); });
+	q.record(ev.at[1]);
+	uint32_t flags[vgsdf::GVAR_ADVANCE_FLAG_WORDS] = {};
+	q.read_back(flags, o + at.flags, sizeof flags);
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, name, "phantom pass", q.e);
+	(void)hipEventElapsedTime(ms, ev.at[0], ev.at[1]);
+	if (flags[vgsdf::GVAR_ADVANCE_FLAG_DELTAS]) {
+		ctx->err = std::string(name) + ": a glyph past VGSDF_GVAR_MAX_DELTAS";
+		return VGSDF_E_GLYF;
+	}
+	return VGSDF_OK;
+}
+
+namespace {
 // what both `…_kernel_ms` getters answer: the context's count / deltas / emit triple of the last call, zeros without a context
 void gvar_ms_out(const float *triple, float ms[3])
 {
@@ -519,5 +583,37 @@ int vgsdf_fonts_create_gvar(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *in, vgs
 }
 
 void vgsdf_fonts_gvar_kernel_ms(const vgsdf_ctx *ctx, float ms[3]) { gvar_ms_out(ctx ? ctx->gvar_batch_ms : nullptr, ms); }
+
+int vgsdf_gvar_advance_deltas(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in, float *delta, uint8_t *state)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	const char *name = "vgsdf_gvar_advance_deltas";
+	ctx->gvar_advance_ms = 0.0f;
+	if (!delta || !state) {
+		ctx->err = std::string(name) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	try {
+		if (const int rc = gvar_advance_described(ctx, name, in); rc != VGSDF_OK)
+			return rc;
+		const uint32_t n = in->tables.num_glyphs;
+		ScratchBuf out;
+		if (hipError_t e = out.ensure(gvar_advance_bytes(n) + 16); e != hipSuccess)
+			return font_hip_error(ctx, name, "hipMalloc", e);
+		if (const int rc = gvar_advance_on_device(ctx, name, in, (uint8_t *)out.p, &ctx->gvar_advance_ms); rc != VGSDF_OK)
+			return rc;
+		if (n) {
+			HIP_TRY(ctx, hipMemcpy(delta, out.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+			HIP_TRY(ctx, hipMemcpy(state, (const uint8_t *)out.p + gvar_advance_state_at(n), n, hipMemcpyDeviceToHost));
+		}
+		return VGSDF_OK;
+	} catch (const std::bad_alloc &) {
+		ctx->err = std::string(name) + ": out of host memory";
+		return VGSDF_E_OOM;
+	}
+}
+
+float vgsdf_gvar_advance_kernel_ms(const vgsdf_ctx *ctx) { return ctx ? ctx->gvar_advance_ms : 0.0f; }
 
 } // extern "C"

@@ -133,6 +133,7 @@ void vgsdf_destroy(vgsdf_ctx *ctx)
 	if (ctx->charstring_spill)
 		(void)hipFree(ctx->charstring_spill);
 	ctx->gvar_scratch.release();
+	ctx->gvar_advance.release();
 	delete ctx;
 }
 

@@ -136,6 +136,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_fonts_create_gvar", "vgsdf_fonts_create_gvar_within", "vgsdf_fonts_gvar_kernel_ms",
     "vgsdf_outlines_submit_resident_mixed", "vgsdf_family_create_mixed", "vgsdf_family_create_tables_mixed",
     "vgsdf_family_create_tables_var", "vgsdf_family_create_tables_var_mixed",
+    "vgsdf_gvar_advance_deltas", "vgsdf_gvar_advance_kernel_ms", "vgsdf_family_create_tables_gvar", "vgsdf_family_create_tables_gvar_mixed",
 ]
 
 _lib = None
@@ -226,6 +227,11 @@ def load_library():
         L.vgsdf_family_create_tables.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), C.POINTER(vp)]
         L.vgsdf_family_create_tables_var.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), vp, C.POINTER(vp)]
         L.vgsdf_family_create_tables_var_mixed.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), vp, C.POINTER(vp)]
+        L.vgsdf_family_create_tables_gvar.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), vp, vp, C.POINTER(vp)]
+        L.vgsdf_family_create_tables_gvar_mixed.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), vp, vp, C.POINTER(vp)]
+        L.vgsdf_gvar_advance_deltas.argtypes = [vp, C.POINTER(_CFontGvarDesc), vp, vp]
+        L.vgsdf_gvar_advance_kernel_ms.argtypes = [vp]
+        L.vgsdf_gvar_advance_kernel_ms.restype = C.c_float
         L.vgsdf_family_read.argtypes = [vp, vp, C.POINTER(C.c_uint32)] + [vp] * 9
         L.vgsdf_family_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_family_tables_kernel_ms.restype = None
@@ -708,6 +714,40 @@ class SdfContext:
         self._check(load_library().vgsdf_font_create_gvar(self._h, C.byref(d), C.byref(h)))
         return ResidentFont(self, h)
 
+    @staticmethod
+    def _gvar_desc(desc: dict, keep: list, override=None):
+        """vgsdf_font_gvar_desc of a dict as font_create_gvar takes it; the arrays it points to are appended to keep"""
+        override = override or {}
+        loca, glyf = np.frombuffer(bytes(desc["loca"]), dtype=np.uint8), np.frombuffer(bytes(desc["glyf"]), dtype=np.uint8)
+        gvar = np.frombuffer(bytes(desc["gvar"]), dtype=np.uint8)
+        coords = np.ascontiguousarray(desc["coords"], dtype=np.int16)
+        keep += [loca, glyf, gvar, coords]
+        d = _CFontGvarDesc()
+        d.tables = _CFontTablesDesc(int(override.get("num_glyphs", desc["num_glyphs"])), int(override.get("loca_entries", desc["loca_entries"])),
+                                    int(desc["loca_long"]), override.get("n_loca_bytes", len(loca)), override.get("n_glyf_bytes", len(glyf)),
+                                    loca.ctypes.data if len(loca) else None, glyf.ctypes.data if len(glyf) else None)
+        d.gvar = gvar.ctypes.data if len(gvar) else None
+        d.gvar_len = override.get("gvar_len", len(gvar))
+        d.n_axes = override.get("n_axes", len(coords))
+        d.coords = coords.ctypes.data if len(coords) else None
+        return d
+
+    def gvar_advance_deltas(self, desc: dict, **override):
+        """vgsdf_gvar_advance_deltas: the phantom pass alone over a placed `glyf` face (desc as font_create_gvar takes it), read
+        back -> (delta float32[num_glyphs], state uint8[num_glyphs]: 0 none, 1 delta, 2 malformed).  override: raw struct fields
+        (num_glyphs, loca_entries, n_loca_bytes, n_glyf_bytes, gvar_len, n_axes) for descriptions that lie.  VgsdfError with code
+        VGSDF_E_GLYF: a glyph id past VGSDF_GVAR_MAX_DELTAS"""
+        keep = []
+        d = self._gvar_desc(desc, keep, override)
+        n = int(d.tables.num_glyphs)
+        delta, state = np.full(max(n, 1), np.nan, np.float32), np.full(max(n, 1), 0xEE, np.uint8)
+        self._check(load_library().vgsdf_gvar_advance_deltas(self._h, C.byref(d), delta.ctypes.data, state.ctypes.data))
+        return delta[:n], state[:n]
+
+    def gvar_advance_kernel_ms(self) -> float:
+        """milliseconds of the phantom pass of this context's last gvar_advance_deltas / family_create_tables_gvar"""
+        return float(load_library().vgsdf_gvar_advance_kernel_ms(self._h))
+
     def font_gvar_kernel_ms(self):
         """(count, deltas, emit) pass milliseconds of this context's last font_create_gvar"""
         ms = (C.c_float * 3)()
@@ -861,7 +901,16 @@ class SdfContext:
         return self.family_create_tables(fonts, faces, entry="vgsdf_family_create_tables_var" + ("_mixed" if mixed else ""),
                                          variation=[None] * len(fonts) if variation is None else variation, no_records=variation is None)
 
-    def family_create_tables(self, fonts, faces, entry="vgsdf_family_create_tables", variation=None, no_records=False) -> ResidentFamily:
+    def family_create_tables_gvar(self, fonts, faces, variation, gvar, mixed=False, **override) -> ResidentFamily:
+        """vgsdf_family_create_tables_gvar (mixed: its _mixed twin): family_create_tables_var with, per font, what
+        FontManager.family_gvar_desc / gvar_font_desc returns (a dict as font_create_gvar takes it) or None for a face that takes
+        nothing from gvar; gvar None: no array at all.  override: raw struct fields of every gvar description"""
+        return self.family_create_tables(fonts, faces, entry="vgsdf_family_create_tables_gvar" + ("_mixed" if mixed else ""),
+                                         variation=[None] * len(fonts) if variation is None else variation, no_records=variation is None,
+                                         gvar=[None] * len(fonts) if gvar is None else gvar, no_gvar=gvar is None, gvar_override=override)
+
+    def family_create_tables(self, fonts, faces, entry="vgsdf_family_create_tables", variation=None, no_records=False, gvar=None,
+                             no_gvar=False, gvar_override=None) -> ResidentFamily:
         """vgsdf_family_create_tables: the family of `fonts` (ResidentFont, one kind, provider order) built on the device from
         `faces`, one dict per font as FontManager.family_tables_desc returns it: {cmap, hmtx (bytes or uint8 arrays),
         units_per_em, num_glyphs, num_hmetrics, subtable_off, subtable_format}"""
@@ -895,7 +944,14 @@ class SdfContext:
             r.hvar, r.hvar_len = (hv.ctypes.data if len(hv) else None), int(v.get("hvar_len", len(hv)))
             r.store_off, r.map_off = int(v["store_off"]), int(v["map_off"])
             r.region_scalars, r.n_regions = (sc.ctypes.data if len(sc) else None), len(sc)
-        self._check(getattr(load_library(), entry)(self._h, C.byref(d), None if no_records else C.cast(vrecs, C.c_void_p), C.byref(h)))
+        if gvar is None:
+            self._check(getattr(load_library(), entry)(self._h, C.byref(d), None if no_records else C.cast(vrecs, C.c_void_p), C.byref(h)))
+            return ResidentFamily(self, h, fonts)
+        assert len(gvar) == len(fonts)
+        gdescs = [self._gvar_desc(g, keep, gvar_override) if g else None for g in gvar]
+        gptrs = (C.c_void_p * max(len(fonts), 1))(*[C.addressof(g) if g is not None else None for g in gdescs])
+        self._check(getattr(load_library(), entry)(self._h, C.byref(d), None if no_records else C.cast(vrecs, C.c_void_p),
+                                                   None if no_gvar else C.cast(gptrs, C.c_void_p), C.byref(h)))
         return ResidentFamily(self, h, fonts)
 
     def family_read(self, family: ResidentFamily) -> dict:

@@ -83,6 +83,10 @@ class GvarStats(C.Structure):  # vg_gvar_stats
     _fields_ = [(k, C.c_uint64) for k in ("fonts_built", "font_bytes", "fallbacks")]
 
 
+class GvarAdvanceStats(C.Structure):  # vg_gvar_advance_stats
+    _fields_ = [(k, C.c_uint64) for k in ("faces", "device_builds", "fallbacks")]
+
+
 WRITE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint8), C.c_size_t, C.c_int)
 
 VGFONT_SYMBOLS = [
@@ -112,6 +116,8 @@ VGFONT_SYMBOLS = [
     "vg_manager_add_font_instance", "vg_manager_add_font_instance_normalized", "vg_font_variation_axes", "vg_font_named_instances",
     "vg_manager_family_variation_desc", "vg_manager_font_position", "vg_manager_font_hor_advances",
     "vg_manager_add_font_named_instances", "vg_manager_set_scan_named_instances", "vg_manager_set_gvar_batched", "vg_manager_gvar_batch_stats",
+    "vg_manager_set_gvar_advances", "vg_manager_gvar_advance_stats", "vg_manager_font_gvar_advance_deltas",
+    "vg_manager_family_gvar_desc",
 ]
 
 VG_FONT_ID_MAX = 256
@@ -191,6 +197,10 @@ def _L():
         L.vg_manager_family_variation_desc.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(_CFaceVariation)]
         L.vg_manager_font_position.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_int]
         L.vg_manager_font_hor_advances.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_int]
+        L.vg_manager_font_gvar_advance_deltas.argtypes = [vp, C.c_char_p, C.c_int, vp, vp, C.c_int]
+        L.vg_manager_set_gvar_advances.argtypes = [vp, C.c_int]
+        L.vg_manager_set_gvar_advances.restype = None
+        L.vg_manager_gvar_advance_stats.argtypes = [vp, C.POINTER(GvarAdvanceStats)]
         L.vg_name_to_id.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.vg_manager_block_counts.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint32)]
         L.vg_manager_render_glyphs.argtypes = [vp, vp, WRITE_CB, vp]
@@ -622,6 +632,19 @@ class FontManager:
         _L().vg_manager_gvar_batch_stats(self._h, C.byref(s))
         return {k: int(getattr(s, k)) for k, _ in GlyfTableBatchStats._fields_}
 
+    def set_gvar_advances(self, on: bool):
+        """vg_manager_set_gvar_advances: glyf + gvar faces placed AFTER the call whose file has no readable HVAR take their
+        advances from gvar's phantom points (rule G7 of csrc/host/ttf_face.hpp) instead of keeping hmtx's; not retroactive
+        (default off)"""
+        _L().vg_manager_set_gvar_advances(self._h, int(bool(on)))
+
+    def gvar_advance_stats(self) -> dict:
+        """{faces: placed so far whose advances follow G7; device_builds, fallbacks: of the last render, the families with such a
+        face the device built / refused} (vg_gvar_advance_stats)"""
+        s = GvarAdvanceStats()
+        _L().vg_manager_gvar_advance_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in GvarAdvanceStats._fields_}
+
     def add_path(self, path):
         """manager.rs:39-53: the file's own name table decides the font id."""
         if _L().vg_manager_add_path(self._h, str(path).encode()) != 0:
@@ -960,6 +983,17 @@ class FontManager:
         L.vg_manager_font_hor_advances(self._h, font_id.encode(), int(file_index), a.ctypes.data, len(a))
         return a
 
+    def font_gvar_advance_deltas(self, font_id: str, file_index: int = 0, extra: int = 0):
+        """rule G7 for every glyph id of a glyf face placed by gvar, and `extra` ids past numGlyphs, whether or not its advances
+        follow it (vg_manager_font_gvar_advance_deltas) -> (d: float32, state: uint8 — 0 none, 1 delta, 2 malformed)"""
+        L = _L()
+        n = L.vg_manager_font_gvar_advance_deltas(self._h, font_id.encode(), int(file_index), None, None, 0)
+        if n < 0:
+            raise RuntimeError(_err())
+        d, st = np.zeros(n + extra, np.float32), np.zeros(n + extra, np.uint8)
+        L.vg_manager_font_gvar_advance_deltas(self._h, font_id.encode(), int(file_index), d.ctypes.data, st.ctypes.data, len(d))
+        return d, st
+
     def family_variation_desc(self, font_id: str, file_index: int):
         """what SdfContext.family_create_tables_var takes beside family_tables_desc for a file at a position
         (vg_manager_family_variation_desc): {hvar (bytes), store_off, map_off, region_scalars (float32)}, copies; {} for a file
@@ -1006,6 +1040,18 @@ class FontManager:
         return {"loca": C.string_at(t.loca, t.n_loca_bytes) if t.n_loca_bytes else b"", "glyf": C.string_at(t.glyf, t.n_glyf_bytes) if t.n_glyf_bytes else b"",
                 "num_glyphs": int(t.num_glyphs), "loca_entries": int(t.loca_entries), "loca_long": int(t.loca_long),
                 "gvar": C.string_at(d.gvar, d.gvar_len), "coords": np.frombuffer(C.string_at(d.coords, 2 * d.n_axes), dtype=np.int16).copy()}
+
+    def family_gvar_desc(self, font_id: str, file_index: int = 0):
+        """what SdfContext.family_create_tables_gvar takes beside family_tables_desc and family_variation_desc
+        (vg_manager_family_gvar_desc): the dict of gvar_font_desc for a face whose advances follow gvar's phantom points, None for
+        every other face"""
+        from .device import _CFontGvarDesc
+        L = _L()
+        L.vg_manager_family_gvar_desc.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        d = _CFontGvarDesc()
+        if L.vg_manager_family_gvar_desc(self._h, font_id.encode(), int(file_index), C.byref(d)) != 0:
+            raise RuntimeError(_err())
+        return self.gvar_font_desc(font_id, file_index) if d.gvar else None
 
     def record_resident_commands(self, font_id: str) -> dict:
         """record_resident against command fonts: for any face the reader can read (CFF, CFF2, glyf)"""
