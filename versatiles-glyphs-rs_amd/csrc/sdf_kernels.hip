@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void sdf_chunk_boxes(const GlyphDesc *__restri
 #ifdef VGSDF_DEV_VARIANTS
 // development builds: the same kernel source a second time, with in-kernel stamps (cdna_hip_programming.md, "In-kernel
 // stamps": read the SHARES, never this instance's run time) and counters, summed per wave into g_span_dbg
-__device__ unsigned long long g_span_dbg[24];
+__device__ unsigned long long g_span_dbg[28];
 #define VG_SPAN_KERNEL sdf_tiles_span_stamped
 #define VG_SPAN_STAMPED 1
 #define VG_STAMP(region)                                                                      \
@@ -286,7 +286,7 @@ extern "C" int vgsdf_launch_tiles(int variant, int list_order, const vgsdf::Glyp
 	hipLaunchKernelGGL((vgsdf::sdf_tiles_filtered<A, C>), grid, dim3(vgsdf::TPB), 0, stream, glyphs, \
 	                   tiles, n_tiles, sx, sy, ex, ey, out)
 	else if (variant == 58) { // diagnostic: s_memtime stamps per phase; prints the shares of wave time on stderr
-		unsigned long long h[24] = {0};
+		unsigned long long h[28] = {0};
 		(void)hipMemcpyToSymbolAsync(HIP_SYMBOL(vgsdf::g_span_dbg), h, sizeof(h), 0, hipMemcpyHostToDevice, stream);
 		hipLaunchKernelGGL(vgsdf::sdf_tiles_span_stamped, grid, dim3(vgsdf::TPB), 0, stream, glyphs, tiles, n_tiles, sx, sy, ex,
 		                   ey, seg_stride, out, (const float4 *)boxes, (const vgsdf::PlanHeader *)nullptr);

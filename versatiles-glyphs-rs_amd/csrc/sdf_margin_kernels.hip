@@ -36,7 +36,7 @@ struct MarginInstance {
 #define VG_SPAN_KERNEL sdf_margin_span_base
 #include "sdf_span_kernel.inc"
 // ---- 61 count: VG_COUNT on, VG_STAMP off; counters summed per wave into g_span_dbg (vgsdf_margin_counters) ----
-__device__ unsigned long long g_span_dbg[24];
+__device__ unsigned long long g_span_dbg[28];
 #define VG_SPAN_KERNEL sdf_margin_span_count
 #define VG_SPAN_COUNTED 1
 #define VG_COUNT(stmt) stmt
@@ -195,7 +195,7 @@ extern "C" int vgsdf_margin_launch(VG_MARGIN_PART_ARGS)
 // waves with more (every lane for itself) — nine values.  Call with the context's work complete (after a download).
 extern "C" int vgsdf_margin_counters(unsigned long long *out, int reset)
 {
-	unsigned long long h[24] = {0};
+	unsigned long long h[28] = {0};
 	hipError_t e = hipSuccess;
 	if (out != nullptr) {
 		e = hipMemcpyFromSymbol(h, HIP_SYMBOL(vgsdf::g_span_dbg), sizeof(h), 0, hipMemcpyDeviceToHost);
@@ -204,9 +204,20 @@ extern "C" int vgsdf_margin_counters(unsigned long long *out, int reset)
 			out[i] = h[idx[i]];
 	}
 	if (e == hipSuccess && reset) {
-		const unsigned long long z[24] = {0};
+		const unsigned long long z[28] = {0};
 		e = hipMemcpyToSymbol(HIP_SYMBOL(vgsdf::g_span_dbg), z, sizeof(z), 0, hipMemcpyHostToDevice);
 	}
+	return (int)e;
+}
+
+// The `count` instance's counters of phase 2's pair rounds, behind the nine above (which keep their places): out[0..1] =
+// half rounds taken, sweeps that left behind phase 1 without a pair.  Same accumulation; vgsdf_margin_counters resets these too.
+extern "C" int vgsdf_margin_pair_round_counters(unsigned long long *out)
+{
+	unsigned long long h[28] = {0};
+	const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(vgsdf::g_span_dbg), sizeof(h), 0, hipMemcpyDeviceToHost);
+	for (int i = 0; i < 2; i++)
+		out[i] = h[23 + i];
 	return (int)e;
 }
 #endif

@@ -118,6 +118,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 #if defined(VG_SPAN_STAMPED) || defined(VG_SPAN_COUNTED)
 	unsigned long long cn_pairs = 0, cn_rounds = 0, cn_tc = 0, cn_fb = 0, cn_fbl = 0;
 	unsigned long long cn_over = 0, cn_fb_pool = 0, cn_fb_lane = 0; // phase-2 pool overflows; waves by exact-evaluation branch
+	unsigned long long cn_half = 0, cn_leave = 0;                   // half rounds taken; sweeps that left behind phase 1 without a pair
 #endif
 	VG_STAMP(-1);
 	constexpr uint32_t GRP = 8, NGRP = FCHUNK / GRP; // 32 groups per chunk: one mask bit each
@@ -496,24 +497,24 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			auto rec4 = [](const float4 *row, uint32_t goff, uint32_t hq) { // records 4 hq .. 4 hq + 3 of the group at byte goff of `row`
 				return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(row) + goff + 16u * hq);
 			};
+			auto half_min = [&](uint32_t acc, uint32_t goff, uint32_t hq, float qx, float qy) { // min(acc, F of records 4 hq .. 4 hq + 3 of the group at byte goff)
+				const float4 vx4 = rec4(q_vx, goff, hq), vy4 = rec4(q_vy, goff, hq), dx4 = rec4(q_dx, goff, hq), dy4 = rec4(q_dy, goff, hq),
+				             iv4 = rec4(q_inv, goff, hq);
+				const uint32_t f0 = __float_as_uint(sc_filter(qx, qy, vx4.x, vy4.x, dx4.x, dy4.x, iv4.x));
+				const uint32_t f1 = __float_as_uint(sc_filter(qx, qy, vx4.y, vy4.y, dx4.y, dy4.y, iv4.y));
+				const uint32_t f2 = __float_as_uint(sc_filter(qx, qy, vx4.z, vy4.z, dx4.z, dy4.z, iv4.z));
+				const uint32_t f3 = __float_as_uint(sc_filter(qx, qy, vx4.w, vy4.w, dx4.w, dy4.w, iv4.w));
+				uint32_t mn;
+				asm("v_min3_u32 %0, %1, %2, %3" : "=v"(mn) : "v"(acc), "v"(f0), "v"(f1));
+				asm("v_min3_u32 %0, %1, %2, %3" : "=v"(acc) : "v"(mn), "v"(f2), "v"(f3));
+				return acc;
+			};
 			auto group_min = [&](uint32_t acc, uint32_t goff, float qx, float qy) { // min(acc, F of the 8 members of the group at byte goff = 32 g of a row)
 				// two halves of 4 records: 20 + 4 live values instead of 40 + 8 (the kernel sits at the 128-VGPR
 				// limit of 4 waves per SIMD; spills would go to scratch, i.e. to memory)
-#pragma unroll
-				for (uint32_t hq = 0; hq < 2; hq++) {
-					const float4 vx4 = rec4(q_vx, goff, hq), vy4 = rec4(q_vy, goff, hq), dx4 = rec4(q_dx, goff, hq), dy4 = rec4(q_dy, goff, hq),
-					             iv4 = rec4(q_inv, goff, hq);
-					const uint32_t f0 = __float_as_uint(sc_filter(qx, qy, vx4.x, vy4.x, dx4.x, dy4.x, iv4.x));
-					const uint32_t f1 = __float_as_uint(sc_filter(qx, qy, vx4.y, vy4.y, dx4.y, dy4.y, iv4.y));
-					const uint32_t f2 = __float_as_uint(sc_filter(qx, qy, vx4.z, vy4.z, dx4.z, dy4.z, iv4.z));
-					const uint32_t f3 = __float_as_uint(sc_filter(qx, qy, vx4.w, vy4.w, dx4.w, dy4.w, iv4.w));
-					uint32_t mn;
-					asm("v_min3_u32 %0, %1, %2, %3" : "=v"(mn) : "v"(acc), "v"(f0), "v"(f1));
-					asm("v_min3_u32 %0, %1, %2, %3" : "=v"(acc) : "v"(mn), "v"(f2), "v"(f3));
-					if (hq == 0)
-						__builtin_amdgcn_sched_barrier(0);
-				}
-				return acc;
+				acc = half_min(acc, goff, 0, qx, qy);
+				__builtin_amdgcn_sched_barrier(0);
+				return half_min(acc, goff, 1, qx, qy);
 			};
 			if (sane) {
 				if (o >= npix)
@@ -526,6 +527,14 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				const uint32_t incl = wave_scan_add(c); // inclusive prefix sum over the wave
 				const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 				VG_COUNT(cn_pairs += total; cn_rounds += (total + 63) / 64; cn_tc += 1);
+				// No lane of the wave holds a candidate (wave-uniform; 18 % of the sweeps of Noto Sans): k1 stays "none" in every
+				// lane, nothing is undecided and the bytes keep what they hold (min with 255, max with 0).  Only the bound,
+				// which phase 1 may have lowered, is kept.
+				if (total == 0) {
+					st_ub2[k * TPB + tid] = ub2;
+					VG_COUNT(cn_leave += 1);
+					continue;
+				}
 				if (total <= QCAP) {
 					uint32_t *qp = &q_pair[wv][incl - c];
 					q_min[wv][lane] = 0xFFFFFFFFu;
@@ -538,27 +547,48 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 					}
 					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 					__builtin_amdgcn_wave_barrier();
+					// A last round of 1 .. 32 entries (40 % of the pooled sweeps end in one) is a HALF round: lanes l and l + 32
+					// take entry l and four of the group's eight records each (one step of group_min), and both merge onto the
+					// pixel's slot.  The full rounds in front of it are all full; `tail` and `lim` are wave-uniform.
+					const uint32_t tail = ((total - 1u) & 63u) + 1u;
+					const uint32_t lim = tail <= 32u ? total - tail : total; // entries of the full rounds
 					// The entry of the round after this one is read before this round's filters: a round then waits for the
 					// pixel and the records only, not for its entry first (the first round's is read ahead of the loop; past
-					// the last round the read takes the last pair again: q_pair holds QCAP entries, total = 0 reads its own lane's).
-					// The loop runs on the NEXT round's base, the only index a round forms: its own is that minus 64.
+					// the last round the read takes the last pair again: q_pair holds QCAP entries).  The half round's entry
+					// arrives the same way.  The loop runs on the NEXT round's base, the only index a round forms: its own is
+					// that minus 64.
 					uint32_t e = q_pair[wv][min(lane, total - 1)]; // (a lane past the end takes the last pair and drops its result)
-					const uint32_t total64 = total + 64;          // (total <= QCAP)
-					for (uint32_t next = 64; next < total64; next += 64) {
+					const uint32_t lim64 = lim + 64;              // (total <= QCAP)
+					for (uint32_t next = 64; next < lim64; next += 64) {
 						const uint32_t idx_next = next + lane;
 						const uint32_t e_next = q_pair[wv][min(idx_next, total - 1)];
 						const uint32_t src4 = e >> 16;
 						const float qx = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpx)));
 						const float qy = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpy)));
 						const uint32_t mn = group_min(0xFFFFFFFFu, e & 0xFFFFu, qx, qy);
-						if (idx_next < total64) // this round's index < total
+						if (idx_next < lim64) // this round's index < lim
 							atomicMin(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(q_min[wv]) + src4), mn);
 						e = e_next;
+					}
+					if (lim != total) {
+						VG_COUNT(cn_half += 1);
+						// e is the entry lim + lane: the upper half of the wave takes the lower half's (v_permlane32_swap: lanes
+						// 32..63 of the first operand <-> lanes 0..31 of the second).  A group's padding records (F = 2e36) lose
+						// against the other half's real ones on the slot as they do inside group_min.
+						const uint32_t eh = __builtin_amdgcn_permlane32_swap(e, e, false, false)[0];
+						const uint32_t src4 = eh >> 16;
+						const float qx = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpx)));
+						const float qy = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)src4, (int)__float_as_uint(rpy)));
+						const uint32_t mn = half_min(0xFFFFFFFFu, eh & 0xFFFFu, lane >> 5, qx, qy);
+						if ((lane & 31u) < tail)
+							atomicMin(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(q_min[wv]) + src4), mn);
 					}
 					__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 					__builtin_amdgcn_wave_barrier();
 					k1 = q_min[wv][lane];
 				} else {
+					// (pooling such a sweep in passes over windows of QCAP pairs was built and measured: slower than this walk,
+					// profiles/pair_rounds_ab.txt)
 					VG_COUNT(cn_over += 1);
 					uint32_t m = cand;
 					while (m) {
@@ -773,6 +803,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 		atomicAdd(&g_span_dbg[20], cn_over);
 		atomicAdd(&g_span_dbg[21], cn_fb_pool);
 		atomicAdd(&g_span_dbg[22], cn_fb_lane);
+		atomicAdd(&g_span_dbg[23], cn_half);
+		atomicAdd(&g_span_dbg[24], cn_leave);
 	}
 #endif
 }
