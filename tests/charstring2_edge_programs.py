@@ -42,8 +42,10 @@ def blend_sets(desc):
     return {k: desc[k] for k in ("set_ok", "set_off", "factors")}
 
 
-def interpret(desc, gid, sets=None, budget=MAX_TOKENS):
-    """glyph id `gid` of a CFF2 description under the blend sets `sets` ({set_ok, set_off, factors}; None: the description's)"""
+def interpret(desc, gid, sets=None, budget=MAX_TOKENS, trace=None):
+    """glyph id `gid` of a CFF2 description under the blend sets `sets` ({set_ok, set_off, factors}; None: the description's).
+    trace: called as trace(op, data, pos, end, stack, depth, st) for every token about to be executed, pos behind its first byte
+    (and once more, with op = (12, second byte), for an escaped operator); st["scalars"] are the selected set's factors"""
     sets = blend_sets(desc) if sets is None else sets
     set_ok, set_off, factors = sets["set_ok"], sets["set_off"], np.asarray(sets["factors"], np.float32)
     data = desc["bytes"].tobytes()
@@ -85,6 +87,8 @@ def interpret(desc, gid, sets=None, budget=MAX_TOKENS):
                 stop("budget")
             op = data[pos]
             pos += 1
+            if trace is not None:
+                trace(op, data, pos, end, stack, depth, st)
             if op >= 32 or op == 28:
                 if op == 28:
                     need(end - pos >= 2)
@@ -246,6 +250,8 @@ def interpret(desc, gid, sets=None, budget=MAX_TOKENS):
                 need(pos < end)
                 op2 = data[pos]
                 pos += 1
+                if trace is not None:
+                    trace((12, op2), data, pos, end, stack, depth, st)
                 need(st["has_move"])
                 if op2 == 35:
                     need(sp == 13)

@@ -66,7 +66,9 @@ class _Stop(Exception):
     pass
 
 
-def interpret(desc, gid, budget=MAX_TOKENS):
+def interpret(desc, gid, budget=MAX_TOKENS, trace=None):
+    """trace: called as trace(op, data, pos, end, stack, depth, st) for every token about to be executed, pos behind its first
+    byte (and once more, with op = (12, second byte), for an escaped operator)"""
     data = desc["bytes"].tobytes() if not isinstance(desc["bytes"], (bytes, bytearray)) else desc["bytes"]
     cs_off, gs_off, ls_off, ls_first = desc["cs_off"], desc["gsubr_off"], desc["lsubr_off"], desc["lsubr_first"]
     fd = 0 if desc.get("fd_of") is None else int(desc["fd_of"][gid])
@@ -102,6 +104,8 @@ def interpret(desc, gid, budget=MAX_TOKENS):
                 stop("budget")
             op = data[pos]
             pos += 1
+            if trace is not None:
+                trace(op, data, pos, end, stack, depth, st)
             if op >= 32 or op == 28:
                 if op == 28:
                     need(end - pos >= 2)
@@ -273,6 +277,8 @@ def interpret(desc, gid, budget=MAX_TOKENS):
                 need(pos < end)
                 op2 = data[pos]
                 pos += 1
+                if trace is not None:
+                    trace((12, op2), data, pos, end, stack, depth, st)
                 need(st["has_move"])
                 if op2 == 35:
                     need(sp == 13)

@@ -215,9 +215,10 @@ def gvar_table(glyphs, shared_tuples=(), n_axes=1, long_offsets=True, glyph_coun
                        1 if long_offsets else 0, shared_at + len(shared)) + array + shared + data
 
 
-def raw_font(entries, gvar, n_axes=1, advances=None, cut_gvar=None):
+def raw_font(entries, gvar, n_axes=1, advances=None, cut_gvar=None, bearings=None):
     """a TrueType font whose glyph i is the raw entry entries[i] (code point 0x100 + i, long loca) with an fvar of n_axes axes
-    (-1 .. 0 .. 1 in user space: a user value is its normalised one) and `gvar` as given (None: no gvar table)"""
+    (-1 .. 0 .. 1 in user space: a user value is its normalised one) and `gvar` as given (None: no gvar table).  advances,
+    bearings: {glyph id: hmtx advance / left side bearing} (600 / 0 where not given)"""
     from fontTools.fontBuilder import FontBuilder
     from fontTools.ttLib import TTFont
     from fontTools.ttLib.tables._g_l_y_f import Glyph
@@ -227,7 +228,7 @@ def raw_font(entries, gvar, n_axes=1, advances=None, cut_gvar=None):
     fb.setupGlyphOrder(order)
     fb.setupCharacterMap({0x100 + i: g for i, g in enumerate(order)})
     fb.setupGlyf({g: Glyph() for g in order})
-    fb.setupHorizontalMetrics({g: ((advances or {}).get(i, 600), 0) for i, g in enumerate(order)})
+    fb.setupHorizontalMetrics({g: ((advances or {}).get(i, 600), (bearings or {}).get(i, 0)) for i, g in enumerate(order)})
     fb.setupHorizontalHeader(ascent=935, descent=-265)
     fb.setupNameTable({"familyName": "Synth Edge", "styleName": "Regular"})
     fb.setupOS2()
@@ -259,6 +260,14 @@ class Malformed(Exception):
     pass
 
 
+TRACE = None      # a callable(what, *details): told what the restatement meets (tests/gvar_fuzz_kit.py counts its features with it)
+
+
+def _t(*what):
+    if TRACE is not None:
+        TRACE(*what)
+
+
 def _u16(b, at):
     if at + 2 > len(b):
         raise Malformed
@@ -281,14 +290,19 @@ def read_points(b, p):
     count = _u8(b, p)
     p += 1
     if count == 0:
+        _t("point_count", "all", 0)
         return None, p
     if count & 0x80:
         count = ((count & 0x7F) << 8) | _u8(b, p)
         p += 1
+        _t("point_count", "two_bytes", count)
+    else:
+        _t("point_count", "one_byte", count)
     out, number = [], 0
     while len(out) < count:
         control = _u8(b, p)
         p += 1
+        _t("point_run", "words" if control & 0x80 else "bytes", min((control & 0x7F) + 1, count - len(out)))
         for _ in range((control & 0x7F) + 1):
             if len(out) == count:
                 break
@@ -310,6 +324,7 @@ def read_deltas(b, p, n):
     while len(out) < n:
         control = _u8(b, p)
         p += 1
+        _t("delta_run", "zero" if control & 0x80 else "words" if control & 0x40 else "bytes", min((control & 0x3F) + 1, n - len(out)))
         for _ in range((control & 0x3F) + 1):
             if len(out) == n:
                 break
@@ -328,11 +343,15 @@ def read_deltas(b, p, n):
 def infer(p, pa, pb, da, db):
     """G5, one coordinate of one untouched point"""
     if pa == pb:
+        _t("infer", "equal_coordinates_equal_deltas" if da == db else "equal_coordinates_unequal_deltas")
         return da if da == db else f32(0)
     if p <= min(pa, pb):
+        _t("infer", "at_the_low_end" if p == min(pa, pb) else "below_the_pair")
         return da if pa < pb else db
     if p >= max(pa, pb):
+        _t("infer", "at_the_high_end" if p == max(pa, pb) else "above_the_pair")
         return da if pa > pb else db
+    _t("infer", "between")
     d = f32(f32(p - pa) / f32(pb - pa))
     return f32(f32(f32(f32(1) - d) * da) + f32(d * db))
 
@@ -386,6 +405,8 @@ def accumulate(gvar, gid, coords, n, xs=None, ys=None, last=None):
         for i in range(n_axes):
             fac = V.axis_factor(coords[i], start[i], peak[i], end[i])
             scalar = f32(0) if fac == 0 or scalar == 0 else f32(scalar * fac)
+        _t("tuple", "embedded_peak" if index & 0x8000 else "shared_peak", "intermediate" if index & 0x4000 else "plain",
+           "private_points" if index & 0x2000 else "shared_points", "skipped" if scalar == 0 else "applied" if scalar == 1 else "scaled")
         if scalar == 0:
             continue
         numbers, p = shared_numbers, 0
@@ -403,6 +424,7 @@ def accumulate(gvar, gid, coords, n, xs=None, ys=None, last=None):
             if number < n + 4:
                 got[number] = [f32(f32(values[k]) * scalar), f32(f32(values[len(numbers) + k]) * scalar)]
         add = dict(got)
+        _t("phantom", any(n <= number < n + 4 for number in numbers), any(number >= n + 4 for number in numbers))
         if last is not None:
             first = 0
             while first < n:
@@ -410,6 +432,7 @@ def accumulate(gvar, gid, coords, n, xs=None, ys=None, last=None):
                 while stop + 1 < n and not last[stop]:
                     stop += 1
                 touched = [i for i in range(first, stop + 1) if i in got]
+                _t("contour", len(touched), stop + 1 - first, first in got, stop in got)
                 if touched:
                     for i in range(first, stop + 1):
                         if i in got:
@@ -605,6 +628,7 @@ def walk(t, coords, gid, depth, tr, out):
             if pts is None:
                 return True
             xs, ys, on, last = pts
+            _t("glyph", "simple", depth, sum(last), len(xs))
             acc = accumulate(t.gvar, gid, coords, len(xs), xs, ys, last)
             moved = [(f32(f32(x) + a[0]), f32(f32(y) + a[1])) for x, y, a in zip(xs, ys, acc)]
             emit(moved, on, last, None if all(a == b for a, b in zip(tr, IDENTITY)) else tr, f32, out)
@@ -612,6 +636,7 @@ def walk(t, coords, gid, depth, tr, out):
         if nc == 0 or len(g) < 10:
             return nc == 0
         recs = components(body)
+        _t("glyph", "composite", depth, len(recs), any(not all(a == b for a, b in zip(k[:4], IDENTITY[:4])) for _, k in recs))
         acc = accumulate(t.gvar, gid, coords, len(recs))
     except Malformed:
         return False
