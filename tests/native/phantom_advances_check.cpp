@@ -7,7 +7,11 @@
 // One line per file: "<path>: placed <axes> <glyph ids> <deltas> <malformed> <advances moved> <checksum>" (the three counts over
 // all positions) | "refused <why>" | "no fvar".
 // Exit 1: an advance that is not the rule's over the delta and the advance of the same face placed without the option, or a face
-// that follows G7 although it should not (or the reverse).
+// that follows G7 although it should not (or the reverse); or a glyph id for which GvarTable::phantom_sums and GvarTable::accumulate
+// (the same glyph id, coordinates and point count, no contours given) disagree: one malformed and the other not, or l / r not the
+// 32 bits of acc[2 * n] / acc[2 * (n + 1)].  Bit equality is the rule's own: nothing is inferred without contours, ascending numbers
+// write no point twice within a tuple, and both add (float)v * scalar for the same tuples in the same order.
+#include "gvar.hpp"
 #include "ttf_face.hpp"
 
 #include <cstdio>
@@ -17,6 +21,75 @@
 #include <iterator>
 #include <string>
 #include <vector>
+
+// G7's point count of the glyph id's own entry, restated over the tables the face hands to the device (Face's own is private):
+// false: the entry is malformed.  This copy is validated where it is used: sums_agree's last line requires that the state and
+// delta the face itself computes (with its own count) are those of the sums taken with this one, so a drift here fails the run.
+static bool own_point_count(const vg::FontTables &t, uint32_t gid, uint32_t &n)
+{
+	n = 0;
+	if (t.n_loca_bytes == 0 || t.n_glyf_bytes == 0 || gid == 0xFFFFu || gid + 1 >= t.loca_entries)
+		return true;
+	const vg::Bytes loca(t.loca, t.n_loca_bytes);
+	const size_t a = t.loca_long ? loca.u32((size_t)gid * 4) : (size_t)loca.u16((size_t)gid * 2) * 2;
+	const size_t b = t.loca_long ? loca.u32((size_t)gid * 4 + 4) : (size_t)loca.u16((size_t)gid * 2 + 2) * 2;
+	if (a >= b || b > t.n_glyf_bytes)
+		return true;
+	const vg::Bytes glyph(t.glyf + a, b - a);
+	if (glyph.size() < 2)
+		return false;
+	const int16_t n_contours = glyph.i16(0);
+	if (n_contours == 0)
+		return true;
+	if (glyph.size() < 10)
+		return false;
+	const vg::Bytes body = glyph.from(10);
+	if (n_contours > 0) {
+		if (!body.has(0, (size_t)n_contours * 2) || body.u16((size_t)(n_contours - 1) * 2) == 0xFFFF)
+			return false;
+		n = (uint32_t)body.u16((size_t)(n_contours - 1) * 2) + 1;
+		return true;
+	}
+	for (size_t p = 0; body.has(p, 4);) { // one point per component record: flags and child, arguments if x and y, transform
+		const uint16_t flags = body.u16(p);
+		const size_t args = (flags & 0x0002) ? ((flags & 0x0001) ? 4 : 2) : 0;
+		const size_t form = (flags & 0x0080) ? 8 : (flags & 0x0040) ? 4 : (flags & 0x0008) ? 2 : 0;
+		if (!body.has(p + 4, args) || !body.has(p + 4 + args, form))
+			break;
+		p += 4 + args + form;
+		n++;
+		if (!(flags & 0x0020))
+			break;
+	}
+	return true;
+}
+
+static uint32_t bits_of(float f)
+{
+	uint32_t u;
+	std::memcpy(&u, &f, 4);
+	return u;
+}
+
+// G7 held against G1 to G5 directly: the advance pass and the outline's accumulation (no contours given: nothing is inferred)
+// refuse the same glyph ids, and where both succeed l and r are bit for bit the x sums of points n and n + 1
+static bool sums_agree(const vg::Face &face, const vg::GvarTable &gvar, const vg::GvarTables &t, uint16_t gid)
+{
+	uint32_t n;
+	if (!own_point_count(t.tables, gid, n))
+		return true; // (a malformed entry: gvar is not asked)
+	const std::vector<int16_t> coords(t.coords, t.coords + t.n_axes);
+	float l, r, d;
+	std::vector<float> acc;
+	const uint8_t state = gvar.phantom_sums(gid, coords, n, l, r);
+	const bool outline = gvar.accumulate(gid, coords, vg::GvarPoints{n}, acc);
+	if (outline != (state != vg::Face::kGvarAdvanceMalformed))
+		return false;
+	if (outline && (acc.size() != (size_t)2 * (n + 4) || bits_of(l) != bits_of(acc[(size_t)2 * n]) || bits_of(r) != bits_of(acc[(size_t)2 * (n + 1)])))
+		return false;
+	// (and the count above is the face's: its own delta is that of these sums)
+	return face.gvar_advance_delta(gid, d) == state && (state != vg::Face::kGvarAdvanceDelta || bits_of(d) == bits_of(r - l));
+}
 
 int main(int argc, char **argv)
 {
@@ -54,7 +127,11 @@ int main(int argc, char **argv)
 			ok = ok && !plain->advances_by_gvar() && (!face->advances_by_gvar() || face->placed_by_gvar());
 			n_glyphs = face->number_of_glyphs();
 			const std::vector<uint16_t> all = face->hor_advances(n_glyphs + 2u);
+			const vg::GvarTables tables = face->gvar_tables();
+			const auto gvar = tables.ok ? vg::GvarTable::parse(vg::Bytes(tables.gvar, tables.gvar_len), tables.n_axes) : std::nullopt;
+			ok = ok && gvar.has_value() == face->placed_by_gvar();
 			for (uint32_t g = 0; g < n_glyphs + 2u && g <= 0xFFFFu; g++) {
+				ok = ok && (!gvar || sums_agree(*face, *gvar, tables, (uint16_t)g));
 				float d = 0.0f;
 				const uint8_t state = face->gvar_advance_delta((uint16_t)g, d);
 				const auto got = face->glyph_hor_advance((uint16_t)g), stood = plain->glyph_hor_advance((uint16_t)g);

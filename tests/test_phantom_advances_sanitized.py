@@ -1,6 +1,9 @@
 """Rule G7's streaming walk under AddressSanitizer and UBSan (CPU): tests/native/phantom_advances_check.cpp, a stand-alone program,
 places a glyf face with advances from gvar's phantom points at four positions and asks every glyph id's delta and advance, for
 every hand-written face of tests/phantom_advances_kit.py, every truncation of their gvar tables and damaged copies of six of them.
+For every glyph id visited the program also holds GvarTable::phantom_sums against GvarTable::accumulate (same glyph id, position
+and point count, no contours): malformed to one exactly where malformed to the other, and l / r the 32 bits of the outline's x sums
+of points n and n + 1 (G7 pinned against G1 to G5 directly).
 Nothing sanitised is loaded into Python, and nothing of this runs on a GPU."""
 import shutil
 import struct

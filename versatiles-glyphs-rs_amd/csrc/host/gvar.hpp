@@ -40,6 +40,10 @@ public:
 	uint32_t glyph_count() const { return glyph_count_; }
 
 private:
+	// G1 to G4, the one walk over a glyph id's tuples that accumulate and phantom_sums both are (ttf_face.cpp states the visitor)
+	enum class Tuples { None, Applied, Malformed };
+	template <class Visit> Tuples applied_tuples(uint16_t glyph_id, const std::vector<int16_t> &coords, Visit &&visit) const;
+
 	Bytes table_;
 	uint32_t axis_count_ = 0, shared_count_ = 0, shared_at_ = 0, glyph_count_ = 0, data_at_ = 0;
 	bool long_offsets_ = false;

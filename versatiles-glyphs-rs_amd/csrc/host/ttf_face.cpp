@@ -794,231 +794,7 @@ std::optional<GvarTable> GvarTable::parse(Bytes table, uint32_t n_axes)
 
 namespace {
 
-// G2: packed point numbers at b[p...]; false: they leave b, or do not ascend
-bool read_point_numbers(Bytes b, size_t &p, bool &all, std::vector<uint16_t> &numbers)
-{
-	numbers.clear();
-	all = false;
-	if (!b.has(p, 1))
-		return false;
-	uint32_t count = b.u8(p++);
-	if (count == 0) {
-		all = true;
-		return true;
-	}
-	if (count & 0x80) {
-		if (!b.has(p, 1))
-			return false;
-		count = ((count & 0x7F) << 8) | b.u8(p++);
-	}
-	uint16_t number = 0;
-	while (numbers.size() < count) {
-		if (!b.has(p, 1))
-			return false;
-		const uint8_t control = b.u8(p++);
-		const bool words = (control & 0x80) != 0;
-		for (uint32_t left = (control & 0x7Fu) + 1; left && numbers.size() < count; left--) {
-			if (!b.has(p, words ? 2 : 1))
-				return false;
-			const uint16_t step = words ? b.u16(p) : b.u8(p);
-			p += words ? 2 : 1;
-			const uint16_t next = (uint16_t)(number + step);
-			if (!numbers.empty() && next <= number)
-				return false;
-			numbers.push_back(number = next);
-		}
-	}
-	return true;
-}
-
-// G3: the packed deltas of a tuple as one stream of values
-struct DeltaStream {
-	Bytes b;
-	size_t p;
-	uint32_t left = 0; // of the run in hand
-	uint8_t control = 0;
-	bool next(int32_t &v)
-	{
-		if (left == 0) {
-			if (!b.has(p, 1))
-				return false;
-			control = b.u8(p++);
-			left = (control & 0x3Fu) + 1;
-		}
-		left--;
-		if (control & 0x80) {
-			v = 0;
-		} else if (control & 0x40) {
-			if (!b.has(p, 2))
-				return false;
-			v = b.i16(p), p += 2;
-		} else {
-			if (!b.has(p, 1))
-				return false;
-			v = (int8_t)b.u8(p), p += 1;
-		}
-		return true;
-	}
-};
-
-// G5: what a point at p takes from the touched points at pa (before it) and pb (behind it) of its contour
-float inferred(int32_t p, int32_t pa, int32_t pb, float da, float db)
-{
-	if (pa == pb)
-		return da == db ? da : 0.0f;
-	if (p <= std::min(pa, pb))
-		return pa < pb ? da : db;
-	if (p >= std::max(pa, pb))
-		return pa > pb ? da : db;
-	const float d = (float)(p - pa) / (float)(pb - pa);
-	return (1.0f - d) * da + d * db;
-}
-
-} // namespace
-
-bool GvarTable::accumulate(uint16_t gid, const std::vector<int16_t> &coords, const GvarPoints &pts, std::vector<float> &acc) const
-{
-	const uint32_t n_all = pts.n + 4;
-	acc.assign((size_t)2 * n_all, 0.0f);
-	if (gid >= glyph_count_ || coords.size() != axis_count_)
-		return true;
-	// G1
-	size_t from, to;
-	if (long_offsets_)
-		from = table_.u32(20 + (size_t)gid * 4), to = table_.u32(24 + (size_t)gid * 4);
-	else
-		from = (size_t)table_.u16(20 + (size_t)gid * 2) * 2, to = (size_t)table_.u16(22 + (size_t)gid * 2) * 2;
-	if (from == to)
-		return true;
-	if (from > to || !table_.has(data_at_, to))
-		return false;
-	const Bytes d = table_.sub(data_at_ + from, to - from);
-	if (!d.has(0, 4))
-		return false;
-	const uint32_t n_tuples = d.u16(0) & 0x0FFFu;
-	const bool have_shared = (d.u16(0) & 0x8000u) != 0;
-	if (n_tuples == 0)
-		return true;
-	size_t cursor = d.u16(2);
-	if (cursor > d.size())
-		return false;
-	bool shared_all = true, all = true;
-	std::vector<uint16_t> shared, own;
-	if (have_shared && !read_point_numbers(d, cursor, shared_all, shared))
-		return false;
-	std::vector<float> sx, sy;
-	std::vector<uint8_t> mark; // 1: touched, 2: inferred
-	std::vector<uint32_t> before, behind;
-	size_t h = 4;
-	const size_t tuple_bytes = (size_t)axis_count_ * 2;
-	for (uint32_t t = 0; t < n_tuples; t++) {
-		if (!d.has(h, 4))
-			return false;
-		const size_t size = d.u16(h);
-		const uint32_t index = d.u16(h + 2);
-		h += 4;
-		Bytes peak, start, end;
-		if (index & 0x8000u) {
-			if (!d.has(h, tuple_bytes))
-				return false;
-			peak = d.sub(h, tuple_bytes);
-			h += tuple_bytes;
-		} else {
-			if ((index & 0x0FFFu) >= shared_count_)
-				return false;
-			peak = table_.sub(shared_at_ + (size_t)(index & 0x0FFFu) * tuple_bytes, tuple_bytes);
-		}
-		if (index & 0x4000u) {
-			if (!d.has(h, 2 * tuple_bytes))
-				return false;
-			start = d.sub(h, tuple_bytes), end = d.sub(h + tuple_bytes, tuple_bytes);
-			h += 2 * tuple_bytes;
-		}
-		if (!d.has(cursor, size))
-			return false;
-		const Bytes data = d.sub(cursor, size);
-		cursor += size;
-		// G4
-		float scalar = 1.0f;
-		for (uint32_t i = 0; i < axis_count_ && scalar != 0.0f; i++) {
-			const int16_t pk = peak.i16((size_t)i * 2);
-			const int16_t st = start.empty() ? std::min<int16_t>(pk, 0) : start.i16((size_t)i * 2);
-			const int16_t en = end.empty() ? std::max<int16_t>(pk, 0) : end.i16((size_t)i * 2);
-			const float f = axis_factor(coords[i], st, pk, en);
-			scalar = f == 0.0f ? 0.0f : scalar * f;
-		}
-		if (scalar == 0.0f)
-			continue;
-		size_t p = 0;
-		const std::vector<uint16_t> *numbers = &shared;
-		all = shared_all;
-		if (index & 0x2000u) {
-			if (!read_point_numbers(data, p, all, own))
-				return false;
-			numbers = &own;
-		}
-		DeltaStream deltas{data, p};
-		int32_t v;
-		if (all) {
-			for (int axis = 0; axis < 2; axis++)
-				for (uint32_t i = 0; i < n_all; i++) {
-					if (!deltas.next(v))
-						return false;
-					acc[(size_t)2 * i + axis] += (float)v * scalar;
-				}
-			continue;
-		}
-		sx.assign(n_all, 0.0f), sy.assign(n_all, 0.0f), mark.assign(n_all, 0);
-		for (int axis = 0; axis < 2; axis++)
-			for (const uint16_t number : *numbers) {
-				if (!deltas.next(v))
-					return false;
-				if (number < n_all) // (a number at or past the count names no point)
-					(axis ? sy : sx)[number] = (float)v * scalar, mark[number] = 1;
-			}
-		if (pts.last_of_contour) {
-			before.resize(pts.n), behind.resize(pts.n);
-			for (uint32_t first = 0; first < pts.n;) {
-				uint32_t last = first;
-				while (last + 1 < pts.n && !pts.last_of_contour[last])
-					last++;
-				uint32_t lo = 0xFFFFFFFFu, hi = 0;
-				for (uint32_t i = first; i <= last; i++)
-					if (mark[i] == 1)
-						lo = std::min(lo, i), hi = i;
-				if (lo != 0xFFFFFFFFu) {
-					// (cyclic: in front of the first touched point lies the last one, behind the last the first)
-					for (uint32_t i = first, at = hi; i <= last; i++) {
-						if (mark[i] == 1)
-							at = i;
-						before[i] = at;
-					}
-					for (uint32_t i = last + 1, at = lo; i-- > first;) {
-						if (mark[i] == 1)
-							at = i;
-						behind[i] = at;
-					}
-					for (uint32_t i = first; i <= last; i++)
-						if (mark[i] == 0) {
-							const uint32_t a = before[i], b = behind[i];
-							sx[i] = inferred(pts.x[i], pts.x[a], pts.x[b], sx[a], sx[b]);
-							sy[i] = inferred(pts.y[i], pts.y[a], pts.y[b], sy[a], sy[b]);
-							mark[i] = 2;
-						}
-				}
-				first = last + 1;
-			}
-		}
-		for (uint32_t i = 0; i < n_all; i++)
-			if (mark[i])
-				acc[(size_t)2 * i] += sx[i], acc[(size_t)2 * i + 1] += sy[i];
-	}
-	return true;
-}
-
-namespace {
-
-// G2 as a stream (G7's walk): the packed point numbers of b from p on, one after the other
+// G2: the packed point numbers of b from p on, one after the other; false: they leave b, or do not ascend
 struct PointNumberStream {
 	Bytes b;
 	size_t p = 0;
@@ -1075,13 +851,60 @@ bool check_point_numbers(Bytes b, size_t p, bool &all, size_t &end)
 	return true;
 }
 
+// G3: the packed deltas of a tuple as one stream of values
+struct DeltaStream {
+	Bytes b;
+	size_t p;
+	uint32_t left = 0; // of the run in hand
+	uint8_t control = 0;
+	bool next(int32_t &v)
+	{
+		if (left == 0) {
+			if (!b.has(p, 1))
+				return false;
+			control = b.u8(p++);
+			left = (control & 0x3Fu) + 1;
+		}
+		left--;
+		if (control & 0x80) {
+			v = 0;
+		} else if (control & 0x40) {
+			if (!b.has(p, 2))
+				return false;
+			v = b.i16(p), p += 2;
+		} else {
+			if (!b.has(p, 1))
+				return false;
+			v = (int8_t)b.u8(p), p += 1;
+		}
+		return true;
+	}
+};
+
+// G5: what a point at p takes from the touched points at pa (before it) and pb (behind it) of its contour
+float inferred(int32_t p, int32_t pa, int32_t pb, float da, float db)
+{
+	if (pa == pb)
+		return da == db ? da : 0.0f;
+	if (p <= std::min(pa, pb))
+		return pa < pb ? da : db;
+	if (p >= std::max(pa, pb))
+		return pa > pb ? da : db;
+	const float d = (float)(p - pa) / (float)(pb - pa);
+	return (1.0f - d) * da + d * db;
+}
+
 } // namespace
 
-uint8_t GvarTable::phantom_sums(uint16_t gid, const std::vector<int16_t> &coords, uint32_t n, float &l, float &r) const
+// The one walk over a glyph id's tuples, rules G1 to G4 and nothing else: accumulate and phantom_sums are this walk with a visitor
+// each, so what is malformed to the outline is malformed to the advances (G7).  Of every tuple whose scalar is not zero
+// visit(scalar, all, numbers_in, numbers_at, deltas): all, or the tuple's point numbers are those of numbers_in from numbers_at
+// on (check_point_numbers has passed them); deltas (a DeltaStream) stands at the tuple's first delta.  The visitor returns
+// false for malformed.  Tuples::None: no variation data (nothing was visited), Applied, or Malformed.
+template <class Visit> GvarTable::Tuples GvarTable::applied_tuples(uint16_t gid, const std::vector<int16_t> &coords, Visit &&visit) const
 {
-	l = r = 0.0f;
 	if (gid >= glyph_count_ || coords.size() != axis_count_)
-		return Face::kGvarAdvanceNone;
+		return Tuples::None;
 	// G1
 	size_t from, to;
 	if (long_offsets_)
@@ -1089,53 +912,53 @@ uint8_t GvarTable::phantom_sums(uint16_t gid, const std::vector<int16_t> &coords
 	else
 		from = (size_t)table_.u16(20 + (size_t)gid * 2) * 2, to = (size_t)table_.u16(22 + (size_t)gid * 2) * 2;
 	if (from == to)
-		return Face::kGvarAdvanceNone;
+		return Tuples::None;
 	if (from > to || !table_.has(data_at_, to))
-		return Face::kGvarAdvanceMalformed;
+		return Tuples::Malformed;
 	const Bytes d = table_.sub(data_at_ + from, to - from);
 	if (!d.has(0, 4))
-		return Face::kGvarAdvanceMalformed;
+		return Tuples::Malformed;
 	const uint32_t n_tuples = d.u16(0) & 0x0FFFu;
 	const bool have_shared = (d.u16(0) & 0x8000u) != 0;
 	if (n_tuples == 0)
-		return Face::kGvarAdvanceNone;
+		return Tuples::None;
 	size_t cursor = d.u16(2);
 	if (cursor > d.size())
-		return Face::kGvarAdvanceMalformed;
+		return Tuples::Malformed;
 	bool shared_all = true;
 	size_t shared_at = 0;
 	if (have_shared) {
 		shared_at = cursor;
 		if (!check_point_numbers(d, shared_at, shared_all, cursor))
-			return Face::kGvarAdvanceMalformed;
+			return Tuples::Malformed;
 	}
 	size_t h = 4;
 	const size_t tuple_bytes = (size_t)axis_count_ * 2;
 	for (uint32_t t = 0; t < n_tuples; t++) {
 		if (!d.has(h, 4))
-			return Face::kGvarAdvanceMalformed;
+			return Tuples::Malformed;
 		const size_t size = d.u16(h);
 		const uint32_t index = d.u16(h + 2);
 		h += 4;
 		Bytes peak, start, end;
 		if (index & 0x8000u) {
 			if (!d.has(h, tuple_bytes))
-				return Face::kGvarAdvanceMalformed;
+				return Tuples::Malformed;
 			peak = d.sub(h, tuple_bytes);
 			h += tuple_bytes;
 		} else {
 			if ((index & 0x0FFFu) >= shared_count_)
-				return Face::kGvarAdvanceMalformed;
+				return Tuples::Malformed;
 			peak = table_.sub(shared_at_ + (size_t)(index & 0x0FFFu) * tuple_bytes, tuple_bytes);
 		}
 		if (index & 0x4000u) {
 			if (!d.has(h, 2 * tuple_bytes))
-				return Face::kGvarAdvanceMalformed;
+				return Tuples::Malformed;
 			start = d.sub(h, tuple_bytes), end = d.sub(h + tuple_bytes, tuple_bytes);
 			h += 2 * tuple_bytes;
 		}
 		if (!d.has(cursor, size))
-			return Face::kGvarAdvanceMalformed;
+			return Tuples::Malformed;
 		const Bytes data = d.sub(cursor, size);
 		cursor += size;
 		// G4
@@ -1156,27 +979,108 @@ uint8_t GvarTable::phantom_sums(uint16_t gid, const std::vector<int16_t> &coords
 		if (index & 0x2000u) {
 			numbers_in = data, numbers_at = 0;
 			if (!check_point_numbers(data, 0, all, deltas_at))
-				return Face::kGvarAdvanceMalformed;
+				return Tuples::Malformed;
 		}
 		DeltaStream deltas{data, deltas_at};
+		if (!visit(scalar, all, numbers_in, numbers_at, deltas))
+			return Tuples::Malformed;
+	}
+	return Tuples::Applied;
+}
+
+bool GvarTable::accumulate(uint16_t gid, const std::vector<int16_t> &coords, const GvarPoints &pts, std::vector<float> &acc) const
+{
+	const uint32_t n_all = pts.n + 4;
+	acc.assign((size_t)2 * n_all, 0.0f);
+	std::vector<float> sx, sy;
+	std::vector<uint8_t> mark; // 1: touched, 2: inferred
+	std::vector<uint32_t> before, behind;
+	const auto tuple = [&](float scalar, bool all, Bytes numbers_in, size_t numbers_at, DeltaStream &deltas) {
+		int32_t v;
+		if (all) {
+			for (int axis = 0; axis < 2; axis++)
+				for (uint32_t i = 0; i < n_all; i++) {
+					if (!deltas.next(v))
+						return false;
+					acc[(size_t)2 * i + axis] += (float)v * scalar;
+				}
+			return true;
+		}
+		sx.assign(n_all, 0.0f), sy.assign(n_all, 0.0f), mark.assign(n_all, 0);
+		for (int axis = 0; axis < 2; axis++) { // the numbers once for x and once for y
+			PointNumberStream numbers;
+			(void)numbers.open(numbers_in, numbers_at); // (the walk checked them)
+			while (numbers.got < numbers.count) {
+				uint16_t number = 0;
+				if (!numbers.next(number) || !deltas.next(v))
+					return false;
+				if (number < n_all) // (a number at or past the count names no point)
+					(axis ? sy : sx)[number] = (float)v * scalar, mark[number] = 1;
+			}
+		}
+		if (pts.last_of_contour) {
+			before.resize(pts.n), behind.resize(pts.n);
+			for (uint32_t first = 0; first < pts.n;) {
+				uint32_t last = first;
+				while (last + 1 < pts.n && !pts.last_of_contour[last])
+					last++;
+				uint32_t lo = 0xFFFFFFFFu, hi = 0;
+				for (uint32_t i = first; i <= last; i++)
+					if (mark[i] == 1)
+						lo = std::min(lo, i), hi = i;
+				if (lo != 0xFFFFFFFFu) {
+					// (cyclic: in front of the first touched point lies the last one, behind the last the first)
+					for (uint32_t i = first, at = hi; i <= last; i++) {
+						if (mark[i] == 1)
+							at = i;
+						before[i] = at;
+					}
+					for (uint32_t i = last + 1, at = lo; i-- > first;) {
+						if (mark[i] == 1)
+							at = i;
+						behind[i] = at;
+					}
+					for (uint32_t i = first; i <= last; i++)
+						if (mark[i] == 0) {
+							const uint32_t a = before[i], b = behind[i];
+							sx[i] = inferred(pts.x[i], pts.x[a], pts.x[b], sx[a], sx[b]);
+							sy[i] = inferred(pts.y[i], pts.y[a], pts.y[b], sy[a], sy[b]);
+							mark[i] = 2;
+						}
+				}
+				first = last + 1;
+			}
+		}
+		for (uint32_t i = 0; i < n_all; i++)
+			if (mark[i])
+				acc[(size_t)2 * i] += sx[i], acc[(size_t)2 * i + 1] += sy[i];
+		return true;
+	};
+	return applied_tuples(gid, coords, tuple) != Tuples::Malformed;
+}
+
+uint8_t GvarTable::phantom_sums(uint16_t gid, const std::vector<int16_t> &coords, uint32_t n, float &l, float &r) const
+{
+	l = r = 0.0f;
+	const Tuples walked = applied_tuples(gid, coords, [&](float scalar, bool all, Bytes numbers_in, size_t numbers_at, DeltaStream &deltas) {
 		int32_t v;
 		if (all) {
 			for (uint32_t i = 0; i < 2 * (n + 4); i++) { // the x deltas first
 				if (!deltas.next(v))
-					return Face::kGvarAdvanceMalformed;
+					return false;
 				if (i == n)
 					l += (float)v * scalar;
 				else if (i == n + 1)
 					r += (float)v * scalar;
 			}
-			continue;
+			return true;
 		}
 		PointNumberStream numbers;
-		(void)numbers.open(numbers_in, numbers_at); // (checked above)
+		(void)numbers.open(numbers_in, numbers_at); // (the walk checked them)
 		while (numbers.got < numbers.count) {
 			uint16_t number = 0;
 			if (!numbers.next(number) || !deltas.next(v))
-				return Face::kGvarAdvanceMalformed;
+				return false;
 			if (number == n)
 				l += (float)v * scalar;
 			else if (number == n + 1)
@@ -1184,9 +1088,10 @@ uint8_t GvarTable::phantom_sums(uint16_t gid, const std::vector<int16_t> &coords
 		}
 		for (uint32_t i = 0; i < numbers.count; i++) // the y deltas
 			if (!deltas.next(v))
-				return Face::kGvarAdvanceMalformed;
-	}
-	return Face::kGvarAdvanceDelta;
+				return false;
+		return true;
+	});
+	return walked == Tuples::None ? Face::kGvarAdvanceNone : walked == Tuples::Applied ? Face::kGvarAdvanceDelta : Face::kGvarAdvanceMalformed;
 }
 
 // ---- glyf ------------------------------------------------------------------------------

@@ -257,9 +257,11 @@ public:
 	//   (f32)hmtx advance + (d + 0.5), truncated, none outside 0 .. 65535.  A glyph id at or past glyphCount, with an empty
 	//   range of `gvar` or with tuple count 0 has d = 0.  Malformed data, by G1 to G5's meaning at that position — every applied
 	//   tuple's point numbers and all 2 * count of its deltas are walked, not only those up to n + 1 — or a malformed entry
-	//   gives no delta: the `hmtx` advance stands.  NOT BUILT: USE_MY_METRICS is not consulted (a composite's phantom points take
-	//   the composite's own data, as fontTools does); the outline is not shifted by the left phantom point, as it is not under
-	//   `HVAR`; the vertical phantom points (n + 2, n + 3) are not read.
+	//   gives no delta: the `hmtx` advance stands.  In this reader G1 to G4 are one function (GvarTable::applied_tuples), which
+	//   the outline's accumulation and this rule's sums both call; the device still states them once in its accumulate and once
+	//   in its phantom_sums (profiles/gvar_tuple_walk_ab.txt says why).  NOT BUILT: USE_MY_METRICS is not consulted
+	//   (a composite's phantom points take the composite's own data, as fontTools does); the outline is not shifted by the left
+	//   phantom point, as it is not under `HVAR`; the vertical phantom points (n + 2, n + 3) are not read.
 	// Malformed data of a glyph id — a header, point numbers or deltas that leave the glyph's range, a tuple that ends before
 	// its deltas do — delivers nothing from where the data is needed: outline_glyph returns false there, leaves delivered
 	// before it stay.  PARITY UNPINNED like the rest of the variation code; checked against fontTools and a strict restatement
