@@ -251,6 +251,22 @@ typedef struct {
 	uint64_t faces; /* the faces they were given */
 } vg_gvar_batch_stats;
 int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out);
+/* family tables of all instances of a file in one device build, 0 (default) / 1; has an effect only with
+ * vg_manager_set_family_tables_on_device: when the family of a font id whose ONE file is a placed face that shares its bytes
+ * with other placed faces — the instances of vg_manager_add_font_named_instances, `glyf` + `gvar` and CFF2 alike — is asked
+ * for, the stores of the group's faces are made as today and the family tables of ALL its single-file font ids that the lane's
+ * device lacks are built in one call (vgsdf_families_create_tables: cmap, hmtx and HVAR or loca, glyf and gvar uploaded once,
+ * one phantom pass, one count and one emit pass over all positions), each under its own family's serial.  A refused position is
+ * remembered and gets its table the host's way, counted as any family-table fallback.  A font id of several files (two records
+ * merged into one id), a group of one and a family past the budget stay on the single path.  vg_renderer_preload_fonts is not
+ * touched.  Same families, registry, budget and family-table stats, same output.  Off by default whatever a measurement says
+ * (profiles/family_batch_ab.txt).  vg_manager_family_batch_stats: of the last render. */
+void vg_manager_set_family_tables_batched(vg_manager *m, int on);
+typedef struct {
+	uint64_t calls;    /* batched calls made during the render (a group whose families were all there makes none) */
+	uint64_t families; /* the families they made */
+} vg_family_batch_stats;
+int vg_manager_family_batch_stats(const vg_manager *m, vg_family_batch_stats *out);
 /* advances from gvar's phantom points, 0 (default) / 1: a `glyf` + `gvar` face placed AFTER the call — by
  * vg_manager_add_font_instance, _normalized, vg_manager_add_font_named_instances or the named-instance scan — whose file has no
  * readable `HVAR` takes every glyph id's advance from the deltas of phantom points n and n + 1 of its `gvar` data (rule G7 of
@@ -331,6 +347,10 @@ int vg_manager_add_font_instance_normalized(vg_manager *m, const char *name, con
 #define VG_FONT_ID_MAX 256
 int vg_manager_add_font_named_instances(vg_manager *m, const uint8_t *data, size_t len, char (*ids)[VG_FONT_ID_MAX], int cap);
 void vg_manager_set_scan_named_instances(vg_manager *m, int on);
+/* inspection: the font ids of the faces that share their bytes with the ONE file of font_id — every instance record's id of the
+ * file vg_manager_add_font_named_instances took, in the table's order (an id two records arrive at: twice); the first `cap` into
+ * ids.  Returns their number; 0 for an unknown id, an id of several files or a file added any other way; negative: an error. */
+int vg_manager_instance_group(const vg_manager *m, const char *font_id, char (*ids)[VG_FONT_ID_MAX], int cap);
 /* What a file's `fvar` offers (host only), so that a caller can turn "the named instances of this file" into calls of
  * vg_manager_add_font_instance without a font parser of its own.  _axes: the number of axes, and the first `cap` of them in
  * tags / min / def / max (user space; each array may be NULL).  _named_instances: the number of instance records, and the first

@@ -705,6 +705,47 @@ int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_en
  * vgsdf_family_create_tables took (HIP events around the pass; 0 0 before the first, and for a pass that did not run) */
 void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
 /*
+ * The family tables of ONE FACE AT MANY POSITIONS in one call — the named instances of a variable file, whose stores
+ * vgsdf_fonts_create_gvar (or the CFF2 constructor, position by position) has made.  Position p is a family of one face over
+ * fonts[p]: `tables` is the one face's cmap and hmtx, var[p] its HVAR with the region factors of position p (every record names
+ * the same hvar, hvar_len, store_off, map_off and n_regions: one file has one HVAR or none), gvar the description
+ * vgsdf_fonts_create_gvar takes, with the coordinates of all positions.  What runs once for the call: the tables' upload; the
+ * PHANTOM PASS — only with gvar given and no HVAR described, HVAR wins as in the single call — over (glyph id, position) pairs,
+ * pair index glyph id x n_positions + position, a lane doing for its pair what a lane of vgsdf_gvar_advance_deltas does for its
+ * glyph id (csrc/gvar_advance_batch_kernels.hip: the same device text), into the context's array (now 5 bytes per glyph id AND
+ * position, grown on demand, freed with the context); the count pass, its read-back, the layout and the emit pass, each over a
+ * second grid dimension, the position (csrc/family_table_kernels.hip: the single call's text).  Counts are taken per position:
+ * the command-slot sums come from font p, and the call does not assume the fonts are alike.
+ * out[p] is a family of its own, freed alone: its vgsdf_family_read arrays, vgsdf_family_device_bytes and vgsdf_family_count
+ * cannot be told from what vgsdf_family_create_tables_gvar (_mixed: _gvar_mixed) makes of the one face with fonts[p], var[p]
+ * and the single description at position p.  The same position given twice: two families.
+ *   VGSDF_E_ARG before anything runs, nothing allocated: a NULL argument, more than VGSDF_FAMILY_MAX_POSITIONS positions,
+ *     anything the single calls validate, var records that do not name one HVAR, gvar->n_positions other than n_positions.
+ *   VGSDF_E_GLYF for the whole call, every out[p] NULL, the context sound: a glyph id past VGSDF_GVAR_MAX_DELTAS (the count
+ *     decides before a tuple is walked, whatever the position).
+ *   status[p] VGSDF_E_ARG, out[p] NULL, the other positions built: a code point that maps to a glyph id at or past font p's.
+ *   A HIP error or an exhausted host fails the whole call: nothing left allocated, every out[p] NULL, the context sound.
+ *   n_positions == 0: VGSDF_OK, nothing is touched.
+ */
+#define VGSDF_FAMILY_MAX_POSITIONS 64u
+typedef struct {
+	uint32_t n_positions;              /* 0 .. VGSDF_FAMILY_MAX_POSITIONS */
+	const vgsdf_font *const *fonts;    /* [n_positions]: the face's font at position p; one device, one kind */
+	vgsdf_face_tables tables;          /* the ONE face */
+	const vgsdf_face_variation *var;   /* [n_positions] or NULL; region_scalars differ per position */
+	const vgsdf_fonts_gvar_desc *gvar; /* or NULL; its n_positions must equal n_positions above */
+} vgsdf_families_tables_desc;
+int vgsdf_families_create_tables(vgsdf_ctx *ctx, const vgsdf_families_tables_desc *in, vgsdf_family **out /* [n_positions] */,
+                                 int *status /* [n_positions] */);
+int vgsdf_families_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_families_tables_desc *in, vgsdf_family **out, int *status);
+/* test / inspection: the batched phantom pass alone, read back.  delta, state: [n_positions * num_glyphs] each, position after
+ * position; bit for bit what vgsdf_gvar_advance_deltas gives at each position.  Validation and VGSDF_E_GLYF as there; more than
+ * VGSDF_FAMILY_MAX_POSITIONS positions: VGSDF_E_ARG; none: VGSDF_OK, nothing touched. */
+int vgsdf_gvar_advance_deltas_batch(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *in, float *delta, uint8_t *state);
+/* test / inspection (tools/family_batch_ab.py): milliseconds the phantom, the count and the emit pass of the context's last
+ * vgsdf_families_create_tables took (0 for a pass that did not run; vgsdf_gvar_advance_deltas_batch sets [0] alone) */
+void vgsdf_families_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[3]);
+/*
  * The glyph sequence of a ranges submission: the tasks in order, and inside a task the mapped code points of
  * [first, last] of its family, ascending.  The output is, byte for byte, that of vgsdf_outlines_submit_resident given that
  * sequence with the families' fonts, the entries' scale and shift_x, pbf_pre[g] = the task's value on its first glyph and 0

@@ -81,6 +81,9 @@ struct vgsdf_ctx {
 	// vgsdf_family_create_tables_gvar: the phantom pass's output for the call's faces, read by its emit pass; grown on demand,
 	// belongs to no family (the call ends with a synchronisation)
 	DevBuf gvar_advance;
+	// phantom / count / emit kernels of the last vgsdf_families_create_tables (one face at many positions: 5 bytes per glyph id and
+	// position of gvar_advance above); [0] alone of the last vgsdf_gvar_advance_deltas_batch
+	float families_tables_ms[3] = {0.0f, 0.0f, 0.0f};
 	// vgsdf_font_create_gvar, vgsdf_fonts_create_gvar: the deltas pass's scratch for one launch (GvarScratch: 13 bytes per point of
 	// at most 2^17 points — points x positions in the batched call —, or of one glyph id at one position); grown on demand, belongs
 	// to no font

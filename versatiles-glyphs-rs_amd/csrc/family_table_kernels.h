@@ -39,6 +39,12 @@ struct FamilyFaceGvar {
 	uint32_t pad;
 };
 static_assert(sizeof(FamilyFaceGvar) == 24, "one 24-byte record per face");
+// the batched passes' table of one position: where the emit pass writes FamilyTableLayout(n_entries); table 0: nothing is emitted
+struct FamilyBatchTable {
+	uint64_t table;
+	uint32_t n_entries, pad;
+};
+static_assert(sizeof(FamilyBatchTable) == 16, "one 16-byte record per position");
 struct FamilySubtable {
 	uint32_t off, format; // into cmap; 0 4 6 10 12 13
 };
@@ -67,4 +73,11 @@ int vgsdf_family_tables_emit_var(const vgsdf::FamilyFaceRef *faces, const vgsdf:
 // ... and some of which take their advance's delta from gvar's phantom points: gvar[n_faces] beside var[n_faces]
 int vgsdf_family_tables_emit_gvar(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, const vgsdf::FamilyFaceGvar *gvar,
                                   uint32_t n_faces, const uint32_t *counts, uint32_t n_entries, uint8_t *table, hipStream_t stream);
+// The same passes for ONE face at n_positions positions, the position a second grid dimension (vgsdf_families_create_tables):
+// faces[p] is the face with font p's store; counts[4 x kFamilyGroups x p ..] and flags[p] (zeroed) are position p's.
+int vgsdf_family_tables_batch_count(const vgsdf::FamilyFaceRef *faces, uint32_t n_positions, uint32_t *counts, uint32_t *flags, hipStream_t stream);
+// tables[p]: position p's table and its counted entries (table 0: skipped); var: NULL or [n_positions]; gvar: NULL or [n_positions]
+// beside var[n_positions]
+int vgsdf_family_tables_batch_emit(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, const vgsdf::FamilyFaceGvar *gvar,
+                                   uint32_t n_positions, const uint32_t *counts, const vgsdf::FamilyBatchTable *tables, hipStream_t stream);
 }

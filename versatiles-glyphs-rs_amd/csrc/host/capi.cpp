@@ -289,6 +289,29 @@ int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out)
 	*out = vg_gvar_batch_stats{t.gvar_batch_calls, t.gvar_batch_faces};
 	return 0;
 }
+void vg_manager_set_family_tables_batched(vg_manager *m, int on) { m->m.set_family_tables_batched(on != 0); }
+int vg_manager_family_batch_stats(const vg_manager *m, vg_family_batch_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_family_batch_stats{t.family_batch_calls, t.family_batch_families};
+	return 0;
+}
+int vg_manager_instance_group(const vg_manager *m, const char *font_id, char (*ids)[VG_FONT_ID_MAX], int cap)
+{
+	try {
+		if (!m || !font_id || cap < 0 || (cap && !ids))
+			return fail("vg_manager_instance_group: bad argument");
+		const std::vector<std::string> group = m->m.instance_group(font_id);
+		for (int k = 0; k < cap && (size_t)k < group.size(); k++) {
+			const size_t n = std::min(group[(size_t)k].size(), (size_t)VG_FONT_ID_MAX - 1);
+			std::memcpy(ids[k], group[(size_t)k].data(), n);
+			ids[k][n] = 0;
+		}
+		return (int)group.size();
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
 void vg_manager_set_gvar_advances(vg_manager *m, int on) { m->m.set_gvar_advances(on != 0); }
 int vg_manager_gvar_advance_stats(const vg_manager *m, vg_gvar_advance_stats *out)
 {

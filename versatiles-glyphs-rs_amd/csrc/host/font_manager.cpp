@@ -300,14 +300,34 @@ bool FontManager::add_font_named_instances(std::vector<uint8_t> data, std::vecto
 	}
 	invalidate_shards();
 	ids.clear();
+	InstanceGroup &group = instance_groups_[bytes->data()];
 	for (auto &e : entries) {
 		gvar_advance_faces_ += e->face().advances_by_gvar();
-		if (e->face().placed_by_gvar())
-			gvar_groups_[e->face().gvar_tables().gvar].push_back(&e->face());
 		ids.push_back(name_to_id(e->metadata().generate_name()));
+		group.faces.push_back(&e->face()), group.ids.push_back(ids.back());
+		instance_bytes_of_[&e->face()] = bytes->data();
 		fonts_[ids.back()].add_file(std::move(e));
 	}
 	return true;
+}
+
+const FontManager::InstanceGroup *FontManager::instance_group_of(const Face &face) const
+{
+	const FontManager &root = parent_ ? *parent_ : *this;
+	const auto key = root.instance_bytes_of_.find(&face);
+	if (key == root.instance_bytes_of_.end())
+		return nullptr;
+	const auto group = root.instance_groups_.find(key->second);
+	return group == root.instance_groups_.end() ? nullptr : &group->second;
+}
+
+std::vector<std::string> FontManager::instance_group(const std::string &font_id) const
+{
+	const auto it = fonts().find(font_id);
+	if (it == fonts().end() || it->second.files().size() != 1)
+		return {};
+	const InstanceGroup *group = instance_group_of(it->second.files()[0]->face());
+	return group ? group->ids : std::vector<std::string>{};
 }
 
 bool FontManager::add_path(const std::string &path, std::string *err)

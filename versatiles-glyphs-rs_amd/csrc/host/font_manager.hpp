@@ -185,6 +185,9 @@ struct RenderTimings {
 	// included (set_family_tables_on_device; counted among family_tables_built too), and those it refused, whose tables came from
 	// the host reader instead (counted among family_table_fallbacks too)
 	uint64_t gvar_advance_builds = 0, gvar_advance_fallbacks = 0;
+	// with set_family_tables_batched: the calls that built the family tables of the instances of one file in one device build
+	// (one per group of faces over the same bytes and device lane) and the families they made (counted among family_tables_built too)
+	uint64_t family_batch_calls = 0, family_batch_families = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -219,10 +222,11 @@ struct RenderTimings {
 		gvar_fonts_built += counts.gvar_fonts_built, gvar_font_bytes += counts.gvar_font_bytes, gvar_fallbacks += counts.gvar_fallbacks;
 		gvar_batch_calls += counts.gvar_batch_calls, gvar_batch_faces += counts.gvar_batch_faces;
 		gvar_advance_builds += counts.gvar_advance_builds, gvar_advance_fallbacks += counts.gvar_advance_fallbacks;
+		family_batch_calls += counts.family_batch_calls, family_batch_families += counts.family_batch_families;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 43 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 45 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -360,6 +364,16 @@ public:
 	// with set_gvar_on_device: the stores of ALL placed glyf faces over the same bytes (add_font_named_instances) that the lane's
 	// device has yet to build, in one call when the first of them is asked for (Renderer::gvar_fonts)
 	void set_gvar_batched(bool on) { gvar_batched_ = on; }
+	// with set_family_tables_on_device: when the family of a font id whose ONE file is a placed face that shares its bytes with
+	// other placed faces (add_font_named_instances, glyf + gvar and CFF2 alike) is asked for, the family tables of ALL such font
+	// ids of that group that the lane's device lacks are built in one call (Renderer::families_from_tables: the tables uploaded
+	// once, one phantom pass, one count and one emit pass over all positions).  A font id of several files (two records merged
+	// into one id), a group of one and a family past the budget stay on the single path.  Same families, same output
+	void set_family_tables_batched(bool on) { family_tables_batched_ = on; }
+	// the font ids of the faces that share their bytes with the ONE file of `font_id` (add_font_named_instances: every record's
+	// id, in the table's order, an id two records arrive at twice); empty: an unknown id, an id of several files, a file added
+	// any other way
+	std::vector<std::string> instance_group(const std::string &font_id) const;
 	// faces placed from now on (add_font_instance, _normalized, add_font_named_instances and the named-instance scan) that are
 	// glyf + gvar without a readable HVAR take their advances from gvar's phantom points (rule G7 of ttf_face.hpp; default off:
 	// their hmtx advances stand).  Not retroactive: stores and families are keyed by serials taken at placement.
@@ -635,9 +649,21 @@ private:
 	bool gvar_batched_ = false, scan_named_instances_ = false;
 	bool gvar_advances_ = false;
 	uint64_t gvar_advance_faces_ = 0;
-	// the placed glyf faces that share their bytes, by the address of their gvar table (the faces of add_font_named_instances; a
-	// child manager reads its parent's); a group of one makes no batched call
-	std::map<const uint8_t *, std::vector<const Face *>> gvar_groups_;
+	// the placed faces that share their bytes — the faces add_font_named_instances made of one file, glyf + gvar or CFF2 —, by the
+	// address of those bytes, each with the font id it went to (a child manager reads its parent's); a group of one makes no
+	// batched call
+	struct InstanceGroup {
+		std::vector<const Face *> faces;
+		std::vector<std::string> ids;
+	};
+	std::map<const uint8_t *, InstanceGroup> instance_groups_;
+	std::map<const Face *, const uint8_t *> instance_bytes_of_; // a grouped face -> its group's key
+	const InstanceGroup *instance_group_of(const Face &face) const;
+	bool family_tables_batched_ = false;
+	// family_tables_batched_: the families of the single-file font ids of `font`'s instance group that the device has yet to
+	// build, in one call; the family_from_tables of each behind it finds its family (or goes the way of one that was refused or
+	// did not fit); counts into `counts`
+	void families_batched(const Renderer &renderer, int lane, const FontWrapper &font, StoreKind kind, RenderTimings &counts) const;
 	// gvar_batched_: the command stores of `face`'s group that the device has yet to build, in one call; the gvar_font of each face
 	// behind it finds its store (or goes the way of a face that was refused or did not fit); counts into `counts`
 	void gvar_stores_batched(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;

@@ -344,12 +344,11 @@ void FontManager::gvar_stores_batched(const Renderer &renderer, int lane, const 
 {
 	if (!gvar_batched_)
 		return;
-	const auto &groups = parent_ ? parent_->gvar_groups_ : gvar_groups_;
-	const auto group = groups.find(face.gvar_tables().gvar);
-	if (group == groups.end() || group->second.size() < 2)
+	const InstanceGroup *group = instance_group_of(face);
+	if (!group || group->faces.size() < 2)
 		return; // (a face with bytes of its own: its own call)
 	std::vector<Renderer::GvarJob> faces;
-	for (const Face *f : group->second)
+	for (const Face *f : group->faces)
 		faces.push_back(Renderer::GvarJob{f->command_serial(), f->gvar_tables()});
 	std::vector<Renderer::TablesOutcome> outcomes;
 	renderer.gvar_fonts(lane, faces, outcomes, &counts.gvar_batch_calls, &counts.gvar_batch_faces);
@@ -359,6 +358,52 @@ void FontManager::gvar_stores_batched(const Renderer &renderer, int lane, const 
 		if (o.built) {
 			count_upload(o.uploaded, counts.gvar_fonts_built, counts.gvar_font_bytes);
 			count_upload(o.uploaded, counts.command_fonts_uploaded, counts.command_font_bytes);
+		}
+	}
+}
+
+void FontManager::families_batched(const Renderer &renderer, int lane, const FontWrapper &font, StoreKind kind, RenderTimings &counts) const
+{
+	if (!family_tables_on_device_ || !family_tables_batched_ || kind == StoreKind::Glyf || font.files().size() != 1)
+		return; // (a placed face has no glyf form: its family is over command stores, alone or mixed)
+	const InstanceGroup *group = instance_group_of(font.files()[0]->face());
+	if (!group || group->faces.size() < 2)
+		return;
+	std::vector<Renderer::FamilyJob> jobs;
+	for (size_t k = 0; k < group->faces.size(); k++) {
+		const auto it = fonts().find(group->ids[k]);
+		if (it == fonts().end() || it->second.files().size() != 1)
+			continue; // (two records merged into one id: a family of two files, the single way)
+		const Face &face = *group->faces[k];
+		const FamilyTables &t = face.family_tables();
+		if (!t.ok)
+			continue; // (the single way refuses it and counts that)
+		FamilyTable *shell = family_shell(it->first, 1);
+		{
+			std::lock_guard<std::mutex> lock(family_mu_of());
+			if (shell->refused)
+				continue;
+		}
+		const vgsdf_font *store = command_store(renderer, lane, face, counts); // (gvar_stores_batched inside, as today)
+		if (!store)
+			continue; // (over the budget)
+		jobs.push_back(Renderer::FamilyJob{shell->serial, store, &t, face.advances_by_gvar() ? face.gvar_tables() : GvarTables{}});
+	}
+	if (jobs.size() < 2)
+		return;
+	std::vector<Renderer::FamilyOutcome> outcomes;
+	renderer.families_from_tables(lane, jobs, kind == StoreKind::Mixed ? Renderer::kFamilyMixed : Renderer::kFamilyCommands, outcomes,
+	                              &counts.family_batch_calls, &counts.family_batch_families);
+	for (size_t i = 0; i < outcomes.size(); i++) { // (as device_family counts what family_from_tables says)
+		const Renderer::FamilyOutcome &o = outcomes[i];
+		if (o.refused) {
+			counts.family_table_fallbacks++;
+			counts.gvar_advance_fallbacks += jobs[i].gvar.ok;
+		}
+		if (o.built) {
+			count_upload(o.uploaded, counts.families_uploaded, counts.family_bytes);
+			counts.family_tables_built++;
+			counts.gvar_advance_builds += jobs[i].gvar.ok;
 		}
 	}
 }
@@ -441,6 +486,8 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 	std::vector<const vgsdf_font *> stores;
 	if (kind == StoreKind::Glyf || (kind == StoreKind::Mixed && !glyf_refused_.count(&font_id)))
 		glyf_stores_batched(renderer, lane, font, counts);
+	if (on_device)
+		families_batched(renderer, lane, font, kind, counts); // (the lookup below then finds the family)
 	for (const auto &file : font.files()) {
 		bool glyf = kind == StoreKind::Glyf;
 		const vgsdf_font *f = kind == StoreKind::Mixed ? file_store(renderer, lane, font_id, file->face(), counts, &glyf)

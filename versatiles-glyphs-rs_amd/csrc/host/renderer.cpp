@@ -803,6 +803,96 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 	return rf.keep(rf.families, key, f, vgsdf_family_device_bytes(f), uploaded_bytes);
 }
 
+void Renderer::families_from_tables(int lane, const std::vector<FamilyJob> &jobs, int kind, std::vector<FamilyOutcome> &outcomes, uint64_t *calls,
+                                    uint64_t *n_families) const
+{
+	outcomes.assign(jobs.size(), FamilyOutcome{});
+	if (mode_ != Mode::Hip)
+		return;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	std::vector<size_t> sent;
+	const FamilyJob *first = nullptr;
+	auto flush = [&] {
+		if (sent.empty())
+			return;
+		const FamilyTables &t = *first->tables;
+		std::vector<const vgsdf_font *> fonts;
+		std::vector<vgsdf_face_variation> var;
+		std::vector<int16_t> coords;
+		for (size_t i : sent) {
+			const FamilyTables &ti = *jobs[i].tables;
+			fonts.push_back(jobs[i].font);
+			if (t.hvar)
+				var.push_back(vgsdf_face_variation{ti.hvar, ti.hvar_len, ti.hvar_store, ti.hvar_map, ti.region_scalars.data(), (uint32_t)ti.region_scalars.size()});
+			if (first->gvar.ok)
+				coords.insert(coords.end(), jobs[i].gvar.coords, jobs[i].gvar.coords + jobs[i].gvar.n_axes);
+		}
+		vgsdf_fonts_gvar_desc g{};
+		if (first->gvar.ok) {
+			const GvarTables &gt = first->gvar;
+			g.tables = tables_desc(gt.tables);
+			g.gvar = gt.gvar, g.gvar_len = gt.gvar_len, g.n_axes = gt.n_axes, g.coords = coords.data(), g.n_positions = (uint32_t)sent.size();
+		}
+		vgsdf_families_tables_desc d{};
+		d.n_positions = (uint32_t)sent.size();
+		d.fonts = fonts.data();
+		d.tables.cmap = t.cmap, d.tables.cmap_len = t.cmap_len, d.tables.hmtx = t.hmtx, d.tables.hmtx_len = t.hmtx_len;
+		d.tables.units_per_em = t.units_per_em, d.tables.num_glyphs = t.num_glyphs, d.tables.num_hmetrics = t.num_hmetrics;
+		d.tables.n_subtables = (uint16_t)t.subtable_off.size();
+		d.tables.subtable_off = t.subtable_off.data(), d.tables.subtable_format = t.subtable_format.data();
+		d.var = var.empty() ? nullptr : var.data();
+		d.gvar = first->gvar.ok ? &g : nullptr;
+		std::vector<vgsdf_family *> made(sent.size(), nullptr);
+		std::vector<int> status(sent.size(), 0);
+		vgsdf_ctx *c = lane_ctx(lane & 1);
+		std::lock_guard<std::mutex> lock(mu_);
+		const int rc = kind == kFamilyMixed ? vgsdf_families_create_tables_mixed(c, &d, made.data(), status.data())
+		                                    : vgsdf_families_create_tables(c, &d, made.data(), status.data());
+		*calls += 1;
+		for (size_t k = 0; k < sent.size(); k++) {
+			const auto key = std::make_tuple(device_, jobs[sent[k]].serial, kind);
+			FamilyOutcome &o = outcomes[sent[k]];
+			if (rc != VGSDF_OK || status[k] != VGSDF_OK) { // (the whole call, or this position alone: the host's way, for good)
+				rf.refused_family_tables.insert(key);
+				o.refused = true;
+				continue;
+			}
+			// the budget as family() holds it
+			const uint64_t want = vgsdf::FamilyTableLayout(vgsdf_family_count(made[k], 0, 0xFFFF)).bytes;
+			if (rf.bytes[device_] + want > rf.budget) {
+				(void)vgsdf_family_free(c, made[k]);
+				continue;
+			}
+			o.built = true;
+			*n_families += 1;
+			rf.keep(rf.families, key, made[k], vgsdf_family_device_bytes(made[k]), &o.uploaded);
+		}
+		sent.clear();
+	};
+	std::set<uint64_t> seen;
+	for (size_t i = 0; i < jobs.size(); i++) {
+		const FamilyJob &j = jobs[i];
+		const auto key = std::make_tuple(device_, j.serial, kind);
+		if (!j.tables || !j.tables->ok || !j.font || rf.find(rf.families, key) || rf.refused_family_tables.count(key))
+			continue;
+		if (!seen.insert(j.serial).second)
+			continue; // (a family named twice: one family)
+		if (!first)
+			first = &j;
+		const FamilyTables &a = *j.tables, &b = *first->tables;
+		if (a.cmap != b.cmap || a.hmtx != b.hmtx || a.hvar != b.hvar || a.hvar_len != b.hvar_len || a.hvar_store != b.hvar_store ||
+		    a.hvar_map != b.hvar_map || a.region_scalars.size() != b.region_scalars.size() || j.gvar.ok != first->gvar.ok ||
+		    (j.gvar.ok && (j.gvar.gvar != first->gvar.gvar || j.gvar.n_axes != first->gvar.n_axes || j.gvar.tables.glyf != first->gvar.tables.glyf ||
+		                   j.gvar.tables.loca != first->gvar.tables.loca)))
+			continue; // (not over the first job's tables: its own family_from_tables builds it)
+		if (sent.size() == VGSDF_FAMILY_MAX_POSITIONS)
+			flush();
+		sent.push_back(i);
+	}
+	flush();
+}
+
 void Renderer::family_names(int lane, const vgsdf_family *family, std::vector<uint16_t> &code_point, std::vector<uint32_t> &advance) const
 {
 	vgsdf_ctx *c = lane_ctx(lane & 1);

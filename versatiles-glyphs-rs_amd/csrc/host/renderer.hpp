@@ -539,6 +539,26 @@ public:
 	                                       const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
 	                                       bool *built, const std::vector<vgsdf_face_variation> &variation = {},
 	                                       const std::vector<const vgsdf_font_gvar_desc *> &gvar = {}) const;
+	// family_from_tables for the families of ONE file's placed faces, a family of one face each (vgsdf_families_create_tables: the
+	// tables uploaded once, one phantom pass, one count and one emit pass over all positions), in as few calls as their number
+	// allows.  Shaped like gvar_fonts: under the registry's lock for the whole of it; a job is sent when its tables are ok and
+	// those of the first job sent (the same cmap, hmtx and HVAR bytes, the same gvar or none), the registry has no family under
+	// (device, serial, kind) and the key is not remembered as refused; outcomes[i], the registry and the refused set are left as
+	// family_from_tables would leave them (a refused position, or every position of a call that failed, is remembered; a family
+	// past the budget is freed and not remembered), so that a family_from_tables of any of the jobs behind this call finds its
+	// family, or goes the way it went.  *calls / *n_families: the calls made, the families they made
+	struct FamilyJob {
+		uint64_t serial = 0;                  // of the family's shell
+		const vgsdf_font *font = nullptr;     // the face's store on this device
+		const FamilyTables *tables = nullptr; // the face's: hvar and region_scalars at its position
+		GvarTables gvar;                      // ok: the face's advances follow gvar's phantom points
+	};
+	struct FamilyOutcome {
+		bool refused = false, built = false;
+		uint64_t uploaded = 0;
+	};
+	void families_from_tables(int lane, const std::vector<FamilyJob> &jobs, int kind, std::vector<FamilyOutcome> &outcomes, uint64_t *calls,
+	                          uint64_t *n_families) const;
 	// a family's code points and advances, read back (what a host that built no table names the glyphs of a ranges group by)
 	void family_names(int lane, const vgsdf_family *family, std::vector<uint16_t> &code_point, std::vector<uint32_t> &advance) const;
 	// a submission of code-point ranges of such families (n_glyphs: for the first capacity guess), and where its tasks'

@@ -43,6 +43,14 @@ VGSDF_INTERNAL size_t gvar_advance_bytes(uint32_t n_glyph_ids);
 VGSDF_INTERNAL size_t gvar_advance_state_at(uint32_t n_glyph_ids);
 VGSDF_INTERNAL int gvar_advance_on_device(vgsdf_ctx *ctx, const char *entry, const vgsdf_font_gvar_desc *desc, uint8_t *out, float *ms);
 
+// ... and over one placed glyf face at MANY positions (gvar_advance_batch_kernels.h): the same trio over vgsdf_fonts_gvar_desc
+// (n_positions 1 .. VGSDF_FAMILY_MAX_POSITIONS), one launch over (glyph id, position) pairs; `out` holds delta [n_positions x
+// num_glyphs] f32 at 0 and the state bytes at gvar_advance_batch_state_at, position after position
+VGSDF_INTERNAL int gvar_advance_batch_described(vgsdf_ctx *ctx, const char *entry, const vgsdf_fonts_gvar_desc *desc);
+VGSDF_INTERNAL size_t gvar_advance_batch_bytes(uint32_t n_glyph_ids, uint32_t n_positions);
+VGSDF_INTERNAL size_t gvar_advance_batch_state_at(uint32_t n_glyph_ids, uint32_t n_positions);
+VGSDF_INTERNAL int gvar_advance_batch_on_device(vgsdf_ctx *ctx, const char *entry, const vgsdf_fonts_gvar_desc *desc, uint8_t *out, float *ms);
+
 // The calls of a constructor on its stream, in order, up to the first that fails: after it nothing more is issued, and the
 // caller hands `e` to font_hip_error under the name of the phase it is in.  A constructor ends with sync(): its store is complete
 // on the device when the call returns, so every context may name the font or family.

@@ -1,12 +1,14 @@
 // resident_families.cpp — the families over resident fonts (resident_fonts.cpp): a font id's table
 // code point -> (font, glyph id, advance, scale, shift_x) on host and device (upload_layout.h, FamilyTableLayout), stated by the
-// host (vgsdf_family_create) or built by the device from the faces' cmap and hmtx (vgsdf_family_create_tables), for submissions
+// host (vgsdf_family_create) or built by the device from the faces' cmap and hmtx (vgsdf_family_create_tables; for one face at
+// many positions, a family each, by one call: vgsdf_families_create_tables), for submissions
 // that name code-point ranges (vgsdf_outlines_submit_ranges).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <new>
+#include <vector>
 
 #include "family_table_kernels.h"
 #include "resident_build.h"
@@ -136,6 +138,42 @@ const char *variation_refused(const vgsdf_face_variation &v)
 	return nullptr;
 }
 
+// the host's copy of a table the device built, from its one read-back (FamilyTableLayout(n)); the 64-bit running sums from the
+// table's differences (exact: a glyph holds fewer than 2^31 slots and fewer than 2^32 leaves)
+void adopt_table(vgsdf_family &f, const uint8_t *back, uint32_t n)
+{
+	const vgsdf::FamilyTableLayout at(n);
+	auto slice = [&](auto &v, size_t off, size_t count) {
+		v.resize(count);
+		if (count)
+			std::memcpy(v.data(), back + off, sizeof(v[0]) * count);
+	};
+	slice(f.scale, at.scale, n), slice(f.shift_x, at.shift_x, n), slice(f.advance, at.advance, n), slice(f.code_point, at.code_point, n);
+	slice(f.font_of, at.font_of, n), slice(f.glyph_id, at.glyph_id, n), slice(f.pbf_fix, at.pbf_fix, n);
+	f.cmd_pre.assign((size_t)n + 1, 0);
+	f.leaf_pre.assign((size_t)n + 1, 0);
+	const uint32_t *cp32 = (const uint32_t *)(back + at.cmd_pre), *lp32 = (const uint32_t *)(back + at.leaf_pre);
+	for (uint32_t i = 0; i < n; i++) {
+		f.cmd_pre[i + 1] = f.cmd_pre[i] + (uint32_t)(cp32[i + 1] - cp32[i]);
+		f.leaf_pre[i + 1] = f.leaf_pre[i] + (uint32_t)(lp32[i + 1] - lp32[i]);
+	}
+}
+
+// what vgsdf_family_create_tables validates of one face's tables; nullptr: nothing against them
+const char *face_tables_refused(const vgsdf_face_tables &t)
+{
+	if ((t.cmap_len && !t.cmap) || (t.hmtx_len && !t.hmtx) || (t.n_subtables && (!t.subtable_off || !t.subtable_format)))
+		return "a NULL table or subtable array of a length that is not 0";
+	if (t.units_per_em < 16 || t.units_per_em > 16384)
+		return "units_per_em not 16 .. 16384";
+	for (uint32_t s = 0; s < t.n_subtables; s++) {
+		const uint16_t fm = t.subtable_format[s];
+		if (t.subtable_off[s] >= t.cmap_len || !(fm == 0 || fm == 4 || fm == 6 || fm == 10 || fm == 12 || fm == 13))
+			return "a subtable offset at or past cmap_len, or a format that is not 0, 4, 6, 10, 12 or 13";
+	}
+	return nullptr;
+}
+
 // vgsdf_family_create_tables and vgsdf_family_create_tables_mixed (the kernels take the kind face by face: FamilyFaceRef::commands)
 // and their _var forms (var: NULL, or a record per face) and _gvar forms (gvar: NULL, or per face a description or NULL)
 int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out, bool mixed,
@@ -169,20 +207,9 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 			ctx->err = std::string(me) + ": " + kFontsRefused[mixed];
 			return VGSDF_E_ARG;
 		}
-		if ((t.cmap_len && !t.cmap) || (t.hmtx_len && !t.hmtx) || (t.n_subtables && (!t.subtable_off || !t.subtable_format))) {
-			ctx->err = std::string(me) + ": a NULL table or subtable array of a length that is not 0";
+		if (const char *why = face_tables_refused(t)) {
+			ctx->err = std::string(me) + ": " + why;
 			return VGSDF_E_ARG;
-		}
-		if (t.units_per_em < 16 || t.units_per_em > 16384) {
-			ctx->err = std::string(me) + ": units_per_em not 16 .. 16384";
-			return VGSDF_E_ARG;
-		}
-		for (uint32_t s = 0; s < t.n_subtables; s++) {
-			const uint16_t fm = t.subtable_format[s];
-			if (t.subtable_off[s] >= t.cmap_len || !(fm == 0 || fm == 4 || fm == 6 || fm == 10 || fm == 12 || fm == 13)) {
-				ctx->err = std::string(me) + ": a subtable offset at or past cmap_len, or a format that is not 0, 4, 6, 10, 12 or 13";
-				return VGSDF_E_ARG;
-			}
 		}
 		n_subtables += t.n_subtables;
 		table_bytes += align_up(t.cmap_len, 4) + align_up(t.hmtx_len, 4);
@@ -340,25 +367,215 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 	if (q.failed())
 		return font_hip_error(ctx, me, "emit pass", q.e);
 	ev.elapsed(ctx->family_tables_ms, 1);
-	// the host's copy from the one read-back; the 64-bit running sums from the table's differences (exact: a glyph holds fewer
-	// than 2^31 slots and fewer than 2^32 leaves)
-	auto slice = [&](auto &v, size_t off, size_t count) {
-		v.resize(count);
-		if (count)
-			std::memcpy(v.data(), back.data() + off, sizeof(v[0]) * count);
-	};
-	slice(f->scale, at.scale, n), slice(f->shift_x, at.shift_x, n), slice(f->advance, at.advance, n), slice(f->code_point, at.code_point, n);
-	slice(f->font_of, at.font_of, n), slice(f->glyph_id, at.glyph_id, n), slice(f->pbf_fix, at.pbf_fix, n);
-	f->cmd_pre.assign((size_t)n + 1, 0);
-	f->leaf_pre.assign((size_t)n + 1, 0);
-	const uint32_t *cp32 = (const uint32_t *)(back.data() + at.cmd_pre), *lp32 = (const uint32_t *)(back.data() + at.leaf_pre);
-	for (uint32_t i = 0; i < n; i++) {
-		f->cmd_pre[i + 1] = f->cmd_pre[i] + (uint32_t)(cp32[i + 1] - cp32[i]);
-		f->leaf_pre[i + 1] = f->leaf_pre[i] + (uint32_t)(lp32[i + 1] - lp32[i]);
-	}
+	adopt_table(*f, back.data(), n);
 	// (scales_plain stays true: every scale is 24 / units_per_em of a checked units_per_em)
 	*out = f.release();
 	return VGSDF_OK;
+}
+
+// vgsdf_families_create_tables and _mixed: family_create_tables for ONE face at all positions of a call, position p a family of one
+// face over fonts[p].  The tables go up once; the phantom pass (a gvar description and no HVAR) runs once over (glyph id,
+// position) pairs into the context's array; the count pass, its read-back, the layout and the emit pass run once each with the
+// position as the grid's second dimension; two synchronisations behind the phantom pass's
+int families_create_tables(vgsdf_ctx *ctx, const vgsdf_families_tables_desc *in, vgsdf_family **out, int *status, bool mixed, const char *me)
+{
+	if (!in) {
+		ctx->err = std::string(me) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	const uint32_t n_pos = in->n_positions;
+	if (n_pos == 0)
+		return VGSDF_OK;
+	if (!out || !status || !in->fonts) {
+		ctx->err = std::string(me) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if (n_pos > VGSDF_FAMILY_MAX_POSITIONS) {
+		ctx->err = std::string(me) + ": more than 64 positions in one call";
+		return VGSDF_E_ARG;
+	}
+	for (uint32_t p = 0; p < n_pos; p++)
+		out[p] = nullptr, status[p] = VGSDF_OK;
+	ctx->families_tables_ms[0] = ctx->families_tables_ms[1] = ctx->families_tables_ms[2] = 0.0f;
+	const vgsdf_face_tables &t = in->tables;
+	const vgsdf_face_variation *var = in->var;
+	const vgsdf_fonts_gvar_desc *gvar = in->gvar;
+	for (uint32_t p = 0; p < n_pos; p++)
+		if (!family_font_fits(ctx, in->fonts, p, mixed)) {
+			ctx->err = std::string(me) + ": " + kFontsRefused[mixed];
+			return VGSDF_E_ARG;
+		}
+	if (const char *why = face_tables_refused(t)) {
+		ctx->err = std::string(me) + ": " + why;
+		return VGSDF_E_ARG;
+	}
+	if (var)
+		for (uint32_t p = 0; p < n_pos; p++) {
+			if (const char *why = variation_refused(var[p])) {
+				ctx->err = std::string(me) + ": " + why;
+				return VGSDF_E_ARG;
+			}
+			if (var[p].hvar != var[0].hvar || var[p].hvar_len != var[0].hvar_len || var[p].store_off != var[0].store_off ||
+			    var[p].map_off != var[0].map_off || var[p].n_regions != var[0].n_regions) {
+				ctx->err = std::string(me) + ": variation records that do not name one HVAR table (hvar, hvar_len, store_off, map_off, n_regions)";
+				return VGSDF_E_ARG;
+			}
+		}
+	if (gvar) {
+		if (const int rc = gvar_advance_batch_described(ctx, me, gvar); rc != VGSDF_OK)
+			return rc;
+		if (gvar->n_positions != n_pos) {
+			ctx->err = std::string(me) + ": a gvar description of another number of positions";
+			return VGSDF_E_ARG;
+		}
+	}
+	const bool any_var = var && var[0].hvar, any_gvar = gvar && !any_var; // (a face with both descriptions uses HVAR)
+	const bool with_var = any_var || any_gvar;
+	const uint32_t n_regions = any_var ? var[0].n_regions : 0, hvar_len = any_var ? var[0].hvar_len : 0;
+	std::vector<std::unique_ptr<vgsdf_family>> made(n_pos); // freed on every way out but the last
+	for (uint32_t p = 0; p < n_pos; p++) {
+		made[p].reset(new vgsdf_family());
+		adopt_fonts(*made[p], ctx, in->fonts + p, 1, mixed);
+	}
+	// the staging block: FamilyFaceRef[n_pos] | FamilySubtable[all] | cmap, hmtx (4-aligned) | with a variation: FamilyFaceVar[n_pos]
+	// (zeroed without HVAR) | HVAR | factors [n_pos x n_regions] | FamilyFaceGvar[n_pos] | then, 16-aligned: FamilyBatchTable[n_pos]
+	// (uploaded behind the count pass) | counts [n_pos x 4 x kFamilyGroups] | flags [n_pos]
+	const size_t per_counts = (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups;
+	const size_t a_subs = sizeof(vgsdf::FamilyFaceRef) * (size_t)n_pos, a_bytes = a_subs + sizeof(vgsdf::FamilySubtable) * (size_t)t.n_subtables,
+	             a_var = align_up(a_bytes + align_up(t.cmap_len, 4) + align_up(t.hmtx_len, 4), 8), a_hvar = a_var + (with_var ? sizeof(vgsdf::FamilyFaceVar) * (size_t)n_pos : 0),
+	             a_scalars = a_hvar + align_up(hvar_len, 4), a_gvar = align_up(a_scalars + 4 * (size_t)n_regions * n_pos, 8),
+	             a_tables = align_up(a_gvar + (any_gvar ? sizeof(vgsdf::FamilyFaceGvar) * (size_t)n_pos : 0), 16),
+	             a_counts = a_tables + sizeof(vgsdf::FamilyBatchTable) * (size_t)n_pos, a_flags = a_counts + 4 * per_counts * n_pos,
+	             a_total = align_up(a_flags + 4 * (size_t)n_pos, 16);
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	ScratchBuf dev;
+	if (hipError_t e = dev.ensure(a_total + 16); e != hipSuccess)
+		return font_hip_error(ctx, me, "hipMalloc", e);
+	uint8_t *d = (uint8_t *)dev.p;
+	const uint32_t n_ids = any_gvar ? gvar->tables.num_glyphs : 0;
+	if (any_gvar) { // the phantom pass, once (nothing in flight reads the context's array: every call that does ends synchronised)
+		if (hipError_t e = ctx->gvar_advance.ensure(gvar_advance_batch_bytes(n_ids, n_pos) + 16); e != hipSuccess)
+			return font_hip_error(ctx, me, "hipMalloc", e);
+		if (const int rc = gvar_advance_batch_on_device(ctx, me, gvar, (uint8_t *)ctx->gvar_advance.p, &ctx->families_tables_ms[0]); rc != VGSDF_OK)
+			return rc;
+	}
+	std::vector<uint8_t> h(a_tables, 0);
+	{
+		vgsdf::FamilyFaceRef *faces = (vgsdf::FamilyFaceRef *)h.data();
+		vgsdf::FamilySubtable *subs = (vgsdf::FamilySubtable *)(h.data() + a_subs);
+		for (uint32_t s = 0; s < t.n_subtables; s++)
+			subs[s] = vgsdf::FamilySubtable{t.subtable_off[s], t.subtable_format[s]};
+		const size_t at_hmtx = a_bytes + align_up(t.cmap_len, 4);
+		if (t.cmap_len)
+			std::memcpy(h.data() + a_bytes, t.cmap, t.cmap_len);
+		if (t.hmtx_len)
+			std::memcpy(h.data() + at_hmtx, t.hmtx, t.hmtx_len);
+		if (any_var)
+			std::memcpy(h.data() + a_hvar, var[0].hvar, hvar_len);
+		for (uint32_t p = 0; p < n_pos; p++) {
+			const vgsdf_font &ft = *in->fonts[p];
+			vgsdf::FamilyFaceRef &r = faces[p];
+			r.subtables = (uint64_t)(uintptr_t)(d + a_subs);
+			r.cmap = (uint64_t)(uintptr_t)(d + a_bytes);
+			r.hmtx = t.hmtx_len ? (uint64_t)(uintptr_t)(d + at_hmtx) : 0;
+			r.off = ft.commands ? ft.cref.cmd_off : ft.ref.leaf_off;
+			r.leaves = ft.commands ? 0 : ft.ref.leaves;
+			r.cmap_len = t.cmap_len, r.hmtx_len = t.hmtx_len;
+			r.n_glyph_ids = ft.n_glyph_ids;
+			r.units_per_em = t.units_per_em, r.num_glyphs = t.num_glyphs, r.num_hmetrics = t.num_hmetrics, r.n_subtables = t.n_subtables;
+			r.commands = ft.commands ? 1u : 0u;
+			if (any_var) {
+				vgsdf::FamilyFaceVar &v = ((vgsdf::FamilyFaceVar *)(h.data() + a_var))[p];
+				const size_t at = a_scalars + 4 * (size_t)n_regions * p;
+				v.hvar = (uint64_t)(uintptr_t)(d + a_hvar);
+				v.scalars = (uint64_t)(uintptr_t)(d + at);
+				if (n_regions)
+					std::memcpy(h.data() + at, var[p].region_scalars, 4 * (size_t)n_regions);
+				v.hvar_len = hvar_len, v.store_off = var[0].store_off, v.map_off = var[0].map_off, v.n_regions = n_regions;
+			}
+			if (any_gvar) { // position p's slices of the batched phantom pass
+				const uint8_t *o = (const uint8_t *)ctx->gvar_advance.p;
+				((vgsdf::FamilyFaceGvar *)(h.data() + a_gvar))[p] =
+				    vgsdf::FamilyFaceGvar{(uint64_t)(uintptr_t)(o + 4 * (size_t)n_ids * p),
+				                          (uint64_t)(uintptr_t)(o + gvar_advance_batch_state_at(n_ids, n_pos) + (size_t)n_ids * p), n_ids, 0};
+			}
+		}
+	}
+	PassEvents ev;
+	if (hipError_t err = ev.create(); err != hipSuccess)
+		return font_hip_error(ctx, me, "hipEventCreate", err);
+	const vgsdf::FamilyFaceRef *faces = (const vgsdf::FamilyFaceRef *)d;
+	uint32_t *counts = (uint32_t *)(d + a_counts), *flags = (uint32_t *)(d + a_flags);
+	Calls q(st);
+	q.copy(d, h.data(), h.size());
+	q.zero(d + a_flags, 4 * (size_t)n_pos);
+	q.record(ev.at[0]);
+	q.launch([&] { return vgsdf_family_tables_batch_count(faces, n_pos, counts, flags, st); });
+	q.record(ev.at[1]);
+	std::vector<uint32_t> got((per_counts + 1) * n_pos); // the counts and, behind them, the positions' flag words
+	q.read_back(got.data(), counts, 4 * got.size());
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, me, "count pass", q.e);
+	ev.elapsed(ctx->families_tables_ms + 1, 0);
+	// per position: refused, or a table as vgsdf_family_create allocates it (the same size: the same vgsdf_family_device_bytes)
+	std::vector<vgsdf::FamilyBatchTable> tables(n_pos, vgsdf::FamilyBatchTable{0, 0, 0});
+	std::vector<std::vector<uint8_t>> back(n_pos);
+	uint32_t n_built = 0;
+	for (uint32_t p = 0; p < n_pos; p++) {
+		if (got[per_counts * n_pos + p]) {
+			ctx->err = std::string(me) + ": position " + std::to_string(p) + ": a glyph id past its face";
+			status[p] = VGSDF_E_ARG;
+			made[p].reset();
+			continue;
+		}
+		uint32_t n = 0;
+		for (uint32_t w = 0; w < vgsdf::kFamilyGroups; w++)
+			n += got[per_counts * p + vgsdf::kFamilyCounts * w];
+		const vgsdf::FamilyTableLayout at(n);
+		if (hipError_t err = made[p]->table.ensure(at.bytes + 16); err != hipSuccess)
+			return font_hip_error(ctx, me, "hipMalloc", err);
+		tables[p] = vgsdf::FamilyBatchTable{(uint64_t)(uintptr_t)made[p]->table.p, n, 0};
+		back[p].resize(at.bytes);
+		n_built++;
+	}
+	if (n_built == 0)
+		return VGSDF_OK;
+	q.copy(d + a_tables, tables.data(), sizeof(vgsdf::FamilyBatchTable) * (size_t)n_pos);
+	q.record(ev.at[1]);
+	q.launch([&] {
+		return vgsdf_family_tables_batch_emit(faces, with_var ? (const vgsdf::FamilyFaceVar *)(d + a_var) : nullptr,
+		                                      any_gvar ? (const vgsdf::FamilyFaceGvar *)(d + a_gvar) : nullptr, n_pos, counts,
+		                                      (const vgsdf::FamilyBatchTable *)(d + a_tables), st);
+	});
+	q.record(ev.at[2]);
+	for (uint32_t p = 0; p < n_pos; p++)
+		if (made[p] && !back[p].empty())
+			q.read_back(back[p].data(), made[p]->table.p, back[p].size());
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, me, "emit pass", q.e);
+	ev.elapsed(ctx->families_tables_ms + 1, 1);
+	for (uint32_t p = 0; p < n_pos; p++)
+		if (made[p])
+			adopt_table(*made[p], back[p].data(), tables[p].n_entries);
+	for (uint32_t p = 0; p < n_pos; p++)
+		out[p] = made[p].release();
+	return VGSDF_OK;
+}
+
+// the exported pair: no context, no call; an exhausted host fails the call whole (the families made so far are freed on the way)
+int families_create_tables_guarded(vgsdf_ctx *ctx, const vgsdf_families_tables_desc *in, vgsdf_family **out, int *status, bool mixed, const char *me)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	try {
+		return families_create_tables(ctx, in, out, status, mixed, me);
+	} catch (const std::bad_alloc &) {
+		ctx->err = std::string(me) + ": out of host memory";
+		return VGSDF_E_OOM;
+	}
 }
 
 } // namespace
@@ -399,6 +616,21 @@ int vgsdf_family_create_tables_gvar_mixed(vgsdf_ctx *ctx, const vgsdf_family_tab
                                           const vgsdf_font_gvar_desc *const *gvar, vgsdf_family **out)
 {
 	return family_create_tables(ctx, in, var, out, true, "vgsdf_family_create_tables_gvar_mixed", gvar);
+}
+
+int vgsdf_families_create_tables(vgsdf_ctx *ctx, const vgsdf_families_tables_desc *in, vgsdf_family **out, int *status)
+{
+	return families_create_tables_guarded(ctx, in, out, status, false, "vgsdf_families_create_tables");
+}
+int vgsdf_families_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_families_tables_desc *in, vgsdf_family **out, int *status)
+{
+	return families_create_tables_guarded(ctx, in, out, status, true, "vgsdf_families_create_tables_mixed");
+}
+void vgsdf_families_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[3])
+{
+	if (ms)
+		for (int i = 0; i < 3; i++)
+			ms[i] = ctx ? ctx->families_tables_ms[i] : 0.0f;
 }
 
 void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]) { pass_ms_out(ctx ? ctx->family_tables_ms : nullptr, ms); }

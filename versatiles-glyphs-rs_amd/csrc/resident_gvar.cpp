@@ -7,6 +7,7 @@
 #include <memory>
 #include <new>
 
+#include "gvar_advance_batch_kernels.h"
 #include "gvar_advance_kernels.h"
 #include "gvar_kernels.h"
 #include "gvar_limits.h"
@@ -532,6 +533,81 @@ int gvar_advance_on_device(vgsdf_ctx *ctx, const char *name, const vgsdf_font_gv
 	return VGSDF_OK;
 }
 
+// The phantom pass over one face at MANY positions (gvar_advance_batch_kernels.h), for vgsdf_gvar_advance_deltas_batch and
+// vgsdf_families_create_tables.  _described: n_positions 1 .. VGSDF_FAMILY_MAX_POSITIONS and the description validated as
+// create_gvar_batch validates it (VGSDF_E_ARG).  _bytes / _state_at: what the pass writes for n glyph ids at n_pos positions,
+// delta [n_pos x n] f32 at 0 | state [n_pos x n] bytes | flags, each 16-aligned, position-major.  _on_device, over a description
+// that passed _described: the tables and all coordinates uploaded once into an arena of the call's own, ONE launch over all
+// pairs into `o`, its flag word read back, synchronisation; *ms: the pass's milliseconds.
+namespace {
+struct GvarAdvanceBatchLayout {
+	size_t delta = 0, state, flags, total;
+	constexpr GvarAdvanceBatchLayout(size_t n, size_t n_pos)
+	    : state(align_up(4 * n * n_pos, 16)), flags(align_up(state + n * n_pos, 16)), total(flags + 4 * vgsdf::GVAR_ADVANCE_FLAG_WORDS)
+	{
+	}
+};
+static_assert(GvarAdvanceBatchLayout(5, 1).state == GvarAdvanceLayout(5).state && GvarAdvanceBatchLayout(5, 1).total == GvarAdvanceLayout(5).total &&
+                  GvarAdvanceBatchLayout(5, 3).state == 64 && GvarAdvanceBatchLayout(5, 3).flags == 80,
+              "delta | state | flags over glyph ids x positions; one position: the single pass's layout");
+} // namespace
+int gvar_advance_batch_described(vgsdf_ctx *ctx, const char *name, const vgsdf_fonts_gvar_desc *desc)
+{
+	if (!desc || !tables_given(desc->tables) || !desc->gvar || !desc->coords) {
+		ctx->err = std::string(name) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if (desc->n_positions == 0 || desc->n_positions > VGSDF_FAMILY_MAX_POSITIONS) {
+		ctx->err = std::string(name) + ": a gvar description of no position or of more than 64";
+		return VGSDF_E_ARG;
+	}
+	vgsdf::GvarRef face{};
+	return gvar_face_described(ctx, name, desc->tables, desc->gvar, desc->gvar_len, desc->n_axes, face) ? VGSDF_OK : VGSDF_E_ARG;
+}
+size_t gvar_advance_batch_bytes(uint32_t n, uint32_t n_pos) { return GvarAdvanceBatchLayout(n, n_pos).total; }
+size_t gvar_advance_batch_state_at(uint32_t n, uint32_t n_pos) { return GvarAdvanceBatchLayout(n, n_pos).state; }
+
+int gvar_advance_batch_on_device(vgsdf_ctx *ctx, const char *name, const vgsdf_fonts_gvar_desc *desc, uint8_t *o, float *ms)
+{
+	*ms = 0.0f;
+	const vgsdf_font_tables_desc &in = desc->tables;
+	const uint32_t n = in.num_glyphs, n_pos = desc->n_positions;
+	vgsdf::GvarRef face{};
+	if (!gvar_face_described(ctx, name, in, desc->gvar, desc->gvar_len, desc->n_axes, face))
+		return VGSDF_E_ARG;
+	(void)hipSetDevice(ctx->device);
+	PassEvents ev;
+	if (hipError_t err = ev.create(); err != hipSuccess)
+		return font_hip_error(ctx, name, "hipEventCreate", err);
+	const GvarArenaLayout arena(in.n_loca_bytes, in.n_glyf_bytes, desc->gvar_len, desc->n_axes, 0, n_pos, false);
+	const GvarAdvanceBatchLayout at(n, n_pos);
+	ScratchBuf dev;
+	if (hipError_t e = dev.ensure(arena.total + 16); e != hipSuccess)
+		return font_hip_error(ctx, name, "hipMalloc", e);
+	uint8_t *a = (uint8_t *)dev.p;
+	Calls q(ctx->stream);
+	upload_gvar_face(q, a, arena, in, desc->gvar, desc->gvar_len, desc->n_axes, desc->coords, n_pos, face);
+	q.zero(o + at.flags, 4 * vgsdf::GVAR_ADVANCE_FLAG_WORDS);
+	q.record(ev.at[0]);
+	if (n)
+		q.launch([&] {
+			return vgsdf_gvar_advance_batch_pass(&face, (const int16_t *)(a + arena.coords), n_pos, (float *)(o + at.delta), o + at.state,
+			                                     (uint32_t *)(o + at.flags), q.st);
+		});
+	q.record(ev.at[1]);
+	uint32_t flags[vgsdf::GVAR_ADVANCE_FLAG_WORDS] = {};
+	q.read_back(flags, o + at.flags, sizeof flags);
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, name, "phantom pass", q.e);
+	(void)hipEventElapsedTime(ms, ev.at[0], ev.at[1]);
+	if (flags[vgsdf::GVAR_ADVANCE_FLAG_DELTAS]) {
+		ctx->err = std::string(name) + ": a glyph past VGSDF_GVAR_MAX_DELTAS";
+		return VGSDF_E_GLYF;
+	}
+	return VGSDF_OK;
+}
+
 namespace {
 // what both `…_kernel_ms` getters answer: the context's count / deltas / emit triple of the last call, zeros without a context
 void gvar_ms_out(const float *triple, float ms[3])
@@ -615,5 +691,42 @@ int vgsdf_gvar_advance_deltas(vgsdf_ctx *ctx, const vgsdf_font_gvar_desc *in, fl
 }
 
 float vgsdf_gvar_advance_kernel_ms(const vgsdf_ctx *ctx) { return ctx ? ctx->gvar_advance_ms : 0.0f; }
+
+int vgsdf_gvar_advance_deltas_batch(vgsdf_ctx *ctx, const vgsdf_fonts_gvar_desc *in, float *delta, uint8_t *state)
+{
+	if (!ctx)
+		return VGSDF_E_ARG;
+	const char *name = "vgsdf_gvar_advance_deltas_batch";
+	if (!in) {
+		ctx->err = std::string(name) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if (in->n_positions == 0)
+		return VGSDF_OK;
+	ctx->families_tables_ms[0] = ctx->families_tables_ms[1] = ctx->families_tables_ms[2] = 0.0f;
+	if (!delta || !state) {
+		ctx->err = std::string(name) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	try {
+		if (const int rc = gvar_advance_batch_described(ctx, name, in); rc != VGSDF_OK)
+			return rc;
+		const size_t pairs = (size_t)in->tables.num_glyphs * in->n_positions;
+		ScratchBuf out;
+		if (hipError_t e = out.ensure(gvar_advance_batch_bytes(in->tables.num_glyphs, in->n_positions) + 16); e != hipSuccess)
+			return font_hip_error(ctx, name, "hipMalloc", e);
+		if (const int rc = gvar_advance_batch_on_device(ctx, name, in, (uint8_t *)out.p, &ctx->families_tables_ms[0]); rc != VGSDF_OK)
+			return rc;
+		if (pairs) {
+			HIP_TRY(ctx, hipMemcpy(delta, out.p, 4 * pairs, hipMemcpyDeviceToHost));
+			HIP_TRY(ctx, hipMemcpy(state, (const uint8_t *)out.p + gvar_advance_batch_state_at(in->tables.num_glyphs, in->n_positions), pairs,
+			                       hipMemcpyDeviceToHost));
+		}
+		return VGSDF_OK;
+	} catch (const std::bad_alloc &) {
+		ctx->err = std::string(name) + ": out of host memory";
+		return VGSDF_E_OOM;
+	}
+}
 
 } // extern "C"

@@ -102,6 +102,10 @@ class _CFamilyTablesDesc(C.Structure):  # vgsdf_family_tables_desc
     _fields_ = [("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("tables", C.c_void_p)]
 
 
+class _CFamiliesTablesDesc(C.Structure):  # vgsdf_families_tables_desc
+    _fields_ = [("n_positions", C.c_uint32), ("fonts", C.c_void_p), ("tables", _CFaceTables), ("var", C.c_void_p), ("gvar", C.c_void_p)]
+
+
 class _CFontTablesDesc(C.Structure):  # vgsdf_font_tables_desc
     _fields_ = [("num_glyphs", C.c_uint32), ("loca_entries", C.c_uint32), ("loca_long", C.c_uint32), ("n_loca_bytes", C.c_uint32),
                 ("n_glyf_bytes", C.c_uint32), ("loca", C.c_void_p), ("glyf", C.c_void_p)]
@@ -137,6 +141,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_outlines_submit_resident_mixed", "vgsdf_family_create_mixed", "vgsdf_family_create_tables_mixed",
     "vgsdf_family_create_tables_var", "vgsdf_family_create_tables_var_mixed",
     "vgsdf_gvar_advance_deltas", "vgsdf_gvar_advance_kernel_ms", "vgsdf_family_create_tables_gvar", "vgsdf_family_create_tables_gvar_mixed",
+    "vgsdf_families_create_tables", "vgsdf_families_create_tables_mixed", "vgsdf_gvar_advance_deltas_batch", "vgsdf_families_tables_kernel_ms",
 ]
 
 _lib = None
@@ -232,6 +237,11 @@ def load_library():
         L.vgsdf_gvar_advance_deltas.argtypes = [vp, C.POINTER(_CFontGvarDesc), vp, vp]
         L.vgsdf_gvar_advance_kernel_ms.argtypes = [vp]
         L.vgsdf_gvar_advance_kernel_ms.restype = C.c_float
+        L.vgsdf_families_create_tables.argtypes = [vp, vp, vp, vp]
+        L.vgsdf_families_create_tables_mixed.argtypes = [vp, vp, vp, vp]
+        L.vgsdf_gvar_advance_deltas_batch.argtypes = [vp, vp, vp, vp]
+        L.vgsdf_families_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_families_tables_kernel_ms.restype = None
         L.vgsdf_family_read.argtypes = [vp, vp, C.POINTER(C.c_uint32)] + [vp] * 9
         L.vgsdf_family_tables_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_family_tables_kernel_ms.restype = None
@@ -953,6 +963,104 @@ class SdfContext:
         self._check(getattr(load_library(), entry)(self._h, C.byref(d), None if no_records else C.cast(vrecs, C.c_void_p),
                                                    None if no_gvar else C.cast(gptrs, C.c_void_p), C.byref(h)))
         return ResidentFamily(self, h, fonts)
+
+    @staticmethod
+    def _fonts_gvar_desc(desc: dict, positions, keep: list, override=None):
+        """vgsdf_fonts_gvar_desc of a dict as font_create_gvar takes it (its own "coords" is not looked at) and `positions` (each
+        n_axes normalised int16 coordinates); override: n_positions, n_axes, num_glyphs, loca_entries, n_loca_bytes, n_glyf_bytes,
+        gvar_len; the arrays it points to are appended to keep"""
+        override = override or {}
+        loca, glyf = np.frombuffer(bytes(desc["loca"]), dtype=np.uint8), np.frombuffer(bytes(desc["glyf"]), dtype=np.uint8)
+        gvar = np.frombuffer(bytes(desc["gvar"]), dtype=np.uint8)
+        coords = np.ascontiguousarray(np.asarray(positions, dtype=np.int16).reshape(len(positions), -1 if len(positions) else 0))
+        keep += [loca, glyf, gvar, coords]
+        d = _CFontsGvarDesc()
+        d.tables = _CFontTablesDesc(int(override.get("num_glyphs", desc["num_glyphs"])), int(override.get("loca_entries", desc["loca_entries"])),
+                                    int(desc["loca_long"]), override.get("n_loca_bytes", len(loca)), override.get("n_glyf_bytes", len(glyf)),
+                                    loca.ctypes.data if len(loca) else None, glyf.ctypes.data if len(glyf) else None)
+        d.gvar = gvar.ctypes.data if len(gvar) else None
+        d.gvar_len = override.get("gvar_len", len(gvar))
+        d.n_axes = override.get("n_axes", coords.shape[1] if len(positions) else len(desc["coords"]))
+        d.coords = coords.ctypes.data if coords.size else None
+        d.n_positions = int(override.get("n_positions", len(positions)))
+        return d
+
+    def gvar_advance_deltas_batch(self, desc: dict, positions, **override):
+        """vgsdf_gvar_advance_deltas_batch: the phantom pass alone over ONE placed `glyf` face (desc as font_create_gvar takes it)
+        at every position of `positions` in one launch, read back -> (delta float32[n_positions, num_glyphs], state uint8[same]).
+        override: as gvar_advance_deltas, and n_positions.  VgsdfError with code VGSDF_E_GLYF: a glyph id past VGSDF_GVAR_MAX_DELTAS"""
+        keep = []
+        d = self._fonts_gvar_desc(desc, positions, keep, override)
+        n, n_pos = int(d.tables.num_glyphs), len(positions)
+        delta, state = np.full(max(n * n_pos, 1), np.nan, np.float32), np.full(max(n * n_pos, 1), 0xEE, np.uint8)
+        self._check(load_library().vgsdf_gvar_advance_deltas_batch(self._h, C.addressof(d), delta.ctypes.data, state.ctypes.data))
+        return delta[:n * n_pos].reshape(n_pos, n), state[:n * n_pos].reshape(n_pos, n)
+
+    def families_create_tables(self, fonts, face, variation=None, gvar=None, positions=None, mixed=False, **override):
+        """vgsdf_families_create_tables (mixed: its _mixed twin): the family tables of ONE face at len(fonts) positions in one call.
+        fonts: the face's ResidentFont at each position; face: one dict as FontManager.family_tables_desc returns it; variation:
+        None or per position what FontManager.family_variation_desc returns (records whose "hvar" bytes are equal share one
+        buffer, as the call demands); gvar: None or a dict as font_create_gvar takes it, with `positions` the coordinates of every
+        position -> (families, statuses), each a list per position: a ResidentFamily or None, VGSDF_OK or VGSDF_E_ARG for a
+        position whose font lacks a glyph id the face maps.  VgsdfError: the whole call failed.
+        override (for calls that lie): n_positions; gvar_n_positions; null: the names among "desc", "fonts", "out", "status" to
+        pass as NULL; every other key is a raw field of the gvar description (as gvar_advance_deltas_batch)"""
+        keep, n_fonts = [], len(fonts)
+        null = set(override.pop("null", ()))
+        n = int(override.pop("n_positions", n_fonts))
+        gvar_n = override.pop("gvar_n_positions", None)
+        d = _CFamiliesTablesDesc()
+        d.n_positions = n
+        handles = (C.c_void_p * max(n_fonts, 1))(*[f._h if f is not None else None for f in fonts])
+        d.fonts = None if "fonts" in null else C.cast(handles, C.c_void_p)
+        t, r = face, d.tables
+        cmap, hmtx = np.frombuffer(bytes(t["cmap"]), dtype=np.uint8), np.frombuffer(bytes(t["hmtx"]), dtype=np.uint8)
+        off, fmt = np.ascontiguousarray(t["subtable_off"], dtype=np.uint32), np.ascontiguousarray(t["subtable_format"], dtype=np.uint16)
+        assert len(off) == len(fmt)
+        keep += [cmap, hmtx, off, fmt]
+        r.cmap, r.cmap_len = (cmap.ctypes.data if len(cmap) else None), len(cmap)
+        r.hmtx, r.hmtx_len = (hmtx.ctypes.data if len(hmtx) else None), len(hmtx)
+        r.units_per_em, r.num_glyphs, r.num_hmetrics = int(t["units_per_em"]), int(t["num_glyphs"]), int(t["num_hmetrics"])
+        r.n_subtables = len(off)
+        r.subtable_off, r.subtable_format = (off.ctypes.data if len(off) else None), (fmt.ctypes.data if len(fmt) else None)
+        if variation is not None:
+            assert len(variation) == n_fonts
+            vrecs, shared = (_CFaceVariation * max(n_fonts, 1))(), {}
+            for rec, v in zip(vrecs, variation):
+                if not v:
+                    continue
+                raw = bytes(v["hvar"])
+                hv = shared.setdefault(raw, np.frombuffer(raw, dtype=np.uint8))
+                sc = np.ascontiguousarray(v["region_scalars"], dtype=np.float32)
+                keep += [hv, sc]
+                rec.hvar, rec.hvar_len = (hv.ctypes.data if len(hv) else None), int(v.get("hvar_len", len(hv)))
+                rec.store_off, rec.map_off = int(v["store_off"]), int(v["map_off"])
+                rec.region_scalars, rec.n_regions = (sc.ctypes.data if len(sc) else None), len(sc)
+            keep.append(vrecs)
+            d.var = C.cast(vrecs, C.c_void_p)
+        if gvar is not None:
+            g = self._fonts_gvar_desc(gvar, positions if positions is not None else [], keep, override)
+            if gvar_n is not None:
+                g.n_positions = int(gvar_n)
+            keep.append(g)
+            d.gvar = C.addressof(g)
+        room = max(n_fonts, n if n <= 4096 else 0, 1)
+        out, status = (C.c_void_p * room)(), (C.c_int * room)()
+        entry = "vgsdf_families_create_tables" + ("_mixed" if mixed else "")
+        try:
+            self._check(getattr(load_library(), entry)(self._h, None if "desc" in null else C.addressof(d), None if "out" in null else out,
+                                                       None if "status" in null else status))
+        except VgsdfError:
+            assert not any(out[i] for i in range(room)), "a failed call left a family behind"
+            raise
+        k = min(n, n_fonts)
+        return ([ResidentFamily(self, C.c_void_p(out[i]), [fonts[i]]) if out[i] else None for i in range(k)], [int(status[i]) for i in range(k)])
+
+    def families_tables_kernel_ms(self):
+        """(phantom, count, emit) pass milliseconds of this context's last families_create_tables"""
+        ms = (C.c_float * 3)()
+        load_library().vgsdf_families_tables_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1]), float(ms[2])
 
     def family_read(self, family: ResidentFamily) -> dict:
         """vgsdf_family_read: the DEVICE's copy of a family's table, whichever call made it"""

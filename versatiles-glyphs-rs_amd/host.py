@@ -75,6 +75,10 @@ class GlyfTableBatchStats(C.Structure):  # vg_glyf_table_batch_stats
     _fields_ = [("calls", C.c_uint64), ("faces", C.c_uint64)]
 
 
+class FamilyBatchStats(C.Structure):  # vg_family_batch_stats
+    _fields_ = [("calls", C.c_uint64), ("families", C.c_uint64)]
+
+
 class CharstringStats(C.Structure):  # vg_charstring_stats
     _fields_ = [(k, C.c_uint64) for k in ("fonts_decoded", "font_bytes", "fallbacks")]
 
@@ -116,6 +120,7 @@ VGFONT_SYMBOLS = [
     "vg_manager_add_font_instance", "vg_manager_add_font_instance_normalized", "vg_font_variation_axes", "vg_font_named_instances",
     "vg_manager_family_variation_desc", "vg_manager_font_position", "vg_manager_font_hor_advances",
     "vg_manager_add_font_named_instances", "vg_manager_set_scan_named_instances", "vg_manager_set_gvar_batched", "vg_manager_gvar_batch_stats",
+    "vg_manager_set_family_tables_batched", "vg_manager_family_batch_stats", "vg_manager_instance_group",
     "vg_manager_set_gvar_advances", "vg_manager_gvar_advance_stats", "vg_manager_font_gvar_advance_deltas",
     "vg_manager_family_gvar_desc",
 ]
@@ -184,6 +189,10 @@ def _L():
         L.vg_manager_set_gvar_batched.argtypes = [vp, C.c_int]
         L.vg_manager_set_gvar_batched.restype = None
         L.vg_manager_gvar_batch_stats.argtypes = [vp, C.POINTER(GlyfTableBatchStats)]
+        L.vg_manager_set_family_tables_batched.argtypes = [vp, C.c_int]
+        L.vg_manager_set_family_tables_batched.restype = None
+        L.vg_manager_family_batch_stats.argtypes = [vp, C.POINTER(FamilyBatchStats)]
+        L.vg_manager_instance_group.argtypes = [vp, C.c_char_p, vp, C.c_int]
         L.vg_manager_set_lane_form.argtypes = [vp, C.c_int]
         L.vg_manager_set_lane_form.restype = None
         L.vg_manager_plan_lanes.argtypes = [vp, C.c_char_p, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
@@ -631,6 +640,29 @@ class FontManager:
         s = GlyfTableBatchStats()  # (vg_gvar_batch_stats has the same two fields)
         _L().vg_manager_gvar_batch_stats(self._h, C.byref(s))
         return {k: int(getattr(s, k)) for k, _ in GlyfTableBatchStats._fields_}
+
+    def set_family_tables_batched(self, on: bool):
+        """with set_family_tables_on_device: the family tables of all single-file font ids over the same bytes
+        (add_font_named_instances) are built in ONE call (vgsdf_families_create_tables) instead of one per font id; same
+        families, same output (default off)"""
+        _L().vg_manager_set_family_tables_batched(self._h, int(bool(on)))
+
+    def family_batch_stats(self) -> dict:
+        """of the last render: {calls, families} of the batched family-table builds (vg_family_batch_stats)"""
+        s = FamilyBatchStats()
+        _L().vg_manager_family_batch_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in FamilyBatchStats._fields_}
+
+    def instance_group(self, font_id: str):
+        """vg_manager_instance_group: the font ids of the faces that share their bytes with the one file of font_id (every record
+        of the file add_font_named_instances took, in the table's order); [] for a static file, a merged id, an unknown id"""
+        L = _L()
+        cap = 4096
+        ids = ((C.c_char * VG_FONT_ID_MAX) * cap)()
+        n = L.vg_manager_instance_group(self._h, font_id.encode(), ids, cap)
+        if n < 0:
+            raise RuntimeError(_err())
+        return [ids[k].value.decode() for k in range(min(n, cap))]
 
     def set_gvar_advances(self, on: bool):
         """vg_manager_set_gvar_advances: glyf + gvar faces placed AFTER the call whose file has no readable HVAR take their
