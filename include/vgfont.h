@@ -251,6 +251,22 @@ typedef struct {
 	uint64_t faces; /* the faces they were given */
 } vg_gvar_batch_stats;
 int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out);
+/* CFF2 command stores of all instances of a file in one device build, 0 (default) / 1; has an effect only with
+ * vg_manager_set_charstrings_on_device(m, 2): when the command store of a placed CFF2 face that shares its bytes with other placed
+ * faces — the instances of vg_manager_add_font_named_instances; files added with vg_manager_add_font_instance keep their own
+ * copies and their own calls — is asked for, the stores of ALL faces of that group that the lane's device lacks and that are not
+ * remembered as refused or as not fitting are built in one call (vgsdf_fonts_create_charstrings2_within: the charstrings uploaded
+ * once, the count and the emit pass over all positions), each under its own command serial.  A refused position gets its store
+ * from the host reader, counted in vg_charstring_stats.fallbacks and remembered; one past the budget is left unbuilt, as without
+ * the switch.  vg_renderer_preload_fonts and the batched family path do the same.  Same stores, registry, budget and
+ * vg_charstring_stats, same output.  Off by default whatever a measurement says (profiles/charstrings2_batch_ab.txt).
+ * vg_manager_charstring_batch_stats: of the last render. */
+void vg_manager_set_charstrings_batched(vg_manager *m, int on);
+typedef struct {
+	uint64_t calls; /* batched calls made during the render (a group whose stores were all there makes none) */
+	uint64_t faces; /* the faces they were given */
+} vg_charstring_batch_stats;
+int vg_manager_charstring_batch_stats(const vg_manager *m, vg_charstring_batch_stats *out);
 /* family tables of all instances of a file in one device build, 0 (default) / 1; has an effect only with
  * vg_manager_set_family_tables_on_device: when the family of a font id whose ONE file is a placed face that shares its bytes
  * with other placed faces — the instances of vg_manager_add_font_named_instances, `glyf` + `gvar` and CFF2 alike — is asked
@@ -515,6 +531,12 @@ int vg_manager_charstring_font_desc(const vg_manager *m, const char *font_id, in
  * factors the reader multiplies `blend` deltas by (at the file's position: the default one unless it is an instance).  -1: unknown font / file, anything that is not CFF2, an
  * INDEX whose entries do not ascend inside their data, or a set of more than 65535 subroutines. */
 int vg_manager_charstring2_font_desc(const vg_manager *m, const char *font_id, int file_index, vgsdf_font_charstrings2_desc *desc);
+/* The batched description (vgsdf_fonts_create_charstrings2) of the instance group the ONE file of font_id belongs to —
+ * vg_manager_instance_group's, in its order: position p's slice of face.factors is what vg_manager_charstring2_font_desc gives
+ * for instance p, everything else is the first face's.  Views that stay valid while the manager holds the fonts.  -1: where
+ * vg_manager_charstring2_font_desc(m, font_id, 0, ...) returns -1, a font id that is not in a group, or faces of the group that
+ * disagree in anything but the factors (one file, one parse: they cannot). */
+int vg_manager_charstring2_fonts_desc(const vg_manager *m, const char *font_id, vgsdf_fonts_charstrings2_desc *desc);
 vg_resident_batch *vg_manager_record_resident_commands(const vg_manager *m, const char *font_id);
 
 /* The host half of a resident family (vgsdf_family_create / vgsdf_outlines_submit_ranges), no device needed: for every code

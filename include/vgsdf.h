@@ -418,6 +418,43 @@ int vgsdf_font_create_charstrings2_within(vgsdf_ctx *ctx, const vgsdf_font_chars
  * vgsdf_font_create_charstrings or vgsdf_font_create_charstrings2 took (HIP events around the pass, all its launches; 0 0 before
  * the first, and for a pass that did not run) */
 void vgsdf_font_charstrings_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
+/*
+ * The same for ONE CFF2 FACE AT MANY POSITIONS in one call — the named instances of a variable file, say.  The description goes
+ * up once, with the factors of all positions: face.factors holds n_positions x face.n_factors of them, position after position,
+ * each position's laid out by face.set_off.  Both passes run over (glyph id, position) pairs, the lanes of one glyph id at
+ * different positions side by side (csrc/charstring_batch_kernels.hip: the single call's device text).  The COUNT pass runs over
+ * pairs too: the operand a `callsubr` / `callgsubr` takes as its index, or a `blend` as its count, may itself be blended, so two
+ * positions may deliver different numbers of commands; counts, layout and store size are each position's own.  One read-back of
+ * all counts and all flag words, the context pass per store, two synchronisations for the whole call.  A launch covers
+ * max(1, 16384 / n_positions) glyph ids with all their positions, so the context's workspace grows no further than under the
+ * single call.  Each position that is built is a vgsdf_font of its own, with its own store: it cannot be told from what
+ * vgsdf_font_create_charstrings2 makes of the same face with that position's factors alone (vgsdf_font_commands_read,
+ * vgsdf_font_device_bytes), and is read, named by submissions and families, and freed like it, each alone (the same position
+ * given twice: two fonts).  Per position p:
+ *   built                                      status[p] VGSDF_OK      out[p] the font
+ *   over the limit (_within)                   status[p] VGSDF_OK      out[p] NULL, needed[p] its store's bytes
+ *   refused: a glyph past VGSDF_CHARSTRING_MAX_TOKENS AT p, or a store past the command store's bounds AT p
+ *                                              status[p] VGSDF_E_GLYF  out[p] NULL, no room taken, the other positions untouched
+ * _within takes the positions in order: one that is not refused is built when its store fits into what the positions built
+ * before it have left of max_store_bytes; one that does not fit is passed over and does not stop those behind it.  needed (may
+ * be NULL): [n_positions], 0 for a refused position.
+ * The whole call fails with VGSDF_E_ARG, before anything runs and with nothing allocated, for a NULL argument, more than
+ * VGSDF_CHARSTRING2_MAX_POSITIONS positions, anything vgsdf_font_create_charstrings2 validates, or a factor of any position
+ * that is not finite; a HIP error or an exhausted host fails it too: nothing is left allocated, every out[p] is NULL and the
+ * context stays sound.  n_positions == 0: VGSDF_OK, nothing is touched.
+ */
+#define VGSDF_CHARSTRING2_MAX_POSITIONS 64u
+typedef struct {
+	vgsdf_font_charstrings2_desc face; /* face.factors: [n_positions * face.n_factors], position after position */
+	uint32_t n_positions;              /* 0 .. VGSDF_CHARSTRING2_MAX_POSITIONS */
+} vgsdf_fonts_charstrings2_desc;
+int vgsdf_fonts_create_charstrings2(vgsdf_ctx *ctx, const vgsdf_fonts_charstrings2_desc *in, vgsdf_font **out /* [n_positions] */,
+                                    int *status /* [n_positions] */);
+int vgsdf_fonts_create_charstrings2_within(vgsdf_ctx *ctx, const vgsdf_fonts_charstrings2_desc *in, uint64_t max_store_bytes,
+                                           vgsdf_font **out, int *status, uint64_t *needed /* [n_positions], may be NULL */);
+/* test / inspection (tools/charstrings2_batch_ab.py): the count and the emit pass of the context's last
+ * vgsdf_fonts_create_charstrings2 */
+void vgsdf_fonts_charstrings2_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
 /* test / inspection: download a command font's store.  *n_glyph_ids / *n_cmds: its counts (either may be NULL); cmd_off
  * [n_glyph_ids + 1], records [28 * n_cmds bytes: x1 y1 x2 y2 x y as f32, kind as u32], context [n_cmds]: each NULL or filled.
  * A font from vgsdf_font_create: VGSDF_E_ARG. */
@@ -706,7 +743,7 @@ int vgsdf_family_read(vgsdf_ctx *ctx, const vgsdf_family *family, uint32_t *n_en
 void vgsdf_family_tables_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
 /*
  * The family tables of ONE FACE AT MANY POSITIONS in one call — the named instances of a variable file, whose stores
- * vgsdf_fonts_create_gvar (or the CFF2 constructor, position by position) has made.  Position p is a family of one face over
+ * vgsdf_fonts_create_gvar (or vgsdf_fonts_create_charstrings2 for a CFF2 file) has made.  Position p is a family of one face over
  * fonts[p]: `tables` is the one face's cmap and hmtx, var[p] its HVAR with the region factors of position p (every record names
  * the same hvar, hvar_len, store_off, map_off and n_regions: one file has one HVAR or none), gvar the description
  * vgsdf_fonts_create_gvar takes, with the coordinates of all positions.  What runs once for the call: the tables' upload; the

@@ -2,10 +2,11 @@
 per seed one face of 192 (`CFF `, CFF2) or 128 (gvar) glyph ids, the comparison of tests/test_decoder_fuzz_host.py (the host reader
 against the kit's interpreter / restatement, bit for bit; CFF2 at three positions, gvar at the face's three with its advance
 deltas) and, where a device is there, that of tests/test_gpu_decoder_fuzz.py (the store the device builds against the store of the
-host reader's table; CFF2 also under two arrays of other blend factors, gvar also batched and the phantom pass).  Without a device
-it runs host-only.  At the first difference it prints the seed, the face, the glyph id and the first differing record, and stops
+host reader's table; CFF2 also under two arrays of other blend factors, gvar also batched and the phantom pass; with --batched the
+CFF2 face's five arrays of factors once more in ONE vgsdf_fonts_create_charstrings2, every store against its single call's).
+Without a device it runs host-only.  At the first difference it prints the seed, the face, the glyph id and the first differing record, and stops
 with exit status 1; nothing is tried again.  Every program was run to its end by the kit's interpreter when its face was made.
-  python tools/fuzz_decoders.py --seeds 100..199 [--decoder cff|cff2|gvar] [--host-only]"""
+  python tools/fuzz_decoders.py --seeds 100..199 [--decoder cff|cff2|gvar] [--host-only] [--batched]"""
 import argparse
 import sys
 import time
@@ -59,10 +60,17 @@ def device_difference(ctx, built, table, name):
         want.free()
 
 
-def charstring_seed(vg, ctx, seed, cff2):
+def charstring_seed(vg, ctx, seed, cff2, batched=False):
     """-> (glyphs compared on the host, glyphs compared on the device, the first difference or None)"""
     face = F.face(seed, cff2)
     font, n, on_host, on_device = face.font(), len(face.glyphs), 0, 0
+    singles, first = [], None          # batched: (factors, the single call's store) of every position sent to the device
+
+    def made(d):
+        built = make(d)
+        if batched and cff2:
+            singles.append((np.asarray(d["factors"], np.float32), frozen(ctx, built)))
+        return built
     for coords in (F.POSITIONS2 if cff2 else (None,)):
         desc, host = F.host_views(vg, font, cff2, coords)
         diff = F.first_difference(f"{face.name} at {coords}", desc, host, cff2)
@@ -72,7 +80,8 @@ def charstring_seed(vg, ctx, seed, cff2):
         if ctx is None:
             continue
         make = ctx.font_create_charstrings2 if cff2 else ctx.font_create_charstrings
-        diff = device_difference(ctx, make(desc), host, f"{face.name} at {coords} on the device")
+        first = first or desc
+        diff = device_difference(ctx, made(desc), host, f"{face.name} at {coords} on the device")
         on_device += n
         if diff:
             return on_host, on_device, diff
@@ -80,10 +89,21 @@ def charstring_seed(vg, ctx, seed, cff2):
             for shift in (0, 3):
                 d = dict(desc, **K2.alt_sets(desc, shift))
                 want, _ = K2.expected_commands(d, budget=F.MAX_RUN_TOKENS)
-                diff = device_difference(ctx, make(d), want, f"{face.name} with the factors of alt_sets(shift={shift}) on the device")
+                diff = device_difference(ctx, made(d), want, f"{face.name} with the factors of alt_sets(shift={shift}) on the device")
                 on_device += n
                 if diff:
                     return on_host, on_device, diff
+    if singles:
+        fonts, status, _ = ctx.fonts_create_charstrings2(first, [f for f, _ in singles])
+        try:
+            for p, (built, (_, single)) in enumerate(zip(fonts, singles)):
+                if built is None or frozen(ctx, built) != single:
+                    return on_host, on_device, f"{face.name}: position {p} of the batched call is not the single call's store (status {list(status)})"
+            on_device += n * len(fonts)
+        finally:
+            for built in fonts:
+                if built is not None:
+                    built.free()
     return on_host, on_device, None
 
 
@@ -128,6 +148,7 @@ def main():
     ap.add_argument("--seeds", required=True, help="A..B (inclusive)")
     ap.add_argument("--decoder", choices=("cff", "cff2", "gvar"), action="append")
     ap.add_argument("--host-only", action="store_true")
+    ap.add_argument("--batched", action="store_true", help="CFF2: the positions once more in one vgsdf_fonts_create_charstrings2")
     args = ap.parse_args()
     a, b = (int(v) for v in args.seeds.split(".."))
     vg = load_product()
@@ -140,7 +161,7 @@ def main():
     for decoder in args.decoder or ("cff", "cff2", "gvar"):
         t0, on_host, on_device, diff = time.time(), 0, 0, None
         for seed in range(a, b + 1):
-            h, d, diff = gvar_seed(vg, ctx, seed) if decoder == "gvar" else charstring_seed(vg, ctx, seed, decoder == "cff2")
+            h, d, diff = gvar_seed(vg, ctx, seed) if decoder == "gvar" else charstring_seed(vg, ctx, seed, decoder == "cff2", args.batched)
             on_host, on_device = on_host + h, on_device + d
             if diff:
                 print(f"{decoder}: DIFFERENCE at seed {seed}: {diff}", flush=True)

@@ -67,6 +67,7 @@ struct vgsdf_ctx {
 	uint64_t *d_counters = nullptr;
 	void *comm = nullptr; // ncclComm_t of the communicator this context last reduced in (owned by run_counters.cpp's cache)
 	float charstring_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_font_create_charstrings / _charstrings2 (resident_charstrings.cpp)
+	float charstring_batch_ms[2] = {0.0f, 0.0f}; // the same of the last vgsdf_fonts_create_charstrings2: one face at all its positions
 	// vgsdf_font_create_charstrings2: operand slots past the decoder's LDS window, for one launch (at most 16384 glyph ids); grows
 	// to exactly what the largest launch so far needed and belongs to no font
 	void *charstring_spill = nullptr;

@@ -289,6 +289,13 @@ int vg_manager_gvar_batch_stats(const vg_manager *m, vg_gvar_batch_stats *out)
 	*out = vg_gvar_batch_stats{t.gvar_batch_calls, t.gvar_batch_faces};
 	return 0;
 }
+void vg_manager_set_charstrings_batched(vg_manager *m, int on) { m->m.set_charstrings_batched(on != 0); }
+int vg_manager_charstring_batch_stats(const vg_manager *m, vg_charstring_batch_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_charstring_batch_stats{t.charstring_batch_calls, t.charstring_batch_faces};
+	return 0;
+}
 void vg_manager_set_family_tables_batched(vg_manager *m, int on) { m->m.set_family_tables_batched(on != 0); }
 int vg_manager_family_batch_stats(const vg_manager *m, vg_family_batch_stats *out)
 {
@@ -989,6 +996,39 @@ int vg_manager_charstring2_font_desc(const vg_manager *m, const char *font_id, i
 		desc->set_ok = t->set_ok.data();
 		desc->set_off = t->set_off.data();
 		desc->factors = t->factors.data();
+		return 0;
+	} catch (const std::exception &e) {
+		g_err = e.what();
+		return -1;
+	}
+}
+int vg_manager_charstring2_fonts_desc(const vg_manager *m, const char *font_id, vgsdf_fonts_charstrings2_desc *desc)
+{
+	try {
+		std::string err;
+		vg::FontManager::Charstring2Group group;
+		if (!m || !font_id || !desc || !m->m.charstring2_group(font_id, group, &err)) {
+			g_err = err.empty() ? "vg_manager_charstring2_fonts_desc: bad argument" : err;
+			return -1;
+		}
+		const vg::CharstringTable *t = group.first;
+		vgsdf_font_charstrings_desc &cs = desc->face.charstrings;
+		cs.n_glyph_ids = (uint32_t)t->cs_off.size() - 1;
+		cs.n_bytes = (uint32_t)t->bytes.size();
+		cs.bytes = t->bytes.data();
+		cs.cs_off = t->cs_off.data();
+		cs.n_gsubrs = (uint32_t)t->gsubr_off.size() - 1;
+		cs.gsubr_off = t->gsubr_off.data();
+		cs.n_fds = t->n_fds;
+		cs.lsubr_first = t->lsubr_first.data();
+		cs.lsubr_off = t->lsubr_off.data();
+		cs.fd_of = nullptr;
+		desc->face.n_sets = (uint32_t)t->set_ok.size();
+		desc->face.n_factors = (uint32_t)t->factors.size();
+		desc->face.set_ok = t->set_ok.data();
+		desc->face.set_off = t->set_off.data();
+		desc->face.factors = group.factors;
+		desc->n_positions = group.n_positions;
 		return 0;
 	} catch (const std::exception &e) {
 		g_err = e.what();

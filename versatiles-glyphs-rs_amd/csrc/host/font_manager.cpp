@@ -330,6 +330,40 @@ std::vector<std::string> FontManager::instance_group(const std::string &font_id)
 	return group ? group->ids : std::vector<std::string>{};
 }
 
+bool FontManager::charstring2_group(const std::string &font_id, Charstring2Group &out, std::string *err) const
+{
+	if (!charstring2_table(font_id, 0, err))
+		return false;
+	const auto it = fonts().find(font_id);
+	const InstanceGroup *group = it == fonts().end() || it->second.files().size() != 1 ? nullptr : instance_group_of(it->second.files()[0]->face());
+	if (!group) {
+		if (err)
+			*err = "font '" + font_id + "': not one file of an instance group";
+		return false;
+	}
+	std::call_once(group->charstring2_once, [&] {
+		const CharstringTable &first = group->faces[0]->charstring2_table();
+		std::vector<float> all;
+		for (const Face *f : group->faces) {
+			const CharstringTable &t = f->charstring2_table();
+			if (!t.ok || !first.ok || !t.same_face(first))
+				return;
+			all.insert(all.end(), t.factors.begin(), t.factors.end());
+		}
+		group->charstring2_factors.swap(all);
+		group->charstring2_alike = true;
+	});
+	if (!group->charstring2_alike) {
+		if (err)
+			*err = "font '" + font_id + "': the faces of its instance group have no `CFF2` charstrings in common";
+		return false;
+	}
+	out.first = &group->faces[0]->charstring2_table();
+	out.factors = group->charstring2_factors.data();
+	out.n_positions = (uint32_t)group->faces.size();
+	return true;
+}
+
 bool FontManager::add_path(const std::string &path, std::string *err)
 {
 	std::vector<uint8_t> data;

@@ -181,6 +181,8 @@ struct RenderTimings {
 	uint64_t gvar_fonts_built = 0, gvar_font_bytes = 0, gvar_fallbacks = 0;
 	// ... and, with set_gvar_batched, the calls that built them (one per group of faces over the same bytes) and the faces sent
 	uint64_t gvar_batch_calls = 0, gvar_batch_faces = 0;
+	// with set_charstrings_batched: the calls that built CFF2 instances' stores (one per group of faces over the same bytes), the faces sent
+	uint64_t charstring_batch_calls = 0, charstring_batch_faces = 0;
 	// families with a face whose advances follow gvar's phantom points (set_gvar_advances) that the device built, the phantom pass
 	// included (set_family_tables_on_device; counted among family_tables_built too), and those it refused, whose tables came from
 	// the host reader instead (counted among family_table_fallbacks too)
@@ -221,12 +223,13 @@ struct RenderTimings {
 		glyf_table_batch_calls += counts.glyf_table_batch_calls, glyf_table_batch_faces += counts.glyf_table_batch_faces;
 		gvar_fonts_built += counts.gvar_fonts_built, gvar_font_bytes += counts.gvar_font_bytes, gvar_fallbacks += counts.gvar_fallbacks;
 		gvar_batch_calls += counts.gvar_batch_calls, gvar_batch_faces += counts.gvar_batch_faces;
+		charstring_batch_calls += counts.charstring_batch_calls, charstring_batch_faces += counts.charstring_batch_faces;
 		gvar_advance_builds += counts.gvar_advance_builds, gvar_advance_fallbacks += counts.gvar_advance_fallbacks;
 		family_batch_calls += counts.family_batch_calls, family_batch_families += counts.family_batch_families;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 45 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 47 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -364,6 +367,19 @@ public:
 	// with set_gvar_on_device: the stores of ALL placed glyf faces over the same bytes (add_font_named_instances) that the lane's
 	// device has yet to build, in one call when the first of them is asked for (Renderer::gvar_fonts)
 	void set_gvar_batched(bool on) { gvar_batched_ = on; }
+	// with set_charstrings_on_device(2): the stores of ALL placed CFF2 faces over the same bytes (add_font_named_instances) that the
+	// lane's device has yet to build, in one call when the first of them is asked for (Renderer::charstring2_fonts)
+	void set_charstrings_batched(bool on) { charstrings_batched_ = on; }
+	// The batched description (vgsdf_fonts_create_charstrings2) of the instance group the ONE file of `font_id` belongs to, in the
+	// group's order: the first face's charstring2_table() and the factors of every face, one behind the other (views that stay
+	// while the manager holds the fonts).  false, *err: where charstring2_table(font_id, 0) fails, a font id not in a group, a face
+	// of the group without such a table, or faces that disagree in anything but the factors
+	struct Charstring2Group {
+		const CharstringTable *first = nullptr;
+		const float *factors = nullptr;
+		uint32_t n_positions = 0;
+	};
+	bool charstring2_group(const std::string &font_id, Charstring2Group &out, std::string *err) const;
 	// with set_family_tables_on_device: when the family of a font id whose ONE file is a placed face that shares its bytes with
 	// other placed faces (add_font_named_instances, glyf + gvar and CFF2 alike) is asked for, the family tables of ALL such font
 	// ids of that group that the lane's device lacks are built in one call (Renderer::families_from_tables: the tables uploaded
@@ -646,7 +662,7 @@ private:
 	bool glyf_tables_on_device_ = false;
 	bool gvar_on_device_ = false;
 	bool glyf_tables_batched_ = false;
-	bool gvar_batched_ = false, scan_named_instances_ = false;
+	bool gvar_batched_ = false, scan_named_instances_ = false, charstrings_batched_ = false;
 	bool gvar_advances_ = false;
 	uint64_t gvar_advance_faces_ = 0;
 	// the placed faces that share their bytes — the faces add_font_named_instances made of one file, glyf + gvar or CFF2 —, by the
@@ -655,6 +671,10 @@ private:
 	struct InstanceGroup {
 		std::vector<const Face *> faces;
 		std::vector<std::string> ids;
+		// charstring2_group(): the faces' CFF2 factors one behind the other, made once (empty with `alike` false: not describable)
+		mutable std::once_flag charstring2_once;
+		mutable std::vector<float> charstring2_factors;
+		mutable bool charstring2_alike = false;
 	};
 	std::map<const uint8_t *, InstanceGroup> instance_groups_;
 	std::map<const Face *, const uint8_t *> instance_bytes_of_; // a grouped face -> its group's key
@@ -667,6 +687,9 @@ private:
 	// gvar_batched_: the command stores of `face`'s group that the device has yet to build, in one call; the gvar_font of each face
 	// behind it finds its store (or goes the way of a face that was refused or did not fit); counts into `counts`
 	void gvar_stores_batched(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
+	// charstrings_batched_ (with charstrings_on_device_ 2): the same for the CFF2 faces of `face`'s group; the charstring_font of
+	// each face behind it finds its store (or goes the way of one that was refused or did not fit); counts into `counts`
+	void charstring2_stores_batched(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
 	// glyf_tables_batched_: the glyf fonts of `font`'s files that the device has yet to build, in one call; the glyf_store of each
 	// file behind it finds its font (or goes the way of a face that was refused or did not fit); counts into `counts`
 	void glyf_stores_batched(const Renderer &renderer, int lane, const FontWrapper &font, RenderTimings &counts) const;

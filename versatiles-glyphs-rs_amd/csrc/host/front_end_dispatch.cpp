@@ -362,6 +362,30 @@ void FontManager::gvar_stores_batched(const Renderer &renderer, int lane, const 
 	}
 }
 
+void FontManager::charstring2_stores_batched(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const
+{
+	if (!charstrings_batched_ || charstrings_on_device_ < 2)
+		return;
+	const InstanceGroup *group = instance_group_of(face);
+	if (!group || group->faces.size() < 2)
+		return; // (a face with bytes of its own: its own call)
+	std::vector<Renderer::Charstring2Job> faces;
+	for (const Face *f : group->faces) {
+		const CharstringTable &t = f->charstring2_table();
+		faces.push_back(Renderer::Charstring2Job{t.serial, &t});
+	}
+	std::vector<Renderer::TablesOutcome> outcomes;
+	renderer.charstring2_fonts(lane, faces, outcomes, &counts.charstring_batch_calls, &counts.charstring_batch_faces);
+	for (const Renderer::TablesOutcome &o : outcomes) { // (as command_store counts what charstring_font says)
+		if (o.refused)
+			counts.charstring_fallbacks++;
+		if (o.built) {
+			count_upload(o.uploaded, counts.charstring_fonts_decoded, counts.charstring_font_bytes);
+			count_upload(o.uploaded, counts.command_fonts_uploaded, counts.command_font_bytes);
+		}
+	}
+}
+
 void FontManager::families_batched(const Renderer &renderer, int lane, const FontWrapper &font, StoreKind kind, RenderTimings &counts) const
 {
 	if (!family_tables_on_device_ || !family_tables_batched_ || kind == StoreKind::Glyf || font.files().size() != 1)
@@ -417,6 +441,8 @@ const vgsdf_font *FontManager::command_store(const Renderer &renderer, int lane,
 	if (!cs && charstrings_on_device_ >= 2 && face.charstring2_table().ok)
 		cs = &face.charstring2_table();
 	if (cs) {
+		if (cs->cff2)
+			charstring2_stores_batched(renderer, lane, face, counts);
 		bool refused = false, over_budget = false;
 		f = renderer.charstring_font(lane, *cs, &uploaded, &refused, &over_budget);
 		if (refused)

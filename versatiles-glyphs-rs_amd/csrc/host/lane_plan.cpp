@@ -410,6 +410,7 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 		c->gvar_on_device_ = gvar_on_device_;
 		c->glyf_tables_batched_ = glyf_tables_batched_;
 		c->gvar_batched_ = gvar_batched_;
+		c->charstrings_batched_ = charstrings_batched_;
 		c->resident_families_ = resident_families_;
 		c->batch_blocks_ = batch_blocks_;
 		c->batch_blocks_set_ = batch_blocks_set_;

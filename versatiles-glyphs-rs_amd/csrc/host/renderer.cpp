@@ -730,6 +730,74 @@ void Renderer::gvar_fonts(int lane, const std::vector<GvarJob> &faces, std::vect
 	flush();
 }
 
+void Renderer::charstring2_fonts(int lane, const std::vector<Charstring2Job> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls,
+                                 uint64_t *n_sent) const
+{
+	outcomes.assign(faces.size(), TablesOutcome{});
+	if (mode_ != Mode::Hip)
+		return;
+	ResidentFonts &rf = *resident_;
+	std::lock_guard<std::mutex> table_lock(rf.mu);
+	std::vector<size_t> sent;
+	std::vector<float> factors;
+	const CharstringTable *first = nullptr;
+	auto flush = [&] {
+		if (sent.empty())
+			return;
+		const CharstringTable &t = *first;
+		vgsdf_fonts_charstrings2_desc d{};
+		vgsdf_font_charstrings_desc &cs = d.face.charstrings;
+		cs.n_glyph_ids = (uint32_t)t.cs_off.size() - 1;
+		cs.n_bytes = (uint32_t)t.bytes.size();
+		cs.bytes = t.bytes.data();
+		cs.cs_off = t.cs_off.data();
+		cs.n_gsubrs = (uint32_t)t.gsubr_off.size() - 1;
+		cs.gsubr_off = t.gsubr_off.data();
+		cs.n_fds = t.n_fds;
+		cs.lsubr_first = t.lsubr_first.data();
+		cs.lsubr_off = t.lsubr_off.data();
+		cs.fd_of = nullptr;
+		d.face.n_sets = (uint32_t)t.set_ok.size();
+		d.face.n_factors = (uint32_t)t.factors.size();
+		d.face.set_ok = t.set_ok.data();
+		d.face.set_off = t.set_off.data();
+		d.face.factors = factors.data();
+		d.n_positions = (uint32_t)sent.size();
+		std::vector<vgsdf_font *> made(sent.size(), nullptr);
+		std::vector<int> status(sent.size(), 0);
+		std::vector<uint64_t> needed(sent.size(), 0);
+		vgsdf_ctx *c = lane_ctx(lane & 1);
+		int rc;
+		{
+			std::lock_guard<std::mutex> lock(mu_);
+			rc = vgsdf_fonts_create_charstrings2_within(c, &d, rf.room(device_), made.data(), status.data(), needed.data());
+		}
+		if (rc != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_fonts_create_charstrings2: ") + vgsdf_last_error(c));
+		*calls += 1, *n_sent += sent.size();
+		settle_batch(rf.charstrings, c, false, faces, sent, made, status, needed, outcomes); // (refused at this position)
+		sent.clear(), factors.clear();
+	};
+	std::set<uint64_t> seen;
+	for (size_t i = 0; i < faces.size(); i++) {
+		const CharstringTable *t = faces[i].table;
+		const auto key = std::make_pair(device_, faces[i].serial);
+		if (!t || !t->ok || !t->cff2 || rf.find(rf.fonts, key) || rf.charstrings.known(key, rf.room(device_)))
+			continue; // (charstring_font says over_budget when it is asked)
+		if (!seen.insert(faces[i].serial).second)
+			continue; // (a face named twice: one store)
+		if (!first)
+			first = t;
+		if (t != first && !t->same_face(*first))
+			continue; // (not the first face's charstrings: its own charstring_font builds it)
+		if (sent.size() == VGSDF_CHARSTRING2_MAX_POSITIONS)
+			flush();
+		sent.push_back(i);
+		factors.insert(factors.end(), t->factors.begin(), t->factors.end());
+	}
+	flush();
+}
+
 const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std::vector<const vgsdf_font *> &fonts, int kind,
                                      uint64_t *uploaded_bytes) const
 {

@@ -514,6 +514,17 @@ public:
 		GvarTables tables;
 	};
 	void gvar_fonts(int lane, const std::vector<GvarJob> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls, uint64_t *n_sent) const;
+	// charstring_font for ALL placed CFF2 faces over ONE file's charstrings (the same bytes, offsets and sets; each its own factors
+	// and command serial) in as few calls as their number allows (vgsdf_fonts_create_charstrings2_within: the description uploaded
+	// once, count and emit pass over all positions).  Shaped like gvar_fonts, the same registry protocol; what is remembered is
+	// charstring_font's (DeviceBuilt charstrings), so that a charstring_font of any of the faces behind this call finds its store, or
+	// goes the way it went.  A face whose table is not the first sent face's but for the factors is left to its own charstring_font
+	struct Charstring2Job {
+		uint64_t serial = 0;
+		const CharstringTable *table = nullptr;
+	};
+	void charstring2_fonts(int lane, const std::vector<Charstring2Job> &faces, std::vector<TablesOutcome> &outcomes, uint64_t *calls,
+	                       uint64_t *n_sent) const;
 	// Resident families (vgsdf_family_create): the device copy of a font id's table code point -> (file, glyph id, advance,
 	// scale, shift_x) over the device fonts of its files, one per (device, table serial, kind of store) in the registry of the
 	// fonts — same budget, freed with the renderer, in front of the fonts.  A table rebuilt after a file was added has a new

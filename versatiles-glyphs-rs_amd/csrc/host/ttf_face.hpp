@@ -95,6 +95,13 @@ struct CharstringTable {
 	std::vector<uint8_t> set_ok;       // [sets] 0: a charstring that selects the set ends there
 	std::vector<uint32_t> set_off;     // [sets + 1] into factors
 	std::vector<float> factors;
+	// the same face but for the factors: every array the device's decoder is given equal, and as many factors
+	bool same_face(const CharstringTable &o) const
+	{
+		return cff2 == o.cff2 && n_fds == o.n_fds && factors.size() == o.factors.size() && set_off == o.set_off && set_ok == o.set_ok &&
+		       lsubr_first == o.lsubr_first && lsubr_off == o.lsubr_off && gsubr_off == o.gsubr_off && cs_off == o.cs_off && fd_of == o.fd_of &&
+		       bytes == o.bytes;
+	}
 };
 
 // A face's `cmap` and `hmtx` for the device's family-table kernels (vgsdf_face_tables of include/vgsdf.h, field for field): views of

@@ -77,6 +77,10 @@ class _CFontCharstrings2Desc(C.Structure):  # vgsdf_font_charstrings2_desc
                 ("set_off", C.c_void_p), ("factors", C.c_void_p)]
 
 
+class _CFontsCharstrings2Desc(C.Structure):  # vgsdf_fonts_charstrings2_desc
+    _fields_ = [("face", _CFontCharstrings2Desc), ("n_positions", C.c_uint32)]
+
+
 class _COutlinesResident(C.Structure):  # vgsdf_outlines_resident
     _fields_ = [("n_glyphs", C.c_uint32), ("n_fonts", C.c_uint32), ("fonts", C.c_void_p), ("font_of", C.c_void_p),
                 ("glyph_id", C.c_void_p), ("scale", C.c_void_p), ("shift_x", C.c_void_p), ("pbf_pre", C.c_void_p),
@@ -132,6 +136,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_add_counters", "vgsdf_reset_counters", "vgsdf_reduce_counters", "vgsdf_reduce_counters_rccl", "vgsdf_reduce_path", "vgsdf_outlines_pbf_positions", "vgsdf_outlines_peek",
     "vgsdf_font_create", "vgsdf_font_free", "vgsdf_font_device_bytes", "vgsdf_outlines_submit_resident", "vgsdf_outlines_resident_upload_bytes",
     "vgsdf_font_create_commands", "vgsdf_font_create_charstrings", "vgsdf_font_create_charstrings_within", "vgsdf_font_create_charstrings2", "vgsdf_font_create_charstrings2_within", "vgsdf_font_charstrings_kernel_ms", "vgsdf_font_commands_read",
+    "vgsdf_fonts_create_charstrings2", "vgsdf_fonts_create_charstrings2_within", "vgsdf_fonts_charstrings2_kernel_ms",
     "vgsdf_family_create", "vgsdf_family_free", "vgsdf_family_device_bytes", "vgsdf_family_count", "vgsdf_outlines_submit_ranges",
     "vgsdf_outlines_task_extents", "vgsdf_family_create_tables", "vgsdf_family_read", "vgsdf_family_tables_kernel_ms",
     "vgsdf_font_create_tables", "vgsdf_font_create_tables_within", "vgsdf_font_read", "vgsdf_font_tables_kernel_ms",
@@ -196,6 +201,10 @@ def load_library():
         L.vgsdf_font_create_charstrings2_within.argtypes = [vp, C.POINTER(_CFontCharstrings2Desc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.vgsdf_font_charstrings_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.vgsdf_font_charstrings_kernel_ms.restype = None
+        L.vgsdf_fonts_create_charstrings2.argtypes = [vp, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vgsdf_fonts_create_charstrings2_within.argtypes = [vp, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.vgsdf_fonts_charstrings2_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_fonts_charstrings2_kernel_ms.restype = None
         L.vgsdf_font_commands_read.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), vp, vp, vp]
         L.vgsdf_font_create_tables.argtypes = [vp, C.POINTER(_CFontTablesDesc), C.POINTER(vp)]
         L.vgsdf_font_create_tables_within.argtypes = [vp, C.POINTER(_CFontTablesDesc), C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -662,6 +671,51 @@ class SdfContext:
             return (ResidentFont(self, h) if h.value else None), int(want.value)
         self._check(load_library().vgsdf_font_create_charstrings2(self._h, C.byref(d), C.byref(h)))
         return ResidentFont(self, h)
+
+    def fonts_create_charstrings2(self, desc: dict, positions, max_store_bytes=None, **override):
+        """vgsdf_fonts_create_charstrings2: ONE `CFF2` face (desc as font_create_charstrings2 takes it; its own "factors" is not
+        looked at) at every position of `positions` (each the n_factors f32 factors of that position, laid out by set_off) in one
+        call -> (fonts, statuses, needed), each a list per position: a ResidentFont or None; VGSDF_OK with a font, VGSDF_OK without
+        one when the store would pass what the positions before it have left of max_store_bytes
+        (vgsdf_fonts_create_charstrings2_within; needed: the store's bytes, 0 without a limit or for a refused position),
+        VGSDF_E_GLYF for a position the device refuses.  VgsdfError: the whole call failed.
+        override (for calls that lie): n_positions, the raw struct fields of font_create_charstrings2; null: the names among
+        "desc", "factors", "out", "status" to pass as NULL"""
+        d, keep = _CFontsCharstrings2Desc(), {}
+        self._fill_charstrings_desc(d.face.charstrings, keep, desc, override)
+        keep["set_ok"] = np.ascontiguousarray(desc["set_ok"], dtype=np.uint8)
+        keep["set_off"] = np.ascontiguousarray(desc["set_off"], dtype=np.uint32)
+        factors = np.asarray(positions, dtype=np.float32)
+        factors = np.ascontiguousarray(factors.reshape(len(positions), factors.size // max(len(positions), 1)))
+        null = set(override.get("null", ()))
+        d.face.n_sets = override.get("n_sets", len(keep["set_ok"]))
+        d.face.n_factors = override.get("n_factors", factors.shape[1] if len(positions) else len(desc["factors"]))
+        d.face.set_ok = keep["set_ok"].ctypes.data
+        d.face.set_off = keep["set_off"].ctypes.data
+        d.face.factors = factors.ctypes.data if factors.size and "factors" not in null else None
+        d.n_positions = n = int(override.get("n_positions", len(positions)))
+        room = max(len(positions), n if n <= 4096 else 0, 1)
+        out, status, needed = (C.c_void_p * room)(), (C.c_int * room)(), (C.c_uint64 * room)()
+        args = [None if "desc" in null else C.byref(d)]
+        tail = [None if "out" in null else out, None if "status" in null else status]
+        L = load_library()
+        try:
+            if max_store_bytes is not None:
+                self._check(L.vgsdf_fonts_create_charstrings2_within(self._h, *args, int(max_store_bytes), *tail, needed))
+            else:
+                self._check(L.vgsdf_fonts_create_charstrings2(self._h, *args, *tail))
+        except VgsdfError:
+            assert not any(out[i] for i in range(room)), "a failed call left a font behind"
+            raise
+        k = min(n, room)
+        return ([ResidentFont(self, C.c_void_p(out[i])) if out[i] else None for i in range(k)], [int(status[i]) for i in range(k)],
+                [int(needed[i]) for i in range(k)])
+
+    def fonts_charstrings2_kernel_ms(self):
+        """(count, emit) pass milliseconds of this context's last fonts_create_charstrings2"""
+        ms = (C.c_float * 2)()
+        load_library().vgsdf_fonts_charstrings2_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
 
     def font_charstrings_kernel_ms(self):
         """(count, emit) pass milliseconds of this context's last font_create_charstrings / font_create_charstrings2"""

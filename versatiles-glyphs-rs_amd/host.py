@@ -120,6 +120,7 @@ VGFONT_SYMBOLS = [
     "vg_manager_add_font_instance", "vg_manager_add_font_instance_normalized", "vg_font_variation_axes", "vg_font_named_instances",
     "vg_manager_family_variation_desc", "vg_manager_font_position", "vg_manager_font_hor_advances",
     "vg_manager_add_font_named_instances", "vg_manager_set_scan_named_instances", "vg_manager_set_gvar_batched", "vg_manager_gvar_batch_stats",
+    "vg_manager_set_charstrings_batched", "vg_manager_charstring_batch_stats", "vg_manager_charstring2_fonts_desc",
     "vg_manager_set_family_tables_batched", "vg_manager_family_batch_stats", "vg_manager_instance_group",
     "vg_manager_set_gvar_advances", "vg_manager_gvar_advance_stats", "vg_manager_font_gvar_advance_deltas",
     "vg_manager_family_gvar_desc",
@@ -189,6 +190,10 @@ def _L():
         L.vg_manager_set_gvar_batched.argtypes = [vp, C.c_int]
         L.vg_manager_set_gvar_batched.restype = None
         L.vg_manager_gvar_batch_stats.argtypes = [vp, C.POINTER(GlyfTableBatchStats)]
+        L.vg_manager_set_charstrings_batched.argtypes = [vp, C.c_int]
+        L.vg_manager_set_charstrings_batched.restype = None
+        L.vg_manager_charstring_batch_stats.argtypes = [vp, C.POINTER(GlyfTableBatchStats)]
+        L.vg_manager_charstring2_fonts_desc.argtypes = [vp, C.c_char_p, C.c_void_p]
         L.vg_manager_set_family_tables_batched.argtypes = [vp, C.c_int]
         L.vg_manager_set_family_tables_batched.restype = None
         L.vg_manager_family_batch_stats.argtypes = [vp, C.POINTER(FamilyBatchStats)]
@@ -641,6 +646,18 @@ class FontManager:
         _L().vg_manager_gvar_batch_stats(self._h, C.byref(s))
         return {k: int(getattr(s, k)) for k, _ in GlyfTableBatchStats._fields_}
 
+    def set_charstrings_batched(self, on: bool):
+        """with set_charstrings_on_device(2): the command stores of all placed CFF2 faces over the same bytes
+        (add_font_named_instances) are built in ONE call (vgsdf_fonts_create_charstrings2) instead of one per face; same stores,
+        same output (default off)"""
+        _L().vg_manager_set_charstrings_batched(self._h, int(bool(on)))
+
+    def charstring_batch_stats(self) -> dict:
+        """of the last render: {calls, faces} of the batched CFF2 builds (vg_charstring_batch_stats)"""
+        s = GlyfTableBatchStats()  # (vg_charstring_batch_stats has the same two fields)
+        _L().vg_manager_charstring_batch_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in GlyfTableBatchStats._fields_}
+
     def set_family_tables_batched(self, on: bool):
         """with set_family_tables_on_device: the family tables of all single-file font ids over the same bytes
         (add_font_named_instances) are built in ONE call (vgsdf_families_create_tables) instead of one per font id; same
@@ -951,6 +968,33 @@ class FontManager:
                 "lsubr_off": arr(d.lsubr_off, int(lsubr_first[-1]) + 1, np.uint32), "fd_of": None,
                 "set_ok": arr(d2.set_ok, d2.n_sets, np.uint8), "set_off": arr(d2.set_off, d2.n_sets + 1, np.uint32),
                 "factors": arr(d2.factors, d2.n_factors, np.float32)}
+
+    def charstring2_fonts_desc(self, font_id: str) -> dict:
+        """the batched description of the instance group font_id's one file belongs to, for vgsdf_fonts_create_charstrings2
+        (vg_manager_charstring2_fonts_desc; no device): the keys of charstring2_font_desc with "factors" the FIRST position's, plus
+        "positions": float32 [n_positions, n_factors], the factors of every instance in the group's order — what
+        Context.fonts_create_charstrings2 takes as (desc, positions).  RuntimeError: anything charstring2_font_desc refuses, a
+        font id that is not in a group"""
+        from .device import _CFontsCharstrings2Desc
+        L = _L()
+        ds = _CFontsCharstrings2Desc()
+        if L.vg_manager_charstring2_fonts_desc(self._h, font_id.encode(), C.byref(ds)) != 0:
+            raise RuntimeError(_err())
+        d2, d = ds.face, ds.face.charstrings
+
+        def arr(ptr, count, dt):
+            if count == 0 or not ptr:
+                return np.zeros(0, dtype=dt)
+            buf = (C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dt, count=count).copy()
+
+        lsubr_first = arr(d.lsubr_first, d.n_fds + 1, np.uint32)
+        positions = arr(d2.factors, d2.n_factors * ds.n_positions, np.float32).reshape(ds.n_positions, d2.n_factors)
+        return {"bytes": arr(d.bytes, d.n_bytes, np.uint8), "cs_off": arr(d.cs_off, d.n_glyph_ids + 1, np.uint32),
+                "gsubr_off": arr(d.gsubr_off, d.n_gsubrs + 1, np.uint32), "lsubr_first": lsubr_first,
+                "lsubr_off": arr(d.lsubr_off, int(lsubr_first[-1]) + 1, np.uint32), "fd_of": None,
+                "set_ok": arr(d2.set_ok, d2.n_sets, np.uint8), "set_off": arr(d2.set_off, d2.n_sets + 1, np.uint32),
+                "factors": positions[0].copy() if ds.n_positions else np.zeros(0, dtype=np.float32), "positions": positions}
 
     def family_desc(self, font_id: str) -> dict:
         """the host half of a resident family (vg_manager_family_desc): {code_point, font_of, glyph_id, advance, scale, shift_x,
