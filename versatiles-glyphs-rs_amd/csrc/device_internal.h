@@ -114,7 +114,7 @@ struct vgsdf_dbatch {
 
 // kernel id understood by vgsdf_launch_tiles.  Variant 0 (default) = kernel 50: bounded groups over spans of tiles;
 // misfits: brute force.  1: everything brute.  Other ids exist only in development builds (vgsdf_set_variant rejects
-// them otherwise): earlier generations and timing-only ablations, see vgsdf_launch_tiles; 60..83 only in `make margins`
+// them otherwise): earlier generations and timing-only ablations, see vgsdf_launch_tiles; 60..84 only in `make margins`
 // builds: the margin instances of the span kernel (sdf_margin_kernels.hip).
 inline int kernel_id(int variant) { return variant == 0 ? 50 : (variant == 13 ? 10 : variant); }
 // the variant's main-class entries are spans: (glyph, first pixel | tile count)

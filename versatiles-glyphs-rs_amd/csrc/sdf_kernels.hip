@@ -230,7 +230,7 @@ extern "C" int vgsdf_launch_span_planned(const vgsdf::GlyphDesc *glyphs, const u
 // for the tiles the host routes there: glyphs too wide for the winding histogram, or with >= 2^24
 // segments.  Everything else exists only in development builds (-DVGSDF_DEV_VARIANTS).
 #ifdef VGSDF_MARGIN_VARIANTS
-// `make margins` only: the margin instances of the span kernel (sdf_margin_kernels.hip), ids 60..83
+// `make margins` only: the margin instances of the span kernel (sdf_margin_kernels.hip), ids 60..84
 extern "C" int vgsdf_margin_known(int kernel);
 extern "C" int vgsdf_margin_launch(int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::GlyphDesc *glyphs, const uint2 *tiles,
                                    const double *sx, const double *sy, const double *ex, const double *ey, uint32_t seg_stride,

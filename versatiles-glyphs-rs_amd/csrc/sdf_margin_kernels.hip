@@ -7,18 +7,19 @@
 // arithmetic only — a constant, or the outcome of a float comparison; never an index, a loop bound, an LDS size, a
 // barrier or an address — so it touches no memory the product kernel does not touch.  It is expected to give wrong
 // bytes on the directed sets of tests/raster_margin_sets.py; tests/test_gpu_raster_margins.py asserts that it does.
+// (Instance 84, the stage's row margin: tests/stage_filter_sets.py and tests/test_gpu_stage_filters.py.)
 //
-// The file is compiled VG_MARGIN_PARTS times with -DVG_MARGIN_PART=0..5 (four instances each: the instances compile in
-// parallel).  Kernel ids = vgsdf_set_variant ids 60..83, known to this build only.
+// The file is compiled VG_MARGIN_PARTS times with -DVG_MARGIN_PART=0..6 (up to four instances each: the instances compile
+// in parallel).  Kernel ids = vgsdf_set_variant ids 60..84, known to this build only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sdf_span_support.h"
 
 #ifndef VG_MARGIN_PART
-#error "compile with -DVG_MARGIN_PART=0..5"
+#error "compile with -DVG_MARGIN_PART=0..6"
 #endif
-#define VG_MARGIN_PARTS 6
+#define VG_MARGIN_PARTS 7
 #define VG_CAT_(a, b) a##b
 #define VG_CAT(a, b) VG_CAT_(a, b)
 
@@ -144,6 +145,13 @@ static const MarginInstance k_instances[] = {{76, sdf_margin_span_e_4}, {77, sdf
 #define VG_M_RG(r) ((r) * 0.125f)
 #include "sdf_span_kernel.inc"
 static const MarginInstance k_instances[] = {{80, sdf_margin_span_dl_8}, {81, sdf_margin_span_rg_2}, {82, sdf_margin_span_rg_4}, {83, sdf_margin_span_rg_8}};
+#elif VG_MARGIN_PART == 6
+// ---- 84 (m) E_row := 0: the stage takes a segment's bracket of rows from the f32 record wherever the record is finite ----
+#define VG_SPAN_KERNEL sdf_margin_span_row_e0
+#define VG_M_ROW_E(e) ((void)(e), 0.0f)
+#include "sdf_span_kernel.inc"
+static const MarginInstance k_instances[] = {{84, sdf_margin_span_row_e0}};
+
 #else
 #error "VG_MARGIN_PART out of range"
 #endif
@@ -173,14 +181,16 @@ extern "C" int vgsdf_margin_launch_p2(VG_MARGIN_PART_ARGS);
 extern "C" int vgsdf_margin_launch_p3(VG_MARGIN_PART_ARGS);
 extern "C" int vgsdf_margin_launch_p4(VG_MARGIN_PART_ARGS);
 extern "C" int vgsdf_margin_launch_p5(VG_MARGIN_PART_ARGS);
+extern "C" int vgsdf_margin_launch_p6(VG_MARGIN_PART_ARGS);
 
-extern "C" int vgsdf_margin_known(int kernel) { return kernel >= 60 && kernel <= 83; }
+extern "C" int vgsdf_margin_known(int kernel) { return kernel >= 60 && kernel <= 84; }
 
 // called by vgsdf_launch_tiles of the margins build for the ids vgsdf_margin_known accepts
 extern "C" int vgsdf_margin_launch(VG_MARGIN_PART_ARGS)
 {
 	int (*const parts[VG_MARGIN_PARTS])(VG_MARGIN_PART_ARGS) = {vgsdf_margin_launch_p0, vgsdf_margin_launch_p1, vgsdf_margin_launch_p2,
-	                                                            vgsdf_margin_launch_p3, vgsdf_margin_launch_p4, vgsdf_margin_launch_p5};
+	                                                            vgsdf_margin_launch_p3, vgsdf_margin_launch_p4, vgsdf_margin_launch_p5,
+	                                                            vgsdf_margin_launch_p6};
 	for (auto part : parts) {
 		const int e = part(kernel, grid, n_tiles_arg, glyphs, tiles, sx, sy, ex, ey, seg_stride, out, boxes, stream);
 		if (e != -1)
@@ -218,6 +228,16 @@ extern "C" int vgsdf_margin_pair_round_counters(unsigned long long *out)
 	const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(vgsdf::g_span_dbg), sizeof(h), 0, hipMemcpyDeviceToHost);
 	for (int i = 0; i < 2; i++)
 		out[i] = h[23 + i];
+	return (int)e;
+}
+
+// The `count` instance's counter of the stage's f32 decision, behind those: out[0] = waves of a chunk whose f64 brackets ran (a
+// lane's end point within E_row of a row centre).  Same accumulation; vgsdf_margin_counters resets it too.
+extern "C" int vgsdf_margin_stage_filter_counters(unsigned long long *out)
+{
+	unsigned long long h[28] = {0};
+	const hipError_t e = hipMemcpyFromSymbol(h, HIP_SYMBOL(vgsdf::g_span_dbg), sizeof(h), 0, hipMemcpyDeviceToHost);
+	out[0] = h[25];
 	return (int)e;
 }
 #endif

@@ -98,6 +98,9 @@
 #ifndef VG_M_TK
 #define VG_M_TK(tk, f1) (tk) // fallback threshold as used by the exact evaluation
 #endif
+#ifndef VG_M_ROW_E
+#define VG_M_ROW_E(e) (e) // stage: distance of an f32 end point from a row centre below which the f64 brackets decide
+#endif
 
 __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__restrict__ glyphs,
                                                           const uint2 *__restrict__ tiles, uint32_t n_tiles,
@@ -119,6 +122,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	unsigned long long cn_pairs = 0, cn_rounds = 0, cn_tc = 0, cn_fb = 0, cn_fbl = 0;
 	unsigned long long cn_over = 0, cn_fb_pool = 0, cn_fb_lane = 0; // phase-2 pool overflows; waves by exact-evaluation branch
 	unsigned long long cn_half = 0, cn_leave = 0;                   // half rounds taken; sweeps that left behind phase 1 without a pair
+	unsigned long long cn_row_fb = 0;                               // stage: waves of a chunk whose f64 brackets ran
 #endif
 	VG_STAMP(-1);
 	constexpr uint32_t GRP = 8, NGRP = FCHUNK / GRP; // 32 groups per chunk: one mask bit each
@@ -228,14 +232,13 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// the compiler cannot hoist them across, from the integers they come from.
 			int gx0 = g.x0, gy0 = g.y0;
 			asm volatile("" : "+s"(gx0), "+s"(gy0));
-			const double x0c = (double)gx0 + 0.5, y0c = (double)gy0 + 0.5; // renderer_precise.rs:27-28
-			const double band_lo = (double)y_lo + y0c, band_hi = (double)y_hi + y0c; // lowest / highest sample row of the span
 			const double ox = (double)gx0 + (double)hw, oy = (double)gy0 + (double)hh;
 			const uint32_t i = tid;
 			float mf = 0.0f;
 			float fvx = 1.0e18f, fvy = 1.0e18f, fdx = 0.0f, fdy = 0.0f, finv = 0.0f; // padding: a record that can never win (F = 2e36)
 			uint32_t nrow = 0; // sample rows of the span this thread's segment crosses: yy in [ya, ya + nrow)
 			int ya = 0;
+			bool row_exact = false; // the f32 record does not fix the brackets: first_ge does, below
 			if (i < cnt) {
 				const size_t s = (size_t)(g.seg_off + c0 + i) * seg_stride; // stride 1: SoA arrays; 4: {sx, sy, ex, ey} records
 				const double vx = seg_sx[s], vy = seg_sy[s], wx = seg_ex[s], wy = seg_ey[s];
@@ -256,12 +259,33 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				mf = fmaxf(fmaxf(fabsf(fvx), fabsf(fvy)), fmaxf(fabsf(fvx + fdx), fabsf(fvy + fdy))) * 1.00001f;
 				mf = mf >= 0.0f ? mf : __builtin_inff(); // NaN -> inf ("no usable bound")
 				// crossings, renderer_precise.rs:41-51: up (+1) s.y <= py < e.y; down (-1) e.y <= py < s.y.
-				// Rows crossed: lo <= py < hi with py = yy + y0c exactly as the reference forms it.  Most segments of
-				// a real font are a fraction of a pixel tall and most lie outside the span's band of rows: two
-				// exact compares reject those before the integer brackets are computed.
+				// Rows crossed: lo <= py < hi with py = yy + y0c exactly as the reference forms it.
+				// The brackets from the f32 record first.  Row n lies at n - hh + 1/2 against the origin, so first_ge(y) =
+				// ceil(t) + hh with t = (y - oy) - 1/2, clamped; tv and tw are t of the two end points to within E_row
+				// (DESIGN.md §4.1), and ceil is monotone, so the smaller one is lo's whichever way the segment runs.  Farther
+				// than E_row from every integer, both are the exact brackets, and the clamps to the span's rows do what
+				// the band test does.  mf = inf (a NaN or an infinity in the record) or >= 10^6 leaves the lane to first_ge.
+				const float tv = fvy - 0.5f, tw = (fvy + fdy) - 0.5f;
+				const float e_row = VG_M_ROW_E(__builtin_fmaf(STAGE_ROW_C, fmaxf(mf, mpix), STAGE_ROW_ABS));
+				const bool decided = __builtin_fminf(int_dist(tv), int_dist(tw)) > e_row && mf < STAGE_M_MAX;
+				const int cv = (int)__builtin_ceilf(tv), cw = (int)__builtin_ceilf(tw);
+				const int c_lo = y_lo - hh, c_hi = y_hi + 1 - hh;
+				const int ca = min(max(min(cv, cw), c_lo), c_hi), cb = min(max(max(cv, cw), c_lo), c_hi);
+				ya = ca + hh;
+				nrow = decided ? (uint32_t)(cb - ca) : 0u;
+				row_exact = vy != wy && !decided; // (a level segment crosses no row wherever it lies: tv == tw)
+			}
+			const bool row_fb = __builtin_amdgcn_ballot_w64(row_exact) != 0; // wave-uniform: the f64 brackets are skipped, not masked
+			VG_COUNT(cn_row_fb += row_fb);
+			if (row_fb && row_exact) {
+				// Most segments of a real font are a fraction of a pixel tall and most lie outside the span's band of rows:
+				// two exact compares reject those before the integer brackets are computed.
+				const double vy = e_vy[i], wy = e_wy[i]; // (this thread's own stores)
+				const double y0c = (double)gy0 + 0.5;    // renderer_precise.rs:28
+				const double band_lo = (double)y_lo + y0c, band_hi = (double)y_hi + y0c; // lowest / highest sample row of the span
 				const bool up = vy < wy;
 				const double lo = up ? vy : wy, hi = up ? wy : vy;
-				if (vy != wy && hi > band_lo && lo <= band_hi) {
+				if (hi > band_lo && lo <= band_hi) {
 					ya = first_ge(lo, y0c, y_lo, y_hi + 1);
 					const int yb = first_ge(hi, y0c, y_lo, y_hi + 1); // first row with py >= hi
 					nrow = yb > ya ? (uint32_t)(yb - ya) : 0u;
@@ -311,6 +335,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				const uint32_t incl = wave_scan_add(nrow); // inclusive prefix sum over the wave
 				const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
 				auto cross = [&](double vx, double vy, double dx, double dy, bool up, int yy) {
+					const double x0c = (double)gx0 + 0.5, y0c = (double)gy0 + 0.5; // renderer_precise.rs:27-28
 					const double pyy = (double)yy + y0c;
 					const double tc = (pyy - vy) / dy;
 					const double xc = vx + tc * dx;               // :45-46 / :48-49
@@ -320,7 +345,10 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 				};
 				if (total != 0 && total <= QCAP) {
 					// (lane, row) pairs of the wave, pooled in LDS (rows of a span: < 1024, host-checked through DELTA_CAP)
+					// (not unrolled: a wave's longest segment crosses two or three rows on a font, and the unrolled loop's
+					// entry checks cost more than its trips)
 					uint32_t off = incl - nrow;
+#pragma unroll 1
 					for (uint32_t r = 0; r < nrow; r++)
 						q_pair[wv][off++] = (lane << 10) | (uint32_t)(y_hi - (ya + (int)r));
 					__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -805,6 +833,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 		atomicAdd(&g_span_dbg[22], cn_fb_lane);
 		atomicAdd(&g_span_dbg[23], cn_half);
 		atomicAdd(&g_span_dbg[24], cn_leave);
+		atomicAdd(&g_span_dbg[25], cn_row_fb);
 	}
 #endif
 }
@@ -837,3 +866,4 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 #undef VG_M_FAR
 #undef VG_M_TK_PUSH
 #undef VG_M_TK
+#undef VG_M_ROW_E

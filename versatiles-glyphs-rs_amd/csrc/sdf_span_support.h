@@ -84,6 +84,21 @@ __device__ __forceinline__ int first_ge(double v, double c, int A, int B)
 	return n;
 }
 
+// ---- The stage's f32 decision ahead of first_ge (sdf_span_kernel.inc; derivation in DESIGN.md §4.1, "The stage's integers").
+// A segment's bracket of sample rows is ceil(t) of a real t that the f32 record gives to within a bound E_row: when t lies
+// farther than E_row from every integer, ceil of the f32 value IS the exact integer, and only the other lanes take first_ge.
+constexpr float STAGE_U = 5.9604644775390625e-08f;    // u = 2^-24
+constexpr float STAGE_ROW_C = 6.0f * STAGE_U;         // E_row = 6 u M + 2^-22
+constexpr float STAGE_ROW_ABS = 2.384185791015625e-07f;
+constexpr float STAGE_M_MAX = 1.0e6f;                 // at and beyond it (the sweep's `sane`), and for a NaN, first_ge decides
+
+// distance of a finite t from the nearest integer (v_fract_f32 is exact; 1 - fr rounds once, inside the bound's absolute term)
+__device__ __forceinline__ float int_dist(float t)
+{
+	const float fr = __builtin_amdgcn_fractf(t);
+	return __builtin_fminf(fr, 1.0f - fr);
+}
+
 // h(F): bound on |Ft - D| for a filter value F, coordinates bounded by M:
 // 64 u M sqrt(F) + 32 u F + 2^-34 M^2 with u = 2^-24, evaluated with upward slack.
 // The constants by name (defaults = the analysed values; only a `make margins` instance overrides one, see
