@@ -87,6 +87,17 @@ void vg_manager_set_threads(vg_manager *m, unsigned threads, unsigned blocks_per
 /* 1: flatten / close / scale / bbox on the GPU (device front-end of vgsdf.h; HIP renderer
  * only), 0: on host threads.  Same bytes either way. */
 void vg_manager_set_device_front_end(vg_manager *m, int on);
+/* Union outlines (rule U; vgsdf_batch_union / vgsdf_outlines_union of vgsdf.h): 1 = every route of the
+ * HIP renderer rasters the BOUNDARY of a glyph's filled set instead of its segments, so that the edges of one contour inside
+ * another (overlapping contours of variable fonts, accents over their bases) no longer draw a seam through the stroke.  The
+ * bitmaps are then deliberately NOT the reference crate's; metrics, advances and PBF framing are.  0 (default): the crate's
+ * bytes.  VG_MODE_DUMMY ignores the switch.  Costs the raster fused behind the device front-end's plan.
+ * The manager hands the switch to the renderer for the length of a render call: a renderer serves ONE manager's render call
+ * at a time (calls one after the other may differ in their switches; two at once on one renderer may not). */
+void vg_manager_set_union_outlines(vg_manager *m, int on);
+/* what the union pass saw in this manager's runs so far: glyphs seen = rebuilt + identity (nothing to do) + passed through
+ * over the limit of 6144 segments + passed through with a coordinate that is not finite.  Any pointer may be NULL. */
+void vg_manager_union_stats(const vg_manager *m, uint64_t *seen, uint64_t *rebuilt, uint64_t *identity, uint64_t *over_limit);
 /* 1 (default): blocks are assembled IN PLACE — the raster stores every bitmap where its block's finished PBF has it, the
  * host writes the ~20 bytes around it (src/protobuf/glyphs.rs:66-70 without a second copy of the bitmaps); 0: bitmaps
  * packed back to back, blocks encoded afterwards.  Same bytes either way. */

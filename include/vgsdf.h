@@ -826,6 +826,25 @@ int vgsdf_outlines_pbf_positions(vgsdf_ctx *ctx, uint64_t *bitmap_at);
 int vgsdf_outlines_segments(vgsdf_ctx *ctx, uint32_t *seg_off, double *sx, double *sy, double *ex, double *ey);
 
 /*
+ * Union outlines (rule U): a glyph's segments rewritten on the device into the boundary of its filled
+ * set { p : winding number != 0 }, so that the edges of one contour inside another no longer take part in the distance.  With
+ * it the output is deliberately NOT the reference's.  state: per glyph 0 = nothing to do (the input less its zero-length
+ * segments), 1 = rebuilt, 2 = more than 6144 segments, passed through unchanged, 3 = a non-finite coordinate, passed through.
+ */
+/* b's segments -> the boundary of its filled sets (rule U).  A NEW resident batch with the same
+ * glyphs, rects and out_off; b is untouched and both may be launched.  state: [n_glyphs] or NULL. */
+int vgsdf_batch_union(vgsdf_ctx *ctx, const vgsdf_dbatch *b, vgsdf_dbatch **out, uint8_t *state);
+/* read a resident batch's segments back (seg_off[n_glyphs+1], then four arrays or NULL to size) */
+int vgsdf_batch_segments_read(vgsdf_ctx *ctx, const vgsdf_dbatch *b, uint32_t *seg_off, double *sx, double *sy, double *ex, double *ey);
+/* the same step for the batch vgsdf_outlines_prepare (or submit with out_bitmaps NULL + wait) left on the
+ * context: replaces its segments, descriptors, work list and chunk boxes; vgsdf_outlines_render then
+ * renders the union.  In-place PBF positions are kept.  n_segments (may be NULL): the union's. */
+int vgsdf_outlines_union(vgsdf_ctx *ctx, uint8_t *state, uint64_t *n_segments);
+/* test / inspection (tools/outline_union_ab.py): milliseconds the count and the emit pass of the context's last
+ * vgsdf_batch_union or vgsdf_outlines_union took (HIP events around the pass; 0 0 before the first) */
+void vgsdf_union_kernel_ms(const vgsdf_ctx *ctx, float ms[2]);
+
+/*
  * Multi-GPU: ONE process drives N devices, one context (+ its own host thread) per device; glyph batches
  * are independent (renderer.rs:103 has no shared state), so results need no exchange and the only collective of the
  * path is the sum of the run counters {blocks, glyphs, pixels} over the contexts.

@@ -8,10 +8,11 @@
 //                           the fonts the device builds: from loca and glyf, from charstrings, from loca, glyf and gvar
 //                           (resident_command_store.h: what the builders of command stores share)
 //   resident_families.cpp   the families over them, named by code-point range (resident_build.h: what all of these share)
+//   outline_union.cpp       union outlines: a resident batch's segments -> the boundary of its filled sets
 //   run_counters.cpp        run counters and their RCCL reduction
 // The kernels they launch are translation units of their own, each with a header of its name: sdf_kernels (raster),
 // input_form_kernels, outline_kernels, outline_plan_kernels (the device front-end: input forms, flattening, plan),
-// charstring_kernels, family_table_kernels, glyf_table_kernels (the constructors of resident stores).
+// charstring_kernels, family_table_kernels, glyf_table_kernels (the constructors of resident stores), outline_union_kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -89,6 +90,7 @@ struct vgsdf_ctx {
 	// at most 2^17 points — points x positions in the batched call —, or of one glyph id at one position); grown on demand, belongs
 	// to no font
 	DevBuf gvar_scratch;
+	float union_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_batch_union or vgsdf_outlines_union (outline_union.cpp)
 	std::string reduce_path; // how the last vgsdf_reduce_counters with this context first took its sum (vgsdf_reduce_path)
 };
 
@@ -122,6 +124,24 @@ inline bool uses_span_list(int variant) { return variant == 0 || (variant >= 50 
 
 constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the one device arena of a resident batch: [descs | tiles | sx | sy | ex | ey | out | chunk boxes], every part aligned to 256
+// bytes; input_bytes: what the host stages (everything in front of `out`)
+struct BatchArena {
+	size_t desc = 0, tiles, sx, sy, ex, ey, input_bytes, out, boxes, bytes;
+	BatchArena(uint32_t n_glyphs, uint64_t n_tiles, uint64_t n_seg, uint64_t n_pix)
+	{
+		const size_t A = 256;
+		tiles = align_up(sizeof(vgsdf::GlyphDesc) * (size_t)n_glyphs, A);
+		sx = align_up(tiles + sizeof(uint2) * (size_t)n_tiles, A);
+		const size_t seg_bytes = align_up(sizeof(double) * (size_t)n_seg, A);
+		sy = sx + seg_bytes, ex = sx + 2 * seg_bytes, ey = sx + 3 * seg_bytes;
+		input_bytes = out = sx + 4 * seg_bytes;
+		boxes = align_up(out + (size_t)n_pix, A);
+		const size_t end = align_up(boxes + vgsdf_chunk_box_bytes(n_seg, n_glyphs), A);
+		bytes = end ? end : A;
+	}
+};
+
 inline double fe_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // (functions shared between the translation units stay out of the library's exported symbols)
@@ -138,6 +158,13 @@ VGSDF_INTERNAL void *pinned_device_ptr(void *p, size_t bytes);
 // Fills the glyph descriptors and the tile list (routing + order) of a batch, and b->n_main, b->stats.n_tiles,
 // b->span_list, b->tile_order.  `ht` must hold one entry per 256-pixel tile of the batch.  (work_list.cpp)
 VGSDF_INTERNAL void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, uint2 *ht, vgsdf_dbatch *b, bool span);
+
+// Rule U over a resident batch (outline_union.cpp): a NEW batch with src's glyphs, rects and out_off whose segments are the
+// boundary of the filled sets, with descriptors, work list and chunk boxes over them; complete on the device when the call
+// returns.  own_output false: without an output buffer of its own (d_out NULL: the caller points it at one of out_bytes).
+// state_out: [n_glyphs] or NULL.  `entry`: the exported function's name for the error text
+VGSDF_INTERNAL int union_resident(vgsdf_ctx *ctx, const char *entry, const vgsdf_dbatch *src, vgsdf_dbatch **out, uint8_t *state_out,
+                                  bool own_output);
 
 // frees the front-end state of a context that is being destroyed (outline_front_end.cpp)
 VGSDF_INTERNAL void fe_destroy(struct FrontEnd *fe);

@@ -131,6 +131,19 @@ void vg_manager_reduced_counters(const vg_manager *m, uint64_t counters[3]) { st
 vg_manager *vg_manager_new(int parallel) { return new vg_manager(parallel != 0); }
 void vg_manager_free(vg_manager *m) { delete m; }
 void vg_manager_set_device_front_end(vg_manager *m, int on) { m->m.set_device_front_end(on != 0); }
+void vg_manager_set_union_outlines(vg_manager *m, int on) { m->m.set_union_outlines(on != 0); }
+void vg_manager_union_stats(const vg_manager *m, uint64_t *seen, uint64_t *rebuilt, uint64_t *identity, uint64_t *over_limit)
+{
+	const uint64_t *s = m->m.union_stats();
+	if (seen)
+		*seen = s[0] + s[1] + s[2] + s[3];
+	if (rebuilt)
+		*rebuilt = s[1];
+	if (identity)
+		*identity = s[0];
+	if (over_limit)
+		*over_limit = s[2];
+}
 void vg_manager_set_in_place_pbf(vg_manager *m, int on) { m->m.set_in_place_pbf(on != 0); }
 void vg_manager_set_glyf_on_device(vg_manager *m, int on) { m->m.set_glyf_on_device(on != 0); }
 void vg_manager_set_resident_fonts(vg_manager *m, int on) { m->m.set_resident_fonts(on != 0); }

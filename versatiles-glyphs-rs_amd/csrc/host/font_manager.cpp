@@ -963,8 +963,31 @@ const std::vector<GlyphBlock> &FontManager::task_blocks(const std::string &font_
 	return shard_blocks_[font_id] = std::move(blocks);
 }
 
+// A run's union switch: handed to the renderer (and its peers) for the run and taken back when it is over, also when it throws,
+// with what the pass saw.  The lanes of a multi-device run are inside their parent's.
+struct FontManager::UnionRun {
+	FontManager &m;
+	const Renderer &r;
+	UnionRun(FontManager &mgr, const Renderer &ren) : m(mgr), r(ren)
+	{
+		if (!m.parent_)
+			r.set_union_outlines(m.union_outlines_);
+	}
+	~UnionRun()
+	{
+		if (m.parent_)
+			return;
+		r.set_union_outlines(false);
+		uint64_t seen[4];
+		r.take_union_stats(seen);
+		for (int s = 0; s < 4; s++)
+			m.union_stats_[s] += seen[s];
+	}
+};
+
 void FontManager::render_glyphs(Writer &writer, const Renderer &renderer)
 {
+	const UnionRun union_run(*this, renderer);
 	if (renderer.n_devices() > 1 && renderer.mode() == Renderer::Mode::Hip && !parent_) {
 		render_glyphs_multi(writer, renderer);
 		return;
@@ -987,6 +1010,7 @@ void FontManager::render_blocks(Writer &writer, const Renderer &renderer, const 
 	const FontEntry *it = find_font(font_id, &err);
 	if (!it)
 		throw std::runtime_error(err);
+	const UnionRun union_run(*this, renderer);
 	const std::vector<GlyphBlock> &blocks = task_blocks(it->first, it->second);
 	std::vector<Todo> tasks;
 	for (uint32_t start : block_starts) {

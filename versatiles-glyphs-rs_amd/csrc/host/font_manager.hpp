@@ -312,6 +312,14 @@ public:
 	// false: host tessellation.  Both produce identical bytes.
 	void set_device_front_end(bool on) { device_front_end_ = on; }
 	bool device_front_end() const { return device_front_end_; }
+	// true: union outlines (rule U) — render_glyphs and render_blocks of this manager hand the switch to their
+	// renderer for the run (Renderer::set_union_outlines), on either route; the bitmaps are then deliberately NOT the reference's.  Off by default;
+	// the dummy renderer ignores it.  Metrics, advances and PBF framing do not change.
+	void set_union_outlines(bool on) { union_outlines_ = on; }
+	bool union_outlines() const { return union_outlines_; }
+	// glyphs the union pass has seen in this manager's runs: {identity, rebuilt, passed through over the limit, passed through
+	// with a non-finite coordinate}
+	const uint64_t *union_stats() const { return union_stats_; }
 	// true (default): with the device front-end the blocks are assembled IN PLACE — the raster stores every bitmap where
 	// the finished PBF has it and the host writes the ~20 bytes around it; false: bitmaps packed back to back, blocks
 	// encoded afterwards (one more copy of every bitmap).  Same bytes either way.
@@ -700,6 +708,9 @@ private:
 	const vgsdf_font *command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
 	bool resident_families_ = false;
 	bool device_front_end_ = true; // HIP renderer: flatten on the GPU unless switched off
+	bool union_outlines_ = false;
+	uint64_t union_stats_[4] = {0, 0, 0, 0};
+	struct UnionRun; // (font_manager.cpp)
 	std::map<std::string, FontWrapper> fonts_; // reference: HashMap (arbitrary order); sorted here
 	bool parallel_;
 	unsigned threads_ = 0;       // 0 = hardware_concurrency

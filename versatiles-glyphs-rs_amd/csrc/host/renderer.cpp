@@ -420,7 +420,8 @@ void Renderer::submit_on_lane(int lane, const Batch &v, HostBuffer<uint8_t> &out
 		if (out.capacity() == 0)
 			out.ensure((size_t)v.n_glyphs * 480 + 16384);
 		std::lock_guard<std::mutex> lock(mu_);
-		if (submit(c, &v, out.data(), out.capacity()) != VGSDF_OK)
+		const bool u = union_outlines(); // no raster behind the plan: wait_outlines renders the union
+		if (submit(c, &v, u ? nullptr : out.data(), u ? 0 : out.capacity()) != VGSDF_OK)
 			throw std::runtime_error(std::string(name) + ": " + vgsdf_last_error(c));
 		if (block_bytes)
 			*block_bytes = vgsdf_outlines_resident_upload_bytes(c);
@@ -983,7 +984,8 @@ void Renderer::submit_ranges(int lane, const vgsdf_outlines_ranges &v, uint32_t 
 		if (out.capacity() == 0)
 			out.ensure((size_t)n_glyphs * 480 + 16384);
 		std::lock_guard<std::mutex> lock(mu_);
-		if (vgsdf_outlines_submit_ranges(c, &v, out.data(), out.capacity()) != VGSDF_OK)
+		const bool u = union_outlines(); // (as submit_on_lane)
+		if (vgsdf_outlines_submit_ranges(c, &v, u ? nullptr : out.data(), u ? 0 : out.capacity()) != VGSDF_OK)
 			throw std::runtime_error(std::string("vgsdf_outlines_submit_ranges: ") + vgsdf_last_error(c));
 		if (block_bytes)
 			*block_bytes = vgsdf_outlines_resident_upload_bytes(c);
@@ -1061,6 +1063,12 @@ void Renderer::wait_outlines(int lane, std::vector<vgsdf_rect> &rects, HostBuffe
 		throw std::runtime_error(std::string("vgsdf_outlines_wait: ") + vgsdf_last_error(c));
 	}
 	if (!rendered && out_bytes) {
+		if (union_outlines()) {
+			std::vector<uint8_t> state(n_glyphs);
+			if (vgsdf_outlines_union(c, state.data(), nullptr) != VGSDF_OK)
+				throw std::runtime_error(std::string("vgsdf_outlines_union: ") + vgsdf_last_error(c));
+			count_union_states(state);
+		}
 		out.ensure((size_t)out_bytes + 1);
 		if (vgsdf_outlines_render(c, out.data()) != VGSDF_OK)
 			throw std::runtime_error(std::string("vgsdf_outlines_render: ") + vgsdf_last_error(c));
@@ -1086,13 +1094,73 @@ void Renderer::render_outlines(const vgsdf_outlines &v, std::vector<vgsdf_rect> 
 	if (out.capacity() == 0)
 		out.ensure((size_t)v.n_glyphs * 448 + 4096);
 	int rendered = 0;
-	if (vgsdf_outlines_render_into(ctx_, &v, rects.data(), out.data(), out.capacity(), &out_bytes, &n_segments, &rendered) != VGSDF_OK)
+	const bool u = union_outlines();
+	if (vgsdf_outlines_render_into(ctx_, &v, rects.data(), u ? nullptr : out.data(), u ? 0 : out.capacity(), &out_bytes, &n_segments, &rendered) != VGSDF_OK)
 		throw std::runtime_error(std::string("vgsdf_outlines_render_into: ") + vgsdf_last_error(ctx_));
 	if (!rendered && out_bytes) {
+		if (u) {
+			std::vector<uint8_t> state(v.n_glyphs);
+			if (vgsdf_outlines_union(ctx_, state.data(), nullptr) != VGSDF_OK)
+				throw std::runtime_error(std::string("vgsdf_outlines_union: ") + vgsdf_last_error(ctx_));
+			count_union_states(state);
+		}
 		out.ensure((size_t)out_bytes + 1);
 		if (vgsdf_outlines_render(ctx_, out.data()) != VGSDF_OK)
 			throw std::runtime_error(std::string("vgsdf_outlines_render: ") + vgsdf_last_error(ctx_));
 	}
+}
+
+void Renderer::set_union_outlines(bool on) const
+{
+	union_outlines_.store(on);
+	for (const auto &p : peers_)
+		p->set_union_outlines(on);
+}
+
+void Renderer::take_union_stats(uint64_t by_state[4]) const
+{
+	for (int s = 0; s < 4; s++)
+		by_state[s] = union_seen_[s].exchange(0);
+	for (const auto &p : peers_) {
+		uint64_t theirs[4];
+		p->take_union_stats(theirs);
+		for (int s = 0; s < 4; s++)
+			by_state[s] += theirs[s];
+	}
+}
+
+void Renderer::count_union_states(const std::vector<uint8_t> &state) const
+{
+	uint64_t seen[4] = {0, 0, 0, 0};
+	for (uint8_t s : state)
+		seen[s & 3]++;
+	for (int s = 0; s < 4; s++)
+		union_seen_[s] += seen[s];
+}
+
+void Renderer::render_view(const vgsdf_batch &v, uint8_t *out) const
+{
+	if (!union_outlines()) {
+		if (vgsdf_render_batch(ctx_, &v, out) != VGSDF_OK)
+			throw std::runtime_error(std::string("vgsdf_render_batch: ") + vgsdf_last_error(ctx_));
+		return;
+	}
+	vgsdf_dbatch *in = nullptr, *un = nullptr;
+	std::vector<uint8_t> state(v.n_glyphs);
+	const char *step = "vgsdf_batch_upload";
+	int rc = vgsdf_batch_upload(ctx_, &v, &in);
+	if (rc == VGSDF_OK)
+		step = "vgsdf_batch_union", rc = vgsdf_batch_union(ctx_, in, &un, state.data());
+	if (rc == VGSDF_OK)
+		step = "vgsdf_batch_launch", rc = vgsdf_batch_launch(ctx_, un);
+	if (rc == VGSDF_OK)
+		step = "vgsdf_batch_download", rc = vgsdf_batch_download(ctx_, un, out);
+	const std::string what = rc == VGSDF_OK ? std::string() : std::string(step) + ": " + vgsdf_last_error(ctx_);
+	vgsdf_batch_free(ctx_, un);
+	vgsdf_batch_free(ctx_, in);
+	if (rc != VGSDF_OK)
+		throw std::runtime_error(what);
+	count_union_states(state);
 }
 
 void Renderer::render_batch(const GlyphBatch &batch, uint8_t *out) const
@@ -1104,9 +1172,7 @@ void Renderer::render_batch(const GlyphBatch &batch, uint8_t *out) const
 		return;
 	}
 	std::lock_guard<std::mutex> lock(mu_);
-	const vgsdf_batch v = batch.view();
-	if (vgsdf_render_batch(ctx_, &v, out) != VGSDF_OK)
-		throw std::runtime_error(std::string("vgsdf_render_batch: ") + vgsdf_last_error(ctx_));
+	render_view(batch.view(), out);
 }
 
 void Renderer::render_packed(PackedBatch &batch) const
@@ -1118,9 +1184,7 @@ void Renderer::render_packed(PackedBatch &batch) const
 		return;
 	}
 	std::lock_guard<std::mutex> lock(mu_);
-	const vgsdf_batch v = batch.view();
-	if (vgsdf_render_batch(ctx_, &v, batch.out.data()) != VGSDF_OK)
-		throw std::runtime_error(std::string("vgsdf_render_batch: ") + vgsdf_last_error(ctx_));
+	render_view(batch.view(), batch.out.data());
 }
 
 std::optional<PbfGlyph> Renderer::render_glyph(const Face &face, uint32_t index) const

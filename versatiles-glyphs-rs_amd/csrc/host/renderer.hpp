@@ -18,6 +18,7 @@
 #include <set>
 #include <memory>
 #include <new>
+#include <atomic>
 #include <mutex>
 #include <optional>
 #include <stdexcept>
@@ -577,6 +578,17 @@ public:
 	void submit_ranges(int lane, const vgsdf_outlines_ranges &batch, uint32_t n_glyphs, HostBuffer<uint8_t> &out, uint64_t *block_bytes) const;
 	void task_extents(int lane, std::vector<uint64_t> &begin, uint32_t n_tasks) const;
 	void set_resident_budget(uint64_t bytes_per_device);
+	// Union outlines (rule U; off by default): every Hip route renders the boundary of a glyph's filled set
+	// instead of its segments — render_batch / render_packed go upload, vgsdf_batch_union, launch, download, and the device
+	// front-end's submissions go without a destination (no raster behind the plan), vgsdf_outlines_union, vgsdf_outlines_render
+	// in wait_outlines.  Dummy ignores it.  Reaches the peers of a multi-device renderer.  FontManager sets it for its runs
+	// (render_glyphs, render_blocks) and takes it back afterwards: the switch and the counts below are the RENDERER's, so a
+	// renderer serves one manager's run at a time — two managers that render on one renderer from two threads at once would
+	// switch each other's run and share the counts (runs one after the other, with any switches, are fine).
+	void set_union_outlines(bool on) const;
+	bool union_outlines() const { return union_outlines_.load(); }
+	// glyphs the union pass has seen since the last call, by state {identity, rebuilt, over the limit, non-finite}; resets them
+	void take_union_stats(uint64_t by_state[4]) const;
 	uint64_t resident_bytes(int device) const; // what the renderer's resident fonts occupy on a device
 	void wait_outlines(int lane, std::vector<vgsdf_rect> &rects, HostBuffer<uint8_t> &out, uint64_t &out_bytes,
 	                   uint64_t &n_segments, uint32_t n_glyphs, std::vector<uint64_t> *pbf_at = nullptr) const;
@@ -607,6 +619,11 @@ private:
 	mutable vgsdf_ctx *ctx2_ = nullptr; // lane 1 of the two-deep pipeline (created on first use)
 	mutable std::mutex lane_mu_[2];     // held from submit_outlines to wait_outlines
 	vgsdf_ctx *lane_ctx(int lane) const;
+	mutable std::atomic<bool> union_outlines_{false};
+	mutable std::atomic<uint64_t> union_seen_[4] = {};
+	void count_union_states(const std::vector<uint8_t> &state) const;
+	// vgsdf_render_batch, or with union outlines its four steps around vgsdf_batch_union; under mu_
+	void render_view(const vgsdf_batch &v, uint8_t *out) const;
 	// what the submit_outlines overloads share: the lane held from here to wait_outlines (released when this throws), the first
 	// capacity guess for `out`, the context's lock around the C call `submit` (`name`: for the error)
 	template <class Batch>

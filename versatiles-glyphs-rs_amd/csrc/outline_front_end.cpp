@@ -60,6 +60,17 @@ struct FrontEnd {
 	vgsdf_dbatch batch; // borrowed view over the buffers above
 	bool prepared = false;
 	bool peeked = false; // vgsdf_outlines_peek has waited for the read-back of the pending submission
+	// vgsdf_outlines_union: the arena `batch` views instead of the buffers above, until the next submission is waited for
+	vgsdf_dbatch *unioned = nullptr;
+	void drop_union() // (nothing in flight uses it: the callers stand behind a synchronisation)
+	{
+		if (!unioned)
+			return;
+		(void)hipFree(unioned->d_arena);
+		(void)hipHostFree(unioned->h_stage);
+		delete unioned;
+		unioned = nullptr;
+	}
 	FrontEnd()
 	{
 		h_rects.host = true;
@@ -71,6 +82,7 @@ struct FrontEnd {
 		for (DevBuf *b : {&cmds, &kinds, &coords, &meta, &cmd_open, &counts, &pt_local, &cmd_box, &cmd_mask, &rings, &cmd_ring, &rects_hdr, &descs, &tiles, &flag, &seg, &out, &boxes, &pbf_in,
 		                  &h_rects, &h_stage})
 			b->release();
+		drop_union();
 	}
 };
 
@@ -841,6 +853,7 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 	}
 	p.active = false;
 	if (n == 0) {
+		fe.drop_union(); // (the batch it belonged to is gone; the union and every render of it ended with a synchronisation)
 		fe.prepared = true;
 		if (rendered && p.spec_out)
 			*rendered = 1;
@@ -850,6 +863,7 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 	hipStream_t st = ctx->stream;
 	FE_TRY(hipStreamSynchronize(st)); // the one synchronisation of the submission
 	FE_TRY(hipEventSynchronize(ctx->ev_rects)); // (the read-back finished long ago: it left right behind the plan)
+	fe.drop_union();
 	const double tr2 = fe_now();
 	if (rects_out)
 		std::memcpy(rects_out, fe.h_rects.p, sizeof(vgsdf_rect) * (size_t)n);
@@ -1441,6 +1455,39 @@ int vgsdf_outlines_render(vgsdf_ctx *ctx, uint8_t *out_bitmaps)
 	return rc;
 }
 
+int vgsdf_outlines_union(vgsdf_ctx *ctx, uint8_t *state, uint64_t *n_segments)
+{
+	if (n_segments)
+		*n_segments = 0;
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!ctx->fe || !ctx->fe->prepared) {
+		ctx->err = "vgsdf_outlines_union: call vgsdf_outlines_prepare first";
+		return VGSDF_E_ARG;
+	}
+	FrontEnd &fe = *ctx->fe;
+	if (fe.n_glyphs == 0)
+		return VGSDF_OK;
+	// the prepared batch's segments, descriptors, work list and chunk boxes are replaced; its output buffer and, with in-place
+	// PBF assembly, the bitmap positions in the descriptors' out_off stay
+	vgsdf_dbatch *u = nullptr;
+	if (int rc = union_resident(ctx, "vgsdf_outlines_union", &fe.batch, &u, state, /*own_output=*/false); rc != VGSDF_OK)
+		return rc;
+	fe.drop_union(); // (a second union of the same batch read the first one's arena)
+	fe.unioned = u;
+	vgsdf_dbatch &b = fe.batch;
+	b.stats = u->stats;
+	b.d_glyphs = u->d_glyphs, b.d_tiles = u->d_tiles;
+	b.d_sx = u->d_sx, b.d_sy = u->d_sy, b.d_ex = u->d_ex, b.d_ey = u->d_ey;
+	b.seg_stride = u->seg_stride;
+	b.d_boxes = u->span_list ? u->d_boxes : nullptr;
+	b.n_main = u->n_main, b.span_list = u->span_list, b.tile_order = u->tile_order;
+	fe.n_segs = (uint32_t)u->stats.n_segments;
+	if (n_segments)
+		*n_segments = fe.n_segs;
+	return VGSDF_OK;
+}
+
 int vgsdf_outlines_segments(vgsdf_ctx *ctx, uint32_t *seg_off, double *sx, double *sy, double *ex, double *ey)
 {
 	if (!ctx)
@@ -1450,6 +1497,8 @@ int vgsdf_outlines_segments(vgsdf_ctx *ctx, uint32_t *seg_off, double *sx, doubl
 		return VGSDF_E_ARG;
 	}
 	FrontEnd &fe = *ctx->fe;
+	if (fe.unioned && seg_off) // (after vgsdf_outlines_union: the union's segments)
+		return vgsdf_batch_segments_read(ctx, fe.unioned, seg_off, sx, sy, ex, ey);
 	(void)hipSetDevice(ctx->device);
 	std::vector<vgsdf::GlyphDesc> hd;
 	if (fe.n_glyphs && seg_off) {

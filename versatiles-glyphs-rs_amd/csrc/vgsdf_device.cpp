@@ -249,22 +249,11 @@ static int upload_impl(vgsdf_ctx *ctx, const vgsdf_batch *in, vgsdf_dbatch **out
 	b->stats.alg_bytes = 32 * n_seg + 32 * (uint64_t)n + n_pixels;
 	b->out_bytes = n_pix;
 
-	const size_t A = 256;
-	size_t off = 0;
-	const size_t off_desc = off;
-	off = align_up(off + sizeof(vgsdf::GlyphDesc) * (size_t)n, A);
-	const size_t off_tiles = off;
-	off = align_up(off + sizeof(uint2) * (size_t)n_tiles, A);
-	const size_t seg_bytes = align_up(sizeof(double) * (size_t)n_seg, A);
-	const size_t off_sx = off, off_sy = off + seg_bytes, off_ex = off + 2 * seg_bytes,
-	             off_ey = off + 3 * seg_bytes;
-	off += 4 * seg_bytes;
-	b->input_bytes = off;
-	const size_t off_out = off;
-	off = align_up(off + (size_t)n_pix, A);
-	const size_t off_boxes = off;
-	off = align_up(off + vgsdf_chunk_box_bytes(n_seg, n), A);
-	b->arena_bytes = off ? off : A;
+	const BatchArena at(n, n_tiles, n_seg, n_pix);
+	const size_t off_desc = at.desc, off_tiles = at.tiles, off_sx = at.sx, off_sy = at.sy, off_ex = at.ex, off_ey = at.ey, off_out = at.out,
+	             off_boxes = at.boxes;
+	b->input_bytes = at.input_bytes;
+	b->arena_bytes = at.bytes;
 
 	(void)hipSetDevice(ctx->device);
 	hipError_t e = hipSuccess;

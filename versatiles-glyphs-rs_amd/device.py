@@ -147,6 +147,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_family_create_tables_var", "vgsdf_family_create_tables_var_mixed",
     "vgsdf_gvar_advance_deltas", "vgsdf_gvar_advance_kernel_ms", "vgsdf_family_create_tables_gvar", "vgsdf_family_create_tables_gvar_mixed",
     "vgsdf_families_create_tables", "vgsdf_families_create_tables_mixed", "vgsdf_gvar_advance_deltas_batch", "vgsdf_families_tables_kernel_ms",
+    "vgsdf_batch_union", "vgsdf_batch_segments_read", "vgsdf_outlines_union", "vgsdf_union_kernel_ms",
 ]
 
 _lib = None
@@ -191,6 +192,11 @@ def load_library():
         L.vgsdf_outlines_submit_packed.argtypes = [vp, vp, vp, C.c_size_t]
         L.vgsdf_outlines_submit_glyf.argtypes = [vp, vp, vp, C.c_size_t]
         L.vgsdf_outlines_segments.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.vgsdf_batch_union.argtypes = [vp, vp, C.POINTER(vp), vp]
+        L.vgsdf_batch_segments_read.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        L.vgsdf_outlines_union.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+        L.vgsdf_union_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.vgsdf_union_kernel_ms.restype = None
         L.vgsdf_outlines_pbf_positions.argtypes = [vp, vp]
         L.vgsdf_outlines_peek.argtypes = [vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.vgsdf_font_create.argtypes = [vp, C.POINTER(_CFontDesc), C.POINTER(vp)]
@@ -371,6 +377,24 @@ class DeviceBatch:
 
     def device_output_ptr(self) -> int:
         return int(load_library().vgsdf_batch_device_output(self._h) or 0)
+
+    def union(self):
+        """vgsdf_batch_union: rule U over this batch -> (a NEW DeviceBatch of the same glyphs and rects whose segments are
+        the boundary of the filled sets, state u8[n_glyphs]: 0 identity, 1 rebuilt, 2 over the limit, 3 non-finite)"""
+        state = np.zeros(self.stats()["n_glyphs"], dtype=np.uint8)
+        h = C.c_void_p()
+        self.ctx._check(load_library().vgsdf_batch_union(self.ctx._h, self._h, C.byref(h), state.ctypes.data))
+        return DeviceBatch(self.ctx, h, self.out_bytes), state
+
+    def segments(self):
+        """vgsdf_batch_segments_read -> (seg_off[n+1], segs[S,4])"""
+        L = load_library()
+        seg_off = np.zeros(self.stats()["n_glyphs"] + 1, dtype=np.uint32)
+        self.ctx._check(L.vgsdf_batch_segments_read(self.ctx._h, self._h, seg_off.ctypes.data, None, None, None, None))
+        ns = int(seg_off[-1])
+        cols = [np.zeros(ns, dtype=np.float64) for _ in range(4)]
+        self.ctx._check(L.vgsdf_batch_segments_read(self.ctx._h, self._h, seg_off.ctypes.data, *[c.ctypes.data for c in cols]))
+        return seg_off, np.stack(cols, axis=1) if ns else np.zeros((0, 4))
 
     def free(self):
         if self._h:
@@ -1203,6 +1227,22 @@ class SdfContext:
         out = np.empty(self._fe[1], dtype=np.uint8)
         self._check(load_library().vgsdf_outlines_render(self._h, out.ctypes.data))
         return out
+
+    def outlines_union(self) -> np.ndarray:
+        """vgsdf_outlines_union: rule U over the prepared batch (outlines_render then renders the union) -> state u8[n]"""
+        n, ob, _ = self._fe
+        state = np.zeros(n, dtype=np.uint8)
+        ns = C.c_uint64(0)
+        self._check(load_library().vgsdf_outlines_union(self._h, state.ctypes.data, C.byref(ns)))
+        if n:
+            self._fe = (n, ob, int(ns.value))
+        return state
+
+    def union_kernel_ms(self):
+        """(count, emit) milliseconds of the last union on this context"""
+        ms = (C.c_float * 2)()
+        load_library().vgsdf_union_kernel_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
 
     def outlines_segments(self):
         """the segments the device front-end produced -> (seg_off[n+1], segs[S,4])"""

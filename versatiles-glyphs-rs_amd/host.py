@@ -95,7 +95,7 @@ WRITE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint8), C.
 
 VGFONT_SYMBOLS = [
     "vg_last_error", "vg_renderer_new", "vg_renderer_free", "vg_manager_new", "vg_manager_free",
-    "vg_manager_set_threads", "vg_manager_set_device_front_end", "vg_manager_add_font_with_name", "vg_manager_add_font_data", "vg_manager_add_path",
+    "vg_manager_set_threads", "vg_manager_set_device_front_end", "vg_manager_set_union_outlines", "vg_manager_union_stats", "vg_manager_add_font_with_name", "vg_manager_add_font_data", "vg_manager_add_path",
     "vg_name_to_id", "vg_manager_block_counts", "vg_manager_render_glyphs", "vg_manager_timings",
     "vg_manager_render_block", "vg_manager_render_blocks", "vg_render_glyph", "vg_manager_build_batch", "vg_glyph_batch_view",
     "vg_glyph_batch_free", "vg_manager_record_outlines", "vg_outline_batch_view", "vg_outline_batch_free", "vg_pbf_encode", "vg_manager_family_desc",
@@ -146,6 +146,10 @@ def _L():
         L.vg_manager_set_threads.argtypes = [vp, C.c_uint, C.c_uint]
         L.vg_manager_set_device_front_end.argtypes = [vp, C.c_int]
         L.vg_manager_set_device_front_end.restype = None
+        L.vg_manager_set_union_outlines.argtypes = [vp, C.c_int]
+        L.vg_manager_set_union_outlines.restype = None
+        L.vg_manager_union_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+        L.vg_manager_union_stats.restype = None
         L.vg_manager_set_in_place_pbf.argtypes = [vp, C.c_int]
         L.vg_manager_set_in_place_pbf.restype = None
         L.vg_manager_set_glyf_on_device.argtypes = [vp, C.c_int]
@@ -582,6 +586,17 @@ class FontManager:
         """several device lanes: -1 / 2 hybrid (whole (font, block) tasks, the heaviest blocks split between lanes), 1 whole tasks
         only, 0 glyph-level shards of every font + merge"""
         _L().vg_manager_set_lane_form(self._h, int(form))
+
+    def set_union_outlines(self, on: bool):
+        """union outlines (rule U): the HIP renderer rasters the boundary of every glyph's filled set, so overlapping
+        contours leave no seam; the bitmaps are then NOT the reference's.  Off by default; the dummy renderer ignores it"""
+        _L().vg_manager_set_union_outlines(self._h, 1 if on else 0)
+
+    def union_stats(self) -> dict:
+        """glyphs the union pass saw in this manager's runs: seen = rebuilt + identity + over_limit (+ non-finite)"""
+        v = [C.c_uint64(0) for _ in range(4)]
+        _L().vg_manager_union_stats(self._h, *[C.byref(x) for x in v])
+        return dict(zip(("seen", "rebuilt", "identity", "over_limit"), (int(x.value) for x in v)))
 
     def set_device_front_end(self, on: bool):
         """flatten / close / scale / bbox on the GPU instead of host threads (HIP renderer only)"""
