@@ -220,6 +220,19 @@ typedef struct {
 	uint64_t fallbacks;       /* font ids whose families came from the host's table although the switch is on */
 } vg_family_table_stats;
 int vg_manager_family_table_stats(const vg_manager *m, vg_family_table_stats *out);
+/* ... and of the families of the supplementary planes (vg_manager_set_supplementary_planes; of the last render).  With the switch
+ * above on, a STATIC font id's supplementary families are built by the device (vgsdf_family_create_tables_at), the planes chosen by
+ * ONE vgsdf_family_tables_census call per font id — a plane whose bits are all clear is not built on the device; the host's block
+ * table remains the authority for what is written.  A font id with a placed face (an fvar instance), or with the switch off, or
+ * whose build was refused, takes vgsdf_family_create_at from the host's table.  built_on_device counts among
+ * vg_family_table_stats.built_on_device too. */
+typedef struct {
+	uint64_t census_calls;    /* vgsdf_family_tables_census calls */
+	uint64_t built_on_device; /* supplementary families the device built */
+	uint64_t stated_by_host;  /* supplementary families stated by the host through vgsdf_family_create_at */
+	uint64_t planes;          /* bit p: a family of plane p (1 .. 16) was made, either way */
+} vg_family_plane_stats;
+int vg_manager_family_plane_stats(const vg_manager *m, vg_family_plane_stats *out);
 /* Glyf tables on the device, 0 (default) / 1: wherever the renderer makes a glyf-kind resident font — glyph-named groups, the
  * families, vg_renderer_preload_fonts — the DEVICE walks the face's `loca` and `glyf` tables (vgsdf_font_create_tables); the host
  * only says where the tables are (vg_manager_font_tables_desc) and interprets no glyph.  A face whose build the device refuses
@@ -423,6 +436,27 @@ long vg_manager_families_json(const vg_manager *m, uint8_t *out, size_t cap);
 int vg_name_to_id(const char *name, char *out, size_t cap);
 /* number of code points (<= 0xFFFF) the font id maps after first-provider-wins merging */
 int vg_manager_block_counts(const vg_manager *m, const char *font_id, uint32_t counts[256]);
+/*
+ * Supplementary planes (default off): code points above U+FFFF, which the reference skips (wrapper.rs:66-68).  With the switch
+ * on every font id's block table keeps its 256 blocks of the BMP, all of them, empty ones included, and lists behind them one
+ * block per POPULATED range [256 b, 256 b + 255] above U+FFFF, ascending, first provider wins as in the BMP; empty supplementary
+ * blocks are not written.  vg_manager_render_glyphs writes "<start>-<start + 255>.pbf" for them like any other block;
+ * vg_manager_render_blocks and vg_manager_render_block find such a block by its start, and a supplementary start the font id
+ * does not populate is "bad block start".  A supplementary block is never split: under vg_manager_set_glyph_shard it belongs
+ * whole to rank (start / 256) % world and the other ranks neither list nor write it (vg_manager_render_blocks passes such a
+ * start over), so the files of all ranks together are the single-rank files; in a multi-device run it goes whole to that lane.
+ * owner[65536] / cost[65536] of vg_manager_shard_glyphs and vg_manager_plan_lanes keep their size and meaning.  The forms that
+ * name glyphs (host tessellation, packed, glyf parts, resident fonts and command stores, mixed) take such a block as any other;
+ * the ranges forms (vg_manager_set_resident_families) name ONE FAMILY PER PLANE of the font id — same stores, budget and lifetime,
+ * each table with a serial of its own — and emit tasks with the low halves; with vg_manager_set_family_tables_on_device a static
+ * font id's supplementary families are built by the device, the planes chosen by one census call (vg_family_plane_stats below),
+ * otherwise and for a font id with a placed face the host states them from its block table (vgsdf_family_create_at).
+ * Union outlines, in-place PBF and VG_MODE_DUMMY work on such a block as on any other.  With the switch off every byte stays what
+ * it is.  vg_manager_supplementary_blocks: how many such blocks the font id has (0 with the switch off); fills up to `cap` of
+ * starts / counts (each may be NULL), ascending; -1: unknown font id.  vg_manager_block_counts is unchanged.
+ */
+int vg_manager_set_supplementary_planes(vg_manager *m, int on);
+int vg_manager_supplementary_blocks(const vg_manager *m, const char *font_id, uint32_t *starts, uint32_t *counts, int cap);
 
 /* Native sinks (src/writer): a ustar stream into a file or an open descriptor (e.g. 1 = stdout,
  * `recurse --tar`), or a directory tree.  mtime < 0 stamps every tar header with the wall clock as

@@ -683,6 +683,44 @@ int vgsdf_family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *i
  * entries.  (vgsdf_family_tables_kernel_ms reports its passes as well.) */
 int vgsdf_family_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, vgsdf_family **out);
 /*
+ * A family belongs to a PLANE p, 0 .. 16: its 16-bit code_point entries, and the first / last of a task that names it, are the
+ * low halves of (p << 16) | x.  Every constructor above and below makes plane 0; these two make any plane, and plane 0 through
+ * them is the family the old entry point makes.  `kind` chooses what the pair of constructors chooses: VGSDF_FAMILY_ONE_KIND
+ * (vgsdf_family_create / _create_tables) or VGSDF_FAMILY_MIXED (_create_mixed / _create_tables_mixed); validation is theirs, and a
+ * plane above 16 or another kind is VGSDF_E_ARG.  pbf_fix counts the varint of the FULL code point (3 bytes in planes 1 .. 16), and
+ * the device writes the full value as the id of an entry's PBF bytes.  vgsdf_family_create_at takes any face, placed ones included
+ * (the host states the advances).  vgsdf_family_create_tables_at is the device build over the code points (p << 16) + 0 .. 0xFFFF
+ * with the surrogates taken from the full value — static faces only — and its result is indistinguishable from
+ * vgsdf_family_create_at of the same entries (vgsdf_family_read).  The lookup answers any code point: a format 0, 4 or 6 subtable
+ * has nothing above 0xFFFF, formats 10, 12 and 13 are followed, a format 12 group whose id + (c - start) passes 0xFFFF has no
+ * value from there on.  One vgsdf_outlines_submit_ranges may name families of different planes (of one kind, as ever); its
+ * output is that of vgsdf_outlines_submit_resident of the sequence with pbf_fix from the full ids.  vgsdf_family_count keeps its
+ * meaning on low halves; vgsdf_family_plane reads the plane back (0 for NULL).
+ */
+#define VGSDF_FAMILY_ONE_KIND 0
+#define VGSDF_FAMILY_MIXED 1
+int vgsdf_family_create_at(vgsdf_ctx *ctx, const vgsdf_family_desc *in, int kind, uint32_t plane, vgsdf_family **out);
+int vgsdf_family_create_tables_at(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, int kind, uint32_t plane, vgsdf_family **out);
+uint32_t vgsdf_family_plane(const vgsdf_family *family);
+/*
+ * Which planes are worth a family: a CENSUS of the faces' cmap tables on the device, for the caller of
+ * vgsdf_family_create_tables_at, who has not parsed cmap.  bits is a bitmap over the 4352 blocks [256 b, 256 b + 255] up to
+ * 0x10FFFF, bit b at bits[b / 32] >> (b % 32).  Bit b is set exactly when some face's subtable of the description LISTS a code
+ * point c of the block that is no surrogate and at most 0x10FFFF, where a subtable lists
+ *   format 0: c < 256, when the table has its 262 bytes;   format 4: its segments [start, end], less a closing segment
+ *   0xFFFF - 0xFFFF;   formats 6 and 10: [first, first + count - 1];   formats 12 and 13: its groups.
+ * A span that ends past 0x10FFFF is cut there; a span that straddles the surrogates sets what lies on either side of them.  A
+ * listed code point may have no value, so the census is a SUPERSET of the blocks that map something: it promises only that a
+ * clear bit maps nothing (on the regular tables vg_manager_family_tables_desc describes).  One workgroup per subtable, its lanes
+ * over the segments / groups, each ORing its span into the bitmap with atomics, whole words where the span covers them
+ * (csrc/family_census_kernels.hip); every read is bounded by cmap_len.  The tables are validated as vgsdf_family_create_tables
+ * validates them (VGSDF_E_ARG, bits untouched, the context sound); the description's fonts are not looked at and may be NULL.
+ * vgsdf_family_census_kernel_ms: milliseconds the kernel of the context's last census took (HIP events; 0 before the first).
+ */
+#define VGSDF_CENSUS_WORDS 136u
+int vgsdf_family_tables_census(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, uint32_t bits[VGSDF_CENSUS_WORDS]);
+float vgsdf_family_census_kernel_ms(const vgsdf_ctx *ctx);
+/*
  * The same with faces AT A POSITION of their design space, whose advances follow `HVAR` (vg_manager_add_font_instance of
  * vgfont.h): var[k] beside tables[k] says where face k's HVAR is and what factor every region of its ItemVariationStore has at
  * the face's position (the host evaluates the regions, once; the device takes the factors as data, as the CFF2 decoder takes

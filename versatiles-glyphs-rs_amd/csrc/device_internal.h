@@ -74,6 +74,7 @@ struct vgsdf_ctx {
 	void *charstring_spill = nullptr;
 	size_t charstring_spill_bytes = 0;
 	float family_tables_ms[2] = {0.0f, 0.0f}; // count / emit kernels of the last vgsdf_family_create_tables (resident_families.cpp)
+	float family_census_ms = 0.0f;            // the kernel of the last vgsdf_family_tables_census (resident_families.cpp)
 	float glyf_tables_ms[2] = {0.0f, 0.0f};   // count / emit kernels of the last vgsdf_font_create_tables (resident_glyf_tables.cpp)
 	float glyf_batch_ms[2] = {0.0f, 0.0f};    // the same of the last vgsdf_fonts_create_tables: one launch each over all its faces
 	float gvar_ms[3] = {0.0f, 0.0f, 0.0f};    // count / deltas / emit kernels of the last vgsdf_font_create_gvar (resident_gvar.cpp)

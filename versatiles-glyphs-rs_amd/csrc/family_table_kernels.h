@@ -62,10 +62,12 @@ enum : uint32_t {
 
 extern "C" {
 // count pass: counts[4 w ..] = {entries, command slots mod 2^32, leaves mod 2^32, 0} of workgroup w's 256 code points; flags: one
-// zeroed word
-int vgsdf_family_tables_count(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts, uint32_t *flags, hipStream_t stream);
-// emit pass: the n_entries = sum of the counted entries, each at its rank, into `table` (FamilyTableLayout(n_entries))
-int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, const uint32_t *counts, uint32_t n_entries,
+// zeroed word.  plane (0 .. 16): the code points are (plane << 16) + 0 .. 0xFFFF; the passes below it, which take none, run plane 0
+int vgsdf_family_tables_count(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, uint32_t plane, uint32_t *counts, uint32_t *flags,
+                              hipStream_t stream);
+// emit pass: the n_entries = sum of the counted entries, each at its rank, into `table` (FamilyTableLayout(n_entries)); the table
+// keeps the code points' low halves, pbf_fix the length of the full value
+int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, uint32_t plane, const uint32_t *counts, uint32_t n_entries,
                              uint8_t *table, hipStream_t stream);
 // the emit pass over faces some of which are at a position: var[n_faces] beside faces
 int vgsdf_family_tables_emit_var(const vgsdf::FamilyFaceRef *faces, const vgsdf::FamilyFaceVar *var, uint32_t n_faces, const uint32_t *counts,

@@ -78,7 +78,7 @@ __device__ int32_t lookup(const Sub &d, uint32_t format, uint32_t c, bool &liste
 		return -1;
 	}
 	case 6: {
-		if (!has(d, 0, 10))
+		if (c > 0xFFFFu || !has(d, 0, 10)) // (a 16-bit format: nothing above the BMP, wherever first + count reaches)
 			return -1;
 		const uint32_t first = be16(d.p + 6), count = be16(d.p + 8);
 		if (c < first || c - first >= count || !has(d, 10 + (uint64_t)(c - first) * 2, 2))
@@ -112,7 +112,7 @@ __device__ int32_t lookup(const Sub &d, uint32_t format, uint32_t c, bool &liste
 			else {
 				uint64_t id = be32(g + 8);
 				if (format == 12)
-					id = id + c - start; // (c <= 0xFFFF: the sum stays below 2^33)
+					id = id + c - start; // (c <= 0x10FFFF: below 2^33; an id + c past 2^32 - 1, which the reader refuses, has id > 0xFFFF)
 				return id > 0xFFFFu ? -1 : (int32_t)id;
 			}
 		}
@@ -279,7 +279,7 @@ template <class A, class B> __device__ inline B second_of(A, B b) { return b; }
 // them keep the arguments (and with them the kernel descriptor and the name) they have always had
 template <bool EMIT, bool VAR = false, class... Var>
 __global__ __launch_bounds__(kFamilyThreads) void family_tables_pass(const FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts,
-                                                                       uint32_t *flags, uint32_t n_entries, uint8_t *table, Var... var)
+                                                                       uint32_t *flags, uint32_t n_entries, uint8_t *table, uint32_t plane, Var... var)
 {
 	const uint32_t group = blockIdx.x;
 #include "family_table_pass.inc"
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kFamilyThreads) void family_tables_batch_pass(const
                                                                              const FamilyBatchTable *tables, Var... var)
 {
 	const uint32_t group = blockIdx.x, position = blockIdx.y;
-	constexpr uint32_t n_faces = 1;
+	constexpr uint32_t n_faces = 1, plane = 0; // (the batched constructors build the BMP)
 	faces += position, counts += (size_t)kFamilyCounts * kFamilyGroups * position, flags += position;
 	((var += position), ...);
 	uint32_t n_entries = 0;
@@ -313,18 +313,18 @@ __global__ __launch_bounds__(kFamilyThreads) void family_tables_batch_pass(const
 
 extern "C" {
 
-int vgsdf_family_tables_count(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, uint32_t *counts, uint32_t *flags, hipStream_t stream)
+int vgsdf_family_tables_count(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, uint32_t plane, uint32_t *counts, uint32_t *flags, hipStream_t stream)
 {
 	hipLaunchKernelGGL(vgsdf::family_tables_pass<false>, dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces, n_faces,
-	                   counts, flags, 0u, (uint8_t *)nullptr);
+	                   counts, flags, 0u, (uint8_t *)nullptr, plane);
 	return (int)hipGetLastError();
 }
 
-int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, const uint32_t *counts, uint32_t n_entries,
+int vgsdf_family_tables_emit(const vgsdf::FamilyFaceRef *faces, uint32_t n_faces, uint32_t plane, const uint32_t *counts, uint32_t n_entries,
                              uint8_t *table, hipStream_t stream)
 {
 	hipLaunchKernelGGL(vgsdf::family_tables_pass<true>, dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces, n_faces,
-	                   const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table);
+	                   const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, plane);
 	return (int)hipGetLastError();
 }
 
@@ -332,7 +332,7 @@ int vgsdf_family_tables_emit_var(const vgsdf::FamilyFaceRef *faces, const vgsdf:
                                  uint32_t n_entries, uint8_t *table, hipStream_t stream)
 {
 	hipLaunchKernelGGL((vgsdf::family_tables_pass<true, true>), dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces,
-	                   n_faces, const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, var);
+	                   n_faces, const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, 0u, var);
 	return (int)hipGetLastError();
 }
 
@@ -340,7 +340,7 @@ int vgsdf_family_tables_emit_gvar(const vgsdf::FamilyFaceRef *faces, const vgsdf
                                   uint32_t n_faces, const uint32_t *counts, uint32_t n_entries, uint8_t *table, hipStream_t stream)
 {
 	hipLaunchKernelGGL((vgsdf::family_tables_pass<true, true>), dim3(vgsdf::kFamilyGroups), dim3(vgsdf::kFamilyThreads), 0, stream, faces,
-	                   n_faces, const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, var, gvar);
+	                   n_faces, const_cast<uint32_t *>(counts), (uint32_t *)nullptr, n_entries, table, 0u, var, gvar);
 	return (int)hipGetLastError();
 }
 

@@ -1,9 +1,10 @@
 // family_table_pass.inc — the text of the family table's passes for workgroup `group` (of kFamilyGroups) of ONE table, included
 // as the body of family_tables_pass and of family_tables_batch_pass (family_table_kernels.hip), which name: EMIT, VAR, Var...,
-// faces, n_faces, counts (this table's), flags (this table's word), n_entries, table, group and the pack var.
+// faces, n_faces, counts (this table's), flags (this table's word), n_entries, table, group, plane and the pack var.  The lanes
+// are the 65536 code points of `plane` (0 .. 16); the table keeps their low halves, pbf_fix counts the full value.
 	static_assert(VAR ? sizeof...(Var) == 1 || sizeof...(Var) == 2 : sizeof...(Var) == 0, "the variation records come with VAR and only with it");
 	__shared__ uint32_t lds_base[kFamilyThreads / 64][3], lds_wave[kFamilyThreads / 64][3];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = group * kFamilyThreads + tid;
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = (plane << 16) + group * kFamilyThreads + tid;
 	const Entry e = find_entry(faces, n_faces, c);
 	uint32_t slots = 0, leaves = 0;
 	if (e.found) {

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kExpandThreads) void FAMILY_KERNEL(const uint8_t *_
 					if (L.with_pbf) {
 						pre = k == 0 ? T.pbf_pre : 0u;
 						fix = (tb + at.pbf_fix)[e];
-						nm.id = reinterpret_cast<const uint16_t *>(tb + at.code_point)[e];
+						nm.id = F.cp_base + reinterpret_cast<const uint16_t *>(tb + at.code_point)[e];
 						nm.advance = reinterpret_cast<const uint32_t *>(tb + at.advance)[e];
 						nm.task_first = k == 0 ? t0 + lo + 1u : 0u;
 					}

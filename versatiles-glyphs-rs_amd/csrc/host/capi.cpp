@@ -225,6 +225,12 @@ int vg_manager_family_table_stats(const vg_manager *m, vg_family_table_stats *ou
 	*out = vg_family_table_stats{t.family_tables_built, t.family_table_fallbacks};
 	return 0;
 }
+int vg_manager_family_plane_stats(const vg_manager *m, vg_family_plane_stats *out)
+{
+	const vg::RenderTimings &t = m->m.last_timings();
+	*out = vg_family_plane_stats{t.family_census_calls, t.plane_families_built, t.plane_families_stated, t.plane_family_planes};
+	return 0;
+}
 void vg_manager_set_lane_form(vg_manager *m, int form) { m->m.set_lane_form(form < 0 || form > 2 ? -1 : form); }
 void vg_manager_set_threads(vg_manager *m, unsigned threads, unsigned blocks_per_batch)
 {
@@ -716,6 +722,32 @@ int vg_manager_block_counts(const vg_manager *m, const char *font_id, uint32_t c
 	return 0;
 }
 
+int vg_manager_set_supplementary_planes(vg_manager *m, int on)
+{
+	try {
+		m->m.set_supplementary_planes(on != 0);
+		return 0;
+	} catch (const std::exception &e) {
+		return fail(e.what());
+	}
+}
+int vg_manager_supplementary_blocks(const vg_manager *m, const char *font_id, uint32_t *starts, uint32_t *counts, int cap)
+{
+	auto it = m->m.fonts().find(font_id);
+	if (it == m->m.fonts().end())
+		return fail(std::string("unknown font id ") + font_id);
+	const std::vector<vg::GlyphBlock> &blocks = it->second.blocks();
+	int n = 0;
+	for (size_t i = vg::kBmpBlocks; i < blocks.size(); i++, n++)
+		if (n < cap) {
+			if (starts)
+				starts[n] = blocks[i].start_index;
+			if (counts)
+				counts[n] = (uint32_t)blocks[i].len();
+		}
+	return n;
+}
+
 int vg_manager_render_glyphs(vg_manager *m, vg_renderer *r, vg_write_cb cb, void *user)
 {
 	try {
@@ -752,10 +784,13 @@ long vg_manager_render_block(vg_manager *m, vg_renderer *r, const char *font_id,
 		auto it = m->m.fonts().find(font_id);
 		if (it == m->m.fonts().end())
 			return fail(std::string("unknown font id ") + font_id);
-		if (start % 256 || start > 0xFF00)
+		if (start % 256 || (start > 0xFF00 && !m->m.supplementary_planes()))
 			return fail("block start must be a multiple of 256 below 65536");
 		const auto blocks = it->second.get_blocks();
-		const std::vector<uint8_t> pbf = blocks[start / 256].render(font_id, *r->r);
+		const vg::GlyphBlock *block = vg::FontWrapper::find_block(blocks, start);
+		if (!block) // (a supplementary start the font id does not populate)
+			return fail("bad block start " + std::to_string(start));
+		const std::vector<uint8_t> pbf = block->render(font_id, *r->r);
 		if (out && pbf.size() <= cap)
 			std::memcpy(out, pbf.data(), pbf.size());
 		return (long)pbf.size();

@@ -168,17 +168,36 @@ bool FontWrapper::add_paths(const std::vector<std::string> &paths, std::string *
 
 std::vector<GlyphBlock> FontWrapper::get_blocks() const
 {
-	constexpr uint32_t kBmpBlocks = 0x10000 / GLYPH_BLOCK_SIZE; // wrapper.rs:55
 	std::vector<GlyphBlock> blocks(kBmpBlocks);
 	for (uint32_t i = 0; i < kBmpBlocks; i++)
 		blocks[i].start_index = i * GLYPH_BLOCK_SIZE;
+	std::map<uint32_t, GlyphBlock> above; // by start, populated ones only
 	for (const auto &file : files_)
 		for (uint32_t cp : file->codepoints()) {
-			if (cp > 0xFFFF) // wrapper.rs:66-68
+			if (cp > 0xFFFF) { // wrapper.rs:66-68, unless the supplementary planes are on
+				if (!supplementary_ || cp > 0x10FFFF)
+					continue;
+				GlyphBlock &b = above[cp / GLYPH_BLOCK_SIZE * GLYPH_BLOCK_SIZE];
+				b.start_index = cp / GLYPH_BLOCK_SIZE * GLYPH_BLOCK_SIZE;
+				b.set_glyph_font((uint8_t)(cp % GLYPH_BLOCK_SIZE), file.get());
 				continue;
+			}
 			blocks[cp / GLYPH_BLOCK_SIZE].set_glyph_font((uint8_t)(cp % GLYPH_BLOCK_SIZE), file.get());
 		}
+	for (auto &kv : above)
+		blocks.push_back(std::move(kv.second));
 	return blocks;
+}
+
+const GlyphBlock *FontWrapper::find_block(const std::vector<GlyphBlock> &blocks, uint32_t start)
+{
+	if (start % GLYPH_BLOCK_SIZE)
+		return nullptr;
+	if (start < 0x10000)
+		return start / GLYPH_BLOCK_SIZE < blocks.size() ? &blocks[start / GLYPH_BLOCK_SIZE] : nullptr;
+	const auto first = blocks.begin() + std::min<size_t>(kBmpBlocks, blocks.size());
+	const auto it = std::lower_bound(first, blocks.end(), start, [](const GlyphBlock &b, uint32_t s) { return b.start_index < s; });
+	return it != blocks.end() && it->start_index == start ? &*it : nullptr;
 }
 
 FontManager::~FontManager() = default;
@@ -204,10 +223,27 @@ void FontManager::invalidate_shards()
 	glyf_refused_.clear();
 }
 
+FontWrapper &FontManager::font_slot(const std::string &font_id)
+{
+	FontWrapper &w = fonts_[font_id];
+	w.set_supplementary(supplementary_planes_);
+	return w;
+}
+
+void FontManager::set_supplementary_planes(bool on)
+{
+	if (on == supplementary_planes_)
+		return;
+	supplementary_planes_ = on;
+	invalidate_shards(); // (the lane plan and the ranks' tables point into the block tables rebuilt below)
+	for (auto &kv : fonts_)
+		kv.second.set_supplementary(on);
+}
+
 bool FontManager::add_font_with_name(const std::string &name, const std::vector<std::string> &sources, std::string *err)
 {
 	invalidate_shards();
-	return fonts_[name_to_id(name)].add_paths(sources, err);
+	return font_slot(name_to_id(name)).add_paths(sources, err);
 }
 
 bool FontManager::add_font_data(const std::string &name, std::vector<uint8_t> data, std::string *err)
@@ -216,7 +252,7 @@ bool FontManager::add_font_data(const std::string &name, std::vector<uint8_t> da
 	if (!e)
 		return false;
 	invalidate_shards();
-	fonts_[name_to_id(name)].add_file(std::move(e));
+	font_slot(name_to_id(name)).add_file(std::move(e));
 	return true;
 }
 
@@ -228,7 +264,7 @@ bool FontManager::add_font_instance_normalized(const std::string &name, std::vec
 		return false;
 	gvar_advance_faces_ += e->face().advances_by_gvar();
 	invalidate_shards();
-	fonts_[name_to_id(name)].add_file(std::move(e));
+	font_slot(name_to_id(name)).add_file(std::move(e));
 	return true;
 }
 
@@ -306,7 +342,7 @@ bool FontManager::add_font_named_instances(std::vector<uint8_t> data, std::vecto
 		ids.push_back(name_to_id(e->metadata().generate_name()));
 		group.faces.push_back(&e->face()), group.ids.push_back(ids.back());
 		instance_bytes_of_[&e->face()] = bytes->data();
-		fonts_[ids.back()].add_file(std::move(e));
+		font_slot(ids.back()).add_file(std::move(e));
 	}
 	return true;
 }
@@ -381,7 +417,7 @@ bool FontManager::add_path(const std::string &path, std::string *err)
 	if (!e)
 		return false;
 	invalidate_shards();
-	fonts_[name_to_id(e->metadata().generate_name())].add_file(std::move(e));
+	font_slot(name_to_id(e->metadata().generate_name())).add_file(std::move(e));
 	return true;
 }
 
@@ -733,21 +769,22 @@ uint64_t next_family_serial()
 }
 } // namespace
 
-FontManager::FamilyTable *FontManager::family_shell(const std::string &font_id, size_t n_files) const
+FontManager::FamilyTable *FontManager::family_shell(const std::string &font_id, size_t n_files, uint32_t plane) const
 {
 	if (parent_)
-		return parent_->family_shell(font_id, n_files);
+		return parent_->family_shell(font_id, n_files, plane);
 	std::lock_guard<std::mutex> lock(family_mu_);
-	std::unique_ptr<FamilyTable> &slot = family_shells_[font_id];
+	std::unique_ptr<FamilyTable> &slot = family_shells_[FamilyKey(font_id, plane)];
 	if (!slot || slot->n_files != n_files) {
 		slot = std::make_unique<FamilyTable>();
 		slot->serial = next_family_serial();
 		slot->n_files = n_files;
+		slot->plane = plane;
 	}
 	return slot.get();
 }
 
-const FontManager::FamilyTable *FontManager::family_table(const std::string &font_id, std::string *err) const
+const FontManager::FamilyTable *FontManager::family_table(const std::string &font_id, std::string *err, uint32_t plane) const
 {
 	const FontEntry *it = find_font(font_id, err);
 	if (!it)
@@ -758,10 +795,10 @@ const FontManager::FamilyTable *FontManager::family_table(const std::string &fon
 		return nullptr;
 	}
 	if (parent_) // (a lane of a multi-device run: the table is the font id's, whatever share of its blocks the lane renders)
-		return parent_->family_table(font_id, err);
+		return parent_->family_table(font_id, err, plane);
 	const auto &files = it->second.files();
 	std::lock_guard<std::mutex> lock(family_mu_);
-	std::unique_ptr<FamilyTable> &slot = family_tables_[font_id];
+	std::unique_ptr<FamilyTable> &slot = family_tables_[FamilyKey(font_id, plane)];
 	if (slot && slot->n_files == files.size())
 		return slot.get();
 	std::map<const FontFileEntry *, uint16_t> file_of;
@@ -769,12 +806,13 @@ const FontManager::FamilyTable *FontManager::family_table(const std::string &fon
 		file_of.emplace(files[k].get(), (uint16_t)k);
 	ResidentBatch all;
 	for (const GlyphBlock &b : it->second.blocks()) // (the font id's own blocks, not a rank's share of them)
-		for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE && b.start_index + ci <= 0xFFFFu; ci++)
+		for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE && b.start_index >> 16 == plane; ci++)
 			if (const FontFileEntry *f = b.glyphs[ci])
 				Renderer::record_resident(f->face(), file_of.at(f), b.start_index + ci, all);
 	auto t = std::make_unique<FamilyTable>();
 	t->serial = next_family_serial();
 	t->n_files = files.size();
+	t->plane = plane;
 	for (const GlyphJob &j : all.jobs) {
 		t->code_point.push_back((uint16_t)j.id);
 		t->advance.push_back(j.advance);
@@ -875,6 +913,8 @@ void assign_lpt(GlyphShard &out)
 // estimated costs of the mapped glyphs of one block (cheap: table walks, no flattening), first provider wins
 void block_costs(const GlyphBlock &b, OutlineBatch &rec, std::vector<double> &cost)
 {
+	if (b.start_index >= cost.size()) // (a supplementary block: never split, no place in the tables of 65536 code points)
+		return;
 	for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE; ci++)
 		if (const FontFileEntry *f = b.glyphs[ci]) {
 			const uint32_t cp = b.start_index + ci;
@@ -954,12 +994,18 @@ const std::vector<GlyphBlock> &FontManager::task_blocks(const std::string &font_
 		return it->second; // (every add_* clears this table: invalidate_shards)
 	const GlyphShard &sh = cached_shard(font_id, font, shard_world_);
 	std::vector<GlyphBlock> blocks = font.blocks(); // copy, then drop what other ranks own
-	for (GlyphBlock &b : blocks)
+	for (size_t i = 0; i < blocks.size() && blocks[i].start_index < 0x10000; i++) {
+		GlyphBlock &b = blocks[i];
 		for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE; ci++)
 			if (b.glyphs[ci] && sh.owner[b.start_index + ci] != shard_rank_) {
 				b.glyphs[ci] = nullptr;
 				b.count--;
 			}
+	}
+	// a supplementary block is never split: it is one rank's whole, and the other ranks do not list it (no empty file)
+	blocks.erase(std::remove_if(blocks.begin(), blocks.end(),
+	                            [&](const GlyphBlock &b) { return b.start_index >= 0x10000 && b.start_index / GLYPH_BLOCK_SIZE % shard_world_ != shard_rank_; }),
+	             blocks.end());
 	return shard_blocks_[font_id] = std::move(blocks);
 }
 
@@ -1014,9 +1060,10 @@ void FontManager::render_blocks(Writer &writer, const Renderer &renderer, const 
 	const std::vector<GlyphBlock> &blocks = task_blocks(it->first, it->second);
 	std::vector<Todo> tasks;
 	for (uint32_t start : block_starts) {
-		if (start % GLYPH_BLOCK_SIZE || start / GLYPH_BLOCK_SIZE >= blocks.size())
+		if (!FontWrapper::find_block(it->second.blocks(), start)) // (a supplementary start that is not populated, or the switch off)
 			throw std::runtime_error("bad block start " + std::to_string(start));
-		tasks.push_back(Todo{&it->first, blocks[start / GLYPH_BLOCK_SIZE]});
+		if (const GlyphBlock *b = FontWrapper::find_block(blocks, start)) // (nullptr: a supplementary block of another rank)
+			tasks.push_back(Todo{&it->first, *b});
 	}
 	run_tasks(tasks, writer, renderer);
 }

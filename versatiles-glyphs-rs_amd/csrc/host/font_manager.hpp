@@ -121,7 +121,18 @@ public:
 	}
 	bool add_paths(const std::vector<std::string> &paths, std::string *err); // wrapper.rs:31-39
 	const std::vector<std::unique_ptr<FontFileEntry>> &files() const { return files_; }
-	std::vector<GlyphBlock> get_blocks() const; // wrapper.rs:53-76: always 256 blocks
+	// wrapper.rs:53-76: always the 256 blocks of the BMP, empty ones included; with set_supplementary(true) one block more per
+	// POPULATED range of 256 code points above U+FFFF, ascending behind them (empty ones are not listed: 4096 empty files per font
+	// serve nobody); first provider wins there as in the BMP
+	std::vector<GlyphBlock> get_blocks() const;
+	void set_supplementary(bool on)
+	{
+		if (supplementary_ != on)
+			blocks_valid_ = false;
+		supplementary_ = on;
+	}
+	// the block that starts at `start` in a table get_blocks (or a rank's share of it) made; nullptr: none
+	static const GlyphBlock *find_block(const std::vector<GlyphBlock> &blocks, uint32_t start);
 	// the same table, built once per set of files (0.5 MiB per font: rebuilding it for every
 	// render_glyphs call was 7 % of an end-to-end run); valid until the next add_file / add_paths
 	const std::vector<GlyphBlock> &blocks() const
@@ -137,7 +148,9 @@ private:
 	std::vector<std::unique_ptr<FontFileEntry>> files_;
 	mutable std::vector<GlyphBlock> blocks_;
 	mutable bool blocks_valid_ = false;
+	bool supplementary_ = false;
 };
+constexpr uint32_t kBmpBlocks = 0x10000 / GLYPH_BLOCK_SIZE; // wrapper.rs:55
 
 // Glyph-level shard of one font over `world` ranks: every mapped code point <= 0xFFFF has an
 // owner; costs are estimates of w*h*N (bitmap area x segment count) computed from the recorded outline
@@ -190,6 +203,11 @@ struct RenderTimings {
 	// with set_family_tables_batched: the calls that built the family tables of the instances of one file in one device build
 	// (one per group of faces over the same bytes and device lane) and the families they made (counted among family_tables_built too)
 	uint64_t family_batch_calls = 0, family_batch_families = 0;
+	// supplementary planes: census calls (one per font id whose supplementary family the device is to build), supplementary
+	// families the device built (vgsdf_family_create_tables_at; counted among family_tables_built too), those the host stated
+	// (vgsdf_family_create_at: a font id with a placed face, the switch off, a refusal), and the planes 1 .. 16 either kind was
+	// made for, bit p for plane p
+	uint64_t family_census_calls = 0, plane_families_built = 0, plane_families_stated = 0, plane_family_planes = 0;
 
 	// The timings of a device lane of a multi-lane run folded into the run's: the lanes work side by side, so a phase takes as
 	// long as the slowest lane's; counters add up.  (blocks, pbf_bytes, write_s and total_s are the run's own: it writes the files.)
@@ -226,10 +244,12 @@ struct RenderTimings {
 		charstring_batch_calls += counts.charstring_batch_calls, charstring_batch_faces += counts.charstring_batch_faces;
 		gvar_advance_builds += counts.gvar_advance_builds, gvar_advance_fallbacks += counts.gvar_advance_fallbacks;
 		family_batch_calls += counts.family_batch_calls, family_batch_families += counts.family_batch_families;
+		family_census_calls += counts.family_census_calls, plane_families_built += counts.plane_families_built;
+		plane_families_stated += counts.plane_families_stated, plane_family_planes |= counts.plane_family_planes;
 	}
 };
 // (a field added above belongs in one of the two folds, or in the comment of the first)
-static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 47 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
+static_assert(sizeof(RenderTimings) == 6 * sizeof(double) + 51 * sizeof(uint64_t), "RenderTimings has a field its folds do not know");
 
 class FontManager {
 public:
@@ -358,6 +378,15 @@ public:
 	// one per run of code points for a block the hybrid lane plan has split — and the device writes the PBF entries; recording
 	// is O(tasks).  With glyph sharding on (set_glyph_shard, lane form 0) groups go by glyph names as without the switch
 	void set_resident_families(bool on) { resident_families_ = on; }
+	// Supplementary planes (default off): every font id's block table lists, behind the 256 blocks of the BMP, one block per
+	// populated range of 256 code points above U+FFFF (FontWrapper::get_blocks), and render_glyphs / render_blocks write their
+	// files like any other.  A supplementary block is never split: under set_glyph_shard it belongs whole to rank
+	// (start / 256) % world, in a multi-device run to that lane.  The forms that name glyphs take such a block as any other; the
+	// ranges forms name the font id's family of the block's PLANE: built by the device for a static font id with
+	// set_family_tables_on_device (planes chosen by one census per font id), from family_table(font_id, err, plane) otherwise.
+	// With the switch off every byte stays what it is.
+	void set_supplementary_planes(bool on);
+	bool supplementary_planes() const { return supplementary_planes_; }
 	// Family tables on the device (default off): a resident family's table is built by the device from the faces' cmap and hmtx
 	// tables (Face::family_tables, vgsdf_family_create_tables) and family_table() below is not built for the font id; a font id
 	// whose description refuses, or whose build the device refuses, gets its family the host's way (remembered).  Same table bytes.
@@ -433,11 +462,16 @@ public:
 		// a table the DEVICE builds (family_shell): code_point and advance are the family's read-back, filled when the first
 		// device has built it, the other arrays stay empty; refused: the faces' description refuses, the host builds the table
 		bool filled = false, refused = false;
+		uint32_t plane = 0; // code_point holds the low halves of (plane << 16) | x
+		// the plane-0 shell of a font id also keeps its census (vgsdf_family_tables_census, one call per font id): bit p of
+		// census_planes says that some block of plane p is listed; census_done 2: the call failed, the block table alone decides
+		int census_done = 0;
+		uint32_t census_planes = 0;
 		std::vector<uint16_t> code_point, font_of, glyph_id;
 		std::vector<uint32_t> advance;
 		std::vector<double> scale, shift_x;
 	};
-	const FamilyTable *family_table(const std::string &font_id, std::string *err) const;
+	const FamilyTable *family_table(const std::string &font_id, std::string *err, uint32_t plane = 0) const;
 
 private:
 	using FontEntry = std::map<std::string, FontWrapper>::value_type;
@@ -446,11 +480,12 @@ private:
 	bool record_named(const std::string &font_id, ResidentBatch &out, bool commands, std::string *err) const;
 	template <class Table>
 	const Table *file_table(const std::string &font_id, size_t file_index, const Table &(Face::*table)() const, const char *why, std::string *err) const;
-	mutable std::map<std::string, std::unique_ptr<FamilyTable>> family_tables_; // per font id
-	mutable std::map<std::string, std::unique_ptr<FamilyTable>> family_shells_; // per font id: set_family_tables_on_device
+	using FamilyKey = std::pair<std::string, uint32_t>; // (font id, plane)
+	mutable std::map<FamilyKey, std::unique_ptr<FamilyTable>> family_tables_; // the host's tables
+	mutable std::map<FamilyKey, std::unique_ptr<FamilyTable>> family_shells_; // set_family_tables_on_device
 	// the font id's table as the device builds it: serial and n_files at once, the names once a device has built it (rebuilt, as
 	// family_table, when a file is added)
-	FamilyTable *family_shell(const std::string &font_id, size_t n_files) const;
+	FamilyTable *family_shell(const std::string &font_id, size_t n_files, uint32_t plane = 0) const;
 	mutable std::mutex family_mu_;
 	std::mutex &family_mu_of() const { return parent_ ? parent_->family_mu_ : family_mu_; }
 	struct Todo {
@@ -629,14 +664,15 @@ private:
 	// commands: against the faces' command stores (every readable face has one) instead of their glyf stores
 	// Mixed: per file the store it gets (file_store); false also when no file of the group gets a glyf store
 	bool fe_record_named(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, StoreKind kind);
-	// false: as above, or a family over the budget, or a block past code point 0xFFFF
+	// false: as above, or a family over the budget.  A supplementary block names the font id's family of ITS plane (device_family);
+	// its tasks carry the low halves
 	bool fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, const Renderer &renderer, int lane, StoreKind kind);
 	// the device family of a font id over its files' stores of one kind (nullptr: a file without such a store, or the budget), or
 	// (Mixed) over the store each file gets, a family of the mixed kind; *glyf_stores / *command_stores (may be NULL): += the stores of
 	// either kind among them
 	const vgsdf_family *device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font, StoreKind kind,
 	                                  const FamilyTable **table, RenderTimings &counts, uint32_t *glyf_stores = nullptr,
-	                                  uint32_t *command_stores = nullptr) const;
+	                                  uint32_t *command_stores = nullptr, uint32_t plane = 0) const;
 	// Mixed stores: the store a FILE gets — its glyf store where the face has `glyf` outlines, its font id has not been refused by
 	// the decoder and the store can be made (host table or device builder); a command store otherwise.  *glyf says which
 	const vgsdf_font *file_store(const Renderer &renderer, int lane, const std::string &font_id, const Face &face, RenderTimings &counts,
@@ -707,6 +743,8 @@ private:
 	// a face's command store on the renderer's device, by either path; counts into `counts`
 	const vgsdf_font *command_store(const Renderer &renderer, int lane, const Face &face, RenderTimings &counts) const;
 	bool resident_families_ = false;
+	bool supplementary_planes_ = false;
+	FontWrapper &font_slot(const std::string &font_id); // fonts_[font_id], made with the manager's supplementary switch
 	bool device_front_end_ = true; // HIP renderer: flatten on the GPU unless switched off
 	bool union_outlines_ = false;
 	uint64_t union_stats_[4] = {0, 0, 0, 0};

@@ -501,18 +501,22 @@ bool FontManager::may_mix(const std::vector<Todo> &tasks, size_t g0, size_t g1) 
 
 const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lane, const std::string &font_id, const FontWrapper &font,
                                                StoreKind kind, const FamilyTable **table, RenderTimings &counts, uint32_t *glyf_stores,
-                                               uint32_t *command_stores) const
+                                               uint32_t *command_stores, uint32_t plane) const
 {
 	const bool commands = kind == StoreKind::Commands;
 	const int family_kind = kind == StoreKind::Mixed ? Renderer::kFamilyMixed : commands ? Renderer::kFamilyCommands : Renderer::kFamilyGlyf;
-	const bool on_device = family_tables_on_device_ && font.files().size() <= 0x10000;
-	const FamilyTable *ft = on_device ? nullptr : family_table(font_id, nullptr);
+	// (a supplementary plane: the device builds a STATIC font id's family; a font id with a placed face takes the host's table,
+	// since the _var and _gvar constructors are plane 0)
+	bool on_device = family_tables_on_device_ && font.files().size() <= 0x10000;
+	for (const auto &file : font.files())
+		on_device = on_device && !(plane && file->face().at_position());
+	const FamilyTable *ft = on_device ? nullptr : family_table(font_id, nullptr, plane);
 	if (!ft && !on_device)
 		return nullptr;
 	std::vector<const vgsdf_font *> stores;
 	if (kind == StoreKind::Glyf || (kind == StoreKind::Mixed && !glyf_refused_.count(&font_id)))
 		glyf_stores_batched(renderer, lane, font, counts);
-	if (on_device)
+	if (on_device && plane == 0)
 		families_batched(renderer, lane, font, kind, counts); // (the lookup below then finds the family)
 	for (const auto &file : font.files()) {
 		bool glyf = kind == StoreKind::Glyf;
@@ -529,7 +533,7 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 	if (on_device) {
 		// the faces' descriptions (no code point is looked up) and the device's build; a refusal of either sends the font id the
 		// host's way below, for good
-		FamilyTable *shell = family_shell(font_id, font.files().size());
+		FamilyTable *shell = family_shell(font_id, font.files().size(), plane);
 		std::vector<vgsdf_face_tables> descs;
 		std::vector<vgsdf_face_variation> variation; // filled once a face at a position with an HVAR is met
 		// the faces whose advances follow gvar's phantom points (Face::advances_by_gvar): their tables beside `variation`
@@ -569,10 +573,25 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 				}
 			}
 		}
-		if (descs.size() == font.files().size()) {
+		// which planes are worth a device build: ONE census of the font id's tables, kept in its plane-0 shell.  (The block table
+		// has already said that the plane holds a block; a plane the census finds empty — it cannot, being a superset — and a census
+		// that failed leave the family to the host's table.)
+		bool listed = true;
+		if (plane && descs.size() == font.files().size()) {
+			FamilyTable *root = family_shell(font_id, font.files().size(), 0);
+			std::lock_guard<std::mutex> lock(family_mu_of());
+			if (!root->census_done) {
+				root->census_done = renderer.family_census(lane, descs, &root->census_planes) ? 1 : 2;
+				counts.family_census_calls++;
+			}
+			listed = root->census_done == 1 && ((root->census_planes >> plane) & 1u);
+		}
+		if (descs.size() == font.files().size() && listed) {
 			int refused = 0;
 			bool built = false;
-			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, family_kind, &uploaded, &refused, &built, variation, gvar);
+			const vgsdf_family *fam = renderer.family_from_tables(lane, shell->serial, descs, stores, family_kind, &uploaded, &refused, &built, variation, gvar, plane);
+			if (built && plane)
+				counts.plane_families_built++, counts.plane_family_planes |= 1ull << plane;
 			if (refused == 1) {
 				counts.family_table_fallbacks++;
 				counts.gvar_advance_fallbacks += !gvar_descs.empty();
@@ -596,14 +615,16 @@ const vgsdf_family *FontManager::device_family(const Renderer &renderer, int lan
 			}
 		}
 		uploaded = 0;
-		ft = family_table(font_id, nullptr);
+		ft = family_table(font_id, nullptr, plane);
 		if (!ft)
 			return nullptr;
 	}
-	const Renderer::FamilyArrays fa{ft->serial, &ft->code_point, &ft->font_of, &ft->glyph_id, &ft->advance, &ft->scale, &ft->shift_x};
+	const Renderer::FamilyArrays fa{ft->serial, &ft->code_point, &ft->font_of, &ft->glyph_id, &ft->advance, &ft->scale, &ft->shift_x, ft->plane};
 	const vgsdf_family *fam = renderer.family(lane, fa, stores, family_kind, &uploaded);
 	if (fam)
 		count_upload(uploaded, counts.families_uploaded, counts.family_bytes);
+	if (fam && uploaded && plane)
+		counts.plane_families_stated++, counts.plane_family_planes |= 1ull << plane;
 	if (table)
 		*table = ft;
 	return fam;
@@ -621,16 +642,17 @@ bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, c
 	std::vector<uint32_t> task_g0(nb + 1, 0);
 	const std::string *last = nullptr;
 	const FamilyTable *ft = nullptr;
-	uint32_t n_jobs = 0;
+	uint32_t n_jobs = 0, last_plane = 0;
 	for (size_t t = G.g0; t < G.g1; t++) {
-		if (tasks[t].name != last) {
+		const uint32_t plane = tasks[t].block.start_index >> 16; // (a family per font id AND plane)
+		if (tasks[t].name != last || plane != last_plane) {
 			auto it = fonts().find(*tasks[t].name);
 			if (it == fonts().end() || R.families.size() >= 0xFFFF)
 				return false;
-			const vgsdf_family *fam = device_family(renderer, lane, it->first, it->second, kind, &ft, timings_, &G.mixed_glyf_stores, &G.mixed_command_stores);
+			const vgsdf_family *fam = device_family(renderer, lane, it->first, it->second, kind, &ft, timings_, &G.mixed_glyf_stores, &G.mixed_command_stores, plane);
 			if (!fam)
 				return false;
-			last = tasks[t].name;
+			last = tasks[t].name, last_plane = plane;
 			R.families.push_back(fam);
 			R.tables.push_back(ft);
 		}
@@ -639,9 +661,7 @@ bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, c
 		R.task_r0.push_back((uint32_t)R.first.size());
 		if (blk.len() == 0)
 			continue;
-		if (blk.start_index + GLYPH_BLOCK_SIZE - 1 > 0xFFFFu)
-			return false;
-		const auto &cp = ft->code_point;
+		const auto &cp = ft->code_point; // (low halves, as the tasks' first and last)
 		auto add = [&](uint32_t a, uint32_t b, uint32_t room) { // code points [a, b] of the block
 			const auto lo = std::lower_bound(cp.begin(), cp.end(), (uint16_t)a), hi = std::upper_bound(cp.begin(), cp.end(), (uint16_t)b);
 			R.family_of.push_back((uint16_t)(R.families.size() - 1));
@@ -653,7 +673,7 @@ bool FontManager::fe_record_ranges(const std::vector<Todo> &tasks, FeGroup &G, c
 			return (uint32_t)(hi - lo);
 		};
 		const uint32_t room = (uint32_t)(kPbfHeadRoom + pbf_block_fields(tasks[t].name->size(), blk.range().size()));
-		const uint32_t s = blk.start_index;
+		const uint32_t s = blk.start_index & 0xFFFFu;
 		const auto lo = std::lower_bound(cp.begin(), cp.end(), (uint16_t)s), hi = std::upper_bound(cp.begin(), cp.end(), (uint16_t)(s + GLYPH_BLOCK_SIZE - 1));
 		if ((size_t)(hi - lo) == blk.len()) {
 			add(s, s + GLYPH_BLOCK_SIZE - 1, room);
@@ -1012,7 +1032,7 @@ void FontManager::fe_encode_write(const std::vector<Todo> &tasks, FeGroup &G, Wr
 		for (size_t r = 0; r < R.first.size(); r++) {
 			const FamilyTable &ft = *R.tables[R.family_of[r]];
 			for (uint32_t e = R.entry_first[r]; e < ft.code_point.size() && ft.code_point[e] <= R.last[r] && g < n_jobs; e++, g++) {
-				m.jobs[g].id = ft.code_point[e];
+				m.jobs[g].id = (ft.plane << 16) | ft.code_point[e];
 				m.jobs[g].advance = ft.advance[e];
 			}
 		}

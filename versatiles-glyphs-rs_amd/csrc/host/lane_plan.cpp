@@ -90,9 +90,11 @@ void FontManager::build_lane_plan(uint32_t world, int form)
 		uint32_t task, part, n_parts;
 		double w;
 	};
+	// (a supplementary block is no item: it is never split and goes whole to lane (start / 256) % world, below)
+	auto is_item = [&](size_t i) { return !plan.all[i].block.is_empty() && plan.all[i].block.start_index < 0x10000; };
 	std::vector<Item> items;
 	for (size_t i = 0; i < n_tasks; i++)
-		if (!plan.all[i].block.is_empty())
+		if (is_item(i))
 			items.push_back(Item{(uint32_t)i, 0, 1, weight[i]});
 	std::vector<uint32_t> item_lane;
 	std::vector<double> load;
@@ -132,7 +134,7 @@ void FontManager::build_lane_plan(uint32_t world, int form)
 			const size_t nb = font.blocks().size();
 			for (size_t bi = 0; bi < nb; bi++) {
 				const GlyphBlock &blk = plan.all[t0 + bi].block;
-				if (blk.is_empty())
+				if (!is_item(t0 + bi))
 					continue;
 				std::vector<double> &gc = glyph_cost[t0 + bi];
 				gc.assign(GLYPH_BLOCK_SIZE, 0.0);
@@ -158,7 +160,7 @@ void FontManager::build_lane_plan(uint32_t world, int form)
 		auto rebuild_items = [&]() {
 			items.clear();
 			for (size_t i = 0; i < n_tasks; i++) {
-				if (plan.all[i].block.is_empty())
+				if (!is_item(i))
 					continue;
 				const uint32_t n = task_parts[i];
 				if (n == 1) {
@@ -242,7 +244,7 @@ void FontManager::build_lane_plan(uint32_t world, int form)
 			plan.lane_tasks[r].push_back(plan.all[i]);
 			plan.lane_blocks[r]++;
 		} else if (split_of[i] < 0) {
-			const uint32_t r = lanes_of[i].at(0);
+			const uint32_t r = is_item(i) ? lanes_of[i].at(0) : plan.all[i].block.start_index / GLYPH_BLOCK_SIZE % world;
 			plan.owner[i] = r;
 			plan.slot[i] = (uint32_t)plan.lane_tasks[r].size();
 			plan.lane_tasks[r].push_back(plan.all[i]);
@@ -283,8 +285,8 @@ bool FontManager::plan_lanes(const std::string &font_id, uint32_t world, std::ve
 	owner.assign(0x10000, 0xFF);
 	n_split_blocks = 0;
 	for (size_t i = 0; i < plan.all.size(); i++) {
-		if (*plan.all[i].name != font_id || plan.all[i].block.is_empty())
-			continue;
+		if (*plan.all[i].name != font_id || plan.all[i].block.is_empty() || plan.all[i].block.start_index >= 0x10000)
+			continue; // (owner[65536] keeps its size and meaning: supplementary blocks are not in it)
 		const GlyphBlock &blk = plan.all[i].block;
 		if (plan.owner[i] != LanePlan::kSplit) {
 			for (uint32_t ci = 0; ci < GLYPH_BLOCK_SIZE; ci++)
@@ -447,15 +449,45 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 	std::vector<const std::string *> names;
 	for (const auto &kv : fonts_)
 		names.push_back(&kv.first);
-	const size_t n_files = names.size() * (0x10000 / GLYPH_BLOCK_SIZE);
-	for (const CaptureWriter &p : parts)
-		if (p.files.size() != n_files)
-			throw std::runtime_error("render_glyphs: a device lane produced " + std::to_string(p.files.size()) + " files instead of " + std::to_string(n_files));
+	// the files in the order a lane writes them, font after font: the 256 blocks of the BMP from every lane, then the font's
+	// supplementary blocks, each from the one lane that owns it whole (task_blocks)
+	struct Source {
+		const std::string *name;
+		uint32_t start, lane; // lane == world: every lane holds a part
+		std::vector<size_t> at; // the file's index in the lane's (or every lane's) capture
+	};
+	std::vector<Source> files;
+	std::vector<size_t> lane_at(world, 0);
+	for (const auto &kv : fonts_) {
+		const std::vector<GlyphBlock> &blocks = kv.second.blocks();
+		for (const GlyphBlock &b : blocks) {
+			Source s{&kv.first, b.start_index, world, {}};
+			if (b.start_index < 0x10000) {
+				s.at = lane_at;
+				for (size_t &a : lane_at)
+					a++;
+			} else {
+				s.lane = b.start_index / GLYPH_BLOCK_SIZE % world;
+				s.at.assign(1, lane_at[s.lane]++);
+			}
+			files.push_back(std::move(s));
+		}
+	}
+	const size_t n_files = files.size();
+	for (uint32_t r = 0; r < world; r++)
+		if (parts[r].files.size() != lane_at[r])
+			throw std::runtime_error("render_glyphs: a device lane produced " + std::to_string(parts[r].files.size()) + " files instead of " + std::to_string(lane_at[r]));
 	std::vector<std::vector<uint8_t>> merged(n_files);
 	tp.run(n_files, [&](size_t i, unsigned) {
+		const Source &s = files[i];
+		if (s.lane < world) {
+			const CaptureWriter &p = parts[s.lane];
+			merged[i].assign(p.data(s.at[0]), p.data(s.at[0]) + p.size(s.at[0]));
+			return;
+		}
 		std::vector<std::pair<const uint8_t *, size_t>> ps;
-		for (const CaptureWriter &p : parts)
-			ps.emplace_back(p.data(i), p.size(i));
+		for (uint32_t r = 0; r < world; r++)
+			ps.emplace_back(parts[r].data(s.at[r]), parts[r].size(s.at[r]));
 		merged[i] = merge_pbf_partials(ps);
 	});
 	const double t_merged = now_s();
@@ -463,9 +495,8 @@ void FontManager::render_glyphs_multi(Writer &writer, const Renderer &renderer)
 	for (const std::string *name : names)
 		writer.write_directory(*name + "/");
 	for (size_t i = 0; i < n_files; i++) {
-		const uint32_t start = (uint32_t)(i % (0x10000 / GLYPH_BLOCK_SIZE)) * GLYPH_BLOCK_SIZE;
-		writer.write_file(*names[i / (0x10000 / GLYPH_BLOCK_SIZE)] + "/" + std::to_string(start) + "-" + std::to_string(start + GLYPH_BLOCK_SIZE - 1) + ".pbf",
-		                  merged[i]);
+		const uint32_t start = files[i].start;
+		writer.write_file(*files[i].name + "/" + std::to_string(start) + "-" + std::to_string(start + GLYPH_BLOCK_SIZE - 1) + ".pbf", merged[i]);
 		timings_.pbf_bytes += merged[i].size();
 	}
 	const double t_written = now_s();

@@ -822,15 +822,19 @@ const vgsdf_family *Renderer::family(int lane, const FamilyArrays &t, const std:
 	d.advance = t.advance->data();
 	d.scale = t.scale->data();
 	d.shift_x = t.shift_x->data();
-	vgsdf_family *f = kind == kFamilyMixed ? create_resident(lane, vgsdf_family_create_mixed, d, "vgsdf_family_create_mixed")
-	                                       : create_resident(lane, vgsdf_family_create, d, "vgsdf_family_create");
+	// (plane 0 through vgsdf_family_create_at is the family vgsdf_family_create / _mixed makes)
+	static thread_local uint32_t at_plane;
+	at_plane = t.plane;
+	vgsdf_family *f = kind == kFamilyMixed
+	                      ? create_resident(lane, +[](vgsdf_ctx *c, const vgsdf_family_desc *in, vgsdf_family **out) { return vgsdf_family_create_at(c, in, VGSDF_FAMILY_MIXED, at_plane, out); }, d, "vgsdf_family_create_at")
+	                      : create_resident(lane, +[](vgsdf_ctx *c, const vgsdf_family_desc *in, vgsdf_family **out) { return vgsdf_family_create_at(c, in, VGSDF_FAMILY_ONE_KIND, at_plane, out); }, d, "vgsdf_family_create_at");
 	return rf.keep(rf.families, key, f, vgsdf_family_device_bytes(f), uploaded_bytes);
 }
 
 const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
                                                  const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
                                                  bool *built, const std::vector<vgsdf_face_variation> &variation,
-                                                 const std::vector<const vgsdf_font_gvar_desc *> &gvar) const
+                                                 const std::vector<const vgsdf_font_gvar_desc *> &gvar, uint32_t plane) const
 {
 	if (mode_ != Mode::Hip)
 		return nullptr;
@@ -839,6 +843,10 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 	const auto key = std::make_tuple(device_, serial, kind);
 	if (auto *found = rf.find(rf.families, key))
 		return found;
+	if (plane && (!variation.empty() || !gvar.empty())) { // (the caller's to keep: the _var and _gvar constructors are plane 0)
+		*refused = 1;
+		return nullptr;
+	}
 	if (rf.refused_family_tables.count(key)) {
 		*refused = 2;
 		return nullptr;
@@ -856,6 +864,7 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 		    (!gvar.empty() ? (kind == kFamilyMixed ? vgsdf_family_create_tables_gvar_mixed(c, &d, var, gvar.data(), &f)
 		                                          : vgsdf_family_create_tables_gvar(c, &d, var, gvar.data(), &f))
 		     : var ? (kind == kFamilyMixed ? vgsdf_family_create_tables_var_mixed(c, &d, var, &f) : vgsdf_family_create_tables_var(c, &d, var, &f))
+		     : plane ? vgsdf_family_create_tables_at(c, &d, kind == kFamilyMixed ? VGSDF_FAMILY_MIXED : VGSDF_FAMILY_ONE_KIND, plane, &f)
 		         : (kind == kFamilyMixed ? vgsdf_family_create_tables_mixed(c, &d, &f) : vgsdf_family_create_tables(c, &d, &f))) != VGSDF_OK) {
 			rf.refused_family_tables.insert(key);
 			*refused = 1;
@@ -870,6 +879,27 @@ const vgsdf_family *Renderer::family_from_tables(int lane, uint64_t serial, cons
 	}
 	*built = true;
 	return rf.keep(rf.families, key, f, vgsdf_family_device_bytes(f), uploaded_bytes);
+}
+
+bool Renderer::family_census(int lane, const std::vector<vgsdf_face_tables> &tables, uint32_t *planes) const
+{
+	if (mode_ != Mode::Hip || tables.empty())
+		return false;
+	vgsdf_family_tables_desc d;
+	d.n_fonts = (uint32_t)tables.size();
+	d.fonts = nullptr; // (the census does not look at fonts)
+	d.tables = tables.data();
+	uint32_t bits[VGSDF_CENSUS_WORDS];
+	{
+		std::lock_guard<std::mutex> lock(mu_);
+		if (vgsdf_family_tables_census(lane_ctx(lane & 1), &d, bits) != VGSDF_OK)
+			return false;
+	}
+	*planes = 0;
+	for (uint32_t w = 0; w < VGSDF_CENSUS_WORDS; w++) // 256 blocks, 8 words, to a plane
+		if (bits[w])
+			*planes |= 1u << (w / 8);
+	return true;
 }
 
 void Renderer::families_from_tables(int lane, const std::vector<FamilyJob> &jobs, int kind, std::vector<FamilyOutcome> &outcomes, uint64_t *calls,

@@ -535,6 +535,7 @@ public:
 		const std::vector<uint16_t> *code_point, *font_of, *glyph_id;
 		const std::vector<uint32_t> *advance;
 		const std::vector<double> *scale, *shift_x;
+		uint32_t plane = 0; // code_point: the low halves of (plane << 16) | x (every table has its own serial, whatever its plane)
 	};
 	// kind: kFamilyGlyf / kFamilyCommands — every font of `fonts` of that kind — or kFamilyMixed: fonts of either kind, the family
 	// made with the _mixed constructors (a third kind to the device, and a third key here)
@@ -550,7 +551,11 @@ public:
 	const vgsdf_family *family_from_tables(int lane, uint64_t serial, const std::vector<vgsdf_face_tables> &tables,
 	                                       const std::vector<const vgsdf_font *> &fonts, int kind, uint64_t *uploaded_bytes, int *refused,
 	                                       bool *built, const std::vector<vgsdf_face_variation> &variation = {},
-	                                       const std::vector<const vgsdf_font_gvar_desc *> &gvar = {}) const;
+	                                       const std::vector<const vgsdf_font_gvar_desc *> &gvar = {}, uint32_t plane = 0) const;
+	// (plane 1 .. 16: static faces only — variation and gvar empty — through vgsdf_family_create_tables_at)
+	// vgsdf_family_tables_census over a font id's faces: bit p of *planes set where some block of plane p is listed.  false: not a
+	// HIP renderer, or the call failed
+	bool family_census(int lane, const std::vector<vgsdf_face_tables> &tables, uint32_t *planes) const;
 	// family_from_tables for the families of ONE file's placed faces, a family of one face each (vgsdf_families_create_tables: the
 	// tables uploaded once, one phantom pass, one count and one emit pass over all positions), in as few calls as their number
 	// allows.  Shaped like gvar_fonts: under the registry's lock for the whole of it; a job is sent when its tables are ok and
@@ -635,7 +640,9 @@ private:
 	struct ResidentFonts { // of a renderer and its peers
 		std::mutex mu;
 		std::map<std::pair<int, uint64_t>, vgsdf_font *> fonts; // (device, the face's serial number) -> its copy there
-		std::map<std::tuple<int, uint64_t, int>, vgsdf_family *> families; // (device, table serial, kind of stores) -> the family
+		// (device, table serial, kind of stores) -> the family.  A font id's families of different PLANES are different tables, each
+		// with a serial of its own, so the serial stands for the plane as well
+		std::map<std::tuple<int, uint64_t, int>, vgsdf_family *> families;
 		std::map<int, uint64_t> bytes;                          // per device
 		std::set<std::tuple<int, uint64_t, int>> refused_family_tables; // the key of `families`: the device has refused to build the table
 		// What the registry remembers of the faces one kind of DEVICE-BUILT font was asked for and did not get, by (device, serial):

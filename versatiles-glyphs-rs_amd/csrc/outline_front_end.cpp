@@ -1304,6 +1304,7 @@ int vgsdf_outlines_submit_ranges(vgsdf_ctx *ctx, const vgsdf_outlines_ranges *in
 		r.n_entries = (uint32_t)fm.code_point.size();
 		r.font_base = font_base;
 		r.n_fonts = (uint32_t)fm.fonts.size();
+		r.cp_base = fm.plane << 16;
 		frefs[k] = r;
 		for (const vgsdf_font *ft : fm.fonts) { // (both references are 32 bytes)
 			if (mixed)

@@ -10,6 +10,7 @@
 #include <new>
 #include <vector>
 
+#include "family_census_kernels.h"
 #include "family_table_kernels.h"
 #include "resident_build.h"
 
@@ -35,8 +36,8 @@ void adopt_fonts(vgsdf_family &f, const vgsdf_ctx *ctx, const vgsdf_font *const 
 const char *const kFontsRefused[2] = {"a NULL font, a font of another device than the context's, or fonts of both kinds",
                                       "a NULL font, or a font of another device than the context's"};
 
-// vgsdf_family_create and vgsdf_family_create_mixed: `me` names the call in its messages
-int family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out, bool mixed, const char *me)
+// vgsdf_family_create, vgsdf_family_create_mixed and, with a plane, vgsdf_family_create_at: `me` names the call in its messages
+int family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **out, bool mixed, const char *me, uint32_t plane = 0)
 {
 	if (!ctx)
 		return VGSDF_E_ARG;
@@ -46,6 +47,10 @@ int family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **ou
 		return VGSDF_E_ARG;
 	}
 	*out = nullptr;
+	if (plane > 16) {
+		ctx->err = std::string(me) + ": plane must be 0 .. 16";
+		return VGSDF_E_ARG;
+	}
 	const uint32_t n = in->n_entries;
 	if (in->n_fonts == 0 || in->n_fonts > 0x10000u || n > 0x10000u) {
 		ctx->err = std::string(me) + ": n_fonts must be 1 .. 65536 and n_entries at most 65536";
@@ -68,6 +73,7 @@ int family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **ou
 		return VGSDF_E_OOM;
 	}
 	adopt_fonts(*f, ctx, in->fonts, in->n_fonts, mixed);
+	f->plane = plane;
 	f->code_point.assign(in->code_point, in->code_point + n);
 	f->font_of.assign(in->font_of, in->font_of + n);
 	f->glyph_id.assign(in->glyph_id, in->glyph_id + n);
@@ -83,7 +89,7 @@ int family_create(vgsdf_ctx *ctx, const vgsdf_family_desc *in, vgsdf_family **ou
 		const uint32_t id = f->glyph_id[i];
 		f->cmd_pre[i + 1] = f->cmd_pre[i] + ft.slots[id];
 		f->leaf_pre[i + 1] = f->leaf_pre[i] + (ft.commands ? 0u : ft.leaf_off[id + 1] - ft.leaf_off[id]);
-		f->pbf_fix[i] = (uint8_t)((1u + varint_len(f->code_point[i])) | ((1u + varint_len(f->advance[i])) << 4));
+		f->pbf_fix[i] = (uint8_t)((1u + varint_len((plane << 16) | f->code_point[i])) | ((1u + varint_len(f->advance[i])) << 4));
 		f->scales_plain = f->scales_plain && f->scale[i] > 0.0 && f->scale[i] < HUGE_VAL;
 	}
 	// the device's copy: one block in FamilyTableLayout, staged on the host and copied once
@@ -177,7 +183,7 @@ const char *face_tables_refused(const vgsdf_face_tables &t)
 // vgsdf_family_create_tables and vgsdf_family_create_tables_mixed (the kernels take the kind face by face: FamilyFaceRef::commands)
 // and their _var forms (var: NULL, or a record per face) and _gvar forms (gvar: NULL, or per face a description or NULL)
 int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out, bool mixed,
-                         const char *me, const vgsdf_font_gvar_desc *const *gvar = nullptr)
+                         const char *me, const vgsdf_font_gvar_desc *const *gvar = nullptr, uint32_t plane = 0)
 {
 	if (!ctx)
 		return VGSDF_E_ARG;
@@ -186,6 +192,10 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 		return VGSDF_E_ARG;
 	}
 	*out = nullptr;
+	if (plane > 16) {
+		ctx->err = std::string(me) + ": plane must be 0 .. 16";
+		return VGSDF_E_ARG;
+	}
 	ctx->family_tables_ms[0] = ctx->family_tables_ms[1] = 0.0f;
 	if (gvar)
 		ctx->gvar_advance_ms = 0.0f;
@@ -242,6 +252,7 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 		return VGSDF_E_OOM;
 	}
 	adopt_fonts(*f, ctx, in->fonts, n_fonts, mixed);
+	f->plane = plane; // (other than 0 only from vgsdf_family_create_tables_at: static faces, var and gvar NULL)
 	const size_t a_subs = sizeof(vgsdf::FamilyFaceRef) * (size_t)n_fonts, a_bytes = a_subs + sizeof(vgsdf::FamilySubtable) * n_subtables,
 	             a_var = align_up(a_bytes + table_bytes, 8), a_gvar = align_up(a_var + var_bytes, 8), a_counts = align_up(a_gvar + gvar_records, 16), a_flags = a_counts + 4 * (size_t)vgsdf::kFamilyCounts * vgsdf::kFamilyGroups,
 	             a_total = a_flags + 16;
@@ -333,7 +344,7 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 	q.copy(d, h.data(), h.size());
 	q.zero(d + a_flags, 16);
 	q.record(ev.at[0]);
-	q.launch([&] { return vgsdf_family_tables_count(faces, n_fonts, counts, flags, st); });
+	q.launch([&] { return vgsdf_family_tables_count(faces, n_fonts, plane, counts, flags, st); });
 	q.record(ev.at[1]);
 	uint32_t got[vgsdf::kFamilyCounts * vgsdf::kFamilyGroups + 1]; // the counts and, behind them, the flag word
 	q.read_back(got, counts, sizeof got);
@@ -359,7 +370,7 @@ int family_create_tables(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, con
 			return vgsdf_family_tables_emit_gvar(faces, (const vgsdf::FamilyFaceVar *)(d + a_var), (const vgsdf::FamilyFaceGvar *)(d + a_gvar), n_fonts,
 			                                     counts, n, (uint8_t *)f->table.p, st);
 		return any_var ? vgsdf_family_tables_emit_var(faces, (const vgsdf::FamilyFaceVar *)(d + a_var), n_fonts, counts, n, (uint8_t *)f->table.p, st)
-		               : vgsdf_family_tables_emit(faces, n_fonts, counts, n, (uint8_t *)f->table.p, st);
+		               : vgsdf_family_tables_emit(faces, n_fonts, plane, counts, n, (uint8_t *)f->table.p, st);
 	});
 	q.record(ev.at[2]);
 	q.read_back(back.data(), f->table.p, at.bytes);
@@ -598,6 +609,96 @@ int vgsdf_family_create_tables_mixed(vgsdf_ctx *ctx, const vgsdf_family_tables_d
 {
 	return family_create_tables(ctx, in, nullptr, out, true, "vgsdf_family_create_tables_mixed");
 }
+// the planes' entry points: `kind` chooses between the two constructors of each pair
+int vgsdf_family_create_at(vgsdf_ctx *ctx, const vgsdf_family_desc *in, int kind, uint32_t plane, vgsdf_family **out)
+{
+	if (ctx && kind != VGSDF_FAMILY_ONE_KIND && kind != VGSDF_FAMILY_MIXED) {
+		ctx->err = "vgsdf_family_create_at: kind must be VGSDF_FAMILY_ONE_KIND or VGSDF_FAMILY_MIXED";
+		return VGSDF_E_ARG;
+	}
+	return family_create(ctx, in, out, kind == VGSDF_FAMILY_MIXED, "vgsdf_family_create_at", plane);
+}
+int vgsdf_family_create_tables_at(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, int kind, uint32_t plane, vgsdf_family **out)
+{
+	if (ctx && kind != VGSDF_FAMILY_ONE_KIND && kind != VGSDF_FAMILY_MIXED) {
+		ctx->err = "vgsdf_family_create_tables_at: kind must be VGSDF_FAMILY_ONE_KIND or VGSDF_FAMILY_MIXED";
+		return VGSDF_E_ARG;
+	}
+	return family_create_tables(ctx, in, nullptr, out, kind == VGSDF_FAMILY_MIXED, "vgsdf_family_create_tables_at", nullptr, plane);
+}
+uint32_t vgsdf_family_plane(const vgsdf_family *family) { return family ? family->plane : 0; }
+
+// the census of the faces' cmap tables (family_census_kernels.hip): the tables go up, one workgroup per subtable ORs what it lists
+// into 136 zeroed words, the words come back; one synchronisation.  The fonts of the description are not looked at
+int vgsdf_family_tables_census(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, uint32_t bits[VGSDF_CENSUS_WORDS])
+{
+	const char *me = "vgsdf_family_tables_census";
+	if (!ctx)
+		return VGSDF_E_ARG;
+	if (!in || !bits || !in->tables) {
+		ctx->err = std::string(me) + ": NULL argument";
+		return VGSDF_E_ARG;
+	}
+	if (in->n_fonts == 0 || in->n_fonts > 0x10000u) {
+		ctx->err = std::string(me) + ": n_fonts must be 1 .. 65536";
+		return VGSDF_E_ARG;
+	}
+	size_t n_subtables = 0, table_bytes = 0;
+	for (uint32_t k = 0; k < in->n_fonts; k++) {
+		if (const char *why = face_tables_refused(in->tables[k])) {
+			ctx->err = std::string(me) + ": " + why;
+			return VGSDF_E_ARG;
+		}
+		n_subtables += in->tables[k].n_subtables;
+		table_bytes += align_up(in->tables[k].cmap_len, 4);
+	}
+	if (n_subtables > 0x7FFFFFFFu) {
+		ctx->err = std::string(me) + ": more than 2^31 - 1 subtables over the faces";
+		return VGSDF_E_ARG;
+	}
+	ctx->family_census_ms = 0.0f;
+	// the staging block: CensusSubtable[all] | per face cmap (4-aligned) | then, 16-aligned: the bitmap
+	const size_t a_bytes = sizeof(vgsdf::CensusSubtable) * n_subtables, a_bits = align_up(a_bytes + table_bytes, 16),
+	             a_total = a_bits + 4 * (size_t)vgsdf::kCensusWords;
+	static_assert(VGSDF_CENSUS_WORDS == vgsdf::kCensusWords, "the bitmap of the header is the kernel's");
+	(void)hipSetDevice(ctx->device);
+	hipStream_t st = ctx->stream;
+	ScratchBuf dev;
+	if (hipError_t e = dev.ensure(a_total + 16); e != hipSuccess)
+		return font_hip_error(ctx, me, "hipMalloc", e);
+	uint8_t *d = (uint8_t *)dev.p;
+	std::vector<uint8_t> h(a_bits, 0);
+	{
+		vgsdf::CensusSubtable *subs = (vgsdf::CensusSubtable *)h.data();
+		size_t at_sub = 0, at_byte = a_bytes;
+		for (uint32_t k = 0; k < in->n_fonts; k++) {
+			const vgsdf_face_tables &t = in->tables[k];
+			for (uint32_t s = 0; s < t.n_subtables; s++) // (subtable_off < cmap_len: face_tables_refused)
+				subs[at_sub++] = vgsdf::CensusSubtable{(uint64_t)(uintptr_t)(d + at_byte + t.subtable_off[s]), t.cmap_len - t.subtable_off[s], t.subtable_format[s]};
+			if (t.cmap_len)
+				std::memcpy(h.data() + at_byte, t.cmap, t.cmap_len);
+			at_byte += align_up(t.cmap_len, 4);
+		}
+	}
+	PassEvents ev;
+	if (hipError_t err = ev.create(); err != hipSuccess)
+		return font_hip_error(ctx, me, "hipEventCreate", err);
+	uint32_t got[vgsdf::kCensusWords];
+	Calls q(st);
+	q.copy(d, h.data(), h.size());
+	q.zero(d + a_bits, 4 * (size_t)vgsdf::kCensusWords);
+	q.record(ev.at[0]);
+	q.launch([&] { return vgsdf_family_census_launch((const vgsdf::CensusSubtable *)d, (uint32_t)n_subtables, (uint32_t *)(d + a_bits), st); });
+	q.record(ev.at[1]);
+	q.read_back(got, d + a_bits, sizeof got);
+	q.sync();
+	if (q.failed())
+		return font_hip_error(ctx, me, "census", q.e);
+	(void)hipEventElapsedTime(&ctx->family_census_ms, ev.at[0], ev.at[1]);
+	std::memcpy(bits, got, sizeof got);
+	return VGSDF_OK;
+}
+float vgsdf_family_census_kernel_ms(const vgsdf_ctx *ctx) { return ctx ? ctx->family_census_ms : 0.0f; }
 int vgsdf_family_create_tables_var(vgsdf_ctx *ctx, const vgsdf_family_tables_desc *in, const vgsdf_face_variation *var, vgsdf_family **out)
 {
 	return family_create_tables(ctx, in, var, out, false, "vgsdf_family_create_tables_var");

@@ -42,6 +42,7 @@ struct vgsdf_family {
 	bool commands = false;    // the kind of its fonts
 	bool mixed = false;       // a third kind (vgsdf_family_create_mixed): fonts of either kind, font by font; `commands` stays false
 	bool scales_plain = true; // every scale positive and finite
+	uint32_t plane = 0;       // 0 .. 16: code_point holds the low halves of (plane << 16) | x (vgsdf_family_create_at)
 	uint32_t max_cap = 0, max_len = 0; // over its fonts (vgsdf_font); a mixed family: over its glyf fonts
 	std::vector<const vgsdf_font *> fonts;
 	std::vector<uint16_t> code_point, font_of, glyph_id;

@@ -181,7 +181,8 @@ struct FamilyRef {
 	uint32_t n_entries; // (what FamilyTableLayout is made from)
 	uint32_t font_base; // where the family's fonts begin in the block's font list
 	uint32_t n_fonts;
-	uint32_t reserved[3];
+	uint32_t cp_base; // the family's plane << 16: an entry's id is cp_base + its code_point
+	uint32_t reserved[2];
 };
 static_assert(sizeof(RangeTask) == 32 && sizeof(FamilyRef) == 32, "one record size throughout the block");
 struct RangesBlockLayout {

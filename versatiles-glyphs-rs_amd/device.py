@@ -148,6 +148,7 @@ VGSDF_SYMBOLS = [
     "vgsdf_gvar_advance_deltas", "vgsdf_gvar_advance_kernel_ms", "vgsdf_family_create_tables_gvar", "vgsdf_family_create_tables_gvar_mixed",
     "vgsdf_families_create_tables", "vgsdf_families_create_tables_mixed", "vgsdf_gvar_advance_deltas_batch", "vgsdf_families_tables_kernel_ms",
     "vgsdf_batch_union", "vgsdf_batch_segments_read", "vgsdf_outlines_union", "vgsdf_union_kernel_ms",
+    "vgsdf_family_create_at", "vgsdf_family_create_tables_at", "vgsdf_family_plane", "vgsdf_family_tables_census", "vgsdf_family_census_kernel_ms",
 ]
 
 _lib = None
@@ -239,6 +240,13 @@ def load_library():
         L.vgsdf_family_create.argtypes = [vp, C.POINTER(_CFamilyDesc), C.POINTER(vp)]
         L.vgsdf_family_create_mixed.argtypes = [vp, C.POINTER(_CFamilyDesc), C.POINTER(vp)]
         L.vgsdf_family_create_tables_mixed.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), C.POINTER(vp)]
+        L.vgsdf_family_create_at.argtypes = [vp, C.POINTER(_CFamilyDesc), C.c_int, C.c_uint32, C.POINTER(vp)]
+        L.vgsdf_family_create_tables_at.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), C.c_int, C.c_uint32, C.POINTER(vp)]
+        L.vgsdf_family_plane.argtypes = [vp]
+        L.vgsdf_family_tables_census.argtypes = [vp, C.POINTER(_CFamilyTablesDesc), vp]
+        L.vgsdf_family_census_kernel_ms.argtypes = [vp]
+        L.vgsdf_family_census_kernel_ms.restype = C.c_float
+        L.vgsdf_family_plane.restype = C.c_uint32
         L.vgsdf_family_free.argtypes = [vp, vp]
         L.vgsdf_family_device_bytes.argtypes = [vp]
         L.vgsdf_family_device_bytes.restype = C.c_uint64
@@ -443,8 +451,13 @@ class ResidentFamily:
     def device_bytes(self) -> int:
         return int(load_library().vgsdf_family_device_bytes(self._h)) if self._h else 0
 
+    @property
+    def plane(self) -> int:
+        """vgsdf_family_plane: the plane whose low halves the family's code points are"""
+        return int(load_library().vgsdf_family_plane(self._h)) if self._h else 0
+
     def count(self, first: int, last: int) -> int:
-        """mapped code points in [first, last]"""
+        """mapped code points in [first, last] (low halves, whatever the plane)"""
         return int(load_library().vgsdf_family_count(self._h, first, last))
 
     def free(self):
@@ -970,8 +983,18 @@ class SdfContext:
         """vgsdf_family_create_tables_mixed: family_create_tables over `fonts` of either kind -> a mixed family"""
         return self.family_create_tables(fonts, faces, entry="vgsdf_family_create_tables_mixed")
 
-    def family_create(self, fonts, code_point, font_of, glyph_id, advance, scale, shift_x, entry="vgsdf_family_create") -> ResidentFamily:
-        """vgsdf_family_create: the entries of a font id over `fonts` (ResidentFont, one kind), code points strictly ascending"""
+    def family_create_at(self, fonts, code_point, font_of, glyph_id, advance, scale, shift_x, plane, mixed=False) -> ResidentFamily:
+        """vgsdf_family_create_at: family_create (mixed: family_create_mixed) for the code points (plane << 16) | code_point"""
+        return self.family_create(fonts, code_point, font_of, glyph_id, advance, scale, shift_x, entry="vgsdf_family_create_at",
+                                  at=(int(mixed), int(plane)))
+
+    def family_create_tables_at(self, fonts, faces, plane, mixed=False) -> ResidentFamily:
+        """vgsdf_family_create_tables_at: family_create_tables (mixed: its _mixed twin) over the code points of `plane`"""
+        return self.family_create_tables(fonts, faces, entry="vgsdf_family_create_tables_at", at=(int(mixed), int(plane)))
+
+    def family_create(self, fonts, code_point, font_of, glyph_id, advance, scale, shift_x, entry="vgsdf_family_create", at=()) -> ResidentFamily:
+        """vgsdf_family_create: the entries of a font id over `fonts` (ResidentFont, one kind), code points strictly ascending;
+        at: (kind, plane) of the _at entry point"""
         a = [np.ascontiguousarray(code_point, dtype=np.uint16), np.ascontiguousarray(font_of, dtype=np.uint16),
              np.ascontiguousarray(glyph_id, dtype=np.uint16), np.ascontiguousarray(advance, dtype=np.uint32),
              np.ascontiguousarray(scale, dtype=np.float64), np.ascontiguousarray(shift_x, dtype=np.float64)]
@@ -979,7 +1002,7 @@ class SdfContext:
         handles = (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts])
         d = _CFamilyDesc(len(fonts), C.cast(handles, C.c_void_p), len(a[0]), *[x.ctypes.data for x in a])
         h = C.c_void_p()
-        self._check(getattr(load_library(), entry)(self._h, C.byref(d), C.byref(h)))
+        self._check(getattr(load_library(), entry)(self._h, C.byref(d), *at, C.byref(h)))
         return ResidentFamily(self, h, fonts)
 
     def family_create_tables_var(self, fonts, faces, variation, mixed=False) -> ResidentFamily:
@@ -997,13 +1020,11 @@ class SdfContext:
                                          variation=[None] * len(fonts) if variation is None else variation, no_records=variation is None,
                                          gvar=[None] * len(fonts) if gvar is None else gvar, no_gvar=gvar is None, gvar_override=override)
 
-    def family_create_tables(self, fonts, faces, entry="vgsdf_family_create_tables", variation=None, no_records=False, gvar=None,
-                             no_gvar=False, gvar_override=None) -> ResidentFamily:
-        """vgsdf_family_create_tables: the family of `fonts` (ResidentFont, one kind, provider order) built on the device from
-        `faces`, one dict per font as FontManager.family_tables_desc returns it: {cmap, hmtx (bytes or uint8 arrays),
-        units_per_em, num_glyphs, num_hmetrics, subtable_off, subtable_format}"""
-        assert len(fonts) == len(faces)
-        keep, recs = [], (_CFaceTables * max(len(faces), 1))()
+    @staticmethod
+    def _face_table_records(faces, keep: list):
+        """vgsdf_face_tables[len(faces)] of dicts as FontManager.family_tables_desc returns them; the arrays they point to are
+        appended to keep"""
+        recs = (_CFaceTables * max(len(faces), 1))()
         for r, t in zip(recs, faces):
             cmap, hmtx = np.frombuffer(bytes(t["cmap"]), dtype=np.uint8), np.frombuffer(bytes(t["hmtx"]), dtype=np.uint8)
             off = np.ascontiguousarray(t["subtable_off"], dtype=np.uint32)
@@ -1015,11 +1036,34 @@ class SdfContext:
             r.units_per_em, r.num_glyphs, r.num_hmetrics = int(t["units_per_em"]), int(t["num_glyphs"]), int(t["num_hmetrics"])
             r.n_subtables = len(off)
             r.subtable_off, r.subtable_format = (off.ctypes.data if len(off) else None), (fmt.ctypes.data if len(fmt) else None)
+        return recs
+
+    def family_tables_census(self, faces) -> np.ndarray:
+        """vgsdf_family_tables_census: uint32[136], bit b set where some face's unicode subtable lists a code point of block b
+        (256 b .. 256 b + 255) that is no surrogate; faces: dicts as family_create_tables takes them (no fonts are needed)"""
+        keep = []
+        recs = self._face_table_records(faces, keep)
+        d = _CFamilyTablesDesc(len(faces), None, C.cast(recs, C.c_void_p))
+        bits = np.full(136, 0xEEEEEEEE, np.uint32)
+        self._check(load_library().vgsdf_family_tables_census(self._h, C.byref(d), bits.ctypes.data))
+        return bits
+
+    def family_census_kernel_ms(self) -> float:
+        return float(load_library().vgsdf_family_census_kernel_ms(self._h))
+
+    def family_create_tables(self, fonts, faces, entry="vgsdf_family_create_tables", variation=None, no_records=False, gvar=None,
+                             no_gvar=False, gvar_override=None, at=()) -> ResidentFamily:
+        """vgsdf_family_create_tables: the family of `fonts` (ResidentFont, one kind, provider order) built on the device from
+        `faces`, one dict per font as FontManager.family_tables_desc returns it: {cmap, hmtx (bytes or uint8 arrays),
+        units_per_em, num_glyphs, num_hmetrics, subtable_off, subtable_format}"""
+        assert len(fonts) == len(faces)
+        keep = []
+        recs = self._face_table_records(faces, keep)
         handles = (C.c_void_p * max(len(fonts), 1))(*[f._h for f in fonts])
         d = _CFamilyTablesDesc(len(fonts), C.cast(handles, C.c_void_p), C.cast(recs, C.c_void_p))
         h = C.c_void_p()
         if variation is None:
-            self._check(getattr(load_library(), entry)(self._h, C.byref(d), C.byref(h)))
+            self._check(getattr(load_library(), entry)(self._h, C.byref(d), *at, C.byref(h)))  # (at: kind and plane of the _at entry point)
             return ResidentFamily(self, h, fonts)
         assert len(variation) == len(fonts)
         vrecs = (_CFaceVariation * max(len(fonts), 1))()

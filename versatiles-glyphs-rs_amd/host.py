@@ -67,6 +67,10 @@ class FamilyTableStats(C.Structure):  # vg_family_table_stats
     _fields_ = [(k, C.c_uint64) for k in ("built_on_device", "fallbacks")]
 
 
+class FamilyPlaneStats(C.Structure):  # vg_family_plane_stats
+    _fields_ = [(k, C.c_uint64) for k in ("census_calls", "built_on_device", "stated_by_host", "planes")]
+
+
 class GlyfTableStats(C.Structure):  # vg_glyf_table_stats
     _fields_ = [(k, C.c_uint64) for k in ("built_on_device", "bytes", "fallbacks")]
 
@@ -96,6 +100,7 @@ WRITE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint8), C.
 VGFONT_SYMBOLS = [
     "vg_last_error", "vg_renderer_new", "vg_renderer_free", "vg_manager_new", "vg_manager_free",
     "vg_manager_set_threads", "vg_manager_set_device_front_end", "vg_manager_set_union_outlines", "vg_manager_union_stats", "vg_manager_add_font_with_name", "vg_manager_add_font_data", "vg_manager_add_path",
+    "vg_manager_set_supplementary_planes", "vg_manager_supplementary_blocks", "vg_manager_family_plane_stats",
     "vg_name_to_id", "vg_manager_block_counts", "vg_manager_render_glyphs", "vg_manager_timings",
     "vg_manager_render_block", "vg_manager_render_blocks", "vg_render_glyph", "vg_manager_build_batch", "vg_glyph_batch_view",
     "vg_glyph_batch_free", "vg_manager_record_outlines", "vg_outline_batch_view", "vg_outline_batch_free", "vg_pbf_encode", "vg_manager_family_desc",
@@ -179,6 +184,7 @@ def _L():
         L.vg_manager_set_family_tables_on_device.argtypes = [vp, C.c_int]
         L.vg_manager_set_family_tables_on_device.restype = None
         L.vg_manager_family_table_stats.argtypes = [vp, C.POINTER(FamilyTableStats)]
+        L.vg_manager_family_plane_stats.argtypes = [vp, C.POINTER(FamilyPlaneStats)]
         L.vg_manager_set_glyf_tables_on_device.argtypes = [vp, C.c_int]
         L.vg_manager_set_glyf_tables_on_device.restype = None
         L.vg_manager_set_gvar_on_device.argtypes = [vp, C.c_int]
@@ -221,6 +227,8 @@ def _L():
         L.vg_manager_gvar_advance_stats.argtypes = [vp, C.POINTER(GvarAdvanceStats)]
         L.vg_name_to_id.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
         L.vg_manager_block_counts.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint32)]
+        L.vg_manager_set_supplementary_planes.argtypes = [vp, C.c_int]
+        L.vg_manager_supplementary_blocks.argtypes = [vp, C.c_char_p, vp, vp, C.c_int]
         L.vg_manager_render_glyphs.argtypes = [vp, vp, WRITE_CB, vp]
         L.vg_manager_render_blocks.argtypes = [vp, vp, C.c_char_p, C.POINTER(C.c_uint32), C.c_int, WRITE_CB, vp]
         L.vg_manager_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -562,6 +570,12 @@ class FontManager:
         _L().vg_manager_glyf_table_batch_stats(self._h, C.byref(s))
         return {k: int(getattr(s, k)) for k, _ in GlyfTableBatchStats._fields_}
 
+    def family_plane_stats(self) -> dict:
+        """of the last render: {census_calls, built_on_device, stated_by_host, planes} (vg_family_plane_stats)"""
+        s = FamilyPlaneStats()
+        _L().vg_manager_family_plane_stats(self._h, C.byref(s))
+        return {k: int(getattr(s, k)) for k, _ in FamilyPlaneStats._fields_}
+
     def family_table_stats(self) -> dict:
         """of the last render: {built_on_device, fallbacks} (vg_family_table_stats)"""
         s = FamilyTableStats()
@@ -794,6 +808,21 @@ class FontManager:
         if _L().vg_manager_block_counts(self._h, font_id.encode(), out.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
             raise KeyError(_err())
         return out
+
+    def set_supplementary_planes(self, on: bool):
+        """code points above U+FFFF (default off): one more block per populated range of 256 of them behind the 256 of the BMP"""
+        if _L().vg_manager_set_supplementary_planes(self._h, int(bool(on))) != 0:
+            raise RuntimeError(_err())
+
+    def supplementary_blocks(self, font_id: str) -> dict:
+        """{start: mapped code points} of the font id's supplementary blocks, ascending (empty with the switch off)"""
+        n = _L().vg_manager_supplementary_blocks(self._h, font_id.encode(), None, None, 0)
+        if n < 0:
+            raise KeyError(_err())
+        starts, counts = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        if _L().vg_manager_supplementary_blocks(self._h, font_id.encode(), starts.ctypes.data, counts.ctypes.data, n) != n:
+            raise RuntimeError(_err())
+        return {int(s): int(c) for s, c in zip(starts[:n], counts[:n])}
 
     def render_glyphs(self, writer, renderer: Renderer, font_id: str = None, block_starts=None):
         """FontManager::render_glyphs(&mut writer, &renderer).  `writer` needs
