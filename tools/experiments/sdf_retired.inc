@@ -58,8 +58,7 @@ __device__ __forceinline__ uint32_t umed3(uint32_t a, uint32_t b, uint32_t c)
 // ABL: timing-only ablation mask (0 in production; non-zero variants give WRONG pixels):
 // 1 no winding pass, 2 no filter loop, 4 no exact evaluation, 16 no prefix loop
 template <int ABL, bool CULL>
-__global__ __launch_bounds__(TPB) void sdf_tiles_filtered(const GlyphDesc *__restrict__ glyphs,
-                                                          const uint2 *__restrict__ tiles,
+__global__ __launch_bounds__(TPB) void sdf_tiles_filtered(const SpanRec *__restrict__ tiles,
                                                           uint32_t n_tiles,
                                                           const double *__restrict__ seg_sx,
                                                           const double *__restrict__ seg_sy,
@@ -76,8 +75,8 @@ __global__ __launch_bounds__(TPB) void sdf_tiles_filtered(const GlyphDesc *__res
 
 	const uint32_t tid = threadIdx.x;
 	const uint32_t tile = xcd_remap(blockIdx.x, n_tiles);
-	const uint2 t = tiles[tile];
-	const GlyphDesc g = glyphs[t.x];
+	const SpanRec g = tiles[tile]; // (the glyph's descriptor travels in the entry)
+	const uint2 t = make_uint2(g.glyph, g.first);
 	const uint32_t npix = g.w * g.h;
 	const uint32_t o = t.y + tid;
 	const bool active = o < npix;
@@ -338,8 +337,7 @@ __device__ __forceinline__ f2 pk_filter(f2 rpx, f2 rpy, f2 vx, f2 vy, f2 dx, f2 
 }
 
 template <int ABL, bool CULL, int PPL>
-__global__ __launch_bounds__(TPB / PPL) void sdf_tiles_pk(const GlyphDesc *__restrict__ glyphs,
-                                                          const uint2 *__restrict__ tiles, uint32_t n_tiles,
+__global__ __launch_bounds__(TPB / PPL) void sdf_tiles_pk(const SpanRec *__restrict__ tiles, uint32_t n_tiles,
                                                           const double *__restrict__ seg_sx,
                                                           const double *__restrict__ seg_sy,
                                                           const double *__restrict__ seg_ex,
@@ -361,8 +359,8 @@ __global__ __launch_bounds__(TPB / PPL) void sdf_tiles_pk(const GlyphDesc *__res
 
 	const uint32_t tid = threadIdx.x;
 	const uint32_t tile = xcd_remap(blockIdx.x, n_tiles);
-	const uint2 t = tiles[tile];
-	const GlyphDesc g = glyphs[t.x];
+	const SpanRec g = tiles[tile]; // (the glyph's descriptor travels in the entry)
+	const uint2 t = make_uint2(g.glyph, g.first);
 	const uint32_t npix = g.w * g.h;
 	const double x0c = (double)g.x0 + 0.5, y0c = (double)g.y0 + 0.5;
 
@@ -709,8 +707,7 @@ __global__ __launch_bounds__(TPB / PPL) void sdf_tiles_pk(const GlyphDesc *__res
 // ones for M < 4096; D_g^2 has relative error < 2^-21).  For M >= 4096 every group is a candidate.
 // ---------------------------------------------------------------------------------------
 template <int ABL, bool LAZY>
-__global__ __launch_bounds__(TPB) void sdf_tiles_hier(const GlyphDesc *__restrict__ glyphs,
-                                                      const uint2 *__restrict__ tiles, uint32_t n_tiles,
+__global__ __launch_bounds__(TPB) void sdf_tiles_hier(const SpanRec *__restrict__ tiles, uint32_t n_tiles,
                                                       const double *__restrict__ seg_sx,
                                                       const double *__restrict__ seg_sy,
                                                       const double *__restrict__ seg_ex,
@@ -727,8 +724,8 @@ __global__ __launch_bounds__(TPB) void sdf_tiles_hier(const GlyphDesc *__restric
 
 	const uint32_t tid = threadIdx.x;
 	const uint32_t tile = xcd_remap(blockIdx.x, n_tiles);
-	const uint2 t = tiles[tile];
-	const GlyphDesc g = glyphs[t.x];
+	const SpanRec g = tiles[tile]; // (the glyph's descriptor travels in the entry)
+	const uint2 t = make_uint2(g.glyph, g.first);
 	const uint32_t npix = g.w * g.h;
 	const double x0c = (double)g.x0 + 0.5, y0c = (double)g.y0 + 0.5;
 	const uint32_t o = t.y + tid;

@@ -102,7 +102,7 @@ struct vgsdf_dbatch {
 	size_t arena_bytes = 0, input_bytes = 0;
 	void *h_stage = nullptr; // pinned staging of the input part
 	vgsdf::GlyphDesc *d_glyphs = nullptr;
-	uint2 *d_tiles = nullptr;
+	vgsdf::SpanRec *d_tiles = nullptr;
 	void *d_boxes = nullptr; // chunk boxes (span kernel); NULL: none
 	double *d_sx = nullptr, *d_sy = nullptr, *d_ex = nullptr, *d_ey = nullptr;
 	uint32_t seg_stride = 1; // 1: four SoA arrays (C ABI batches); 4: 32-byte records (device front-end)
@@ -111,7 +111,7 @@ struct vgsdf_dbatch {
 	// work list = [main kernel | brute force]
 	uint32_t n_main = 0; // entries [0, n_main): main kernel; the rest: brute-force tiles
 	int tile_order = 1;
-	bool span_list = false; // main-class entries are (glyph, first pixel | tile count): sdf_tiles_span only
+	bool span_list = false; // main-class entries say first pixel | tile count: sdf_tiles_span only
 	bool borrowed = false; // arena + staging belong to the context (vgsdf_render_batch)
 };
 
@@ -120,7 +120,7 @@ struct vgsdf_dbatch {
 // them otherwise): earlier generations and timing-only ablations, see vgsdf_launch_tiles; 60..84 only in `make margins`
 // builds: the margin instances of the span kernel (sdf_margin_kernels.hip).
 inline int kernel_id(int variant) { return variant == 0 ? 50 : (variant == 13 ? 10 : variant); }
-// the variant's main-class entries are spans: (glyph, first pixel | tile count)
+// the variant's main-class entries are spans: first pixel | tile count
 inline bool uses_span_list(int variant) { return variant == 0 || (variant >= 50 && variant <= 99); }
 
 constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -133,7 +133,7 @@ struct BatchArena {
 	{
 		const size_t A = 256;
 		tiles = align_up(sizeof(vgsdf::GlyphDesc) * (size_t)n_glyphs, A);
-		sx = align_up(tiles + sizeof(uint2) * (size_t)n_tiles, A);
+		sx = align_up(tiles + sizeof(vgsdf::SpanRec) * (size_t)n_tiles, A);
 		const size_t seg_bytes = align_up(sizeof(double) * (size_t)n_seg, A);
 		sy = sx + seg_bytes, ex = sx + 2 * seg_bytes, ey = sx + 3 * seg_bytes;
 		input_bytes = out = sx + 4 * seg_bytes;
@@ -158,7 +158,7 @@ VGSDF_INTERNAL void *pinned_device_ptr(void *p, size_t bytes);
 
 // Fills the glyph descriptors and the tile list (routing + order) of a batch, and b->n_main, b->stats.n_tiles,
 // b->span_list, b->tile_order.  `ht` must hold one entry per 256-pixel tile of the batch.  (work_list.cpp)
-VGSDF_INTERNAL void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, uint2 *ht, vgsdf_dbatch *b, bool span);
+VGSDF_INTERNAL void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, vgsdf::SpanRec *ht, vgsdf_dbatch *b, bool span);
 
 // Rule U over a resident batch (outline_union.cpp): a NEW batch with src's glyphs, rects and out_off whose segments are the
 // boundary of the filled sets, with descriptors, work list and chunk boxes over them; complete on the device when the call

@@ -138,7 +138,7 @@ int fe_launch_plan(vgsdf_ctx *ctx, FrontEnd &fe, uint32_t spans_launched)
 	const FePending &p = fe.pend;
 	const FeDev d = fe_dev(fe);
 	return vgsdf_outline_plan(d.rects, p.n, p.span ? 1 : 0, (uint32_t)vgsdf_filtered_delta_cap(), p.span_max, p.span_budget,
-	                          (uint32_t)std::min<size_t>(fe.tile_cap, 0x7FFFFFFFu), d.descs, (uint2 *)fe.tiles.p, d.hdr,
+	                          (uint32_t)std::min<size_t>(fe.tile_cap, 0x7FFFFFFFu), d.descs, (vgsdf::SpanRec *)fe.tiles.p, d.hdr,
 	                          fe.flag_word(), (unsigned long long)fe.seg_cap, (unsigned long long)p.spec_cap,
 	                          spans_launched, p.d_pbf_pre, p.d_pbf_fix,
 	                          p.d_pbf_fix ? (unsigned long long *)((uint8_t *)fe.rects_hdr.p + p.at_off) : nullptr, fe.next_flag_word(), ctx->stream);
@@ -175,9 +175,9 @@ hipError_t fe_ensure_tiles(FrontEnd &fe, size_t want)
 {
 	if (want <= fe.tile_cap)
 		return hipSuccess;
-	hipError_t e = fe.tiles.ensure(sizeof(uint2) * want);
+	hipError_t e = fe.tiles.ensure(sizeof(vgsdf::SpanRec) * want);
 	if (e == hipSuccess)
-		fe.tile_cap = fe.tiles.cap / sizeof(uint2);
+		fe.tile_cap = fe.tiles.cap / sizeof(vgsdf::SpanRec);
 	return e;
 }
 hipError_t fe_ensure_segs(FrontEnd &fe, size_t want, uint32_t n_glyphs)
@@ -703,7 +703,7 @@ static int fe_enqueue(vgsdf_ctx *ctx, FrontEnd &fe, const FeInput *in, const FeU
 	}
 	FE_KERNEL(fe_launch_emit(ctx, fe));
 	if (p.spec)
-		FE_KERNEL(vgsdf_launch_span_planned(d.descs, (const uint2 *)fe.tiles.p, p.launch_spans, (const double *)fe.seg.p,
+		FE_KERNEL(vgsdf_launch_span_planned((const vgsdf::SpanRec *)fe.tiles.p, p.launch_spans, (const double *)fe.seg.p,
 		                                    (const double *)fe.seg.p + 1, (const double *)fe.seg.p + 2, (const double *)fe.seg.p + 3, 4,
 		                                    p.d_spec, fe.boxes.p, d.hdr, st));
 	if (!early_copy) {
@@ -939,7 +939,7 @@ static int fe_wait(vgsdf_ctx *ctx, vgsdf_rect *rects_out, uint64_t *out_bytes, u
 	if (!(done && p.spec_direct))
 		FE_TRY(fe.out.ensure(std::max((size_t)fe.out_bytes, done ? p.spec_cap : (size_t)0) + 16));
 	b.d_glyphs = d.descs;
-	b.d_tiles = (uint2 *)fe.tiles.p;
+	b.d_tiles = (vgsdf::SpanRec *)fe.tiles.p;
 	b.d_sx = (double *)fe.seg.p;
 	b.d_sy = (double *)fe.seg.p + 1;
 	b.d_ex = (double *)fe.seg.p + 2;

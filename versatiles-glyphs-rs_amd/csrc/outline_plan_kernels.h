@@ -2,12 +2,13 @@
 // entry bytes behind the plan.
 #pragma once
 #include "outline_kernels.h"
+#include "sdf_kernels.h" // SpanRec: the entries of the work list the plan writes
 
 extern "C" {
 // seg_cap / out_cap / launch_spans: what PlanHeader::ok is decided against (capacity of the segment records, of the
 // output buffer, grid of the raster launch enqueued behind the plan; launch_spans = 0: no such launch)
 int vgsdf_outline_plan(const vgsdf::OutlineRect *rects, uint32_t n_glyphs, int span_list, uint32_t delta_cap, uint32_t span_max,
-                       uint32_t span_budget, uint32_t tile_cap, vgsdf::GlyphDesc *descs, uint2 *tiles, vgsdf::PlanHeader *hdr,
+                       uint32_t span_budget, uint32_t tile_cap, vgsdf::GlyphDesc *descs, vgsdf::SpanRec *tiles, vgsdf::PlanHeader *hdr,
                        const uint32_t *error_flag, unsigned long long seg_cap, unsigned long long out_cap, uint32_t launch_spans,
                        const uint32_t *pbf_pre /* NULL: bitmaps packed back to back */, const uint8_t *pbf_fix,
                        unsigned long long *pbf_at /* [n_glyphs] positions of the bitmaps in the arena */,

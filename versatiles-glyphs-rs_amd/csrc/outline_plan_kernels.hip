@@ -99,7 +99,7 @@ template <uint32_t KEEP, bool PBF>
 __global__ __launch_bounds__(kPlanThreads) void outline_plan(const OutlineRect *__restrict__ rects, uint32_t n_glyphs, int span_list,
                                                              uint32_t delta_cap, uint32_t span_max, uint32_t span_budget,
                                                              uint32_t tile_cap, GlyphDesc *__restrict__ descs,
-                                                             uint2 *__restrict__ tiles, PlanHeader *__restrict__ hdr,
+                                                             SpanRec *__restrict__ tiles, PlanHeader *__restrict__ hdr,
                                                              const uint32_t *__restrict__ error_flag, unsigned long long seg_cap,
                                                              unsigned long long out_cap, uint32_t launch_spans,
                                                              const uint32_t *__restrict__ pbf_pre, const uint8_t *__restrict__ pbf_fix,
@@ -263,16 +263,18 @@ __global__ __launch_bounds__(kPlanThreads) void outline_plan(const OutlineRect *
 	// (every glyph's entries are in place when the kernel ends: a launch enqueued behind it may read the list)
 	if (tid == 0)
 		hdr->ok = s_carry[0] <= seg_cap && s_carry[1] <= out_cap && s_nall == s_nmain && s_nmain <= launch_spans;
-	// pass B: entries.  One per span of T tiles: (glyph, first pixel | T) in the span list's main class, else
-	// (glyph, first pixel).
+	// pass B: entries.  One per span of T tiles: the glyph's descriptor as pass A stored it (by this thread for a kept
+	// glyph, else by another one in front of the barriers above), the glyph, and first pixel | T in the span list's main
+	// class, else the first pixel.
 	auto entries = [&](uint32_t g, const OutlineRect &r, uint32_t cls, uint32_t T, uint32_t nspans, uint32_t weight) {
 		if (!nspans)
 			return;
 		uint32_t at = atomicAdd(&s_hist[cls][weight_bucket(weight)], nspans);
 		const unsigned long long px = (unsigned long long)r.w * r.h;
+		const GlyphDesc d = descs[g];
 		for (unsigned long long p = 0; p < px; p += 256ull * T) {
 			const uint32_t left = (uint32_t)((px - p + 255ull) >> 8);
-			tiles[at++] = make_uint2(g, span_list && cls == 0 ? ((uint32_t)p | min(T, left)) : (uint32_t)p);
+			tiles[at++] = span_rec(d, g, span_list && cls == 0 ? ((uint32_t)p | min(T, left)) : (uint32_t)p);
 		}
 	};
 	if (kept) {
@@ -364,7 +366,7 @@ __global__ __launch_bounds__(256) void pbf_entries(const OutlineRect *__restrict
 using namespace vgsdf;
 
 extern "C" int vgsdf_outline_plan(const OutlineRect *rects, uint32_t n_glyphs, int span_list, uint32_t delta_cap, uint32_t span_max,
-                                  uint32_t span_budget, uint32_t tile_cap, GlyphDesc *descs, uint2 *tiles, PlanHeader *hdr,
+                                  uint32_t span_budget, uint32_t tile_cap, GlyphDesc *descs, SpanRec *tiles, PlanHeader *hdr,
                                   const uint32_t *error_flag, unsigned long long seg_cap, unsigned long long out_cap,
                                   uint32_t launch_spans, const uint32_t *pbf_pre, const uint8_t *pbf_fix,
                                   unsigned long long *pbf_at, uint32_t *next_flag, hipStream_t stream)

@@ -107,7 +107,7 @@ int union_resident(vgsdf_ctx *ctx, const char *entry, const vgsdf_dbatch *src, v
 	}
 	uint8_t *const da = (uint8_t *)b->d_arena, *const hs = (uint8_t *)b->h_stage;
 	b->d_glyphs = (vgsdf::GlyphDesc *)(da + at.desc);
-	b->d_tiles = (uint2 *)(da + at.tiles);
+	b->d_tiles = (vgsdf::SpanRec *)(da + at.tiles);
 	b->d_sx = (double *)(da + at.sx), b->d_sy = (double *)(da + at.sy), b->d_ex = (double *)(da + at.ex), b->d_ey = (double *)(da + at.ey);
 	b->seg_stride = 1;
 	b->d_out = own_output ? da + at.out : nullptr;
@@ -116,7 +116,7 @@ int union_resident(vgsdf_ctx *ctx, const char *entry, const vgsdf_dbatch *src, v
 		vgsdf_batch in{};
 		in.n_glyphs = n, in.seg_off = seg_off.data();
 		in.x0 = x0.data(), in.y0 = y0.data(), in.w = w.data(), in.h = h.data(), in.out_off = out_off.data();
-		build_descs_and_tiles(&in, (vgsdf::GlyphDesc *)(hs + at.desc), (uint2 *)(hs + at.tiles), b, uses_span_list(ctx->variant));
+		build_descs_and_tiles(&in, (vgsdf::GlyphDesc *)(hs + at.desc), (vgsdf::SpanRec *)(hs + at.tiles), b, uses_span_list(ctx->variant));
 		q.copy(b->d_arena, b->h_stage, stage_bytes);
 		q.copy(d_off, seg_off.data(), 4 * ((size_t)n + 1));
 		q.record(ev.at[1]);

@@ -22,6 +22,33 @@ static_assert(sizeof(GlyphDesc) == 32, "GlyphDesc must stay 32 bytes");
 // monotone seg_off, so no offset table is needed; the table has (total segments >> 8) + n_glyphs + 1 entries.
 __device__ __forceinline__ uint32_t chunk_box_index(uint32_t seg_off, uint32_t glyph, uint32_t c) { return (seg_off >> 8) + glyph + c; }
 
+// One entry of the raster's work list, written by both planners (work_list.cpp on the host, outline_plan on the device): the
+// glyph's descriptor, copied, beside what the entry itself says.  A workgroup of sdf_tiles_span or sdf_tiles_brute reads its
+// entry with one group of scalar loads and nothing behind it: the descriptor used to be a second, dependent load through the
+// glyph index.  GlyphDesc[] stays for the passes that walk glyphs (chunk boxes, PBF entries, the union pass).
+// 40 bytes: the descriptor's 32 are full at their documented ranges (32-bit offsets and rects, a 64-bit output offset), so the
+// entry's own two words follow it; the loads of both parts are issued together and waited for once.
+struct SpanRec {
+	uint32_t seg_off; // = GlyphDesc of `glyph`
+	uint32_t n_seg;
+	int32_t x0, y0;
+	uint32_t w, h;
+	uint64_t out_off;
+	uint32_t first; // main class of a span list: first pixel | T (T = 1..4 tiles of 256 pixels); else the first pixel
+	uint32_t glyph; // index of the glyph (chunk_box_index)
+};
+static_assert(sizeof(SpanRec) == 40, "SpanRec: a GlyphDesc and two words");
+
+__host__ __device__ __forceinline__ SpanRec span_rec(const GlyphDesc &d, uint32_t glyph, uint32_t first)
+{
+	SpanRec r;
+	r.seg_off = d.seg_off, r.n_seg = d.n_seg;
+	r.x0 = d.x0, r.y0 = d.y0, r.w = d.w, r.h = d.h;
+	r.out_off = d.out_off;
+	r.first = first, r.glyph = glyph;
+	return r;
+}
+
 } // namespace vgsdf
 
 // largest rows*(w+1) a tile of the filtered kernel may need (winding histogram in LDS)
@@ -33,15 +60,14 @@ extern "C" int vgsdf_kernel_known(int kernel);
 
 // Segment layout: seg_stride 1 = four SoA arrays as the C ABI hands them (vgsdf_batch); 4 = records {sx, sy, ex, ey} of
 // 32 bytes with sx / sy / ex / ey pointing at the four fields of record 0 (what the device front-end writes).
-// tiles[i] = (glyph index, first output byte of the tile inside that glyph's bitmap)
+// tiles[i] = a SpanRec: the glyph's descriptor, its index, and the first output byte of the tile inside that glyph's bitmap
 // list_order != 0: workgroups take tiles in list order; 0: per-XCD contiguous remap
-extern "C" int vgsdf_launch_tiles(int variant, int list_order, const vgsdf::GlyphDesc *glyphs,
-                                  const uint2 *tiles, uint32_t n_tiles, const double *sx,
+extern "C" int vgsdf_launch_tiles(int variant, int list_order, const vgsdf::SpanRec *tiles, uint32_t n_tiles, const double *sx,
                                   const double *sy, const double *ex, const double *ey, uint32_t seg_stride,
                                   uint8_t *out, const void *boxes, hipStream_t stream);
 
 // the span kernel over a device-planned work list that may still be in the making when the launch is enqueued (see .hip)
-extern "C" int vgsdf_launch_span_planned(const vgsdf::GlyphDesc *glyphs, const uint2 *tiles, uint32_t grid, const double *sx,
+extern "C" int vgsdf_launch_span_planned(const vgsdf::SpanRec *tiles, uint32_t grid, const double *sx,
                                          const double *sy, const double *ex, const double *ey, uint32_t seg_stride, uint8_t *out,
                                          const void *boxes, const void *plan, hipStream_t stream);
 

@@ -31,8 +31,7 @@ constexpr int SEG_CHUNK = 512; // segments per LDS stage: 7 * 512 * 8 B = 28 KiB
 // ---------------------------------------------------------------------------------------
 // Variant 1: brute force.  Every pixel evaluates every segment.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TPB) void sdf_tiles_brute(const GlyphDesc *__restrict__ glyphs,
-                                                       const uint2 *__restrict__ tiles,
+__global__ __launch_bounds__(TPB) void sdf_tiles_brute(const SpanRec *__restrict__ tiles,
                                                        uint32_t n_tiles,
                                                        const double *__restrict__ seg_sx,
                                                        const double *__restrict__ seg_sy,
@@ -44,10 +43,9 @@ __global__ __launch_bounds__(TPB) void sdf_tiles_brute(const GlyphDesc *__restri
 	__shared__ double s_dx[SEG_CHUNK], s_dy[SEG_CHUNK], s_l2[SEG_CHUNK];
 
 	const uint32_t tile = xcd_remap(blockIdx.x, n_tiles);
-	const uint2 t = tiles[tile];
-	const GlyphDesc g = glyphs[t.x];
+	const SpanRec g = tiles[tile]; // (the glyph's descriptor travels in the entry)
 	const uint32_t npix = g.w * g.h;
-	const uint32_t o = t.y + threadIdx.x; // index into the glyph's output bitmap
+	const uint32_t o = g.first + threadIdx.x; // index into the glyph's output bitmap
 	const bool active = o < npix;
 	const uint32_t oc = active ? o : npix - 1;
 	const uint32_t row = oc / g.w;       // output row (top row first)
@@ -215,13 +213,13 @@ extern "C" int vgsdf_launch_chunk_boxes(const vgsdf::GlyphDesc *glyphs, uint32_t
 
 // The span kernel over a work list that outline_plan is still writing when this is enqueued: `grid` workgroups
 // (a guess >= plan->n_main, else plan->ok is 0 and nothing runs), list order.
-extern "C" int vgsdf_launch_span_planned(const vgsdf::GlyphDesc *glyphs, const uint2 *tiles, uint32_t grid, const double *sx,
+extern "C" int vgsdf_launch_span_planned(const vgsdf::SpanRec *tiles, uint32_t grid, const double *sx,
                                          const double *sy, const double *ex, const double *ey, uint32_t seg_stride, uint8_t *out,
                                          const void *boxes, const void *plan, hipStream_t stream)
 {
 	if (grid == 0)
 		return 0;
-	hipLaunchKernelGGL(vgsdf::sdf_tiles_span, dim3(grid), dim3(vgsdf::TPB), 0, stream, glyphs, tiles, grid | 0x80000000u, sx, sy,
+	hipLaunchKernelGGL(vgsdf::sdf_tiles_span, dim3(grid), dim3(vgsdf::TPB), 0, stream, tiles, grid | 0x80000000u, sx, sy,
 	                   ex, ey, seg_stride, out, (const float4 *)boxes, (const vgsdf::PlanHeader *)plan);
 	return (int)hipGetLastError();
 }
@@ -232,7 +230,7 @@ extern "C" int vgsdf_launch_span_planned(const vgsdf::GlyphDesc *glyphs, const u
 #ifdef VGSDF_MARGIN_VARIANTS
 // `make margins` only: the margin instances of the span kernel (sdf_margin_kernels.hip), ids 60..84
 extern "C" int vgsdf_margin_known(int kernel);
-extern "C" int vgsdf_margin_launch(int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::GlyphDesc *glyphs, const uint2 *tiles,
+extern "C" int vgsdf_margin_launch(int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::SpanRec *tiles,
                                    const double *sx, const double *sy, const double *ex, const double *ey, uint32_t seg_stride,
                                    uint8_t *out, const void *boxes, hipStream_t stream);
 #endif
@@ -252,8 +250,7 @@ extern "C" int vgsdf_kernel_known(int kernel)
 	return kernel == 1 || kernel == 50;
 }
 
-extern "C" int vgsdf_launch_tiles(int variant, int list_order, const vgsdf::GlyphDesc *glyphs,
-                                  const uint2 *tiles, uint32_t n_tiles_in, const double *sx,
+extern "C" int vgsdf_launch_tiles(int variant, int list_order, const vgsdf::SpanRec *tiles, uint32_t n_tiles_in, const double *sx,
                                   const double *sy, const double *ex, const double *ey, uint32_t seg_stride,
                                   uint8_t *out, const void *boxes, hipStream_t stream)
 {
@@ -263,32 +260,32 @@ extern "C" int vgsdf_launch_tiles(int variant, int list_order, const vgsdf::Glyp
 	// kernel argument: tile count, top bit set = dispatch in list order (no per-XCD remap)
 	const uint32_t n_tiles = n_tiles_in | (list_order ? 0x80000000u : 0u);
 	if (variant == 1)
-		hipLaunchKernelGGL(vgsdf::sdf_tiles_brute, grid, dim3(vgsdf::TPB), 0, stream, glyphs,
-		                   tiles, n_tiles, sx, sy, ex, ey, seg_stride, out);
+		hipLaunchKernelGGL(vgsdf::sdf_tiles_brute, grid, dim3(vgsdf::TPB), 0, stream, tiles, n_tiles, sx,
+		                   sy, ex, ey, seg_stride, out);
 	else if (variant == 50) // bounded groups over spans of up to 4 tiles (tile list: first pixel | T)
-		hipLaunchKernelGGL(vgsdf::sdf_tiles_span, grid, dim3(vgsdf::TPB), 0, stream, glyphs, tiles, n_tiles, sx, sy, ex, ey,
+		hipLaunchKernelGGL(vgsdf::sdf_tiles_span, grid, dim3(vgsdf::TPB), 0, stream, tiles, n_tiles, sx, sy, ex, ey,
 		                   seg_stride, out, (const float4 *)boxes, (const vgsdf::PlanHeader *)nullptr);
 #ifdef VGSDF_MARGIN_VARIANTS
 	else if (vgsdf_margin_known(variant))
-		return vgsdf_margin_launch(variant, n_tiles_in, n_tiles, glyphs, tiles, sx, sy, ex, ey, seg_stride, out, boxes, stream);
+		return vgsdf_margin_launch(variant, n_tiles_in, n_tiles, tiles, sx, sy, ex, ey, seg_stride, out, boxes, stream);
 #endif
 #ifdef VGSDF_DEV_VARIANTS
 	// development builds only (`make dev`): the stamped instance of the span kernel and the earlier generations
 	else if (seg_stride != 1 && variant != 58) // the earlier generations read SoA arrays only
 		return (int)hipErrorInvalidValue;
 #define VG_LAUNCH_PK(A, C, P)                                                                            \
-	hipLaunchKernelGGL((vgsdf::sdf_tiles_pk<A, C, P>), grid, dim3(vgsdf::TPB / P), 0, stream, glyphs, tiles,  \
+	hipLaunchKernelGGL((vgsdf::sdf_tiles_pk<A, C, P>), grid, dim3(vgsdf::TPB / P), 0, stream, tiles,  \
 	                   n_tiles, sx, sy, ex, ey, out)
 #define VG_LAUNCH_HIER(A, L)                                                                               \
-	hipLaunchKernelGGL((vgsdf::sdf_tiles_hier<A, L>), grid, dim3(vgsdf::TPB), 0, stream, glyphs, tiles, n_tiles,   \
+	hipLaunchKernelGGL((vgsdf::sdf_tiles_hier<A, L>), grid, dim3(vgsdf::TPB), 0, stream, tiles, n_tiles,   \
 	                   sx, sy, ex, ey, out)
 #define VG_LAUNCH_FILTERED(A, C)                                                                          \
-	hipLaunchKernelGGL((vgsdf::sdf_tiles_filtered<A, C>), grid, dim3(vgsdf::TPB), 0, stream, glyphs, \
+	hipLaunchKernelGGL((vgsdf::sdf_tiles_filtered<A, C>), grid, dim3(vgsdf::TPB), 0, stream, \
 	                   tiles, n_tiles, sx, sy, ex, ey, out)
 	else if (variant == 58) { // diagnostic: s_memtime stamps per phase; prints the shares of wave time on stderr
 		unsigned long long h[28] = {0};
 		(void)hipMemcpyToSymbolAsync(HIP_SYMBOL(vgsdf::g_span_dbg), h, sizeof(h), 0, hipMemcpyHostToDevice, stream);
-		hipLaunchKernelGGL(vgsdf::sdf_tiles_span_stamped, grid, dim3(vgsdf::TPB), 0, stream, glyphs, tiles, n_tiles, sx, sy, ex,
+		hipLaunchKernelGGL(vgsdf::sdf_tiles_span_stamped, grid, dim3(vgsdf::TPB), 0, stream, tiles, n_tiles, sx, sy, ex,
 		                   ey, seg_stride, out, (const float4 *)boxes, (const vgsdf::PlanHeader *)nullptr);
 		(void)hipStreamSynchronize(stream);
 		(void)hipMemcpyFromSymbol(h, HIP_SYMBOL(vgsdf::g_span_dbg), sizeof(h), 0, hipMemcpyDeviceToHost);

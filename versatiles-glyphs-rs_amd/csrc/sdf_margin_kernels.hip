@@ -25,7 +25,7 @@
 
 namespace vgsdf {
 
-typedef void (*span_fn)(const GlyphDesc *, const uint2 *, uint32_t, const double *, const double *, const double *, const double *,
+typedef void (*span_fn)(const SpanRec *, uint32_t, const double *, const double *, const double *, const double *,
                         uint32_t, uint8_t *, const float4 *, const PlanHeader *);
 struct MarginInstance {
 	int id;
@@ -160,12 +160,12 @@ static const MarginInstance k_instances[] = {{84, sdf_margin_span_row_e0}};
 
 // this part's instances: 0 launched (or the HIP error), -1 not one of mine
 extern "C" __attribute__((visibility("hidden"))) int VG_CAT(vgsdf_margin_launch_p, VG_MARGIN_PART)(
-    int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::GlyphDesc *glyphs, const uint2 *tiles, const double *sx, const double *sy,
+    int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::SpanRec *tiles, const double *sx, const double *sy,
     const double *ex, const double *ey, uint32_t seg_stride, uint8_t *out, const void *boxes, hipStream_t stream)
 {
 	for (const vgsdf::MarginInstance &m : vgsdf::k_instances)
 		if (m.id == kernel) {
-			hipLaunchKernelGGL(m.fn, dim3(grid), dim3(vgsdf::TPB), 0, stream, glyphs, tiles, n_tiles_arg, sx, sy, ex, ey, seg_stride, out,
+			hipLaunchKernelGGL(m.fn, dim3(grid), dim3(vgsdf::TPB), 0, stream, tiles, n_tiles_arg, sx, sy, ex, ey, seg_stride, out,
 			                   (const float4 *)boxes, (const vgsdf::PlanHeader *)nullptr);
 			return (int)hipGetLastError();
 		}
@@ -174,7 +174,7 @@ extern "C" __attribute__((visibility("hidden"))) int VG_CAT(vgsdf_margin_launch_
 
 #if VG_MARGIN_PART == 0
 #define VG_MARGIN_PART_ARGS                                                                                                          \
-	int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::GlyphDesc *glyphs, const uint2 *tiles, const double *sx, const double *sy, \
+	int kernel, uint32_t grid, uint32_t n_tiles_arg, const vgsdf::SpanRec *tiles, const double *sx, const double *sy, \
 	    const double *ex, const double *ey, uint32_t seg_stride, uint8_t *out, const void *boxes, hipStream_t stream
 extern "C" int vgsdf_margin_launch_p1(VG_MARGIN_PART_ARGS);
 extern "C" int vgsdf_margin_launch_p2(VG_MARGIN_PART_ARGS);
@@ -192,7 +192,7 @@ extern "C" int vgsdf_margin_launch(VG_MARGIN_PART_ARGS)
 	                                                            vgsdf_margin_launch_p3, vgsdf_margin_launch_p4, vgsdf_margin_launch_p5,
 	                                                            vgsdf_margin_launch_p6};
 	for (auto part : parts) {
-		const int e = part(kernel, grid, n_tiles_arg, glyphs, tiles, sx, sy, ex, ey, seg_stride, out, boxes, stream);
+		const int e = part(kernel, grid, n_tiles_arg, tiles, sx, sy, ex, ey, seg_stride, out, boxes, stream);
 		if (e != -1)
 			return e;
 	}

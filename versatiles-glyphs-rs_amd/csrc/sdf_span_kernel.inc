@@ -9,8 +9,8 @@
 // one after the other, so a glyph of <= 1024 pixels (99.7 % of Noto Sans) reads its segments from HBM/L2 once and
 // pays the staging arithmetic once.  Per-pixel state between chunks (upper bound of the squared distance, the two
 // candidate bytes) lives in LDS.
-//   tiles[i] = (glyph, first pixel | T): T in 1..4 tiles, chosen by the list builder so that the rows the span
-//   touches fit the winding histogram.
+//   tiles[i] = SpanRec (sdf_kernels.h): the glyph's descriptor, its index, and first pixel | T: T in 1..4 tiles, chosen by
+//   the list builder so that the rows the span touches fit the winding histogram.
 // Because quantisation is monotone in the distance, the minimum over chunks can be taken on the BYTES: outside the
 // nearest segment gives the largest byte, inside the smallest; both are kept until the winding number (complete
 // only after the last chunk) picks one.  DESIGN.md §4.1 holds the exactness argument.
@@ -102,8 +102,7 @@
 #define VG_M_ROW_E(e) (e) // stage: distance of an f32 end point from a row centre below which the f64 brackets decide
 #endif
 
-__global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__restrict__ glyphs,
-                                                          const uint2 *__restrict__ tiles, uint32_t n_tiles,
+__global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const SpanRec *__restrict__ tiles, uint32_t n_tiles,
                                                           const double *__restrict__ seg_sx,
                                                           const double *__restrict__ seg_sy,
                                                           const double *__restrict__ seg_ex,
@@ -111,10 +110,6 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
                                                           uint8_t *__restrict__ out, const float4 *__restrict__ boxes,
                                                           const PlanHeader *__restrict__ plan)
 {
-	// Behind the device front-end the launch is enqueued before the host has seen the plan: the grid is a guess
-	// (>= the work list, or the plan says "not ok": some capacity was too small and the host launches again)
-	if (plan != nullptr && (!plan->ok || blockIdx.x >= plan->n_main))
-		return;
 #ifdef VG_SPAN_STAMPED
 	unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
 #endif
@@ -125,6 +120,24 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	unsigned long long cn_row_fb = 0;                               // stage: waves of a chunk whose f64 brackets ran
 #endif
 	VG_STAMP(-1);
+	// A workgroup's way to its first segment is two round trips of scalar loads and one of vector loads: the kernel
+	// arguments; the work-list entry (which carries the glyph's descriptor) together with the plan's verdict; the segments
+	// of chunk 0 behind the first barrier.  Every argument is named here, so that none is fetched later behind a wait of
+	// its own.
+	asm volatile("" ::"s"(seg_sx), "s"(seg_sy), "s"(seg_ex), "s"(seg_ey), "s"(seg_stride), "s"(out), "s"(boxes));
+	const uint32_t tile = xcd_remap(blockIdx.x, n_tiles);
+	// Behind the device front-end the launch is enqueued before the host has seen the plan: the grid is a guess
+	// (>= the work list, or the plan says "not ok": some capacity was too small and the host launches again).  The entry
+	// is read beside the verdict, not behind it: the grid never exceeds the list's capacity, and nothing of an entry is
+	// used before the check below.  The empty statement is where both loads must have arrived: one wait for the two.
+	const plan_ptr verdict = plan != nullptr ? (plan_ptr)plan : (plan_ptr)&k_plan_absent;
+	uint32_t plan_ok = verdict->ok, plan_n_main = verdict->n_main;
+	SpanRec g = tiles[tile];
+	asm volatile(""
+	             : "+s"(plan_ok), "+s"(plan_n_main), "+s"(g.seg_off), "+s"(g.n_seg), "+s"(g.x0), "+s"(g.y0), "+s"(g.w), "+s"(g.h), "+s"(g.out_off),
+	               "+s"(g.first), "+s"(g.glyph));
+	if (!plan_ok || blockIdx.x >= plan_n_main)
+		return;
 	constexpr uint32_t GRP = 8, NGRP = FCHUNK / GRP; // 32 groups per chunk: one mask bit each
 	static_assert(NGRP == 32 && TPB == FCHUNK, "one candidate bit per group, one staging thread per record");
 	// (arrays of one kind are rows of ONE array: the compiler keeps a thread's address into each LDS array in a VGPR for
@@ -154,11 +167,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 	// workgroup (tools/model_wave_shares.py).  Whatever is indexed by tid (the stage's records, st_ub2, st_byte) stays put.
 	const uint32_t rot = wave_rot(blockIdx.x);
 	const uint32_t pw = ((wv + rot) & 3u) * 64u;
-	const uint32_t tile = xcd_remap(blockIdx.x, n_tiles);
-	const uint2 t = tiles[tile];
-	const GlyphDesc g = glyphs[t.x];
 	const uint32_t npix = g.w * g.h;
-	const uint32_t p0 = t.y & ~255u, T = min(max(t.y & 255u, 1u), SPAN_TILES);
+	const uint32_t p0 = g.first & ~255u, T = min(max(g.first & 255u, 1u), SPAN_TILES);
 	const uint32_t p_end = min(p0 + T * (uint32_t)TPB, npix); // pixels [p0, p_end) of the glyph's bitmap
 
 	const uint32_t r_first = p0 / g.w, r_last = (p_end - 1) / g.w;
@@ -210,7 +220,7 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			// not the minimum, or the byte is saturated whatever the minimum is.  f32 roundings (box, pixel
 			// centres) are covered by padk.  (Tightening R with the pixels' running upper bounds was
 			// measured: the bookkeeping costs more than the extra skips on real fonts.) ----
-			const float4 bb = boxes[chunk_box_index(g.seg_off, t.x, c0 / FCHUNK)];
+			const float4 bb = boxes[chunk_box_index(g.seg_off, g.glyph, c0 / FCHUNK)];
 			const float mag = fmaxf(fmaxf(fabsf(bb.x), fabsf(bb.y)), fmaxf(fmaxf(fabsf(bb.z), fabsf(bb.w)), wh));
 			const float padk = VG_M_BOX_PADK(mag);
 			const float ry0 = (float)y_lo + 0.5f, ry1 = (float)y_hi + 0.5f; // sample rows of the span, relative to y0
@@ -241,6 +251,8 @@ __global__ __launch_bounds__(TPB, 4) void VG_SPAN_KERNEL(const GlyphDesc *__rest
 			bool row_exact = false; // the f32 record does not fix the brackets: first_ge does, below
 			if (i < cnt) {
 				const size_t s = (size_t)(g.seg_off + c0 + i) * seg_stride; // stride 1: SoA arrays; 4: {sx, sy, ex, ey} records
+				// (issued here, behind the chunk-top barrier.  Chunk 0's loads issued at the top of the kernel, under the rest of the
+				// prologue, were built and measured: slower; a later chunk's above the barrier spill: profiles/span_startup_ab.txt)
 				const double vx = seg_sx[s], vy = seg_sy[s], wx = seg_ex[s], wy = seg_ey[s];
 				e_vx[i] = vx;
 				e_vy[i] = vy;

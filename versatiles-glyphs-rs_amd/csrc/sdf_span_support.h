@@ -15,6 +15,13 @@ namespace vgsdf {
 
 constexpr int TPB = VGSDF_TILE_PIXELS; // 256 threads, one pixel each
 
+// What the span kernel reads in place of a plan when it is launched without one (a resident batch: the host planned it):
+// "ok", and every workgroup of the grid inside the list.  One scalar load for both cases, issued beside the load of the
+// work-list entry (constant address space: the load stays scalar behind the choice between the two addresses; a plan is
+// complete before the launch behind it starts).
+typedef const __attribute__((address_space(4))) PlanHeader *plan_ptr;
+static __constant__ const PlanHeader k_plan_absent = {0ull, 0ull, 0u, 0xFFFFFFFFu, 0u, 1u};
+
 // Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Remap so that
 // each XCD walks a contiguous range of tiles: tiles of one glyph (which re-read the same
 // segment list) then hit the same L2.  Pure performance hint; any placement is correct.

@@ -296,7 +296,7 @@ static int upload_impl(vgsdf_ctx *ctx, const vgsdf_batch *in, vgsdf_dbatch **out
 	}
 	uint8_t *hs = (uint8_t *)b->h_stage, *da = (uint8_t *)b->d_arena;
 	b->d_glyphs = (vgsdf::GlyphDesc *)(da + off_desc);
-	b->d_tiles = (uint2 *)(da + off_tiles);
+	b->d_tiles = (vgsdf::SpanRec *)(da + off_tiles);
 	b->d_sx = (double *)(da + off_sx);
 	b->d_sy = (double *)(da + off_sy);
 	b->d_ex = (double *)(da + off_ex);
@@ -306,7 +306,7 @@ static int upload_impl(vgsdf_ctx *ctx, const vgsdf_batch *in, vgsdf_dbatch **out
 
 	if (n) {
 		vgsdf::GlyphDesc *hd = (vgsdf::GlyphDesc *)(hs + off_desc);
-		uint2 *ht = (uint2 *)(hs + off_tiles);
+		vgsdf::SpanRec *ht = (vgsdf::SpanRec *)(hs + off_tiles);
 		build_descs_and_tiles(in, hd, ht, b, uses_span_list(ctx->variant));
 		if (n_seg && !direct) {
 			std::memcpy(hs + off_sx, in->seg_sx, sizeof(double) * n_seg);
@@ -380,10 +380,10 @@ int vgsdf_batch_launch(vgsdf_ctx *ctx, vgsdf_dbatch *b)
 		return VGSDF_E_ARG;
 	}
 	const int list_order = b->tile_order == 1;
-	int e = vgsdf_launch_tiles(k_main, list_order, b->d_glyphs, b->d_tiles, n_main, b->d_sx, b->d_sy, b->d_ex, b->d_ey,
+	int e = vgsdf_launch_tiles(k_main, list_order, b->d_tiles, n_main, b->d_sx, b->d_sy, b->d_ex, b->d_ey,
 	                           b->seg_stride, b->d_out, b->span_list ? b->d_boxes : nullptr, ctx->stream);
 	if (e == 0)
-		e = vgsdf_launch_tiles(1, list_order, b->d_glyphs, b->d_tiles + n_main, n_all - n_main, b->d_sx, b->d_sy, b->d_ex,
+		e = vgsdf_launch_tiles(1, list_order, b->d_tiles + n_main, n_all - n_main, b->d_sx, b->d_sy, b->d_ex,
 		                       b->d_ey, b->seg_stride, b->d_out, nullptr, ctx->stream);
 	if (e != 0) {
 		ctx->err = std::string("vgsdf_batch_launch: ") + hipGetErrorString((hipError_t)e);

@@ -7,7 +7,7 @@
 #include "device_internal.h"
 #include "work_plan.h"
 
-void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, uint2 *ht, vgsdf_dbatch *b, bool span)
+void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, vgsdf::SpanRec *ht, vgsdf_dbatch *b, bool span)
 {
 	static_assert(VGSDF_TILE_PIXELS == 256, "work_plan.h counts in tiles of 256 pixels");
 	const uint32_t n = in->n_glyphs;
@@ -15,6 +15,16 @@ void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, uint2 *h
 	uint32_t span_max, span_budget;
 	vgsdf::span_policy_from_env(n, span_max, span_budget);
 	b->span_list = span;
+	// the descriptors first: every entry of the work list carries a copy of its glyph's
+	for (uint32_t g = 0; g < n; g++) {
+		hd[g].seg_off = in->seg_off[g];
+		hd[g].n_seg = in->seg_off[g + 1] - in->seg_off[g];
+		hd[g].x0 = in->x0[g];
+		hd[g].y0 = in->y0[g];
+		hd[g].w = in->w[g];
+		hd[g].h = in->h[g];
+		hd[g].out_off = in->out_off[g];
+	}
 	const char *ord = std::getenv("VGSDF_TILE_ORDER");
 	b->tile_order = ord ? std::atoi(ord) : 1;
 
@@ -65,7 +75,8 @@ void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, uint2 *h
 		}
 		const double ts1 = trace_l ? fe_now() : 0;
 		tl_sort += ts1 - ts0;
-		// entries of glyph g: one per span of T tiles (T = 1 unless this is the span list's main class)
+		// entries of glyph g: one per span of T tiles (T = 1 unless this is the span list's main class), as (glyph, first pixel | T);
+		// the list takes them as SpanRec, with the glyph's descriptor
 		auto emit = [&](uint32_t g, auto &&push) {
 			const uint64_t px = (uint64_t)in->w[g] * in->h[g];
 			const uint32_t T = span_t[g];
@@ -105,28 +116,19 @@ void build_descs_and_tiles(const vgsdf_batch *in, vgsdf::GlyphDesc *hd, uint2 *h
 						for (size_t m = 0; m < 8; m++) // dry: borrow from the fullest queue
 							if (qlen[m] - taken[m] > qlen[src] - taken[src])
 								src = m;
-					ht[ti++] = qbuf[src][taken[src]++];
+					const uint2 e = qbuf[src][taken[src]++];
+					ht[ti++] = vgsdf::span_rec(hd[e.x], e.x, e.y);
 				}
 		} else {
 			for (uint64_t k : gl)
-				emit((uint32_t)k, [&](uint2 e) { ht[ti++] = e; });
+				emit((uint32_t)k, [&](uint2 e) { ht[ti++] = vgsdf::span_rec(hd[e.x], e.x, e.y); });
 		}
 		if (cls == 0)
 			b->n_main = (uint32_t)ti;
 		tl_deal += (trace_l ? fe_now() : 0) - ts1;
 	}
-	const double tl1 = trace_l ? fe_now() : 0;
 	b->stats.n_tiles = ti; // workgroups actually launched (<= the 256-pixel tile count the list was sized for)
-	for (uint32_t g = 0; g < n; g++) {
-		hd[g].seg_off = in->seg_off[g];
-		hd[g].n_seg = in->seg_off[g + 1] - in->seg_off[g];
-		hd[g].x0 = in->x0[g];
-		hd[g].y0 = in->y0[g];
-		hd[g].w = in->w[g];
-		hd[g].h = in->h[g];
-		hd[g].out_off = in->out_off[g];
-	}
 	if (trace_l)
-		std::fprintf(stderr, "[vgsdf] list: sort %.3f ms, deal+emit %.3f ms, descs %.3f ms (total after pass 1: %.3f)\n", tl_sort * 1e3,
-		             tl_deal * 1e3, (fe_now() - tl1) * 1e3, (fe_now() - tl0) * 1e3);
+		std::fprintf(stderr, "[vgsdf] list: sort %.3f ms, deal+emit %.3f ms (total after pass 1: %.3f)\n", tl_sort * 1e3, tl_deal * 1e3,
+		             (fe_now() - tl0) * 1e3);
 }
